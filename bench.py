@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the nd.la hot path on MI355X (BASELINE.json).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Step = one 4096x4096x4096 fp64 matmul (BASELINE configs[1]) through the C ABI on device-resident
@@ -30,7 +30,35 @@ def parse():
     p.add_argument("--n", type=int, default=4096, help="matrix size (default = BASELINE configs[1])")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-ops", action="store_true", help="skip the QR/LU/SVD side measurements")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="after the timed steps, write rank 0's product C of the last step to DIR/*.npy (see dump_outputs)")
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_MAX_ENTRIES = 1 << 22          # 32 MB of float64, under the 64 MB bound of --dump-outputs
+
+
+def dump_outputs(d, C):
+    """--dump-outputs: C = A B of the last timed step, float64, as DIR/C.npy when it has at most DUMP_MAX_ENTRIES entries, else
+    DIR/C_sample.npy: the entries at DUMP_MAX_ENTRIES flat indices drawn without replacement by numpy's default_rng(0), ascending.
+    The inputs are fixed by their seeds, so two builds run with the same arguments can be compared file for file. A directory
+    created here gets a .gitignore of its own."""
+    import numpy as np
+    import torch
+    flat = C.reshape(-1)
+    if flat.numel() <= DUMP_MAX_ENTRIES:
+        name, vals = "C", C.cpu().numpy()
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(flat.numel(), DUMP_MAX_ENTRIES, replace=False))
+        name, vals = "C_sample", flat[torch.from_numpy(idx).to(C.device)].cpu().numpy()
+    if not os.path.isdir(d):
+        os.makedirs(d)
+        with open(os.path.join(d, ".gitignore"), "w") as f:
+            f.write("*\n")
+    np.save(os.path.join(d, name + ".npy"), vals)
 
 
 # The true reference (nd4js dist/nd.js under Node 12) timed in the survey container (BASELINE.md §2: 8-vCPU Xeon 2.1 GHz, 1 thread):
@@ -206,6 +234,8 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = tt.item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, C)
     flops = 2.0 * n ** 3
     value = world * flops * args.steps / elapsed / 1e9
 

@@ -1,5 +1,6 @@
 """The production host: JS wrapper (nd4js_amd/js/index.js) over the N-API addon. Skipped where node
 or its headers are missing (the addon is only built when /usr/include/node exists)."""
+import json
 import os
 import shutil
 import subprocess
@@ -35,10 +36,21 @@ def test_js_wrapper_validation_and_loud_failure():
         assert cut == la.chain_plan(cases[name]["shapes"]), name
 
 
+def _reference_bundle():
+    """the reference's dist/nd.js: ND4_REFERENCE (as for oracle/gen_golden.js), else under BASELINE.json's reference_path"""
+    if os.environ.get("ND4_REFERENCE"):
+        return os.environ["ND4_REFERENCE"]
+    with open(os.path.join(ROOT, "BASELINE.json")) as f:
+        return os.path.join(json.load(f)["reference_path"], "dist", "nd.js")
+
+
+REF_BUNDLE = _reference_bundle()
+
+
 @needs_node
-@pytest.mark.skipif(not os.path.exists("/root/reference/dist/nd.js"), reason="reference bundle only exists in the build container")
+@pytest.mark.skipif(not os.path.exists(REF_BUNDLE), reason="the reference bundle (ND4_REFERENCE, or dist/nd.js under BASELINE.json's reference_path) is not here")
 def test_install_patches_reference_module():
-    assert "node install checks ok" in run("install", "/root/reference/dist/nd.js")
+    assert "node install checks ok" in run("install", REF_BUNDLE)
 
 
 @needs_node
