@@ -208,6 +208,43 @@ int nd4hip_dgeqrf_full_batched    (nd4hip_handle* h, int64_t batch, int64_t M, i
 int nd4hip_dgeqrf_qty_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t L, double* A, double* Y);
 int nd4hip_dgeqrf_qty_batched    (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t L, double* A, double* Y);
 
+/* ---- rrqr_decomp / rrqr_decomp_full: replace src/la/rrqr.js:278-395 / :88-184 (column-pivoted QR) -----------------------
+ * A [batch,M,N] -> P [batch,N] int32 with A[:, P] = Q R. dgeqp3: Q [batch,M,L], R [batch,L,N], L = min(M,N) (the economic form of
+ * rrqr_decomp; for M <= N it is the full form). dgeqp3_full: Q [batch,M,M], R [batch,M,N]. The pivot is chosen as the reference does
+ * (rrqr.js:124-138): before step i every remaining column's norm below row i is recomputed from scratch (no downdating), the first
+ * maximum wins (an earlier column on a tie, a NaN never), and the pass stops when that maximum is exactly zero, leaving the
+ * remaining columns in their order. Q and R are those of dgeqrf_q / dgeqrf_full on A[:, P] (as the reference's are those of
+ * its qr_decomp of A[:, P]), with their sign conventions and, for M > N in the full form, the same orthonormal completion.
+ * Two limits of those conventions show on structured input: for M > N the c >= 0 rule is read off the leading minors of Q's
+ * top block, which vanish for a permuted diagonal or zero-row matrix, and a column whose part below the diagonal is exactly
+ * zero can still get R_jj >= 0 where the reference keeps the entry's sign. There single columns of Q (rows of R) differ
+ * from the reference's in sign. Deterministic: no atomics; a second call gives
+ * the same bits. Non-finite input returns normally with unspecified factors. */
+int nd4hip_dgeqp3_batched_dev     (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* Q, double* R, int32_t* P);
+int nd4hip_dgeqp3_batched         (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* Q, double* R, int32_t* P);
+int nd4hip_dgeqp3_full_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* Q, double* R, int32_t* P);
+int nd4hip_dgeqp3_full_batched    (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* Q, double* R, int32_t* P);
+
+/* ---- rrqr_rank: replaces src/la/rrqr.js:398-414 (_rrqr_rank :57-85) -----------------------------------------------------
+ * rank [batch] int32 of R [batch,M,N]: tmp[i] = ||R[i:L, j >= row]|| (the upper-triangle entries of rows i.. L-1), T = 2 eps
+ * max(M,N) tmp[0], rank = the number of leading tmp[i] > T. A non-finite tmp[i] gives rank -1 in the _dev form; the host form
+ * returns ND4HIP_ERR_ARG with 'Infinity or NaN encountered during rank estimation.' */
+int nd4hip_dqp3rank_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* R, int32_t* rank);
+int nd4hip_dqp3rank_batched    (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* R, int32_t* rank);
+
+/* ---- rrqr_lstsq: replaces src/la/rrqr.js:447-580 -------------------------------------------------------------------------
+ * X [batch,I,J] with z[0:r] = R[0:r,0:r]^-1 (Q^T Y)[0:r], z[r:] = 0, X[P[i],:] = z[i,:], r = the rank of R as dqp3rank (each
+ * matrix's own, computed on the device); Q [batch,N,M], R [batch,M,I], P [batch,I], Y [batch,N,J]; strides in elements, 0 =
+ * broadcast. rank [batch] receives r (-1: non-finite) and may be NULL. The _dev form makes no device-to-host copy; the host form
+ * refuses a P that is not a permutation ('rrqr_lstsq(Q,R,P,y): Invalid indices in P.') and a non-finite rank estimate (the
+ * rrqr_rank message), both ND4HIP_ERR_ARG. rrqr_solve (:417-444) is this plus the host's check rank == N. */
+int nd4hip_dqp3ls_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, int64_t M, int64_t I, int64_t J,
+                              const double* Q, int64_t strideQ, const double* R, int64_t strideR, const int32_t* P, int64_t strideP,
+                              const double* Y, int64_t strideY, double* X, int32_t* rank);
+int nd4hip_dqp3ls_batched    (nd4hip_handle* h, int64_t batch, int64_t N, int64_t M, int64_t I, int64_t J,
+                              const double* Q, int64_t strideQ, const double* R, int64_t strideR, const int32_t* P, int64_t strideP,
+                              const double* Y, int64_t strideY, double* X, int32_t* rank);
+
 /* ---- svd_decomp: replaces the output contract of src/la/svd.js:25 (= svd_dc.js:883-932) ----------
  * A [batch,M,N] -> U [batch,M,L], sv [batch,L] (>= 0, descending), V [batch,L,N] (rows = right
  * singular vectors), L = min(M,N); one-sided Jacobi with the reference's Jacobi post-processing

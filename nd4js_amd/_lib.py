@@ -67,6 +67,16 @@ SIGNATURES = {
     "nd4hip_dgeqrf_full_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
     "nd4hip_dgeqrf_qty_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp]),
     "nd4hip_dgeqrf_qty_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp]),
+    "nd4hip_dgeqp3_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, ctypes.c_void_p]),
+    "nd4hip_dgeqp3_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, ctypes.c_void_p]),
+    "nd4hip_dgeqp3_full_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, ctypes.c_void_p]),
+    "nd4hip_dgeqp3_full_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, ctypes.c_void_p]),
+    "nd4hip_dqp3rank_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, ctypes.c_void_p]),
+    "nd4hip_dqp3rank_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, ctypes.c_void_p]),
+    "nd4hip_dqp3ls_batched_dev": (c_int, [ctypes.c_void_p] + [c_i64] * 5 + [c_dp, c_i64, c_dp, c_i64, ctypes.c_void_p, c_i64, c_dp, c_i64,
+                                                                             c_dp, ctypes.c_void_p]),
+    "nd4hip_dqp3ls_batched": (c_int, [ctypes.c_void_p] + [c_i64] * 5 + [c_dp, c_i64, c_dp, c_i64, ctypes.c_void_p, c_i64, c_dp, c_i64,
+                                                                         c_dp, ctypes.c_void_p]),
     "nd4hip_dgesvdj_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp,
                                            ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_double)]),
     "nd4hip_dgesvdj_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp,

@@ -53,6 +53,11 @@ static int (*p_dgeqrf_qty[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t
 static gesvdj_fn p_dgesvdj[2];
 static int (*p_svd_info)(nd4hip_handle*, int*, unsigned long long*, double*);
 static qrls_fn p_dqrls[2];
+static int (*p_dgeqp3[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, double*, double*, int32_t*);
+static int (*p_dgeqp3_full[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, double*, double*, int32_t*);
+static int (*p_dqp3rank[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, int32_t*);
+static int (*p_dqp3ls[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t,
+                          const int32_t*, int64_t, const double*, int64_t, double*, int32_t*);
 static svdls_fn p_dsvdls[2];
 static getrs_fn p_dgetrs[2];
 static int (*p_dpotrf[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*);
@@ -113,6 +118,10 @@ static int load_library(void) {
   SYM2(p_dldltrf, "nd4hip_dldltrf_batched");
   SYM2(p_dldltrs, "nd4hip_dldltrs_batched");
   SYM2(p_dqrls, "nd4hip_dqrls_batched");
+  SYM2(p_dgeqp3, "nd4hip_dgeqp3_batched");
+  SYM2(p_dgeqp3_full, "nd4hip_dgeqp3_full_batched");
+  SYM2(p_dqp3rank, "nd4hip_dqp3rank_batched");
+  SYM2(p_dqp3ls, "nd4hip_dqp3ls_batched");
   SYM2(p_dsvdls, "nd4hip_dsvdls_batched");
   SYM2(p_dtrsm, "nd4hip_dtrsm_batched");
 #undef SYM2
@@ -411,6 +420,50 @@ static napi_value js_dqrls(napi_env env, napi_callback_info info) {
   FAIL_IF(p_dqrls[X.dev](g_handle, batch, N, M, I, J, (const double*)Q.p, sQ, (const double*)R.p, sR, (const double*)Y.p, sY, (double*)X.p));
   return NULL;
 }
+/* dgeqp3_batched / dgeqp3_full_batched(batch, M, N, A, Q, R, P)   (rrqr_decomp, rrqr.js:278-395 / rrqr_decomp_full :88-184) */
+static napi_value geqp3_common(napi_env env, napi_callback_info info, int full) {
+  size_t argc = 7; napi_value a[7]; napi_get_cb_info(env, info, &argc, a, NULL, NULL);
+  NEED(argc == 7, "dgeqp3_batched: 7 arguments expected");
+  int64_t batch, M, N; opnd A, Q, R, P;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &M) || get_i64(env, a[2], &N) || F64(3, A) || F64(4, Q) || F64(5, R) || I32(6, P)) return NULL;
+  const int64_t L = M < N ? M : N, qc = full ? M : L, rr = full ? M : L;
+  NEED(batch >= 0 && M >= 0 && N >= 0 && (size_t)(batch * M * N) <= A.len && (size_t)(batch * M * qc) <= Q.len &&
+       (size_t)(batch * rr * N) <= R.len && (size_t)(batch * N) <= P.len, "dgeqp3_batched: buffer too small");
+  SAME_SIDE(A.dev == Q.dev && Q.dev == R.dev && R.dev == P.dev, "dgeqp3_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF((full ? p_dgeqp3_full : p_dgeqp3)[A.dev](g_handle, batch, M, N, (const double*)A.p, (double*)Q.p, (double*)R.p, (int32_t*)P.p));
+  return NULL;
+}
+static napi_value js_dgeqp3(napi_env env, napi_callback_info info) { return geqp3_common(env, info, 0); }
+static napi_value js_dgeqp3_full(napi_env env, napi_callback_info info) { return geqp3_common(env, info, 1); }
+/* dqp3rank_batched(batch, M, N, R, rank)   (rrqr_rank, rrqr.js:398-414; host form throws the reference's message) */
+static napi_value js_dqp3rank(napi_env env, napi_callback_info info) {
+  ARGS(5, "dqp3rank_batched");
+  int64_t batch, M, N; opnd R, r;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &M) || get_i64(env, a[2], &N) || F64(3, R) || I32(4, r)) return NULL;
+  NEED(batch >= 0 && M >= 0 && N >= 0 && (size_t)(batch * M * N) <= R.len && (size_t)batch <= r.len, "dqp3rank_batched: buffer too small");
+  SAME_SIDE(R.dev == r.dev, "dqp3rank_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dqp3rank[R.dev](g_handle, batch, M, N, (const double*)R.p, (int32_t*)r.p));
+  return NULL;
+}
+/* dqp3ls_batched(batch, N, M, I, J, Q, strideQ, R, strideR, P, strideP, Y, strideY, X, rank)   (rrqr_lstsq, rrqr.js:447-580) */
+static napi_value js_dqp3ls(napi_env env, napi_callback_info info) {
+  ARGS(15, "dqp3ls_batched");
+  int64_t batch, N, M, I, J, sQ, sR, sP, sY; opnd Q, R, P, Y, X, r;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || get_i64(env, a[2], &M) || get_i64(env, a[3], &I) || get_i64(env, a[4], &J) ||
+      F64(5, Q) || get_i64(env, a[6], &sQ) || F64(7, R) || get_i64(env, a[8], &sR) || I32(9, P) || get_i64(env, a[10], &sP) ||
+      F64(11, Y) || get_i64(env, a[12], &sY) || F64(13, X) || I32(14, r)) return NULL;
+  NEED(batch >= 0 && N >= 0 && M >= 0 && I >= 0 && J >= 0 && sQ >= 0 && sR >= 0 && sP >= 0 && sY >= 0, "dqp3ls_batched: negative extent");
+  NEED(batch == 0 || ((size_t)((batch - 1) * sQ + N * M) <= Q.len && (size_t)((batch - 1) * sR + M * I) <= R.len &&
+                      (size_t)((batch - 1) * sP + I) <= P.len && (size_t)((batch - 1) * sY + N * J) <= Y.len &&
+                      (size_t)(batch * I * J) <= X.len && (size_t)batch <= r.len), "dqp3ls_batched: buffer too small");
+  SAME_SIDE(Q.dev == R.dev && R.dev == P.dev && P.dev == Y.dev && Y.dev == X.dev && X.dev == r.dev, "dqp3ls_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dqp3ls[X.dev](g_handle, batch, N, M, I, J, (const double*)Q.p, sQ, (const double*)R.p, sR, (const int32_t*)P.p, sP,
+                          (const double*)Y.p, sY, (double*)X.p, (int32_t*)r.p));
+  return NULL;
+}
 /* dsvdls_batched(batch, N, M, I, J, U, strideU, sv, strideSv, V, strideV, Y, strideY, X)   (svd_lstsq, svd.js:100-228) */
 static napi_value js_dsvdls(napi_env env, napi_callback_info info) {
   ARGS(14, "dsvdls_batched");
@@ -599,6 +652,10 @@ static napi_value init(napi_env env, napi_value exports) {
     {"dgetrs_batched", NULL, js_dgetrs, NULL, NULL, NULL, napi_default, NULL},
     {"dqrls_batched", NULL, js_dqrls, NULL, NULL, NULL, napi_default, NULL},
     {"dsvdls_batched", NULL, js_dsvdls, NULL, NULL, NULL, napi_default, NULL},
+    {"dgeqp3_batched", NULL, js_dgeqp3, NULL, NULL, NULL, napi_default, NULL},
+    {"dgeqp3_full_batched", NULL, js_dgeqp3_full, NULL, NULL, NULL, napi_default, NULL},
+    {"dqp3rank_batched", NULL, js_dqp3rank, NULL, NULL, NULL, napi_default, NULL},
+    {"dqp3ls_batched", NULL, js_dqp3ls, NULL, NULL, NULL, napi_default, NULL},
     {"dtrsm_batched", NULL, js_dtrsm, NULL, NULL, NULL, napi_default, NULL},
     {"dpotrf_batched", NULL, js_dpotrf, NULL, NULL, NULL, napi_default, NULL},
     {"dpotrs_batched", NULL, js_dpotrs, NULL, NULL, NULL, napi_default, NULL},

@@ -22,6 +22,13 @@ inline double nd4_flops_svd(int64_t M, int64_t N) {         // Golub-Reinsch cou
   return 4.0 * m * m * n + 8.0 * m * n * n + 9.0 * n * n * n;
 }
 
+// column-pivoted QR: the pivot pass touches every trailing element once per step (dot 2 + update 2 + norm 2 flops), then the QR
+// with explicit Q of the permuted matrix
+inline double nd4_flops_qp3(int64_t M, int64_t N) {
+  const double m = (double)M, n = (double)N, k = (double)(M < N ? M : N);
+  return 6.0 * (k * m * n - (m + n) * k * (k - 1.0) / 2.0 + (k - 1.0) * k * (2.0 * k - 1.0) / 6.0) + nd4_flops_qr(M, N);
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------ matmul
@@ -274,6 +281,63 @@ extern "C" int nd4hip_dgeqrf_qty_batched_dev(nd4hip_handle* h, int64_t batch, in
     ND4_TRY(nd4_gemm(h, true, false, M, L, M, 1.0, Q, M, M * M, Y, L, M * L, 0.0, Yt, L, M * L, batch));
     ND4_HIP(hipMemcpyAsync(Y, Yt, D * (size_t)(batch * M * L), hipMemcpyDeviceToDevice, h->stream));
   }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------ column-pivoted QR
+// rrqr_decomp (rrqr.js:278-395): Q [M, L], R [L, N], P [N]; rrqr_decomp_full (:88-184): Q [M, M], R [M, N], P [N]
+static int geqp3_dev(nd4hip_handle* h, const char* name, bool full, int64_t batch, int64_t M, int64_t N, const double* A, double* Q,
+                     double* R, int32_t* P) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_%s: NULL handle", name);
+  Nd4DeviceGuard guard(h);
+  const int64_t L = M < N ? M : N, qc = full ? M : L, rr = full ? M : L;
+  Nd4Prof prof(h, name, (double)batch * nd4_flops_qp3(M, N), 8.0 * batch * (double)(M * N + M * qc + rr * N) + 4.0 * batch * (double)N);
+  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_%s: negative extent", name);
+  if (batch == 0 || M == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(A && Q && R && P, "nd4hip_%s: NULL pointer", name);
+  ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_geqp3(h, nb, M, N, A + b0 * M * N, Q + b0 * M * qc, R + b0 * rr * N, P + b0 * N, full));
+  return 0;
+}
+extern "C" int nd4hip_dgeqp3_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* Q, double* R, int32_t* P) {
+  return geqp3_dev(h, "dgeqp3_batched", false, batch, M, N, A, Q, R, P);
+}
+extern "C" int nd4hip_dgeqp3_full_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* Q, double* R, int32_t* P) {
+  return geqp3_dev(h, "dgeqp3_full_batched", true, batch, M, N, A, Q, R, P);
+}
+
+// rrqr_rank (rrqr.js:398-414): rank [batch] of R [M, N]; -1 marks a matrix whose partial norms are not finite
+extern "C" int nd4hip_dqp3rank_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* R, int32_t* rank) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dqp3rank_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  const int64_t L = M < N ? M : N;
+  Nd4Prof prof(h, "dqp3rank_batched", 3.0 * batch * (double)(L * N - L * (L - 1) / 2), 8.0 * batch * (double)(L * N - L * (L - 1) / 2) + 4.0 * batch);
+  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dqp3rank_batched: negative extent");
+  if (batch == 0) return 0;
+  ND4_CHECK_ARG(rank && (R || L == 0), "nd4hip_dqp3rank_batched: NULL pointer");
+  ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_qp3rank(h, nb, M, N, R + b0 * M * N, M * N, rank + b0));
+  return 0;
+}
+
+// rrqr_lstsq (rrqr.js:447-580): Q [N, M], R [M, I], P [I], Y [N, J] -> X [I, J]; rank [batch] (may be NULL) as dqp3rank
+extern "C" int nd4hip_dqp3ls_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, int64_t M, int64_t I, int64_t J,
+                                         const double* Q, int64_t strideQ, const double* R, int64_t strideR, const int32_t* P, int64_t strideP,
+                                         const double* Y, int64_t strideY, double* X, int32_t* rank) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dqp3ls_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  const int64_t L = M < I ? M : I;
+  Nd4Prof prof(h, "dqp3ls_batched", (double)batch * (2.0 * L * N * J + (double)L * L * J),
+               8.0 * (double)((strideQ ? batch : 1) * N * M + (strideR ? batch : 1) * M * I + (strideY ? batch : 1) * N * J + batch * I * J));
+  ND4_CHECK_ARG(batch >= 0 && N >= 0 && M >= 0 && I >= 0 && J >= 0, "nd4hip_dqp3ls_batched: negative extent");
+  ND4_CHECK_ARG((strideQ == 0 || strideQ >= N * M) && (strideR == 0 || strideR >= M * I) && (strideP == 0 || strideP >= I) &&
+                (strideY == 0 || strideY >= N * J), "nd4hip_dqp3ls_batched: a stride must be 0 or at least the size of one operand");
+  if (batch == 0) return 0;
+  if (I == 0 || J == 0) {
+    if (rank) ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_qp3rank(h, nb, M, I, R ? R + b0 * strideR : nullptr, strideR, rank + b0));
+    return 0;
+  }
+  ND4_CHECK_ARG(Q && R && P && Y && X, "nd4hip_dqp3ls_batched: NULL pointer");
+  ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_qp3ls(h, nb, N, M, I, J, Q + b0 * strideQ, strideQ, R + b0 * strideR, strideR, P + b0 * strideP, strideP,
+                                          Y + b0 * strideY, strideY, X + b0 * I * J, rank ? rank + b0 : nullptr));
   return 0;
 }
 

@@ -11,6 +11,7 @@
 //   * a single large matmul is pipelined over the ROWS of A and C (B is a broadcast operand).
 // Error path: a failing chunk stops the block, the block's streams are synchronised BEFORE its staging returns to the cache.
 #include "nd4hip_internal.h"
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -452,6 +453,88 @@ extern "C" int nd4hip_dgeqrf_qty_batched(nd4hip_handle* h, int64_t batch, int64_
     return nd4hip_dgeqrf_qty_batched_dev(hd, nb, M, N, L, P(d, 0), L > 0 ? P(d, 1) : nullptr);
   };
   return run_host(h, batch, ops, fn);
+}
+
+// ------------------------------------------------------------------------------------ column-pivoted QR
+extern "C" int nd4hip_dgeqp3_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* Q, double* R, int32_t* Pv) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dgeqp3_batched: NULL handle");
+  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dgeqp3_batched: negative extent");
+  if (batch == 0 || M == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(A && Q && R && Pv, "nd4hip_dgeqp3_batched: NULL pointer");
+  const int64_t L = M < N ? M : N;
+  std::vector<Operand> ops{in_op(A, M * N, M * N), out_op(Q, M * L), out_op(R, L * N), out_op(Pv, N, 4)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
+    return nd4hip_dgeqp3_batched_dev(hd, nb, M, N, P(d, 0), P(d, 1), P(d, 2), static_cast<int32_t*>(d[3]));
+  };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_dgeqp3_full_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* Q, double* R, int32_t* Pv) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dgeqp3_full_batched: NULL handle");
+  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dgeqp3_full_batched: negative extent");
+  if (batch == 0 || M == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(A && Q && R && Pv, "nd4hip_dgeqp3_full_batched: NULL pointer");
+  std::vector<Operand> ops{in_op(A, M * N, M * N), out_op(Q, M * M), out_op(R, M * N), out_op(Pv, N, 4)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
+    return nd4hip_dgeqp3_full_batched_dev(hd, nb, M, N, P(d, 0), P(d, 1), P(d, 2), static_cast<int32_t*>(d[3]));
+  };
+  return run_host(h, batch, ops, fn);
+}
+
+namespace {
+// _rrqr_rank throws on a non-finite partial norm (rrqr.js:78-79); the kernels mark such a matrix with rank -1
+int qp3_rank_verdict(const int32_t* rank, int64_t batch) {
+  for (int64_t b = 0; b < batch; b++)
+    ND4_CHECK_ARG(rank[b] >= 0, "Infinity or NaN encountered during rank estimation.");
+  return 0;
+}
+}  // namespace
+
+extern "C" int nd4hip_dqp3rank_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* R, int32_t* rank) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dqp3rank_batched: NULL handle");
+  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dqp3rank_batched: negative extent");
+  if (batch == 0) return 0;
+  ND4_CHECK_ARG(rank != nullptr, "nd4hip_dqp3rank_batched: NULL pointer");
+  if (M == 0 || N == 0) { memset(rank, 0, sizeof(int32_t) * (size_t)batch); return 0; }
+  ND4_CHECK_ARG(R != nullptr, "nd4hip_dqp3rank_batched: NULL pointer");
+  std::vector<Operand> ops{in_op(R, M * N, M * N), out_op(rank, 1, 4)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
+    return nd4hip_dqp3rank_batched_dev(hd, nb, M, N, P(d, 0), static_cast<int32_t*>(d[1]));
+  };
+  ND4_TRY(run_host(h, batch, ops, fn));
+  return qp3_rank_verdict(rank, batch);
+}
+
+extern "C" int nd4hip_dqp3ls_batched(nd4hip_handle* h, int64_t batch, int64_t N, int64_t M, int64_t I, int64_t J,
+                                     const double* Q, int64_t strideQ, const double* R, int64_t strideR, const int32_t* Pv, int64_t strideP,
+                                     const double* Y, int64_t strideY, double* X, int32_t* rank) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dqp3ls_batched: NULL handle");
+  ND4_CHECK_ARG(batch >= 0 && N >= 0 && M >= 0 && I >= 0 && J >= 0, "nd4hip_dqp3ls_batched: negative extent");
+  ND4_CHECK_ARG((strideQ == 0 || strideQ >= N * M) && (strideR == 0 || strideR >= M * I) && (strideP == 0 || strideP >= I) &&
+                (strideY == 0 || strideY >= N * J), "nd4hip_dqp3ls_batched: a stride must be 0 or at least the size of one operand");
+  if (batch == 0) return 0;
+  ND4_CHECK_ARG(Q && R && Pv && Y && (X || I * J == 0), "nd4hip_dqp3ls_batched: NULL pointer");
+  // the reference's un-permutation refuses indices that do not form a permutation (rrqr.js:560-563)
+  {
+    std::vector<char> seen((size_t)I);
+    for (int64_t b = 0; b < (strideP ? batch : 1); b++) {
+      std::fill(seen.begin(), seen.end(), 0);
+      for (int64_t i = 0; i < I; i++) {
+        const int32_t k = Pv[b * strideP + i];
+        ND4_CHECK_ARG(k >= 0 && k < I && !seen[(size_t)k], "rrqr_lstsq(Q,R,P,y): Invalid indices in P.");
+        seen[(size_t)k] = 1;
+      }
+    }
+  }
+  std::vector<int32_t> own;
+  if (!rank) { own.resize((size_t)batch); rank = own.data(); }
+  std::vector<Operand> ops{in_op(Q, N * M, strideQ), in_op(R, M * I, strideR), in_op(Pv, I, strideP, 4), in_op(Y, N * J, strideY),
+                           out_op(X, I * J), out_op(rank, 1, 4)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
+    return nd4hip_dqp3ls_batched_dev(hd, nb, N, M, I, J, P(d, 0), strideQ, P(d, 1), strideR, static_cast<const int32_t*>(d[2]), strideP,
+                                     P(d, 3), strideY, P(d, 4), static_cast<int32_t*>(d[5]));
+  };
+  ND4_TRY(run_host(h, batch, ops, fn));
+  return qp3_rank_verdict(rank, batch);
 }
 
 // ------------------------------------------------------------------------------------ SVD

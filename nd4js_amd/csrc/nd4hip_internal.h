@@ -118,6 +118,11 @@ int nd4_givens_signs(nd4hip_handle* h, int batch, int M, int L, int ncols, bool 
                      double* R, long ldr, long sR, const double* taus, long sTau, int* flips);
 int nd4_wy_form(nd4hip_handle* h, int M, int n, const double* V, const double* Tdiag, int bs, double* Q, int Lq);
 int nd4_geqrf_q_ex(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* Q, double* R, bool full);
+// column-pivoted QR, its rank estimate and least squares (rrqr.hip)
+int nd4_geqp3(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* Q, double* R, int32_t* P, bool full);
+int nd4_qp3rank(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* R, int64_t sR, int* rank);
+int nd4_qp3ls(nd4hip_handle* h, int64_t batch, int64_t N, int64_t M, int64_t I, int64_t J, const double* Q, int64_t sQ,
+              const double* R, int64_t sR, const int32_t* P, int64_t sP, const double* Y, int64_t sY, double* X, int* rank_out);
 int nd4_gesvdj(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A,
                double* U, double* sv, double* V, int* sweeps_out, double* offnorm_out);
 

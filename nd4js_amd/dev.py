@@ -301,3 +301,65 @@ def bidiag_decomp(A):
     h = _h(A)
     _lib.check(h.lib.nd4hip_dgebrd_batched_dev(h.ptr, _batch(lead), M, N, _p(A), _p(U), _p(B), _p(V)))
     return U, B, V
+
+
+def _rrqr(A, full):
+    _chk(A, "A")
+    if A.dim() < 2:
+        raise ValueError("A must be at least 2D.")
+    M, N = A.shape[-2:]
+    L = M if full else min(M, N)
+    lead = tuple(A.shape[:-2])
+    Q = torch.empty(lead + (M, L), dtype=torch.float64, device=A.device)
+    R = torch.empty(lead + (L, N), dtype=torch.float64, device=A.device)
+    P = torch.empty(lead + (N,), dtype=torch.int32, device=A.device)
+    h = _h(A)
+    fn = h.lib.nd4hip_dgeqp3_full_batched_dev if full else h.lib.nd4hip_dgeqp3_batched_dev
+    _lib.check(fn(h.ptr, _batch(lead), M, N, _p(A), _p(Q), _p(R), _p(P)))
+    return Q, R, P
+
+
+def rrqr_decomp(A):
+    """device-resident rrqr_decomp (rrqr.js:278-395): Q [..., M, L], R [..., L, N], P [..., N] int32"""
+    return _rrqr(A, False)
+
+
+def rrqr_decomp_full(A):
+    """device-resident rrqr_decomp_full (rrqr.js:88-184)"""
+    return _rrqr(A, True)
+
+
+def rrqr_rank(R):
+    """device-resident rrqr_rank (rrqr.js:398-414): int32 tensor; -1 where the reference would throw (no host read-back here)"""
+    _chk(R, "R")
+    M, N = R.shape[-2:]
+    r = torch.empty(tuple(R.shape[:-2]), dtype=torch.int32, device=R.device)
+    h = _h(R)
+    _lib.check(h.lib.nd4hip_dqp3rank_batched_dev(h.ptr, _batch(R.shape[:-2]), M, N, _p(R), _p(r)))
+    return r
+
+
+def rrqr_lstsq(Q, R, P, Y, rank=None):
+    """device-resident rrqr_lstsq (rrqr.js:447-580): Q [..., N, M], R [..., M, I], P [..., I] int32, Y [..., N, J] with equal
+    leading dims; `rank` (optional int32 tensor of the batch shape) receives each matrix's rank (-1: non-finite). No host read-back."""
+    _chk(Q, "Q"), _chk(R, "R"), _chk(Y, "Y")
+    if not (isinstance(P, torch.Tensor) and P.is_cuda and P.dtype == torch.int32 and P.is_contiguous()):
+        raise ValueError('rrqr_lstsq(Q,R,P, y): P.dtype must be "int32".')
+    N, M = Q.shape[-2:]
+    I, J = R.shape[-1], Y.shape[-1]
+    if N != Y.shape[-2]:
+        raise ValueError("rrqr_lstsq(Q,R,P,y): Q and y don't match.")
+    if M != R.shape[-2]:
+        raise ValueError("rrqr_lstsq(Q,R,P,y): Q and R don't match.")
+    if I != P.shape[-1]:
+        raise ValueError("rrqr_lstsq(Q,R,P,y): R and P don't match.")
+    lead = tuple(Y.shape[:-2])
+    if tuple(Q.shape[:-2]) != lead or tuple(R.shape[:-2]) != lead or tuple(P.shape[:-1]) != lead:
+        raise ValueError("rrqr_lstsq(Q,R,P,y): Q,R,P,y not broadcast-compatible.")   # general broadcasting: host wrapper (la.py)
+    X = torch.empty(lead + (I, J), dtype=torch.float64, device=Y.device)
+    h = _h(Y)
+    b = _batch(lead)
+    _lib.check(h.lib.nd4hip_dqp3ls_batched_dev(h.ptr, b, N, M, I, J, _p(Q), N * M if b > 1 else 0, _p(R), M * I if b > 1 else 0,
+                                               _p(P), I if b > 1 else 0, _p(Y), N * J if b > 1 else 0, _p(X),
+                                               _p(rank) if rank is not None else None))
+    return X

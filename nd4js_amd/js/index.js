@@ -96,6 +96,11 @@ class DeviceNDArray {
   dispose() { this._buf.free(); }                // optional: dropped arrays are freed by the GC finalizer
 }
 const isDev = a => a instanceof DeviceNDArray;
+/* singular_matrix_solve_error.js: thrown by rrqr_solve / solve of a rank-deficient system, `.x` = the least-squares solution.
+ * Standalone this class is thrown; after install(nd) the host module's own nd.la.SingularMatrixSolveError is. */
+class SingularMatrixSolveError extends Error {
+  constructor(x, ...args) { super(...args); this.x = x; }
+}
 
 function makeAsarray(NDA) {
   return function asarray(a) {
@@ -190,7 +195,7 @@ function productShape(sA, sB, mismatch) {
   return [lead.concat([I, J]), I, K, J];
 }
 
-function makeLa(NDA, fallback) {
+function makeLa(NDA, fallback, SolveError) {
   const asarray = makeAsarray(NDA);
   const gpuOk = a => { const d = dtypeOf(a); return d === 'float64' || d === 'int32'; };
   const la = {};
@@ -552,10 +557,99 @@ function makeLa(NDA, fallback) {
     }
     return new NDA(Int32Array.from(sv.shape.subarray(0, sv.ndim - 1)), r);
   };
+
+  /* ---- column-pivoted QR (rrqr.js) and solve (solve.js:23-27), csrc/rrqr.hip ---- */
+  const rrqr = (name, full) => function (A) {
+    A = asarray(A);
+    if (A.ndim < 2) throw new Error('A must be at least 2D.');                     // rrqr.js:91 / :281
+    if (!gpuOk(A)) { if (fallback && fallback[name]) return fallback[name](A); throw new Error('nd4hip.' + name + ': dtype ' + dtypeOf(A) + ' is not accelerated.'); }
+    const nd_ = A.ndim, M = A.shape[nd_ - 2], N = A.shape[nd_ - 1], L = full ? M : Math.min(M, N), batch = prod(A.shape, 0, nd_ - 2);
+    const lead = Array.from(A.shape.subarray(0, nd_ - 2));
+    const dev = isDev(A), temps = [];
+    const Q = alloc(dev, batch * M * L), R = alloc(dev, batch * L * N), P = alloc(dev, batch * N, Int32Array);
+    native()[full ? 'dgeqp3_full_batched' : 'dgeqp3_batched'](batch, M, N, view(opF64(A, dev, temps), 0), view(Q, 0), view(R, 0), view(P, 0));
+    release(temps);
+    return [wrap(dev, [...lead, M, L], Q), wrap(dev, [...lead, L, N], R), wrap(dev, [...lead, N], P)];
+  };
+  la.rrqr_decomp = rrqr('rrqr_decomp', false);
+  la.rrqr_decomp_full = rrqr('rrqr_decomp_full', true);
+  const RANK_NAN = 'Infinity or NaN encountered during rank estimation.';
+  const hostInts = x => x instanceof DevBuf ? new DeviceNDArray(Int32Array.of(x.length), x).data : x;
+  la.rrqr_rank = function rrqr_rank(R) {                     // rrqr.js:398-414
+    R = asarray(R);
+    if (R.ndim < 2) throw new Error('rrqr_rank(R): R.ndim must be at least 2.');
+    if (!gpuOk(R)) { if (fallback && fallback.rrqr_rank) return fallback.rrqr_rank(R); throw new Error('nd4hip.rrqr_rank: dtype ' + dtypeOf(R) + ' is not accelerated.'); }
+    const nd_ = R.ndim, M = R.shape[nd_ - 2], N = R.shape[nd_ - 1], batch = prod(R.shape, 0, nd_ - 2);
+    const dev = isDev(R), temps = [], r = alloc(dev, batch, Int32Array);
+    native().dqp3rank_batched(batch, M, N, view(opF64(R, dev, temps), 0), view(r, 0));
+    release(temps);
+    if (dev && hostInts(r).some(k => k < 0)) throw new Error(RANK_NAN);             // the _dev form marks it with -1
+    return wrap(dev, Array.from(R.shape.subarray(0, nd_ - 2)), r);
+  };
+  const rrqrArgs = (Q, R, P, y) => {
+    if (y == undefined) {
+      if (P != undefined) throw new Error('rrqr_lstsq(Q,R,P, y): Either 2 ([Q,R,P], y) or 4 arguments (Q,R,P, y) expected.');
+      y = R; [Q, R, P] = Q;
+    }
+    return [Q, R, P, y];
+  };
+  // rrqr.js:447-580 -> [X, ranks (host Int32Array or device buffer)]; null when the dtypes are not accelerated
+  const rrqrLstsq = (Q, R, P, y) => {
+    Q = asarray(Q); if (Q.ndim < 2) throw new Error('rrqr_lstsq(Q,R,P, y): Q.ndim must be at least 2.');
+    R = asarray(R); if (R.ndim < 2) throw new Error('rrqr_lstsq(Q,R,P, y): R.ndim must be at least 2.');
+    P = asarray(P); if (P.ndim < 1) throw new Error('rrqr_lstsq(Q,R,P, y): P.ndim must be at least 1.');
+    y = asarray(y); if (y.ndim < 2) throw new Error('rrqr_lstsq(Q,R,P, y): y.ndim must be at least 2.');
+    if (dtypeOf(P) !== 'int32') throw new Error('rrqr_lstsq(Q,R,P, y): P.dtype must be "int32".');
+    const N = Q.shape[Q.ndim - 2], M = Q.shape[Q.ndim - 1], I = R.shape[R.ndim - 1], J = y.shape[y.ndim - 1];
+    if (N != y.shape[y.ndim - 2]) throw new Error("rrqr_lstsq(Q,R,P,y): Q and y don't match.");
+    if (M != R.shape[R.ndim - 2]) throw new Error("rrqr_lstsq(Q,R,P,y): Q and R don't match.");
+    if (I != P.shape[P.ndim - 1]) throw new Error("rrqr_lstsq(Q,R,P,y): R and P don't match.");
+    const lQ = Array.from(Q.shape.subarray(0, Q.ndim - 2)), lR = Array.from(R.shape.subarray(0, R.ndim - 2)),
+          lP = Array.from(P.shape.subarray(0, P.ndim - 1)), lY = Array.from(y.shape.subarray(0, y.ndim - 2));
+    const lead = bcastLead([lQ, lR, lY, lP], 'rrqr_lstsq(Q,R,P,y): Q,R,P,y not broadcast-compatible.');
+    if (!gpuOk(Q) || !gpuOk(R) || !gpuOk(y)) return null;
+    const total = lead.reduce((a, b) => a * b, 1);
+    const dev = isDev(Q) || isDev(R) || isDev(P) || isDev(y), temps = [];
+    const X = alloc(dev, total * I * J), ranks = alloc(dev, total, Int32Array);
+    const Qd = opF64(Q, dev, temps), Rd = opF64(R, dev, temps), Pd = opI32(P, dev, temps), yd = opF64(y, dev, temps);
+    try {
+      for (const [cnt, [oQ, oR, oP, oY], [sQ, sR, sP, sY], b0] of bcastGroupsN(lead, [lQ, lR, lP, lY], [N * M, M * I, I, N * J]))
+        native().dqp3ls_batched(cnt, N, M, I, J, view(Qd, oQ), sQ, view(Rd, oR), sR, view(Pd, oP), sP, view(yd, oY), sY,
+                                view(X, b0 * I * J), view(ranks, b0));
+    } finally { release(temps); }
+    if (dev && hostInts(ranks).some(k => k < 0)) throw new Error(RANK_NAN);
+    return [wrap(dev, [...lead, I, J], X), ranks];
+  };
+  la.rrqr_lstsq = function rrqr_lstsq(Q, R, P, y) {
+    [Q, R, P, y] = rrqrArgs(Q, R, P, y);
+    const out = rrqrLstsq(Q, R, P, y);
+    if (out) return out[0];
+    if (fallback && fallback.rrqr_lstsq) return fallback.rrqr_lstsq(Q, R, P, y);
+    throw new Error('nd4hip.rrqr_lstsq: dtype is not accelerated.');
+  };
+  la.rrqr_solve = function rrqr_solve(Q, R, P, y) {          // rrqr.js:417-444
+    [Q, R, P, y] = rrqrArgs(Q, R, P, y);
+    Q = asarray(Q); R = asarray(R);
+    const N = Q.shape[Q.ndim - 2];
+    if (N !== R.shape[R.ndim - 1]) throw new Error('rrqr_solve(Q,R,P, y): Q @ R not square.');
+    const out = rrqrLstsq(Q, R, P, y);
+    if (!out) {
+      if (fallback && fallback.rrqr_solve) return fallback.rrqr_solve(Q, R, P, y);
+      throw new Error('nd4hip.rrqr_solve: dtype is not accelerated.');
+    }
+    const [x, ranks] = out;
+    if (hostInts(ranks).some(k => k < N)) throw new SolveError(la.to_host(x));
+    return x;
+  };
+  la.solve = function solve(A, y) {                            // solve.js:23-27
+    const [Q, R, P] = la.rrqr_decomp(A);
+    return la.rrqr_solve(Q, R, P, y);
+  };
+  la.SingularMatrixSolveError = SolveError;
   return la;
 }
 
-const standalone = makeLa(NDArray, null);
+const standalone = makeLa(NDArray, null, SingularMatrixSolveError);
 
 // estimated work of a call (flops, SURVEY.md 8d conventions up to a constant): what install(nd, {minWork}) compares with
 function estimatedWork(name, args) {
@@ -581,8 +675,10 @@ function install(nd, opts) {
                     lu_solve: nd.la.lu_solve, tril_solve: nd.la.tril_solve, triu_solve: nd.la.triu_solve,
                     qr_lstsq: nd.la.qr_lstsq, svd_lstsq: nd.la.svd_lstsq, svd_solve: nd.la.svd_solve, svd_rank: nd.la.svd_rank,
                     cholesky_decomp: nd.la.cholesky_decomp, cholesky_solve: nd.la.cholesky_solve,
-                    ldl_decomp: nd.la.ldl_decomp, ldl_solve: nd.la.ldl_solve, hessenberg_decomp: nd.la.hessenberg_decomp, bidiag_decomp: nd.la.bidiag_decomp};
-  const acc = makeLa(nd.NDArray, original);
+                    ldl_decomp: nd.la.ldl_decomp, ldl_solve: nd.la.ldl_solve, hessenberg_decomp: nd.la.hessenberg_decomp, bidiag_decomp: nd.la.bidiag_decomp,
+                    rrqr_decomp: nd.la.rrqr_decomp, rrqr_decomp_full: nd.la.rrqr_decomp_full, rrqr_rank: nd.la.rrqr_rank,
+                    rrqr_lstsq: nd.la.rrqr_lstsq, rrqr_solve: nd.la.rrqr_solve, solve: nd.la.solve};
+  const acc = makeLa(nd.NDArray, original, nd.la.SingularMatrixSolveError || SingularMatrixSolveError);
   const target = Object.isFrozen(nd.la) || !Object.getOwnPropertyDescriptor(nd.la, 'matmul2').writable ? null : nd.la;
   const patched = target || Object.create(nd.la);
   const route = k => {
@@ -606,7 +702,7 @@ function install(nd, opts) {
 }
 
 module.exports = Object.assign(standalone, {
-  NDArray, DeviceNDArray, install, bcastGroups,
+  NDArray, DeviceNDArray, SingularMatrixSolveError, install, bcastGroups,
   accelerated: a => !!a && (isDev(a) || a.data instanceof Float64Array || a.data instanceof Int32Array),
   device_count: () => native().device_count(),
   devices: () => native().devices(),            // ids behind the handle (ND4HIP_DEVICES=all|0,1,...: batched host calls are sharded)

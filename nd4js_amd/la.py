@@ -541,3 +541,137 @@ def bidiag_decomp(A, device=None):
     h = _lib.handle(device)
     _lib.check(h.lib.nd4hip_dgebrd_batched(h.ptr, int(np.prod(lead, dtype=np.int64)), M, N, _ptr(A), _ptr(U), _ptr(B), _ptr(V)))
     return U, B, V
+
+
+# ---------------------------------------------------------------------------------------------------
+# Column-pivoted QR (src/la/rrqr.js) and the general solver built on it (src/la/solve.js), csrc/rrqr.hip
+# ---------------------------------------------------------------------------------------------------
+class SingularMatrixSolveError(ValueError):
+    """singular_matrix_solve_error.js: raised by rrqr_solve / solve when a matrix is rank-deficient; `.x` holds the
+    least-squares solution that was computed anyway."""
+
+    def __init__(self, x, *args):
+        super().__init__(*args)
+        self.x = x
+
+
+def _rrqr(A, full, name, device):
+    A = np.asarray(A)
+    if A.ndim < 2:
+        raise ValueError("A must be at least 2D.")                   # rrqr.js:91 / :281
+    A = _asarray(A, name)
+    M, N = A.shape[-2:]
+    L = M if full else min(M, N)
+    lead = A.shape[:-2]
+    Q, R = np.empty(lead + (M, L)), np.empty(lead + (L, N))
+    P = np.empty(lead + (N,), dtype=np.int32)
+    h = _lib.handle(device)
+    fn = h.lib.nd4hip_dgeqp3_full_batched if full else h.lib.nd4hip_dgeqp3_batched
+    _lib.check(fn(h.ptr, int(np.prod(lead, dtype=np.int64)), M, N, _ptr(A), _ptr(Q), _ptr(R), _ptr(P)))
+    return Q, R, P
+
+
+def rrqr_decomp(A, device=None):
+    """rrqr.js:278-395: (Q, R, P) with A[..., :, P] = Q R; Q [..., M, L], R [..., L, N], L = min(M, N)."""
+    return _rrqr(A, False, "rrqr_decomp(A)", device)
+
+
+def rrqr_decomp_full(A, device=None):
+    """rrqr.js:88-184: (Q [..., M, M], R [..., M, N], P [..., N])."""
+    return _rrqr(A, True, "rrqr_decomp_full(A)", device)
+
+
+def rrqr_rank(R, device=None):
+    """rrqr.js:398-414: int32 ranks of the leading matrices of R (threshold 2 eps max(M,N) ||R||_upper)."""
+    R = np.asarray(R)
+    if R.ndim < 2:
+        raise ValueError("rrqr_rank(R): R.ndim must be at least 2.")
+    R = _asarray(R, "rrqr_rank(R)")
+    M, N = R.shape[-2:]
+    r = np.empty(R.shape[:-2], dtype=np.int32)
+    h = _lib.handle(device)
+    try:
+        _lib.check(h.lib.nd4hip_dqp3rank_batched(h.ptr, int(np.prod(R.shape[:-2], dtype=np.int64)), M, N, _ptr(R), _ptr(r)))
+    except _lib.Nd4HipError as e:
+        if e.code == -1 and "Infinity or NaN" in str(e):
+            raise ValueError("Infinity or NaN encountered during rank estimation.")
+        raise
+    return r
+
+
+def _rrqr_args(Q, R, P, y):
+    if y is None:
+        if P is not None:
+            raise ValueError("rrqr_lstsq(Q,R,P, y): Either 2 ([Q,R,P], y) or 4 arguments (Q,R,P, y) expected.")
+        y = R
+        Q, R, P = Q
+    return Q, R, P, y
+
+
+def _rrqr_lstsq(Q, R, P, y, device):
+    """rrqr.js:447-580 -> (X, ranks of the broadcast members)"""
+    Q, R, P, y = np.asarray(Q), np.asarray(R), np.asarray(P), np.asarray(y)
+    if Q.ndim < 2:
+        raise ValueError("rrqr_lstsq(Q,R,P, y): Q.ndim must be at least 2.")
+    if R.ndim < 2:
+        raise ValueError("rrqr_lstsq(Q,R,P, y): R.ndim must be at least 2.")
+    if P.ndim < 1:
+        raise ValueError("rrqr_lstsq(Q,R,P, y): P.ndim must be at least 1.")
+    if y.ndim < 2:
+        raise ValueError("rrqr_lstsq(Q,R,P, y): y.ndim must be at least 2.")
+    if P.dtype != np.int32:
+        raise ValueError('rrqr_lstsq(Q,R,P, y): P.dtype must be "int32".')
+    Q, R, y = _asarray(Q, "rrqr_lstsq"), _asarray(R, "rrqr_lstsq"), _asarray(y, "rrqr_lstsq")
+    P = np.ascontiguousarray(P)
+    N, M = Q.shape[-2:]
+    I, J = R.shape[-1], y.shape[-1]
+    if N != y.shape[-2]:
+        raise ValueError("rrqr_lstsq(Q,R,P,y): Q and y don't match.")
+    if M != R.shape[-2]:
+        raise ValueError("rrqr_lstsq(Q,R,P,y): Q and R don't match.")
+    if I != P.shape[-1]:
+        raise ValueError("rrqr_lstsq(Q,R,P,y): R and P don't match.")
+    try:
+        lead = np.broadcast_shapes(Q.shape[:-2], R.shape[:-2], y.shape[:-2], P.shape[:-1])
+    except ValueError:
+        raise ValueError("rrqr_lstsq(Q,R,P,y): Q,R,P,y not broadcast-compatible.")
+    X = np.empty(tuple(lead) + (I, J))
+    ranks = np.empty(tuple(lead), dtype=np.int32)
+    h = _lib.handle(device)
+    for cnt, (oQ, oR, oP, oY), (sQ, sR, sP, sY), b0 in _bcast_groups_n(
+            tuple(lead), [Q.shape[:-2], R.shape[:-2], P.shape[:-1], y.shape[:-2]], [N * M, M * I, I, N * J]):
+        try:
+            _lib.check(h.lib.nd4hip_dqp3ls_batched(h.ptr, cnt, N, M, I, J, _off(Q, oQ), sQ, _off(R, oR), sR, _off(P, oP, 4), sP,
+                                                   _off(y, oY), sY, _off(X, b0 * I * J), _off(ranks, b0, 4)))
+        except _lib.Nd4HipError as e:
+            msg = str(e)
+            for text in ("Infinity or NaN encountered during rank estimation.", "rrqr_lstsq(Q,R,P,y): Invalid indices in P."):
+                if e.code == -1 and text in msg:
+                    raise ValueError(text)
+            raise
+    return X, ranks
+
+
+def rrqr_lstsq(Q, R, P=None, y=None, device=None):
+    """rrqr.js:447-580; accepts rrqr_lstsq((Q,R,P), y) like the reference (:449-454)."""
+    Q, R, P, y = _rrqr_args(Q, R, P, y)
+    return _rrqr_lstsq(Q, R, P, y, device)[0]
+
+
+def rrqr_solve(Q, R, P=None, y=None, device=None):
+    """rrqr.js:417-444: rrqr_lstsq of a square Q @ R; raises SingularMatrixSolveError (with .x) when a rank is < N."""
+    Q, R, P, y = _rrqr_args(Q, R, P, y)
+    Q, R = np.asarray(Q), np.asarray(R)
+    N = Q.shape[-2]
+    if N != R.shape[-1]:
+        raise ValueError("rrqr_solve(Q,R,P, y): Q @ R not square.")
+    x, ranks = _rrqr_lstsq(Q, R, P, y, device)
+    if np.any(ranks < N):
+        raise SingularMatrixSolveError(x)
+    return x
+
+
+def solve(A, y, device=None):
+    """solve.js:23-27: rrqr_solve(rrqr_decomp(A), y)."""
+    Q, R, P = rrqr_decomp(A, device=device)
+    return rrqr_solve(Q, R, P, y, device=device)
