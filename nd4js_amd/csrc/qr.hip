@@ -551,7 +551,7 @@ __global__ __launch_bounds__(256) void qr_narrow_apply(double* __restrict__ Wm, 
   {
     const int i = t / 16, j = t % 16;
 #pragma unroll
-    for (int l = 0; l < NB; l++) wv += s_Tm[l][i] * s_Xs[l * 16 + j];            // T^T X (T: full 16 x 16, see qrh_reconstruct)
+    for (int l = 0; l < NB; l++) wv += s_Tm[l][i] * s_Xs[l * 16 + j];            // T^T X (T: full 16 x 16, see qrh_bc)
   }
   __syncthreads();
   s_Xs[t] = -wv;
@@ -634,17 +634,17 @@ __global__ __launch_bounds__(NT) void qr_update_blocks(double* __restrict__ Cm, 
 //      first 16 columns are Q S, so H^T [panel] = [S R; 0]: (W, K, S R) is a (V, T, R) triple for everything downstream — V's
 //      top block is full instead of unit lower triangular and T is a full 16 x 16 matrix, which is why every consumer of T
 //      uses all 256 entries. The same launch leaves the partials of X = V^T C for the NEXT panel's columns.
-// Three short launches per panel instead of one long one. The previous reflector's work on the other column blocks (trailing
-// columns of W, Q^T) rides along in two phases, split over 512-row chunks like the panel itself: partial X = V^T C in launch A,
-// C -= V (T^T X) in launches B (W) and C (Q^T). Panels the Gram route must not take — (nearly) dependent columns (a Cholesky
+// The three phases run in ONE launch per panel (qrh_bc), the partial matrices crossing between its row workgroups as tagged words.
+// The previous reflector's work on the other column blocks (trailing columns of W, Q^T) rides along in the same launch, split over
+// 512-row chunks like the panel itself (qrh_side_fused). Panels the Gram route must not take — (nearly) dependent columns (a Cholesky
 // pivot below HR_PIVOT_THR of its diagonal entry), columns that are exactly zero below the top block (triangular / banded input,
 // where the reference skips rotations: qr.js:60,63) or non-finite data — are flagged by phase B and factorised by
-// qr_panel_row_body in workgroup 0 of phase C: same result as before, at the old speed.
+// qr_panel_row_body in workgroup 0: same result as before, at the old speed.
 constexpr double HR_PIVOT_THR = 1e-5;
 constexpr double HR_SERIES_MAX = 1e-5;
 constexpr int HR_MIN_ROWS = 64;
 
-enum { SEG_NX = 0, SEG_NA, SEG_NX0, SEG_F };   // SEG_NX0: partial X of the next panel's block alone; SEG_F: partial X, exchange, apply in one go
+enum { SEG_NX = 0, SEG_NA, SEG_F };   // SEG_F: partial X, exchange, apply in one go
 struct QrhSeg { int kind, first, count; };
 
 struct QrhP {
@@ -653,22 +653,19 @@ struct QrhP {
   double* Tall; long strideT;
   double* taus; long strideTau;
   double* Xp; long strideXp;        // partials of X = V^T C on the next panel's columns: [part][256]
-  double* Gp; long strideGp;        // slot 0: Gram of the top 16 rows; slots 1..: partial Gram matrices of the rows below
-  double* G2p; long strideG2;       // partial Gram matrices of Q1
-  double* R1; int* flag;            // per matrix: R1 (16 x 16), fall-back flag
+  int* flag;                        // per matrix: fall-back flag
   double* QT; long strideQT;
   double* Xs; long strideXs;        // side work: partials of X per (column block, row chunk): [cb][rc][256]
   int j0;                           // first row / column of the panel
   int pj0;                          // previous panel (-1: none): its reflector is what the side blocks and phase A apply
   int nxp;                          // partials of X to sum in phase A
   int nrow;                         // row workgroups of this launch
-  int ngp;                          // Gram partials to sum (phase B: phase A's row workgroups; phase C: phase B's)
   int wide0, nnw, nqb, nrc;         // side work (reflector pj0): nnw column blocks of W from wide0 on, then nqb blocks of Q^T; nrc row chunks each;
                                     // a side workgroup takes TWO adjacent blocks (pairs of W blocks first, then pairs of Q^T blocks)
   int nseg; QrhSeg seg[2];          // the side work of this launch: workgroups nrow.. walk these segments
   int skip_x;                       // phase C: no partial X for the next panel (last panel of an outer block: the block update covers it)
-  int na_shift;                     // SEG_NA starts at this block of W (1: the fused launch B+C, whose row workgroups take the next panel's columns themselves)
-  unsigned long long* Xch; long strideXch;   // fused launch B+C: the row workgroups' exchange slots (512 tagged words each)
+  int na_shift;                     // the side pairs start at this block of W (1: the panel launch's row workgroups take the next panel's columns themselves)
+  unsigned long long* Xch; long strideXch;   // the panel launch: the row workgroups' exchange slots (QX_ROW_SLOT tagged words each)
   unsigned long long* Xsx; long strideXsx;   // fused side work: [column block][row chunk] slots of 512 tagged words (rcs_max chunks per block)
   int rcs_max;
   long long* stamps; int stamp_slot; // debug (ND4HIP_QR_STAMPS): 100 MHz wall-clock stamps of workgroup 0, 8 per launch
@@ -876,9 +873,9 @@ __device__ __forceinline__ void qrh_apply_rows(double* __restrict__ s_w, const d
 
 // ---- tagged words: the in-kernel exchange between co-resident workgroups (see qrh_bc) ----
 // (qx_st / qx_sum: xchg.h)
-// ---- side work of the panel launches: the previous reflector (panel pj0) on the other column blocks (trailing columns of W, then
-// Q^T), in two phases split over 512-row chunks like the panel itself: partial X = V^T C (SEG_NX, launch A), C -= V (T^T X)
-// (SEG_NA: the blocks of W in launch B, whose first one phase C reads; those of Q^T in launch C) ----
+// ---- side work: the previous reflector (panel pj0) on the other column blocks (trailing columns of W, then Q^T), split over
+// 512-row chunks like the panel itself. Inside a panel launch both phases of a chunk run in one workgroup (SEG_F); after the last
+// panel, two launches of their own: partial X = V^T C (SEG_NX), then C -= V (T^T X) (SEG_NA) ----
 struct QrhSide { double* C; long ldc; int c0, nc, cb, rc; };   // cb: first block (index among W blocks, then Q^T blocks); nc: columns of the pair
 __device__ __forceinline__ QrhSide qrh_near_of(const QrhP& P, int mat, int e) {
   QrhSide s;
@@ -1063,11 +1060,6 @@ __device__ __forceinline__ void qrh_side(const QrhP& P, int mat, int i, double* 
     qrh_side_x(P, mat, s, P.pj0, P.Xs + mat * P.strideXs + ((long)s.cb * P.nrc + s.rc) * 256, s_buf);
   } else if (kind == SEG_NA) {
     qrh_near_apply(P, mat, e, s_buf);
-  } else if (kind == SEG_NX0) {                                        // the block right behind the panel alone: e = row chunk
-    QrhSide s;
-    s.rc = e; s.cb = 0; s.C = P.Wm + mat * P.strideW; s.ldc = P.ld; s.c0 = P.wide0;
-    s.nc = P.N - s.c0 < NB ? P.N - s.c0 : NB;
-    qrh_side_x(P, mat, s, P.pj0, P.Xs + mat * P.strideXs + (long)s.rc * 256, s_buf);
   } else if (kind == SEG_F) {
     qrh_side_fused(P, mat, e, s_buf);
   }
@@ -1099,299 +1091,6 @@ __device__ __forceinline__ void qrh_x_full(double* __restrict__ s_part, const do
   qrh_reduce_store(s_part, a0, a1, dst);
 }
 
-// ---- phase A: the previous reflector on the panel's own columns (rows from j0 - 16), then the partial Gram matrices ----
-__global__ __launch_bounds__(512) void qrh_gram(const QrhP P) {
-  __shared__ double s_buf[QRH_SMEM];
-  const int mat = blockIdx.y;
-  if ((int)blockIdx.x >= P.nrow) { qrh_side(P, mat, (int)blockIdx.x - P.nrow, s_buf); return; }
-  const int g = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6, fx = lane & 15, fk = lane >> 4;
-  double* A = P.Wm + mat * P.strideW;
-  const int j0 = P.j0, ub = j0 - NB, M = P.M;
-  const int rb = ub + (g * 8 + wave) * 64;
-  d4 cc[1][4];
-  d4 (&c)[4] = cc[0];
-  qrh_stamp(P, 0);
-  if (P.pj0 >= 0) {
-    const double* Xsrc = P.Xp + mat * P.strideXp;
-    int nx = P.nxp;
-    if (P.Xch != nullptr && P.flag[mat]) {
-      // the previous panel took the fall-back inside the fused launch B+C, which leaves no partials of X behind: every workgroup
-      // forms X = V^T C over all rows itself (rare path), in its own slot of Xp
-      double* mine = P.Xp + mat * P.strideXp + (long)g * 256;
-      qrh_x_full(s_buf, P.Vall + mat * P.strideV + (long)ub * P.ldv + ub, P.ldv, A + (long)ub * P.ld + j0, P.ld, M - ub, NB, mine);
-      __syncthreads();
-      Xsrc = mine; nx = 1;
-    }
-    qrh_apply_rows<1>(s_buf, Xsrc, 0, nx, P.Tall + mat * P.strideT + (long)(ub / NB) * NB * NB,
-                      P.Vall + mat * P.strideV + ub, P.ldv, A + j0, P.ld, NB, rb, M, cc);
-    __syncthreads();                                                  // s_buf is reused below
-    qrh_stamp(P, 1);
-  } else {
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const int rc = rb + q * 16 + fk + 4 * r;
-        c[q][r] = (rc >= 0 && rc < M) ? A[(long)rc * P.ld + j0 + fx] : 0.0;
-      }
-    }
-  }
-  // Gram matrices: the accumulator image of a 16-row tile is four 4-row slabs in operand layout (A and B operand alike)
-  d4 g0 = d4{0.0, 0.0, 0.0, 0.0}, g1 = g0, gt = g0;
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    const int ti = (g * 8 + wave) * 4 + q;                            // tile 0: the 16 rows above the panel, tile 1: its top block
-    if (ti == 1) {
-#pragma unroll
-      for (int r = 0; r < 4; r++) gt = __builtin_amdgcn_mfma_f64_16x16x4f64(c[q][r], c[q][r], gt, 0, 0, 0);
-    } else if (ti >= 2) {
-      g0 = __builtin_amdgcn_mfma_f64_16x16x4f64(c[q][0], c[q][0], g0, 0, 0, 0);
-      g1 = __builtin_amdgcn_mfma_f64_16x16x4f64(c[q][1], c[q][1], g1, 0, 0, 0);
-      g0 = __builtin_amdgcn_mfma_f64_16x16x4f64(c[q][2], c[q][2], g0, 0, 0, 0);
-      g1 = __builtin_amdgcn_mfma_f64_16x16x4f64(c[q][3], c[q][3], g1, 0, 0, 0);
-    }
-  }
-  if (g == 0 && wave == 0) {
-#pragma unroll
-    for (int r = 0; r < 4; r++) P.Gp[mat * P.strideGp + (fk + 4 * r) * 16 + fx] = gt[r];
-  }
-  qrh_reduce_store(s_buf, g0, g1, P.Gp + mat * P.strideGp + (long)(1 + g) * 256);
-  qrh_stamp(P, 4);
-}
-
-// the wave's 64 rows of the panel's 16 columns as MFMA A operands (k-step kk <-> column 4 fk + kk: 32 contiguous bytes per lane)
-__device__ __forceinline__ void qrh_load_rows(const double* __restrict__ A, long ld, int j0, int rb, int M, double (&a)[4][4], int lo = 0) {
-  const int lane = threadIdx.x & 63, fx = lane & 15, fk = lane >> 4;
-  const bool vec = (ld & 1) == 0;
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    const int ra = rb + q * 16 + fx;
-    const double* src = A + (long)ra * ld + j0 + 4 * fk;
-    if (ra < M && ra >= lo) {
-      if (vec) {
-        const double2 v0 = *reinterpret_cast<const double2*>(src), v1 = *reinterpret_cast<const double2*>(src + 2);
-        a[q][0] = v0.x; a[q][1] = v0.y; a[q][2] = v1.x; a[q][3] = v1.y;
-      } else { a[q][0] = src[0]; a[q][1] = src[1]; a[q][2] = src[2]; a[q][3] = src[3]; }
-    } else { a[q][0] = a[q][1] = a[q][2] = a[q][3] = 0.0; }
-  }
-}
-
-// ---- phase B: R1 = chol(G), Q1 = C R1^-1 in place, partial Gram matrices of Q1; decides the fall-back ----
-__global__ __launch_bounds__(512) void qrh_chol(const QrhP P) {
-  __shared__ double s_buf[QRH_SMEM];
-  __shared__ double s_G[256], s_R[256], s_Ri[256], s_db[16];
-  __shared__ int s_flag;
-  const int mat = blockIdx.y;
-  if ((int)blockIdx.x >= P.nrow) { qrh_side(P, mat, (int)blockIdx.x - P.nrow, s_buf); return; }
-  const int g = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6, fx = lane & 15, fk = lane >> 4;
-  double* A = P.Wm + mat * P.strideW;
-  const int j0 = P.j0, M = P.M;
-  const long ld = P.ld;
-  const int rb = j0 + (g * 8 + wave) * 64;
-  double a[4][4];
-  qrh_load_rows(A, ld, j0, rb, M, a);
-  qrh_stamp(P, 0);
-  if (t < 256) {
-    const double gb = qrh_sum_parts(P.Gp + mat * P.strideGp + 256 + t, P.ngp);
-    s_G[t] = gb + P.Gp[mat * P.strideGp + t];
-    if (t % 17 == 0) s_db[t / 17] = gb;                               // column sums of squares below the top block
-  }
-  __syncthreads();
-  qrh_stamp(P, 1);
-  if (wave == 0) {
-    __builtin_amdgcn_s_setprio(3);                                     // the chain wave shares its CU with riding side workgroups
-    bool ok = ND4_CHOL16(s_G, s_R, s_Ri, HR_PIVOT_THR);
-    __builtin_amdgcn_s_setprio(0);
-#pragma unroll
-    for (int k = 0; k < 16; k++) ok = ok && (s_db[k] > 0.0);
-    if (lane == 0) s_flag = ok ? 0 : 1;
-  }
-  __syncthreads();
-  const int flag = s_flag;
-  qrh_stamp(P, 2);
-  if (g == 0) {
-    if (t == 0) P.flag[mat] = flag;
-    if (t < 256) P.R1[(long)mat * 256 + t] = s_R[t];
-  }
-  if (flag) return;
-  double bw[4];
-#pragma unroll
-  for (int kk = 0; kk < 4; kk++) bw[kk] = s_Ri[(4 * fk + kk) * 16 + fx];
-  d4 acc[4];
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    acc[q] = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int kk = 0; kk < 4; kk++) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[q][kk], bw[kk], acc[q], 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const int rc = rb + q * 16 + fk + 4 * r;
-      if (rc < M) A[(long)rc * ld + j0 + fx] = acc[q][r];
-    }
-  }
-  d4 g0 = d4{0.0, 0.0, 0.0, 0.0}, g1 = g0;
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    g0 = __builtin_amdgcn_mfma_f64_16x16x4f64(acc[q][0], acc[q][0], g0, 0, 0, 0);
-    g1 = __builtin_amdgcn_mfma_f64_16x16x4f64(acc[q][1], acc[q][1], g1, 0, 0, 0);
-    g0 = __builtin_amdgcn_mfma_f64_16x16x4f64(acc[q][2], acc[q][2], g0, 0, 0, 0);
-    g1 = __builtin_amdgcn_mfma_f64_16x16x4f64(acc[q][3], acc[q][3], g1, 0, 0, 0);
-  }
-  qrh_reduce_store(s_buf, g0, g1, P.G2p + mat * P.strideG2 + (long)g * 256);
-  qrh_stamp(P, 4);
-}
-
-// ---- phase C: R2, the representation (W, K, S R), and the partials of X = V^T C for the next panel's columns ----
-template <int R>
-__global__ __launch_bounds__(512) void qrh_reconstruct(const QrhP P) {
-  __shared__ double s_buf[QRH_SMEM];
-  const int mat = blockIdx.y;
-  if ((int)blockIdx.x >= P.nrow) { qrh_side(P, mat, (int)blockIdx.x - P.nrow, s_buf); return; }
-  const int g = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6, fx = lane & 15, fk = lane >> 4;
-  double* A = P.Wm + mat * P.strideW;
-  const int j0 = P.j0, M = P.M, N = P.N;
-  const long ld = P.ld;
-  const int c0 = j0 + NB, nc = P.skip_x ? 0 : (N - c0 < NB ? N - c0 : NB);   // the next panel's columns (nc <= 0: none)
-  double* Xdst = P.Xp + mat * P.strideXp + (long)g * 256;
-  if (P.flag[mat]) {
-    if constexpr (R == 0) return;                                      // tall panel: qr_panel_flagged + qrh_x_flagged follow
-    else if (g == 0) {
-      qr_panel_row_body<(R > 0 ? R : 1)>(mat, P.Wm, M, ld, P.strideW, P.Vall, P.ldv, P.strideV, P.Tall, P.strideT, P.taus, P.strideTau, j0, NB);
-      __threadfence();
-      __syncthreads();
-      if (nc > 0) qrh_x_full(s_buf, P.Vall + mat * P.strideV + (long)j0 * P.ldv + j0, P.ldv, A + (long)j0 * ld + c0, ld, M - j0, nc, Xdst);
-    } else if (nc > 0 && t < 256) Xdst[t] = 0.0;
-    return;
-  }
-  double* s_E = s_buf + QRH_LDS; double* s_F = s_E + 256; double* s_P = s_F + 256; double* s_R1 = s_P + 256; double* s_Qt = s_R1 + 256;
-  double* s_R2 = s_Qt + 256; double* s_R2i = s_R2 + 256; double* s_Z = s_R2i + 256; double* s_Rm = s_Z + 256; double* s_K = s_Rm + 256; double* s_S = s_K + 256;
-  __shared__ int s_emax;
-  const int rb = j0 + (g * 8 + wave) * 64;
-  double a[4][4]; d4 cs[4];
-  qrh_load_rows(A, ld, j0, rb, M, a);
-  qrh_stamp(P, 0);
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const int rc = rb + q * 16 + fk + 4 * r;
-      cs[q][r] = (rc < M && fx < nc) ? A[(long)rc * ld + c0 + fx] : 0.0;
-    }
-  }
-  const int i = (t & 255) / 16, j = t % 16;
-  double x = 0.0, r1v = 0.0, qtv = 0.0;
-  if (t < 256) {
-    x = qrh_sum_parts(P.G2p + mat * P.strideG2 + t, P.ngp);
-    r1v = P.R1[(long)mat * 256 + t];
-    qtv = A[(long)(j0 + i) * ld + j0 + j];
-  }
-  if (t == 0) s_emax = 0;
-  __syncthreads();
-  if (t < 256) {
-    x -= (i == j) ? 1.0 : 0.0;                                         // E = Q1^T Q1 - I
-    s_E[t] = x;
-    s_F[t] = (i < j) ? x : ((i == j) ? 0.5 * x : 0.0);
-    s_R1[t] = r1v;
-    s_Qt[t] = qtv;
-    const float ax = fabsf((float)x);
-    atomicMax(&s_emax, (ax == ax) ? __float_as_int(ax) : 0x7f800000);
-  }
-  __syncthreads();
-  const bool series = __int_as_float(s_emax) <= (float)HR_SERIES_MAX;
-  qrh_stamp(P, 1);
-  if (series) {
-    // R2 = I + F with F = triu(E - F^T F) (diagonal halved), two fixed-point steps from F = triu(E): error O(|E|^3);
-    // R2^-1 = (I - F)(I + F^2) = I - F + F^2 - F^3: error O(|F|^4)
-    if (t < 256) {
-      double pp = 0.0;
-#pragma unroll
-      for (int l = 0; l < 16; l++) pp += s_F[l * 16 + i] * s_F[l * 16 + j];
-      s_P[t] = pp;
-    }
-    __syncthreads();
-    if (t < 256) {
-      const double x = s_E[t] - s_P[t];
-      s_F[t] = (i < j) ? x : ((i == j) ? 0.5 * x : 0.0);
-    }
-    __syncthreads();
-    if (t < 256) {
-      double pp = 0.0;
-#pragma unroll
-      for (int l = 0; l < 16; l++) pp += s_F[i * 16 + l] * s_F[l * 16 + j];
-      s_P[t] = pp + ((i == j) ? 1.0 : 0.0);                            // I + F^2
-      s_R2[t] = s_F[t] + ((i == j) ? 1.0 : 0.0);
-    }
-    __syncthreads();
-    if (t < 256) {
-      double pp = 0.0;
-#pragma unroll
-      for (int l = 0; l < 16; l++) pp += (((i == l) ? 1.0 : 0.0) - s_F[i * 16 + l]) * s_P[l * 16 + j];
-      s_R2i[t] = pp;
-    }
-  } else {
-    if (t < 256) s_E[t] += (i == j) ? 1.0 : 0.0;
-    __syncthreads();
-    if (wave == 0) (void)ND4_CHOL16(s_E, s_R2, s_R2i, 0.0);
-  }
-  __syncthreads();
-  if (t < 256) {
-    double z = 0.0, rr = 0.0;
-#pragma unroll
-    for (int l = 0; l < 16; l++) {
-      z += s_Qt[i * 16 + l] * s_R2i[l * 16 + j];                       // top block of Q = Q1 R2^-1
-      rr += s_R2[i * 16 + l] * s_R1[l * 16 + j];                       // R = R2 R1
-    }
-    s_Z[t] = z; s_Rm[t] = rr;
-  }
-  __syncthreads();
-  qrh_stamp(P, 3);
-  if (wave == 0) { __builtin_amdgcn_s_setprio(3); ND4_GJ16(s_Z, s_K, s_S); __builtin_amdgcn_s_setprio(0); }
-  double bw[4];
-#pragma unroll
-  for (int kk = 0; kk < 4; kk++) bw[kk] = s_R2i[(4 * fk + kk) * 16 + fx];
-  d4 y[4];
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    y[q] = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int kk = 0; kk < 4; kk++) y[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[q][kk], bw[kk], y[q], 0, 0, 0);
-  }
-  __syncthreads();                                                     // s_K, s_S
-  qrh_stamp(P, 4);
-  double* V = P.Vall + mat * P.strideV + j0;
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    const bool top = (g == 0 && wave == 0 && q == 0);
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const int ii = fk + 4 * r, rc = rb + q * 16 + ii;
-      double wv = 0.0;
-      if (top) {                                                       // W = Q - [S; 0]; R = S R2 R1 in place
-        if (ii == fx) y[q][r] -= s_S[ii];
-        wv = (ii <= fx) ? s_S[ii] * s_Rm[ii * 16 + fx] : 0.0;
-      }
-      if (rc < M) { V[(long)rc * P.ldv + fx] = y[q][r]; A[(long)rc * ld + j0 + fx] = wv; }
-    }
-  }
-  if (g == 0) {
-    if (t < 256) P.Tall[mat * P.strideT + (long)(j0 / NB) * NB * NB + t] = s_K[t];
-    if (t < 16) P.taus[mat * P.strideTau + j0 + t] = 1.0;             // "a reflector was needed" (qr_flips)
-  }
-  if (nc > 0) {
-    d4 x0 = d4{0.0, 0.0, 0.0, 0.0}, x1 = x0;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      x0 = __builtin_amdgcn_mfma_f64_16x16x4f64(y[q][0], cs[q][0], x0, 0, 0, 0);
-      x1 = __builtin_amdgcn_mfma_f64_16x16x4f64(y[q][1], cs[q][1], x1, 0, 0, 0);
-      x0 = __builtin_amdgcn_mfma_f64_16x16x4f64(y[q][2], cs[q][2], x0, 0, 0, 0);
-      x1 = __builtin_amdgcn_mfma_f64_16x16x4f64(y[q][3], cs[q][3], x1, 0, 0, 0);
-    }
-    qrh_reduce_store(s_buf, x0, x1, Xdst);
-  }
-  qrh_stamp(P, 5);
-  qrh_stamp(P, 6);
-}
-
 // ---- phases B and C in ONE launch (round 3, second half) ----
 // What phase C needs from the other row workgroups of phase B is one 16 x 16 matrix each (the partial Gram matrix of Q1). An exchange
 // of that size inside a kernel costs ~1.4 us on this chip when it is made of agent-scope relaxed atomics only (sc1 stores are
@@ -1401,14 +1100,14 @@ __global__ __launch_bounds__(512) void qrh_reconstruct(const QrhP P) {
 // of payload and a 32-bit tag (panel number + 1): a double is valid as soon as both its words carry the tag, so there is no flag,
 // no s_waitcnt and no ordering between words. The row partition is phase A's (rows from j0 - 16: tile 0 of workgroup 0 lies above
 // the panel and only sees the previous reflector). The next panel's 16 columns get the previous reflector from the ROW workgroups
-// here (X summed from the side partials of launch A), each for its own rows, which it then holds for the partial X of the next
+// here (X summed in the first exchange), each for its own rows, which it then holds for the partial X of the next
 // panel: the side work of this launch starts one block later (na_shift) and covers W and Q^T in one go.
-// A flagged panel: workgroup 0 runs qr_panel_row_body (R > 0; tall panels: qr_panel_flagged in a launch of its own, as before) and
-// nobody writes partials of X: the next launch A forms X itself (qrh_gram), the last panel's narrow update goes through qrh_x_flagged.
-constexpr long QX_ROW_SLOT = 2560;   // words per row workgroup: values [0,256) G, [256,512) X of the next block, [512,768) top-tile Gram, 768 "stores are out", [1024,1280) Gram of Q1
-// MERGED: phase A in the same launch as well — the previous reflector on the panel's own columns, the partial Gram matrices and the
+// Phase A rides in the same launch as well — the previous reflector on the panel's own columns, the partial Gram matrices and the
 // partial X of the NEXT panel's block cross in a first exchange, so a panel is ONE launch (all side work rides in it).
-template <int R, bool MERGED>
+// A flagged panel: workgroup 0 runs qr_panel_row_body (R > 0; tall panels: qr_panel_flagged in a launch of its own, as before) and
+// nobody writes partials of X: the next launch forms X itself over all rows, the last panel's narrow update goes through qrh_x_flagged.
+constexpr long QX_ROW_SLOT = 2560;   // words per row workgroup: values [0,256) G, [256,512) X of the next block, [512,768) top-tile Gram, 768 "stores are out", [1024,1280) Gram of Q1
+template <int R>
 __global__ __launch_bounds__(512) void qrh_bc(const QrhP P) {
   __shared__ double s_buf[QRH_SMEM];
   __shared__ double s_G[256], s_R[256], s_Ri[256], s_db[16];
@@ -1426,11 +1125,10 @@ __global__ __launch_bounds__(512) void qrh_bc(const QrhP P) {
   qx_u64* myslot = slots + (long)g * QX_ROW_SLOT;
   double* Xdst = P.Xp + mat * P.strideXp + (long)g * 256;
   qrh_stamp(P, 0);
-  d4 csb[1][4];
-  d4 (&cs)[4] = csb[0];
+  d4 cs[4];
   double a[4][4];
   __shared__ double s_T2[256], s_Xs[256], s_Xn[256];
-  d4 cnx[4]; double avp[4][4]; bool nextupd = false;       // MERGED: the next block's tile, the previous reflector's rows
+  d4 cnx[4]; double avp[4][4]; bool nextupd = false;       // the next block's tile, the previous reflector's rows
   // the next block through the previous reflector for this workgroup's rows: C -= V (T^T X), -T^T X in s_Xn
   auto apply_next = [&]() {
     double bwn[4];
@@ -1447,7 +1145,7 @@ __global__ __launch_bounds__(512) void qrh_bc(const QrhP P) {
       }
     }
   };
-  if constexpr (MERGED) {
+  {
     // ---- phase A: the previous reflector on the panel's own columns, partial Gram matrices, partial X of the next block ----
     // All loads first: the own tile and the next block's tile in the accumulator image (== slab image: slab u = 4 q + r), the
     // previous reflector's rows as A operands (avp) and as slabs (vs). The next block's tile and avp stay in registers until the
@@ -1456,7 +1154,7 @@ __global__ __launch_bounds__(512) void qrh_bc(const QrhP P) {
     const bool havep = P.pj0 >= 0;
     nextupd = nc > 0 && havep;
     const double* Vp = P.Vall + mat * P.strideV + ub;
-    const bool prevflag = havep && P.flag[mat] != 0;                  // the previous panel was flagged: no partials of X (see qrh_gram)
+    const bool prevflag = havep && P.flag[mat] != 0;                  // the previous panel was flagged: no partials of X
     // first the loads that head the dependent chain of the own-column update (loads return in order): X partials and T
     double xsum0 = 0.0, tprev = 0.0, xp8[8];
 #pragma unroll
@@ -1621,31 +1319,6 @@ __global__ __launch_bounds__(512) void qrh_bc(const QrhP P) {
       for (int l = 0; l < NB; l++) wv += s_T2[l * 16 + i] * s_Xs[l * 16 + j];
       s_Xn[t - 256] = -wv;
     }
-  } else {
-    // ---- the next panel's columns: the previous reflector for this workgroup's rows (kept in cs for the partial X below) ----
-    if (nc > 0 && P.pj0 >= 0) {
-      qrh_apply_rows<1>(s_buf, P.Xs + mat * P.strideXs, 0, P.nrc, P.Tall + mat * P.strideT + (long)(ub / NB) * NB * NB,
-                        P.Vall + mat * P.strideV + ub, P.ldv, A + c0, ld, nc, rb, M, csb);
-      __syncthreads();
-    } else {
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-          const int rc = rb + q * 16 + fk + 4 * r;
-          cs[q][r] = (rc >= j0 && rc < M && fx < nc) ? A[(long)rc * ld + c0 + fx] : 0.0;
-        }
-      }
-    }
-    qrh_load_rows(A, ld, j0, rb, M, a, j0);
-    if (t < 256) {
-      const double gb = qrh_sum_parts(P.Gp + mat * P.strideGp + 256 + t, P.ngp);
-      s_G[t] = gb + P.Gp[mat * P.strideGp + t];
-      if (t % 17 == 0) s_db[t / 17] = gb;                             // column sums of squares below the top block
-    }
-    if (t == 0) s_emax = 0;
-    __syncthreads();
-    qrh_stamp(P, 1);
   }
   // ---- phase B: R1 = chol(G), the fall-back decision ----
   if (wave == 0) {
@@ -1660,28 +1333,26 @@ __global__ __launch_bounds__(512) void qrh_bc(const QrhP P) {
   const int flag = s_flag;                                            // (the same in every row workgroup: same sums in the same order)
   if (g == 0 && t == 0) P.flag[mat] = flag;
   if (flag) {
-    if constexpr (MERGED) { if (nextupd) apply_next(); }          // (the next launch needs the block whatever happens to this panel)
+    if (nextupd) apply_next();                                        // (the next launch needs the block whatever happens to this panel)
     if constexpr (R > 0) {
-      if constexpr (MERGED) {
-        // the panel's columns were written by all row workgroups of THIS launch: every workgroup pushes its stores out (release:
-        // write back the L2) and says so; workgroup 0 waits for all, invalidates (acquire) and runs the classic panel. Rare path.
-        __threadfence();
-        __syncthreads();
-        if (t == 0) qx_st(myslot, 768, 1.0, tag);
-        if (g == 0) {
-          if (t < P.nrow) {
-            int spins = 0;
-            for (;;) {
-              bool ok = true;
-              (void)qx_sum(slots + (long)t * QX_ROW_SLOT, 768, 1, tag, ok, QX_ROW_SLOT);
-              if (ok) break;
-              if (++spins > QX_SPIN_LIMIT) { qx_raise(P.status); break; }
-              __builtin_amdgcn_s_sleep(4);
-            }
+      // the panel's columns were written by all row workgroups of THIS launch: every workgroup pushes its stores out (release:
+      // write back the L2) and says so; workgroup 0 waits for all, invalidates (acquire) and runs the classic panel. Rare path.
+      __threadfence();
+      __syncthreads();
+      if (t == 0) qx_st(myslot, 768, 1.0, tag);
+      if (g == 0) {
+        if (t < P.nrow) {
+          int spins = 0;
+          for (;;) {
+            bool ok = true;
+            (void)qx_sum(slots + (long)t * QX_ROW_SLOT, 768, 1, tag, ok, QX_ROW_SLOT);
+            if (ok) break;
+            if (++spins > QX_SPIN_LIMIT) { qx_raise(P.status); break; }
+            __builtin_amdgcn_s_sleep(4);
           }
-          __syncthreads();
-          __threadfence();
         }
+        __syncthreads();
+        __threadfence();
       }
       if (g == 0) qr_panel_row_body<(R > 0 ? R : 1)>(mat, P.Wm, M, ld, P.strideW, P.Vall, P.ldv, P.strideV, P.Tall, P.strideT, P.taus, P.strideTau, j0, NB);
     }
@@ -1722,11 +1393,9 @@ __global__ __launch_bounds__(512) void qrh_bc(const QrhP P) {
     for (int w = 0; w < 8; w++) xs += s_buf[w * 256 + t];
     qx_st(myslot, 1024 + t, xs, tag);
   }
-  if constexpr (MERGED) {                                              // in the shadow of the exchange: the next block
-    if (nextupd) apply_next();
+  if (nextupd) apply_next();                                           // in the shadow of the exchange: the next block
 #pragma unroll
-    for (int q = 0; q < 4; q++) cs[q] = cnx[q];
-  }
+  for (int q = 0; q < 4; q++) cs[q] = cnx[q];
   qrh_stamp(P, 3);
   double x = 0.0;
   if (t < 256) {
@@ -2239,6 +1908,7 @@ void launch_panel_row(nd4hip_handle* h, int batch, double* W, int M, long ld, lo
 // (bench ops.qr_panel). All three shapes then run at the same 1.75 TB/s: the launch is bound by the instruction issue of the
 // 4096 wave-panels (8500 instructions each, two waves per SIMD); forcing three waves per SIMD spills (196 us).
 // Batches of full panels on the matrix cores (qr_batched_panel.h). ZERO: the rows below the top block are zeroed in W.
+constexpr int QR_SMALL_WG_BATCH = 64;
 template <int R, int NWV, bool ZERO>
 static void launch_qrb(nd4hip_handle* h, int batch, double* W, int M, long ld, long sW, double* V, long ldv, long sV,
                        double* T, long sT, double* taus, long sTau, int j0, long long* stamps) {
@@ -2247,8 +1917,7 @@ static void launch_qrb(nd4hip_handle* h, int batch, double* W, int M, long ld, l
 template <bool ZERO>
 static void launch_panel_mfma(nd4hip_handle* h, int batch, double* W, int M, int m, long ld, long sW, double* V, long ldv, long sV,
                               double* T, long sT, double* taus, long sTau, int j0, long long* stamps = nullptr) {
-  static const int small_min = [] { const char* e = getenv("ND4HIP_QR_SMALL_WG_BATCH"); return e ? atoi(e) : 64; }();   // 0: never
-  const bool many = small_min > 0 && batch >= small_min;
+  const bool many = batch >= QR_SMALL_WG_BATCH;
   if (many && m <= 256)       launch_qrb<4, 1, ZERO>(h, batch, W, M, ld, sW, V, ldv, sV, T, sT, taus, sTau, j0, stamps);
   else if (many && m <= 512)  launch_qrb<4, 2, ZERO>(h, batch, W, M, ld, sW, V, ldv, sV, T, sT, taus, sTau, j0, stamps);
   else if (many && m <= 1024) launch_qrb<4, 4, ZERO>(h, batch, W, M, ld, sW, V, ldv, sV, T, sT, taus, sTau, j0, stamps);
@@ -2258,8 +1927,7 @@ static void launch_panel_mfma(nd4hip_handle* h, int batch, double* W, int M, int
 }
 static void launch_panel_rows(nd4hip_handle* h, int batch, double* W, int M, int m, long ld, long sW, double* V, long ldv, long sV,
                               double* T, long sT, double* taus, long sTau, int j0, int nb) {
-  static const int small_min = [] { const char* e = getenv("ND4HIP_QR_SMALL_WG_BATCH"); return e ? atoi(e) : 64; }();   // 0: never
-  const bool many = small_min > 0 && batch >= small_min;
+  const bool many = batch >= QR_SMALL_WG_BATCH;
   if (many && m <= 256)       launch_panel_row<4, 1>(h, batch, W, M, ld, sW, V, ldv, sV, T, sT, taus, sTau, j0, nb);
   else if (many && m <= 512)  launch_panel_row<4, 2>(h, batch, W, M, ld, sW, V, ldv, sV, T, sT, taus, sTau, j0, nb);
   else if (many && m <= 1024) launch_panel_row<4, 4>(h, batch, W, M, ld, sW, V, ldv, sV, T, sT, taus, sTau, j0, nb);
@@ -2334,103 +2002,65 @@ int form_q_compact_wy(nd4hip_handle* h, const QrWs& ws, int batch, int M, int Lq
 }
 
 
-// host side of the multi-workgroup panels: one panel = three launches (+ two conditional ones for panels taller than the register
-// kernel), the previous reflector's side work riding along on the column blocks of W up to near_end (then, optionally, Q^T)
+// host side of the multi-workgroup panels: one launch per panel (+ a conditional one for panels taller than the register kernel),
+// the previous reflector's side work riding along on the column blocks of W up to near_end (then, optionally, Q^T)
 struct QrhHost {
   nd4hip_handle* h; QrhP P; int batch; int nq;          // nq: column blocks of Q^T (0: no Q^T accumulation)
   double *V, *T; long ldv, sV, sT;                        // for qr_narrow_apply
   int pj0 = -1;                                           // the reflector whose narrow / side work is pending (-1: none)
-  bool fused_last = false;                                // the last panel went through qrh_bc
+  // every field of P; the slices a caller has no use for are nullptr (the panel entry point: no partials of X, side work or Q^T).
+  // Zeroes the exchange slots and the fall-back flags.
+  int init(nd4hip_handle* hh, int nmat, double* W, int M, int N, long ld, long sW, double* Vm, long ldv_, long sV_, double* Tm, long sT_,
+           double* taus, long sTau, int* flag, unsigned long long* Xch, long sXch, double* Xp, long sXp, double* QT, long sQT,
+           double* Xs, long sXs, unsigned long long* Xsx, long sXsx, int rcs_max) {
+    h = hh; batch = nmat; nq = QT ? (M + NB - 1) / NB : 0; V = Vm; T = Tm; ldv = ldv_; sV = sV_; sT = sT_;
+    P.Wm = W; P.M = M; P.N = N; P.ld = ld; P.strideW = sW; P.Vall = Vm; P.ldv = ldv_; P.strideV = sV_; P.Tall = Tm; P.strideT = sT_;
+    P.taus = taus; P.strideTau = sTau; P.Xp = Xp; P.strideXp = sXp; P.flag = flag; P.QT = QT; P.strideQT = sQT; P.Xs = Xs; P.strideXs = sXs;
+    P.Xch = Xch; P.strideXch = sXch; P.Xsx = Xsx; P.strideXsx = sXsx; P.rcs_max = rcs_max;
+    P.nxp = 0; P.na_shift = 0; P.nseg = 0; P.wide0 = 0; P.nrc = 1; P.nnw = 0; P.nqb = 0; P.skip_x = 0; P.j0 = 0; P.pj0 = -1; P.nrow = 0;
+    P.stamps = nullptr; P.stamp_slot = 0; P.status = h->xstat; { const int dp = nd4_test_drop_panel(); P.drop_tag = dp >= 0 ? dp + 1 : -1; }
+    if (Xsx) ND4_HIP(hipMemsetAsync(Xsx, 0, sizeof(unsigned long long) * (size_t)batch * sXsx, h->stream));
+    ND4_HIP(hipMemsetAsync(Xch, 0, sizeof(unsigned long long) * (size_t)batch * sXch, h->stream));
+    ND4_HIP(hipMemsetAsync(flag, 0, sizeof(int) * (size_t)batch, h->stream));
+    return 0;
+  }
   void add_seg(int kind, int first, int count) { if (count > 0) { P.seg[P.nseg].kind = kind; P.seg[P.nseg].first = first; P.seg[P.nseg].count = count; P.nseg++; } }
   int seg_total() const { int n = 0; for (int i = 0; i < P.nseg; i++) n += P.seg[i].count; return n; }
   void side_launch() { if (P.nseg > 0) hipLaunchKernelGGL(qrh_side_only, dim3((unsigned)seg_total(), (unsigned)batch), dim3(512), 0, h->stream, P); P.nseg = 0; }
-  // the side work of the reflector at pj: workgroups for W (columns [pj + 32, near_end)), for W and Q^T
-  void side_of(int pj, int near_end, bool with_qt, int& nw_e, int& all_e) {
-    nw_e = 0; all_e = 0;
-    if (pj < 0) return;
+  // the side work of the reflector at pj: column blocks of W from pj + 32 to near_end, then (with_qt) of Q^T; returns its
+  // workgroups when both phases run on their own
+  int side_of(int pj, int near_end, bool with_qt) {
+    if (pj < 0) return 0;
     const int wide0 = pj + 2 * NB;
     P.wide0 = wide0; P.nrc = (P.M - pj + 511) / 512;
     P.nnw = wide0 < near_end ? (near_end - wide0 + NB - 1) / NB : 0;
     P.nqb = with_qt ? nq : 0;
-    nw_e = ((P.nnw + 1) / 2) * P.nrc; all_e = nw_e + ((P.nqb + 1) / 2) * P.nrc;      // a workgroup takes two adjacent column blocks
+    return ((P.nnw + 1) / 2 + (P.nqb + 1) / 2) * P.nrc;                            // a workgroup takes two adjacent column blocks
   }
+  // ONE launch per panel (qrh_bc): phase A rides in front of B and C (first exchange: Gram partials + partial X of the next block);
+  // the row workgroups also take the next panel's columns through the previous reflector, so its side work (qrh_side_fused, W pairs
+  // then Q^T pairs) starts one block later
   int panel(int j0, int near_end, bool with_qt, bool skip_x) {
     const int m = P.M - j0;
-    int side_w = 0, side_all = 0;
-    side_of(pj0, near_end, with_qt, side_w, side_all);
-    P.j0 = j0; P.pj0 = pj0; P.skip_x = skip_x ? 1 : 0; P.na_shift = 0;
-    const int nA = (m + NB + 511) / 512, nB = (m + 511) / 512;
-    // phases B and C in one launch (qrh_bc): the row workgroups keep phase A's partition and exchange the Gram matrices of Q1 inside
-    // the kernel; they also take the next panel's columns through the previous reflector, so the side work starts one block later.
-    // The side work itself: both phases of a (block pair, row chunk) in one workgroup (qrh_side_fused): W pairs ride in launch A,
-    // Q^T pairs in launch B+C; only the next panel's own block still needs its partial X ahead of launch B+C (SEG_NX0).
-    static const bool bc_off = [] { const char* e = getenv("ND4HIP_QR_NO_FUSED_BC"); return e && *e && *e != '0'; }();
-    static const bool sf_off = [] { const char* e = getenv("ND4HIP_QR_NO_FUSED_SIDE"); return e && *e && *e != '0'; }();
-    const bool next_cols = !skip_x && j0 + NB < P.N;
-    if (!bc_off && P.Xch != nullptr && !(pj0 >= 0 && next_cols && P.nnw < 1)) {
-      const int sh = (pj0 >= 0 && next_cols) ? 1 : 0;
-      const int nwp = pj0 >= 0 ? (P.nnw - sh + 1) / 2 : 0, nqp = pj0 >= 0 ? (P.nqb + 1) / 2 : 0;
-      const bool sf = !sf_off && P.Xsx != nullptr;
-      static const bool mg_off = [] { const char* e = getenv("ND4HIP_QR_NO_MERGED"); return e && *e && *e != '0'; }();
-      if ((sf || side_all == 0) && !mg_off) {
-        // ONE launch per panel: phase A rides in front of B and C (first exchange: Gram partials + partial X of the next block)
-        P.na_shift = sh;
-        P.nrow = nA; P.ngp = 0; P.nseg = 0; add_seg(SEG_F, 0, (nwp + nqp) * P.nrc);
-        const dim3 gm((unsigned)(nA + seg_total()), (unsigned)batch);
-        if (m <= 512)       hipLaunchKernelGGL((qrh_bc<1, true>), gm, dim3(512), 0, h->stream, P);
-        else if (m <= 1024) hipLaunchKernelGGL((qrh_bc<2, true>), gm, dim3(512), 0, h->stream, P);
-        else if (m <= 2048) hipLaunchKernelGGL((qrh_bc<4, true>), gm, dim3(512), 0, h->stream, P);
-        else {
-          hipLaunchKernelGGL((qrh_bc<0, true>), gm, dim3(512), 0, h->stream, P);
-          hipLaunchKernelGGL(qr_panel_flagged, dim3((unsigned)batch), dim3(1024), 0, h->stream, P.Wm, P.M, P.ld, P.strideW, P.Vall, P.ldv, P.strideV,
-                             P.Tall, P.strideT, P.taus, P.strideTau, j0, NB, P.flag);
-        }
-        P.na_shift = 0;
-        pj0 = j0; P.nxp = nA; P.nseg = 0; P.stamp_slot++; fused_last = true;
-        ND4_HIP(hipGetLastError());
-        return 0;
-      }
-      P.nrow = nA; P.ngp = 0; P.nseg = 0;
-      static const int sf_a = [] { const char* e = getenv("ND4HIP_QR_SIDE_IN_A"); return e ? atoi(e) : 0; }();   // percent of the W pairs that ride in launch A
-      const int nwa = nwp * sf_a / 100;
-      if (sf) { P.na_shift = sh; if (sh) add_seg(SEG_NX0, 0, P.nrc); add_seg(SEG_F, 0, nwa * P.nrc); }
-      else add_seg(SEG_NX, 0, side_all);
-      hipLaunchKernelGGL(qrh_gram, dim3((unsigned)(nA + seg_total()), (unsigned)batch), dim3(512), 0, h->stream, P); P.stamp_slot++;
-      P.na_shift = sh;
-      P.nrow = nA; P.ngp = nA; P.nseg = 0;
-      if (sf) add_seg(SEG_F, nwa * P.nrc, (nwp - nwa + nqp) * P.nrc); else add_seg(SEG_NA, 0, (nwp + nqp) * P.nrc);
-      const dim3 gc((unsigned)(nA + seg_total()), (unsigned)batch);
-      if (m <= 512)       hipLaunchKernelGGL((qrh_bc<1, false>), gc, dim3(512), 0, h->stream, P);
-      else if (m <= 1024) hipLaunchKernelGGL((qrh_bc<2, false>), gc, dim3(512), 0, h->stream, P);
-      else if (m <= 2048) hipLaunchKernelGGL((qrh_bc<4, false>), gc, dim3(512), 0, h->stream, P);
-      else {
-        hipLaunchKernelGGL((qrh_bc<0, false>), gc, dim3(512), 0, h->stream, P);
-        hipLaunchKernelGGL(qr_panel_flagged, dim3((unsigned)batch), dim3(1024), 0, h->stream, P.Wm, P.M, P.ld, P.strideW, P.Vall, P.ldv, P.strideV,
-                           P.Tall, P.strideT, P.taus, P.strideTau, j0, NB, P.flag);
-      }
-      P.na_shift = 0;
-      pj0 = j0; P.nxp = nA; P.nseg = 0; P.stamp_slot++; fused_last = true;
-      ND4_HIP(hipGetLastError());
-      return 0;
-    }
-    P.nrow = nA; P.ngp = 0; P.nseg = 0; add_seg(SEG_NX, 0, side_all);
-    hipLaunchKernelGGL(qrh_gram, dim3((unsigned)(nA + seg_total()), (unsigned)batch), dim3(512), 0, h->stream, P); P.stamp_slot++;
-    fused_last = false;
-    P.nrow = nB; P.ngp = nA; P.nseg = 0; add_seg(SEG_NA, 0, side_w);
-    hipLaunchKernelGGL(qrh_chol, dim3((unsigned)(nB + seg_total()), (unsigned)batch), dim3(512), 0, h->stream, P); P.stamp_slot++;
-    P.ngp = nB; P.nseg = 0; add_seg(SEG_NA, side_w, side_all - side_w);
-    const dim3 gc((unsigned)(nB + seg_total()), (unsigned)batch);
-    if (m <= 512)       hipLaunchKernelGGL(qrh_reconstruct<1>, gc, dim3(512), 0, h->stream, P);
-    else if (m <= 1024) hipLaunchKernelGGL(qrh_reconstruct<2>, gc, dim3(512), 0, h->stream, P);
-    else if (m <= 2048) hipLaunchKernelGGL(qrh_reconstruct<4>, gc, dim3(512), 0, h->stream, P);
+    side_of(pj0, near_end, with_qt);
+    P.j0 = j0; P.pj0 = pj0; P.skip_x = skip_x ? 1 : 0;
+    const int nA = (m + NB + 511) / 512;
+    const int sh = (pj0 >= 0 && !skip_x && j0 + NB < P.N) ? 1 : 0;
+    const int nwp = pj0 >= 0 ? (P.nnw - sh + 1) / 2 : 0, nqp = pj0 >= 0 ? (P.nqb + 1) / 2 : 0;
+    P.na_shift = sh;
+    P.nrow = nA; P.nseg = 0; add_seg(SEG_F, 0, (nwp + nqp) * P.nrc);
+    const dim3 gm((unsigned)(nA + seg_total()), (unsigned)batch);
+    if (m <= 512)       hipLaunchKernelGGL(qrh_bc<1>, gm, dim3(512), 0, h->stream, P);
+    else if (m <= 1024) hipLaunchKernelGGL(qrh_bc<2>, gm, dim3(512), 0, h->stream, P);
+    else if (m <= 2048) hipLaunchKernelGGL(qrh_bc<4>, gm, dim3(512), 0, h->stream, P);
     else {
       // taller than the register-resident panel: a flagged panel is factorised by the global-memory panel kernel in a launch of its own
-      hipLaunchKernelGGL(qrh_reconstruct<0>, gc, dim3(512), 0, h->stream, P);
+      hipLaunchKernelGGL(qrh_bc<0>, gm, dim3(512), 0, h->stream, P);
       hipLaunchKernelGGL(qr_panel_flagged, dim3((unsigned)batch), dim3(1024), 0, h->stream, P.Wm, P.M, P.ld, P.strideW, P.Vall, P.ldv, P.strideV,
                          P.Tall, P.strideT, P.taus, P.strideTau, j0, NB, P.flag);
-      if (!skip_x) hipLaunchKernelGGL(qrh_x_flagged, dim3((unsigned)nB, (unsigned)batch), dim3(512), 0, h->stream, P);
     }
-    pj0 = j0; P.nxp = nB; P.nseg = 0; P.stamp_slot++;
+    P.na_shift = 0;
+    pj0 = j0; P.nxp = nA; P.nseg = 0; P.stamp_slot++;
     ND4_HIP(hipGetLastError());
     return 0;
   }
@@ -2439,15 +2069,12 @@ struct QrhHost {
     if (pj0 < 0) return 0;
     if (narrow && pj0 + NB < P.N) {
       const int m = P.M - pj0;
-      if (fused_last) {   // a flagged panel of the fused launch left no partials of X behind
-        P.j0 = pj0; P.na_shift = 0;
-        hipLaunchKernelGGL(qrh_x_flagged, dim3((unsigned)P.nxp, (unsigned)batch), dim3(512), 0, h->stream, P);
-      }
+      P.j0 = pj0; P.na_shift = 0;                         // a flagged panel left no partials of X behind
+      hipLaunchKernelGGL(qrh_x_flagged, dim3((unsigned)P.nxp, (unsigned)batch), dim3(512), 0, h->stream, P);
       hipLaunchKernelGGL(qr_narrow_apply, dim3((unsigned)((m + 255) / 256), (unsigned)batch), dim3(256), 0, h->stream,
                          P.Wm, P.M, P.N, P.ld, P.strideW, V, ldv, sV, T, sT, pj0, pj0 + NB, P.Xp, P.strideXp, P.nxp);
     }
-    int side_w = 0, side_all = 0;
-    side_of(pj0, near_end, with_qt, side_w, side_all);
+    const int side_all = side_of(pj0, near_end, with_qt);
     P.pj0 = pj0;
     P.nseg = 0; add_seg(SEG_NX, 0, side_all); side_launch();
     add_seg(SEG_NA, 0, side_all); side_launch();
@@ -2570,289 +2197,184 @@ static int geqrf_tsqr(nd4hip_handle* h, int batch, int M, int N, const double* A
   return nd4_givens_signs(h, batch, M, N, N, true, Q, N, (long)M * N, R, N, (long)N * N, nullptr, 0, flips);
 }
 
-int nd4_geqrf_q_ex(nd4hip_handle* h, int64_t batch64, int64_t M64, int64_t N64, const double* A, double* Q, double* R, bool full) {
-  ND4_CHECK_ARG(M64 < (1ll << 30) && N64 < (1ll << 30) && batch64 < 65536, "nd4_geqrf_q: extent out of range");
-  const int M = (int)M64, N = (int)N64, batch = (int)batch64;
-  {
-    static const bool tsqr_off = [] { const char* e = getenv("ND4HIP_QR_NO_TSQR"); return e && *e && *e != '0'; }();
-    const long nblk = (M + 2047) / 2048;
-    // every block needs >= N rows, and the stacked R (nblk N rows) must either fit the fast panel kernel directly or be
-    // at most half as tall as the input (so that the recursion terminates quickly)
-    if (!full && !tsqr_off && M > 2048 && N <= 2048 && (long)batch * nblk <= 32768 && M / nblk >= N &&
-        (nblk * N <= 2048 || 2 * nblk * N <= (long)M))
-      return geqrf_tsqr(h, batch, M, N, A, Q, R);
-  }
-  const int L = M < N ? M : N;
-  const int npanels = (L + NB - 1) / NB;
-  const bool tall = M > N;
-  const int Lq = (full && tall) ? M : L;                    // columns of Q
-  const int Lr = (full && tall) ? M : L;                    // rows of R
+// ---- the strategies of nd4_geqrf_q_ex, chosen once from the shape ----
+constexpr int QR_LA_MAX_BATCH = 24;        // look-ahead form up to this many matrices; a batch that fills the chip takes the plain sequence
+                                           // with the matrix-core panels (1024 x 512^2 48.6 -> 43.7 ms; 8 matrices 1.97 against 2.53 ms, 32: 2.91 against 2.87)
+constexpr int QR_ROWSPLIT_MAX_BATCH = 8;   // row-split panels (qrh_bc) up to this many matrices; more: one workgroup per panel
+constexpr int QR_QT_MAX_BATCH = 4;         // Q^T accumulated (look-ahead) or Q formed in one shot (compact WY) up to this many matrices
+constexpr int QR_TALL_MAX_ROWS = 16384;    // the tall row-split form for 2048 < M <= this
+constexpr int QR_OUTER = 128;              // columns per outer block of the two-level forms ...
+constexpr int QR_BATCH_OUTER_NARROW = 64;  // ... and of the batched form below 16 panels (1024 x 512^2: 43.8 one level, 30.5 (64), 23.6 ms (128))
 
-  // ---- workspace carve-up (all per-matrix blocks are multiples of 2 doubles -> 16-B aligned) ----
+enum QrForm {
+  QR_TSQR,        // tall-skinny: row blocks factorised as one batch, then their stacked R factors (geqrf_tsqr)
+  QR_LOOKAHEAD,   // 64 <= M <= 2048, few matrices: row-split panels while they are tall enough, then thread-per-row panels with look-ahead
+  QR_TALL,        // 2048 < M <= QR_TALL_MAX_ROWS, few matrices: row-split panels inside outer blocks, block reflectors on the rest
+  QR_BATCHED,     // M <= 2048, batches beyond the look-ahead form: two levels, every step batched
+  QR_BLOCKED,     // the rest: one level, or two with a per-matrix far update when M > 2048
+};
+
+static int qr_batch_outer(int npanels) { return npanels >= 16 ? QR_OUTER : QR_BATCH_OUTER_NARROW; }
+
+static QrForm qr_choose(int batch, int M, int N, bool full) {
+  const int L = M < N ? M : N, npanels = (L + NB - 1) / NB;
+  const long nblk = (M + 2047) / 2048;
+  // TSQR: every block needs >= N rows, and the stacked R (nblk N rows) must either fit the fast panel kernel directly or be
+  // at most half as tall as the input (so that the recursion terminates quickly)
+  if (!full && M > 2048 && N <= 2048 && (long)batch * nblk <= 32768 && M / nblk >= N &&
+      (nblk * N <= 2048 || 2 * nblk * N <= (long)M))
+    return QR_TSQR;
+  if (M <= 2048 && M >= 64 && batch <= QR_LA_MAX_BATCH) return QR_LOOKAHEAD;
+  // (a ragged last panel must fit the thread-per-row kernel)
+  if (batch <= QR_ROWSPLIT_MAX_BATCH && M > 2048 && M <= QR_TALL_MAX_ROWS && L >= 256 && (L % NB == 0 || M - (L / NB) * NB <= 2048))
+    return QR_TALL;
+  if (M <= 2048 && batch > 1 && L % NB == 0 && npanels >= 2 * (qr_batch_outer(npanels) / NB)) return QR_BATCHED;
+  return QR_BLOCKED;
+}
+
+// one factorisation in flight: shapes, the working matrix W (R's buffer when M <= N, a workspace copy when tall), the workspace slices
+struct QrJob {
+  nd4hip_handle* h; QrForm form; int batch, M, N, L, npanels, Lq;
+  double* W; long ld, sW;
   QrWs ws;
-  ws.ldv = ((L + NB - 1) / NB) * NB;                        // Vall: M x ldv, zero above each panel
-  ws.sV = (long)M * ws.ldv;
-  ws.sT = (long)npanels * NB * NB;
-  ws.sTau = ws.ldv;
-  const int ncols = (N > Lq ? N : Lq);
-  ws.ldw = ((ncols + 1) / 2) * 2;
-  ws.nchunks_max = (M + VTC_ROWS - 1) / VTC_ROWS;
-  ws.sChunk = (long)NB * ws.ldw;
-  ws.sWb = ws.sChunk * ws.nchunks_max;
-  ws.sW2 = ws.sChunk;
-  const long sWork = tall ? (long)M * N : 0;
-  static const bool la_off = [] { const char* e = getenv("ND4HIP_QR_NO_LOOKAHEAD"); return e && *e && *e != '0'; }();
-  static const bool wy_off = [] { const char* e = getenv("ND4HIP_QR_NO_WY"); return e && *e && *e != '0'; }();
-  static const bool qt_off = [] { const char* e = getenv("ND4HIP_QR_NO_QT"); return e && *e && *e != '0'; }();
-  // (like LU: the look-ahead launches serve few matrices; a batch that fills the chip takes the plain sequence with the
-  //  matrix-core panels of qr_batched_panel.h: 1024 x 512^2 48.6 -> 43.7 ms; 8 matrices 1.97 against 2.53 ms, 32: 2.91 against 2.87.
-  //  ND4HIP_QR_LA_MAX_BATCH moves the switch.)
-  static const int la_max_batch = [] { const char* e = getenv("ND4HIP_QR_LA_MAX_BATCH"); return e ? atoi(e) : 24; }();
-  const bool lookahead = !la_off && M <= 2048 && M >= 64 && batch <= la_max_batch;
-  const bool use_qt = lookahead && !wy_off && !qt_off && batch <= 4 && L >= 256;   // Q^T accumulated in the shadow of the panels
-  const long sQT = use_qt ? (long)M * M : 0;
-  static const bool hr_off = [] { const char* e = getenv("ND4HIP_QR_NO_HR"); return e && *e && *e != '0'; }();
-  // panels taller than the register kernel: two-level driver below (a ragged last panel must fit the thread-per-row kernel)
-  const bool hr_tall = !hr_off && !la_off && batch <= 8 && M > 2048 && M <= 16384 && L >= 256 && (L % NB == 0 || M - (L / NB) * NB <= 2048);
-  const bool use_hr = (lookahead && !hr_off && batch <= 8) || hr_tall;    // multi-workgroup panels (CholeskyQR2 + compact orthogonal completion)
-  const int hr_parts = (M + NB + 511) / 512 + 1;
-  const long sGp = use_hr ? (long)(hr_parts + 1) * 256 : 0, sG2 = use_hr ? (long)hr_parts * QX_ROW_SLOT : 0, sR1 = use_hr ? 256 : 0;   // G2: partials (3 launches) or 512 tagged words per row workgroup (qrh_bc)
-  const long hr_rcs = (M + 511) / 512;
-  const long sXs = use_hr ? ((N + NB - 1) / NB + (use_qt ? (M + NB - 1) / NB : 0)) * hr_rcs * 256 : 0;   // side work: [column block][row chunk][256]
-  const long sXsx = 2 * sXs;                                 // fused side work: 512 tagged words per (column block, row chunk)
-  size_t doubles = (size_t)batch * (ws.sV + 2 * ws.sT + ws.sTau + ws.sWb + ws.sW2 + sWork + sQT + sGp + sG2 + sR1 + sXs + sXsx);
-  size_t bytes = doubles * sizeof(double) + ((size_t)batch * L + 2) * sizeof(int) + (size_t)batch * 8 + (size_t)batch * sizeof(int) + 64;
-  void* p = nullptr;
-  Nd4WsScope scope(h);
-  ND4_TRY(nd4_ws_alloc(h, bytes, &p));
-  double* d = static_cast<double*>(p);
-  ws.V = d; d += (size_t)batch * ws.sV;
-  ws.T = d; d += (size_t)batch * ws.sT;
-  ws.Tside = d; d += (size_t)batch * ws.sT;                 // diagonal blocks of slots factorised in parts (tall panels)
-  ws.taus = d; d += (size_t)batch * ws.sTau;
-  ws.Wp = d; d += (size_t)batch * ws.sWb;
-  ws.W2 = d; d += (size_t)batch * ws.sW2;
-  ws.work = tall ? d : nullptr; d += (size_t)batch * sWork;
-  double* QT = use_qt ? d : nullptr; d += (size_t)batch * sQT;
-  double* hrGp = d; d += (size_t)batch * sGp;
-  double* hrG2 = d; d += (size_t)batch * sG2;
-  double* hrR1 = d; d += (size_t)batch * sR1;
-  double* hrXs = d; d += (size_t)batch * sXs;
-  double* hrXsx = d; d += (size_t)batch * sXsx;
-  ws.flips = reinterpret_cast<int*>(d);
+  double* QT; long sQT;                    // the look-ahead form's Q^T accumulator (nullptr: none)
+  QrhHost hr; bool use_hr;                 // row-split panels
+  // two-level forms: the outer blocks' compact-WY factors (bT, kept for Q) and the far update's scratch (bG, bTmp: wy_build_T; bX, bW)
+  double *bT = nullptr, *bG = nullptr, *bTmp = nullptr, *bX = nullptr, *bW = nullptr;
+  long bsT = 0, bsX = 0;                   // QR_BATCHED: per matrix
+  int ppb = 0, first_low = 0;              // panels per outer block; QR_TALL: first panel of the one-level part
+};
 
-  // working matrix: R's buffer when it has A's shape (M <= N), a workspace copy when tall
-  double* W = tall ? ws.work : R;
-  const long ld = N, sW = (long)M * N;
-  unsigned long long* exps = reinterpret_cast<unsigned long long*>(ws.flips + (((size_t)batch * L + 1) & ~size_t(1)));   // max|a| bits per matrix
-  int* hrFlag = reinterpret_cast<int*>(exps + batch);
-  ND4_HIP(hipMemsetAsync(exps, 0, sizeof(unsigned long long) * batch, h->stream));
-  {
-    long nblk = (sW + 256 * 16 - 1) / (256 * 16); if (nblk > 2048) nblk = 2048;
-    hipLaunchKernelGGL(qr_amax, dim3((unsigned)nblk, (unsigned)batch), dim3(256), 0, h->stream, A, sW, exps);
-  }
-  hipLaunchKernelGGL(qr_scale_apply, dim3((unsigned)((sW + 255) / 256), (unsigned)batch), dim3(256), 0, h->stream, A, W, sW, exps, -1);
-  ND4_HIP(hipMemsetAsync(ws.V, 0, sizeof(double) * (size_t)batch * ws.sV, h->stream));
-  if (M > 2048) ND4_HIP(hipMemsetAsync(ws.Tside, 0, sizeof(double) * (size_t)batch * ws.sT, h->stream));
+// C <- (I - V op(T) V^T) C for nblk reflector columns V [m, nblk] and their nblk x nblk factor T: X = V^T C, W = op(T) X, C -= V W
+// (X, W: nblk x n, leading dimension n); strides per matrix of the batch (0 for one matrix)
+static int block_update(nd4hip_handle* h, bool transT, int m, int n, int nblk, const double* V, long ldv, long sV, const double* T, long sT,
+                        double* C, long ldc, long sC, double* X, double* W, long sX, int batch) {
+  ND4_TRY(nd4_gemm(h, true, false, nblk, n, m, 1.0, V, ldv, sV, C, ldc, sC, 0.0, X, n, sX, batch));
+  ND4_TRY(nd4_gemm(h, transT, false, nblk, n, nblk, 1.0, T, nblk, sT, X, n, sX, 0.0, W, n, sX, batch));
+  return nd4_gemm(h, false, false, m, n, nblk, -1.0, V, ldv, sV, W, n, sX, 1.0, C, ldc, sC, batch);
+}
 
-  // ---- factorisation: panels left to right ----
-  // Look-ahead form (every panel fits the thread-per-row kernel): panel p shares its launch with the update of the columns behind
-  // it by reflector p-1; only the 16 columns of panel p+1 are updated between two panels. See qr_colblock_update.
-  static const int hr_min_rows = [] { const char* e = getenv("ND4HIP_QR_HR_MIN_ROWS"); const int v = e ? atoi(e) : 0; return v >= HR_MIN_ROWS ? v : HR_MIN_ROWS; }();
-  QrhHost hr;
-  hr.h = h; hr.batch = batch; hr.nq = QT ? (M + NB - 1) / NB : 0; hr.V = ws.V; hr.T = ws.T; hr.ldv = ws.ldv; hr.sV = ws.sV; hr.sT = ws.sT;
-  if (use_hr) {
-    QrhP& P = hr.P;
-    P.Wm = W; P.M = M; P.N = N; P.ld = ld; P.strideW = sW; P.Vall = ws.V; P.ldv = ws.ldv; P.strideV = ws.sV; P.Tall = ws.T; P.strideT = ws.sT;
-    P.taus = ws.taus; P.strideTau = ws.sTau; P.Xp = ws.Wp; P.strideXp = ws.sWb; P.Gp = hrGp; P.strideGp = sGp; P.G2p = hrG2; P.strideG2 = sG2;
-    P.R1 = hrR1; P.flag = hrFlag; P.QT = QT; P.strideQT = sQT; P.nxp = 0; P.Xs = hrXs; P.strideXs = sXs;
-    P.Xch = reinterpret_cast<unsigned long long*>(hrG2); P.strideXch = sG2; P.na_shift = 0;
-    P.Xsx = reinterpret_cast<unsigned long long*>(hrXsx); P.strideXsx = sXsx; P.rcs_max = (int)hr_rcs;
-    ND4_HIP(hipMemsetAsync(hrXsx, 0, sizeof(double) * (size_t)batch * sXsx, h->stream));
-    ND4_HIP(hipMemsetAsync(hrG2, 0, sizeof(double) * (size_t)batch * sG2, h->stream));
-    ND4_HIP(hipMemsetAsync(hrFlag, 0, sizeof(int) * (size_t)batch, h->stream));
-    P.nseg = 0; P.wide0 = 0; P.nrc = 1; P.nnw = 0; P.nqb = 0; P.skip_x = 0; P.j0 = 0; P.pj0 = -1; P.nrow = 0; P.ngp = 0;
-    static const bool want_stamps = [] { const char* e = getenv("ND4HIP_QR_STAMPS"); return e && *e && *e != '0'; }();
-    P.stamps = nullptr; P.stamp_slot = 0; P.status = h->xstat; { const int dp = nd4_test_drop_panel(); P.drop_tag = dp >= 0 ? dp + 1 : -1; }
-    if (want_stamps) { ND4_HIP(hipMalloc(&P.stamps, sizeof(long long) * 8 * 3 * (npanels + 1))); ND4_HIP(hipMemset(P.stamps, 0, sizeof(long long) * 8 * 3 * (npanels + 1))); }
+// matrix mt: the nblk reflector columns from J on — their factor Tb from the panels' factors first (wy_build_T) unless Tb holds it
+// already — applied to the n columns of C (rows [J, M))
+static int wy_block_update(QrJob& j, int mt, int J, int nblk, bool build, double* Tb, bool transT, double* C, long ldc, int n) {
+  const QrWs& ws = j.ws;
+  const int mJ = j.M - J;
+  const double* Vb = ws.V + (long)mt * ws.sV + (long)J * ws.ldv + J;
+  if (build) ND4_TRY(wy_build_T(j.h, mJ, nblk, Vb, ws.ldv, ws.T + (long)mt * ws.sT + (long)(J / NB) * NB * NB, NB, Tb, j.bG, j.bTmp));
+  return block_update(j.h, transT, mJ, n, nblk, Vb, ws.ldv, 0, Tb, 0, C, ldc, 0, j.bX, j.bW, 0, 1);
+}
+
+// Thread-per-row panels from pnl on with look-ahead: panel p shares its launch with the update of the columns behind it (and of Q^T)
+// by reflector p-1; only the 16 columns of panel p+1 are updated between two panels. See qr_colblock_update.
+static int qr_rows_lookahead(QrJob& j, int pnl) {
+  nd4hip_handle* h = j.h;
+  const QrWs& ws = j.ws;
+  const int M = j.M, N = j.N, L = j.L, npanels = j.npanels, batch = j.batch;
+  double* W = j.W; double* QT = j.QT;
+  const long ld = j.ld, sW = j.sW, sQT = j.sQT;
+  const int nq = QT ? (M + NB - 1) / NB : 0;
+  int pj0 = -1;                                              // first row/column of the previous panel
+  for (; pnl < npanels; pnl++) {
+    const int j0 = pnl * NB, nb = L - j0 < NB ? L - j0 : NB, m = M - j0;
+    // reflector p-1 has reached the 16 columns behind its own panel (the narrow launch: [pj0 + NB, pj0 + 2 NB), which contain this
+    // panel); the columns from there on still lack it
+    const int wide0 = pj0 + 2 * NB, nwide = (pj0 >= 0 && wide0 < N) ? (N - wide0 + NB - 1) / NB : 0;
+    const int wc0 = j0 + nb;
+    const dim3 grid((unsigned)(1 + nwide + (pj0 >= 0 ? nq : 0)), (unsigned)batch);
+    if (m <= 512)       hipLaunchKernelGGL(qr_panel_row_la<1>, grid, dim3(512), 0, h->stream, W, M, N, ld, sW, ws.V, ws.ldv, ws.sV, ws.T, ws.sT, ws.taus, ws.sTau, j0, nb, pj0 < 0 ? 0 : pj0, wide0, nwide, QT, sQT);
+    else if (m <= 1024) hipLaunchKernelGGL(qr_panel_row_la<2>, grid, dim3(512), 0, h->stream, W, M, N, ld, sW, ws.V, ws.ldv, ws.sV, ws.T, ws.sT, ws.taus, ws.sTau, j0, nb, pj0 < 0 ? 0 : pj0, wide0, nwide, QT, sQT);
+    else                hipLaunchKernelGGL(qr_panel_row_la<4>, grid, dim3(512), 0, h->stream, W, M, N, ld, sW, ws.V, ws.ldv, ws.sV, ws.T, ws.sT, ws.taus, ws.sTau, j0, nb, pj0 < 0 ? 0 : pj0, wide0, nwide, QT, sQT);
+    if (wc0 < N) {                                           // the next panel's columns (or the first block right of the last panel)
+      const dim3 gn((unsigned)((m + 255) / 256), (unsigned)batch);
+      hipLaunchKernelGGL(qr_narrow_x, gn, dim3(256), 0, h->stream, W, M, N, ld, sW, ws.V, ws.ldv, ws.sV, j0, wc0, ws.Wp, ws.sWb);
+      hipLaunchKernelGGL(qr_narrow_apply, gn, dim3(256), 0, h->stream, W, M, N, ld, sW, ws.V, ws.ldv, ws.sV, ws.T, ws.sT, j0, wc0, ws.Wp, ws.sWb, 0);
+    }
+    pj0 = j0;
   }
-  double *btT = nullptr, *btG = nullptr, *btX = nullptr, *btW = nullptr;              // batched two-level form (generic branch below)
-  int bt_ppb = 0; long bt_sT = 0, bt_sX = 0;
-  if (lookahead) {
-    int pj0 = -1;                                            // first row/column of the previous panel
-    const int nq = QT ? (M + NB - 1) / NB : 0;
-    if (QT) ND4_TRY(nd4_set_identity(h, M, M, QT, M, batch, sQT));
-    int pnl = 0;
-    if (use_hr) {
-      // multi-workgroup panels while they are full and tall enough: three launches per panel (Gram / Cholesky / representation). The
-      // previous reflector's side work rides along: partial X of every column block (trailing columns of W, then Q^T) in launch A,
-      // the update of the blocks of W in launch B (phase C reads the first of them), of Q^T in launch C.
-      for (; pnl < npanels; pnl++) {
-        const int j0 = pnl * NB, nb = L - j0 < NB ? L - j0 : NB, m = M - j0;
-        if (nb < NB || m < hr_min_rows) break;
-        ND4_TRY(hr.panel(j0, N, QT != nullptr, false));
-      }
-      ND4_TRY(hr.finish(N, QT != nullptr, true));             // nothing pending afterwards: the remaining panels start afresh
-      ND4_TRY(hr.dump_stamps());
-    }
-    for (; pnl < npanels; pnl++) {
-      const int j0 = pnl * NB, nb = L - j0 < NB ? L - j0 : NB, m = M - j0;
-      // reflector p-1 has reached the 16 columns behind its own panel (the narrow launch: [pj0 + NB, pj0 + 2 NB), which contain this
-      // panel); the columns from there on still lack it
-      const int wide0 = pj0 + 2 * NB, nwide = (pj0 >= 0 && wide0 < N) ? (N - wide0 + NB - 1) / NB : 0;
-      const int wc0 = j0 + nb;
-      const dim3 grid((unsigned)(1 + nwide + (pj0 >= 0 ? nq : 0)), (unsigned)batch);
-      if (m <= 512)       hipLaunchKernelGGL(qr_panel_row_la<1>, grid, dim3(512), 0, h->stream, W, M, N, ld, sW, ws.V, ws.ldv, ws.sV, ws.T, ws.sT, ws.taus, ws.sTau, j0, nb, pj0 < 0 ? 0 : pj0, wide0, nwide, QT, sQT);
-      else if (m <= 1024) hipLaunchKernelGGL(qr_panel_row_la<2>, grid, dim3(512), 0, h->stream, W, M, N, ld, sW, ws.V, ws.ldv, ws.sV, ws.T, ws.sT, ws.taus, ws.sTau, j0, nb, pj0 < 0 ? 0 : pj0, wide0, nwide, QT, sQT);
-      else                hipLaunchKernelGGL(qr_panel_row_la<4>, grid, dim3(512), 0, h->stream, W, M, N, ld, sW, ws.V, ws.ldv, ws.sV, ws.T, ws.sT, ws.taus, ws.sTau, j0, nb, pj0 < 0 ? 0 : pj0, wide0, nwide, QT, sQT);
-      if (wc0 < N) {                                           // the next panel's columns (or the first block right of the last panel)
-        const dim3 gn((unsigned)((m + 255) / 256), (unsigned)batch);
-        hipLaunchKernelGGL(qr_narrow_x, gn, dim3(256), 0, h->stream, W, M, N, ld, sW, ws.V, ws.ldv, ws.sV, j0, wc0, ws.Wp, ws.sWb);
-        hipLaunchKernelGGL(qr_narrow_apply, gn, dim3(256), 0, h->stream, W, M, N, ld, sW, ws.V, ws.ldv, ws.sV, ws.T, ws.sT, j0, wc0, ws.Wp, ws.sWb, 0);
-      }
-      pj0 = j0;
-    }
-    if (pj0 >= 0) {   // the last panel was a thread-per-row one; wide input: its reflector on the columns right of the block the narrow launch has done
-      const int j0 = (npanels - 1) * NB, nb = L - j0 < NB ? L - j0 : NB, wc0 = j0 + nb + NB;
-      if (wc0 < N)
-        hipLaunchKernelGGL(qr_update_blocks<512>, dim3((unsigned)((N - wc0 + NB - 1) / NB), (unsigned)batch), dim3(512), 0, h->stream,
-                           W, M, N, ld, sW, ws.V, ws.ldv, ws.sV, ws.T, ws.sT, j0, wc0);
-      if (QT) hipLaunchKernelGGL(qr_update_blocks<512>, dim3((unsigned)nq, (unsigned)batch), dim3(512), 0, h->stream,
-                                 QT, M, M, (long)M, sQT, ws.V, ws.ldv, ws.sV, ws.T, ws.sT, (npanels - 1) * NB, 0);
-    }
-    ND4_HIP(hipGetLastError());
-  } else if (hr_tall) {
-    // ---- M > 2048, two levels with multi-workgroup panels (round 3) ----
-    // The split register panels (two 8-column halves / four 4-column quarters per 16-column slot, each followed by its own
-    // block-reflector launches and a Gram product) took ~165 us per slot, and every slot read-modify-wrote the whole trailing
-    // matrix. Now: outer blocks of 128 columns; inside a block the row-split panels of qrh_* (no height limit: the rows are cut into
-    // 512-row workgroups) with the previous reflector riding along on the block's own columns only; after the block its compact-WY
-    // factor T (128 x 128: the panels' 16 x 16 factors on the diagonal, T12 = -T1 (V1^T V2) T2 level by level from one Gram matrix)
-    // takes all 128 reflectors to the columns right of it at once on the tiled MFMA kernel: X = V^T C, W = T^T X, C -= V W (K = 128).
-    // Once the panels fit the register kernel (m <= 2048) the rest is factorised with one level, as a 2048-row problem. Q is formed
-    // afterwards by applying the same block reflectors backwards (4/3 M^3 flop instead of the 6 M n^2 of the one-shot formation).
-    const int ppb = 128 / NB;
-    const size_t nbo = 128, nblocks = (size_t)(npanels + ppb - 1) / ppb;
-    void* q = nullptr;
-    const int ncq = N > Lq ? N : Lq;
-    ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (nblocks * nbo * nbo + nbo * nbo * 2 + nbo * nbo / 2 + 16 + 2 * nbo * (size_t)ncq + 64), &q));
-    double* blkT = static_cast<double*>(q); double* farG = blkT + nblocks * nbo * nbo; double* farTmp = farG + nbo * nbo;
-    double* farX = farTmp + nbo * nbo / 2 + 16; double* farW = farX + nbo * (size_t)ncq;
-    int pnl = 0;
-    int first_low = npanels;                                  // first panel of the one-level part
-    for (int P0 = 0; P0 < npanels && M - P0 * NB > 2048; P0 += ppb) {
-      const int pend = P0 + ppb < npanels ? P0 + ppb : npanels;
-      const int bend = pend < npanels ? pend * NB : N;
-      bool ok = true;
-      for (pnl = P0; pnl < pend; pnl++) {
-        const int j0 = pnl * NB, nb = L - j0 < NB ? L - j0 : NB;
-        if (nb < NB) { ok = false; break; }                   // (a ragged last panel: only when L is not a multiple of 16; handled below)
-        ND4_TRY(hr.panel(j0, bend, false, pnl == pend - 1));
-      }
-      if (!ok) break;
-      ND4_TRY(hr.finish(bend, false, false));                 // the block's last reflector has no column of the block left to reach
-      first_low = pend;
-      if (bend < N) {
-        const int J = P0 * NB, nblk = (pend - P0) * NB, mJ = M - J, far = N - bend;
-        for (int mt = 0; mt < batch; mt++) {
-          const double* Vb = ws.V + (long)mt * ws.sV + (long)J * ws.ldv + J;
-          double* C = W + (long)mt * sW + (long)J * ld + bend;
-          double* Tb = blkT + (size_t)(P0 / ppb) * nbo * nbo;
-          ND4_TRY(wy_build_T(h, mJ, nblk, Vb, ws.ldv, ws.T + (long)mt * ws.sT + (long)P0 * NB * NB, NB, Tb, farG, farTmp));
-          ND4_TRY(nd4_gemm(h, true, false, nblk, far, mJ, 1.0, Vb, ws.ldv, 0, C, ld, 0, 0.0, farX, far, 0, 1));
-          ND4_TRY(nd4_gemm(h, true, false, nblk, far, nblk, 1.0, Tb, nblk, 0, farX, far, 0, 0.0, farW, far, 0, 1));
-          ND4_TRY(nd4_gemm(h, false, false, mJ, far, nblk, -1.0, Vb, ws.ldv, 0, farW, far, 0, 1.0, C, ld, 0, 1));
-        }
-      }
-    }
-    // the rest as one level: multi-workgroup panels with all remaining columns as side work, then the short tail panels
-    pnl = first_low;
-    for (; pnl < npanels; pnl++) {
-      const int j0 = pnl * NB, nb = L - j0 < NB ? L - j0 : NB, m = M - j0;
-      if (nb < NB || m < hr_min_rows) break;
-      ND4_TRY(hr.panel(j0, N, false, false));
-    }
-    ND4_TRY(hr.finish(N, false, true));
-    {
-      int pj0 = -1;
-      for (; pnl < npanels; pnl++) {
-        const int j0 = pnl * NB, nb = L - j0 < NB ? L - j0 : NB, m = M - j0;
-        const int wide0 = pj0 + 2 * NB, nwide = (pj0 >= 0 && wide0 < N) ? (N - wide0 + NB - 1) / NB : 0;
-        const int wc0 = j0 + nb;
-        const dim3 grid((unsigned)(1 + nwide), (unsigned)batch);
-        if (m <= 512)       hipLaunchKernelGGL(qr_panel_row_la<1>, grid, dim3(512), 0, h->stream, W, M, N, ld, sW, ws.V, ws.ldv, ws.sV, ws.T, ws.sT, ws.taus, ws.sTau, j0, nb, pj0 < 0 ? 0 : pj0, wide0, nwide, (double*)nullptr, 0l);
-        else if (m <= 1024) hipLaunchKernelGGL(qr_panel_row_la<2>, grid, dim3(512), 0, h->stream, W, M, N, ld, sW, ws.V, ws.ldv, ws.sV, ws.T, ws.sT, ws.taus, ws.sTau, j0, nb, pj0 < 0 ? 0 : pj0, wide0, nwide, (double*)nullptr, 0l);
-        else                hipLaunchKernelGGL(qr_panel_row_la<4>, grid, dim3(512), 0, h->stream, W, M, N, ld, sW, ws.V, ws.ldv, ws.sV, ws.T, ws.sT, ws.taus, ws.sTau, j0, nb, pj0 < 0 ? 0 : pj0, wide0, nwide, (double*)nullptr, 0l);
-        if (wc0 < N) {
-          const dim3 gn((unsigned)((m + 255) / 256), (unsigned)batch);
-          hipLaunchKernelGGL(qr_narrow_x, gn, dim3(256), 0, h->stream, W, M, N, ld, sW, ws.V, ws.ldv, ws.sV, j0, wc0, ws.Wp, ws.sWb);
-          hipLaunchKernelGGL(qr_narrow_apply, gn, dim3(256), 0, h->stream, W, M, N, ld, sW, ws.V, ws.ldv, ws.sV, ws.T, ws.sT, j0, wc0, ws.Wp, ws.sWb, 0);
-        }
-        pj0 = j0;
-      }
-      if (pj0 >= 0) {
-        const int j0 = (npanels - 1) * NB, nb = L - j0 < NB ? L - j0 : NB, wc0 = j0 + nb + NB;
-        if (wc0 < N)
-          hipLaunchKernelGGL(qr_update_blocks<512>, dim3((unsigned)((N - wc0 + NB - 1) / NB), (unsigned)batch), dim3(512), 0, h->stream,
-                             W, M, N, ld, sW, ws.V, ws.ldv, ws.sV, ws.T, ws.sT, j0, wc0);
-      }
-      ND4_HIP(hipGetLastError());
-    }
-    ND4_TRY(hr.dump_stamps());
-    // ---- Q = H_0 H_1 ... [I; 0] by the block reflectors of 128 columns, applied backwards to E (the blocks of the one-level part
-    // get their T now) ----
-    {
-      const long sQ = (long)M * Lq;
-      ND4_TRY(nd4_set_identity(h, M, Lq, Q, Lq, batch, sQ));
-      const int ncolsV = npanels * NB;
-      for (int mt = 0; mt < batch; mt++) {
-        for (int b = (int)nblocks - 1; b >= 0; b--) {
-          const int J = b * (int)nbo, nblk = ncolsV - J < (int)nbo ? ncolsV - J : (int)nbo, mJ = M - J, nq2 = Lq - J;
-          if (nq2 <= 0) continue;
-          const double* Vb = ws.V + (long)mt * ws.sV + (long)J * ws.ldv + J;
-          double* Tb = blkT + (size_t)b * nbo * nbo;
-          if (b * ppb >= first_low || batch > 1)               // (blocks of the tall part of a single matrix still hold their T)
-            ND4_TRY(wy_build_T(h, mJ, nblk, Vb, ws.ldv, ws.T + (long)mt * ws.sT + (long)b * ppb * NB * NB, NB, Tb, farG, farTmp));
-          double* Qs = Q + (long)mt * sQ + (long)J * Lq + J;
-          ND4_TRY(nd4_gemm(h, true, false, nblk, nq2, mJ, 1.0, Vb, ws.ldv, 0, Qs, Lq, 0, 0.0, farX, nq2, 0, 1));
-          ND4_TRY(nd4_gemm(h, false, false, nblk, nq2, nblk, 1.0, Tb, nblk, 0, farX, nq2, 0, 0.0, farW, nq2, 0, 1));
-          ND4_TRY(nd4_gemm(h, false, false, mJ, nq2, nblk, -1.0, Vb, ws.ldv, 0, farW, nq2, 0, 1.0, Qs, Lq, 0, 1));
-        }
-      }
-    }
-  } else {
-  // Two-level blocking for M > 2048 (round 3): every panel used to read-modify-write the whole trailing matrix with a K = 16 update
-  // (qr_vtc / qr_tw / rank-16 product). Now the panels of an outer block of 128 columns (ND4HIP_QR_OUTER) apply their reflectors to
-  // the block's own columns only; then the block's compact-WY factor T (128 x 128: the panels' factors on the diagonal,
-  // T12 = -T1 (V1^T V2) T2 level by level from ONE Gram matrix, the routine Q is formed with) takes all 128 reflectors to the rest at
-  // once on the tiled MFMA kernel: X = V^T C, W = T^T X, C -= V W (K = 128). M <= 2048 without look-ahead: one level.
-  static const int nbo_env = [] { const char* e = getenv("ND4HIP_QR_OUTER"); return e ? atoi(e) : 128; }();
-  // Batches beyond the look-ahead form (M <= 2048), round 4: the same two levels with outer blocks of 128 columns (64 below 256 columns; ND4HIP_QR_BATCH_OUTER:
-  // 32 | 48 | 64 | 128, 0 = off), everything batched — G = Vb^T Vb and the three products of the far update as strided GEMMs over the batch,
-  // the block's T by one small workgroup per matrix (wy_t_small) — and Q formed backwards block by block from the stored T's: the
-  // rank-16 updates of every panel over the whole trailing matrix (56 % of 1024 x 512^2) become rank-128 updates, an eighth of the traffic.
-  static const int qbo_set = [] { const char* e = getenv("ND4HIP_QR_BATCH_OUTER"); return e ? atoi(e) : -1; }();
-  const int qbo_env = qbo_set >= 0 ? qbo_set : (npanels >= 16 ? 128 : 64);          // 1024 x 512^2: 43.8 (off) -> 30.5 (64) -> 23.6 ms (128)
-  const bool batch2 = M <= 2048 && batch > 1 && (qbo_env == 32 || qbo_env == 48 || qbo_env == 64 || qbo_env == 128) && L % NB == 0 && npanels >= 2 * (qbo_env / NB);
-  const int ppb = (M > 2048 && nbo_env >= 32) ? nbo_env / NB : (batch2 ? qbo_env / NB : npanels);        // panels per outer block
-  double *farT = nullptr, *farG = nullptr, *farTmp = nullptr, *farX = nullptr, *farW = nullptr;
-  if (batch2) {
-    const size_t nbo = (size_t)ppb * NB, nblocks = (size_t)(npanels + ppb - 1) / ppb, wcols = (size_t)(N > Lq ? N : Lq);
-    void* q = nullptr;
-    ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)batch * (nblocks * nbo * nbo + nbo * nbo + 2 * nbo * wcols) + 64, &q));
-    btT = static_cast<double*>(q); btG = btT + (size_t)batch * nblocks * nbo * nbo; btX = btG + (size_t)batch * nbo * nbo; btW = btX + (size_t)batch * nbo * wcols;
-    bt_ppb = ppb; bt_sT = (long)(nblocks * nbo * nbo); bt_sX = (long)(nbo * wcols);
-    ND4_HIP(hipMemsetAsync(btT, 0, sizeof(double) * (size_t)batch * nblocks * nbo * nbo, h->stream));   // (the blocks below the diagonal 64 x 64 blocks stay zero)
-  } else
-  if (ppb < npanels) {
-    const size_t nbo = (size_t)ppb * NB;
-    void* q = nullptr;
-    ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (nbo * nbo * 2 + nbo * nbo / 2 + 16 + 2 * nbo * (size_t)N + 64), &q));
-    farT = static_cast<double*>(q); farG = farT + nbo * nbo; farTmp = farG + nbo * nbo; farX = farTmp + nbo * nbo / 2 + 16; farW = farX + nbo * (size_t)N;
+  if (pj0 >= 0) {   // the last panel was a thread-per-row one; wide input: its reflector on the columns right of the block the narrow launch has done
+    const int j0 = (npanels - 1) * NB, nb = L - j0 < NB ? L - j0 : NB, wc0 = j0 + nb + NB;
+    if (wc0 < N)
+      hipLaunchKernelGGL(qr_update_blocks<512>, dim3((unsigned)((N - wc0 + NB - 1) / NB), (unsigned)batch), dim3(512), 0, h->stream,
+                         W, M, N, ld, sW, ws.V, ws.ldv, ws.sV, ws.T, ws.sT, j0, wc0);
+    if (QT) hipLaunchKernelGGL(qr_update_blocks<512>, dim3((unsigned)nq, (unsigned)batch), dim3(512), 0, h->stream,
+                               QT, M, M, (long)M, sQT, ws.V, ws.ldv, ws.sV, ws.T, ws.sT, (npanels - 1) * NB, 0);
   }
-  for (int P0 = 0; P0 < npanels; P0 += ppb) {
-  const int pend = P0 + ppb < npanels ? P0 + ppb : npanels;
-  const int bend = pend < npanels ? pend * NB : N;                                // the block's reflectors reach the columns up to here at once
+  ND4_HIP(hipGetLastError());
+  return 0;
+}
+
+// QR_LOOKAHEAD: row-split panels while they are full and tall enough (one launch each, the previous reflector's side work riding
+// along on the trailing columns of W, then Q^T), then the thread-per-row look-ahead sequence
+static int qr_factor_lookahead(QrJob& j) {
+  if (j.QT) ND4_TRY(nd4_set_identity(j.h, j.M, j.M, j.QT, j.M, j.batch, j.sQT));
+  int pnl = 0;
+  if (j.use_hr) {
+    for (; pnl < j.npanels; pnl++) {
+      const int j0 = pnl * NB, nb = j.L - j0 < NB ? j.L - j0 : NB, m = j.M - j0;
+      if (nb < NB || m < HR_MIN_ROWS) break;
+      ND4_TRY(j.hr.panel(j0, j.N, j.QT != nullptr, false));
+    }
+    ND4_TRY(j.hr.finish(j.N, j.QT != nullptr, true));       // nothing pending afterwards: the remaining panels start afresh
+    ND4_TRY(j.hr.dump_stamps());
+  }
+  return qr_rows_lookahead(j, pnl);
+}
+
+// QR_TALL (round 3). The split register panels (two 8-column halves / four 4-column quarters per 16-column slot, each followed by its
+// own block-reflector launches and a Gram product) took ~165 us per slot, and every slot read-modify-wrote the whole trailing matrix.
+// Now: outer blocks of 128 columns; inside a block the row-split panels of qrh_* (no height limit: the rows are cut into 512-row
+// workgroups) with the previous reflector riding along on the block's own columns only; after the block its compact-WY factor T
+// (128 x 128: the panels' 16 x 16 factors on the diagonal, T12 = -T1 (V1^T V2) T2 level by level from one Gram matrix) takes all 128
+// reflectors to the columns right of it at once on the tiled MFMA kernel: X = V^T C, W = T^T X, C -= V W (K = 128). Once the panels
+// fit the register kernel (m <= 2048) the rest is factorised with one level, as a 2048-row problem. Q is formed afterwards by applying
+// the same block reflectors backwards (qr_form_q: 4/3 M^3 flop instead of the 6 M n^2 of the one-shot formation).
+static int qr_factor_tall(QrJob& j) {
+  const int M = j.M, N = j.N, L = j.L, npanels = j.npanels;
+  const int ppb = QR_OUTER / NB;
+  const size_t nbo = QR_OUTER, nblocks = (size_t)(npanels + ppb - 1) / ppb;
+  void* q = nullptr;
+  const int ncq = N > j.Lq ? N : j.Lq;
+  ND4_TRY(nd4_ws_alloc(j.h, sizeof(double) * (nblocks * nbo * nbo + nbo * nbo * 2 + nbo * nbo / 2 + 16 + 2 * nbo * (size_t)ncq + 64), &q));
+  j.bT = static_cast<double*>(q); j.bG = j.bT + nblocks * nbo * nbo; j.bTmp = j.bG + nbo * nbo;
+  j.bX = j.bTmp + nbo * nbo / 2 + 16; j.bW = j.bX + nbo * (size_t)ncq; j.ppb = ppb;
+  int pnl = 0;
+  j.first_low = npanels;
+  for (int P0 = 0; P0 < npanels && M - P0 * NB > 2048; P0 += ppb) {
+    const int pend = P0 + ppb < npanels ? P0 + ppb : npanels;
+    const int bend = pend < npanels ? pend * NB : N;
+    bool ok = true;
+    for (pnl = P0; pnl < pend; pnl++) {
+      const int j0 = pnl * NB, nb = L - j0 < NB ? L - j0 : NB;
+      if (nb < NB) { ok = false; break; }                   // (a ragged last panel: only when L is not a multiple of 16; handled below)
+      ND4_TRY(j.hr.panel(j0, bend, false, pnl == pend - 1));
+    }
+    if (!ok) break;
+    ND4_TRY(j.hr.finish(bend, false, false));                 // the block's last reflector has no column of the block left to reach
+    j.first_low = pend;
+    if (bend < N) {
+      const int J = P0 * NB, nblk = (pend - P0) * NB;
+      for (int mt = 0; mt < j.batch; mt++)
+        ND4_TRY(wy_block_update(j, mt, J, nblk, true, j.bT + (size_t)(P0 / ppb) * nbo * nbo, true, j.W + (long)mt * j.sW + (long)J * j.ld + bend, j.ld, N - bend));
+    }
+  }
+  // the rest as one level: multi-workgroup panels with all remaining columns as side work, then the short tail panels
+  for (pnl = j.first_low; pnl < npanels; pnl++) {
+    const int j0 = pnl * NB, nb = L - j0 < NB ? L - j0 : NB, m = M - j0;
+    if (nb < NB || m < HR_MIN_ROWS) break;
+    ND4_TRY(j.hr.panel(j0, N, false, false));
+  }
+  ND4_TRY(j.hr.finish(N, false, true));
+  ND4_TRY(qr_rows_lookahead(j, pnl));
+  return j.hr.dump_stamps();
+}
+
+// the panels [P0, pend) of an outer block, each followed by its reflector on the block's columns up to bend
+static int qr_block_panels(QrJob& j, int P0, int pend, int bend) {
+  nd4hip_handle* h = j.h;
+  const QrWs& ws = j.ws;
+  const int M = j.M, L = j.L, batch = j.batch;
+  double* W = j.W;
+  const long ld = j.ld, sW = j.sW;
   for (int pnl = P0; pnl < pend; pnl++) {
     const int j0 = pnl * NB, nb = L - j0 < NB ? L - j0 : NB, m = M - j0;
     if (m > 2048 && m <= 8192) {
@@ -2880,8 +2402,7 @@ int nd4_geqrf_q_ex(nd4hip_handle* h, int64_t batch64, int64_t M64, int64_t N64, 
     if (m <= 2048) {
       // batches of full panels: one workgroup per panel on the matrix cores (qr_batched_panel.h: V = Q - [S; 0], full T, like the
       // row-split panels of one matrix); short / narrow / odd-stride panels keep the thread-per-row Householder kernel
-      static const bool qrb_off = [] { const char* e = getenv("ND4HIP_QR_NO_BATCHED_MFMA"); return e && *e && *e != '0'; }();
-      if (!qrb_off && batch > 8 && nb == NB && m >= HR_MIN_ROWS && (ld & 1) == 0 && (ws.ldv & 1) == 0)
+      if (batch > QR_ROWSPLIT_MAX_BATCH && nb == NB && m >= HR_MIN_ROWS && (ld & 1) == 0 && (ws.ldv & 1) == 0)
         launch_panel_mfma<true>(h, batch, W, M, m, ld, sW, ws.V, ws.ldv, ws.sV, ws.T, ws.sT, ws.taus, ws.sTau, j0);
       else
         launch_panel_rows(h, batch, W, M, m, ld, sW, ws.V, ws.ldv, ws.sV, ws.T, ws.sT, ws.taus, ws.sTau, j0, nb);
@@ -2890,87 +2411,217 @@ int nd4_geqrf_q_ex(nd4hip_handle* h, int64_t batch64, int64_t M64, int64_t N64, 
     // trailing columns of the outer block: C <- H^T C = (I - V T^T V^T) C
     ND4_TRY(apply_block_reflector(h, ws, batch, M, j0, pnl, /*trans=*/1, W + (long)j0 * ld + j0 + nb, ld, sW, bend - j0 - nb));
   }
-  if (batch2) {                                                                    // the block's T for every member; its reflectors on everything right of it
+  return 0;
+}
+
+// QR_BATCHED (round 4): two levels with outer blocks of 128 columns (64 below 256 columns), everything batched — G = Vb^T Vb and the
+// three products of the far update as strided GEMMs over the batch, the block's T by one small workgroup per matrix (wy_t_small) — and
+// Q formed backwards block by block from the stored T's: the rank-16 updates of every panel over the whole trailing matrix (56 % of
+// 1024 x 512^2) become rank-128 updates, an eighth of the traffic.
+static int qr_factor_batched(QrJob& j) {
+  nd4hip_handle* h = j.h;
+  const QrWs& ws = j.ws;
+  const int M = j.M, N = j.N, npanels = j.npanels, batch = j.batch;
+  const int ppb = qr_batch_outer(npanels) / NB;
+  const size_t nbo = (size_t)ppb * NB, nblocks = (size_t)(npanels + ppb - 1) / ppb, wcols = (size_t)(N > j.Lq ? N : j.Lq);
+  void* q = nullptr;
+  ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)batch * (nblocks * nbo * nbo + nbo * nbo + 2 * nbo * wcols) + 64, &q));
+  j.bT = static_cast<double*>(q); j.bG = j.bT + (size_t)batch * nblocks * nbo * nbo; j.bX = j.bG + (size_t)batch * nbo * nbo; j.bW = j.bX + (size_t)batch * nbo * wcols;
+  j.ppb = ppb; j.bsT = (long)(nblocks * nbo * nbo); j.bsX = (long)(nbo * wcols);
+  ND4_HIP(hipMemsetAsync(j.bT, 0, sizeof(double) * (size_t)batch * nblocks * nbo * nbo, h->stream));   // (the blocks below the diagonal 64 x 64 blocks stay zero)
+  const long nbo2 = (long)nbo * nbo;
+  for (int P0 = 0; P0 < npanels; P0 += ppb) {
+    const int pend = P0 + ppb < npanels ? P0 + ppb : npanels;
+    const int bend = pend < npanels ? pend * NB : N;                              // the block's reflectors reach the columns up to here at once
+    ND4_TRY(qr_block_panels(j, P0, pend, bend));
+    // the block's T for every member; its reflectors on everything right of it
     const int J = P0 * NB, nblk = (pend - P0) * NB, mJ = M - J, far = N - bend;
-    const long nbo2 = (long)bt_ppb * NB * bt_ppb * NB;
     const double* Vb = ws.V + (long)J * ws.ldv + J;
-    double* Tb = btT + (long)(P0 / bt_ppb) * nbo2;
-    ND4_TRY(nd4_gemm(h, true, false, nblk, nblk, mJ, 1.0, Vb, ws.ldv, ws.sV, Vb, ws.ldv, ws.sV, 0.0, btG, nblk, nbo2, batch));
+    double* Tb = j.bT + (long)(P0 / ppb) * nbo2;
+    ND4_TRY(nd4_gemm(h, true, false, nblk, nblk, mJ, 1.0, Vb, ws.ldv, ws.sV, Vb, ws.ldv, ws.sV, 0.0, j.bG, nblk, nbo2, batch));
     {
       // T of the block: 64-column halves in LDS (wy_t_small), the coupling of the two halves of a 128-column block by two products
       const int n1 = nblk < 64 ? nblk : 64, n2 = nblk - n1;
-      hipLaunchKernelGGL(wy_t_small, dim3((unsigned)batch), dim3(256), 0, h->stream, ws.T + (long)P0 * NB * NB, ws.sT, btG, nblk, nbo2, Tb, nblk, bt_sT, n1);
+      hipLaunchKernelGGL(wy_t_small, dim3((unsigned)batch), dim3(256), 0, h->stream, ws.T + (long)P0 * NB * NB, ws.sT, j.bG, nblk, nbo2, Tb, nblk, j.bsT, n1);
       if (n2 > 0) {
-        hipLaunchKernelGGL(wy_t_small, dim3((unsigned)batch), dim3(256), 0, h->stream, ws.T + (long)(P0 + 4) * NB * NB, ws.sT, btG + (long)n1 * nblk + n1, nblk, nbo2,
-                           Tb + (long)n1 * nblk + n1, nblk, bt_sT, n2);
-        ND4_TRY(nd4_gemm(h, false, false, n1, n2, n2, 1.0, btG + n1, nblk, nbo2, Tb + (long)n1 * nblk + n1, nblk, bt_sT, 0.0, btX, n2, bt_sX, batch));
-        ND4_TRY(nd4_gemm(h, false, false, n1, n2, n1, -1.0, Tb, nblk, bt_sT, btX, n2, bt_sX, 0.0, Tb + n1, nblk, bt_sT, batch));
+        hipLaunchKernelGGL(wy_t_small, dim3((unsigned)batch), dim3(256), 0, h->stream, ws.T + (long)(P0 + 4) * NB * NB, ws.sT, j.bG + (long)n1 * nblk + n1, nblk, nbo2,
+                           Tb + (long)n1 * nblk + n1, nblk, j.bsT, n2);
+        ND4_TRY(nd4_gemm(h, false, false, n1, n2, n2, 1.0, j.bG + n1, nblk, nbo2, Tb + (long)n1 * nblk + n1, nblk, j.bsT, 0.0, j.bX, n2, j.bsX, batch));
+        ND4_TRY(nd4_gemm(h, false, false, n1, n2, n1, -1.0, Tb, nblk, j.bsT, j.bX, n2, j.bsX, 0.0, Tb + n1, nblk, j.bsT, batch));
       }
       ND4_HIP(hipGetLastError());
     }
-    if (far > 0) {
-      double* C = W + (long)J * ld + bend;
-      ND4_TRY(nd4_gemm(h, true, false, nblk, far, mJ, 1.0, Vb, ws.ldv, ws.sV, C, ld, sW, 0.0, btX, far, bt_sX, batch));
-      ND4_TRY(nd4_gemm(h, true, false, nblk, far, nblk, 1.0, Tb, nblk, bt_sT, btX, far, bt_sX, 0.0, btW, far, bt_sX, batch));
-      ND4_TRY(nd4_gemm(h, false, false, mJ, far, nblk, -1.0, Vb, ws.ldv, ws.sV, btW, far, bt_sX, 1.0, C, ld, sW, batch));
+    if (far > 0)
+      ND4_TRY(block_update(h, true, mJ, far, nblk, Vb, ws.ldv, ws.sV, Tb, j.bsT, j.W + (long)J * j.ld + bend, j.ld, j.sW, j.bX, j.bW, j.bsX, batch));
+  }
+  return 0;
+}
+
+// QR_BLOCKED. M > 2048 (round 3): every panel used to read-modify-write the whole trailing matrix with a K = 16 update (qr_vtc / qr_tw /
+// rank-16 product). Now the panels of an outer block of 128 columns apply their reflectors to the block's own columns only; then the
+// block's compact-WY factor T (128 x 128: the panels' factors on the diagonal, T12 = -T1 (V1^T V2) T2 level by level from ONE Gram
+// matrix, the routine Q is formed with) takes all 128 reflectors to the rest at once on the tiled MFMA kernel: X = V^T C, W = T^T X,
+// C -= V W (K = 128). M <= 2048: one level.
+static int qr_factor_blocked(QrJob& j) {
+  const int M = j.M, N = j.N, npanels = j.npanels;
+  const int ppb = M > 2048 ? QR_OUTER / NB : npanels;                             // panels per outer block
+  if (ppb < npanels) {
+    const size_t nbo = (size_t)ppb * NB;
+    void* q = nullptr;
+    ND4_TRY(nd4_ws_alloc(j.h, sizeof(double) * (nbo * nbo * 2 + nbo * nbo / 2 + 16 + 2 * nbo * (size_t)N + 64), &q));
+    j.bT = static_cast<double*>(q); j.bG = j.bT + nbo * nbo; j.bTmp = j.bG + nbo * nbo; j.bX = j.bTmp + nbo * nbo / 2 + 16; j.bW = j.bX + nbo * (size_t)N;
+  }
+  for (int P0 = 0; P0 < npanels; P0 += ppb) {
+    const int pend = P0 + ppb < npanels ? P0 + ppb : npanels;
+    const int bend = pend < npanels ? pend * NB : N;                              // the block's reflectors reach the columns up to here at once
+    ND4_TRY(qr_block_panels(j, P0, pend, bend));
+    if (bend < N) {                                                               // the block's 128 reflectors on everything right of it
+      const int J = P0 * NB, nblk = (pend - P0) * NB;
+      for (int mt = 0; mt < j.batch; mt++)
+        ND4_TRY(wy_block_update(j, mt, J, nblk, true, j.bT, true, j.W + (long)mt * j.sW + (long)J * j.ld + bend, j.ld, N - bend));
     }
-  } else
-  if (bend < N) {                                                                  // the block's 128 reflectors on everything right of it
-    const int J = P0 * NB, nblk = (pend - P0) * NB, mJ = M - J, far = N - bend;
+  }
+  return 0;
+}
+
+// Q = H_0 H_1 ... H_{p-1} [I; 0]
+static int qr_form_q(QrJob& j, double* Q) {
+  nd4hip_handle* h = j.h;
+  const QrWs& ws = j.ws;
+  const int M = j.M, Lq = j.Lq, npanels = j.npanels, batch = j.batch;
+  const long sQ = (long)M * Lq;
+  if (j.QT) return nd4_transpose(h, Lq, M, j.QT, M, Q, Lq, batch, j.sQT, sQ);          // Q = (first Lq rows of Q^T)^T
+  if (j.form != QR_TALL && batch <= QR_QT_MAX_BATCH && j.L >= 256) return form_q_compact_wy(h, ws, batch, M, Lq, npanels, Q, sQ);
+  ND4_TRY(nd4_set_identity(h, M, Lq, Q, Lq, batch, sQ));
+  if (j.form == QR_TALL) {
+    // the block reflectors of 128 columns applied backwards to E (the blocks of the one-level part get their T now; those of the tall
+    // part of a single matrix still hold theirs)
+    const int ncolsV = npanels * NB, nbo = QR_OUTER, nblocks = (npanels + j.ppb - 1) / j.ppb;
     for (int mt = 0; mt < batch; mt++) {
-      const double* Vb = ws.V + (long)mt * ws.sV + (long)J * ws.ldv + J;
-      double* C = W + (long)mt * sW + (long)J * ld + bend;
-      ND4_TRY(wy_build_T(h, mJ, nblk, Vb, ws.ldv, ws.T + (long)mt * ws.sT + (long)P0 * NB * NB, NB, farT, farG, farTmp));
-      ND4_TRY(nd4_gemm(h, true, false, nblk, far, mJ, 1.0, Vb, ws.ldv, 0, C, ld, 0, 0.0, farX, far, 0, 1));
-      ND4_TRY(nd4_gemm(h, true, false, nblk, far, nblk, 1.0, farT, nblk, 0, farX, far, 0, 0.0, farW, far, 0, 1));
-      ND4_TRY(nd4_gemm(h, false, false, mJ, far, nblk, -1.0, Vb, ws.ldv, 0, farW, far, 0, 1.0, C, ld, 0, 1));
+      for (int b = nblocks - 1; b >= 0; b--) {
+        const int J = b * nbo, nblk = ncolsV - J < nbo ? ncolsV - J : nbo, nq2 = Lq - J;
+        if (nq2 <= 0) continue;
+        ND4_TRY(wy_block_update(j, mt, J, nblk, b * j.ppb >= j.first_low || batch > 1, j.bT + (size_t)b * nbo * nbo, false,
+                                Q + (long)mt * sQ + (long)J * Lq + J, Lq, nq2));
+      }
+    }
+  } else if (j.form == QR_BATCHED) {
+    // Q <- (I - Vb Tb Vb^T) Q block by block, backwards, with the blocks' stored factors
+    const long nbo2 = (long)j.ppb * NB * j.ppb * NB;
+    for (int P0 = ((npanels - 1) / j.ppb) * j.ppb; P0 >= 0; P0 -= j.ppb) {
+      const int pend = P0 + j.ppb < npanels ? P0 + j.ppb : npanels;
+      const int J = P0 * NB, nblk = (pend - P0) * NB, mJ = M - J, nq2 = Lq - J;
+      if (nq2 <= 0) continue;
+      ND4_TRY(block_update(h, false, mJ, nq2, nblk, ws.V + (long)J * ws.ldv + J, ws.ldv, ws.sV, j.bT + (long)(P0 / j.ppb) * nbo2, j.bsT,
+                           Q + (long)J * Lq + J, Lq, sQ, j.bX, j.bW, j.bsX, batch));
+    }
+  } else {
+    for (int pnl = npanels - 1; pnl >= 0; pnl--) {
+      const int j0 = pnl * NB;
+      ND4_TRY(apply_block_reflector(h, ws, batch, M, j0, pnl, /*trans=*/0, Q + (long)j0 * Lq + j0, Lq, sQ, Lq - j0));
     }
   }
+  return 0;
+}
+
+int nd4_geqrf_q_ex(nd4hip_handle* h, int64_t batch64, int64_t M64, int64_t N64, const double* A, double* Q, double* R, bool full) {
+  ND4_CHECK_ARG(M64 < (1ll << 30) && N64 < (1ll << 30) && batch64 < 65536, "nd4_geqrf_q: extent out of range");
+  const int M = (int)M64, N = (int)N64, batch = (int)batch64;
+  const QrForm form = qr_choose(batch, M, N, full);
+  if (form == QR_TSQR) return geqrf_tsqr(h, batch, M, N, A, Q, R);
+  const int L = M < N ? M : N;
+  const int npanels = (L + NB - 1) / NB;
+  const bool tall = M > N;
+  const int Lq = (full && tall) ? M : L;                    // columns of Q
+  const int Lr = (full && tall) ? M : L;                    // rows of R
+
+  // ---- workspace carve-up (all per-matrix blocks are multiples of 2 doubles -> 16-B aligned) ----
+  QrJob j;
+  j.h = h; j.form = form; j.batch = batch; j.M = M; j.N = N; j.L = L; j.npanels = npanels; j.Lq = Lq;
+  QrWs& ws = j.ws;
+  ws.ldv = ((L + NB - 1) / NB) * NB;                        // Vall: M x ldv, zero above each panel
+  ws.sV = (long)M * ws.ldv;
+  ws.sT = (long)npanels * NB * NB;
+  ws.sTau = ws.ldv;
+  const int ncols = (N > Lq ? N : Lq);
+  ws.ldw = ((ncols + 1) / 2) * 2;
+  ws.nchunks_max = (M + VTC_ROWS - 1) / VTC_ROWS;
+  ws.sChunk = (long)NB * ws.ldw;
+  ws.sWb = ws.sChunk * ws.nchunks_max;
+  ws.sW2 = ws.sChunk;
+  const long sWork = tall ? (long)M * N : 0;
+  const bool use_qt = form == QR_LOOKAHEAD && batch <= QR_QT_MAX_BATCH && L >= 256;      // Q^T accumulated in the shadow of the panels
+  j.use_hr = (form == QR_LOOKAHEAD && batch <= QR_ROWSPLIT_MAX_BATCH) || form == QR_TALL;   // multi-workgroup panels (CholeskyQR2 + compact orthogonal completion)
+  j.sQT = use_qt ? (long)M * M : 0;
+  const int hr_parts = (M + NB + 511) / 512 + 1;
+  const long sXch = j.use_hr ? (long)hr_parts * QX_ROW_SLOT : 0;                           // QX_ROW_SLOT tagged words per row workgroup (qrh_bc)
+  const long hr_rcs = (M + 511) / 512;
+  const long sXs = j.use_hr ? ((N + NB - 1) / NB + (use_qt ? (M + NB - 1) / NB : 0)) * hr_rcs * 256 : 0;   // side work: [column block][row chunk][256]
+  const long sXsx = 2 * sXs;                                 // fused side work: 512 tagged words per (column block, row chunk)
+  size_t doubles = (size_t)batch * (ws.sV + 2 * ws.sT + ws.sTau + ws.sWb + ws.sW2 + sWork + j.sQT + sXch + sXs + sXsx);
+  size_t bytes = doubles * sizeof(double) + ((size_t)batch * L + 2) * sizeof(int) + (size_t)batch * 8 + (size_t)batch * sizeof(int) + 64;
+  void* p = nullptr;
+  Nd4WsScope scope(h);
+  ND4_TRY(nd4_ws_alloc(h, bytes, &p));
+  double* d = static_cast<double*>(p);
+  ws.V = d; d += (size_t)batch * ws.sV;
+  ws.T = d; d += (size_t)batch * ws.sT;
+  ws.Tside = d; d += (size_t)batch * ws.sT;                 // diagonal blocks of slots factorised in parts (tall panels)
+  ws.taus = d; d += (size_t)batch * ws.sTau;
+  ws.Wp = d; d += (size_t)batch * ws.sWb;
+  ws.W2 = d; d += (size_t)batch * ws.sW2;
+  ws.work = tall ? d : nullptr; d += (size_t)batch * sWork;
+  j.QT = use_qt ? d : nullptr; d += (size_t)batch * j.sQT;
+  unsigned long long* hrXch = reinterpret_cast<unsigned long long*>(d); d += (size_t)batch * sXch;
+  double* hrXs = d; d += (size_t)batch * sXs;
+  unsigned long long* hrXsx = reinterpret_cast<unsigned long long*>(d); d += (size_t)batch * sXsx;
+  ws.flips = reinterpret_cast<int*>(d);
+
+  // working matrix: R's buffer when it has A's shape (M <= N), a workspace copy when tall
+  j.W = tall ? ws.work : R;
+  j.ld = N; j.sW = (long)M * N;
+  double* W = j.W;
+  const long sW = j.sW;
+  unsigned long long* exps = reinterpret_cast<unsigned long long*>(ws.flips + (((size_t)batch * L + 1) & ~size_t(1)));   // max|a| bits per matrix
+  int* hrFlag = reinterpret_cast<int*>(exps + batch);
+  ND4_HIP(hipMemsetAsync(exps, 0, sizeof(unsigned long long) * batch, h->stream));
+  {
+    long nblk = (sW + 256 * 16 - 1) / (256 * 16); if (nblk > 2048) nblk = 2048;
+    hipLaunchKernelGGL(qr_amax, dim3((unsigned)nblk, (unsigned)batch), dim3(256), 0, h->stream, A, sW, exps);
   }
+  hipLaunchKernelGGL(qr_scale_apply, dim3((unsigned)((sW + 255) / 256), (unsigned)batch), dim3(256), 0, h->stream, A, W, sW, exps, -1);
+  ND4_HIP(hipMemsetAsync(ws.V, 0, sizeof(double) * (size_t)batch * ws.sV, h->stream));
+  if (M > 2048) ND4_HIP(hipMemsetAsync(ws.Tside, 0, sizeof(double) * (size_t)batch * ws.sT, h->stream));
+  if (j.use_hr) {
+    ND4_TRY(j.hr.init(h, batch, W, M, N, j.ld, sW, ws.V, ws.ldv, ws.sV, ws.T, ws.sT, ws.taus, ws.sTau, hrFlag, hrXch, sXch,
+                      ws.Wp, ws.sWb, j.QT, j.sQT, hrXs, sXs, hrXsx, sXsx, (int)hr_rcs));
+    static const bool want_stamps = [] { const char* e = getenv("ND4HIP_QR_STAMPS"); return e && *e && *e != '0'; }();
+    QrhP& P = j.hr.P;
+    if (want_stamps) { ND4_HIP(hipMalloc(&P.stamps, sizeof(long long) * 8 * 3 * (npanels + 1))); ND4_HIP(hipMemset(P.stamps, 0, sizeof(long long) * 8 * 3 * (npanels + 1))); }
+  }
+
+  // ---- factorisation: panels left to right ----
+  switch (form) {
+    case QR_LOOKAHEAD: ND4_TRY(qr_factor_lookahead(j)); break;
+    case QR_TALL:      ND4_TRY(qr_factor_tall(j)); ND4_TRY(qr_form_q(j, Q)); break;   // (Q right away, ahead of R)
+    case QR_BATCHED:   ND4_TRY(qr_factor_batched(j)); break;
+    default:           ND4_TRY(qr_factor_blocked(j)); break;
   }
 
   // ---- R out (tall: top N x N of the work matrix; else already in place, lower part zeroed by the panels) ----
   if (tall) {
     if (Lr > L) ND4_HIP(hipMemsetAsync(R, 0, sizeof(double) * (size_t)batch * Lr * N, h->stream));
-    ND4_TRY(nd4_copy_matrix(h, L, N, W, ld, R, N, batch, sW, (long)Lr * N));
+    ND4_TRY(nd4_copy_matrix(h, L, N, W, j.ld, R, N, batch, sW, (long)Lr * N));
   }
 
   {   // undo the power-of-two normalisation on R (exact; a no-op when the exponent is 0)
     const long nR = (long)Lr * N;
     hipLaunchKernelGGL(qr_scale_apply, dim3((unsigned)((nR + 255) / 256), (unsigned)batch), dim3(256), 0, h->stream, R, R, nR, exps, +1);
   }
-  // ---- Q = H_0 H_1 ... H_{p-1} [I; 0]: block reflectors applied backwards ----
-  const long sQ = (long)M * Lq;
-  if (hr_tall) {
-    // formed above from the block reflectors
-  } else if (use_qt) {
-    ND4_TRY(nd4_transpose(h, Lq, M, QT, M, Q, Lq, batch, sQT, sQ));        // Q = (first Lq rows of Q^T)^T
-  } else if (!wy_off && batch <= 4 && L >= 256) {
-    ND4_TRY(form_q_compact_wy(h, ws, batch, M, Lq, npanels, Q, sQ));
-  } else if (btT != nullptr) {
-    // batches, two-level: Q <- (I - Vb Tb Vb^T) Q block by block, backwards, with the blocks' stored factors
-    ND4_TRY(nd4_set_identity(h, M, Lq, Q, Lq, batch, sQ));
-    const long nbo2 = (long)bt_ppb * NB * bt_ppb * NB;
-    for (int P0 = ((npanels - 1) / bt_ppb) * bt_ppb; P0 >= 0; P0 -= bt_ppb) {
-      const int pend = P0 + bt_ppb < npanels ? P0 + bt_ppb : npanels;
-      const int J = P0 * NB, nblk = (pend - P0) * NB, mJ = M - J, nq2 = Lq - J;
-      if (nq2 <= 0) continue;
-      const double* Vb = ws.V + (long)J * ws.ldv + J;
-      const double* Tb = btT + (long)(P0 / bt_ppb) * nbo2;
-      double* Qs = Q + (long)J * Lq + J;
-      ND4_TRY(nd4_gemm(h, true, false, nblk, nq2, mJ, 1.0, Vb, ws.ldv, ws.sV, Qs, Lq, sQ, 0.0, btX, nq2, bt_sX, batch));
-      ND4_TRY(nd4_gemm(h, false, false, nblk, nq2, nblk, 1.0, Tb, nblk, bt_sT, btX, nq2, bt_sX, 0.0, btW, nq2, bt_sX, batch));
-      ND4_TRY(nd4_gemm(h, false, false, mJ, nq2, nblk, -1.0, Vb, ws.ldv, ws.sV, btW, nq2, bt_sX, 1.0, Qs, Lq, sQ, batch));
-    }
-  } else {
-    ND4_TRY(nd4_set_identity(h, M, Lq, Q, Lq, batch, sQ));
-    for (int pnl = npanels - 1; pnl >= 0; pnl--) {
-      const int j0 = pnl * NB;
-      ND4_TRY(apply_block_reflector(h, ws, batch, M, j0, pnl, /*trans=*/0, Q + (long)j0 * Lq + j0, Lq, sQ, Lq - j0));
-    }
-  }
+  if (form != QR_TALL) ND4_TRY(qr_form_q(j, Q));
 
   // ---- reference sign convention ----
+  const long sQ = (long)M * Lq;
   return nd4_givens_signs(h, batch, M, L, N, tall && !full, Q, Lq, sQ, R, N, (long)Lr * N, ws.taus, ws.sTau, ws.flips);
 }
 
@@ -2983,35 +2634,21 @@ int nd4_geqr2_panel(nd4hip_handle* h, int batch, int M, double* A, double* V, do
   Nd4WsScope scope(h);
   void* p = nullptr;
   const int parts = (M + NB + 511) / 512 + 1;
-  ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)batch * (NB + (parts + 1) * 256 + parts * QX_ROW_SLOT + 256 + 2) + 64, &p));
+  ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)batch * (NB + parts * QX_ROW_SLOT + 2) + 64, &p));
   double* taus = static_cast<double*>(p);
   const long sW = (long)M * NB;
   const int nb = M < NB ? M : NB;
-  static const bool hr_off = [] { const char* e = getenv("ND4HIP_QR_NO_HR"); return e && *e && *e != '0'; }();
-  if (!hr_off && batch <= 8 && M >= HR_MIN_ROWS) {
-    // few panels: the row-split form (three launches, the rows over workgroups of 512): V = Q - [S; 0] and T = K of qrh_reconstruct
+  if (batch <= QR_ROWSPLIT_MAX_BATCH && M >= HR_MIN_ROWS) {
+    // few panels: the row-split form (one launch, the rows over workgroups of 512): V = Q - [S; 0] and T = K of qrh_bc
     QrhHost hr;
-    hr.h = h; hr.batch = batch; hr.nq = 0; hr.V = V; hr.T = T; hr.ldv = NB; hr.sV = sW; hr.sT = NB * NB;
-    QrhP& P = hr.P;
-    double* d = taus + (size_t)batch * NB;
-    P.Wm = A; P.M = M; P.N = NB; P.ld = NB; P.strideW = sW; P.Vall = V; P.ldv = NB; P.strideV = sW; P.Tall = T; P.strideT = NB * NB;
-    P.taus = taus; P.strideTau = NB; P.Xp = nullptr; P.strideXp = 0;
-    P.Gp = d; P.strideGp = (long)(parts + 1) * 256; d += (size_t)batch * P.strideGp;
-    P.G2p = d; P.strideG2 = (long)parts * QX_ROW_SLOT; d += (size_t)batch * P.strideG2;
-    P.Xch = reinterpret_cast<unsigned long long*>(P.G2p); P.strideXch = P.strideG2; P.na_shift = 0;
-    P.Xsx = nullptr; P.strideXsx = 0; P.rcs_max = 1;
-    ND4_HIP(hipMemsetAsync(P.G2p, 0, sizeof(double) * (size_t)batch * P.strideG2, h->stream));
-    P.R1 = d; d += (size_t)batch * 256;
-    P.flag = reinterpret_cast<int*>(d);
-    ND4_HIP(hipMemsetAsync(P.flag, 0, sizeof(int) * (size_t)batch, h->stream));   // (as in the main path: never read before written today, but not by accident)
-    P.QT = nullptr; P.strideQT = 0; P.nxp = 0; P.Xs = nullptr; P.strideXs = 0;
-    P.nseg = 0; P.wide0 = 0; P.nrc = 1; P.nnw = 0; P.nqb = 0; P.skip_x = 1; P.j0 = 0; P.pj0 = -1; P.nrow = 0; P.ngp = 0;
-    P.stamps = nullptr; P.stamp_slot = 0; P.status = h->xstat; { const int dp = nd4_test_drop_panel(); P.drop_tag = dp >= 0 ? dp + 1 : -1; }
+    const long sXch = (long)parts * QX_ROW_SLOT;
+    unsigned long long* Xch = reinterpret_cast<unsigned long long*>(taus + (size_t)batch * NB);
+    ND4_TRY(hr.init(h, batch, A, M, NB, NB, sW, V, NB, sW, T, NB * NB, taus, NB, reinterpret_cast<int*>(Xch + (size_t)batch * sXch), Xch, sXch,
+                    nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, 1));
     ND4_TRY(hr.panel(0, NB, false, true));
     return 0;
   }
-  static const bool qrb_off = [] { const char* e = getenv("ND4HIP_QR_NO_BATCHED_MFMA"); return e && *e && *e != '0'; }();
-  if (!qrb_off && nb == NB && M >= HR_MIN_ROWS) {
+  if (nb == NB && M >= HR_MIN_ROWS) {
     // a batch of panels: one workgroup per panel on the matrix cores (qr_batched_panel.h); V = Q - [S; 0], T = K as above
     static const bool stamps_on = [] { const char* e = getenv("ND4HIP_QRB_STAMPS"); return e && *e && *e != '0'; }();
     long long* stamps = nullptr;
