@@ -245,6 +245,46 @@ int nd4hip_dqp3ls_batched    (nd4hip_handle* h, int64_t batch, int64_t N, int64_
                               const double* Q, int64_t strideQ, const double* R, int64_t strideR, const int32_t* P, int64_t strideP,
                               const double* Y, int64_t strideY, double* X, int32_t* rank);
 
+/* ---- srrqr_decomp_full: replaces src/la/srrqr.js:58-802 (Gu-Eisenstat strong rank-revealing QR) ---------------------------
+ * A [batch,M,N] -> Q [batch,M,M], R [batch,M,N], P [batch,N] int32 with A[:, P] = Q R, rank [batch] int32. P and the rank are
+ * decided as the reference decides them: A is scaled by ||A||_F (a zero matrix by 1), the rank is found by a binary search over
+ * k, and at each checkpoint the column swap with the first maximum F_ij = hypot((A_k^-1 B_k)_ij, ||row i of A_k^-1|| ||column
+ * j of C_k||) (row-major order) is made while F > dtol, with the reference's cyclic shift, so P matches it position for
+ * position. dtol >= 1 (the reference's default is 1.01); ztol < 0 selects the default sqrt(eps) ||A/||A||_F||_F max(M,N),
+ * ztol >= 0 is used as given, in units of ||A||_F. Q and R are those of dgeqrf_full on A[:, P]: R[:r, :] and Q[:, :r] equal
+ * the reference's up to the sign of each row of R (column of Q), R[r:, r:] is triangular (the reference leaves that block
+ * untriangularised; its norm is <= ztol ||A||_F either way) and the columns r.. of Q are an orthonormal completion.
+ * The _dev form leaves rank -1 / -3 for an ||A||_F that is Infinity / NaN and -2 for a matrix that hit the static swap cap; the
+ * host form returns ND4HIP_ERR_ARG with the reference's 'Assertion failed: Infinity' / 'Assertion failed: NaN', resp.
+ * ND4HIP_ERR_NOCONV. dtol < 1, NaN or Infinity and ztol NaN or Infinity are ND4HIP_ERR_ARG with the reference's messages.
+ * One workgroup per matrix decides (csrc/srrqr.hip); nothing waits on another workgroup. Deterministic: a second call gives
+ * the same bits. */
+int nd4hip_dsrrqr_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double dtol, double ztol,
+                              double* Q, double* R, int32_t* P, int32_t* rank);
+int nd4hip_dsrrqr_batched    (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double dtol, double ztol,
+                              double* Q, double* R, int32_t* P, int32_t* rank);
+
+/* ---- urv_decomp_full / urv_lstsq: replace src/la/urv.js:100-135 / :138-323 (complete orthogonal decomposition) ------------
+ * durv: A [batch,M,N] -> U [batch,M,M] (srrqr's Q), R [batch,M,N] = [[T,0],[0,0]] with T [r,r] upper triangular and exact zeros
+ * elsewhere, V [batch,N,N] orthogonal, rank [batch] (srrqr's r, default tolerances), A = U R V. T and V[:r] equal the reference's
+ * up to signs (a sign per row of T's rows / V's rows and per column of T); V[r:] is an orthonormal completion; r == N gives the
+ * reference's permutation V[i, P[i]] = 1 exactly. The r x N trapezoid is reduced from the right by the full QR of its reversed
+ * transpose (csrc/srrqr.hip: urv_pack / urv_unpack). Error markers and codes as dsrrqr (the host form: 'Assertion failed: Infinity' / 'NaN').
+ * durvls: U [I,J], R [J,K], V [K,L], rank, Y [I,Jc] -> X [batch,L,Jc] = V[:r]^T T^-1 (U^T Y)[:r] with T = R[:r,:r] and r each
+ * matrix's own rank (clamped to [0, min(J,K)]): the minimum-norm least-squares solution. Strides in elements, 0 = broadcast
+ * (strideRank 0 or 1). J <= I and K <= L are required ('Assertion failed.', urv.js:263-264). The _dev form makes no
+ * device-to-host copy. */
+int nd4hip_durv_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* U, double* R, double* V,
+                            int32_t* rank);
+int nd4hip_durv_batched    (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* U, double* R, double* V,
+                            int32_t* rank);
+int nd4hip_durvls_batched_dev(nd4hip_handle* h, int64_t batch, int64_t I, int64_t J, int64_t K, int64_t L, int64_t Jc,
+                              const double* U, int64_t strideU, const double* R, int64_t strideR, const double* V, int64_t strideV,
+                              const int32_t* rank, int64_t strideRank, const double* Y, int64_t strideY, double* X);
+int nd4hip_durvls_batched    (nd4hip_handle* h, int64_t batch, int64_t I, int64_t J, int64_t K, int64_t L, int64_t Jc,
+                              const double* U, int64_t strideU, const double* R, int64_t strideR, const double* V, int64_t strideV,
+                              const int32_t* rank, int64_t strideRank, const double* Y, int64_t strideY, double* X);
+
 /* ---- svd_decomp: replaces the output contract of src/la/svd.js:25 (= svd_dc.js:883-932) ----------
  * A [batch,M,N] -> U [batch,M,L], sv [batch,L] (>= 0, descending), V [batch,L,N] (rows = right
  * singular vectors), L = min(M,N); one-sided Jacobi with the reference's Jacobi post-processing

@@ -71,6 +71,16 @@ SIGNATURES = {
     "nd4hip_dgeqp3_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, ctypes.c_void_p]),
     "nd4hip_dgeqp3_full_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, ctypes.c_void_p]),
     "nd4hip_dgeqp3_full_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, ctypes.c_void_p]),
+    "nd4hip_dsrrqr_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, ctypes.c_double, ctypes.c_double, c_dp, c_dp,
+                                          ctypes.c_void_p, ctypes.c_void_p]),
+    "nd4hip_dsrrqr_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, ctypes.c_double, ctypes.c_double, c_dp, c_dp,
+                                      ctypes.c_void_p, ctypes.c_void_p]),
+    "nd4hip_durv_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, ctypes.c_void_p]),
+    "nd4hip_durv_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, ctypes.c_void_p]),
+    "nd4hip_durvls_batched_dev": (c_int, [ctypes.c_void_p] + [c_i64] * 6 + [c_dp, c_i64, c_dp, c_i64, c_dp, c_i64, ctypes.c_void_p, c_i64,
+                                                                            c_dp, c_i64, c_dp]),
+    "nd4hip_durvls_batched": (c_int, [ctypes.c_void_p] + [c_i64] * 6 + [c_dp, c_i64, c_dp, c_i64, c_dp, c_i64, ctypes.c_void_p, c_i64,
+                                                                        c_dp, c_i64, c_dp]),
     "nd4hip_dqp3rank_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, ctypes.c_void_p]),
     "nd4hip_dqp3rank_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, ctypes.c_void_p]),
     "nd4hip_dqp3ls_batched_dev": (c_int, [ctypes.c_void_p] + [c_i64] * 5 + [c_dp, c_i64, c_dp, c_i64, ctypes.c_void_p, c_i64, c_dp, c_i64,

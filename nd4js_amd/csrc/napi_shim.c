@@ -55,6 +55,10 @@ static int (*p_svd_info)(nd4hip_handle*, int*, unsigned long long*, double*);
 static qrls_fn p_dqrls[2];
 static int (*p_dgeqp3[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, double*, double*, int32_t*);
 static int (*p_dgeqp3_full[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, double*, double*, int32_t*);
+static int (*p_dsrrqr[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, double, double, double*, double*, int32_t*, int32_t*);
+static int (*p_durv[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, double*, double*, double*, int32_t*);
+static int (*p_durvls[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t,
+                          const double*, int64_t, const int32_t*, int64_t, const double*, int64_t, double*);
 static int (*p_dqp3rank[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, int32_t*);
 static int (*p_dqp3ls[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t,
                           const int32_t*, int64_t, const double*, int64_t, double*, int32_t*);
@@ -121,6 +125,9 @@ static int load_library(void) {
   SYM2(p_dgeqp3, "nd4hip_dgeqp3_batched");
   SYM2(p_dgeqp3_full, "nd4hip_dgeqp3_full_batched");
   SYM2(p_dqp3rank, "nd4hip_dqp3rank_batched");
+  SYM2(p_dsrrqr, "nd4hip_dsrrqr_batched");
+  SYM2(p_durv, "nd4hip_durv_batched");
+  SYM2(p_durvls, "nd4hip_durvls_batched");
   SYM2(p_dqp3ls, "nd4hip_dqp3ls_batched");
   SYM2(p_dsvdls, "nd4hip_dsvdls_batched");
   SYM2(p_dtrsm, "nd4hip_dtrsm_batched");
@@ -436,6 +443,51 @@ static napi_value geqp3_common(napi_env env, napi_callback_info info, int full) 
 }
 static napi_value js_dgeqp3(napi_env env, napi_callback_info info) { return geqp3_common(env, info, 0); }
 static napi_value js_dgeqp3_full(napi_env env, napi_callback_info info) { return geqp3_common(env, info, 1); }
+/* dsrrqr_batched(batch, M, N, A, dtol, ztol, Q, R, P, rank)   (srrqr_decomp_full, srrqr.js:58-802; ztol < 0: the default) */
+static napi_value js_dsrrqr(napi_env env, napi_callback_info info) {
+  ARGS(10, "dsrrqr_batched");
+  int64_t batch, M, N; double dtol, ztol; opnd A, Q, R, P, r;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &M) || get_i64(env, a[2], &N) || F64(3, A) ||
+      napi_get_value_double(env, a[4], &dtol) != napi_ok || napi_get_value_double(env, a[5], &ztol) != napi_ok ||
+      F64(6, Q) || F64(7, R) || I32(8, P) || I32(9, r)) return NULL;
+  NEED(batch >= 0 && M >= 0 && N >= 0 && (size_t)(batch * M * N) <= A.len && (size_t)(batch * M * M) <= Q.len &&
+       (size_t)(batch * M * N) <= R.len && (size_t)(batch * N) <= P.len && (size_t)batch <= r.len, "dsrrqr_batched: buffer too small");
+  SAME_SIDE(A.dev == Q.dev && Q.dev == R.dev && R.dev == P.dev && P.dev == r.dev, "dsrrqr_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dsrrqr[A.dev](g_handle, batch, M, N, (const double*)A.p, dtol, ztol, (double*)Q.p, (double*)R.p, (int32_t*)P.p, (int32_t*)r.p));
+  return NULL;
+}
+/* durv_batched(batch, M, N, A, U, R, V, rank)   (urv_decomp_full, urv.js:100-135) */
+static napi_value js_durv(napi_env env, napi_callback_info info) {
+  ARGS(8, "durv_batched");
+  int64_t batch, M, N; opnd A, U, R, V, r;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &M) || get_i64(env, a[2], &N) || F64(3, A) || F64(4, U) || F64(5, R) || F64(6, V) ||
+      I32(7, r)) return NULL;
+  NEED(batch >= 0 && M >= 0 && N >= 0 && (size_t)(batch * M * N) <= A.len && (size_t)(batch * M * M) <= U.len && (size_t)(batch * M * N) <= R.len &&
+       (size_t)(batch * N * N) <= V.len && (size_t)batch <= r.len, "durv_batched: buffer too small");
+  SAME_SIDE(A.dev == U.dev && U.dev == R.dev && R.dev == V.dev && V.dev == r.dev, "durv_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_durv[A.dev](g_handle, batch, M, N, (const double*)A.p, (double*)U.p, (double*)R.p, (double*)V.p, (int32_t*)r.p));
+  return NULL;
+}
+/* durvls_batched(batch, I, J, K, L, Jc, U, sU, R, sR, V, sV, rank, sRank, Y, sY, X)   (urv_lstsq, urv.js:138-323) */
+static napi_value js_durvls(napi_env env, napi_callback_info info) {
+  ARGS(17, "durvls_batched");
+  int64_t batch, I, J, K, L, Jc, sU, sR, sV, sK, sY; opnd U, R, V, k, Y, X;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &I) || get_i64(env, a[2], &J) || get_i64(env, a[3], &K) || get_i64(env, a[4], &L) ||
+      get_i64(env, a[5], &Jc) || F64(6, U) || get_i64(env, a[7], &sU) || F64(8, R) || get_i64(env, a[9], &sR) || F64(10, V) ||
+      get_i64(env, a[11], &sV) || I32(12, k) || get_i64(env, a[13], &sK) || F64(14, Y) || get_i64(env, a[15], &sY) || F64(16, X)) return NULL;
+  NEED(batch >= 0 && I >= 0 && J >= 0 && K >= 0 && L >= 0 && Jc >= 0 && sU >= 0 && sR >= 0 && sV >= 0 && sK >= 0 && sY >= 0,
+       "durvls_batched: negative extent");
+  NEED(batch == 0 || ((size_t)((batch - 1) * sU + I * J) <= U.len && (size_t)((batch - 1) * sR + J * K) <= R.len &&
+                      (size_t)((batch - 1) * sV + K * L) <= V.len && (size_t)((batch - 1) * sK + 1) <= k.len &&
+                      (size_t)((batch - 1) * sY + I * Jc) <= Y.len && (size_t)(batch * L * Jc) <= X.len), "durvls_batched: buffer too small");
+  SAME_SIDE(U.dev == R.dev && R.dev == V.dev && V.dev == k.dev && k.dev == Y.dev && Y.dev == X.dev, "durvls_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_durvls[X.dev](g_handle, batch, I, J, K, L, Jc, (const double*)U.p, sU, (const double*)R.p, sR, (const double*)V.p, sV,
+                          (const int32_t*)k.p, sK, (const double*)Y.p, sY, (double*)X.p));
+  return NULL;
+}
 /* dqp3rank_batched(batch, M, N, R, rank)   (rrqr_rank, rrqr.js:398-414; host form throws the reference's message) */
 static napi_value js_dqp3rank(napi_env env, napi_callback_info info) {
   ARGS(5, "dqp3rank_batched");
@@ -655,6 +707,9 @@ static napi_value init(napi_env env, napi_value exports) {
     {"dgeqp3_batched", NULL, js_dgeqp3, NULL, NULL, NULL, napi_default, NULL},
     {"dgeqp3_full_batched", NULL, js_dgeqp3_full, NULL, NULL, NULL, napi_default, NULL},
     {"dqp3rank_batched", NULL, js_dqp3rank, NULL, NULL, NULL, napi_default, NULL},
+    {"dsrrqr_batched", NULL, js_dsrrqr, NULL, NULL, NULL, napi_default, NULL},
+    {"durv_batched", NULL, js_durv, NULL, NULL, NULL, napi_default, NULL},
+    {"durvls_batched", NULL, js_durvls, NULL, NULL, NULL, napi_default, NULL},
     {"dqp3ls_batched", NULL, js_dqp3ls, NULL, NULL, NULL, napi_default, NULL},
     {"dtrsm_batched", NULL, js_dtrsm, NULL, NULL, NULL, napi_default, NULL},
     {"dpotrf_batched", NULL, js_dpotrf, NULL, NULL, NULL, napi_default, NULL},

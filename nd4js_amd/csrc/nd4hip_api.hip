@@ -305,6 +305,65 @@ extern "C" int nd4hip_dgeqp3_full_batched_dev(nd4hip_handle* h, int64_t batch, i
   return geqp3_dev(h, "dgeqp3_full_batched", true, batch, M, N, A, Q, R, P);
 }
 
+// srrqr_decomp_full (srrqr.js:58-802): Q [M, M], R [M, N], P [N], rank []
+extern "C" int nd4hip_dsrrqr_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double dtol, double ztol,
+                                         double* Q, double* R, int32_t* P, int32_t* rank) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dsrrqr_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "dsrrqr_batched", (double)batch * nd4_flops_qp3(M, N), 8.0 * batch * (double)(M * N + M * M + M * N) + 4.0 * batch * (double)(N + 1));
+  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dsrrqr_batched: negative extent");
+  ND4_CHECK_ARG(dtol >= 1.0, "srrqr_decomp_full(A,opt): Invalid opt.dtol: %s. Must be >=1.", dtol != dtol ? "NaN" : "a value below 1");
+  ND4_CHECK_ARG(dtol <= 1.79769313486231570e308, "Assertion failed. Invalid dtol: Infinity.");
+  ND4_CHECK_ARG(!(ztol != ztol), "srrqr_decomp_full(A,opt): invalid opt.ztol: NaN. Must be non-negative number.");
+  ND4_CHECK_ARG(ztol <= 1.79769313486231570e308, "Assertion failed. Invalid ztol: Infinity.");
+  if (batch == 0) return 0;
+  ND4_CHECK_ARG(P && rank && (Q || M == 0) && (A && R || M * N == 0), "nd4hip_dsrrqr_batched: NULL pointer");
+  ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_srrqr(h, nb, M, N, A ? A + b0 * M * N : nullptr, dtol, ztol, Q ? Q + b0 * M * M : nullptr,
+                                          R ? R + b0 * M * N : nullptr, P + b0 * N, rank + b0));
+  return 0;
+}
+
+// urv_decomp_full (urv.js:100-135): U [M, M], R [M, N], V [N, N], rank []
+extern "C" int nd4hip_durv_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* U, double* R,
+                                       double* V, int32_t* rank) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_durv_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "durv_batched", (double)batch * (nd4_flops_qp3(M, N) + nd4_flops_qr(N, M < N ? M : N)),
+               8.0 * batch * (double)(2 * M * N + M * M + N * N) + 4.0 * batch);
+  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_durv_batched: negative extent");
+  if (batch == 0) return 0;
+  ND4_CHECK_ARG(rank && (U || M == 0) && (V || N == 0) && (A && R || M * N == 0), "nd4hip_durv_batched: NULL pointer");
+  if (N == 0) {
+    ND4_HIP(hipMemsetAsync(rank, 0, sizeof(int32_t) * (size_t)batch, h->stream));
+    if (M > 0) ND4_TRY(nd4_set_identity(h, M, M, U, M, batch, M * M));
+    return 0;
+  }
+  ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_urv(h, nb, M, N, A ? A + b0 * M * N : nullptr, U ? U + b0 * M * M : nullptr, R ? R + b0 * M * N : nullptr,
+                                        V + b0 * N * N, rank + b0));
+  return 0;
+}
+
+// urv_lstsq (urv.js:138-323): U [I, J], R [J, K], V [K, L], rank [], Y [I, Jc] -> X [L, Jc]; strides in elements, 0 = broadcast
+extern "C" int nd4hip_durvls_batched_dev(nd4hip_handle* h, int64_t batch, int64_t I, int64_t J, int64_t K, int64_t L, int64_t Jc,
+                                         const double* U, int64_t strideU, const double* R, int64_t strideR, const double* V, int64_t strideV,
+                                         const int32_t* rank, int64_t strideRank, const double* Y, int64_t strideY, double* X) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_durvls_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  const int64_t Lr = J < K ? J : K;
+  Nd4Prof prof(h, "durvls_batched", (double)batch * (2.0 * Lr * I * Jc + (double)Lr * Lr * Jc + 2.0 * Lr * L * Jc),
+               8.0 * batch * (double)(I * J + J * K + K * L + I * Jc + L * Jc));
+  ND4_CHECK_ARG(batch >= 0 && I >= 0 && J >= 0 && K >= 0 && L >= 0 && Jc >= 0, "nd4hip_durvls_batched: negative extent");
+  ND4_CHECK_ARG(J <= I && K <= L, "Assertion failed.");
+  ND4_CHECK_ARG((strideU == 0 || strideU >= I * J) && (strideR == 0 || strideR >= J * K) && (strideV == 0 || strideV >= K * L) &&
+                (strideRank == 0 || strideRank == 1) && (strideY == 0 || strideY >= I * Jc),
+                "nd4hip_durvls_batched: a stride must be 0 or at least the size of one operand");
+  if (batch == 0 || L * Jc == 0) return 0;
+  ND4_CHECK_ARG(U && R && V && rank && Y && X, "nd4hip_durvls_batched: NULL pointer");
+  ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_urvls(h, nb, I, J, K, L, Jc, U + b0 * strideU, strideU, R + b0 * strideR, strideR, V + b0 * strideV, strideV,
+                                          rank + b0 * strideRank, strideRank, Y + b0 * strideY, strideY, X + b0 * L * Jc));
+  return 0;
+}
+
 // rrqr_rank (rrqr.js:398-414): rank [batch] of R [M, N]; -1 marks a matrix whose partial norms are not finite
 extern "C" int nd4hip_dqp3rank_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* R, int32_t* rank) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dqp3rank_batched: NULL handle");

@@ -537,6 +537,89 @@ extern "C" int nd4hip_dqp3ls_batched(nd4hip_handle* h, int64_t batch, int64_t N,
   return qp3_rank_verdict(rank, batch);
 }
 
+// ------------------------------------------------------------------------------------ strong rank-revealing QR
+namespace {
+// the decision kernel marks a non-finite scale (srrqr.js:592-593 throws 'Assertion failed: ' + SCALE) and the swap cap
+int srrqr_rank_verdict(const int32_t* rank, int64_t batch) {
+  for (int64_t b = 0; b < batch; b++) {
+    ND4_CHECK_ARG(rank[b] != -1, "Assertion failed: Infinity");
+    ND4_CHECK_ARG(rank[b] != -3, "Assertion failed: NaN");
+    if (rank[b] < 0) { nd4_set_error("srrqr_decomp_full(A,opt): the swap limit was reached."); return ND4HIP_ERR_NOCONV; }
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" int nd4hip_dsrrqr_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double dtol, double ztol,
+                                     double* Q, double* R, int32_t* Pv, int32_t* rank) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dsrrqr_batched: NULL handle");
+  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dsrrqr_batched: negative extent");
+  ND4_CHECK_ARG(dtol >= 1.0, "srrqr_decomp_full(A,opt): Invalid opt.dtol: %s. Must be >=1.", dtol != dtol ? "NaN" : "a value below 1");
+  ND4_CHECK_ARG(dtol <= 1.79769313486231570e308, "Assertion failed. Invalid dtol: Infinity.");
+  ND4_CHECK_ARG(!(ztol != ztol), "srrqr_decomp_full(A,opt): invalid opt.ztol: NaN. Must be non-negative number.");
+  ND4_CHECK_ARG(ztol <= 1.79769313486231570e308, "Assertion failed. Invalid ztol: Infinity.");
+  if (batch == 0) return 0;
+  ND4_CHECK_ARG(Pv && rank && (Q || M == 0) && (A && R || M * N == 0), "nd4hip_dsrrqr_batched: NULL pointer");
+  if (M == 0 || N == 0) {                                    // nothing to decide: P = identity, rank 0, Q = I
+    for (int64_t b = 0; b < batch; b++) {
+      rank[b] = 0;
+      for (int64_t j = 0; j < N; j++) Pv[b * N + j] = (int32_t)j;
+      for (int64_t i = 0; i < M * M; i++) Q[b * M * M + i] = (i % (M + 1) == 0) ? 1.0 : 0.0;
+    }
+    return 0;
+  }
+  std::vector<Operand> ops{in_op(A, M * N, M * N), out_op(Q, M * M), out_op(R, M * N), out_op(Pv, N, 4), out_op(rank, 1, 4)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
+    return nd4hip_dsrrqr_batched_dev(hd, nb, M, N, P(d, 0), dtol, ztol, P(d, 1), P(d, 2), static_cast<int32_t*>(d[3]),
+                                     static_cast<int32_t*>(d[4]));
+  };
+  ND4_TRY(run_host(h, batch, ops, fn));
+  return srrqr_rank_verdict(rank, batch);
+}
+
+// ------------------------------------------------------------------------------------ URV
+extern "C" int nd4hip_durv_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* U, double* R, double* V,
+                                   int32_t* rank) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_durv_batched: NULL handle");
+  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_durv_batched: negative extent");
+  if (batch == 0) return 0;
+  ND4_CHECK_ARG(rank && (U || M == 0) && (V || N == 0) && (A && R || M * N == 0), "nd4hip_durv_batched: NULL pointer");
+  if (M == 0 || N == 0) {                                    // rank 0, U = I, V = I
+    for (int64_t b = 0; b < batch; b++) {
+      rank[b] = 0;
+      for (int64_t i = 0; i < M * M; i++) U[b * M * M + i] = (i % (M + 1) == 0) ? 1.0 : 0.0;
+      for (int64_t i = 0; i < N * N; i++) V[b * N * N + i] = (i % (N + 1) == 0) ? 1.0 : 0.0;
+    }
+    return 0;
+  }
+  std::vector<Operand> ops{in_op(A, M * N, M * N), out_op(U, M * M), out_op(R, M * N), out_op(V, N * N), out_op(rank, 1, 4)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
+    return nd4hip_durv_batched_dev(hd, nb, M, N, P(d, 0), P(d, 1), P(d, 2), P(d, 3), static_cast<int32_t*>(d[4]));
+  };
+  ND4_TRY(run_host(h, batch, ops, fn));
+  return srrqr_rank_verdict(rank, batch);
+}
+
+extern "C" int nd4hip_durvls_batched(nd4hip_handle* h, int64_t batch, int64_t I, int64_t J, int64_t K, int64_t L, int64_t Jc,
+                                     const double* U, int64_t strideU, const double* R, int64_t strideR, const double* V, int64_t strideV,
+                                     const int32_t* rank, int64_t strideRank, const double* Y, int64_t strideY, double* X) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_durvls_batched: NULL handle");
+  ND4_CHECK_ARG(batch >= 0 && I >= 0 && J >= 0 && K >= 0 && L >= 0 && Jc >= 0, "nd4hip_durvls_batched: negative extent");
+  ND4_CHECK_ARG(J <= I && K <= L, "Assertion failed.");
+  ND4_CHECK_ARG((strideU == 0 || strideU >= I * J) && (strideR == 0 || strideR >= J * K) && (strideV == 0 || strideV >= K * L) &&
+                (strideRank == 0 || strideRank == 1) && (strideY == 0 || strideY >= I * Jc),
+                "nd4hip_durvls_batched: a stride must be 0 or at least the size of one operand");
+  if (batch == 0 || L * Jc == 0) return 0;
+  ND4_CHECK_ARG(U && R && V && rank && Y && X, "nd4hip_durvls_batched: NULL pointer");
+  std::vector<Operand> ops{in_op(U, I * J, strideU), in_op(R, J * K, strideR), in_op(V, K * L, strideV), in_op(rank, 1, strideRank, 4),
+                           in_op(Y, I * Jc, strideY), out_op(X, L * Jc)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
+    return nd4hip_durvls_batched_dev(hd, nb, I, J, K, L, Jc, P(d, 0), strideU, P(d, 1), strideR, P(d, 2), strideV,
+                                     static_cast<const int32_t*>(d[3]), strideRank, P(d, 4), strideY, P(d, 5));
+  };
+  return run_host(h, batch, ops, fn);
+}
+
 // ------------------------------------------------------------------------------------ SVD
 extern "C" int nd4hip_dgesvdj_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A,
                                       double* U, double* sv, double* V, int* sweeps_out, double* offnorm_out) {

@@ -123,6 +123,13 @@ int nd4_geqp3(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const doubl
 int nd4_qp3rank(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* R, int64_t sR, int* rank);
 int nd4_qp3ls(nd4hip_handle* h, int64_t batch, int64_t N, int64_t M, int64_t I, int64_t J, const double* Q, int64_t sQ,
               const double* R, int64_t sR, const int32_t* P, int64_t sP, const double* Y, int64_t sY, double* X, int* rank_out);
+// strong rank-revealing QR (srrqr.hip)
+int nd4_srrqr(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double dtol, double ztol, double* Q, double* R,
+              int32_t* P, int32_t* rank);
+int nd4_urv(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* U, double* R, double* V, int32_t* rank);
+int nd4_urvls(nd4hip_handle* h, int64_t batch, int64_t I, int64_t J, int64_t K, int64_t Lv, int64_t Jc, const double* U, int64_t sU,
+              const double* R, int64_t sR, const double* V, int64_t sV, const int32_t* rank, int64_t sRank, const double* Y, int64_t sY,
+              double* X);
 int nd4_gesvdj(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A,
                double* U, double* sv, double* V, int* sweeps_out, double* offnorm_out);
 

@@ -363,3 +363,58 @@ def rrqr_lstsq(Q, R, P, Y, rank=None):
                                                _p(P), I if b > 1 else 0, _p(Y), N * J if b > 1 else 0, _p(X),
                                                _p(rank) if rank is not None else None))
     return X
+
+
+def srrqr_decomp_full(A, dtol=1.01, ztol=None):
+    """device-resident srrqr_decomp_full (srrqr.js:58-802): Q [..., M, M], R [..., M, N], P [..., N] int32, r [...] int32.
+    No host read-back: r is -1 where ||A||_F is not finite and -2 where the swap cap was hit."""
+    _chk(A, "A")
+    if A.dim() < 2:
+        raise ValueError("srrqr_decomp_full(A,opt): A must be at least 2D.")
+    from .la import _srrqr_opts
+    dtol, ztol = _srrqr_opts(None, dtol, ztol)
+    M, N = A.shape[-2:]
+    lead = tuple(A.shape[:-2])
+    Q = torch.empty(lead + (M, M), dtype=torch.float64, device=A.device)
+    R = torch.empty(lead + (M, N), dtype=torch.float64, device=A.device)
+    P = torch.empty(lead + (N,), dtype=torch.int32, device=A.device)
+    r = torch.empty(lead, dtype=torch.int32, device=A.device)
+    h = _h(A)
+    _lib.check(h.lib.nd4hip_dsrrqr_batched_dev(h.ptr, _batch(lead), M, N, _p(A), dtol, ztol, _p(Q), _p(R), _p(P), _p(r)))
+    return Q, R, P, r
+
+
+def urv_decomp_full(A):
+    """device-resident urv_decomp_full (urv.js:100-135): U [..., M, M], R [..., M, N], V [..., N, N], r [...] int32 with A = U R V.
+    No host read-back: r is -1 / -3 where ||A||_F is Infinity / NaN and -2 where the swap cap was hit."""
+    _chk(A, "A")
+    if A.dim() < 2:
+        raise ValueError("srrqr_decomp_full(A,opt): A must be at least 2D.")
+    M, N = A.shape[-2:]
+    lead = tuple(A.shape[:-2])
+    U = torch.empty(lead + (M, M), dtype=torch.float64, device=A.device)
+    R = torch.empty(lead + (M, N), dtype=torch.float64, device=A.device)
+    V = torch.empty(lead + (N, N), dtype=torch.float64, device=A.device)
+    r = torch.empty(lead, dtype=torch.int32, device=A.device)
+    h = _h(A)
+    _lib.check(h.lib.nd4hip_durv_batched_dev(h.ptr, _batch(lead), M, N, _p(A), _p(U), _p(R), _p(V), _p(r)))
+    return U, R, V, r
+
+
+def urv_lstsq(U, R, V, ranks, Y):
+    """device-resident urv_lstsq (urv.js:138-323): U [..., I, J], R [..., J, K], V [..., K, L], ranks [...] int32, Y [..., I, Jc]
+    with equal leading dims -> X [..., L, Jc] (minimum-norm least squares). No host read-back."""
+    _chk(U, "U"), _chk(R, "R"), _chk(V, "V"), _chk(Y, "Y")
+    if not (isinstance(ranks, torch.Tensor) and ranks.is_cuda and ranks.dtype == torch.int32 and ranks.is_contiguous()):
+        raise TypeError("ranks must be a contiguous int32 CUDA tensor")
+    I, J = U.shape[-2:]
+    K, L = V.shape[-2:]
+    Jc = Y.shape[-1]
+    lead = tuple(U.shape[:-2])
+    if tuple(R.shape) != lead + (J, K) or tuple(V.shape[:-2]) != lead or tuple(Y.shape) != lead + (I, Jc) or tuple(ranks.shape) != lead:
+        raise ValueError("urv_lstsq( U,R,V,ranks, Y ): Matrix dimensions incompatible.")
+    X = torch.empty(lead + (L, Jc), dtype=torch.float64, device=U.device)
+    h = _h(U)
+    _lib.check(h.lib.nd4hip_durvls_batched_dev(h.ptr, _batch(lead), I, J, K, L, Jc, _p(U), I * J, _p(R), J * K, _p(V), K * L,
+                                               _p(ranks), 1, _p(Y), I * Jc, _p(X)))
+    return X

@@ -646,6 +646,74 @@ function makeLa(NDA, fallback, SolveError) {
     return la.rrqr_solve(Q, R, P, y);
   };
   la.SingularMatrixSolveError = SolveError;
+
+  /* ---- strong rank-revealing QR (srrqr.js) and URV (urv.js), csrc/srrqr.hip ---- */
+  const jsNum = x => Number.isNaN(x) ? 'NaN' : String(x);
+  const isArr = x => x instanceof NDA || !!(x && x.shape && x.data);
+  la.srrqr_decomp_full = function srrqr_decomp_full(A, opt = {}) {
+    A = asarray(A);
+    if (A.ndim < 2) throw new Error('srrqr_decomp_full(A,opt): A must be at least 2D.');
+    const {dtol = 1.01, ztol = undefined} = opt || {};
+    if (isArr(dtol)) throw new Error('srrqr_decomp_full(A,opt): NDArray as opt.dtol not yet supported.');
+    if (!(dtol >= 1)) throw new Error(`srrqr_decomp_full(A,opt): Invalid opt.dtol: ${jsNum(dtol)}. Must be >=1.`);
+    if (isArr(ztol)) throw new Error('srrqr_decomp_full(A,opt): NDArray as opt.ztol not yet supported.');
+    if (ztol != null && !(ztol >= 0)) throw new Error(`srrqr_decomp_full(A,opt): invalid opt.ztol: ${jsNum(ztol)}. Must be non-negative number.`);
+    if (!gpuOk(A)) { if (fallback && fallback.srrqr_decomp_full) return fallback.srrqr_decomp_full(A, opt); throw new Error('nd4hip.srrqr_decomp_full: dtype ' + dtypeOf(A) + ' is not accelerated.'); }
+    if (!isFinite(dtol)) throw new Error(`Assertion failed. Invalid dtol: ${dtol}.`);
+    if (ztol != null && !isFinite(ztol)) throw new Error(`Assertion failed. Invalid ztol: ${ztol}.`);
+    const nd_ = A.ndim, M = A.shape[nd_ - 2], N = A.shape[nd_ - 1], batch = prod(A.shape, 0, nd_ - 2);
+    const lead = Array.from(A.shape.subarray(0, nd_ - 2));
+    const dev = isDev(A), temps = [];
+    const Q = alloc(dev, batch * M * M), R = alloc(dev, batch * M * N), P = alloc(dev, batch * N, Int32Array), r = alloc(dev, batch, Int32Array);
+    try {
+      native().dsrrqr_batched(batch, M, N, view(opF64(A, dev, temps), 0), +dtol, ztol == null ? -1 : +ztol, view(Q, 0), view(R, 0), view(P, 0), view(r, 0));
+    } finally { release(temps); }
+    return [wrap(dev, [...lead, M, M], Q), wrap(dev, [...lead, M, N], R), wrap(dev, [...lead, N], P), wrap(dev, lead, r)];
+  };
+  la.urv_decomp_full = function urv_decomp_full(A) {           // urv.js:100-135
+    A = asarray(A);
+    if (A.ndim < 2) throw new Error('srrqr_decomp_full(A,opt): A must be at least 2D.');
+    if (!gpuOk(A)) { if (fallback && fallback.urv_decomp_full) return fallback.urv_decomp_full(A); throw new Error('nd4hip.urv_decomp_full: dtype ' + dtypeOf(A) + ' is not accelerated.'); }
+    const nd_ = A.ndim, M = A.shape[nd_ - 2], N = A.shape[nd_ - 1], batch = prod(A.shape, 0, nd_ - 2);
+    const lead = Array.from(A.shape.subarray(0, nd_ - 2));
+    const dev = isDev(A), temps = [];
+    const U = alloc(dev, batch * M * M), R = alloc(dev, batch * M * N), V = alloc(dev, batch * N * N), r = alloc(dev, batch, Int32Array);
+    try { native().durv_batched(batch, M, N, view(opF64(A, dev, temps), 0), view(U, 0), view(R, 0), view(V, 0), view(r, 0)); }
+    finally { release(temps); }
+    return [wrap(dev, [...lead, M, M], U), wrap(dev, [...lead, M, N], R), wrap(dev, [...lead, N, N], V), wrap(dev, lead, r)];
+  };
+  la.urv_lstsq = function urv_lstsq(U, R, V, ranks, Y) {        // urv.js:138-323
+    if (Y == null) {
+      if (ranks != null || V != null) throw new Error('urv_lstsq( U,R,V,ranks, Y ): Either 2 ([U,R,V,ranks], Y) or 5 arguments (U,R,V,ranks, Y) expected.');
+      Y = R; [U, R, V, ranks] = U;
+    }
+    U = asarray(U); if (!(U.ndim >= 2)) throw new Error('urv_lstsq(U,R,V, Y): U.ndim must be at least 2.');
+    R = asarray(R); if (!(R.ndim >= 2)) throw new Error('urv_lstsq(U,R,V, Y): R.ndim must be at least 2.');
+    V = asarray(V); if (!(V.ndim >= 2)) throw new Error('urv_lstsq(U,R,V, Y): V.ndim must be at least 2.');
+    Y = asarray(Y); if (!(Y.ndim >= 2)) throw new Error('urv_lstsq(U,R,V, Y): Y.ndim must be at least 2.');
+    ranks = asarray(ranks);
+    const lU = Array.from(U.shape.subarray(0, U.ndim - 2)), lR = Array.from(R.shape.subarray(0, R.ndim - 2)),
+          lV = Array.from(V.shape.subarray(0, V.ndim - 2)), lY = Array.from(Y.shape.subarray(0, Y.ndim - 2)), lK = Array.from(ranks.shape);
+    const lead = bcastLead([lU, lR, lV, lY, lK], 'urv_lstsq( U,R,V,ranks, Y ): U,R,V,ranks, Y not broadcast-compatible.');
+    const I = U.shape[U.ndim - 2], J = U.shape[U.ndim - 1], K = V.shape[V.ndim - 2], L = V.shape[V.ndim - 1], Jc = Y.shape[Y.ndim - 1];
+    if (R.shape[R.ndim - 2] !== J || R.shape[R.ndim - 1] !== K || Y.shape[Y.ndim - 2] !== I) throw new Error('urv_lstsq( U,R,V,ranks, Y ): Matrix dimensions incompatible.');
+    if (J !== K && ((I < L && I !== J) || (I >= L && K !== L))) throw new Error('Assertion failed.');
+    if (!(I >= J) || !(K <= L)) throw new Error('Assertion failed.');
+    if (!gpuOk(U) || !gpuOk(R) || !gpuOk(V) || !gpuOk(Y)) {
+      if (fallback && fallback.urv_lstsq) return fallback.urv_lstsq(U, R, V, ranks, Y);
+      throw new Error('nd4hip.urv_lstsq: dtype is not accelerated.');
+    }
+    const total = lead.reduce((a, b) => a * b, 1);
+    const dev = isDev(U) || isDev(R) || isDev(V) || isDev(Y) || isDev(ranks), temps = [];
+    const X = alloc(dev, total * L * Jc);
+    const Ud = opF64(U, dev, temps), Rd = opF64(R, dev, temps), Vd = opF64(V, dev, temps), Kd = opI32(ranks, dev, temps), Yd = opF64(Y, dev, temps);
+    try {
+      for (const [cnt, [oU, oR, oV, oK, oY], [sU, sR, sV, sK, sY], b0] of bcastGroupsN(lead, [lU, lR, lV, lK, lY], [I * J, J * K, K * L, 1, I * Jc]))
+        native().durvls_batched(cnt, I, J, K, L, Jc, view(Ud, oU), sU, view(Rd, oR), sR, view(Vd, oV), sV, view(Kd, oK), sK, view(Yd, oY), sY,
+                                view(X, b0 * L * Jc));
+    } finally { release(temps); }
+    return wrap(dev, [...lead, L, Jc], X);
+  };
   return la;
 }
 
@@ -655,6 +723,7 @@ const standalone = makeLa(NDArray, null, SingularMatrixSolveError);
 function estimatedWork(name, args) {
   const dims = a => { const s = a && a.shape ? Array.from(a.shape) : null; if (!s || s.length < 2) return null;
                       let b = 1; for (let i = 0; i < s.length - 2; i++) b *= s[i]; return [b, s[s.length - 2], s[s.length - 1]]; };
+  if (name === 'urv_lstsq' && Array.isArray(args[0])) args = args[0];   // urv_lstsq([U,R,V,ranks], Y): the work of U
   const a = dims(args[0]);
   if (!a) return Infinity;                                  // nested JS arrays etc.: let the accelerated path coerce them
   if (name === 'matmul2') { const b = dims(args[1]); return b ? 2 * Math.max(a[0], b[0]) * a[1] * a[2] * b[2] : Infinity; }
@@ -677,7 +746,8 @@ function install(nd, opts) {
                     cholesky_decomp: nd.la.cholesky_decomp, cholesky_solve: nd.la.cholesky_solve,
                     ldl_decomp: nd.la.ldl_decomp, ldl_solve: nd.la.ldl_solve, hessenberg_decomp: nd.la.hessenberg_decomp, bidiag_decomp: nd.la.bidiag_decomp,
                     rrqr_decomp: nd.la.rrqr_decomp, rrqr_decomp_full: nd.la.rrqr_decomp_full, rrqr_rank: nd.la.rrqr_rank,
-                    rrqr_lstsq: nd.la.rrqr_lstsq, rrqr_solve: nd.la.rrqr_solve, solve: nd.la.solve};
+                    rrqr_lstsq: nd.la.rrqr_lstsq, rrqr_solve: nd.la.rrqr_solve, solve: nd.la.solve,
+                    srrqr_decomp_full: nd.la.srrqr_decomp_full, urv_decomp_full: nd.la.urv_decomp_full, urv_lstsq: nd.la.urv_lstsq};
   const acc = makeLa(nd.NDArray, original, nd.la.SingularMatrixSolveError || SingularMatrixSolveError);
   const target = Object.isFrozen(nd.la) || !Object.getOwnPropertyDescriptor(nd.la, 'matmul2').writable ? null : nd.la;
   const patched = target || Object.create(nd.la);

@@ -604,7 +604,7 @@ def _rrqr_args(Q, R, P, y):
         if P is not None:
             raise ValueError("rrqr_lstsq(Q,R,P, y): Either 2 ([Q,R,P], y) or 4 arguments (Q,R,P, y) expected.")
         y = R
-        Q, R, P = Q
+        Q, R, P = tuple(Q)[:3]                                        # srrqr_decomp_full's (Q, R, P, r) works too
     return Q, R, P, y
 
 
@@ -675,3 +675,136 @@ def solve(A, y, device=None):
     """solve.js:23-27: rrqr_solve(rrqr_decomp(A), y)."""
     Q, R, P = rrqr_decomp(A, device=device)
     return rrqr_solve(Q, R, P, y, device=device)
+
+
+# ---------------------------------------------------------------------------------------------------
+# Strong rank-revealing QR (src/la/srrqr.js), csrc/srrqr.hip
+# ---------------------------------------------------------------------------------------------------
+def _js_num(x):
+    """a number as the reference's template strings print it"""
+    x = float(x)
+    if x != x:
+        return "NaN"
+    if x in (float("inf"), float("-inf")):
+        return "Infinity" if x > 0 else "-Infinity"
+    return str(int(x)) if x == int(x) and abs(x) < 1e21 else repr(x)
+
+
+def _srrqr_opts(opt, dtol, ztol):
+    """srrqr.js:186-225: (dtol, ztol) for the C ABI; ztol -1 selects the reference's default"""
+    opt = dict(opt or {})
+    if dtol is not None:
+        opt["dtol"] = dtol
+    if ztol is not None:
+        opt["ztol"] = ztol
+    d = opt.get("dtol", 1.01)
+    z = opt.get("ztol", None)
+    if isinstance(d, np.ndarray):
+        raise ValueError("srrqr_decomp_full(A,opt): NDArray as opt.dtol not yet supported.")
+    d = float(d)
+    if not d >= 1:
+        raise ValueError("srrqr_decomp_full(A,opt): Invalid opt.dtol: %s. Must be >=1." % _js_num(d))
+    if isinstance(z, np.ndarray):
+        raise ValueError("srrqr_decomp_full(A,opt): NDArray as opt.ztol not yet supported.")
+    if z is not None:
+        z = float(z)
+        if not z >= 0:
+            raise ValueError("srrqr_decomp_full(A,opt): invalid opt.ztol: %s. Must be non-negative number." % _js_num(z))
+    if d == float("inf"):                                             # srrqr.js:601-604, per matrix, after the option checks
+        raise ValueError("Assertion failed. Invalid dtol: Infinity.")
+    if z == float("inf"):
+        raise ValueError("Assertion failed. Invalid ztol: Infinity.")
+    return d, (-1.0 if z is None else z)
+
+
+def _arg_error(e):
+    """the reference's message of an ND4HIP_ERR_ARG raised by the library (the text after 'nd4hip error -1: ')"""
+    return ValueError(str(e).split(": ", 1)[1]) if e.code == -1 else e
+
+
+def srrqr_decomp_full(A, opt=None, dtol=None, ztol=None, device=None):
+    """srrqr.js:58-802: (Q [..., M, M], R [..., M, N], P [..., N] int32, r [...] int32) with A[..., :, P] = Q R and r the
+    rank found by the strong RRQR. `opt` is the reference's {dtol, ztol}; dtol / ztol may also be given as keywords."""
+    A = np.asarray(A)
+    if A.ndim < 2:
+        raise ValueError("srrqr_decomp_full(A,opt): A must be at least 2D.")
+    if np.iscomplexobj(A):
+        raise ValueError("srrqr_decomp_full(A,opt): Complex A not (yet) supported.")
+    d, z = _srrqr_opts(opt, dtol, ztol)
+    A = _asarray(A, "srrqr_decomp_full(A,opt)")
+    M, N = A.shape[-2:]
+    lead = A.shape[:-2]
+    Q, R = np.empty(lead + (M, M)), np.empty(lead + (M, N))
+    P = np.empty(lead + (N,), dtype=np.int32)
+    r = np.empty(lead, dtype=np.int32)
+    h = _lib.handle(device)
+    try:
+        _lib.check(h.lib.nd4hip_dsrrqr_batched(h.ptr, int(np.prod(lead, dtype=np.int64)), M, N, _ptr(A), d, z, _ptr(Q), _ptr(R),
+                                               _ptr(P), _ptr(r)))
+    except _lib.Nd4HipError as e:
+        raise _arg_error(e)
+    return Q, R, P, r
+
+
+# ---------------------------------------------------------------------------------------------------
+# URV (src/la/urv.js), csrc/srrqr.hip
+# ---------------------------------------------------------------------------------------------------
+def urv_decomp_full(A, device=None):
+    """urv.js:100-135: (U [..., M, M], R [..., M, N], V [..., N, N], ranks [...] int32) with A = U R V and
+    R = [[T, 0], [0, 0]], T upper triangular of size rank."""
+    A = np.asarray(A)
+    if A.ndim < 2:
+        raise ValueError("srrqr_decomp_full(A,opt): A must be at least 2D.")
+    if np.iscomplexobj(A):
+        raise ValueError("srrqr_decomp_full(A,opt): Complex A not (yet) supported.")
+    A = _asarray(A, "urv_decomp_full(A)")
+    M, N = A.shape[-2:]
+    lead = A.shape[:-2]
+    U, R, V = np.empty(lead + (M, M)), np.empty(lead + (M, N)), np.empty(lead + (N, N))
+    r = np.empty(lead, dtype=np.int32)
+    h = _lib.handle(device)
+    try:
+        _lib.check(h.lib.nd4hip_durv_batched(h.ptr, int(np.prod(lead, dtype=np.int64)), M, N, _ptr(A), _ptr(U), _ptr(R), _ptr(V), _ptr(r)))
+    except _lib.Nd4HipError as e:
+        raise _arg_error(e)
+    return U, R, V, r
+
+
+def urv_lstsq(U, R, V=None, ranks=None, Y=None, device=None):
+    """urv.js:138-323: the minimum-norm least-squares X = V[:r]^T T^-1 (U^T Y)[:r] per (broadcast) matrix; accepts
+    urv_lstsq((U, R, V, ranks), Y) like the reference (:200-206)."""
+    if Y is None:
+        if ranks is not None or V is not None:
+            raise ValueError("urv_lstsq( U,R,V,ranks, Y ): Either 2 ([U,R,V,ranks], Y) or 5 arguments (U,R,V,ranks, Y) expected.")
+        Y = R
+        U, R, V, ranks = U
+    U, R, V, Y = np.asarray(U), np.asarray(R), np.asarray(V), np.asarray(Y)
+    for x, n in ((U, "U"), (R, "R"), (V, "V"), (Y, "Y")):
+        if x.ndim < 2:
+            raise ValueError("urv_lstsq(U,R,V, Y): %s.ndim must be at least 2." % n)
+    ranks = np.asarray(ranks)
+    U, R, V, Y = (_asarray(x, "urv_lstsq") for x in (U, R, V, Y))
+    ranks = np.array(ranks, dtype=np.int32, order="C")                 # (keeps a 0-d rank 0-d)
+    try:
+        lead = np.broadcast_shapes(U.shape[:-2], R.shape[:-2], V.shape[:-2], Y.shape[:-2], ranks.shape)
+    except ValueError:
+        raise ValueError("urv_lstsq( U,R,V,ranks, Y ): U,R,V,ranks, Y not broadcast-compatible.")
+    I, J = U.shape[-2:]
+    K, L = V.shape[-2:]
+    Jc = Y.shape[-1]
+    if R.shape[-2] != J or R.shape[-1] != K or Y.shape[-2] != I:
+        raise ValueError("urv_lstsq( U,R,V,ranks, Y ): Matrix dimensions incompatible.")
+    if J != K and ((I < L and I != J) or (I >= L and K != L)):
+        raise ValueError("Assertion failed.")
+    if not (I >= J) or not (K <= L):
+        raise ValueError("Assertion failed.")
+    X = np.zeros(tuple(lead) + (L, Jc))
+    h = _lib.handle(device)
+    for cnt, (oU, oR, oV, oK, oY), (sU, sR, sV, sK, sY), b0 in _bcast_groups_n(
+            tuple(lead), [U.shape[:-2], R.shape[:-2], V.shape[:-2], ranks.shape, Y.shape[:-2]], [I * J, J * K, K * L, 1, I * Jc]):
+        try:
+            _lib.check(h.lib.nd4hip_durvls_batched(h.ptr, cnt, I, J, K, L, Jc, _off(U, oU), sU, _off(R, oR), sR, _off(V, oV), sV,
+                                                   _off(ranks, oK, 4), sK, _off(Y, oY), sY, _off(X, b0 * L * Jc)))
+        except _lib.Nd4HipError as e:
+            raise _arg_error(e)
+    return X

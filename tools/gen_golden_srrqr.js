@@ -1,0 +1,177 @@
+#!/usr/bin/env node
+/* Golden vectors of the strong rank-revealing QR (srrqr_decomp_full and its use in rrqr_lstsq / rrqr_rank) from the real
+ * reference bundle. Inputs come from the repo's counter-based generator nd4_uniform (twin of nd4js_amd/rng.py) and the input
+ * families of tests/families.py; only numbers (outputs, sampled entries, norms) are written, as .npy files plus their own
+ * manifest.json under tests/golden/srrqr/.
+ *
+ *   ND4_REFERENCE=<path to dist/nd.js> node tools/gen_golden_srrqr.js         # all cases (~10 s, most of it 1024^2)
+ *
+ * Without ND4_REFERENCE the bundle is found through BASELINE.json's reference_path, as the node tests do.
+ */
+'use strict';
+const fs = require('fs'), path = require('path');
+const ROOT = path.join(__dirname, '..');
+function referenceBundle() {
+  if (process.env.ND4_REFERENCE) return process.env.ND4_REFERENCE;
+  const base = JSON.parse(fs.readFileSync(path.join(ROOT, 'BASELINE.json')));
+  return path.join(base.reference_path, 'dist', 'nd.js');
+}
+const nd = require(referenceBundle());
+const OUT = path.join(ROOT, 'tests', 'golden', 'srrqr');
+fs.mkdirSync(OUT, {recursive: true});
+
+/* ---------- the repo's counter-based generator (nd4js_amd/rng.py) ---------- */
+function fmix32(h) {
+  h ^= h >>> 16; h = Math.imul(h, 0x85ebca6b);
+  h ^= h >>> 13; h = Math.imul(h, 0xc2b2ae35);
+  h ^= h >>> 16; return h >>> 0;
+}
+function nd4_uniform(seed, idx) {
+  const hi = fmix32((idx ^ fmix32(seed >>> 0)) >>> 0);
+  const lo = fmix32((hi + 0x9E3779B9 + idx) >>> 0);
+  const m = (hi >>> 5) * 67108864 + (lo >>> 6);
+  return m * 2.220446049250313e-16 - 1.0;
+}
+function fill(seed, n) { const a = new Float64Array(n); for (let i = 0; i < n; i++) a[i] = nd4_uniform(seed, i); return a; }
+function hashIdx(seed, i, mod) { return fmix32((fmix32(seed) + Math.imul(i, 0x9E3779B1)) >>> 0) % mod; }
+
+/* ---------- tests/families.py, plus the special inputs of this family ---------- */
+function applyFamily(fam, a, M, N, seed) {
+  switch (fam) {
+    case 'dense': break;
+    case 'sparse10': for (let i = 0; i < a.length; i++) if (hashIdx(seed + 77, i, 10) === 0) a[i] = 0; break;
+    case 'zerorow': { const r = hashIdx(seed + 78, 0, M); for (let j = 0; j < N; j++) a[r * N + j] = 0; break; }
+    case 'zerocol': { const c = hashIdx(seed + 79, 0, N); for (let i = 0; i < M; i++) a[i * N + c] = 0; break; }
+    case 'rankdef': {
+      const rank = Math.max(1, Math.min(M, N) >> 1);
+      for (let i = rank; i < M; i++) for (let j = 0; j < N; j++)
+        a[i * N + j] = 0.5 * a[((i - rank) % rank) * N + j] - 0.25 * a[((i + 1) % rank) * N + j];
+      break; }
+    case 'diag': for (let i = 0; i < M; i++) for (let j = 0; j < N; j++) if (i !== j) a[i * N + j] = 0; break;
+    case 'triu': for (let i = 0; i < M; i++) for (let j = 0; j < i && j < N; j++) a[i * N + j] = 0; break;
+    case 'identity': for (let i = 0; i < M; i++) for (let j = 0; j < N; j++) a[i * N + j] = i === j ? 1 : 0; break;
+    case 'zero': a.fill(0); break;
+    case 'dupcols': for (let i = 0; i < M; i++) for (let j = 1; j < N; j += 2) a[i * N + j] = a[i * N + j - 1]; break;
+    default: throw new Error(fam);
+  }
+  return a;
+}
+function input(seed, shape, fam) {
+  const M = shape[shape.length - 2], N = shape[shape.length - 1], n = shape.reduce((a, b) => a * b, 1);
+  const a = fill(seed, n);
+  for (let o = 0, b = 0; o < n; o += M * N, b++) applyFamily(fam, a.subarray(o, o + M * N), M, N, seed + b);
+  return new nd.NDArray(Int32Array.from(shape), a);
+}
+
+/* ---------- npy + manifest ---------- */
+function npy(name, typed, shape) {
+  const descr = typed instanceof Float64Array ? '<f8' : typed instanceof Int32Array ? '<i4' : null;
+  if (!descr) throw new Error('dtype');
+  let hdr = `{'descr': '${descr}', 'fortran_order': False, 'shape': (${shape.join(', ')}${shape.length === 1 ? ',' : ''}), }`;
+  const pad = 64 - ((10 + hdr.length + 1) % 64);
+  hdr += ' '.repeat(pad % 64) + '\n';
+  const head = Buffer.alloc(10);
+  head.write('\x93NUMPY', 0, 'latin1'); head[6] = 1; head[7] = 0; head.writeUInt16LE(hdr.length, 8);
+  fs.writeFileSync(path.join(OUT, name + '.npy'), Buffer.concat([head, Buffer.from(hdr, 'latin1'), Buffer.from(typed.buffer, typed.byteOffset, typed.byteLength)]));
+}
+const manifest = {rng: 'fmix32-v1', cases: {}};
+function record(name, meta, tensors) {
+  const files = {};
+  for (const [k, arr] of Object.entries(tensors)) {
+    const [typed, shape] = arr instanceof nd.NDArray ? [arr.data, Array.from(arr.shape)] : arr;
+    npy(`${name}.${k}`, typed, shape); files[k] = `${name}.${k}.npy`;
+  }
+  manifest.cases[name] = Object.assign({}, meta, {files});
+  console.log('wrote', name);
+}
+function sample(typed, n, seed) {
+  const idx = new Int32Array(n), val = new Float64Array(n);
+  for (let i = 0; i < n; i++) { idx[i] = hashIdx(seed, i, typed.length); val[i] = typed[idx[i]]; }
+  return [idx, val];
+}
+function lowrank(seed, M, N, r) {                       // B [M, r] C [r, N] from the generator
+  const B = fill(seed, M * r), C = fill(seed + 1, r * N), a = new Float64Array(M * N);
+  for (let i = 0; i < M; i++) for (let k = 0; k < r; k++) { const b = B[i * r + k]; for (let j = 0; j < N; j++) a[i * N + j] += b * C[k * N + j]; }
+  return new nd.NDArray(Int32Array.from([M, N]), a);
+}
+function kahan(n, theta) {                              // (i, j >= i) = sin^i (i == j ? 1 : -cos) (1 - 25 eps i)
+  const s = Math.sin(theta), c = Math.cos(theta), a = new Float64Array(n * n);
+  for (let i = 0; i < n; i++) for (let j = i; j < n; j++) a[i * n + j] = Math.pow(s, i) * (i === j ? 1 : -c) * (1 - 25 * 2.220446049250313e-16 * i);
+  return new nd.NDArray(Int32Array.from([n, n]), a);
+}
+
+/* ---------- cases ---------- */
+function caseSrrqr(name, meta, A, opt) {
+  const [Q, R, P, r] = opt ? nd.la.srrqr_decomp_full(A, opt) : nd.la.srrqr_decomp_full(A);
+  const [, Rw] = nd.la.rrqr_decomp(A);
+  record(name, Object.assign({op: 'srrqr_decomp_full', opt: opt || null, rrqr_rank: Array.from(nd.la.rrqr_rank(Rw).data),
+                              rrqr_rank_of_srrqr_R: Array.from(nd.la.rrqr_rank(R).data)}, meta),
+         A.data.length > 40000 ? {P, r} : {Q, R, P, r});                // large inputs: the decisions only
+}
+function caseGen(name, seed, shape, fam, opt) { caseSrrqr(name, {seed, shape, family: fam}, input(seed, shape, fam), opt); }
+function caseLarge(name, seed, N) {
+  const A = input(seed, [N, N], 'dense');
+  const t0 = Date.now();
+  const [Q, R, P, r] = nd.la.srrqr_decomp_full(A);
+  const ms = Date.now() - t0;
+  const diag = new Float64Array(N); for (let i = 0; i < N; i++) diag[i] = R.data[i * N + i];
+  const [ri, rv] = sample(R.data, 4096, seed + 12);
+  record(name, {op: 'srrqr_decomp_full', seed, shape: [N, N], family: 'dense', sampled: true, js_ms: ms},
+         {P, r, Rdiag: [diag, [N]], R_idx: [ri, [4096]], R_val: [rv, [4096]]});
+}
+function caseLstsq(name, meta, A, J, seed) {
+  const N = A.shape[0];
+  const y = new nd.NDArray(Int32Array.from([N, J]), fill(seed + 1000, N * J));
+  const x = nd.la.rrqr_lstsq(nd.la.srrqr_decomp_full(A), y);
+  record(name, Object.assign({op: 'rrqr_lstsq(srrqr_decomp_full)', J, y_seed: seed + 1000}, meta), {x});
+}
+
+caseGen('dense_48x48', 901, [48, 48], 'dense');
+caseGen('dense_60x40', 902, [60, 40], 'dense');
+caseGen('dense_40x60', 903, [40, 60], 'dense');
+caseGen('dense_64x64', 904, [64, 64], 'dense');
+caseGen('dense_120x200', 905, [120, 200], 'dense');
+caseGen('dense_200x120', 906, [200, 120], 'dense');
+let s = 910;
+for (const fam of ['rankdef', 'sparse10', 'zerorow', 'zerocol', 'diag'])
+  for (const [M, N] of [[48, 48], [60, 40], [40, 60]])
+    caseGen(`${fam}_${M}x${N}`, s++, [M, N], fam);
+caseGen('identity16', 930, [16, 16], 'identity');
+caseGen('zero8x6', 931, [8, 6], 'zero');
+caseGen('dupcols20x12', 932, [20, 12], 'dupcols');
+caseGen('batch5x24', 933, [5, 24, 24], 'dense');
+caseGen('dtol15_64x64', 934, [64, 64], 'dense', {dtol: 1.5});
+caseGen('ztol_48x48', 935, [48, 48], 'dense', {ztol: 0.05});
+caseGen('dtol15_40x60', 936, [40, 60], 'dense', {dtol: 1.5});
+caseGen('dtol15_rankdef_60x40', 937, [60, 40], 'rankdef', {dtol: 1.5});
+caseSrrqr('eye3_ztol2', {shape: [3, 3], family: 'identity'}, nd.array([[1, 0, 0], [0, 1, 0], [0, 0, 1]]), {ztol: 2});
+caseSrrqr('lowrank40_256', {seed: 940, shape: [256, 256], family: 'lowrank', lowrank: 40}, lowrank(940, 256, 256, 40));
+caseSrrqr('lowrank77_300x200', {seed: 941, shape: [300, 200], family: 'lowrank', lowrank: 77}, lowrank(941, 300, 200, 77));
+caseSrrqr('kahan60', {shape: [60, 60], family: 'kahan', theta: 1.2}, kahan(60, 1.2));
+caseSrrqr('kahan90', {shape: [90, 90], family: 'kahan', theta: 1.2}, kahan(90, 1.2));
+caseGen('dense_512x512', 950, [512, 512], 'dense');
+caseLstsq('ls_rankdef_48', {seed: 960, shape: [48, 48], family: 'rankdef'}, input(960, [48, 48], 'rankdef'), 3, 960);
+caseLstsq('ls_lowrank_300x200', {seed: 941, shape: [300, 200], family: 'lowrank', lowrank: 77}, lowrank(941, 300, 200, 77), 2, 941);
+caseLarge('large1024', 970, 1024);
+function caseUrv(name, meta, A) {
+  const [U, R, V, r] = nd.la.urv_decomp_full(A);
+  record(name, Object.assign({op: 'urv_decomp_full'}, meta), {R, V, r});
+}
+function caseUrvLs(name, meta, A, J) {
+  const N = A.shape[A.ndim - 2];
+  const y = new nd.NDArray(Int32Array.from([N, J]), fill(meta.seed + 1000, N * J));
+  const x = nd.la.urv_lstsq(nd.la.urv_decomp_full(A), y);
+  record(name, Object.assign({op: 'urv_lstsq', J, y_seed: meta.seed + 1000}, meta), {x});
+}
+for (const [nm, sd, sh, fam] of [['dense_48x48', 980, [48, 48], 'dense'], ['dense_60x40', 981, [60, 40], 'dense'],
+                                  ['dense_40x60', 982, [40, 60], 'dense'], ['rankdef_48x48', 983, [48, 48], 'rankdef'],
+                                  ['rankdef_40x60', 984, [40, 60], 'rankdef'], ['zerocol_48x48', 985, [48, 48], 'zerocol'],
+                                  ['batch3x20', 986, [3, 20, 20], 'rankdef']])
+  caseUrv(`urv_${nm}`, {seed: sd, shape: sh, family: fam}, input(sd, sh, fam));
+caseUrv('urv_lowrank77_300x200', {seed: 941, shape: [300, 200], family: 'lowrank', lowrank: 77}, lowrank(941, 300, 200, 77));
+caseUrvLs('urvls_rankdef_48', {seed: 990, shape: [48, 48], family: 'rankdef'}, input(990, [48, 48], 'rankdef'), 3);
+caseUrvLs('urvls_rankdef_60x40', {seed: 991, shape: [60, 40], family: 'rankdef'}, input(991, [60, 40], 'rankdef'), 2);
+caseUrvLs('urvls_rankdef_40x60', {seed: 992, shape: [40, 60], family: 'rankdef'}, input(992, [40, 60], 'rankdef'), 1);
+caseUrvLs('urvls_lowrank_300x200', {seed: 941, shape: [300, 200], family: 'lowrank', lowrank: 77}, lowrank(941, 300, 200, 77), 4);
+caseUrvLs('urvls_dense_40x40', {seed: 993, shape: [40, 40], family: 'dense'}, input(993, [40, 40], 'dense'), 2);
+fs.writeFileSync(path.join(OUT, 'manifest.json'), JSON.stringify(manifest, null, 1));
