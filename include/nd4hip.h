@@ -285,6 +285,34 @@ int nd4hip_durvls_batched    (nd4hip_handle* h, int64_t batch, int64_t I, int64_
                               const double* U, int64_t strideU, const double* R, int64_t strideR, const double* V, int64_t strideV,
                               const int32_t* rank, int64_t strideRank, const double* Y, int64_t strideY, double* X);
 
+/* ---- det / slogdet / det_tri / slogdet_tri / norm: replace src/la/det.js:24-106 and src/la/norm.js:22-85 ---------------------
+ * ddet: A [batch,M,N] -> det [batch]; dslogdet: -> sign [batch], logdet [batch]. The reference's det is det_tri(qr_decomp(A)[1]):
+ * square N <= 64 runs qr_decomp_full's Givens elimination in its own operation order (blocked J, I, i, j with B = 8, its skips,
+ * no contraction), so the result is the reference's bit for bit; N > 64 and every tall input (M > N) run qr_decomp's R without Q
+ * (nd4_geqrf_q_ex's R-only mode; a tall input gives prod(diag(R)) of its N x N R with the c >= 0 signs, as the reference does).
+ * M < N is ND4HIP_ERR_ARG with the reference's 'det_tri(a): a must be square matrices.' ('det_tri(A): A must be square
+ * matrices.' for slogdet), raised before any device work. Where the reference's Givens rotation asserts (a NaN or Infinity
+ * reached a rotation: 'Assertion failed: NaN'), the _dev form writes a NaN with the bits ND4HIP_DET_ASSERT_NAN_BITS into det
+ * (sign and logdet) and the host form returns ND4HIP_ERR_ARG with that message. The environment variable ND4HIP_DET_FORCE_QR=1
+ * (read per call) sends square N <= 64 through the R-only QR path too, to compare the two paths. The R-only path factors with
+ * the row-split panels: an in-kernel exchange that times out is ND4HIP_ERR_XCHG (the host form returns it; after the _dev form
+ * the next synchronising entry point does), never a determinant.
+ * ddettri / dslogdettri: A [batch,N,N] -> the product of the diagonal in index order (bit for bit det_tri) / sign = the product of
+ * Math.sign(a_ii) (signed zeros and NaN kept) and logdet = the sum of log|a_ii| in index order. Only the diagonal is read.
+ * dnrmfro: the Frobenius norm of n elements (norm(A), ord 'fro', no axis), one double into *out (a host pointer for the host form,
+ * a device pointer for _dev); n = 0 gives 0; any Infinity gives +Infinity, otherwise any NaN gives NaN; deterministic bits. */
+#define ND4HIP_DET_ASSERT_NAN_BITS 0x7ff80000de7a5e27ull
+int nd4hip_ddet_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* det);
+int nd4hip_ddet_batched    (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* det);
+int nd4hip_dslogdet_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* sign, double* logdet);
+int nd4hip_dslogdet_batched    (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* sign, double* logdet);
+int nd4hip_ddettri_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* det);
+int nd4hip_ddettri_batched    (nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* det);
+int nd4hip_dslogdettri_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* sign, double* logdet);
+int nd4hip_dslogdettri_batched    (nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* sign, double* logdet);
+int nd4hip_dnrmfro_dev(nd4hip_handle* h, int64_t n, const double* A, double* out);
+int nd4hip_dnrmfro    (nd4hip_handle* h, int64_t n, const double* A, double* out);
+
 /* ---- svd_decomp: replaces the output contract of src/la/svd.js:25 (= svd_dc.js:883-932) ----------
  * A [batch,M,N] -> U [batch,M,L], sv [batch,L] (>= 0, descending), V [batch,L,N] (rows = right
  * singular vectors), L = min(M,N); one-sided Jacobi with the reference's Jacobi post-processing

@@ -81,6 +81,16 @@ SIGNATURES = {
                                                                             c_dp, c_i64, c_dp]),
     "nd4hip_durvls_batched": (c_int, [ctypes.c_void_p] + [c_i64] * 6 + [c_dp, c_i64, c_dp, c_i64, c_dp, c_i64, ctypes.c_void_p, c_i64,
                                                                         c_dp, c_i64, c_dp]),
+    "nd4hip_ddet_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp]),
+    "nd4hip_ddet_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp]),
+    "nd4hip_dslogdet_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_dslogdet_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_ddettri_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp]),
+    "nd4hip_ddettri_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp]),
+    "nd4hip_dslogdettri_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_dslogdettri_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_dnrmfro_dev": (c_int, [ctypes.c_void_p, c_i64, c_dp, c_dp]),
+    "nd4hip_dnrmfro": (c_int, [ctypes.c_void_p, c_i64, c_dp, c_dp]),
     "nd4hip_dqp3rank_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, ctypes.c_void_p]),
     "nd4hip_dqp3rank_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, ctypes.c_void_p]),
     "nd4hip_dqp3ls_batched_dev": (c_int, [ctypes.c_void_p] + [c_i64] * 5 + [c_dp, c_i64, c_dp, c_i64, ctypes.c_void_p, c_i64, c_dp, c_i64,

@@ -59,6 +59,11 @@ static int (*p_dsrrqr[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const doubl
 static int (*p_durv[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, double*, double*, double*, int32_t*);
 static int (*p_durvls[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t,
                           const double*, int64_t, const int32_t*, int64_t, const double*, int64_t, double*);
+static int (*p_ddet[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, double*);
+static int (*p_dslogdet[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, double*, double*);
+static int (*p_ddettri[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*);
+static int (*p_dslogdettri[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*, double*);
+static int (*p_dnrmfro[2])(nd4hip_handle*, int64_t, const double*, double*);
 static int (*p_dqp3rank[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, int32_t*);
 static int (*p_dqp3ls[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t,
                           const int32_t*, int64_t, const double*, int64_t, double*, int32_t*);
@@ -124,6 +129,11 @@ static int load_library(void) {
   SYM2(p_dqrls, "nd4hip_dqrls_batched");
   SYM2(p_dgeqp3, "nd4hip_dgeqp3_batched");
   SYM2(p_dgeqp3_full, "nd4hip_dgeqp3_full_batched");
+  SYM2(p_ddet, "nd4hip_ddet_batched");
+  SYM2(p_dslogdet, "nd4hip_dslogdet_batched");
+  SYM2(p_ddettri, "nd4hip_ddettri_batched");
+  SYM2(p_dslogdettri, "nd4hip_dslogdettri_batched");
+  SYM(p_dnrmfro[0], "nd4hip_dnrmfro"); SYM(p_dnrmfro[1], "nd4hip_dnrmfro_dev");
   SYM2(p_dqp3rank, "nd4hip_dqp3rank_batched");
   SYM2(p_dsrrqr, "nd4hip_dsrrqr_batched");
   SYM2(p_durv, "nd4hip_durv_batched");
@@ -488,6 +498,72 @@ static napi_value js_durvls(napi_env env, napi_callback_info info) {
                           (const int32_t*)k.p, sK, (const double*)Y.p, sY, (double*)X.p));
   return NULL;
 }
+/* ddet_batched(batch, M, N, A, det) / dslogdet_batched(batch, M, N, A, sign, logdet)   (det / slogdet, det.js:95-106) */
+static napi_value js_ddet(napi_env env, napi_callback_info info) {
+  ARGS(5, "ddet_batched");
+  int64_t batch, M, N; opnd A, D;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &M) || get_i64(env, a[2], &N) || F64(3, A) || F64(4, D)) return NULL;
+  NEED(batch >= 0 && M >= 0 && N >= 0 && (size_t)(batch * M * N) <= A.len && (size_t)batch <= D.len, "ddet_batched: buffer too small");
+  SAME_SIDE(A.dev == D.dev, "ddet_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_ddet[A.dev](g_handle, batch, M, N, (const double*)A.p, (double*)D.p));
+  return NULL;
+}
+static napi_value js_dslogdet(napi_env env, napi_callback_info info) {
+  ARGS(6, "dslogdet_batched");
+  int64_t batch, M, N; opnd A, S, L;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &M) || get_i64(env, a[2], &N) || F64(3, A) || F64(4, S) || F64(5, L)) return NULL;
+  NEED(batch >= 0 && M >= 0 && N >= 0 && (size_t)(batch * M * N) <= A.len && (size_t)batch <= S.len && (size_t)batch <= L.len,
+       "dslogdet_batched: buffer too small");
+  SAME_SIDE(A.dev == S.dev && S.dev == L.dev, "dslogdet_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dslogdet[A.dev](g_handle, batch, M, N, (const double*)A.p, (double*)S.p, (double*)L.p));
+  return NULL;
+}
+/* ddettri_batched(batch, N, A, det) / dslogdettri_batched(batch, N, A, sign, logdet)   (det_tri / slogdet_tri, det.js:24-92) */
+static napi_value js_ddettri(napi_env env, napi_callback_info info) {
+  ARGS(4, "ddettri_batched");
+  int64_t batch, N; opnd A, D;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || F64(2, A) || F64(3, D)) return NULL;
+  NEED(batch >= 0 && N >= 0 && (size_t)(batch * N * N) <= A.len && (size_t)batch <= D.len, "ddettri_batched: buffer too small");
+  SAME_SIDE(A.dev == D.dev, "ddettri_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_ddettri[A.dev](g_handle, batch, N, (const double*)A.p, (double*)D.p));
+  return NULL;
+}
+static napi_value js_dslogdettri(napi_env env, napi_callback_info info) {
+  ARGS(5, "dslogdettri_batched");
+  int64_t batch, N; opnd A, S, L;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || F64(2, A) || F64(3, S) || F64(4, L)) return NULL;
+  NEED(batch >= 0 && N >= 0 && (size_t)(batch * N * N) <= A.len && (size_t)batch <= S.len && (size_t)batch <= L.len,
+       "dslogdettri_batched: buffer too small");
+  SAME_SIDE(A.dev == S.dev && S.dev == L.dev, "dslogdettri_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dslogdettri[A.dev](g_handle, batch, N, (const double*)A.p, (double*)S.p, (double*)L.p));
+  return NULL;
+}
+/* dnrmfro(n, A) -> number   (norm(A) 'fro', norm.js:22-85); a device operand's result comes back as a host number too */
+static napi_value js_dnrmfro(napi_env env, napi_callback_info info) {
+  ARGS(2, "dnrmfro");
+  int64_t n; opnd A;
+  if (get_i64(env, a[0], &n) || F64(1, A)) return NULL;
+  NEED(n >= 0 && (size_t)n <= A.len, "dnrmfro: buffer too small");
+  if (ensure_handle(env)) return NULL;
+  double out = 0.0;
+  if (!A.dev || n == 0) {
+    FAIL_IF(p_dnrmfro[0](g_handle, n, A.dev ? NULL : (const double*)A.p, &out));
+  } else {
+    void* d = NULL;
+    FAIL_IF(p_malloc(g_handle, sizeof(double), &d));
+    int rc = p_dnrmfro[1](g_handle, n, (const double*)A.p, (double*)d);
+    if (rc == 0) rc = p_d2h(g_handle, &out, d, sizeof(double));
+    p_free(g_handle, d);
+    FAIL_IF(rc);
+  }
+  napi_value r;
+  napi_create_double(env, out, &r);
+  return r;
+}
 /* dqp3rank_batched(batch, M, N, R, rank)   (rrqr_rank, rrqr.js:398-414; host form throws the reference's message) */
 static napi_value js_dqp3rank(napi_env env, napi_callback_info info) {
   ARGS(5, "dqp3rank_batched");
@@ -706,6 +782,11 @@ static napi_value init(napi_env env, napi_value exports) {
     {"dsvdls_batched", NULL, js_dsvdls, NULL, NULL, NULL, napi_default, NULL},
     {"dgeqp3_batched", NULL, js_dgeqp3, NULL, NULL, NULL, napi_default, NULL},
     {"dgeqp3_full_batched", NULL, js_dgeqp3_full, NULL, NULL, NULL, napi_default, NULL},
+    {"ddet_batched", NULL, js_ddet, NULL, NULL, NULL, napi_default, NULL},
+    {"dslogdet_batched", NULL, js_dslogdet, NULL, NULL, NULL, napi_default, NULL},
+    {"ddettri_batched", NULL, js_ddettri, NULL, NULL, NULL, napi_default, NULL},
+    {"dslogdettri_batched", NULL, js_dslogdettri, NULL, NULL, NULL, napi_default, NULL},
+    {"dnrmfro", NULL, js_dnrmfro, NULL, NULL, NULL, napi_default, NULL},
     {"dqp3rank_batched", NULL, js_dqp3rank, NULL, NULL, NULL, napi_default, NULL},
     {"dsrrqr_batched", NULL, js_dsrrqr, NULL, NULL, NULL, napi_default, NULL},
     {"durv_batched", NULL, js_durv, NULL, NULL, NULL, napi_default, NULL},

@@ -2,6 +2,7 @@
 // forms that the N-API shim binds live in nd4hip_host.hip.
 #include "nd4hip_internal.h"
 #include <cmath>
+#include <cstdlib>
 
 namespace {
 
@@ -362,6 +363,60 @@ extern "C" int nd4hip_durvls_batched_dev(nd4hip_handle* h, int64_t batch, int64_
   ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_urvls(h, nb, I, J, K, L, Jc, U + b0 * strideU, strideU, R + b0 * strideR, strideR, V + b0 * strideV, strideV,
                                           rank + b0 * strideRank, strideRank, Y + b0 * strideY, strideY, X + b0 * L * Jc));
   return 0;
+}
+
+// det / slogdet (det.js:95-106): det [batch] or sign, logdet [batch] of A [M, N], M >= N
+namespace {
+bool det_force_qr() { const char* e = getenv("ND4HIP_DET_FORCE_QR"); return e && *e && *e != '0'; }   // read per call
+
+int det_dev(nd4hip_handle* h, const char* op, bool log_form, int64_t batch, int64_t M, int64_t N, const double* A, double* D, double* L) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_%s: NULL handle", op);
+  Nd4DeviceGuard guard(h);
+  const double m = (double)M, n = (double)N;
+  Nd4Prof prof(h, op, (double)batch * 2.0 * (m * n * n - n * n * n / 3.0), 8.0 * batch * (double)(M * N + (log_form ? 2 : 1)));
+  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_%s: negative extent", op);
+  ND4_CHECK_ARG(M >= N, log_form ? "det_tri(A): A must be square matrices." : "det_tri(a): a must be square matrices.");
+  if (batch == 0) return 0;
+  ND4_CHECK_ARG(D && (L || !log_form) && (A || M * N == 0), "nd4hip_%s: NULL pointer", op);
+  const bool force = det_force_qr();
+  if (N == 0 || (M == N && N <= 64 && !force)) return nd4_det(h, log_form, batch, M, N, A, D, L, false);   // one launch, any batch
+  ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_det(h, log_form, nb, M, N, A + b0 * M * N, D + b0, log_form ? L + b0 : nullptr, force));
+  return 0;
+}
+
+int dettri_dev(nd4hip_handle* h, const char* op, bool log_form, int64_t batch, int64_t N, const double* A, double* D, double* L) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_%s: NULL handle", op);
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, op, (double)batch * N, 8.0 * batch * (double)(N + (log_form ? 2 : 1)));
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_%s: negative extent", op);
+  if (batch == 0) return 0;
+  ND4_CHECK_ARG(D && (L || !log_form) && (A || N == 0), "nd4hip_%s: NULL pointer", op);
+  return nd4_dettri(h, log_form, batch, N, A, N * N, D, L);
+}
+}  // namespace
+
+extern "C" int nd4hip_ddet_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* det) {
+  return det_dev(h, "ddet_batched", false, batch, M, N, A, det, nullptr);
+}
+extern "C" int nd4hip_dslogdet_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* sign, double* logdet) {
+  return det_dev(h, "dslogdet_batched", true, batch, M, N, A, sign, logdet);
+}
+// det_tri / slogdet_tri (det.js:24-92): the diagonal rule on A [N, N]
+extern "C" int nd4hip_ddettri_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* det) {
+  return dettri_dev(h, "ddettri_batched", false, batch, N, A, det, nullptr);
+}
+extern "C" int nd4hip_dslogdettri_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* sign, double* logdet) {
+  return dettri_dev(h, "dslogdettri_batched", true, batch, N, A, sign, logdet);
+}
+// norm(A) 'fro' (norm.js:22-85): one double into the device pointer out
+extern "C" int nd4hip_dnrmfro_dev(nd4hip_handle* h, int64_t n, const double* A, double* out) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dnrmfro: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "dnrmfro", 3.0 * (double)n, 8.0 * (double)n + 8.0);
+  ND4_CHECK_ARG(n >= 0, "nd4hip_dnrmfro: negative extent");
+  ND4_CHECK_ARG(out && (A || n == 0), "nd4hip_dnrmfro: NULL pointer");
+  if (n == 0) { ND4_HIP(hipMemsetAsync(out, 0, sizeof(double), h->stream)); return 0; }
+  return nd4_nrmfro(h, n, A, out);
 }
 
 // rrqr_rank (rrqr.js:398-414): rank [batch] of R [M, N]; -1 marks a matrix whose partial norms are not finite

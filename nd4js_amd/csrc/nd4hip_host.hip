@@ -620,6 +620,77 @@ extern "C" int nd4hip_durvls_batched(nd4hip_handle* h, int64_t batch, int64_t I,
   return run_host(h, batch, ops, fn);
 }
 
+// ------------------------------------------------------------------------------------ det, slogdet, det_tri, slogdet_tri, norm
+namespace {
+// the Givens tiers mark a matrix where the reference's _giv_rot_qr asserts (_giv_rot.js:34: 'Assertion failed: ' + NaN)
+int det_verdict(const double* D, int64_t batch) {
+  for (int64_t b = 0; b < batch; b++) {
+    uint64_t bits;
+    std::memcpy(&bits, D + b, sizeof bits);
+    ND4_CHECK_ARG(bits != (uint64_t)ND4HIP_DET_ASSERT_NAN_BITS, "Assertion failed: NaN");
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" int nd4hip_ddet_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* det) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_ddet_batched: NULL handle");
+  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_ddet_batched: negative extent");
+  ND4_CHECK_ARG(M >= N, "det_tri(a): a must be square matrices.");
+  if (batch == 0) return 0;
+  ND4_CHECK_ARG(det && (A || M * N == 0), "nd4hip_ddet_batched: NULL pointer");
+  std::vector<Operand> ops{in_op(A, M * N, M * N), out_op(det, 1)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_ddet_batched_dev(hd, nb, M, N, P(d, 0), P(d, 1)); };
+  ND4_TRY(run_host(h, batch, ops, fn));
+  return det_verdict(det, batch);
+}
+
+extern "C" int nd4hip_dslogdet_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* sign, double* logdet) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dslogdet_batched: NULL handle");
+  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dslogdet_batched: negative extent");
+  ND4_CHECK_ARG(M >= N, "det_tri(A): A must be square matrices.");
+  if (batch == 0) return 0;
+  ND4_CHECK_ARG(sign && logdet && (A || M * N == 0), "nd4hip_dslogdet_batched: NULL pointer");
+  std::vector<Operand> ops{in_op(A, M * N, M * N), out_op(sign, 1), out_op(logdet, 1)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
+    return nd4hip_dslogdet_batched_dev(hd, nb, M, N, P(d, 0), P(d, 1), P(d, 2));
+  };
+  ND4_TRY(run_host(h, batch, ops, fn));
+  return det_verdict(sign, batch);
+}
+
+extern "C" int nd4hip_ddettri_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* det) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_ddettri_batched: NULL handle");
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_ddettri_batched: negative extent");
+  if (batch == 0) return 0;
+  ND4_CHECK_ARG(det && (A || N == 0), "nd4hip_ddettri_batched: NULL pointer");
+  std::vector<Operand> ops{in_op(A, N * N, N * N), out_op(det, 1)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_ddettri_batched_dev(hd, nb, N, P(d, 0), P(d, 1)); };
+  return run_host(h, batch, ops, fn);
+}
+
+extern "C" int nd4hip_dslogdettri_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* sign, double* logdet) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dslogdettri_batched: NULL handle");
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dslogdettri_batched: negative extent");
+  if (batch == 0) return 0;
+  ND4_CHECK_ARG(sign && logdet && (A || N == 0), "nd4hip_dslogdettri_batched: NULL pointer");
+  std::vector<Operand> ops{in_op(A, N * N, N * N), out_op(sign, 1), out_op(logdet, 1)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
+    return nd4hip_dslogdettri_batched_dev(hd, nb, N, P(d, 0), P(d, 1), P(d, 2));
+  };
+  return run_host(h, batch, ops, fn);
+}
+
+extern "C" int nd4hip_dnrmfro(nd4hip_handle* h, int64_t n, const double* A, double* out) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dnrmfro: NULL handle");
+  ND4_CHECK_ARG(n >= 0, "nd4hip_dnrmfro: negative extent");
+  ND4_CHECK_ARG(out && (A || n == 0), "nd4hip_dnrmfro: NULL pointer");
+  if (n == 0) { *out = 0.0; return 0; }
+  std::vector<Operand> ops{in_op(A, n, n), out_op(out, 1)};     // one "matrix" of n elements
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t, void* const* d) { return nd4hip_dnrmfro_dev(hd, n, P(d, 0), P(d, 1)); };
+  return run_host(h, 1, ops, fn);
+}
+
 // ------------------------------------------------------------------------------------ SVD
 extern "C" int nd4hip_dgesvdj_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A,
                                       double* U, double* sv, double* V, int* sweeps_out, double* offnorm_out) {

@@ -130,6 +130,10 @@ int nd4_urv(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double*
 int nd4_urvls(nd4hip_handle* h, int64_t batch, int64_t I, int64_t J, int64_t K, int64_t Lv, int64_t Jc, const double* U, int64_t sU,
               const double* R, int64_t sR, const double* V, int64_t sV, const int32_t* rank, int64_t sRank, const double* Y, int64_t sY,
               double* X);
+// determinants and the Frobenius norm (det.hip)
+int nd4_dettri(nd4hip_handle* h, bool log_form, int64_t batch, int64_t N, const double* A, int64_t sA, double* D, double* L);
+int nd4_det(nd4hip_handle* h, bool log_form, int64_t batch, int64_t M, int64_t N, const double* A, double* D, double* L, bool force_qr);
+int nd4_nrmfro(nd4hip_handle* h, int64_t n, const double* A, double* out);
 int nd4_gesvdj(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A,
                double* U, double* sv, double* V, int* sweeps_out, double* offnorm_out);
 

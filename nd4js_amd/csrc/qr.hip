@@ -2163,6 +2163,10 @@ int nd4_geqrf_q(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const dou
 }
 
 // full = false: qr_decomp (qr.js:80-145): Q [M, L], R [L, N], tall input with the c >= 0 convention of :97-139.
+// Q == nullptr (full = false, M <= N): R only. Q is never formed (no Q^T accumulation in the look-ahead form, no qr_form_q) and
+//               the sign convention flips R's rows alone; R is bit-for-bit the R of the call with a Q, because everything that
+//               touches R runs unchanged. Tall input (M > N, which includes every TSQR shape) keeps the Q-forming path on a workspace
+//               Q: its c >= 0 convention is decided from Q's leading L x L block (nd4_givens_signs, lu_rule).
 // full = true : qr_decomp_full (qr.js:27-77): Q [M, M], R [M, N] with the Givens-full convention for every shape
 //               (R_jj >= 0 wherever something was eliminated; det Q = +1 fixes the last row when M <= N). For M > N the
 //               trailing M-N columns of Q are an orthonormal completion (not unique; the reference's is the one its
@@ -2527,6 +2531,13 @@ static int qr_form_q(QrJob& j, double* Q) {
 int nd4_geqrf_q_ex(nd4hip_handle* h, int64_t batch64, int64_t M64, int64_t N64, const double* A, double* Q, double* R, bool full) {
   ND4_CHECK_ARG(M64 < (1ll << 30) && N64 < (1ll << 30) && batch64 < 65536, "nd4_geqrf_q: extent out of range");
   const int M = (int)M64, N = (int)N64, batch = (int)batch64;
+  ND4_CHECK_ARG(Q != nullptr || !full, "nd4_geqrf_q: the R-only mode is qr_decomp's (full = false)");
+  if (!Q && M > N) {                                        // R only, tall: the sign rule reads Q (see above)
+    Nd4WsScope scope(h);
+    void* q = nullptr;
+    ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)batch * M * N, &q));
+    return nd4_geqrf_q_ex(h, batch, M, N, A, static_cast<double*>(q), R, false);
+  }
   const QrForm form = qr_choose(batch, M, N, full);
   if (form == QR_TSQR) return geqrf_tsqr(h, batch, M, N, A, Q, R);
   const int L = M < N ? M : N;
@@ -2550,7 +2561,7 @@ int nd4_geqrf_q_ex(nd4hip_handle* h, int64_t batch64, int64_t M64, int64_t N64, 
   ws.sWb = ws.sChunk * ws.nchunks_max;
   ws.sW2 = ws.sChunk;
   const long sWork = tall ? (long)M * N : 0;
-  const bool use_qt = form == QR_LOOKAHEAD && batch <= QR_QT_MAX_BATCH && L >= 256;      // Q^T accumulated in the shadow of the panels
+  const bool use_qt = Q && form == QR_LOOKAHEAD && batch <= QR_QT_MAX_BATCH && L >= 256;   // Q^T accumulated in the shadow of the panels
   j.use_hr = (form == QR_LOOKAHEAD && batch <= QR_ROWSPLIT_MAX_BATCH) || form == QR_TALL;   // multi-workgroup panels (CholeskyQR2 + compact orthogonal completion)
   j.sQT = use_qt ? (long)M * M : 0;
   const int hr_parts = (M + NB + 511) / 512 + 1;
@@ -2603,7 +2614,7 @@ int nd4_geqrf_q_ex(nd4hip_handle* h, int64_t batch64, int64_t M64, int64_t N64, 
   // ---- factorisation: panels left to right ----
   switch (form) {
     case QR_LOOKAHEAD: ND4_TRY(qr_factor_lookahead(j)); break;
-    case QR_TALL:      ND4_TRY(qr_factor_tall(j)); ND4_TRY(qr_form_q(j, Q)); break;   // (Q right away, ahead of R)
+    case QR_TALL:      ND4_TRY(qr_factor_tall(j)); if (Q) ND4_TRY(qr_form_q(j, Q)); break;   // (Q right away, ahead of R)
     case QR_BATCHED:   ND4_TRY(qr_factor_batched(j)); break;
     default:           ND4_TRY(qr_factor_blocked(j)); break;
   }
@@ -2618,7 +2629,7 @@ int nd4_geqrf_q_ex(nd4hip_handle* h, int64_t batch64, int64_t M64, int64_t N64, 
     const long nR = (long)Lr * N;
     hipLaunchKernelGGL(qr_scale_apply, dim3((unsigned)((nR + 255) / 256), (unsigned)batch), dim3(256), 0, h->stream, R, R, nR, exps, +1);
   }
-  if (form != QR_TALL) ND4_TRY(qr_form_q(j, Q));
+  if (form != QR_TALL && Q) ND4_TRY(qr_form_q(j, Q));
 
   // ---- reference sign convention ----
   const long sQ = (long)M * Lq;
@@ -2688,9 +2699,10 @@ int nd4_geqr2_panel(nd4hip_handle* h, int batch, int M, double* A, double* V, do
 //             and det Q = +1 (plane rotations) decides the last one when Q is square (M == L);
 //   lu_rule = true  (the c >= 0 branches for tall input, qr.js:97-139 / bidiag.js:49-61): every leading principal minor of
 //             Q's top L x L block is positive = positive pivots in its LU factorisation WITHOUT pivoting.
-// flips: L ints per matrix of scratch.
+// flips: L ints per matrix of scratch. Q == nullptr (lu_rule = false only): R's rows are flipped and there is no Q to follow them.
 int nd4_givens_signs(nd4hip_handle* h, int batch, int M, int L, int ncols, bool lu_rule, double* Q, long ldq, long sQ,
                      double* R, long ldr, long sR, const double* taus, long sTau, int* flips) {
+  ND4_CHECK_ARG(Q != nullptr || !lu_rule, "nd4_givens_signs: the c >= 0 rule needs Q");
   if (lu_rule) {
     Nd4WsScope scope2(h);
     void* q = nullptr;
@@ -2710,7 +2722,7 @@ int nd4_givens_signs(nd4hip_handle* h, int batch, int M, int L, int ncols, bool 
     hipLaunchKernelGGL(qr_flip_rows, dim3((unsigned)((ncols + 255) / 256), gy, (unsigned)batch), dim3(256), 0, h->stream,
                        R, ldr, sR, L, ncols, flips, L);
     const unsigned gq = (unsigned)(M < 512 ? M : 512);
-    hipLaunchKernelGGL(qr_flip_cols, dim3((unsigned)((L + 255) / 256), gq, (unsigned)batch), dim3(256), 0, h->stream,
+    if (Q) hipLaunchKernelGGL(qr_flip_cols, dim3((unsigned)((L + 255) / 256), gq, (unsigned)batch), dim3(256), 0, h->stream,
                        Q, ldq, sQ, M, L, flips, L);
   }
   ND4_HIP(hipGetLastError());

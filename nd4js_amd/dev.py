@@ -418,3 +418,87 @@ def urv_lstsq(U, R, V, ranks, Y):
     _lib.check(h.lib.nd4hip_durvls_batched_dev(h.ptr, _batch(lead), I, J, K, L, Jc, _p(U), I * J, _p(R), J * K, _p(V), K * L,
                                                _p(ranks), 1, _p(Y), I * Jc, _p(X)))
     return X
+
+
+def _det_dev(A, log_form):
+    _chk(A, "A")
+    if A.dim() < 2:
+        raise ValueError("qr_decomp(A): A.ndim must be at least 2.")
+    M, N = A.shape[-2:]
+    if M < N:
+        raise ValueError("det_tri(A): A must be square matrices." if log_form else "det_tri(a): a must be square matrices.")
+    lead = tuple(A.shape[:-2])
+    D = torch.empty(lead, dtype=torch.float64, device=A.device)
+    h = _h(A)
+    if log_form:
+        L = torch.empty(lead, dtype=torch.float64, device=A.device)
+        _lib.check(h.lib.nd4hip_dslogdet_batched_dev(h.ptr, _batch(lead), M, N, _p(A), _p(D), _p(L)))
+        return [D, L]
+    _lib.check(h.lib.nd4hip_ddet_batched_dev(h.ptr, _batch(lead), M, N, _p(A), _p(D)))
+    return D
+
+
+def det(A):
+    """device-resident det (det.js:95-99): float64 [...]. No host read-back: a matrix where the reference's Givens rotation
+    asserts ('Assertion failed: NaN') gets the NaN with the bits ND4HIP_DET_ASSERT_NAN_BITS (include/nd4hip.h)."""
+    return _det_dev(A, False)
+
+
+def slogdet(A):
+    """device-resident slogdet (det.js:102-106): [sign, logdet]."""
+    return _det_dev(A, True)
+
+
+def _dettri_dev(A, log_form):
+    _chk(A, "A")
+    if A.dim() < 2:
+        raise ValueError("det_tri(A): A.ndim must be at least 2." if log_form else
+                         "det_tri(a): a.shape=[%s]; a.ndim must be at least 2." % ",".join(str(s) for s in A.shape))
+    M, N = A.shape[-2:]
+    if M != N:
+        raise ValueError("det_tri(A): A must be square matrices." if log_form else "det_tri(a): a must be square matrices.")
+    lead = tuple(A.shape[:-2])
+    D = torch.empty(lead, dtype=torch.float64, device=A.device)
+    h = _h(A)
+    if log_form:
+        L = torch.empty(lead, dtype=torch.float64, device=A.device)
+        _lib.check(h.lib.nd4hip_dslogdettri_batched_dev(h.ptr, _batch(lead), N, _p(A), _p(D), _p(L)))
+        return [D, L]
+    _lib.check(h.lib.nd4hip_ddettri_batched_dev(h.ptr, _batch(lead), N, _p(A), _p(D)))
+    return D
+
+
+def det_tri(A):
+    """device-resident det_tri (det.js:24-50)."""
+    return _dettri_dev(A, False)
+
+
+def slogdet_tri(A):
+    """device-resident slogdet_tri (det.js:53-92): [sign, logdet]."""
+    return _dettri_dev(A, True)
+
+
+def rank(A):
+    """rank.js:23-27 on the device: svd_rank of the device SVD's singular values (U and V stay on the device and are dropped)."""
+    from .la import svd_rank
+    return svd_rank(svd_decomp(A)[1].cpu().numpy())
+
+
+def lstsq(A, Y):
+    """lstsq.js:22-26 on the device: svd_lstsq(svd_decomp(A), Y) with equal leading dims (the host wrapper broadcasts)."""
+    U, sv, V = svd_decomp(A)
+    return svd_lstsq(U, sv, V, Y)
+
+
+def norm(A, ord="fro", axis=None):
+    """norm.js:74-85 of a device tensor: a Python float (the one number is read back)."""
+    if not (isinstance(ord, str) and ord == "fro"):
+        from .la import _js_num
+        raise ValueError("norm(A,ord,axis): Unsupported ord: %s." % ("null" if ord is None else ord if isinstance(ord, str) else _js_num(ord)))
+    if axis is not None:
+        raise ValueError("norm(A,ord,axis): axis argument not yet supported.")
+    _chk(A, "A")
+    out = torch.zeros((), dtype=torch.float64, device=A.device)
+    h = _h(A)
+    _lib.check(h.lib.nd4hip_dnrmfro_dev(h.ptr, A.numel(), _p(A), _p(out)))
+    return float(out.item())

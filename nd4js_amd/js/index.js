@@ -337,7 +337,7 @@ function makeLa(NDA, fallback, SolveError) {
     const U = alloc(dev, batch * M * L), sv = alloc(dev, batch * L), V = alloc(dev, batch * L * N);
     la.last_svd_info = native().dgesvdj_batched(batch, M, N, view(opF64(A, dev, temps), 0), view(U, 0), view(sv, 0), view(V, 0));
     release(temps);
-    return [wrap(dev, Us, U), wrap(dev, Us.subarray(0, nd_ - 1), sv), wrap(dev, Vs, V)];
+    return [wrap(dev, Us, U), wrap(dev, Vs.subarray(0, nd_ - 1), sv), wrap(dev, Vs, V)];
   };
   la.svd_dc = la.svd_decomp;
 
@@ -714,6 +714,59 @@ function makeLa(NDA, fallback, SolveError) {
     } finally { release(temps); }
     return wrap(dev, [...lead, L, Jc], X);
   };
+
+  /* ---- det / slogdet / det_tri / slogdet_tri (det.js), rank (rank.js), lstsq (lstsq.js), norm (norm.js), csrc/det.hip ---- */
+  const f64Only = a => dtypeOf(a) === 'float64';
+  const detCommon = (name, logForm, A) => {
+    A = asarray(A);
+    if (A.ndim < 2) throw new Error('qr_decomp(A): A.ndim must be at least 2.');                 // det.js:97 / :104: qr_decomp first
+    if (!f64Only(A)) { if (fallback && fallback[name]) return fallback[name](A); throw new Error(`nd4hip.${name}: dtype ${dtypeOf(A)} is not accelerated.`); }
+    const nd_ = A.ndim, M = A.shape[nd_ - 2], N = A.shape[nd_ - 1], batch = prod(A.shape, 0, nd_ - 2);
+    if (M < N) throw new Error(logForm ? 'det_tri(A): A must be square matrices.' : 'det_tri(a): a must be square matrices.');
+    const lead = Array.from(A.shape.subarray(0, nd_ - 2));
+    const dev = isDev(A), temps = [];
+    const D = alloc(dev, batch), L = logForm ? alloc(dev, batch) : null;
+    try {
+      if (logForm) native().dslogdet_batched(batch, M, N, view(opF64(A, dev, temps), 0), view(D, 0), view(L, 0));
+      else native().ddet_batched(batch, M, N, view(opF64(A, dev, temps), 0), view(D, 0));
+    } finally { release(temps); }
+    return logForm ? [wrap(dev, lead, D), wrap(dev, lead, L)] : wrap(dev, lead, D);
+  };
+  la.det = function det(A) { return detCommon('det', false, A); };
+  la.slogdet = function slogdet(A) { return detCommon('slogdet', true, A); };
+  const detTriCommon = (name, logForm, A) => {
+    A = asarray(A);
+    if (A.ndim < 2) throw new Error(logForm ? 'det_tri(A): A.ndim must be at least 2.' : `det_tri(a): a.shape=[${Array.from(A.shape)}]; a.ndim must be at least 2.`);
+    const nd_ = A.ndim, M = A.shape[nd_ - 2], N = A.shape[nd_ - 1], batch = prod(A.shape, 0, nd_ - 2);
+    if (M !== N) throw new Error(logForm ? 'det_tri(A): A must be square matrices.' : 'det_tri(a): a must be square matrices.');
+    if (!f64Only(A)) { if (fallback && fallback[name]) return fallback[name](A); throw new Error(`nd4hip.${name}: dtype ${dtypeOf(A)} is not accelerated.`); }
+    const lead = Array.from(A.shape.subarray(0, nd_ - 2));
+    const dev = isDev(A), temps = [];
+    const D = alloc(dev, batch), L = logForm ? alloc(dev, batch) : null;
+    try {
+      if (logForm) native().dslogdettri_batched(batch, N, view(opF64(A, dev, temps), 0), view(D, 0), view(L, 0));
+      else native().ddettri_batched(batch, N, view(opF64(A, dev, temps), 0), view(D, 0));
+    } finally { release(temps); }
+    return logForm ? [wrap(dev, lead, D), wrap(dev, lead, L)] : wrap(dev, lead, D);
+  };
+  la.det_tri = function det_tri(A) { return detTriCommon('det_tri', false, A); };
+  la.slogdet_tri = function slogdet_tri(A) { return detTriCommon('slogdet_tri', true, A); };
+  la.rank = function rank(A) {                                   // rank.js:23-27
+    const [, sv] = la.svd_decomp(A);
+    return la.svd_rank(sv);
+  };
+  la.lstsq = function lstsq(A, y) {                              // lstsq.js:22-26
+    const [U, sv, V] = la.svd_decomp(A);
+    return la.svd_lstsq(U, sv, V, y);
+  };
+  la.norm = function norm(A, ord = 'fro', axis = undefined) {    // norm.js:74-85: a number, also for a DeviceNDArray
+    A = asarray(A);
+    if (ord !== 'fro') throw new Error(`norm(A,ord,axis): Unsupported ord: ${ord}.`);
+    if (axis != null) throw new Error('norm(A,ord,axis): axis argument not yet supported.');
+    if (!f64Only(A)) { if (fallback && fallback.norm) return fallback.norm(A, ord, axis); throw new Error('nd4hip.norm: dtype ' + dtypeOf(A) + ' is not accelerated.'); }
+    const n = prod(A.shape, 0, A.ndim);
+    return native().dnrmfro(n, isDev(A) ? view(A._buf, 0) : A.data);
+  };
   return la;
 }
 
@@ -724,7 +777,9 @@ function estimatedWork(name, args) {
   const dims = a => { const s = a && a.shape ? Array.from(a.shape) : null; if (!s || s.length < 2) return null;
                       let b = 1; for (let i = 0; i < s.length - 2; i++) b *= s[i]; return [b, s[s.length - 2], s[s.length - 1]]; };
   if (name === 'urv_lstsq' && Array.isArray(args[0])) args = args[0];   // urv_lstsq([U,R,V,ranks], Y): the work of U
+  if (name === 'norm') { const x = args[0]; return x && x.shape ? Array.from(x.shape).reduce((p, q) => p * q, 1) : Infinity; }   // its size
   const a = dims(args[0]);
+  if (a && (name === 'det_tri' || name === 'slogdet_tri')) return a[0] * a[1];                   // N per matrix
   if (!a) return Infinity;                                  // nested JS arrays etc.: let the accelerated path coerce them
   if (name === 'matmul2') { const b = dims(args[1]); return b ? 2 * Math.max(a[0], b[0]) * a[1] * a[2] * b[2] : Infinity; }
   if (name === 'matmul') { let w = 0; for (let i = 0; i + 1 < args.length; i++) { const x = dims(args[i]), y = dims(args[i + 1]); if (!x || !y) return Infinity; w += 2 * Math.max(x[0], y[0]) * x[1] * x[2] * y[2]; } return w; }
@@ -747,7 +802,9 @@ function install(nd, opts) {
                     ldl_decomp: nd.la.ldl_decomp, ldl_solve: nd.la.ldl_solve, hessenberg_decomp: nd.la.hessenberg_decomp, bidiag_decomp: nd.la.bidiag_decomp,
                     rrqr_decomp: nd.la.rrqr_decomp, rrqr_decomp_full: nd.la.rrqr_decomp_full, rrqr_rank: nd.la.rrqr_rank,
                     rrqr_lstsq: nd.la.rrqr_lstsq, rrqr_solve: nd.la.rrqr_solve, solve: nd.la.solve,
-                    srrqr_decomp_full: nd.la.srrqr_decomp_full, urv_decomp_full: nd.la.urv_decomp_full, urv_lstsq: nd.la.urv_lstsq};
+                    srrqr_decomp_full: nd.la.srrqr_decomp_full, urv_decomp_full: nd.la.urv_decomp_full, urv_lstsq: nd.la.urv_lstsq,
+                    det: nd.la.det, slogdet: nd.la.slogdet, det_tri: nd.la.det_tri, slogdet_tri: nd.la.slogdet_tri,
+                    rank: nd.la.rank, lstsq: nd.la.lstsq, norm: nd.la.norm};
   const acc = makeLa(nd.NDArray, original, nd.la.SingularMatrixSolveError || SingularMatrixSolveError);
   const target = Object.isFrozen(nd.la) || !Object.getOwnPropertyDescriptor(nd.la, 'matmul2').writable ? null : nd.la;
   const patched = target || Object.create(nd.la);

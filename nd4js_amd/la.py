@@ -808,3 +808,97 @@ def urv_lstsq(U, R, V=None, ranks=None, Y=None, device=None):
         except _lib.Nd4HipError as e:
             raise _arg_error(e)
     return X
+
+
+# ---------------------------------------------------------------------------------------------------
+# Determinants, rank, lstsq and norm (src/la/det.js, rank.js, lstsq.js, norm.js), csrc/det.hip
+# ---------------------------------------------------------------------------------------------------
+def _det_args(A, what):
+    A = np.asarray(A)
+    if A.ndim < 2:
+        raise ValueError("qr_decomp(A): A.ndim must be at least 2.")        # det.js:97 / :104 go through qr_decomp first
+    M, N = A.shape[-2:]
+    if M < N:                                                            # qr_decomp succeeds, det_tri rejects its M x N R
+        raise ValueError(what)
+    return _asarray(A, "det(A)"), M, N
+
+
+def det(A, device=None):
+    """det.js:95-99: det_tri(qr_decomp(A)[1]) -> float64 [...] (0-d for one matrix). Square N <= 64 runs the reference's own
+    Givens elimination (bit-identical); larger and tall inputs take qr_decomp's R without Q."""
+    A, M, N = _det_args(A, "det_tri(a): a must be square matrices.")
+    D = np.empty(A.shape[:-2])
+    h = _lib.handle(device)
+    try:
+        _lib.check(h.lib.nd4hip_ddet_batched(h.ptr, int(np.prod(A.shape[:-2], dtype=np.int64)), M, N, _ptr(A), _ptr(D)))
+    except _lib.Nd4HipError as e:
+        raise _arg_error(e)
+    return D
+
+
+def slogdet(A, device=None):
+    """det.js:102-106: [sign, logdet] of slogdet_tri(qr_decomp(A)[1])."""
+    A, M, N = _det_args(A, "det_tri(A): A must be square matrices.")
+    S, L = np.empty(A.shape[:-2]), np.empty(A.shape[:-2])
+    h = _lib.handle(device)
+    try:
+        _lib.check(h.lib.nd4hip_dslogdet_batched(h.ptr, int(np.prod(A.shape[:-2], dtype=np.int64)), M, N, _ptr(A), _ptr(S), _ptr(L)))
+    except _lib.Nd4HipError as e:
+        raise _arg_error(e)
+    return [S, L]
+
+
+def _dettri_args(A, ndim_msg, square_msg):
+    A = np.asarray(A)
+    if A.ndim < 2:
+        raise ValueError(ndim_msg)
+    M, N = A.shape[-2:]
+    if M != N:
+        raise ValueError(square_msg)
+    return _asarray(A, "det_tri(a)"), N
+
+
+def det_tri(A, device=None):
+    """det.js:24-50: the product of each matrix's diagonal in index order."""
+    a = np.asarray(A)
+    A, N = _dettri_args(a, "det_tri(a): a.shape=[%s]; a.ndim must be at least 2." % ",".join(str(s) for s in a.shape),
+                        "det_tri(a): a must be square matrices.")
+    D = np.empty(A.shape[:-2])
+    h = _lib.handle(device)
+    _lib.check(h.lib.nd4hip_ddettri_batched(h.ptr, int(np.prod(A.shape[:-2], dtype=np.int64)), N, _ptr(A), _ptr(D)))
+    return D
+
+
+def slogdet_tri(A, device=None):
+    """det.js:53-92: [sign, logdet] with Math.sign's signed zeros and NaN, the log-sum in index order."""
+    A, N = _dettri_args(A, "det_tri(A): A.ndim must be at least 2.", "det_tri(A): A must be square matrices.")
+    S, L = np.empty(A.shape[:-2]), np.empty(A.shape[:-2])
+    h = _lib.handle(device)
+    _lib.check(h.lib.nd4hip_dslogdettri_batched(h.ptr, int(np.prod(A.shape[:-2], dtype=np.int64)), N, _ptr(A), _ptr(S), _ptr(L)))
+    return [S, L]
+
+
+def rank(A, device=None):
+    """rank.js:23-27: svd_rank(svd_decomp(A)[1])."""
+    return svd_rank(svd_decomp(A, device=device)[1])
+
+
+def lstsq(A, y, device=None):
+    """lstsq.js:22-26: svd_lstsq(...svd_decomp(A), y)."""
+    U, sv, V = svd_decomp(A, device=device)
+    return svd_lstsq(U, sv, V, y, device=device)
+
+
+def norm(A, ord="fro", axis=None, device=None):
+    """norm.js:74-85 (FrobeniusNorm :22-71): the Frobenius norm of the whole array as a Python float."""
+    A = np.asarray(A)
+    if not (isinstance(ord, str) and ord == "fro"):
+        o = "null" if ord is None else ord if isinstance(ord, str) else _js_num(ord)
+        raise ValueError("norm(A,ord,axis): Unsupported ord: %s." % o)
+    if axis is not None:
+        raise ValueError("norm(A,ord,axis): axis argument not yet supported.")
+    A = _asarray(A, "norm(A)")
+    out = ctypes.c_double(0.0)
+    h = _lib.handle(device)
+    _lib.check(h.lib.nd4hip_dnrmfro(h.ptr, A.size, _ptr(A), ctypes.byref(out)))
+    return out.value
