@@ -47,6 +47,6 @@ ND4HIP_QR_STAMPS=1 python3 $R/tools/prof_ops.py qr --n 2048 --reps 1 2>&1 | grep
 ND4HIP_HESSP_STAMPS=1 ND4HIP_BDP_STAMPS=1 python3 $R/tools/time_hess.py 2048 2>&1 | grep -E '^hessp|^bdp' | sort -u > $out/hess_bidiag_phase_stamps.txt
 ( echo "== thread-per-row copy (ND4HIP_QRB_COPY_ONLY=1)"; ND4HIP_QRB_COPY_ONLY=1 python3 $R/tools/time_panel.py 2>/dev/null; echo "== whole-line copy (=2)"; ND4HIP_QRB_COPY_ONLY=2 python3 $R/tools/time_panel.py 2>/dev/null; echo "== plain device copy"; python3 $R/tools/copy_bw.py ) > $out/qr_panel_copy_ceiling.txt 2>&1
 python3 $R/tools/time_batch.py 1024 lu qr > $out/lu_qr_batch_times.txt 2>&1
-python3 $R/bench.py > $out/bench_default.json 2> $out/bench_default.err
+python3 $R/bench.py --full > $out/bench_full.json 2> $out/bench_full.err
 rm -rf $out/*/p_kernel_trace.csv $out/*/p_agent_info.csv $out/*/p_domain_stats.csv
 ls $out
