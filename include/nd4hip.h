@@ -318,7 +318,10 @@ int nd4hip_dnrmfro    (nd4hip_handle* h, int64_t n, const double* A, double* out
  * singular vectors), L = min(M,N); one-sided Jacobi with the reference's Jacobi post-processing
  * contract (_svd_jac_utils.js:123-188). sweeps_out / offnorm_out are HOST pointers (may be NULL):
  * max sweeps over the batch and the largest remaining |a_p.a_q| / (|a_p||a_q|). Both forms
- * synchronise the stream (the sweep loop is host-driven). */
+ * synchronise the stream (the sweep loop is host-driven). Each member is scaled by the exact power
+ * of two 2^-e, e = frexp exponent of its max|a|, before the QR / Jacobi and sv by 2^e afterwards:
+ * any finite scale works (no overflow or underflow of the sums of squares), and svd_decomp(2^k A)
+ * gives bit for bit the U and V of svd_decomp(A) and sv times 2^k while the entries stay normal. */
 int nd4hip_dgesvdj_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A,
                                double* U, double* sv, double* V, int* sweeps_out, double* offnorm_out);
 int nd4hip_dgesvdj_batched    (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A,

@@ -35,6 +35,13 @@ namespace {
 constexpr int NB = 16;
 constexpr int RMAX = 48;   // (slots per lane group of the global-memory fallback panel)
 [[maybe_unused]] constexpr int RMAX_USED = RMAX;
+// A reflector is formed only when the column below the diagonal has sum of squares sigma >= QR_SIGMA_MIN (or is not finite). The work
+// copy is normalised to max|a| in [1, 2), but a column can still shrink far below that: with bitwise identical columns (a matrix of
+// ones) every reflector leaves the next column at eps times the previous one, and after ~10 columns the squares are subnormal. sigma
+// and alpha^2 then carry only a few bits, beta and tau stop matching v, and H = I - tau v v^T is no longer orthogonal (Q of
+// ones(96, 80) was off by 1e-3). Below 2^-960 the column (norm < 2^-480 against a max of 1) is left as it is (tau = 0, like an
+// exactly zero column): a backward error far below eps. At or above it the subnormal terms change sigma by < 2^-90 relatively.
+constexpr double QR_SIGMA_MIN = 0x1p-960;
 constexpr int VTC_ROWS = 256;     // rows per workgroup of qr_vtc
 constexpr int VTC_COLS = 64;      // columns per workgroup of qr_vtc
 
@@ -111,7 +118,7 @@ __device__ __forceinline__ void qr_panel_body(double* __restrict__ Wm, int M, lo
     for (int w = 0; w < 16; w++) sigma += s_red[w];
     const double alpha = s_alpha;
     double beta = alpha, tau = 0.0, scale = 0.0;
-    if (sigma != 0.0) {
+    if (!(sigma < QR_SIGMA_MIN)) {                                   // (0, tiny: no reflector; NaN: as before)
       beta = -copysign(sqrt(alpha * alpha + sigma), alpha);
       tau = (beta - alpha) / beta;
       scale = 1.0 / (alpha - beta);
@@ -306,7 +313,7 @@ __device__ __forceinline__ void qr_panel_row_body(const int mat, double* __restr
 #undef ND4_RL
       const double sigma = wv[k], alpha = s_top[k & 1][k];
       double beta = alpha, tau = 0.0, scale = 0.0;
-      if (sigma != 0.0) {
+      if (!(sigma < QR_SIGMA_MIN)) {                                   // (0, tiny: no reflector; NaN: as before)
         // sqrt and the two divisions sit on the column's critical path (~100 dependent instructions): one rsqrt and one
         // rcp with two Newton steps each instead. The work copy is normalised to max|a| in [1,2), so nothing over/underflows;
         // a few ulp in (beta, tau, scale) perturb H by a few ulp, like the rounding of the update itself.
@@ -1105,7 +1112,8 @@ __device__ __forceinline__ void qrh_x_full(double* __restrict__ s_part, const do
 // Phase A rides in the same launch as well — the previous reflector on the panel's own columns, the partial Gram matrices and the
 // partial X of the NEXT panel's block cross in a first exchange, so a panel is ONE launch (all side work rides in it).
 // A flagged panel: workgroup 0 runs qr_panel_row_body (R > 0; tall panels: qr_panel_flagged in a launch of its own, as before) and
-// nobody writes partials of X: the next launch forms X itself over all rows, the last panel's narrow update goes through qrh_x_flagged.
+// nobody writes partials of X: qrh_x_flagged forms them over all rows ahead of the next launch (QrhHost::panel) and ahead of the last
+// panel's narrow update (QrhHost::finish).
 constexpr long QX_ROW_SLOT = 2560;   // words per row workgroup: values [0,256) G, [256,512) X of the next block, [512,768) top-tile Gram, 768 "stores are out", [1024,1280) Gram of Q1
 template <int R>
 __global__ __launch_bounds__(512) void qrh_bc(const QrhP P) {
@@ -1154,16 +1162,13 @@ __global__ __launch_bounds__(512) void qrh_bc(const QrhP P) {
     const bool havep = P.pj0 >= 0;
     nextupd = nc > 0 && havep;
     const double* Vp = P.Vall + mat * P.strideV + ub;
-    const bool prevflag = havep && P.flag[mat] != 0;                  // the previous panel was flagged: no partials of X
     // first the loads that head the dependent chain of the own-column update (loads return in order): X partials and T
     double xsum0 = 0.0, tprev = 0.0, xp8[8];
 #pragma unroll
     for (int p8 = 0; p8 < 8; p8++) xp8[p8] = 0.0;
     if (havep && t < 256) {
-      if (!prevflag) {
 #pragma unroll
-        for (int p8 = 0; p8 < 8; p8++) if (p8 < P.nxp) xp8[p8] = P.Xp[mat * P.strideXp + (long)p8 * 256 + t];   // (summed below, after the tile loads are under way)
-      }
+      for (int p8 = 0; p8 < 8; p8++) if (p8 < P.nxp) xp8[p8] = P.Xp[mat * P.strideXp + (long)p8 * 256 + t];   // (summed below, after the tile loads are under way)
       tprev = P.Tall[mat * P.strideT + (long)(ub / NB) * NB * NB + t];
     }
     double vs[16];
@@ -1186,19 +1191,10 @@ __global__ __launch_bounds__(512) void qrh_bc(const QrhP P) {
     }
     const int i = (t & 255) / 16, j = t % 16;
     if (havep) {
-      if (prevflag) {
-        double* mine = P.Xp + mat * P.strideXp + (long)g * 256;
-        qrh_x_full(s_buf, P.Vall + mat * P.strideV + (long)ub * P.ldv + ub, P.ldv, A + (long)ub * ld + j0, ld, M - ub, NB, mine);
-        __syncthreads();
-        if (t < 256) xsum0 = mine[t];
-        __syncthreads();
-      }
       if (t < 256) {
-        if (!prevflag) {
 #pragma unroll
-          for (int p8 = 0; p8 < 8; p8++) xsum0 += xp8[p8];
-          if (P.nxp > 8) xsum0 += qrh_sum_parts(P.Xp + mat * P.strideXp + 8 * 256 + t, P.nxp - 8);
-        }
+        for (int p8 = 0; p8 < 8; p8++) xsum0 += xp8[p8];
+        if (P.nxp > 8) xsum0 += qrh_sum_parts(P.Xp + mat * P.strideXp + 8 * 256 + t, P.nxp - 8);
         s_buf[t] = xsum0; s_T2[t] = tprev;
       }
       __syncthreads();
@@ -1620,7 +1616,7 @@ __global__ __launch_bounds__(1024) void qr_panel_part(double* __restrict__ Wm, i
       for (int w = 0; w < NW; w++) sigma += s_red[w];
       const double alpha = s_alpha;
       double beta = alpha, tau = 0.0, scale = 0.0;
-      if (sigma != 0.0) {
+      if (!(sigma < QR_SIGMA_MIN)) {                                   // (0, tiny: no reflector; NaN: as before)
         // sqrt and the two divisions sit on the column's critical path (~100 dependent instructions): one rsqrt and one
         // rcp with two Newton steps each instead. The work copy is normalised to max|a| in [1,2), so nothing over/underflows;
         // a few ulp in (beta, tau, scale) perturb H by a few ulp, like the rounding of the update itself.
@@ -2042,6 +2038,14 @@ struct QrhHost {
   // then Q^T pairs) starts one block later
   int panel(int j0, int near_end, bool with_qt, bool skip_x) {
     const int m = P.M - j0;
+    if (pj0 >= 0) {
+      // A flagged previous panel left no partials of X = V^T C for this panel's columns. They are formed here, over all rows, before
+      // the panel's launch: inside it every row workgroup updates its rows of these columns in phase A, so a workgroup that formed X
+      // over all rows there could read rows another workgroup had already updated (seen with batches: wrong columns from the panel
+      // after a rank-deficient one). Not flagged: returns at once, the partials of the previous launch stay as they are.
+      P.j0 = pj0; P.na_shift = 0;
+      hipLaunchKernelGGL(qrh_x_flagged, dim3((unsigned)P.nxp, (unsigned)batch), dim3(512), 0, h->stream, P);
+    }
     side_of(pj0, near_end, with_qt);
     P.j0 = j0; P.pj0 = pj0; P.skip_x = skip_x ? 1 : 0;
     const int nA = (m + NB + 511) / 512;

@@ -512,6 +512,51 @@ int jacobi_square(nd4hip_handle* h, int batch, int N, double* W, double* U, doub
   return 0;
 }
 
+// ---- exact power-of-two scaling of every member ----
+// The sums of squares above (row norms, Gram blocks, noise floors) overflow once entries pass ~1e154 and underflow to zero below
+// ~1e-154. The reference's svd_decomp normalises by the Frobenius norm; here each member is multiplied by 2^-e, e = the frexp
+// exponent of its max|a| (so max|a| lands in [0.5, 1)), and sv by 2^e at the end. Both are exact, so for any A and any k that keeps
+// the entries normal svd_decomp(2^k A) has bit for bit the U and V of svd_decomp(A) and sv times 2^k; U and V need nothing.
+// mx[mat] = max|a| of the member as the bits of a non-negative double: those order like unsigned integers (a NaN above +inf).
+__global__ __launch_bounds__(256) void svd_absmax(const double* __restrict__ A, long n, long sA, unsigned long long* __restrict__ mx) {
+  const double* a = A + blockIdx.y * sA;
+  unsigned long long m = 0;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(fabs(a[i]));
+    m = b > m ? b : m;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_xor(m, off); m = o > m ? o : m; }
+  if ((threadIdx.x & 63) == 0 && m) atomicMax(mx + blockIdx.y, m);
+}
+
+// e of the member (0 for a zero or non-finite member: those are left alone)
+__device__ __forceinline__ int svd_scale_exp(unsigned long long bits) {
+  const double m = __longlong_as_double((long long)bits);
+  int e = 0;
+  if (m > 0.0 && m <= DBL_MAX) (void)frexp(m, &e);
+  return e;
+}
+
+// dst = 2^-e src, member by member (dst may be src)
+__global__ __launch_bounds__(256) void svd_scale(const double* src, double* dst, long n, long s, const unsigned long long* __restrict__ mx) {
+  const int e = svd_scale_exp(mx[blockIdx.y]);
+  const double* a = src + blockIdx.y * s;
+  double* b = dst + blockIdx.y * s;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) b[i] = ldexp(a[i], -e);
+}
+
+// sv *= 2^e (ldexp: no factor 2^e is formed, which would overflow for e = 1024)
+__global__ void svd_unscale(double* __restrict__ sv, long L, long total, const unsigned long long* __restrict__ mx) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < total) sv[i] = ldexp(sv[i], svd_scale_exp(mx[i / L]));
+}
+
+dim3 svd_scale_grid(long n, int batch) {
+  const long x = (n + 2047) / 2048;                                // 8 elements per thread
+  return dim3((unsigned)(x < 1 ? 1 : (x > 4096 ? 4096 : x)), (unsigned)batch);
+}
+
 }  // namespace
 
 int nd4_gesvdj(nd4hip_handle* h, int64_t batch64, int64_t M64, int64_t N64, const double* A,
@@ -522,29 +567,50 @@ int nd4_gesvdj(nd4hip_handle* h, int64_t batch64, int64_t M64, int64_t N64, cons
   const int L = M < N ? M : N;
   Nd4WsScope scope(h);
   const long sL = (long)L * L;
+  const long sA = (long)M * N;                 // also the size of the thin Q
+  void* pm = nullptr;
+  ND4_TRY(nd4_ws_alloc(h, sizeof(unsigned long long) * (size_t)batch, &pm));
+  unsigned long long* mx = static_cast<unsigned long long*>(pm);
+  ND4_HIP(hipMemsetAsync(mx, 0, sizeof(unsigned long long) * (size_t)batch, h->stream));
+  hipLaunchKernelGGL(svd_absmax, svd_scale_grid(sA, batch), dim3(256), 0, h->stream, A, sA, sA, mx);
+  ND4_HIP(hipGetLastError());
+  auto unscale = [&]() -> int {
+    const long total = (long)batch * L;
+    hipLaunchKernelGGL(svd_unscale, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, sv, (long)L, total, mx);
+    ND4_HIP(hipGetLastError());
+    return 0;
+  };
   void* p = nullptr;
   if (M == N) {
     ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)batch * sL, &p));
     double* W = static_cast<double*>(p);
-    ND4_HIP(hipMemcpyAsync(W, A, sizeof(double) * (size_t)batch * sL, hipMemcpyDeviceToDevice, h->stream));
-    return jacobi_square(h, batch, N, W, U, sv, V, sweeps_out, offnorm_out);
+    hipLaunchKernelGGL(svd_scale, svd_scale_grid(sL, batch), dim3(256), 0, h->stream, A, W, sL, sL, mx);   // the copy Jacobi destroys
+    ND4_HIP(hipGetLastError());
+    ND4_TRY(jacobi_square(h, batch, N, W, U, sv, V, sweeps_out, offnorm_out));
+    return unscale();
   }
-  const long sA = (long)M * N;                 // also the size of the thin Q
   if (M > N) {
-    // A = Q R ; R = Ur S V  ->  U = Q Ur                         (svd_jac_2sided.js:44-47)
-    ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)batch * (sA + 2 * sL), &p));
+    // A = Q R ; R = Ur S V  ->  U = Q Ur                         (svd_jac_2sided.js:44-47), on the scaled copy As of A
+    ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)batch * (2 * sA + 2 * sL), &p));
     double* Q = static_cast<double*>(p); double* R = Q + (size_t)batch * sA; double* Ur = R + (size_t)batch * sL;
-    ND4_TRY(nd4_geqrf_q(h, batch, M, N, A, Q, R));
+    double* As = Ur + (size_t)batch * sL;
+    hipLaunchKernelGGL(svd_scale, svd_scale_grid(sA, batch), dim3(256), 0, h->stream, A, As, sA, sA, mx);
+    ND4_HIP(hipGetLastError());
+    ND4_TRY(nd4_geqrf_q(h, batch, M, N, As, Q, R));
     ND4_TRY(jacobi_square(h, batch, N, R, Ur, sv, V, sweeps_out, offnorm_out));
-    return nd4_gemm(h, false, false, M, N, N, 1.0, Q, N, sA, Ur, N, sL, 0.0, U, N, sA, batch);
+    ND4_TRY(nd4_gemm(h, false, false, M, N, N, 1.0, Q, N, sA, Ur, N, sL, 0.0, U, N, sA, batch));
+    return unscale();
   }
-  // M < N:  A^T = Q R  ->  A = R^T Q^T ; R^T = U S Vr  ->  V = Vr Q^T   (svd_jac_2sided.js:48-52)
+  // M < N:  A^T = Q R  ->  A = R^T Q^T ; R^T = U S Vr  ->  V = Vr Q^T   (svd_jac_2sided.js:48-52), At scaled in place
   ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)batch * (2 * sA + 3 * sL), &p));
   double* At = static_cast<double*>(p); double* Q = At + (size_t)batch * sA;
   double* R = Q + (size_t)batch * sA; double* Rt = R + (size_t)batch * sL; double* Vr = Rt + (size_t)batch * sL;
   ND4_TRY(nd4_transpose(h, M, N, A, N, At, M, batch, sA, sA));
+  hipLaunchKernelGGL(svd_scale, svd_scale_grid(sA, batch), dim3(256), 0, h->stream, At, At, sA, sA, mx);
+  ND4_HIP(hipGetLastError());
   ND4_TRY(nd4_geqrf_q(h, batch, N, M, At, Q, R));
   ND4_TRY(nd4_transpose(h, M, M, R, M, Rt, M, batch, sL, sL));
   ND4_TRY(jacobi_square(h, batch, M, Rt, U, sv, Vr, sweeps_out, offnorm_out));
-  return nd4_gemm(h, false, true, M, N, M, 1.0, Vr, M, sL, Q, M, sA, 0.0, V, N, sA, batch);
+  ND4_TRY(nd4_gemm(h, false, true, M, N, M, 1.0, Vr, M, sL, Q, M, sA, 0.0, V, N, sA, batch));
+  return unscale();
 }
