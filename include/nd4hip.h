@@ -88,6 +88,18 @@ int nd4hip_dgemm_batched_dev(nd4hip_handle* h, int64_t batch, int64_t I, int64_t
 int nd4hip_dgemm_batched    (nd4hip_handle* h, int64_t batch, int64_t I, int64_t K, int64_t J,
                              const double* A, int64_t strideA, const double* B, int64_t strideB, double* C);
 
+/* ---- complex matmul2: replaces matmul2_CC, matmul2_CR and matmul2_RC, src/la/matmul.js:74-87 ------------------------
+ * C[b] (I x J, complex) = A[b] (I x K) * B[b] (K x J). An operand whose flag (a_complex / b_complex) is set is complex128:
+ * interleaved (re, im) doubles, the layout of the reference's ComplexArray._array, numpy and torch; otherwise it is float64.
+ * At least one flag must be set; C is always complex and dense [batch, I, J]. Strides count elements of each operand (one
+ * complex element = one element = 16 bytes), 0 = broadcast, as nd4hip_dgemm_batched. The reference's products are formed:
+ * CC four (Re = Ar Br - Ai Bi, Im = Ar Bi + Ai Br, no 3M trick), CR and RC two, so NaN / Inf land where the reference puts
+ * them. RC runs as the real product of A with the K x 2J real view of B. */
+int nd4hip_zgemm_batched_dev(nd4hip_handle* h, int a_complex, int b_complex, int64_t batch, int64_t I, int64_t K, int64_t J,
+                             const double* A, int64_t strideA, const double* B, int64_t strideB, double* C);
+int nd4hip_zgemm_batched    (nd4hip_handle* h, int a_complex, int b_complex, int64_t batch, int64_t I, int64_t K, int64_t J,
+                             const double* A, int64_t strideA, const double* B, int64_t strideB, double* C);
+
 /* general strided form used by the decompositions and exposed for tests:
  * C = alpha * op(A) * op(B) + beta * C, row-major with leading dimensions; transA/transB != 0
  * means the stored matrix is the transpose of the operand (A stored K x M, B stored N x K). */

@@ -37,6 +37,8 @@ SIGNATURES = {
     "nd4hip_fill_uniform_dev": (c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, c_i64, c_dp]),
     "nd4hip_dgemm_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_dp, c_i64, c_dp, c_i64, c_dp]),
     "nd4hip_dgemm_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_dp, c_i64, c_dp, c_i64, c_dp]),
+    "nd4hip_zgemm_batched_dev": (c_int, [ctypes.c_void_p, c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_dp, c_i64, c_dp, c_i64, c_dp]),
+    "nd4hip_zgemm_batched": (c_int, [ctypes.c_void_p, c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_dp, c_i64, c_dp, c_i64, c_dp]),
     "nd4hip_dgemm_ex_dev": (c_int, [ctypes.c_void_p, c_int, c_int, c_i64, c_i64, c_i64, ctypes.c_double, c_dp, c_i64,
                                     c_dp, c_i64, ctypes.c_double, c_dp, c_i64]),
     "nd4hip_dgetrf_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, ctypes.c_void_p]),

@@ -44,6 +44,7 @@ static const char* (*p_last_error)(void);
 static const char* (*p_version)(void);
 /* [0] = host-pointer entry point, [1] = its _dev twin */
 static gemm_fn p_dgemm[2];
+static int (*p_zgemm[2])(nd4hip_handle*, int, int, int64_t, int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t, double*);
 static getrf_fn p_dgetrf[2];
 static geqrf_fn p_dgeqrf[2];
 static geqrf_fn p_dgeqrf_full[2];
@@ -114,6 +115,7 @@ static int load_library(void) {
   SYM(p_version, "nd4hip_version");
 #define SYM2(var, name) SYM(var[0], name); SYM(var[1], name "_dev")
   SYM2(p_dgemm, "nd4hip_dgemm_batched");
+  SYM2(p_zgemm, "nd4hip_zgemm_batched");
   SYM2(p_dgetrf, "nd4hip_dgetrf_batched");
   SYM2(p_dgeqrf, "nd4hip_dgeqrf_q_batched");
   SYM2(p_dgeqrf_full, "nd4hip_dgeqrf_full_batched");
@@ -296,6 +298,26 @@ static napi_value js_dgemm(napi_env env, napi_callback_info info) {
   SAME_SIDE(A.dev == B.dev && B.dev == C.dev, "dgemm_batched");
   if (ensure_handle(env)) return NULL;
   FAIL_IF(p_dgemm[A.dev](g_handle, batch, I, K, J, (const double*)A.p, sA, (const double*)B.p, sB, (double*)C.p));
+  return NULL;
+}
+/* zgemm_batched(a_complex, b_complex, batch, I, K, J, A, strideA, B, strideB, C): complex operands are Float64Arrays (or
+   device views) of interleaved (re, im) pairs, the reference's ComplexArray._array; extents and strides count elements, so a
+   complex operand needs 2 doubles per element. C is always complex. */
+static napi_value js_zgemm(napi_env env, napi_callback_info info) {
+  ARGS(11, "zgemm_batched");
+  int64_t ac, bc, batch, I, K, J, sA, sB; opnd A, B, C;
+  if (get_i64(env, a[0], &ac) || get_i64(env, a[1], &bc) || get_i64(env, a[2], &batch) || get_i64(env, a[3], &I) ||
+      get_i64(env, a[4], &K) || get_i64(env, a[5], &J) || F64(6, A) || get_i64(env, a[7], &sA) || F64(8, B) ||
+      get_i64(env, a[9], &sB) || F64(10, C)) return NULL;
+  NEED(ac || bc, "zgemm_batched: at least one operand must be complex");
+  NEED(batch >= 0 && I >= 0 && K >= 0 && J >= 0 && sA >= 0 && sB >= 0, "zgemm_batched: negative extent");
+  const size_t ea = ac ? 2 : 1, eb = bc ? 2 : 1;
+  NEED(batch == 0 || (ea * (size_t)((batch - 1) * sA + I * K) <= A.len && eb * (size_t)((batch - 1) * sB + K * J) <= B.len &&
+                      2 * (size_t)(batch * I * J) <= C.len),
+       "zgemm_batched: buffer too small");
+  SAME_SIDE(A.dev == B.dev && B.dev == C.dev, "zgemm_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_zgemm[A.dev](g_handle, ac != 0, bc != 0, batch, I, K, J, (const double*)A.p, sA, (const double*)B.p, sB, (double*)C.p));
   return NULL;
 }
 /* dgetrf_batched(batch, N, A, LU, P) */
@@ -770,6 +792,7 @@ static napi_value init(napi_env env, napi_value exports) {
     {"version", NULL, js_version, NULL, NULL, NULL, napi_default, NULL},
     {"devices", NULL, js_devices, NULL, NULL, NULL, napi_default, NULL},
     {"dgemm_batched", NULL, js_dgemm, NULL, NULL, NULL, napi_default, NULL},
+    {"zgemm_batched", NULL, js_zgemm, NULL, NULL, NULL, napi_default, NULL},
     {"dgetrf_batched", NULL, js_dgetrf, NULL, NULL, NULL, napi_default, NULL},
     {"dgeqrf_q_batched", NULL, js_dgeqrf, NULL, NULL, NULL, napi_default, NULL},
     {"dgeqrf_full_batched", NULL, js_dgeqrf_full, NULL, NULL, NULL, napi_default, NULL},

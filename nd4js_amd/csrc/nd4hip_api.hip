@@ -51,6 +51,31 @@ extern "C" int nd4hip_dgemm_batched_dev(nd4hip_handle* h, int64_t batch, int64_t
   return 0;
 }
 
+extern "C" int nd4hip_zgemm_batched_dev(nd4hip_handle* h, int a_complex, int b_complex, int64_t batch, int64_t I, int64_t K, int64_t J,
+                                        const double* A, int64_t strideA, const double* B, int64_t strideB, double* C) {
+  // the argument checks come first: they need no handle (and are testable without a device)
+  ND4_CHECK_ARG(a_complex || b_complex, "nd4hip_zgemm_batched: at least one operand must be complex");
+  ND4_CHECK_ARG(batch >= 0 && I >= 0 && K >= 0 && J >= 0, "nd4hip_zgemm_batched: negative extent");
+  ND4_CHECK_ARG(strideA == 0 || strideA >= I * K, "nd4hip_zgemm_batched: strideA must be 0 or >= I*K");
+  ND4_CHECK_ARG(strideB == 0 || strideB >= K * J, "nd4hip_zgemm_batched: strideB must be 0 or >= K*J");
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zgemm_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  const double ea = a_complex ? 2.0 : 1.0, eb = b_complex ? 2.0 : 1.0;     // doubles per element
+  Nd4Prof prof(h, "zgemm_batched", (double)((a_complex && b_complex ? 8.0 : 4.0) * batch * I * K * J),
+               8.0 * (2.0 * batch * I * J + ea * (strideA ? batch : 1) * I * K + eb * (strideB ? batch : 1) * K * J));
+  if (batch == 0 || I == 0 || J == 0) return 0;
+  ND4_CHECK_ARG(C && (K == 0 || (A && B)), "nd4hip_zgemm_batched: NULL matrix pointer");   // K = 0: nothing is read
+  for (int64_t b0 = 0; b0 < batch; b0 += 32768) {             // gridDim.y limit
+    const int64_t nb = batch - b0 < 32768 ? batch - b0 : 32768;
+    if (!a_complex)   // RC: A (I x K) times the K x 2J real view of B, into the I x 2J real view of C: the reference's products
+      ND4_TRY(nd4_gemm(h, false, false, I, 2 * J, K, 1.0, A + b0 * strideA, K, strideA, B + 2 * b0 * strideB, 2 * J, 2 * strideB,
+                       0.0, C + 2 * b0 * I * J, 2 * J, 2 * I * J, nb));
+    else
+      ND4_TRY(nd4_zgemm(h, b_complex != 0, nb, I, K, J, A + 2 * b0 * strideA, strideA,
+                      B + (b_complex ? 2 : 1) * b0 * strideB, strideB, C + 2 * b0 * I * J));
+  }
+  return 0;
+}
 
 extern "C" int nd4hip_dgemm_ex_dev(nd4hip_handle* h, int transA, int transB, int64_t M, int64_t N, int64_t K,
                                    double alpha, const double* A, int64_t lda, const double* B, int64_t ldb,

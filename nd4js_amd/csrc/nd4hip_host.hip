@@ -271,6 +271,34 @@ extern "C" int nd4hip_dgemm_batched(nd4hip_handle* h, int64_t batch, int64_t I, 
   return run_host(h, batch, ops, fn);
 }
 
+// complex: the same plans as nd4hip_dgemm_batched, with 16-byte elements for the complex operands
+extern "C" int nd4hip_zgemm_batched(nd4hip_handle* h, int a_complex, int b_complex, int64_t batch, int64_t I, int64_t K, int64_t J,
+                                    const double* A, int64_t strideA, const double* B, int64_t strideB, double* C) {
+  ND4_CHECK_ARG(a_complex || b_complex, "nd4hip_zgemm_batched: at least one operand must be complex");
+  ND4_CHECK_ARG(batch >= 0 && I >= 0 && K >= 0 && J >= 0, "nd4hip_zgemm_batched: negative extent");
+  ND4_CHECK_ARG(strideA == 0 || strideA >= I * K, "nd4hip_zgemm_batched: strideA must be 0 or >= I*K");
+  ND4_CHECK_ARG(strideB == 0 || strideB >= K * J, "nd4hip_zgemm_batched: strideB must be 0 or >= K*J");
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zgemm_batched: NULL handle");
+  if (batch == 0 || I == 0 || J == 0) return 0;
+  ND4_CHECK_ARG(C && (K == 0 || (A && B)), "nd4hip_zgemm_batched: NULL matrix pointer");
+  const int ac = a_complex ? 1 : 0, bc = b_complex ? 1 : 0;
+  const size_t ea = a_complex ? 2 * D : D, eb = b_complex ? 2 * D : D;
+  if (batch == 1 && K > 0) {
+    // one product: pipelined over the rows of A and C (B is a broadcast operand), one device (replicas only)
+    Plan plan; plan.min_chunk = 512;
+    std::vector<Operand> ops{in_op(A, K, K, ea), in_op(B, K * J, 0, eb), out_op(C, J, 2 * D)};
+    ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t rows, void* const* d) {
+      return nd4hip_zgemm_batched_dev(hd, ac, bc, 1, rows, K, J, P(d, 0), 0, P(d, 1), 0, P(d, 2));
+    };
+    return run_block(h, 0, 0, I, ops, fn, plan);
+  }
+  std::vector<Operand> ops{in_op(A, I * K, strideA, ea), in_op(B, K * J, strideB, eb), out_op(C, I * J, 2 * D)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
+    return nd4hip_zgemm_batched_dev(hd, ac, bc, nb, I, K, J, P(d, 0), nb > 1 ? strideA : 0, P(d, 1), nb > 1 ? strideB : 0, P(d, 2));
+  };
+  return run_host(h, batch, ops, fn);
+}
+
 // ------------------------------------------------------------------------------------ LU
 extern "C" int nd4hip_dgetrf_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* LU, int32_t* Pv) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgetrf_batched: NULL handle");

@@ -88,6 +88,10 @@ int nd4_gemm(nd4hip_handle* h, bool transA, bool transB, int64_t M, int64_t N, i
              double alpha, const double* A, int64_t lda, int64_t sA,
              const double* B, int64_t ldb, int64_t sB,
              double beta, double* C, int64_t ldc, int64_t sC, int64_t batch);
+// complex: C[b] = A[b] * B[b] on interleaved (re, im) doubles, A complex I x K, B complex (b_complex) or real K x J,
+// C dense complex [batch, I, J]; strides in elements of each operand, batch <= 65535 (zgemm.hip)
+int nd4_zgemm(nd4hip_handle* h, bool b_complex, int64_t batch, int64_t I, int64_t K, int64_t J,
+              const double* A, int64_t sA, const double* B, int64_t sB, double* C);
 
 int nd4_getrf(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* LU, int32_t* P);
 int nd4_getrf_nopivot(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* LU, int32_t* P);

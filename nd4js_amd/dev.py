@@ -40,8 +40,19 @@ def fill_uniform(seed, shape, device="cuda", offset=0):
     return out
 
 
+def _chk_mm(t, name):
+    """an operand of the complex path: its values as stored. torch's lazy conjugate / negative views (x.conj(), ...) share
+    the storage of x and only flag it, so they are materialised here (the kernels read the storage)."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in (torch.float64, torch.complex128) and t.is_contiguous()):
+        raise TypeError("%s must be a contiguous float64 or complex128 CUDA tensor" % name)
+    return t.resolve_conj().resolve_neg()
+
+
 def matmul2(a, b, out=None):
-    """[..., I, K] x [..., K, J]; leading dims must be equal or one operand plain 2-D (broadcast)."""
+    """[..., I, K] x [..., K, J]; leading dims must be equal or one operand plain 2-D (broadcast).
+    float64 x float64 -> float64; complex128 with complex128 or float64, in either order -> complex128."""
+    if getattr(a, "dtype", None) == torch.complex128 or getattr(b, "dtype", None) == torch.complex128:
+        return _zmatmul2(a, b, out)
     _chk(a, "a"), _chk(b, "b")
     I, K = a.shape[-2:]
     J = b.shape[-1]
@@ -62,6 +73,36 @@ def matmul2(a, b, out=None):
     h = _h(a)
     _lib.check(h.lib.nd4hip_dgemm_batched_dev(h.ptr, batch, I, K, J, _p(a), sA if batch > 1 else 0,
                                               _p(b), sB if batch > 1 else 0, _p(_chk(out, "out"))))
+    return out
+
+
+def _zmatmul2(a, b, out):
+    a, b = _chk_mm(a, "a"), _chk_mm(b, "b")
+    I, K = a.shape[-2:]
+    J = b.shape[-1]
+    if b.shape[-2] != K:
+        raise ValueError("The last dimension of A and the 2nd to last dimension of B do not match.")
+    la, lb = tuple(a.shape[:-2]), tuple(b.shape[:-2])
+    if la == lb:
+        lead, sA, sB = la, I * K, K * J
+    elif _batch(lb) == 1:
+        lead, sA, sB = la, I * K, 0
+    elif _batch(la) == 1:
+        lead, sA, sB = lb, 0, K * J
+    else:
+        raise ValueError("Shapes are not broadcast-compatible.")
+    batch = _batch(lead)
+    if out is None:
+        out = torch.empty(lead + (I, J), dtype=torch.complex128, device=a.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.complex128 and out.is_contiguous()
+              and tuple(out.shape) == lead + (I, J) and not out.is_conj() and not out.is_neg()):
+        # (a conjugate or negative view would read back what the kernel writes conjugated / negated)
+        raise TypeError("out must be a contiguous complex128 CUDA tensor of shape %r without a conjugate or negative bit"
+                        % (lead + (I, J),))
+    h = _h(a)
+    _lib.check(h.lib.nd4hip_zgemm_batched_dev(h.ptr, int(a.dtype == torch.complex128), int(b.dtype == torch.complex128),
+                                              batch, I, K, J, _p(a), sA if batch > 1 else 0,
+                                              _p(b), sB if batch > 1 else 0, _p(out)))
     return out
 
 

@@ -11,8 +11,9 @@
  *   const la = require('nd4js_amd/js');                 // standalone: minimal NDArray, float64 only
  *   const nd = require('nd4js'); require('nd4js_amd/js').install(nd);
  *        // drop-in: nd.la.{matmul2,matmul,qr_decomp,lu_decomp,svd_decomp,svd_dc} run on the GPU for
- *        // float64 / int32(promoted) input; other dtypes (float32, complex128, object, int32 x int32
- *        // matmul) keep going to nd4js's own functions, exactly as before.
+ *        // float64 / int32(promoted) input, matmul2 / matmul also for complex128 paired with complex128,
+ *        // float64 or int32 (results in the host module's Complex128Array); other dtypes (float32, object,
+ *        // int32 x int32 matmul, complex input to the other functions) keep going to nd4js's own functions.
  */
 const path = require('path');
 let addon = null;
@@ -74,21 +75,28 @@ class DevBuf {
   view(off) { if (!this.ext) throw new Error('nd4hip: device array was disposed.'); return {b: this.ext, o: off}; }
   free() { if (this.ext) { native().dev_free(this.ext); this.ext = null; } }
 }
+/* A host-module complex array over the interleaved (re, im) doubles `f64`, without a copy: the reference's ComplexArray constructor
+ * is (buffer, byteOffset, length in complex elements), src/dt/complex_array.js, and keeps the doubles as `_array`. */
+const complexOver = (Complex, f64) => new Complex(f64.buffer, f64.byteOffset, f64.length / 2);
+/* complex128: `Complex` is the host module's Complex128Array class; the buffer holds 2n doubles, interleaved (re, im) as
+ * the reference's ComplexArray._array, and `.data` is a Complex128Array over the downloaded Float64Array. */
 class DeviceNDArray {
-  constructor(shape, buf) {
+  constructor(shape, buf, Complex) {
     if (!(shape instanceof Int32Array)) throw new Error('Shape must be Int32Array.');
-    if (!(buf instanceof DevBuf) || buf.length !== shape.reduce((a, b) => a * b, 1)) throw new Error(`Shape [${shape}] does not match the device buffer.`);
-    this.shape = shape; this._buf = buf; this._host = null;
+    const n = shape.reduce((a, b) => a * b, 1);
+    if (!(buf instanceof DevBuf) || buf.length !== (Complex ? 2 * n : n)) throw new Error(`Shape [${shape}] does not match the device buffer.`);
+    if (Complex && buf.Ctor !== Float64Array) throw new Error('nd4hip: a complex128 device array is stored as float64 pairs.');
+    this.shape = shape; this._buf = buf; this._host = null; this._complex = Complex || null;
   }
   get ndim() { return this.shape.length; }
-  get dtype() { return this._buf.Ctor === Int32Array ? 'int32' : 'float64'; }
+  get dtype() { return this._complex ? 'complex128' : this._buf.Ctor === Int32Array ? 'int32' : 'float64'; }
   get onDevice() { return true; }
   get data() {                                   // lazy D2H (blocks until everything queued before it has finished)
     if (this._host === null) {
       if (!this._buf.ext) throw new Error('nd4hip: device array was disposed.');
       const h = new this._buf.Ctor(this._buf.length);
       native().dev_download(h, this._buf.ext, 0);
-      this._host = h;
+      this._host = this._complex ? complexOver(this._complex, h) : h;
     }
     return this._host;
   }
@@ -96,6 +104,7 @@ class DeviceNDArray {
   dispose() { this._buf.free(); }                // optional: dropped arrays are freed by the GC finalizer
 }
 const isDev = a => a instanceof DeviceNDArray;
+const isComplexDev = a => isDev(a) && a.dtype === 'complex128';
 /* singular_matrix_solve_error.js: thrown by rrqr_solve / solve of a rank-deficient system, `.x` = the least-squares solution.
  * Standalone this class is thrown; after install(nd) the host module's own nd.la.SingularMatrixSolveError is. */
 class SingularMatrixSolveError extends Error {
@@ -195,7 +204,7 @@ function productShape(sA, sB, mismatch) {
   return [lead.concat([I, J]), I, K, J];
 }
 
-function makeLa(NDA, fallback, SolveError) {
+function makeLa(NDA, fallback, SolveError, Complex) {
   const asarray = makeAsarray(NDA);
   const gpuOk = a => { const d = dtypeOf(a); return d === 'float64' || d === 'int32'; };
   const la = {};
@@ -215,7 +224,9 @@ function makeLa(NDA, fallback, SolveError) {
   };
   const release = temps => { for (const t of temps) t.free(); };
   la.DeviceNDArray = DeviceNDArray;
-  la.to_device = a => { a = asarray(a); if (isDev(a)) return a; if (!gpuOk(a)) throw new Error('nd4hip.to_device: dtype ' + dtypeOf(a) + ' is not accelerated.');
+  la.to_device = a => { a = asarray(a); if (isDev(a)) return a;
+                        if (dtypeOf(a) === 'complex128') { const Cx = needComplex('to_device'); return new DeviceNDArray(Int32Array.from(a.shape), DevBuf.from(a.data._array), Cx); }
+                        if (!gpuOk(a)) throw new Error('nd4hip.to_device: dtype ' + dtypeOf(a) + ' is not accelerated.');
                         return new DeviceNDArray(Int32Array.from(a.shape), DevBuf.from(a.data)); };
   la.to_host = a => isDev(a) ? a.toHost(NDA) : asarray(a);
   la.synchronize = () => native().synchronize();
@@ -223,12 +234,39 @@ function makeLa(NDA, fallback, SolveError) {
   la.profile_enable = on => native().profile_enable(on !== false);
   la.profile_last = () => native().profile_last();
 
+  /* complex128 lives in the host module's Complex128Array; the standalone module has none */
+  const needComplex = name => {
+    if (!Complex) throw new Error(`nd4hip.${name}: complex128 needs the host nd4js module (install(nd)); the standalone module has no complex arrays.`);
+    return Complex;
+  };
+  const opZ = (a, dev, temps) => {               // operand storage as doubles (complex: interleaved re, im) on the call's side
+    if (dtypeOf(a) !== 'complex128') return opF64(a, dev, temps);
+    if (isDev(a)) return a._buf;
+    if (!dev) return a.data._array;
+    const b = DevBuf.from(a.data._array); temps.push(b); return b;
+  };
+  /* matmul2_CC / _CR / _RC (matmul.js:74-87): zgemm_batched; strides count elements, buffer offsets count doubles */
+  const zmatmul2 = (a, b, shape, I, K, J) => {
+    const Cx = needComplex('matmul2');
+    const ac = dtypeOf(a) === 'complex128', bc = dtypeOf(b) === 'complex128', ea = ac ? 2 : 1, eb = bc ? 2 : 1;
+    const lead = shape.slice(0, -2), n = shape.reduce((m, k) => m * k, 1);
+    const dev = isDev(a) || isDev(b), temps = [];
+    const A = opZ(a, dev, temps), B = opZ(b, dev, temps), C = alloc(dev, 2 * n);
+    try {
+      for (const [cnt, offA, sA, offB, sB, offC] of bcastGroups(lead, a.shape.subarray(0, a.ndim - 2), b.shape.subarray(0, b.ndim - 2), I * K, K * J))
+        native().zgemm_batched(ac ? 1 : 0, bc ? 1 : 0, cnt, I, K, J, view(A, ea * offA), sA, view(B, eb * offB), sB, view(C, 2 * offC * I * J));
+    } finally { release(temps); }
+    return dev ? new DeviceNDArray(Int32Array.from(shape), C, Cx) : new NDA(Int32Array.from(shape), complexOver(Cx, C));
+  };
+
   la.matmul2 = function matmul2(a, b) {
     a = asarray(a); b = asarray(b);
     if (a.ndim < 2) throw new Error('A must be at least 2D.');
     if (b.ndim < 2) throw new Error('B must be at least 2D.');
     const [shape, I, K, J] = productShape(a.shape, b.shape, 'The last dimension of A and the 2nd to last dimension of B do not match.');
     const da = dtypeOf(a), db = dtypeOf(b);
+    // complex128 with complex128, float64 or int32 (either order): result complex128, the reference's products
+    if ((da === 'complex128' && (db === 'complex128' || gpuOk(b))) || (db === 'complex128' && gpuOk(a))) return zmatmul2(a, b, shape, I, K, J);
     // GPU path: at least one float64 operand and the other float64/int32 (result dtype float64, matmul.js:119);
     // int32 x int32 (wrapping Int32Array result), float32, complex128, object -> the host's own function
     if (!((da === 'float64' && gpuOk(b)) || (db === 'float64' && gpuOk(a)))) {
@@ -767,10 +805,25 @@ function makeLa(NDA, fallback, SolveError) {
     const n = prod(A.shape, 0, A.ndim);
     return native().dnrmfro(n, isDev(A) ? view(A._buf, 0) : A.data);
   };
+
+  // complex128 device arrays are accepted by matmul2 / matmul only: every other function refuses them before it looks at the
+  // buffer (which holds 2n doubles, not n float64 entries)
+  const complexOk = new Set(['matmul2', 'matmul', '_chain_plan', 'to_device', 'to_host', 'synchronize', 'profile_enable', 'profile_last']);
+  for (const k of Object.keys(la)) {
+    const f = la[k];
+    if (typeof f !== 'function' || complexOk.has(k) || f === DeviceNDArray || f === SolveError) continue;   // (classes stay as they are)
+    const g = function (...args) {
+      if (args.some(x => isComplexDev(x) || (Array.isArray(x) && x.some(isComplexDev))))
+        throw new Error(`nd4hip.${k}: complex128 device arrays are not accelerated (only matmul2 and matmul take them).`);
+      return f.apply(this, args);
+    };
+    Object.defineProperty(g, 'name', {value: f.name});
+    la[k] = g;
+  }
   return la;
 }
 
-const standalone = makeLa(NDArray, null, SingularMatrixSolveError);
+const standalone = makeLa(NDArray, null, SingularMatrixSolveError, null);
 
 // estimated work of a call (flops, SURVEY.md 8d conventions up to a constant): what install(nd, {minWork}) compares with
 function estimatedWork(name, args) {
@@ -781,8 +834,10 @@ function estimatedWork(name, args) {
   const a = dims(args[0]);
   if (a && (name === 'det_tri' || name === 'slogdet_tri')) return a[0] * a[1];                   // N per matrix
   if (!a) return Infinity;                                  // nested JS arrays etc.: let the accelerated path coerce them
-  if (name === 'matmul2') { const b = dims(args[1]); return b ? 2 * Math.max(a[0], b[0]) * a[1] * a[2] * b[2] : Infinity; }
-  if (name === 'matmul') { let w = 0; for (let i = 0; i + 1 < args.length; i++) { const x = dims(args[i]), y = dims(args[i + 1]); if (!x || !y) return Infinity; w += 2 * Math.max(x[0], y[0]) * x[1] * x[2] * y[2]; } return w; }
+  // real flops of one product: 2 IKJ real, 8 IKJ complex x complex, 4 IKJ mixed
+  const cx = x => !!x && x.dtype === 'complex128', fl = (x, y) => cx(x) && cx(y) ? 8 : cx(x) || cx(y) ? 4 : 2;
+  if (name === 'matmul2') { const b = dims(args[1]); return b ? fl(args[0], args[1]) * Math.max(a[0], b[0]) * a[1] * a[2] * b[2] : Infinity; }
+  if (name === 'matmul') { let w = 0; for (let i = 0; i + 1 < args.length; i++) { const x = dims(args[i]), y = dims(args[i + 1]); if (!x || !y) return Infinity; w += fl(args[i], args[i + 1]) * Math.max(x[0], y[0]) * x[1] * x[2] * y[2]; } return w; }
   return a[0] * a[1] * a[2] * Math.min(a[1], a[2]);
 }
 
@@ -805,7 +860,7 @@ function install(nd, opts) {
                     srrqr_decomp_full: nd.la.srrqr_decomp_full, urv_decomp_full: nd.la.urv_decomp_full, urv_lstsq: nd.la.urv_lstsq,
                     det: nd.la.det, slogdet: nd.la.slogdet, det_tri: nd.la.det_tri, slogdet_tri: nd.la.slogdet_tri,
                     rank: nd.la.rank, lstsq: nd.la.lstsq, norm: nd.la.norm};
-  const acc = makeLa(nd.NDArray, original, nd.la.SingularMatrixSolveError || SingularMatrixSolveError);
+  const acc = makeLa(nd.NDArray, original, nd.la.SingularMatrixSolveError || SingularMatrixSolveError, (nd.dt && nd.dt.Complex128Array) || null);
   const target = Object.isFrozen(nd.la) || !Object.getOwnPropertyDescriptor(nd.la, 'matmul2').writable ? null : nd.la;
   const patched = target || Object.create(nd.la);
   const route = k => {
@@ -829,7 +884,7 @@ function install(nd, opts) {
 }
 
 module.exports = Object.assign(standalone, {
-  NDArray, DeviceNDArray, SingularMatrixSolveError, install, bcastGroups,
+  NDArray, DeviceNDArray, SingularMatrixSolveError, install, bcastGroups, complexOver,
   accelerated: a => !!a && (isDev(a) || a.data instanceof Float64Array || a.data instanceof Int32Array),
   device_count: () => native().device_count(),
   devices: () => native().devices(),            // ids behind the handle (ND4HIP_DEVICES=all|0,1,...: batched host calls are sharded)

@@ -2,7 +2,7 @@
 error text) on top of the C ABI — used by the parity tests and bench.py. The production host is the
 JS wrapper nd4js_amd/js/index.js over the N-API shim; both call the same libnd4hip.so entry points.
 
-  matmul2(a, b)        src/la/matmul.js:91-147      -> nd4hip_dgemm_batched
+  matmul2(a, b)        src/la/matmul.js:91-147      -> nd4hip_dgemm_batched, complex128: nd4hip_zgemm_batched
   matmul(*ms)          src/la/matmul.js:150-236     (chain ordering stays on the host)
   qr_decomp(A)         src/la/qr.js:80-145          -> nd4hip_dgeqrf_q_batched
   lu_decomp(A)         src/la/lu.js:24-81           -> nd4hip_dgetrf_batched
@@ -10,7 +10,8 @@ JS wrapper nd4js_amd/js/index.js over the N-API shim; both call the same libnd4h
 
 Inputs are numpy arrays / nested lists (NDArray analogue: dense, row-major, leading axes = batch).
 Only float64 (and int32 promoted to float64 for QR/LU/SVD, as qr.js:31-37, lu.js:27, svd_dc.js:904
-do) runs here; other dtypes raise TypeError — there is NO CPU fallback in this package.
+do) runs here, plus complex128 (paired with complex128, float64 or int32) in matmul2 / matmul; other
+dtypes raise TypeError — there is NO CPU fallback in this package.
 """
 import ctypes
 
@@ -26,6 +27,16 @@ def _asarray(a, what):
     if a.dtype != np.float64:
         raise TypeError("%s: only float64 (or int32 promoted to float64) runs on the GPU path, got %s" % (what, a.dtype))
     return np.ascontiguousarray(a)
+
+
+def _asarray_mm(a, what):
+    """matmul operands: complex128 as it is (interleaved re, im: the reference's ComplexArray._array layout), else _asarray."""
+    a = np.asarray(a)
+    if a.dtype == np.complex128:
+        return np.ascontiguousarray(a)
+    if a.dtype.kind == "c":
+        raise TypeError("%s: only complex128 runs on the GPU path, got %s" % (what, a.dtype))
+    return _asarray(a, what)
 
 
 def _ptr(a):
@@ -61,8 +72,8 @@ def _bcast_groups(lead, la, lb, IK, KJ):
 def matmul2(a, b, device=None, out=None):
     """`out`: optional preallocated C-contiguous float64 result (a fresh 128 MiB array costs 8-15 ms of page faults on its first
     write — the OS's price, tools/pcie_fresh.hip — which a caller that reuses buffers does not pay)."""
-    a = _asarray(a, "matmul2(a,b)")
-    b = _asarray(b, "matmul2(a,b)")
+    a = _asarray_mm(a, "matmul2(a,b)")
+    b = _asarray_mm(b, "matmul2(a,b)")
     if a.ndim < 2:
         raise ValueError("A must be at least 2D.")
     if b.ndim < 2:
@@ -75,11 +86,23 @@ def matmul2(a, b, device=None, out=None):
         lead = np.broadcast_shapes(a.shape[:-2], b.shape[:-2])
     except ValueError:
         raise ValueError("Shapes are not broadcast-compatible.")
-    c = np.empty(tuple(lead) + (I, J), dtype=np.float64) if out is None else out
-    if c.shape != tuple(lead) + (I, J) or c.dtype != np.float64 or not c.flags.c_contiguous:
-        raise ValueError("matmul2(a,b,out): out must be a C-contiguous float64 array of shape %r" % (tuple(lead) + (I, J),))
+    ac, bc = a.dtype == np.complex128, b.dtype == np.complex128
+    dt = np.complex128 if ac or bc else np.float64
+    c = np.empty(tuple(lead) + (I, J), dtype=dt) if out is None else out
+    if c.shape != tuple(lead) + (I, J) or c.dtype != dt or not c.flags.c_contiguous:
+        raise ValueError("matmul2(a,b,out): out must be a C-contiguous %s array of shape %r" % (np.dtype(dt).name, tuple(lead) + (I, J)))
     h = _lib.handle(device)
-    for cnt, offA, sA, offB, sB, offC in _bcast_groups(tuple(lead), a.shape[:-2], b.shape[:-2], I * K, K * J):
+    groups = _bcast_groups(tuple(lead), a.shape[:-2], b.shape[:-2], I * K, K * J)
+    if ac or bc:
+        # strides and offsets count elements of each operand: 16 bytes for a complex one, 8 for a real one
+        for cnt, offA, sA, offB, sB, offC in groups:
+            _lib.check(h.lib.nd4hip_zgemm_batched(
+                h.ptr, int(ac), int(bc), cnt, I, K, J,
+                ctypes.c_void_p(a.ctypes.data + a.itemsize * offA), sA,
+                ctypes.c_void_p(b.ctypes.data + b.itemsize * offB), sB,
+                ctypes.c_void_p(c.ctypes.data + 16 * offC * I * J)))
+        return c
+    for cnt, offA, sA, offB, sB, offC in groups:
         _lib.check(h.lib.nd4hip_dgemm_batched(
             h.ptr, cnt, I, K, J,
             ctypes.c_void_p(a.ctypes.data + 8 * offA), sA,
@@ -133,7 +156,7 @@ def chain_plan(shapes):
 def matmul(*matrices, device=None, _matmul2=None):
     """Product of a chain of matrices in the FLOP-optimal order (contract of matmul.js:150-236): one operand
     is returned as is, two go straight to matmul2, longer chains are parenthesised by `chain_plan`."""
-    ms = [_asarray(m, "matmul(...)") for m in matrices]
+    ms = [_asarray_mm(m, "matmul(...)") for m in matrices]
     mm = _matmul2 or (lambda x, y: matmul2(x, y, device))
     if len(ms) == 1:
         return ms[0]
