@@ -15,6 +15,7 @@
  *   node oracle/gen_golden.js c5 [stride]      # 512^2 SVDs of every `stride`-th batch member
  *   node oracle/gen_golden.js chain            # matmul(...ms) chains: hand cases of matmul_test.js:32-79 + seeded 3-5 operand chains
  *   node oracle/gen_golden.js c3b              # 4096^2 QR + LU (rows beyond the 2048-row register panels) (~3 min)
+ *   node oracle/gen_golden.js c6               # 2048^2-class Hessenberg + bidiagonal samples (~2 min)
  */
 'use strict';
 const fs = require('fs'), path = require('path');
@@ -446,6 +447,49 @@ if (what === 'c4') {
   const [ui, uv] = sample(U.data, 4096, 901), [vi, vv] = sample(V.data, 4096, 902);
   record('c4_svd2048', {op: 'svd_decomp', seed: 9, shape: [N, N], ref_seconds: secs},
     {sv: [sv.data, [N]], Uidx: [ui, [4096]], Uval: [uv, [4096]], Vidx: [vi, [4096]], Vval: [vv, [4096]]});
+}
+
+if (what === 'c6') {
+  /* 2048^2-class Hessenberg and bidiagonal reductions: the sizes of the largest one-launch build (hessp<8> / bdp<8>) and of the
+     fall-backs behind it. Sampled (the full factors would be 32 MB a case): diagonals in full, hashed entries, row sums, norms. */
+  const rowsOf = (seed, N) => { const r = new Int32Array(64); for (let k = 0; k < 64; k++) r[k] = hashIdx(seed, k, N); return r; };
+  const rowsum = (X, rows, N) => {
+    const s = new Float64Array(rows.length);
+    rows.forEach((r, k) => { let t = 0; for (let j = 0; j < N; j++) t += X[r * N + j]; s[k] = t; });
+    return s;
+  };
+  const caseHess = (name, seed, N) => {
+    const a = fill(seed, N * N), t = Date.now();
+    const [U, H] = nd.la.hessenberg_decomp(NDA([N, N], a)); const secs = (Date.now() - t) / 1e3;
+    const dH = new Float64Array(N), sH = new Float64Array(N - 1);
+    for (let i = 0; i < N; i++) dH[i] = H.data[i * N + i];
+    for (let i = 1; i < N; i++) sH[i - 1] = H.data[i * N + i - 1];
+    const hi = new Int32Array(4096), hv = new Float64Array(4096);        // entries of the band j >= i - 1 (below it H is 0)
+    for (let k = 0; k < 4096; k++) {
+      const i = hashIdx(seed * 10 + 1, 2 * k, N), j0 = Math.max(0, i - 1), j = j0 + hashIdx(seed * 10 + 1, 2 * k + 1, N - j0);
+      hi[k] = i * N + j; hv[k] = H.data[hi[k]];
+    }
+    const [ui, uv] = sample(U.data, 4096, seed * 10 + 2), rows = rowsOf(seed * 10 + 3, N);
+    record(name, {op: 'hessenberg_decomp_sampled', seed, shape: [N, N], froH: fro(H.data), ref_seconds: secs},
+      {diagH: [dH, [N]], subH: [sH, [N - 1]], Hidx: [hi, [4096]], Hval: [hv, [4096]], Uidx: [ui, [4096]], Uval: [uv, [4096]],
+       rows: [rows, [64]], Hrowsum: [rowsum(H.data, rows, N), [64]], Urowsum: [rowsum(U.data, rows, N), [64]]});
+  };
+  const caseBd = (name, seed, M, N) => {
+    const a = fill(seed, M * N), t = Date.now();
+    const [U, B, V] = nd.la.bidiag_decomp(NDA([M, N], a)); const secs = (Date.now() - t) / 1e3;
+    const I = B.shape[0], J = B.shape[1];
+    const dB = new Float64Array(I), sB = new Float64Array(J - 1);       // B[i, i] and B[i, i + 1]
+    for (let i = 0; i < I; i++) dB[i] = B.data[i * J + i];
+    for (let i = 0; i + 1 < J; i++) sB[i] = B.data[i * J + i + 1];
+    const [ui, uv] = sample(U.data, 4096, seed * 10 + 2), [vi, vv] = sample(V.data, 4096, seed * 10 + 4);
+    record(name, {op: 'bidiag_decomp_sampled', seed, shape: [M, N], shapeB: [I, J], froB: fro(B.data), ref_seconds: secs},
+      {diagB: [dB, [I]], superB: [sB, [J - 1]], Uidx: [ui, [4096]], Uval: [uv, [4096]], Vidx: [vi, [4096]], Vval: [vv, [4096]]});
+  };
+  caseHess('c6_hess2048', 61, 2048);
+  caseHess('c6_hess2047', 62, 2047);            // odd: zero-padded tiles in hessp<8>, the unblocked path under NO_PERSIST
+  caseBd('c6_bidiag2048', 63, 2048, 2048);
+  caseBd('c6_bidiag2048x1152', 64, 2048, 1152);
+  caseBd('c6_bidiag1152x2048', 65, 1152, 2048);  // M < N: B is I x (I + 1)
 }
 
 if (what === 'c5') {

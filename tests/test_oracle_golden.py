@@ -266,3 +266,28 @@ def test_bidiag_bit_exact(golden, name):
     u, b, v = oracle.bidiag_decomp(bidiag_input(g))
     assert u.shape == g["U"].shape and b.shape == g["B"].shape and v.shape == g["V"].shape
     assert np.array_equal(b, g["B"]) and np.array_equal(u, g["U"]) and np.array_equal(v, g["V"])
+
+
+# ---- 2048^2-class fixtures of the reductions (gen_golden.js c6): sampled, the full factors are 32 MB each ----
+def test_hessenberg_2048_sampled(golden):
+    """The oracle's Hessenberg reduction reproduces the reference's at 2048^2 bit for bit: both diagonals in full, entries sampled from
+    the band j >= i - 1 of H and from U, the row sums of 64 rows. The GPU tests at this size compare with these fixtures, and at
+    1025 / 1536 with the oracle directly."""
+    g = golden("c6_hess2048")
+    u, h = oracle.hessenberg_decomp(rng.matrix(g.seed, *g.shape))
+    assert np.array_equal(np.diagonal(h), g["diagH"]) and np.array_equal(np.diagonal(h, -1), g["subH"])
+    assert np.array_equal(h.reshape(-1)[g["Hidx"]], g["Hval"]) and np.array_equal(u.reshape(-1)[g["Uidx"]], g["Uval"])
+    rows = g["rows"]
+    assert np.array_equal(np.cumsum(h[rows], axis=1)[:, -1], g["Hrowsum"])          # summed left to right, as the generator does
+    assert np.array_equal(np.cumsum(u[rows], axis=1)[:, -1], g["Urowsum"])
+    assert np.isclose(np.linalg.norm(h), g.froH, rtol=1e-14)
+
+
+def test_bidiag_2048_sampled(golden):
+    """The same for the bidiagonal reduction at 2048^2: both diagonals of B in full, sampled entries of U and V."""
+    g = golden("c6_bidiag2048")
+    u, b, v = oracle.bidiag_decomp(rng.matrix(g.seed, *g.shape))
+    assert b.shape == tuple(g.shapeB)
+    assert np.array_equal(np.diagonal(b), g["diagB"]) and np.array_equal(np.diagonal(b, 1), g["superB"])
+    assert np.array_equal(u.reshape(-1)[g["Uidx"]], g["Uval"]) and np.array_equal(v.reshape(-1)[g["Vidx"]], g["Vval"])
+    assert np.isclose(np.linalg.norm(b), g.froB, rtol=1e-14)
