@@ -42,7 +42,7 @@ extern "C" int nd4hip_dgemm_batched_dev(nd4hip_handle* h, int64_t batch, int64_t
   ND4_CHECK_ARG(strideA == 0 || strideA >= I * K, "nd4hip_dgemm_batched: strideA must be 0 or >= I*K");
   ND4_CHECK_ARG(strideB == 0 || strideB >= K * J, "nd4hip_dgemm_batched: strideB must be 0 or >= K*J");
   if (batch == 0 || I == 0 || J == 0) return 0;
-  ND4_CHECK_ARG(A && B && C, "nd4hip_dgemm_batched: NULL matrix pointer");
+  ND4_CHECK_ARG(C && (K == 0 || (A && B)), "nd4hip_dgemm_batched: NULL matrix pointer");   // K = 0: nothing is read, C = 0
   for (int64_t b0 = 0; b0 < batch; b0 += 32768) {             // gridDim.y limit
     const int64_t nb = batch - b0 < 32768 ? batch - b0 : 32768;
     ND4_TRY(nd4_gemm(h, false, false, I, J, K, 1.0, A + b0 * strideA, K, strideA, B + b0 * strideB, J, strideB,

@@ -91,6 +91,12 @@ def test_inputs_untouched_and_zero_extent(la):
     a0, b0 = a.copy(), b.copy()
     la.matmul2(a, b)
     assert np.array_equal(a, a0) and np.array_equal(b, b0)
+    # zero extents: I = 0 and J = 0 give empty results, K = 0 an empty sum, that is zeros (also over an `out` that held NaN)
+    for sa, sb, sc in (((0, 20), (20, 20), (0, 20)), ((20, 20), (20, 0), (20, 0)), ((20, 0), (0, 20), (20, 20)),
+                       ((3, 5, 0), (3, 0, 7), (3, 5, 7)), ((3, 5, 0), (0, 7), (3, 5, 7)), ((2, 0, 4), (4, 7), (2, 0, 7))):
+        c = la.matmul2(np.zeros(sa), np.zeros(sb))
+        assert c.shape == sc and c.dtype == np.float64 and np.array_equal(c, np.zeros(sc)), (sa, sb)
+        assert np.array_equal(la.matmul2(np.zeros(sa), np.zeros(sb), out=np.full(sc, np.nan)), np.zeros(sc)), (sa, sb)
 
 
 def test_special_values_propagate(la):
