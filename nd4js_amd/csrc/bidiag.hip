@@ -801,6 +801,156 @@ int reflect_right(nd4hip_handle* h, int batch, const Blk& b, const double* v, lo
   return 0;
 }
 
+// ---- host driver: one function per factorisation path and per way of forming U and V; nd4_gebrd keeps allocation, path choice
+//      and the sign convention ----
+// what the paths share: the working copy W [M][N], the left reflectors UL [M][K] with their taus, the right ones VR [K][N] (unit
+// vectors) with their on/off flags
+struct BdCall {
+  nd4hip_handle* h;
+  int batch, M, N, K, J, mx;
+  double *W, *UL, *VR, *tauL; int* flagR;
+  BdWs ws;
+};
+// s_sleep(8) units (~0.22 us) before bdp's first look of rounds 1 / 3 (high byte) and rounds 2 / 4 (low byte)
+constexpr int BDP_DELAY = 0 << 8 | 4;
+using bdp_fn = void (*)(double*, int, int, int, double*, double*, double*, int*, BdPx, int*, int, long long*, int);
+// E x E elements per thread: the smallest tile of 16 E that covers max(M, N) with 16 x 16 workgroups
+bdp_fn bdp_for(int mx) { return mx <= 512 ? bdp<2> : (mx <= 1024 ? bdp<4> : bdp<8>); }
+
+// One launch: 16 x 16 workgroups keep the matrix in registers for the whole reduction (see bdp)
+int gebrd_persistent(const BdCall& c) {
+  nd4hip_handle* h = c.h;
+  const int M = c.M, N = c.N, K = c.K;
+  const int E = c.mx <= 512 ? 2 : (c.mx <= 1024 ? 4 : 8), T = 16 * E;
+  const size_t V1 = 3 * T, V2 = 2 * E, V3 = T, V4 = 2 * E;
+  const size_t xbytes = 16 * 2 * 256 * (V1 + V2 + V3 + V4) + (size_t)BP_NREP * (BP_REP_A2 + BP_REP_A4);
+  Nd4WsScope scope(h);
+  void* qp = nullptr;
+  ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)K * M + xbytes + 64, &qp));
+  double* ULt = static_cast<double*>(qp);                  // [K][M]: reflector i as a row (transposed into UL at the end)
+  BdPx X;
+  X.base = reinterpret_cast<qx_u64*>(ULt + (size_t)K * M);
+  X.o1 = 0; X.o2 = X.o1 + (unsigned)(2 * 256 * V1 * 16); X.o3 = X.o2 + (unsigned)(2 * 256 * V2 * 16); X.o4 = X.o3 + (unsigned)(2 * 256 * V3 * 16);
+  X.oA2 = X.o4 + (unsigned)(2 * 256 * V4 * 16); X.oA4 = X.oA2 + BP_NREP * BP_REP_A2; X.bytes = X.oA4 + BP_NREP * BP_REP_A4;
+  X.abort = reinterpret_cast<int*>(reinterpret_cast<char*>(X.base) + xbytes);
+  ND4_HIP(hipMemsetAsync(X.base, 0, xbytes + 64, h->stream));
+  static const bool want_stamps = getenv("ND4HIP_BDP_STAMPS") != nullptr;
+  long long* stamps = nullptr;
+  if (want_stamps) { void* sp = nullptr; ND4_TRY(nd4_ws_alloc(h, sizeof(long long) * 256 * 8, &sp)); stamps = static_cast<long long*>(sp); }
+  hipLaunchKernelGGL(bdp_for(c.mx), dim3(256), dim3(256), 0, h->stream, c.W, M, N, K, ULt, c.tauL, c.VR, c.flagR, X, h->xstat, BDP_DELAY, stamps, nd4_test_drop_panel());
+  ND4_HIP(hipGetLastError());
+  if (stamps) {                                     // per step, in us: left reflector | round 1 | sums + round 2 | right reflector | round 3 | sums + round 4 | update
+    long long hs[256 * 8];
+    ND4_HIP(hipMemcpyAsync(hs, stamps, sizeof(hs), hipMemcpyDeviceToHost, h->stream));
+    ND4_HIP(hipStreamSynchronize(h->stream));
+    for (int g : {0, 119, 255})
+      fprintf(stderr, "bdp %dx%d wg %3d: left %.2f  r1 %.2f  r2 %.2f  right %.2f  r3 %.2f  r4 %.2f  update %.2f us per step\n", M, N, g,
+              hs[g * 8] * 0.01 / K, hs[g * 8 + 1] * 0.01 / K, hs[g * 8 + 2] * 0.01 / K, hs[g * 8 + 3] * 0.01 / K, hs[g * 8 + 4] * 0.01 / K,
+              hs[g * 8 + 5] * 0.01 / K, hs[g * 8 + 6] * 0.01 / K);
+  }
+  return nd4_transpose(h, K, M, ULt, M, c.UL, K, 1, 0, 0);
+}
+
+// Fused: two launches per step (bd2_colpass, bd2_rowpass), one matrix
+int gebrd_fused(const BdCall& c) {
+  nd4hip_handle* h = c.h;
+  const int M = c.M, N = c.N, K = c.K, mx = c.mx;
+  double* ucol = c.ws.zpart;                               // M doubles (the partial sums of the generic form are not needed)
+  double* rowfin = ucol + mx;                              // N doubles
+  double* ubuf[2] = {rowfin + mx, rowfin + 2 * mx};        // contiguous u of the previous / the current step
+  constexpr int PMAXZ = 8;
+  double* zbuf[2] = {rowfin + 3 * mx, rowfin + (3 + PMAXZ) * (size_t)mx};     // z in up to PMAXZ row parts, alternating by step
+  int Pprev = 1;
+  hipLaunchKernelGGL(bd2_init_ucol, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, h->stream, c.W, M, N, ucol);
+  int prev = -1;                                           // step whose rank-2 update and row are still pending
+  for (int i = 0; i < K; i++) {
+    const int nc = N - i - 1, nr = M - i - 1;
+    const int has_right = (i + 1 < N - 1) ? 1 : 0;
+    const int ncb = nc > 0 ? (nc + 15) / 16 : 1;
+    // two row parts (z as two partial sums added by its readers) while one part per column block would leave half of the CUs idle;
+    // more parts cost more than they give (every part repeats the reflector prologue, every reader adds P partials: 4-8 parts
+    // on 256 threads 71 ms against 63 at 2048^2)
+    const int P = (ncb <= 128 && M - i >= 512) ? 2 : 1;
+    const int rpp = ((((M - i) + P - 1) / P) + 15) & ~15;
+    hipLaunchKernelGGL(bd2_colpass, dim3((unsigned)ncb, (unsigned)P), dim3(CPT), sizeof(double) * 3 * (size_t)rpp, h->stream,
+                       c.W, M, N, i, c.UL, K, c.tauL, ucol, zbuf[(i + 1) & 1], Pprev, zbuf[i & 1], prev, ubuf[(i + 1) & 1], ubuf[i & 1], c.ws.y, c.VR, rowfin);
+    prev = -1;
+    if (nc <= 0) continue;
+    hipLaunchKernelGGL(bd2_rowpass, dim3((unsigned)(nr > 0 ? (nr + 3) / 4 : 1)), dim3(256), sizeof(double) * 2 * (size_t)nc, h->stream,
+                       c.W, M, N, i, c.UL, K, zbuf[i & 1], P, c.VR, c.flagR, c.ws.y, has_right, rowfin, ubuf[i & 1], ucol);
+    prev = i; Pprev = P;
+  }
+  if (prev >= 0)                                           // only for M < N: the last step has no rows below, its row is all that is pending
+    hipLaunchKernelGGL(bd2_finish_row, dim3((unsigned)((N - prev - 1 + 255) / 256)), dim3(256), 0, h->stream, c.W, N, prev, rowfin);
+  ND4_HIP(hipGetLastError());
+  return 0;
+}
+
+// Generic (batches, small or very large shapes): every step as reflector + left update + reflector + right update
+int gebrd_per_step(const BdCall& c) {
+  nd4hip_handle* h = c.h;
+  const int M = c.M, N = c.N, K = c.K, batch = c.batch;
+  const long sW = (long)M * N, sUL = (long)M * K, sVRm = (long)K * N;
+  for (int i = 0; i < K; i++) {
+    hipLaunchKernelGGL(bd_vec_col, dim3((unsigned)batch), dim3(256), 0, h->stream, c.W, M, N, i, c.UL, K, c.tauL);
+    {
+      Blk b{c.W, N, sW, i, M, i + 1, N};                     // (I - tau u u^T) on the columns to the right
+      ND4_TRY(reflect_left(h, batch, b, c.UL, K, sUL, i, c.tauL, K, i, c.ws));
+    }
+    if (i + 1 < N - 1) {                                     // something to the right of the super-diagonal
+      hipLaunchKernelGGL(bd_vec_row, dim3((unsigned)batch), dim3(256), 0, h->stream, c.W, M, N, i, c.VR, K, c.flagR);
+      Blk b{c.W, N, sW, i + 1, M, i + 1, N};                 // rows below, same reflector from the right
+      ND4_TRY(reflect_right(h, batch, b, c.VR + (long)i * N, sVRm, c.flagR, K, i, c.ws));
+    }
+  }
+  return 0;
+}
+
+// One big matrix: U and V at once from the compact-WY form of the stored reflectors (nd4_wy_form, shared with QR):
+// U = [I;0] - UL (T_L UL[0:K,:]^T) with the taus on T_L's diagonal; V^T[:, 0:J] = E_J - VR^T (T_R VR[:,0:J]) with
+// tau = 2 for the unit vectors of the right reflectors (a skipped step stored v = 0 and drops out).
+int gebrd_form_uv_wy(const BdCall& c, double* U, double* V) {
+  nd4hip_handle* h = c.h;
+  const int M = c.M, N = c.N, K = c.K, J = c.J;
+  Nd4WsScope scope(h);
+  void* q = nullptr;
+  ND4_TRY(nd4_ws_alloc(h, sizeof(double) * ((size_t)N * K + (size_t)N * J + (size_t)K + 16), &q));
+  double* VRt = static_cast<double*>(q);                   // N x K: column k = v_k
+  double* Vt = VRt + (size_t)N * K;                        // N x J
+  double* twos = Vt + (size_t)N * J;
+  hipLaunchKernelGGL(bd_fill, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, h->stream, twos, K, 2.0);
+  for (int m = 0; m < c.batch; m++) {
+    ND4_TRY(nd4_wy_form(h, M, K, c.UL + (size_t)m * M * K, c.tauL + (size_t)m * K, 1, U + (size_t)m * M * K, K));
+    ND4_TRY(nd4_transpose(h, K, N, c.VR + (size_t)m * K * N, N, VRt, K, 1, 0, 0));
+    ND4_TRY(nd4_wy_form(h, N, K, VRt, twos, 1, Vt, J));
+    ND4_TRY(nd4_transpose(h, N, J, Vt, J, V + (size_t)m * J * N, N, 1, 0, 0));
+  }
+  return 0;
+}
+// Otherwise the reflectors applied backwards to the identity: U = H_0 ... H_{K-1} [I; 0], V = first J rows of H^R_{r-1} ... H^R_0
+int gebrd_form_uv_backward(const BdCall& c, double* U, double* V) {
+  nd4hip_handle* h = c.h;
+  const int M = c.M, N = c.N, K = c.K, J = c.J, batch = c.batch;
+  {
+    const unsigned gy = (unsigned)(M < 512 ? M : 512);
+    hipLaunchKernelGGL(bd_set_identity, dim3((unsigned)((K + 255) / 256), gy, (unsigned)batch), dim3(256), 0, h->stream, U, M, K);
+  }
+  for (int i = K - 1; i >= 0; i--) {
+    Blk b{U, K, (long)M * K, i, M, i, K};
+    ND4_TRY(reflect_left(h, batch, b, c.UL, K, (long)M * K, i, c.tauL, K, i, c.ws));
+  }
+  {
+    const unsigned gy = (unsigned)(J < 512 ? J : 512);
+    hipLaunchKernelGGL(bd_set_identity, dim3((unsigned)((N + 255) / 256), gy, (unsigned)batch), dim3(256), 0, h->stream, V, J, N);
+  }
+  for (int k = K - 1; k >= 0; k--) {
+    if (!(k + 1 < N - 1)) continue;
+    Blk b{V, N, (long)J * N, k + 1, J, k + 1, N};
+    ND4_TRY(reflect_right(h, batch, b, c.VR + (long)k * N, (long)K * N, c.flagR, K, k, c.ws));
+  }
+  return 0;
+}
+
 }  // namespace
 
 // A [batch, M, N] -> U [batch, M, K], B [batch, K, J], V [batch, J, N]; K = min(M, N), J = K (M >= N) or K + 1
@@ -815,151 +965,39 @@ int nd4_gebrd(nd4hip_handle* h, int64_t batch64, int64_t M64, int64_t N64, const
   void* p = nullptr;
   const size_t nd = (size_t)batch * ((size_t)M * N + (size_t)M * K + (size_t)K * N + (size_t)K + 2 * (size_t)mx + (size_t)(Pmax + 24) * mx);   // (+24 mx: scratch of the fused form)
   ND4_TRY(nd4_ws_alloc(h, sizeof(double) * nd + sizeof(int) * (size_t)batch * (2 * (size_t)K + 2) + 256, &p));
-  double* W = static_cast<double*>(p);
-  double* UL = W + (size_t)batch * M * N;
-  double* VR = UL + (size_t)batch * M * K;
-  double* tauL = VR + (size_t)batch * K * N;
-  BdWs ws;
-  ws.z = tauL + (size_t)batch * K; ws.y = ws.z + (size_t)batch * mx; ws.zpart = ws.y + (size_t)batch * mx;
+  BdCall c;
+  c.h = h; c.batch = batch; c.M = M; c.N = N; c.K = K; c.J = J; c.mx = mx;
+  c.W = static_cast<double*>(p);
+  c.UL = c.W + (size_t)batch * M * N;
+  c.VR = c.UL + (size_t)batch * M * K;
+  c.tauL = c.VR + (size_t)batch * K * N;
+  BdWs& ws = c.ws;
+  ws.z = c.tauL + (size_t)batch * K; ws.y = ws.z + (size_t)batch * mx; ws.zpart = ws.y + (size_t)batch * mx;
   ws.sV = mx; ws.sZ = (long)Pmax * mx; ws.ncols_total = mx;
-  int* flagR = reinterpret_cast<int*>(ws.zpart + (size_t)batch * (Pmax + 24) * mx);
-  int* flips = flagR + (size_t)batch * K + 1;
-  const long sW = (long)M * N, sUL = (long)M * K, sVRm = (long)K * N;
-  ND4_HIP(hipMemcpyAsync(W, A, sizeof(double) * (size_t)batch * sW, hipMemcpyDeviceToDevice, h->stream));
-  ND4_HIP(hipMemsetAsync(VR, 0, sizeof(double) * (size_t)batch * sVRm, h->stream));
-  ND4_HIP(hipMemsetAsync(flagR, 0, sizeof(int) * (size_t)batch * K, h->stream));
+  c.flagR = reinterpret_cast<int*>(ws.zpart + (size_t)batch * (Pmax + 24) * mx);
+  int* flips = c.flagR + (size_t)batch * K + 1;
+  ND4_HIP(hipMemcpyAsync(c.W, A, sizeof(double) * (size_t)batch * M * N, hipMemcpyDeviceToDevice, h->stream));
+  ND4_HIP(hipMemsetAsync(c.VR, 0, sizeof(double) * (size_t)batch * K * N, h->stream));
+  ND4_HIP(hipMemsetAsync(c.flagR, 0, sizeof(int) * (size_t)batch * K, h->stream));
 
   // ---- factorisation ----
-  static const bool fused_off = getenv("ND4HIP_BIDIAG_UNFUSED") != nullptr;          // A/B switch
+  const bool one_matrix = batch == 1 && M >= 128 && N >= 128;
   const bool no_persist = getenv("ND4HIP_BIDIAG_NO_PERSIST") != nullptr;          // (read per call: the tests switch between the paths)
-  bool persist = !fused_off && !no_persist && batch == 1 && M >= 128 && N >= 128 && M <= 2048 && N <= 2048;
+  bool persist = !no_persist && one_matrix && M <= 2048 && N <= 2048;
   if (persist) {                                             // (the 256 workgroups of bdp must all be resident at once, see xchg.h)
     int per_cu = 0;
-    const hipError_t oe = mx <= 512 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bdp<2>, 256, 0)
-                        : mx <= 1024 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bdp<4>, 256, 0)
-                                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bdp<8>, 256, 0);
-    persist = oe == hipSuccess && (long)per_cu * h->num_cu >= 256;
+    persist = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bdp_for(mx), 256, 0) == hipSuccess && (long)per_cu * h->num_cu >= 256;
   }
-  if (persist) {
-    // ---- one launch: 16 x 16 workgroups keep the matrix in registers for the whole reduction (see bdp) ----
-    const int E = mx <= 512 ? 2 : (mx <= 1024 ? 4 : 8), T = 16 * E;
-    const size_t V1 = 3 * T, V2 = 2 * E, V3 = T, V4 = 2 * E;
-    const size_t xbytes = 16 * 2 * 256 * (V1 + V2 + V3 + V4) + (size_t)BP_NREP * (BP_REP_A2 + BP_REP_A4);
-    Nd4WsScope scope2(h);
-    void* qp = nullptr;
-    ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)K * M + xbytes + 64, &qp));
-    double* ULt = static_cast<double*>(qp);                  // [K][M]: reflector i as a row (transposed into UL at the end)
-    BdPx X;
-    X.base = reinterpret_cast<qx_u64*>(ULt + (size_t)K * M);
-    X.o1 = 0; X.o2 = X.o1 + (unsigned)(2 * 256 * V1 * 16); X.o3 = X.o2 + (unsigned)(2 * 256 * V2 * 16); X.o4 = X.o3 + (unsigned)(2 * 256 * V3 * 16);
-    X.oA2 = X.o4 + (unsigned)(2 * 256 * V4 * 16); X.oA4 = X.oA2 + BP_NREP * BP_REP_A2; X.bytes = X.oA4 + BP_NREP * BP_REP_A4;
-    X.abort = reinterpret_cast<int*>(reinterpret_cast<char*>(X.base) + xbytes);
-    ND4_HIP(hipMemsetAsync(X.base, 0, xbytes + 64, h->stream));
-    static const bool want_stamps = getenv("ND4HIP_BDP_STAMPS") != nullptr;
-    // s_sleep(8) units (~0.22 us) before the first look of rounds 1 / 3 (high byte) and rounds 2 / 4 (low byte)
-    const int delay = getenv("ND4HIP_BDP_DELAY") ? atoi(getenv("ND4HIP_BDP_DELAY")) : (0 << 8 | 4);
-    long long* stamps = nullptr;
-    if (want_stamps) { void* sp = nullptr; ND4_TRY(nd4_ws_alloc(h, sizeof(long long) * 256 * 8, &sp)); stamps = static_cast<long long*>(sp); }
-    if (E == 2) hipLaunchKernelGGL(bdp<2>, dim3(256), dim3(256), 0, h->stream, W, M, N, K, ULt, tauL, VR, flagR, X, h->xstat, delay, stamps, nd4_test_drop_panel());
-    else if (E == 4) hipLaunchKernelGGL(bdp<4>, dim3(256), dim3(256), 0, h->stream, W, M, N, K, ULt, tauL, VR, flagR, X, h->xstat, delay, stamps, nd4_test_drop_panel());
-    else hipLaunchKernelGGL(bdp<8>, dim3(256), dim3(256), 0, h->stream, W, M, N, K, ULt, tauL, VR, flagR, X, h->xstat, delay, stamps, nd4_test_drop_panel());
-    ND4_HIP(hipGetLastError());
-    if (stamps) {                                     // per step, in us: left reflector | round 1 | sums + round 2 | right reflector | round 3 | sums + round 4 | update
-      long long hs[256 * 8];
-      ND4_HIP(hipMemcpyAsync(hs, stamps, sizeof(hs), hipMemcpyDeviceToHost, h->stream));
-      ND4_HIP(hipStreamSynchronize(h->stream));
-      for (int g : {0, 119, 255})
-        fprintf(stderr, "bdp %dx%d wg %3d: left %.2f  r1 %.2f  r2 %.2f  right %.2f  r3 %.2f  r4 %.2f  update %.2f us per step\n", M, N, g,
-                hs[g * 8] * 0.01 / K, hs[g * 8 + 1] * 0.01 / K, hs[g * 8 + 2] * 0.01 / K, hs[g * 8 + 3] * 0.01 / K, hs[g * 8 + 4] * 0.01 / K,
-                hs[g * 8 + 5] * 0.01 / K, hs[g * 8 + 6] * 0.01 / K);
-    }
-    ND4_TRY(nd4_transpose(h, K, M, ULt, M, UL, K, 1, 0, 0));
-  } else if (!fused_off && batch == 1 && M >= 128 && N >= 128 && M <= BD2_MAXM && N <= BD2_MAXN) {
-    double* ucol = ws.zpart;                                 // M doubles (the partial sums of the unfused form are not needed)
-    double* rowfin = ucol + mx;                              // N doubles
-    double* ubuf[2] = {rowfin + mx, rowfin + 2 * mx};        // contiguous u of the previous / the current step
-    constexpr int PMAXZ = 8;
-    double* zbuf[2] = {rowfin + 3 * mx, rowfin + (3 + PMAXZ) * (size_t)mx};     // z in up to PMAXZ row parts, alternating by step
-    int Pprev = 1;
-    hipLaunchKernelGGL(bd2_init_ucol, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, h->stream, W, M, N, ucol);
-    int prev = -1;                                           // step whose rank-2 update and row are still pending
-    for (int i = 0; i < K; i++) {
-      const int nc = N - i - 1, nr = M - i - 1;
-      const int has_right = (i + 1 < N - 1) ? 1 : 0;
-      const int ncb = nc > 0 ? (nc + 15) / 16 : 1;
-      // two row parts (z as two partial sums added by its readers) while one part per column block would leave half of the CUs idle;
-      // more parts cost more than they give (every part repeats the reflector prologue, every reader adds P partials: 4-8 parts
-      // on 256 threads 71 ms against 63 at 2048^2)
-      static const int p_env = getenv("ND4HIP_BD_PARTS") ? atoi(getenv("ND4HIP_BD_PARTS")) : 0;
-      const int P = p_env ? (p_env > PMAXZ ? PMAXZ : p_env) : ((ncb <= 128 && M - i >= 512) ? 2 : 1);
-      const int rpp = ((((M - i) + P - 1) / P) + 15) & ~15;
-      hipLaunchKernelGGL(bd2_colpass, dim3((unsigned)ncb, (unsigned)P), dim3(CPT), sizeof(double) * 3 * (size_t)rpp, h->stream,
-                         W, M, N, i, UL, K, tauL, ucol, zbuf[(i + 1) & 1], Pprev, zbuf[i & 1], prev, ubuf[(i + 1) & 1], ubuf[i & 1], ws.y, VR, rowfin);
-      prev = -1;
-      if (nc <= 0) continue;
-      hipLaunchKernelGGL(bd2_rowpass, dim3((unsigned)(nr > 0 ? (nr + 3) / 4 : 1)), dim3(256), sizeof(double) * 2 * (size_t)nc, h->stream,
-                         W, M, N, i, UL, K, zbuf[i & 1], P, VR, flagR, ws.y, has_right, rowfin, ubuf[i & 1], ucol);
-      prev = i; Pprev = P;
-    }
-    if (prev >= 0)                                           // only for M < N: the last step has no rows below, its row is all that is pending
-      hipLaunchKernelGGL(bd2_finish_row, dim3((unsigned)((N - prev - 1 + 255) / 256)), dim3(256), 0, h->stream, W, N, prev, rowfin);
-    ND4_HIP(hipGetLastError());
-  } else
-  for (int i = 0; i < K; i++) {
-    hipLaunchKernelGGL(bd_vec_col, dim3((unsigned)batch), dim3(256), 0, h->stream, W, M, N, i, UL, K, tauL);
-    {
-      Blk b{W, N, sW, i, M, i + 1, N};                       // (I - tau u u^T) on the columns to the right
-      ND4_TRY(reflect_left(h, batch, b, UL, K, sUL, i, tauL, K, i, ws));
-    }
-    if (i + 1 < N - 1) {                                     // something to the right of the super-diagonal
-      hipLaunchKernelGGL(bd_vec_row, dim3((unsigned)batch), dim3(256), 0, h->stream, W, M, N, i, VR, K, flagR);
-      Blk b{W, N, sW, i + 1, M, i + 1, N};                   // rows below, same reflector from the right
-      ND4_TRY(reflect_right(h, batch, b, VR + (long)i * N, sVRm, flagR, K, i, ws));
-    }
-  }
+  if (persist)                                               ND4_TRY(gebrd_persistent(c));
+  else if (one_matrix && M <= BD2_MAXM && N <= BD2_MAXN)     ND4_TRY(gebrd_fused(c));
+  else                                                       ND4_TRY(gebrd_per_step(c));
   {
     const unsigned gy = (unsigned)(K < 512 ? K : 512);
-    hipLaunchKernelGGL(bd_extract, dim3((unsigned)((J + 255) / 256), gy, (unsigned)batch), dim3(256), 0, h->stream, W, M, N, B, K, J);
+    hipLaunchKernelGGL(bd_extract, dim3((unsigned)((J + 255) / 256), gy, (unsigned)batch), dim3(256), 0, h->stream, c.W, M, N, B, K, J);
   }
-  if (batch <= 4 && K >= 256) {
-    // one big matrix: U and V at once from the compact-WY form of the stored reflectors (nd4_wy_form, shared with QR):
-    // U = [I;0] - UL (T_L UL[0:K,:]^T) with the taus on T_L's diagonal; V^T[:, 0:J] = E_J - VR^T (T_R VR[:,0:J]) with
-    // tau = 2 for the unit vectors of the right reflectors (a skipped step stored v = 0 and drops out).
-    Nd4WsScope scope2(h);
-    void* q = nullptr;
-    ND4_TRY(nd4_ws_alloc(h, sizeof(double) * ((size_t)N * K + (size_t)N * J + (size_t)K + 16), &q));
-    double* VRt = static_cast<double*>(q);                   // N x K: column k = v_k
-    double* Vt = VRt + (size_t)N * K;                        // N x J
-    double* twos = Vt + (size_t)N * J;
-    hipLaunchKernelGGL(bd_fill, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, h->stream, twos, K, 2.0);
-    for (int m = 0; m < batch; m++) {
-      ND4_TRY(nd4_wy_form(h, M, K, UL + (size_t)m * sUL, tauL + (size_t)m * K, 1, U + (size_t)m * M * K, K));
-      ND4_TRY(nd4_transpose(h, K, N, VR + (size_t)m * sVRm, N, VRt, K, 1, 0, 0));
-      ND4_TRY(nd4_wy_form(h, N, K, VRt, twos, 1, Vt, J));
-      ND4_TRY(nd4_transpose(h, N, J, Vt, J, V + (size_t)m * J * N, N, 1, 0, 0));
-    }
-  } else {
-  // ---- U = H_0 ... H_{K-1} [I; 0]: reflectors applied backwards ----
-  {
-    const unsigned gy = (unsigned)(M < 512 ? M : 512);
-    hipLaunchKernelGGL(bd_set_identity, dim3((unsigned)((K + 255) / 256), gy, (unsigned)batch), dim3(256), 0, h->stream, U, M, K);
-  }
-  for (int i = K - 1; i >= 0; i--) {
-    Blk b{U, K, (long)M * K, i, M, i, K};
-    ND4_TRY(reflect_left(h, batch, b, UL, K, sUL, i, tauL, K, i, ws));
-  }
-  // ---- V = first J rows of H^R_{r-1} ... H^R_0 ----
-  {
-    const unsigned gy = (unsigned)(J < 512 ? J : 512);
-    hipLaunchKernelGGL(bd_set_identity, dim3((unsigned)((N + 255) / 256), gy, (unsigned)batch), dim3(256), 0, h->stream, V, J, N);
-  }
-  for (int k = K - 1; k >= 0; k--) {
-    if (!(k + 1 < N - 1)) continue;
-    Blk b{V, N, (long)J * N, k + 1, J, k + 1, N};
-    ND4_TRY(reflect_right(h, batch, b, VR + (long)k * N, sVRm, flagR, K, k, ws));
-  }
-  }
+  if (batch <= 4 && K >= 256) ND4_TRY(gebrd_form_uv_wy(c, U, V));
+  else                        ND4_TRY(gebrd_form_uv_backward(c, U, V));
   ND4_HIP(hipGetLastError());
   // ---- the reference's sign convention on (columns of U, rows of B) ----
-  return nd4_givens_signs(h, batch, M, K, J, M > N, U, K, (long)M * K, B, J, (long)K * J, tauL, K, flips);
+  return nd4_givens_signs(h, batch, M, K, J, M > N, U, K, (long)M * K, B, J, (long)K * J, c.tauL, K, flips);
 }

@@ -378,96 +378,69 @@ __global__ void chol_finish(double* __restrict__ Lm, int N) {
   for (int i = blockIdx.y; i < N && i < j; i += gridDim.y) Lm[base + (long)i * N + j] = 0.0;
 }
 
-}  // namespace
-
-// S [batch, N, N] -> L [batch, N, N]; flags [batch] int (device), set to 1 where a pivot was NaN
-int nd4_potrf(nd4hip_handle* h, int64_t batch64, int64_t N64, const double* S, double* L, int* flags) {
-  ND4_CHECK_ARG(N64 < (1ll << 30) && batch64 < 65536, "nd4_potrf: extent out of range");
-  const int N = (int)N64, batch = (int)batch64;
-  if (N == 0 || batch == 0) return 0;
-  const long sL = (long)N * N;
-  const unsigned gy = (unsigned)(N < 1024 ? N : 1024);
-  ND4_HIP(hipMemsetAsync(flags, 0, sizeof(int) * (size_t)batch, h->stream));
-  hipLaunchKernelGGL(chol_copy_lower, dim3((unsigned)((N + 255) / 256), gy, (unsigned)batch), dim3(256), 0, h->stream, S, L, N);
-  static const bool la_off = getenv("ND4HIP_CHOL_NO_LOOKAHEAD") != nullptr;          // A/B switch
-  const bool lookahead = !la_off && N >= 4 * CB && (long)batch * N <= 65536;
-  static const bool fused_off = getenv("ND4HIP_CHOL_NO_FUSED_TRSM") != nullptr;      // A/B switch
-  const bool fused_trsm = lookahead && !fused_off && (N % CB) == 0;                  // chol_trsm_narrow
-  Nd4WsScope scope(h);
-  double* inv = nullptr;
-  double* ynext = nullptr;
-  if (fused_trsm) { void* p = nullptr; ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)batch * 2 * CB * CB, &p)); inv = static_cast<double*>(p); ynext = inv + (size_t)batch * CB * CB; }
+// ---- host drivers: one function per strategy; nd4_potrf / nd4_ldltrf choose by shape ----
+// Look-ahead with the fused triangular solve (N a multiple of CB), Cholesky and LDL^T (LDL: D in it): the diagonal block at j0 shares
+// its launch (chol_diag_la) with the update block column pj0 still owes the columns from j0 + CB on; chol_trsm_narrow then does the
+// rows below the block and completes the next block column in one launch.
+template <bool LDL>
+int chol_lookahead_fused(nd4hip_handle* h, int batch, int N, double* L, int* flags) {
+  void* p = nullptr;
+  ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)batch * 2 * CB * CB, &p));
+  double* inv = static_cast<double*>(p);
+  double* ynext = inv + (size_t)batch * CB * CB;
   for (int j0 = 0, pj0 = -1; j0 < N; j0 += CB) {
-    const int nb = N - j0 < CB ? N - j0 : CB;
-    if (lookahead) {
-      // block column j0 is complete (narrow update below); the columns from j0 + CB on still lack the update of block column pj0
-      const int rest = N - (j0 + CB);
-      const int ntr = (pj0 >= 0 && rest > 0) ? (rest + 63) / 64 : 0, ntc = (pj0 >= 0 && rest > 0) ? (rest + 31) / 32 : 1;
-      hipLaunchKernelGGL(chol_diag_la<false>, dim3((unsigned)(1 + ntr * ntc), (unsigned)batch), dim3(256), 0, h->stream, L, N, j0, nb, flags,
-                         pj0 < 0 ? 0 : pj0, ntc, inv, ynext);
-    } else {
-      hipLaunchKernelGGL(chol_diag, dim3((unsigned)batch), dim3(64), 0, h->stream, L, N, j0, nb, flags);
-    }
-    const int m2 = N - j0 - nb;
+    // block column j0 is complete; the columns from j0 + CB on still lack the update of block column pj0
+    const int rest = N - (j0 + CB);
+    const int ntr = (pj0 >= 0 && rest > 0) ? (rest + 63) / 64 : 0, ntc = (pj0 >= 0 && rest > 0) ? (rest + 31) / 32 : 1;
+    hipLaunchKernelGGL(chol_diag_la<LDL>, dim3((unsigned)(1 + ntr * ntc), (unsigned)batch), dim3(256), 0, h->stream, L, N, j0, CB, flags,
+                       pj0 < 0 ? 0 : pj0, ntc, inv, ynext);
+    const int m2 = N - j0 - CB;
     if (m2 <= 0) break;
-    if (fused_trsm) {                                      // rows below the block and the next block column in one launch
-      hipLaunchKernelGGL(chol_trsm_narrow<false>, dim3((unsigned)((m2 + 63) / 64), (unsigned)batch), dim3(256), 0, h->stream, L, N, j0, inv, ynext);
-      ND4_HIP(hipGetLastError());
-      pj0 = j0;
-      continue;
-    }
-    hipLaunchKernelGGL(chol_trsm, dim3((unsigned)((m2 + 255) / 256), (unsigned)batch), dim3(256), 0, h->stream, L, N, j0, nb);
+    hipLaunchKernelGGL(chol_trsm_narrow<LDL>, dim3((unsigned)((m2 + 63) / 64), (unsigned)batch), dim3(256), 0, h->stream, L, N, j0, inv, ynext);
     ND4_HIP(hipGetLastError());
-    const int r0 = j0 + nb;
-    if (lookahead) {
-      // only the next block column now: A[r0:, r0:r0+CB] -= L[r0:, j0:j0+CB] L[r0:r0+CB, j0:j0+CB]^T; the rest rides under the next diagonal block
-      const int ncn = N - r0 < CB ? N - r0 : CB;
-      ND4_TRY(nd4_gemm(h, false, true, N - r0, ncn, nb, -1.0, L + (long)r0 * N + j0, N, sL, L + (long)r0 * N + j0, N, sL,
-                       1.0, L + (long)r0 * N + r0, N, sL, batch));
-      pj0 = j0;
-    } else {
-      // A22 -= L21 L21^T: one launch, 128x128 tiles strictly above the diagonal are skipped
-      ND4_TRY(nd4_syrk_lower(h, N - r0, nb, -1.0, L + (long)r0 * N + j0, N, sL, 1.0, L + (long)r0 * N + r0, N, sL, batch));
-    }
+    pj0 = j0;
   }
-  hipLaunchKernelGGL(chol_finish, dim3((unsigned)((N + 255) / 256), gy, (unsigned)batch), dim3(256), 0, h->stream, L, N);
-  ND4_HIP(hipGetLastError());
   return 0;
 }
-
-// S [batch, N, N] -> packed LD [batch, N, N] (ldl.js:67-90)
-int nd4_ldltrf(nd4hip_handle* h, int64_t batch64, int64_t N64, const double* S, double* LD) {
-  ND4_CHECK_ARG(N64 < (1ll << 30) && batch64 < 65536, "nd4_ldltrf: extent out of range");
-  const int N = (int)N64, batch = (int)batch64;
-  if (N == 0 || batch == 0) return 0;
-  const long sL = (long)N * N, sW = (long)N * CB;
-  Nd4WsScope scope(h);
-  void* p = nullptr;
-  ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)batch * (size_t)sW, &p));
-  double* W = static_cast<double*>(p);
-  const unsigned gy = (unsigned)(N < 1024 ? N : 1024);
-  hipLaunchKernelGGL(chol_copy_lower, dim3((unsigned)((N + 255) / 256), gy, (unsigned)batch), dim3(256), 0, h->stream, S, LD, N);
-  static const bool la_off = getenv("ND4HIP_CHOL_NO_LOOKAHEAD") != nullptr || getenv("ND4HIP_CHOL_NO_FUSED_TRSM") != nullptr;   // A/B switches
-  if (!la_off && N >= 4 * CB && (N % CB) == 0 && (long)batch * N <= 65536) {
-    // the Cholesky look-ahead step with D in it (chol_diag_la<true> / chol_trsm_narrow<true>): see nd4_potrf
-    void* q = nullptr;
-    ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)batch * 2 * CB * CB, &q));
-    double* inv = static_cast<double*>(q);
-    double* ynext = inv + (size_t)batch * CB * CB;
-    for (int j0 = 0, pj0 = -1; j0 < N; j0 += CB) {
-      const int rest = N - (j0 + CB);
-      const int ntr = (pj0 >= 0 && rest > 0) ? (rest + 63) / 64 : 0, ntc = (pj0 >= 0 && rest > 0) ? (rest + 31) / 32 : 1;
-      hipLaunchKernelGGL(chol_diag_la<true>, dim3((unsigned)(1 + ntr * ntc), (unsigned)batch), dim3(256), 0, h->stream, LD, N, j0, CB,
-                         (int*)nullptr, pj0 < 0 ? 0 : pj0, ntc, inv, ynext);
-      const int m2 = N - j0 - CB;
-      if (m2 <= 0) break;
-      hipLaunchKernelGGL(chol_trsm_narrow<true>, dim3((unsigned)((m2 + 63) / 64), (unsigned)batch), dim3(256), 0, h->stream, LD, N, j0, inv, ynext);
-      pj0 = j0;
-    }
-    hipLaunchKernelGGL(chol_finish, dim3((unsigned)((N + 255) / 256), gy, (unsigned)batch), dim3(256), 0, h->stream, LD, N);
+// Look-ahead for N not a multiple of CB (Cholesky only): the same diagonal launch, then the solve for the rows below (chol_trsm) and
+// the update of the next block column alone as launches of their own; the rest rides under the next diagonal block.
+int potrf_lookahead(nd4hip_handle* h, int batch, int N, double* L, int* flags) {
+  const long sL = (long)N * N;
+  for (int j0 = 0, pj0 = -1; j0 < N; j0 += CB) {
+    const int nb = N - j0 < CB ? N - j0 : CB;
+    const int rest = N - (j0 + CB);
+    const int ntr = (pj0 >= 0 && rest > 0) ? (rest + 63) / 64 : 0, ntc = (pj0 >= 0 && rest > 0) ? (rest + 31) / 32 : 1;
+    hipLaunchKernelGGL(chol_diag_la<false>, dim3((unsigned)(1 + ntr * ntc), (unsigned)batch), dim3(256), 0, h->stream, L, N, j0, nb, flags,
+                       pj0 < 0 ? 0 : pj0, ntc, (double*)nullptr, (double*)nullptr);
+    const int m2 = N - j0 - nb;
+    if (m2 <= 0) break;
+    hipLaunchKernelGGL(chol_trsm, dim3((unsigned)((m2 + 255) / 256), (unsigned)batch), dim3(256), 0, h->stream, L, N, j0, nb);
     ND4_HIP(hipGetLastError());
-    return 0;
+    // A[r0:, r0:r0+CB] -= L[r0:, j0:j0+CB] L[r0:r0+CB, j0:j0+CB]^T
+    const int r0 = j0 + nb, ncn = N - r0 < CB ? N - r0 : CB;
+    ND4_TRY(nd4_gemm(h, false, true, N - r0, ncn, nb, -1.0, L + (long)r0 * N + j0, N, sL, L + (long)r0 * N + j0, N, sL,
+                     1.0, L + (long)r0 * N + r0, N, sL, batch));
+    pj0 = j0;
   }
+  return 0;
+}
+// Plain right-looking loop (small N; batches that fill the chip): diagonal block, solve for the rows below, one update of the trailing matrix
+int potrf_plain(nd4hip_handle* h, int batch, int N, double* L, int* flags) {
+  const long sL = (long)N * N;
+  for (int j0 = 0; j0 < N; j0 += CB) {
+    const int nb = N - j0 < CB ? N - j0 : CB;
+    hipLaunchKernelGGL(chol_diag, dim3((unsigned)batch), dim3(64), 0, h->stream, L, N, j0, nb, flags);
+    const int m2 = N - j0 - nb;
+    if (m2 <= 0) break;
+    hipLaunchKernelGGL(chol_trsm, dim3((unsigned)((m2 + 255) / 256), (unsigned)batch), dim3(256), 0, h->stream, L, N, j0, nb);
+    ND4_HIP(hipGetLastError());
+    const int r0 = j0 + nb;                        // A22 -= L21 L21^T: one launch, 128x128 tiles strictly above the diagonal are skipped
+    ND4_TRY(nd4_syrk_lower(h, N - r0, nb, -1.0, L + (long)r0 * N + j0, N, sL, 1.0, L + (long)r0 * N + r0, N, sL, batch));
+  }
+  return 0;
+}
+int ldltrf_plain(nd4hip_handle* h, int batch, int N, double* LD, double* W) {
+  const long sL = (long)N * N, sW = (long)N * CB;
   for (int j0 = 0; j0 < N; j0 += CB) {
     const int nb = N - j0 < CB ? N - j0 : CB;
     hipLaunchKernelGGL(ldl_diag, dim3((unsigned)batch), dim3(64), 0, h->stream, LD, N, j0, nb);
@@ -478,6 +451,42 @@ int nd4_ldltrf(nd4hip_handle* h, int64_t batch64, int64_t N64, const double* S, 
     const int r0 = j0 + nb;                        // A22 -= (L21 D11) L21^T, tiles above the diagonal skipped
     ND4_TRY(nd4_gemm_nt_lower(h, m2, nb, -1.0, W, CB, sW, LD + (long)r0 * N + j0, N, sL, 1.0, LD + (long)r0 * N + r0, N, sL, batch));
   }
+  return 0;
+}
+// the look-ahead forms hide a latency chain behind idle CUs: from four blocks on, and not for batches that fill the chip by themselves
+bool chol_lookahead_ok(int batch, int N) { return N >= 4 * CB && (long)batch * N <= 65536; }
+
+}  // namespace
+
+// S [batch, N, N] -> L [batch, N, N]; flags [batch] int (device), set to 1 where a pivot was NaN
+int nd4_potrf(nd4hip_handle* h, int64_t batch64, int64_t N64, const double* S, double* L, int* flags) {
+  ND4_CHECK_ARG(N64 < (1ll << 30) && batch64 < 65536, "nd4_potrf: extent out of range");
+  const int N = (int)N64, batch = (int)batch64;
+  if (N == 0 || batch == 0) return 0;
+  const unsigned gy = (unsigned)(N < 1024 ? N : 1024);
+  ND4_HIP(hipMemsetAsync(flags, 0, sizeof(int) * (size_t)batch, h->stream));
+  hipLaunchKernelGGL(chol_copy_lower, dim3((unsigned)((N + 255) / 256), gy, (unsigned)batch), dim3(256), 0, h->stream, S, L, N);
+  Nd4WsScope scope(h);
+  if (!chol_lookahead_ok(batch, N)) ND4_TRY(potrf_plain(h, batch, N, L, flags));
+  else if ((N % CB) == 0)           ND4_TRY(chol_lookahead_fused<false>(h, batch, N, L, flags));
+  else                              ND4_TRY(potrf_lookahead(h, batch, N, L, flags));
+  hipLaunchKernelGGL(chol_finish, dim3((unsigned)((N + 255) / 256), gy, (unsigned)batch), dim3(256), 0, h->stream, L, N);
+  ND4_HIP(hipGetLastError());
+  return 0;
+}
+
+// S [batch, N, N] -> packed LD [batch, N, N] (ldl.js:67-90)
+int nd4_ldltrf(nd4hip_handle* h, int64_t batch64, int64_t N64, const double* S, double* LD) {
+  ND4_CHECK_ARG(N64 < (1ll << 30) && batch64 < 65536, "nd4_ldltrf: extent out of range");
+  const int N = (int)N64, batch = (int)batch64;
+  if (N == 0 || batch == 0) return 0;
+  Nd4WsScope scope(h);
+  void* p = nullptr;
+  ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)batch * (size_t)N * CB, &p));     // L21 D11 of the plain loop
+  const unsigned gy = (unsigned)(N < 1024 ? N : 1024);
+  hipLaunchKernelGGL(chol_copy_lower, dim3((unsigned)((N + 255) / 256), gy, (unsigned)batch), dim3(256), 0, h->stream, S, LD, N);
+  if (chol_lookahead_ok(batch, N) && (N % CB) == 0) ND4_TRY(chol_lookahead_fused<true>(h, batch, N, LD, nullptr));
+  else                                              ND4_TRY(ldltrf_plain(h, batch, N, LD, static_cast<double*>(p)));
   hipLaunchKernelGGL(chol_finish, dim3((unsigned)((N + 255) / 256), gy, (unsigned)batch), dim3(256), 0, h->stream, LD, N);
   ND4_HIP(hipGetLastError());
   return 0;

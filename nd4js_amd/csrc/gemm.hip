@@ -331,11 +331,6 @@ __global__ __launch_bounds__(256) void dgemm_splitk_reduce(const double* __restr
   *c = v;
 }
 
-// ND4HIP_GEMM_TILED=1 sends every product through the tiled kernel (A/B measurements of the rank-k kernel)
-bool nd4_gemm_force_tiled() {
-  static const bool v = [] { const char* e = getenv("ND4HIP_GEMM_TILED"); return e && *e && *e != '0'; }();
-  return v;
-}
 
 template <bool TA, bool TB>
 int launch(nd4hip_handle* h, const GemmArgs& g, bool vec, int64_t batch) {
@@ -364,7 +359,7 @@ int nd4_gemm(nd4hip_handle* h, bool transA, bool transB, int64_t M, int64_t N, i
   g.alpha = alpha; g.beta = beta; g.lower = 0; g.kchunk = 0; g.Cpart = nullptr;
   g.tiles_m = (int)((M + BM - 1) / BM); g.tiles_n = (int)((N + BN - 1) / BN);
   ND4_CHECK_ARG((int64_t)g.tiles_m * g.tiles_n < (1ll << 31), "nd4_gemm: too many tiles");
-  if (smallk_ok(g, transA) && !nd4_gemm_force_tiled()) return transB ? launch_smallk<true>(h, g, batch) : launch_smallk<false>(h, g, batch);
+  if (smallk_ok(g, transA)) return transB ? launch_smallk<true>(h, g, batch) : launch_smallk<false>(h, g, batch);
   // few output tiles and a long K (tall-skinny products, Gram matrices, Q^T y): split K over blockIdx.z so that the chip is
   // filled, then add the partials in a fixed order. (64 x 4096) x (4096 x 4096): 0.62 -> see DESIGN.md 4.1.
   Nd4WsScope scope(h);
@@ -414,7 +409,7 @@ int nd4_gemm_nt_lower(nd4hip_handle* h, int64_t N, int64_t K, double alpha, cons
   g.A = A; g.B = B; g.C = C; g.M = (int)N; g.N = (int)N; g.K = (int)K;
   g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.sA = sA; g.sB = sB; g.sC = sC;
   g.alpha = alpha; g.beta = beta; g.lower = 1; g.kchunk = 0; g.Cpart = nullptr;
-  if (smallk_ok(g, false) && !nd4_gemm_force_tiled()) return launch_smallk<true>(h, g, batch);
+  if (smallk_ok(g, false)) return launch_smallk<true>(h, g, batch);
   g.tiles_m = (int)((N + BM - 1) / BM); g.tiles_n = g.tiles_m;
   auto ok = [](const double* p, int64_t ld, int64_t st) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && (ld & 1) == 0 && (st & 1) == 0; };
   const bool vec = ok(A, lda, sA) && ok(B, ldb, sB) && (K & 1) == 0;

@@ -716,6 +716,95 @@ __global__ __launch_bounds__(256) void hessp(double* __restrict__ H, int N, doub
     }
 }
 
+// ---- host driver: one function per factorisation path; nd4_gehrd keeps allocation, path choice and the forming of U ----
+// s_sleep(8) units (~0.22 us) before hessp's first look of round B (high byte) and round C (low byte)
+constexpr int HESSP_DELAY = 2 << 8 | 4;
+using hessp_fn = void (*)(double*, int, double*, HessPx, int*, int, long long*, int);
+// E x E elements per thread: the smallest tile of 16 E that covers N with 16 x 16 workgroups
+hessp_fn hessp_for(int N) { return N <= 512 ? hessp<2> : (N <= 1024 ? hessp<4> : hessp<8>); }
+
+// One launch: 16 x 16 workgroups keep H in registers for the whole reduction (see hessp); the reflectors end up in ws.vstore
+int gehrd_persistent(nd4hip_handle* h, double* H, int N, const HessWs& ws) {
+  const int nstore = ws.nstore;
+  const int E = N <= 512 ? 2 : (N <= 1024 ? 4 : 8), T = 16 * E;
+  const size_t BV = 3 * T, CV = 3 * E;                                                    // values (16 bytes each) per slot
+  const size_t xwords = 2 * (2 * 256 * (BV + CV)) + (size_t)HP_NREP * (HP_REP_BV + HP_REP_CN) / 8;
+  void* q = nullptr;
+  ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)nstore * N + sizeof(qx_u64) * xwords + 64, &q));
+  double* vrows = static_cast<double*>(q);
+  HessPx X;
+  X.base = reinterpret_cast<qx_u64*>(vrows + (size_t)nstore * N);
+  X.oB = 0; X.oC = (unsigned)(2 * 256 * BV * 16); X.oBv = X.oC + (unsigned)(2 * 256 * CV * 16); X.oCn = X.oBv + HP_NREP * HP_REP_BV;
+  X.bytes = X.oCn + HP_NREP * HP_REP_CN;
+  X.abort = reinterpret_cast<int*>(X.base + xwords);
+  ND4_HIP(hipMemsetAsync(vrows, 0, sizeof(double) * (size_t)nstore * N + sizeof(qx_u64) * xwords + 64, h->stream));
+  const int drop = nd4_test_drop_panel() >= 0 ? N - 1 - nd4_test_drop_panel() : -1;       // test hook: row N-1-k is never published
+  static const bool want_stamps = getenv("ND4HIP_HESSP_STAMPS") != nullptr;
+  long long* stamps = nullptr;
+  if (want_stamps) { void* sp = nullptr; ND4_TRY(nd4_ws_alloc(h, sizeof(long long) * 256 * 8, &sp)); stamps = static_cast<long long*>(sp); }
+  hipLaunchKernelGGL(hessp_for(N), dim3(256), dim3(256), 0, h->stream, H, N, vrows, X, h->xstat, drop, stamps, HESSP_DELAY);
+  ND4_HIP(hipGetLastError());
+  if (stamps) {                                     // per step, in us: reflector | products | B | sums + C | update
+    long long hs[256 * 8];
+    ND4_HIP(hipMemcpyAsync(hs, stamps, sizeof(hs), hipMemcpyDeviceToHost, h->stream));
+    ND4_HIP(hipStreamSynchronize(h->stream));
+    for (int g : {0, 17, 119, 255})
+      fprintf(stderr, "hessp N=%d wg %3d: scalars+v %.2f  matvec %.2f  B %.2f  C %.2f  update %.2f us per step\n", N, g,
+              hs[g * 8] * 0.01 / (N - 2), hs[g * 8 + 1] * 0.01 / (N - 2), hs[g * 8 + 2] * 0.01 / (N - 2), hs[g * 8 + 3] * 0.01 / (N - 2), hs[g * 8 + 4] * 0.01 / (N - 2));
+  }
+  return nd4_transpose(h, nstore, N, vrows, N, ws.vstore, nstore, 1, 0, 0);            // reflectors as columns for nd4_wy_form
+}
+
+// Blocked: NBH steps per block, H untouched inside a block, two GEMMs per block; the reflectors end up in ws.vstore
+int gehrd_blocked(nd4hip_handle* h, double* H, int N, const HessWs& ws) {
+  const int nstore = ws.nstore;
+  const int nchunks = (N + BC - 1) / BC;
+  void* q = nullptr;
+  ND4_TRY(nd4_ws_alloc(h, sizeof(double) * ((size_t)3 * N * NBH + 3 * NBH + (size_t)N + (size_t)nchunks * N + (size_t)((N + BR - 1) / BR) * nchunks + (size_t)nstore * N + (size_t)N) +
+                              sizeof(int) * (size_t)N + 64, &q));
+  HessBlk bk;
+  bk.Vt = static_cast<double*>(q); bk.Wt = bk.Vt + (size_t)N * NBH; bk.Yt = bk.Wt + (size_t)N * NBH;
+  bk.dots = bk.Yt + (size_t)N * NBH; bk.nrm = bk.dots + 3 * NBH; bk.ypart = bk.nrm + N; bk.vyp = bk.ypart + (size_t)nchunks * N;
+  bk.vrows = bk.vyp + (size_t)((N + BR - 1) / BR) * nchunks;
+  bk.nextrow = bk.vrows + (size_t)nstore * N;
+  bk.skipv = reinterpret_cast<int*>(bk.nextrow + N);
+  ND4_HIP(hipMemsetAsync(bk.skipv, 0, sizeof(int) * (size_t)N, h->stream));
+  ND4_HIP(hipMemsetAsync(bk.vrows, 0, sizeof(double) * (size_t)nstore * N, h->stream));
+  for (int ihi = N - 1; ihi > 1; ihi -= NBH) {
+    const int ilo = ihi - NBH + 1 > 2 ? ihi - NBH + 1 : 2;
+    ND4_HIP(hipMemsetAsync(bk.Vt, 0, sizeof(double) * (size_t)3 * N * NBH, h->stream));
+    for (int i = ihi, k = 0; i >= ilo; i--, k++) {
+      const int ngroups = (i + BR - 1) / BR, ndot = (3 * k + 3) / 4;
+      // two launches per step: the pass builds the reflector itself (every workgroup, from the row hessb_reduce left behind)
+      hipLaunchKernelGGL(hessb_pass, dim3((unsigned)(ngroups * nchunks + ndot)), dim3(256), (size_t)N * sizeof(double), h->stream, H, N, i, k, ngroups, nchunks, ws, bk);
+      hipLaunchKernelGGL(hessb_reduce, dim3((unsigned)((N + RC - 1) / RC)), dim3(256), 0, h->stream, H, N, i, k, nchunks, i > ilo ? 1 : 0, ws, bk);
+    }
+    ND4_HIP(hipGetLastError());
+    const int nk = ihi - ilo + 1;
+    // H[0:ihi, :] -= V W^T + Y V^T   (rows >= ihi: V and Y are zero there); V^T etc. are stored [NBH][N]: transA
+    ND4_TRY(nd4_gemm(h, true, false, ihi, N, nk, -1.0, bk.Vt, N, 0, bk.Wt, N, 0, 1.0, H, N, 0, 1));
+    ND4_TRY(nd4_gemm(h, true, false, ihi, N, nk, -1.0, bk.Yt, N, 0, bk.Vt, N, 0, 1.0, H, N, 0, 1));
+    hipLaunchKernelGGL(hessb_fix, dim3((unsigned)((N + 255) / 256), (unsigned)nk), dim3(256), 0, h->stream, H, N, ilo, ihi, bk);
+  }
+  ND4_HIP(hipGetLastError());
+  return nd4_transpose(h, nstore, N, bk.vrows, N, ws.vstore, nstore, 1, 0, 0);     // reflectors as columns for nd4_wy_form
+}
+
+// Generic (batches, small N, N beyond the other paths): four launches per step. with_u: U is dragged through every step; otherwise
+// the reflectors are stored in ws.vstore
+int gehrd_per_step(nd4hip_handle* h, int batch, double* H, double* U, int N, bool with_u, const HessWs& ws) {
+  const int cchunks = (N + 255) / 256;
+  const unsigned rg = (unsigned)((N - 1 + HR - 1) / HR);           // row groups: enough for U's N-1 rows (H uses i <= N-1)
+  for (int i = N - 1; i > 1; i--) {
+    hipLaunchKernelGGL(hess_vec, dim3((unsigned)batch), dim3(256), 0, h->stream, H, N, i, ws);
+    hipLaunchKernelGGL(hess_pass_a, dim3(rg, with_u ? 2 : 1, (unsigned)batch), dim3(256), 0, h->stream, H, U, N, i, ws);
+    hipLaunchKernelGGL(hess_reduce, dim3((unsigned)((N + RC - 1) / RC), (unsigned)batch), dim3(256), 0, h->stream, N, i, ws);
+    hipLaunchKernelGGL(hess_pass_b, dim3((unsigned)((with_u ? 2 : 1) * cchunks), rg, (unsigned)batch), dim3(256), 0, h->stream, H, U, N, i, cchunks, ws);
+    ND4_HIP(hipGetLastError());
+  }
+  return 0;
+}
+
 }  // namespace
 
 // A [batch, N, N] -> U, H [batch, N, N]
@@ -750,92 +839,17 @@ int nd4_gehrd(nd4hip_handle* h, int64_t batch64, int64_t N64, const double* A, d
     ND4_HIP(hipMemsetAsync(ws.vstore, 0, sizeof(double) * (size_t)batch * N * nstore, h->stream));
     hipLaunchKernelGGL(hess_fill, dim3((unsigned)((nstore + 255) / 256)), dim3(256), 0, h->stream, ones, nstore, 1.0);
   }
-  const int cchunks = (N + 255) / 256;
-  const bool blocked_path = wy && batch == 1 && N >= 512 && (N & 1) == 0 && (size_t)N * sizeof(double) <= 48 * 1024 && !getenv("ND4HIP_HESS_UNBLOCKED");
+  const bool blocked_path = wy && batch == 1 && N >= 512 && (N & 1) == 0 && (size_t)N * sizeof(double) <= 48 * 1024;
   const bool no_persist = getenv("ND4HIP_HESS_NO_PERSIST") != nullptr;            // (read per call: the tests switch between the paths)
   // (the 256 workgroups of hessp must all be resident at once: one or two per CU, see xchg.h)
-  bool persist = wy && batch == 1 && N >= 128 && N <= 2048 && !no_persist && !getenv("ND4HIP_HESS_UNBLOCKED");
+  bool persist = wy && batch == 1 && N >= 128 && N <= 2048 && !no_persist;
   if (persist) {
     int per_cu = 0;
-    const hipError_t oe = N <= 512 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hessp<2>, 256, 0)
-                        : N <= 1024 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hessp<4>, 256, 0)
-                                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hessp<8>, 256, 0);
-    persist = oe == hipSuccess && (long)per_cu * h->num_cu >= 256;
+    persist = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hessp_for(N), 256, 0) == hipSuccess && (long)per_cu * h->num_cu >= 256;
   }
-  if (persist) {
-    // ---- one launch: 16 x 16 workgroups keep H in registers for the whole reduction (see hessp) ----
-    const int E = N <= 512 ? 2 : (N <= 1024 ? 4 : 8), T = 16 * E;
-    const size_t BV = 3 * T, CV = 3 * E;                                                    // values (16 bytes each) per slot
-    const size_t xwords = 2 * (2 * 256 * (BV + CV)) + (size_t)HP_NREP * (HP_REP_BV + HP_REP_CN) / 8;
-    void* q = nullptr;
-    ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)nstore * N + sizeof(qx_u64) * xwords + 64, &q));
-    double* vrows = static_cast<double*>(q);
-    HessPx X;
-    X.base = reinterpret_cast<qx_u64*>(vrows + (size_t)nstore * N);
-    X.oB = 0; X.oC = (unsigned)(2 * 256 * BV * 16); X.oBv = X.oC + (unsigned)(2 * 256 * CV * 16); X.oCn = X.oBv + HP_NREP * HP_REP_BV;
-    X.bytes = X.oCn + HP_NREP * HP_REP_CN;
-    X.abort = reinterpret_cast<int*>(X.base + xwords);
-    ND4_HIP(hipMemsetAsync(vrows, 0, sizeof(double) * (size_t)nstore * N + sizeof(qx_u64) * xwords + 64, h->stream));
-    const int drop = nd4_test_drop_panel() >= 0 ? N - 1 - nd4_test_drop_panel() : -1;       // test hook: row N-1-k is never published
-    static const bool want_stamps = getenv("ND4HIP_HESSP_STAMPS") != nullptr;
-    // s_sleep(8) units (~0.22 us) before the first look of round B (high byte) and round C (low byte)
-    const int delay = getenv("ND4HIP_HESSP_DELAY") ? atoi(getenv("ND4HIP_HESSP_DELAY")) : (2 << 8 | 4);
-    long long* stamps = nullptr;
-    if (want_stamps) { void* sp = nullptr; ND4_TRY(nd4_ws_alloc(h, sizeof(long long) * 256 * 8, &sp)); stamps = static_cast<long long*>(sp); }
-    if (E == 2) hipLaunchKernelGGL(hessp<2>, dim3(256), dim3(256), 0, h->stream, H, N, vrows, X, h->xstat, drop, stamps, delay);
-    else if (E == 4) hipLaunchKernelGGL(hessp<4>, dim3(256), dim3(256), 0, h->stream, H, N, vrows, X, h->xstat, drop, stamps, delay);
-    else hipLaunchKernelGGL(hessp<8>, dim3(256), dim3(256), 0, h->stream, H, N, vrows, X, h->xstat, drop, stamps, delay);
-    ND4_HIP(hipGetLastError());
-    if (stamps) {                                     // per step, in us: reflector | products | B | sums + C | update
-      long long hs[256 * 8];
-      ND4_HIP(hipMemcpyAsync(hs, stamps, sizeof(hs), hipMemcpyDeviceToHost, h->stream));
-      ND4_HIP(hipStreamSynchronize(h->stream));
-      for (int g : {0, 17, 119, 255})
-        fprintf(stderr, "hessp N=%d wg %3d: scalars+v %.2f  matvec %.2f  B %.2f  C %.2f  update %.2f us per step\n", N, g,
-                hs[g * 8] * 0.01 / (N - 2), hs[g * 8 + 1] * 0.01 / (N - 2), hs[g * 8 + 2] * 0.01 / (N - 2), hs[g * 8 + 3] * 0.01 / (N - 2), hs[g * 8 + 4] * 0.01 / (N - 2));
-    }
-    ND4_TRY(nd4_transpose(h, nstore, N, vrows, N, ws.vstore, nstore, 1, 0, 0));            // reflectors as columns for nd4_wy_form
-  } else if (blocked_path) {
-    // ---- blocked: NBH steps per block, H untouched inside a block, two GEMMs per block ----
-    const int nchunks = (N + BC - 1) / BC;
-    void* q = nullptr;
-    ND4_TRY(nd4_ws_alloc(h, sizeof(double) * ((size_t)3 * N * NBH + 3 * NBH + (size_t)N + (size_t)nchunks * N + (size_t)((N + BR - 1) / BR) * nchunks + (size_t)nstore * N + (size_t)N) +
-                                sizeof(int) * (size_t)N + 64, &q));
-    HessBlk bk;
-    bk.Vt = static_cast<double*>(q); bk.Wt = bk.Vt + (size_t)N * NBH; bk.Yt = bk.Wt + (size_t)N * NBH;
-    bk.dots = bk.Yt + (size_t)N * NBH; bk.nrm = bk.dots + 3 * NBH; bk.ypart = bk.nrm + N; bk.vyp = bk.ypart + (size_t)nchunks * N;
-    bk.vrows = bk.vyp + (size_t)((N + BR - 1) / BR) * nchunks;
-    bk.nextrow = bk.vrows + (size_t)nstore * N;
-    bk.skipv = reinterpret_cast<int*>(bk.nextrow + N);
-    ND4_HIP(hipMemsetAsync(bk.skipv, 0, sizeof(int) * (size_t)N, h->stream));
-    ND4_HIP(hipMemsetAsync(bk.vrows, 0, sizeof(double) * (size_t)nstore * N, h->stream));
-    for (int ihi = N - 1; ihi > 1; ihi -= NBH) {
-      const int ilo = ihi - NBH + 1 > 2 ? ihi - NBH + 1 : 2;
-      ND4_HIP(hipMemsetAsync(bk.Vt, 0, sizeof(double) * (size_t)3 * N * NBH, h->stream));
-      for (int i = ihi, k = 0; i >= ilo; i--, k++) {
-        const int ngroups = (i + BR - 1) / BR, ndot = (3 * k + 3) / 4;
-        // two launches per step: the pass builds the reflector itself (every workgroup, from the row hessb_reduce left behind)
-        hipLaunchKernelGGL(hessb_pass, dim3((unsigned)(ngroups * nchunks + ndot)), dim3(256), (size_t)N * sizeof(double), h->stream, H, N, i, k, ngroups, nchunks, ws, bk);
-        hipLaunchKernelGGL(hessb_reduce, dim3((unsigned)((N + RC - 1) / RC)), dim3(256), 0, h->stream, H, N, i, k, nchunks, i > ilo ? 1 : 0, ws, bk);
-      }
-      ND4_HIP(hipGetLastError());
-      const int nk = ihi - ilo + 1;
-      // H[0:ihi, :] -= V W^T + Y V^T   (rows >= ihi: V and Y are zero there); V^T etc. are stored [NBH][N]: transA
-      ND4_TRY(nd4_gemm(h, true, false, ihi, N, nk, -1.0, bk.Vt, N, 0, bk.Wt, N, 0, 1.0, H, N, 0, 1));
-      ND4_TRY(nd4_gemm(h, true, false, ihi, N, nk, -1.0, bk.Yt, N, 0, bk.Vt, N, 0, 1.0, H, N, 0, 1));
-      hipLaunchKernelGGL(hessb_fix, dim3((unsigned)((N + 255) / 256), (unsigned)nk), dim3(256), 0, h->stream, H, N, ilo, ihi, bk);
-    }
-    ND4_HIP(hipGetLastError());
-    ND4_TRY(nd4_transpose(h, nstore, N, bk.vrows, N, ws.vstore, nstore, 1, 0, 0));     // reflectors as columns for nd4_wy_form
-  } else
-  for (int i = N - 1; i > 1; i--) {
-    hipLaunchKernelGGL(hess_vec, dim3((unsigned)batch), dim3(256), 0, h->stream, H, N, i, ws);
-    const unsigned rg = (unsigned)((N - 1 + HR - 1) / HR);           // row groups: enough for U's N-1 rows (H uses i <= N-1)
-    hipLaunchKernelGGL(hess_pass_a, dim3(rg, wy ? 1 : 2, (unsigned)batch), dim3(256), 0, h->stream, H, U, N, i, ws);
-    hipLaunchKernelGGL(hess_reduce, dim3((unsigned)((N + RC - 1) / RC), (unsigned)batch), dim3(256), 0, h->stream, N, i, ws);
-    hipLaunchKernelGGL(hess_pass_b, dim3((unsigned)((wy ? 1 : 2) * cchunks), rg, (unsigned)batch), dim3(256), 0, h->stream, H, U, N, i, cchunks, ws);
-    ND4_HIP(hipGetLastError());
-  }
+  if (persist)           ND4_TRY(gehrd_persistent(h, H, N, ws));
+  else if (blocked_path) ND4_TRY(gehrd_blocked(h, H, N, ws));
+  else                   ND4_TRY(gehrd_per_step(h, batch, H, U, N, !wy, ws));
   if (wy)
     for (int m = 0; m < batch; m++)                                   // skipped steps stored v = 0: they drop out of V T V^T
       ND4_TRY(nd4_wy_form(h, N, nstore, ws.vstore + (size_t)m * N * nstore, ones, 1, U + (size_t)m * nn, N));

@@ -448,10 +448,10 @@ __device__ __forceinline__ double mw_ld(const mw_u64* slot, int v, unsigned tag,
 
 // stage != nullptr (look-ahead form): the panel's columns come from the contiguous block lu_narrow_fused has left behind, and the
 // 16 x 16 block of U above the panel (stage_top) is copied into place on the way (as in lu_panel_row_body).
-template <int R, int PQ, bool STAMPS = false>
+template <int R, int PQ>
 __device__ __forceinline__ void lu_panel_mw_body(const int w, const int mat, double* __restrict__ LU, int N, long strideM, int j0,
                                                  int32_t* __restrict__ ipiv, int nopivot, double* __restrict__ xbuf, int* __restrict__ stuck,
-                                                 int P, unsigned long long* __restrict__ stamps, const double* __restrict__ stage,
+                                                 int P, const double* __restrict__ stage,
                                                  const double* __restrict__ stage_top, const int fold_pj0 = -1) {
   // fold_pj0 >= 0 (one row per thread only): the previous panel's work on THESE 16 columns happens here instead of in a launch of
   // its own (lu_narrow_fused): every workgroup works out the interchanges, gathers the 16 x 16 block above the panel, solves
@@ -554,9 +554,6 @@ __device__ __forceinline__ void lu_panel_mw_body(const int w, const int mat, dou
   auto column = [&](auto kc) {
     constexpr int k = decltype(kc)::value;
     const int jc = j0 + k, tag = jc + 1;
-    // debug stamps (ND4HIP_LU_STAMPS): [workgroup][wave][column][phase] shader clocks of lane 0
-    auto stamp = [&](int ph) { if constexpr (STAMPS) { if (lane == 0 && mat == 0) stamps[(((long)w * NWV + wave) * W + k) * 8 + ph] = __builtin_amdgcn_s_memtime(); } };
-    stamp(0);
     mw_u64* myslot = slots + ((long)(k & 1) * MW_MAXP + w) * MW_SLOT;
     const mw_u64* sl = slots + (long)(k & 1) * MW_MAXP * MW_SLOT;
     // ---- this wave's candidate ----
@@ -586,9 +583,7 @@ __device__ __forceinline__ void lu_panel_mw_body(const int w, const int mat, dou
 #pragma unroll
       for (int c = 0; c < W; c++) s_j[c] = a[0][c];
     }
-    stamp(1);
     __syncthreads();
-    stamp(2);
     if (wave == 0) {
       // ---- publish the workgroup's candidate ----
       const PivCand c8 = s_red[lane & (NWV - 1)];
@@ -601,7 +596,6 @@ __device__ __forceinline__ void lu_panel_mw_body(const int w, const int mat, dou
       else if (lane == 16) mw_st(myslot, 16, bm, (unsigned)tag);
       else if (lane == 17) mw_st(myslot, 17, __longlong_as_double((long long)bi), (unsigned)tag);
       else if (w == 0 && lane >= 32 && lane < 32 + W) mw_st(myslot, 18 + (lane - 32), s_j[lane - 32], (unsigned)tag);
-      stamp(3);
       // ---- all candidates at once, until every word carries this column's tag: lanes 0..15 magnitude + row number of workgroup
       //      `lane`, lanes 32..47 the displaced row jc, and the P row segments 16 lanes each ----
       // Three polls in flight, a few hundred cycles apart (loads return in order, so the first is examined while the others are
@@ -660,7 +654,6 @@ __device__ __forceinline__ void lu_panel_mw_body(const int w, const int mat, dou
           if ((spins & 255) == 0 && __hip_atomic_load(stuck, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { take(wa); break; }
         }
       }
-      stamp(4);
       double mm = lane < W ? m1 : -3.0;
       mm = fmax(mm, nd4dpp::xor1(mm)); mm = fmax(mm, nd4dpp::xor2(mm)); mm = fmax(mm, nd4dpp::xor4(mm)); mm = fmax(mm, nd4dpp::xor8(mm));
       int ii = (lane < P && m1 == mm) ? (int)__double_as_longlong(m2) : 0x7fffffff;
@@ -680,7 +673,6 @@ __device__ __forceinline__ void lu_panel_mw_body(const int w, const int mat, dou
     double u[W];
 #pragma unroll
     for (int c = 0; c < W; c++) u[c] = s_u[c];
-    stamp(5);
     if (piv != jc) {
 #pragma unroll
       for (int i = 0; i < R; i++)
@@ -708,7 +700,6 @@ __device__ __forceinline__ void lu_panel_mw_body(const int w, const int mat, dou
         for (int c = k + 1; c < W; c++) a[i][c] -= l * u[c];
       }
     }
-    stamp(6);
     __builtin_amdgcn_sched_barrier(0);
   };
 #define ND4_COL(K) column(std::integral_constant<int, K>{});
@@ -731,11 +722,10 @@ __device__ __forceinline__ void lu_panel_mw_body(const int w, const int mat, dou
     }
   }
 }
-template <int R, int PQ, bool STAMPS = false>
+template <int R, int PQ>
 __global__ __launch_bounds__(512) void lu_panel_mw(double* __restrict__ LU, int N, long strideM, int j0, int32_t* __restrict__ ipiv,
-                                                   int nopivot, double* __restrict__ xbuf, int* __restrict__ stuck, int P,
-                                                   unsigned long long* __restrict__ stamps = nullptr) {
-  lu_panel_mw_body<R, PQ, STAMPS>(blockIdx.x, blockIdx.y, LU, N, strideM, j0, ipiv, nopivot, xbuf, stuck, P, stamps, nullptr, nullptr);
+                                                   int nopivot, double* __restrict__ xbuf, int* __restrict__ stuck, int P) {
+  lu_panel_mw_body<R, PQ>(blockIdx.x, blockIdx.y, LU, N, strideM, j0, ipiv, nopivot, xbuf, stuck, P, nullptr, nullptr);
 }
 // the same panel (workgroups 0 .. P-1 of a matrix) together with everything the previous panel (at pj0) still owes the other columns
 template <int R, int PQ>
@@ -745,8 +735,8 @@ __global__ __launch_bounds__(512) void lu_panel_mw_la(double* __restrict__ LU, i
                                                       const double* __restrict__ stage, long strideStage, int full_end, int fold) {
   if ((int)blockIdx.x < P) {
     const double* sg = stage != nullptr ? stage + blockIdx.y * strideStage : nullptr;
-    lu_panel_mw_body<R, PQ, false>(blockIdx.x, blockIdx.y, LU, N, strideM, j0, ipiv, nopivot, xbuf, stuck, P, nullptr,
-                                   sg != nullptr ? sg + NB * NB : nullptr, sg, fold ? pj0 : -1);
+    lu_panel_mw_body<R, PQ>(blockIdx.x, blockIdx.y, LU, N, strideM, j0, ipiv, nopivot, xbuf, stuck, P,
+                            sg != nullptr ? sg + NB * NB : nullptr, sg, fold ? pj0 : -1);
     return;
   }
   lu_update_block<512, true>((int)blockIdx.x - P, blockIdx.y, LU, N, strideM, pj0, wide0, ipiv, nopivot ? 0 : 1, Pm, full_end);
@@ -991,12 +981,182 @@ void launch_panel_row(nd4hip_handle* h, double* LU, int N, long strideM, int j0,
   hipLaunchKernelGGL((lu_panel_row<R, NB, 512>), dim3(batch), dim3(512), 0, h->stream, LU, N, strideM, j0, nb, P, ipiv, nopivot);
 }
 
-}  // namespace
-
 template <int R, int W, int T>
 void launch_panel_row_wt(nd4hip_handle* h, double* LU, int N, long strideM, int j0, int nb, int32_t* P, int32_t* ipiv, int batch, int nopivot) {
   hipLaunchKernelGGL((lu_panel_row<R, W, T>), dim3(batch), dim3(T), 0, h->stream, LU, N, strideM, j0, nb, P, ipiv, nopivot);
 }
+
+// ---- host driver ----
+// N > 2048: two-level blocking. With panels of 8 / 4 columns every step used to read-modify-write the whole trailing matrix
+// (N^3 / (3 NB) * 16 B: 180 GB at 8192^2 for 366 GFLOP). Now an outer block of LU_OUTER columns (with the look-ahead panels 256: 3 %
+// slower, 1024: 1 % faster) is factorised by the same panel kernels with the rank-NB updates restricted to the block (the
+// interchanges still go to every column at once: two rows per swap), then U12 = L11^-1 A12 for the whole block row (unit lower, the
+// one-launch solver of trsm.hip on a contiguous copy) and ONE K = LU_OUTER product A22 -= L21 U12 on the tiled MFMA kernel.
+constexpr int LU_OUTER = 512;
+// The look-ahead form (panel p in one workgroup, panel p - 1's column-block updates riding in the same launch) hides a latency chain
+// behind otherwise idle CUs: right for one or a few matrices. A batch that fills the chip by itself is a throughput problem, for which
+// the plain sequence panel -> interchanges + U12 -> rank-16 product on the MFMA kernel moves fewer bytes per launch (1024 x 512^2:
+// 73.9 ms with the look-ahead form, 19.8 ms without; 8 matrices: 1.05 against 1.37 ms, 16: 1.64 against 1.48).
+constexpr int LU_LA_MAX_BATCH = 12;
+// Such batches are bound by the read-modify-write of every trailing matrix per 16-column panel (1024 x 512^2: 45 GB for 4.3 GB of
+// matrices): two levels for them too, in outer blocks of LU_BATCH_OUTER columns (1024 x 512^2: one level 19.9 ms, outer 32 / 64 /
+// 128: 16.6 / 15.8 / 14.7 ms).
+constexpr int LU_BATCH_OUTER = 128;
+static_assert(LU_OUTER % NB == 0 && LU_OUTER <= 2048, "phase 1 of getrf_impl walks whole outer blocks of whole panels");
+
+// what every regime of one factorisation shares
+struct LuCall {
+  nd4hip_handle* h;
+  double* LU; int32_t* P; int32_t* ipiv;
+  int N; int64_t batch; long strideM; int nopivot;
+  bool p_in_laswp;                       // every panel is followed by lu_laswp (N > NB): P rides along with it
+  bool mw_on; int mw_rt;                 // panels taller than 2048 rows: over co-resident workgroups of mw_rt rows each (lu_panel_mw)
+  double* xbuf; int* stuck;              //   their exchange slots and status words
+  double* u12buf;                        // two-level blocking: the contiguous copy of an outer block's U12
+  double* stage; long sStage;            // look-ahead form: where lu_narrow_fused leaves the next panel's columns
+};
+
+// lu_panel_mw<R, PQ> / lu_panel_mw_la<R, PQ> for mw_rt = 512 R rows per workgroup and Pw <= 4 PQ workgroups: f(R, PQ) as integral constants
+template <class F>
+void mw_dispatch(const int mw_rt, const int Pw, F&& f) {
+  auto with_r = [&](auto R) {
+    if (Pw <= 4) f(R, std::integral_constant<int, 1>{}); else if (Pw <= 8) f(R, std::integral_constant<int, 2>{}); else f(R, std::integral_constant<int, 4>{});
+  };
+  if (mw_rt == 2048) with_r(std::integral_constant<int, 4>{}); else if (mw_rt == 1024) with_r(std::integral_constant<int, 2>{}); else with_r(std::integral_constant<int, 1>{});
+}
+void launch_panel_mw(const LuCall& c, const int j0, const int Pw) {
+  mw_dispatch(c.mw_rt, Pw, [&](auto R, auto PQ) {
+    hipLaunchKernelGGL((lu_panel_mw<decltype(R)::value, decltype(PQ)::value>), dim3((unsigned)Pw, (unsigned)c.batch), dim3(512), 0, c.h->stream,
+                       c.LU, c.N, c.strideM, j0, c.ipiv, c.nopivot, c.xbuf, c.stuck, Pw);
+  });
+}
+void launch_panel_mw_la(const LuCall& c, const int j0, const int Pw, const int nupd, const int pj0, const int wide0, const double* sg,
+                        const int full_end, const int fold) {
+  mw_dispatch(c.mw_rt, Pw, [&](auto R, auto PQ) {
+    hipLaunchKernelGGL((lu_panel_mw_la<decltype(R)::value, decltype(PQ)::value>), dim3((unsigned)(Pw + nupd), (unsigned)c.batch), dim3(512), 0, c.h->stream,
+                       c.LU, c.N, c.strideM, j0, c.P, c.ipiv, c.nopivot, c.xbuf, c.stuck, Pw, pj0, wide0, sg, c.sStage, full_end, fold);
+  });
+}
+
+// the part of an outer block's work beyond it: U12 = L11^-1 A12 for the whole block row, then ONE K = nbo product on the tiled MFMA kernel
+int lu_outer_far(const LuCall& c, const int J, const int bend) {
+  const int N = c.N, far = N - bend, nbo = bend - J;
+  if (far <= 0) return 0;
+  ND4_HIP(hipGetLastError());
+  const long sU = (long)nbo * far;
+  ND4_TRY(nd4_copy_matrix(c.h, nbo, far, c.LU + (long)J * N + bend, N, c.u12buf, far, c.batch, c.strideM, sU));
+  ND4_TRY(nd4_trsm_ld(c.h, false, true, c.batch, nbo, far, c.LU + (long)J * N + J, N, c.strideM, c.u12buf, sU));
+  ND4_TRY(nd4_copy_matrix(c.h, nbo, far, c.u12buf, far, c.LU + (long)J * N + bend, N, c.batch, sU, c.strideM));
+  return nd4_gemm(c.h, false, false, far, far, nbo, -1.0, c.LU + (long)bend * N + J, N, c.strideM, c.u12buf, far, sU,
+                  1.0, c.LU + (long)bend * N + bend, N, c.strideM, c.batch);
+}
+
+// ---- throughput form: panel -> interchanges + U12 (lu_laswp) -> rank-nb product, for the panels of columns [J, bend), the updates
+//      restricted to the columns left of bend. two_level: followed by the block's work on the columns beyond it. ----
+int lu_outer_block(const LuCall& c, const int J, const int bend, const bool two_level) {
+  nd4hip_handle* h = c.h;
+  double* LU = c.LU;
+  const int N = c.N, batch = (int)c.batch, nopivot = c.nopivot;
+  const long strideM = c.strideM;
+  for (int j0 = J, step = NB; j0 < bend; j0 += step) {
+    const int m = N - j0;
+    // taller panels keep the thread-per-row layout on 1024 threads (128 VGPRs per lane) by narrowing the panel:
+    // 4 rows x 8 columns up to 4096 rows, 8 rows x 4 columns up to 8192 rows
+    const bool tall8 = m > 2048 && m <= 4096;
+    const bool tall4 = m > 4096 && m <= 8192;
+    const bool mw = c.mw_on && m > 2048 && bend - j0 >= NB;
+    step = mw ? NB : tall8 ? 8 : tall4 ? 4 : NB;
+    const int nb = bend - j0 < step ? bend - j0 : step;
+    if (mw) {
+      launch_panel_mw(c, j0, (m + c.mw_rt - 1) / c.mw_rt);
+    } else if (tall8) {
+      launch_panel_row_wt<4, 8, 1024>(h, LU, N, strideM, j0, nb, c.P, c.ipiv, batch, nopivot);
+    } else if (tall4) {
+      launch_panel_row_wt<8, 4, 1024>(h, LU, N, strideM, j0, nb, c.P, c.ipiv, batch, nopivot);
+    } else if (m >= 64 && m <= 2048) {
+      if (m <= 512)       launch_panel_row<1>(h, LU, N, strideM, j0, nb, c.P, c.ipiv, batch, nopivot);
+      else if (m <= 1024) launch_panel_row<2>(h, LU, N, strideM, j0, nb, c.P, c.ipiv, batch, nopivot);
+      else                launch_panel_row<4>(h, LU, N, strideM, j0, nb, c.P, c.ipiv, batch, nopivot);
+    } else {
+      int T = ((m * NB + 63) / 64) * 64; if (T > 1024) T = 1024; if (T < 64) T = 64;
+      hipLaunchKernelGGL(lu_panel_global, dim3((unsigned)batch), dim3(T), 0, h->stream, LU, N, strideM, j0, nb, c.P, c.ipiv, nopivot);
+    }
+    const int rest = N - j0 - nb;
+    if (N > nb && (!nopivot || rest > 0))
+      hipLaunchKernelGGL(lu_laswp, dim3((unsigned)((N - nb + 255) / 256), (unsigned)batch), dim3(256), 0, h->stream,
+                         LU, N, strideM, j0, nb, c.ipiv, nopivot ? 0 : 1, c.p_in_laswp ? c.P : (int32_t*)nullptr, bend);
+    const int inner = bend - j0 - nb;                        // columns of the block right of the panel
+    if (rest > 0 && inner > 0) {
+      ND4_HIP(hipGetLastError());
+      ND4_TRY(nd4_gemm(h, false, false, rest, inner, nb, -1.0,
+                       LU + (long)(j0 + nb) * N + j0, N, strideM,
+                       LU + (long)j0 * N + j0 + nb, N, strideM,
+                       1.0, LU + (long)(j0 + nb) * N + j0 + nb, N, strideM, c.batch));
+    }
+  }
+  return two_level ? lu_outer_far(c, J, bend) : 0;
+}
+
+// ---- look-ahead form (see lu_colblock_update): the panel at j0 shares its launch with everything the previous panel still owes the
+//      other columns; between two panels only the next panel's 16 columns are updated. Panels of <= 2048 rows: lu_panel_row_la;
+//      taller ones (two-level blocking, the rows over P workgroups): lu_panel_mw_la.
+//      [j_from, j_to): the panels of the range; full_end: columns from there on get the interchanges only (two-level: the outer
+//      block's end; their U12 and update come from lu_outer_far). *j_next: the first column it did not factorise. ----
+int lu_la_range(const LuCall& c, const int j_from, const int j_to, const int full_end, int* j_next) {
+  nd4hip_handle* h = c.h;
+  double* LU = c.LU;
+  const int N = c.N, nopivot = c.nopivot;
+  const unsigned batch = (unsigned)c.batch;
+  const long strideM = c.strideM, sStage = c.sStage;
+  // the next panel's columns between two panels: staged out of place in one launch (lu_narrow_fused, double2 rows: even N), else in
+  // place in two (lu_narrow_top + lu_narrow_gemm), or folded into the next panel's own prologue (see below)
+  const bool fused = (N & 1) == 0;
+  int pj0 = -1, j0 = j_from;
+  bool narrow_done = true, folded = false;                  // folded: this panel's kernel does the previous panel's narrow update itself
+  for (; j0 < j_to && N - j0 >= 64; j0 += NB) {
+    const int m = N - j0;
+    // the panel at pj0 has reached its own columns and the 16 behind them (the narrow launch: [pj0 + NB, pj0 + 2 NB) = this panel,
+    // staged out of place by lu_narrow_fused); it still owes the columns from pj0 + 2 NB on, the columns left of it, and P
+    const int wide0 = pj0 + 2 * NB;
+    const int nupd = pj0 < 0 ? 0 : 1 + pj0 / NB + (wide0 < N ? (N - wide0 + NB - 1) / NB : 0);
+    const double* sg = (fused && pj0 >= 0 && !folded) ? c.stage : nullptr;
+    const int pp = pj0 < 0 ? 0 : pj0;
+    if (m > 2048) {
+      launch_panel_mw_la(c, j0, (m + c.mw_rt - 1) / c.mw_rt, nupd, pp, wide0, sg, full_end, folded ? 1 : 0);
+    } else {
+      const dim3 grid((unsigned)(1 + nupd), batch);
+      if (m <= 512)       hipLaunchKernelGGL(lu_panel_row_la<1>, grid, dim3(512), 0, h->stream, LU, N, strideM, j0, c.P, c.ipiv, nopivot, pp, wide0, sg, sStage, full_end);
+      else if (m <= 1024) hipLaunchKernelGGL(lu_panel_row_la<2>, grid, dim3(512), 0, h->stream, LU, N, strideM, j0, c.P, c.ipiv, nopivot, pp, wide0, sg, sStage, full_end);
+      else                hipLaunchKernelGGL(lu_panel_row_la<4>, grid, dim3(512), 0, h->stream, LU, N, strideM, j0, c.P, c.ipiv, nopivot, pp, wide0, sg, sStage, full_end);
+    }
+    const int c0 = j0 + NB;                                // the next panel's columns
+    const bool more = c0 < j_to && N - c0 >= 64;           // another look-ahead panel follows: stage its columns out of place
+    narrow_done = true;
+    folded = false;
+    if (more && c.mw_rt == 512 && m - NB > 2048) {
+      folded = true;                                       // the next panel is a multi-workgroup one with one row per thread: it folds this in
+    } else if (fused && more) {
+      hipLaunchKernelGGL(lu_narrow_fused, dim3((unsigned)((m - NB + 255) / 256), batch), dim3(256), 0, h->stream,
+                         LU, N, strideM, c.ipiv, nopivot, j0, c.stage, sStage);
+    } else if (c0 < full_end && c0 < N) {
+      hipLaunchKernelGGL(lu_narrow_top, dim3(batch), dim3(512), 0, h->stream, LU, N, strideM, c.ipiv, nopivot, j0, c0);
+      hipLaunchKernelGGL(lu_narrow_gemm, dim3((unsigned)((m - NB + 255) / 256), batch), dim3(256), 0, h->stream, LU, N, strideM, j0, c0);
+    } else {
+      narrow_done = false;                                 // the range's last panel with nothing of the outer block right of it
+    }
+    pj0 = j0;
+  }
+  if (pj0 >= 0) {   // the last panel's debt
+    const int wide0 = narrow_done ? pj0 + 2 * NB : pj0 + NB;
+    const int nupd = 1 + pj0 / NB + (wide0 < N ? (N - wide0 + NB - 1) / NB : 0);
+    hipLaunchKernelGGL(lu_update_blocks, dim3((unsigned)nupd, batch), dim3(512), 0, h->stream, LU, N, strideM, c.P, c.ipiv, nopivot, pj0, wide0, full_end);
+  }
+  ND4_HIP(hipGetLastError());
+  *j_next = j0;
+  return 0;
+}
+
+}  // namespace
 
 static int getrf_impl(nd4hip_handle* h, int64_t batch, int64_t N64, const double* A, double* LU, int32_t* P, int nopivot) {
   ND4_CHECK_ARG(N64 < (1ll << 30) && batch < 65536, "nd4_getrf: extent out of range");
@@ -1004,235 +1164,77 @@ static int getrf_impl(nd4hip_handle* h, int64_t batch, int64_t N64, const double
   const long strideM = (long)N * N;
   if (LU != A) ND4_HIP(hipMemcpyAsync(LU, A, sizeof(double) * batch * strideM, hipMemcpyDeviceToDevice, h->stream));
   const long total = (long)batch * N;
-  void* ws = nullptr;
   Nd4WsScope scope(h);
+  LuCall c{};
+  c.h = h; c.LU = LU; c.P = P; c.N = N; c.batch = batch; c.strideM = strideM; c.nopivot = nopivot;
+  void* ws = nullptr;
   ND4_TRY(nd4_ws_alloc(h, sizeof(int32_t) * total, &ws));
-  int32_t* ipiv = static_cast<int32_t*>(ws);
-
+  c.ipiv = static_cast<int32_t*>(ws);
   // every panel of a matrix wider than one panel is followed by lu_laswp: P then rides along with it
-  const bool p_in_laswp = N > NB;
-  if (p_in_laswp) hipLaunchKernelGGL(lu_iota, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, P, total, (int)N);
-  int j_start = 0;
-  // Two-level blocking for N > 2048 (round 3): with panels of 8 / 4 columns every step used to read-modify-write the whole trailing
-  // matrix (N^3 / (3 NB) * 16 B: 180 GB at 8192^2 for 366 GFLOP). Now an outer block of 512 columns (ND4HIP_LU_OUTER; with the look-ahead panels 256: 3 % slower, 1024: 1 % faster) is factorised by the same
-  // panel kernels with the rank-NB updates restricted to the block (the interchanges still go to every column at once: two rows per
-  // swap), then U12 = L11^-1 A12 for the whole block row (unit lower, the one-launch solver of trsm.hip on a contiguous
-  // copy) and ONE K = 256 product A22 -= L21 U12 on the tiled MFMA kernel. N <= 2048: one level (nbo = N), as before.
-  static const int nbo_env = [] { const char* e = getenv("ND4HIP_LU_OUTER"); return e ? atoi(e) : 512; }();
-  // Batches that fill the chip (no look-ahead form, see la_on below) are bound by the read-modify-write of every trailing matrix per
-  // 16-column panel (1024 x 512^2: 45 GB for 4.3 GB of matrices): two levels for them too, outer blocks of ND4HIP_LU_BATCH_OUTER
-  // columns (1024 x 512^2: one level 19.9 ms, outer 32 / 64 / 128: 16.6 / 15.8 / 14.7 ms).
-  static const int la_max_batch = [] { const char* e = getenv("ND4HIP_LU_LA_MAX_BATCH"); return e ? atoi(e) : 12; }();
-  static const int nbo_batch = [] { const char* e = getenv("ND4HIP_LU_BATCH_OUTER"); return e ? atoi(e) : 128; }();
-  const bool batch_two_level = batch > la_max_batch && nbo_batch >= 32 && N <= 2048 && N >= 4 * nbo_batch;
-  const int NBO = (N > 2048 && nbo_env >= 32) ? nbo_env : (batch_two_level ? nbo_batch : N);
-  void* u12buf = nullptr;
-  if (NBO < N) ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)batch * NBO * N, &u12buf));
+  c.p_in_laswp = N > NB;
+  if (c.p_in_laswp) hipLaunchKernelGGL(lu_iota, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, P, total, (int)N);
+
+  // ---- the regime, from the shape alone (the measurements: at LU_OUTER / LU_LA_MAX_BATCH / LU_BATCH_OUTER above) ----
+  const bool la_on = N >= 64 + NB && batch <= LU_LA_MAX_BATCH;                           // one or a few matrices: look-ahead form
+  const bool batch_two_level = batch > LU_LA_MAX_BATCH && N <= 2048 && N >= 4 * LU_BATCH_OUTER;   // batches that fill the chip
+  const int NBO = N > 2048 ? LU_OUTER : (batch_two_level ? LU_BATCH_OUTER : N);         // outer block; N: one level
+  if (NBO < N) {
+    ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)batch * NBO * N, &ws));
+    c.u12buf = static_cast<double*>(ws);
+  }
   // panels taller than 2048 rows: the rows over P co-resident workgroups of 512 threads x R rows (lu_panel_mw), 16 columns wide
   // (rows per thread R: the fewest that keep P <= 16 — N <= 8192: 1, <= 16384: 2, <= 32768: 4; measured at 8192^2: 42.3 / 43.1 / 48.4 ms
-  //  for R = 1 / 2 / 4. ND4HIP_LU_MW_R = 1, 2, 4 forces one, 0 switches back to round 2's split panels.)
+  //  for R = 1 / 2 / 4. ND4HIP_LU_MW_R = 1, 2, 4 forces one, 0 switches back to the split panels of 8 / 4 columns.)
   const int mw_env = [] { const char* e = getenv("ND4HIP_LU_MW_R"); return e ? atoi(e) : -1; }();   // (read per call: the tests switch it)
   const int mw_r = mw_env >= 0 ? mw_env : (N <= MW_MAXP * 512 ? 1 : (N <= MW_MAXP * 1024 ? 2 : 4));
-  const int mw_rt = (mw_r == 1 ? 1 : mw_r == 2 ? 2 : 4) * 512;
-  const bool mw_on = mw_r != 0 && N > 2048 && (long)batch * ((N + mw_rt - 1) / mw_rt) <= 64 && N <= MW_MAXP * mw_rt;
-  double* xbuf = nullptr; int* stuck = nullptr;
-  if (mw_on) {
-    void* xb = nullptr;
+  c.mw_rt = (mw_r == 1 ? 1 : mw_r == 2 ? 2 : 4) * 512;
+  c.mw_on = mw_r != 0 && N > 2048 && (long)batch * ((N + c.mw_rt - 1) / c.mw_rt) <= 64 && N <= MW_MAXP * c.mw_rt;
+  if (c.mw_on) {
     const size_t xbytes = sizeof(double) * (size_t)batch * MW_STRIDE + 256;
-    ND4_TRY(nd4_ws_alloc(h, xbytes, &xb));
-    ND4_HIP(hipMemsetAsync(xb, 0, xbytes, h->stream));
-    stuck = static_cast<int*>(xb);
+    ND4_TRY(nd4_ws_alloc(h, xbytes, &ws));
+    ND4_HIP(hipMemsetAsync(ws, 0, xbytes, h->stream));
+    c.stuck = static_cast<int*>(ws);
     if (const int dp = nd4_test_drop_panel(); dp >= 0) {               // tests only: word 1 = the column tag whose publication one workgroup drops
       const int dtag = dp * NB + 1;
-      ND4_HIP(hipMemcpyAsync(stuck + 1, &dtag, sizeof(int), hipMemcpyHostToDevice, h->stream));
+      ND4_HIP(hipMemcpyAsync(c.stuck + 1, &dtag, sizeof(int), hipMemcpyHostToDevice, h->stream));
       ND4_HIP(hipStreamSynchronize(h->stream));
     }
-    xbuf = reinterpret_cast<double*>(static_cast<char*>(xb) + 256);
+    c.xbuf = reinterpret_cast<double*>(static_cast<char*>(ws) + 256);
   }
-  // the part of an outer block's work beyond it: U12 = L11^-1 A12 for the whole block row, then ONE K = nbo product on the tiled MFMA kernel
-  auto outer_far = [&](const int J, const int bend) -> int {
-    const int far = N - bend, nbo = bend - J;
-    if (far > 0) {
-      ND4_HIP(hipGetLastError());
-      double* U12 = static_cast<double*>(u12buf);
-      const long sU = (long)nbo * far;
-      ND4_TRY(nd4_copy_matrix(h, nbo, far, LU + (long)J * N + bend, N, U12, far, batch, strideM, sU));
-      ND4_TRY(nd4_trsm_ld(h, false, true, batch, nbo, far, LU + (long)J * N + J, N, strideM, U12, sU));
-      ND4_TRY(nd4_copy_matrix(h, nbo, far, U12, far, LU + (long)J * N + bend, N, batch, sU, strideM));
-      ND4_TRY(nd4_gemm(h, false, false, far, far, nbo, -1.0, LU + (long)bend * N + J, N, strideM, U12, far, sU,
-                       1.0, LU + (long)bend * N + bend, N, strideM, batch));
-    }
-    return 0;
-  };
-  auto outer_block = [&](const int J, const int bend, const bool two_level) -> int {
-    for (int j0 = J, step = NB; j0 < bend; j0 += step) {
-      const int m = N - j0;
-      // taller panels keep the thread-per-row layout on 1024 threads (128 VGPRs per lane) by narrowing the panel:
-      // 4 rows x 8 columns up to 4096 rows, 8 rows x 4 columns up to 8192 rows
-      const bool tall8 = m > 2048 && m <= 4096;
-      const bool tall4 = m > 4096 && m <= 8192;
-      const bool mw = mw_on && m > 2048 && bend - j0 >= NB;
-      step = mw ? NB : tall8 ? 8 : tall4 ? 4 : NB;
-      const int nb = bend - j0 < step ? bend - j0 : step;
-      if (mw) {
-        const int Pw = (m + mw_rt - 1) / mw_rt;
-        const dim3 grid((unsigned)Pw, (unsigned)batch);
-#define ND4_MW(RR, PQ) hipLaunchKernelGGL((lu_panel_mw<RR, PQ>), grid, dim3(512), 0, h->stream, LU, N, strideM, j0, ipiv, nopivot, xbuf, stuck, Pw)
-        static const bool stamps_on = [] { const char* e = getenv("ND4HIP_LU_STAMPS"); return e && *e && *e != '0'; }();
-        if (stamps_on && mw_rt == 1024 && Pw <= 4 && j0 == 0) {
-          unsigned long long* st = nullptr; const size_t nst = (size_t)4 * 8 * 16 * 8;
-          ND4_HIP(hipMalloc(&st, nst * 8)); ND4_HIP(hipMemset(st, 0, nst * 8));
-          hipLaunchKernelGGL((lu_panel_mw<2, 1, true>), grid, dim3(512), 0, h->stream, LU, N, strideM, j0, ipiv, nopivot, xbuf, stuck, Pw, st);
-          std::vector<unsigned long long> hs(nst);
-          ND4_HIP(hipStreamSynchronize(h->stream)); ND4_HIP(hipMemcpy(hs.data(), st, nst * 8, hipMemcpyDeviceToHost)); ND4_HIP(hipFree(st));
-          const unsigned long long t0 = hs[0];
-          for (int ww = 0; ww < Pw; ww++) for (int wv = 0; wv < 8; wv += 7) for (int kk = 6; kk < 9; kk++) {
-            fprintf(stderr, "mw stamps wg %d wave %d col %2d:", ww, wv, kk);
-            for (int ph = 0; ph < 7; ph++) fprintf(stderr, " %8lld", (long long)(hs[(((size_t)ww * 8 + wv) * 16 + kk) * 8 + ph] - t0));
-            fprintf(stderr, "\n");
-          }
-        } else
-        if (mw_rt == 2048) { if (Pw <= 4) ND4_MW(4, 1); else if (Pw <= 8) ND4_MW(4, 2); else ND4_MW(4, 4); }
-        else if (mw_rt == 1024) { if (Pw <= 4) ND4_MW(2, 1); else if (Pw <= 8) ND4_MW(2, 2); else ND4_MW(2, 4); }
-        else               { if (Pw <= 4) ND4_MW(1, 1); else if (Pw <= 8) ND4_MW(1, 2); else ND4_MW(1, 4); }
-#undef ND4_MW
-      } else if (tall8) {
-        launch_panel_row_wt<4, 8, 1024>(h, LU, N, strideM, j0, nb, P, ipiv, (int)batch, nopivot);
-      } else if (tall4) {
-        launch_panel_row_wt<8, 4, 1024>(h, LU, N, strideM, j0, nb, P, ipiv, (int)batch, nopivot);
-      } else if (m >= 64 && m <= 2048) {
-        if (m <= 512)       launch_panel_row<1>(h, LU, N, strideM, j0, nb, P, ipiv, (int)batch, nopivot);
-        else if (m <= 1024) launch_panel_row<2>(h, LU, N, strideM, j0, nb, P, ipiv, (int)batch, nopivot);
-        else                launch_panel_row<4>(h, LU, N, strideM, j0, nb, P, ipiv, (int)batch, nopivot);
-      } else {
-        int T = ((m * NB + 63) / 64) * 64; if (T > 1024) T = 1024; if (T < 64) T = 64;
-        hipLaunchKernelGGL(lu_panel_global, dim3((unsigned)batch), dim3(T), 0, h->stream, LU, N, strideM, j0, nb, P, ipiv, nopivot);
-      }
-      const int rest = N - j0 - nb;
-      if (N > nb && (!nopivot || rest > 0))
-        hipLaunchKernelGGL(lu_laswp, dim3((unsigned)((N - nb + 255) / 256), (unsigned)batch), dim3(256), 0, h->stream,
-                           LU, N, strideM, j0, nb, ipiv, nopivot ? 0 : 1, p_in_laswp ? P : (int32_t*)nullptr, bend);
-      const int inner = bend - j0 - nb;                        // columns of the block right of the panel
-      if (rest > 0 && inner > 0) {
-        ND4_HIP(hipGetLastError());
-        ND4_TRY(nd4_gemm(h, false, false, rest, inner, nb, -1.0,
-                         LU + (long)(j0 + nb) * N + j0, N, strideM,
-                         LU + (long)j0 * N + j0 + nb, N, strideM,
-                         1.0, LU + (long)(j0 + nb) * N + j0 + nb, N, strideM, batch));
-      }
-    }
-    if (two_level) ND4_TRY(outer_far(J, bend));
-      return 0;
-  };
-  // ---- look-ahead form (see lu_colblock_update): the panel at j0 shares its launch with everything the previous panel still owes the
-  //      other columns; between two panels only the next panel's 16 columns are updated (staged out of place by lu_narrow_fused).
-  //      Panels of <= 2048 rows: lu_panel_row_la; taller ones (two-level blocking, the rows over P workgroups): lu_panel_mw_la.
-  //      [j_from, j_to): the panels of the range; full_end: columns from there on get the interchanges only (two-level: the outer
-  //      block's end; their U12 and update come from outer_far). Returns the first column it did not factorise. ----
-  static const bool la_off = [] { const char* e = getenv("ND4HIP_LU_NO_LOOKAHEAD"); return e && *e && *e != '0'; }();
-  static const bool fuse_off = [] { const char* e = getenv("ND4HIP_LU_NO_FUSED_NARROW"); return e && *e && *e != '0'; }();
-  const bool fused = !fuse_off && (N & 1) == 0;
-  const long sStage = (long)NB * NB + (long)N * NB;
-  double* stage = nullptr;
-  // The look-ahead form (panel p in one workgroup, panel p - 1's column-block updates riding in the same launch) hides a latency
-  // chain behind otherwise idle CUs: right for one or a few matrices. A batch that fills the chip by itself is a throughput
-  // problem, for which the plain sequence panel -> interchanges + U12 -> rank-16 product on the MFMA kernel moves fewer bytes per
-  // launch (1024 x 512^2: 73.9 ms with the look-ahead form, 19.8 ms without; 8 matrices: 1.05 against 1.37 ms, 16: 1.64 against
-  // 1.48). ND4HIP_LU_LA_MAX_BATCH moves the switch.
-  const bool la_on = !la_off && N >= 64 + NB && p_in_laswp && batch <= la_max_batch;
+  c.sStage = (long)NB * NB + (long)N * NB;
   if (la_on) {
-    void* stg = nullptr;
-    ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)batch * sStage, &stg));
-    stage = static_cast<double*>(stg);
+    ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)batch * c.sStage, &ws));
+    c.stage = static_cast<double*>(ws);
   }
-  // (ND4HIP_LU_NO_FOLD=1: the narrow update of a multi-workgroup panel's columns as a launch of its own, as for the short panels)
-  static const bool fold_off = [] { const char* e = getenv("ND4HIP_LU_NO_FOLD"); return e && *e && *e != '0'; }();
-  auto la_range = [&](const int j_from, const int j_to, const int full_end, int* j_next) -> int {
-    int pj0 = -1, j0 = j_from;
-    bool narrow_done = true, folded = false;                  // folded: this panel's kernel does the previous panel's narrow update itself
-    for (; j0 < j_to && N - j0 >= 64; j0 += NB) {
-      const int m = N - j0;
-      // the panel at pj0 has reached its own columns and the 16 behind them (the narrow launch: [pj0 + NB, pj0 + 2 NB) = this panel,
-      // staged out of place by lu_narrow_fused); it still owes the columns from pj0 + 2 NB on, the columns left of it, and P
-      const int wide0 = pj0 + 2 * NB;
-      const int nupd = pj0 < 0 ? 0 : 1 + pj0 / NB + (wide0 < N ? (N - wide0 + NB - 1) / NB : 0);
-      const double* sg = (fused && pj0 >= 0 && !folded) ? stage : nullptr;
-      const int pp = pj0 < 0 ? 0 : pj0;
-      const int fold_arg = folded ? 1 : 0;
-      if (m > 2048) {
-        const int Pw = (m + mw_rt - 1) / mw_rt;
-        const dim3 grid((unsigned)(Pw + nupd), (unsigned)batch);
-#define ND4_MWLA(RR, PQ) hipLaunchKernelGGL((lu_panel_mw_la<RR, PQ>), grid, dim3(512), 0, h->stream, LU, N, strideM, j0, P, ipiv, nopivot, xbuf, stuck, Pw, pp, wide0, sg, sStage, full_end, fold_arg)
-        if (mw_rt == 2048)      { if (Pw <= 4) ND4_MWLA(4, 1); else if (Pw <= 8) ND4_MWLA(4, 2); else ND4_MWLA(4, 4); }
-        else if (mw_rt == 1024) { if (Pw <= 4) ND4_MWLA(2, 1); else if (Pw <= 8) ND4_MWLA(2, 2); else ND4_MWLA(2, 4); }
-        else                    { if (Pw <= 4) ND4_MWLA(1, 1); else if (Pw <= 8) ND4_MWLA(1, 2); else ND4_MWLA(1, 4); }
-#undef ND4_MWLA
-      } else {
-        const dim3 grid((unsigned)(1 + nupd), (unsigned)batch);
-        if (m <= 512)       hipLaunchKernelGGL(lu_panel_row_la<1>, grid, dim3(512), 0, h->stream, LU, N, strideM, j0, P, ipiv, nopivot, pp, wide0, sg, sStage, full_end);
-        else if (m <= 1024) hipLaunchKernelGGL(lu_panel_row_la<2>, grid, dim3(512), 0, h->stream, LU, N, strideM, j0, P, ipiv, nopivot, pp, wide0, sg, sStage, full_end);
-        else                hipLaunchKernelGGL(lu_panel_row_la<4>, grid, dim3(512), 0, h->stream, LU, N, strideM, j0, P, ipiv, nopivot, pp, wide0, sg, sStage, full_end);
-      }
-      const int c0 = j0 + NB;                                // the next panel's columns
-      const bool more = c0 < j_to && N - c0 >= 64;           // another look-ahead panel follows: stage its columns out of place
-      narrow_done = true;
-      folded = false;
-      if (more && !fold_off && mw_rt == 512 && m - NB > 2048) {
-        folded = true;                                       // the next panel is a multi-workgroup one with one row per thread: it folds this in
-      } else if (fused && more) {
-        hipLaunchKernelGGL(lu_narrow_fused, dim3((unsigned)((m - NB + 255) / 256), (unsigned)batch), dim3(256), 0, h->stream,
-                           LU, N, strideM, ipiv, nopivot, j0, stage, sStage);
-      } else if (c0 < full_end && c0 < N) {
-        hipLaunchKernelGGL(lu_narrow_top, dim3((unsigned)batch), dim3(512), 0, h->stream, LU, N, strideM, ipiv, nopivot, j0, c0);
-        hipLaunchKernelGGL(lu_narrow_gemm, dim3((unsigned)((m - NB + 255) / 256), (unsigned)batch), dim3(256), 0, h->stream, LU, N, strideM, j0, c0);
-      } else {
-        narrow_done = false;                                 // the range's last panel with nothing of the outer block right of it
-      }
-      pj0 = j0;
-    }
-    if (pj0 >= 0) {   // the last panel's debt
-      const int wide0 = narrow_done ? pj0 + 2 * NB : pj0 + NB;
-      const int nupd = 1 + pj0 / NB + (wide0 < N ? (N - wide0 + NB - 1) / NB : 0);
-      hipLaunchKernelGGL(lu_update_blocks, dim3((unsigned)nupd, (unsigned)batch), dim3(512), 0, h->stream, LU, N, strideM, P, ipiv, nopivot, pj0, wide0, full_end);
-    }
-    ND4_HIP(hipGetLastError());
-    *j_next = j0;
-    return 0;
-  };
+
+  int j = 0;                              // the first column not factorised yet
   // phase 1 (N > 2048): outer blocks while the panels are taller than 2048 rows
-  if (NBO < N) {
-    int J = 0;
-    for (; N - J > 2048; J += NBO) {
-      const int bend = J + NBO < N ? J + NBO : N;
-      if (la_on && mw_on && (bend - J) % NB == 0) {
-        int jn = 0;
-        ND4_TRY(la_range(J, bend, bend, &jn));
-        ND4_TRY(outer_far(J, bend));
-      } else {
-        ND4_TRY(outer_block(J, bend, true));
-      }
+  for (; N - j > 2048; j += LU_OUTER) {
+    if (la_on && c.mw_on) {
+      int jn = 0;
+      ND4_TRY(lu_la_range(c, j, j + LU_OUTER, j + LU_OUTER, &jn));
+      ND4_TRY(lu_outer_far(c, j, j + LU_OUTER));
+    } else {
+      ND4_TRY(lu_outer_block(c, j, j + LU_OUTER, true));
     }
-    j_start = J;
   }
   // phase 2: the look-ahead form on the whole matrix (N <= 2048) or on the trailing <= 2048 rows of a larger one
-  if (la_on && N - j_start <= 2048 && N - j_start >= 64 + NB) ND4_TRY(la_range(j_start, N, N, &j_start));
-  // phase 3: what is left (short panels after the look-ahead form; everything when it is switched off), one level
-  if (j_start < N) {
-    if (batch_two_level && !la_on) {
-      for (int J = j_start; J < N; J += NBO) {
-        const int bend = J + NBO < N ? J + NBO : N;
-        ND4_TRY(outer_block(J, bend, bend < N));
-      }
-    } else {
-      ND4_TRY(outer_block(j_start, N, false));
+  if (la_on && N - j >= 64 + NB) ND4_TRY(lu_la_range(c, j, N, N, &j));
+  // phase 3: what is left (short panels after the look-ahead form; everything for a batch that fills the chip)
+  if (batch_two_level) {
+    for (; j < N; j += NBO) {
+      const int bend = j + NBO < N ? j + NBO : N;
+      ND4_TRY(lu_outer_block(c, j, bend, bend < N));
     }
+  } else if (j < N) {
+    ND4_TRY(lu_outer_block(c, j, N, false));
   }
-  if (mw_on && p_in_laswp) hipLaunchKernelGGL(lu_mw_poison, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, P, total, stuck, h->xstat);
-  if (p_in_laswp) { ND4_HIP(hipGetLastError()); return 0; }
+  if (c.mw_on && c.p_in_laswp) hipLaunchKernelGGL(lu_mw_poison, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, P, total, c.stuck, h->xstat);
+  if (c.p_in_laswp) { ND4_HIP(hipGetLastError()); return 0; }
   if ((size_t)N * sizeof(int32_t) <= 60 * 1024)
-    hipLaunchKernelGGL(lu_build_perm, dim3((unsigned)batch), dim3(256), (size_t)N * sizeof(int32_t), h->stream, P, ipiv, N, nopivot);
+    hipLaunchKernelGGL(lu_build_perm, dim3((unsigned)batch), dim3(256), (size_t)N * sizeof(int32_t), h->stream, P, c.ipiv, N, nopivot);
   else
-    hipLaunchKernelGGL(lu_build_perm_global, dim3((unsigned)batch), dim3(256), 0, h->stream, P, ipiv, N, nopivot);
+    hipLaunchKernelGGL(lu_build_perm_global, dim3((unsigned)batch), dim3(256), 0, h->stream, P, c.ipiv, N, nopivot);
   ND4_HIP(hipGetLastError());
   return 0;
 }

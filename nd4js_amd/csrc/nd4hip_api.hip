@@ -43,8 +43,7 @@ extern "C" int nd4hip_dgemm_batched_dev(nd4hip_handle* h, int64_t batch, int64_t
   ND4_CHECK_ARG(strideB == 0 || strideB >= K * J, "nd4hip_dgemm_batched: strideB must be 0 or >= K*J");
   if (batch == 0 || I == 0 || J == 0) return 0;
   ND4_CHECK_ARG(C && (K == 0 || (A && B)), "nd4hip_dgemm_batched: NULL matrix pointer");   // K = 0: nothing is read, C = 0
-  for (int64_t b0 = 0; b0 < batch; b0 += 32768) {             // gridDim.y limit
-    const int64_t nb = batch - b0 < 32768 ? batch - b0 : 32768;
+  ND4_FOR_CHUNKS(batch) {
     ND4_TRY(nd4_gemm(h, false, false, I, J, K, 1.0, A + b0 * strideA, K, strideA, B + b0 * strideB, J, strideB,
                      0.0, C + b0 * I * J, J, I * J, nb));
   }
@@ -65,8 +64,7 @@ extern "C" int nd4hip_zgemm_batched_dev(nd4hip_handle* h, int a_complex, int b_c
                8.0 * (2.0 * batch * I * J + ea * (strideA ? batch : 1) * I * K + eb * (strideB ? batch : 1) * K * J));
   if (batch == 0 || I == 0 || J == 0) return 0;
   ND4_CHECK_ARG(C && (K == 0 || (A && B)), "nd4hip_zgemm_batched: NULL matrix pointer");   // K = 0: nothing is read
-  for (int64_t b0 = 0; b0 < batch; b0 += 32768) {             // gridDim.y limit
-    const int64_t nb = batch - b0 < 32768 ? batch - b0 : 32768;
+  ND4_FOR_CHUNKS(batch) {
     if (!a_complex)   // RC: A (I x K) times the K x 2J real view of B, into the I x 2J real view of C: the reference's products
       ND4_TRY(nd4_gemm(h, false, false, I, 2 * J, K, 1.0, A + b0 * strideA, K, strideA, B + 2 * b0 * strideB, 2 * J, 2 * strideB,
                        0.0, C + 2 * b0 * I * J, 2 * J, 2 * I * J, nb));

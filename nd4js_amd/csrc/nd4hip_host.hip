@@ -108,8 +108,7 @@ int run_block(nd4hip_handle* h, int dev, int64_t lo, int64_t hi, const std::vect
   std::vector<DevBuf> bufs(nops * 2);
   auto buf = [&](size_t i, int set) -> DevBuf& { return bufs[i * 2 + (size_t)(ops[i].stride ? set : 0)]; };
   int rc = 0;
-  static const bool one_stream = [] { const char* e = getenv("ND4HIP_HOST_ONE_STREAM"); return e && *e && *e != '0'; }();   // A/B switch
-  hipStream_t cs = (h->copy_stream && !one_stream) ? h->copy_stream : h->stream;       // copies; compute goes to h->stream
+  hipStream_t cs = h->copy_stream ? h->copy_stream : h->stream;       // copies; compute goes to h->stream
   auto fail = [&](int code) {
     // the block's copies / kernels may still be using the staging blocks: drain before the DevBufs go back to the cache
     (void)hipStreamSynchronize(cs); (void)hipStreamSynchronize(h->stream);

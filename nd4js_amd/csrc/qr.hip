@@ -682,107 +682,7 @@ struct QrhP {
 
 #include "qr_chain16.h"
 
-// (round 3's unblocked chains: kept behind -DND4HIP_QR_OLD_CHAINS for A/B builds)
-template <int K, int I>
-__device__ __forceinline__ void qrh_ge_row(double (&g)[16], double gk) {
-  if constexpr (I > K) g[I] = fma(-nd4dpp::rl_d(g[I], K), gk, g[I]);
-}
-template <int K, int... I>
-__device__ __forceinline__ void qrh_ge_rows(double (&g)[16], double gk, std::integer_sequence<int, I...>) { (qrh_ge_row<K, I>(g, gk), ...); }
-template <int K>
-__device__ __forceinline__ void qrh_ge_step(double (&g)[16], double (&d)[16]) {
-  const double pk = nd4dpp::rl_d(g[K], K);
-  d[K] = pk;
-  qrh_ge_rows<K>(g, g[K] * nd4dpp::fast_rcp(pk), std::make_integer_sequence<int, 16>{});     // row i -= G[i][K] * (row K / pivot)
-}
-template <int... K>
-__device__ __forceinline__ void qrh_ge_all(double (&g)[16], double (&d)[16], std::integer_sequence<int, K...>) { (qrh_ge_step<K>(g, d), ...); }
-
-// One wave. s_G: symmetric positive definite 16 x 16. Out: s_R = chol(G)^T (upper, G = R^T R), s_Ri = R^-1 (upper).
-// Lanes 0..15 hold the columns of G, lanes 16..31 the columns of I; elimination without pivoting leaves U = D L^T and L^-1,
-// R = D^-1/2 U, R^-1 = (D^-1/2 L^-1)^T. Returns true when every pivot is positive and >= thr * its diagonal entry.
-// Optional: s_Rt[j * 16 + i] = R[i][j] (column j contiguous) and s_rd[i] = 1 / R[i][i], what a forward substitution x R = c reads.
-__device__ __forceinline__ bool qrh_chol16(const double* __restrict__ s_G, double* __restrict__ s_R, double* __restrict__ s_Ri, double thr,
-                                           double* __restrict__ s_Rt = nullptr, double* __restrict__ s_rd = nullptr) {
-  const int lane = threadIdx.x & 63;
-  double g[16], d[16], d0[16];
-#pragma unroll
-  for (int i = 0; i < 16; i++) g[i] = lane < 16 ? s_G[i * 16 + lane] : ((lane - 16) == i ? 1.0 : 0.0);
-#define ND4_D0(K) d0[K] = nd4dpp::rl_d(g[K], K);
-  ND4_D0(0) ND4_D0(1) ND4_D0(2) ND4_D0(3) ND4_D0(4) ND4_D0(5) ND4_D0(6) ND4_D0(7)
-  ND4_D0(8) ND4_D0(9) ND4_D0(10) ND4_D0(11) ND4_D0(12) ND4_D0(13) ND4_D0(14) ND4_D0(15)
-#undef ND4_D0
-  qrh_ge_all(g, d, std::make_integer_sequence<int, 16>{});
-  bool ok = true;
-  double rs[16];
-#pragma unroll
-  for (int k = 0; k < 16; k++) {
-    ok = ok && (d[k] > 0.0) && (d[k] >= thr * d0[k]) && (d0[k] < DBL_MAX);
-    rs[k] = nd4dpp::fast_rsqrt(d[k]);
-  }
-  if (lane < 16) {
-#pragma unroll
-    for (int i = 0; i < 16; i++) s_R[i * 16 + lane] = (i <= lane) ? g[i] * rs[i] : 0.0;
-    if (s_Rt != nullptr) {
-#pragma unroll
-      for (int i = 0; i < 16; i++) s_Rt[lane * 16 + i] = (i <= lane) ? g[i] * rs[i] : 0.0;
-#pragma unroll
-      for (int i = 0; i < 16; i++) if (i == lane) s_rd[i] = rs[i];
-    }
-  } else if (lane < 32) {
-    const int c = lane - 16;
-#pragma unroll
-    for (int r = 0; r < 16; r++) s_Ri[c * 16 + r] = (r >= c) ? g[r] * rs[r] : 0.0;
-  }
-  return ok;
-}
-
-template <int K, int I>
-__device__ __forceinline__ void qrh_gj_row(double (&g)[16], double gk) {
-  if constexpr (I != K) g[I] = fma(-nd4dpp::rl_d(g[I], K), gk, g[I]);
-}
-template <int K, int... I>
-__device__ __forceinline__ void qrh_gj_rows(double (&g)[16], double gk, std::integer_sequence<int, I...>) { (qrh_gj_row<K, I>(g, gk), ...); }
-template <int K>
-__device__ __forceinline__ void qrh_gj_step(double (&g)[16], double (&sg)[16], int lane) {
-  const double p = nd4dpp::rl_d(g[K], K);
-  const double s = (p >= 0.0) ? -1.0 : 1.0;            // the pivot p - s has magnitude >= 1
-  sg[K] = s;
-  if (lane == K) g[K] -= s;
-  const double gk = g[K] * nd4dpp::fast_rcp(p - s);    // row K of [B | I], scaled
-  qrh_gj_rows<K>(g, gk, std::make_integer_sequence<int, 16>{});
-  g[K] = gk;
-}
-template <int... K>
-__device__ __forceinline__ void qrh_gj_all(double (&g)[16], double (&sg)[16], int lane, std::integer_sequence<int, K...>) { (qrh_gj_step<K>(g, sg, lane), ...); }
-
-// One wave. s_Z: top 16 x 16 block of the orthonormal Q. Gauss-Jordan elimination without pivoting of [Z - S | I] with
-// S_k = -sign(pivot) chosen on the way (lanes 0..15: columns of Z, lanes 16..31: columns of I -> B^-1, B = Z - S).
-// Out: s_S (signs) and s_K = K = -S B^-T (K[c][r] = -S_c B^-1[r][c]: lane 16 + c writes row c).
-__device__ __forceinline__ void qrh_gj16(const double* __restrict__ s_Z, double* __restrict__ s_K, double* __restrict__ s_S) {
-  const int lane = threadIdx.x & 63;
-  double g[16], sg[16];
-#pragma unroll
-  for (int i = 0; i < 16; i++) g[i] = lane < 16 ? s_Z[i * 16 + lane] : ((lane - 16) == i ? 1.0 : 0.0);
-  qrh_gj_all(g, sg, lane, std::make_integer_sequence<int, 16>{});
-  if (lane >= 16 && lane < 32) {
-    const int c = lane - 16;
-    double sc = 0.0;
-#pragma unroll
-    for (int k = 0; k < 16; k++) if (c == k) sc = sg[k];
-#pragma unroll
-    for (int r = 0; r < 16; r++) s_K[c * 16 + r] = -sc * g[r];
-    s_S[c] = sc;
-  }
-}
-
-#ifdef ND4HIP_QR_OLD_CHAINS
-#define ND4_CHOL16 qrh_chol16
-#define ND4_GJ16 qrh_gj16
-#else
 #define ND4_CHOL16 qrc_chol16_inv      // the eliminations on the matrix core (qr_chain16.h)
-#define ND4_GJ16 qrc_gj16
-#endif
 constexpr int QRH_LDS = 8 * 256 + 256 + NB * (NB + 1) + 16;      // doubles: what the row phases and the side work need ...
 constexpr int QRH_SMEM = QRH_LDS + 11 * 256 + 32;                // ... and the whole per-workgroup buffer: phase C carves its 16 x 16 matrices behind QRH_LDS
 
@@ -1427,7 +1327,6 @@ __global__ __launch_bounds__(512) void qrh_bc(const QrhP P) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
   }
-#ifndef ND4HIP_QR_OLD_CHAINS
   // R2 and R2^-1 on wave 0 (the products of the series on the matrix core, qr_chain16.h), then — workgroup 0 — the top block of Q,
   // R = R2 R1 and the elimination behind S and K, while the other waves form Q = Q1 R2^-1
   if (wave == 0) qrc_series16(s_E, series, s_R2, s_R2i, s_F);
@@ -1439,55 +1338,6 @@ __global__ __launch_bounds__(512) void qrh_bc(const QrhP P) {
     qrc_gj16(s_Z, s_K, s_S);
     __builtin_amdgcn_s_setprio(0);
   }
-#else
-  if (series) {
-    if (t < 256) {
-      double pp = 0.0;
-#pragma unroll
-      for (int l = 0; l < 16; l++) pp += s_F[l * 16 + i] * s_F[l * 16 + j];
-      s_P[t] = pp;
-    }
-    __syncthreads();
-    if (t < 256) {
-      const double xx = s_E[t] - s_P[t];
-      s_F[t] = (i < j) ? xx : ((i == j) ? 0.5 * xx : 0.0);
-    }
-    __syncthreads();
-    if (t < 256) {
-      double pp = 0.0;
-#pragma unroll
-      for (int l = 0; l < 16; l++) pp += s_F[i * 16 + l] * s_F[l * 16 + j];
-      s_P[t] = pp + ((i == j) ? 1.0 : 0.0);                            // I + F^2
-      s_R2[t] = s_F[t] + ((i == j) ? 1.0 : 0.0);
-    }
-    __syncthreads();
-    if (t < 256) {
-      double pp = 0.0;
-#pragma unroll
-      for (int l = 0; l < 16; l++) pp += (((i == l) ? 1.0 : 0.0) - s_F[i * 16 + l]) * s_P[l * 16 + j];
-      s_R2i[t] = pp;
-    }
-  } else {
-    if (t < 256) s_E[t] += (i == j) ? 1.0 : 0.0;
-    __syncthreads();
-    if (wave == 0) (void)ND4_CHOL16(s_E, s_R2, s_R2i, 0.0);
-  }
-  __syncthreads();
-  if (g == 0) {                                                        // only workgroup 0 holds the top block: Z, R, K, S
-    if (t < 256) {
-      double z = 0.0, rr = 0.0;
-#pragma unroll
-      for (int l = 0; l < 16; l++) {
-        z += s_Qt[i * 16 + l] * s_R2i[l * 16 + j];                     // top block of Q = Q1 R2^-1
-        rr += s_R2[i * 16 + l] * s_R[l * 16 + j];                      // R = R2 R1
-      }
-      s_Z[t] = z; s_Rm[t] = rr;
-    }
-    __syncthreads();
-    qrh_stamp(P, 5);
-    if (wave == 0) { __builtin_amdgcn_s_setprio(3); ND4_GJ16(s_Z, s_K, s_S); __builtin_amdgcn_s_setprio(0); }
-  }
-#endif
 #pragma unroll
   for (int kk = 0; kk < 4; kk++) bw[kk] = s_R2i[(4 * fk + kk) * 16 + fx];
   d4 y[4];

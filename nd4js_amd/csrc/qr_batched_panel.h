@@ -1,5 +1,5 @@
 // Batched QR panels on the matrix cores: ONE workgroup per panel, no exchange between workgroups (round 4).
-// Included by qr.hip inside its anonymous namespace, after qr_panel_row_body, qrh_chol16 and qrh_gj16.
+// Included by qr.hip inside its anonymous namespace, after qr_panel_row_body and qr_chain16.h.
 //
 // Replaces, for batches of panels, the thread-per-row Householder kernel qr_panel_row (the inner step of qr_decomp,
 // src/la/qr.js:54-68): that kernel walks 16 dependent column steps of ~530 instructions per wave, and a batch that fills the chip
@@ -17,7 +17,7 @@
 //                   triangle; the matrix-core form multiplies by the full inverse), no re-layout
 //   R2, Q = Q1 R2^-1  E = Q1^T Q1 - I by the same Gram routine, R2 = I + F from the fixed-point series on one wave (chol when
 //                   max|E| > HR_SERIES_MAX), the same substitution again: Q orthonormal to O(eps)
-//   (V, T, R)       V = Q - [S; 0], T = K = -S (Q_top - S)^-T (qrh_gj16, in the shadow of the row stores), R = S R2 R1
+//   (V, T, R)       V = Q - [S; 0], T = K = -S (Q_top - S)^-T (qrc_gj16, in the shadow of the row stores), R = S R2 R1
 // ZERO: rows below the top block of the panel's columns in W are zeroed (the in-matrix panels of the batched QR driver); the
 // panel entry point leaves them alone, so a panel moves its algorithmic 16 m b bytes and nothing else.
 
@@ -408,7 +408,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void qrb_panel(double* __restrict__ Wm
   // ---- Q = Q1 R2^-1; V = Q - [S; 0] ----
   qrb_trsolve<R>(a, s_R2t, s_rd2, [&](int k) { stamp(17 + k); });
   stamp(10);
-  // Wave 0 first completes the top block (the 16-step elimination behind S and K: qrh_gj16), while the other waves' row stores
+  // Wave 0 first completes the top block (the 16-step elimination behind S and K: qrc_gj16), while the other waves' row stores
   // fill the memory pipeline, and stores its own rows last: behind its own row stores the top block's few stores waited in the
   // queue for up to 10 us.
   double* s_Z = s_X; double* s_K = s_X + 256;

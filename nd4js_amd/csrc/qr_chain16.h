@@ -5,7 +5,7 @@
 // fk = lane >> 4) is M[4 r + fk][fx]. Row k of M is register k / 4 at the 16 lanes fk == k % 4 — exactly where k-slot k % 4 of a B
 // operand (lane (n, kk): B[kk][n]) and of an A operand (lane (m, kk): A[m][kk]) is read. So a rank-1 update  M -= x y^T  with x
 // and y derived from ROW k of M (or of M^T, kept alongside) is one MFMA whose operands are "that row where fk == k % 4, zero
-// elsewhere": no readlane broadcast of 15 multipliers, no 15 row updates. The unblocked chains this replaces (qrh_chol16 / qrh_gj16:
+// elsewhere": no readlane broadcast of 15 multipliers, no 15 row updates. The unblocked chains this replaced (since removed:
 // per pivot 2 readlanes + 1 FMA for each remaining row, ~60 instructions of ONE wave per step at ~8 cycles each) took 3.5 and 4.4 us
 // of a 30-40 us panel; a step is now the pivot's readlane, its reciprocal (square root), a few selects and one to three MFMAs.
 // (A 4 x 4-blocked Cholesky with the diagonal block factorised redundantly by all lanes was measured first: 2.5 us, bound by the
@@ -71,7 +71,7 @@ template <int... K>
 __device__ __forceinline__ void qrc_chol_inv_all(d4& g, d4& y, double (&rrow)[4], double (&rsreg)[4], int fx, int fk, std::integer_sequence<int, K...>) {
   (qrc_chol_inv_step<K>(g, y, rrow, rsreg, fx, fk), ...);
 }
-// One wave; drop-in for qrh_chol16: s_G symmetric positive definite 16 x 16 (row major, all 256 entries). Out: s_R = chol(G)^T
+// One wave. s_G symmetric positive definite 16 x 16 (row major, all 256 entries). Out: s_R = chol(G)^T
 // (upper, G = R^T R) and s_Ri = R^-1 (upper), row major. Returns true when every pivot is positive and >= thr * its diagonal entry.
 __device__ __forceinline__ bool qrc_chol16_inv(const double* __restrict__ s_G, double* __restrict__ s_R, double* __restrict__ s_Ri, double thr) {
   const int lane = threadIdx.x & 63, fx = lane & 15, fk = lane >> 4;

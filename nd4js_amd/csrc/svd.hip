@@ -10,15 +10,14 @@
 //     same permutation applied to U^T rows and V rows, U transposed at the end.
 // W = Ut * A is iterated (Ut = accumulated left rotations, starts as I): at convergence the rows of W
 // are orthogonal, sv_i = |w_i|, V_i = w_i / sv_i, U = Ut^T. Rows are contiguous -> every access is
-// coalesced. Pairs follow a round-robin tournament: N/2 disjoint pairs per step, N-1 steps per sweep,
-// one workgroup per pair; the three inner products use wave shuffle reductions.
+// coalesced. Pairs follow a round-robin tournament: N/2 disjoint pairs per step, N-1 steps per sweep
+// (N <= 64: jac_small, row pairs in LDS; larger N: the same tournament over 64-row blocks, svd_block.hip).
 // Rectangular input is reduced to square by QR first (svd_jac_2sided.js:42-52 does the same).
 #include "svd_internal.h"
 #include "dpp.h"
 #include <cmath>
 #include <cfloat>
 #include <cstring>
-#include <cstdlib>
 
 namespace {
 
@@ -28,62 +27,6 @@ __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
   return v;
-}
-
-__global__ __launch_bounds__(256) void jac_step(double* __restrict__ Wm, double* __restrict__ Utm, int N, long strideM,
-                                                 int n2, int step, double tol2, JacState* __restrict__ st,
-                                                 const double* __restrict__ floor2, unsigned long long* __restrict__ offmax) {
-  const int mat = blockIdx.y;
-  if (st[mat].done) return;
-  int p, q;
-  nd4_rr_pair(n2, step, blockIdx.x, p, q);
-  if (q >= N) return;                                  // dummy player of an odd N
-  double* wp = Wm + mat * strideM + (long)p * N;
-  double* wq = Wm + mat * strideM + (long)q * N;
-  const int t = threadIdx.x;
-  double aa = 0.0, bb = 0.0, ab = 0.0;
-  for (int j = t; j < N; j += 256) {
-    const double a = wp[j], b = wq[j];
-    aa += a * a; bb += b * b; ab += a * b;
-  }
-  __shared__ double s_red[4][3];
-  aa = wave_sum(aa); bb = wave_sum(bb); ab = wave_sum(ab);
-  if ((t & 63) == 0) { s_red[t >> 6][0] = aa; s_red[t >> 6][1] = bb; s_red[t >> 6][2] = ab; }
-  __syncthreads();
-  aa = (s_red[0][0] + s_red[1][0]) + (s_red[2][0] + s_red[3][0]);
-  bb = (s_red[0][1] + s_red[1][1]) + (s_red[2][1] + s_red[3][1]);
-  ab = (s_red[0][2] + s_red[1][2]) + (s_red[2][2] + s_red[3][2]);
-  // rows at or below the noise floor N*eps*max|a_i| carry no information (a rotation only swaps
-  // rounding noise): they are frozen here and get an orthonormal completion in the epilogue
-  const double fl = floor2[mat];
-  if (aa <= fl || bb <= fl) return;
-  const double lim = tol2 * aa * bb;
-  if (!(ab * ab > lim)) return;                        // orthogonal enough (also: NaN)
-  // rotation that zeroes the inner product: t^2 + 2*zeta*t - 1 = 0, smaller root
-  const double zeta = (bb - aa) / (2.0 * ab);
-  const double tn = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-  const double c = 1.0 / sqrt(1.0 + tn * tn), s = c * tn;
-  // Rutishauser form with tau = tan(theta/2): x_p' = x_p - s (x_q + tau x_p), x_q' = x_q + s (x_p - tau x_q).
-  // 1 - c = s*tau is carried exactly, so the rotation stays orthogonal to O(eps * theta^2) even when c
-  // rounds to 1 (plain c*x - s*y grows every row norm by theta^2 per tiny rotation: a systematic drift).
-  const double tau = s / (1.0 + c);
-  for (int j = t; j < N; j += 256) {
-    const double a = wp[j], b = wq[j];
-    wp[j] = a - s * (b + tau * a);
-    wq[j] = b + s * (a - tau * b);
-  }
-  double* up = Utm + mat * strideM + (long)p * N;
-  double* uq = Utm + mat * strideM + (long)q * N;
-  for (int j = t; j < N; j += 256) {
-    const double a = up[j], b = uq[j];
-    up[j] = a - s * (b + tau * a);
-    uq[j] = b + s * (a - tau * b);
-  }
-  if (t == 0) {
-    atomicAdd(&st[mat].rotations, 1u);
-    const double rel = (ab * ab) / (aa * bb);          // cos^2 of the angle before the rotation
-    atomicMax(offmax, (unsigned long long)__double_as_longlong(rel));
-  }
 }
 
 // floor2[mat] = (N*eps)^2 * max_i |w_i|^2 from the row norms (jac_norms); one workgroup per matrix
@@ -233,7 +176,11 @@ __global__ __launch_bounds__(1024) void jac_complete(double* __restrict__ Vm, in
 // padded to an odd stride), 8 lanes own a row pair of the current round (32 pairs x 8 lanes = 256 threads; each lane 1/8 of the
 // columns, the three inner products meet by three DPP-free shuffle steps inside the 8 lanes), one barrier per round, and the sweep loop
 // runs on the device until a sweep rotates nothing — the same rule (svd_jac_2sided.js:95-97, :112 in its one-sided form), the same
-// noise floor and the same Rutishauser rotation as jac_step. W and Ut go back to global memory for the common epilogue.
+// noise floor (rows at or below N*eps*max|a_i| carry no information — a rotation only swaps rounding noise — so they are frozen
+// and get an orthonormal completion in the epilogue) and the rotation that zeroes the inner product (t^2 + 2*zeta*t - 1 = 0, smaller
+// root) in Rutishauser's form with tau = tan(theta/2): x_p' = x_p - s (x_q + tau x_p), x_q' = x_q + s (x_p - tau x_q). 1 - c = s*tau is
+// carried exactly, so the rotation stays orthogonal to O(eps * theta^2) even when c rounds to 1 (plain c*x - s*y grows every row
+// norm by theta^2 per tiny rotation: a systematic drift). W and Ut go back to global memory for the common epilogue.
 template <int NMAX>
 __global__ __launch_bounds__(256) void jac_small(double* __restrict__ Wm, double* __restrict__ Utm, int N, long strideM, double tol2,
                                                   double* __restrict__ floor2_out, unsigned* __restrict__ sweeps_max, unsigned* __restrict__ not_converged,
@@ -351,18 +298,13 @@ int jacobi_square(nd4hip_handle* h, int batch, int N, double* W, double* U, doub
   Nd4WsScope scope(h);
   const long sM = (long)N * N;
   void* p = nullptr;
-  // Block Jacobi on the matrix cores (svd_block.hip) wants N = 0 mod 64. Other N >= 16 run it on the matrix padded with
+  // Block Jacobi on the matrix cores (svd_block.hip) wants N = 0 mod 64. Other N > 64 run it on the matrix padded with
   // zero rows and columns to Np = the next multiple of 64: a zero row has norm 0 < the noise floor and is never rotated, a
   // zero column stays zero under row rotations, so the leading N x N parts of W and Ut evolve exactly as they would alone
-  // (Ut' = diag(Ut, I)) and are copied back before the epilogue. (The row-pair kernel it replaces there is 4-6x slower:
-  // N = 1000 took 222 ms against 39 ms at 1024.)
-  // environment switches are read once per process (never inside the sweep loop)
-  static const bool noblock = getenv("ND4HIP_SVD_NOBLOCK") != nullptr;
-  static const bool precheck_always = getenv("ND4HIP_JAC_PRECHECK_ALWAYS") != nullptr;
-  static const bool debug = getenv("ND4HIP_SVD_DEBUG") != nullptr;
-  static const bool small_off = getenv("ND4HIP_SVD_NO_SMALL") != nullptr;
-  const bool small = !small_off && N > 1 && N <= 64;              // all sweeps in one launch (jac_small)
-  const bool blocked = N >= 16 && !noblock && !small;             // (without jac_small: below 16 the row-pair kernel)
+  // (Ut' = diag(Ut, I)) and are copied back before the epilogue. (A kernel with one workgroup per row pair, used there before, was
+  // 4-6x slower: N = 1000 took 222 ms against 39 ms at 1024.)
+  const bool small = N > 1 && N <= 64;                            // all sweeps in one launch (jac_small)
+  const bool blocked = N > 64;                                    // block sweeps, one sweep per pass of the loop below (N = 1: nothing to rotate)
   const int Np = blocked ? ((N + 63) / 64) * 64 : N;
   const bool padded = Np != N;
   const long sMp = (long)Np * Np;
@@ -400,7 +342,6 @@ int jacobi_square(nd4hip_handle* h, int batch, int N, double* W, double* U, doub
   double* Wb = padded ? Wp : W;                                         // what the block sweeps work on
   double* Utb = padded ? Utpad : Ut;
 
-  const int n2 = (N + 1) & ~1;
   const double eps = 0x1p-52, tol = N * eps, tol2 = tol * tol;
   if (!small) {
     hipLaunchKernelGGL(jac_norms, dim3((unsigned)((N + 3) / 4), (unsigned)batch), dim3(256), 0, h->stream, W, N, sM, svr);
@@ -409,7 +350,7 @@ int jacobi_square(nd4hip_handle* h, int batch, int N, double* W, double* U, doub
   int sweeps = 0;
   unsigned long long last_off = 0, rot_seen = 0;
   // the first sweep of a large matrix rotates (nearly) every pair; afterwards the rotation count of the last sweep decides
-  bool dense_phase = blocked && Np >= 512 && !precheck_always;
+  bool dense_phase = blocked && Np >= 512;
   if (small) {
     // all sweeps in ONE launch, one workgroup per matrix (jac_small); sweeps_max lives in the word behind `active`
     ND4_HIP(hipMemsetAsync(active, 0, 16, h->stream));
@@ -421,32 +362,20 @@ int jacobi_square(nd4hip_handle* h, int batch, int N, double* W, double* U, doub
     sweeps = (int)h_active[1];
     last_off = *h_off;
     if (h_active[0] != 0) sweeps = MAX_SWEEPS;                        // some matrix did not converge
-  } else
-  if (N > 1) {
+  } else if (blocked) {
     for (;;) {
       ND4_HIP(hipMemsetAsync(active, 0, 16, h->stream));            // active + offmax (the rotation total runs on)
-      if (blocked) {
-        ND4_TRY(nd4_jacobi_block_sweep(h, batch, Np, Wb, Utb, st, floor2, tol2, offmax, bscratch, dense_phase));
-      } else {
-        for (int s = 0; s < n2 - 1; s++)
-          hipLaunchKernelGGL(jac_step, dim3((unsigned)(n2 / 2), (unsigned)batch), dim3(256), 0, h->stream,
-                             W, Ut, N, sM, n2, s, tol2, st, floor2, offmax);
-      }
+      ND4_TRY(nd4_jacobi_block_sweep(h, batch, Np, Wb, Utb, st, floor2, tol2, offmax, bscratch, dense_phase));
       hipLaunchKernelGGL(jac_sweep_end, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, h->stream, st, batch, active, rot_total);
       ND4_HIP(hipGetLastError());
       sweeps++;
       // The convergence flag is read back (one stream synchronisation) after every sweep for large matrices; a sweep of a
-      // small matrix costs less than the round trip, so it is checked every 4th (N <= 64) / 2nd (N <= 256) sweep only:
+      // small matrix costs less than the round trip, so it is checked every 2nd sweep only (Np <= 256):
       // converged matrices are skipped on the device anyway (JacState.done), an extra sweep over them rotates nothing.
-      const int check_every = Np <= 64 ? 4 : (Np <= 256 ? 2 : 1);
+      const int check_every = Np <= 256 ? 2 : 1;
       if (sweeps % check_every != 0 && sweeps < MAX_SWEEPS) continue;
       ND4_HIP(hipMemcpyAsync(h_active, active, 24, hipMemcpyDeviceToHost, h->stream));   // active, offmax, rotation total
       ND4_HIP(hipStreamSynchronize(h->stream));
-      if (debug) {
-        double r; unsigned long long bb = *h_off; memcpy(&r, &bb, 8);
-        fprintf(stderr, "[nd4hip svd] sweep %d: active matrices %u, max |cos| found %.3e, rotations so far %llu\n", sweeps, h_active[0], sqrt(r),
-                (unsigned long long)h_off[1]);
-      }
       if (h_active[0] == 0) { last_off = *h_off; break; }
       last_off = *h_off;
       {

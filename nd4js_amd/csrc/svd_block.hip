@@ -1,11 +1,10 @@
-// Block one-sided Jacobi sweeps for the SVD (N % 64 == 0): the HBM-bound row-pair rotations of
-// svd.hip become GEMM-shaped work on the fp64 matrix cores.
+// Block one-sided Jacobi sweeps for the SVD (N % 64 == 0): the HBM-bound rotations of row pairs
+// become GEMM-shaped work on the fp64 matrix cores.
 //
 // Rows are grouped in blocks of 32; a sweep visits every block pair (I,J) once (round-robin tournament
 // over blocks, nblk/2 disjoint pairs per step). For each pair, X = [W_I; W_J] (64 x N):
-//   jacb_gram    Gp[chunk] = X[:,chunk] X[:,chunk]^T      fp64 MFMA fed straight from global memory
-//                (the A and B fragments of a Gram product are the SAME "16 rows x 4 k" register image;
-//                 one 16-byte load feeds two MFMA k-steps); wave w owns tile-row w -> no reduction.
+//   jacb_gram2   Gp[chunk] = X[:,chunk] X[:,chunk]^T      fp64 MFMA; the chunk is staged through LDS, every wave owns
+//                2-3 of the ten tiles of the symmetric product over all of the chunk's columns -> no reduction.
 //   jacb_eigen   G = sum_chunks Gp; cyclic two-sided Jacobi on the 64x64 Gram matrix in LDS with the
 //                reference's relative criterion (svd_jac_2sided.js:112, one-sided form) and the noise
 //                floor of svd.hip; 32 disjoint rotations per round, each wave owns 8 of them (angles
@@ -96,18 +95,6 @@ __device__ __forceinline__ void gram_mfma_group(d4 (&acc)[4][4], const d2 (&f)[2
         acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(f[u][i].y, f[u][j].y, acc[i][j], 0, 0, 0);
       }
 }
-// NG groups of 16 columns starting at col0, all inside the matrix; the loads of group g+1 are in flight while the 40 MFMAs of
-// group g run (straight-line code: the register indices of the two fragment buffers are static)
-template <int NG>
-__device__ __forceinline__ void gram_accumulate_fixed(d4 (&acc)[4][4], const double* const (&rp)[4], int col0, int fk) {
-  d2 f[2][2][4];
-  gram_load_group(f[0], rp, col0 + 4 * fk);
-#pragma unroll
-  for (int g = 0; g < NG; g++) {
-    if (g + 1 < NG) gram_load_group(f[(g + 1) & 1], rp, col0 + (g + 1) * 16 + 4 * fk);
-    gram_mfma_group(acc, f[g & 1]);
-  }
-}
 // any number of columns (a multiple of 16), clipped at N (a multiple of 16)
 __device__ __forceinline__ void gram_accumulate(d4 (&acc)[4][4], const double* const (&rp)[4], int col0, int ncols, int N, int fk) {
   for (int c0 = col0; c0 < col0 + ncols && c0 < N; c0 += 16) {
@@ -139,38 +126,10 @@ __device__ __forceinline__ void gram_reduce_lds(double (*G)[LDG], const d4 (&acc
   }
 }
 
-__global__ __launch_bounds__(256) void jacb_gram(const double* __restrict__ Wm, int N, long sM, int nblk, int nblk2, int step,
-                                                  const JacState* __restrict__ st, double* __restrict__ Gpart, int nchunks, long sG_mat) {
-  __shared__ double s_g[PB][PB + 1];
-  const int pairIdx = blockIdx.x, chunk = blockIdx.y, mat = blockIdx.z;
-  if (st[mat].done) return;
-  int I, J;
-  jacb_pair(nblk2, step, pairIdx, I, J);
-  if (J >= nblk) return;
-  const double* W = Wm + mat * sM;
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int fx = lane & 15, fk = lane >> 4;
-  const double* rp[4];
-#pragma unroll
-  for (int t = 0; t < 4; t++) rp[t] = W + pair_row(t * 16 + fx, I, J) * N;
-  // wave w owns columns [col0 + 64 w, +64) of the chunk and accumulates ALL 16 tiles over them: every
-  // fragment is loaded by exactly one wave
-  d4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; i++)
-#pragma unroll
-    for (int j = 0; j < 4; j++) acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
-  const int col0 = chunk * CH + wave * (CH / 4);
-  if (col0 + CH / 4 <= N) gram_accumulate_fixed<CH / 64>(acc, rp, col0, fk);   // N % 64 == 0: a wave's strip is inside or outside
-  gram_reduce_lds<PB + 1>(s_g, acc, wave, fk, fx);
-  double* G = Gpart + mat * sG_mat + ((long)pairIdx * nchunks + chunk) * (PB * PB);
-  for (int e = threadIdx.x; e < PB * PB; e += 256) G[e] = s_g[e / PB][e % PB];
-}
-
-// ---- Gram partials, second form: tiles per wave, fragments through LDS -------------------------------------------------------
-// jacb_gram gives every wave its own columns and ALL ten tiles: each wave then loads four 16-row fragments straight from global
-// memory in MFMA layout (16 rows x 64 B per instruction) and the four waves' accumulators meet in a 4-phase LDS reduction.
-// Here the 64 x 256 chunk is staged through LDS in four sub-chunks of 64 columns (coalesced: 32 lanes read one 512-B row segment),
+// ---- Gram partials: tiles per wave, fragments through LDS ---------------------------------------------------------------------
+// (The fused Gram of jacb_eigen<true> gives every wave its own columns and ALL ten tiles: each wave then loads four 16-row fragments
+// straight from global memory in MFMA layout (16 rows x 64 B per instruction) and the four waves' accumulators meet in a 4-phase
+// LDS reduction.) Here the 64 x 256 chunk is staged through LDS in four sub-chunks of 64 columns (coalesced: 32 lanes read one 512-B row segment),
 // double-buffered, and each wave owns 2-3 of the ten tiles over ALL columns: no cross-wave reduction, every wave stores its
 // tiles itself. LDS image [64][66]: lane (fx, fk) of a fragment read hits bank (4 fx + 2 fk) mod 64 -> conflict-free b64 reads.
 template <int NT>
@@ -317,7 +276,7 @@ __global__ __launch_bounds__(2048 / PW) void jacb_eigen(const double* __restrict
       else nd4_rr_pair(PB, r, wave * PW + (lane & (PW - 1)), p, q);
       const double a = G[p][p], b = G[q][q], g = G[p][q];
       const bool go = (a > fl) && (b > fl) && (g * g > tol2 * a * b);
-      double c = 1.0, s = 0.0;                              // kept as (s, tau = tan(theta/2)): see svd.hip jac_step
+      double c = 1.0, s = 0.0;                              // kept as (s, tau = tan(theta/2)): Rutishauser's form, see svd.hip jac_small
       if (go) {
         // t = sign(zeta) / (|zeta| + sqrt(1 + zeta^2)), zeta = (b-a)/(2g), rewritten without the division by g
         const double d = b - a, hh = 2.0 * g, rr = d * d + hh * hh;
@@ -698,145 +657,155 @@ size_t nd4_jacobi_block_scratch_doubles(int batch, int N) {
   return per * batch;                                // Gram partials + two sets of (Qt, flags): see jacb_eigen_pu
 }
 
-int nd4_jacobi_block_sweep(nd4hip_handle* h, int batch, int N, double* W, double* Ut, JacState* st,
-                           const double* floor2, double tol2, unsigned long long* offmax, double* scratch, bool dense_phase) {
-  const int nblk = N / BB, nblk2 = (nblk + 1) & ~1, npairs = nblk2 / 2, nchunks = (N + CH - 1) / CH;
-  const long sM = (long)N * N;
-  const long sG = (long)npairs * nchunks * PB * PB, sQ = (long)npairs * PB * PB;
-  double* Gpart = scratch;
-  const long sF = ((npairs + 1) / 2 + 1) * 2;          // ints per matrix
-  double* Qt2[2]; int* flags2[2];
-  Qt2[0] = Gpart + (size_t)batch * sG;
-  flags2[0] = reinterpret_cast<int*>(Qt2[0] + (size_t)batch * sQ);
-  Qt2[1] = Qt2[0] + (size_t)batch * sQ + (size_t)batch * (sF / 2);
-  flags2[1] = reinterpret_cast<int*>(Qt2[1] + (size_t)batch * sQ);
-  static const bool no_defer = getenv("ND4HIP_JAC_NO_DEFER") != nullptr;           // A/B switch
-  const bool defer = !no_defer && (long)batch * npairs <= 64 && N >= 512;            // see jacb_eigen_pu
-  // Round 3: two chains of launches side by side. The rotation kernel of a step keeps only npairs workgroups busy for ~26 us (issue-
-  // bound on their CUs) while Gram and the W update are throughput kernels; in ONE stream they cannot overlap (a launch that combines
-  // the rotation kernel of one pair group with the Gram / update of another still has the rotation kernel in two of every three
-  // launches). With the block-recursive tournament of jacb_pair the slots [0, npairs/2) and [npairs/2, npairs) of every step are two
-  // closed groups for a whole phase, so each group's Gram -> rotation -> update chain runs on its own stream (chain A on the handle's
-  // stream, chain B on aux_stream) and the rotation kernel of one chain runs beside the throughput kernels of the other. The chains
-  // meet at the three phase ends of a sweep (one event pair each); the step before a meeting applies W and U together (no deferred
-  // U update across a meeting). Single large matrix only.
-  // Measured: 4096^2 317 -> 268 ms; 2048^2 57.5 -> 57.3 and 1024^2 22.6 -> 23.4 ms: there each of the three kernels of a step is ONE wave of
-  // workgroups whose duration does not shrink with half the pairs (Gram 12.2 -> 11.5 us, W update 16.6 -> 18.7, and the rotation kernel
-  // slows from 26 to 35 us when it shares the chip), so a chain's step takes as long as the whole step did. Hence N >= 4096 only
-  // (ND4HIP_JAC_TWO_CHAINS=<min N> moves the threshold, 0 switches it off) — and, because the deferred U update needs
-  // batch * npairs <= 64 (`defer`: N <= 4096 with 32-row blocks), in effect for padded N == 4096 alone: 8192^2 keeps one chain.
-  const char* two_e = getenv("ND4HIP_JAC_TWO_CHAINS");      // (read per sweep, not cached: the tests move the threshold)
-  const int two_env = two_e ? atoi(two_e) : 4096;
-  const bool two_off = two_env <= 0;
-  const int two_min_n = two_env > 0 ? two_env : 1 << 30;
-  if (!two_off && defer && batch == 1 && nblk % 4 == 0 && N >= two_min_n) {
-    const int n2 = -nblk, hq = nblk / 2, q = nblk / 4, nsteps = nblk - 1;
-    static const int wstrips_env2 = getenv("ND4HIP_JAC_WSTRIPS") ? atoi(getenv("ND4HIP_JAC_WSTRIPS")) : 0;
-    const int wstrips = wstrips_env2 ? wstrips_env2 : (N <= 2048 ? 1 : 2);
-    hipStream_t chain[2] = {h->stream, h->aux_stream};
-    auto meet = [&]() -> int {                               // both chains wait for each other
+namespace {
+
+// one sweep's arguments and the scratch layout (nd4_jacobi_block_scratch_doubles), shared by the two forms of the sweep
+struct JacbSweep {
+  nd4hip_handle* h;
+  int batch, N; double* W; double* Ut; JacState* st; const double* floor2; double tol2; unsigned long long* offmax;
+  int precheck;                          // jacb_eigen_p / _pu: 0 while (nearly) every pair still rotates (the dense first sweeps)
+  int nblk, npairs, nchunks;
+  long sM, sG, sQ, sF;                   // per matrix: W / Ut, Gram partials, Qt (doubles), flags (ints)
+  double* Gpart; double* Qt2[2]; int* flags2[2];   // Qt and flags alternate by step where the U update is deferred (see jacb_eigen_pu)
+  int wstrips;                           // jacb_apply_w<1 | 2>. 2048^2: 58.8 ms with 256-column chunks, 57.5 with 128, 57.2 with 64; 4096^2: 322 / 318 / 328
+};
+
+// W <- Qt W alone for slots [p0, p0 + np) of the step (deferred: Ut follows with the next step's rotation kernel)
+void jacb_launch_apply_w(const JacbSweep& s, hipStream_t stream, int n2, int step, int np, int batch, double* Qt, int* flags, int p0) {
+  if (s.wstrips == 1)
+    hipLaunchKernelGGL(jacb_apply_w<1>, dim3((unsigned)np, (unsigned)(s.N / 64), (unsigned)batch), dim3(256), 0, stream,
+                       s.W, s.N, s.sM, s.nblk, n2, step, s.st, Qt, s.sQ, flags, s.sF, p0);
+  else
+    hipLaunchKernelGGL(jacb_apply_w<2>, dim3((unsigned)np, (unsigned)((s.N + 127) / 128), (unsigned)batch), dim3(256), 0, stream,
+                       s.W, s.N, s.sM, s.nblk, n2, step, s.st, Qt, s.sQ, flags, s.sF, p0);
+}
+
+// Two chains of launches side by side (one large matrix, nblk % 4 == 0, deferred U update). The rotation kernel of a step keeps only
+// npairs workgroups busy for ~26 us (issue-bound on their CUs) while Gram and the W update are throughput kernels; in ONE stream they
+// cannot overlap (a launch that combines the rotation kernel of one pair group with the Gram / update of another still has the
+// rotation kernel in two of every three launches). With the block-recursive tournament of jacb_pair the slots [0, npairs/2) and
+// [npairs/2, npairs) of every step are two closed groups for a whole phase, so each group's Gram -> rotation -> update chain runs on
+// its own stream (chain A on the handle's stream, chain B on aux_stream) and the rotation kernel of one chain runs beside the
+// throughput kernels of the other. The chains meet at the three phase ends of a sweep (one event pair each); the step before a
+// meeting applies W and U together (no deferred U update across a meeting).
+int jacb_sweep_two_chains(const JacbSweep& s) {
+  nd4hip_handle* h = s.h;
+  const int N = s.N, nblk = s.nblk, npairs = s.npairs, nchunks = s.nchunks;
+  const int n2 = -nblk, hq = nblk / 2, q = nblk / 4, nsteps = nblk - 1;
+  hipStream_t chain[2] = {h->stream, h->aux_stream};
+  // step 0 (all pairs of the 64 rows, intra-block pairs included) on the handle's stream, as in the one-chain form
+  hipLaunchKernelGGL(jacb_gram2, dim3((unsigned)npairs, (unsigned)nchunks, 1u), dim3(256), 0, chain[0], s.W, N, s.sM, nblk, n2, 0, s.st, s.Gpart, nchunks, s.sG, 0);
+  hipLaunchKernelGGL((jacb_eigen<false, 2>), dim3((unsigned)npairs, 1u), dim3(1024), 0, chain[0],
+                     s.Gpart, nchunks, s.sG, nblk, n2, 0, s.st, s.floor2, s.tol2, s.Qt2[0], s.sQ, s.flags2[0], s.sF, s.offmax, 1, 0);
+  hipLaunchKernelGGL(jacb_apply, dim3((unsigned)npairs, (unsigned)(2 * nchunks), 1u), dim3(256), 0, chain[0],
+                     s.W, s.Ut, N, s.sM, nblk, n2, 0, s.st, s.Qt2[0], s.sQ, s.flags2[0], s.sF, nchunks, 0, 0);
+  ND4_HIP(hipEventRecord(h->ev_aux_a, chain[0]));
+  ND4_HIP(hipStreamWaitEvent(chain[1], h->ev_aux_a, 0));
+  bool prev_full = true;                                   // the previous step applied U itself (nothing deferred)
+  for (int step = 1; step < nsteps; step++) {
+    const bool phase_end = step == hq - 2 || step == hq - 2 + q || step == nsteps - 1;
+    double* Qt = s.Qt2[step & 1];
+    int* flags = s.flags2[step & 1];
+    for (int c = 0; c < 2; c++) {
+      const int p0 = c * q;
+      hipLaunchKernelGGL(jacb_gram2, dim3((unsigned)q, (unsigned)nchunks, 1u), dim3(256), 0, chain[c], s.W, N, s.sM, nblk, n2, step, s.st, s.Gpart, nchunks, s.sG, p0);
+      if (prev_full)
+        hipLaunchKernelGGL(jacb_eigen_p, dim3((unsigned)q, 1u), dim3(576), 0, chain[c],
+                           s.Gpart, nchunks, s.sG, nblk, n2, step, s.st, s.floor2, s.tol2, Qt, s.sQ, flags, s.sF, s.offmax, s.precheck, p0);
+      else
+        hipLaunchKernelGGL(jacb_eigen_pu, dim3((unsigned)(q + q * nchunks), 1u), dim3(576), 0, chain[c],
+                           s.Gpart, nchunks, s.sG, nblk, n2, step, s.st, s.floor2, s.tol2, Qt, s.sQ, flags, s.sF, s.offmax, s.precheck, q,
+                           s.Ut, N, s.sM, s.Qt2[(step - 1) & 1], s.flags2[(step - 1) & 1], p0);
+      if (phase_end)
+        hipLaunchKernelGGL(jacb_apply, dim3((unsigned)q, (unsigned)(2 * nchunks), 1u), dim3(256), 0, chain[c],
+                           s.W, s.Ut, N, s.sM, nblk, n2, step, s.st, Qt, s.sQ, flags, s.sF, nchunks, 0, p0);
+      else
+        jacb_launch_apply_w(s, chain[c], n2, step, q, 1, Qt, flags, p0);
+    }
+    prev_full = phase_end;
+    if (phase_end) {                                       // both chains wait for each other
       ND4_HIP(hipEventRecord(h->ev_aux_a, chain[0]));
       ND4_HIP(hipEventRecord(h->ev_aux_b, chain[1]));
       ND4_HIP(hipStreamWaitEvent(chain[1], h->ev_aux_a, 0));
       ND4_HIP(hipStreamWaitEvent(chain[0], h->ev_aux_b, 0));
-      return 0;
-    };
-    // step 0 (all pairs of the 64 rows, intra-block pairs included) on the handle's stream, as in the one-chain form
-    {
-      hipLaunchKernelGGL(jacb_gram2, dim3((unsigned)npairs, (unsigned)nchunks, 1u), dim3(256), 0, chain[0], W, N, sM, nblk, n2, 0, st, Gpart, nchunks, sG, 0);
-      hipLaunchKernelGGL((jacb_eigen<false, 2>), dim3((unsigned)npairs, 1u), dim3(1024), 0, chain[0],
-                         Gpart, nchunks, sG, nblk, n2, 0, st, floor2, tol2, Qt2[0], sQ, flags2[0], sF, offmax, 1, 0);
-      hipLaunchKernelGGL(jacb_apply, dim3((unsigned)npairs, (unsigned)(2 * nchunks), 1u), dim3(256), 0, chain[0],
-                         W, Ut, N, sM, nblk, n2, 0, st, Qt2[0], sQ, flags2[0], sF, nchunks, 0, 0);
-      ND4_HIP(hipEventRecord(h->ev_aux_a, chain[0]));
-      ND4_HIP(hipStreamWaitEvent(chain[1], h->ev_aux_a, 0));
     }
-    bool prev_full = true;                                   // the previous step applied U itself (nothing deferred)
-    for (int step = 1; step < nsteps; step++) {
-      const bool phase_end = step == hq - 2 || step == hq - 2 + q || step == nsteps - 1;
-      double* Qt = Qt2[step & 1];
-      int* flags = flags2[step & 1];
-      for (int c = 0; c < 2; c++) {
-        const int p0 = c * q;
-        hipLaunchKernelGGL(jacb_gram2, dim3((unsigned)q, (unsigned)nchunks, 1u), dim3(256), 0, chain[c], W, N, sM, nblk, n2, step, st, Gpart, nchunks, sG, p0);
-        static const int pad2_kb = getenv("ND4HIP_JAC_EIGEN_PAD_KB") ? atoi(getenv("ND4HIP_JAC_EIGEN_PAD_KB")) : 0;
-        if (prev_full)
-          hipLaunchKernelGGL(jacb_eigen_p, dim3((unsigned)q, 1u), dim3(576), (size_t)pad2_kb * 1024, chain[c],
-                             Gpart, nchunks, sG, nblk, n2, step, st, floor2, tol2, Qt, sQ, flags, sF, offmax, dense_phase ? 0 : 1, p0);
-        else
-          hipLaunchKernelGGL(jacb_eigen_pu, dim3((unsigned)(q + q * nchunks), 1u), dim3(576), (size_t)pad2_kb * 1024, chain[c],
-                             Gpart, nchunks, sG, nblk, n2, step, st, floor2, tol2, Qt, sQ, flags, sF, offmax, dense_phase ? 0 : 1, q,
-                             Ut, N, sM, Qt2[(step - 1) & 1], flags2[(step - 1) & 1], p0);
-        if (phase_end)
-          hipLaunchKernelGGL(jacb_apply, dim3((unsigned)q, (unsigned)(2 * nchunks), 1u), dim3(256), 0, chain[c],
-                             W, Ut, N, sM, nblk, n2, step, st, Qt, sQ, flags, sF, nchunks, 0, p0);
-        else if (wstrips == 1)
-          hipLaunchKernelGGL(jacb_apply_w<1>, dim3((unsigned)q, (unsigned)(N / 64), 1u), dim3(256), 0, chain[c],
-                             W, N, sM, nblk, n2, step, st, Qt, sQ, flags, sF, p0);
-        else
-          hipLaunchKernelGGL(jacb_apply_w<2>, dim3((unsigned)q, (unsigned)((N + 127) / 128), 1u), dim3(256), 0, chain[c],
-                             W, N, sM, nblk, n2, step, st, Qt, sQ, flags, sF, p0);
-      }
-      prev_full = phase_end;
-      if (phase_end) ND4_TRY(meet());
-    }
-    ND4_HIP(hipGetLastError());
-    return 0;
   }
+  ND4_HIP(hipGetLastError());
+  return 0;
+}
+
+// One chain on the handle's stream: per step Gram -> rotations -> update (or the first two fused). defer: W now, Ut with the next
+// step's rotation kernel (jacb_eigen_pu); the last step of a sweep has no successor and does both.
+int jacb_sweep_one_chain(const JacbSweep& s, const bool defer) {
+  nd4hip_handle* h = s.h;
+  const int N = s.N, batch = s.batch, nblk = s.nblk, nblk2 = (nblk + 1) & ~1, npairs = s.npairs, nchunks = s.nchunks;
+  // fused Gram+eigen pays when the (pair, matrix) workgroups alone fill the chip about once or twice; with many
+  // more of them the separate, fully parallel Gram launch hides its load latency better (measured at N = 512:
+  // batch 64: 83 -> 52 ms fused; batch 128: 94 -> 102; batch 1024: 738 -> 790)
+  const bool fused = N <= 1024 && batch * npairs >= 128 && batch * npairs <= 768;
   for (int step = 0; step < nblk2 - 1; step++) {
     // step 0 of a sweep rotates all pairs of the 64 rows (the pairs inside a block are visited there, once per sweep); the later
     // steps only the 32 x 32 pairs across the two blocks
     const bool cross_only = step > 0;
-    // fused Gram+eigen pays when the (pair, matrix) workgroups alone fill the chip about once or twice; with many
-    // more of them the separate, fully parallel Gram launch hides its load latency better (measured at N = 512:
-    // batch 64: 83 -> 52 ms fused; batch 128: 94 -> 102; batch 1024: 738 -> 790)
-    const bool fused = N <= 1024 && batch * npairs >= 128 && batch * npairs <= 768;
-    double* Qt = Qt2[defer ? (step & 1) : 0];
-    int* flags = flags2[defer ? (step & 1) : 0];
+    double* Qt = s.Qt2[defer ? (step & 1) : 0];
+    int* flags = s.flags2[defer ? (step & 1) : 0];
     const bool last = step == nblk2 - 2;
     if (fused) {
       hipLaunchKernelGGL((jacb_eigen<true, 8>), dim3((unsigned)npairs, (unsigned)batch), dim3(256), 0, h->stream,
-                         W, N, sM, nblk, nblk2, step, st, floor2, tol2, Qt, sQ, flags, sF, offmax, 1, cross_only ? 1 : 0);
+                         s.W, N, s.sM, nblk, nblk2, step, s.st, s.floor2, s.tol2, Qt, s.sQ, flags, s.sF, s.offmax, 1, cross_only ? 1 : 0);
     } else {
-      static const bool gram1 = getenv("ND4HIP_JAC_GRAM1") != nullptr;             // A/B switch: the first form of the Gram kernel
-      if (gram1)
-        hipLaunchKernelGGL(jacb_gram, dim3((unsigned)npairs, (unsigned)nchunks, (unsigned)batch), dim3(256), 0, h->stream,
-                           W, N, sM, nblk, nblk2, step, st, Gpart, nchunks, sG);
-      else
-        hipLaunchKernelGGL(jacb_gram2, dim3((unsigned)npairs, (unsigned)nchunks, (unsigned)batch), dim3(256), 0, h->stream,
-                           W, N, sM, nblk, nblk2, step, st, Gpart, nchunks, sG, 0);
+      hipLaunchKernelGGL(jacb_gram2, dim3((unsigned)npairs, (unsigned)nchunks, (unsigned)batch), dim3(256), 0, h->stream,
+                         s.W, N, s.sM, nblk, nblk2, step, s.st, s.Gpart, nchunks, s.sG, 0);
       if (cross_only && defer) {
-        // dynamic LDS on top of the kernel's ~70 KB: above 80 KB in all a rotation workgroup has its CU to itself (the riding U
-        // workgroups go elsewhere): its rounds are bound by the instruction issue of that one CU
-        static const int pad_kb = getenv("ND4HIP_JAC_EIGEN_PAD_KB") ? atoi(getenv("ND4HIP_JAC_EIGEN_PAD_KB")) : 0;
-        hipLaunchKernelGGL(jacb_eigen_pu, dim3((unsigned)(npairs + npairs * nchunks), (unsigned)batch), dim3(576), (size_t)pad_kb * 1024, h->stream,
-                           Gpart, nchunks, sG, nblk, nblk2, step, st, floor2, tol2, Qt, sQ, flags, sF, offmax, dense_phase ? 0 : 1, npairs,
-                           Ut, N, sM, Qt2[(step - 1) & 1], flags2[(step - 1) & 1], 0);
+        hipLaunchKernelGGL(jacb_eigen_pu, dim3((unsigned)(npairs + npairs * nchunks), (unsigned)batch), dim3(576), 0, h->stream,
+                           s.Gpart, nchunks, s.sG, nblk, nblk2, step, s.st, s.floor2, s.tol2, Qt, s.sQ, flags, s.sF, s.offmax, s.precheck, npairs,
+                           s.Ut, N, s.sM, s.Qt2[(step - 1) & 1], s.flags2[(step - 1) & 1], 0);
       } else if (cross_only) {
         hipLaunchKernelGGL(jacb_eigen_p, dim3((unsigned)npairs, (unsigned)batch), dim3(576), 0, h->stream,
-                           Gpart, nchunks, sG, nblk, nblk2, step, st, floor2, tol2, Qt, sQ, flags, sF, offmax, dense_phase ? 0 : 1, 0);
+                           s.Gpart, nchunks, s.sG, nblk, nblk2, step, s.st, s.floor2, s.tol2, Qt, s.sQ, flags, s.sF, s.offmax, s.precheck, 0);
       } else if ((long)batch * npairs <= 256) {            // few workgroups: latency matters, 16 waves hide more of it
         hipLaunchKernelGGL((jacb_eigen<false, 2>), dim3((unsigned)npairs, (unsigned)batch), dim3(1024), 0, h->stream,
-                           Gpart, nchunks, sG, nblk, nblk2, step, st, floor2, tol2, Qt, sQ, flags, sF, offmax, 1, 0);
+                           s.Gpart, nchunks, s.sG, nblk, nblk2, step, s.st, s.floor2, s.tol2, Qt, s.sQ, flags, s.sF, s.offmax, 1, 0);
       } else {
         hipLaunchKernelGGL((jacb_eigen<false, 8>), dim3((unsigned)npairs, (unsigned)batch), dim3(256), 0, h->stream,
-                           Gpart, nchunks, sG, nblk, nblk2, step, st, floor2, tol2, Qt, sQ, flags, sF, offmax, 1, 0);
+                           s.Gpart, nchunks, s.sG, nblk, nblk2, step, s.st, s.floor2, s.tol2, Qt, s.sQ, flags, s.sF, s.offmax, 1, 0);
       }
     }
-    // deferred: W now, Ut with the next step's rotation kernel; the last step of a sweep has no successor and does both
-    // 2048^2: 58.8 ms with 256-column chunks, 57.5 with 128, 57.2 with 64; 4096^2: 322 / 318 / 328
-    static const int wstrips_env = getenv("ND4HIP_JAC_WSTRIPS") ? atoi(getenv("ND4HIP_JAC_WSTRIPS")) : 0;
-    const int wstrips = wstrips_env ? wstrips_env : (N <= 2048 ? 1 : 2);
-    if (defer && !last && wstrips == 1)
-      hipLaunchKernelGGL(jacb_apply_w<1>, dim3((unsigned)npairs, (unsigned)(N / 64), (unsigned)batch), dim3(256), 0, h->stream,
-                         W, N, sM, nblk, nblk2, step, st, Qt, sQ, flags, sF, 0);
-    else if (defer && !last && wstrips == 2)
-      hipLaunchKernelGGL(jacb_apply_w<2>, dim3((unsigned)npairs, (unsigned)((N + 127) / 128), (unsigned)batch), dim3(256), 0, h->stream,
-                         W, N, sM, nblk, nblk2, step, st, Qt, sQ, flags, sF, 0);
+    if (defer && !last)
+      jacb_launch_apply_w(s, h->stream, nblk2, step, npairs, batch, Qt, flags, 0);
     else
-      hipLaunchKernelGGL(jacb_apply, dim3((unsigned)npairs, (unsigned)((defer && !last ? 1 : 2) * nchunks), (unsigned)batch), dim3(256), 0, h->stream,
-                         W, Ut, N, sM, nblk, nblk2, step, st, Qt, sQ, flags, sF, nchunks, 0, 0);
+      hipLaunchKernelGGL(jacb_apply, dim3((unsigned)npairs, (unsigned)(2 * nchunks), (unsigned)batch), dim3(256), 0, h->stream,
+                         s.W, s.Ut, N, s.sM, nblk, nblk2, step, s.st, Qt, s.sQ, flags, s.sF, nchunks, 0, 0);
   }
   ND4_HIP(hipGetLastError());
   return 0;
+}
+
+}  // namespace
+
+int nd4_jacobi_block_sweep(nd4hip_handle* h, int batch, int N, double* W, double* Ut, JacState* st,
+                           const double* floor2, double tol2, unsigned long long* offmax, double* scratch, bool dense_phase) {
+  JacbSweep s;
+  s.h = h; s.batch = batch; s.N = N; s.W = W; s.Ut = Ut; s.st = st; s.floor2 = floor2; s.tol2 = tol2; s.offmax = offmax;
+  s.precheck = dense_phase ? 0 : 1;
+  s.nblk = N / BB; s.npairs = ((s.nblk + 1) & ~1) / 2; s.nchunks = (N + CH - 1) / CH;
+  s.sM = (long)N * N;
+  s.sG = (long)s.npairs * s.nchunks * PB * PB; s.sQ = (long)s.npairs * PB * PB;
+  s.sF = ((s.npairs + 1) / 2 + 1) * 2;
+  s.Gpart = scratch;
+  s.Qt2[0] = s.Gpart + (size_t)batch * s.sG;
+  s.flags2[0] = reinterpret_cast<int*>(s.Qt2[0] + (size_t)batch * s.sQ);
+  s.Qt2[1] = s.Qt2[0] + (size_t)batch * s.sQ + (size_t)batch * (s.sF / 2);
+  s.flags2[1] = reinterpret_cast<int*>(s.Qt2[1] + (size_t)batch * s.sQ);
+  s.wstrips = N <= 2048 ? 1 : 2;
+  const bool defer = (long)batch * s.npairs <= 64 && N >= 512;                     // see jacb_eigen_pu
+  // Two chains, measured: 4096^2 317 -> 268 ms; 2048^2 57.5 -> 57.3 and 1024^2 22.6 -> 23.4 ms: there each of the three kernels of a step
+  // is ONE wave of workgroups whose duration does not shrink with half the pairs (Gram 12.2 -> 11.5 us, W update 16.6 -> 18.7, and the
+  // rotation kernel slows from 26 to 35 us when it shares the chip), so a chain's step takes as long as the whole step did. Hence
+  // N >= 4096 only (ND4HIP_JAC_TWO_CHAINS=<min N> moves the threshold, 0 switches it off) — and, because the deferred U update needs
+  // batch * npairs <= 64 (`defer`: N <= 4096 with 32-row blocks), in effect for padded N == 4096 alone: 8192^2 keeps one chain.
+  const char* two_e = getenv("ND4HIP_JAC_TWO_CHAINS");      // (read per sweep, not cached: the tests move the threshold)
+  const int two_min_n = two_e ? atoi(two_e) : 4096;
+  if (two_min_n > 0 && defer && batch == 1 && s.nblk % 4 == 0 && N >= two_min_n) return jacb_sweep_two_chains(s);
+  return jacb_sweep_one_chain(s, defer);
 }

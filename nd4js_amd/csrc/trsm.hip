@@ -307,9 +307,9 @@ int nd4_trsm_ld(nd4hip_handle* h, bool upper, bool unit, int64_t batch, int64_t 
   const int M = (int)M64, J = (int)J64, ldT = (int)ldT64;
   if (M == 0 || J == 0 || batch == 0) return 0;
   const long sX = (long)sX64;
-  static const bool cols_off = getenv("ND4HIP_TRSM_BLOCKED") != nullptr;            // A/B switch: block solve + GEMM per 32 rows
-  if (!cols_off && trsm_cols_ok(M, J, batch, T, ldT, sT))
+  if (trsm_cols_ok(M, J, batch, T, ldT, sT))
     return upper ? launch_trsm_cols<true>(h, unit, false, batch, M, J, T, ldT, sT, X, sX) : launch_trsm_cols<false>(h, unit, false, batch, M, J, T, ldT, sT, X, sX);
+  // otherwise: block solve + GEMM per TB rows
   const dim3 grid((unsigned)((J + 255) / 256), (unsigned)batch);
   const int nblocks = (M + TB - 1) / TB;
   for (int bi = 0; bi < nblocks; bi++) {
@@ -341,8 +341,7 @@ int nd4_trsm_t_ex(nd4hip_handle* h, bool unit, int64_t batch, int64_t M64, int64
   const int M = (int)M64, J = (int)J64, ldT = (int)ldT64;
   if (M == 0 || J == 0 || batch == 0) return 0;
   const long sX = (long)sX64;
-  static const bool cols_off = getenv("ND4HIP_TRSM_BLOCKED") != nullptr;
-  if (!cols_off && trsm_cols_ok(M, J, batch, T, ldT, sT)) return launch_trsm_cols<true>(h, unit, true, batch, M, J, T, ldT, sT, X, sX);
+  if (trsm_cols_ok(M, J, batch, T, ldT, sT)) return launch_trsm_cols<true>(h, unit, true, batch, M, J, T, ldT, sT, X, sX);
   const dim3 grid((unsigned)((J + 255) / 256), (unsigned)batch);
   const int nblocks = (M + TB - 1) / TB;
   for (int b = nblocks - 1; b >= 0; b--) {
