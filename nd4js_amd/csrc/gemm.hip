@@ -8,9 +8,13 @@
 //    each wave owns a 64x64 sub-tile = 4x4 accumulators of v_mfma_f64_16x16x4_f64
 //    (16 independent 64-cycle MFMA chains per wave -> the matrix pipe never waits on a dependency).
 //  * operand tiles are staged global -> registers -> LDS, double-buffered, ONE barrier per K-step:
-//    the global loads of step t+1 are issued before the 64 MFMAs of step t and written to the other
-//    LDS buffer after them. Two workgroups per CU (<= 256 VGPR, 72 KiB LDS each) cover each other's
-//    barrier / write phases.
+//    the global loads of step t+2 are issued right after the barrier of step t and written to the other
+//    LDS buffer before the third MFMA group of step t+1. Two workgroups per CU (<= 256 VGPR, 72 KiB LDS
+//    each) cover each other's barrier phases.
+//  * the MFMA fragments live in two register sets: the six LDS reads of group g+1 are issued before the
+//    16 MFMAs of group g, also across the barrier (group 0 of tile t+1 is read behind the barrier and
+//    ahead of the MFMAs of group 3 of tile t), and the K loop is unrolled by two so that the LDS buffer
+//    index is a constant: no MFMA group waits for an LDS round trip, no address is recomputed per step.
 //  * LDS images are chosen so that every ds_read_b64 fragment read is bank-conflict free:
 //      "row" image  [128][17]  (operand stored x-major, k contiguous): lane (x=l&15,k=l>>4) ->
 //                   dword bank (34*x + 2*k) mod 64: 32 lanes x 2 dwords cover all 64 banks once;
@@ -108,6 +112,23 @@ __device__ __forceinline__ void store_kmaj(double* S, const d2 (&r)[4], int t) {
     *reinterpret_cast<d2*>(S + (t >> 4) * LDK + q * 32 + ((t & 15) << 1)) = r[q];
 }
 
+// C tile of one wave: c points at this lane's first element, `rows` / `cols` are the extents left from there (edge tiles)
+template <bool FULL, bool BETA>
+__device__ __forceinline__ void store_c(const d4 (&acc)[4][4], double* __restrict__ c0, long ldc, int rows, int cols, double alpha, double beta) {
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+#pragma unroll
+      for (int r = 0; r < 4; r++)
+        if (FULL || (i * 16 + 4 * r < rows && j * 16 < cols)) {
+          double* c = c0 + (long)(i * 16 + 4 * r) * ldc + j * 16;
+          double v = alpha * acc[i][j][r];
+          if (BETA) v += beta * *c;
+          *c = v;
+        }
+}
+
 // TA: A is stored K x M (operand = transpose of the stored matrix); TB: B is stored N x K.
 // FULL: M, N multiples of 128 and K a multiple of 16 (and VEC): no bounds predicate anywhere.
 template <bool TA, bool TB, bool VEC, bool FULL>
@@ -164,60 +185,72 @@ __global__ __launch_bounds__(256, 2) void dgemm_kernel(GemmArgs g) {
     if (TB) store_row(sb, rb, t);  else store_kmaj(sb, rb, t);
   };
 
+  // this lane's element of fragment (i = 0, group 0) in buffer 0: every fragment read is one of these two bases plus a constant
+  const double* fa = lds + (TA ? fk * LDK + wm + fx : (wm + fx) * LDR + fk);
+  const double* fb = lds + TILE + (TB ? (wn + fx) * LDR + fk : fk * LDK + wn + fx);
+  // the 4 A and 4 B fragments of group kk (k = 4 kk .. 4 kk + 3) of buffer `buf`
+  auto fread = [&](double (&a)[4], double (&b)[4], int buf, int kk) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) a[i] = fa[buf * 2 * TILE + (TA ? kk * 4 * LDK + i * 16 : i * 16 * LDR + kk * 4)];
+#pragma unroll
+    for (int j = 0; j < 4; j++) b[j] = fb[buf * 2 * TILE + (TB ? j * 16 * LDR + kk * 4 : kk * 4 * LDK + j * 16)];
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto mma = [&](const double (&a)[4], const double (&b)[4]) __attribute__((always_inline)) {
+    // (no s_setprio around the cluster: with nothing left to wait for between the groups it measured 0.4 % slower)
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+        acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+
   const int nk = (kend - kbeg + BK - 1) / BK;
   gload(kbeg);
   sstore(0);
+  if (nk > 1) gload(kbeg + BK);                     // in flight during the MFMAs of the first K-step
   __syncthreads();
 
-  for (int kt = 0; kt < nk; kt++) {
-    const int cur = kt & 1;
-    if (kt + 1 < nk) gload(kbeg + (kt + 1) * BK);   // in flight during the MFMAs below
-    const double* sa = lds + cur * 2 * TILE;
-    const double* sb = sa + TILE;
-#pragma unroll
-    for (int kk = 0; kk < BK / 4; kk++) {
-      double a[4], b[4];
-#pragma unroll
-      for (int i = 0; i < 4; i++)
-        a[i] = TA ? sa[(kk * 4 + fk) * LDK + wm + i * 16 + fx] : sa[(wm + i * 16 + fx) * LDR + kk * 4 + fk];
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-        b[j] = TB ? sb[(wn + j * 16 + fx) * LDR + kk * 4 + fk] : sb[(kk * 4 + fk) * LDK + wn + j * 16 + fx];
-      if (kk == BK / 4 - 1 && kt + 1 < nk) {
-        // stage tile kt+1 into the other LDS buffer BEFORE the last 16 MFMAs: the LDS writes drain behind
-        // them, so at the barrier nobody waits for vmcnt / the write pass (the other buffer is idle: its
-        // last reader passed the previous barrier)
-        sstore(cur ^ 1);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-          acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
+  // Two fragment sets: the six LDS reads of a group are issued BEFORE the 16 MFMAs of the group in front of it and waited for
+  // after them (a counted lgkmcnt that has long been met). The pipeline runs across the barrier: K-step kt enters with group 0
+  // of its buffer already in set 0, and leaves with group 0 of the next buffer in flight behind the MFMAs of its own group 3.
+  double a0[4], b0[4], a1[4], b1[4];
+  fread(a0, b0, 0, 0);
+  // one K-step on buffer `cur`. `more`: tile kt + 1 exists; its global loads are in flight since the step before and its LDS
+  // image goes to cur ^ 1. `more2`: tile kt + 2 exists; its global loads are issued as soon as ra / rb are free.
+  auto kstep = [&](int cur, int kt, bool more, bool more2) __attribute__((always_inline)) {
+    fread(a1, b1, cur, 1); mma(a0, b0);
+    fread(a0, b0, cur, 2); mma(a1, b1);
+    fread(a1, b1, cur, 3);
+    // stage tile kt + 1 BEFORE the MFMAs of group 2: the LDS writes and the reads of group 3 drain behind them, so the
+    // lgkmcnt(0) of the barrier is met when the wave gets there (cur ^ 1 is idle: its last reader passed the previous barrier)
+    if (more) { sstore(cur ^ 1); __builtin_amdgcn_sched_barrier(0); }
+    mma(a0, b0);
+    if (more) {
+      // every read of `cur` by this wave has landed (lgkmcnt(0) of the barrier): after it nobody reads `cur` again, and the
+      // image of tile kt + 1 is complete in cur ^ 1
+      __syncthreads();
+      if (more2) gload(kbeg + (kt + 2) * BK);
+      fread(a0, b0, cur ^ 1, 0);
     }
-    __syncthreads();
+    mma(a1, b1);
+  };
+  // unrolled by two: the buffer index is a constant in each half, so the LDS addresses are fa / fb plus immediates. The loop
+  // body always has a successor tile (no join in front of an MFMA group, which would make it wait for the reads issued just
+  // before it); the last one or two K-steps follow it. nk is uniform over the workgroup: every wave meets the same barriers.
+  int kt = 0;
+  for (; kt + 2 < nk; kt += 2) {
+    kstep(0, kt, true, true);
+    kstep(1, kt + 1, true, kt + 3 < nk);
   }
+  if (kt < nk) kstep(0, kt, kt + 1 < nk, false);
+  if (kt + 1 < nk) kstep(1, kt + 1, false, false);
 
   // ---- epilogue: lane holds C[row = (lane>>4) + 4r][col = lane&15] of each 16x16 tile ----
-#pragma unroll
-  for (int i = 0; i < 4; i++)
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      const int col = n0 + wn + j * 16 + fx;
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const int row = m0 + wm + i * 16 + fk + 4 * r;
-        if (FULL || (row < g.M && col < g.N)) {
-          double* c = C + (long)row * ldc + col;
-          double v = alpha * acc[i][j][r];
-          if (beta != 0.0) v += beta * *c;
-          *c = v;
-        }
-      }
-    }
+  double* c0 = C + (long)(m0 + wm + fk) * ldc + n0 + wn + fx;
+  if (beta != 0.0) store_c<FULL, true>(acc, c0, ldc, g.M - (m0 + wm + fk), g.N - (n0 + wn + fx), alpha, beta);
+  else             store_c<FULL, false>(acc, c0, ldc, g.M - (m0 + wm + fk), g.N - (n0 + wn + fx), alpha, beta);
 }
 
 // ---- rank-k update kernel: K <= 32, A not transposed --------------------------------------------------------------
