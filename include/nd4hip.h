@@ -325,6 +325,36 @@ int nd4hip_dslogdettri_batched    (nd4hip_handle* h, int64_t batch, int64_t N, c
 int nd4hip_dnrmfro_dev(nd4hip_handle* h, int64_t n, const double* A, double* out);
 int nd4hip_dnrmfro    (nd4hip_handle* h, int64_t n, const double* A, double* out);
 
+/* ---- schur_eigenvals / schur_eigen / eigen_balance_pre / eigen_balance_post: replace src/la/schur.js:31-370 and
+ * src/la/eigen.js:91-270 (the direct parts of the nonsymmetric eigenproblem; schur_decomp's Francis iteration has no device form)
+ * Complex values are interleaved (re, im) doubles, as in zgemm.
+ * dtreval: T [batch,N,N] quasi-triangular -> Lam [batch,N] complex, the reference's block detection and 2x2 formula, bit for bit.
+ * dtrevc: Q, T [batch,N,N] -> Lam [batch,N] complex and V = Q X [batch,N,N] complex, X the eigenvectors of T by the reference's
+ * back-substitution (N <= 64: one lane per column in its operation order, no contraction; X has its bits) with unit columns, Q X as the
+ * real GEMM on the N x 2N view of X.
+ * dgebal: A [batch,N,N], p >= 1 or +Infinity -> D [batch,N] (powers of two), B = D^-1 A D [batch,N,N], the reference's
+ * Gauss-Seidel sweeps with block-reduced norms. zgebak: D [batch,N], V [batch,N,N] complex -> W = diag(D) V with unit columns.
+ * Where the reference throws, a per-matrix flag word is raised on the device; both forms read it back (one small copy, the call
+ * synchronises) and return ND4HIP_ERR_ARG with the reference's text for the first such matrix: ND4HIP_EV_FLAG_REAL2X2
+ * 'schur_eigenvals(T): T must not contain real eigenvalued 2x2 blocks.' (from dtrevc too, schur.js:308), ND4HIP_EV_FLAG_ASSERT
+ * 'Assertion failed.' (a NaN tolerance or a zero 2x2 determinant), ND4HIP_EV_FLAG_NAN 'NaN encountered.' (dgebal). One deviation: the reference's balancing sweeps have no bound; dgebal stops
+ * after 1024 sweeps (every accepted step shrinks a norm by at least 5 %, so finite input ends long before) and then returns
+ * ND4HIP_ERR_ARG 'nd4hip_dgebal_batched: no fixed point after 1024 sweeps.' (ND4HIP_EV_FLAG_SWEEPS), so that no input can hold
+ * a device. dtrevc at N > 64 is the blocked tier (row blocks of 64, one GEMM per block; within rounding of the reference, not its
+ * bits) and reads the block structure back once per call (it synchronises the stream). */
+#define ND4HIP_EV_FLAG_REAL2X2 1
+#define ND4HIP_EV_FLAG_ASSERT  2
+#define ND4HIP_EV_FLAG_NAN     4
+#define ND4HIP_EV_FLAG_SWEEPS  8
+int nd4hip_dtreval_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* T, double* Lam);
+int nd4hip_dtreval_batched    (nd4hip_handle* h, int64_t batch, int64_t N, const double* T, double* Lam);
+int nd4hip_dtrevc_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* Q, const double* T, double* Lam, double* V);
+int nd4hip_dtrevc_batched    (nd4hip_handle* h, int64_t batch, int64_t N, const double* Q, const double* T, double* Lam, double* V);
+int nd4hip_dgebal_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, double p, const double* A, double* D, double* B);
+int nd4hip_dgebal_batched    (nd4hip_handle* h, int64_t batch, int64_t N, double p, const double* A, double* D, double* B);
+int nd4hip_zgebak_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* D, const double* V, double* W);
+int nd4hip_zgebak_batched    (nd4hip_handle* h, int64_t batch, int64_t N, const double* D, const double* V, double* W);
+
 /* ---- svd_decomp: replaces the output contract of src/la/svd.js:25 (= svd_dc.js:883-932) ----------
  * A [batch,M,N] -> U [batch,M,L], sv [batch,L] (>= 0, descending), V [batch,L,N] (rows = right
  * singular vectors), L = min(M,N); one-sided Jacobi with the reference's Jacobi post-processing

@@ -93,6 +93,14 @@ SIGNATURES = {
     "nd4hip_dslogdettri_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),
     "nd4hip_dnrmfro_dev": (c_int, [ctypes.c_void_p, c_i64, c_dp, c_dp]),
     "nd4hip_dnrmfro": (c_int, [ctypes.c_void_p, c_i64, c_dp, c_dp]),
+    "nd4hip_dtreval_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp]),
+    "nd4hip_dtreval_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp]),
+    "nd4hip_dtrevc_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp]),
+    "nd4hip_dtrevc_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp]),
+    "nd4hip_dgebal_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, ctypes.c_double, c_dp, c_dp, c_dp]),
+    "nd4hip_dgebal_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, ctypes.c_double, c_dp, c_dp, c_dp]),
+    "nd4hip_zgebak_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_zgebak_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),
     "nd4hip_dqp3rank_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, ctypes.c_void_p]),
     "nd4hip_dqp3rank_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, ctypes.c_void_p]),
     "nd4hip_dqp3ls_batched_dev": (c_int, [ctypes.c_void_p] + [c_i64] * 5 + [c_dp, c_i64, c_dp, c_i64, ctypes.c_void_p, c_i64, c_dp, c_i64,

@@ -65,6 +65,10 @@ static int (*p_dslogdet[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const dou
 static int (*p_ddettri[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*);
 static int (*p_dslogdettri[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*, double*);
 static int (*p_dnrmfro[2])(nd4hip_handle*, int64_t, const double*, double*);
+static int (*p_dtreval[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*);
+static int (*p_dtrevc[2])(nd4hip_handle*, int64_t, int64_t, const double*, const double*, double*, double*);
+static int (*p_dgebal[2])(nd4hip_handle*, int64_t, int64_t, double, const double*, double*, double*);
+static int (*p_zgebak[2])(nd4hip_handle*, int64_t, int64_t, const double*, const double*, double*);
 static int (*p_dqp3rank[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, int32_t*);
 static int (*p_dqp3ls[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t,
                           const int32_t*, int64_t, const double*, int64_t, double*, int32_t*);
@@ -136,6 +140,10 @@ static int load_library(void) {
   SYM2(p_ddettri, "nd4hip_ddettri_batched");
   SYM2(p_dslogdettri, "nd4hip_dslogdettri_batched");
   SYM(p_dnrmfro[0], "nd4hip_dnrmfro"); SYM(p_dnrmfro[1], "nd4hip_dnrmfro_dev");
+  SYM2(p_dtreval, "nd4hip_dtreval_batched");
+  SYM2(p_dtrevc, "nd4hip_dtrevc_batched");
+  SYM2(p_dgebal, "nd4hip_dgebal_batched");
+  SYM2(p_zgebak, "nd4hip_zgebak_batched");
   SYM2(p_dqp3rank, "nd4hip_dqp3rank_batched");
   SYM2(p_dsrrqr, "nd4hip_dsrrqr_batched");
   SYM2(p_durv, "nd4hip_durv_batched");
@@ -564,6 +572,52 @@ static napi_value js_dslogdettri(napi_env env, napi_callback_info info) {
   FAIL_IF(p_dslogdettri[A.dev](g_handle, batch, N, (const double*)A.p, (double*)S.p, (double*)L.p));
   return NULL;
 }
+/* dtreval_batched(batch, N, T, Lam) / dtrevc_batched(batch, N, Q, T, Lam, V)   (schur_eigenvals / schur_eigen, schur.js:31-370);
+ * Lam and V are complex: Float64Arrays (or device views) of interleaved (re, im) doubles */
+static napi_value js_dtreval(napi_env env, napi_callback_info info) {
+  ARGS(4, "dtreval_batched");
+  int64_t batch, N; opnd T, L;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || F64(2, T) || F64(3, L)) return NULL;
+  NEED(batch >= 0 && N >= 0 && (size_t)(batch * N * N) <= T.len && (size_t)(2 * batch * N) <= L.len, "dtreval_batched: buffer too small");
+  SAME_SIDE(T.dev == L.dev, "dtreval_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dtreval[T.dev](g_handle, batch, N, (const double*)T.p, (double*)L.p));
+  return NULL;
+}
+static napi_value js_dtrevc(napi_env env, napi_callback_info info) {
+  ARGS(6, "dtrevc_batched");
+  int64_t batch, N; opnd Q, T, L, V;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || F64(2, Q) || F64(3, T) || F64(4, L) || F64(5, V)) return NULL;
+  NEED(batch >= 0 && N >= 0 && (size_t)(batch * N * N) <= Q.len && (size_t)(batch * N * N) <= T.len && (size_t)(2 * batch * N) <= L.len &&
+       (size_t)(2 * batch * N * N) <= V.len, "dtrevc_batched: buffer too small");
+  SAME_SIDE(Q.dev == T.dev && T.dev == L.dev && L.dev == V.dev, "dtrevc_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dtrevc[T.dev](g_handle, batch, N, (const double*)Q.p, (const double*)T.p, (double*)L.p, (double*)V.p));
+  return NULL;
+}
+/* dgebal_batched(batch, N, p, A, D, B) / zgebak_batched(batch, N, D, V, W)   (eigen_balance_pre / _post, eigen.js:91-270); V, W complex */
+static napi_value js_dgebal(napi_env env, napi_callback_info info) {
+  ARGS(6, "dgebal_batched");
+  int64_t batch, N; double p; opnd A, D, B;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || napi_get_value_double(env, a[2], &p) != napi_ok || F64(3, A) || F64(4, D) || F64(5, B)) return NULL;
+  NEED(batch >= 0 && N >= 0 && (size_t)(batch * N * N) <= A.len && (size_t)(batch * N) <= D.len && (size_t)(batch * N * N) <= B.len,
+       "dgebal_batched: buffer too small");
+  SAME_SIDE(A.dev == D.dev && D.dev == B.dev, "dgebal_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dgebal[A.dev](g_handle, batch, N, p, (const double*)A.p, (double*)D.p, (double*)B.p));
+  return NULL;
+}
+static napi_value js_zgebak(napi_env env, napi_callback_info info) {
+  ARGS(5, "zgebak_batched");
+  int64_t batch, N; opnd D, V, W;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || F64(2, D) || F64(3, V) || F64(4, W)) return NULL;
+  NEED(batch >= 0 && N >= 0 && (size_t)(batch * N) <= D.len && (size_t)(2 * batch * N * N) <= V.len && (size_t)(2 * batch * N * N) <= W.len,
+       "zgebak_batched: buffer too small");
+  SAME_SIDE(D.dev == V.dev && V.dev == W.dev, "zgebak_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_zgebak[D.dev](g_handle, batch, N, (const double*)D.p, (const double*)V.p, (double*)W.p));
+  return NULL;
+}
 /* dnrmfro(n, A) -> number   (norm(A) 'fro', norm.js:22-85); a device operand's result comes back as a host number too */
 static napi_value js_dnrmfro(napi_env env, napi_callback_info info) {
   ARGS(2, "dnrmfro");
@@ -810,6 +864,10 @@ static napi_value init(napi_env env, napi_value exports) {
     {"ddettri_batched", NULL, js_ddettri, NULL, NULL, NULL, napi_default, NULL},
     {"dslogdettri_batched", NULL, js_dslogdettri, NULL, NULL, NULL, napi_default, NULL},
     {"dnrmfro", NULL, js_dnrmfro, NULL, NULL, NULL, napi_default, NULL},
+    {"dtreval_batched", NULL, js_dtreval, NULL, NULL, NULL, napi_default, NULL},
+    {"dtrevc_batched", NULL, js_dtrevc, NULL, NULL, NULL, napi_default, NULL},
+    {"dgebal_batched", NULL, js_dgebal, NULL, NULL, NULL, napi_default, NULL},
+    {"zgebak_batched", NULL, js_zgebak, NULL, NULL, NULL, napi_default, NULL},
     {"dqp3rank_batched", NULL, js_dqp3rank, NULL, NULL, NULL, napi_default, NULL},
     {"dsrrqr_batched", NULL, js_dsrrqr, NULL, NULL, NULL, napi_default, NULL},
     {"durv_batched", NULL, js_durv, NULL, NULL, NULL, napi_default, NULL},

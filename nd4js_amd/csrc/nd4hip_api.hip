@@ -442,6 +442,88 @@ extern "C" int nd4hip_dnrmfro_dev(nd4hip_handle* h, int64_t n, const double* A, 
   return nd4_nrmfro(h, n, A, out);
 }
 
+// ---- schur_eigenvals / schur_eigen (schur.js:31-370), eigen_balance_pre / _post (eigen.js:91-270)
+namespace {
+// the reference throws at the first matrix that trips; the kernels raise a flag word per matrix instead: one small read-back
+int ev_verdict(nd4hip_handle* h, const int* flags, int64_t batch) {
+  void* hp = nullptr;
+  ND4_TRY(nd4_pinned(h, sizeof(int) * (size_t)batch, &hp));
+  int* host = static_cast<int*>(hp);
+  ND4_HIP(hipMemcpyAsync(host, flags, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, h->stream));
+  ND4_HIP(hipStreamSynchronize(h->stream));
+  for (int64_t b = 0; b < batch; b++) {
+    ND4_CHECK_ARG(!(host[b] & ND4HIP_EV_FLAG_ASSERT), "Assertion failed.");
+    ND4_CHECK_ARG(!(host[b] & ND4HIP_EV_FLAG_REAL2X2), "schur_eigenvals(T): T must not contain real eigenvalued 2x2 blocks.");
+    ND4_CHECK_ARG(!(host[b] & ND4HIP_EV_FLAG_NAN), "NaN encountered.");
+    ND4_CHECK_ARG(!(host[b] & ND4HIP_EV_FLAG_SWEEPS), "nd4hip_dgebal_batched: no fixed point after 1024 sweeps.");
+  }
+  return 0;
+}
+int ev_flags(nd4hip_handle* h, int64_t batch, int** flags) {
+  void* p = nullptr;
+  ND4_TRY(nd4_ws_alloc(h, sizeof(int) * (size_t)batch, &p));
+  *flags = static_cast<int*>(p);
+  ND4_HIP(hipMemsetAsync(p, 0, sizeof(int) * (size_t)batch, h->stream));
+  return 0;
+}
+constexpr int64_t EV_MAX_N = 32768;
+}  // namespace
+
+extern "C" int nd4hip_dtreval_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* T, double* Lam) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dtreval_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "dtreval_batched", 8.0 * (double)batch * N, 8.0 * (double)batch * 5.0 * N);
+  ND4_CHECK_ARG(batch >= 0 && N >= 0 && N <= EV_MAX_N, "nd4hip_dtreval_batched: extent out of range");
+  if (batch == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(T && Lam, "nd4hip_dtreval_batched: NULL pointer");
+  Nd4WsScope scope(h);
+  int* flags = nullptr;
+  ND4_TRY(ev_flags(h, batch, &flags));
+  ND4_TRY(nd4_trevals(h, batch, N, T, Lam, nullptr, flags));
+  return ev_verdict(h, flags, batch);
+}
+
+extern "C" int nd4hip_dtrevc_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* Q, const double* T, double* Lam, double* V) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dtrevc_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  const double n = (double)N;
+  Nd4Prof prof(h, "dtrevc_batched", (double)batch * (4.0 / 3.0 * n * n * n + 4.0 * n * n * n), 8.0 * (double)batch * (4.0 * n * n + 2.0 * n));
+  ND4_CHECK_ARG(batch >= 0 && N >= 0 && N <= EV_MAX_N, "nd4hip_dtrevc_batched: extent out of range");
+  if (batch == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(Q && T && Lam && V, "nd4hip_dtrevc_batched: NULL pointer");
+  Nd4WsScope scope(h);
+  int* flags = nullptr;
+  ND4_TRY(ev_flags(h, batch, &flags));
+  ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_trevc(h, nb, N, Q + b0 * N * N, T + b0 * N * N, Lam + 2 * b0 * N, V + 2 * b0 * N * N, flags + b0));
+  return ev_verdict(h, flags, batch);
+}
+
+extern "C" int nd4hip_dgebal_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, double p, const double* A, double* D, double* B) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dgebal_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "dgebal_batched", 6.0 * (double)batch * N * N, 8.0 * (double)batch * (4.0 * N * N + N));   // per sweep; two sweeps are typical
+  ND4_CHECK_ARG(p >= 1.0, "nd4hip_dgebal_batched: p must be >= 1");
+  ND4_CHECK_ARG(batch >= 0 && N >= 0 && N <= EV_MAX_N, "nd4hip_dgebal_batched: extent out of range");
+  if (batch == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(A && D && B, "nd4hip_dgebal_batched: NULL pointer");
+  Nd4WsScope scope(h);
+  int* flags = nullptr;
+  ND4_TRY(ev_flags(h, batch, &flags));
+  ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_gebal(h, nb, N, p, A + b0 * N * N, D + b0 * N, B + b0 * N * N, flags + b0));
+  return ev_verdict(h, flags, batch);
+}
+
+extern "C" int nd4hip_zgebak_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* D, const double* V, double* W) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zgebak_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "zgebak_batched", 10.0 * (double)batch * N * N, 8.0 * (double)batch * (8.0 * N * N + N));
+  ND4_CHECK_ARG(batch >= 0 && N >= 0 && N <= EV_MAX_N, "nd4hip_zgebak_batched: extent out of range");
+  if (batch == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(D && V && W && V != W, "nd4hip_zgebak_batched: NULL or aliased pointer");
+  ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_gebak(h, nb, N, D + b0 * N, V + 2 * b0 * N * N, W + 2 * b0 * N * N));
+  return 0;
+}
+
 // rrqr_rank (rrqr.js:398-414): rank [batch] of R [M, N]; -1 marks a matrix whose partial norms are not finite
 extern "C" int nd4hip_dqp3rank_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* R, int32_t* rank) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dqp3rank_batched: NULL handle");

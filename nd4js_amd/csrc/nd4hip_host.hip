@@ -718,6 +718,51 @@ extern "C" int nd4hip_dnrmfro(nd4hip_handle* h, int64_t n, const double* A, doub
   return run_host(h, 1, ops, fn);
 }
 
+// ------------------------------------------------------------------------------------ schur_eigenvals, schur_eigen, eigen_balance_pre / _post
+// the _dev forms read the device flags back and return the reference's message; run_host hands the first failing chunk's code on
+extern "C" int nd4hip_dtreval_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* T, double* Lam) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dtreval_batched: NULL handle");
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dtreval_batched: extent out of range");
+  if (batch == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(T && Lam, "nd4hip_dtreval_batched: NULL pointer");
+  std::vector<Operand> ops{in_op(T, N * N, N * N), out_op(Lam, 2 * N)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_dtreval_batched_dev(hd, nb, N, P(d, 0), P(d, 1)); };
+  return run_host(h, batch, ops, fn);
+}
+
+extern "C" int nd4hip_dtrevc_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* Q, const double* T, double* Lam, double* V) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dtrevc_batched: NULL handle");
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dtrevc_batched: extent out of range");
+  if (batch == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(Q && T && Lam && V, "nd4hip_dtrevc_batched: NULL pointer");
+  std::vector<Operand> ops{in_op(Q, N * N, N * N), in_op(T, N * N, N * N), out_op(Lam, 2 * N), out_op(V, 2 * N * N)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
+    return nd4hip_dtrevc_batched_dev(hd, nb, N, P(d, 0), P(d, 1), P(d, 2), P(d, 3));
+  };
+  return run_host(h, batch, ops, fn);
+}
+
+extern "C" int nd4hip_dgebal_batched(nd4hip_handle* h, int64_t batch, int64_t N, double p, const double* A, double* D, double* B) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dgebal_batched: NULL handle");
+  ND4_CHECK_ARG(p >= 1.0, "nd4hip_dgebal_batched: p must be >= 1");
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dgebal_batched: extent out of range");
+  if (batch == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(A && D && B, "nd4hip_dgebal_batched: NULL pointer");
+  std::vector<Operand> ops{in_op(A, N * N, N * N), out_op(D, N), out_op(B, N * N)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_dgebal_batched_dev(hd, nb, N, p, P(d, 0), P(d, 1), P(d, 2)); };
+  return run_host(h, batch, ops, fn);
+}
+
+extern "C" int nd4hip_zgebak_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* Dv, const double* V, double* W) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zgebak_batched: NULL handle");
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_zgebak_batched: extent out of range");
+  if (batch == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(Dv && V && W, "nd4hip_zgebak_batched: NULL pointer");
+  std::vector<Operand> ops{in_op(Dv, N, N), in_op(V, 2 * N * N, 2 * N * N), out_op(W, 2 * N * N)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_zgebak_batched_dev(hd, nb, N, P(d, 0), P(d, 1), P(d, 2)); };
+  return run_host(h, batch, ops, fn);
+}
+
 // ------------------------------------------------------------------------------------ SVD
 extern "C" int nd4hip_dgesvdj_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A,
                                       double* U, double* sv, double* V, int* sweeps_out, double* offnorm_out) {

@@ -138,6 +138,11 @@ int nd4_urvls(nd4hip_handle* h, int64_t batch, int64_t I, int64_t J, int64_t K, 
 int nd4_dettri(nd4hip_handle* h, bool log_form, int64_t batch, int64_t N, const double* A, int64_t sA, double* D, double* L);
 int nd4_det(nd4hip_handle* h, bool log_form, int64_t batch, int64_t M, int64_t N, const double* A, double* D, double* L, bool force_qr);
 int nd4_nrmfro(nd4hip_handle* h, int64_t n, const double* A, double* out);
+// eigenpairs of a real Schur form and balancing (eigvec.hip); flags [batch]: ND4HIP_EV_FLAG_* per matrix
+int nd4_trevals(nd4hip_handle* h, int64_t batch, int64_t N, const double* T, double* Lam, int* blk, int* flags);
+int nd4_trevc(nd4hip_handle* h, int64_t batch, int64_t N, const double* Q, const double* T, double* Lam, double* V, int* flags);
+int nd4_gebal(nd4hip_handle* h, int64_t batch, int64_t N, double p, const double* A, double* D, double* B, int* flags);
+int nd4_gebak(nd4hip_handle* h, int64_t batch, int64_t N, const double* D, const double* V, double* W);
 int nd4_gesvdj(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A,
                double* U, double* sv, double* V, int* sweeps_out, double* offnorm_out);
 

@@ -543,3 +543,81 @@ def norm(A, ord="fro", axis=None):
     h = _h(A)
     _lib.check(h.lib.nd4hip_dnrmfro_dev(h.ptr, A.numel(), _p(A), _p(out)))
     return float(out.item())
+
+
+def _ev_sq(T, what):
+    _chk(T, "T")
+    if T.dim() < 2 or T.shape[-2] != T.shape[-1]:
+        raise ValueError(what)
+    return tuple(T.shape[:-2]), int(T.shape[-1])
+
+
+def _ev_call(fn, *args):
+    from .la import _arg_error
+    try:
+        _lib.check(fn(*args))
+    except _lib.Nd4HipError as e:
+        raise _arg_error(e)
+
+
+def schur_eigenvals(T):
+    """device-resident schur_eigenvals (schur.js:31-87): complex128 [..., N]. The per-matrix flags are read back (one small
+    copy): a real-eigenvalued 2x2 block raises the reference's error."""
+    lead, N = _ev_sq(T, "T is not square.")
+    L = torch.empty(lead + (N,), dtype=torch.complex128, device=T.device)
+    h = _h(T)
+    _ev_call(h.lib.nd4hip_dtreval_batched_dev, h.ptr, _batch(lead), N, _p(T), _p(L))
+    return L
+
+
+def schur_eigen(Q, T):
+    """device-resident schur_eigen (schur.js:90-370): [eigenvalues [..., N], Q V [..., N, N]], both complex128. Synchronises: the
+    per-matrix flags are read back (the reference's errors), and for N > 64 the block structure is."""
+    _chk(Q, "Q"), _chk(T, "T")
+    if Q.device != T.device:
+        raise ValueError("Q and T must be on the same device")
+    if Q.dim() != T.dim():
+        raise ValueError("Q.ndim != T.ndim.")
+    if tuple(Q.shape) != tuple(T.shape):
+        raise ValueError("Q.shape != T.shape.")
+    lead, N = _ev_sq(T, "Q is not square.")
+    L = torch.empty(lead + (N,), dtype=torch.complex128, device=T.device)
+    V = torch.empty(lead + (N, N), dtype=torch.complex128, device=T.device)
+    h = _h(T)
+    _ev_call(h.lib.nd4hip_dtrevc_batched_dev, h.ptr, _batch(lead), N, _p(Q), _p(T), _p(L), _p(V))
+    return [L, V]
+
+
+def eigen_balance_pre(A, p=2):
+    """device-resident eigen_balance_pre (eigen.js:91-226): [D [..., N], B [..., N, N]]. Synchronises: the per-matrix flags are read
+    back ('NaN encountered.')."""
+    from .la import _js_num
+    p = 2.0 if p is None else float(p)
+    if not p >= 1:
+        raise ValueError("Invalid norm p=%s;" % _js_num(p))
+    lead, N = _ev_sq(A, "A is not square")
+    D = torch.empty(lead + (N,), dtype=torch.float64, device=A.device)
+    B = torch.empty(lead + (N, N), dtype=torch.float64, device=A.device)
+    h = _h(A)
+    _ev_call(h.lib.nd4hip_dgebal_batched_dev, h.ptr, _batch(lead), N, p, _p(A), _p(D), _p(B))
+    return [D, B]
+
+
+def eigen_balance_post(D, V):
+    """device-resident eigen_balance_post (eigen.js:229-270): D [..., N] float64, V [..., N, N] complex128 with equal leading
+    dims -> diag(D) V with unit columns."""
+    _chk(D, "D")
+    V = _chk_mm(V, "V")
+    if V.dim() < 2:
+        raise ValueError("eigen_balance_post(D,V): V.ndim must be at least 2.")
+    if V.shape[-2] != V.shape[-1]:
+        raise ValueError("eigen_balance_post(D,V): V must be square.")
+    if V.dtype != torch.complex128:
+        V = V.to(torch.complex128)
+    if tuple(D.shape) != tuple(V.shape[:-1]):
+        raise ValueError("eigen_balance_post(D,V): D.shape must be V.shape[:-1].")
+    N = int(V.shape[-1])
+    W = torch.empty_like(V)
+    h = _h(V)
+    _ev_call(h.lib.nd4hip_zgebak_batched_dev, h.ptr, _batch(V.shape[:-2]), N, _p(D), _p(V), _p(W))
+    return W

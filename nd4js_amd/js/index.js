@@ -806,9 +806,62 @@ function makeLa(NDA, fallback, SolveError, Complex) {
     return native().dnrmfro(n, isDev(A) ? view(A._buf, 0) : A.data);
   };
 
+  /* ---- schur_eigenvals / schur_eigen (schur.js:31-370), eigen_balance_pre / _post (eigen.js:91-270), csrc/eigvec.hip ---- */
+  const wrapZ = (name, dev, shape, x) => { const Cx = needComplex(name);
+    return dev ? new DeviceNDArray(Int32Array.from(shape), x, Cx) : new NDA(Int32Array.from(shape), complexOver(Cx, x)); };
+  const evFallback = (name, args) => { if (fallback && fallback[name]) return fallback[name](...args); throw new Error(`nd4hip.${name}: dtype is not accelerated.`); };
+  la.schur_eigenvals = function schur_eigenvals(T) {
+    T = asarray(T);
+    const nd_ = T.ndim, N = T.shape[nd_ - 1];
+    if (nd_ < 2 || T.shape[nd_ - 2] !== N) throw new Error('T is not square.');
+    if (!f64Only(T)) return evFallback('schur_eigenvals', [T]);
+    const batch = prod(T.shape, 0, nd_ - 2), dev = isDev(T), temps = [];
+    const L = alloc(dev, 2 * batch * N);
+    try { native().dtreval_batched(batch, N, view(opF64(T, dev, temps), 0), view(L, 0)); } finally { release(temps); }
+    return wrapZ('schur_eigenvals', dev, Array.from(T.shape.subarray(0, nd_ - 1)), L);
+  };
+  la.schur_eigen = function schur_eigen(Q, T) {
+    Q = asarray(Q); T = asarray(T);
+    if (Q.ndim !== T.ndim) throw new Error('Q.ndim != T.ndim.');
+    for (let i = T.ndim; i-- > 0;) if (Q.shape[i] !== T.shape[i]) throw new Error('Q.shape != T.shape.');
+    const nd_ = T.ndim, N = T.shape[nd_ - 1];
+    if (nd_ < 2 || T.shape[nd_ - 2] !== N) throw new Error('Q is not square.');
+    if (!f64Only(Q) || !f64Only(T)) return evFallback('schur_eigen', [Q, T]);
+    const batch = prod(T.shape, 0, nd_ - 2), dev = isDev(Q) || isDev(T), temps = [];
+    const L = alloc(dev, 2 * batch * N), V = alloc(dev, 2 * batch * N * N);
+    try { native().dtrevc_batched(batch, N, view(opF64(Q, dev, temps), 0), view(opF64(T, dev, temps), 0), view(L, 0), view(V, 0)); } finally { release(temps); }
+    return [wrapZ('schur_eigen', dev, Array.from(T.shape.subarray(0, nd_ - 1)), L), wrapZ('schur_eigen', dev, Array.from(T.shape), V)];
+  };
+  la.eigen_balance_pre = function eigen_balance_pre(A, p) {
+    A = asarray(A);
+    if (p == null) p = 2;
+    if (!(p >= 1)) throw new Error(`Invalid norm p=${p};`);
+    const nd_ = A.ndim, N = A.shape[nd_ - 1];
+    if (nd_ < 2 || A.shape[nd_ - 2] !== N) throw new Error('A is not square');
+    if (!f64Only(A)) return evFallback('eigen_balance_pre', [A, p]);
+    const batch = prod(A.shape, 0, nd_ - 2), dev = isDev(A), temps = [];
+    const D = alloc(dev, batch * N), B = alloc(dev, batch * N * N);
+    try { native().dgebal_batched(batch, N, +p, view(opF64(A, dev, temps), 0), view(D, 0), view(B, 0)); } finally { release(temps); }
+    return [wrap(dev, Array.from(A.shape.subarray(0, nd_ - 1)), D), wrap(dev, Array.from(A.shape), B)];
+  };
+  la.eigen_balance_post = function eigen_balance_post(D, V) {
+    D = asarray(D); V = asarray(V);
+    if (V.ndim < 2) throw new Error('eigen_balance_post(D,V): V.ndim must be at least 2.');
+    const nd_ = V.ndim, N = V.shape[nd_ - 1];
+    if (V.shape[nd_ - 2] !== N) throw new Error('eigen_balance_post(D,V): V must be square.');
+    // the accelerated form takes a complex128 V and a float64 D of V's leading shape; anything else is the host module's
+    let same = D.ndim === nd_ - 1;
+    for (let i = 0; same && i < D.ndim; i++) same = D.shape[i] === V.shape[i];
+    if (!same || !f64Only(D) || dtypeOf(V) !== 'complex128') return evFallback('eigen_balance_post', [D, V]);
+    const batch = prod(V.shape, 0, nd_ - 2), dev = isDev(D) || isDev(V), temps = [];
+    const W = alloc(dev, 2 * batch * N * N);
+    try { native().zgebak_batched(batch, N, view(opF64(D, dev, temps), 0), view(opZ(V, dev, temps), 0), view(W, 0)); } finally { release(temps); }
+    return wrapZ('eigen_balance_post', dev, Array.from(V.shape), W);
+  };
+
   // complex128 device arrays are accepted by matmul2 / matmul only: every other function refuses them before it looks at the
   // buffer (which holds 2n doubles, not n float64 entries)
-  const complexOk = new Set(['matmul2', 'matmul', '_chain_plan', 'to_device', 'to_host', 'synchronize', 'profile_enable', 'profile_last']);
+  const complexOk = new Set(['matmul2', 'matmul', 'eigen_balance_post', '_chain_plan', 'to_device', 'to_host', 'synchronize', 'profile_enable', 'profile_last']);
   for (const k of Object.keys(la)) {
     const f = la[k];
     if (typeof f !== 'function' || complexOk.has(k) || f === DeviceNDArray || f === SolveError) continue;   // (classes stay as they are)
@@ -859,7 +912,9 @@ function install(nd, opts) {
                     rrqr_lstsq: nd.la.rrqr_lstsq, rrqr_solve: nd.la.rrqr_solve, solve: nd.la.solve,
                     srrqr_decomp_full: nd.la.srrqr_decomp_full, urv_decomp_full: nd.la.urv_decomp_full, urv_lstsq: nd.la.urv_lstsq,
                     det: nd.la.det, slogdet: nd.la.slogdet, det_tri: nd.la.det_tri, slogdet_tri: nd.la.slogdet_tri,
-                    rank: nd.la.rank, lstsq: nd.la.lstsq, norm: nd.la.norm};
+                    rank: nd.la.rank, lstsq: nd.la.lstsq, norm: nd.la.norm,
+                    schur_eigenvals: nd.la.schur_eigenvals, schur_eigen: nd.la.schur_eigen,
+                    eigen_balance_pre: nd.la.eigen_balance_pre, eigen_balance_post: nd.la.eigen_balance_post};
   const acc = makeLa(nd.NDArray, original, nd.la.SingularMatrixSolveError || SingularMatrixSolveError, (nd.dt && nd.dt.Complex128Array) || null);
   const target = Object.isFrozen(nd.la) || !Object.getOwnPropertyDescriptor(nd.la, 'matmul2').writable ? null : nd.la;
   const patched = target || Object.create(nd.la);

@@ -925,3 +925,85 @@ def norm(A, ord="fro", axis=None, device=None):
     h = _lib.handle(device)
     _lib.check(h.lib.nd4hip_dnrmfro(h.ptr, A.size, _ptr(A), ctypes.byref(out)))
     return out.value
+
+
+# ---------------------------------------------------------------------------------------------------
+# Eigenpairs of a real Schur form and balancing (src/la/schur.js:31-370, eigen.js:91-270), csrc/eigvec.hip
+# ---------------------------------------------------------------------------------------------------
+def _ev_call(fn, *args):
+    try:
+        _lib.check(fn(*args))
+    except _lib.Nd4HipError as e:
+        raise _arg_error(e)
+
+
+def schur_eigenvals(T, device=None):
+    """schur.js:31-87: the eigenvalues of a quasi-triangular T [..., N, N] -> complex128 [..., N], the reference's bits."""
+    T = np.asarray(T)
+    if T.ndim < 2 or T.shape[-2] != T.shape[-1]:
+        raise ValueError("T is not square.")
+    T = _asarray(T, "schur_eigenvals(T)")
+    N = T.shape[-1]
+    L = np.empty(T.shape[:-1], dtype=np.complex128)
+    h = _lib.handle(device)
+    _ev_call(h.lib.nd4hip_dtreval_batched, h.ptr, int(np.prod(T.shape[:-2], dtype=np.int64)), N, _ptr(T), _ptr(L))
+    return L
+
+
+def schur_eigen(Q, T, device=None):
+    """schur.js:90-370: [eigenvalues complex128 [..., N], Q V complex128 [..., N, N]] with V the unit-norm eigenvectors of the
+    quasi-triangular T by the reference's back-substitution."""
+    Q, T = np.asarray(Q), np.asarray(T)
+    if Q.ndim != T.ndim:
+        raise ValueError("Q.ndim != T.ndim.")
+    if Q.shape != T.shape:
+        raise ValueError("Q.shape != T.shape.")
+    if T.ndim < 2 or T.shape[-2] != T.shape[-1]:
+        raise ValueError("Q is not square.")                               # the reference's text for a non-square T (schur.js:150)
+    Q, T = _asarray(Q, "schur_eigen(Q,T)"), _asarray(T, "schur_eigen(Q,T)")
+    N = T.shape[-1]
+    L = np.empty(T.shape[:-1], dtype=np.complex128)
+    V = np.empty(T.shape, dtype=np.complex128)
+    h = _lib.handle(device)
+    _ev_call(h.lib.nd4hip_dtrevc_batched, h.ptr, int(np.prod(T.shape[:-2], dtype=np.int64)), N, _ptr(Q), _ptr(T), _ptr(L), _ptr(V))
+    return [L, V]
+
+
+def eigen_balance_pre(A, p=2, device=None):
+    """eigen.js:91-226: [D [..., N], B [..., N, N]] with B = diag(D)^-1 A diag(D), D powers of two that balance the p-norms of
+    every off-diagonal row and column (p >= 1, or Infinity for the max-norm variant)."""
+    if p is None:
+        p = 2
+    p = float(p)
+    if not p >= 1:
+        raise ValueError("Invalid norm p=%s;" % _js_num(p))
+    A = np.asarray(A)
+    if A.ndim < 2 or A.shape[-2] != A.shape[-1]:
+        raise ValueError("A is not square")
+    A = _asarray(A, "eigen_balance_pre(A,p)")
+    N = A.shape[-1]
+    D, B = np.empty(A.shape[:-1]), np.empty(A.shape)
+    h = _lib.handle(device)
+    _ev_call(h.lib.nd4hip_dgebal_batched, h.ptr, int(np.prod(A.shape[:-2], dtype=np.int64)), N, p, _ptr(A), _ptr(D), _ptr(B))
+    return [D, B]
+
+
+def eigen_balance_post(D, V, device=None):
+    """eigen.js:229-270: diag(D) V with columns of unit 2-norm, complex128 [..., N, N]; D [..., N] real, V complex128 or real."""
+    D, V = np.asarray(D), np.asarray(V)
+    if V.ndim < 2:
+        raise ValueError("eigen_balance_post(D,V): V.ndim must be at least 2.")
+    if V.shape[-2] != V.shape[-1]:
+        raise ValueError("eigen_balance_post(D,V): V must be square.")
+    V = _asarray_mm(V, "eigen_balance_post(D,V)")
+    D = _asarray(D, "eigen_balance_post(D,V)")
+    lead = np.broadcast_shapes(D.shape[:-1], V.shape[:-2])
+    N = V.shape[-1]
+    if D.shape[-1] != N:
+        raise ValueError("Shapes are not broadcast-compatible.")
+    D = np.ascontiguousarray(np.broadcast_to(D, tuple(lead) + (N,)))
+    V = np.ascontiguousarray(np.broadcast_to(V, tuple(lead) + (N, N)).astype(np.complex128))
+    W = np.empty(V.shape, dtype=np.complex128)
+    h = _lib.handle(device)
+    _ev_call(h.lib.nd4hip_zgebak_batched, h.ptr, int(np.prod(lead, dtype=np.int64)), N, _ptr(D), _ptr(V), _ptr(W))
+    return W
