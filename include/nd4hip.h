@@ -127,7 +127,9 @@ int nd4hip_dgetrs_batched    (nd4hip_handle* h, int64_t batch, int64_t N, int64_
 
 /* ---- tril_solve / triu_solve: replace src/la/tri.js:155-290 (kernels :45-95) ----------------------
  * X [batch,M,J] = T^-1 Y with T [batch,M,M] lower (upper = 0) or upper (upper != 0) triangular; only that
- * triangle of T is read; unit_diag != 0 treats the diagonal as ones. strideT / strideY = 0 broadcast. */
+ * triangle of T is read; unit_diag != 0 treats the diagonal as ones: the stored diagonal is not read at all (it may hold
+ * anything, NaN included, e.g. the D of a packed LDL^T or the U diagonal of a packed LU). strideT / strideY = 0 broadcast;
+ * X is dense ([batch,M,J], no stride) and may be Y itself when strideY = M*J. T, Y and everything outside X are never written. */
 int nd4hip_dtrsm_batched_dev(nd4hip_handle* h, int upper, int unit_diag, int64_t batch, int64_t M, int64_t J,
                              const double* T, int64_t strideT, const double* Y, int64_t strideY, double* X);
 int nd4hip_dtrsm_batched    (nd4hip_handle* h, int upper, int unit_diag, int64_t batch, int64_t M, int64_t J,

@@ -12,6 +12,7 @@
 namespace {
 
 constexpr int TB = 32;
+constexpr int TS = 8;                                 // trsm_cols: the diagonal sub-blocks that are inverted explicitly
 
 template <bool UPPER>
 __global__ __launch_bounds__(256) void tri_block_solve(const double* __restrict__ Tm, int M, long sT, double* __restrict__ Xm, int J, long sX,
@@ -62,8 +63,8 @@ __global__ __launch_bounds__(256) void tri_block_solve(const double* __restrict_
 // ---- many right-hand sides: the whole solve in ONE launch, 16 columns per workgroup ----
 // A triangular solve is independent per right-hand-side column, so a workgroup that owns 16 columns needs no other workgroup: its
 // M x 16 slice of X lives in the MFMA accumulator registers of 8 waves for the whole solve (wave w owns the 32-row blocks w, w + 8, ...),
-// and per block b: the owner wave forms X_b = E_bb^-1 B_b with the explicitly inverted 32 x 32 diagonal block (12 MFMAs; tri_inv_blocks
-// computes the inverses by substitution, true divisions, once per call), publishes it through LDS in B-operand layout (the
+// and per block b: the owner wave solves E_bb X_b = B_b with the matrix G_b of tri_inv_blocks (16 MFMAs: the four 8 x 8 diagonal
+// sub-blocks are inverted explicitly, once per call, and coupled by substitution), publishes X_b through LDS in B-operand layout (the
 // accumulator layout of a 16-row tile IS the B-operand layout of its four k-steps), one barrier, and every wave subtracts E[rows, b] X_b
 // from the blocks it owns (A operands straight from global memory; T is read once per workgroup and stays in L2). 2 M^2 16 flop per
 // workgroup on ONE CU's MFMA pipe: 2048 x 2048 rhs in ~0.3 ms against 64 blocks x (block solve + GEMM launch) = 1.4 ms.
@@ -73,39 +74,74 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 // would put the prefetched operands of trsm_cols on the critical path of every step
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// inverse of every 32 x 32 diagonal block of E = op(T): thread j solves E_bb y = e_j. grid (blocks, batch), 32 threads.
+// G_b for every 32 x 32 diagonal block E_bb of E = op(T), with its 8 x 8 sub-blocks E_km: D_k = E_kk^-1 on the block diagonal and
+// -D_k E_km beside it (below it for a lower E, above for an upper), so that x_k = D_k B_k + sum_m G_km x_m over the sub-blocks m
+// solved before k. Thread j computes column j by substitution in each E_kk, true divisions. grid (blocks, batch), 32 threads.
+// Why not the inverse of the whole block: X_b = E_bb^-1 B_b carries eps |E_bb^-1| |B_b| where substitution carries eps |E_bb| |X_b|, and
+// on a triangle like Kahan's, whose 32 x 32 inverse has entries of 1e4, that is 40 to 80 times the componentwise backward error of
+// the substitution; an 8 x 8 inverse of the same triangle stays below 10, and the solve within 4 x.
+// A reciprocal overflows or flushes where the division of the substitution does not (a diagonal near 2^-1040 against a right-hand
+// side of the same scale), so a block whose largest finite diagonal magnitude 2^e lies outside [2^-TRSM_EXP_PLAIN, 2^TRSM_EXP_PLAIN]
+// is taken as 2^-e E_bb (exact) and e is stored beside G_b: the D_k are then 2^e E_kk^-1, the G_km unchanged, and trsm_cols scales
+// B_b by 2^-e, exact as well. Every other block has e = 0 and goes through unchanged; so does a block that the scaling would harm:
+// one whose smallest non-zero diagonal would fall below 2^-TRSM_EXP_SPAN, or whose largest entry would rise above 2^TRSM_EXP_SPAN
+// (a diagonal spanning 2^600 ... 2^-500: the plain reciprocals are all finite, the scaled small pivot would flush to 0).
+constexpr int TRSM_EXP_PLAIN = 500, TRSM_EXP_SPAN = 1000;
 template <bool UPPER>
 __global__ __launch_bounds__(32) void tri_inv_blocks(const double* __restrict__ Tm, int ldT, long sT, int M, int unit, int trans,
-                                                      double* __restrict__ invm, long sInv) {
+                                                      double* __restrict__ invm, long sInv, int* __restrict__ expm, long sExp) {
   __shared__ double s_t[TB][TB + 1];
+  __shared__ double s_d[TB], s_a[TB];
   const double* T = Tm + blockIdx.y * sT;
   double* inv = invm + blockIdx.y * sInv + (long)blockIdx.x * TB * TB;
   const int r0 = blockIdx.x * TB, j = threadIdx.x, nbt = M - r0 < TB ? M - r0 : TB;
+  double amax = 0.0;                                               // largest finite magnitude of column j
   for (int i = 0; i < TB; i++) {
     double v = (i == j) ? 1.0 : 0.0;                               // identity padding beyond M
     if (i < nbt && j < nbt) {
       const bool tri = UPPER ? (j >= i) : (j <= i);
       v = tri ? (trans ? T[(long)(r0 + j) * ldT + r0 + i] : T[(long)(r0 + i) * ldT + r0 + j]) : 0.0;
       if (unit && i == j) v = 1.0;
+      const double m = fabs(v);
+      if (m > amax && m < HUGE_VAL) amax = m;                      // a NaN or an Inf takes no part
     }
     s_t[i][j] = v;
+  }
+  s_d[j] = (j < nbt) ? fabs(s_t[j][j]) : 0.0;
+  s_a[j] = amax;
+  __syncthreads();
+  double dmax = 0.0, dmin = HUGE_VAL, bmax = 0.0;
+  for (int i = 0; i < TB; i++) {
+    const double d = s_d[i];
+    if (d > 0.0 && d < HUGE_VAL) { dmax = d > dmax ? d : dmax; dmin = d < dmin ? d : dmin; }
+    bmax = s_a[i] > bmax ? s_a[i] : bmax;
+  }
+  int e = 0;
+  if (dmax > 0.0) {
+    e = ilogb(dmax);                                               // right for denormals too
+    if (e >= -TRSM_EXP_PLAIN && e <= TRSM_EXP_PLAIN) e = 0;
+    else if (ilogb(dmin) - e < -TRSM_EXP_SPAN || ilogb(bmax) - e > TRSM_EXP_SPAN) e = 0;
+  }
+  if (j == 0) expm[blockIdx.y * sExp + blockIdx.x] = e;
+  if (e != 0) {
+    for (int i = 0; i < TB; i++) s_t[i][j] = ldexp(s_t[i][j], -e);
   }
   __syncthreads();
   double y[TB];
   if (UPPER) {
 #pragma unroll
     for (int i = TB - 1; i >= 0; i--) {
-      double acc = (i == j) ? 1.0 : 0.0;
+      double acc = (i == j) ? 1.0 : ((i / TS) != (j / TS) ? -s_t[i][j] : 0.0);
 #pragma unroll
-      for (int k = TB - 1; k > i; k--) acc -= s_t[i][k] * y[k];
+      for (int k = (i | (TS - 1)); k > i; k--) acc -= s_t[i][k] * y[k];
       y[i] = acc / s_t[i][i];
     }
   } else {
 #pragma unroll
     for (int i = 0; i < TB; i++) {
-      double acc = (i == j) ? 1.0 : 0.0;
+      double acc = (i == j) ? 1.0 : ((i / TS) != (j / TS) ? -s_t[i][j] : 0.0);
 #pragma unroll
-      for (int k = 0; k < i; k++) acc -= s_t[i][k] * y[k];
+      for (int k = (i & ~(TS - 1)); k < i; k++) acc -= s_t[i][k] * y[k];
       y[i] = acc / s_t[i][i];
     }
   }
@@ -113,16 +149,18 @@ __global__ __launch_bounds__(32) void tri_inv_blocks(const double* __restrict__ 
   for (int i = 0; i < TB; i++) inv[i * TB + j] = y[i];
 }
 
-// One panel of <= 1024 rows (32 blocks): 16 waves, wave w owns blocks w and w + 16 (4 accumulator tiles). All A operands a wave needs
-// in a step (<= 2 blocks x 16 values) are requested BEFORE the step's barriers - they do not depend on X_b - so that after the owner
-// has published X_b only LDS reads and MFMAs remain.
+// One panel of <= 1024 rows (32 blocks): 8 waves, wave w owns blocks w, w + 8, w + 16 and w + 24 (8 accumulator tiles). All A operands
+// a wave needs in a step (<= 4 blocks x 16 values) are requested BEFORE the step's barriers - they do not depend on X_b - so that after
+// the owner has published X_b only LDS reads and MFMAs remain.
 template <bool UPPER, bool TRANS>
 __global__ __launch_bounds__(512) void trsm_cols(const double* __restrict__ Tm, int ldT, long sT, int M,
-                                                   const double* __restrict__ invm, long sInv, double* __restrict__ Xm, int J, long sX) {
+                                                   const double* __restrict__ invm, long sInv, const int* __restrict__ expm, long sExp,
+                                                   double* __restrict__ Xm, int J, long sX) {
   __shared__ double s_x[2][2][4][64];                   // [step parity][tile of the block][k-step][lane]: X_b in B-operand layout
-  __shared__ double s_inv[2][TB][TB + 1];               // the inverted diagonal block of this step / being fetched for the next
+  __shared__ double s_inv[2][TB][TB + 1];               // G_b (tri_inv_blocks: D_k and -D_k E_km) of this step's block / being fetched for the next
   const double* T = Tm + blockIdx.y * sT;
   const double* inv = invm + blockIdx.y * sInv;
+  const int* exps = expm + blockIdx.y * sExp;            // per block: 0, or the power of two E_bb was normalised by (tri_inv_blocks)
   double* X = Xm + blockIdx.y * sX;
   const int t = threadIdx.x, lane = t & 63, w = t >> 6, fx = lane & 15, fk = lane >> 4;
   const int c = blockIdx.x * 16 + fx;
@@ -161,7 +199,7 @@ __global__ __launch_bounds__(512) void trsm_cols(const double* __restrict__ Tm, 
         const int row = (w + 8 * q) * TB + 16 * i + fk + 4 * r;
         acc[2 * q + i][r] = (row < M && cok) ? X[(long)row * J + c] : 0.0;
       }
-  {                                                      // the first step's inverted block
+  {                                                      // the first step's G_b
     const int b0 = UPPER ? nblk - 1 : 0;
     s_inv[0][t / TB][t % TB] = inv[(long)b0 * TB * TB + t];
     s_inv[0][(512 + t) / TB][(512 + t) % TB] = inv[(long)b0 * TB * TB + 512 + t];
@@ -170,7 +208,8 @@ __global__ __launch_bounds__(512) void trsm_cols(const double* __restrict__ Tm, 
     const int b = UPPER ? nblk - 1 - step : step;
     const int par = step & 1;
     const int bn = UPPER ? b - 1 : b + 1;
-    const double inx = (step + 1 < nblk) ? inv[(long)bn * TB * TB + t] : 0.0;   // next step's inverted block: in flight during this step
+    const int eb = exps[b];                              // uniform: a scalar load, back before the first barrier
+    const double inx = (step + 1 < nblk) ? inv[(long)bn * TB * TB + t] : 0.0;   // next step's G_b: in flight during this step
     const double iny = (step + 1 < nblk) ? inv[(long)bn * TB * TB + 512 + t] : 0.0;
     double a0[16], a1[16], a2[16], a3[16];
     const bool t0 = todo(0, b), t1 = todo(1, b), t2 = todo(2, b), t3 = todo(3, b);
@@ -179,21 +218,63 @@ __global__ __launch_bounds__(512) void trsm_cols(const double* __restrict__ Tm, 
     if (t2) loadA(a2, w + 16, b);
     if (t3) loadA(a3, w + 24, b);
     lds_barrier();                                       // s_inv[par] (written during the previous step) is visible
-    if (w == (b & 7)) {                                  // ---- owner: X_b = inv(E_bb) B_b
+    if (w == (b & 7)) {                                  // ---- owner: E_bb X_b = B_b
 #pragma unroll
       for (int q = 0; q < 4; q++)
         if (q == (b >> 3)) {
-          const d4 b0 = acc[2 * q], b1 = acc[2 * q + 1];
-          d4 x0 = d4{0.0, 0.0, 0.0, 0.0}, x1 = d4{0.0, 0.0, 0.0, 0.0};
+          d4 b0 = acc[2 * q], b1 = acc[2 * q + 1];
+          if (eb != 0) {                                 // a block of extreme scale: its D_k are those of 2^-eb E_bb
 #pragma unroll
-          for (int kk = 0; kk < 4; kk++) {
-            x0 = __builtin_amdgcn_mfma_f64_16x16x4f64(s_inv[par][fx][kk * 4 + fk], b0[kk], x0, 0, 0, 0);
-            x1 = __builtin_amdgcn_mfma_f64_16x16x4f64(s_inv[par][16 + fx][16 + kk * 4 + fk], b1[kk], x1, 0, 0, 0);
+            for (int kk = 0; kk < 4; kk++) { b0[kk] = ldexp(b0[kk], -eb); b1[kk] = ldexp(b1[kk], -eb); }
           }
+          // G of tri_inv_blocks as A operands: tile i (16 rows) against the 16 columns of tile jt, k-step kk
+          auto G = [&](int i, int jt, int kk) -> double { return s_inv[par][16 * i + fx][16 * jt + kk * 4 + fk]; };
+          const d4 zero = d4{0.0, 0.0, 0.0, 0.0};
+          // accumulator register r of a tile holds its rows fk + 4 r: registers 0, 1 are the first 8 x 8 sub-block of the tile, 2, 3 the
+          // second, and register kk IS k-step kk of a B operand. One MFMA chain per sub-block, over the columns it needs, in the order
+          // of the substitution; what a chain leaves in the rows of the tile's other sub-block is dropped, so no row that is kept
+          // multiplies a value of a row solved after it.
+          d4 x0, x1;
+          if (UPPER) {                                   // sub-blocks 3, 2, 1, 0
+            d4 ta = zero;
 #pragma unroll
-          for (int kk = 0; kk < 4; kk++) {
-            if (UPPER) x0 = __builtin_amdgcn_mfma_f64_16x16x4f64(s_inv[par][fx][16 + kk * 4 + fk], b1[kk], x0, 0, 0, 0);
-            else       x1 = __builtin_amdgcn_mfma_f64_16x16x4f64(s_inv[par][16 + fx][kk * 4 + fk], b0[kk], x1, 0, 0, 0);
+            for (int kk = 2; kk < 4; kk++) ta = __builtin_amdgcn_mfma_f64_16x16x4f64(G(1, 1, kk), b1[kk], ta, 0, 0, 0);
+            const d4 u1 = d4{b1[0], b1[1], ta[2], ta[3]};                        // (B_2, x_3)
+            d4 tb = zero;
+#pragma unroll
+            for (int kk = 0; kk < 4; kk++) tb = __builtin_amdgcn_mfma_f64_16x16x4f64(G(1, 1, kk), u1[kk], tb, 0, 0, 0);
+            x1 = d4{tb[0], tb[1], ta[2], ta[3]};                                 // (x_2, x_3)
+            d4 z = zero;                                                         // rows 0-15: sum_m G_km x_m over m = 2, 3
+#pragma unroll
+            for (int kk = 0; kk < 4; kk++) z = __builtin_amdgcn_mfma_f64_16x16x4f64(G(0, 1, kk), x1[kk], z, 0, 0, 0);
+            d4 tc = z;
+#pragma unroll
+            for (int kk = 2; kk < 4; kk++) tc = __builtin_amdgcn_mfma_f64_16x16x4f64(G(0, 0, kk), b0[kk], tc, 0, 0, 0);
+            const d4 u0 = d4{b0[0], b0[1], tc[2], tc[3]};                        // (B_0, x_1)
+            d4 td = z;
+#pragma unroll
+            for (int kk = 0; kk < 4; kk++) td = __builtin_amdgcn_mfma_f64_16x16x4f64(G(0, 0, kk), u0[kk], td, 0, 0, 0);
+            x0 = d4{td[0], td[1], tc[2], tc[3]};
+          } else {                                       // sub-blocks 0, 1, 2, 3
+            d4 ta = zero;
+#pragma unroll
+            for (int kk = 0; kk < 2; kk++) ta = __builtin_amdgcn_mfma_f64_16x16x4f64(G(0, 0, kk), b0[kk], ta, 0, 0, 0);
+            const d4 u0 = d4{ta[0], ta[1], b0[2], b0[3]};                        // (x_0, B_1)
+            d4 tb = zero;
+#pragma unroll
+            for (int kk = 0; kk < 4; kk++) tb = __builtin_amdgcn_mfma_f64_16x16x4f64(G(0, 0, kk), u0[kk], tb, 0, 0, 0);
+            x0 = d4{ta[0], ta[1], tb[2], tb[3]};
+            d4 z = zero;                                                         // rows 16-31: sum_m G_km x_m over m = 0, 1
+#pragma unroll
+            for (int kk = 0; kk < 4; kk++) z = __builtin_amdgcn_mfma_f64_16x16x4f64(G(1, 0, kk), x0[kk], z, 0, 0, 0);
+            d4 tc = z;
+#pragma unroll
+            for (int kk = 0; kk < 2; kk++) tc = __builtin_amdgcn_mfma_f64_16x16x4f64(G(1, 1, kk), b1[kk], tc, 0, 0, 0);
+            const d4 u1 = d4{tc[0], tc[1], b1[2], b1[3]};                        // (x_2, B_3)
+            d4 td = z;
+#pragma unroll
+            for (int kk = 0; kk < 4; kk++) td = __builtin_amdgcn_mfma_f64_16x16x4f64(G(1, 1, kk), u1[kk], td, 0, 0, 0);
+            x1 = d4{tc[0], tc[1], td[2], td[3]};
           }
           acc[2 * q] = x0; acc[2 * q + 1] = x1;
 #pragma unroll
@@ -257,19 +338,22 @@ int launch_trsm_cols(nd4hip_handle* h, bool unit, bool trans, int64_t batch, int
   Nd4WsScope scope(h);
   void* p = nullptr;
   const long sInv = (long)nblk * TB * TB;
-  ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)sInv * (sT == 0 ? 1 : batch), &p));
+  const size_t nmem = sT == 0 ? 1 : (size_t)batch;        // a shared T: one set of G_b (and exponents) for all members
+  ND4_TRY(nd4_ws_alloc(h, (sizeof(double) * (size_t)sInv + sizeof(int) * (size_t)nblk) * nmem, &p));
   double* inv = static_cast<double*>(p);
-  hipLaunchKernelGGL(tri_inv_blocks<UPPER>, dim3((unsigned)nblk, (unsigned)(sT == 0 ? 1 : batch)), dim3(32), 0, h->stream,
-                     T, ldT, (long)sT, M, unit ? 1 : 0, trans ? 1 : 0, inv, sInv);
+  int* exps = reinterpret_cast<int*>(inv + (size_t)sInv * nmem);
+  const long sExp = sT == 0 ? 0l : (long)nblk;
+  hipLaunchKernelGGL(tri_inv_blocks<UPPER>, dim3((unsigned)nblk, (unsigned)nmem), dim3(32), 0, h->stream,
+                     T, ldT, (long)sT, M, unit ? 1 : 0, trans ? 1 : 0, inv, sInv, exps, (long)nblk);
   const int npan = (M + TC_PANEL - 1) / TC_PANEL;
   for (int pi = 0; pi < npan; pi++) {
     const int pn = UPPER ? npan - 1 - pi : pi;
     const int p0 = pn * TC_PANEL, mp = M - p0 < TC_PANEL ? M - p0 : TC_PANEL;
     const dim3 grid((unsigned)((J + 15) / 16), (unsigned)batch);
     if (trans) hipLaunchKernelGGL((trsm_cols<UPPER, true>), grid, dim3(512), 0, h->stream, T + (long)p0 * ldT + p0, ldT, (long)sT, mp,
-                                  inv + (long)(p0 / TB) * TB * TB, sT == 0 ? 0l : sInv, X + (long)p0 * J, J, sX);
+                                  inv + (long)(p0 / TB) * TB * TB, sT == 0 ? 0l : sInv, exps + p0 / TB, sExp, X + (long)p0 * J, J, sX);
     else       hipLaunchKernelGGL((trsm_cols<UPPER, false>), grid, dim3(512), 0, h->stream, T + (long)p0 * ldT + p0, ldT, (long)sT, mp,
-                                  inv + (long)(p0 / TB) * TB * TB, sT == 0 ? 0l : sInv, X + (long)p0 * J, J, sX);
+                                  inv + (long)(p0 / TB) * TB * TB, sT == 0 ? 0l : sInv, exps + p0 / TB, sExp, X + (long)p0 * J, J, sX);
     ND4_HIP(hipGetLastError());
     // the rows still to be solved lose E[rows, panel] X[panel]
     if (!UPPER && p0 + mp < M) {
