@@ -647,8 +647,13 @@ __global__ __launch_bounds__(NT) void qr_update_blocks(double* __restrict__ Cm, 
 // pivot below HR_PIVOT_THR of its diagonal entry), columns that are exactly zero below the top block (triangular / banded input,
 // where the reference skips rotations: qr.js:60,63) or non-finite data — are flagged by phase B and factorised by
 // qr_panel_row_body in workgroup 0: same result as before, at the old speed.
+// (HR_* and QR_SMALL_WG_BATCH are restated in tests/qr_common.py, which models these decisions: keep the two in step)
 constexpr double HR_PIVOT_THR = 1e-5;
 constexpr double HR_SERIES_MAX = 1e-5;
+// max |Q1^T Q1 - I| after the first pass beyond which the panel is flagged after all. With max |E| <= 1e-2, ||E||_2 <= 0.16 and
+// cond(Q1)^2 <= 1.16 / 0.84 = 1.4: the second pass leaves Q orthonormal to 1.4 times what it leaves for a well-conditioned panel. Beyond
+// (cond(panel) from about 1e7: max |E| ~ eps cond^2) CholeskyQR2 loses orthogonality: 1e4 ... 1e5 eps at cond = 3e11, measured.
+constexpr double HR_PASS1_MAX = 1e-2;
 constexpr int HR_MIN_ROWS = 64;
 
 enum { SEG_NX = 0, SEG_NA, SEG_F };   // SEG_F: partial X, exchange, apply in one go
@@ -1228,8 +1233,8 @@ __global__ __launch_bounds__(512) void qrh_bc(const QrhP P) {
   __syncthreads();
   const int flag = s_flag;                                            // (the same in every row workgroup: same sums in the same order)
   if (g == 0 && t == 0) P.flag[mat] = flag;
-  if (flag) {
-    if (nextupd) apply_next();                                        // (the next launch needs the block whatever happens to this panel)
+  // the classic panel in place of the Gram route (rare path; the decision is the same in every row workgroup)
+  auto fall_back = [&]() {
     if constexpr (R > 0) {
       // the panel's columns were written by all row workgroups of THIS launch: every workgroup pushes its stores out (release:
       // write back the L2) and says so; workgroup 0 waits for all, invalidates (acquire) and runs the classic panel. Rare path.
@@ -1252,6 +1257,10 @@ __global__ __launch_bounds__(512) void qrh_bc(const QrhP P) {
       }
       if (g == 0) qr_panel_row_body<(R > 0 ? R : 1)>(mat, P.Wm, M, ld, P.strideW, P.Vall, P.ldv, P.strideV, P.Tall, P.strideT, P.taus, P.strideTau, j0, NB);
     }
+  };
+  if (flag) {
+    if (nextupd) apply_next();                                        // (the next launch needs the block whatever happens to this panel)
+    fall_back();
     return;
   }
   // ---- Q1 = C R1^-1 (registers), its partial Gram matrix across to the other row workgroups ----
@@ -1265,6 +1274,37 @@ __global__ __launch_bounds__(512) void qrh_bc(const QrhP P) {
 #pragma unroll
     for (int kk = 0; kk < 4; kk++) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[q][kk], bw[kk], acc[q], 0, 0, 0);
   }
+  // One step of iterative refinement, Q1 += (C - Q1 R1) R1^-1. The product with the explicit inverse alone leaves a column-wise
+  // residual of C - Q1 R1 that grows with the panel's condition (eps |C| |R1^-1| |R1|: 40 ... 800 eps on Kahan blocks of condition
+  // 1.8e3 ... 1.4e6, 1e4 eps at 8.7e6, measured); the refined rows solve x R1 = c as backward stably as a substitution does (Skeel).
+  // Tile by tile; both relayouts (accumulator image -> A-operand image) go through the wave's own piece of LDS, as in phase A.
+  {
+    double* sw = s_buf + 8 * 256 + wave * 272;
+    double br[4];
+#pragma unroll
+    for (int kk = 0; kk < 4; kk++) br[kk] = s_R[(4 * fk + kk) * 16 + fx];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      double qa[4];
+#pragma unroll
+      for (int r = 0; r < 4; r++) sw[(fk + 4 * r) * 17 + fx] = acc[q][r];
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int kk = 0; kk < 4; kk++) qa[kk] = sw[fx * 17 + 4 * fk + kk];
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      d4 pr = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int kk = 0; kk < 4; kk++) pr = __builtin_amdgcn_mfma_f64_16x16x4f64(qa[kk], br[kk], pr, 0, 0, 0);   // Q1 R1
+#pragma unroll
+      for (int r = 0; r < 4; r++) sw[(fk + 4 * r) * 17 + fx] = pr[r];
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int kk = 0; kk < 4; kk++) qa[kk] = a[q][kk] - sw[fx * 17 + 4 * fk + kk];                            // C - Q1 R1
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int kk = 0; kk < 4; kk++) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(qa[kk], bw[kk], acc[q], 0, 0, 0);
+    }
+  }
   d4 g0 = d4{0.0, 0.0, 0.0, 0.0}, g1 = g0;
 #pragma unroll
   for (int q = 0; q < 4; q++) {
@@ -1277,11 +1317,11 @@ __global__ __launch_bounds__(512) void qrh_bc(const QrhP P) {
   double* s_R2 = s_Qt + 256; double* s_R2i = s_R2 + 256; double* s_Z = s_R2i + 256; double* s_Rm = s_Z + 256; double* s_K = s_Rm + 256; double* s_S = s_K + 256;
 #pragma unroll
   for (int r = 0; r < 4; r++) s_buf[wave * 256 + (fk + 4 * r) * 16 + fx] = g0[r] + g1[r];
-  if (g == 0 && wave == 0) {                                           // top block of Q1 (tile 1)
-#pragma unroll
+  __syncthreads();
+  if (g == 0 && wave == 0) {                                           // top block of Q1 (tile 1); behind the barrier: s_Qt lies in the
+#pragma unroll                                                         // LDS the other waves' refinement relayouts went through
     for (int r = 0; r < 4; r++) s_Qt[(fk + 4 * r) * 16 + fx] = acc[1][r];
   }
-  __syncthreads();
   const int i = (t & 255) / 16, j = t % 16;
   if (t < 256) {
     double xs = 0.0;
@@ -1311,6 +1351,13 @@ __global__ __launch_bounds__(512) void qrh_bc(const QrhP P) {
   }
   __syncthreads();
   const bool series = __int_as_float(s_emax) <= (float)HR_SERIES_MAX;
+  // the pivot test does not bound the panel's condition number: beyond HR_PASS1_MAX the second pass no longer restores orthogonality.
+  // Nothing of this panel has been stored yet (Q1 lives in registers, the panel's columns in memory are phase A's): the classic panel.
+  if (!(__int_as_float(s_emax) <= (float)HR_PASS1_MAX)) {
+    if (g == 0 && t == 0) P.flag[mat] = 1;
+    fall_back();
+    return;
+  }
   qrh_stamp(P, 4);
   // Q1 from its accumulator image to the A-operand image, one tile at a time through the wave's own piece of LDS (rows padded to 17
   // doubles; the DS operations of one wave execute in order, the waits keep compiler and hardware from overlapping write and read;
@@ -2056,6 +2103,8 @@ static int geqrf_tsqr(nd4hip_handle* h, int batch, int M, int N, const double* A
 }
 
 // ---- the strategies of nd4_geqrf_q_ex, chosen once from the shape ----
+// tests/qr_common.py restates these constants, qr_choose and the drivers below (form(), panel_plan(), panel_entry()): every case of
+// tests/test_gpu_qr_paths.py asserts through them which kernels it runs. Change a constant or a branch here and change it there.
 constexpr int QR_LA_MAX_BATCH = 24;        // look-ahead form up to this many matrices; a batch that fills the chip takes the plain sequence
                                            // with the matrix-core panels (1024 x 512^2 48.6 -> 43.7 ms; 8 matrices 1.97 against 2.53 ms, 32: 2.91 against 2.87)
 constexpr int QR_ROWSPLIT_MAX_BATCH = 8;   // row-split panels (qrh_bc) up to this many matrices; more: one workgroup per panel
@@ -2200,13 +2249,11 @@ static int qr_factor_tall(QrJob& j) {
   for (int P0 = 0; P0 < npanels && M - P0 * NB > 2048; P0 += ppb) {
     const int pend = P0 + ppb < npanels ? P0 + ppb : npanels;
     const int bend = pend < npanels ? pend * NB : N;
-    bool ok = true;
-    for (pnl = P0; pnl < pend; pnl++) {
-      const int j0 = pnl * NB, nb = L - j0 < NB ? L - j0 : NB;
-      if (nb < NB) { ok = false; break; }                   // (a ragged last panel: only when L is not a multiple of 16; handled below)
-      ND4_TRY(j.hr.panel(j0, bend, false, pnl == pend - 1));
-    }
-    if (!ok) break;
+    // a ragged last panel (L no multiple of 16) takes the thread-per-row kernel: its block goes to the one-level part as a whole.
+    // (Stopping at the ragged panel itself left the block's earlier panels factorised, with a reflector pending, and the one-level
+    // part factorised them a second time: 2310 x 280, full.)
+    if (pend == npanels && L % NB != 0) break;
+    for (pnl = P0; pnl < pend; pnl++) ND4_TRY(j.hr.panel(pnl * NB, bend, false, pnl == pend - 1));
     ND4_TRY(j.hr.finish(bend, false, false));                 // the block's last reflector has no column of the block left to reach
     j.first_low = pend;
     if (bend < N) {

@@ -369,6 +369,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void qrb_panel(double* __restrict__ Wm
       emax = (ax <= emax) ? emax : ax;                                 // a NaN wins
     }
     emax = nd4dpp::wave_max(emax);
+    if (lane == 0 && !(emax <= HR_PASS1_MAX)) s_flag = 1;               // too ill-conditioned for the second pass (see HR_PASS1_MAX)
     double r2[4];
     if (emax <= HR_SERIES_MAX) {
       d4 pp = d4{0.0, 0.0, 0.0, 0.0};
@@ -405,6 +406,10 @@ __global__ __launch_bounds__(64 * NWV, 2) void qrb_panel(double* __restrict__ Wm
   }
   __syncthreads();
   stamp(9);
+  if (__builtin_amdgcn_readfirstlane(s_flag)) {                        // (still nothing written: Q1 lives in registers)
+    qrb_fallback<R, NWV>(mat, Wm, M, ld, strideW, Vall, ldv, strideV, Tall, strideT, taus, strideTau, j0);
+    return;
+  }
   // ---- Q = Q1 R2^-1; V = Q - [S; 0] ----
   qrb_trsolve<R>(a, s_R2t, s_rd2, [&](int k) { stamp(17 + k); });
   stamp(10);
