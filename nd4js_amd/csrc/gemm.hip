@@ -15,6 +15,12 @@
 //    16 MFMAs of group g, also across the barrier (group 0 of tile t+1 is read behind the barrier and
 //    ahead of the MFMAs of group 3 of tile t), and the K loop is unrolled by two so that the LDS buffer
 //    index is a constant: no MFMA group waits for an LDS round trip, no address is recomputed per step.
+//  * full tiles (no predicate) whose spans fit 32-bit byte offsets take the BUF instantiations: the global
+//    loads go through buffer resources whose base is the tile of one K-step, so a thread's share of an address is one VGPR
+//    computed once, the row offsets and the K advance are scalar, and the loop body holds no address VALU at all; its LDS
+//    reads, LDS writes and global loads are placed one behind each MFMA of their group (sched_group_barrier), so that a
+//    wave never issues a run of memory instructions while the matrix pipe waits for it. Same barriers, LDS images and
+//    accumulation order as every other instantiation: the same bits.
 //  * LDS images are chosen so that every ds_read_b64 fragment read is bank-conflict free:
 //      "row" image  [128][17]  (operand stored x-major, k contiguous): lane (x=l&15,k=l>>4) ->
 //                   dword bank (34*x + 2*k) mod 64: 32 lanes x 2 dwords cover all 64 banks once;
@@ -112,6 +118,29 @@ __device__ __forceinline__ void store_kmaj(double* S, const d2 (&r)[4], int t) {
     *reinterpret_cast<d2*>(S + (t >> 4) * LDK + q * 32 + ((t & 15) << 1)) = r[q];
 }
 
+// ---- the same loads through a buffer resource (FULL tiles only: no predicate) ------------------------------------------
+// The resource's base is the first element of this workgroup's tile of one K-step, so what is left of an address is a
+// per-thread constant (voffset, a VGPR computed once), wave-uniform row offsets (soffset, SGPRs) and instruction offsets:
+// a K-step advances the 64-bit base with two scalar adds and no vector instruction computes an address inside the K loop.
+// Every byte offset stays below 2^31 (buf_fits() on the host), which is also what num_records says; word 3 is the gfx9
+// raw-buffer descriptor (DATA_FORMAT = 32 bit, no swizzle, no stride).
+typedef unsigned u4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(const double* p) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(p), 0, (int)0x80000000u, 0x00020000);
+}
+// ROW operand: voff = ((t/8) * ld + 2 (t%8)) * 8 bytes, rowoff = 32 * ld * 8 bytes
+__device__ __forceinline__ void bload_row(d2 (&r)[4], __amdgpu_buffer_rsrc_t rs, int voff, int rowoff) {
+#pragma unroll
+  for (int q = 0; q < 4; q++) r[q] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, q * rowoff, 0));
+}
+// KMAJ operand: voff = ((t/16) * ld + 2 (t%16)) * 8 bytes; the four chunks of a row are 256 bytes apart. (They go into soffset
+// too: added to voff they would be four VGPRs, since the compiler cannot show that the sum does not wrap and so keeps it out of
+// the instruction offset.)
+__device__ __forceinline__ void bload_kmaj(d2 (&r)[4], __amdgpu_buffer_rsrc_t rs, int voff) {
+#pragma unroll
+  for (int q = 0; q < 4; q++) r[q] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, q * 256, 0));
+}
+
 // C tile of one wave: c points at this lane's first element, `rows` / `cols` are the extents left from there (edge tiles)
 template <bool FULL, bool BETA>
 __device__ __forceinline__ void store_c(const d4 (&acc)[4][4], double* __restrict__ c0, long ldc, int rows, int cols, double alpha, double beta) {
@@ -131,8 +160,12 @@ __device__ __forceinline__ void store_c(const d4 (&acc)[4][4], double* __restric
 
 // TA: A is stored K x M (operand = transpose of the stored matrix); TB: B is stored N x K.
 // FULL: M, N multiples of 128 and K a multiple of 16 (and VEC): no bounds predicate anywhere.
-template <bool TA, bool TB, bool VEC, bool FULL>
+// BUF (FULL tiles whose spans fit a buffer resource, buf_fits()): the global loads go through buffer resources with scalar
+// addressing, and in the loop body every LDS and global memory instruction sits behind an MFMA of its group (kstep_il).
+// Barriers, LDS images and the order of accumulation are those of the other instantiations: the bits of C are the same.
+template <bool TA, bool TB, bool VEC, bool FULL, bool BUF>
 __global__ __launch_bounds__(256, 2) void dgemm_kernel(GemmArgs g) {
+  static_assert(FULL || !BUF, "the buffer path carries no predicate");
   __shared__ __attribute__((aligned(16))) double lds[4 * TILE];   // [buf][A|B][TILE]
 
   // ---- XCD-aware tile assignment (bijective for any tile count) ----
@@ -149,7 +182,7 @@ __global__ __launch_bounds__(256, 2) void dgemm_kernel(GemmArgs g) {
   const int tm = first_m + (wg % per_group) % gsz;
   const int tn = (wg % per_group) / gsz;
   const int m0 = tm * BM, n0 = tn * BN;
-  if (g.lower && n0 > m0 + BM - 1) return;          // whole workgroup, before any barrier
+  if (g.lower && n0 > m0 + BM - 1) return;          // whole workgroup, before any barrier and any load
 
   const long bz = blockIdx.y;
   const double* __restrict__ A = g.A + bz * g.sA;
@@ -175,11 +208,27 @@ __global__ __launch_bounds__(256, 2) void dgemm_kernel(GemmArgs g) {
     for (int j = 0; j < 4; j++) acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
 
   d2 ra[4], rb[4];
-  auto gload = [&](int k0) {
-    if (TA) load_kmaj<VEC, FULL>(ra, A, g.lda, m0, g.M, k0, kend, t); else load_row<VEC, FULL>(ra, A, g.lda, m0, g.M, k0, kend, t);
-    if (TB) load_row<VEC, FULL>(rb, B, g.ldb, n0, g.N, k0, kend, t);  else load_kmaj<VEC, FULL>(rb, B, g.ldb, n0, g.N, k0, kend, t);
+  // BUF: first element of this workgroup's A / B tile of K-step 0, the distance to the next K-step, and the per-thread and
+  // per-row byte offsets (all below 2^31: buf_fits()). Everything but voffA / voffB is wave-uniform and lives in SGPRs.
+  const double* const pa = A + (TA ? (long)kbeg * g.lda + m0 : (long)m0 * g.lda + kbeg);
+  const double* const pb = B + (TB ? (long)n0 * g.ldb + kbeg : (long)kbeg * g.ldb + n0);
+  const long stepA = TA ? BK * g.lda : BK, stepB = TB ? BK : BK * g.ldb;
+  const int voffA = (int)((TA ? (t >> 4) * g.lda + ((t & 15) << 1) : (t >> 3) * g.lda + ((t & 7) << 1)) * 8);
+  const int voffB = (int)((TB ? (t >> 3) * g.ldb + ((t & 7) << 1) : (t >> 4) * g.ldb + ((t & 15) << 1)) * 8);
+  const int rowoffA = (int)(32 * g.lda * 8), rowoffB = (int)(32 * g.ldb * 8);
+  // global loads of tile j (k = kbeg + j BK ...)
+  auto gload = [&](int j) __attribute__((always_inline)) {
+    if constexpr (BUF) {
+      const __amdgpu_buffer_rsrc_t sa = tile_rsrc(pa + j * stepA), sb = tile_rsrc(pb + j * stepB);
+      if (TA) bload_kmaj(ra, sa, voffA); else bload_row(ra, sa, voffA, rowoffA);
+      if (TB) bload_row(rb, sb, voffB, rowoffB); else bload_kmaj(rb, sb, voffB);
+    } else {
+      const int k0 = kbeg + j * BK;
+      if (TA) load_kmaj<VEC, FULL>(ra, A, g.lda, m0, g.M, k0, kend, t); else load_row<VEC, FULL>(ra, A, g.lda, m0, g.M, k0, kend, t);
+      if (TB) load_row<VEC, FULL>(rb, B, g.ldb, n0, g.N, k0, kend, t);  else load_kmaj<VEC, FULL>(rb, B, g.ldb, n0, g.N, k0, kend, t);
+    }
   };
-  auto sstore = [&](int buf) {
+  auto sstore = [&](int buf) __attribute__((always_inline)) {
     double* sa = lds + buf * 2 * TILE; double* sb = sa + TILE;
     if (TA) store_kmaj(sa, ra, t); else store_row(sa, ra, t);
     if (TB) store_row(sb, rb, t);  else store_kmaj(sb, rb, t);
@@ -188,28 +237,28 @@ __global__ __launch_bounds__(256, 2) void dgemm_kernel(GemmArgs g) {
   // this lane's element of fragment (i = 0, group 0) in buffer 0: every fragment read is one of these two bases plus a constant
   const double* fa = lds + (TA ? fk * LDK + wm + fx : (wm + fx) * LDR + fk);
   const double* fb = lds + TILE + (TB ? (wn + fx) * LDR + fk : fk * LDK + wn + fx);
-  // the 4 A and 4 B fragments of group kk (k = 4 kk .. 4 kk + 3) of buffer `buf`
-  auto fread = [&](double (&a)[4], double (&b)[4], int buf, int kk) __attribute__((always_inline)) {
+  // the 4 A and 4 B fragments of group kk (k = 4 kk .. 4 kk + 3) of buffer `buf`; `fence`: nothing is scheduled across the end
+  auto fread = [&](double (&a)[4], double (&b)[4], int buf, int kk, bool fence = true) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < 4; i++) a[i] = fa[buf * 2 * TILE + (TA ? kk * 4 * LDK + i * 16 : i * 16 * LDR + kk * 4)];
 #pragma unroll
     for (int j = 0; j < 4; j++) b[j] = fb[buf * 2 * TILE + (TB ? j * 16 * LDR + kk * 4 : kk * 4 * LDK + j * 16)];
-    __builtin_amdgcn_sched_barrier(0);
+    if (fence) __builtin_amdgcn_sched_barrier(0);
   };
-  auto mma = [&](const double (&a)[4], const double (&b)[4]) __attribute__((always_inline)) {
+  auto mma = [&](const double (&a)[4], const double (&b)[4], bool fence = true) __attribute__((always_inline)) {
     // (no s_setprio around the cluster: with nothing left to wait for between the groups it measured 0.4 % slower)
 #pragma unroll
     for (int i = 0; i < 4; i++)
 #pragma unroll
       for (int j = 0; j < 4; j++)
         acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
-    __builtin_amdgcn_sched_barrier(0);
+    if (fence) __builtin_amdgcn_sched_barrier(0);
   };
 
   const int nk = (kend - kbeg + BK - 1) / BK;
-  gload(kbeg);
+  gload(0);
   sstore(0);
-  if (nk > 1) gload(kbeg + BK);                     // in flight during the MFMAs of the first K-step
+  if (nk > 1) gload(1);                             // in flight during the MFMAs of the first K-step
   __syncthreads();
 
   // Two fragment sets: the six LDS reads of a group are issued BEFORE the 16 MFMAs of the group in front of it and waited for
@@ -231,21 +280,56 @@ __global__ __launch_bounds__(256, 2) void dgemm_kernel(GemmArgs g) {
       // every read of `cur` by this wave has landed (lgkmcnt(0) of the barrier): after it nobody reads `cur` again, and the
       // image of tile kt + 1 is complete in cur ^ 1
       __syncthreads();
-      if (more2) gload(kbeg + (kt + 2) * BK);
+      if (more2) gload(kt + 2);
       fread(a0, b0, cur ^ 1, 0);
     }
     mma(a1, b1);
   };
+  // The same K-step with both successors (the loop body of the BUF instantiations), scheduled instruction by instruction: each
+  // of the six fragment reads, the eight LDS writes (each behind the s_waitcnt vmcnt of its own load) and the eight global loads
+  // follows one MFMA of its group, reads first, so the wave never leaves the matrix pipe without work for longer than one
+  // instruction; outside the groups only s_waitcnt lgkmcnt(0), s_barrier and scalar address arithmetic are left. The masks of
+  // sched_group_barrier: 0x008 MFMA, 0x100 LDS read, 0x200 LDS write, 0x020 global load.
+#define ND4_PAIR(mask) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(mask, 1, 0);
+#define ND4_PAIR6(mask) ND4_PAIR(mask) ND4_PAIR(mask) ND4_PAIR(mask) ND4_PAIR(mask) ND4_PAIR(mask) ND4_PAIR(mask)
+#define ND4_PAIR8(mask) ND4_PAIR6(mask) ND4_PAIR(mask) ND4_PAIR(mask)
+#define ND4_REST(n) __builtin_amdgcn_sched_group_barrier(0x008, n, 0); __builtin_amdgcn_sched_barrier(0);
+  auto kstep_il = [&](int cur, int kt) __attribute__((always_inline)) {
+    fread(a1, b1, cur, 1, false); mma(a0, b0, false);
+    ND4_PAIR6(0x100) ND4_REST(10)
+    fread(a0, b0, cur, 2, false); mma(a1, b1, false);
+    ND4_PAIR6(0x100) ND4_REST(10)
+    fread(a1, b1, cur, 3, false); sstore(cur ^ 1); mma(a0, b0, false);
+    ND4_PAIR6(0x100) ND4_PAIR8(0x200) ND4_REST(2)
+    __syncthreads();
+    gload(kt + 2); fread(a0, b0, cur ^ 1, 0, false); mma(a1, b1, false);
+    ND4_PAIR6(0x100) ND4_PAIR8(0x020) ND4_REST(2)
+  };
+#undef ND4_REST
+#undef ND4_PAIR8
+#undef ND4_PAIR6
+#undef ND4_PAIR
   // unrolled by two: the buffer index is a constant in each half, so the LDS addresses are fa / fb plus immediates. The loop
   // body always has a successor tile (no join in front of an MFMA group, which would make it wait for the reads issued just
-  // before it); the last one or two K-steps follow it. nk is uniform over the workgroup: every wave meets the same barriers.
+  // before it); the last K-steps follow it. nk is uniform over the workgroup: every wave meets the same barriers.
   int kt = 0;
-  for (; kt + 2 < nk; kt += 2) {
-    kstep(0, kt, true, true);
-    kstep(1, kt + 1, true, kt + 3 < nk);
+  if constexpr (BUF) {
+    // both halves load unconditionally (tiles kt + 2 and kt + 3): one to three K-steps are left behind the loop
+    for (; kt + 3 < nk; kt += 2) {
+      kstep_il(0, kt);
+      kstep_il(1, kt + 1);
+    }
+    kstep(0, kt, kt + 1 < nk, kt + 2 < nk);
+    if (kt + 1 < nk) kstep(1, kt + 1, kt + 2 < nk, false);
+    if (kt + 2 < nk) kstep(0, kt + 2, false, false);
+  } else {
+    for (; kt + 2 < nk; kt += 2) {
+      kstep(0, kt, true, true);
+      kstep(1, kt + 1, true, kt + 3 < nk);
+    }
+    if (kt < nk) kstep(0, kt, kt + 1 < nk, false);
+    if (kt + 1 < nk) kstep(1, kt + 1, false, false);
   }
-  if (kt < nk) kstep(0, kt, kt + 1 < nk, false);
-  if (kt + 1 < nk) kstep(1, kt + 1, false, false);
 
   // ---- epilogue: lane holds C[row = (lane>>4) + 4r][col = lane&15] of each 16x16 tile ----
   double* c0 = C + (long)(m0 + wm + fk) * ldc + n0 + wn + fx;
@@ -365,14 +449,23 @@ __global__ __launch_bounds__(256) void dgemm_splitk_reduce(const double* __restr
 }
 
 
+// Does a 128 x 16 tile of an operand with leading dimension ld span less than 2^31 bytes? A k-major tile is 16 rows of the
+// stored matrix, an x-major one 128 rows. Beyond that the FULL instantiation with 64-bit pointer loads runs.
+bool buf_fits(bool kmajor, long ld) {
+  return ld > 0 && (kmajor ? BK : BM) * ld * 8 < (1l << 31);
+}
+
 template <bool TA, bool TB>
 int launch(nd4hip_handle* h, const GemmArgs& g, bool vec, int64_t batch) {
   const unsigned nsplit = g.kchunk > 0 ? (unsigned)((g.K + g.kchunk - 1) / g.kchunk) : 1u;
   dim3 grid((unsigned)(g.tiles_m * g.tiles_n), (unsigned)batch, nsplit), block(256, 1, 1);
   const bool full = vec && g.M % BM == 0 && g.N % BN == 0 && g.K % BK == 0 && g.K > 0;
-  if (full)     hipLaunchKernelGGL((dgemm_kernel<TA, TB, true, true>), grid, block, 0, h->stream, g);
-  else if (vec) hipLaunchKernelGGL((dgemm_kernel<TA, TB, true, false>), grid, block, 0, h->stream, g);
-  else          hipLaunchKernelGGL((dgemm_kernel<TA, TB, false, false>), grid, block, 0, h->stream, g);
+  // the buffer path addresses one tile of one K-step with 32-bit byte offsets from the tile's first element
+  const bool buf = full && buf_fits(TA, g.lda) && buf_fits(!TB, g.ldb);
+  if (buf)       hipLaunchKernelGGL((dgemm_kernel<TA, TB, true, true, true>), grid, block, 0, h->stream, g);
+  else if (full) hipLaunchKernelGGL((dgemm_kernel<TA, TB, true, true, false>), grid, block, 0, h->stream, g);
+  else if (vec)  hipLaunchKernelGGL((dgemm_kernel<TA, TB, true, false, false>), grid, block, 0, h->stream, g);
+  else           hipLaunchKernelGGL((dgemm_kernel<TA, TB, false, false, false>), grid, block, 0, h->stream, g);
   ND4_HIP(hipGetLastError());
   return 0;
 }
