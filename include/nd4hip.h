@@ -378,7 +378,7 @@ int nd4hip_dgesvdj_batched    (nd4hip_handle* h, int64_t batch, int64_t M, int64
  * orthogonal and Q_panel^T A = [R; 0]. Panels of fewer than 64 rows take the thread-per-row Householder kernel: V explicit unit
  * lower trapezoidal, T upper triangular (compact WY). Everything else is CholeskyQR2 + a compact orthogonal completion:
  * V = Q - [S; 0] with a full top block, T a full 16 x 16 matrix — up to 8 panels as the row-split launch (the rows of a panel over
- * co-resident workgroups), more than 8 as ONE workgroup per panel on the matrix cores (round 4, qr_batched_panel.h), which reads
+ * co-resident workgroups), more than 8 as ONE workgroup per panel on the matrix cores (round 4, qr_batched_panel.hip), which reads
  * every element of A once and writes V once and nothing else: the rows of A below the top 16 are left untouched. A panel the Gram
  * route must not take (nearly dependent columns, a column that is zero below the top block, non-finite data) is factorised by
  * the thread-per-row kernel in the same launch (compact WY form, rows below R zeroed).

@@ -1242,7 +1242,7 @@ static int getrf_impl(nd4hip_handle* h, int64_t batch, int64_t N64, const double
 int nd4_getrf(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* LU, int32_t* P) {
   return getrf_impl(h, batch, N, A, LU, P, 0);
 }
-// Gaussian elimination WITHOUT pivoting (only the signs of the pivots are used: tall-QR sign convention, qr.hip)
+// Gaussian elimination WITHOUT pivoting (only the signs of the pivots are used: tall-QR sign convention, qr_signs.hip)
 int nd4_getrf_nopivot(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* LU, int32_t* P) {
   return getrf_impl(h, batch, N, A, LU, P, 1);
 }

@@ -1,10 +1,9 @@
 // Batched QR panels on the matrix cores: ONE workgroup per panel, no exchange between workgroups (round 4).
-// Included by qr.hip inside its anonymous namespace, after qr_panel_row_body and qr_chain16.h.
 //
 // Replaces, for batches of panels, the thread-per-row Householder kernel qr_panel_row (the inner step of qr_decomp,
 // src/la/qr.js:54-68): that kernel walks 16 dependent column steps of ~530 instructions per wave, and a batch that fills the chip
 // is bound by their issue (21.6 % of the HBM peak for 256 x 2048 rows). Here a panel is factorised the way the row-split panels
-// of one matrix are (qrh_*: CholeskyQR2 + the compact orthogonal completion, see the comment above HR_PIVOT_THR), with the
+// of one matrix are (qrh_*: CholeskyQR2 + the compact orthogonal completion, see the head of qr_rowsplit.hip), with the
 // whole panel in the registers of ONE workgroup:
 //   rows            thread-per-row: thread t keeps R rows of 16 doubles (row j0 + t + 64 NWV i), 16-byte loads / stores of its own
 //                   128-byte row segment (ld, ldv, j0 even); every element is read once and (as V) written once
@@ -20,7 +19,14 @@
 //   (V, T, R)       V = Q - [S; 0], T = K = -S (Q_top - S)^-T (qrc_gj16, in the shadow of the row stores), R = S R2 R1
 // ZERO: rows below the top block of the panel's columns in W are zeroed (the in-matrix panels of the batched QR driver); the
 // panel entry point leaves them alone, so a panel moves its algorithmic 16 m b bytes and nothing else.
+#include "qr_internal.h"
+#include "qr_panel_row_body.h"
+#include "qr_chain16.h"
+#include "dpp.h"
+#include <cstdlib>
+#include <type_traits>
 
+namespace {
 // A staged slot = 64 rows of 128 bytes in a wave's own 8 KB of LDS; the 16-byte piece p of row l sits at piece p ^ qrb_sw(l).
 // sw(l) = (l1, l2, l0 ^ l3) (bits of l) makes every access pattern of the kernel conflict free: row-wise 16-byte writes and reads
 // (lane = row: 8 consecutive rows give 8 different pieces; the 16 lanes of a ds_read_b128 group — {0-3, 12-15, 20-27}, ... — give
@@ -476,4 +482,51 @@ __global__ __launch_bounds__(64 * NWV, 2) void qrb_panel(double* __restrict__ Wm
     for (int k = 0; k < 4; k++) Tall[mat * strideT + (long)(j0 / NB) * NB * NB + lane + 64 * k] = s_K[lane + 64 * k];
   }
   stamp(13);
+}
+
+// Batches of full panels on the matrix cores. ZERO: the rows below the top block are zeroed in W.
+template <bool ZERO>
+void launch_qrb(nd4hip_handle* h, int batch, double* W, int M, int m, long ld, long sW, double* V, long ldv, long sV,
+                double* T, long sT, double* taus, long sTau, int j0, long long* stamps) {
+  const QrPanelShape s = nd4_qr_panel_shape(batch, m);
+  const auto kern = s.NWV == 1 ? qrb_panel<4, 1, ZERO> : s.NWV == 2 ? qrb_panel<4, 2, ZERO> : s.NWV == 4 ? qrb_panel<4, 4, ZERO>
+                  : s.R == 1 ? qrb_panel<1, 8, ZERO> : s.R == 2 ? qrb_panel<2, 8, ZERO> : qrb_panel<4, 8, ZERO>;
+  hipLaunchKernelGGL(kern, dim3(batch), dim3(64 * s.NWV), 0, h->stream, W, M, ld, sW, V, ldv, sV, T, sT, taus, sTau, j0, stamps);
+}
+
+}  // namespace
+
+void nd4_qr_panel_mfma(nd4hip_handle* h, int batch, double* W, int M, int m, long ld, long sW, double* V, long ldv, long sV,
+                       double* T, long sT, double* taus, long sTau, int j0) {
+  launch_qrb<true>(h, batch, W, M, m, ld, sW, V, ldv, sV, T, sT, taus, sTau, j0, nullptr);
+}
+// The panel entry point's batch of panels (nd4_geqr2_panel: A [batch, M, 16] in place, nothing zeroed), with its debug switches:
+// ND4HIP_QRB_STAMPS prints workgroup 0's phase times, ND4HIP_QRB_COPY_ONLY runs the kernel's data movement alone.
+int nd4_qr_panel_mfma_alone(nd4hip_handle* h, int batch, int M, double* A, double* V, double* T, double* taus) {
+  const long sW = (long)M * NB;
+  static const bool stamps_on = [] { const char* e = getenv("ND4HIP_QRB_STAMPS"); return e && *e && *e != '0'; }();
+  long long* stamps = nullptr;
+  if (stamps_on) { static long long* dbuf = nullptr; if (!dbuf) ND4_HIP(hipMalloc(&dbuf, 512)); stamps = dbuf; }
+  static const bool copy_only = [] { const char* e = getenv("ND4HIP_QRB_COPY_ONLY"); return e && *e && *e != '0'; }();
+  static const int copy_mode = [] { const char* e = getenv("ND4HIP_QRB_COPY_ONLY"); return e ? atoi(e) : 0; }();
+  if (copy_only) {                                                   // debug: the kernel's data movement alone (see qrb_copy_only)
+    const QrPanelShape s = nd4_qr_panel_shape(QR_SMALL_WG_BATCH, M);   // the few-wave shapes <4, NWV> whatever the batch
+    const auto kern = s.NWV == 1 ? qrb_copy_only<4, 1> : s.NWV == 2 ? qrb_copy_only<4, 2> : s.NWV == 4 ? qrb_copy_only<4, 4> : qrb_copy_only<4, 8>;
+    hipLaunchKernelGGL(kern, dim3(batch), dim3(64 * s.NWV), 0, h->stream, A, M, (long)NB, sW, V, (long)NB, sW, 0, copy_mode);
+    ND4_HIP(hipGetLastError());
+    return 0;
+  }
+  launch_qrb<false>(h, batch, A, M, M, NB, sW, V, NB, sW, T, NB * NB, taus, NB, 0, stamps);
+  ND4_HIP(hipGetLastError());
+  if (stamps) {
+    long long hs[64];
+    static const char* names[13] = {"load+gram", "wait all", "chol", "barrier", "q1", "gram2", "wait all", "series", "barrier", "q", "gj", "stores", "T"};
+    ND4_HIP(hipStreamSynchronize(h->stream));
+    ND4_HIP(hipMemcpy(hs, stamps, 512, hipMemcpyDeviceToHost));
+    fprintf(stderr, "qrb stamps %d x %d rows (us | shader cycles; workgroup 0):", batch, M);
+    for (int k = 0; k < 13; k++) fprintf(stderr, " %s %.2f|%lld", names[k], (hs[2 * k + 2] - hs[2 * k]) * 0.01, hs[2 * k + 3] - hs[2 * k + 1]);
+    fprintf(stderr, " total %.2f|%lld; columns 4/8/12 of q1 at %lld %lld %lld of q at %lld %lld %lld\n", (hs[26] - hs[0]) * 0.01, hs[27] - hs[1],
+            hs[29] - hs[9], hs[31] - hs[9], hs[33] - hs[9], hs[35] - hs[19], hs[37] - hs[19], hs[39] - hs[19]);
+  }
+  return 0;
 }

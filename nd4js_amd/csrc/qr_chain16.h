@@ -1,5 +1,5 @@
 // The 16 x 16 chains of a QR panel on ONE wave, with the matrix core doing the eliminations (round 4).
-// Included by qr.hip (anonymous namespace).
+// Used by the row-split panels (qr_rowsplit.hip) and the one-workgroup matrix-core panels (qr_batched_panel.hip).
 //
 // A 16 x 16 matrix lives in the accumulator image of an fp64 MFMA 16x16x4: register r of lane (fx, fk) (fx = lane & 15,
 // fk = lane >> 4) is M[4 r + fk][fx]. Row k of M is register k / 4 at the 16 lanes fk == k % 4 — exactly where k-slot k % 4 of a B
@@ -10,6 +10,13 @@
 // of a 30-40 us panel; a step is now the pivot's readlane, its reciprocal (square root), a few selects and one to three MFMAs.
 // (A 4 x 4-blocked Cholesky with the diagonal block factorised redundantly by all lanes was measured first: 2.5 us, bound by the
 // ~110 wave-uniform instructions per block.)
+#pragma once
+#include "qr_internal.h"
+#include "dpp.h"
+#include <cfloat>
+#include <utility>
+
+namespace {
 
 __device__ __forceinline__ double qrc_rl(double v, int lane) { return nd4dpp::rl_d(v, lane); }
 
@@ -224,3 +231,5 @@ __device__ __forceinline__ void qrc_zr16(const double* __restrict__ s_Qt, const 
   qrc_put(s_Rm, rm, fx, fk);
   QRC_LDS_SYNC();
 }
+
+}  // namespace

@@ -1,8 +1,8 @@
 """Helpers of the QR path tests (test_qr_ref_host.py, test_gpu_qr_paths.py); nothing here needs a GPU to import.
 
   form, panel_plan      Python twins of qr_choose and of the drivers of qr.hip (qr_factor_lookahead, qr_factor_tall, qr_block_panels,
-                        qr_factor_batched, qr_factor_blocked, qr_rows_lookahead, launch_panel_mfma, launch_panel_rows, qr_form_q,
-                        geqrf_tsqr): which kernel factorises every 16-column panel of a call, the outer blocks, how Q is formed.
+                        qr_factor_batched, qr_factor_blocked, qr_rows_lookahead, qr_form_q, geqrf_tsqr) and of the panel units'
+                        launchers (nd4_qr_panel_shape in qr_house.hip, QrhHost::panel in qr_rowsplit.hip): which kernel factorises every 16-column panel of a call, the outer blocks, how Q is formed.
                         Every GPU case asserts through them that it takes the path it is there for.
   panel_entry           the same for nd4hip_dgeqr2_panel_batched_dev (nd4_geqr2_panel)
   dense, graded, cond, kahan, adv, zero_columns, triangular, one_nan (make_input), bare_panel
@@ -20,7 +20,7 @@ from nd4js_amd import rng
 
 EPS = 2.0 ** -52
 
-# ---- the constants of the dispatch, each with its place in nd4js_amd/csrc/qr.hip ------------------------------------------------
+# ---- the constants of the dispatch (nd4js_amd/csrc/qr_internal.h where no file is named) ------------------------------------------------
 NB = 16                        # panel width
 HR_PIVOT_THR = 1e-5            # a Cholesky pivot below this fraction of its diagonal entry flags the panel
 HR_SERIES_MAX = 1e-5           # max |Q1^T Q1 - I| up to which R2 comes from the series, beyond it from the elimination chain
@@ -68,7 +68,7 @@ def _rsel(m):
 
 
 def _few(batch, m):
-    """<R,NWV> of launch_panel_mfma / launch_panel_rows"""
+    """<R,NWV> of nd4_qr_panel_shape (qr_house.hip): qrb_panel and qr_panel_row share it"""
     if batch >= QR_SMALL_WG_BATCH and m <= 1024:
         return "<4,%d>" % (1 if m <= 256 else 2 if m <= 512 else 4)
     return "<%d,8>" % _rsel(m)
@@ -121,7 +121,7 @@ def panel_plan(batch, M, N, full):
                     rows), qrb_panel<R,NWV>, qr_panel_row<R,NWV>, qr_panel_row_la<R>, qr_panel_part<4,8> | <8,4>, qr_panel<1,false>
       outer         (columns per outer block, the last one ragged) of the two-level forms, None for one level
       coupling      the two-half wy_t_small coupling runs (batched form, a block wider than 64 columns)
-      far           a block's reflectors reach columns right of the block at once (block_update / wy_block_update)
+      far           a block's reflectors reach columns right of the block at once (nd4_qr_block_update / wy_block_update)
       t_assemble    qr_t_assemble joins the parts of a panel factorised in halves or quarters
       update_blocks the last thread-per-row reflector reaches a wide tail through qr_update_blocks
       qt            Q^T is accumulated in the shadow of the panels

@@ -1,4 +1,4 @@
-"""Every driver form and panel kernel of qr.hip through the device entry points (the batch reaches qr_choose as it is), against the
+"""Every driver form of qr.hip and every panel kernel of its units (qr_house.hip, qr_rowsplit.hip, qr_batched_panel.hip) through the device entry points (the batch reaches qr_choose as it is), against the
 oracle on the same inputs. Every case asserts through qr_common.panel_plan(), the Python twin of the drivers, that it takes the path
 it names (qr_common.CASES lists case -> kernels -> driver branch; test_qr_ref_host.py pins the twins on the CPU).
 

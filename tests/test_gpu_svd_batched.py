@@ -454,7 +454,7 @@ def test_rank_and_lstsq_at_extreme_scales(scale):
 @pytest.mark.parametrize("M,N", [(200, 48), (96, 80), (600, 272), (272, 600), (1500, 700)])
 def test_input_with_identical_columns(M, N):
     """identical columns: each Householder step leaves the next column at eps times the previous one, so after ~10 columns the sums
-    of squares of the QR front end are subnormal (qr.hip: QR_SIGMA_MIN). U / V must stay orthogonal, alone and batched"""
+    of squares of the QR front end are subnormal (qr_internal.h: QR_SIGMA_MIN). U / V must stay orthogonal, alone and batched"""
     from nd4js_amd import la
     a = np.ones((3, M, N))
     a[1] *= -0.5

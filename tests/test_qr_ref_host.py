@@ -1,4 +1,4 @@
-"""CPU side of the QR path tests: the dispatch twins of qr_common.py pinned on both sides of every boundary of qr.hip's drivers, the
+"""CPU side of the QR path tests: the dispatch twins of qr_common.py pinned on both sides of every boundary of the QR drivers (qr.hip) and panel launchers (qr_house.hip, qr_rowsplit.hip, qr_batched_panel.hip), the
 structured input families proved to do to the oracle and to the panels what they claim, and the oracle's invariance under
 power-of-two column scaling (what lets test_gpu_qr_paths.py demand bit-identical factors for `graded`). No GPU."""
 import numpy as np
