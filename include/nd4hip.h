@@ -328,7 +328,7 @@ int nd4hip_dnrmfro_dev(nd4hip_handle* h, int64_t n, const double* A, double* out
 int nd4hip_dnrmfro    (nd4hip_handle* h, int64_t n, const double* A, double* out);
 
 /* ---- schur_eigenvals / schur_eigen / eigen_balance_pre / eigen_balance_post: replace src/la/schur.js:31-370 and
- * src/la/eigen.js:91-270 (the direct parts of the nonsymmetric eigenproblem; schur_decomp's Francis iteration has no device form)
+ * src/la/eigen.js:91-270 (the direct parts of the nonsymmetric eigenproblem; schur_decomp's Francis iteration follows below: dhseqr)
  * Complex values are interleaved (re, im) doubles, as in zgemm.
  * dtreval: T [batch,N,N] quasi-triangular -> Lam [batch,N] complex, the reference's block detection and 2x2 formula, bit for bit.
  * dtrevc: Q, T [batch,N,N] -> Lam [batch,N] complex and V = Q X [batch,N,N] complex, X the eigenvectors of T by the reference's
@@ -356,6 +356,36 @@ int nd4hip_dgebal_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, double
 int nd4hip_dgebal_batched    (nd4hip_handle* h, int64_t batch, int64_t N, double p, const double* A, double* D, double* B);
 int nd4hip_zgebak_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* D, const double* V, double* W);
 int nd4hip_zgebak_batched    (nd4hip_handle* h, int64_t batch, int64_t N, const double* D, const double* V, double* W);
+
+/* ---- schur_decomp / eigen / eigenvals: replace src/la/schur.js:372-683 and src/la/eigen.js:33-88 --------------------------
+ * dhseqr: a Hessenberg decomposition (U, H) [batch,N,N] -> the real Schur decomposition (Q, T) of U H U^T by the reference's
+ * Francis iteration schur_qrfrancis_inplace (implicit double shift, nested calls on deflated windows, the exceptional shift
+ * drawn from AleaRNG('nd.la.schur_qrfrancis_inplace'), the final pass over real-eigenvalued 2x2 blocks), bit for bit: every
+ * decision and every element is computed in the reference's operation order (csrc/schur.hip). One workgroup per matrix, no
+ * exchange between workgroups; N <= 2048. Q may be U and T may be H. The _ex forms take the tier: ND4HIP_SCHUR_TIER_AUTO,
+ * _LDS (H, Q^T and the nested q in LDS: N <= 65) or _GLOBAL (in global memory, any N); both give the same bits.
+ * dgees: A -> (Q, T) = dhseqr(dgehrd(A)), schur_decomp. The device Hessenberg reduction is within rounding of the reference's,
+ * not its bits, so neither is T.
+ * dgeev: A -> Lam [batch,N] complex and, unless V is NULL, V [batch,N,N] complex: eigen(A) / eigenvals(A) = dgebal with p = 2,
+ * dgees, dtrevc (dtreval if V is NULL), zgebak, all on the device. zgebak scales by the complex (D_i, 0) where eigen.js:59
+ * scales by the real D_i: the same values up to the sign of a zero.
+ * sweeps_out is a HOST pointer (may be NULL): the most sweeps any one francis_qr call took, over the batch. All forms
+ * synchronise the stream (the flag words are read back). One deviation: the reference gives up after 1e9 stuck iterations per
+ * eigenvalue, which is no bound on a shared device; here a francis_qr call on a window of size n stops after 30 max(10, n)
+ * sweeps (LAPACK's dlahqr budget; the fixtures stay below a tenth of it), raises ND4HIP_EV_FLAG_NOCONV and the call returns
+ * ND4HIP_ERR_NOCONV 'nd4hip_dhseqr_batched: no convergence after 30 max(10, n) sweeps of one francis_qr call.' */
+#define ND4HIP_EV_FLAG_NOCONV 16
+#define ND4HIP_SCHUR_TIER_AUTO   0
+#define ND4HIP_SCHUR_TIER_LDS    1
+#define ND4HIP_SCHUR_TIER_GLOBAL 2
+int nd4hip_dhseqr_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* U, const double* H, double* Q, double* T, int* sweeps_out);
+int nd4hip_dhseqr_batched    (nd4hip_handle* h, int64_t batch, int64_t N, const double* U, const double* H, double* Q, double* T, int* sweeps_out);
+int nd4hip_dhseqr_batched_ex_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* U, const double* H, double* Q, double* T, int* sweeps_out, int tier);
+int nd4hip_dhseqr_batched_ex    (nd4hip_handle* h, int64_t batch, int64_t N, const double* U, const double* H, double* Q, double* T, int* sweeps_out, int tier);
+int nd4hip_dgees_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* Q, double* T, int* sweeps_out);
+int nd4hip_dgees_batched    (nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* Q, double* T, int* sweeps_out);
+int nd4hip_dgeev_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* Lam, double* V);
+int nd4hip_dgeev_batched    (nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* Lam, double* V);
 
 /* ---- svd_decomp: replaces the output contract of src/la/svd.js:25 (= svd_dc.js:883-932) ----------
  * A [batch,M,N] -> U [batch,M,L], sv [batch,L] (>= 0, descending), V [batch,L,N] (rows = right

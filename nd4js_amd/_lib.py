@@ -101,6 +101,14 @@ SIGNATURES = {
     "nd4hip_dgebal_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, ctypes.c_double, c_dp, c_dp, c_dp]),
     "nd4hip_zgebak_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),
     "nd4hip_zgebak_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_dhseqr_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, ctypes.POINTER(c_int)]),
+    "nd4hip_dhseqr_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, ctypes.POINTER(c_int)]),
+    "nd4hip_dhseqr_batched_ex_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, ctypes.POINTER(c_int), c_int]),
+    "nd4hip_dhseqr_batched_ex": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, ctypes.POINTER(c_int), c_int]),
+    "nd4hip_dgees_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp, ctypes.POINTER(c_int)]),
+    "nd4hip_dgees_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp, ctypes.POINTER(c_int)]),
+    "nd4hip_dgeev_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_dgeev_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),
     "nd4hip_dqp3rank_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, ctypes.c_void_p]),
     "nd4hip_dqp3rank_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, ctypes.c_void_p]),
     "nd4hip_dqp3ls_batched_dev": (c_int, [ctypes.c_void_p] + [c_i64] * 5 + [c_dp, c_i64, c_dp, c_i64, ctypes.c_void_p, c_i64, c_dp, c_i64,

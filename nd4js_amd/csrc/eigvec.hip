@@ -1,5 +1,5 @@
 // The direct parts of the nonsymmetric eigenproblem (src/la/schur.js:31-370, src/la/eigen.js:91-270) for gfx950: eigenvalues and
-// eigenvectors of a real Schur form, and balancing before / after. The Francis iteration (schur_decomp) is not here.
+// eigenvectors of a real Schur form, and balancing before / after. The Francis iteration (schur_decomp) is in schur.hip.
 //
 //   schur_eigenvals (schur.js:31-87): one lane per matrix walks the diagonal right to left with the reference's block test
 //       (1x1 iff j == 0 or T[j,j-1] == 0) and its 2x2 formula; it also records each row's block type for the eigenvector kernel.

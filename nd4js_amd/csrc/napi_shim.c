@@ -69,6 +69,9 @@ static int (*p_dtreval[2])(nd4hip_handle*, int64_t, int64_t, const double*, doub
 static int (*p_dtrevc[2])(nd4hip_handle*, int64_t, int64_t, const double*, const double*, double*, double*);
 static int (*p_dgebal[2])(nd4hip_handle*, int64_t, int64_t, double, const double*, double*, double*);
 static int (*p_zgebak[2])(nd4hip_handle*, int64_t, int64_t, const double*, const double*, double*);
+static int (*p_dhseqr[2])(nd4hip_handle*, int64_t, int64_t, const double*, const double*, double*, double*, int*);
+static int (*p_dgees[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*, double*, int*);
+static int (*p_dgeev[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*, double*);
 static int (*p_dqp3rank[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, int32_t*);
 static int (*p_dqp3ls[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t,
                           const int32_t*, int64_t, const double*, int64_t, double*, int32_t*);
@@ -144,6 +147,9 @@ static int load_library(void) {
   SYM2(p_dtrevc, "nd4hip_dtrevc_batched");
   SYM2(p_dgebal, "nd4hip_dgebal_batched");
   SYM2(p_zgebak, "nd4hip_zgebak_batched");
+  SYM2(p_dhseqr, "nd4hip_dhseqr_batched");
+  SYM2(p_dgees, "nd4hip_dgees_batched");
+  SYM2(p_dgeev, "nd4hip_dgeev_batched");
   SYM2(p_dqp3rank, "nd4hip_dqp3rank_batched");
   SYM2(p_dsrrqr, "nd4hip_dsrrqr_batched");
   SYM2(p_durv, "nd4hip_durv_batched");
@@ -618,6 +624,58 @@ static napi_value js_zgebak(napi_env env, napi_callback_info info) {
   FAIL_IF(p_zgebak[D.dev](g_handle, batch, N, (const double*)D.p, (const double*)V.p, (double*)W.p));
   return NULL;
 }
+/* dhseqr_batched(batch, N, U, H, Q, T) / dgees_batched(batch, N, A, Q, T) -> the most sweeps of one francis_qr call
+ * (schur_qrfrancis_inplace / schur_decomp, schur.js:372-683); dgeev_batched(batch, N, A, Lam, V) / dgeevals_batched(batch, N, A, Lam)
+ * (eigen / eigenvals, eigen.js:33-88); Lam and V complex */
+static napi_value js_dhseqr(napi_env env, napi_callback_info info) {
+  ARGS(6, "dhseqr_batched");
+  int64_t batch, N; opnd U, H, Q, T;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || F64(2, U) || F64(3, H) || F64(4, Q) || F64(5, T)) return NULL;
+  NEED(batch >= 0 && N >= 0 && (size_t)(batch * N * N) <= U.len && (size_t)(batch * N * N) <= H.len && (size_t)(batch * N * N) <= Q.len &&
+       (size_t)(batch * N * N) <= T.len, "dhseqr_batched: buffer too small");
+  SAME_SIDE(U.dev == H.dev && H.dev == Q.dev && Q.dev == T.dev, "dhseqr_batched");
+  if (ensure_handle(env)) return NULL;
+  int sweeps = 0;
+  FAIL_IF(p_dhseqr[U.dev](g_handle, batch, N, (const double*)U.p, (const double*)H.p, (double*)Q.p, (double*)T.p, &sweeps));
+  napi_value out;
+  napi_create_int32(env, sweeps, &out);
+  return out;
+}
+static napi_value js_dgees(napi_env env, napi_callback_info info) {
+  ARGS(5, "dgees_batched");
+  int64_t batch, N; opnd A, Q, T;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || F64(2, A) || F64(3, Q) || F64(4, T)) return NULL;
+  NEED(batch >= 0 && N >= 0 && (size_t)(batch * N * N) <= A.len && (size_t)(batch * N * N) <= Q.len && (size_t)(batch * N * N) <= T.len,
+       "dgees_batched: buffer too small");
+  SAME_SIDE(A.dev == Q.dev && Q.dev == T.dev, "dgees_batched");
+  if (ensure_handle(env)) return NULL;
+  int sweeps = 0;
+  FAIL_IF(p_dgees[A.dev](g_handle, batch, N, (const double*)A.p, (double*)Q.p, (double*)T.p, &sweeps));
+  napi_value out;
+  napi_create_int32(env, sweeps, &out);
+  return out;
+}
+static napi_value js_dgeev(napi_env env, napi_callback_info info) {
+  ARGS(5, "dgeev_batched");
+  int64_t batch, N; opnd A, L, V;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || F64(2, A) || F64(3, L) || F64(4, V)) return NULL;
+  NEED(batch >= 0 && N >= 0 && (size_t)(batch * N * N) <= A.len && (size_t)(2 * batch * N) <= L.len && (size_t)(2 * batch * N * N) <= V.len,
+       "dgeev_batched: buffer too small");
+  SAME_SIDE(A.dev == L.dev && L.dev == V.dev, "dgeev_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dgeev[A.dev](g_handle, batch, N, (const double*)A.p, (double*)L.p, (double*)V.p));
+  return NULL;
+}
+static napi_value js_dgeevals(napi_env env, napi_callback_info info) {
+  ARGS(4, "dgeevals_batched");
+  int64_t batch, N; opnd A, L;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || F64(2, A) || F64(3, L)) return NULL;
+  NEED(batch >= 0 && N >= 0 && (size_t)(batch * N * N) <= A.len && (size_t)(2 * batch * N) <= L.len, "dgeevals_batched: buffer too small");
+  SAME_SIDE(A.dev == L.dev, "dgeevals_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dgeev[A.dev](g_handle, batch, N, (const double*)A.p, (double*)L.p, NULL));
+  return NULL;
+}
 /* dnrmfro(n, A) -> number   (norm(A) 'fro', norm.js:22-85); a device operand's result comes back as a host number too */
 static napi_value js_dnrmfro(napi_env env, napi_callback_info info) {
   ARGS(2, "dnrmfro");
@@ -868,6 +926,10 @@ static napi_value init(napi_env env, napi_value exports) {
     {"dtrevc_batched", NULL, js_dtrevc, NULL, NULL, NULL, napi_default, NULL},
     {"dgebal_batched", NULL, js_dgebal, NULL, NULL, NULL, napi_default, NULL},
     {"zgebak_batched", NULL, js_zgebak, NULL, NULL, NULL, napi_default, NULL},
+    {"dhseqr_batched", NULL, js_dhseqr, NULL, NULL, NULL, napi_default, NULL},
+    {"dgees_batched", NULL, js_dgees, NULL, NULL, NULL, napi_default, NULL},
+    {"dgeev_batched", NULL, js_dgeev, NULL, NULL, NULL, napi_default, NULL},
+    {"dgeevals_batched", NULL, js_dgeevals, NULL, NULL, NULL, napi_default, NULL},
     {"dqp3rank_batched", NULL, js_dqp3rank, NULL, NULL, NULL, napi_default, NULL},
     {"dsrrqr_batched", NULL, js_dsrrqr, NULL, NULL, NULL, napi_default, NULL},
     {"durv_batched", NULL, js_durv, NULL, NULL, NULL, napi_default, NULL},

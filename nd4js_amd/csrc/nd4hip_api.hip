@@ -524,6 +524,100 @@ extern "C" int nd4hip_zgebak_batched_dev(nd4hip_handle* h, int64_t batch, int64_
   return 0;
 }
 
+// ---- schur_decomp (schur.js:372-683), eigen / eigenvals (eigen.js:33-88)
+namespace {
+// flag words and sweep counts of the batch in one read-back; *sweeps_max (may be NULL) receives the largest count
+int hseqr_verdict(nd4hip_handle* h, const int* fs, int64_t batch, int* sweeps_max) {
+  void* hp = nullptr;
+  ND4_TRY(nd4_pinned(h, sizeof(int) * 2 * (size_t)batch, &hp));
+  int* host = static_cast<int*>(hp);
+  ND4_HIP(hipMemcpyAsync(host, fs, sizeof(int) * 2 * (size_t)batch, hipMemcpyDeviceToHost, h->stream));
+  ND4_HIP(hipStreamSynchronize(h->stream));
+  int mx = 0;
+  for (int64_t b = 0; b < batch; b++) if (host[batch + b] > mx) mx = host[batch + b];
+  if (sweeps_max) *sweeps_max = mx;
+  for (int64_t b = 0; b < batch; b++) {
+    ND4_CHECK_ARG(!(host[b] & ND4HIP_EV_FLAG_ASSERT), "Assertion failed.");
+    if (host[b] & ND4HIP_EV_FLAG_NOCONV) {
+      nd4_set_error("nd4hip_dhseqr_batched: no convergence after 30 max(10, n) sweeps of one francis_qr call.");
+      return ND4HIP_ERR_NOCONV;
+    }
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" int nd4hip_dhseqr_batched_ex_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* U, const double* H, double* Q, double* T,
+                                            int* sweeps_out, int tier) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dhseqr_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  const double n = (double)N;
+  Nd4Prof prof(h, "dhseqr_batched", 25.0 * (double)batch * n * n * n, 8.0 * (double)batch * 4.0 * n * n);
+  if (sweeps_out) *sweeps_out = 0;
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dhseqr_batched: extent out of range");
+  ND4_CHECK_ARG(tier >= ND4HIP_SCHUR_TIER_AUTO && tier <= ND4HIP_SCHUR_TIER_GLOBAL, "nd4hip_dhseqr_batched: unknown tier %d", tier);
+  if (batch == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(U && H && Q && T, "nd4hip_dhseqr_batched: NULL pointer");
+  Nd4WsScope scope(h);
+  void* p = nullptr;
+  ND4_TRY(nd4_ws_alloc(h, sizeof(int) * 2 * (size_t)batch, &p));                  // flag words, then sweep counts
+  int* fs = static_cast<int*>(p);
+  ND4_HIP(hipMemsetAsync(fs, 0, sizeof(int) * 2 * (size_t)batch, h->stream));
+  const int64_t chunk = nd4_hseqr_chunk(N);
+  for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
+    const int64_t nb = batch - b0 < chunk ? batch - b0 : chunk;
+    ND4_TRY(nd4_hseqr(h, nb, N, U + b0 * N * N, H + b0 * N * N, Q + b0 * N * N, T + b0 * N * N, fs + b0, fs + batch + b0, tier));
+  }
+  return hseqr_verdict(h, fs, batch, sweeps_out);
+}
+extern "C" int nd4hip_dhseqr_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* U, const double* H, double* Q, double* T,
+                                         int* sweeps_out) {
+  return nd4hip_dhseqr_batched_ex_dev(h, batch, N, U, H, Q, T, sweeps_out, ND4HIP_SCHUR_TIER_AUTO);
+}
+
+extern "C" int nd4hip_dgees_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* Q, double* T, int* sweeps_out) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dgees_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  const double n = (double)N;
+  Nd4Prof prof(h, "dgees_batched", (25.0 + 14.0 / 3.0) * (double)batch * n * n * n, 8.0 * (double)batch * 3.0 * n * n);
+  if (sweeps_out) *sweeps_out = 0;
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dgees_batched: extent out of range");
+  if (batch == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(A && Q && T, "nd4hip_dgees_batched: NULL pointer");
+  ND4_TRY(nd4hip_dgehrd_batched_dev(h, batch, N, A, Q, T));
+  return nd4hip_dhseqr_batched_dev(h, batch, N, Q, T, Q, T, sweeps_out);
+}
+
+extern "C" int nd4hip_dgeev_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* Lam, double* V) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dgeev_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  const double n = (double)N;
+  Nd4Prof prof(h, "dgeev_batched", (25.0 + 14.0 / 3.0 + (V ? 16.0 / 3.0 : 0.0)) * (double)batch * n * n * n, 8.0 * (double)batch * (V ? 3.0 : 1.0) * n * n);
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dgeev_batched: extent out of range");
+  if (batch == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(A && Lam, "nd4hip_dgeev_batched: NULL pointer");
+  // eigen.js:33-88 per chunk, the intermediates in the workspace: D [N], B, Q, T [N, N] and the eigenvectors before zgebak
+  const int64_t chunk = nd4_hseqr_chunk(N);
+  for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
+    const int64_t nb = batch - b0 < chunk ? batch - b0 : chunk;
+    Nd4WsScope scope(h);
+    void *pd = nullptr, *pb = nullptr, *pq = nullptr, *pt = nullptr, *pv = nullptr;
+    ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)(nb * N), &pd));
+    ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)(nb * N * N), &pb));
+    ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)(nb * N * N), &pq));
+    ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)(nb * N * N), &pt));
+    if (V) ND4_TRY(nd4_ws_alloc(h, 2 * sizeof(double) * (size_t)(nb * N * N), &pv));
+    double *D = static_cast<double*>(pd), *B = static_cast<double*>(pb), *Q = static_cast<double*>(pq), *T = static_cast<double*>(pt),
+           *X = static_cast<double*>(pv);
+    ND4_TRY(nd4hip_dgebal_batched_dev(h, nb, N, 2.0, A + b0 * N * N, D, B));
+    ND4_TRY(nd4hip_dgees_batched_dev(h, nb, N, B, Q, T, nullptr));
+    if (!V) { ND4_TRY(nd4hip_dtreval_batched_dev(h, nb, N, T, Lam + 2 * b0 * N)); continue; }
+    ND4_TRY(nd4hip_dtrevc_batched_dev(h, nb, N, Q, T, Lam + 2 * b0 * N, X));
+    ND4_TRY(nd4hip_zgebak_batched_dev(h, nb, N, D, X, V + 2 * b0 * N * N));
+  }
+  return 0;
+}
+
 // rrqr_rank (rrqr.js:398-414): rank [batch] of R [M, N]; -1 marks a matrix whose partial norms are not finite
 extern "C" int nd4hip_dqp3rank_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* R, int32_t* rank) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dqp3rank_batched: NULL handle");

@@ -763,6 +763,74 @@ extern "C" int nd4hip_zgebak_batched(nd4hip_handle* h, int64_t batch, int64_t N,
   return run_host(h, batch, ops, fn);
 }
 
+// ------------------------------------------------------------------------------------ schur_decomp, eigen, eigenvals
+namespace {
+// the largest of the devices' sweep counts (each device's host thread writes its own slot)
+struct SweepMax {
+  std::vector<int> per;
+  explicit SweepMax(nd4hip_handle* h) : per(1 + h->peers.size(), 0) {}
+  void note(int dev, int sw) { if (sw > per[(size_t)dev]) per[(size_t)dev] = sw; }
+  int max() const { int m = 0; for (int x : per) if (x > m) m = x; return m; }
+};
+}  // namespace
+
+extern "C" int nd4hip_dhseqr_batched_ex(nd4hip_handle* h, int64_t batch, int64_t N, const double* U, const double* H, double* Q, double* T,
+                                        int* sweeps_out, int tier) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dhseqr_batched: NULL handle");
+  if (sweeps_out) *sweeps_out = 0;
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dhseqr_batched: extent out of range");
+  if (batch == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(U && H && Q && T, "nd4hip_dhseqr_batched: NULL pointer");
+  SweepMax sweeps(h);
+  std::vector<Operand> ops{in_op(U, N * N, N * N), in_op(H, N * N, N * N), out_op(Q, N * N), out_op(T, N * N)};
+  ChunkFn fn = [&, N, tier](nd4hip_handle* hd, int dev, int64_t nb, void* const* d) {
+    int sw = 0;
+    const int rc = nd4hip_dhseqr_batched_ex_dev(hd, nb, N, P(d, 0), P(d, 1), P(d, 2), P(d, 3), &sw, tier);
+    sweeps.note(dev, sw);
+    return rc;
+  };
+  const int rc = run_host(h, batch, ops, fn);
+  if (sweeps_out) *sweeps_out = sweeps.max();
+  return rc;
+}
+extern "C" int nd4hip_dhseqr_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* U, const double* H, double* Q, double* T,
+                                     int* sweeps_out) {
+  return nd4hip_dhseqr_batched_ex(h, batch, N, U, H, Q, T, sweeps_out, ND4HIP_SCHUR_TIER_AUTO);
+}
+
+extern "C" int nd4hip_dgees_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* Q, double* T, int* sweeps_out) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dgees_batched: NULL handle");
+  if (sweeps_out) *sweeps_out = 0;
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dgees_batched: extent out of range");
+  if (batch == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(A && Q && T, "nd4hip_dgees_batched: NULL pointer");
+  SweepMax sweeps(h);
+  std::vector<Operand> ops{in_op(A, N * N, N * N), out_op(Q, N * N), out_op(T, N * N)};
+  ChunkFn fn = [&, N](nd4hip_handle* hd, int dev, int64_t nb, void* const* d) {
+    int sw = 0;
+    const int rc = nd4hip_dgees_batched_dev(hd, nb, N, P(d, 0), P(d, 1), P(d, 2), &sw);
+    sweeps.note(dev, sw);
+    return rc;
+  };
+  const int rc = run_host(h, batch, ops, fn);
+  if (sweeps_out) *sweeps_out = sweeps.max();
+  return rc;
+}
+
+extern "C" int nd4hip_dgeev_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* Lam, double* V) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dgeev_batched: NULL handle");
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dgeev_batched: extent out of range");
+  if (batch == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(A && Lam, "nd4hip_dgeev_batched: NULL pointer");
+  std::vector<Operand> ops{in_op(A, N * N, N * N), out_op(Lam, 2 * N)};
+  if (V) ops.push_back(out_op(V, 2 * N * N));
+  const bool vecs = V != nullptr;
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
+    return nd4hip_dgeev_batched_dev(hd, nb, N, P(d, 0), P(d, 1), vecs ? P(d, 2) : nullptr);
+  };
+  return run_host(h, batch, ops, fn);
+}
+
 // ------------------------------------------------------------------------------------ SVD
 extern "C" int nd4hip_dgesvdj_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A,
                                       double* U, double* sv, double* V, int* sweeps_out, double* offnorm_out) {

@@ -143,6 +143,10 @@ int nd4_trevals(nd4hip_handle* h, int64_t batch, int64_t N, const double* T, dou
 int nd4_trevc(nd4hip_handle* h, int64_t batch, int64_t N, const double* Q, const double* T, double* Lam, double* V, int* flags);
 int nd4_gebal(nd4hip_handle* h, int64_t batch, int64_t N, double p, const double* A, double* D, double* B, int* flags);
 int nd4_gebak(nd4hip_handle* h, int64_t batch, int64_t N, const double* D, const double* V, double* W);
+// the Francis iteration of schur_decomp (schur.hip); flags [batch] zero on entry, sweeps [batch]; tier: ND4HIP_SCHUR_TIER_*
+int nd4_hseqr(nd4hip_handle* h, int64_t batch, int64_t N, const double* U, const double* H, double* Q, double* T, int* flags, int* sweeps,
+              int tier);
+int64_t nd4_hseqr_chunk(int64_t N);
 int nd4_gesvdj(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A,
                double* U, double* sv, double* V, int* sweeps_out, double* offnorm_out);
 

@@ -621,3 +621,59 @@ def eigen_balance_post(D, V):
     h = _h(V)
     _ev_call(h.lib.nd4hip_zgebak_batched_dev, h.ptr, _batch(V.shape[:-2]), N, _p(D), _p(V), _p(W))
     return W
+
+
+def schur_qrfrancis(U, H, tier=None, sweeps=False):
+    """device-resident Francis iteration of schur_decomp (schur.js:388-683): [Q, T] from a Hessenberg decomposition (U, H), the
+    reference's bits; `tier` as in la.schur_qrfrancis. Synchronises: the per-matrix flags and sweep counts are read back."""
+    from .la import _schur_tier
+    _chk(U, "U"), _chk(H, "H")
+    if U.device != H.device:
+        raise ValueError("U and H must be on the same device")
+    if U.dim() < 2 or U.shape[-2] != U.shape[-1]:
+        raise ValueError("Q is not square.")
+    if U.dim() != H.dim():
+        raise ValueError("Q.ndim != H.ndim.")
+    if tuple(U.shape) != tuple(H.shape):
+        raise ValueError("Q.shape != H.shape.")
+    t = _schur_tier(tier)
+    N = int(U.shape[-1])
+    Q, T = torch.empty_like(U), torch.empty_like(H)
+    sw = ctypes.c_int(0)
+    h = _h(U)
+    _ev_call(h.lib.nd4hip_dhseqr_batched_ex_dev, h.ptr, _batch(U.shape[:-2]), N, _p(U), _p(H), _p(Q), _p(T), ctypes.byref(sw), t)
+    return [Q, T, sw.value] if sweeps else [Q, T]
+
+
+def schur_decomp(A, sweeps=False):
+    """device-resident schur_decomp (schur.js:372-381): [Q, T]. Synchronises (flags and sweep counts)."""
+    _chk(A, "A")
+    if A.dim() < 2:
+        raise ValueError("hessenberg_decomp(A): A must at least be 2D.")
+    N = int(A.shape[-1])
+    if A.shape[-2] != N:
+        raise ValueError("hessenberg_decomp(A): A must be square.")
+    Q, T = torch.empty_like(A), torch.empty_like(A)
+    sw = ctypes.c_int(0)
+    h = _h(A)
+    _ev_call(h.lib.nd4hip_dgees_batched_dev, h.ptr, _batch(A.shape[:-2]), N, _p(A), _p(Q), _p(T), ctypes.byref(sw))
+    return [Q, T, sw.value] if sweeps else [Q, T]
+
+
+def eigen(A):
+    """device-resident eigen (eigen.js:33-80): [eigenvalues [..., N], unit eigenvectors [..., N, N]], both complex128."""
+    lead, N = _ev_sq(A, "A is not square")
+    L = torch.empty(lead + (N,), dtype=torch.complex128, device=A.device)
+    V = torch.empty(lead + (N, N), dtype=torch.complex128, device=A.device)
+    h = _h(A)
+    _ev_call(h.lib.nd4hip_dgeev_batched_dev, h.ptr, _batch(lead), N, _p(A), _p(L), _p(V))
+    return [L, V]
+
+
+def eigenvals(A):
+    """device-resident eigenvals (eigen.js:83-88): complex128 [..., N]."""
+    lead, N = _ev_sq(A, "A is not square")
+    L = torch.empty(lead + (N,), dtype=torch.complex128, device=A.device)
+    h = _h(A)
+    _ev_call(h.lib.nd4hip_dgeev_batched_dev, h.ptr, _batch(lead), N, _p(A), _p(L), None)
+    return L

@@ -859,6 +859,54 @@ function makeLa(NDA, fallback, SolveError, Complex) {
     return wrapZ('eigen_balance_post', dev, Array.from(V.shape), W);
   };
 
+  /* ---- schur_decomp (schur.js:372-683), eigen / eigenvals (eigen.js:33-88), csrc/schur.hip. The reference's eigen calls its
+   * module-internal schur_decomp, so eigen and eigenvals are composed on the device (dgeev) and not from the patched names ---- */
+  const squareOr = (A, ndimText, squareText) => {
+    if (A.ndim < 2) throw new Error(ndimText);
+    if (A.shape[A.ndim - 2] !== A.shape[A.ndim - 1]) throw new Error(squareText);
+  };
+  la.schur_decomp = function schur_decomp(A) {
+    A = asarray(A);
+    squareOr(A, 'hessenberg_decomp(A): A must at least be 2D.', 'hessenberg_decomp(A): A must be square.');
+    if (!f64Only(A)) return evFallback('schur_decomp', [A]);
+    const nd_ = A.ndim, N = A.shape[nd_ - 1], batch = prod(A.shape, 0, nd_ - 2), dev = isDev(A), temps = [];
+    const Q = alloc(dev, batch * N * N), T = alloc(dev, batch * N * N);
+    try { native().dgees_batched(batch, N, view(opF64(A, dev, temps), 0), view(Q, 0), view(T, 0)); } finally { release(temps); }
+    return [wrap(dev, Array.from(A.shape), Q), wrap(dev, Array.from(A.shape), T)];
+  };
+  // the reference's private in-place step as a function of (U, H) returning new arrays: [Q, T]
+  la.schur_qrfrancis = function schur_qrfrancis(U, H) {
+    U = asarray(U); H = asarray(H);
+    if (U.ndim < 2 || U.shape[U.ndim - 2] !== U.shape[U.ndim - 1]) throw new Error('Q is not square.');
+    if (U.ndim !== H.ndim) throw new Error('Q.ndim != H.ndim.');
+    for (let i = U.ndim; i-- > 0;) if (U.shape[i] !== H.shape[i]) throw new Error('Q.shape != H.shape.');
+    if (!f64Only(U) || !f64Only(H)) throw new Error('nd4hip.schur_qrfrancis: dtype is not accelerated.');
+    const nd_ = U.ndim, N = U.shape[nd_ - 1], batch = prod(U.shape, 0, nd_ - 2), dev = isDev(U) || isDev(H), temps = [];
+    const Q = alloc(dev, batch * N * N), T = alloc(dev, batch * N * N);
+    try { native().dhseqr_batched(batch, N, view(opF64(U, dev, temps), 0), view(opF64(H, dev, temps), 0), view(Q, 0), view(T, 0)); } finally { release(temps); }
+    return [wrap(dev, Array.from(U.shape), Q), wrap(dev, Array.from(U.shape), T)];
+  };
+  la.eigen = function eigen(A) {
+    A = asarray(A);
+    squareOr(A, 'A is not square', 'A is not square');
+    if (!f64Only(A)) return evFallback('eigen', [A]);
+    needComplex('eigen');
+    const nd_ = A.ndim, N = A.shape[nd_ - 1], batch = prod(A.shape, 0, nd_ - 2), dev = isDev(A), temps = [];
+    const L = alloc(dev, 2 * batch * N), V = alloc(dev, 2 * batch * N * N);
+    try { native().dgeev_batched(batch, N, view(opF64(A, dev, temps), 0), view(L, 0), view(V, 0)); } finally { release(temps); }
+    return [wrapZ('eigen', dev, Array.from(A.shape.subarray(0, nd_ - 1)), L), wrapZ('eigen', dev, Array.from(A.shape), V)];
+  };
+  la.eigenvals = function eigenvals(A) {
+    A = asarray(A);
+    squareOr(A, 'A is not square', 'A is not square');
+    if (!f64Only(A)) return evFallback('eigenvals', [A]);
+    needComplex('eigenvals');
+    const nd_ = A.ndim, N = A.shape[nd_ - 1], batch = prod(A.shape, 0, nd_ - 2), dev = isDev(A), temps = [];
+    const L = alloc(dev, 2 * batch * N);
+    try { native().dgeevals_batched(batch, N, view(opF64(A, dev, temps), 0), view(L, 0)); } finally { release(temps); }
+    return wrapZ('eigenvals', dev, Array.from(A.shape.subarray(0, nd_ - 1)), L);
+  };
+
   // complex128 device arrays are accepted by matmul2 / matmul only: every other function refuses them before it looks at the
   // buffer (which holds 2n doubles, not n float64 entries)
   const complexOk = new Set(['matmul2', 'matmul', 'eigen_balance_post', '_chain_plan', 'to_device', 'to_host', 'synchronize', 'profile_enable', 'profile_last']);
@@ -894,6 +942,10 @@ function estimatedWork(name, args) {
   return a[0] * a[1] * a[2] * Math.min(a[1], a[2]);
 }
 
+// schur_decomp, eigen, eigenvals of ONE host matrix: the host module's single thread wins up to N = 128 (64: 6.2 ms against
+// 10.2 ms through the device with copies, 128: 40.5 against 50.8), the device from 256 on (429 against 226 ms); DESIGN.md §4.12
+const SCHUR_ROUTED = new Set(['schur_decomp', 'eigen', 'eigenvals']), SCHUR_HOST_MAX_N = 128;
+
 /** Patch a loaded nd4js instance in place: the hot-path functions run on the GPU. Returns nd.
  *  opts.minWork (default 0 = off): a call whose estimated work (flops: 2 I K J for products, M N min(M, N) per matrix for
  *  decompositions and solves) is below it — and whose operands all live on the host — is forwarded to the HOST MODULE'S OWN
@@ -914,11 +966,22 @@ function install(nd, opts) {
                     det: nd.la.det, slogdet: nd.la.slogdet, det_tri: nd.la.det_tri, slogdet_tri: nd.la.slogdet_tri,
                     rank: nd.la.rank, lstsq: nd.la.lstsq, norm: nd.la.norm,
                     schur_eigenvals: nd.la.schur_eigenvals, schur_eigen: nd.la.schur_eigen,
-                    eigen_balance_pre: nd.la.eigen_balance_pre, eigen_balance_post: nd.la.eigen_balance_post};
+                    eigen_balance_pre: nd.la.eigen_balance_pre, eigen_balance_post: nd.la.eigen_balance_post,
+                    schur_decomp: nd.la.schur_decomp, eigen: nd.la.eigen, eigenvals: nd.la.eigenvals};
   const acc = makeLa(nd.NDArray, original, nd.la.SingularMatrixSolveError || SingularMatrixSolveError, (nd.dt && nd.dt.Complex128Array) || null);
   const target = Object.isFrozen(nd.la) || !Object.getOwnPropertyDescriptor(nd.la, 'matmul2').writable ? null : nd.la;
   const patched = target || Object.create(nd.la);
   const route = k => {
+    if (SCHUR_ROUTED.has(k) && typeof original[k] === 'function') {
+      const f = function (...args) {                      // one host matrix up to the crossover is the host module's (DESIGN.md §4.12)
+        const A = args[0], s = A && A.shape, single = !!s && s.length >= 2 && Array.from(s).slice(0, -2).every(x => x === 1);
+        const onHost = !(A instanceof acc.DeviceNDArray);
+        if (onHost && single && s[s.length - 1] <= SCHUR_HOST_MAX_N) return original[k].apply(nd.la, args);
+        return onHost && minWork && estimatedWork(k, args) < minWork ? original[k].apply(nd.la, args) : acc[k](...args);
+      };
+      Object.defineProperty(f, 'name', {value: k});
+      return f;
+    }
     if (!minWork || typeof original[k] !== 'function') return acc[k];
     const f = function (...args) {
       const onHost = args.every(x => !(x instanceof acc.DeviceNDArray));
@@ -928,7 +991,7 @@ function install(nd, opts) {
     return f;
   };
   for (const k of Object.keys(original)) Object.defineProperty(patched, k, {value: route(k), writable: true, enumerable: true, configurable: true});
-  for (const k of ['to_device', 'to_host', 'synchronize', 'DeviceNDArray', 'profile_enable', 'profile_last'])   // §8f N3 / §8b extensions, not in the reference
+  for (const k of ['to_device', 'to_host', 'synchronize', 'DeviceNDArray', 'profile_enable', 'profile_last', 'schur_qrfrancis'])   // §8f N3 / §8b extensions, not in the reference (schur_qrfrancis: its private step)
     Object.defineProperty(patched, k, {value: acc[k], writable: true, enumerable: false, configurable: true});
   if (!target) { try { nd.la = patched; } catch (e) { /* exported getter: caller uses the returned object */ } }
   patched.__nd4hip_original__ = original;

@@ -1007,3 +1007,79 @@ def eigen_balance_post(D, V, device=None):
     h = _lib.handle(device)
     _ev_call(h.lib.nd4hip_zgebak_batched, h.ptr, int(np.prod(lead, dtype=np.int64)), N, _ptr(D), _ptr(V), _ptr(W))
     return W
+
+
+# ---------------------------------------------------------------------------------------------------
+# schur_decomp (src/la/schur.js:372-683), eigen and eigenvals (src/la/eigen.js:33-88), csrc/schur.hip
+# ---------------------------------------------------------------------------------------------------
+SCHUR_TIERS = {None: 0, "auto": 0, "lds": 1, "global": 2}
+
+
+def _schur_tier(tier):
+    if tier not in SCHUR_TIERS:
+        raise ValueError("schur_qrfrancis(U,H): unknown tier %r (auto, lds or global)." % (tier,))
+    return SCHUR_TIERS[tier]
+
+
+def schur_qrfrancis(U, H, tier=None, device=None, sweeps=False):
+    """schur.js:388-683 (the reference's private schur_qrfrancis_inplace, returning new arrays): the real Schur decomposition
+    [Q, T] of U H U^T from a Hessenberg decomposition (U, H) [..., N, N] by the reference's Francis iteration, its bits. `tier`
+    picks where the kernel keeps the matrices ('lds': N <= 65, 'global': any N <= 2048; the same bits); sweeps=True appends the
+    most sweeps one francis_qr call took."""
+    U, H = np.asarray(U), np.asarray(H)
+    if U.ndim < 2 or U.shape[-2] != U.shape[-1]:
+        raise ValueError("Q is not square.")
+    if U.ndim != H.ndim:
+        raise ValueError("Q.ndim != H.ndim.")
+    if U.shape != H.shape:
+        raise ValueError("Q.shape != H.shape.")
+    t = _schur_tier(tier)
+    U, H = _asarray(U, "schur_qrfrancis(U,H)"), _asarray(H, "schur_qrfrancis(U,H)")
+    N = U.shape[-1]
+    Q, T = np.empty_like(U), np.empty_like(H)
+    sw = ctypes.c_int(0)
+    h = _lib.handle(device)
+    _ev_call(h.lib.nd4hip_dhseqr_batched_ex, h.ptr, int(np.prod(U.shape[:-2], dtype=np.int64)), N, _ptr(U), _ptr(H), _ptr(Q), _ptr(T),
+             ctypes.byref(sw), t)
+    return [Q, T, sw.value] if sweeps else [Q, T]
+
+
+def schur_decomp(A, device=None, sweeps=False):
+    """schur.js:372-381: [Q, T] with A = Q T Q^T, Q orthogonal and T quasi-triangular with complex-eigenvalued 2x2 blocks only:
+    hessenberg_decomp, then the Francis iteration, on the device without a round trip."""
+    A = np.asarray(A)
+    if A.ndim < 2:
+        raise ValueError("hessenberg_decomp(A): A must at least be 2D.")
+    A = _asarray(A, "schur_decomp(A)")
+    N = A.shape[-1]
+    if A.shape[-2] != N:
+        raise ValueError("hessenberg_decomp(A): A must be square.")
+    Q, T = np.empty_like(A), np.empty_like(A)
+    sw = ctypes.c_int(0)
+    h = _lib.handle(device)
+    _ev_call(h.lib.nd4hip_dgees_batched, h.ptr, int(np.prod(A.shape[:-2], dtype=np.int64)), N, _ptr(A), _ptr(Q), _ptr(T), ctypes.byref(sw))
+    return [Q, T, sw.value] if sweeps else [Q, T]
+
+
+def _geev(A, what, vectors, device):
+    A = np.asarray(A)
+    if A.ndim < 2 or A.shape[-2] != A.shape[-1]:
+        raise ValueError("A is not square")                                # eigen_balance_pre's text (eigen.js:91-100)
+    A = _asarray(A, what)
+    N = A.shape[-1]
+    L = np.empty(A.shape[:-1], dtype=np.complex128)
+    V = np.empty(A.shape, dtype=np.complex128) if vectors else None
+    h = _lib.handle(device)
+    _ev_call(h.lib.nd4hip_dgeev_batched, h.ptr, int(np.prod(A.shape[:-2], dtype=np.int64)), N, _ptr(A), _ptr(L), _ptr(V) if vectors else None)
+    return [L, V] if vectors else L
+
+
+def eigen(A, device=None):
+    """eigen.js:33-80: [eigenvalues complex128 [..., N], eigenvectors complex128 [..., N, N] with unit columns]: balancing with
+    p = 2, schur_decomp, schur_eigen, then the balancing undone, all on the device."""
+    return _geev(A, "eigen(A)", True, device)
+
+
+def eigenvals(A, device=None):
+    """eigen.js:83-88: schur_eigenvals of the Schur form of the balanced matrix, complex128 [..., N]."""
+    return _geev(A, "eigenvals(A)", False, device)
