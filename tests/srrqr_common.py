@@ -67,3 +67,25 @@ def strong_F(R, r):
     rn = np.linalg.norm(Ai, axis=1)
     cn = np.linalg.norm(R[r:, r:], axis=0) if r < M else np.zeros(N - r)
     return float(np.hypot(AB, rn[:, None] * cn[None, :]).max())
+
+
+# ---- test_gpu_srrqr_paths.py ------------------------------------------------------------------------------------------------
+def urvls_factors(seed, n, r):
+    """synthetic U R V of order n and rank r for urv_lstsq: U, V orthogonal (numpy's QR of uniform matrices), R = [[T, 0],
+    [0, 0]] with exact zeros outside the r x r triangle T = D + E (cond <= ~5, rrqr_common.ls_factors), Y [n, 3] uniform"""
+    from nd4js_amd import rng
+    from rrqr_common import ls_factors
+    U, R, _, Y = ls_factors(seed, n, n, n, 3, r)
+    R[r:] = 0.0
+    R[:, r:] = 0.0
+    V = np.linalg.qr(rng.matrix(seed + 5, n, n))[0]
+    return U, R, V, Y
+
+
+def urvls_ref(U, R, V, r, Y, dtype=np.longdouble):
+    """urv_lstsq (urv.js:138-323): x = V[:r]^T T^-1 (U^T Y)[:r] with T = R[:r, :r], in `dtype`"""
+    T = np.asarray(R)[:r, :r].astype(dtype)
+    z = np.asarray(U)[:, :r].astype(dtype).T @ np.asarray(Y).astype(dtype)
+    for i in range(r - 1, -1, -1):
+        z[i] = (z[i] - T[i, i + 1:] @ z[i + 1:]) / T[i, i]
+    return np.asarray(V)[:r].astype(dtype).T @ z

@@ -4,7 +4,7 @@
  * families of tests/families.py; only numbers (outputs, sampled entries, norms) are written, as .npy files plus their own
  * manifest.json under tests/golden/srrqr/.
  *
- *   ND4_REFERENCE=<path to dist/nd.js> node tools/gen_golden_srrqr.js         # all cases (~10 s, most of it 1024^2)
+ *   ND4_REFERENCE=<path to dist/nd.js> node tools/gen_golden_srrqr.js         # all cases (~40 s, most of it 1024^2 and 1100^2)
  *
  * Without ND4_REFERENCE the bundle is found through BASELINE.json's reference_path, as the node tests do.
  */
@@ -101,12 +101,12 @@ function kahan(n, theta) {                              // (i, j >= i) = sin^i (
 }
 
 /* ---------- cases ---------- */
-function caseSrrqr(name, meta, A, opt) {
+function caseSrrqr(name, meta, A, opt, decisionsOnly) {
   const [Q, R, P, r] = opt ? nd.la.srrqr_decomp_full(A, opt) : nd.la.srrqr_decomp_full(A);
   const [, Rw] = nd.la.rrqr_decomp(A);
   record(name, Object.assign({op: 'srrqr_decomp_full', opt: opt || null, rrqr_rank: Array.from(nd.la.rrqr_rank(Rw).data),
                               rrqr_rank_of_srrqr_R: Array.from(nd.la.rrqr_rank(R).data)}, meta),
-         A.data.length > 40000 ? {P, r} : {Q, R, P, r});                // large inputs: the decisions only
+         decisionsOnly || A.data.length > 40000 ? {P, r} : {Q, R, P, r});   // large inputs: the decisions only
 }
 function caseGen(name, seed, shape, fam, opt) { caseSrrqr(name, {seed, shape, family: fam}, input(seed, shape, fam), opt); }
 function caseLarge(name, seed, N) {
@@ -174,4 +174,14 @@ caseUrvLs('urvls_rankdef_60x40', {seed: 991, shape: [60, 40], family: 'rankdef'}
 caseUrvLs('urvls_rankdef_40x60', {seed: 992, shape: [40, 60], family: 'rankdef'}, input(992, [40, 60], 'rankdef'), 1);
 caseUrvLs('urvls_lowrank_300x200', {seed: 941, shape: [300, 200], family: 'lowrank', lowrank: 77}, lowrank(941, 300, 200, 77), 4);
 caseUrvLs('urvls_dense_40x40', {seed: 993, shape: [40, 40], family: 'dense'}, input(993, [40, 40], 'dense'), 2);
+/* beyond 1024 rows, columns or rank: a second pass of srrqr_decide's loops over N, M, k and k0 (tests/test_gpu_srrqr_paths.py);
+ * these inputs exceed 40000 entries, so P and r only (~25 s here, most of it the two 1100^2) */
+caseGen('dense_1100x1100', 1001, [1100, 1100], 'dense');
+caseSrrqr('lowrank300_1100', {seed: 1002, shape: [1100, 1100], family: 'lowrank', lowrank: 300}, lowrank(1002, 1100, 1100, 300));
+caseGen('dense_40x1100', 1004, [40, 1100], 'dense');
+caseGen('dense_1100x40', 1005, [1100, 40], 'dense');
+caseSrrqr('lowrank20_40x1100', {seed: 1006, shape: [40, 1100], family: 'lowrank', lowrank: 20}, lowrank(1006, 40, 1100, 20));
+/* the finite members of the batch of six 60^2 of tests/test_gpu_srrqr_paths.py (the sixth is kahan60): P and r only */
+caseSrrqr('b6_dense_60', {seed: 8900, shape: [60, 60], family: 'dense'}, input(8900, [60, 60], 'dense'), undefined, true);
+caseSrrqr('b6_lowrank20_60', {seed: 8901, shape: [60, 60], family: 'lowrank', lowrank: 20}, lowrank(8901, 60, 60, 20), undefined, true);
 fs.writeFileSync(path.join(OUT, 'manifest.json'), JSON.stringify(manifest, null, 1));
