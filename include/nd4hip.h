@@ -31,7 +31,7 @@ typedef struct nd4hip_handle nd4hip_handle;
 #define ND4HIP_ERR_HIP      -2   /* HIP runtime error (message has the hipError string) */
 #define ND4HIP_ERR_NOCONV   -3   /* Jacobi SVD hit the sweep limit */
 #define ND4HIP_ERR_NODEV    -4   /* no usable GPU */
-#define ND4HIP_ERR_SINGULAR -5   /* Cholesky met a NaN pivot: 'Matrix contains NaNs or is (near) singular.' */
+#define ND4HIP_ERR_SINGULAR -5   /* Cholesky met a NaN pivot: 'Matrix contains NaNs or is (near) singular.'; dsytrf_bk a zero column or NaN */
 #define ND4HIP_ERR_XCHG     -6   /* an exchange between co-resident workgroups INSIDE a kernel timed out (the row-split QR panels, the
                                     multi-workgroup LU panels, the one-launch Hessenberg reduction / bidiagonalisation of one matrix of
                                     128 .. 2048 rows and columns): the results of the call are invalid — Q / R hold NaN, the permutation
@@ -161,6 +161,40 @@ int nd4hip_dldltrs_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, int64
                                const double* Y, int64_t strideY, double* X);
 int nd4hip_dldltrs_batched    (nd4hip_handle* h, int64_t batch, int64_t N, int64_t J, const double* LD, int64_t strideLD,
                                const double* Y, int64_t strideY, double* X);
+
+/* ---- pldlp_decomp / pldlp_solve: replace src/la/pldlp.js:191-222 (kernel :35-188) and :519-604 (kernel :441-516) ----
+ * Bunch-Kaufman partial pivoting after LAPACK's DSYTF2, 1x1 and 2x2 pivots. S [batch,N,N] symmetric (lower triangle read) ->
+ * LD [batch,N,N] (unit-lower L below the diagonal blocks, the 1x1 and 2x2 blocks of D on them, exact zeros above the diagonal)
+ * and P [batch,N] int32, the row order, with the SECOND row of every 2x2 block stored complemented (~p). LD and P are the
+ * reference's bit for bit on every tier: the kernels restate its operation order and are compiled without FMA contraction
+ * (csrc/pldlp.hip). S may be LD. A step before the last whose column is zero or holds a NaN where the searches look stops that
+ * matrix: the call returns ND4HIP_ERR_SINGULAR and nd4hip_last_error is the reference's text followed by the lowest such
+ * member, '_pldlp_decomp(M,N, LD,LD_off, P,P_off): Zero column or NaN encountered. (matrix <b>)'; the other members are
+ * complete, in both forms (the host-pointer form brings every member back before it reports). The last step is not checked, like the reference's: [[0]] factorises.
+ * The _ex forms take the tier. LDS: one workgroup per matrix, the triangle in LDS, N <= lds_max_n. GLOBAL: one workgroup per
+ * matrix in global memory, N <= global_max_n. GRID: one matrix over the whole chip, a pivot launch and an update launch (tiles
+ * of grid_tile^2) per step, a batch loops over its members. AUTO: LDS where N fits, else GLOBAL when the batch has at least as
+ * many members as the device has CUs, else GRID. A tier that cannot hold N is ND4HIP_ERR_ARG. nd4hip_dsytrf_bk_limits reports
+ * the three constants (any pointer may be NULL); nd4hip_dsytrf_bk_tier returns the tier a call would take (1..3) or
+ * ND4HIP_ERR_ARG.
+ * dsytrs_bk: X [batch,N,J] = P L^-T D^-1 L^-1 P^T Y; strides in elements, 0 = broadcast; X may be Y. Every index read from P
+ * is range-checked on the device before it is used; an unusable P is ND4HIP_ERR_ARG 'pldlp_solve(LD,P,y): P contains
+ * out-of-bounds indices.' and never reads or writes out of bounds. The host-pointer form checks P completely (range,
+ * duplicates, block structure; the reference's pldlp_p messages) before any device work. */
+#define ND4HIP_PLDLP_TIER_AUTO   0
+#define ND4HIP_PLDLP_TIER_LDS    1
+#define ND4HIP_PLDLP_TIER_GLOBAL 2
+#define ND4HIP_PLDLP_TIER_GRID   3
+int nd4hip_dsytrf_bk_batched_dev   (nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* LD, int32_t* P);
+int nd4hip_dsytrf_bk_batched       (nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* LD, int32_t* P);
+int nd4hip_dsytrf_bk_batched_ex_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* LD, int32_t* P, int tier);
+int nd4hip_dsytrf_bk_batched_ex    (nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* LD, int32_t* P, int tier);
+int nd4hip_dsytrs_bk_batched_dev   (nd4hip_handle* h, int64_t batch, int64_t N, int64_t J, const double* LD, int64_t strideLD,
+                                    const int32_t* P, int64_t strideP, const double* Y, int64_t strideY, double* X);
+int nd4hip_dsytrs_bk_batched       (nd4hip_handle* h, int64_t batch, int64_t N, int64_t J, const double* LD, int64_t strideLD,
+                                    const int32_t* P, int64_t strideP, const double* Y, int64_t strideY, double* X);
+int nd4hip_dsytrf_bk_tier          (nd4hip_handle* h, int64_t batch, int64_t N, int tier);
+int nd4hip_dsytrf_bk_limits        (int* lds_max_n, int* global_max_n, int* grid_tile);
 
 /* ---- bidiag_decomp: replaces src/la/bidiag.js:245-319 (kernels :32-242) -----------------------------------
  * A [batch,M,N] -> U [batch,M,K], B [batch,K,J] upper bidiagonal (exact zeros elsewhere), V [batch,J,N] with A = U B V,

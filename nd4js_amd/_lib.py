@@ -55,6 +55,14 @@ SIGNATURES = {
     "nd4hip_dldltrf_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp]),
     "nd4hip_dldltrs_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_i64, c_dp, c_i64, c_dp]),
     "nd4hip_dldltrs_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_i64, c_dp, c_i64, c_dp]),
+    "nd4hip_dsytrf_bk_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, ctypes.c_void_p]),
+    "nd4hip_dsytrf_bk_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, ctypes.c_void_p]),
+    "nd4hip_dsytrf_bk_batched_ex_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, ctypes.c_void_p, c_int]),
+    "nd4hip_dsytrf_bk_batched_ex": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, ctypes.c_void_p, c_int]),
+    "nd4hip_dsytrs_bk_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_i64, ctypes.c_void_p, c_i64, c_dp, c_i64, c_dp]),
+    "nd4hip_dsytrs_bk_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_i64, ctypes.c_void_p, c_i64, c_dp, c_i64, c_dp]),
+    "nd4hip_dsytrf_bk_tier": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_int]),
+    "nd4hip_dsytrf_bk_limits": (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "nd4hip_dgebrd_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp]),
     "nd4hip_dgebrd_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp]),
     "nd4hip_dgehrd_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),

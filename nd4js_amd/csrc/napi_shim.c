@@ -80,6 +80,8 @@ static getrs_fn p_dgetrs[2];
 static int (*p_dpotrf[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*);
 static int (*p_dldltrf[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*);
 static int (*p_dldltrs[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t, double*);
+static int (*p_dsytrf_bk[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*, int32_t*, int);
+static int (*p_dsytrs_bk[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, int64_t, const int32_t*, int64_t, const double*, int64_t, double*);
 static int (*p_dpotrs[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t, double*);
 static trsm_fn p_dtrsm[2];
 static int (*p_malloc)(nd4hip_handle*, size_t, void**);
@@ -135,6 +137,8 @@ static int load_library(void) {
   SYM2(p_dpotrs, "nd4hip_dpotrs_batched");
   SYM2(p_dldltrf, "nd4hip_dldltrf_batched");
   SYM2(p_dldltrs, "nd4hip_dldltrs_batched");
+  SYM2(p_dsytrf_bk, "nd4hip_dsytrf_bk_batched_ex");
+  SYM2(p_dsytrs_bk, "nd4hip_dsytrs_bk_batched");
   SYM2(p_dqrls, "nd4hip_dqrls_batched");
   SYM2(p_dgeqp3, "nd4hip_dgeqp3_batched");
   SYM2(p_dgeqp3_full, "nd4hip_dgeqp3_full_batched");
@@ -781,6 +785,32 @@ static napi_value js_dldltrf(napi_env env, napi_callback_info info) {
   FAIL_IF(p_dldltrf[S.dev](g_handle, batch, N, (const double*)S.p, (double*)L.p));
   return NULL;
 }
+/* dsytrf_bk_batched(batch, N, S, LD, P, tier)   (pldlp_decomp, pldlp.js:191-222; tier: ND4HIP_PLDLP_TIER_*) */
+static napi_value js_dsytrf_bk(napi_env env, napi_callback_info info) {
+  ARGS(6, "dsytrf_bk_batched");
+  int64_t batch, N, tier; opnd S, L, P;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || F64(2, S) || F64(3, L) || I32(4, P) || get_i64(env, a[5], &tier)) return NULL;
+  NEED(batch >= 0 && N >= 0 && (size_t)(batch * N * N) <= S.len && (size_t)(batch * N * N) <= L.len && (size_t)(batch * N) <= P.len,
+       "dsytrf_bk_batched: buffer too small");
+  SAME_SIDE(S.dev == L.dev && L.dev == P.dev, "dsytrf_bk_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dsytrf_bk[S.dev](g_handle, batch, N, (const double*)S.p, (double*)L.p, (int32_t*)P.p, (int)tier));
+  return NULL;
+}
+/* dsytrs_bk_batched(batch, N, J, LD, strideLD, P, strideP, Y, strideY, X)   (pldlp_solve, pldlp.js:519-604) */
+static napi_value js_dsytrs_bk(napi_env env, napi_callback_info info) {
+  ARGS(10, "dsytrs_bk_batched");
+  int64_t batch, N, J, sL, sP, sY; opnd L, P, Y, X;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || get_i64(env, a[2], &J) || F64(3, L) || get_i64(env, a[4], &sL) ||
+      I32(5, P) || get_i64(env, a[6], &sP) || F64(7, Y) || get_i64(env, a[8], &sY) || F64(9, X)) return NULL;
+  NEED(batch >= 0 && N >= 0 && J >= 0 && sL >= 0 && sP >= 0 && sY >= 0, "dsytrs_bk_batched: negative extent");
+  NEED(batch == 0 || ((size_t)((batch - 1) * sL + N * N) <= L.len && (size_t)((batch - 1) * sP + N) <= P.len &&
+                      (size_t)((batch - 1) * sY + N * J) <= Y.len && (size_t)(batch * N * J) <= X.len), "dsytrs_bk_batched: buffer too small");
+  SAME_SIDE(L.dev == P.dev && P.dev == Y.dev && Y.dev == X.dev, "dsytrs_bk_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dsytrs_bk[X.dev](g_handle, batch, N, J, (const double*)L.p, sL, (const int32_t*)P.p, sP, (const double*)Y.p, sY, (double*)X.p));
+  return NULL;
+}
 /* dldltrs_batched(batch, N, J, LD, strideLD, Y, strideY, X)   (ldl_solve, ldl.js:133-201) */
 static napi_value js_dldltrs(napi_env env, napi_callback_info info) {
   ARGS(8, "dldltrs_batched");
@@ -940,6 +970,8 @@ static napi_value init(napi_env env, napi_value exports) {
     {"dpotrs_batched", NULL, js_dpotrs, NULL, NULL, NULL, napi_default, NULL},
     {"dldltrf_batched", NULL, js_dldltrf, NULL, NULL, NULL, napi_default, NULL},
     {"dldltrs_batched", NULL, js_dldltrs, NULL, NULL, NULL, napi_default, NULL},
+    {"dsytrf_bk_batched", NULL, js_dsytrf_bk, NULL, NULL, NULL, napi_default, NULL},
+    {"dsytrs_bk_batched", NULL, js_dsytrs_bk, NULL, NULL, NULL, napi_default, NULL},
     {"dev_alloc", NULL, js_dev_alloc, NULL, NULL, NULL, napi_default, NULL},
     {"dev_free", NULL, js_dev_free, NULL, NULL, NULL, napi_default, NULL},
     {"dev_upload", NULL, js_dev_upload, NULL, NULL, NULL, napi_default, NULL},

@@ -235,6 +235,84 @@ extern "C" int nd4hip_dldltrs_batched_dev(nd4hip_handle* h, int64_t batch, int64
   return 0;
 }
 
+// ---- pivoted LDL^T: pldlp_decomp (pldlp.js:191-222), pldlp_solve (:519-604)
+int nd4_sytrf_bk_run(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* LD, int32_t* P, int tier, int64_t member0,
+                     int64_t* first_bad) {
+  // the argument checks come first: they need no handle (and are testable without a device)
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsytrf_bk_batched: negative extent");
+  ND4_CHECK_ARG(tier >= ND4HIP_PLDLP_TIER_AUTO && tier <= ND4HIP_PLDLP_TIER_GRID, "nd4hip_dsytrf_bk_batched: unknown tier %d", tier);
+  ND4_CHECK_ARG(tier == ND4HIP_PLDLP_TIER_AUTO || nd4_sytrf_bk_tier(nullptr, batch, N, tier) != 0,
+                "nd4hip_dsytrf_bk_batched: tier %d is not available at N = %lld", tier, (long long)N);
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dsytrf_bk_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "dsytrf_bk_batched", (double)(batch * N * N * N / 3.0), (double)(16.0 * batch * N * N));
+  const int t = nd4_sytrf_bk_tier(h, batch, N, tier);
+  if (batch == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(S && LD && P, "nd4hip_dsytrf_bk_batched: NULL pointer");
+  Nd4WsScope scope(h);
+  void* p = nullptr;
+  ND4_TRY(nd4_ws_alloc(h, sizeof(int) * (size_t)batch, &p));
+  int* flags = static_cast<int*>(p);
+  ND4_HIP(hipMemsetAsync(flags, 0, sizeof(int) * (size_t)batch, h->stream));
+  ND4_TRY(nd4_sytrf_bk(h, batch, N, S, LD, P, flags, t));
+  // the reference throws at the first zero column or NaN (pldlp.js:148-149): one small read-back decides it
+  void* hp = nullptr;
+  ND4_TRY(nd4_pinned(h, sizeof(int) * (size_t)batch, &hp));
+  int* host = static_cast<int*>(hp);
+  ND4_HIP(hipMemcpyAsync(host, flags, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, h->stream));
+  ND4_HIP(hipStreamSynchronize(h->stream));
+  for (int64_t b = 0; b < batch; b++)
+    if (host[b]) {
+      nd4_set_error("_pldlp_decomp(M,N, LD,LD_off, P,P_off): Zero column or NaN encountered. (matrix %lld)", (long long)(member0 + b));
+      if (first_bad) *first_bad = member0 + b;
+      return ND4HIP_ERR_SINGULAR;
+    }
+  return 0;
+}
+extern "C" int nd4hip_dsytrf_bk_batched_ex_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* LD, int32_t* P, int tier) {
+  return nd4_sytrf_bk_run(h, batch, N, S, LD, P, tier, 0, nullptr);
+}
+extern "C" int nd4hip_dsytrf_bk_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* LD, int32_t* P) {
+  return nd4_sytrf_bk_run(h, batch, N, S, LD, P, ND4HIP_PLDLP_TIER_AUTO, 0, nullptr);
+}
+extern "C" int nd4hip_dsytrf_bk_tier(nd4hip_handle* h, int64_t batch, int64_t N, int tier) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dsytrf_bk_tier: NULL handle");
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsytrf_bk_tier: negative extent");
+  ND4_CHECK_ARG(tier >= ND4HIP_PLDLP_TIER_AUTO && tier <= ND4HIP_PLDLP_TIER_GRID, "nd4hip_dsytrf_bk_tier: unknown tier %d", tier);
+  const int t = nd4_sytrf_bk_tier(h, batch, N, tier);
+  ND4_CHECK_ARG(t != 0, "nd4hip_dsytrf_bk_tier: tier %d is not available at N = %lld", tier, (long long)N);
+  return t;
+}
+extern "C" int nd4hip_dsytrf_bk_limits(int* lds_max_n, int* global_max_n, int* grid_tile) {
+  nd4_sytrf_bk_limits(lds_max_n, global_max_n, grid_tile);
+  return 0;
+}
+extern "C" int nd4hip_dsytrs_bk_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, int64_t J, const double* LD, int64_t strideLD,
+                                            const int32_t* P, int64_t strideP, const double* Y, int64_t strideY, double* X) {
+  ND4_CHECK_ARG(batch >= 0 && N >= 0 && J >= 0, "nd4hip_dsytrs_bk_batched: negative extent");
+  ND4_CHECK_ARG((strideLD == 0 || strideLD >= N * N) && (strideP == 0 || strideP >= N) && (strideY == 0 || strideY >= N * J),
+                "nd4hip_dsytrs_bk_batched: a stride must be 0 or at least the size of one operand");
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dsytrs_bk_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "dsytrs_bk_batched", (double)(2.0 * batch * N * N * J), (double)(8.0 * batch * (double)(N * N + 2 * N * J)));
+  if (batch == 0 || N == 0 || J == 0) return 0;
+  ND4_CHECK_ARG(LD && P && Y && X, "nd4hip_dsytrs_bk_batched: NULL pointer");
+  Nd4WsScope scope(h);
+  void* p = nullptr;
+  ND4_TRY(nd4_ws_alloc(h, sizeof(int), &p));
+  int* flag = static_cast<int*>(p);
+  ND4_HIP(hipMemsetAsync(flag, 0, sizeof(int), h->stream));
+  ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_sytrs_bk(h, nb, N, J, LD + b0 * strideLD, strideLD, P + b0 * strideP, strideP, Y + b0 * strideY, strideY,
+                                             X + b0 * N * J, flag));
+  void* hp = nullptr;
+  ND4_TRY(nd4_pinned(h, sizeof(int), &hp));
+  int* host = static_cast<int*>(hp);
+  ND4_HIP(hipMemcpyAsync(host, flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  ND4_HIP(hipStreamSynchronize(h->stream));
+  ND4_CHECK_ARG(host[0] == 0, "pldlp_solve(LD,P,y): P contains out-of-bounds indices.");
+  return 0;
+}
+
 // ---- bidiag_decomp (bidiag.js:245-319)   
 extern "C" int nd4hip_dgebrd_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* U, double* B, double* V) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgebrd_batched: NULL handle");

@@ -12,6 +12,8 @@
 // Error path: a failing chunk stops the block, the block's streams are synchronised BEFORE its staging returns to the cache.
 #include "nd4hip_internal.h"
 #include <algorithm>
+#include <atomic>
+#include <climits>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -87,6 +89,10 @@ struct Plan {
   int max_chunks = 8;
 };
 
+// index, in the caller's batch, of the first member of the chunk whose ChunkFn is running on this thread (for error texts that
+// name a member)
+thread_local int64_t g_chunk_first = 0;
+
 inline size_t span_bytes(const Operand& o, int64_t nb) { return (size_t)((o.stride ? (nb - 1) * o.stride : 0) + o.item) * o.es; }
 
 // One device's contiguous block [lo, hi) of the batch: chunked, double-buffered.
@@ -144,6 +150,7 @@ int run_block(nd4hip_handle* h, int dev, int64_t lo, int64_t hi, const std::vect
     const int set = (int)(c & 1) % nsets;
     if (cs != h->stream) ND4_HIP(hipStreamWaitEvent(h->stream, h->ev_in[set], 0));
     for (size_t i = 0; i < nops; i++) dptr[i] = buf(i, set).p;
+    g_chunk_first = b0;
     ND4_TRY(fn(h, dev, nb, dptr.data()));
     ND4_HIP(hipEventRecord(h->ev_chunk[set], h->stream));
     return 0;
@@ -424,6 +431,69 @@ extern "C" int nd4hip_dldltrs_batched(nd4hip_handle* h, int64_t batch, int64_t N
   std::vector<Operand> ops{in_op(LD, N * N, strideLD), in_op(Y, N * J, strideY), out_op(X, N * J)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
     return nd4hip_dldltrs_batched_dev(hd, nb, N, J, P(d, 0), strideLD, P(d, 1), strideY, P(d, 2));
+  };
+  return run_host(h, batch, ops, fn);
+}
+
+// ---- pivoted LDL^T (pldlp.js)
+extern "C" int nd4hip_dsytrf_bk_batched_ex(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* LD, int32_t* Pv, int tier) {
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsytrf_bk_batched: negative extent");
+  ND4_CHECK_ARG(tier >= ND4HIP_PLDLP_TIER_AUTO && tier <= ND4HIP_PLDLP_TIER_GRID, "nd4hip_dsytrf_bk_batched: unknown tier %d", tier);
+  ND4_CHECK_ARG(tier == ND4HIP_PLDLP_TIER_AUTO || nd4_sytrf_bk_tier(nullptr, batch, N, tier) != 0,
+                "nd4hip_dsytrf_bk_batched: tier %d is not available at N = %lld", tier, (long long)N);
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dsytrf_bk_batched: NULL handle");
+  if (batch == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(S && LD && Pv, "nd4hip_dsytrf_bk_batched: NULL pointer");
+  // AUTO is decided once, by the whole batch: the chunks and devices below must not each choose their own tier
+  const int t = nd4_sytrf_bk_tier(h, batch, N, tier);
+  std::vector<Operand> ops{in_op(S, N * N, N * N), out_op(LD, N * N), out_op(Pv, N, 4)};
+  // a singular member does not stop the others: every chunk runs and comes back, the lowest singular member is reported at the end
+  std::atomic<int64_t> worst(INT64_MAX);
+  ChunkFn fn = [=, &worst](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
+    int64_t bad = INT64_MAX;
+    const int rc = nd4_sytrf_bk_run(hd, nb, N, P(d, 0), P(d, 1), static_cast<int32_t*>(d[2]), t, g_chunk_first, &bad);
+    if (rc != ND4HIP_ERR_SINGULAR) return rc;
+    for (int64_t seen = worst.load(); bad < seen && !worst.compare_exchange_weak(seen, bad);) {}
+    return 0;
+  };
+  ND4_TRY(run_host(h, batch, ops, fn));
+  if (worst.load() != INT64_MAX) {
+    nd4_set_error("_pldlp_decomp(M,N, LD,LD_off, P,P_off): Zero column or NaN encountered. (matrix %lld)", (long long)worst.load());
+    return ND4HIP_ERR_SINGULAR;
+  }
+  return 0;
+}
+extern "C" int nd4hip_dsytrf_bk_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* LD, int32_t* Pv) {
+  return nd4hip_dsytrf_bk_batched_ex(h, batch, N, S, LD, Pv, ND4HIP_PLDLP_TIER_AUTO);
+}
+extern "C" int nd4hip_dsytrs_bk_batched(nd4hip_handle* h, int64_t batch, int64_t N, int64_t J, const double* LD, int64_t strideLD,
+                                        const int32_t* Pv, int64_t strideP, const double* Y, int64_t strideY, double* X) {
+  ND4_CHECK_ARG(batch >= 0 && N >= 0 && J >= 0, "nd4hip_dsytrs_bk_batched: negative extent");
+  ND4_CHECK_ARG((strideLD == 0 || strideLD >= N * N) && (strideP == 0 || strideP >= N) && (strideY == 0 || strideY >= N * J),
+                "nd4hip_dsytrs_bk_batched: a stride must be 0 or at least the size of one operand");
+  if (batch == 0 || N == 0 || J == 0) return 0;
+  ND4_CHECK_ARG(LD && Pv && Y && X, "nd4hip_dsytrs_bk_batched: NULL pointer");
+  {  // pldlp_p's checks (pldlp.js:408-435), before any device work
+    std::vector<char> seen((size_t)N);
+    for (int64_t b = 0; b < (strideP ? batch : 1); b++) {
+      const int32_t* p = Pv + b * strideP;
+      std::fill(seen.begin(), seen.end(), 0);
+      for (int64_t i = N; i-- > 0;) {
+        int64_t q = p[i];
+        if (q < 0) {
+          ND4_CHECK_ARG(i > 0 && p[i - 1] >= 0, "pldlp_solve(LD,P,y): P is invalid.");
+          q = ~q;
+        }
+        ND4_CHECK_ARG(q >= 0 && q < N, "pldlp_solve(LD,P,y): P contains out-of-bounds indices.");
+        ND4_CHECK_ARG(!seen[(size_t)q], "pldlp_solve(LD,P,y): P contains duplicate indices.");
+        seen[(size_t)q] = 1;
+      }
+    }
+  }
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dsytrs_bk_batched: NULL handle");
+  std::vector<Operand> ops{in_op(LD, N * N, strideLD), in_op(Pv, N, strideP, 4), in_op(Y, N * J, strideY), out_op(X, N * J)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
+    return nd4hip_dsytrs_bk_batched_dev(hd, nb, N, J, P(d, 0), strideLD, static_cast<const int32_t*>(d[1]), strideP, P(d, 2), strideY, P(d, 3));
   };
   return run_host(h, batch, ops, fn);
 }

@@ -106,6 +106,16 @@ int nd4_trsm_t(nd4hip_handle* h, int64_t batch, int64_t M, int64_t J, const doub
 int nd4_trsm_t_ex(nd4hip_handle* h, bool unit, int64_t batch, int64_t M, int64_t J, const double* T, int64_t ldT, int64_t sT, double* X, int64_t sX);
 int nd4_ldltrf(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* LD);
 int nd4_ldltrs(nd4hip_handle* h, int64_t batch, int64_t N, int64_t J, const double* LD, int64_t sLD, const double* Y, int64_t sY, double* X);
+// pivoted LDL^T (pldlp.hip); flags [batch] zero on entry, tier: what nd4_sytrf_bk_tier returned (0: N does not fit)
+void nd4_sytrf_bk_limits(int* lds_max_n, int* global_max_n, int* grid_tile);
+int nd4_sytrf_bk_tier(const nd4hip_handle* h, int64_t batch, int64_t N, int tier);
+int nd4_sytrf_bk(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* LD, int32_t* P, int* flags, int tier);
+int nd4_sytrs_bk(nd4hip_handle* h, int64_t batch, int64_t N, int64_t J, const double* LD, int64_t sLD, const int32_t* P, int64_t sP,
+                 const double* Y, int64_t sY, double* X, int* flag);
+// the _dev entry point with the index of its first member in the caller's batch (for the error text of the host-pointer form);
+// *first_bad (may be NULL) receives the lowest singular member, counted in the caller's batch, when ND4HIP_ERR_SINGULAR is returned
+int nd4_sytrf_bk_run(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* LD, int32_t* P, int tier, int64_t member0,
+                     int64_t* first_bad);
 int nd4_gebrd(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* U, double* B, double* V);
 int nd4_gehrd(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* U, double* H);
 int nd4_potrf(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* L, int* flags);

@@ -317,6 +317,55 @@ def ldl_solve(LD, Y):
     return X
 
 
+def pldlp_decomp(S, tier=None, out=None):
+    """[LD, P] (P int32) of symmetric S [..., N, N] by Bunch-Kaufman pivoting, the reference's bits (la.pldlp_decomp); out=S
+    factorises in place. A singular member raises ValueError with the reference's text and the member."""
+    from .la import _arg_error, _pldlp_tier
+    _chk(S, "S")
+    N = S.shape[-1]
+    if S.dim() < 2 or S.shape[-2] != N:
+        raise ValueError("Last two dimensions must be quadratic.")
+    LD = torch.empty_like(S) if out is None else _chk(out, "out")
+    P = torch.empty(S.shape[:-1], dtype=torch.int32, device=S.device)
+    h = _h(S)
+    try:
+        _lib.check(h.lib.nd4hip_dsytrf_bk_batched_ex_dev(h.ptr, _batch(S.shape[:-2]), N, _p(S), _p(LD), _p(P), _pldlp_tier(tier)))
+    except _lib.Nd4HipError as e:
+        if e.code == -5:
+            raise ValueError(str(e).split(": ", 1)[1])
+        raise _arg_error(e)
+    return [LD, P]
+
+
+def pldlp_solve(LD, P, Y, out=None):
+    """X with S X = Y from pldlp_decomp's LD [..., N, N] and P [..., N] (int32); LD and P may be one pair for a batch of Y.
+    out=Y solves in place. An index of P out of range raises ValueError (nothing is read or written out of bounds)."""
+    from .la import _arg_error
+    _chk(LD, "LD"), _chk(Y, "Y")
+    if not (isinstance(P, torch.Tensor) and P.is_cuda and P.dtype == torch.int32 and P.is_contiguous()):
+        raise TypeError("P must be a contiguous int32 CUDA tensor")
+    N, J = Y.shape[-2:]
+    if LD.dim() < 2 or LD.shape[-1] != LD.shape[-2]:
+        raise ValueError("pldlp_solve(LD,P,y): LD must be square.")
+    if P.dim() < 1 or P.shape[-1] != LD.shape[-1] or tuple(P.shape[:-1]) != tuple(LD.shape[:-2]):
+        raise ValueError("pldlp_solve(LD,P,y): LD and P shape mismatch.")
+    if LD.shape[-1] != N:
+        raise ValueError("pldlp_solve(LD,P,y): LD and y shape mismatch.")
+    lead = tuple(Y.shape[:-2])
+    one = _batch(LD.shape[:-2]) == 1
+    if tuple(LD.shape[:-2]) != lead and not one:
+        raise ValueError("Shapes are not broadcast-compatible.")       # general broadcasting: host wrapper (la.py)
+    X = torch.empty_like(Y) if out is None else _chk(out, "out")
+    h = _h(Y)
+    b = _batch(lead)
+    try:
+        _lib.check(h.lib.nd4hip_dsytrs_bk_batched_dev(h.ptr, b, N, J, _p(LD), 0 if one else N * N, _p(P), 0 if one else N, _p(Y),
+                                                      N * J if b > 1 else 0, _p(X)))
+    except _lib.Nd4HipError as e:
+        raise _arg_error(e)
+    return X
+
+
 def hessenberg_decomp(A):
     _chk(A, "A")
     N = A.shape[-1]

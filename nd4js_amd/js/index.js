@@ -486,6 +486,106 @@ function makeLa(NDA, fallback, SolveError, Complex) {
     return wrap(dev, [...lead, N, J], X);
   };
 
+  /* ---- pivoted LDL^T, Bunch-Kaufman (pldlp.js), csrc/pldlp.hip: LD and P are the reference's bits ---- */
+  const PLDLP_TIERS = {auto: 0, lds: 1, global: 2, grid: 3};
+  la.pldlp_decomp = function pldlp_decomp(S, opts) {       // pldlp.js:191-222; opts.tier (not in the reference): auto | lds | global | grid
+    S = asarray(S);
+    const nd_ = S.ndim;
+    if (nd_ < 2 || S.shape[nd_ - 2] !== S.shape[nd_ - 1]) throw new Error('Last two dimensions must be quadratic.');
+    const tier = opts && opts.tier != undefined ? PLDLP_TIERS[opts.tier] : 0;
+    if (tier === undefined) throw new Error('pldlp_decomp(S): unknown tier ' + opts.tier + ' (auto, lds, global or grid).');
+    if (!gpuOk(S)) { if (fallback && fallback.pldlp_decomp) return fallback.pldlp_decomp(S); throw new Error('nd4hip.pldlp_decomp: dtype ' + dtypeOf(S) + ' is not accelerated.'); }
+    const N = S.shape[nd_ - 1], batch = prod(S.shape, 0, nd_ - 2), dev = isDev(S), temps = [];
+    const LD = alloc(dev, batch * N * N), P = alloc(dev, batch * N, Int32Array);
+    try { native().dsytrf_bk_batched(batch, N, view(opF64(S, dev, temps), 0), view(LD, 0), view(P, 0), tier); }
+    catch (e) { if (dev) { LD.free(); P.free(); } throw e; }
+    finally { release(temps); }
+    return [wrap(dev, S.shape, LD), wrap(dev, S.shape.subarray(0, nd_ - 1), P)];
+  };
+  // the argument checks shared by pldlp_l / _d / _p (pldlp.js:231-236) and pldlp_solve (:529-537)
+  const pldlpArgs = (LD, P, y) => {
+    LD = asarray(LD); P = asarray(P);
+    if (y !== undefined) y = asarray(y);
+    if (LD.ndim < 2) throw new Error('pldlp_solve(LD,P,y): LD must be at least 2D.');
+    if (P.ndim < 1) throw new Error('pldlp_solve(LD,P,y): P must be at least 1D.');
+    if (y !== undefined && y.ndim < 2) throw new Error('pldlp_solve(LD,P,y): y must be at least 2D.');
+    const N = LD.shape[LD.ndim - 2];
+    if (N !== LD.shape[LD.ndim - 1]) throw new Error('pldlp_solve(LD,P,y): LD must be square.');
+    if (N !== P.shape[P.ndim - 1]) throw new Error('pldlp_solve(LD,P,y): LD and P shape mismatch.');
+    if (y !== undefined && N !== y.shape[y.ndim - 2]) throw new Error('pldlp_solve(LD,P,y): LD and y shape mismatch.');
+    return [LD, P, y, N];
+  };
+  // P with the marks of the 2x2 blocks removed, after the complete check of pldlp.js:408-435 (last matrix and last row first)
+  const pldlpPerm = (P, N) => {
+    const p = P.data, out = new Int32Array(p.length), seen = new Uint8Array(N);
+    for (let off = p.length - N; N > 0 && off >= 0; off -= N) {
+      seen.fill(0);
+      for (let i = N - 1; i >= 0; i--) {
+        let q = p[off + i];
+        if (q < 0) {
+          if (i === 0 || p[off + i - 1] < 0) throw new Error('pldlp_solve(LD,P,y): P is invalid.');
+          q = ~q;
+        }
+        if (!(q >= 0 && q < N)) throw new Error('pldlp_solve(LD,P,y): P contains out-of-bounds indices.');
+        if (seen[q]) throw new Error('pldlp_solve(LD,P,y): P contains duplicate indices.');
+        seen[q] = 1; out[off + i] = q;
+      }
+    }
+    return out;
+  };
+  // pldlp_l / pldlp_d: host side, one N x N result per broadcast member of (LD, P)
+  const pldlpFactor = (LD, P, member) => {
+    if (P == undefined) [LD, P] = LD;
+    let N; [LD, P, , N] = pldlpArgs(LD, P);
+    const lL = Array.from(LD.shape.subarray(0, LD.ndim - 2)), lP = Array.from(P.shape.subarray(0, P.ndim - 1));
+    const lead = bcastLead([lL, lP], 'Shapes are not broadcast-compatible.');
+    const out = new Float64Array(lead.reduce((a, b) => a * b, 1) * N * N), ld = LD.data, p = P.data;
+    for (const [cnt, [oL, oP], [sL, sP], b0] of bcastGroupsN(lead, [lL, lP], [N * N, N]))
+      for (let c = 0; c < cnt; c++) member(N, ld, oL + c * sL, p, oP + c * sP, out, (b0 + c) * N * N);
+    return new NDA(Int32Array.from([...lead, N, N]), out);
+  };
+  la.pldlp_l = (LD, P) => pldlpFactor(LD, P, (N, ld, oL, p, oP, out, o) => {           // pldlp.js:225-304
+    for (let i = 0; i < N; i++) {
+      const end = p[oP + i] < 0 ? i - 1 : i;             // the entry inside a 2x2 block belongs to D
+      for (let j = 0; j < end; j++) out[o + N * i + j] = ld[oL + N * i + j];
+      out[o + N * i + i] = 1;
+    }
+  });
+  la.pldlp_d = (LD, P) => pldlpFactor(LD, P, (N, ld, oL, p, oP, out, o) => {           // pldlp.js:307-380
+    for (let i = 0; i < N; i++) {
+      out[o + N * i + i] = ld[oL + N * i + i];
+      if (i > 0 && p[oP + i] < 0) out[o + N * i + i - 1] = out[o + N * (i - 1) + i] = ld[oL + N * i + i - 1];
+    }
+  });
+  la.pldlp_p = function pldlp_p(LD, P) {                    // pldlp.js:383-438
+    if (P == undefined) [LD, P] = LD;
+    let N; [LD, P, , N] = pldlpArgs(LD, P);
+    bcastLead([Array.from(LD.shape.subarray(0, LD.ndim - 2)), Array.from(P.shape.subarray(0, P.ndim - 1))], 'Shapes are not broadcast-compatible.');
+    return new NDA(Int32Array.from(P.shape), pldlpPerm(P, N));
+  };
+  la.pldlp_solve = function pldlp_solve(LD, P, y) {         // pldlp.js:519-604
+    if (y == undefined) {
+      if (P == undefined) throw new Error('Assertion failed.');
+      y = P; [LD, P] = LD;
+    }
+    let N; [LD, P, y, N] = pldlpArgs(LD, P, y);
+    const J = y.shape[y.ndim - 1];
+    if (!gpuOk(LD) || !gpuOk(y) || dtypeOf(P) !== 'int32') {
+      if (fallback && fallback.pldlp_solve) return fallback.pldlp_solve(LD, P, y);
+      throw new Error('nd4hip.pldlp_solve: dtype is not accelerated.');
+    }
+    const lL = Array.from(LD.shape.subarray(0, LD.ndim - 2)), lP = Array.from(P.shape.subarray(0, P.ndim - 1)), lY = Array.from(y.shape.subarray(0, y.ndim - 2));
+    const lead = bcastLead([lL, lP, lY], 'Shapes are not broadcast-compatible.');
+    pldlpPerm(P, N);                                        // P is checked completely on the host before any device work
+    const dev = isDev(LD) || isDev(P) || isDev(y), temps = [];
+    const X = alloc(dev, lead.reduce((a, b) => a * b, 1) * N * J), Ld = opF64(LD, dev, temps), Pd = opI32(P, dev, temps), yd = opF64(y, dev, temps);
+    try {
+      for (const [cnt, [oL, oP, oY], [sL, sP, sY], b0] of bcastGroupsN(lead, [lL, lP, lY], [N * N, N, N * J]))
+        native().dsytrs_bk_batched(cnt, N, J, view(Ld, oL), sL, view(Pd, oP), sP, view(yd, oY), sY, view(X, b0 * N * J));
+    } finally { release(temps); }
+    return wrap(dev, [...lead, N, J], X);
+  };
+
   la.bidiag_decomp = function bidiag_decomp(A) {           // bidiag.js:245-319
     A = asarray(A);
     if (A.ndim < 2) throw new Error('bidiag_decomp(A): A must be at least 2D.');
@@ -959,7 +1059,9 @@ function install(nd, opts) {
                     lu_solve: nd.la.lu_solve, tril_solve: nd.la.tril_solve, triu_solve: nd.la.triu_solve,
                     qr_lstsq: nd.la.qr_lstsq, svd_lstsq: nd.la.svd_lstsq, svd_solve: nd.la.svd_solve, svd_rank: nd.la.svd_rank,
                     cholesky_decomp: nd.la.cholesky_decomp, cholesky_solve: nd.la.cholesky_solve,
-                    ldl_decomp: nd.la.ldl_decomp, ldl_solve: nd.la.ldl_solve, hessenberg_decomp: nd.la.hessenberg_decomp, bidiag_decomp: nd.la.bidiag_decomp,
+                    ldl_decomp: nd.la.ldl_decomp, ldl_solve: nd.la.ldl_solve,
+                    pldlp_decomp: nd.la.pldlp_decomp, pldlp_solve: nd.la.pldlp_solve, pldlp_l: nd.la.pldlp_l, pldlp_d: nd.la.pldlp_d, pldlp_p: nd.la.pldlp_p,
+                    hessenberg_decomp: nd.la.hessenberg_decomp, bidiag_decomp: nd.la.bidiag_decomp,
                     rrqr_decomp: nd.la.rrqr_decomp, rrqr_decomp_full: nd.la.rrqr_decomp_full, rrqr_rank: nd.la.rrqr_rank,
                     rrqr_lstsq: nd.la.rrqr_lstsq, rrqr_solve: nd.la.rrqr_solve, solve: nd.la.solve,
                     srrqr_decomp_full: nd.la.srrqr_decomp_full, urv_decomp_full: nd.la.urv_decomp_full, urv_lstsq: nd.la.urv_lstsq,

@@ -1083,3 +1083,184 @@ def eigen(A, device=None):
 def eigenvals(A, device=None):
     """eigen.js:83-88: schur_eigenvals of the Schur form of the balanced matrix, complex128 [..., N]."""
     return _geev(A, "eigenvals(A)", False, device)
+
+
+# ---------------------------------------------------------------------------------------------------
+# Pivoted symmetric indefinite LDL^T, Bunch-Kaufman (src/la/pldlp.js), csrc/pldlp.hip
+# ---------------------------------------------------------------------------------------------------
+PLDLP_TIERS = {None: 0, "auto": 0, "lds": 1, "global": 2, "grid": 3}
+PLDLP_SINGULAR = "_pldlp_decomp(M,N, LD,LD_off, P,P_off): Zero column or NaN encountered."
+
+
+def _pldlp_tier(tier):
+    if tier not in PLDLP_TIERS:
+        raise ValueError("pldlp_decomp(S): unknown tier %r (auto, lds, global or grid)." % (tier,))
+    return PLDLP_TIERS[tier]
+
+
+def pldlp_limits():
+    """the kernels' size constants (needs no device): the largest N of the 'lds' and of the 'global' tier, and the edge of the
+    'grid' tier's update tile"""
+    a, b, c = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    _lib.check(_lib.load().nd4hip_dsytrf_bk_limits(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+    return {"lds_max_n": a.value, "global_max_n": b.value, "grid_tile": c.value}
+
+
+def pldlp_tier(batch, N, tier=None, device=None):
+    """the name of the tier pldlp_decomp takes for `batch` matrices of size N under `tier`"""
+    h = _lib.handle(device)
+    t = h.lib.nd4hip_dsytrf_bk_tier(h.ptr, int(batch), int(N), _pldlp_tier(tier))
+    if t < 0:
+        _ev_call(int, t)                   # raises with the library's text
+    return {1: "lds", 2: "global", 3: "grid"}[t]
+
+
+def pldlp_decomp(S, device=None, tier=None):
+    """pldlp.js:191-222: [LD, P] of the Bunch-Kaufman factorisation S[P][:, P] = L D L^T of symmetric S [..., N, N] (lower
+    triangle read): LD holds the unit-lower L below the 1x1 and 2x2 diagonal blocks of D, zeros above the diagonal; P [..., N]
+    int32 is the row order with the second row of every 2x2 block complemented. The reference's bits on every tier
+    ('lds', 'global', 'grid'; None or 'auto' chooses)."""
+    t = _pldlp_tier(tier)
+    S = np.asarray(S)
+    if S.ndim < 2 or S.shape[-1] != S.shape[-2]:
+        raise ValueError("Last two dimensions must be quadratic.")
+    S = _asarray(S, "pldlp_decomp(S)")
+    LD, P = np.empty_like(S), np.empty(S.shape[:-1], dtype=np.int32)
+    h = _lib.handle(device)
+    try:
+        _lib.check(h.lib.nd4hip_dsytrf_bk_batched_ex(h.ptr, int(np.prod(S.shape[:-2], dtype=np.int64)), S.shape[-1], _ptr(S), _ptr(LD),
+                                                     _ptr(P), t))
+    except _lib.Nd4HipError as e:
+        if e.code == -5:
+            raise ValueError(str(e).split(": ", 1)[1])
+        raise _arg_error(e)
+    return [LD, P]
+
+
+def _pldlp_args(LD, P, y=None, with_y=False):
+    """the reference's argument checks of pldlp_l / _d / _p (pldlp.js:231-236) and pldlp_solve (:529-537)"""
+    LD, P = np.asarray(LD), np.asarray(P)
+    if with_y:
+        y = np.asarray(y)
+    if LD.ndim < 2:
+        raise ValueError("pldlp_solve(LD,P,y): LD must be at least 2D.")
+    if P.ndim < 1:
+        raise ValueError("pldlp_solve(LD,P,y): P must be at least 1D.")
+    if with_y and y.ndim < 2:
+        raise ValueError("pldlp_solve(LD,P,y): y must be at least 2D.")
+    N = LD.shape[-2]
+    if N != LD.shape[-1]:
+        raise ValueError("pldlp_solve(LD,P,y): LD must be square.")
+    if N != P.shape[-1]:
+        raise ValueError("pldlp_solve(LD,P,y): LD and P shape mismatch.")
+    if with_y and N != y.shape[-2]:
+        raise ValueError("pldlp_solve(LD,P,y): LD and y shape mismatch.")
+    if P.dtype.kind not in "iu":
+        raise TypeError("pldlp_solve(LD,P,y): P must be an integer array, got %s" % P.dtype)
+    return LD, np.ascontiguousarray(P.astype(np.int32, copy=False)), y
+
+
+def _pldlp_lead(*shapes):
+    try:
+        return tuple(np.broadcast_shapes(*shapes))
+    except ValueError:
+        raise ValueError("Shapes are not broadcast-compatible.")
+
+
+def _pldlp_real(LD, what):
+    if LD.dtype.kind not in "fiub":
+        raise TypeError("%s: LD must be real, got %s" % (what, LD.dtype))
+    return LD.astype(np.float64, copy=False)
+
+
+def pldlp_l(LD, P=None):
+    """pldlp.js:225-304: the unit lower triangular factor L [..., N, N] (host side, leading axes of LD and P broadcast)"""
+    if P is None:
+        LD, P = LD
+    LD, P, _ = _pldlp_args(LD, P)
+    LD = _pldlp_real(LD, "pldlp_l(LD,P)")
+    N = LD.shape[-1]
+    lead = _pldlp_lead(LD.shape[:-2], P.shape[:-1])
+    L = np.tril(np.broadcast_to(LD, lead + (N, N)), -1)
+    neg = np.broadcast_to(P < 0, lead + (N,))
+    i = np.arange(1, N)
+    L[..., i, i - 1] = np.where(neg[..., 1:], 0.0, L[..., i, i - 1])
+    i = np.arange(N)
+    L[..., i, i] = 1.0
+    return L
+
+
+def pldlp_d(LD, P=None):
+    """pldlp.js:307-380: the block diagonal factor D [..., N, N] with its symmetric 2x2 blocks (host side)"""
+    if P is None:
+        LD, P = LD
+    LD, P, _ = _pldlp_args(LD, P)
+    LD = _pldlp_real(LD, "pldlp_d(LD,P)")
+    N = LD.shape[-1]
+    lead = _pldlp_lead(LD.shape[:-2], P.shape[:-1])
+    LDb = np.broadcast_to(LD, lead + (N, N))
+    neg = np.broadcast_to(P < 0, lead + (N,))
+    D = np.zeros(lead + (N, N))
+    i = np.arange(N)
+    D[..., i, i] = LDb[..., i, i]
+    i = np.arange(1, N)
+    off = np.where(neg[..., 1:], LDb[..., i, i - 1], 0.0)
+    D[..., i, i - 1] = off
+    D[..., i - 1, i] = off
+    return D
+
+
+def _pldlp_perm(P):
+    """pldlp.js:404-437: P [..., N] int32 with the complements undone, or the reference's error"""
+    N = P.shape[-1]
+    neg = P < 0
+    Q = np.where(neg, ~P, P)
+    rows = Q.reshape(-1, N)
+    ok = not (N and neg[..., 0].any()) and not (neg[..., 1:] & neg[..., :-1]).any() and \
+        bool(np.all(np.sort(rows, axis=1) == np.arange(N, dtype=np.int64)))
+    if ok:
+        return Q.astype(np.int32)
+    Pf = P.reshape(-1, N)
+    for b in range(Pf.shape[0] - 1, -1, -1):              # the reference's order: last matrix first, last row first
+        seen = np.zeros(N, dtype=bool)
+        for i in range(N - 1, -1, -1):
+            p = int(Pf[b, i])
+            if p < 0:
+                if not (0 < i) or Pf[b, i - 1] < 0:
+                    raise ValueError("pldlp_solve(LD,P,y): P is invalid.")
+                p = ~p
+            if not (0 <= p < N):
+                raise ValueError("pldlp_solve(LD,P,y): P contains out-of-bounds indices.")
+            if seen[p]:
+                raise ValueError("pldlp_solve(LD,P,y): P contains duplicate indices.")
+            seen[p] = True
+    raise AssertionError("unreachable")
+
+
+def pldlp_p(LD, P=None):
+    """pldlp.js:383-438: the row permutation [..., N] int32 with the 2x2 marks removed, after a complete check of P (host side)"""
+    if P is None:
+        LD, P = LD
+    LD, P, _ = _pldlp_args(LD, P)
+    _pldlp_lead(LD.shape[:-2], P.shape[:-1])
+    return _pldlp_perm(P)
+
+
+def pldlp_solve(LD, P, y=None, device=None):
+    """pldlp.js:519-604: x [..., N, J] with S x = y from pldlp_decomp's [LD, P]; also pldlp_solve([LD, P], y). Leading axes of LD,
+    P and y broadcast. P is checked completely on the host before any device work."""
+    if y is None:
+        if P is None:
+            raise ValueError("Assertion failed.")
+        y = P
+        LD, P = LD
+    LD, P, y = _pldlp_args(LD, P, y, with_y=True)
+    LD, y = _asarray(LD, "pldlp_solve(LD,P,y)"), _asarray(y, "pldlp_solve(LD,P,y)")
+    N, J = LD.shape[-1], y.shape[-1]
+    lead = _pldlp_lead(LD.shape[:-2], P.shape[:-1], y.shape[:-2])
+    _pldlp_perm(P)
+    X = np.empty(lead + (N, J))
+    h = _lib.handle(device)
+    for cnt, (oL, oP, oY), (sL, sP, sY), b0 in _bcast_groups_n(lead, [LD.shape[:-2], P.shape[:-1], y.shape[:-2]], [N * N, N, N * J]):
+        _ev_call(h.lib.nd4hip_dsytrs_bk_batched, h.ptr, cnt, N, J, _off(LD, oL), sL, _off(P, oP, 4), sP, _off(y, oY), sY, _off(X, b0 * N * J))
+    return X
