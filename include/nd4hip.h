@@ -421,6 +421,39 @@ int nd4hip_dgees_batched    (nd4hip_handle* h, int64_t batch, int64_t N, const d
 int nd4hip_dgeev_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* Lam, double* V);
 int nd4hip_dgeev_batched    (nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* Lam, double* V);
 
+/* ---- structure functions: transposition (NDArray.T on the last two axes), tril / triu (src/la/tri.js:23-42), diag / diag_mat
+ * (src/la/diag.js:23-88), permute_rows / permute_cols / unpermute_rows / unpermute_cols (src/la/permute.js:23-306) ----------
+ * Values are moved, never computed: every copied element keeps its 64 bits (NaN payloads, +-Infinity, -0, denormals), every
+ * filled element is +0.0. No output may overlap an input (the reference always returns a fresh array): ND4HIP_ERR_ARG.
+ * dtranspose: A [batch,M,N] -> B [batch,N,M], B[b,j,i] = A[b,i,j].
+ * dtri: A [batch,M,N] -> B [batch,M,N]; upper == 0 is tril, B = (i < j-k) ? +0.0 : A; upper != 0 is triu, B = (i > j-k) ? +0.0 : A;
+ * any int64 k.
+ * ddiag: A [batch,M,N] -> d [batch,L], L = min(M, M+offset, N, N-offset), d[b,i] = A[b, i+max(0,-offset), i+max(0,offset)];
+ * -M < offset < N, else ND4HIP_ERR_ARG.
+ * ddiagmat: d [batch,N] -> D [batch,N,N], written completely (zeros included).
+ * dpermute: A [batch,M,N], P [batch,L] int32 with L = M (cols == 0) or N (cols != 0) -> B [batch,M,N];
+ *   cols == 0, inverse == 0  permute_rows    B[i,:] = A[P[i],:]        cols != 0, inverse == 0  permute_cols    B[:,j] = A[:,P[j]]
+ *   cols == 0, inverse != 0  unpermute_rows  B[P[i],:] = A[i,:]        cols != 0, inverse != 0  unpermute_cols  B[:,P[j]] = A[:,j]
+ * strideA / strideP in elements between consecutive batch members, 0 = the operand is broadcast over the batch. P need not be a
+ * permutation: in the inverse forms the largest i with P[i] = k wins (the reference's later store) and rows / columns that no
+ * i names are +0.0, deterministically (a gather through an inverse map built with integer atomicMax; no scattered stores). An
+ * index outside [0, L) is never turned into an address: it raises a device flag, nothing is read or written for it, and the
+ * call returns ND4HIP_ERR_ARG with the reference's text, e.g. 'permute_rows(A,P): P.contains invalid indices.'; B is then
+ * unspecified and the handle stays usable. To decide that, BOTH forms of dpermute read the flag back: they synchronise the
+ * stream. The other four _dev forms enqueue only. */
+int nd4hip_dtranspose_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* B);
+int nd4hip_dtranspose_batched    (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* B);
+int nd4hip_dtri_batched_dev(nd4hip_handle* h, int upper, int64_t k, int64_t batch, int64_t M, int64_t N, const double* A, double* B);
+int nd4hip_dtri_batched    (nd4hip_handle* h, int upper, int64_t k, int64_t batch, int64_t M, int64_t N, const double* A, double* B);
+int nd4hip_ddiag_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t offset, const double* A, double* d);
+int nd4hip_ddiag_batched    (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t offset, const double* A, double* d);
+int nd4hip_ddiagmat_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* d, double* D);
+int nd4hip_ddiagmat_batched    (nd4hip_handle* h, int64_t batch, int64_t N, const double* d, double* D);
+int nd4hip_dpermute_batched_dev(nd4hip_handle* h, int cols, int inverse, int64_t batch, int64_t M, int64_t N, const double* A,
+                                int64_t strideA, const int32_t* P, int64_t strideP, double* B);
+int nd4hip_dpermute_batched    (nd4hip_handle* h, int cols, int inverse, int64_t batch, int64_t M, int64_t N, const double* A,
+                                int64_t strideA, const int32_t* P, int64_t strideP, double* B);
+
 /* ---- svd_decomp: replaces the output contract of src/la/svd.js:25 (= svd_dc.js:883-932) ----------
  * A [batch,M,N] -> U [batch,M,L], sv [batch,L] (>= 0, descending), V [batch,L,N] (rows = right
  * singular vectors), L = min(M,N); one-sided Jacobi with the reference's Jacobi post-processing

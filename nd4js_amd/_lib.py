@@ -63,6 +63,16 @@ SIGNATURES = {
     "nd4hip_dsytrs_bk_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_i64, ctypes.c_void_p, c_i64, c_dp, c_i64, c_dp]),
     "nd4hip_dsytrf_bk_tier": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_int]),
     "nd4hip_dsytrf_bk_limits": (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "nd4hip_dtranspose_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp]),
+    "nd4hip_dtranspose_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp]),
+    "nd4hip_dtri_batched_dev": (c_int, [ctypes.c_void_p, c_int, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp]),
+    "nd4hip_dtri_batched": (c_int, [ctypes.c_void_p, c_int, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp]),
+    "nd4hip_ddiag_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp]),
+    "nd4hip_ddiag_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp]),
+    "nd4hip_ddiagmat_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp]),
+    "nd4hip_ddiagmat_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp]),
+    "nd4hip_dpermute_batched_dev": (c_int, [ctypes.c_void_p, c_int, c_int, c_i64, c_i64, c_i64, c_dp, c_i64, ctypes.c_void_p, c_i64, c_dp]),
+    "nd4hip_dpermute_batched": (c_int, [ctypes.c_void_p, c_int, c_int, c_i64, c_i64, c_i64, c_dp, c_i64, ctypes.c_void_p, c_i64, c_dp]),
     "nd4hip_dgebrd_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp]),
     "nd4hip_dgebrd_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp]),
     "nd4hip_dgehrd_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),

@@ -82,6 +82,11 @@ static int (*p_dldltrf[2])(nd4hip_handle*, int64_t, int64_t, const double*, doub
 static int (*p_dldltrs[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t, double*);
 static int (*p_dsytrf_bk[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*, int32_t*, int);
 static int (*p_dsytrs_bk[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, int64_t, const int32_t*, int64_t, const double*, int64_t, double*);
+static int (*p_dtranspose[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, double*);
+static int (*p_dtri[2])(nd4hip_handle*, int, int64_t, int64_t, int64_t, int64_t, const double*, double*);
+static int (*p_ddiag[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, const double*, double*);
+static int (*p_ddiagmat[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*);
+static int (*p_dpermute[2])(nd4hip_handle*, int, int, int64_t, int64_t, int64_t, const double*, int64_t, const int32_t*, int64_t, double*);
 static int (*p_dpotrs[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t, double*);
 static trsm_fn p_dtrsm[2];
 static int (*p_malloc)(nd4hip_handle*, size_t, void**);
@@ -139,6 +144,11 @@ static int load_library(void) {
   SYM2(p_dldltrs, "nd4hip_dldltrs_batched");
   SYM2(p_dsytrf_bk, "nd4hip_dsytrf_bk_batched_ex");
   SYM2(p_dsytrs_bk, "nd4hip_dsytrs_bk_batched");
+  SYM2(p_dtranspose, "nd4hip_dtranspose_batched");
+  SYM2(p_dtri, "nd4hip_dtri_batched");
+  SYM2(p_ddiag, "nd4hip_ddiag_batched");
+  SYM2(p_ddiagmat, "nd4hip_ddiagmat_batched");
+  SYM2(p_dpermute, "nd4hip_dpermute_batched");
   SYM2(p_dqrls, "nd4hip_dqrls_batched");
   SYM2(p_dgeqp3, "nd4hip_dgeqp3_batched");
   SYM2(p_dgeqp3_full, "nd4hip_dgeqp3_full_batched");
@@ -811,6 +821,72 @@ static napi_value js_dsytrs_bk(napi_env env, napi_callback_info info) {
   FAIL_IF(p_dsytrs_bk[X.dev](g_handle, batch, N, J, (const double*)L.p, sL, (const int32_t*)P.p, sP, (const double*)Y.p, sY, (double*)X.p));
   return NULL;
 }
+/* structure functions (tri.js:23-42, diag.js:23-88, permute.js:23-306, NDArray.T): values are moved, never computed
+ * dtranspose_batched(batch, M, N, A, B)   B [batch,N,M] */
+static napi_value js_dtranspose(napi_env env, napi_callback_info info) {
+  ARGS(5, "dtranspose_batched");
+  int64_t batch, M, N; opnd A, B;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &M) || get_i64(env, a[2], &N) || F64(3, A) || F64(4, B)) return NULL;
+  NEED(batch >= 0 && M >= 0 && N >= 0 && (size_t)(batch * M * N) <= A.len && (size_t)(batch * M * N) <= B.len, "dtranspose_batched: buffer too small");
+  SAME_SIDE(A.dev == B.dev, "dtranspose_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dtranspose[A.dev](g_handle, batch, M, N, (const double*)A.p, (double*)B.p));
+  return NULL;
+}
+/* dtri_batched(upper, k, batch, M, N, A, B)   tril (upper = 0) / triu */
+static napi_value js_dtri(napi_env env, napi_callback_info info) {
+  ARGS(7, "dtri_batched");
+  int64_t upper, k, batch, M, N; opnd A, B;
+  if (get_i64(env, a[0], &upper) || get_i64(env, a[1], &k) || get_i64(env, a[2], &batch) || get_i64(env, a[3], &M) || get_i64(env, a[4], &N) ||
+      F64(5, A) || F64(6, B)) return NULL;
+  NEED(batch >= 0 && M >= 0 && N >= 0 && (size_t)(batch * M * N) <= A.len && (size_t)(batch * M * N) <= B.len, "dtri_batched: buffer too small");
+  SAME_SIDE(A.dev == B.dev, "dtri_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dtri[A.dev](g_handle, upper != 0, k, batch, M, N, (const double*)A.p, (double*)B.p));
+  return NULL;
+}
+/* ddiag_batched(batch, M, N, offset, A, d)   d [batch, min(M, M+offset, N, N-offset)] */
+static napi_value js_ddiag(napi_env env, napi_callback_info info) {
+  ARGS(6, "ddiag_batched");
+  int64_t batch, M, N, off; opnd A, d;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &M) || get_i64(env, a[2], &N) || get_i64(env, a[3], &off) || F64(4, A) || F64(5, d)) return NULL;
+  NEED(batch >= 0 && M >= 0 && N >= 0 && off > -M && off < N, "ddiag_batched: bad extent or offset");
+  {
+    int64_t L = M < N ? M : N;
+    if (M + off < L) L = M + off;
+    if (N - off < L) L = N - off;
+    NEED((size_t)(batch * M * N) <= A.len && (size_t)(batch * L) <= d.len, "ddiag_batched: buffer too small");
+  }
+  SAME_SIDE(A.dev == d.dev, "ddiag_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_ddiag[A.dev](g_handle, batch, M, N, off, (const double*)A.p, (double*)d.p));
+  return NULL;
+}
+/* ddiagmat_batched(batch, N, d, D)   D [batch,N,N] */
+static napi_value js_ddiagmat(napi_env env, napi_callback_info info) {
+  ARGS(4, "ddiagmat_batched");
+  int64_t batch, N; opnd d, D;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || F64(2, d) || F64(3, D)) return NULL;
+  NEED(batch >= 0 && N >= 0 && (size_t)(batch * N) <= d.len && (size_t)(batch * N * N) <= D.len, "ddiagmat_batched: buffer too small");
+  SAME_SIDE(d.dev == D.dev, "ddiagmat_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_ddiagmat[d.dev](g_handle, batch, N, (const double*)d.p, (double*)D.p));
+  return NULL;
+}
+/* dpermute_batched(cols, inverse, batch, M, N, A, strideA, P, strideP, B)   permute_rows / _cols, unpermute_rows / _cols */
+static napi_value js_dpermute(napi_env env, napi_callback_info info) {
+  ARGS(10, "dpermute_batched");
+  int64_t cols, inverse, batch, M, N, sA, sP; opnd A, P, B;
+  if (get_i64(env, a[0], &cols) || get_i64(env, a[1], &inverse) || get_i64(env, a[2], &batch) || get_i64(env, a[3], &M) || get_i64(env, a[4], &N) ||
+      F64(5, A) || get_i64(env, a[6], &sA) || I32(7, P) || get_i64(env, a[8], &sP) || F64(9, B)) return NULL;
+  NEED(batch >= 0 && M >= 0 && N >= 0 && sA >= 0 && sP >= 0, "dpermute_batched: negative extent");
+  NEED(batch == 0 || ((size_t)((batch - 1) * sA + M * N) <= A.len && (size_t)((batch - 1) * sP + (cols ? N : M)) <= P.len &&
+                      (size_t)(batch * M * N) <= B.len), "dpermute_batched: buffer too small");
+  SAME_SIDE(A.dev == P.dev && P.dev == B.dev, "dpermute_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dpermute[A.dev](g_handle, cols != 0, inverse != 0, batch, M, N, (const double*)A.p, sA, (const int32_t*)P.p, sP, (double*)B.p));
+  return NULL;
+}
 /* dldltrs_batched(batch, N, J, LD, strideLD, Y, strideY, X)   (ldl_solve, ldl.js:133-201) */
 static napi_value js_dldltrs(napi_env env, napi_callback_info info) {
   ARGS(8, "dldltrs_batched");
@@ -972,6 +1048,11 @@ static napi_value init(napi_env env, napi_value exports) {
     {"dldltrs_batched", NULL, js_dldltrs, NULL, NULL, NULL, napi_default, NULL},
     {"dsytrf_bk_batched", NULL, js_dsytrf_bk, NULL, NULL, NULL, napi_default, NULL},
     {"dsytrs_bk_batched", NULL, js_dsytrs_bk, NULL, NULL, NULL, napi_default, NULL},
+    {"dtranspose_batched", NULL, js_dtranspose, NULL, NULL, NULL, napi_default, NULL},
+    {"dtri_batched", NULL, js_dtri, NULL, NULL, NULL, napi_default, NULL},
+    {"ddiag_batched", NULL, js_ddiag, NULL, NULL, NULL, napi_default, NULL},
+    {"ddiagmat_batched", NULL, js_ddiagmat, NULL, NULL, NULL, napi_default, NULL},
+    {"dpermute_batched", NULL, js_dpermute, NULL, NULL, NULL, napi_default, NULL},
     {"dev_alloc", NULL, js_dev_alloc, NULL, NULL, NULL, napi_default, NULL},
     {"dev_free", NULL, js_dev_free, NULL, NULL, NULL, napi_default, NULL},
     {"dev_upload", NULL, js_dev_upload, NULL, NULL, NULL, napi_default, NULL},

@@ -498,6 +498,69 @@ extern "C" int nd4hip_dsytrs_bk_batched(nd4hip_handle* h, int64_t batch, int64_t
   return run_host(h, batch, ops, fn);
 }
 
+// ---- structure functions (tri.js:23-42, diag.js:23-88, permute.js:23-306): pure data movement, sharded like every batched call
+extern "C" int nd4hip_dtranspose_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* B) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dtranspose_batched: NULL handle");
+  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dtranspose_batched: negative extent");
+  if (batch == 0 || M == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(A && B, "nd4hip_dtranspose_batched: NULL pointer");
+  ND4_CHECK_ARG(!nd4_struct_overlap(A, batch * M * N, B, batch * M * N), "nd4hip_dtranspose_batched: B must not overlap A");
+  std::vector<Operand> ops{in_op(A, M * N, M * N), out_op(B, M * N)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_dtranspose_batched_dev(hd, nb, M, N, P(d, 0), P(d, 1)); };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_dtri_batched(nd4hip_handle* h, int upper, int64_t k, int64_t batch, int64_t M, int64_t N, const double* A, double* B) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dtri_batched: NULL handle");
+  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dtri_batched: negative extent");
+  if (batch == 0 || M == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(A && B, "nd4hip_dtri_batched: NULL pointer");
+  ND4_CHECK_ARG(!nd4_struct_overlap(A, batch * M * N, B, batch * M * N), "nd4hip_dtri_batched: B must not overlap A");
+  std::vector<Operand> ops{in_op(A, M * N, M * N), out_op(B, M * N)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_dtri_batched_dev(hd, upper, k, nb, M, N, P(d, 0), P(d, 1)); };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_ddiag_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t offset, const double* A, double* dg) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_ddiag_batched: NULL handle");
+  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_ddiag_batched: negative extent");
+  ND4_CHECK_ARG(offset > -M && offset < N, "nd4hip_ddiag_batched: offset=%lld out of the shape [%lld,%lld]", (long long)offset, (long long)M,
+                (long long)N);
+  const int64_t L = std::min(std::min(M, M + offset), std::min(N, N - offset));
+  if (batch == 0 || L <= 0) return 0;
+  ND4_CHECK_ARG(A && dg, "nd4hip_ddiag_batched: NULL pointer");
+  ND4_CHECK_ARG(!nd4_struct_overlap(A, batch * M * N, dg, batch * L), "nd4hip_ddiag_batched: d must not overlap A");
+  std::vector<Operand> ops{in_op(A, M * N, M * N), out_op(dg, L)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_ddiag_batched_dev(hd, nb, M, N, offset, P(d, 0), P(d, 1)); };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_ddiagmat_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* dg, double* Dm) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_ddiagmat_batched: NULL handle");
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_ddiagmat_batched: negative extent");
+  if (batch == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(dg && Dm, "nd4hip_ddiagmat_batched: NULL pointer");
+  ND4_CHECK_ARG(!nd4_struct_overlap(dg, batch * N, Dm, batch * N * N), "nd4hip_ddiagmat_batched: D must not overlap d");
+  std::vector<Operand> ops{in_op(dg, N, N), out_op(Dm, N * N)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_ddiagmat_batched_dev(hd, nb, N, P(d, 0), P(d, 1)); };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_dpermute_batched(nd4hip_handle* h, int cols, int inverse, int64_t batch, int64_t M, int64_t N, const double* A,
+                                       int64_t strideA, const int32_t* Pv, int64_t strideP, double* B) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dpermute_batched: NULL handle");
+  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dpermute_batched: negative extent");
+  const int64_t L = cols ? N : M;
+  ND4_CHECK_ARG((strideA == 0 || strideA >= M * N) && (strideP == 0 || strideP >= L),
+                "nd4hip_dpermute_batched: a stride must be 0 or at least the size of one operand");
+  if (batch == 0 || M == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(A && Pv && B, "nd4hip_dpermute_batched: NULL pointer");
+  ND4_CHECK_ARG(!nd4_struct_overlap(A, (strideA ? (batch - 1) * strideA : 0) + M * N, B, batch * M * N),
+                "nd4hip_dpermute_batched: B must not overlap A");
+  // the indices are checked on the device, where they are used: a bad one fails its chunk with the reference's text
+  std::vector<Operand> ops{in_op(A, M * N, strideA), in_op(Pv, L, strideP, 4), out_op(B, M * N)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
+    return nd4hip_dpermute_batched_dev(hd, cols, inverse, nb, M, N, P(d, 0), strideA, static_cast<const int32_t*>(d[1]), strideP, P(d, 2));
+  };
+  return run_host(h, batch, ops, fn);
+}
+
 // ---- bidiag_decomp (bidiag.js:245-319), hessenberg_decomp (hessenberg.js:89-115)
 extern "C" int nd4hip_dgebrd_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* U, double* B, double* V) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgebrd_batched: NULL handle");

@@ -157,6 +157,10 @@ int nd4_gebak(nd4hip_handle* h, int64_t batch, int64_t N, const double* D, const
 int nd4_hseqr(nd4hip_handle* h, int64_t batch, int64_t N, const double* U, const double* H, double* Q, double* T, int* flags, int* sweeps,
               int tier);
 int64_t nd4_hseqr_chunk(int64_t N);
+// structure functions (struct.hip): the reference's name of a dpermute mode, and whether an input of in_elems doubles overlaps an
+// output of out_elems doubles
+const char* nd4_permute_name(int cols, int inverse);
+bool nd4_struct_overlap(const void* in, int64_t in_elems, const void* out, int64_t out_elems);
 int nd4_gesvdj(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A,
                double* U, double* sv, double* V, int* sweeps_out, double* offnorm_out);
 

@@ -726,3 +726,97 @@ def eigenvals(A):
     h = _h(A)
     _ev_call(h.lib.nd4hip_dgeev_batched_dev, h.ptr, _batch(lead), N, _p(A), _p(L), None)
     return L
+
+
+# ---- structure functions (csrc/struct.hip): values are moved, never computed; nothing leaves the device ----
+def _struct_call(fn, *args):
+    from .la import _arg_error
+    try:
+        _lib.check(fn(*args))
+    except _lib.Nd4HipError as e:
+        raise _arg_error(e)
+
+
+def transpose(A):
+    """the last two axes swapped (NDArray.T); fewer than two axes: A itself"""
+    _chk(A, "A")
+    if A.dim() < 2:
+        return A
+    M, N = A.shape[-2:]
+    B = torch.empty(tuple(A.shape[:-2]) + (N, M), dtype=torch.float64, device=A.device)
+    h = _h(A)
+    _struct_call(h.lib.nd4hip_dtranspose_batched_dev, h.ptr, _batch(A.shape[:-2]), M, N, _p(A), _p(B))
+    return B
+
+
+def _tri(upper, A, k):
+    from .la import _tri_k
+    _chk(A, "A")
+    if A.dim() < 2:
+        raise ValueError("Input must be at least 2D.")
+    M, N = A.shape[-2:]
+    B = torch.empty_like(A)
+    h = _h(A)
+    _struct_call(h.lib.nd4hip_dtri_batched_dev, h.ptr, upper, _tri_k(k), _batch(A.shape[:-2]), M, N, _p(A), _p(B))
+    return B
+
+
+def tril(A, k=0):
+    return _tri(0, A, k)
+
+
+def triu(A, k=0):
+    return _tri(1, A, k)
+
+
+def diag(A, offset=0):
+    from .la import _diag_args
+    _chk(A, "A")
+    M, N, L = _diag_args(tuple(A.shape), offset)
+    d = torch.empty(tuple(A.shape[:-2]) + (L,), dtype=torch.float64, device=A.device)
+    h = _h(A)
+    _struct_call(h.lib.nd4hip_ddiag_batched_dev, h.ptr, _batch(A.shape[:-2]), M, N, int(offset), _p(A), _p(d))
+    return d
+
+
+def diag_mat(d):
+    from .la import _diag_mat_args
+    _chk(d, "d")
+    N = _diag_mat_args(tuple(d.shape))
+    D = torch.empty(tuple(d.shape) + (N,), dtype=torch.float64, device=d.device)
+    h = _h(d)
+    _struct_call(h.lib.nd4hip_ddiagmat_batched_dev, h.ptr, _batch(d.shape[:-1]), N, _p(d), _p(D))
+    return D
+
+
+def _permute(cols, inverse, A, P):
+    """la._permute on device tensors: the same shape rule (leading axes of A and P broadcast against each other), one call per
+    stride-0 / dense run. A bad index raises ValueError with the reference's text (the call reads one flag word back)."""
+    from .la import _permute_plan
+    name = ("unpermute_" if inverse else "permute_") + ("cols" if cols else "rows")
+    _chk(A, "A")
+    if not (isinstance(P, torch.Tensor) and P.is_cuda and P.is_contiguous()):
+        raise TypeError("P must be a contiguous CUDA tensor")
+    M, N, L, lead, groups = _permute_plan(name, tuple(A.shape), tuple(P.shape), P.dtype == torch.int32, cols)
+    B = torch.empty(lead + (M, N), dtype=torch.float64, device=A.device)
+    h = _h(A)
+    for cnt, (oA, oP), (sA, sP), b0 in groups:
+        _struct_call(h.lib.nd4hip_dpermute_batched_dev, h.ptr, cols, inverse, cnt, M, N, ctypes.c_void_p(A.data_ptr() + 8 * oA), sA,
+                     ctypes.c_void_p(P.data_ptr() + 4 * oP), sP, ctypes.c_void_p(B.data_ptr() + 8 * b0 * M * N))
+    return B
+
+
+def permute_rows(A, P):
+    return _permute(0, 0, A, P)
+
+
+def permute_cols(A, P):
+    return _permute(1, 0, A, P)
+
+
+def unpermute_rows(A, P):
+    return _permute(0, 1, A, P)
+
+
+def unpermute_cols(A, P):
+    return _permute(1, 1, A, P)

@@ -100,6 +100,24 @@ class DeviceNDArray {
     }
     return this._host;
   }
+  /* NDArray.T (nd_array.js): a new device array with the last two axes swapped, transposed on the device (csrc/struct.hip);
+   * fewer than two axes: this array itself. float64 only. */
+  static transposedShape(shape, dtype) {          // the rules of .T without a device: null = the array itself
+    const nd_ = shape.length;
+    if (nd_ < 2) return null;
+    if (dtype !== 'float64') throw new Error(`nd4hip.T: ${dtype} device arrays are not accelerated.`);
+    const out = Int32Array.from(shape);
+    out[nd_ - 2] = shape[nd_ - 1]; out[nd_ - 1] = shape[nd_ - 2];
+    return out;
+  }
+  get T() {
+    const nd_ = this.ndim, shape = DeviceNDArray.transposedShape(this.shape, this.dtype);
+    if (shape === null) return this;
+    const M = this.shape[nd_ - 2], N = this.shape[nd_ - 1];
+    const B = new DevBuf(this._buf.length, Float64Array);
+    native().dtranspose_batched(this._buf.length / (M * N || 1), M, N, this._buf.view(0), B.view(0));
+    return new DeviceNDArray(shape, B);
+  }
   toHost(NDA) { return new (NDA || NDArray)(Int32Array.from(this.shape), this.data); }
   dispose() { this._buf.free(); }                // optional: dropped arrays are freed by the GC finalizer
 }
@@ -1007,6 +1025,72 @@ function makeLa(NDA, fallback, SolveError, Complex) {
     return wrapZ('eigenvals', dev, Array.from(A.shape.subarray(0, nd_ - 1)), L);
   };
 
+  /* ---- structure functions: tril / triu (tri.js:23-42), diag / diag_mat (diag.js:23-88), permute_rows / permute_cols /
+   * unpermute_rows / unpermute_cols (permute.js:23-306), csrc/struct.hip. Values are moved, never computed. ---- */
+  // a device argument is never handed to the host module: its function would read `.data`, a silent download of the whole array
+  const structFallback = (name, args) => { if (fallback && fallback[name] && !args.some(isDev)) return fallback[name](...args); throw new Error(`nd4hip.${name}: dtype is not accelerated.`); };
+  // i < j - k is floor(k) < j - i and i > j - k is ceil(k) > j - i for integer i, j: any number k maps to an integer; NaN never cuts
+  const MAXK = Math.pow(2, 53);
+  const triK = (upper, k) => { k = +k; if (k !== k) return upper ? -MAXK : MAXK; return Math.max(-MAXK, Math.min(MAXK, upper ? Math.ceil(k) : Math.floor(k))); };
+  const tri = (upper, name) => function (m, k = 0) {
+    m = asarray(m);
+    if (m.ndim < 2) throw new Error('Input must be at least 2D.');
+    if (!f64Only(m)) return structFallback(name, [m, k]);
+    const nd_ = m.ndim, M = m.shape[nd_ - 2], N = m.shape[nd_ - 1], batch = prod(m.shape, 0, nd_ - 2), dev = isDev(m), temps = [];
+    const B = alloc(dev, batch * M * N);
+    try { native().dtri_batched(upper, triK(upper, k), batch, M, N, view(opF64(m, dev, temps), 0), view(B, 0)); } finally { release(temps); }
+    return wrap(dev, m.shape, B);
+  };
+  la.tril = tri(0, 'tril'); Object.defineProperty(la.tril, 'name', {value: 'tril'});
+  la.triu = tri(1, 'triu'); Object.defineProperty(la.triu, 'name', {value: 'triu'});
+  la.diag = function diag(A, offset = 0) {
+    A = asarray(A);
+    if (A.ndim < 2) throw new Error(`diag(A, offset): A.ndim=${A.ndim} is less than 2.`);
+    const nd_ = A.ndim, M = A.shape[nd_ - 2], N = A.shape[nd_ - 1];
+    if (!(offset > -M && offset < +N)) throw new Error(`diag(A, offset): offset=${offset} out of A.shape=[undefined].`);   // (the reference prints the shape of A.data)
+    if (!f64Only(A) || !Number.isInteger(+offset)) return structFallback('diag', [A, offset]);
+    const L = Math.min(M, M + offset, N, N - offset), batch = prod(A.shape, 0, nd_ - 2), dev = isDev(A), temps = [];
+    const d = alloc(dev, batch * L);
+    try { native().ddiag_batched(batch, M, N, +offset, view(opF64(A, dev, temps), 0), view(d, 0)); } finally { release(temps); }
+    return wrap(dev, [...A.shape.subarray(0, nd_ - 2), L], d);
+  };
+  la.diag_mat = function diag_mat(diag) {
+    diag = asarray(diag);
+    if (diag.ndim < 1) throw new Error(`diag_mat(diag): diag.ndim=${diag.ndim} is less than 1.`);
+    const N = diag.shape[diag.ndim - 1];
+    if (N <= 0) throw new Error('Assertion Failed!');
+    if (!f64Only(diag)) return structFallback('diag_mat', [diag]);
+    const batch = prod(diag.shape, 0, diag.ndim - 1), dev = isDev(diag), temps = [];
+    const D = alloc(dev, batch * N * N);
+    try { native().ddiagmat_batched(batch, N, view(opF64(diag, dev, temps), 0), view(D, 0)); } finally { release(temps); }
+    return wrap(dev, [...diag.shape, N], D);
+  };
+  const permute = (cols, inverse, name) => {
+    const f = function (A, P) {
+      A = asarray(A); if (A.ndim < 2) throw new Error(`${name}(A,P): A.ndim must be at least 2.`);
+      P = asarray(P); if (P.ndim < 1) throw new Error(`${name}(A,P): P.ndim must be at least 1.`);
+      if (!f64Only(A) || dtypeOf(P) !== 'int32') return structFallback(name, [A, P]);
+      const M = A.shape[A.ndim - 2], N = A.shape[A.ndim - 1], L = cols ? N : M;
+      if (L !== P.shape[P.ndim - 1]) throw new Error(`${name}(A,P): A.shape[${cols ? -1 : -2}] and P.shape[-1] must match.`);
+      const lA = Array.from(A.shape.subarray(0, A.ndim - 2)), lP = Array.from(P.shape.subarray(0, P.ndim - 1));
+      const lead = bcastLead([lA, lP], `${name}(A,P): A and P not broadcast-compatible.`);      // max(A.ndim, P.ndim + 1) axes in all
+      const dev = isDev(A) || isDev(P), temps = [];
+      const B = alloc(dev, lead.reduce((a, b) => a * b, 1) * M * N);
+      try {
+        const Ad = opF64(A, dev, temps), Pd = opI32(P, dev, temps);
+        for (const [cnt, [oA, oP], [sA, sP], b0] of bcastGroupsN(lead, [lA, lP], [M * N, L]))
+          native().dpermute_batched(cols, inverse, cnt, M, N, view(Ad, oA), sA, view(Pd, oP), sP, view(B, b0 * M * N));
+      } finally { release(temps); }
+      return wrap(dev, [...lead, M, N], B);
+    };
+    Object.defineProperty(f, 'name', {value: name});
+    return f;
+  };
+  la.permute_rows = permute(0, 0, 'permute_rows');
+  la.permute_cols = permute(1, 0, 'permute_cols');
+  la.unpermute_rows = permute(0, 1, 'unpermute_rows');
+  la.unpermute_cols = permute(1, 1, 'unpermute_cols');
+
   // complex128 device arrays are accepted by matmul2 / matmul only: every other function refuses them before it looks at the
   // buffer (which holds 2n doubles, not n float64 entries)
   const complexOk = new Set(['matmul2', 'matmul', 'eigen_balance_post', '_chain_plan', 'to_device', 'to_host', 'synchronize', 'profile_enable', 'profile_last']);
@@ -1045,6 +1129,8 @@ function estimatedWork(name, args) {
 // schur_decomp, eigen, eigenvals of ONE host matrix: the host module's single thread wins up to N = 128 (64: 6.2 ms against
 // 10.2 ms through the device with copies, 128: 40.5 against 50.8), the device from 256 on (429 against 226 ms); DESIGN.md §4.12
 const SCHUR_ROUTED = new Set(['schur_decomp', 'eigen', 'eigenvals']), SCHUR_HOST_MAX_N = 128;
+// the structure functions run on the device only for device-resident arguments (a host array would pay two PCIe crossings to be copied)
+const STRUCT_ROUTED = new Set(['tril', 'triu', 'diag', 'diag_mat', 'permute_rows', 'permute_cols', 'unpermute_rows', 'unpermute_cols']);
 
 /** Patch a loaded nd4js instance in place: the hot-path functions run on the GPU. Returns nd.
  *  opts.minWork (default 0 = off): a call whose estimated work (flops: 2 I K J for products, M N min(M, N) per matrix for
@@ -1069,7 +1155,10 @@ function install(nd, opts) {
                     rank: nd.la.rank, lstsq: nd.la.lstsq, norm: nd.la.norm,
                     schur_eigenvals: nd.la.schur_eigenvals, schur_eigen: nd.la.schur_eigen,
                     eigen_balance_pre: nd.la.eigen_balance_pre, eigen_balance_post: nd.la.eigen_balance_post,
-                    schur_decomp: nd.la.schur_decomp, eigen: nd.la.eigen, eigenvals: nd.la.eigenvals};
+                    schur_decomp: nd.la.schur_decomp, eigen: nd.la.eigen, eigenvals: nd.la.eigenvals,
+                    tril: nd.la.tril, triu: nd.la.triu, diag: nd.la.diag, diag_mat: nd.la.diag_mat,
+                    permute_rows: nd.la.permute_rows, permute_cols: nd.la.permute_cols,
+                    unpermute_rows: nd.la.unpermute_rows, unpermute_cols: nd.la.unpermute_cols};
   const acc = makeLa(nd.NDArray, original, nd.la.SingularMatrixSolveError || SingularMatrixSolveError, (nd.dt && nd.dt.Complex128Array) || null);
   const target = Object.isFrozen(nd.la) || !Object.getOwnPropertyDescriptor(nd.la, 'matmul2').writable ? null : nd.la;
   const patched = target || Object.create(nd.la);
@@ -1080,6 +1169,15 @@ function install(nd, opts) {
         const onHost = !(A instanceof acc.DeviceNDArray);
         if (onHost && single && s[s.length - 1] <= SCHUR_HOST_MAX_N) return original[k].apply(nd.la, args);
         return onHost && minWork && estimatedWork(k, args) < minWork ? original[k].apply(nd.la, args) : acc[k](...args);
+      };
+      Object.defineProperty(f, 'name', {value: k});
+      return f;
+    }
+    if (STRUCT_ROUTED.has(k) && typeof original[k] === 'function') {
+      // pure data movement: a call without a device argument is the host module's own, untouched (every dtype, whatever minWork
+      // says); a device argument keeps the chain on the device
+      const f = function (...args) {
+        return args.some(x => x instanceof acc.DeviceNDArray) ? acc[k](...args) : original[k].apply(nd.la, args);
       };
       Object.defineProperty(f, 'name', {value: k});
       return f;
