@@ -454,6 +454,24 @@ int nd4hip_dpermute_batched_dev(nd4hip_handle* h, int cols, int inverse, int64_t
 int nd4hip_dpermute_batched    (nd4hip_handle* h, int cols, int inverse, int64_t batch, int64_t M, int64_t N, const double* A,
                                 int64_t strideA, const int32_t* P, int64_t strideP, double* B);
 
+/* ---- strided N-d copy: NDArray.sliceElems / transpose(...axes) (src/nd_array.js:375-436, 531-642), concat (src/concat.js) and
+ * stack (src/stack.js) on device arrays ----------
+ * For every index vector i of the box shape[0..ndim):  dst[dst_off + sum_d i_d dst_strides[d]] = src[src_off + sum_d i_d src_strides[d]].
+ * Elements are opaque words of elem_bytes = 4 or 8 bytes, moved as integers: every bit is kept. Offsets and strides are in
+ * elements; strides are signed (a negative stride is a reversed slice) and may be 0 where the extent is 1. ndim = 0 copies one
+ * element. complex128 is a box with one more innermost axis of two 8-byte words. src_len / dst_len are the element counts of
+ * the two allocations: before any launch the lowest and the highest element that each side reaches are computed, and the call
+ * returns ND4HIP_ERR_ARG if either leaves [0, len), if an extent is < 1, if ndim is not in 0..8, if elem_bytes is neither 4 nor 8, or
+ * if the byte ranges reached on the two sides intersect (the reference always returns a fresh array, and the tiled path reads
+ * what another workgroup may have written). Nothing is written then and the handle stays usable. The call enqueues on the
+ * handle's stream and does not synchronise; there is no flag to read back. nd4hip_profile_last reports it as "gather_nd" with
+ * 2 elem_bytes count bytes. The axes should come in the order of dst (dst_strides descending, innermost last) and reduced
+ * (extent-1 axes dropped, mergeable neighbours merged): the kernels are chosen from the box as given.
+ * There is no host-pointer form: a host array would cross PCIe twice only to be copied; slice it on the host. */
+int nd4hip_gather_nd_dev(nd4hip_handle* h, int elem_bytes, int ndim, const int64_t* shape,
+                         const void* src, int64_t src_len, int64_t src_off, const int64_t* src_strides,
+                         void* dst, int64_t dst_len, int64_t dst_off, const int64_t* dst_strides);
+
 /* ---- svd_decomp: replaces the output contract of src/la/svd.js:25 (= svd_dc.js:883-932) ----------
  * A [batch,M,N] -> U [batch,M,L], sv [batch,L] (>= 0, descending), V [batch,L,N] (rows = right
  * singular vectors), L = min(M,N); one-sided Jacobi with the reference's Jacobi post-processing

@@ -92,6 +92,8 @@ static trsm_fn p_dtrsm[2];
 static int (*p_malloc)(nd4hip_handle*, size_t, void**);
 static int (*p_free)(nd4hip_handle*, void*);
 static int (*p_h2d)(nd4hip_handle*, void*, const void*, size_t);
+static int (*p_gather_nd)(nd4hip_handle*, int, int, const int64_t*, const void*, int64_t, int64_t, const int64_t*, void*, int64_t, int64_t,
+                         const int64_t*);
 static int (*p_d2h)(nd4hip_handle*, void*, const void*, size_t);
 static int (*p_sync)(nd4hip_handle*);
 static int (*p_prof_enable)(nd4hip_handle*, int);
@@ -172,6 +174,7 @@ static int load_library(void) {
   SYM2(p_dsvdls, "nd4hip_dsvdls_batched");
   SYM2(p_dtrsm, "nd4hip_dtrsm_batched");
 #undef SYM2
+  SYM(p_gather_nd, "nd4hip_gather_nd_dev");
   SYM(p_svd_info, "nd4hip_dgesvdj_last_info");
   SYM(p_malloc, "nd4hip_malloc");
   SYM(p_free, "nd4hip_free");
@@ -887,6 +890,33 @@ static napi_value js_dpermute(napi_env env, napi_callback_info info) {
   FAIL_IF(p_dpermute[A.dev](g_handle, cols != 0, inverse != 0, batch, M, N, (const double*)A.p, sA, (const int32_t*)P.p, sP, (double*)B.p));
   return NULL;
 }
+/* up to 8 numbers of a JS array */
+static int get_i64_list(napi_env env, napi_value v, int64_t* out, uint32_t* n) {
+  bool is_arr = false;
+  napi_is_array(env, v, &is_arr);
+  if (!is_arr || napi_get_array_length(env, v, n) != napi_ok) { napi_throw_type_error(env, "ND4HIP", "expected an array of numbers"); return -1; }
+  if (*n > 8) { napi_throw_range_error(env, "ND4HIP", "gather_nd: more than 8 axes"); return -1; }
+  for (uint32_t i = 0; i < *n; i++) {
+    napi_value e;
+    if (napi_get_element(env, v, i, &e) != napi_ok || get_i64(env, e, &out[i])) return -1;
+  }
+  return 0;
+}
+/* gather_nd(elemBytes, shape, src, srcOff, srcStrides, dst, dstOff, dstStrides): the strided N-d copy of sliceElems, transpose(...axes),
+ * concat and stack; src and dst are device views, their lengths are what the library checks the box against. Device only. */
+static napi_value js_gather_nd(napi_env env, napi_callback_info info) {
+  ARGS(8, "gather_nd");
+  int64_t eb, so, dof, shape[8], ss[8], ds[8]; uint32_t nd = 0, ns = 0, nt = 0; opnd S, D;
+  if (get_i64(env, a[0], &eb) || get_i64_list(env, a[1], shape, &nd) || get_i64(env, a[3], &so) || get_i64_list(env, a[4], ss, &ns) ||
+      get_i64(env, a[6], &dof) || get_i64_list(env, a[7], ds, &nt)) return NULL;
+  NEED(eb == 4 || eb == 8, "gather_nd: elemBytes must be 4 or 8");
+  NEED(ns == nd && nt == nd, "gather_nd: shape and strides must have one length");
+  if (get_op(env, a[2], eb == 8 ? napi_float64_array : napi_int32_array, &S) || get_op(env, a[5], eb == 8 ? napi_float64_array : napi_int32_array, &D)) return NULL;
+  if (!(S.dev == 1 && D.dev == 1)) { napi_throw_type_error(env, "ND4HIP", "gather_nd: device views only (there is no host-pointer form)"); return NULL; }
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_gather_nd(g_handle, (int)eb, (int)nd, shape, S.p, (int64_t)S.len, so, ss, D.p, (int64_t)D.len, dof, ds));
+  return NULL;
+}
 /* dldltrs_batched(batch, N, J, LD, strideLD, Y, strideY, X)   (ldl_solve, ldl.js:133-201) */
 static napi_value js_dldltrs(napi_env env, napi_callback_info info) {
   ARGS(8, "dldltrs_batched");
@@ -1053,6 +1083,7 @@ static napi_value init(napi_env env, napi_value exports) {
     {"ddiag_batched", NULL, js_ddiag, NULL, NULL, NULL, napi_default, NULL},
     {"ddiagmat_batched", NULL, js_ddiagmat, NULL, NULL, NULL, napi_default, NULL},
     {"dpermute_batched", NULL, js_dpermute, NULL, NULL, NULL, napi_default, NULL},
+    {"gather_nd", NULL, js_gather_nd, NULL, NULL, NULL, napi_default, NULL},
     {"dev_alloc", NULL, js_dev_alloc, NULL, NULL, NULL, napi_default, NULL},
     {"dev_free", NULL, js_dev_free, NULL, NULL, NULL, napi_default, NULL},
     {"dev_upload", NULL, js_dev_upload, NULL, NULL, NULL, napi_default, NULL},

@@ -737,8 +737,11 @@ def _struct_call(fn, *args):
         raise _arg_error(e)
 
 
-def transpose(A):
-    """the last two axes swapped (NDArray.T); fewer than two axes: A itself"""
+def transpose(A, *axes, pairs=False):
+    """no axes: the last two axes swapped (NDArray.T); fewer than two axes: A itself. With axes: NDArray.transpose(...axes), any
+    permutation of the axes (csrc/gather.hip), also of int32 tensors and, with pairs=True, of complex128 stored as float64 [..., 2]."""
+    if axes or pairs:
+        return _transpose_axes(A, axes, pairs)
     _chk(A, "A")
     if A.dim() < 2:
         return A
@@ -820,3 +823,115 @@ def unpermute_rows(A, P):
 
 def unpermute_cols(A, P):
     return _permute(1, 1, A, P)
+
+
+# ---- slices, axis permutations, concat and stack (csrc/gather.hip): one strided N-d copy, planned by la._*_plan ----
+_GATHER_BYTES = {torch.float64: 8, torch.int32: 4}
+
+
+def _chk_g(t, name, pairs=False):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in _GATHER_BYTES and t.is_contiguous()):
+        raise TypeError("%s must be a contiguous float64 or int32 CUDA tensor" % name)
+    if pairs and not (t.dtype == torch.float64 and t.dim() >= 1 and t.shape[-1] == 2):
+        raise TypeError("%s must be float64 [..., 2] (complex128 as pairs)" % name)
+    return t
+
+
+def strided_copy(dst, dst_off, dst_strides, src, src_off, src_strides, shape):
+    """dst.flat[dst_off + sum i_d dst_strides[d]] = src.flat[src_off + sum i_d src_strides[d]] for every i of the box `shape`
+    (nd4hip_gather_nd_dev as it is: at most 8 axes, offsets and strides in elements, the box inside both tensors, the two sides
+    disjoint; otherwise ValueError and nothing is written). Enqueues on the current stream."""
+    _chk_g(src, "src")
+    _chk_g(dst, "dst")
+    if src.dtype != dst.dtype or src.device != dst.device:
+        raise TypeError("src and dst must have one dtype and one device")
+    nd = len(shape)
+    if not (len(src_strides) == nd and len(dst_strides) == nd):
+        raise ValueError("shape and strides must have one length")
+    arr = ctypes.c_int64 * max(nd, 1)
+    h = _h(src)
+    _struct_call(h.lib.nd4hip_gather_nd_dev, h.ptr, _GATHER_BYTES[src.dtype], nd, arr(*[int(s) for s in shape]),
+                 _p(src), src.numel(), int(src_off), arr(*[int(s) for s in src_strides]),
+                 _p(dst), dst.numel(), int(dst_off), arr(*[int(s) for s in dst_strides]))
+    return dst
+
+
+def _gather(dst, dst_off, dst_strides, src, src_off, src_strides, shape, pairs):
+    """strided_copy of a planned box: complex pairs become one more innermost axis, the box is reduced (la._reduce_box) and what
+    exceeds 8 axes is a loop of launches"""
+    from .la import _reduce_box
+    shape, ss, ds = list(shape), list(src_strides), list(dst_strides)
+    if pairs:
+        shape, ss, ds = shape + [2], [2 * s for s in ss] + [1], [2 * s for s in ds] + [1]
+        src_off, dst_off = 2 * src_off, 2 * dst_off
+    shape, ss, ds, loop = _reduce_box(shape, ss, ds)
+    for so, do in loop:
+        strided_copy(dst, dst_off + do, ds, src, src_off + so, ss, shape)
+    return dst
+
+
+def _plain(shape, pairs):
+    return tuple(shape[:-1]) if pairs else tuple(shape)
+
+
+def _fresh(like, shape, pairs):
+    return torch.empty(tuple(shape) + ((2,) if pairs else ()), dtype=like.dtype, device=like.device)
+
+
+def slice_elems(A, *slices, pairs=False):
+    """NDArray.sliceElems on a device tensor: a fresh tensor. pairs=True: A is complex128 stored as float64 [..., 2] and the
+    slices address A.shape[:-1]."""
+    from .la import _c_strides, _slice_plan
+    _chk_g(A, "A", pairs)
+    out_shape, off, strides = _slice_plan(_plain(A.shape, pairs), list(slices))
+    B = _fresh(A, out_shape, pairs)
+    return _gather(B, 0, _c_strides(out_shape), A, off, strides, out_shape, pairs)
+
+
+def _transpose_axes(A, axes, pairs):
+    from .la import _c_strides, _transpose_plan
+    _chk_g(A, "A", pairs)
+    out_shape, strides = _transpose_plan(_plain(A.shape, pairs), axes)
+    B = _fresh(A, out_shape, pairs)
+    return _gather(B, 0, _c_strides(out_shape), A, 0, strides, out_shape, pairs)
+
+
+def reshape(A, *shape, pairs=False):
+    """NDArray.reshape: a view of the same storage (no kernel runs); one entry may be -1"""
+    from .la import _reshape_shape
+    _chk_g(A, "A", pairs)
+    plain = _plain(A.shape, pairs)
+    new_shape = _reshape_shape(plain, _batch(plain), shape)
+    return A.view(tuple(new_shape) + ((2,) if pairs else ()))
+
+
+def _concat(fn, plan, axis, tensors, pairs):
+    from .la import _c_strides
+    tensors = list(tensors)
+    for i, t in enumerate(tensors):
+        _chk_g(t, "%s: array %d" % (fn, i), pairs)
+    if not tensors:
+        raise ValueError("%s: no arrays" % fn)
+    if any(t.dtype != tensors[0].dtype or t.device != tensors[0].device for t in tensors):
+        raise TypeError("%s: the arrays must have one dtype and one device" % fn)
+    out_shape, strides, offs, shapes = plan(axis, [_plain(t.shape, pairs) for t in tensors])
+    B = _fresh(tensors[0], out_shape, pairs)
+    for t, sh, off in zip(tensors, shapes, offs):
+        _gather(B, off, strides, t, 0, _c_strides(sh), sh, pairs)
+    return B
+
+
+def concat(axis, tensors, pairs=False):
+    """nd.concat on device tensors of one dtype"""
+    from .la import _concat_plan
+    return _concat("concat", lambda ax, shapes: _concat_plan(ax, shapes) + ([list(s) for s in shapes],), axis, tensors, pairs)
+
+
+def stack(axis, tensors, pairs=False):
+    """nd.stack on device tensors of one dtype"""
+    from .la import _stack_plan
+
+    def plan(ax, shapes):
+        ax, out_shape, strides, offs = _stack_plan(ax, shapes)
+        return out_shape, strides, offs, [list(s[:ax]) + [1] + list(s[ax:]) for s in shapes]
+    return _concat("stack", plan, axis, tensors, pairs)

@@ -62,6 +62,163 @@ function fromNested(a) {           // nested JS arrays -> NDArray(float64)  (asa
   })(a, 0);
   return new NDArray(Int32Array.from(shape.length ? shape : [1]), data);
 }
+/* ---- planners of the strided N-d copy (csrc/gather.hip): sliceElems (nd_array.js:531-642), transpose(...axes) (nd_array.js:375-436),
+ * reshape (nd_array.js:438-462), concat (concat.js) and stack (stack.js) on shapes alone. Own code with the reference's messages;
+ * twins of nd4js_amd/la.py's _slice_plan ... _reduce_box. Offsets and strides are in elements of a row-major operand. ---- */
+function cStrides(shape) {
+  const st = new Array(shape.length); let s = 1;
+  for (let d = shape.length - 1; d >= 0; d--) { st[d] = s; s *= shape[d]; }
+  return st;
+}
+function checkShape(shape, n) {                  // the NDArray constructor's two checks
+  if (shape.some(s => s < 1)) throw new Error(`Invalid shape: ${shape.join(',')}.`);
+  if (n !== shape.reduce((a, b) => a * b, 1)) throw new Error(`Shape [${shape.join(',')}] does not match array length of ${n}.`);
+}
+// -> {shape, off, strides}: out[i] = data[off + sum i_d strides[d]]
+function slicePlan(shape, slices) {
+  shape = Array.from(shape); slices = Array.from(slices);
+  const ndim = shape.length;
+  let nEll = 0, nRed = 0, nSl = 0;
+  for (const s of slices) {
+    if (s === '...') nEll++;
+    else if (s === 'new') continue;
+    else if (typeof s === 'number') { if (!(s % 1 === 0)) throw new Error('Only integral indices allowed.'); nRed++; }
+    else {
+      const len = s == null ? undefined : s.length;
+      if (typeof len !== 'number' || !(len % 1 === 0) || len > 3 || len === 1) throw new Error('Illegal argument(s).');
+      nSl++;
+    }
+  }
+  if (nEll > 1) throw new Error('Highlander! There can be only one ... (ellipsis).');
+  if (nEll === 0) slices.push('...');
+  if (nRed + nSl > ndim) throw new Error('Cannot sliced more dimensions than available.');
+  let off = 0, d = ndim, stride = 1;
+  const out = [], strides = [];                  // innermost first
+  for (let k = slices.length; --k >= 0;) {
+    const s = slices[k];
+    if (s === 'new') { strides.push(0); out.push(1); continue; }
+    if (s === '...') { for (let i = nRed + nSl; i < ndim; i++) { d--; strides.push(stride); out.push(shape[d]); stride *= shape[d]; } continue; }
+    const n = shape[--d];
+    if (typeof s === 'number') {
+      const i = s < 0 ? s + n : s;
+      if (i < 0 || i >= n) throw new Error('Index out of bounds.');
+      off += stride * i;
+    } else {
+      let start = s[0] == null ? null : +s[0], end = s[1] == null ? null : +s[1];
+      const step = s[2] == null ? 1 : +s[2];
+      if (end !== null && end < 0) end += n;
+      if (start !== null && start < 0) start += n;
+      if (start !== null && (start < 0 || start >= n)) throw new Error('Slice start out of bounds.');
+      if (step === 0) throw new Error('Stride/step cannot be zero.');
+      if (step < 0) {
+        if (start === null) start = n - 1;
+        if (end === null) end = -1;
+        if (end < -1 || end >= n) throw new Error('Slice end out of bounds.');
+      } else {
+        if (start === null) start = 0;
+        if (end === null) end = n;
+        if (end < 0 || end > n) throw new Error('Slice end out of bounds.');
+      }
+      strides.push(stride * step);
+      off += stride * start;
+      out.push(1 + Math.trunc((-Math.sign(step) + end - start) / step));
+    }
+    stride *= n;
+  }
+  out.reverse(); strides.reverse();
+  const count = out.reduce((a, b) => a * b, 1);
+  if (count < 0) throw new Error(`Invalid typed array length: ${count}`);      // an empty range the wrong way round: the engine's text
+  if (out.some(x => x < 1)) throw new Error(`Invalid shape: ${out.join(',')}.`);
+  return {shape: out, off, strides};
+}
+// -> {shape, strides}; no axes: the last two swapped; axes that are not named follow the named ones in their own order
+function transposePlan(shape, axes) {
+  shape = Array.from(shape); axes = Array.from(axes);
+  const ndim = shape.length, old = cStrides(shape);
+  let order;
+  if (axes.length === 0) { order = shape.map((_, i) => i); if (ndim > 1) { order[ndim - 2] = ndim - 1; order[ndim - 1] = ndim - 2; } }
+  else {
+    const set = new Set(axes);
+    if (set.size !== axes.length) throw new Error('Duplicate axes are not allowed.');
+    if (axes.some(j => !(j >= 0 && j < ndim))) throw new Error('Axis out of bounds.');
+    order = axes.concat(shape.map((_, i) => i).filter(i => !set.has(i)));
+  }
+  return {shape: order.map(j => shape[j]), strides: order.map(j => old[j])};
+}
+// the new shape of an array of n elements, one -1 inferred
+function reshapeShape(shape, n, newShape) {
+  newShape = Array.from(Int32Array.from(newShape));
+  let rest = 1, infer = -1;
+  for (let i = newShape.length; --i >= 0;)
+    if (newShape[i] < 0) {
+      if (newShape[i] !== -1) throw new Error('Invalid dimension: ' + newShape[i]);
+      if (infer !== -1) throw new Error('At most on dimension may be -1.');
+      infer = i;
+    } else rest *= newShape[i];
+  if (infer !== -1) {
+    if (0 !== n % rest) throw new Error('Shape cannot be inferred.');          // (n % 0 is NaN: refused as well)
+    newShape[infer] = n / rest;
+  }
+  checkShape(newShape, n);
+  return newShape;
+}
+// -> {shape, strides, offs}: piece k, read in its own row-major order, lands at out[offs[k] + sum i_d strides[d]]
+function concatPlan(axis, shapes) {
+  shapes = shapes.map(s => Array.from(s));
+  if (axis == null) axis = 0;
+  const ndim = shapes[0].length;
+  if (0 > axis) axis += ndim;
+  if (0 > axis || axis >= ndim) throw new Error('Axis out of bounds.');
+  const out = shapes[0].slice();
+  for (let i = shapes.length; --i > 0;) {
+    const sh = shapes[i];
+    if (out.length !== sh.length) throw new Error('All shapes must have the same length.');
+    if (!out.every((len, d) => len === sh[d] || axis === d)) throw new Error('Shape along all axes but the concatentation axis must match.');
+    out[axis] += sh[axis];
+  }
+  const strides = cStrides(out), offs = [];
+  let at = 0;
+  for (const sh of shapes) { offs.push(at * strides[axis]); at += sh[axis]; }
+  return {shape: out, strides, offs};
+}
+// -> {axis, shapes (with the new axis of extent 1), shape, strides, offs}
+function stackPlan(axis, shapes) {
+  shapes = shapes.map(s => Array.from(s));
+  if (axis == null) axis = 0;
+  if (0 > axis) axis += shapes[0].length + 1;
+  if (0 > axis || axis > shapes[0].length) throw new Error('Axis out of bounds.');
+  const wide = shapes.map(s => s.slice(0, axis).concat([1], s.slice(axis)));
+  return Object.assign({axis, shapes: wide}, concatPlan(axis, wide));
+}
+const GATHER_MAX_ND = 8;
+// -> {shape, ss, ds, loop}: extent-1 axes dropped, neighbours merged where stride_d == stride_{d+1} shape_{d+1} on both sides, what
+// exceeds GATHER_MAX_ND axes peeled off the outer end into a loop of [src offset, dst offset] pairs, one launch each
+function reduceBox(shape, ss, ds) {
+  const merged = [];
+  for (let d = 0; d < shape.length; d++) {
+    const n = shape[d], s = ss[d], t = ds[d];
+    if (n === 1) continue;
+    const last = merged[merged.length - 1];
+    if (last && last[1] === s * n && last[2] === t * n) { last[0] *= n; last[1] = s; last[2] = t; }
+    else merged.push([n, s, t]);
+  }
+  const cut = Math.max(0, merged.length - GATHER_MAX_ND), kept = merged.slice(cut);
+  let loop = [[0, 0]];
+  for (const [n, s, t] of merged.slice(0, cut)) {
+    const next = [];
+    for (const [a, b] of loop) for (let i = 0; i < n; i++) next.push([a + i * s, b + i * t]);
+    loop = next;
+  }
+  return {shape: kept.map(a => a[0]), ss: kept.map(a => a[1]), ds: kept.map(a => a[2]), loop};
+}
+// one planned copy between device buffers; pairs: complex128, one more innermost axis of two 8-byte words
+function gatherBox(dst, dstOff, dstStrides, src, srcOff, srcStrides, shape, pairs) {
+  const eb = src.Ctor.BYTES_PER_ELEMENT;
+  let sh = Array.from(shape), ss = Array.from(srcStrides), ds = Array.from(dstStrides);
+  if (pairs) { sh.push(2); ss = ss.map(x => 2 * x).concat([1]); ds = ds.map(x => 2 * x).concat([1]); srcOff *= 2; dstOff *= 2; }
+  const box = reduceBox(sh, ss, ds);
+  for (const [so, dof] of box.loop) native().gather_nd(eb, box.shape, src.view(0), srcOff + so, box.ss, dst.view(0), dstOff + dof, box.ds);
+}
 /* ---- device-resident arrays (SURVEY.md §8f N3): `data` stays in HBM across calls, lazy D2H on `.data` ----
  * An extension of the NDArray contract (nd_array.js:128-158), not part of the reference: any nd.la hot-path function
  * that receives at least one DeviceNDArray runs the `_dev` entry points (nothing crosses PCIe except host operands
@@ -117,6 +274,27 @@ class DeviceNDArray {
     const B = new DevBuf(this._buf.length, Float64Array);
     native().dtranspose_batched(this._buf.length / (M * N || 1), M, N, this._buf.view(0), B.view(0));
     return new DeviceNDArray(shape, B);
+  }
+  /* NDArray.sliceElems / transpose(...axes) / reshape on the device (csrc/gather.hip): float64, int32 and complex128. sliceElems and
+   * transpose with axes return fresh device arrays; transpose() without axes is .T and keeps .T's rules. reshape returns a device
+   * array over the SAME buffer, as the reference's reshape shares `data`: dispose() on either one releases both. */
+  sliceElems(...slices) {
+    const p = slicePlan(this.shape, slices), pairs = !!this._complex;
+    const B = new DevBuf(p.shape.reduce((a, b) => a * b, 1) * (pairs ? 2 : 1), this._buf.Ctor);
+    gatherBox(B, 0, cStrides(p.shape), this._buf, p.off, p.strides, p.shape, pairs);
+    return new DeviceNDArray(Int32Array.from(p.shape), B, this._complex);
+  }
+  transpose(...axes) {
+    if (axes.length === 0) return this.T;
+    const p = transposePlan(this.shape, axes), pairs = !!this._complex;
+    const B = new DevBuf(this._buf.length, this._buf.Ctor);
+    gatherBox(B, 0, cStrides(p.shape), this._buf, 0, p.strides, p.shape, pairs);
+    return new DeviceNDArray(Int32Array.from(p.shape), B, this._complex);
+  }
+  reshape(...shape) {
+    const n = this.shape.reduce((a, b) => a * b, 1);
+    if (!this._buf.ext) throw new Error('nd4hip: device array was disposed.');
+    return new DeviceNDArray(Int32Array.from(reshapeShape(this.shape, n, shape)), this._buf, this._complex);
   }
   toHost(NDA) { return new (NDA || NDArray)(Int32Array.from(this.shape), this.data); }
   dispose() { this._buf.free(); }                // optional: dropped arrays are freed by the GC finalizer
@@ -1091,6 +1269,38 @@ function makeLa(NDA, fallback, SolveError, Complex) {
   la.unpermute_rows = permute(0, 1, 'unpermute_rows');
   la.unpermute_cols = permute(1, 1, 'unpermute_cols');
 
+  /* ---- concat (concat.js) / stack (stack.js) on device arrays, csrc/gather.hip: (axis?, dtype?, arrays) as the reference's nd.concat
+   * and nd.stack. At least one array must be a DeviceNDArray; host arrays in the list are uploaded on the way in; all arrays share one
+   * dtype (float64, int32 or complex128) and `dtype`, if given, names it: a conversion would compute, this only moves. Results are
+   * DeviceNDArrays. Not enumerable, like to_device: nd.la has no such names, the reference's own are nd.concat / nd.stack. ---- */
+  const lists = (name, plan) => function (axis, dtype, arrays) {
+    if (arrays == null) {
+      if (dtype == null) { arrays = axis; axis = undefined; }
+      else { arrays = dtype; dtype = undefined; if (typeof axis === 'string') { dtype = axis; axis = undefined; } }
+    }
+    arrays = Array.from(arrays, asarray);
+    if (!arrays.some(isDev)) throw new Error(`nd4hip.${name}: no device array among the arguments.`);
+    const dt = dtypeOf(arrays[0]);
+    if (!['float64', 'int32', 'complex128'].includes(dt) || arrays.some(a => dtypeOf(a) !== dt) || (dtype != null && dtype !== dt))
+      throw new Error(`nd4hip.${name}: dtype is not accelerated.`);
+    const pairs = dt === 'complex128', Cx = pairs ? (arrays.find(isDev)._complex || needComplex(name)) : null;
+    const p = plan(axis, arrays.map(a => Array.from(a.shape))), shapes = p.shapes || arrays.map(a => Array.from(a.shape)), temps = [];
+    const B = new DevBuf(p.shape.reduce((a, b) => a * b, 1) * (pairs ? 2 : 1), pairs || dt === 'float64' ? Float64Array : Int32Array);
+    try {
+      arrays.forEach((a, k) => {
+        let buf = isDev(a) ? a._buf : null;
+        if (!buf) { buf = DevBuf.from(pairs ? a.data._array : a.data); temps.push(buf); }
+        gatherBox(B, p.offs[k], p.strides, buf, 0, cStrides(shapes[k]), shapes[k], pairs);
+      });
+    } catch (e) { B.free(); throw e; } finally { release(temps); }
+    return new DeviceNDArray(Int32Array.from(p.shape), B, Cx);
+  };
+  for (const [name, plan] of [['concat', concatPlan], ['stack', stackPlan]]) {
+    const f = lists(name, plan);
+    Object.defineProperty(f, 'name', {value: name});
+    Object.defineProperty(la, name, {value: f, writable: true, enumerable: false, configurable: true});
+  }
+
   // complex128 device arrays are accepted by matmul2 / matmul only: every other function refuses them before it looks at the
   // buffer (which holds 2n doubles, not n float64 entries)
   const complexOk = new Set(['matmul2', 'matmul', 'eigen_balance_post', '_chain_plan', 'to_device', 'to_host', 'synchronize', 'profile_enable', 'profile_last']);
@@ -1191,7 +1401,7 @@ function install(nd, opts) {
     return f;
   };
   for (const k of Object.keys(original)) Object.defineProperty(patched, k, {value: route(k), writable: true, enumerable: true, configurable: true});
-  for (const k of ['to_device', 'to_host', 'synchronize', 'DeviceNDArray', 'profile_enable', 'profile_last', 'schur_qrfrancis'])   // §8f N3 / §8b extensions, not in the reference (schur_qrfrancis: its private step)
+  for (const k of ['to_device', 'to_host', 'synchronize', 'DeviceNDArray', 'profile_enable', 'profile_last', 'schur_qrfrancis', 'concat', 'stack'])   // §8f N3 / §8b extensions, not in the reference (schur_qrfrancis: its private step)
     Object.defineProperty(patched, k, {value: acc[k], writable: true, enumerable: false, configurable: true});
   if (!target) { try { nd.la = patched; } catch (e) { /* exported getter: caller uses the returned object */ } }
   patched.__nd4hip_original__ = original;
@@ -1203,6 +1413,7 @@ function install(nd, opts) {
 
 module.exports = Object.assign(standalone, {
   NDArray, DeviceNDArray, SingularMatrixSolveError, install, bcastGroups, complexOver,
+  slicePlan, transposePlan, reshapeShape, concatPlan, stackPlan, reduceBox,
   accelerated: a => !!a && (isDev(a) || a.data instanceof Float64Array || a.data instanceof Int32Array),
   device_count: () => native().device_count(),
   devices: () => native().devices(),            // ids behind the handle (ND4HIP_DEVICES=all|0,1,...: batched host calls are sharded)

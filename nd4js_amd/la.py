@@ -1433,3 +1433,243 @@ def unpermute_rows(A, P, device=None):
 def unpermute_cols(A, P, device=None):
     """permute.js:238-306: B[:,P[j]] = A[:,j]"""
     return _permute(1, 1, A, P, device)
+
+
+# planners of the strided N-d copy (csrc/gather.hip): NDArray.sliceElems (nd_array.js:531-642), transpose(...axes)
+# (nd_array.js:375-436), reshape (nd_array.js:438-462), concat (concat.js) and stack (stack.js) on shapes alone. Pure host code:
+# each returns what one nd4hip_gather_nd_dev call needs, in elements of a C-ordered operand, or raises the reference's text.
+def _c_strides(shape):
+    strides, s = [0] * len(shape), 1
+    for d in range(len(shape) - 1, -1, -1):
+        strides[d] = s
+        s *= int(shape[d])
+    return strides
+
+
+def _js_list(shape):
+    return ",".join(_js_num(s) for s in shape)
+
+
+def _check_shape(shape, n):
+    """the NDArray constructor (nd_array.js:135-139) on a new shape over n elements"""
+    if any(s < 1 for s in shape):
+        raise ValueError("Invalid shape: %s." % _js_list(shape))
+    total = 1
+    for s in shape:
+        total *= s
+    if total != n:
+        raise ValueError("Shape [%s] does not match array length of %d." % (_js_list(shape), n))
+
+
+def _integral(x):
+    return isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_)) or (isinstance(x, (float, np.floating)) and float(x).is_integer())
+
+
+def _slice_plan(shape, slices):
+    """sliceElems on a shape: (out_shape, off, strides) with out[i] = data[off + sum i_d strides[d]]. A slice is an integer (the
+    axis disappears), '...' or Ellipsis, 'new' (a new axis of extent 1, stride 0) or [start, end, step] / [start, end] / [] with
+    None for an omitted entry; negative start / end count from the end, a negative step reverses."""
+    shape = [int(s) for s in shape]
+    slices = ["..." if s is Ellipsis else s for s in slices]
+    ndim = len(shape)
+    n_ell = n_red = n_sl = 0
+    for s in slices:
+        if isinstance(s, str) and s == "...":
+            n_ell += 1
+        elif isinstance(s, str) and s == "new":
+            pass
+        elif isinstance(s, (int, float, np.integer, np.floating)) and not isinstance(s, (bool, np.bool_)):
+            if not _integral(s):
+                raise ValueError("Only integral indices allowed.")
+            n_red += 1
+        else:
+            if not isinstance(s, (list, tuple)) or len(s) > 3 or len(s) == 1:
+                raise ValueError("Illegal argument(s).")
+            if any(x is not None and not _integral(x) for x in s):
+                raise TypeError("slice entries must be integers or None")
+            n_sl += 1
+    if n_ell > 1:
+        raise ValueError("Highlander! There can be only one ... (ellipsis).")
+    if n_ell == 0:
+        slices = slices + ["..."]
+    if n_red + n_sl > ndim:
+        raise ValueError("Cannot sliced more dimensions than available.")
+    off, d, stride = 0, ndim, 1
+    out_shape, strides = [], []                              # innermost first, as the reference builds them
+    for s in reversed(slices):
+        if isinstance(s, str) and s == "new":
+            strides.append(0)
+            out_shape.append(1)
+        elif isinstance(s, str):
+            for _ in range(n_red + n_sl, ndim):
+                d -= 1
+                strides.append(stride)
+                out_shape.append(shape[d])
+                stride *= shape[d]
+        else:
+            d -= 1
+            n = shape[d]
+            if not isinstance(s, (list, tuple)):
+                i = int(s)
+                if i < 0:
+                    i += n
+                if i < 0 or i >= n:
+                    raise ValueError("Index out of bounds.")
+                off += stride * i
+            else:
+                start, end, step = (list(s) + [None, None, None])[:3]
+                start = None if start is None else int(start)
+                end = None if end is None else int(end)
+                step = 1 if step is None else int(step)
+                if end is not None and end < 0:
+                    end += n
+                if start is not None and start < 0:
+                    start += n
+                if start is not None and (start < 0 or start >= n):
+                    raise ValueError("Slice start out of bounds.")
+                if step == 0:
+                    raise ValueError("Stride/step cannot be zero.")
+                if step < 0:
+                    start = n - 1 if start is None else start
+                    end = -1 if end is None else end
+                    if end < -1 or end >= n:
+                        raise ValueError("Slice end out of bounds.")
+                else:
+                    start = 0 if start is None else start
+                    end = n if end is None else end
+                    if end < 0 or end > n:
+                        raise ValueError("Slice end out of bounds.")
+                strides.append(stride * step)
+                off += stride * start
+                num = (1 if step < 0 else -1) + end - start
+                out_shape.append(1 + (abs(num) // abs(step)) * (1 if (num < 0) == (step < 0) else -1))      # Math.trunc
+            stride *= n
+    out_shape.reverse()
+    strides.reverse()
+    count = 1
+    for s in out_shape:
+        count *= s
+    if count < 0:                                            # an empty range the wrong way round: the engine's text, before the constructor
+        raise ValueError("Invalid typed array length: %d" % count)
+    if any(s < 1 for s in out_shape):
+        raise ValueError("Invalid shape: %s." % _js_list(out_shape))
+    return out_shape, off, strides
+
+
+def _transpose_plan(shape, axes):
+    """transpose(...axes) on a shape: (out_shape, strides). No axes: the last two swapped. Axes that are not named follow the
+    named ones in their own order."""
+    shape = [int(s) for s in shape]
+    ndim = len(shape)
+    old = _c_strides(shape)
+    axes = list(axes)
+    if not axes:
+        order = list(range(ndim))
+        if ndim > 1:
+            order[-2:] = [ndim - 1, ndim - 2]
+    else:
+        if any(not _integral(j) for j in axes):
+            raise TypeError("axes must be integers")
+        axes = [int(j) for j in axes]
+        if len(set(axes)) != len(axes):
+            raise ValueError("Duplicate axes are not allowed.")
+        if any(j < 0 or j >= ndim for j in axes):
+            raise ValueError("Axis out of bounds.")
+        order = axes + [i for i in range(ndim) if i not in axes]
+    return [shape[j] for j in order], [old[j] for j in order]
+
+
+def _reshape_shape(shape, n, new_shape):
+    """reshape(...new_shape) of an array of `shape` holding n elements: the new shape, one -1 inferred"""
+    if any(not _integral(s) for s in new_shape):
+        raise TypeError("shape entries must be integers")
+    new_shape = [int(s) for s in new_shape]
+    rest, infer = 1, -1
+    for i in range(len(new_shape) - 1, -1, -1):
+        if new_shape[i] < 0:
+            if new_shape[i] != -1:
+                raise ValueError("Invalid dimension: %d" % new_shape[i])
+            if infer != -1:
+                raise ValueError("At most on dimension may be -1.")
+            infer = i
+        else:
+            rest *= new_shape[i]
+    if infer != -1:
+        if rest == 0 or n % rest != 0:
+            raise ValueError("Shape cannot be inferred.")
+        new_shape[infer] = n // rest
+    _check_shape(new_shape, n)
+    return new_shape
+
+
+def _concat_plan(axis, shapes):
+    """concat on shapes: (out_shape, strides of the result, [offset of each piece in the result]); piece k, read in its own
+    C order, lands at out[offset_k + sum i_d strides[d]]"""
+    shapes = [[int(s) for s in sh] for sh in shapes]
+    if not shapes:
+        raise ValueError("concat: no arrays")
+    axis = 0 if axis is None else int(axis)
+    ndim = len(shapes[0])
+    if axis < 0:
+        axis += ndim
+    if axis < 0 or axis >= ndim:
+        raise ValueError("Axis out of bounds.")
+    out = list(shapes[0])
+    for sh in reversed(shapes[1:]):
+        if len(sh) != ndim:
+            raise ValueError("All shapes must have the same length.")
+        if any(out[d] != sh[d] and d != axis for d in range(ndim)):
+            raise ValueError("Shape along all axes but the concatentation axis must match.")
+        out[axis] += sh[axis]
+    strides = _c_strides(out)
+    offs, at = [], 0
+    for sh in shapes:
+        offs.append(at * strides[axis])
+        at += sh[axis]
+    return out, strides, offs
+
+
+def _stack_plan(axis, shapes):
+    """stack on shapes: the shapes with the new axis of extent 1 inserted, then _concat_plan"""
+    shapes = [[int(s) for s in sh] for sh in shapes]
+    if not shapes:
+        raise ValueError("stack: no arrays")
+    axis = 0 if axis is None else int(axis)
+    if axis < 0:
+        axis += len(shapes[0]) + 1
+    if axis < 0 or axis > len(shapes[0]):
+        raise ValueError("Axis out of bounds.")
+    return (axis,) + _concat_plan(axis, [sh[:axis] + [1] + sh[axis:] for sh in shapes])
+
+
+GATHER_MAX_ND = 8
+
+
+def _reduce_box(shape, src_strides, dst_strides):
+    """the box of one strided copy, reduced for the kernel: extent-1 axes dropped, neighbours d, d+1 merged where
+    stride_d == stride_{d+1} shape_{d+1} on both sides, and what is left beyond GATHER_MAX_ND axes peeled off the outer end into a
+    host loop. Returns (shape, src_strides, dst_strides, loop): loop lists the (src offset, dst offset) of every launch."""
+    axes = [[int(n), int(s), int(t)] for n, s, t in zip(shape, src_strides, dst_strides) if int(n) != 1]
+    merged = []
+    for n, s, t in axes:
+        if merged and merged[-1][1] == s * n and merged[-1][2] == t * n:
+            merged[-1] = [merged[-1][0] * n, s, t]
+        else:
+            merged.append([n, s, t])
+    peel, kept = merged[:max(0, len(merged) - GATHER_MAX_ND)], merged[max(0, len(merged) - GATHER_MAX_ND):]
+    loop = [(0, 0)]
+    for n, s, t in peel:
+        loop = [(a + i * s, b + i * t) for a, b in loop for i in range(n)]
+    return [a[0] for a in kept], [a[1] for a in kept], [a[2] for a in kept], loop
+
+
+def _box_reach(shape, strides, off):
+    """the lowest and the highest element a box reaches from `off` (the bounds rule of nd4hip_gather_nd_dev)"""
+    lo = hi = int(off)
+    for n, s in zip(shape, strides):
+        span = (int(n) - 1) * int(s)
+        if span < 0:
+            lo += span
+        else:
+            hi += span
+    return lo, hi
