@@ -472,6 +472,45 @@ int nd4hip_gather_nd_dev(nd4hip_handle* h, int elem_bytes, int ndim, const int64
                          const void* src, int64_t src_len, int64_t src_off, const int64_t* src_strides,
                          void* dst, int64_t dst_len, int64_t dst_off, const int64_t* dst_strides);
 
+/* ---- elementwise arithmetic and ordered axis reductions on float64 device arrays: nd.zip_elems (src/zip_elems.js),
+ * NDArray.mapElems and NDArray.reduceElems (src/nd_array.js:353-360, 464-529) with one of nd.math's add, sub, mul, div, min, max,
+ * neg, abs as the closure ----------
+ * Each operator is one IEEE operation on float64: every non-NaN result has the reference's 64 bits, denormals included. A NaN
+ * result is a NaN; which payload survives is not specified. min and max are Math.min and Math.max: a NaN operand gives NaN,
+ * min(+0, -0) = -0, max(-0, +0) = +0. neg and abs flip and clear the sign bit.
+ *
+ * dzip_nd: for every index vector i of the box shape[0..ndim):  C[i] = op(A[a_off + sum_d i_d a_strides[d]], B[b_off + sum_d i_d
+ * b_strides[d]]), C dense row-major with c_len elements. Offsets and strides are in elements; strides are >= 0 and 0 broadcasts
+ * along an axis of any extent. A unary op takes B == NULL (b_len, b_off, b_strides are ignored then). ndim = 0 is one element.
+ * The kernels are chosen from the box as given, so pass it reduced (extent-1 axes dropped, mergeable neighbours merged).
+ *
+ * dreduce_nd: A is a dense row-major array of `shape`; axis d is folded away where reduced[d] != 0. Per output element the first
+ * element met is copied and the others are folded in as acc = op(x, acc), in row-major order of the reduced axes: the reference's
+ * order, so sums and products have its bits. op is ADD, MUL, MIN or MAX (the operators for which op(x, acc) and op(acc, x) agree).
+ * No reduced axis: a copy. C has one element per index of the kept axes (one element when every axis is reduced).
+ *
+ * Both enqueue on the handle's stream, do not synchronise and have no flag to read back. Both return ND4HIP_ERR_ARG, with nothing
+ * written and the handle still usable, for: an unknown op or one of the wrong arity (B given with a unary op, B missing with a
+ * binary one, a reducer outside the four), ndim outside 0..8, an extent < 1, a negative stride, an operand reaching outside
+ * [0, len), c_len different from the result's element count, C overlapping in bytes what is read of A or B.
+ * nd4hip_profile_last reports "zip_nd" / "reduce_nd" with 0 flops and the bytes read plus written: 8 (count + the distinct
+ * elements read of A and of B: the product of the extents whose stride is not 0), and 8 (elements of A + elements of C).
+ * There is no host-pointer form: a host array would cross PCIe twice for work the host does at memory speed. */
+#define ND4HIP_EW_ADD 0
+#define ND4HIP_EW_SUB 1
+#define ND4HIP_EW_MUL 2
+#define ND4HIP_EW_DIV 3
+#define ND4HIP_EW_MIN 4
+#define ND4HIP_EW_MAX 5
+#define ND4HIP_EW_NEG 16
+#define ND4HIP_EW_ABS 17
+int nd4hip_dzip_nd_dev(nd4hip_handle* h, int op, int ndim, const int64_t* shape,
+                       const double* A, int64_t a_len, int64_t a_off, const int64_t* a_strides,
+                       const double* B, int64_t b_len, int64_t b_off, const int64_t* b_strides,
+                       double* C, int64_t c_len);
+int nd4hip_dreduce_nd_dev(nd4hip_handle* h, int op, int ndim, const int64_t* shape, const int32_t* reduced,
+                          const double* A, int64_t a_len, double* C, int64_t c_len);
+
 /* ---- svd_decomp: replaces the output contract of src/la/svd.js:25 (= svd_dc.js:883-932) ----------
  * A [batch,M,N] -> U [batch,M,L], sv [batch,L] (>= 0, descending), V [batch,L,N] (rows = right
  * singular vectors), L = min(M,N); one-sided Jacobi with the reference's Jacobi post-processing

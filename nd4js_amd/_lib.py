@@ -75,6 +75,10 @@ SIGNATURES = {
     "nd4hip_dpermute_batched": (c_int, [ctypes.c_void_p, c_int, c_int, c_i64, c_i64, c_i64, c_dp, c_i64, ctypes.c_void_p, c_i64, c_dp]),
     "nd4hip_gather_nd_dev": (c_int, [ctypes.c_void_p, c_int, c_int, ctypes.POINTER(c_i64), ctypes.c_void_p, c_i64, c_i64, ctypes.POINTER(c_i64),
                                      ctypes.c_void_p, c_i64, c_i64, ctypes.POINTER(c_i64)]),
+    "nd4hip_dzip_nd_dev": (c_int, [ctypes.c_void_p, c_int, c_int, ctypes.POINTER(c_i64), c_dp, c_i64, c_i64, ctypes.POINTER(c_i64),
+                                   c_dp, c_i64, c_i64, ctypes.POINTER(c_i64), c_dp, c_i64]),
+    "nd4hip_dreduce_nd_dev": (c_int, [ctypes.c_void_p, c_int, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(ctypes.c_int32), c_dp, c_i64,
+                                      c_dp, c_i64]),
     "nd4hip_dgebrd_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp]),
     "nd4hip_dgebrd_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp]),
     "nd4hip_dgehrd_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),

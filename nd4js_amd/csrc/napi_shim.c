@@ -94,6 +94,9 @@ static int (*p_free)(nd4hip_handle*, void*);
 static int (*p_h2d)(nd4hip_handle*, void*, const void*, size_t);
 static int (*p_gather_nd)(nd4hip_handle*, int, int, const int64_t*, const void*, int64_t, int64_t, const int64_t*, void*, int64_t, int64_t,
                          const int64_t*);
+static int (*p_zip_nd)(nd4hip_handle*, int, int, const int64_t*, const double*, int64_t, int64_t, const int64_t*, const double*, int64_t, int64_t,
+                       const int64_t*, double*, int64_t);
+static int (*p_reduce_nd)(nd4hip_handle*, int, int, const int64_t*, const int32_t*, const double*, int64_t, double*, int64_t);
 static int (*p_d2h)(nd4hip_handle*, void*, const void*, size_t);
 static int (*p_sync)(nd4hip_handle*);
 static int (*p_prof_enable)(nd4hip_handle*, int);
@@ -175,6 +178,8 @@ static int load_library(void) {
   SYM2(p_dtrsm, "nd4hip_dtrsm_batched");
 #undef SYM2
   SYM(p_gather_nd, "nd4hip_gather_nd_dev");
+  SYM(p_zip_nd, "nd4hip_dzip_nd_dev");
+  SYM(p_reduce_nd, "nd4hip_dreduce_nd_dev");
   SYM(p_svd_info, "nd4hip_dgesvdj_last_info");
   SYM(p_malloc, "nd4hip_malloc");
   SYM(p_free, "nd4hip_free");
@@ -917,6 +922,50 @@ static napi_value js_gather_nd(napi_env env, napi_callback_info info) {
   FAIL_IF(p_gather_nd(g_handle, (int)eb, (int)nd, shape, S.p, (int64_t)S.len, so, ss, D.p, (int64_t)D.len, dof, ds));
   return NULL;
 }
+/* zip_nd(op, shape, A, aOff, aStrides, B | null, bOff, bStrides, C): C[i] = op(A[..], B[..]) on float64 device views (zip_elems and
+ * mapElems with one of nd.math's operators); C is dense, with one element per index of the box. Device only. */
+static napi_value js_zip_nd(napi_env env, napi_callback_info info) {
+  ARGS(9, "zip_nd");
+  int64_t op, ao, bo = 0, shape[8], as[8], bs[8]; uint32_t nd = 0, na = 0, nb = 0; opnd A, B, C;
+  napi_valuetype tb;
+  if (get_i64(env, a[0], &op) || get_i64_list(env, a[1], shape, &nd) || get_i64(env, a[3], &ao) || get_i64_list(env, a[4], as, &na) ||
+      napi_typeof(env, a[5], &tb) != napi_ok) return NULL;
+  const int unary = tb == napi_null || tb == napi_undefined;
+  NEED(na == nd, "zip_nd: shape and strides must have one length");
+  if (F64(2, A) || F64(8, C)) return NULL;
+  B.p = NULL; B.len = 0; B.dev = 1;
+  if (!unary) {
+    if (get_i64(env, a[6], &bo) || get_i64_list(env, a[7], bs, &nb) || F64(5, B)) return NULL;
+    NEED(nb == nd, "zip_nd: shape and strides must have one length");
+  }
+  if (!(A.dev == 1 && B.dev == 1 && C.dev == 1)) { napi_throw_type_error(env, "ND4HIP", "zip_nd: device views only (there is no host-pointer form)"); return NULL; }
+  int64_t count = 1;
+  for (uint32_t i = 0; i < nd; i++) { NEED(shape[i] >= 1 && count <= INT64_MAX / shape[i], "zip_nd: bad extent"); count *= shape[i]; }
+  NEED((size_t)count <= C.len, "zip_nd: C is too small");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_zip_nd(g_handle, (int)op, (int)nd, shape, (const double*)A.p, (int64_t)A.len, ao, as, (const double*)B.p, (int64_t)B.len, bo, bs,
+                   (double*)C.p, count));
+  return NULL;
+}
+/* reduce_nd(op, shape, reduced, A, C): reduceElems with add, mul, min or max in the reference's order; reduced[d] != 0 folds axis d
+ * away. A and C are device views that start at the operand and at the result. Device only. */
+static napi_value js_reduce_nd(napi_env env, napi_callback_info info) {
+  ARGS(5, "reduce_nd");
+  int64_t op, shape[8], red[8]; int32_t flags[8]; uint32_t nd = 0, nr = 0; opnd A, C;
+  if (get_i64(env, a[0], &op) || get_i64_list(env, a[1], shape, &nd) || get_i64_list(env, a[2], red, &nr) || F64(3, A) || F64(4, C)) return NULL;
+  NEED(nr == nd, "reduce_nd: shape and flags must have one length");
+  int64_t outs = 1;
+  for (uint32_t i = 0; i < nd; i++) {
+    NEED(shape[i] >= 1 && outs <= INT64_MAX / shape[i], "reduce_nd: bad extent");
+    flags[i] = red[i] != 0;
+    if (!flags[i]) outs *= shape[i];
+  }
+  NEED((size_t)outs <= C.len, "reduce_nd: C is too small");
+  if (!(A.dev == 1 && C.dev == 1)) { napi_throw_type_error(env, "ND4HIP", "reduce_nd: device views only (there is no host-pointer form)"); return NULL; }
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_reduce_nd(g_handle, (int)op, (int)nd, shape, flags, (const double*)A.p, (int64_t)A.len, (double*)C.p, outs));
+  return NULL;
+}
 /* dldltrs_batched(batch, N, J, LD, strideLD, Y, strideY, X)   (ldl_solve, ldl.js:133-201) */
 static napi_value js_dldltrs(napi_env env, napi_callback_info info) {
   ARGS(8, "dldltrs_batched");
@@ -1084,6 +1133,8 @@ static napi_value init(napi_env env, napi_value exports) {
     {"ddiagmat_batched", NULL, js_ddiagmat, NULL, NULL, NULL, napi_default, NULL},
     {"dpermute_batched", NULL, js_dpermute, NULL, NULL, NULL, napi_default, NULL},
     {"gather_nd", NULL, js_gather_nd, NULL, NULL, NULL, napi_default, NULL},
+    {"zip_nd", NULL, js_zip_nd, NULL, NULL, NULL, napi_default, NULL},
+    {"reduce_nd", NULL, js_reduce_nd, NULL, NULL, NULL, napi_default, NULL},
     {"dev_alloc", NULL, js_dev_alloc, NULL, NULL, NULL, napi_default, NULL},
     {"dev_free", NULL, js_dev_free, NULL, NULL, NULL, napi_default, NULL},
     {"dev_upload", NULL, js_dev_upload, NULL, NULL, NULL, napi_default, NULL},

@@ -935,3 +935,82 @@ def stack(axis, tensors, pairs=False):
         ax, out_shape, strides, offs = _stack_plan(ax, shapes)
         return out_shape, strides, offs, [list(s[:ax]) + [1] + list(s[ax:]) for s in shapes]
     return _concat("stack", plan, axis, tensors, pairs)
+
+
+# ---- elementwise arithmetic and ordered reductions (csrc/elem.hip), planned by la._zip_plan / la._reduce_plan ----
+def _chk_e(t, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
+        raise TypeError("%s must be a contiguous float64 CUDA tensor" % name)
+    return t
+
+
+def _ew_op(op, allowed, what):
+    from .la import EW_OPS
+    if op not in allowed:
+        raise ValueError("%s: op must be one of %s" % (what, ", ".join(allowed)))
+    return EW_OPS[op]
+
+
+def _zip(code, tensors):
+    from .la import _zip_plan
+    if any(t.device != tensors[0].device for t in tensors):
+        raise TypeError("zip_elems: the tensors must be on one device")
+    shape, _, (bshape, bstrides, loop) = _zip_plan([tuple(t.shape) for t in tensors])
+    C = torch.empty(tuple(shape), dtype=torch.float64, device=tensors[0].device)
+    nd = len(bshape)
+    arr = ctypes.c_int64 * max(nd, 1)
+    count = 1
+    for n in bshape:
+        count *= n
+    A, B = tensors[0], tensors[1] if len(tensors) > 1 else None
+    h = _h(A)
+    for offs in loop:
+        _struct_call(h.lib.nd4hip_dzip_nd_dev, h.ptr, code, nd, arr(*bshape), _p(A), A.numel(), offs[0], arr(*bstrides[0]),
+                     _p(B) if B is not None else None, B.numel() if B is not None else 0, offs[1] if B is not None else 0,
+                     arr(*bstrides[1]) if B is not None else None, ctypes.c_void_p(C.data_ptr() + 8 * offs[-1]), count)
+    return C
+
+
+def zip_elems(tensors, op):
+    """nd.zip_elems(tensors, 'float64', nd.math.<op>) on two device tensors, broadcast by the reference's rule: op is 'add', 'sub',
+    'mul', 'div', 'min' or 'max' (Math.min / Math.max: NaN wins, -0 < +0). A fresh tensor; every non-NaN result has the
+    reference's bits."""
+    from .la import EW_OPS, EW_UNARY
+    tensors = list(tensors)
+    code = _ew_op(op, [k for k in EW_OPS if k not in EW_UNARY], "zip_elems")
+    if len(tensors) != 2:
+        raise ValueError("zip_elems: %s takes two tensors" % op)
+    for i, t in enumerate(tensors):
+        _chk_e(t, "zip_elems: tensor %d" % i)
+    return _zip(code, tensors)
+
+
+def map_elems(t, op=None):
+    """NDArray.mapElems('float64', nd.math.<op>) on a device tensor: op is 'neg' or 'abs'; None: a copy"""
+    from .la import EW_UNARY
+    _chk_e(t, "t")
+    if op is None:
+        C = torch.empty_like(t)
+        return strided_copy(C.view(-1), 0, [1], t.view(-1), 0, [1], [t.numel()]).view(t.shape)
+    return _zip(_ew_op(op, list(EW_UNARY), "map_elems"), [t])
+
+
+def reduce_elems(t, axes, op):
+    """NDArray.reduceElems(axes, 'float64', nd.math.<op>) on a device tensor: op is 'add', 'mul', 'min' or 'max'; axes is a number,
+    a list or a 1-D int32 numpy array. Each output folds its elements in the reference's order (row-major over the reduced axes,
+    the first one copied), so sums and products have its bits. A fresh tensor."""
+    from .la import EW_REDUCERS, _reduce_plan
+    _chk_e(t, "t")
+    code = _ew_op(op, list(EW_REDUCERS), "reduce_elems")
+    out_shape, bshape, flags, loop = _reduce_plan(tuple(t.shape), axes)
+    C = torch.empty(tuple(out_shape), dtype=torch.float64, device=t.device)
+    nd = len(bshape)
+    a_n = c_n = 1
+    for n, f in zip(bshape, flags):
+        a_n *= n
+        c_n *= 1 if f else n
+    h = _h(t)
+    for a_off, c_off in loop:
+        _struct_call(h.lib.nd4hip_dreduce_nd_dev, h.ptr, code, nd, (ctypes.c_int64 * max(nd, 1))(*bshape), (ctypes.c_int32 * max(nd, 1))(*flags),
+                     ctypes.c_void_p(t.data_ptr() + 8 * a_off), a_n, ctypes.c_void_p(C.data_ptr() + 8 * c_off), c_n)
+    return C

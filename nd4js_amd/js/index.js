@@ -219,6 +219,96 @@ function gatherBox(dst, dstOff, dstStrides, src, srcOff, srcStrides, shape, pair
   const box = reduceBox(sh, ss, ds);
   for (const [so, dof] of box.loop) native().gather_nd(eb, box.shape, src.view(0), srcOff + so, box.ss, dst.view(0), dstOff + dof, box.ds);
 }
+/* ---- planners of the elementwise kernels (csrc/elem.hip): zip_elems' broadcast rule (zip_elems.js:43-53) and reduceElems' axes
+ * (nd_array.js:479-497) on shapes alone, with the reference's messages; twins of la.py's _zip_plan and _reduce_plan. ---- */
+const EW_OPS = {add: 0, sub: 1, mul: 2, div: 3, min: 4, max: 5, neg: 16, abs: 17};
+const EW_ARITY = {add: 2, sub: 2, mul: 2, div: 2, min: 2, max: 2, neg: 1, abs: 1};
+const EW_REDUCERS = ['add', 'mul', 'min', 'max'];
+const EW_MAX_ND = 8;
+// -> {shape, strides (per operand, 0 = broadcast), box: {shape, strides, loop}}: the box is reduced for the kernel (extent-1 axes
+// dropped, neighbours merged where every operand allows) and what exceeds EW_MAX_ND axes is peeled off the outer end into a loop
+// of [offset of each operand ..., offset in the result]
+function zipPlan(shapes) {
+  shapes = shapes.map(s => Array.from(s));
+  const ndim = shapes.reduce((n, s) => Math.max(n, s.length), 0), shape = new Array(ndim).fill(1);
+  for (const sh of shapes)
+    for (let i = ndim, j = sh.length; i-- > 0 && j-- > 0;)
+      if (1 === shape[i]) shape[i] = sh[j];
+      else if (shape[i] !== sh[j] && sh[j] !== 1) throw new Error('Shapes are not broadcast-compatible.');
+  const strides = shapes.map(sh => { const own = cStrides(sh), pad = ndim - sh.length; return shape.map((_, d) => d < pad || sh[d - pad] === 1 ? 0 : own[d - pad]); });
+  const cs = cStrides(shape), merged = [];
+  for (let d = 0; d < ndim; d++) {
+    if (shape[d] === 1) continue;
+    const ax = [shape[d], cs[d], ...strides.map(st => st[d])], last = merged[merged.length - 1];
+    if (last && ax.every((s, k) => k === 0 || last[k] === s * ax[0])) { ax[0] *= last[0]; merged[merged.length - 1] = ax; }
+    else merged.push(ax);
+  }
+  const cut = Math.max(0, merged.length - EW_MAX_ND), kept = merged.slice(cut);
+  let loop = [new Array(shapes.length + 1).fill(0)];
+  for (const ax of merged.slice(0, cut)) {
+    const steps = ax.slice(2).concat([ax[1]]), next = [];
+    for (const offs of loop) for (let i = 0; i < ax[0]; i++) next.push(offs.map((o, k) => o + i * steps[k]));
+    loop = next;
+  }
+  return {shape, strides, box: {shape: kept.map(ax => ax[0]), strides: shapes.map((_, k) => kept.map(ax => ax[2 + k])), loop}};
+}
+// -> {shape, box: {shape, flags, loop}}: kept (0) and reduced (1) axes alternate in the box; kept axes beyond EW_MAX_ND are peeled off
+// the outer end into a loop of [offset in the operand, offset in the result]. axes: a number, an iterable or a 1-D int32 NDArray.
+function reducePlan(shape, axes) {
+  shape = Array.from(shape);
+  const ndim = shape.length;
+  if ('number' === typeof axes) axes = [axes];
+  else if (axes != null && axes.shape instanceof Int32Array && axes.data !== undefined) {
+    const dt = dtypeOf(axes);
+    if (dt !== 'int32') throw new Error(`Invalid dtype ${dt} for axes.`);
+    if (axes.shape.length !== 1) throw new Error('Only 1D nd.Array allowed for axes.');
+    axes = axes.data;
+  }
+  const red = new Set();
+  for (let ax of axes) {
+    if (0 > ax) ax += ndim;
+    if (0 > ax || ax >= ndim) throw new Error('Reduction axis ' + ax + ' out of bounds.');
+    red.add(+ax);
+  }
+  const merged = [];
+  shape.forEach((n, d) => {
+    if (n === 1) return;
+    const f = red.has(d) ? 1 : 0, last = merged[merged.length - 1];
+    if (last && last[1] === f) last[0] *= n; else merged.push([n, f]);
+  });
+  let loop = [[0, 0]];
+  while (merged.length > EW_MAX_ND && merged[0][1] === 0) {
+    const n = merged.shift()[0], aStep = merged.reduce((p, m) => p * m[0], 1), cStep = merged.reduce((p, m) => m[1] ? p : p * m[0], 1), next = [];
+    for (const [a, c] of loop) for (let i = 0; i < n; i++) next.push([a + i * aStep, c + i * cStep]);
+    loop = next;
+  }
+  if (merged.length > EW_MAX_ND) throw new Error(`reduceElems: more than ${EW_MAX_ND} alternating kept and reduced axes are not accelerated.`);
+  return {shape: shape.filter((_, d) => !red.has(d)), box: {shape: merged.map(m => m[0]), flags: merged.map(m => m[1]), loop}};
+}
+/* The operators as closures, for standalone use (after install(nd) the host module's own nd.math members are recognised as well):
+ * on float64 each is one IEEE operation, which is what the device runs. A closure is recognised by identity, never by its text. */
+const math = Object.freeze({
+  add: (x, y) => x + y, sub: (x, y) => x - y, mul: (x, y) => x * y, div: (x, y) => x / y,
+  min: (x, y) => Math.min(x, y), max: (x, y) => Math.max(x, y), neg: x => -x, abs: x => Math.abs(x),
+});
+const mathTables = [math];                       // install(nd) adds nd.math
+// the operator name behind `fn` (a name, or a function identical to a member of a known math table), or null
+function ewName(fn) {
+  if (typeof fn === 'string') return Object.prototype.hasOwnProperty.call(EW_OPS, fn) ? fn : null;
+  if (typeof fn !== 'function') return null;
+  for (const t of mathTables) for (const k of Object.keys(EW_OPS)) if (t[k] === fn) return k;
+  return null;
+}
+// C = op(A, B) on device buffers (B null: unary), planned by zipPlan; returns the fresh buffer
+function zipBox(op, plan, bufs) {
+  const n = plan.shape.reduce((a, b) => a * b, 1), C = new DevBuf(n, Float64Array), b = plan.box;
+  try {
+    for (const offs of b.loop)
+      native().zip_nd(EW_OPS[op], b.shape, bufs[0].view(0), offs[0], b.strides[0], bufs.length > 1 ? bufs[1].view(0) : null,
+                      bufs.length > 1 ? offs[1] : 0, bufs.length > 1 ? b.strides[1] : [], C.view(offs[offs.length - 1]));
+  } catch (e) { C.free(); throw e; }
+  return C;
+}
 /* ---- device-resident arrays (SURVEY.md §8f N3): `data` stays in HBM across calls, lazy D2H on `.data` ----
  * An extension of the NDArray contract (nd_array.js:128-158), not part of the reference: any nd.la hot-path function
  * that receives at least one DeviceNDArray runs the `_dev` entry points (nothing crosses PCIe except host operands
@@ -295,6 +385,36 @@ class DeviceNDArray {
     const n = this.shape.reduce((a, b) => a * b, 1);
     if (!this._buf.ext) throw new Error('nd4hip: device array was disposed.');
     return new DeviceNDArray(Int32Array.from(reshapeShape(this.shape, n, shape)), this._buf, this._complex);
+  }
+  /* NDArray.mapElems / reduceElems on the device (csrc/elem.hip), float64 only, for the closures that are one IEEE operation:
+   * mapElems() and mapElems('float64') copy, mapElems('float64', neg | abs) computes; reduceElems(axes, 'float64', add | mul | min |
+   * max) folds every output in the reference's order (sums and products have its bits). An operator is its name or a function
+   * identical to the host module's nd.math member (or this package's `math`). Every other form throws: a device array is never
+   * handed to a host closure. */
+  mapElems(dtype, mapper) {
+    if (typeof dtype === 'function' || (dtype == null && mapper != null)) throw new Error('nd4hip.mapElems: a mapper without dtype is not accelerated.');
+    if ((dtype != null && dtype !== 'float64') || this.dtype !== 'float64') throw new Error('nd4hip.mapElems: dtype is not accelerated.');
+    const n = this._buf.length;
+    if (mapper == null) {
+      const B = new DevBuf(n, Float64Array);
+      gatherBox(B, 0, [1], this._buf, 0, [1], [n], false);
+      return new DeviceNDArray(Int32Array.from(this.shape), B);
+    }
+    const op = ewName(mapper);
+    if (op === null || EW_ARITY[op] !== 1) throw new Error('nd4hip.mapElems: mapper is not accelerated.');
+    return new DeviceNDArray(Int32Array.from(this.shape), zipBox(op, zipPlan([this.shape]), [this._buf]));
+  }
+  reduceElems(axes, dtype, reducer) {
+    if (reducer == null) throw new Error('nd4hip.reduceElems: the forms without (axes, dtype, reducer) are not accelerated.');
+    if (dtype !== 'float64' || this.dtype !== 'float64') throw new Error('nd4hip.reduceElems: dtype is not accelerated.');
+    const op = ewName(reducer);
+    if (op === null || !EW_REDUCERS.includes(op)) throw new Error('nd4hip.reduceElems: reducer is not accelerated.');
+    const p = reducePlan(this.shape, axes), b = p.box;
+    const C = new DevBuf(p.shape.reduce((x, y) => x * y, 1), Float64Array);
+    try {
+      for (const [ao, co] of b.loop) native().reduce_nd(EW_OPS[op], b.shape, b.flags, this._buf.view(ao), C.view(co));
+    } catch (e) { C.free(); throw e; }
+    return new DeviceNDArray(Int32Array.from(p.shape), C);
   }
   toHost(NDA) { return new (NDA || NDArray)(Int32Array.from(this.shape), this.data); }
   dispose() { this._buf.free(); }                // optional: dropped arrays are freed by the GC finalizer
@@ -1301,6 +1421,27 @@ function makeLa(NDA, fallback, SolveError, Complex) {
     Object.defineProperty(la, name, {value: f, writable: true, enumerable: false, configurable: true});
   }
 
+  /* ---- zip_elems (zip_elems.js) on device arrays, csrc/elem.hip: (ndarrays, 'float64', zip_fn) as the reference's nd.zip_elems, for
+   * the closures that are one IEEE operation on float64. zip_fn is an operator name ('add', 'sub', 'mul', 'div', 'min', 'max', 'neg',
+   * 'abs') or a function identical to the host module's nd.math member (standalone: this package's `math`); the number of arrays
+   * is the operator's arity (the reference appends the index to the arguments, so math.min over one array is no minimum). At least
+   * one array must be a DeviceNDArray; host arrays and plain numbers (0-d) are uploaded on the way in. The result is a
+   * DeviceNDArray. Not enumerable, like concat: nd.la has no such name, the reference's own is nd.zip_elems. ---- */
+  const zip_elems = function (ndarrays, dtype, zip_fn) {
+    if (zip_fn == null && typeof dtype === 'function') { zip_fn = dtype; dtype = undefined; }
+    const arrays = Array.from(ndarrays, a => typeof a === 'number' ? {shape: new Int32Array(0), data: Float64Array.of(a)} : asarray(a));
+    if (!arrays.some(isDev)) throw new Error('nd4hip.zip_elems: no device array among the arguments.');
+    const op = ewName(zip_fn);
+    if (op === null || EW_ARITY[op] !== arrays.length) throw new Error('nd4hip.zip_elems: zip_fn is not accelerated.');
+    if (dtype !== 'float64' || arrays.some(a => dtypeOf(a) !== 'float64')) throw new Error('nd4hip.zip_elems: dtype is not accelerated.');
+    const plan = zipPlan(arrays.map(a => a.shape)), temps = [];
+    try {
+      const bufs = arrays.map(a => { if (isDev(a)) return a._buf; const b = DevBuf.from(a.data); temps.push(b); return b; });
+      return new DeviceNDArray(Int32Array.from(plan.shape), zipBox(op, plan, bufs));
+    } finally { release(temps); }
+  };
+  Object.defineProperty(la, 'zip_elems', {value: zip_elems, writable: true, enumerable: false, configurable: true});
+
   // complex128 device arrays are accepted by matmul2 / matmul only: every other function refuses them before it looks at the
   // buffer (which holds 2n doubles, not n float64 entries)
   const complexOk = new Set(['matmul2', 'matmul', 'eigen_balance_post', '_chain_plan', 'to_device', 'to_host', 'synchronize', 'profile_enable', 'profile_last']);
@@ -1369,6 +1510,7 @@ function install(nd, opts) {
                     tril: nd.la.tril, triu: nd.la.triu, diag: nd.la.diag, diag_mat: nd.la.diag_mat,
                     permute_rows: nd.la.permute_rows, permute_cols: nd.la.permute_cols,
                     unpermute_rows: nd.la.unpermute_rows, unpermute_cols: nd.la.unpermute_cols};
+  if (nd.math && !mathTables.includes(nd.math)) mathTables.push(nd.math);       // its closures name the device operators (zip_elems, mapElems, reduceElems)
   const acc = makeLa(nd.NDArray, original, nd.la.SingularMatrixSolveError || SingularMatrixSolveError, (nd.dt && nd.dt.Complex128Array) || null);
   const target = Object.isFrozen(nd.la) || !Object.getOwnPropertyDescriptor(nd.la, 'matmul2').writable ? null : nd.la;
   const patched = target || Object.create(nd.la);
@@ -1401,7 +1543,7 @@ function install(nd, opts) {
     return f;
   };
   for (const k of Object.keys(original)) Object.defineProperty(patched, k, {value: route(k), writable: true, enumerable: true, configurable: true});
-  for (const k of ['to_device', 'to_host', 'synchronize', 'DeviceNDArray', 'profile_enable', 'profile_last', 'schur_qrfrancis', 'concat', 'stack'])   // §8f N3 / §8b extensions, not in the reference (schur_qrfrancis: its private step)
+  for (const k of ['to_device', 'to_host', 'synchronize', 'DeviceNDArray', 'profile_enable', 'profile_last', 'schur_qrfrancis', 'concat', 'stack', 'zip_elems'])   // §8f N3 / §8b extensions, not in the reference (schur_qrfrancis: its private step)
     Object.defineProperty(patched, k, {value: acc[k], writable: true, enumerable: false, configurable: true});
   if (!target) { try { nd.la = patched; } catch (e) { /* exported getter: caller uses the returned object */ } }
   patched.__nd4hip_original__ = original;
@@ -1413,7 +1555,7 @@ function install(nd, opts) {
 
 module.exports = Object.assign(standalone, {
   NDArray, DeviceNDArray, SingularMatrixSolveError, install, bcastGroups, complexOver,
-  slicePlan, transposePlan, reshapeShape, concatPlan, stackPlan, reduceBox,
+  slicePlan, transposePlan, reshapeShape, concatPlan, stackPlan, reduceBox, zipPlan, reducePlan, math,
   accelerated: a => !!a && (isDev(a) || a.data instanceof Float64Array || a.data instanceof Int32Array),
   device_count: () => native().device_count(),
   devices: () => native().devices(),            // ids behind the handle (ND4HIP_DEVICES=all|0,1,...: batched host calls are sharded)

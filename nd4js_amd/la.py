@@ -1673,3 +1673,99 @@ def _box_reach(shape, strides, off):
         else:
             hi += span
     return lo, hi
+
+
+# planners of the elementwise kernels (csrc/elem.hip): nd.zip_elems' broadcast rule (zip_elems.js:43-53) and NDArray.reduceElems'
+# axes (nd_array.js:479-497) on shapes alone, with the reference's texts. Pure host code.
+EW_OPS = {"add": 0, "sub": 1, "mul": 2, "div": 3, "min": 4, "max": 5, "neg": 16, "abs": 17}
+EW_UNARY = ("neg", "abs")
+EW_REDUCERS = ("add", "mul", "min", "max")
+EW_MAX_ND = 8
+
+
+def _zip_plan(shapes):
+    """zip_elems on shapes: (shape, strides, box). shape is the broadcast result; strides[k][d] is operand k's stride along result
+    axis d in elements of its own C order, 0 where it is broadcast; box = (box_shape, box_strides, loop) is the same reduced for
+    nd4hip_dzip_nd_dev: extent-1 axes dropped, neighbours merged where every operand (and the dense result) allows, what exceeds
+    EW_MAX_ND axes peeled off the outer end into `loop`, a list of (offset of each operand ..., offset in the result)."""
+    shapes = [[int(s) for s in sh] for sh in shapes]
+    ndim = max([len(sh) for sh in shapes] + [0])
+    shape = [1] * ndim
+    for sh in shapes:
+        for i, j in zip(range(ndim - 1, -1, -1), range(len(sh) - 1, -1, -1)):
+            if shape[i] == 1:
+                shape[i] = sh[j]
+            elif shape[i] != sh[j] and sh[j] != 1:
+                raise ValueError("Shapes are not broadcast-compatible.")
+    strides = []
+    for sh in shapes:
+        own, pad = _c_strides(sh), ndim - len(sh)
+        strides.append([0 if d < pad or sh[d - pad] == 1 else own[d - pad] for d in range(ndim)])
+    axes = [[shape[d], _c_strides(shape)[d]] + [st[d] for st in strides] for d in range(ndim) if shape[d] != 1]
+    merged = []
+    for ax in axes:
+        if merged and all(p == s * ax[0] for p, s in zip(merged[-1][1:], ax[1:])):
+            merged[-1] = [merged[-1][0] * ax[0]] + ax[1:]
+        else:
+            merged.append(list(ax))
+    cut = max(0, len(merged) - EW_MAX_ND)
+    loop = [tuple([0] * (len(shapes) + 1))]
+    for ax in merged[:cut]:
+        loop = [tuple(o + i * s for o, s in zip(offs, ax[2:] + ax[1:2])) for offs in loop for i in range(ax[0])]
+    kept = merged[cut:]
+    box = ([ax[0] for ax in kept], [[ax[2 + k] for ax in kept] for k in range(len(shapes))], loop)
+    return shape, strides, box
+
+
+def _reduce_axes(ndim, axes):
+    """the set of reduced axes as nd_array.js:479-493 reads them: a number, a list, or a 1-D int32 array; negative axes wrap,
+    duplicates collapse"""
+    if isinstance(axes, np.ndarray):
+        if axes.dtype != np.int32:
+            raise ValueError("Invalid dtype %s for axes." % ("object" if axes.dtype == object else axes.dtype.name))
+        if axes.ndim != 1:
+            raise ValueError("Only 1D nd.Array allowed for axes.")
+        axes = axes.tolist()
+    elif isinstance(axes, (int, float, np.integer, np.floating)) and not isinstance(axes, (bool, np.bool_)):
+        axes = [axes]
+    out = set()
+    for ax in axes:
+        if not _integral(ax):
+            raise TypeError("axes must be integers")
+        ax = int(ax)
+        if ax < 0:
+            ax += ndim
+        if ax < 0 or ax >= ndim:
+            raise ValueError("Reduction axis %d out of bounds." % ax)
+        out.add(ax)
+    return out
+
+
+def _reduce_plan(shape, axes):
+    """reduceElems on a shape: (out_shape, box_shape, box_flags, loop). box is what nd4hip_dreduce_nd_dev takes: extent-1 axes
+    dropped and neighbours of one kind merged, so that kept (flag 0) and reduced (flag 1) axes alternate; kept axes beyond
+    EW_MAX_ND are peeled off the outer end into `loop`, a list of (offset in the operand, offset in the result)."""
+    shape = [int(s) for s in shape]
+    red = _reduce_axes(len(shape), axes)
+    out_shape = [n for d, n in enumerate(shape) if d not in red]
+    merged = []
+    for d, n in enumerate(shape):
+        if n == 1:
+            continue
+        f = 1 if d in red else 0
+        if merged and merged[-1][1] == f:
+            merged[-1][0] *= n
+        else:
+            merged.append([n, f])
+    loop = [(0, 0)]
+    while len(merged) > EW_MAX_ND and merged[0][1] == 0:
+        n = merged.pop(0)[0]
+        a_step, c_step = 1, 1
+        for m, f in merged:
+            a_step *= m
+            if not f:
+                c_step *= m
+        loop = [(a + i * a_step, c + i * c_step) for a, c in loop for i in range(n)]
+    if len(merged) > EW_MAX_ND:
+        raise ValueError("reduceElems: more than %d alternating kept and reduced axes are not accelerated." % EW_MAX_ND)
+    return out_shape, [m[0] for m in merged], [m[1] for m in merged], loop
