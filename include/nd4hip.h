@@ -29,7 +29,7 @@ typedef struct nd4hip_handle nd4hip_handle;
 #define ND4HIP_OK            0
 #define ND4HIP_ERR_ARG      -1   /* bad argument / shape */
 #define ND4HIP_ERR_HIP      -2   /* HIP runtime error (message has the hipError string) */
-#define ND4HIP_ERR_NOCONV   -3   /* Jacobi SVD hit the sweep limit */
+#define ND4HIP_ERR_NOCONV   -3   /* Jacobi SVD hit the sweep limit; the divide & conquer SVD met one of the reference's assertions */
 #define ND4HIP_ERR_NODEV    -4   /* no usable GPU */
 #define ND4HIP_ERR_SINGULAR -5   /* Cholesky met a NaN pivot: 'Matrix contains NaNs or is (near) singular.'; dsytrf_bk a zero column or NaN */
 #define ND4HIP_ERR_XCHG     -6   /* an exchange between co-resident workgroups INSIDE a kernel timed out (the row-split QR panels, the
@@ -524,6 +524,40 @@ int nd4hip_dgesvdj_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64
                                double* U, double* sv, double* V, int* sweeps_out, double* offnorm_out);
 int nd4hip_dgesvdj_batched    (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A,
                                double* U, double* sv, double* V, int* sweeps_out, double* offnorm_out);
+
+/* ---- svd_decomp by divide & conquer: the reference's own algorithm, src/la/svd_dc.js:37-932 (csrc/svd_dc.hip) ------------
+ * dgesdd: the contract of dgesvdj above, A [batch,M,N] -> U [batch,M,L], sv [batch,L] (>= 0, descending), V [batch,L,N], by the
+ * reference's route: bidiagonalise (dgebrd), solve the bidiagonal problem by divide & conquer (dbdsdc), U = U_b U2,
+ * V = V2[:K] V_b; M > N goes through the transpose (svd_dc.js:893-897). The same power-of-two scaling as dgesvdj makes any finite
+ * scale work. An opt-in second algorithm: nothing routes to it by default. min(M, N) <= 2048.
+ * dbdsdc: the solver alone, for an upper bidiagonal K x J matrix, J = K or K + 1 (the shapes dgebrd produces): d [batch,K] the
+ * diagonal, e [batch,J-1] the super-diagonal -> U2 [batch,K,K], sv [batch,K] (>= 0, descending), V2 [batch,J,J] (rows = right
+ * vectors), B = U2 diag(sv) V2[:K]. The reference's tree (split at n >> 1, closed-form leaves of 2 and 3 columns) and its stages
+ * per merge (deflation, secular roots by bisection in the shifted variable, the Gu-Eisenstat z, the two W matrices), one launch
+ * per stage and level; the merges' products run on the fp64 MFMA GEMM. Sums and products across lanes are ordered differently
+ * from the reference's loops: results agree with it to rounding, not bit for bit. Members are independent: a member's result
+ * does not depend on the rest of the batch. K <= 2048.
+ * Where the reference throws 'Assertion failed.' (svd_dc.js:393 sLo > sHi, :405 / :429 a non-finite secular sum, :507 / :583 a W
+ * row of norm 0, ...; non-finite input ends here or in NaN outputs) the device raises a per-call flag word with that line. All
+ * four forms read it back once at the end (they synchronise) and return ND4HIP_ERR_NOCONV with nd4hip_last_error
+ * 'svd_dc: Assertion failed. (svd_dc.js:<line>)'; the outputs are unspecified then and the handle stays usable. Every loop on the
+ * device has a fixed bound (the bisection: 1200 steps, csrc/svd_dc.hip), so no input can hold the device.
+ * dbdsdc_levels needs no device: the level list that replaces the recursion for a problem of n = K + 1 columns, as (level, off,
+ * n) triples in launch order (level 0: the leaves; then the merges of each depth, the deepest first). Returns the number of
+ * nodes; at most `capacity` triples are written. */
+int nd4hip_dbdsdc_batched_dev(nd4hip_handle* h, int64_t batch, int64_t K, int64_t J, const double* d, const double* e,
+                              double* U2, double* sv, double* V2);
+int nd4hip_dbdsdc_batched    (nd4hip_handle* h, int64_t batch, int64_t K, int64_t J, const double* d, const double* e,
+                              double* U2, double* sv, double* V2);
+int nd4hip_dgesdd_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* U, double* sv, double* V);
+int nd4hip_dgesdd_batched    (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* U, double* sv, double* V);
+int nd4hip_dbdsdc_levels(int64_t n, int32_t* nodes, int64_t capacity);
+/* HIP-event time per stage of the LAST dgesdd / dbdsdc call made on this handle while nd4hip_profile_enable was on (all zero
+ * otherwise), in ms, summed over the levels: bidiagonalisation (with the scaling and the transposes), leaves, preparation and
+ * deflation, secular roots, z recomputation and inner order, the two W matrices, the merges' products, the final two products.
+ * Writes min(capacity, ND4HIP_DC_STAGES) values; returns ND4HIP_DC_STAGES. */
+#define ND4HIP_DC_STAGES 8
+int nd4hip_dgesdd_last_stages(nd4hip_handle* h, double* ms, int capacity);
 
 /* ---- one Householder panel on its own: geqr2 + larft of a 16-column panel (the inner step of qr_decomp, src/la/qr.js:54-68
  * eliminates the same entries column by column with Givens rotations) ---------------------------------------------

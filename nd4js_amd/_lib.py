@@ -143,6 +143,12 @@ SIGNATURES = {
                                            ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_double)]),
     "nd4hip_dgesvdj_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp,
                                        ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_double)]),
+    "nd4hip_dbdsdc_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "nd4hip_dbdsdc_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "nd4hip_dgesdd_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp]),
+    "nd4hip_dgesdd_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp]),
+    "nd4hip_dbdsdc_levels": (c_int, [c_i64, ctypes.POINTER(ctypes.c_int32), c_i64]),
+    "nd4hip_dgesdd_last_stages": (c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), c_int]),
     "nd4hip_dgeqr2_panel_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
     "nd4hip_profile_enable": (c_int, [ctypes.c_void_p, c_int]),
     "nd4hip_profile_last": (c_int, [ctypes.c_void_p, ctypes.c_void_p, c_int]),
@@ -243,6 +249,16 @@ class Handle:
         sw, rot, off = c_int(0), ctypes.c_ulonglong(0), ctypes.c_double(0.0)
         check(self.lib.nd4hip_dgesvdj_last_info(self._h, ctypes.byref(sw), ctypes.byref(rot), ctypes.byref(off)))
         return {"sweeps": sw.value, "rotations": rot.value, "offnorm": off.value}
+
+    SVD_DC_STAGES = ("bidiag", "leaves", "prep", "roots", "zhat", "w", "merge", "final")
+
+    def svd_dc_last_stages(self):
+        """ms per stage of the last svd_decomp(algo='dc') / bidiag_svd made with the profile enabled (nd4hip_dgesdd_last_stages)"""
+        ms = (ctypes.c_double * len(self.SVD_DC_STAGES))()
+        n = self.lib.nd4hip_dgesdd_last_stages(self._h, ms, len(self.SVD_DC_STAGES))
+        if n < 0:
+            check(n)
+        return dict(zip(self.SVD_DC_STAGES, ms))
 
     def close(self):
         if self._h:

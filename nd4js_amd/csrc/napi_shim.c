@@ -52,6 +52,7 @@ static int (*p_dgebrd[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const doubl
 static int (*p_dgehrd[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*, double*);
 static int (*p_dgeqrf_qty[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, double*, double*);
 static gesvdj_fn p_dgesvdj[2];
+static int (*p_dgesdd[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, double*, double*, double*);
 static int (*p_svd_info)(nd4hip_handle*, int*, unsigned long long*, double*);
 static qrls_fn p_dqrls[2];
 static int (*p_dgeqp3[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, double*, double*, int32_t*);
@@ -142,6 +143,7 @@ static int load_library(void) {
   SYM2(p_dgehrd, "nd4hip_dgehrd_batched");
   SYM2(p_dgebrd, "nd4hip_dgebrd_batched");
   SYM2(p_dgesvdj, "nd4hip_dgesvdj_batched");
+  SYM2(p_dgesdd, "nd4hip_dgesdd_batched");
   SYM2(p_dgetrs, "nd4hip_dgetrs_batched");
   SYM2(p_dpotrf, "nd4hip_dpotrf_batched");
   SYM2(p_dpotrs, "nd4hip_dpotrs_batched");
@@ -451,6 +453,19 @@ static napi_value js_dgesvdj(napi_env env, napi_callback_info info) {
   FAIL_IF(p_svd_info(g_handle, NULL, &rot, NULL));
   napi_create_double(env, (double)rot, &v); napi_set_named_property(env, r, "rotations", v);     /* exact up to 2^53 */
   return r;
+}
+/* dgesdd_batched(batch, M, N, A, U, sv, V)   (svd_decomp by divide & conquer, svd_dc.js:883-932) */
+static napi_value js_dgesdd(napi_env env, napi_callback_info info) {
+  ARGS(7, "dgesdd_batched");
+  int64_t batch, M, N; opnd A, U, S, V;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &M) || get_i64(env, a[2], &N) || F64(3, A) || F64(4, U) || F64(5, S) || F64(6, V)) return NULL;
+  int64_t L = M < N ? M : N;
+  NEED(batch >= 0 && M >= 0 && N >= 0 && (size_t)(batch * M * N) <= A.len && (size_t)(batch * M * L) <= U.len &&
+       (size_t)(batch * L) <= S.len && (size_t)(batch * L * N) <= V.len, "dgesdd_batched: buffer too small");
+  SAME_SIDE(A.dev == U.dev && U.dev == S.dev && S.dev == V.dev, "dgesdd_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dgesdd[A.dev](g_handle, batch, M, N, (const double*)A.p, (double*)U.p, (double*)S.p, (double*)V.p));
+  return NULL;
 }
 
 /* dgetrs_batched(batch, N, J, LU, strideLU, P, strideP, Y, strideY, X)   (lu_solve, lu.js:84-177) */
@@ -1097,6 +1112,7 @@ static napi_value init(napi_env env, napi_value exports) {
     {"dgebrd_batched", NULL, js_dgebrd, NULL, NULL, NULL, napi_default, NULL},
     {"dgehrd_batched", NULL, js_dgehrd, NULL, NULL, NULL, napi_default, NULL},
     {"dgesvdj_batched", NULL, js_dgesvdj, NULL, NULL, NULL, napi_default, NULL},
+    {"dgesdd_batched", NULL, js_dgesdd, NULL, NULL, NULL, napi_default, NULL},
     {"dgetrs_batched", NULL, js_dgetrs, NULL, NULL, NULL, napi_default, NULL},
     {"dqrls_batched", NULL, js_dqrls, NULL, NULL, NULL, napi_default, NULL},
     {"dsvdls_batched", NULL, js_dsvdls, NULL, NULL, NULL, napi_default, NULL},

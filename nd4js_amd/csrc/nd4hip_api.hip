@@ -760,6 +760,46 @@ extern "C" int nd4hip_dgesvdj_batched_dev(nd4hip_handle* h, int64_t batch, int64
   return 0;
 }
 
+// ---- svd_decomp by divide & conquer (svd_dc.js:883-932) and its bidiagonal solver (svd_dc.hip)
+extern "C" int nd4hip_dbdsdc_levels(int64_t n, int32_t* nodes, int64_t capacity) {
+  ND4_CHECK_ARG(n >= 2 && n <= (1 << 20), "nd4hip_dbdsdc_levels: 2 <= n <= 2^20 columns");
+  ND4_CHECK_ARG(capacity >= 0 && (nodes || capacity == 0), "nd4hip_dbdsdc_levels: NULL nodes");
+  return nd4_bdsdc_plan(n, nodes, capacity);
+}
+
+extern "C" int nd4hip_dbdsdc_batched_dev(nd4hip_handle* h, int64_t batch, int64_t K, int64_t J, const double* d, const double* e,
+                                         double* U2, double* sv, double* V2) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dbdsdc_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  // the merges: about 2 K^3 flops each for U and for V over the whole tree
+  Nd4Prof prof(h, "dbdsdc_batched", 4.0 * batch * (double)K * K * K, 8.0 * batch * (double)(2 * K + J - 1 + K * K + J * J));
+  ND4_CHECK_ARG(batch >= 0 && K >= 0, "nd4hip_dbdsdc_batched: negative extent");
+  ND4_CHECK_ARG(J == K || J == K + 1, "nd4hip_dbdsdc_batched: B must be K x K or K x (K+1)");
+  if (batch == 0 || K == 0) return 0;
+  ND4_CHECK_ARG(d && (e || J < 2) && U2 && sv && V2, "nd4hip_dbdsdc_batched: NULL pointer");
+  ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_bdsdc_rows(h, nb, K, J, d + b0 * K, e ? e + b0 * (J - 1) : nullptr, U2 + b0 * K * K, sv + b0 * K, V2 + b0 * J * J));
+  return 0;
+}
+
+extern "C" int nd4hip_dgesdd_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A,
+                                         double* U, double* sv, double* V) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dgesdd_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "svd_dc", (double)(batch * nd4_flops_svd(M, N)), (double)(8.0 * batch * (double)(M * N + (M + N + 1) * (M < N ? M : N))));
+  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dgesdd_batched: negative extent");
+  if (batch == 0 || M == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(A && U && sv && V, "nd4hip_dgesdd_batched: NULL pointer");
+  { const int64_t L = M < N ? M : N;
+    ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_gesdd(h, nb, M, N, A + b0 * M * N, U + b0 * M * L, sv + b0 * L, V + b0 * L * N)); }
+  return 0;
+}
+
+extern "C" int nd4hip_dgesdd_last_stages(nd4hip_handle* h, double* ms, int capacity) {
+  ND4_CHECK_ARG(h != nullptr && (ms != nullptr || capacity <= 0), "nd4hip_dgesdd_last_stages: NULL argument");
+  for (int i = 0; i < capacity && i < ND4HIP_DC_STAGES; ++i) ms[i] = h->dc_stage_ms[i];
+  return ND4HIP_DC_STAGES;
+}
+
 extern "C" int nd4hip_dgeqr2_panel_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t b, double* A, double* V, double* T) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgeqr2_panel_batched: NULL handle");
   Nd4DeviceGuard guard(h);

@@ -999,3 +999,31 @@ extern "C" int nd4hip_dgesvdj_batched(nd4hip_handle* h, int64_t batch, int64_t M
   if (offnorm_out) *offnorm_out = of;
   return 0;
 }
+
+// svd_decomp by divide & conquer and the bidiagonal solver (svd_dc.hip)
+extern "C" int nd4hip_dgesdd_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* U, double* sv, double* V) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dgesdd_batched: NULL handle");
+  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dgesdd_batched: negative extent");
+  if (batch == 0 || M == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(A && U && sv && V, "nd4hip_dgesdd_batched: NULL pointer");
+  const int64_t L = M < N ? M : N;
+  std::vector<Operand> ops{in_op(A, M * N, M * N), out_op(U, M * L), out_op(sv, L), out_op(V, L * N)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_dgesdd_batched_dev(hd, nb, M, N, P(d, 0), P(d, 1), P(d, 2), P(d, 3)); };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_dbdsdc_batched(nd4hip_handle* h, int64_t batch, int64_t K, int64_t J, const double* d, const double* e,
+                                     double* U2, double* sv, double* V2) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dbdsdc_batched: NULL handle");
+  ND4_CHECK_ARG(batch >= 0 && K >= 0, "nd4hip_dbdsdc_batched: negative extent");
+  ND4_CHECK_ARG(J == K || J == K + 1, "nd4hip_dbdsdc_batched: B must be K x K or K x (K+1)");
+  if (batch == 0 || K == 0) return 0;
+  ND4_CHECK_ARG(d && (e || J < 2) && U2 && sv && V2, "nd4hip_dbdsdc_batched: NULL pointer");
+  if (J < 2) {                                    // 1 x 1: there is no super-diagonal to move
+    std::vector<Operand> ops{in_op(d, K, K), out_op(U2, K * K), out_op(sv, K), out_op(V2, J * J)};
+    ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) { return nd4hip_dbdsdc_batched_dev(hd, nb, K, J, P(p, 0), nullptr, P(p, 1), P(p, 2), P(p, 3)); };
+    return run_host(h, batch, ops, fn);
+  }
+  std::vector<Operand> ops{in_op(d, K, K), in_op(e, J - 1, J - 1), out_op(U2, K * K), out_op(sv, K), out_op(V2, J * J)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) { return nd4hip_dbdsdc_batched_dev(hd, nb, K, J, P(p, 0), P(p, 1), P(p, 2), P(p, 3), P(p, 4)); };
+  return run_host(h, batch, ops, fn);
+}

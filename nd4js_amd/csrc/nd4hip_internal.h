@@ -33,6 +33,7 @@ struct nd4hip_handle {
   int svd_sweeps = 0; unsigned long long svd_rotations = 0; double svd_offnorm = 0.0;   // audit of the last SVD call
   bool prof_on = false, prof_valid = false; int prof_depth = 0;                          // nd4hip_profile_enable / _last
   hipEvent_t ev_p0 = nullptr, ev_p1 = nullptr; double prof_flops = 0.0, prof_bytes = 0.0; char prof_op[32] = "";
+  double dc_stage_ms[ND4HIP_DC_STAGES] = {0};   // per-stage times of the last divide & conquer SVD run with the profile enabled
 };
 
 // Makes h->device the calling thread's current HIP device for the duration of an entry point and restores the previous
@@ -163,6 +164,15 @@ const char* nd4_permute_name(int cols, int inverse);
 bool nd4_struct_overlap(const void* in, int64_t in_elems, const void* out, int64_t out_elems);
 int nd4_gesvdj(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A,
                double* U, double* sv, double* V, int* sweeps_out, double* offnorm_out);
+// the exact power-of-two scaling of the SVD entries (svd.hip): max|a| per member, dst = 2^-e src, sv *= 2^e
+int nd4_svd_scale_begin(nd4hip_handle* h, int64_t batch, int64_t n, const double* A, unsigned long long* mx);
+int nd4_svd_scale_apply(nd4hip_handle* h, int64_t batch, int64_t n, const double* src, double* dst, const unsigned long long* mx);
+int nd4_svd_scale_undo(nd4hip_handle* h, int64_t batch, int64_t L, double* sv, const unsigned long long* mx);
+// divide & conquer SVD (svd_dc.hip): the level list of n columns as (level, off, n) triples; the bidiagonal solver with V2 as
+// rows; svd_decomp through bidiagonalisation. The last two synchronise once to read the assertion flag.
+int nd4_bdsdc_plan(int64_t n, int32_t* out, int64_t capacity);
+int nd4_bdsdc_rows(nd4hip_handle* h, int64_t batch, int64_t K, int64_t J, const double* d, const double* e, double* U2, double* sv, double* V2);
+int nd4_gesdd(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* U, double* sv, double* V);
 
 // small utility kernels (nd4hip_core.hip)
 int nd4_copy_matrix(nd4hip_handle* h, int64_t rows, int64_t cols, const double* src, int64_t lds,

@@ -543,3 +543,23 @@ int nd4_gesvdj(nd4hip_handle* h, int64_t batch64, int64_t M64, int64_t N64, cons
   ND4_TRY(nd4_gemm(h, false, true, M, N, M, 1.0, Vr, M, sL, Q, M, sA, 0.0, V, N, sA, batch));
   return unscale();
 }
+
+// The scaling above for the divide & conquer route (svd_dc.hip): mx [batch] receives max|a| of every member (n elements each,
+// members n apart), _apply writes dst = 2^-e src (dst may be src), _undo multiplies the L values of every member by 2^e.
+int nd4_svd_scale_begin(nd4hip_handle* h, int64_t batch, int64_t n, const double* A, unsigned long long* mx) {
+  ND4_HIP(hipMemsetAsync(mx, 0, sizeof(unsigned long long) * (size_t)batch, h->stream));
+  hipLaunchKernelGGL(svd_absmax, svd_scale_grid((long)n, (int)batch), dim3(256), 0, h->stream, A, (long)n, (long)n, mx);
+  ND4_HIP(hipGetLastError());
+  return 0;
+}
+int nd4_svd_scale_apply(nd4hip_handle* h, int64_t batch, int64_t n, const double* src, double* dst, const unsigned long long* mx) {
+  hipLaunchKernelGGL(svd_scale, svd_scale_grid((long)n, (int)batch), dim3(256), 0, h->stream, src, dst, (long)n, (long)n, mx);
+  ND4_HIP(hipGetLastError());
+  return 0;
+}
+int nd4_svd_scale_undo(nd4hip_handle* h, int64_t batch, int64_t L, double* sv, const unsigned long long* mx) {
+  const long total = (long)batch * L;
+  hipLaunchKernelGGL(svd_unscale, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, sv, (long)L, total, mx);
+  ND4_HIP(hipGetLastError());
+  return 0;
+}

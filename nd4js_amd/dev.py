@@ -138,7 +138,10 @@ def qr_decomp(A):
     return Q, R
 
 
-def svd_decomp(A, info=None):
+def svd_decomp(A, info=None, algo=None):
+    """algo None / 'jacobi': block one-sided Jacobi (the default route); 'dc': bidiagonalisation + divide & conquer (opt-in)"""
+    if algo not in (None, "jacobi", "dc"):
+        raise ValueError("svd_decomp(A, algo): algo must be None, 'jacobi' or 'dc'.")
     _chk(A, "A")
     if A.dim() < 2:
         raise ValueError("svd_decomp(A): A.ndim must be at least 2.")
@@ -150,12 +153,32 @@ def svd_decomp(A, info=None):
     V = torch.empty(lead + (L, N), dtype=torch.float64, device=A.device)
     sweeps, off = ctypes.c_int(0), ctypes.c_double(0.0)
     h = _h(A)
+    if algo == "dc":
+        _lib.check(h.lib.nd4hip_dgesdd_batched_dev(h.ptr, _batch(lead), M, N, _p(A), _p(U), _p(sv), _p(V)))
+        return U, sv, V
     _lib.check(h.lib.nd4hip_dgesvdj_batched_dev(h.ptr, _batch(lead), M, N, _p(A), _p(U), _p(sv), _p(V),
                                                 ctypes.byref(sweeps), ctypes.byref(off)))
     if info is not None:
         info["sweeps"], info["offnorm"] = sweeps.value, off.value
         info["rotations"] = h.svd_last_info()["rotations"]
     return U, sv, V
+
+
+def bidiag_svd(d, e):
+    """device-resident la.bidiag_svd: d [..., K], e [..., J-1] (J = K or K + 1) -> U2 [..., K, K], sv [..., K], V2 [..., J, J]"""
+    _chk(d, "d"), _chk(e, "e")
+    if d.dim() < 1 or e.dim() < 1 or tuple(d.shape[:-1]) != tuple(e.shape[:-1]):
+        raise ValueError("bidiag_svd(d,e): d and e must have the same leading dimensions.")
+    K, J = d.shape[-1], e.shape[-1] + 1
+    if K < 1 or J not in (K, K + 1):
+        raise ValueError("bidiag_svd(d,e): e must have len(d) - 1 or len(d) entries.")
+    lead = tuple(d.shape[:-1])
+    U2 = torch.empty(lead + (K, K), dtype=torch.float64, device=d.device)
+    sv = torch.empty(lead + (K,), dtype=torch.float64, device=d.device)
+    V2 = torch.empty(lead + (J, J), dtype=torch.float64, device=d.device)
+    h = _h(d)
+    _lib.check(h.lib.nd4hip_dbdsdc_batched_dev(h.ptr, _batch(lead), K, J, _p(d), _p(e), _p(U2), _p(sv), _p(V2)))
+    return U2, sv, V2
 
 
 def lu_solve(LU, P, Y):

@@ -680,7 +680,10 @@ function makeLa(NDA, fallback, SolveError, Complex) {
     return [wrap(dev, A.shape, LU), wrap(dev, A.shape.subarray(0, nd_ - 1), P)];
   };
 
-  la.svd_decomp = function svd_decomp(A) {
+  // opts.algo: undefined / 'jacobi' (the default route) or 'dc' (bidiagonalisation + divide & conquer, svd_dc.js's own algorithm)
+  la.svd_decomp = function svd_decomp(A, opts) {
+    const algo = opts == null ? undefined : opts.algo;
+    if (algo !== undefined && algo !== null && algo !== 'jacobi' && algo !== 'dc') throw new Error("svd_decomp(A, {algo}): algo must be 'jacobi' or 'dc'.");
     A = asarray(A);
     if (String(dtypeOf(A)).startsWith('complex')) throw new Error('svd_dc(A): A.dtype must be float.');
     if (A.ndim < 2) throw new Error('svd_decomp(A): A.ndim must be at least 2.');
@@ -689,7 +692,8 @@ function makeLa(NDA, fallback, SolveError, Complex) {
     const Us = Int32Array.from(A.shape), Vs = Int32Array.from(A.shape); Us[nd_ - 1] = L; Vs[nd_ - 2] = L;
     const dev = isDev(A), temps = [];
     const U = alloc(dev, batch * M * L), sv = alloc(dev, batch * L), V = alloc(dev, batch * L * N);
-    la.last_svd_info = native().dgesvdj_batched(batch, M, N, view(opF64(A, dev, temps), 0), view(U, 0), view(sv, 0), view(V, 0));
+    if (algo === 'dc') native().dgesdd_batched(batch, M, N, view(opF64(A, dev, temps), 0), view(U, 0), view(sv, 0), view(V, 0));
+    else la.last_svd_info = native().dgesvdj_batched(batch, M, N, view(opF64(A, dev, temps), 0), view(U, 0), view(sv, 0), view(V, 0));
     release(temps);
     return [wrap(dev, Us, U), wrap(dev, Vs.subarray(0, nd_ - 1), sv), wrap(dev, Vs, V)];
   };

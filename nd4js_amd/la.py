@@ -6,7 +6,8 @@ JS wrapper nd4js_amd/js/index.js over the N-API shim; both call the same libnd4h
   matmul(*ms)          src/la/matmul.js:150-236     (chain ordering stays on the host)
   qr_decomp(A)         src/la/qr.js:80-145          -> nd4hip_dgeqrf_q_batched
   lu_decomp(A)         src/la/lu.js:24-81           -> nd4hip_dgetrf_batched
-  svd_decomp(A)        src/la/svd.js:25             -> nd4hip_dgesvdj_batched
+  svd_decomp(A)        src/la/svd.js:25             -> nd4hip_dgesvdj_batched; algo='dc' (opt-in): nd4hip_dgesdd_batched
+  bidiag_svd(d, e)     src/la/svd_dc.js:169-824     -> nd4hip_dbdsdc_batched
 
 Inputs are numpy arrays / nested lists (NDArray analogue: dense, row-major, leading axes = batch).
 Only float64 (and int32 promoted to float64 for QR/LU/SVD, as qr.js:31-37, lu.js:27, svd_dc.js:904
@@ -228,7 +229,18 @@ def lu_decomp(A, device=None):
     return LU, P
 
 
-def svd_decomp(A, device=None, info=None):
+def _svd_algo(algo):
+    """None / 'jacobi': block one-sided Jacobi (the default route); 'dc': bidiagonalisation + divide & conquer, the
+    reference's own algorithm (svd_dc.js), opt-in"""
+    if algo is None or algo == "jacobi":
+        return False
+    if algo == "dc":
+        return True
+    raise ValueError("svd_decomp(A, algo): algo must be None, 'jacobi' or 'dc'.")
+
+
+def svd_decomp(A, device=None, info=None, algo=None):
+    dc = _svd_algo(algo)
     A = np.asarray(A)
     if np.iscomplexobj(A):
         raise TypeError("svd_dc(A): A.dtype must be float.")
@@ -243,6 +255,9 @@ def svd_decomp(A, device=None, info=None):
     V = np.empty(A.shape[:-2] + (L, N))
     sweeps, off = ctypes.c_int(0), ctypes.c_double(0.0)
     h = _lib.handle(device)
+    if dc:
+        _lib.check(h.lib.nd4hip_dgesdd_batched(h.ptr, batch, M, N, _ptr(A), _ptr(U), _ptr(sv), _ptr(V)))
+        return U, sv, V
     _lib.check(h.lib.nd4hip_dgesvdj_batched(h.ptr, batch, M, N, _ptr(A), _ptr(U), _ptr(sv), _ptr(V),
                                             ctypes.byref(sweeps), ctypes.byref(off)))
     if info is not None:
@@ -252,6 +267,24 @@ def svd_decomp(A, device=None, info=None):
 
 
 svd_dc = svd_decomp
+
+
+def bidiag_svd(d, e, device=None):
+    """SVD of the upper bidiagonal K x J matrix with diagonal d [..., K] and super-diagonal e [..., J-1], J = K or K + 1 (the
+    shapes bidiag_decomp produces), by the reference's divide & conquer (svd_dc.js:169-824):
+    (U2 [..., K, K], sv [..., K] >= 0 descending, V2 [..., J, J] with rows = right vectors), B = U2 diag(sv) V2[:K]."""
+    d = _asarray(d, "bidiag_svd(d,e)")
+    e = _asarray(e, "bidiag_svd(d,e)")
+    if d.ndim < 1 or e.ndim < 1 or d.shape[:-1] != e.shape[:-1]:
+        raise ValueError("bidiag_svd(d,e): d and e must have the same leading dimensions.")
+    K, J = d.shape[-1], e.shape[-1] + 1
+    if K < 1 or J not in (K, K + 1):
+        raise ValueError("bidiag_svd(d,e): e must have len(d) - 1 or len(d) entries.")
+    lead = d.shape[:-1]
+    U2, sv, V2 = np.empty(lead + (K, K)), np.empty(lead + (K,)), np.empty(lead + (J, J))
+    h = _lib.handle(device)
+    _lib.check(h.lib.nd4hip_dbdsdc_batched(h.ptr, int(np.prod(lead, dtype=np.int64)), K, J, _ptr(d), _ptr(e), _ptr(U2), _ptr(sv), _ptr(V2)))
+    return U2, sv, V2
 
 
 # ---------------------------------------------------------------------------------------------------
