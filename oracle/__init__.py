@@ -59,6 +59,8 @@ def lib():
         L.nd4o_svd_lstsq.restype = ctypes.c_int
         L.nd4o_svd_dc.restype = ctypes.c_int
         L.nd4o_svd_dc.argtypes = [_i64, _i64, _i64, _dp, _dp, _dp, _dp]
+        L.nd4o_bidiag_svd_dc.restype = ctypes.c_int
+        L.nd4o_bidiag_svd_dc.argtypes = [_i64, _i64, _dp, _dp, _dp, _dp, _dp, _ip, _i64, ctypes.POINTER(_i64)]
         L.nd4o_svd_jac_2sided.restype = ctypes.c_int
         L.nd4o_svd_jac_2sided.argtypes = [_i64, _i64, _dp, _dp, _dp, _dp]
         _lib = L
@@ -154,6 +156,37 @@ def svd_dc(a):
 
 
 svd_decomp = svd_dc          # svd.js:25
+
+DC_STAT_FIELDS = ("off", "n", "n0", "n1", "shift_hi", "hh_zero", "rot_last", "rot_chain")
+
+
+def bidiag_svd_dc(d, e, stats=False):
+    """_svd_dc_bidiag (svd_dc.js:666-824) on the upper bidiagonal K x J matrix with diagonal d [K] and super-diagonal e [J-1],
+    J = K or K + 1, with no bidiagonalisation in front: (U2 [K,K], sv [K], V2 [J,J] with rows as right vectors), the contract of
+    la.bidiag_svd. stats=True also returns one dict per merge in the recursion's order: off, n (the node), n0, n1 (the deflation
+    counts), shift_hi (roots shifted to the upper pole), hh_zero (zero middle row), rot_last (rotations whose partner is m - 1),
+    rot_chain (rotations that share their partner with the rotation before them)."""
+    d, e = _f64(d), _f64(e)
+    if d.ndim != 1 or e.ndim != 1:
+        raise ValueError("bidiag_svd_dc(d,e): one problem per call.")
+    K, J = d.shape[0], e.shape[0] + 1
+    if K < 1 or J not in (K, K + 1):
+        raise ValueError("bidiag_svd_dc(d,e): e must have len(d) - 1 or len(d) entries.")
+    u2, sv, v2 = np.empty((K, K)), np.empty(K), np.empty((J, J))
+    nf = len(DC_STAT_FIELDS)
+    rec = np.zeros((K, nf), dtype=np.int32)               # a tree of K + 1 columns has fewer than K merges
+    count = _i64(0)
+    rc = lib().nd4o_bidiag_svd_dc(K, J, _d(d), _d(e), _d(u2), _d(sv), _d(v2), _i(rec) if stats else None, K, ctypes.byref(count))
+    if rc != 0:
+        raise RuntimeError("svd_dc: 'Assertion failed.' (svd_dc.js:%d)" % rc if rc > 0 else "svd_dc: out of memory")
+    if not stats:
+        return u2, sv, v2
+    records = []
+    for r in rec[:count.value]:
+        q = dict(zip(DC_STAT_FIELDS, (int(x) for x in r)))
+        q["hh_zero"] = bool(q["hh_zero"])
+        records.append(q)
+    return u2, sv, v2, records
 
 
 def svd_jac_2sided(a):

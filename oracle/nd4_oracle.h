@@ -90,6 +90,16 @@ int nd4o_svd_jac_2sided(int64_t batch, int64_t N, const double* A, double* U, do
  * nd4_oracle_svd_dc.c: A [batch,M,N] -> U [batch,M,L], sv [batch,L], V [batch,L,N], L = min(M,N). Returns 0, the line number of
  * the reference assertion that failed, or -1 (out of memory). */
 int nd4o_svd_dc(int64_t batch, int64_t M, int64_t N, const double* A, double* U, double* sv, double* V);
+/* src/la/svd_dc.js:666-824 _svd_dc_bidiag alone (no bidiagonalisation in front) on the K x (K+1) upper bidiagonal problem with
+ * diagonal d [K] and super-diagonal e [J-1], J = K or K + 1 (J = K: e[K-1] = 0): U2 [K,K], sv [K], V2 [J,J] with rows as right
+ * vectors. stats (or NULL) receives one record of ND4O_DC_STAT_FIELDS int32 per merge in the recursion's order, at most
+ * stats_cap records: off, n (the node: n columns at column off), n0, n1 (the two deflation counts, :261-378), shift_hi (roots
+ * whose shift went to the upper pole, :396-412), hh_zero (the Givens norm of :779-782 is 0), rot_last (deflation rotations
+ * whose partner is index m - 1), rot_chain (deflation rotations that share their partner with the rotation before them: three
+ * or more equal values). *stats_n receives the number of merges. Returns like nd4o_svd_dc. */
+#define ND4O_DC_STAT_FIELDS 8
+int nd4o_bidiag_svd_dc(int64_t K, int64_t J, const double* d, const double* e, double* U2, double* sv, double* V2,
+                       int32_t* stats, int64_t stats_cap, int64_t* stats_n);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,14 @@
 #define JS_MIN_VALUE 4.9406564584124654e-324                    /* Number.MIN_VALUE */
 #define JS_EPSILON   2.220446049250313e-16                      /* Number.EPSILON = eps('float64'), dt/index.js:33-43 */
 
+/* Which path each merge took, for nd4o_bidiag_svd_dc(..., stats): one record of ND4O_DC_STAT_FIELDS int32 per merge in the
+ * recursion's order (children before their parent). NULL outside that call, so nd4o_svd_dc computes what it always did: the
+ * records only count, no floating-point statement depends on them. */
+enum { DC_STAT_OFF = 0, DC_STAT_N, DC_STAT_N0, DC_STAT_N1, DC_STAT_SHIFT_HI, DC_STAT_HH_ZERO, DC_STAT_ROT_LAST, DC_STAT_ROT_CHAIN };
+static int32_t* dc_stats = NULL;          /* the caller's records */
+static int64_t dc_stats_cap = 0, dc_stats_n = 0, dc_stats_B0 = 0;
+static int32_t* dc_stat_cur = NULL;       /* the record of the merge that is running */
+
 static double fro_result(const fro_t* f) { return isfinite(f->max) ? sqrt(f->sum) * f->max : f->max; }   /* norm.js:59-62 */
 static double js_sign(double x) { return x > 0 ? 1.0 : (x < 0 ? -1.0 : x); }                            /* Math.sign: +-0 and NaN pass */
 
@@ -153,6 +161,8 @@ static int svd_dc_neves(int64_t N, int64_t n, double* U, int64_t U_off, double* 
         F[B_off + 2 * j] = F[s_off + n1] = di;
         I[out_off + n1] = oi;
         I[rot_off + n1] = (int32_t)j;
+        if (dc_stat_cur && j == m - 1) ++dc_stat_cur[DC_STAT_ROT_LAST];
+        if (dc_stat_cur && n1 > n0 && I[rot_off + n1 - 1] == j) ++dc_stat_cur[DC_STAT_ROT_CHAIN];
         ++n1;
       } else {
         --j;
@@ -166,6 +176,7 @@ static int svd_dc_neves(int64_t N, int64_t n, double* U, int64_t U_off, double* 
     F[B_off + i] = F[W_off + i];
     F[W_off + i] = 0;
   }
+  if (dc_stat_cur) { dc_stat_cur[DC_STAT_N0] = (int32_t)n0; dc_stat_cur[DC_STAT_N1] = (int32_t)n1; }
 
   /* STEP 3: the secular equations by bisection (:388-436) */
   for (int64_t i = n1; i < m; i++) {
@@ -185,6 +196,7 @@ static int svd_dc_neves(int64_t N, int64_t n, double* U, int64_t U_off, double* 
         if (!isfinite(sum)) SVD_DC_FAIL(405);
         if (sum < 0) { const double s = sHi; sLo = sLo - sHi; sHi = -JS_MIN_VALUE; shift = s; taken = 1; }
       }
+      if (dc_stat_cur && taken) ++dc_stat_cur[DC_STAT_SHIFT_HI];
       if (!taken) { const double s = sLo; sHi = sHi - sLo; sLo = +JS_MIN_VALUE; shift = s; }
     }
     for (;;) {
@@ -371,7 +383,15 @@ static int svd_dc_bidiag(int64_t N, int64_t n, double* U, int64_t U_off, double*
   nd4o_giv_rot_qr(b1 * F[V_off + N * m0 + m0], b2 * F[V_off + N * n0 + m], &c, &s, &h);         /* :779-782 */
   F[B_off + 2 * m0] = 0;
   F[B_off + 2 * m0 + 1] = h;
-  if (0 != h) {                                                                                  /* :789-794 */
+  dc_stat_cur = NULL;
+  if (dc_stats && dc_stats_n < dc_stats_cap) {
+    dc_stat_cur = dc_stats + ND4O_DC_STAT_FIELDS * dc_stats_n++;
+    memset(dc_stat_cur, 0, sizeof(int32_t) * ND4O_DC_STAT_FIELDS);
+    dc_stat_cur[DC_STAT_OFF] = (int32_t)((B_off - dc_stats_B0) / 2);
+    dc_stat_cur[DC_STAT_N] = (int32_t)n;
+    dc_stat_cur[DC_STAT_HH_ZERO] = 0 == h;
+  }
+  if (0 != h) {                                                                                 /* :789-794 */
     for (int64_t i = 0; i < n0; i++) { F[V_off + N * i + m] = F[V_off + N * i + m0] * -s; F[V_off + N * i + m0] *= c; }
     for (int64_t i = n0; i < n; i++) { F[V_off + N * i + m0] = F[V_off + N * i + m] * s; F[V_off + N * i + m] *= c; }
   }
@@ -453,6 +473,36 @@ int nd4o_svd_dc(int64_t batch, int64_t M, int64_t N, const double* A, double* U,
     for (int64_t e = 0; e < M * M; e++) u[e] = 0.0;
     memcpy(v, A + b * M * N, sizeof(double) * (size_t)(M * N));
     rc = svd_dc1(M, N, u, sv + b * M, v, I, F);
+  }
+  free(F); free(I);
+  return rc;
+}
+
+/* svd_dc.js:666-824 alone: _svd_dc_bidiag on the K x (K + 1) upper bidiagonal problem with diagonal d [K] and super-diagonal
+ * e [J - 1], J = K or K + 1 (J = K: e[K-1] = 0), set up as svd_dc1 sets it up but with no bidiagonalisation in front.
+ * U2 [K,K], sv [K], V2 [J,J] with rows as right vectors (the transpose of the reference's V1, cut to J). stats (or NULL)
+ * receives one record of ND4O_DC_STAT_FIELDS int32 per merge, in the recursion's order, at most stats_cap of them:
+ * (off, n, n0, n1, shift_hi, hh_zero, rot_last, rot_chain); *stats_n receives how many merges ran. Returns like nd4o_svd_dc. */
+int nd4o_bidiag_svd_dc(int64_t K, int64_t J, const double* d, const double* e, double* U2, double* sv, double* V2,
+                       int32_t* stats, int64_t stats_cap, int64_t* stats_n) {
+  const int64_t M = K, B_off = M * (M + 2), V1_off = B_off + M * 2;
+  if (K < 1 || (J != K && J != K + 1)) return 682;
+  double* F = (double*)calloc((size_t)(V1_off + (M + 1) * (M + 1)), sizeof(double));
+  int32_t* I = (int32_t*)calloc((size_t)(M * 3 + 3), sizeof(int32_t));
+  if (!F || !I) { free(F); free(I); return -1; }
+  for (int64_t i = 0; i < M; i++) {
+    F[B_off + 2 * i] = d[i];
+    F[B_off + 2 * i + 1] = i < J - 1 ? e[i] : 0.0;
+  }
+  for (int64_t i = 0; i < M * M; i++) U2[i] = 0.0;
+  dc_stats = stats; dc_stats_cap = stats ? stats_cap : 0; dc_stats_n = 0; dc_stats_B0 = B_off; dc_stat_cur = NULL;
+  const int rc = svd_dc_bidiag(M + 1, M + 1, U2, 0, F, B_off, V1_off, I);
+  if (stats_n) *stats_n = dc_stats_n;
+  dc_stats = NULL; dc_stat_cur = NULL; dc_stats_cap = 0;
+  if (rc == 0) {
+    for (int64_t i = 0; i < M; i++) sv[i] = F[B_off + 2 * i];
+    for (int64_t i = 0; i < J; i++)
+      for (int64_t j = 0; j < J; j++) V2[J * i + j] = F[V1_off + (M + 1) * j + i];
   }
   free(F); free(I);
   return rc;
