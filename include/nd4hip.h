@@ -559,6 +559,25 @@ int nd4hip_dbdsdc_levels(int64_t n, int32_t* nodes, int64_t capacity);
 #define ND4HIP_DC_STAGES 8
 int nd4hip_dgesdd_last_stages(nd4hip_handle* h, double* ms, int capacity);
 
+/* ---- eigen_sym / eigenvals_sym: the symmetric eigenproblem (planned by the reference, src/la/eigen.js:28-30; csrc/syev.hip) ----
+ * S [batch,N,N] symmetric, read ONLY in its lower triangle (j <= i; the upper triangle may hold anything, NaN included) and never
+ * written -> lambda [batch,N] descending and V [batch,N,N] with the eigenvectors as columns: S V = V diag(lambda), V^T V = I.
+ * V = NULL: the values alone (the same bits as with V). Route: the mirrored lower triangle, scaled by an exact power of two, is
+ * tridiagonalised by dgehrd; T is shifted by c = g (1 + 2^-20), g its Gershgorin bound, into a positive definite matrix whose
+ * bidiagonal Cholesky factor B goes to dbdsdc; lambda = sv^2 - c, V = U V2^T. The error of every eigenvalue is a few
+ * eps ||S||_F in absolute terms: small eigenvalues of a graded matrix are accurate relative to ||S||, not to themselves.
+ * N = 0 and N = 1 need no solver; N > 2048 (the solver's limit) is ND4HIP_ERR_ARG before anything is written. NaN or Inf in
+ * the lower triangle: ND4HIP_ERR_NOCONV with 'eigen_sym(S): S contains NaN or Infinity in its lower triangle.' (one flag word
+ * per call, read back at the end; the outputs are unspecified then, the solver ran on finite stand-in data, the handle stays
+ * usable). Members are independent of the rest of the batch. Both forms synchronise. */
+int nd4hip_dsyevd_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V);
+int nd4hip_dsyevd_batched    (nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V);
+/* HIP-event time per stage of the LAST dsyevd call (one chunk of <= 32768 members) made on this handle while
+ * nd4hip_profile_enable was on (all zero otherwise), in ms: symmetrise and scale, tridiagonal reduction, shift and Cholesky,
+ * bidiagonal solver, values and the vectors' GEMM. Writes min(capacity, ND4HIP_SYEV_STAGES) values; returns ND4HIP_SYEV_STAGES. */
+#define ND4HIP_SYEV_STAGES 5
+int nd4hip_dsyevd_last_stages(nd4hip_handle* h, double* ms, int capacity);
+
 /* ---- one Householder panel on its own: geqr2 + larft of a 16-column panel (the inner step of qr_decomp, src/la/qr.js:54-68
  * eliminates the same entries column by column with Givens rotations) ---------------------------------------------
  * A [batch,M,16] (1 <= M <= 2048) is overwritten with R in its top 16 x 16 (entries below the diagonal are left as the kernel

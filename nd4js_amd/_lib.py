@@ -149,6 +149,9 @@ SIGNATURES = {
     "nd4hip_dgesdd_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp]),
     "nd4hip_dbdsdc_levels": (c_int, [c_i64, ctypes.POINTER(ctypes.c_int32), c_i64]),
     "nd4hip_dgesdd_last_stages": (c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), c_int]),
+    "nd4hip_dsyevd_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_dsyevd_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_dsyevd_last_stages": (c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), c_int]),
     "nd4hip_dgeqr2_panel_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
     "nd4hip_profile_enable": (c_int, [ctypes.c_void_p, c_int]),
     "nd4hip_profile_last": (c_int, [ctypes.c_void_p, ctypes.c_void_p, c_int]),
@@ -259,6 +262,16 @@ class Handle:
         if n < 0:
             check(n)
         return dict(zip(self.SVD_DC_STAGES, ms))
+
+    EIGSYM_STAGES = ("symm", "reduce", "chol", "solve", "gemm")
+
+    def eigsym_last_stages(self):
+        """ms per stage of the last eigen_sym / eigenvals_sym made with the profile enabled (nd4hip_dsyevd_last_stages)"""
+        ms = (ctypes.c_double * len(self.EIGSYM_STAGES))()
+        n = self.lib.nd4hip_dsyevd_last_stages(self._h, ms, len(self.EIGSYM_STAGES))
+        if n < 0:
+            check(n)
+        return dict(zip(self.EIGSYM_STAGES, ms))
 
     def close(self):
         if self._h:

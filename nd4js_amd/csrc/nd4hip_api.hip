@@ -800,6 +800,27 @@ extern "C" int nd4hip_dgesdd_last_stages(nd4hip_handle* h, double* ms, int capac
   return ND4HIP_DC_STAGES;
 }
 
+// ---- eigen_sym / eigenvals_sym (syev.hip). Algorithmic flops per matrix: 10/3 N^3 for the reduction with U (4/3 N^3 for T, 2 N^3
+// for U), 2 N^3 for the eigenvector half of the solver's merges, 2 N^3 for V = U V2^T; without V the last term drops out
+extern "C" int nd4hip_dsyevd_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dsyevd_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  const double n3 = (double)N * N * N;
+  Nd4Prof prof(h, "dsyevd_batched", batch * ((10.0 / 3.0 + 2.0 + (V ? 2.0 : 0.0)) * n3), 8.0 * batch * (double)(N * N / 2 + N + (V ? N * N : 0)));
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsyevd_batched: negative extent");
+  ND4_CHECK_ARG(N <= 2048, "nd4hip_dsyevd_batched: the divide & conquer solver takes N <= 2048");
+  if (batch == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(S && lambda, "nd4hip_dsyevd_batched: NULL pointer");
+  ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_syevd(h, nb, N, S + b0 * N * N, lambda + b0 * N, V ? V + b0 * N * N : nullptr));
+  return 0;
+}
+
+extern "C" int nd4hip_dsyevd_last_stages(nd4hip_handle* h, double* ms, int capacity) {
+  ND4_CHECK_ARG(h != nullptr && (ms != nullptr || capacity <= 0), "nd4hip_dsyevd_last_stages: NULL argument");
+  for (int i = 0; i < capacity && i < ND4HIP_SYEV_STAGES; ++i) ms[i] = h->syev_stage_ms[i];
+  return ND4HIP_SYEV_STAGES;
+}
+
 extern "C" int nd4hip_dgeqr2_panel_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t b, double* A, double* V, double* T) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgeqr2_panel_batched: NULL handle");
   Nd4DeviceGuard guard(h);

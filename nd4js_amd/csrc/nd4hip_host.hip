@@ -1027,3 +1027,20 @@ extern "C" int nd4hip_dbdsdc_batched(nd4hip_handle* h, int64_t batch, int64_t K,
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) { return nd4hip_dbdsdc_batched_dev(hd, nb, K, J, P(p, 0), P(p, 1), P(p, 2), P(p, 3), P(p, 4)); };
   return run_host(h, batch, ops, fn);
 }
+
+// eigen_sym / eigenvals_sym (syev.hip); V = NULL: the values alone
+extern "C" int nd4hip_dsyevd_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dsyevd_batched: NULL handle");
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsyevd_batched: negative extent");
+  ND4_CHECK_ARG(N <= 2048, "nd4hip_dsyevd_batched: the divide & conquer solver takes N <= 2048");
+  if (batch == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(S && lambda, "nd4hip_dsyevd_batched: NULL pointer");
+  if (!V) {
+    std::vector<Operand> ops{in_op(S, N * N, N * N), out_op(lambda, N)};
+    ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_dsyevd_batched_dev(hd, nb, N, P(d, 0), P(d, 1), nullptr); };
+    return run_host(h, batch, ops, fn);
+  }
+  std::vector<Operand> ops{in_op(S, N * N, N * N), out_op(lambda, N), out_op(V, N * N)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_dsyevd_batched_dev(hd, nb, N, P(d, 0), P(d, 1), P(d, 2)); };
+  return run_host(h, batch, ops, fn);
+}

@@ -34,6 +34,7 @@ struct nd4hip_handle {
   bool prof_on = false, prof_valid = false; int prof_depth = 0;                          // nd4hip_profile_enable / _last
   hipEvent_t ev_p0 = nullptr, ev_p1 = nullptr; double prof_flops = 0.0, prof_bytes = 0.0; char prof_op[32] = "";
   double dc_stage_ms[ND4HIP_DC_STAGES] = {0};   // per-stage times of the last divide & conquer SVD run with the profile enabled
+  double syev_stage_ms[ND4HIP_SYEV_STAGES] = {0};   // the same for the last symmetric eigenproblem (syev.hip)
 };
 
 // Makes h->device the calling thread's current HIP device for the duration of an entry point and restores the previous
@@ -173,6 +174,8 @@ int nd4_svd_scale_undo(nd4hip_handle* h, int64_t batch, int64_t L, double* sv, c
 int nd4_bdsdc_plan(int64_t n, int32_t* out, int64_t capacity);
 int nd4_bdsdc_rows(nd4hip_handle* h, int64_t batch, int64_t K, int64_t J, const double* d, const double* e, double* U2, double* sv, double* V2);
 int nd4_gesdd(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* U, double* sv, double* V);
+// symmetric eigenproblem (syev.hip): lower triangle of S -> lambda descending, V columns (V may be NULL); synchronises
+int nd4_syevd(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V);
 
 // small utility kernels (nd4hip_core.hip)
 int nd4_copy_matrix(nd4hip_handle* h, int64_t rows, int64_t cols, const double* src, int64_t lds,

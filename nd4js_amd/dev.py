@@ -751,6 +751,34 @@ def eigenvals(A):
     return L
 
 
+def _syevd(S, what, vectors):
+    if isinstance(S, torch.Tensor) and S.dtype != torch.float64:
+        raise TypeError("%s: S.dtype must be float." % what)
+    _chk(S, "S")
+    if S.dim() < 2:
+        raise ValueError("%s: S.ndim must be at least 2." % what)
+    N = S.shape[-1]
+    if S.shape[-2] != N:
+        raise ValueError("%s: S must be quadratic." % what)
+    lead = tuple(S.shape[:-2])
+    L = torch.empty(lead + (N,), dtype=torch.float64, device=S.device)
+    V = torch.empty(lead + (N, N), dtype=torch.float64, device=S.device) if vectors else None
+    h = _h(S)
+    _lib.check(h.lib.nd4hip_dsyevd_batched_dev(h.ptr, _batch(lead), N, _p(S), _p(L), _p(V) if vectors else None))
+    return (L, V) if vectors else L
+
+
+def eigen_sym(S):
+    """device-resident la.eigen_sym: (eigenvalues [..., N] descending, eigenvectors [..., N, N] as columns), float64; only the
+    lower triangle of S is read and S is not written"""
+    return _syevd(S, "eigen_sym(S)", True)
+
+
+def eigenvals_sym(S):
+    """device-resident la.eigenvals_sym: the eigenvalues of eigen_sym alone, the same bits"""
+    return _syevd(S, "eigenvals_sym(S)", False)
+
+
 # ---- structure functions (csrc/struct.hip): values are moved, never computed; nothing leaves the device ----
 def _struct_call(fn, *args):
     from .la import _arg_error

@@ -1446,6 +1446,33 @@ function makeLa(NDA, fallback, SolveError, Complex) {
   };
   Object.defineProperty(la, 'zip_elems', {value: zip_elems, writable: true, enumerable: false, configurable: true});
 
+  /* ---- eigen_sym / eigenvals_sym, csrc/syev.hip: the functions the reference plans at eigen.js:28-30. S [..., N, N] float64, read
+   * only in its lower triangle -> [eigenvalues [..., N] descending, eigenvectors [..., N, N] as columns], resp. the eigenvalues alone.
+   * Host arrays or DeviceNDArrays in, the same kind out. Not enumerable, like concat: the reference's nd.la has no such names. ---- */
+  const eigSym = (name, vectors) => {
+    const f = function (S) {
+      S = asarray(S);
+      if (isComplexDev(S) || String(dtypeOf(S)).startsWith('complex')) throw new TypeError(`${name}(S): S.dtype must be float.`);
+      if (S.ndim < 2) throw new Error(`${name}(S): S.ndim must be at least 2.`);
+      const nd_ = S.ndim, N = S.shape[nd_ - 1];
+      if (S.shape[nd_ - 2] != N) throw new Error(`${name}(S): S must be quadratic.`);
+      if (!gpuOk(S)) throw new TypeError(`${name}(S): dtype ${dtypeOf(S)} is not accelerated.`);
+      const batch = prod(S.shape, 0, nd_ - 2), dev = isDev(S), temps = [];
+      const L = alloc(dev, batch * N), V = vectors ? alloc(dev, batch * N * N) : null;
+      try {
+        if (vectors) native().dsyevd_batched(batch, N, view(opF64(S, dev, temps), 0), view(L, 0), view(V, 0));
+        else native().dsyevals_batched(batch, N, view(opF64(S, dev, temps), 0), view(L, 0));
+      }
+      catch (e) { if (dev) { L.free(); if (V) V.free(); } throw e; }
+      finally { release(temps); }
+      const Lw = wrap(dev, S.shape.subarray(0, nd_ - 1), L);
+      return vectors ? [Lw, wrap(dev, S.shape, V)] : Lw;
+    };
+    Object.defineProperty(f, 'name', {value: name});
+    Object.defineProperty(la, name, {value: f, writable: true, enumerable: false, configurable: true});
+  };
+  eigSym('eigen_sym', true); eigSym('eigenvals_sym', false);
+
   // complex128 device arrays are accepted by matmul2 / matmul only: every other function refuses them before it looks at the
   // buffer (which holds 2n doubles, not n float64 entries)
   const complexOk = new Set(['matmul2', 'matmul', 'eigen_balance_post', '_chain_plan', 'to_device', 'to_host', 'synchronize', 'profile_enable', 'profile_last']);
@@ -1547,7 +1574,7 @@ function install(nd, opts) {
     return f;
   };
   for (const k of Object.keys(original)) Object.defineProperty(patched, k, {value: route(k), writable: true, enumerable: true, configurable: true});
-  for (const k of ['to_device', 'to_host', 'synchronize', 'DeviceNDArray', 'profile_enable', 'profile_last', 'schur_qrfrancis', 'concat', 'stack', 'zip_elems'])   // §8f N3 / §8b extensions, not in the reference (schur_qrfrancis: its private step)
+  for (const k of ['to_device', 'to_host', 'synchronize', 'DeviceNDArray', 'profile_enable', 'profile_last', 'schur_qrfrancis', 'concat', 'stack', 'zip_elems', 'eigen_sym', 'eigenvals_sym'])   // §8f N3 / §8b extensions, not in the reference (schur_qrfrancis: its private step)
     Object.defineProperty(patched, k, {value: acc[k], writable: true, enumerable: false, configurable: true});
   if (!target) { try { nd.la = patched; } catch (e) { /* exported getter: caller uses the returned object */ } }
   patched.__nd4hip_original__ = original;

@@ -8,6 +8,7 @@ JS wrapper nd4js_amd/js/index.js over the N-API shim; both call the same libnd4h
   lu_decomp(A)         src/la/lu.js:24-81           -> nd4hip_dgetrf_batched
   svd_decomp(A)        src/la/svd.js:25             -> nd4hip_dgesvdj_batched; algo='dc' (opt-in): nd4hip_dgesdd_batched
   bidiag_svd(d, e)     src/la/svd_dc.js:169-824     -> nd4hip_dbdsdc_batched
+  eigen_sym(S), eigenvals_sym(S)   planned at src/la/eigen.js:28-30   -> nd4hip_dsyevd_batched
 
 Inputs are numpy arrays / nested lists (NDArray analogue: dense, row-major, leading axes = batch).
 Only float64 (and int32 promoted to float64 for QR/LU/SVD, as qr.js:31-37, lu.js:27, svd_dc.js:904
@@ -1116,6 +1117,35 @@ def eigen(A, device=None):
 def eigenvals(A, device=None):
     """eigen.js:83-88: schur_eigenvals of the Schur form of the balanced matrix, complex128 [..., N]."""
     return _geev(A, "eigenvals(A)", False, device)
+
+
+def _syevd(S, what, vectors, device):
+    S = np.asarray(S)
+    if np.iscomplexobj(S):
+        raise TypeError("%s: S.dtype must be float." % what)
+    if S.ndim < 2:
+        raise ValueError("%s: S.ndim must be at least 2." % what)
+    if S.shape[-2] != S.shape[-1]:
+        raise ValueError("%s: S must be quadratic." % what)
+    S = _asarray(S, what)
+    N = S.shape[-1]
+    L = np.empty(S.shape[:-1])
+    V = np.empty(S.shape) if vectors else None
+    h = _lib.handle(device)
+    _lib.check(h.lib.nd4hip_dsyevd_batched(h.ptr, int(np.prod(S.shape[:-2], dtype=np.int64)), N, _ptr(S), _ptr(L), _ptr(V) if vectors else None))
+    return (L, V) if vectors else L
+
+
+def eigen_sym(S, device=None):
+    """the function the reference plans at eigen.js:28-30: (eigenvalues float64 [..., N] descending, eigenvectors float64
+    [..., N, N] as columns) of the symmetric S, S V = V diag(L) and V^T V = I. Only the lower triangle of S is read. NaN or
+    Infinity there raises Nd4HipError with code -3. N <= 2048."""
+    return _syevd(S, "eigen_sym(S)", True, device)
+
+
+def eigenvals_sym(S, device=None):
+    """the eigenvalues of eigen_sym alone (the same bits); no eigenvector product is computed or stored"""
+    return _syevd(S, "eigenvals_sym(S)", False, device)
 
 
 # ---------------------------------------------------------------------------------------------------
