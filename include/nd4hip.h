@@ -565,7 +565,8 @@ int nd4hip_dgesdd_last_stages(nd4hip_handle* h, double* ms, int capacity);
  * V = NULL: the values alone (the same bits as with V). Route: the mirrored lower triangle, scaled by an exact power of two, is
  * tridiagonalised by dgehrd; T is shifted by c = g (1 + 2^-20), g its Gershgorin bound, into a positive definite matrix whose
  * bidiagonal Cholesky factor B goes to dbdsdc; lambda = sv^2 - c, V = U V2^T. The error of every eigenvalue is a few
- * eps ||S||_F in absolute terms: small eigenvalues of a graded matrix are accurate relative to ||S||, not to themselves.
+ * eps ||S||_F in absolute terms: small eigenvalues of a graded matrix are accurate relative to ||S||, not to themselves
+ * (for N <= 128 nd4hip_dsyevj_batched below delivers them to their own relative accuracy).
  * N = 0 and N = 1 need no solver; N > 2048 (the solver's limit) is ND4HIP_ERR_ARG before anything is written. NaN or Inf in
  * the lower triangle: ND4HIP_ERR_NOCONV with 'eigen_sym(S): S contains NaN or Infinity in its lower triangle.' (one flag word
  * per call, read back at the end; the outputs are unspecified then, the solver ran on finite stand-in data, the handle stays
@@ -577,6 +578,23 @@ int nd4hip_dsyevd_batched    (nd4hip_handle* h, int64_t batch, int64_t N, const 
  * bidiagonal solver, values and the vectors' GEMM. Writes min(capacity, ND4HIP_SYEV_STAGES) values; returns ND4HIP_SYEV_STAGES. */
 #define ND4HIP_SYEV_STAGES 5
 int nd4hip_dsyevd_last_stages(nd4hip_handle* h, double* ms, int capacity);
+
+/* ---- eigen_sym / eigenvals_sym, algo = 'jacobi': cyclic two-sided Jacobi for stacks of small matrices (csrc/syevj.hip) ----
+ * The same contract as dsyevd (lower triangle read only, S never written, lambda descending, eigenvectors as the columns of V,
+ * V = NULL: the values alone with the same bits and no V accumulated), for 1 <= N <= 128 (N = 0: nothing to do; N > 128 is
+ * ND4HIP_ERR_ARG before anything is written). Every member is solved inside one launch: N <= 32 one wave per member, N <= 64 one
+ * workgroup with S and V^T in LDS, N <= 128 one workgroup with S in LDS and V^T in global memory. A sweep is the round-robin
+ * tournament over all pairs; pair (p, q) is rotated iff s_pq != 0 and |s_pq| > eps sqrt|s_pp| sqrt|s_qq|, eps = 2^-52; a member
+ * is finished after a sweep that rotates nothing. sweeps [batch] (may be NULL) receives the sweeps of each member, that last
+ * one included; a member that needs more than 60: ND4HIP_ERR_NOCONV, 'eigen_sym(S, algo='jacobi'): no convergence after 60
+ * sweeps.' NaN or Inf in a lower triangle: ND4HIP_ERR_NOCONV with dsyevd's message; that member's outputs are not written.
+ * Accuracy: the bounds of dsyevd, and, for symmetric positive definite S with A = D^-1 S D^-1, D = diag(sqrt s_ii):
+ *   |lambda^ - lambda| <= N eps kappa_2(A) lambda   for EVERY eigenvalue,
+ * however small it is against ||S|| (the default route's errors are relative to ||S||). Members are scaled by an exact power
+ * of two: 2^k S gives bit-identical V and lambda 2^k while entries stay normal. A member's results do not depend on the batch.
+ * All arithmetic is rounded operation by operation (no FMA contraction, no reductions). Both forms synchronise. */
+int nd4hip_dsyevj_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V, int32_t* sweeps);
+int nd4hip_dsyevj_batched    (nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V, int32_t* sweeps);
 
 /* ---- one Householder panel on its own: geqr2 + larft of a 16-column panel (the inner step of qr_decomp, src/la/qr.js:54-68
  * eliminates the same entries column by column with Givens rotations) ---------------------------------------------

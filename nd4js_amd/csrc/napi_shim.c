@@ -74,6 +74,7 @@ static int (*p_dhseqr[2])(nd4hip_handle*, int64_t, int64_t, const double*, const
 static int (*p_dgees[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*, double*, int*);
 static int (*p_dgeev[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*, double*);
 static int (*p_dsyevd[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*, double*);
+static int (*p_dsyevj[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*, double*, int32_t*);
 static int (*p_dqp3rank[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, int32_t*);
 static int (*p_dqp3ls[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t,
                           const int32_t*, int64_t, const double*, int64_t, double*, int32_t*);
@@ -173,6 +174,7 @@ static int load_library(void) {
   SYM2(p_dgees, "nd4hip_dgees_batched");
   SYM2(p_dgeev, "nd4hip_dgeev_batched");
   SYM2(p_dsyevd, "nd4hip_dsyevd_batched");
+  SYM2(p_dsyevj, "nd4hip_dsyevj_batched");
   SYM2(p_dqp3rank, "nd4hip_dqp3rank_batched");
   SYM2(p_dsrrqr, "nd4hip_dsrrqr_batched");
   SYM2(p_durv, "nd4hip_durv_batched");
@@ -737,6 +739,29 @@ static napi_value js_dsyevals(napi_env env, napi_callback_info info) {
   FAIL_IF(p_dsyevd[S.dev](g_handle, batch, N, (const double*)S.p, (double*)L.p, NULL));
   return NULL;
 }
+/* dsyevj_batched(batch, N, S, L, V) / dsyevjals_batched(batch, N, S, L)   (eigen_sym / eigenvals_sym with {algo: 'jacobi'}, N <= 128;
+ * the sweep counts are not asked for) */
+static napi_value js_dsyevj(napi_env env, napi_callback_info info) {
+  ARGS(5, "dsyevj_batched");
+  int64_t batch, N; opnd S, L, V;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || F64(2, S) || F64(3, L) || F64(4, V)) return NULL;
+  NEED(batch >= 0 && N >= 0 && (size_t)(batch * N * N) <= S.len && (size_t)(batch * N) <= L.len && (size_t)(batch * N * N) <= V.len,
+       "dsyevj_batched: buffer too small");
+  SAME_SIDE(S.dev == L.dev && L.dev == V.dev, "dsyevj_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dsyevj[S.dev](g_handle, batch, N, (const double*)S.p, (double*)L.p, (double*)V.p, NULL));
+  return NULL;
+}
+static napi_value js_dsyevjals(napi_env env, napi_callback_info info) {
+  ARGS(4, "dsyevjals_batched");
+  int64_t batch, N; opnd S, L;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || F64(2, S) || F64(3, L)) return NULL;
+  NEED(batch >= 0 && N >= 0 && (size_t)(batch * N * N) <= S.len && (size_t)(batch * N) <= L.len, "dsyevjals_batched: buffer too small");
+  SAME_SIDE(S.dev == L.dev, "dsyevjals_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dsyevj[S.dev](g_handle, batch, N, (const double*)S.p, (double*)L.p, NULL, NULL));
+  return NULL;
+}
 /* dnrmfro(n, A) -> number   (norm(A) 'fro', norm.js:22-85); a device operand's result comes back as a host number too */
 static napi_value js_dnrmfro(napi_env env, napi_callback_info info) {
   ARGS(2, "dnrmfro");
@@ -1157,6 +1182,8 @@ static napi_value init(napi_env env, napi_value exports) {
     {"dgeevals_batched", NULL, js_dgeevals, NULL, NULL, NULL, napi_default, NULL},
     {"dsyevd_batched", NULL, js_dsyevd, NULL, NULL, NULL, napi_default, NULL},
     {"dsyevals_batched", NULL, js_dsyevals, NULL, NULL, NULL, napi_default, NULL},
+    {"dsyevj_batched", NULL, js_dsyevj, NULL, NULL, NULL, napi_default, NULL},
+    {"dsyevjals_batched", NULL, js_dsyevjals, NULL, NULL, NULL, napi_default, NULL},
     {"dqp3rank_batched", NULL, js_dqp3rank, NULL, NULL, NULL, napi_default, NULL},
     {"dsrrqr_batched", NULL, js_dsrrqr, NULL, NULL, NULL, napi_default, NULL},
     {"durv_batched", NULL, js_durv, NULL, NULL, NULL, napi_default, NULL},

@@ -815,6 +815,22 @@ extern "C" int nd4hip_dsyevd_batched_dev(nd4hip_handle* h, int64_t batch, int64_
   return 0;
 }
 
+// ---- eigen_sym / eigenvals_sym, algo = 'jacobi' (syevj.hip). The sweep count is not known beforehand: the profile counts 8 sweeps
+// (what a dense matrix of N <= 128 needs, give or take two) of 4 N^3 flops for S (2 x 2 blocks of the lower triangle, two
+// rotations each) and 4 N^3 for V^T
+extern "C" int nd4hip_dsyevj_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V, int32_t* sweeps) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dsyevj_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  const double n3 = (double)N * N * N;
+  Nd4Prof prof(h, "syevj", batch * 8.0 * (V ? 8.0 : 4.0) * n3, 8.0 * batch * (double)(N * N / 2 + N + (V ? N * N : 0)));
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsyevj_batched: negative extent");
+  ND4_CHECK_ARG(N <= 128, "nd4hip_dsyevj_batched: the Jacobi route takes N <= 128");
+  if (batch == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(S && lambda, "nd4hip_dsyevj_batched: NULL pointer");
+  ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_syevj(h, nb, N, S + b0 * N * N, lambda + b0 * N, V ? V + b0 * N * N : nullptr, sweeps ? sweeps + b0 : nullptr));
+  return 0;
+}
+
 extern "C" int nd4hip_dsyevd_last_stages(nd4hip_handle* h, double* ms, int capacity) {
   ND4_CHECK_ARG(h != nullptr && (ms != nullptr || capacity <= 0), "nd4hip_dsyevd_last_stages: NULL argument");
   for (int i = 0; i < capacity && i < ND4HIP_SYEV_STAGES; ++i) ms[i] = h->syev_stage_ms[i];

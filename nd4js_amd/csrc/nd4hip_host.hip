@@ -1044,3 +1044,22 @@ extern "C" int nd4hip_dsyevd_batched(nd4hip_handle* h, int64_t batch, int64_t N,
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_dsyevd_batched_dev(hd, nb, N, P(d, 0), P(d, 1), P(d, 2)); };
   return run_host(h, batch, ops, fn);
 }
+
+// the same with algo = 'jacobi' (syevj.hip); V = NULL: the values alone; sweeps = NULL: not wanted
+extern "C" int nd4hip_dsyevj_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V, int32_t* sweeps) {
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dsyevj_batched: NULL handle");
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsyevj_batched: negative extent");
+  ND4_CHECK_ARG(N <= 128, "nd4hip_dsyevj_batched: the Jacobi route takes N <= 128");
+  if (batch == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(S && lambda, "nd4hip_dsyevj_batched: NULL pointer");
+  // the operands that are wanted, in the order S, lambda, [V], [sweeps]
+  std::vector<Operand> ops{in_op(S, N * N, N * N), out_op(lambda, N)};
+  const int iv = V ? (int)ops.size() : -1;
+  if (V) ops.push_back(out_op(V, N * N));
+  const int is = sweeps ? (int)ops.size() : -1;
+  if (sweeps) ops.push_back(out_op(sweeps, 1, 4));
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
+    return nd4hip_dsyevj_batched_dev(hd, nb, N, P(d, 0), P(d, 1), iv >= 0 ? P(d, iv) : nullptr, is >= 0 ? static_cast<int32_t*>(d[is]) : nullptr);
+  };
+  return run_host(h, batch, ops, fn);
+}

@@ -176,6 +176,8 @@ int nd4_bdsdc_rows(nd4hip_handle* h, int64_t batch, int64_t K, int64_t J, const 
 int nd4_gesdd(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* U, double* sv, double* V);
 // symmetric eigenproblem (syev.hip): lower triangle of S -> lambda descending, V columns (V may be NULL); synchronises
 int nd4_syevd(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V);
+// the same by two-sided Jacobi in one launch (syevj.hip): 1 <= N <= 128; sweeps [batch] may be NULL; synchronises
+int nd4_syevj(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V, int32_t* sweeps);
 
 // small utility kernels (nd4hip_core.hip)
 int nd4_copy_matrix(nd4hip_handle* h, int64_t rows, int64_t cols, const double* src, int64_t lds,

@@ -751,7 +751,9 @@ def eigenvals(A):
     return L
 
 
-def _syevd(S, what, vectors):
+def _syevd(S, what, vectors, algo=None, info=None):
+    from .la import _eigsym_algo
+    jacobi = _eigsym_algo(algo, what)
     if isinstance(S, torch.Tensor) and S.dtype != torch.float64:
         raise TypeError("%s: S.dtype must be float." % what)
     _chk(S, "S")
@@ -764,19 +766,26 @@ def _syevd(S, what, vectors):
     L = torch.empty(lead + (N,), dtype=torch.float64, device=S.device)
     V = torch.empty(lead + (N, N), dtype=torch.float64, device=S.device) if vectors else None
     h = _h(S)
-    _lib.check(h.lib.nd4hip_dsyevd_batched_dev(h.ptr, _batch(lead), N, _p(S), _p(L), _p(V) if vectors else None))
+    if jacobi:
+        sweeps = torch.zeros(lead, dtype=torch.int32, device=S.device)
+        _lib.check(h.lib.nd4hip_dsyevj_batched_dev(h.ptr, _batch(lead), N, _p(S), _p(L), _p(V) if vectors else None, _p(sweeps)))
+        if info is not None:
+            info["sweeps"] = sweeps
+    else:
+        _lib.check(h.lib.nd4hip_dsyevd_batched_dev(h.ptr, _batch(lead), N, _p(S), _p(L), _p(V) if vectors else None))
     return (L, V) if vectors else L
 
 
-def eigen_sym(S):
+def eigen_sym(S, algo=None, info=None):
     """device-resident la.eigen_sym: (eigenvalues [..., N] descending, eigenvectors [..., N, N] as columns), float64; only the
-    lower triangle of S is read and S is not written"""
-    return _syevd(S, "eigen_sym(S)", True)
+    lower triangle of S is read and S is not written. algo='jacobi' (N <= 128): the one-launch Jacobi route; `info` then
+    receives 'sweeps', an int32 tensor [...] on the device."""
+    return _syevd(S, "eigen_sym(S)", True, algo, info)
 
 
-def eigenvals_sym(S):
+def eigenvals_sym(S, algo=None, info=None):
     """device-resident la.eigenvals_sym: the eigenvalues of eigen_sym alone, the same bits"""
-    return _syevd(S, "eigenvals_sym(S)", False)
+    return _syevd(S, "eigenvals_sym(S)", False, algo, info)
 
 
 # ---- structure functions (csrc/struct.hip): values are moved, never computed; nothing leaves the device ----

@@ -1448,9 +1448,14 @@ function makeLa(NDA, fallback, SolveError, Complex) {
 
   /* ---- eigen_sym / eigenvals_sym, csrc/syev.hip: the functions the reference plans at eigen.js:28-30. S [..., N, N] float64, read
    * only in its lower triangle -> [eigenvalues [..., N] descending, eigenvectors [..., N, N] as columns], resp. the eigenvalues alone.
-   * Host arrays or DeviceNDArrays in, the same kind out. Not enumerable, like concat: the reference's nd.la has no such names. ---- */
+   * Host arrays or DeviceNDArrays in, the same kind out. Not enumerable, like concat: the reference's nd.la has no such names.
+   * opts.algo: undefined / 'dc' (the default route) or 'jacobi' (csrc/syevj.hip, N <= 128: two-sided Jacobi in one launch, small
+   * eigenvalues of a positive definite S to their own relative accuracy). ---- */
   const eigSym = (name, vectors) => {
-    const f = function (S) {
+    const f = function (S, opts) {
+      const algo = opts == null ? undefined : opts.algo;
+      if (algo !== undefined && algo !== null && algo !== 'dc' && algo !== 'jacobi') throw new Error(`${name}(S, {algo}): algo must be 'dc' or 'jacobi'.`);
+      const jac = algo === 'jacobi';
       S = asarray(S);
       if (isComplexDev(S) || String(dtypeOf(S)).startsWith('complex')) throw new TypeError(`${name}(S): S.dtype must be float.`);
       if (S.ndim < 2) throw new Error(`${name}(S): S.ndim must be at least 2.`);
@@ -1460,8 +1465,8 @@ function makeLa(NDA, fallback, SolveError, Complex) {
       const batch = prod(S.shape, 0, nd_ - 2), dev = isDev(S), temps = [];
       const L = alloc(dev, batch * N), V = vectors ? alloc(dev, batch * N * N) : null;
       try {
-        if (vectors) native().dsyevd_batched(batch, N, view(opF64(S, dev, temps), 0), view(L, 0), view(V, 0));
-        else native().dsyevals_batched(batch, N, view(opF64(S, dev, temps), 0), view(L, 0));
+        if (vectors) native()[jac ? 'dsyevj_batched' : 'dsyevd_batched'](batch, N, view(opF64(S, dev, temps), 0), view(L, 0), view(V, 0));
+        else native()[jac ? 'dsyevjals_batched' : 'dsyevals_batched'](batch, N, view(opF64(S, dev, temps), 0), view(L, 0));
       }
       catch (e) { if (dev) { L.free(); if (V) V.free(); } throw e; }
       finally { release(temps); }

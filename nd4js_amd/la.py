@@ -8,7 +8,7 @@ JS wrapper nd4js_amd/js/index.js over the N-API shim; both call the same libnd4h
   lu_decomp(A)         src/la/lu.js:24-81           -> nd4hip_dgetrf_batched
   svd_decomp(A)        src/la/svd.js:25             -> nd4hip_dgesvdj_batched; algo='dc' (opt-in): nd4hip_dgesdd_batched
   bidiag_svd(d, e)     src/la/svd_dc.js:169-824     -> nd4hip_dbdsdc_batched
-  eigen_sym(S), eigenvals_sym(S)   planned at src/la/eigen.js:28-30   -> nd4hip_dsyevd_batched
+  eigen_sym(S), eigenvals_sym(S)   planned at src/la/eigen.js:28-30   -> nd4hip_dsyevd_batched; algo='jacobi' (opt-in): nd4hip_dsyevj_batched
 
 Inputs are numpy arrays / nested lists (NDArray analogue: dense, row-major, leading axes = batch).
 Only float64 (and int32 promoted to float64 for QR/LU/SVD, as qr.js:31-37, lu.js:27, svd_dc.js:904
@@ -1119,7 +1119,17 @@ def eigenvals(A, device=None):
     return _geev(A, "eigenvals(A)", False, device)
 
 
-def _syevd(S, what, vectors, device):
+def _eigsym_algo(algo, what):
+    """True for the Jacobi route (csrc/syevj.hip, N <= 128, opt-in); None / 'dc' is the default route (csrc/syev.hip)"""
+    if algo is None or algo == "dc":
+        return False
+    if algo == "jacobi":
+        return True
+    raise ValueError("%s: algo must be None, 'dc' or 'jacobi'." % what.replace("(S)", "(S, algo)"))
+
+
+def _syevd(S, what, vectors, device, algo=None, info=None):
+    jacobi = _eigsym_algo(algo, what)
     S = np.asarray(S)
     if np.iscomplexobj(S):
         raise TypeError("%s: S.dtype must be float." % what)
@@ -1132,20 +1142,31 @@ def _syevd(S, what, vectors, device):
     L = np.empty(S.shape[:-1])
     V = np.empty(S.shape) if vectors else None
     h = _lib.handle(device)
-    _lib.check(h.lib.nd4hip_dsyevd_batched(h.ptr, int(np.prod(S.shape[:-2], dtype=np.int64)), N, _ptr(S), _ptr(L), _ptr(V) if vectors else None))
+    batch = int(np.prod(S.shape[:-2], dtype=np.int64))
+    if jacobi:
+        sweeps = np.zeros(S.shape[:-2], dtype=np.int32)
+        _lib.check(h.lib.nd4hip_dsyevj_batched(h.ptr, batch, N, _ptr(S), _ptr(L), _ptr(V) if vectors else None, sweeps.ctypes.data))
+        if info is not None:
+            info["sweeps"] = sweeps
+    else:
+        _lib.check(h.lib.nd4hip_dsyevd_batched(h.ptr, batch, N, _ptr(S), _ptr(L), _ptr(V) if vectors else None))
     return (L, V) if vectors else L
 
 
-def eigen_sym(S, device=None):
+def eigen_sym(S, device=None, algo=None, info=None):
     """the function the reference plans at eigen.js:28-30: (eigenvalues float64 [..., N] descending, eigenvectors float64
     [..., N, N] as columns) of the symmetric S, S V = V diag(L) and V^T V = I. Only the lower triangle of S is read. NaN or
-    Infinity there raises Nd4HipError with code -3. N <= 2048."""
-    return _syevd(S, "eigen_sym(S)", True, device)
+    Infinity there raises Nd4HipError with code -3. N <= 2048.
+    algo None / 'dc': tridiagonalisation + divide & conquer (the default route). algo 'jacobi' (opt-in, N <= 128): every member by
+    cyclic two-sided Jacobi inside one launch; for positive definite S every eigenvalue, however small, is accurate to
+    N eps kappa_2(D^-1 S D^-1) relative to itself, D = diag(sqrt s_ii). `info` (a dict) then receives 'sweeps', int32 [...]."""
+    return _syevd(S, "eigen_sym(S)", True, device, algo, info)
 
 
-def eigenvals_sym(S, device=None):
-    """the eigenvalues of eigen_sym alone (the same bits); no eigenvector product is computed or stored"""
-    return _syevd(S, "eigenvals_sym(S)", False, device)
+def eigenvals_sym(S, device=None, algo=None, info=None):
+    """the eigenvalues of eigen_sym alone (the same bits); no eigenvector product is computed or stored. With algo='jacobi' no
+    eigenvector is accumulated at all."""
+    return _syevd(S, "eigenvals_sym(S)", False, device, algo, info)
 
 
 # ---------------------------------------------------------------------------------------------------
