@@ -12,14 +12,15 @@
 //         p_0 = sqrt(d_0 + c),  q_i = e_i / p_i,  p_i+1 = sqrt((d_i+1 + c) - q_i^2).
 //      lambda_min(2^k T + c I) >= c - g = 2^-20 g, and every Schur complement of a positive definite matrix is at least its
 //      smallest eigenvalue, so the exact radicand is >= 2^-20 and its computed value (three roundings of numbers <= 4.01) stays
-//      above 2^-20 - 2^-49: no pivot of finite input can be non-positive. A radicand that is not a positive finite number (NaN or
-//      Inf in the input) raises the call's flag word and the member gets the bidiagonal of the identity, so the solver sees
-//      finite data whatever the input was. A member with e = 0 throughout (a diagonal T: the identity, the zero matrix, a
-//      diagonal S) is marked: its eigenvalues are its d, which step 5 sorts instead of squaring and subtracting, so they are exact.
+//      above 2^-20 - 2^-49: no pivot of finite input can be non-positive. NaN or Inf in the lower triangle of S (max|s_ij| of
+//      step 1 above DBL_MAX: the entrance check) or in d, e raises the call's flag word and the member gets the bidiagonal of
+//      the identity, so the solver sees finite data whatever the input was. A member with e = 0 throughout (a diagonal T: the
+//      identity, the zero matrix, a diagonal S) is marked: its eigenvalues are its d, which step 5 sorts instead of squaring and
+//      subtracting, so they are exact.
 //   4. nd4_bdsdc_rows (svd_dc.hip, unchanged): B = U2 diag(sv) V2, sv descending. B^T B = V2^T diag(sv^2) V2: the rows of V2 are
 //      the eigenvectors of T.
-//   5. syev_values: lambda_i = 2^(e1 - k) (sv_i^2 - c), descending because sv is (a marked member: 2^e1 d by descending rank);
-//      V = U V2^T on the fp64 MFMA GEMM.
+//   5. syev_values: lambda_i = 2^(e1 - k) (sv_i^2 - c), descending because sv is (a marked member: 2^e1 d by descending rank, and
+//      the unit vectors in that order for the rows of V2); V = U V2^T on the fp64 MFMA GEMM.
 // The subtraction in 5 cancels: the error of lambda is absolute, a few eps g <= a few eps sqrt(3) ||S||_F, for every eigenvalue,
 // small ones included. That is the bound of any backward stable symmetric solver, not more.
 #include "nd4hip_internal.h"
@@ -33,6 +34,7 @@ typedef unsigned long long u64;
 
 constexpr int SYEV_TILE = 64;
 constexpr int SYEV_MAXN = 2048;            // the divide & conquer solver's limit; d and e of one member are staged in 32 KB of LDS
+constexpr u64 SYEV_MAX_BITS = 0x7FEFFFFFFFFFFFFFull;   // the bits of DBL_MAX: those of Inf and of every |NaN| lie above
 constexpr int SYEV_DIAG = INT_MIN;         // kexp of a member whose tridiagonal form is diagonal (e = 0): lambda = d, sorted
 
 // e1 of a member from the bits of max|s_ij| (0 for a zero or non-finite member: those are left alone)
@@ -80,10 +82,13 @@ __global__ __launch_bounds__(256) void syev_symm(const double* __restrict__ S, d
 
 // One wave per member. H [batch, N, N]: the Hessenberg form of a symmetric matrix. p [batch, N], q [batch, N-1]:
 // the bidiagonal Cholesky factor of 2^k T + c I; cs [batch] = c; kexp [batch] = k, or SYEV_DIAG for a diagonal T. *flag: raised
-// to 1 when a member is not finite. The recurrence is serial (lane 0); its operands come from LDS. No contraction: the radicand is
-// (d + c) - q q with each operation rounded once, as the bound in the head of this file assumes.
-__global__ __launch_bounds__(64) void syev_shift_chol(const double* __restrict__ H, int N, double* __restrict__ p, double* __restrict__ q,
-                                                      double* __restrict__ cs, int* __restrict__ kexp, int* __restrict__ flag) {
+// to 1 when a member is not finite: when mx[b], the bits of max|s_ij| over its lower triangle, lie above those of DBL_MAX (NaN
+// or Inf anywhere in the triangle, also where the reduction leaves it below the subdiagonal of H: hess.hip finds a row that is
+// already reduced with fmax, which drops NaN), or when d or e of H are not finite. The recurrence is serial (lane 0); its
+// operands come from LDS. No contraction: the radicand is (d + c) - q q with each operation rounded once, as the bound in the
+// head of this file assumes.
+__global__ __launch_bounds__(64) void syev_shift_chol(const double* __restrict__ H, int N, const u64* __restrict__ mx, double* __restrict__ p,
+                                                      double* __restrict__ q, double* __restrict__ cs, int* __restrict__ kexp, int* __restrict__ flag) {
 #pragma clang fp contract(off)
   __shared__ double sd[SYEV_MAXN], se[SYEV_MAXN];
   const int b = blockIdx.x, lane = threadIdx.x;
@@ -93,7 +98,7 @@ __global__ __launch_bounds__(64) void syev_shift_chol(const double* __restrict__
     se[i] = i + 1 < N ? h[(size_t)(i + 1) * N + i] : 0.0;
   }
   __syncthreads();
-  double g = 0.0; int bad = 0, offdiag = 0;
+  double g = 0.0; int bad = mx[b] > SYEV_MAX_BITS, offdiag = 0;
   for (int i = lane; i < N; i += 64) {
     offdiag |= se[i] != 0.0;
     const double row = (fabs(sd[i]) + (i > 0 ? fabs(se[i - 1]) : 0.0)) + fabs(se[i]);
@@ -132,10 +137,13 @@ __global__ __launch_bounds__(64) void syev_shift_chol(const double* __restrict__
 }
 
 // lambda = 2^(e1 - k) (sv^2 - c), one thread per value. A diagonal member (H [batch, N, N] holds its d): thread j writes
-// 2^e1 d_j at its descending rank (ties by index), which is the solver's order of sqrt(d + c) up to ties of the rounded roots.
+// 2^e1 d_j at its descending rank (ties by index) and, where the vectors are wanted (V2 != NULL), the unit vector e_j as row
+// `rank` of V2 [batch, N, N] in place of the solver's. The solver's own rows are a permutation only up to rounding (its
+// deflation rotates tied and near-zero pairs: entries like cos(pi/2) = 6.1e-17), and its order of the rounded roots
+// sqrt(d + c) is the order of d only up to their ties; with e_j the pairs (2^e1 d_j, U e_j) of a diagonal T are exact.
 __global__ __launch_bounds__(256) void syev_values(const double* __restrict__ sv, const double* __restrict__ H, int N, long total,
                                                    const double* __restrict__ cs, const int* __restrict__ kexp, const u64* __restrict__ mx,
-                                                   double* __restrict__ lam) {
+                                                   double* __restrict__ lam, double* __restrict__ V2) {
 #pragma clang fp contract(off)
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
@@ -148,6 +156,10 @@ __global__ __launch_bounds__(256) void syev_values(const double* __restrict__ sv
     int rank = 0;
     for (int m = 0; m < N; ++m) { const double dm = h[(size_t)m * N + m]; rank += dm > dj || (dm == dj && m < j); }
     lam[b * N + rank] = ldexp(dj, e1);                        // rank < N: at most N - 1 others precede j
+    if (V2) {
+      double* row = V2 + ((size_t)b * N + rank) * N;          // row rank < N of member b < batch
+      for (int m = 0; m < N; ++m) row[m] = m == j ? 1.0 : 0.0;
+    }
     return;
   }
   const double s = sv[i];
@@ -220,13 +232,14 @@ int nd4_syevd(nd4hip_handle* h, int64_t batch, int64_t N64, const double* S, dou
   st.mark();
   ND4_TRY(nd4_gehrd(h, batch, N, W, U, W));                   // in place: H overwrites W
   st.mark();
-  hipLaunchKernelGGL(syev_shift_chol, dim3((unsigned)batch), dim3(64), 0, h->stream, W, N, p, q, cs, kexp, flag);
+  hipLaunchKernelGGL(syev_shift_chol, dim3((unsigned)batch), dim3(64), 0, h->stream, W, N, mx, p, q, cs, kexp, flag);
   ND4_HIP(hipGetLastError());
   st.mark();
   ND4_TRY(nd4_bdsdc_rows(h, batch, N, N, p, q, U2, sv, V2));  // synchronises
   st.mark();
   const long total = (long)batch * N;
-  hipLaunchKernelGGL(syev_values, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, sv, W, N, total, cs, kexp, mx, lambda);
+  hipLaunchKernelGGL(syev_values, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, sv, W, N, total, cs, kexp, mx, lambda,
+                     V ? V2 : nullptr);
   ND4_HIP(hipGetLastError());
   if (V) ND4_TRY(nd4_gemm(h, false, true, N, N, N, 1.0, U, N, (int64_t)nn, V2, N, (int64_t)nn, 0.0, V, N, (int64_t)nn, batch));
   st.mark();
