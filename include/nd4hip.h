@@ -596,6 +596,39 @@ int nd4hip_dsyevd_last_stages(nd4hip_handle* h, double* ms, int capacity);
 int nd4hip_dsyevj_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V, int32_t* sweeps);
 int nd4hip_dsyevj_batched    (nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V, int32_t* sweeps);
 
+/* ---- eigen_sym_gen / eigenvals_sym_gen: A x = lambda B x, A symmetric, B symmetric positive definite (csrc/sygv.hip) ----
+ * A [batch,N,N]; B [batch,N,N] (strideB = N*N) or ONE B [N,N] for every member (strideB = 0; it is factorised once per call of the
+ * _dev form, once per staged chunk of the host form, never once per member). Only the lower triangles of A and B are read and
+ * neither is written: NaN or garbage above the diagonals changes no bit of the result. lambda [batch,N] descending; X [batch,N,N]
+ * with the eigenvectors as columns, A X = B X diag(lambda), X^T B X = I; X = NULL: the values alone, the same bits, no
+ * back-transformation. algo 0: the default route of dsyevd (N <= 2048); algo 1: dsyevj (N <= 128), sweeps [batch] (may be NULL; it
+ * is not written for algo 0) then receives each member's sweep count. A larger N or another algo is ND4HIP_ERR_ARG before anything
+ * is written. N = 0 and empty batches: nothing to do.
+ * Route (LAPACK's dsygvd): L = chol(B); C = L^-1 A L^-T, lower triangle; (lambda, Y) of C by dsyevd / dsyevj, unchanged;
+ * X = L^-T Y. Tiers: N <= 64 two fused kernels with one workgroup per member, A, B and L in LDS, all arithmetic rounded
+ * operation by operation in the order of the numpy model in tests/sygv_common.py, whose bits they return; 64 < N <= 2048 dpotrf,
+ * two dtrsm around a transposition, and the transposed solve for X.
+ * Errors. B not positive definite (some Cholesky radicand is not a finite number > 0, an exact zero in the last pivot included):
+ * ND4HIP_ERR_SINGULAR with 'eigen_sym_gen(A,B): B is not positive definite. (matrix <b>)', b the lowest such member. C not finite:
+ * ND4HIP_ERR_NOCONV with 'eigen_sym_gen(A,B): L^-1 A L^-T is not finite (NaN or Infinity in the lower triangle of A, or
+ * overflow).' The outputs are unspecified then; the handle stays usable.
+ * Accuracy, per member, sigma the singular values of B and kappa = sigma_max / sigma_min, within 1e-12 of:
+ *   |lambda^_i - lambda_i| <= ||A||_F / sigma_min + kappa |lambda_i|;   ||A X - B X diag(lambda)||_F <= (||A||_F + ||B||_F max|lambda|) ||X||_F;
+ *   ||X^T B X - I||_F <= kappa sqrt(N);   and for step 2 (dsygst below, both tiers):   ||L C L^T - A||_F <= ||L||_F^2 ||C||_F.
+ * 2^k A gives 2^k lambda and the same X, 4^j B gives 4^-j lambda and 2^-j X, exactly, while nothing leaves the normal range.
+ * A member's results do not depend on the batch. Both forms synchronise. Profile op "dsygvd_batched": dsyevd's (dsyevj's) flops
+ * plus (1/3 + 2) N^3 for L and C, plus N^3 with X. */
+int nd4hip_dsygvd_batched_dev(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B, int64_t strideB,
+                              double* lambda, double* X, int32_t* sweeps);
+int nd4hip_dsygvd_batched    (nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B, int64_t strideB,
+                              double* lambda, double* X, int32_t* sweeps);
+/* step 2 on its own (LAPACK's dsygst): C [batch,N,N] = L^-1 A L^-T from a given lower triangular L [batch,N,N] (strideL = N*N, or
+ * 0: one L); the lower triangle of C is written and exact zeros above it. The same two tiers, N <= 2048. No verdict is read.
+ * Accuracy: ||L C L^T - A||_F <= 1e-12 ||L||_F^2 ||C||_F with C mirrored from its lower triangle; for N <= 64 the bits of
+ * sygst_model in tests/sygv_common.py. */
+int nd4hip_dsygst_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, const double* L, int64_t strideL, double* C);
+int nd4hip_dsygst_batched    (nd4hip_handle* h, int64_t batch, int64_t N, const double* A, const double* L, int64_t strideL, double* C);
+
 /* ---- one Householder panel on its own: geqr2 + larft of a 16-column panel (the inner step of qr_decomp, src/la/qr.js:54-68
  * eliminates the same entries column by column with Givens rotations) ---------------------------------------------
  * A [batch,M,16] (1 <= M <= 2048) is overwritten with R in its top 16 x 16 (entries below the diagonal are left as the kernel

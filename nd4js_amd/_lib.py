@@ -154,6 +154,10 @@ SIGNATURES = {
     "nd4hip_dsyevd_last_stages": (c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), c_int]),
     "nd4hip_dsyevj_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp, ctypes.c_void_p]),
     "nd4hip_dsyevj_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp, ctypes.c_void_p]),
+    "nd4hip_dsygvd_batched_dev": (c_int, [ctypes.c_void_p, c_int, c_i64, c_i64, c_dp, c_dp, c_i64, c_dp, c_dp, ctypes.c_void_p]),
+    "nd4hip_dsygvd_batched": (c_int, [ctypes.c_void_p, c_int, c_i64, c_i64, c_dp, c_dp, c_i64, c_dp, c_dp, ctypes.c_void_p]),
+    "nd4hip_dsygst_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_i64, c_dp]),
+    "nd4hip_dsygst_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_i64, c_dp]),
     "nd4hip_dgeqr2_panel_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
     "nd4hip_profile_enable": (c_int, [ctypes.c_void_p, c_int]),
     "nd4hip_profile_last": (c_int, [ctypes.c_void_p, ctypes.c_void_p, c_int]),

@@ -75,6 +75,7 @@ static int (*p_dgees[2])(nd4hip_handle*, int64_t, int64_t, const double*, double
 static int (*p_dgeev[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*, double*);
 static int (*p_dsyevd[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*, double*);
 static int (*p_dsyevj[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*, double*, int32_t*);
+static int (*p_dsygvd[2])(nd4hip_handle*, int, int64_t, int64_t, const double*, const double*, int64_t, double*, double*, int32_t*);
 static int (*p_dqp3rank[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, int32_t*);
 static int (*p_dqp3ls[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t,
                           const int32_t*, int64_t, const double*, int64_t, double*, int32_t*);
@@ -175,6 +176,7 @@ static int load_library(void) {
   SYM2(p_dgeev, "nd4hip_dgeev_batched");
   SYM2(p_dsyevd, "nd4hip_dsyevd_batched");
   SYM2(p_dsyevj, "nd4hip_dsyevj_batched");
+  SYM2(p_dsygvd, "nd4hip_dsygvd_batched");
   SYM2(p_dqp3rank, "nd4hip_dqp3rank_batched");
   SYM2(p_dsrrqr, "nd4hip_dsrrqr_batched");
   SYM2(p_durv, "nd4hip_durv_batched");
@@ -762,6 +764,32 @@ static napi_value js_dsyevjals(napi_env env, napi_callback_info info) {
   FAIL_IF(p_dsyevj[S.dev](g_handle, batch, N, (const double*)S.p, (double*)L.p, NULL, NULL));
   return NULL;
 }
+/* dsygvd_batched(algo, batch, N, A, B, strideB, L, X) / dsygvals_batched(algo, batch, N, A, B, strideB, L)   (eigen_sym_gen /
+ * eigenvals_sym_gen: A x = lambda B x; algo 0 dc, 1 jacobi; strideB N*N or 0 = one B; the sweep counts are not asked for) */
+static napi_value js_dsygvd(napi_env env, napi_callback_info info) {
+  ARGS(8, "dsygvd_batched");
+  int64_t algo, batch, N, sB; opnd A, B, L, X;
+  if (get_i64(env, a[0], &algo) || get_i64(env, a[1], &batch) || get_i64(env, a[2], &N) || F64(3, A) || F64(4, B) || get_i64(env, a[5], &sB) ||
+      F64(6, L) || F64(7, X)) return NULL;
+  NEED(batch >= 0 && N >= 0 && (sB == 0 || sB == N * N) && (size_t)(batch * N * N) <= A.len && (size_t)((sB ? batch : 1) * N * N) <= B.len &&
+       (size_t)(batch * N) <= L.len && (size_t)(batch * N * N) <= X.len, "dsygvd_batched: buffer too small");
+  SAME_SIDE(A.dev == B.dev && B.dev == L.dev && L.dev == X.dev, "dsygvd_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dsygvd[A.dev](g_handle, (int)algo, batch, N, (const double*)A.p, (const double*)B.p, sB, (double*)L.p, (double*)X.p, NULL));
+  return NULL;
+}
+static napi_value js_dsygvals(napi_env env, napi_callback_info info) {
+  ARGS(7, "dsygvals_batched");
+  int64_t algo, batch, N, sB; opnd A, B, L;
+  if (get_i64(env, a[0], &algo) || get_i64(env, a[1], &batch) || get_i64(env, a[2], &N) || F64(3, A) || F64(4, B) || get_i64(env, a[5], &sB) ||
+      F64(6, L)) return NULL;
+  NEED(batch >= 0 && N >= 0 && (sB == 0 || sB == N * N) && (size_t)(batch * N * N) <= A.len && (size_t)((sB ? batch : 1) * N * N) <= B.len &&
+       (size_t)(batch * N) <= L.len, "dsygvals_batched: buffer too small");
+  SAME_SIDE(A.dev == B.dev && B.dev == L.dev, "dsygvals_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dsygvd[A.dev](g_handle, (int)algo, batch, N, (const double*)A.p, (const double*)B.p, sB, (double*)L.p, NULL, NULL));
+  return NULL;
+}
 /* dnrmfro(n, A) -> number   (norm(A) 'fro', norm.js:22-85); a device operand's result comes back as a host number too */
 static napi_value js_dnrmfro(napi_env env, napi_callback_info info) {
   ARGS(2, "dnrmfro");
@@ -1184,6 +1212,8 @@ static napi_value init(napi_env env, napi_value exports) {
     {"dsyevals_batched", NULL, js_dsyevals, NULL, NULL, NULL, napi_default, NULL},
     {"dsyevj_batched", NULL, js_dsyevj, NULL, NULL, NULL, napi_default, NULL},
     {"dsyevjals_batched", NULL, js_dsyevjals, NULL, NULL, NULL, napi_default, NULL},
+    {"dsygvd_batched", NULL, js_dsygvd, NULL, NULL, NULL, napi_default, NULL},
+    {"dsygvals_batched", NULL, js_dsygvals, NULL, NULL, NULL, napi_default, NULL},
     {"dqp3rank_batched", NULL, js_dqp3rank, NULL, NULL, NULL, napi_default, NULL},
     {"dsrrqr_batched", NULL, js_dsrrqr, NULL, NULL, NULL, napi_default, NULL},
     {"durv_batched", NULL, js_durv, NULL, NULL, NULL, napi_default, NULL},

@@ -831,6 +831,43 @@ extern "C" int nd4hip_dsyevj_batched_dev(nd4hip_handle* h, int64_t batch, int64_
   return 0;
 }
 
+// ---- eigen_sym_gen / eigenvals_sym_gen (sygv.hip). Flops: the solver's count above, (1/3 + 2) N^3 for L = chol(B) and the two
+// triangular solves of C = L^-1 A L^-T, N^3 for X = L^-T Y
+int nd4_sygvd_run(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B, int64_t strideB, double* lambda,
+                  double* X, int32_t* sweeps, int64_t member0) {
+  // the argument checks come first: they need no handle (and are testable without a device)
+  ND4_CHECK_ARG(algo == 0 || algo == 1, "nd4hip_dsygvd_batched: algo must be 0 (dc) or 1 (jacobi)");
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsygvd_batched: negative extent");
+  ND4_CHECK_ARG(algo == 1 || N <= 2048, "nd4hip_dsygvd_batched: the divide & conquer solver takes N <= 2048");
+  ND4_CHECK_ARG(algo == 0 || N <= 128, "nd4hip_dsygvd_batched: the Jacobi route takes N <= 128");
+  ND4_CHECK_ARG(strideB == 0 || strideB == N * N, "nd4hip_dsygvd_batched: strideB must be N*N or 0");
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dsygvd_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  const double n3 = (double)N * N * N;
+  const double solver = algo == 1 ? 8.0 * (X ? 8.0 : 4.0) : 10.0 / 3.0 + 2.0 + (X ? 2.0 : 0.0);
+  Nd4Prof prof(h, "dsygvd_batched", batch * ((solver + 1.0 / 3.0 + 2.0 + (X ? 1.0 : 0.0)) * n3),
+               8.0 * ((double)(batch + (strideB ? batch : 1)) * (double)(N * N / 2) + batch * (double)(N + (X ? N * N : 0))));
+  if (batch == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(A && B && lambda, "nd4hip_dsygvd_batched: NULL pointer");
+  return nd4_sygvd(h, algo, batch, N, A, B, strideB, lambda, X, algo == 1 ? sweeps : nullptr, member0);
+}
+extern "C" int nd4hip_dsygvd_batched_dev(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B,
+                                         int64_t strideB, double* lambda, double* X, int32_t* sweeps) {
+  return nd4_sygvd_run(h, algo, batch, N, A, B, strideB, lambda, X, sweeps, 0);
+}
+extern "C" int nd4hip_dsygst_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, const double* L, int64_t strideL,
+                                         double* C) {
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsygst_batched: negative extent");
+  ND4_CHECK_ARG(N <= 2048, "nd4hip_dsygst_batched: N <= 2048");
+  ND4_CHECK_ARG(strideL == 0 || strideL == N * N, "nd4hip_dsygst_batched: strideL must be N*N or 0");
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dsygst_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "dsygst_batched", batch * 2.0 * (double)N * N * N, 8.0 * batch * 2.0 * (double)(N * N));
+  if (batch == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(A && L && C, "nd4hip_dsygst_batched: NULL pointer");
+  return nd4_sygst(h, batch, N, A, L, strideL, C);
+}
+
 extern "C" int nd4hip_dsyevd_last_stages(nd4hip_handle* h, double* ms, int capacity) {
   ND4_CHECK_ARG(h != nullptr && (ms != nullptr || capacity <= 0), "nd4hip_dsyevd_last_stages: NULL argument");
   for (int i = 0; i < capacity && i < ND4HIP_SYEV_STAGES; ++i) ms[i] = h->syev_stage_ms[i];

@@ -1063,3 +1063,41 @@ extern "C" int nd4hip_dsyevj_batched(nd4hip_handle* h, int64_t batch, int64_t N,
   };
   return run_host(h, batch, ops, fn);
 }
+
+// eigen_sym_gen / eigenvals_sym_gen (sygv.hip); X = NULL: the values alone; sweeps = NULL: not wanted; strideB = 0: one B, uploaded
+// once per device
+extern "C" int nd4hip_dsygvd_batched(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B, int64_t strideB,
+                                     double* lambda, double* X, int32_t* sweeps) {
+  ND4_CHECK_ARG(algo == 0 || algo == 1, "nd4hip_dsygvd_batched: algo must be 0 (dc) or 1 (jacobi)");
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsygvd_batched: negative extent");
+  ND4_CHECK_ARG(algo == 1 || N <= 2048, "nd4hip_dsygvd_batched: the divide & conquer solver takes N <= 2048");
+  ND4_CHECK_ARG(algo == 0 || N <= 128, "nd4hip_dsygvd_batched: the Jacobi route takes N <= 128");
+  ND4_CHECK_ARG(strideB == 0 || strideB == N * N, "nd4hip_dsygvd_batched: strideB must be N*N or 0");
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dsygvd_batched: NULL handle");
+  if (batch == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(A && B && lambda, "nd4hip_dsygvd_batched: NULL pointer");
+  if (algo == 0) sweeps = nullptr;
+  // the operands that are wanted, in the order A, B, lambda, [X], [sweeps]
+  std::vector<Operand> ops{in_op(A, N * N, N * N), in_op(B, N * N, strideB), out_op(lambda, N)};
+  const int ix = X ? (int)ops.size() : -1;
+  if (X) ops.push_back(out_op(X, N * N));
+  const int is = sweeps ? (int)ops.size() : -1;
+  if (sweeps) ops.push_back(out_op(sweeps, 1, 4));
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
+    return nd4_sygvd_run(hd, algo, nb, N, P(d, 0), P(d, 1), strideB, P(d, 2), ix >= 0 ? P(d, ix) : nullptr,
+                         is >= 0 ? static_cast<int32_t*>(d[is]) : nullptr, g_chunk_first);
+  };
+  return run_host(h, batch, ops, fn);
+}
+
+extern "C" int nd4hip_dsygst_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, const double* L, int64_t strideL, double* C) {
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsygst_batched: negative extent");
+  ND4_CHECK_ARG(N <= 2048, "nd4hip_dsygst_batched: N <= 2048");
+  ND4_CHECK_ARG(strideL == 0 || strideL == N * N, "nd4hip_dsygst_batched: strideL must be N*N or 0");
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dsygst_batched: NULL handle");
+  if (batch == 0 || N == 0) return 0;
+  ND4_CHECK_ARG(A && L && C, "nd4hip_dsygst_batched: NULL pointer");
+  std::vector<Operand> ops{in_op(A, N * N, N * N), in_op(L, N * N, strideL), out_op(C, N * N)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_dsygst_batched_dev(hd, nb, N, P(d, 0), P(d, 1), strideL, P(d, 2)); };
+  return run_host(h, batch, ops, fn);
+}

@@ -178,6 +178,14 @@ int nd4_gesdd(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const doubl
 int nd4_syevd(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V);
 // the same by two-sided Jacobi in one launch (syevj.hip): 1 <= N <= 128; sweeps [batch] may be NULL; synchronises
 int nd4_syevj(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V, int32_t* sweeps);
+// generalised symmetric-definite eigenproblem (sygv.hip): arguments already checked, batch >= 1, 1 <= N; sB / sL 0 = one for all;
+// member0: index of the first member in the caller's batch (error text); nd4_sygvd synchronises
+int nd4_sygvd(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B, int64_t sB, double* lambda,
+              double* X, int32_t* sweeps, int64_t member0);
+int nd4_sygst(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, const double* L, int64_t sL, double* C);
+// the _dev entry point of eigen_sym_gen with member0 (for the host-pointer form, as nd4_sytrf_bk_run)
+int nd4_sygvd_run(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B, int64_t strideB, double* lambda,
+                  double* X, int32_t* sweeps, int64_t member0);
 
 // small utility kernels (nd4hip_core.hip)
 int nd4_copy_matrix(nd4hip_handle* h, int64_t rows, int64_t cols, const double* src, int64_t lds,

@@ -788,6 +788,59 @@ def eigenvals_sym(S, algo=None, info=None):
     return _syevd(S, "eigenvals_sym(S)", False, algo, info)
 
 
+def _sygv_chk(A, B, what):
+    from .la import _sygv_args
+    named = ((what[what.index("(") + 1], A), (what[what.index(",") + 1], B))
+    for name, M in named:
+        if isinstance(M, torch.Tensor) and M.dtype != torch.float64:
+            raise TypeError("%s: %s.dtype must be float." % (what, name))
+    for name, M in named:
+        _chk(M, name)
+    one = _sygv_args(A, B, what, lambda M: True, lambda M: M.dim(), lambda M: M.shape)
+    if B.device != A.device:
+        raise ValueError("%s: both operands must be on the same device." % what)
+    return one
+
+
+def _sygvd(A, B, what, vectors, algo, info):
+    from .la import _eigsym_algo
+    jacobi = _eigsym_algo(algo, what)
+    one_b = _sygv_chk(A, B, what)
+    N = A.shape[-1]
+    lead = tuple(A.shape[:-2])
+    L = torch.empty(lead + (N,), dtype=torch.float64, device=A.device)
+    X = torch.empty(lead + (N, N), dtype=torch.float64, device=A.device) if vectors else None
+    sweeps = torch.zeros(lead, dtype=torch.int32, device=A.device) if jacobi else None
+    h = _h(A)
+    _lib.check(h.lib.nd4hip_dsygvd_batched_dev(h.ptr, 1 if jacobi else 0, _batch(lead), N, _p(A), _p(B), 0 if one_b else N * N, _p(L),
+                                               _p(X) if vectors else None, _p(sweeps) if jacobi else None))
+    if jacobi and info is not None:
+        info["sweeps"] = sweeps
+    return (L, X) if vectors else L
+
+
+def eigen_sym_gen(A, B, algo=None, info=None):
+    """device-resident la.eigen_sym_gen: A x = lambda B x with A symmetric and B symmetric positive definite, (eigenvalues [..., N]
+    descending, eigenvectors [..., N, N] as columns, X^T B X = I), float64. B has A's shape or is exactly [N, N] (one B for every
+    member, factorised once). Only the lower triangles are read; A and B are not written. The same bits as through la."""
+    return _sygvd(A, B, "eigen_sym_gen(A,B)", True, algo, info)
+
+
+def eigenvals_sym_gen(A, B, algo=None, info=None):
+    """device-resident la.eigenvals_sym_gen: the eigenvalues of eigen_sym_gen alone, the same bits"""
+    return _sygvd(A, B, "eigenvals_sym_gen(A,B)", False, algo, info)
+
+
+def _sygst(A, L):
+    """device-resident la._sygst: C = L^-1 A L^-T, lower triangle, zeros above"""
+    one_l = _sygv_chk(A, L, "_sygst(A,L)")
+    N = A.shape[-1]
+    C = torch.empty_like(A)
+    h = _h(A)
+    _lib.check(h.lib.nd4hip_dsygst_batched_dev(h.ptr, _batch(A.shape[:-2]), N, _p(A), _p(L), 0 if one_l else N * N, _p(C)))
+    return C
+
+
 # ---- structure functions (csrc/struct.hip): values are moved, never computed; nothing leaves the device ----
 def _struct_call(fn, *args):
     from .la import _arg_error

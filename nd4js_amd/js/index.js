@@ -1478,6 +1478,42 @@ function makeLa(NDA, fallback, SolveError, Complex) {
   };
   eigSym('eigen_sym', true); eigSym('eigenvals_sym', false);
 
+  /* ---- eigen_sym_gen / eigenvals_sym_gen, csrc/sygv.hip: A x = lambda B x, A symmetric, B symmetric positive definite, both read
+   * only in their lower triangles. A [..., N, N]; B of the same shape or exactly [N, N] (one B for every member, factorised once)
+   * -> [eigenvalues [..., N] descending, eigenvectors [..., N, N] as columns with X^T B X = I], resp. the eigenvalues alone (the
+   * same bits). Host arrays or DeviceNDArrays in (both of one kind), the same kind out. opts.algo as for eigen_sym. ---- */
+  const eigSymGen = (name, vectors) => {
+    const f = function (A, B, opts) {
+      const algo = opts == null ? undefined : opts.algo;
+      if (algo !== undefined && algo !== null && algo !== 'dc' && algo !== 'jacobi') throw new Error(`${name}(A,B, {algo}): algo must be 'dc' or 'jacobi'.`);
+      A = asarray(A); B = asarray(B);
+      for (const [nm, M] of [['A', A], ['B', B]]) {
+        if (isComplexDev(M) || String(dtypeOf(M)).startsWith('complex')) throw new TypeError(`${name}(A,B): ${nm}.dtype must be float.`);
+        if (M.ndim < 2) throw new Error(`${name}(A,B): ${nm}.ndim must be at least 2.`);
+        if (M.shape[M.ndim - 2] != M.shape[M.ndim - 1]) throw new Error(`${name}(A,B): ${nm} must be quadratic.`);
+        if (!gpuOk(M)) throw new TypeError(`${name}(A,B): dtype ${dtypeOf(M)} is not accelerated.`);
+      }
+      const nd_ = A.ndim, N = A.shape[nd_ - 1];
+      const same = B.ndim === nd_ && A.shape.every((s, i) => s == B.shape[i]), one = !same && B.ndim === 2 && B.shape[0] == N && B.shape[1] == N;
+      if (!same && !one) throw new Error(`${name}(A,B): B.shape must be A.shape or A.shape.slice(-2), got [${Array.from(B.shape)}] and [${Array.from(A.shape)}].`);
+      if (isDev(A) !== isDev(B)) throw new TypeError(`${name}(A,B): A and B must be both host arrays or both DeviceNDArrays.`);
+      const batch = prod(A.shape, 0, nd_ - 2), dev = isDev(A), temps = [], jac = algo === 'jacobi' ? 1 : 0;
+      const L = alloc(dev, batch * N), X = vectors ? alloc(dev, batch * N * N) : null;
+      try {
+        const a = view(opF64(A, dev, temps), 0), b = view(opF64(B, dev, temps), 0);
+        if (vectors) native().dsygvd_batched(jac, batch, N, a, b, same ? N * N : 0, view(L, 0), view(X, 0));
+        else native().dsygvals_batched(jac, batch, N, a, b, same ? N * N : 0, view(L, 0));
+      }
+      catch (e) { if (dev) { L.free(); if (X) X.free(); } throw e; }
+      finally { release(temps); }
+      const Lw = wrap(dev, A.shape.subarray(0, nd_ - 1), L);
+      return vectors ? [Lw, wrap(dev, A.shape, X)] : Lw;
+    };
+    Object.defineProperty(f, 'name', {value: name});
+    Object.defineProperty(la, name, {value: f, writable: true, enumerable: false, configurable: true});
+  };
+  eigSymGen('eigen_sym_gen', true); eigSymGen('eigenvals_sym_gen', false);
+
   // complex128 device arrays are accepted by matmul2 / matmul only: every other function refuses them before it looks at the
   // buffer (which holds 2n doubles, not n float64 entries)
   const complexOk = new Set(['matmul2', 'matmul', 'eigen_balance_post', '_chain_plan', 'to_device', 'to_host', 'synchronize', 'profile_enable', 'profile_last']);
@@ -1579,7 +1615,7 @@ function install(nd, opts) {
     return f;
   };
   for (const k of Object.keys(original)) Object.defineProperty(patched, k, {value: route(k), writable: true, enumerable: true, configurable: true});
-  for (const k of ['to_device', 'to_host', 'synchronize', 'DeviceNDArray', 'profile_enable', 'profile_last', 'schur_qrfrancis', 'concat', 'stack', 'zip_elems', 'eigen_sym', 'eigenvals_sym'])   // §8f N3 / §8b extensions, not in the reference (schur_qrfrancis: its private step)
+  for (const k of ['to_device', 'to_host', 'synchronize', 'DeviceNDArray', 'profile_enable', 'profile_last', 'schur_qrfrancis', 'concat', 'stack', 'zip_elems', 'eigen_sym', 'eigenvals_sym', 'eigen_sym_gen', 'eigenvals_sym_gen'])   // §8f N3 / §8b extensions, not in the reference (schur_qrfrancis: its private step)
     Object.defineProperty(patched, k, {value: acc[k], writable: true, enumerable: false, configurable: true});
   if (!target) { try { nd.la = patched; } catch (e) { /* exported getter: caller uses the returned object */ } }
   patched.__nd4hip_original__ = original;

@@ -9,6 +9,7 @@ JS wrapper nd4js_amd/js/index.js over the N-API shim; both call the same libnd4h
   svd_decomp(A)        src/la/svd.js:25             -> nd4hip_dgesvdj_batched; algo='dc' (opt-in): nd4hip_dgesdd_batched
   bidiag_svd(d, e)     src/la/svd_dc.js:169-824     -> nd4hip_dbdsdc_batched
   eigen_sym(S), eigenvals_sym(S)   planned at src/la/eigen.js:28-30   -> nd4hip_dsyevd_batched; algo='jacobi' (opt-in): nd4hip_dsyevj_batched
+  eigen_sym_gen(A, B), eigenvals_sym_gen(A, B)   A x = lambda B x, not in the reference   -> nd4hip_dsygvd_batched
 
 Inputs are numpy arrays / nested lists (NDArray analogue: dense, row-major, leading axes = batch).
 Only float64 (and int32 promoted to float64 for QR/LU/SVD, as qr.js:31-37, lu.js:27, svd_dc.js:904
@@ -1167,6 +1168,69 @@ def eigenvals_sym(S, device=None, algo=None, info=None):
     """the eigenvalues of eigen_sym alone (the same bits); no eigenvector product is computed or stored. With algo='jacobi' no
     eigenvector is accumulated at all."""
     return _syevd(S, "eigenvals_sym(S)", False, device, algo, info)
+
+
+def _sygv_args(A, B, what, is_float64, ndim, shape):
+    """the argument checks of eigen_sym_gen / eigenvals_sym_gen, shared with dev.py; returns whether one B serves every member"""
+    nb = what[what.index(",") + 1]                                          # 'B', or 'L' for _sygst(A,L)
+    for name, M in (("A", A), (nb, B)):
+        if not is_float64(M):
+            raise TypeError("%s: %s.dtype must be float." % (what, name))
+        if ndim(M) < 2:
+            raise ValueError("%s: %s.ndim must be at least 2." % (what, name))
+        if shape(M)[-2] != shape(M)[-1]:
+            raise ValueError("%s: %s must be quadratic." % (what, name))
+    sa, sb = tuple(shape(A)), tuple(shape(B))
+    if sb != sa and sb != sa[-2:]:
+        raise ValueError("%s: %s.shape must be A.shape or A.shape[-2:], got %s and %s." % (what, nb, list(sb), list(sa)))
+    return sb != sa
+
+
+def _sygvd(A, B, what, vectors, device, algo, info):
+    jacobi = _eigsym_algo(algo, what)
+    A, B = np.asarray(A), np.asarray(B)
+    one_b = _sygv_args(A, B, what, lambda M: not np.iscomplexobj(M), lambda M: M.ndim, lambda M: M.shape)
+    A, B = _asarray(A, what), _asarray(B, what)
+    N = A.shape[-1]
+    L = np.empty(A.shape[:-1])
+    X = np.empty(A.shape) if vectors else None
+    batch = int(np.prod(A.shape[:-2], dtype=np.int64))
+    sweeps = np.zeros(A.shape[:-2], dtype=np.int32) if jacobi else None
+    h = _lib.handle(device)
+    _lib.check(h.lib.nd4hip_dsygvd_batched(h.ptr, 1 if jacobi else 0, batch, N, _ptr(A), _ptr(B), 0 if one_b else N * N, _ptr(L),
+                                           _ptr(X) if vectors else None, sweeps.ctypes.data if jacobi else None))
+    if jacobi and info is not None:
+        info["sweeps"] = sweeps
+    return (L, X) if vectors else L
+
+
+def eigen_sym_gen(A, B, device=None, algo=None, info=None):
+    """the generalised symmetric-definite eigenproblem A x = lambda B x: (eigenvalues float64 [..., N] descending, eigenvectors
+    float64 [..., N, N] as columns) with A X = B X diag(L) and X^T B X = I. A [..., N, N] symmetric; B of the same shape, or exactly
+    [N, N]: one B for every member, factorised once. Only the lower triangles of A and B are read; neither is written.
+    Route: L = chol(B), C = L^-1 A L^-T, eigen_sym(C, algo) unchanged, X = L^-T Y (csrc/sygv.hip; N <= 64 in two fused kernels).
+    algo and info as for eigen_sym (N <= 2048; 'jacobi': N <= 128, info['sweeps']). B not positive definite raises Nd4HipError with
+    code -5 and the lowest such member; NaN or Infinity in A's lower triangle, or overflow of C, code -3."""
+    return _sygvd(A, B, "eigen_sym_gen(A,B)", True, device, algo, info)
+
+
+def eigenvals_sym_gen(A, B, device=None, algo=None, info=None):
+    """the eigenvalues of eigen_sym_gen alone (the same bits); no back-transformation is computed"""
+    return _sygvd(A, B, "eigenvals_sym_gen(A,B)", False, device, algo, info)
+
+
+def _sygst(A, L, device=None):
+    """step 2 of eigen_sym_gen on its own, for the tests of both tiers: C = L^-1 A L^-T from a given lower triangular L [..., N, N] or
+    [N, N]; the lower triangle of C and exact zeros above it (nd4hip_dsygst_batched)"""
+    A, L = np.asarray(A), np.asarray(L)
+    one_l = _sygv_args(A, L, "_sygst(A,L)", lambda M: not np.iscomplexobj(M), lambda M: M.ndim, lambda M: M.shape)
+    A, L = _asarray(A, "_sygst(A,L)"), _asarray(L, "_sygst(A,L)")
+    N = A.shape[-1]
+    C = np.empty(A.shape)
+    h = _lib.handle(device)
+    _lib.check(h.lib.nd4hip_dsygst_batched(h.ptr, int(np.prod(A.shape[:-2], dtype=np.int64)), N, _ptr(A), _ptr(L), 0 if one_l else N * N,
+                                           _ptr(C)))
+    return C
 
 
 # ---------------------------------------------------------------------------------------------------
