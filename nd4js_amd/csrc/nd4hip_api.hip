@@ -1,6 +1,6 @@
-// extern "C" entry points of include/nd4hip.h: argument validation and the *_dev (device pointer) forms. The host-pointer
-// forms that the N-API shim binds live in nd4hip_host.hip.
-#include "nd4hip_internal.h"
+// extern "C" entry points of include/nd4hip.h: the *_dev (device pointer) forms. The host-pointer forms that the N-API shim
+// binds live in nd4hip_host.hip; the argument checks that the two forms of an operation share, in nd4hip_args.h.
+#include "nd4hip_args.h"
 #include <cmath>
 #include <cstdlib>
 
@@ -12,6 +12,17 @@ constexpr size_t D = sizeof(double);
 // first matrix of the chunk, `nb` its length; strides that are 0 (broadcast operand) stay 0.
 constexpr int64_t ND4_CHUNK = 32768;
 #define ND4_FOR_CHUNKS(batch) for (int64_t b0 = 0, nb = 0; (nb = ((batch) - b0 < ND4_CHUNK ? (batch) - b0 : ND4_CHUNK)) > 0; b0 += nb)
+
+// The kernels raise flag words where the reference throws. One small read-back decides: `count` ints from the device into the
+// handle's pinned buffer on h->stream, synchronised; *host stays valid until the next nd4_pinned of the handle.
+int read_flags(nd4hip_handle* h, const int* flags, size_t count, const int** host) {
+  void* hp = nullptr;
+  ND4_TRY(nd4_pinned(h, sizeof(int) * count, &hp));
+  ND4_HIP(hipMemcpyAsync(hp, flags, sizeof(int) * count, hipMemcpyDeviceToHost, h->stream));
+  ND4_HIP(hipStreamSynchronize(h->stream));
+  *host = static_cast<const int*>(hp);
+  return 0;
+}
 
 // algorithmic flop conventions of SURVEY.md 8(d) for nd4hip_profile_last
 inline double nd4_flops_qr(int64_t M, int64_t N) {          // with explicit Q: 4 (M N^2 - N^3 / 3) for M >= N, 8/3 N^3 when square
@@ -38,11 +49,7 @@ extern "C" int nd4hip_dgemm_batched_dev(nd4hip_handle* h, int64_t batch, int64_t
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgemm_batched: NULL handle");
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "dgemm_batched", (double)(2.0 * batch * I * K * J), (double)(8.0 * (double)(batch * I * J + (strideA ? batch : 1) * I * K + (strideB ? batch : 1) * K * J)));
-  ND4_CHECK_ARG(batch >= 0 && I >= 0 && K >= 0 && J >= 0, "nd4hip_dgemm_batched: negative extent");
-  ND4_CHECK_ARG(strideA == 0 || strideA >= I * K, "nd4hip_dgemm_batched: strideA must be 0 or >= I*K");
-  ND4_CHECK_ARG(strideB == 0 || strideB >= K * J, "nd4hip_dgemm_batched: strideB must be 0 or >= K*J");
-  if (batch == 0 || I == 0 || J == 0) return 0;
-  ND4_CHECK_ARG(C && (K == 0 || (A && B)), "nd4hip_dgemm_batched: NULL matrix pointer");   // K = 0: nothing is read, C = 0
+  ND4_ARGS(nd4_args_gemm("dgemm_batched", true, batch, I, K, J, A, strideA, B, strideB, C));
   ND4_FOR_CHUNKS(batch) {
     ND4_TRY(nd4_gemm(h, false, false, I, J, K, 1.0, A + b0 * strideA, K, strideA, B + b0 * strideB, J, strideB,
                      0.0, C + b0 * I * J, J, I * J, nb));
@@ -53,17 +60,12 @@ extern "C" int nd4hip_dgemm_batched_dev(nd4hip_handle* h, int64_t batch, int64_t
 extern "C" int nd4hip_zgemm_batched_dev(nd4hip_handle* h, int a_complex, int b_complex, int64_t batch, int64_t I, int64_t K, int64_t J,
                                         const double* A, int64_t strideA, const double* B, int64_t strideB, double* C) {
   // the argument checks come first: they need no handle (and are testable without a device)
-  ND4_CHECK_ARG(a_complex || b_complex, "nd4hip_zgemm_batched: at least one operand must be complex");
-  ND4_CHECK_ARG(batch >= 0 && I >= 0 && K >= 0 && J >= 0, "nd4hip_zgemm_batched: negative extent");
-  ND4_CHECK_ARG(strideA == 0 || strideA >= I * K, "nd4hip_zgemm_batched: strideA must be 0 or >= I*K");
-  ND4_CHECK_ARG(strideB == 0 || strideB >= K * J, "nd4hip_zgemm_batched: strideB must be 0 or >= K*J");
+  ND4_ARGS(nd4_args_gemm("zgemm_batched", a_complex || b_complex, batch, I, K, J, A, strideA, B, strideB, C));
   ND4_CHECK_ARG(h != nullptr, "nd4hip_zgemm_batched: NULL handle");
   Nd4DeviceGuard guard(h);
   const double ea = a_complex ? 2.0 : 1.0, eb = b_complex ? 2.0 : 1.0;     // doubles per element
   Nd4Prof prof(h, "zgemm_batched", (double)((a_complex && b_complex ? 8.0 : 4.0) * batch * I * K * J),
                8.0 * (2.0 * batch * I * J + ea * (strideA ? batch : 1) * I * K + eb * (strideB ? batch : 1) * K * J));
-  if (batch == 0 || I == 0 || J == 0) return 0;
-  ND4_CHECK_ARG(C && (K == 0 || (A && B)), "nd4hip_zgemm_batched: NULL matrix pointer");   // K = 0: nothing is read
   ND4_FOR_CHUNKS(batch) {
     if (!a_complex)   // RC: A (I x K) times the K x 2J real view of B, into the I x 2J real view of C: the reference's products
       ND4_TRY(nd4_gemm(h, false, false, I, 2 * J, K, 1.0, A + b0 * strideA, K, strideA, B + 2 * b0 * strideB, 2 * J, 2 * strideB,
@@ -92,9 +94,7 @@ extern "C" int nd4hip_dgetrf_batched_dev(nd4hip_handle* h, int64_t batch, int64_
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgetrf_batched: NULL handle");
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "dgetrf_batched", (double)(2.0 / 3.0 * batch * N * N * N), (double)(16.0 * batch * N * N));
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dgetrf_batched: negative extent");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && LU && P, "nd4hip_dgetrf_batched: NULL pointer");
+  ND4_ARGS(nd4_args_dense("dgetrf_batched", {batch, N}, {A, LU, P}));
   ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_getrf(h, nb, N, A + b0 * N * N, LU + b0 * N * N, P + b0 * N));
   return 0;
 }
@@ -112,11 +112,7 @@ extern "C" int nd4hip_dgetrs_batched_dev(nd4hip_handle* h, int64_t batch, int64_
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgetrs_batched: NULL handle");
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "dgetrs_batched", (double)(2.0 * batch * N * N * J), (double)(8.0 * batch * (double)(N * N + 2 * N * J)));
-  ND4_CHECK_ARG(batch >= 0 && N >= 0 && J >= 0, "nd4hip_dgetrs_batched: negative extent");
-  ND4_CHECK_ARG((strideLU == 0 || strideLU >= N * N) && (strideP == 0 || strideP >= N) && (strideY == 0 || strideY >= N * J),
-                "nd4hip_dgetrs_batched: a stride must be 0 or at least the size of one operand");
-  if (batch == 0 || N == 0 || J == 0) return 0;
-  ND4_CHECK_ARG(LU && P && Y && X, "nd4hip_dgetrs_batched: NULL pointer");
+  ND4_ARGS(nd4_args_solve("dgetrs_batched", batch, N, J, {{LU, strideLU, N * N}, {P, strideP, N}, {Y, strideY, N * J}}, X));
   ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_getrs(h, nb, N, J, LU + b0 * strideLU, strideLU, P + b0 * strideP, strideP, Y + b0 * strideY, strideY, X + b0 * N * J));
   return 0;
 }
@@ -126,11 +122,7 @@ extern "C" int nd4hip_dtrsm_batched_dev(nd4hip_handle* h, int upper, int unit_di
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dtrsm_batched: NULL handle");
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "dtrsm_batched", (double)(1.0 * batch * M * M * J), (double)(8.0 * batch * (double)(M * M / 2 + 2 * M * J)));
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && J >= 0, "nd4hip_dtrsm_batched: negative extent");
-  ND4_CHECK_ARG((strideT == 0 || strideT >= M * M) && (strideY == 0 || strideY >= M * J),
-                "nd4hip_dtrsm_batched: a stride must be 0 or at least the size of one operand");
-  if (batch == 0 || M == 0 || J == 0) return 0;
-  ND4_CHECK_ARG(T && Y && X, "nd4hip_dtrsm_batched: NULL pointer");
+  ND4_ARGS(nd4_args_solve("dtrsm_batched", batch, M, J, {{T, strideT, M * M}, {Y, strideY, M * J}}, X));
   if (X != Y || strideY != M * J) ND4_TRY(copy_rhs(h, batch, M, J, Y, strideY, X));
   ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_trsm(h, upper != 0, unit_diag != 0, nb, M, J, T + b0 * strideT, strideT, X + b0 * M * J));
   return 0;
@@ -143,14 +135,8 @@ extern "C" int nd4hip_dqrls_batched_dev(nd4hip_handle* h, int64_t batch, int64_t
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dqrls_batched: NULL handle");
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "dqrls_batched", (double)(0.0), (double)(0.0));
-  ND4_CHECK_ARG(batch >= 0 && N >= 0 && M >= 0 && I >= 0 && J >= 0, "nd4hip_dqrls_batched: negative extent");
-  ND4_CHECK_ARG(I <= N, "qr_lstsq(Q,R,y): Under-determined systems not supported. Use rrqr instead.");      // qr.js:209
-  ND4_CHECK_ARG((strideQ == 0 || strideQ >= N * M) && (strideR == 0 || strideR >= M * I) && (strideY == 0 || strideY >= N * J),
-                "nd4hip_dqrls_batched: a stride must be 0 or at least the size of one operand");
-  if (batch == 0 || I == 0 || J == 0) return 0;
-  ND4_CHECK_ARG(X != nullptr, "nd4hip_dqrls_batched: NULL pointer");
+  ND4_ARGS(nd4_args_factor_ls("dqrls_batched", true, batch, N, M, I, J, {{Q, strideQ, N * M}, {R, strideR, M * I}, {Y, strideY, N * J}}, X));
   if (N == 0 || M == 0) { ND4_HIP(hipMemsetAsync(X, 0, D * (size_t)(batch * I * J), h->stream)); return 0; }
-  ND4_CHECK_ARG(Q && R && Y, "nd4hip_dqrls_batched: NULL pointer");
   ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_qrls(h, nb, N, M, I, J, Q + b0 * strideQ, strideQ, R + b0 * strideR, strideR, Y + b0 * strideY, strideY, X + b0 * I * J));
   return 0;
 }
@@ -161,13 +147,9 @@ extern "C" int nd4hip_dsvdls_batched_dev(nd4hip_handle* h, int64_t batch, int64_
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dsvdls_batched: NULL handle");
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "dsvdls_batched", (double)(0.0), (double)(0.0));
-  ND4_CHECK_ARG(batch >= 0 && N >= 0 && M >= 0 && I >= 0 && J >= 0, "nd4hip_dsvdls_batched: negative extent");
-  ND4_CHECK_ARG((strideU == 0 || strideU >= N * M) && (strideSv == 0 || strideSv >= M) && (strideV == 0 || strideV >= M * I) &&
-                (strideY == 0 || strideY >= N * J), "nd4hip_dsvdls_batched: a stride must be 0 or at least the size of one operand");
-  if (batch == 0 || I == 0 || J == 0) return 0;
-  ND4_CHECK_ARG(X != nullptr, "nd4hip_dsvdls_batched: NULL pointer");
+  ND4_ARGS(nd4_args_factor_ls("dsvdls_batched", false, batch, N, M, I, J,
+                              {{U, strideU, N * M}, {sv, strideSv, M}, {V, strideV, M * I}, {Y, strideY, N * J}}, X));
   if (N == 0 || M == 0) { ND4_HIP(hipMemsetAsync(X, 0, D * (size_t)(batch * I * J), h->stream)); return 0; }
-  ND4_CHECK_ARG(U && sv && V && Y, "nd4hip_dsvdls_batched: NULL pointer");
   ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_svdls(h, nb, N, M, I, J, U + b0 * strideU, strideU, sv + b0 * strideSv, strideSv, V + b0 * strideV, strideV,
                                           Y + b0 * strideY, strideY, X + b0 * I * J));
   return 0;
@@ -178,20 +160,15 @@ extern "C" int nd4hip_dpotrf_batched_dev(nd4hip_handle* h, int64_t batch, int64_
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dpotrf_batched: NULL handle");
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "dpotrf_batched", (double)(batch * N * N * N / 3.0), (double)(16.0 * batch * N * N));
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dpotrf_batched: negative extent");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(S && L, "nd4hip_dpotrf_batched: NULL pointer");
+  ND4_ARGS(nd4_args_dense("dpotrf_batched", {batch, N}, {S, L}));
   Nd4WsScope scope(h);
   void* p = nullptr;
   ND4_TRY(nd4_ws_alloc(h, sizeof(int) * (size_t)batch, &p));
   int* flags = static_cast<int*>(p);
   ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_potrf(h, nb, N, S + b0 * N * N, L + b0 * N * N, flags + b0));
   // the reference throws on the first NaN pivot (cholesky.js:43-44): one small read-back decides it
-  void* hp = nullptr;
-  ND4_TRY(nd4_pinned(h, sizeof(int) * (size_t)batch, &hp));
-  int* host = static_cast<int*>(hp);
-  ND4_HIP(hipMemcpyAsync(host, flags, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, h->stream));
-  ND4_HIP(hipStreamSynchronize(h->stream));
+  const int* host = nullptr;
+  ND4_TRY(read_flags(h, flags, (size_t)batch, &host));
   for (int64_t b = 0; b < batch; b++)
     if (host[b]) { nd4_set_error("Matrix contains NaNs or is (near) singular."); return ND4HIP_ERR_SINGULAR; }
   return 0;
@@ -201,11 +178,7 @@ extern "C" int nd4hip_dpotrs_batched_dev(nd4hip_handle* h, int64_t batch, int64_
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dpotrs_batched: NULL handle");
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "dpotrs_batched", (double)(2.0 * batch * N * N * J), (double)(8.0 * batch * (double)(N * N + 2 * N * J)));
-  ND4_CHECK_ARG(batch >= 0 && N >= 0 && J >= 0, "nd4hip_dpotrs_batched: negative extent");
-  ND4_CHECK_ARG((strideL == 0 || strideL >= N * N) && (strideY == 0 || strideY >= N * J),
-                "nd4hip_dpotrs_batched: a stride must be 0 or at least the size of one operand");
-  if (batch == 0 || N == 0 || J == 0) return 0;
-  ND4_CHECK_ARG(L && Y && X, "nd4hip_dpotrs_batched: NULL pointer");
+  ND4_ARGS(nd4_args_solve("dpotrs_batched", batch, N, J, {{L, strideL, N * N}, {Y, strideY, N * J}}, X));
   ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_potrs(h, nb, N, J, L + b0 * strideL, strideL, Y + b0 * strideY, strideY, X + b0 * N * J));
   return 0;
 }
@@ -215,9 +188,7 @@ extern "C" int nd4hip_dldltrf_batched_dev(nd4hip_handle* h, int64_t batch, int64
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dldltrf_batched: NULL handle");
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "dldltrf_batched", (double)(batch * N * N * N / 3.0), (double)(16.0 * batch * N * N));
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dldltrf_batched: negative extent");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(S && LD, "nd4hip_dldltrf_batched: NULL pointer");
+  ND4_ARGS(nd4_args_dense("dldltrf_batched", {batch, N}, {S, LD}));
   ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_ldltrf(h, nb, N, S + b0 * N * N, LD + b0 * N * N));
   return 0;
 }
@@ -226,11 +197,7 @@ extern "C" int nd4hip_dldltrs_batched_dev(nd4hip_handle* h, int64_t batch, int64
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dldltrs_batched: NULL handle");
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "dldltrs_batched", (double)(2.0 * batch * N * N * J), (double)(8.0 * batch * (double)(N * N + 2 * N * J)));
-  ND4_CHECK_ARG(batch >= 0 && N >= 0 && J >= 0, "nd4hip_dldltrs_batched: negative extent");
-  ND4_CHECK_ARG((strideLD == 0 || strideLD >= N * N) && (strideY == 0 || strideY >= N * J),
-                "nd4hip_dldltrs_batched: a stride must be 0 or at least the size of one operand");
-  if (batch == 0 || N == 0 || J == 0) return 0;
-  ND4_CHECK_ARG(LD && Y && X, "nd4hip_dldltrs_batched: NULL pointer");
+  ND4_ARGS(nd4_args_solve("dldltrs_batched", batch, N, J, {{LD, strideLD, N * N}, {Y, strideY, N * J}}, X));
   ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_ldltrs(h, nb, N, J, LD + b0 * strideLD, strideLD, Y + b0 * strideY, strideY, X + b0 * N * J));
   return 0;
 }
@@ -239,16 +206,11 @@ extern "C" int nd4hip_dldltrs_batched_dev(nd4hip_handle* h, int64_t batch, int64
 int nd4_sytrf_bk_run(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* LD, int32_t* P, int tier, int64_t member0,
                      int64_t* first_bad) {
   // the argument checks come first: they need no handle (and are testable without a device)
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsytrf_bk_batched: negative extent");
-  ND4_CHECK_ARG(tier >= ND4HIP_PLDLP_TIER_AUTO && tier <= ND4HIP_PLDLP_TIER_GRID, "nd4hip_dsytrf_bk_batched: unknown tier %d", tier);
-  ND4_CHECK_ARG(tier == ND4HIP_PLDLP_TIER_AUTO || nd4_sytrf_bk_tier(nullptr, batch, N, tier) != 0,
-                "nd4hip_dsytrf_bk_batched: tier %d is not available at N = %lld", tier, (long long)N);
+  ND4_ARGS(nd4_args_sytrf_bk(batch, N, S, LD, P, tier));
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dsytrf_bk_batched: NULL handle");
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "dsytrf_bk_batched", (double)(batch * N * N * N / 3.0), (double)(16.0 * batch * N * N));
   const int t = nd4_sytrf_bk_tier(h, batch, N, tier);
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(S && LD && P, "nd4hip_dsytrf_bk_batched: NULL pointer");
   Nd4WsScope scope(h);
   void* p = nullptr;
   ND4_TRY(nd4_ws_alloc(h, sizeof(int) * (size_t)batch, &p));
@@ -256,11 +218,8 @@ int nd4_sytrf_bk_run(nd4hip_handle* h, int64_t batch, int64_t N, const double* S
   ND4_HIP(hipMemsetAsync(flags, 0, sizeof(int) * (size_t)batch, h->stream));
   ND4_TRY(nd4_sytrf_bk(h, batch, N, S, LD, P, flags, t));
   // the reference throws at the first zero column or NaN (pldlp.js:148-149): one small read-back decides it
-  void* hp = nullptr;
-  ND4_TRY(nd4_pinned(h, sizeof(int) * (size_t)batch, &hp));
-  int* host = static_cast<int*>(hp);
-  ND4_HIP(hipMemcpyAsync(host, flags, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, h->stream));
-  ND4_HIP(hipStreamSynchronize(h->stream));
+  const int* host = nullptr;
+  ND4_TRY(read_flags(h, flags, (size_t)batch, &host));
   for (int64_t b = 0; b < batch; b++)
     if (host[b]) {
       nd4_set_error("_pldlp_decomp(M,N, LD,LD_off, P,P_off): Zero column or NaN encountered. (matrix %lld)", (long long)(member0 + b));
@@ -277,11 +236,8 @@ extern "C" int nd4hip_dsytrf_bk_batched_dev(nd4hip_handle* h, int64_t batch, int
 }
 extern "C" int nd4hip_dsytrf_bk_tier(nd4hip_handle* h, int64_t batch, int64_t N, int tier) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dsytrf_bk_tier: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsytrf_bk_tier: negative extent");
-  ND4_CHECK_ARG(tier >= ND4HIP_PLDLP_TIER_AUTO && tier <= ND4HIP_PLDLP_TIER_GRID, "nd4hip_dsytrf_bk_tier: unknown tier %d", tier);
-  const int t = nd4_sytrf_bk_tier(h, batch, N, tier);
-  ND4_CHECK_ARG(t != 0, "nd4hip_dsytrf_bk_tier: tier %d is not available at N = %lld", tier, (long long)N);
-  return t;
+  ND4_ARGS(nd4_args_sytrf_bk_tier("dsytrf_bk_tier", batch, N, tier));
+  return nd4_sytrf_bk_tier(h, batch, N, tier);
 }
 extern "C" int nd4hip_dsytrf_bk_limits(int* lds_max_n, int* global_max_n, int* grid_tile) {
   nd4_sytrf_bk_limits(lds_max_n, global_max_n, grid_tile);
@@ -289,14 +245,11 @@ extern "C" int nd4hip_dsytrf_bk_limits(int* lds_max_n, int* global_max_n, int* g
 }
 extern "C" int nd4hip_dsytrs_bk_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, int64_t J, const double* LD, int64_t strideLD,
                                             const int32_t* P, int64_t strideP, const double* Y, int64_t strideY, double* X) {
-  ND4_CHECK_ARG(batch >= 0 && N >= 0 && J >= 0, "nd4hip_dsytrs_bk_batched: negative extent");
-  ND4_CHECK_ARG((strideLD == 0 || strideLD >= N * N) && (strideP == 0 || strideP >= N) && (strideY == 0 || strideY >= N * J),
-                "nd4hip_dsytrs_bk_batched: a stride must be 0 or at least the size of one operand");
+  // the argument checks come first: they need no handle (and are testable without a device)
+  ND4_ARGS(nd4_args_solve("dsytrs_bk_batched", batch, N, J, {{LD, strideLD, N * N}, {P, strideP, N}, {Y, strideY, N * J}}, X));
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dsytrs_bk_batched: NULL handle");
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "dsytrs_bk_batched", (double)(2.0 * batch * N * N * J), (double)(8.0 * batch * (double)(N * N + 2 * N * J)));
-  if (batch == 0 || N == 0 || J == 0) return 0;
-  ND4_CHECK_ARG(LD && P && Y && X, "nd4hip_dsytrs_bk_batched: NULL pointer");
   Nd4WsScope scope(h);
   void* p = nullptr;
   ND4_TRY(nd4_ws_alloc(h, sizeof(int), &p));
@@ -304,11 +257,8 @@ extern "C" int nd4hip_dsytrs_bk_batched_dev(nd4hip_handle* h, int64_t batch, int
   ND4_HIP(hipMemsetAsync(flag, 0, sizeof(int), h->stream));
   ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_sytrs_bk(h, nb, N, J, LD + b0 * strideLD, strideLD, P + b0 * strideP, strideP, Y + b0 * strideY, strideY,
                                              X + b0 * N * J, flag));
-  void* hp = nullptr;
-  ND4_TRY(nd4_pinned(h, sizeof(int), &hp));
-  int* host = static_cast<int*>(hp);
-  ND4_HIP(hipMemcpyAsync(host, flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  ND4_HIP(hipStreamSynchronize(h->stream));
+  const int* host = nullptr;
+  ND4_TRY(read_flags(h, flag, 1, &host));
   ND4_CHECK_ARG(host[0] == 0, "pldlp_solve(LD,P,y): P contains out-of-bounds indices.");
   return 0;
 }
@@ -318,9 +268,7 @@ extern "C" int nd4hip_dgebrd_batched_dev(nd4hip_handle* h, int64_t batch, int64_
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgebrd_batched: NULL handle");
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "dgebrd_batched", (double)(batch * nd4_flops_qr(M, N)), (double)(8.0 * batch * (double)(2 * M * N + M * M + N * N)));
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dgebrd_batched: negative extent");
-  if (batch == 0 || M == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && U && B && V, "nd4hip_dgebrd_batched: NULL pointer");
+  ND4_ARGS(nd4_args_dense("dgebrd_batched", {batch, M, N}, {A, U, B, V}));
   { const int64_t K = M < N ? M : N, Jb = M >= N ? K : K + 1;
     ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_gebrd(h, nb, M, N, A + b0 * M * N, U + b0 * M * K, B + b0 * K * Jb, V + b0 * Jb * N)); }
   return 0;
@@ -331,9 +279,7 @@ extern "C" int nd4hip_dgehrd_batched_dev(nd4hip_handle* h, int64_t batch, int64_
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgehrd_batched: NULL handle");
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "dgehrd_batched", (double)(14.0 / 3.0 * batch * N * N * N), (double)(24.0 * batch * N * N));
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dgehrd_batched: negative extent");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && U && H, "nd4hip_dgehrd_batched: NULL pointer");
+  ND4_ARGS(nd4_args_dense("dgehrd_batched", {batch, N}, {A, U, H}));
   ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_gehrd(h, nb, N, A + b0 * N * N, U + b0 * N * N, H + b0 * N * N));
   return 0;
 }
@@ -343,9 +289,7 @@ extern "C" int nd4hip_dgeqrf_q_batched_dev(nd4hip_handle* h, int64_t batch, int6
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgeqrf_q_batched: NULL handle");
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "dgeqrf_q_batched", (double)(batch * nd4_flops_qr(M, N)), (double)(8.0 * batch * (double)(M * N + (M + N) * (M < N ? M : N))));
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dgeqrf_q_batched: negative extent");
-  if (batch == 0 || M == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && Q && R, "nd4hip_dgeqrf_q_batched: NULL pointer");
+  ND4_ARGS(nd4_args_dense("dgeqrf_q_batched", {batch, M, N}, {A, Q, R}));
   { const int64_t L = M < N ? M : N;
     ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_geqrf_q(h, nb, M, N, A + b0 * M * N, Q + b0 * M * L, R + b0 * L * N)); }
   return 0;
@@ -356,9 +300,7 @@ extern "C" int nd4hip_dgeqrf_full_batched_dev(nd4hip_handle* h, int64_t batch, i
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgeqrf_full_batched: NULL handle");
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "dgeqrf_full_batched", (double)(batch * nd4_flops_qr(M, N)), (double)(8.0 * batch * (double)(2 * M * N + M * M)));
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dgeqrf_full_batched: negative extent");
-  if (batch == 0 || M == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && Q && R, "nd4hip_dgeqrf_full_batched: NULL pointer");
+  ND4_ARGS(nd4_args_dense("dgeqrf_full_batched", {batch, M, N}, {A, Q, R}));
   ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_geqrf_q_ex(h, nb, M, N, A + b0 * M * N, Q + b0 * M * M, R + b0 * M * N, true));
   return 0;
 }
@@ -368,9 +310,7 @@ extern "C" int nd4hip_dgeqrf_qty_batched_dev(nd4hip_handle* h, int64_t batch, in
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgeqrf_qty_batched: NULL handle");
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "dgeqrf_qty_batched", (double)(batch * nd4_flops_qr(M, N)), (double)(16.0 * batch * (double)(M * N + M * L)));
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0 && L >= 0, "nd4hip_dgeqrf_qty_batched: negative extent");
-  if (batch == 0 || M == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && (Y || L == 0), "nd4hip_dgeqrf_qty_batched: NULL pointer");
+  ND4_ARGS(nd4_args_geqrf_qty(batch, M, N, L, A, Y));
   Nd4WsScope scope(h);
   void* p = nullptr;
   ND4_TRY(nd4_ws_alloc(h, D * (size_t)batch * (size_t)(M * M + M * N + M * L), &p));
@@ -394,9 +334,7 @@ static int geqp3_dev(nd4hip_handle* h, const char* name, bool full, int64_t batc
   Nd4DeviceGuard guard(h);
   const int64_t L = M < N ? M : N, qc = full ? M : L, rr = full ? M : L;
   Nd4Prof prof(h, name, (double)batch * nd4_flops_qp3(M, N), 8.0 * batch * (double)(M * N + M * qc + rr * N) + 4.0 * batch * (double)N);
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_%s: negative extent", name);
-  if (batch == 0 || M == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && Q && R && P, "nd4hip_%s: NULL pointer", name);
+  ND4_ARGS(nd4_args_dense(name, {batch, M, N}, {A, Q, R, P}));
   ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_geqp3(h, nb, M, N, A + b0 * M * N, Q + b0 * M * qc, R + b0 * rr * N, P + b0 * N, full));
   return 0;
 }
@@ -413,13 +351,7 @@ extern "C" int nd4hip_dsrrqr_batched_dev(nd4hip_handle* h, int64_t batch, int64_
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dsrrqr_batched: NULL handle");
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "dsrrqr_batched", (double)batch * nd4_flops_qp3(M, N), 8.0 * batch * (double)(M * N + M * M + M * N) + 4.0 * batch * (double)(N + 1));
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dsrrqr_batched: negative extent");
-  ND4_CHECK_ARG(dtol >= 1.0, "srrqr_decomp_full(A,opt): Invalid opt.dtol: %s. Must be >=1.", dtol != dtol ? "NaN" : "a value below 1");
-  ND4_CHECK_ARG(dtol <= 1.79769313486231570e308, "Assertion failed. Invalid dtol: Infinity.");
-  ND4_CHECK_ARG(!(ztol != ztol), "srrqr_decomp_full(A,opt): invalid opt.ztol: NaN. Must be non-negative number.");
-  ND4_CHECK_ARG(ztol <= 1.79769313486231570e308, "Assertion failed. Invalid ztol: Infinity.");
-  if (batch == 0) return 0;
-  ND4_CHECK_ARG(P && rank && (Q || M == 0) && (A && R || M * N == 0), "nd4hip_dsrrqr_batched: NULL pointer");
+  ND4_ARGS(nd4_args_srrqr(batch, M, N, A, dtol, ztol, Q, R, P, rank));
   ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_srrqr(h, nb, M, N, A ? A + b0 * M * N : nullptr, dtol, ztol, Q ? Q + b0 * M * M : nullptr,
                                           R ? R + b0 * M * N : nullptr, P + b0 * N, rank + b0));
   return 0;
@@ -432,9 +364,7 @@ extern "C" int nd4hip_durv_batched_dev(nd4hip_handle* h, int64_t batch, int64_t 
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "durv_batched", (double)batch * (nd4_flops_qp3(M, N) + nd4_flops_qr(N, M < N ? M : N)),
                8.0 * batch * (double)(2 * M * N + M * M + N * N) + 4.0 * batch);
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_durv_batched: negative extent");
-  if (batch == 0) return 0;
-  ND4_CHECK_ARG(rank && (U || M == 0) && (V || N == 0) && (A && R || M * N == 0), "nd4hip_durv_batched: NULL pointer");
+  ND4_ARGS(nd4_args_urv(batch, M, N, A, U, R, V, rank));
   if (N == 0) {
     ND4_HIP(hipMemsetAsync(rank, 0, sizeof(int32_t) * (size_t)batch, h->stream));
     if (M > 0) ND4_TRY(nd4_set_identity(h, M, M, U, M, batch, M * M));
@@ -454,13 +384,7 @@ extern "C" int nd4hip_durvls_batched_dev(nd4hip_handle* h, int64_t batch, int64_
   const int64_t Lr = J < K ? J : K;
   Nd4Prof prof(h, "durvls_batched", (double)batch * (2.0 * Lr * I * Jc + (double)Lr * Lr * Jc + 2.0 * Lr * L * Jc),
                8.0 * batch * (double)(I * J + J * K + K * L + I * Jc + L * Jc));
-  ND4_CHECK_ARG(batch >= 0 && I >= 0 && J >= 0 && K >= 0 && L >= 0 && Jc >= 0, "nd4hip_durvls_batched: negative extent");
-  ND4_CHECK_ARG(J <= I && K <= L, "Assertion failed.");
-  ND4_CHECK_ARG((strideU == 0 || strideU >= I * J) && (strideR == 0 || strideR >= J * K) && (strideV == 0 || strideV >= K * L) &&
-                (strideRank == 0 || strideRank == 1) && (strideY == 0 || strideY >= I * Jc),
-                "nd4hip_durvls_batched: a stride must be 0 or at least the size of one operand");
-  if (batch == 0 || L * Jc == 0) return 0;
-  ND4_CHECK_ARG(U && R && V && rank && Y && X, "nd4hip_durvls_batched: NULL pointer");
+  ND4_ARGS(nd4_args_urvls(batch, I, J, K, L, Jc, U, strideU, R, strideR, V, strideV, rank, strideRank, Y, strideY, X));
   ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_urvls(h, nb, I, J, K, L, Jc, U + b0 * strideU, strideU, R + b0 * strideR, strideR, V + b0 * strideV, strideV,
                                           rank + b0 * strideRank, strideRank, Y + b0 * strideY, strideY, X + b0 * L * Jc));
   return 0;
@@ -475,10 +399,7 @@ int det_dev(nd4hip_handle* h, const char* op, bool log_form, int64_t batch, int6
   Nd4DeviceGuard guard(h);
   const double m = (double)M, n = (double)N;
   Nd4Prof prof(h, op, (double)batch * 2.0 * (m * n * n - n * n * n / 3.0), 8.0 * batch * (double)(M * N + (log_form ? 2 : 1)));
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_%s: negative extent", op);
-  ND4_CHECK_ARG(M >= N, log_form ? "det_tri(A): A must be square matrices." : "det_tri(a): a must be square matrices.");
-  if (batch == 0) return 0;
-  ND4_CHECK_ARG(D && (L || !log_form) && (A || M * N == 0), "nd4hip_%s: NULL pointer", op);
+  ND4_ARGS(nd4_args_det(op, log_form, batch, M, N, A, D, L));
   const bool force = det_force_qr();
   if (N == 0 || (M == N && N <= 64 && !force)) return nd4_det(h, log_form, batch, M, N, A, D, L, false);   // one launch, any batch
   ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_det(h, log_form, nb, M, N, A + b0 * M * N, D + b0, log_form ? L + b0 : nullptr, force));
@@ -489,9 +410,7 @@ int dettri_dev(nd4hip_handle* h, const char* op, bool log_form, int64_t batch, i
   ND4_CHECK_ARG(h != nullptr, "nd4hip_%s: NULL handle", op);
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, op, (double)batch * N, 8.0 * batch * (double)(N + (log_form ? 2 : 1)));
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_%s: negative extent", op);
-  if (batch == 0) return 0;
-  ND4_CHECK_ARG(D && (L || !log_form) && (A || N == 0), "nd4hip_%s: NULL pointer", op);
+  ND4_ARGS(nd4_args_det(op, log_form, batch, N, N, A, D, L));          // the square case of det's rules
   return nd4_dettri(h, log_form, batch, N, A, N * N, D, L);
 }
 }  // namespace
@@ -514,8 +433,7 @@ extern "C" int nd4hip_dnrmfro_dev(nd4hip_handle* h, int64_t n, const double* A, 
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dnrmfro: NULL handle");
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "dnrmfro", 3.0 * (double)n, 8.0 * (double)n + 8.0);
-  ND4_CHECK_ARG(n >= 0, "nd4hip_dnrmfro: negative extent");
-  ND4_CHECK_ARG(out && (A || n == 0), "nd4hip_dnrmfro: NULL pointer");
+  ND4_ARGS(nd4_args_nrmfro(n, A, out));
   if (n == 0) { ND4_HIP(hipMemsetAsync(out, 0, sizeof(double), h->stream)); return 0; }
   return nd4_nrmfro(h, n, A, out);
 }
@@ -524,11 +442,8 @@ extern "C" int nd4hip_dnrmfro_dev(nd4hip_handle* h, int64_t n, const double* A, 
 namespace {
 // the reference throws at the first matrix that trips; the kernels raise a flag word per matrix instead: one small read-back
 int ev_verdict(nd4hip_handle* h, const int* flags, int64_t batch) {
-  void* hp = nullptr;
-  ND4_TRY(nd4_pinned(h, sizeof(int) * (size_t)batch, &hp));
-  int* host = static_cast<int*>(hp);
-  ND4_HIP(hipMemcpyAsync(host, flags, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, h->stream));
-  ND4_HIP(hipStreamSynchronize(h->stream));
+  const int* host = nullptr;
+  ND4_TRY(read_flags(h, flags, (size_t)batch, &host));
   for (int64_t b = 0; b < batch; b++) {
     ND4_CHECK_ARG(!(host[b] & ND4HIP_EV_FLAG_ASSERT), "Assertion failed.");
     ND4_CHECK_ARG(!(host[b] & ND4HIP_EV_FLAG_REAL2X2), "schur_eigenvals(T): T must not contain real eigenvalued 2x2 blocks.");
@@ -544,16 +459,13 @@ int ev_flags(nd4hip_handle* h, int64_t batch, int** flags) {
   ND4_HIP(hipMemsetAsync(p, 0, sizeof(int) * (size_t)batch, h->stream));
   return 0;
 }
-constexpr int64_t EV_MAX_N = 32768;
 }  // namespace
 
 extern "C" int nd4hip_dtreval_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* T, double* Lam) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dtreval_batched: NULL handle");
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "dtreval_batched", 8.0 * (double)batch * N, 8.0 * (double)batch * 5.0 * N);
-  ND4_CHECK_ARG(batch >= 0 && N >= 0 && N <= EV_MAX_N, "nd4hip_dtreval_batched: extent out of range");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(T && Lam, "nd4hip_dtreval_batched: NULL pointer");
+  ND4_ARGS(nd4_args_ev("dtreval_batched", EV_MAX_N, batch, N, {T, Lam}));
   Nd4WsScope scope(h);
   int* flags = nullptr;
   ND4_TRY(ev_flags(h, batch, &flags));
@@ -566,9 +478,7 @@ extern "C" int nd4hip_dtrevc_batched_dev(nd4hip_handle* h, int64_t batch, int64_
   Nd4DeviceGuard guard(h);
   const double n = (double)N;
   Nd4Prof prof(h, "dtrevc_batched", (double)batch * (4.0 / 3.0 * n * n * n + 4.0 * n * n * n), 8.0 * (double)batch * (4.0 * n * n + 2.0 * n));
-  ND4_CHECK_ARG(batch >= 0 && N >= 0 && N <= EV_MAX_N, "nd4hip_dtrevc_batched: extent out of range");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(Q && T && Lam && V, "nd4hip_dtrevc_batched: NULL pointer");
+  ND4_ARGS(nd4_args_ev("dtrevc_batched", EV_MAX_N, batch, N, {Q, T, Lam, V}));
   Nd4WsScope scope(h);
   int* flags = nullptr;
   ND4_TRY(ev_flags(h, batch, &flags));
@@ -580,10 +490,7 @@ extern "C" int nd4hip_dgebal_batched_dev(nd4hip_handle* h, int64_t batch, int64_
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgebal_batched: NULL handle");
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "dgebal_batched", 6.0 * (double)batch * N * N, 8.0 * (double)batch * (4.0 * N * N + N));   // per sweep; two sweeps are typical
-  ND4_CHECK_ARG(p >= 1.0, "nd4hip_dgebal_batched: p must be >= 1");
-  ND4_CHECK_ARG(batch >= 0 && N >= 0 && N <= EV_MAX_N, "nd4hip_dgebal_batched: extent out of range");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && D && B, "nd4hip_dgebal_batched: NULL pointer");
+  ND4_ARGS(nd4_args_gebal(batch, N, p, A, D, B));
   Nd4WsScope scope(h);
   int* flags = nullptr;
   ND4_TRY(ev_flags(h, batch, &flags));
@@ -595,9 +502,7 @@ extern "C" int nd4hip_zgebak_batched_dev(nd4hip_handle* h, int64_t batch, int64_
   ND4_CHECK_ARG(h != nullptr, "nd4hip_zgebak_batched: NULL handle");
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "zgebak_batched", 10.0 * (double)batch * N * N, 8.0 * (double)batch * (8.0 * N * N + N));
-  ND4_CHECK_ARG(batch >= 0 && N >= 0 && N <= EV_MAX_N, "nd4hip_zgebak_batched: extent out of range");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(D && V && W && V != W, "nd4hip_zgebak_batched: NULL or aliased pointer");
+  ND4_ARGS(nd4_args_gebak(true, batch, N, D, V, W));
   ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_gebak(h, nb, N, D + b0 * N, V + 2 * b0 * N * N, W + 2 * b0 * N * N));
   return 0;
 }
@@ -606,11 +511,8 @@ extern "C" int nd4hip_zgebak_batched_dev(nd4hip_handle* h, int64_t batch, int64_
 namespace {
 // flag words and sweep counts of the batch in one read-back; *sweeps_max (may be NULL) receives the largest count
 int hseqr_verdict(nd4hip_handle* h, const int* fs, int64_t batch, int* sweeps_max) {
-  void* hp = nullptr;
-  ND4_TRY(nd4_pinned(h, sizeof(int) * 2 * (size_t)batch, &hp));
-  int* host = static_cast<int*>(hp);
-  ND4_HIP(hipMemcpyAsync(host, fs, sizeof(int) * 2 * (size_t)batch, hipMemcpyDeviceToHost, h->stream));
-  ND4_HIP(hipStreamSynchronize(h->stream));
+  const int* host = nullptr;
+  ND4_TRY(read_flags(h, fs, 2 * (size_t)batch, &host));
   int mx = 0;
   for (int64_t b = 0; b < batch; b++) if (host[batch + b] > mx) mx = host[batch + b];
   if (sweeps_max) *sweeps_max = mx;
@@ -632,10 +534,7 @@ extern "C" int nd4hip_dhseqr_batched_ex_dev(nd4hip_handle* h, int64_t batch, int
   const double n = (double)N;
   Nd4Prof prof(h, "dhseqr_batched", 25.0 * (double)batch * n * n * n, 8.0 * (double)batch * 4.0 * n * n);
   if (sweeps_out) *sweeps_out = 0;
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dhseqr_batched: extent out of range");
-  ND4_CHECK_ARG(tier >= ND4HIP_SCHUR_TIER_AUTO && tier <= ND4HIP_SCHUR_TIER_GLOBAL, "nd4hip_dhseqr_batched: unknown tier %d", tier);
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(U && H && Q && T, "nd4hip_dhseqr_batched: NULL pointer");
+  ND4_ARGS(nd4_args_hseqr(batch, N, U, H, Q, T, tier));
   Nd4WsScope scope(h);
   void* p = nullptr;
   ND4_TRY(nd4_ws_alloc(h, sizeof(int) * 2 * (size_t)batch, &p));                  // flag words, then sweep counts
@@ -659,9 +558,7 @@ extern "C" int nd4hip_dgees_batched_dev(nd4hip_handle* h, int64_t batch, int64_t
   const double n = (double)N;
   Nd4Prof prof(h, "dgees_batched", (25.0 + 14.0 / 3.0) * (double)batch * n * n * n, 8.0 * (double)batch * 3.0 * n * n);
   if (sweeps_out) *sweeps_out = 0;
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dgees_batched: extent out of range");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && Q && T, "nd4hip_dgees_batched: NULL pointer");
+  ND4_ARGS(nd4_args_ev("dgees_batched", INT64_MAX, batch, N, {A, Q, T}));
   ND4_TRY(nd4hip_dgehrd_batched_dev(h, batch, N, A, Q, T));
   return nd4hip_dhseqr_batched_dev(h, batch, N, Q, T, Q, T, sweeps_out);
 }
@@ -671,9 +568,7 @@ extern "C" int nd4hip_dgeev_batched_dev(nd4hip_handle* h, int64_t batch, int64_t
   Nd4DeviceGuard guard(h);
   const double n = (double)N;
   Nd4Prof prof(h, "dgeev_batched", (25.0 + 14.0 / 3.0 + (V ? 16.0 / 3.0 : 0.0)) * (double)batch * n * n * n, 8.0 * (double)batch * (V ? 3.0 : 1.0) * n * n);
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dgeev_batched: extent out of range");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && Lam, "nd4hip_dgeev_batched: NULL pointer");
+  ND4_ARGS(nd4_args_ev("dgeev_batched", INT64_MAX, batch, N, {A, Lam}));
   // eigen.js:33-88 per chunk, the intermediates in the workspace: D [N], B, Q, T [N, N] and the eigenvectors before zgebak
   const int64_t chunk = nd4_hseqr_chunk(N);
   for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
@@ -702,9 +597,7 @@ extern "C" int nd4hip_dqp3rank_batched_dev(nd4hip_handle* h, int64_t batch, int6
   Nd4DeviceGuard guard(h);
   const int64_t L = M < N ? M : N;
   Nd4Prof prof(h, "dqp3rank_batched", 3.0 * batch * (double)(L * N - L * (L - 1) / 2), 8.0 * batch * (double)(L * N - L * (L - 1) / 2) + 4.0 * batch);
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dqp3rank_batched: negative extent");
-  if (batch == 0) return 0;
-  ND4_CHECK_ARG(rank && (R || L == 0), "nd4hip_dqp3rank_batched: NULL pointer");
+  ND4_ARGS(nd4_args_qp3rank(batch, M, N, R, rank));
   ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_qp3rank(h, nb, M, N, R + b0 * M * N, M * N, rank + b0));
   return 0;
 }
@@ -718,15 +611,11 @@ extern "C" int nd4hip_dqp3ls_batched_dev(nd4hip_handle* h, int64_t batch, int64_
   const int64_t L = M < I ? M : I;
   Nd4Prof prof(h, "dqp3ls_batched", (double)batch * (2.0 * L * N * J + (double)L * L * J),
                8.0 * (double)((strideQ ? batch : 1) * N * M + (strideR ? batch : 1) * M * I + (strideY ? batch : 1) * N * J + batch * I * J));
-  ND4_CHECK_ARG(batch >= 0 && N >= 0 && M >= 0 && I >= 0 && J >= 0, "nd4hip_dqp3ls_batched: negative extent");
-  ND4_CHECK_ARG((strideQ == 0 || strideQ >= N * M) && (strideR == 0 || strideR >= M * I) && (strideP == 0 || strideP >= I) &&
-                (strideY == 0 || strideY >= N * J), "nd4hip_dqp3ls_batched: a stride must be 0 or at least the size of one operand");
-  if (batch == 0) return 0;
+  ND4_ARGS(nd4_args_qp3ls(batch, N, M, I, J, Q, strideQ, R, strideR, P, strideP, Y, strideY, X));
   if (I == 0 || J == 0) {
     if (rank) ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_qp3rank(h, nb, M, I, R ? R + b0 * strideR : nullptr, strideR, rank + b0));
     return 0;
   }
-  ND4_CHECK_ARG(Q && R && P && Y && X, "nd4hip_dqp3ls_batched: NULL pointer");
   ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_qp3ls(h, nb, N, M, I, J, Q + b0 * strideQ, strideQ, R + b0 * strideR, strideR, P + b0 * strideP, strideP,
                                           Y + b0 * strideY, strideY, X + b0 * I * J, rank ? rank + b0 : nullptr));
   return 0;
@@ -738,11 +627,9 @@ extern "C" int nd4hip_dgesvdj_batched_dev(nd4hip_handle* h, int64_t batch, int64
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgesvdj_batched: NULL handle");
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "dgesvdj_batched", (double)(batch * nd4_flops_svd(M, N)), (double)(8.0 * batch * (double)(M * N + (M + N + 1) * (M < N ? M : N))));
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dgesvdj_batched: negative extent");
   if (sweeps_out) *sweeps_out = 0;
   if (offnorm_out) *offnorm_out = 0.0;
-  if (batch == 0 || M == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && U && sv && V, "nd4hip_dgesvdj_batched: NULL pointer");
+  ND4_ARGS(nd4_args_dense("dgesvdj_batched", {batch, M, N}, {A, U, sv, V}));
   {
     const int64_t L = M < N ? M : N;
     int sweeps = 0; double off = 0.0; unsigned long long rot = 0;
@@ -773,10 +660,7 @@ extern "C" int nd4hip_dbdsdc_batched_dev(nd4hip_handle* h, int64_t batch, int64_
   Nd4DeviceGuard guard(h);
   // the merges: about 2 K^3 flops each for U and for V over the whole tree
   Nd4Prof prof(h, "dbdsdc_batched", 4.0 * batch * (double)K * K * K, 8.0 * batch * (double)(2 * K + J - 1 + K * K + J * J));
-  ND4_CHECK_ARG(batch >= 0 && K >= 0, "nd4hip_dbdsdc_batched: negative extent");
-  ND4_CHECK_ARG(J == K || J == K + 1, "nd4hip_dbdsdc_batched: B must be K x K or K x (K+1)");
-  if (batch == 0 || K == 0) return 0;
-  ND4_CHECK_ARG(d && (e || J < 2) && U2 && sv && V2, "nd4hip_dbdsdc_batched: NULL pointer");
+  ND4_ARGS(nd4_args_bdsdc(batch, K, J, d, e, U2, sv, V2));
   ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_bdsdc_rows(h, nb, K, J, d + b0 * K, e ? e + b0 * (J - 1) : nullptr, U2 + b0 * K * K, sv + b0 * K, V2 + b0 * J * J));
   return 0;
 }
@@ -786,9 +670,7 @@ extern "C" int nd4hip_dgesdd_batched_dev(nd4hip_handle* h, int64_t batch, int64_
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgesdd_batched: NULL handle");
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "svd_dc", (double)(batch * nd4_flops_svd(M, N)), (double)(8.0 * batch * (double)(M * N + (M + N + 1) * (M < N ? M : N))));
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dgesdd_batched: negative extent");
-  if (batch == 0 || M == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && U && sv && V, "nd4hip_dgesdd_batched: NULL pointer");
+  ND4_ARGS(nd4_args_dense("dgesdd_batched", {batch, M, N}, {A, U, sv, V}));
   { const int64_t L = M < N ? M : N;
     ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_gesdd(h, nb, M, N, A + b0 * M * N, U + b0 * M * L, sv + b0 * L, V + b0 * L * N)); }
   return 0;
@@ -807,10 +689,7 @@ extern "C" int nd4hip_dsyevd_batched_dev(nd4hip_handle* h, int64_t batch, int64_
   Nd4DeviceGuard guard(h);
   const double n3 = (double)N * N * N;
   Nd4Prof prof(h, "dsyevd_batched", batch * ((10.0 / 3.0 + 2.0 + (V ? 2.0 : 0.0)) * n3), 8.0 * batch * (double)(N * N / 2 + N + (V ? N * N : 0)));
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsyevd_batched: negative extent");
-  ND4_CHECK_ARG(N <= 2048, "nd4hip_dsyevd_batched: the divide & conquer solver takes N <= 2048");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(S && lambda, "nd4hip_dsyevd_batched: NULL pointer");
+  ND4_ARGS(nd4_args_syev("dsyevd_batched", false, batch, N, S, lambda));
   ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_syevd(h, nb, N, S + b0 * N * N, lambda + b0 * N, V ? V + b0 * N * N : nullptr));
   return 0;
 }
@@ -823,10 +702,7 @@ extern "C" int nd4hip_dsyevj_batched_dev(nd4hip_handle* h, int64_t batch, int64_
   Nd4DeviceGuard guard(h);
   const double n3 = (double)N * N * N;
   Nd4Prof prof(h, "syevj", batch * 8.0 * (V ? 8.0 : 4.0) * n3, 8.0 * batch * (double)(N * N / 2 + N + (V ? N * N : 0)));
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsyevj_batched: negative extent");
-  ND4_CHECK_ARG(N <= 128, "nd4hip_dsyevj_batched: the Jacobi route takes N <= 128");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(S && lambda, "nd4hip_dsyevj_batched: NULL pointer");
+  ND4_ARGS(nd4_args_syev("dsyevj_batched", true, batch, N, S, lambda));
   ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_syevj(h, nb, N, S + b0 * N * N, lambda + b0 * N, V ? V + b0 * N * N : nullptr, sweeps ? sweeps + b0 : nullptr));
   return 0;
 }
@@ -836,19 +712,13 @@ extern "C" int nd4hip_dsyevj_batched_dev(nd4hip_handle* h, int64_t batch, int64_
 int nd4_sygvd_run(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B, int64_t strideB, double* lambda,
                   double* X, int32_t* sweeps, int64_t member0) {
   // the argument checks come first: they need no handle (and are testable without a device)
-  ND4_CHECK_ARG(algo == 0 || algo == 1, "nd4hip_dsygvd_batched: algo must be 0 (dc) or 1 (jacobi)");
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsygvd_batched: negative extent");
-  ND4_CHECK_ARG(algo == 1 || N <= 2048, "nd4hip_dsygvd_batched: the divide & conquer solver takes N <= 2048");
-  ND4_CHECK_ARG(algo == 0 || N <= 128, "nd4hip_dsygvd_batched: the Jacobi route takes N <= 128");
-  ND4_CHECK_ARG(strideB == 0 || strideB == N * N, "nd4hip_dsygvd_batched: strideB must be N*N or 0");
+  ND4_ARGS(nd4_args_sygvd(algo, batch, N, A, B, strideB, lambda));
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dsygvd_batched: NULL handle");
   Nd4DeviceGuard guard(h);
   const double n3 = (double)N * N * N;
   const double solver = algo == 1 ? 8.0 * (X ? 8.0 : 4.0) : 10.0 / 3.0 + 2.0 + (X ? 2.0 : 0.0);
   Nd4Prof prof(h, "dsygvd_batched", batch * ((solver + 1.0 / 3.0 + 2.0 + (X ? 1.0 : 0.0)) * n3),
                8.0 * ((double)(batch + (strideB ? batch : 1)) * (double)(N * N / 2) + batch * (double)(N + (X ? N * N : 0))));
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && B && lambda, "nd4hip_dsygvd_batched: NULL pointer");
   return nd4_sygvd(h, algo, batch, N, A, B, strideB, lambda, X, algo == 1 ? sweeps : nullptr, member0);
 }
 extern "C" int nd4hip_dsygvd_batched_dev(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B,
@@ -857,14 +727,11 @@ extern "C" int nd4hip_dsygvd_batched_dev(nd4hip_handle* h, int algo, int64_t bat
 }
 extern "C" int nd4hip_dsygst_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, const double* L, int64_t strideL,
                                          double* C) {
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsygst_batched: negative extent");
-  ND4_CHECK_ARG(N <= 2048, "nd4hip_dsygst_batched: N <= 2048");
-  ND4_CHECK_ARG(strideL == 0 || strideL == N * N, "nd4hip_dsygst_batched: strideL must be N*N or 0");
+  // the argument checks come first: they need no handle (and are testable without a device)
+  ND4_ARGS(nd4_args_sygst(batch, N, A, L, strideL, C));
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dsygst_batched: NULL handle");
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "dsygst_batched", batch * 2.0 * (double)N * N * N, 8.0 * batch * 2.0 * (double)(N * N));
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && L && C, "nd4hip_dsygst_batched: NULL pointer");
   return nd4_sygst(h, batch, N, A, L, strideL, C);
 }
 

@@ -10,7 +10,7 @@
 //     the calling host thread, the kernels do not, which is all the overlap needs;
 //   * a single large matmul is pipelined over the ROWS of A and C (B is a broadcast operand).
 // Error path: a failing chunk stops the block, the block's streams are synchronised BEFORE its staging returns to the cache.
-#include "nd4hip_internal.h"
+#include "nd4hip_args.h"
 #include <algorithm>
 #include <atomic>
 #include <climits>
@@ -255,11 +255,7 @@ extern "C" int nd4hip_partition(int64_t batch, int n_dev, int index, int64_t* lo
 extern "C" int nd4hip_dgemm_batched(nd4hip_handle* h, int64_t batch, int64_t I, int64_t K, int64_t J,
                                     const double* A, int64_t strideA, const double* B, int64_t strideB, double* C) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgemm_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && I >= 0 && K >= 0 && J >= 0, "nd4hip_dgemm_batched: negative extent");
-  ND4_CHECK_ARG(strideA == 0 || strideA >= I * K, "nd4hip_dgemm_batched: strideA must be 0 or >= I*K");
-  ND4_CHECK_ARG(strideB == 0 || strideB >= K * J, "nd4hip_dgemm_batched: strideB must be 0 or >= K*J");
-  if (batch == 0 || I == 0 || J == 0) return 0;
-  ND4_CHECK_ARG(C && (K == 0 || (A && B)), "nd4hip_dgemm_batched: NULL matrix pointer");
+  ND4_ARGS(nd4_args_gemm("dgemm_batched", true, batch, I, K, J, A, strideA, B, strideB, C));
   if (batch == 1 && K > 0) {
     // one product: the "batch" of the driver is the rows of A and C (a row of C needs its row of A and all of B), so the
     // upload of the next row block and the download of the previous one overlap the MFMA kernel; one device (replicas only)
@@ -280,13 +276,8 @@ extern "C" int nd4hip_dgemm_batched(nd4hip_handle* h, int64_t batch, int64_t I, 
 // complex: the same plans as nd4hip_dgemm_batched, with 16-byte elements for the complex operands
 extern "C" int nd4hip_zgemm_batched(nd4hip_handle* h, int a_complex, int b_complex, int64_t batch, int64_t I, int64_t K, int64_t J,
                                     const double* A, int64_t strideA, const double* B, int64_t strideB, double* C) {
-  ND4_CHECK_ARG(a_complex || b_complex, "nd4hip_zgemm_batched: at least one operand must be complex");
-  ND4_CHECK_ARG(batch >= 0 && I >= 0 && K >= 0 && J >= 0, "nd4hip_zgemm_batched: negative extent");
-  ND4_CHECK_ARG(strideA == 0 || strideA >= I * K, "nd4hip_zgemm_batched: strideA must be 0 or >= I*K");
-  ND4_CHECK_ARG(strideB == 0 || strideB >= K * J, "nd4hip_zgemm_batched: strideB must be 0 or >= K*J");
+  ND4_ARGS(nd4_args_gemm("zgemm_batched", a_complex || b_complex, batch, I, K, J, A, strideA, B, strideB, C));
   ND4_CHECK_ARG(h != nullptr, "nd4hip_zgemm_batched: NULL handle");
-  if (batch == 0 || I == 0 || J == 0) return 0;
-  ND4_CHECK_ARG(C && (K == 0 || (A && B)), "nd4hip_zgemm_batched: NULL matrix pointer");
   const int ac = a_complex ? 1 : 0, bc = b_complex ? 1 : 0;
   const size_t ea = a_complex ? 2 * D : D, eb = b_complex ? 2 * D : D;
   if (batch == 1 && K > 0) {
@@ -308,9 +299,7 @@ extern "C" int nd4hip_zgemm_batched(nd4hip_handle* h, int a_complex, int b_compl
 // ------------------------------------------------------------------------------------ LU
 extern "C" int nd4hip_dgetrf_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* LU, int32_t* Pv) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgetrf_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dgetrf_batched: negative extent");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && LU && Pv, "nd4hip_dgetrf_batched: NULL pointer");
+  ND4_ARGS(nd4_args_dense("dgetrf_batched", {batch, N}, {A, LU, Pv}));
   std::vector<Operand> ops{in_op(A, N * N, N * N), out_op(LU, N * N), out_op(Pv, N, 4)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
     return nd4hip_dgetrf_batched_dev(hd, nb, N, P(d, 0), P(d, 1), static_cast<int32_t*>(d[2]));
@@ -322,11 +311,7 @@ extern "C" int nd4hip_dgetrf_batched(nd4hip_handle* h, int64_t batch, int64_t N,
 extern "C" int nd4hip_dgetrs_batched(nd4hip_handle* h, int64_t batch, int64_t N, int64_t J, const double* LU, int64_t strideLU,
                                      const int32_t* Pv, int64_t strideP, const double* Y, int64_t strideY, double* X) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgetrs_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && N >= 0 && J >= 0, "nd4hip_dgetrs_batched: negative extent");
-  ND4_CHECK_ARG((strideLU == 0 || strideLU >= N * N) && (strideP == 0 || strideP >= N) && (strideY == 0 || strideY >= N * J),
-                "nd4hip_dgetrs_batched: a stride must be 0 or at least the size of one operand");
-  if (batch == 0 || N == 0 || J == 0) return 0;
-  ND4_CHECK_ARG(LU && Pv && Y && X, "nd4hip_dgetrs_batched: NULL pointer");
+  ND4_ARGS(nd4_args_solve("dgetrs_batched", batch, N, J, {{LU, strideLU, N * N}, {Pv, strideP, N}, {Y, strideY, N * J}}, X));
   std::vector<Operand> ops{in_op(LU, N * N, strideLU), in_op(Pv, N, strideP, 4), in_op(Y, N * J, strideY), out_op(X, N * J)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
     return nd4hip_dgetrs_batched_dev(hd, nb, N, J, P(d, 0), strideLU, static_cast<const int32_t*>(d[1]), strideP, P(d, 2), strideY, P(d, 3));
@@ -336,11 +321,7 @@ extern "C" int nd4hip_dgetrs_batched(nd4hip_handle* h, int64_t batch, int64_t N,
 extern "C" int nd4hip_dtrsm_batched(nd4hip_handle* h, int upper, int unit_diag, int64_t batch, int64_t M, int64_t J,
                                     const double* T, int64_t strideT, const double* Y, int64_t strideY, double* X) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dtrsm_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && J >= 0, "nd4hip_dtrsm_batched: negative extent");
-  ND4_CHECK_ARG((strideT == 0 || strideT >= M * M) && (strideY == 0 || strideY >= M * J),
-                "nd4hip_dtrsm_batched: a stride must be 0 or at least the size of one operand");
-  if (batch == 0 || M == 0 || J == 0) return 0;
-  ND4_CHECK_ARG(T && Y && X, "nd4hip_dtrsm_batched: NULL pointer");
+  ND4_ARGS(nd4_args_solve("dtrsm_batched", batch, M, J, {{T, strideT, M * M}, {Y, strideY, M * J}}, X));
   std::vector<Operand> ops{in_op(T, M * M, strideT), in_op(Y, M * J, strideY), out_op(X, M * J)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
     return nd4hip_dtrsm_batched_dev(hd, upper, unit_diag, nb, M, J, P(d, 0), strideT, P(d, 1), strideY, P(d, 2));
@@ -353,14 +334,8 @@ extern "C" int nd4hip_dqrls_batched(nd4hip_handle* h, int64_t batch, int64_t N, 
                                     const double* Q, int64_t strideQ, const double* R, int64_t strideR,
                                     const double* Y, int64_t strideY, double* X) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dqrls_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && N >= 0 && M >= 0 && I >= 0 && J >= 0, "nd4hip_dqrls_batched: negative extent");
-  ND4_CHECK_ARG(I <= N, "qr_lstsq(Q,R,y): Under-determined systems not supported. Use rrqr instead.");      // qr.js:209
-  ND4_CHECK_ARG((strideQ == 0 || strideQ >= N * M) && (strideR == 0 || strideR >= M * I) && (strideY == 0 || strideY >= N * J),
-                "nd4hip_dqrls_batched: a stride must be 0 or at least the size of one operand");
-  if (batch == 0 || I == 0 || J == 0) return 0;
-  ND4_CHECK_ARG(X != nullptr, "nd4hip_dqrls_batched: NULL pointer");
+  ND4_ARGS(nd4_args_factor_ls("dqrls_batched", true, batch, N, M, I, J, {{Q, strideQ, N * M}, {R, strideR, M * I}, {Y, strideY, N * J}}, X));
   if (N == 0 || M == 0) { memset(X, 0, D * (size_t)(batch * I * J)); return 0; }
-  ND4_CHECK_ARG(Q && R && Y, "nd4hip_dqrls_batched: NULL pointer");
   std::vector<Operand> ops{in_op(Q, N * M, strideQ), in_op(R, M * I, strideR), in_op(Y, N * J, strideY), out_op(X, I * J)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
     return nd4hip_dqrls_batched_dev(hd, nb, N, M, I, J, P(d, 0), strideQ, P(d, 1), strideR, P(d, 2), strideY, P(d, 3));
@@ -371,13 +346,9 @@ extern "C" int nd4hip_dsvdls_batched(nd4hip_handle* h, int64_t batch, int64_t N,
                                      const double* U, int64_t strideU, const double* sv, int64_t strideSv,
                                      const double* V, int64_t strideV, const double* Y, int64_t strideY, double* X) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dsvdls_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && N >= 0 && M >= 0 && I >= 0 && J >= 0, "nd4hip_dsvdls_batched: negative extent");
-  ND4_CHECK_ARG((strideU == 0 || strideU >= N * M) && (strideSv == 0 || strideSv >= M) && (strideV == 0 || strideV >= M * I) &&
-                (strideY == 0 || strideY >= N * J), "nd4hip_dsvdls_batched: a stride must be 0 or at least the size of one operand");
-  if (batch == 0 || I == 0 || J == 0) return 0;
-  ND4_CHECK_ARG(X != nullptr, "nd4hip_dsvdls_batched: NULL pointer");
+  ND4_ARGS(nd4_args_factor_ls("dsvdls_batched", false, batch, N, M, I, J,
+                              {{U, strideU, N * M}, {sv, strideSv, M}, {V, strideV, M * I}, {Y, strideY, N * J}}, X));
   if (N == 0 || M == 0) { memset(X, 0, D * (size_t)(batch * I * J)); return 0; }
-  ND4_CHECK_ARG(U && sv && V && Y, "nd4hip_dsvdls_batched: NULL pointer");
   const size_t nS = (size_t)(strideSv ? (batch - 1) * strideSv + M : M);
   for (size_t i = 0; i < nS; i++) ND4_CHECK_ARG(std::isfinite(sv[i]), "svd_solve(): NaN or Infinity encountered.");   // svd.js:171-172
   std::vector<Operand> ops{in_op(U, N * M, strideU), in_op(sv, M, strideSv), in_op(V, M * I, strideV), in_op(Y, N * J, strideY), out_op(X, I * J)};
@@ -390,9 +361,7 @@ extern "C" int nd4hip_dsvdls_batched(nd4hip_handle* h, int64_t batch, int64_t N,
 // ---- Cholesky / LDL^T
 extern "C" int nd4hip_dpotrf_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* L) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dpotrf_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dpotrf_batched: negative extent");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(S && L, "nd4hip_dpotrf_batched: NULL pointer");
+  ND4_ARGS(nd4_args_dense("dpotrf_batched", {batch, N}, {S, L}));
   std::vector<Operand> ops{in_op(S, N * N, N * N), out_op(L, N * N)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_dpotrf_batched_dev(hd, nb, N, P(d, 0), P(d, 1)); };
   return run_host(h, batch, ops, fn);
@@ -400,11 +369,7 @@ extern "C" int nd4hip_dpotrf_batched(nd4hip_handle* h, int64_t batch, int64_t N,
 extern "C" int nd4hip_dpotrs_batched(nd4hip_handle* h, int64_t batch, int64_t N, int64_t J, const double* L, int64_t strideL,
                                      const double* Y, int64_t strideY, double* X) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dpotrs_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && N >= 0 && J >= 0, "nd4hip_dpotrs_batched: negative extent");
-  ND4_CHECK_ARG((strideL == 0 || strideL >= N * N) && (strideY == 0 || strideY >= N * J),
-                "nd4hip_dpotrs_batched: a stride must be 0 or at least the size of one operand");
-  if (batch == 0 || N == 0 || J == 0) return 0;
-  ND4_CHECK_ARG(L && Y && X, "nd4hip_dpotrs_batched: NULL pointer");
+  ND4_ARGS(nd4_args_solve("dpotrs_batched", batch, N, J, {{L, strideL, N * N}, {Y, strideY, N * J}}, X));
   std::vector<Operand> ops{in_op(L, N * N, strideL), in_op(Y, N * J, strideY), out_op(X, N * J)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
     return nd4hip_dpotrs_batched_dev(hd, nb, N, J, P(d, 0), strideL, P(d, 1), strideY, P(d, 2));
@@ -413,9 +378,7 @@ extern "C" int nd4hip_dpotrs_batched(nd4hip_handle* h, int64_t batch, int64_t N,
 }
 extern "C" int nd4hip_dldltrf_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* LD) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dldltrf_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dldltrf_batched: negative extent");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(S && LD, "nd4hip_dldltrf_batched: NULL pointer");
+  ND4_ARGS(nd4_args_dense("dldltrf_batched", {batch, N}, {S, LD}));
   std::vector<Operand> ops{in_op(S, N * N, N * N), out_op(LD, N * N)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_dldltrf_batched_dev(hd, nb, N, P(d, 0), P(d, 1)); };
   return run_host(h, batch, ops, fn);
@@ -423,11 +386,7 @@ extern "C" int nd4hip_dldltrf_batched(nd4hip_handle* h, int64_t batch, int64_t N
 extern "C" int nd4hip_dldltrs_batched(nd4hip_handle* h, int64_t batch, int64_t N, int64_t J, const double* LD, int64_t strideLD,
                                       const double* Y, int64_t strideY, double* X) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dldltrs_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && N >= 0 && J >= 0, "nd4hip_dldltrs_batched: negative extent");
-  ND4_CHECK_ARG((strideLD == 0 || strideLD >= N * N) && (strideY == 0 || strideY >= N * J),
-                "nd4hip_dldltrs_batched: a stride must be 0 or at least the size of one operand");
-  if (batch == 0 || N == 0 || J == 0) return 0;
-  ND4_CHECK_ARG(LD && Y && X, "nd4hip_dldltrs_batched: NULL pointer");
+  ND4_ARGS(nd4_args_solve("dldltrs_batched", batch, N, J, {{LD, strideLD, N * N}, {Y, strideY, N * J}}, X));
   std::vector<Operand> ops{in_op(LD, N * N, strideLD), in_op(Y, N * J, strideY), out_op(X, N * J)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
     return nd4hip_dldltrs_batched_dev(hd, nb, N, J, P(d, 0), strideLD, P(d, 1), strideY, P(d, 2));
@@ -437,13 +396,8 @@ extern "C" int nd4hip_dldltrs_batched(nd4hip_handle* h, int64_t batch, int64_t N
 
 // ---- pivoted LDL^T (pldlp.js)
 extern "C" int nd4hip_dsytrf_bk_batched_ex(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* LD, int32_t* Pv, int tier) {
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsytrf_bk_batched: negative extent");
-  ND4_CHECK_ARG(tier >= ND4HIP_PLDLP_TIER_AUTO && tier <= ND4HIP_PLDLP_TIER_GRID, "nd4hip_dsytrf_bk_batched: unknown tier %d", tier);
-  ND4_CHECK_ARG(tier == ND4HIP_PLDLP_TIER_AUTO || nd4_sytrf_bk_tier(nullptr, batch, N, tier) != 0,
-                "nd4hip_dsytrf_bk_batched: tier %d is not available at N = %lld", tier, (long long)N);
+  ND4_ARGS(nd4_args_sytrf_bk(batch, N, S, LD, Pv, tier));
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dsytrf_bk_batched: NULL handle");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(S && LD && Pv, "nd4hip_dsytrf_bk_batched: NULL pointer");
   // AUTO is decided once, by the whole batch: the chunks and devices below must not each choose their own tier
   const int t = nd4_sytrf_bk_tier(h, batch, N, tier);
   std::vector<Operand> ops{in_op(S, N * N, N * N), out_op(LD, N * N), out_op(Pv, N, 4)};
@@ -468,11 +422,7 @@ extern "C" int nd4hip_dsytrf_bk_batched(nd4hip_handle* h, int64_t batch, int64_t
 }
 extern "C" int nd4hip_dsytrs_bk_batched(nd4hip_handle* h, int64_t batch, int64_t N, int64_t J, const double* LD, int64_t strideLD,
                                         const int32_t* Pv, int64_t strideP, const double* Y, int64_t strideY, double* X) {
-  ND4_CHECK_ARG(batch >= 0 && N >= 0 && J >= 0, "nd4hip_dsytrs_bk_batched: negative extent");
-  ND4_CHECK_ARG((strideLD == 0 || strideLD >= N * N) && (strideP == 0 || strideP >= N) && (strideY == 0 || strideY >= N * J),
-                "nd4hip_dsytrs_bk_batched: a stride must be 0 or at least the size of one operand");
-  if (batch == 0 || N == 0 || J == 0) return 0;
-  ND4_CHECK_ARG(LD && Pv && Y && X, "nd4hip_dsytrs_bk_batched: NULL pointer");
+  ND4_ARGS(nd4_args_solve("dsytrs_bk_batched", batch, N, J, {{LD, strideLD, N * N}, {Pv, strideP, N}, {Y, strideY, N * J}}, X));
   {  // pldlp_p's checks (pldlp.js:408-435), before any device work
     std::vector<char> seen((size_t)N);
     for (int64_t b = 0; b < (strideP ? batch : 1); b++) {
@@ -501,9 +451,7 @@ extern "C" int nd4hip_dsytrs_bk_batched(nd4hip_handle* h, int64_t batch, int64_t
 // ---- structure functions (tri.js:23-42, diag.js:23-88, permute.js:23-306): pure data movement, sharded like every batched call
 extern "C" int nd4hip_dtranspose_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* B) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dtranspose_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dtranspose_batched: negative extent");
-  if (batch == 0 || M == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && B, "nd4hip_dtranspose_batched: NULL pointer");
+  ND4_ARGS(nd4_args_dense("dtranspose_batched", {batch, M, N}, {A, B}));
   ND4_CHECK_ARG(!nd4_struct_overlap(A, batch * M * N, B, batch * M * N), "nd4hip_dtranspose_batched: B must not overlap A");
   std::vector<Operand> ops{in_op(A, M * N, M * N), out_op(B, M * N)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_dtranspose_batched_dev(hd, nb, M, N, P(d, 0), P(d, 1)); };
@@ -511,9 +459,7 @@ extern "C" int nd4hip_dtranspose_batched(nd4hip_handle* h, int64_t batch, int64_
 }
 extern "C" int nd4hip_dtri_batched(nd4hip_handle* h, int upper, int64_t k, int64_t batch, int64_t M, int64_t N, const double* A, double* B) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dtri_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dtri_batched: negative extent");
-  if (batch == 0 || M == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && B, "nd4hip_dtri_batched: NULL pointer");
+  ND4_ARGS(nd4_args_dense("dtri_batched", {batch, M, N}, {A, B}));
   ND4_CHECK_ARG(!nd4_struct_overlap(A, batch * M * N, B, batch * M * N), "nd4hip_dtri_batched: B must not overlap A");
   std::vector<Operand> ops{in_op(A, M * N, M * N), out_op(B, M * N)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_dtri_batched_dev(hd, upper, k, nb, M, N, P(d, 0), P(d, 1)); };
@@ -521,12 +467,8 @@ extern "C" int nd4hip_dtri_batched(nd4hip_handle* h, int upper, int64_t k, int64
 }
 extern "C" int nd4hip_ddiag_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t offset, const double* A, double* dg) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_ddiag_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_ddiag_batched: negative extent");
-  ND4_CHECK_ARG(offset > -M && offset < N, "nd4hip_ddiag_batched: offset=%lld out of the shape [%lld,%lld]", (long long)offset, (long long)M,
-                (long long)N);
-  const int64_t L = std::min(std::min(M, M + offset), std::min(N, N - offset));
-  if (batch == 0 || L <= 0) return 0;
-  ND4_CHECK_ARG(A && dg, "nd4hip_ddiag_batched: NULL pointer");
+  ND4_ARGS(nd4_args_diag(batch, M, N, offset, A, dg));
+  const int64_t L = nd4_diag_length(M, N, offset);
   ND4_CHECK_ARG(!nd4_struct_overlap(A, batch * M * N, dg, batch * L), "nd4hip_ddiag_batched: d must not overlap A");
   std::vector<Operand> ops{in_op(A, M * N, M * N), out_op(dg, L)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_ddiag_batched_dev(hd, nb, M, N, offset, P(d, 0), P(d, 1)); };
@@ -534,9 +476,7 @@ extern "C" int nd4hip_ddiag_batched(nd4hip_handle* h, int64_t batch, int64_t M, 
 }
 extern "C" int nd4hip_ddiagmat_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* dg, double* Dm) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_ddiagmat_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_ddiagmat_batched: negative extent");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(dg && Dm, "nd4hip_ddiagmat_batched: NULL pointer");
+  ND4_ARGS(nd4_args_dense("ddiagmat_batched", {batch, N}, {dg, Dm}));
   ND4_CHECK_ARG(!nd4_struct_overlap(dg, batch * N, Dm, batch * N * N), "nd4hip_ddiagmat_batched: D must not overlap d");
   std::vector<Operand> ops{in_op(dg, N, N), out_op(Dm, N * N)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_ddiagmat_batched_dev(hd, nb, N, P(d, 0), P(d, 1)); };
@@ -545,12 +485,8 @@ extern "C" int nd4hip_ddiagmat_batched(nd4hip_handle* h, int64_t batch, int64_t 
 extern "C" int nd4hip_dpermute_batched(nd4hip_handle* h, int cols, int inverse, int64_t batch, int64_t M, int64_t N, const double* A,
                                        int64_t strideA, const int32_t* Pv, int64_t strideP, double* B) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dpermute_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dpermute_batched: negative extent");
+  ND4_ARGS(nd4_args_permute(cols, batch, M, N, A, strideA, Pv, strideP, B));
   const int64_t L = cols ? N : M;
-  ND4_CHECK_ARG((strideA == 0 || strideA >= M * N) && (strideP == 0 || strideP >= L),
-                "nd4hip_dpermute_batched: a stride must be 0 or at least the size of one operand");
-  if (batch == 0 || M == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && Pv && B, "nd4hip_dpermute_batched: NULL pointer");
   ND4_CHECK_ARG(!nd4_struct_overlap(A, (strideA ? (batch - 1) * strideA : 0) + M * N, B, batch * M * N),
                 "nd4hip_dpermute_batched: B must not overlap A");
   // the indices are checked on the device, where they are used: a bad one fails its chunk with the reference's text
@@ -564,9 +500,7 @@ extern "C" int nd4hip_dpermute_batched(nd4hip_handle* h, int cols, int inverse, 
 // ---- bidiag_decomp (bidiag.js:245-319), hessenberg_decomp (hessenberg.js:89-115)
 extern "C" int nd4hip_dgebrd_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* U, double* B, double* V) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgebrd_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dgebrd_batched: negative extent");
-  if (batch == 0 || M == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && U && B && V, "nd4hip_dgebrd_batched: NULL pointer");
+  ND4_ARGS(nd4_args_dense("dgebrd_batched", {batch, M, N}, {A, U, B, V}));
   const int64_t K = M < N ? M : N, J = M >= N ? K : K + 1;
   std::vector<Operand> ops{in_op(A, M * N, M * N), out_op(U, M * K), out_op(B, K * J), out_op(V, J * N)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_dgebrd_batched_dev(hd, nb, M, N, P(d, 0), P(d, 1), P(d, 2), P(d, 3)); };
@@ -574,9 +508,7 @@ extern "C" int nd4hip_dgebrd_batched(nd4hip_handle* h, int64_t batch, int64_t M,
 }
 extern "C" int nd4hip_dgehrd_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* U, double* H) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgehrd_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dgehrd_batched: negative extent");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && U && H, "nd4hip_dgehrd_batched: NULL pointer");
+  ND4_ARGS(nd4_args_dense("dgehrd_batched", {batch, N}, {A, U, H}));
   std::vector<Operand> ops{in_op(A, N * N, N * N), out_op(U, N * N), out_op(H, N * N)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_dgehrd_batched_dev(hd, nb, N, P(d, 0), P(d, 1), P(d, 2)); };
   return run_host(h, batch, ops, fn);
@@ -585,9 +517,7 @@ extern "C" int nd4hip_dgehrd_batched(nd4hip_handle* h, int64_t batch, int64_t N,
 // ------------------------------------------------------------------------------------ QR
 extern "C" int nd4hip_dgeqrf_q_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* Q, double* R) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgeqrf_q_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dgeqrf_q_batched: negative extent");
-  if (batch == 0 || M == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && Q && R, "nd4hip_dgeqrf_q_batched: NULL pointer");
+  ND4_ARGS(nd4_args_dense("dgeqrf_q_batched", {batch, M, N}, {A, Q, R}));
   const int64_t L = M < N ? M : N;
   std::vector<Operand> ops{in_op(A, M * N, M * N), out_op(Q, M * L), out_op(R, L * N)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_dgeqrf_q_batched_dev(hd, nb, M, N, P(d, 0), P(d, 1), P(d, 2)); };
@@ -595,18 +525,14 @@ extern "C" int nd4hip_dgeqrf_q_batched(nd4hip_handle* h, int64_t batch, int64_t 
 }
 extern "C" int nd4hip_dgeqrf_full_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* Q, double* R) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgeqrf_full_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dgeqrf_full_batched: negative extent");
-  if (batch == 0 || M == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && Q && R, "nd4hip_dgeqrf_full_batched: NULL pointer");
+  ND4_ARGS(nd4_args_dense("dgeqrf_full_batched", {batch, M, N}, {A, Q, R}));
   std::vector<Operand> ops{in_op(A, M * N, M * N), out_op(Q, M * M), out_op(R, M * N)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_dgeqrf_full_batched_dev(hd, nb, M, N, P(d, 0), P(d, 1), P(d, 2)); };
   return run_host(h, batch, ops, fn);
 }
 extern "C" int nd4hip_dgeqrf_qty_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t L, double* A, double* Y) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgeqrf_qty_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0 && L >= 0, "nd4hip_dgeqrf_qty_batched: negative extent");
-  if (batch == 0 || M == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && (Y || L == 0), "nd4hip_dgeqrf_qty_batched: NULL pointer");
+  ND4_ARGS(nd4_args_geqrf_qty(batch, M, N, L, A, Y));
   std::vector<Operand> ops{inout_op(A, M * N)};
   if (L > 0) ops.push_back(inout_op(Y, M * L));
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
@@ -618,9 +544,7 @@ extern "C" int nd4hip_dgeqrf_qty_batched(nd4hip_handle* h, int64_t batch, int64_
 // ------------------------------------------------------------------------------------ column-pivoted QR
 extern "C" int nd4hip_dgeqp3_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* Q, double* R, int32_t* Pv) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgeqp3_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dgeqp3_batched: negative extent");
-  if (batch == 0 || M == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && Q && R && Pv, "nd4hip_dgeqp3_batched: NULL pointer");
+  ND4_ARGS(nd4_args_dense("dgeqp3_batched", {batch, M, N}, {A, Q, R, Pv}));
   const int64_t L = M < N ? M : N;
   std::vector<Operand> ops{in_op(A, M * N, M * N), out_op(Q, M * L), out_op(R, L * N), out_op(Pv, N, 4)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
@@ -630,9 +554,7 @@ extern "C" int nd4hip_dgeqp3_batched(nd4hip_handle* h, int64_t batch, int64_t M,
 }
 extern "C" int nd4hip_dgeqp3_full_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* Q, double* R, int32_t* Pv) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgeqp3_full_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dgeqp3_full_batched: negative extent");
-  if (batch == 0 || M == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && Q && R && Pv, "nd4hip_dgeqp3_full_batched: NULL pointer");
+  ND4_ARGS(nd4_args_dense("dgeqp3_full_batched", {batch, M, N}, {A, Q, R, Pv}));
   std::vector<Operand> ops{in_op(A, M * N, M * N), out_op(Q, M * M), out_op(R, M * N), out_op(Pv, N, 4)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
     return nd4hip_dgeqp3_full_batched_dev(hd, nb, M, N, P(d, 0), P(d, 1), P(d, 2), static_cast<int32_t*>(d[3]));
@@ -651,11 +573,8 @@ int qp3_rank_verdict(const int32_t* rank, int64_t batch) {
 
 extern "C" int nd4hip_dqp3rank_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* R, int32_t* rank) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dqp3rank_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dqp3rank_batched: negative extent");
-  if (batch == 0) return 0;
-  ND4_CHECK_ARG(rank != nullptr, "nd4hip_dqp3rank_batched: NULL pointer");
+  ND4_ARGS(nd4_args_qp3rank(batch, M, N, R, rank));
   if (M == 0 || N == 0) { memset(rank, 0, sizeof(int32_t) * (size_t)batch); return 0; }
-  ND4_CHECK_ARG(R != nullptr, "nd4hip_dqp3rank_batched: NULL pointer");
   std::vector<Operand> ops{in_op(R, M * N, M * N), out_op(rank, 1, 4)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
     return nd4hip_dqp3rank_batched_dev(hd, nb, M, N, P(d, 0), static_cast<int32_t*>(d[1]));
@@ -668,11 +587,9 @@ extern "C" int nd4hip_dqp3ls_batched(nd4hip_handle* h, int64_t batch, int64_t N,
                                      const double* Q, int64_t strideQ, const double* R, int64_t strideR, const int32_t* Pv, int64_t strideP,
                                      const double* Y, int64_t strideY, double* X, int32_t* rank) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dqp3ls_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && N >= 0 && M >= 0 && I >= 0 && J >= 0, "nd4hip_dqp3ls_batched: negative extent");
-  ND4_CHECK_ARG((strideQ == 0 || strideQ >= N * M) && (strideR == 0 || strideR >= M * I) && (strideP == 0 || strideP >= I) &&
-                (strideY == 0 || strideY >= N * J), "nd4hip_dqp3ls_batched: a stride must be 0 or at least the size of one operand");
-  if (batch == 0) return 0;
-  ND4_CHECK_ARG(Q && R && Pv && Y && (X || I * J == 0), "nd4hip_dqp3ls_batched: NULL pointer");
+  ND4_ARGS(nd4_args_qp3ls(batch, N, M, I, J, Q, strideQ, R, strideR, Pv, strideP, Y, strideY, X));
+  // the rank-only shape (I = 0 or J = 0) is staged like every other, so this form needs its four inputs there too
+  ND4_CHECK_ARG(Q && R && Pv && Y, "nd4hip_dqp3ls_batched: NULL pointer");
   // the reference's un-permutation refuses indices that do not form a permutation (rrqr.js:560-563)
   {
     std::vector<char> seen((size_t)I);
@@ -713,13 +630,7 @@ int srrqr_rank_verdict(const int32_t* rank, int64_t batch) {
 extern "C" int nd4hip_dsrrqr_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double dtol, double ztol,
                                      double* Q, double* R, int32_t* Pv, int32_t* rank) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dsrrqr_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dsrrqr_batched: negative extent");
-  ND4_CHECK_ARG(dtol >= 1.0, "srrqr_decomp_full(A,opt): Invalid opt.dtol: %s. Must be >=1.", dtol != dtol ? "NaN" : "a value below 1");
-  ND4_CHECK_ARG(dtol <= 1.79769313486231570e308, "Assertion failed. Invalid dtol: Infinity.");
-  ND4_CHECK_ARG(!(ztol != ztol), "srrqr_decomp_full(A,opt): invalid opt.ztol: NaN. Must be non-negative number.");
-  ND4_CHECK_ARG(ztol <= 1.79769313486231570e308, "Assertion failed. Invalid ztol: Infinity.");
-  if (batch == 0) return 0;
-  ND4_CHECK_ARG(Pv && rank && (Q || M == 0) && (A && R || M * N == 0), "nd4hip_dsrrqr_batched: NULL pointer");
+  ND4_ARGS(nd4_args_srrqr(batch, M, N, A, dtol, ztol, Q, R, Pv, rank));
   if (M == 0 || N == 0) {                                    // nothing to decide: P = identity, rank 0, Q = I
     for (int64_t b = 0; b < batch; b++) {
       rank[b] = 0;
@@ -741,9 +652,7 @@ extern "C" int nd4hip_dsrrqr_batched(nd4hip_handle* h, int64_t batch, int64_t M,
 extern "C" int nd4hip_durv_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* U, double* R, double* V,
                                    int32_t* rank) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_durv_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_durv_batched: negative extent");
-  if (batch == 0) return 0;
-  ND4_CHECK_ARG(rank && (U || M == 0) && (V || N == 0) && (A && R || M * N == 0), "nd4hip_durv_batched: NULL pointer");
+  ND4_ARGS(nd4_args_urv(batch, M, N, A, U, R, V, rank));
   if (M == 0 || N == 0) {                                    // rank 0, U = I, V = I
     for (int64_t b = 0; b < batch; b++) {
       rank[b] = 0;
@@ -764,13 +673,7 @@ extern "C" int nd4hip_durvls_batched(nd4hip_handle* h, int64_t batch, int64_t I,
                                      const double* U, int64_t strideU, const double* R, int64_t strideR, const double* V, int64_t strideV,
                                      const int32_t* rank, int64_t strideRank, const double* Y, int64_t strideY, double* X) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_durvls_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && I >= 0 && J >= 0 && K >= 0 && L >= 0 && Jc >= 0, "nd4hip_durvls_batched: negative extent");
-  ND4_CHECK_ARG(J <= I && K <= L, "Assertion failed.");
-  ND4_CHECK_ARG((strideU == 0 || strideU >= I * J) && (strideR == 0 || strideR >= J * K) && (strideV == 0 || strideV >= K * L) &&
-                (strideRank == 0 || strideRank == 1) && (strideY == 0 || strideY >= I * Jc),
-                "nd4hip_durvls_batched: a stride must be 0 or at least the size of one operand");
-  if (batch == 0 || L * Jc == 0) return 0;
-  ND4_CHECK_ARG(U && R && V && rank && Y && X, "nd4hip_durvls_batched: NULL pointer");
+  ND4_ARGS(nd4_args_urvls(batch, I, J, K, L, Jc, U, strideU, R, strideR, V, strideV, rank, strideRank, Y, strideY, X));
   std::vector<Operand> ops{in_op(U, I * J, strideU), in_op(R, J * K, strideR), in_op(V, K * L, strideV), in_op(rank, 1, strideRank, 4),
                            in_op(Y, I * Jc, strideY), out_op(X, L * Jc)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
@@ -795,10 +698,7 @@ int det_verdict(const double* D, int64_t batch) {
 
 extern "C" int nd4hip_ddet_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* det) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_ddet_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_ddet_batched: negative extent");
-  ND4_CHECK_ARG(M >= N, "det_tri(a): a must be square matrices.");
-  if (batch == 0) return 0;
-  ND4_CHECK_ARG(det && (A || M * N == 0), "nd4hip_ddet_batched: NULL pointer");
+  ND4_ARGS(nd4_args_det("ddet_batched", false, batch, M, N, A, det, nullptr));
   std::vector<Operand> ops{in_op(A, M * N, M * N), out_op(det, 1)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_ddet_batched_dev(hd, nb, M, N, P(d, 0), P(d, 1)); };
   ND4_TRY(run_host(h, batch, ops, fn));
@@ -807,10 +707,7 @@ extern "C" int nd4hip_ddet_batched(nd4hip_handle* h, int64_t batch, int64_t M, i
 
 extern "C" int nd4hip_dslogdet_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* sign, double* logdet) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dslogdet_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dslogdet_batched: negative extent");
-  ND4_CHECK_ARG(M >= N, "det_tri(A): A must be square matrices.");
-  if (batch == 0) return 0;
-  ND4_CHECK_ARG(sign && logdet && (A || M * N == 0), "nd4hip_dslogdet_batched: NULL pointer");
+  ND4_ARGS(nd4_args_det("dslogdet_batched", true, batch, M, N, A, sign, logdet));
   std::vector<Operand> ops{in_op(A, M * N, M * N), out_op(sign, 1), out_op(logdet, 1)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
     return nd4hip_dslogdet_batched_dev(hd, nb, M, N, P(d, 0), P(d, 1), P(d, 2));
@@ -821,9 +718,7 @@ extern "C" int nd4hip_dslogdet_batched(nd4hip_handle* h, int64_t batch, int64_t 
 
 extern "C" int nd4hip_ddettri_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* det) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_ddettri_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_ddettri_batched: negative extent");
-  if (batch == 0) return 0;
-  ND4_CHECK_ARG(det && (A || N == 0), "nd4hip_ddettri_batched: NULL pointer");
+  ND4_ARGS(nd4_args_det("ddettri_batched", false, batch, N, N, A, det, nullptr));
   std::vector<Operand> ops{in_op(A, N * N, N * N), out_op(det, 1)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_ddettri_batched_dev(hd, nb, N, P(d, 0), P(d, 1)); };
   return run_host(h, batch, ops, fn);
@@ -831,9 +726,7 @@ extern "C" int nd4hip_ddettri_batched(nd4hip_handle* h, int64_t batch, int64_t N
 
 extern "C" int nd4hip_dslogdettri_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* sign, double* logdet) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dslogdettri_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dslogdettri_batched: negative extent");
-  if (batch == 0) return 0;
-  ND4_CHECK_ARG(sign && logdet && (A || N == 0), "nd4hip_dslogdettri_batched: NULL pointer");
+  ND4_ARGS(nd4_args_det("dslogdettri_batched", true, batch, N, N, A, sign, logdet));
   std::vector<Operand> ops{in_op(A, N * N, N * N), out_op(sign, 1), out_op(logdet, 1)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
     return nd4hip_dslogdettri_batched_dev(hd, nb, N, P(d, 0), P(d, 1), P(d, 2));
@@ -843,8 +736,7 @@ extern "C" int nd4hip_dslogdettri_batched(nd4hip_handle* h, int64_t batch, int64
 
 extern "C" int nd4hip_dnrmfro(nd4hip_handle* h, int64_t n, const double* A, double* out) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dnrmfro: NULL handle");
-  ND4_CHECK_ARG(n >= 0, "nd4hip_dnrmfro: negative extent");
-  ND4_CHECK_ARG(out && (A || n == 0), "nd4hip_dnrmfro: NULL pointer");
+  ND4_ARGS(nd4_args_nrmfro(n, A, out));
   if (n == 0) { *out = 0.0; return 0; }
   std::vector<Operand> ops{in_op(A, n, n), out_op(out, 1)};     // one "matrix" of n elements
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t, void* const* d) { return nd4hip_dnrmfro_dev(hd, n, P(d, 0), P(d, 1)); };
@@ -855,9 +747,7 @@ extern "C" int nd4hip_dnrmfro(nd4hip_handle* h, int64_t n, const double* A, doub
 // the _dev forms read the device flags back and return the reference's message; run_host hands the first failing chunk's code on
 extern "C" int nd4hip_dtreval_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* T, double* Lam) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dtreval_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dtreval_batched: extent out of range");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(T && Lam, "nd4hip_dtreval_batched: NULL pointer");
+  ND4_ARGS(nd4_args_ev("dtreval_batched", EV_MAX_N, batch, N, {T, Lam}));
   std::vector<Operand> ops{in_op(T, N * N, N * N), out_op(Lam, 2 * N)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_dtreval_batched_dev(hd, nb, N, P(d, 0), P(d, 1)); };
   return run_host(h, batch, ops, fn);
@@ -865,9 +755,7 @@ extern "C" int nd4hip_dtreval_batched(nd4hip_handle* h, int64_t batch, int64_t N
 
 extern "C" int nd4hip_dtrevc_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* Q, const double* T, double* Lam, double* V) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dtrevc_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dtrevc_batched: extent out of range");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(Q && T && Lam && V, "nd4hip_dtrevc_batched: NULL pointer");
+  ND4_ARGS(nd4_args_ev("dtrevc_batched", EV_MAX_N, batch, N, {Q, T, Lam, V}));
   std::vector<Operand> ops{in_op(Q, N * N, N * N), in_op(T, N * N, N * N), out_op(Lam, 2 * N), out_op(V, 2 * N * N)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
     return nd4hip_dtrevc_batched_dev(hd, nb, N, P(d, 0), P(d, 1), P(d, 2), P(d, 3));
@@ -877,10 +765,7 @@ extern "C" int nd4hip_dtrevc_batched(nd4hip_handle* h, int64_t batch, int64_t N,
 
 extern "C" int nd4hip_dgebal_batched(nd4hip_handle* h, int64_t batch, int64_t N, double p, const double* A, double* D, double* B) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgebal_batched: NULL handle");
-  ND4_CHECK_ARG(p >= 1.0, "nd4hip_dgebal_batched: p must be >= 1");
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dgebal_batched: extent out of range");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && D && B, "nd4hip_dgebal_batched: NULL pointer");
+  ND4_ARGS(nd4_args_gebal(batch, N, p, A, D, B));
   std::vector<Operand> ops{in_op(A, N * N, N * N), out_op(D, N), out_op(B, N * N)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_dgebal_batched_dev(hd, nb, N, p, P(d, 0), P(d, 1), P(d, 2)); };
   return run_host(h, batch, ops, fn);
@@ -888,9 +773,7 @@ extern "C" int nd4hip_dgebal_batched(nd4hip_handle* h, int64_t batch, int64_t N,
 
 extern "C" int nd4hip_zgebak_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* Dv, const double* V, double* W) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_zgebak_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_zgebak_batched: extent out of range");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(Dv && V && W, "nd4hip_zgebak_batched: NULL pointer");
+  ND4_ARGS(nd4_args_gebak(false, batch, N, Dv, V, W));
   std::vector<Operand> ops{in_op(Dv, N, N), in_op(V, 2 * N * N, 2 * N * N), out_op(W, 2 * N * N)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_zgebak_batched_dev(hd, nb, N, P(d, 0), P(d, 1), P(d, 2)); };
   return run_host(h, batch, ops, fn);
@@ -911,9 +794,7 @@ extern "C" int nd4hip_dhseqr_batched_ex(nd4hip_handle* h, int64_t batch, int64_t
                                         int* sweeps_out, int tier) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dhseqr_batched: NULL handle");
   if (sweeps_out) *sweeps_out = 0;
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dhseqr_batched: extent out of range");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(U && H && Q && T, "nd4hip_dhseqr_batched: NULL pointer");
+  ND4_ARGS(nd4_args_hseqr(batch, N, U, H, Q, T, tier));
   SweepMax sweeps(h);
   std::vector<Operand> ops{in_op(U, N * N, N * N), in_op(H, N * N, N * N), out_op(Q, N * N), out_op(T, N * N)};
   ChunkFn fn = [&, N, tier](nd4hip_handle* hd, int dev, int64_t nb, void* const* d) {
@@ -934,9 +815,7 @@ extern "C" int nd4hip_dhseqr_batched(nd4hip_handle* h, int64_t batch, int64_t N,
 extern "C" int nd4hip_dgees_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* Q, double* T, int* sweeps_out) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgees_batched: NULL handle");
   if (sweeps_out) *sweeps_out = 0;
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dgees_batched: extent out of range");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && Q && T, "nd4hip_dgees_batched: NULL pointer");
+  ND4_ARGS(nd4_args_ev("dgees_batched", INT64_MAX, batch, N, {A, Q, T}));
   SweepMax sweeps(h);
   std::vector<Operand> ops{in_op(A, N * N, N * N), out_op(Q, N * N), out_op(T, N * N)};
   ChunkFn fn = [&, N](nd4hip_handle* hd, int dev, int64_t nb, void* const* d) {
@@ -952,9 +831,7 @@ extern "C" int nd4hip_dgees_batched(nd4hip_handle* h, int64_t batch, int64_t N, 
 
 extern "C" int nd4hip_dgeev_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* Lam, double* V) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgeev_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dgeev_batched: extent out of range");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && Lam, "nd4hip_dgeev_batched: NULL pointer");
+  ND4_ARGS(nd4_args_ev("dgeev_batched", INT64_MAX, batch, N, {A, Lam}));
   std::vector<Operand> ops{in_op(A, N * N, N * N), out_op(Lam, 2 * N)};
   if (V) ops.push_back(out_op(V, 2 * N * N));
   const bool vecs = V != nullptr;
@@ -968,11 +845,9 @@ extern "C" int nd4hip_dgeev_batched(nd4hip_handle* h, int64_t batch, int64_t N, 
 extern "C" int nd4hip_dgesvdj_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A,
                                       double* U, double* sv, double* V, int* sweeps_out, double* offnorm_out) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgesvdj_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dgesvdj_batched: negative extent");
   if (sweeps_out) *sweeps_out = 0;
   if (offnorm_out) *offnorm_out = 0.0;
-  if (batch == 0 || M == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && U && sv && V, "nd4hip_dgesvdj_batched: NULL pointer");
+  ND4_ARGS(nd4_args_dense("dgesvdj_batched", {batch, M, N}, {A, U, sv, V}));
   const int64_t L = M < N ? M : N;
   const int ndev = 1 + (int)h->peers.size();
   // per-device audit (each device's host thread writes its own slot); reduced on the host afterwards — this is the R1
@@ -1003,9 +878,7 @@ extern "C" int nd4hip_dgesvdj_batched(nd4hip_handle* h, int64_t batch, int64_t M
 // svd_decomp by divide & conquer and the bidiagonal solver (svd_dc.hip)
 extern "C" int nd4hip_dgesdd_batched(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* U, double* sv, double* V) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dgesdd_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dgesdd_batched: negative extent");
-  if (batch == 0 || M == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && U && sv && V, "nd4hip_dgesdd_batched: NULL pointer");
+  ND4_ARGS(nd4_args_dense("dgesdd_batched", {batch, M, N}, {A, U, sv, V}));
   const int64_t L = M < N ? M : N;
   std::vector<Operand> ops{in_op(A, M * N, M * N), out_op(U, M * L), out_op(sv, L), out_op(V, L * N)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_dgesdd_batched_dev(hd, nb, M, N, P(d, 0), P(d, 1), P(d, 2), P(d, 3)); };
@@ -1014,44 +887,35 @@ extern "C" int nd4hip_dgesdd_batched(nd4hip_handle* h, int64_t batch, int64_t M,
 extern "C" int nd4hip_dbdsdc_batched(nd4hip_handle* h, int64_t batch, int64_t K, int64_t J, const double* d, const double* e,
                                      double* U2, double* sv, double* V2) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dbdsdc_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && K >= 0, "nd4hip_dbdsdc_batched: negative extent");
-  ND4_CHECK_ARG(J == K || J == K + 1, "nd4hip_dbdsdc_batched: B must be K x K or K x (K+1)");
-  if (batch == 0 || K == 0) return 0;
-  ND4_CHECK_ARG(d && (e || J < 2) && U2 && sv && V2, "nd4hip_dbdsdc_batched: NULL pointer");
-  if (J < 2) {                                    // 1 x 1: there is no super-diagonal to move
-    std::vector<Operand> ops{in_op(d, K, K), out_op(U2, K * K), out_op(sv, K), out_op(V2, J * J)};
-    ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) { return nd4hip_dbdsdc_batched_dev(hd, nb, K, J, P(p, 0), nullptr, P(p, 1), P(p, 2), P(p, 3)); };
-    return run_host(h, batch, ops, fn);
-  }
-  std::vector<Operand> ops{in_op(d, K, K), in_op(e, J - 1, J - 1), out_op(U2, K * K), out_op(sv, K), out_op(V2, J * J)};
-  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) { return nd4hip_dbdsdc_batched_dev(hd, nb, K, J, P(p, 0), P(p, 1), P(p, 2), P(p, 3), P(p, 4)); };
+  ND4_ARGS(nd4_args_bdsdc(batch, K, J, d, e, U2, sv, V2));
+  // the operands in the order d, U2, sv, V2, [e]; 1 x 1: there is no super-diagonal to move
+  std::vector<Operand> ops{in_op(d, K, K), out_op(U2, K * K), out_op(sv, K), out_op(V2, J * J)};
+  const int ie = J >= 2 ? (int)ops.size() : -1;
+  if (J >= 2) ops.push_back(in_op(e, J - 1, J - 1));
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return nd4hip_dbdsdc_batched_dev(hd, nb, K, J, P(p, 0), ie >= 0 ? P(p, ie) : nullptr, P(p, 1), P(p, 2), P(p, 3));
+  };
   return run_host(h, batch, ops, fn);
 }
 
 // eigen_sym / eigenvals_sym (syev.hip); V = NULL: the values alone
 extern "C" int nd4hip_dsyevd_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dsyevd_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsyevd_batched: negative extent");
-  ND4_CHECK_ARG(N <= 2048, "nd4hip_dsyevd_batched: the divide & conquer solver takes N <= 2048");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(S && lambda, "nd4hip_dsyevd_batched: NULL pointer");
-  if (!V) {
-    std::vector<Operand> ops{in_op(S, N * N, N * N), out_op(lambda, N)};
-    ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_dsyevd_batched_dev(hd, nb, N, P(d, 0), P(d, 1), nullptr); };
-    return run_host(h, batch, ops, fn);
-  }
-  std::vector<Operand> ops{in_op(S, N * N, N * N), out_op(lambda, N), out_op(V, N * N)};
-  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_dsyevd_batched_dev(hd, nb, N, P(d, 0), P(d, 1), P(d, 2)); };
+  ND4_ARGS(nd4_args_syev("dsyevd_batched", false, batch, N, S, lambda));
+  // the operands that are wanted, in the order S, lambda, [V]
+  std::vector<Operand> ops{in_op(S, N * N, N * N), out_op(lambda, N)};
+  const int iv = V ? (int)ops.size() : -1;
+  if (V) ops.push_back(out_op(V, N * N));
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
+    return nd4hip_dsyevd_batched_dev(hd, nb, N, P(d, 0), P(d, 1), iv >= 0 ? P(d, iv) : nullptr);
+  };
   return run_host(h, batch, ops, fn);
 }
 
 // the same with algo = 'jacobi' (syevj.hip); V = NULL: the values alone; sweeps = NULL: not wanted
 extern "C" int nd4hip_dsyevj_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V, int32_t* sweeps) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dsyevj_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsyevj_batched: negative extent");
-  ND4_CHECK_ARG(N <= 128, "nd4hip_dsyevj_batched: the Jacobi route takes N <= 128");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(S && lambda, "nd4hip_dsyevj_batched: NULL pointer");
+  ND4_ARGS(nd4_args_syev("dsyevj_batched", true, batch, N, S, lambda));
   // the operands that are wanted, in the order S, lambda, [V], [sweeps]
   std::vector<Operand> ops{in_op(S, N * N, N * N), out_op(lambda, N)};
   const int iv = V ? (int)ops.size() : -1;
@@ -1068,14 +932,8 @@ extern "C" int nd4hip_dsyevj_batched(nd4hip_handle* h, int64_t batch, int64_t N,
 // once per device
 extern "C" int nd4hip_dsygvd_batched(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B, int64_t strideB,
                                      double* lambda, double* X, int32_t* sweeps) {
-  ND4_CHECK_ARG(algo == 0 || algo == 1, "nd4hip_dsygvd_batched: algo must be 0 (dc) or 1 (jacobi)");
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsygvd_batched: negative extent");
-  ND4_CHECK_ARG(algo == 1 || N <= 2048, "nd4hip_dsygvd_batched: the divide & conquer solver takes N <= 2048");
-  ND4_CHECK_ARG(algo == 0 || N <= 128, "nd4hip_dsygvd_batched: the Jacobi route takes N <= 128");
-  ND4_CHECK_ARG(strideB == 0 || strideB == N * N, "nd4hip_dsygvd_batched: strideB must be N*N or 0");
+  ND4_ARGS(nd4_args_sygvd(algo, batch, N, A, B, strideB, lambda));
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dsygvd_batched: NULL handle");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && B && lambda, "nd4hip_dsygvd_batched: NULL pointer");
   if (algo == 0) sweeps = nullptr;
   // the operands that are wanted, in the order A, B, lambda, [X], [sweeps]
   std::vector<Operand> ops{in_op(A, N * N, N * N), in_op(B, N * N, strideB), out_op(lambda, N)};
@@ -1091,12 +949,8 @@ extern "C" int nd4hip_dsygvd_batched(nd4hip_handle* h, int algo, int64_t batch, 
 }
 
 extern "C" int nd4hip_dsygst_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, const double* L, int64_t strideL, double* C) {
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsygst_batched: negative extent");
-  ND4_CHECK_ARG(N <= 2048, "nd4hip_dsygst_batched: N <= 2048");
-  ND4_CHECK_ARG(strideL == 0 || strideL == N * N, "nd4hip_dsygst_batched: strideL must be N*N or 0");
+  ND4_ARGS(nd4_args_sygst(batch, N, A, L, strideL, C));
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dsygst_batched: NULL handle");
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && L && C, "nd4hip_dsygst_batched: NULL pointer");
   std::vector<Operand> ops{in_op(A, N * N, N * N), in_op(L, N * N, strideL), out_op(C, N * N)};
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_dsygst_batched_dev(hd, nb, N, P(d, 0), P(d, 1), strideL, P(d, 2)); };
   return run_host(h, batch, ops, fn);

@@ -11,7 +11,7 @@
 // atomicMax in LDS (a work item that holds whole members, M N <= STRUCT_STAGE) or in the handle's workspace (members cut into
 // row blocks, maps beyond STRUCT_LDS_MAP): the reference's "a later i overwrites an earlier one",
 // without racing stores. An index outside [0, L) raises a flag word and is never turned into an address.
-#include "nd4hip_internal.h"
+#include "nd4hip_args.h"
 #include <algorithm>
 
 namespace {
@@ -290,11 +290,9 @@ bool nd4_struct_overlap(const void* in, int64_t in_elems, const void* out, int64
 
 extern "C" int nd4hip_dtranspose_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* B) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dtranspose_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dtranspose_batched: negative extent");
+  ND4_ARGS(nd4_args_dense("dtranspose_batched", {batch, M, N}, {A, B}));
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "dtranspose_batched", 0.0, 16.0 * (double)batch * (double)M * (double)N);
-  if (batch == 0 || M == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && B, "nd4hip_dtranspose_batched: NULL pointer");
   ND4_CHECK_ARG(!nd4_struct_overlap(A, batch * M * N, B, batch * M * N), "nd4hip_dtranspose_batched: B must not overlap A");
   const u64* a = reinterpret_cast<const u64*>(A);
   u64* b = reinterpret_cast<u64*>(B);
@@ -315,11 +313,9 @@ extern "C" int nd4hip_dtranspose_batched_dev(nd4hip_handle* h, int64_t batch, in
 
 extern "C" int nd4hip_dtri_batched_dev(nd4hip_handle* h, int upper, int64_t k, int64_t batch, int64_t M, int64_t N, const double* A, double* B) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dtri_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dtri_batched: negative extent");
+  ND4_ARGS(nd4_args_dense("dtri_batched", {batch, M, N}, {A, B}));
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "dtri_batched", 0.0, 16.0 * (double)batch * (double)M * (double)N);
-  if (batch == 0 || M == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && B, "nd4hip_dtri_batched: NULL pointer");
   ND4_CHECK_ARG(!nd4_struct_overlap(A, batch * M * N, B, batch * M * N), "nd4hip_dtri_batched: B must not overlap A");
   // j - i lies in [-(M-1), N-1]: every k <= -M behaves like -M and every k >= N like N, and j - k cannot overflow
   const int64_t kc = k < -M ? -M : (k > N ? N : k);
@@ -336,14 +332,10 @@ extern "C" int nd4hip_dtri_batched_dev(nd4hip_handle* h, int upper, int64_t k, i
 
 extern "C" int nd4hip_ddiag_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t offset, const double* A, double* d) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_ddiag_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_ddiag_batched: negative extent");
-  ND4_CHECK_ARG(offset > -M && offset < N, "nd4hip_ddiag_batched: offset=%lld out of the shape [%lld,%lld]", (long long)offset, (long long)M,
-                (long long)N);
-  const int64_t L = std::min(std::min(M, M + offset), std::min(N, N - offset));
+  ND4_ARGS(nd4_args_diag(batch, M, N, offset, A, d));
+  const int64_t L = nd4_diag_length(M, N, offset);
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "ddiag_batched", 0.0, 16.0 * (double)batch * (double)L);
-  if (batch == 0 || L <= 0) return 0;
-  ND4_CHECK_ARG(A && d, "nd4hip_ddiag_batched: NULL pointer");
   ND4_CHECK_ARG(!nd4_struct_overlap(A, batch * M * N, d, batch * L), "nd4hip_ddiag_batched: d must not overlap A");
   const int64_t total = batch * L, a_off = offset >= 0 ? offset : -offset * N;
   hipLaunchKernelGGL(diag_kernel, dim3(grid_for(h, (total + 255) / 256)), dim3(256), 0, h->stream, total, L, M * N, N, a_off,
@@ -354,11 +346,9 @@ extern "C" int nd4hip_ddiag_batched_dev(nd4hip_handle* h, int64_t batch, int64_t
 
 extern "C" int nd4hip_ddiagmat_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* d, double* Dm) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_ddiagmat_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_ddiagmat_batched: negative extent");
+  ND4_ARGS(nd4_args_dense("ddiagmat_batched", {batch, N}, {d, Dm}));
   Nd4DeviceGuard guard(h);
   Nd4Prof prof(h, "ddiagmat_batched", 0.0, 8.0 * (double)batch * ((double)N + (double)N * (double)N));
-  if (batch == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(d && Dm, "nd4hip_ddiagmat_batched: NULL pointer");
   ND4_CHECK_ARG(!nd4_struct_overlap(d, batch * N, Dm, batch * N * N), "nd4hip_ddiagmat_batched: D must not overlap d");
   const int64_t total = batch * N * N;
   if (N % 2 == 0 && aligned16(Dm))
@@ -375,14 +365,9 @@ extern "C" int nd4hip_dpermute_batched_dev(nd4hip_handle* h, int cols, int inver
                                            int64_t strideA, const int32_t* P, int64_t strideP, double* B) {
   const char* name = nd4_permute_name(cols, inverse);
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dpermute_batched: NULL handle");
-  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dpermute_batched: negative extent");
+  ND4_ARGS(nd4_args_permute(cols, batch, M, N, A, strideA, P, strideP, B));
   const int64_t L = cols ? N : M;
-  ND4_CHECK_ARG(M <= INT32_MAX && N <= INT32_MAX, "nd4hip_dpermute_batched: M and N must fit int32 (P is int32)");
-  ND4_CHECK_ARG((strideA == 0 || strideA >= M * N) && (strideP == 0 || strideP >= L),
-                "nd4hip_dpermute_batched: a stride must be 0 or at least the size of one operand");
   Nd4DeviceGuard guard(h);
-  if (batch == 0 || M == 0 || N == 0) return 0;
-  ND4_CHECK_ARG(A && P && B, "nd4hip_dpermute_batched: NULL pointer");
   ND4_CHECK_ARG(!nd4_struct_overlap(A, (strideA ? (batch - 1) * strideA : 0) + M * N, B, batch * M * N),
                 "nd4hip_dpermute_batched: B must not overlap A");
   ND4_CHECK_ARG(!overlaps(P, (size_t)((strideP ? (batch - 1) * strideP : 0) + L) * 4, B, (size_t)(batch * M * N) * 8),
