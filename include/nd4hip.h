@@ -596,6 +596,44 @@ int nd4hip_dsyevd_last_stages(nd4hip_handle* h, double* ms, int capacity);
 int nd4hip_dsyevj_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V, int32_t* sweeps);
 int nd4hip_dsyevj_batched    (nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V, int32_t* sweeps);
 
+/* ---- selected eigenpairs: eigen_sym(S, subset), tridiag_eigen(d, e, subset), tridiag_count(d, e, x) (csrc/syevx.hip) ----
+ * The host-pointer forms of these three end in _host (not the bare name of every other pair): on purpose, see DESIGN.md 4.20.
+ * T = tridiag(d [batch,N], e [batch,N-1]) symmetric tridiagonal; the subset (i0, i1), 0 <= i0 <= i1 <= N, selects lambda[i0:i1] of
+ * the DESCENDING spectrum, k = i1 - i0 values. 1 <= N <= 2048 (d and e^2 of a member are staged in LDS); N = 0, an empty batch
+ * and an empty subset have nothing to do and write nothing. Each member is scaled by the exact power of two that puts
+ * max(|d|, |e|) in [0.5, 1): 2^m T gives 2^m lambda, the same counts and bit-identical vectors while entries stay normal.
+ *   dstcnt: count [batch,M] (int32) = the number of eigenvalues of T greater than x [batch,M]: N minus the negative terms of the
+ *           Sturm sequence q_0 = d_0 - x, q_i = (d_i - x) - e_i-1^2 / q_i-1, |q| < 2^-1022 replaced by -2^-1022. A probe exactly on
+ *           an eigenvalue of a diagonal T does not count that eigenvalue. Enqueues only (the _dev form); members with NaN or Inf in
+ *           d or e are counted as the identity. NaN in x is the caller's to refuse.
+ *   dstevx: lambda [batch,k] by bisection on that count from the Gershgorin interval until hi - lo <= 2 eps max(|lo|,|hi|) + eps g
+ *           (g the Gershgorin bound), at most 128 halvings: absolute error a few eps g per value. Z [batch,k,N] (may be NULL: the
+ *           values alone, the same bits): row j is the unit eigenvector of lambda[j], by three rounds of inverse iteration with
+ *           the start vector u(seed, (i0 + j) N + i) and Gram-Schmidt applied twice inside clusters (gaps <= 1e-3 g); its first
+ *           component of largest magnitude is positive. A diagonal member: its d by descending rank, ties by index, and the unit
+ *           vectors. NaN or Inf in d or e: ND4HIP_ERR_NOCONV, 'tridiag_eigen(d,e): d or e contains NaN or Infinity.'
+ *   dsyevx: the same for the lower triangle of S [batch,N,N] (the contract of dsyevd: upper triangle never read, S never written):
+ *           steps 1-2 of dsyevd, dstevx on diag(H), subdiag(H), V [batch,N,k] = U Z^T with the eigenvectors as columns (V = NULL:
+ *           values alone, the same bits, no inverse iteration). NaN or Inf in the lower triangle: ND4HIP_ERR_NOCONV with dsyevd's
+ *           message. A diagonal S returns lambda[i0:i1] and V[:, i0:i1] of dsyevd bit for bit.
+ * Bounds as dsyevd's (1e-12 norm-wise); vectors whose eigenvalues are just more than 1e-3 g apart are orthogonal to about
+ * eps / 1e-3 only. A member's results do not depend on the batch or on the run. dstevx and dsyevx synchronise (one flag word is
+ * read back). Profile ops "dstcnt_batched", "dstevx_batched", "dsyevx_batched" (10/3 N^3 + 2 N^2 k flops with V). */
+int nd4hip_dstcnt_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, int64_t M, const double* d, const double* e, const double* x,
+                               int32_t* count);
+int nd4hip_dstcnt_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t M, const double* d, const double* e, const double* x,
+                               int32_t* count);
+int nd4hip_dstevx_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* d, const double* e,
+                               double* lambda, double* Z);
+int nd4hip_dstevx_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* d, const double* e,
+                               double* lambda, double* Z);
+int nd4hip_dsyevx_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* S, double* lambda, double* V);
+int nd4hip_dsyevx_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* S, double* lambda, double* V);
+/* HIP-event time per stage of the LAST dsyevx / dstevx call (one chunk) made on this handle while nd4hip_profile_enable was on, in
+ * ms: symmetrise and scale, tridiagonal reduction (both 0 for dstevx), bisection, inverse iteration, the vectors' GEMM. */
+#define ND4HIP_SYEVX_STAGES 5
+int nd4hip_dsyevx_last_stages(nd4hip_handle* h, double* ms, int capacity);
+
 /* ---- eigen_sym_gen / eigenvals_sym_gen: A x = lambda B x, A symmetric, B symmetric positive definite (csrc/sygv.hip) ----
  * A [batch,N,N]; B [batch,N,N] (strideB = N*N) or ONE B [N,N] for every member (strideB = 0; it is factorised once per call of the
  * _dev form, once per staged chunk of the host form, never once per member). Only the lower triangles of A and B are read and

@@ -154,6 +154,13 @@ SIGNATURES = {
     "nd4hip_dsyevd_last_stages": (c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), c_int]),
     "nd4hip_dsyevj_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp, ctypes.c_void_p]),
     "nd4hip_dsyevj_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp, ctypes.c_void_p]),
+    "nd4hip_dstcnt_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, ctypes.c_void_p]),
+    "nd4hip_dstcnt_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, ctypes.c_void_p]),
+    "nd4hip_dstevx_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp]),
+    "nd4hip_dstevx_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp]),
+    "nd4hip_dsyevx_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_dsyevx_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_dsyevx_last_stages": (c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), c_int]),
     "nd4hip_dsygvd_batched_dev": (c_int, [ctypes.c_void_p, c_int, c_i64, c_i64, c_dp, c_dp, c_i64, c_dp, c_dp, ctypes.c_void_p]),
     "nd4hip_dsygvd_batched": (c_int, [ctypes.c_void_p, c_int, c_i64, c_i64, c_dp, c_dp, c_i64, c_dp, c_dp, ctypes.c_void_p]),
     "nd4hip_dsygst_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_i64, c_dp]),
@@ -278,6 +285,16 @@ class Handle:
         if n < 0:
             check(n)
         return dict(zip(self.EIGSYM_STAGES, ms))
+
+    EIGSYM_SUBSET_STAGES = ("symm", "reduce", "bisect", "invit", "gemm")
+
+    def eigsym_subset_last_stages(self):
+        """ms per stage of the last eigen_sym(S, subset) / tridiag_eigen made with the profile enabled (nd4hip_dsyevx_last_stages)"""
+        ms = (ctypes.c_double * len(self.EIGSYM_SUBSET_STAGES))()
+        n = self.lib.nd4hip_dsyevx_last_stages(self._h, ms, len(self.EIGSYM_SUBSET_STAGES))
+        if n < 0:
+            check(n)
+        return dict(zip(self.EIGSYM_SUBSET_STAGES, ms))
 
     def close(self):
         if self._h:

@@ -707,6 +707,47 @@ extern "C" int nd4hip_dsyevj_batched_dev(nd4hip_handle* h, int64_t batch, int64_
   return 0;
 }
 
+// ---- selected eigenpairs by bisection and inverse iteration (syevx.hip). The argument checks come first: they need no handle.
+// Algorithmic flops: a Sturm count is 3 N; a bisection takes about 55 of them per value; an inverse iteration is 13 N per vector and
+// round; dsyevx: 10/3 N^3 for the reduction with U and 2 N^2 k for V = U Z^T
+extern "C" int nd4hip_dstcnt_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, int64_t M, const double* d, const double* e, const double* x,
+                                         int32_t* count) {
+  ND4_ARGS(nd4_args_stcnt(batch, N, M, d, e, x, count));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dstcnt_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "dstcnt_batched", 3.0 * batch * (double)N * M, 8.0 * batch * (double)(2 * N + M) + 4.0 * batch * (double)M);
+  const int64_t ne = N > 1 ? N - 1 : 0;
+  ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_stcnt(h, nb, N, M, d + b0 * N, e ? e + b0 * ne : nullptr, x + b0 * M, count + b0 * M));
+  return 0;
+}
+extern "C" int nd4hip_dstevx_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* d, const double* e,
+                                         double* lambda, double* Z) {
+  ND4_ARGS(nd4_args_stevx(batch, N, i0, i1, d, e, lambda));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dstevx_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  const int64_t k = i1 - i0, ne = N > 1 ? N - 1 : 0;
+  Nd4Prof prof(h, "dstevx_batched", batch * (double)k * N * (165.0 + (Z ? 39.0 : 0.0)), 8.0 * batch * (double)(2 * N + k + (Z ? k * N : 0)));
+  ND4_FOR_CHUNKS(batch)
+    ND4_TRY(nd4_stevx(h, nb, N, i0, i1, d + b0 * N, e ? e + b0 * ne : nullptr, lambda + b0 * k, Z ? Z + b0 * k * N : nullptr));
+  return 0;
+}
+extern "C" int nd4hip_dsyevx_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* S, double* lambda,
+                                         double* V) {
+  ND4_ARGS(nd4_args_syevx(batch, N, i0, i1, S, lambda));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dsyevx_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  const int64_t k = i1 - i0;
+  const double n2 = (double)N * N;
+  Nd4Prof prof(h, "dsyevx_batched", batch * (10.0 / 3.0 * n2 * N + (V ? 2.0 * n2 * k : 0.0)), 8.0 * batch * (double)(N * N / 2 + k + (V ? N * k : 0)));
+  ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_syevx(h, nb, N, i0, i1, S + b0 * N * N, lambda + b0 * k, V ? V + b0 * N * k : nullptr));
+  return 0;
+}
+extern "C" int nd4hip_dsyevx_last_stages(nd4hip_handle* h, double* ms, int capacity) {
+  ND4_CHECK_ARG(h != nullptr && (ms != nullptr || capacity <= 0), "nd4hip_dsyevx_last_stages: NULL argument");
+  for (int i = 0; i < capacity && i < ND4HIP_SYEVX_STAGES; ++i) ms[i] = h->syevx_stage_ms[i];
+  return ND4HIP_SYEVX_STAGES;
+}
+
 // ---- eigen_sym_gen / eigenvals_sym_gen (sygv.hip). Flops: the solver's count above, (1/3 + 2) N^3 for L = chol(B) and the two
 // triangular solves of C = L^-1 A L^-T, N^3 for X = L^-T Y
 int nd4_sygvd_run(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B, int64_t strideB, double* lambda,

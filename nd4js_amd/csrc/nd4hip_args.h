@@ -229,6 +229,28 @@ inline int nd4_args_syev(const char* op, bool jacobi, int64_t batch, int64_t N, 
   ND4_CHECK_ARG(S && lambda, "nd4hip_%s: NULL pointer", op);
   return ND4_ARGS_GO;
 }
+// ---- selected eigenpairs by bisection and inverse iteration (syevx.hip): the vectors (Z, V) are optional, e is not read for N = 1
+inline int nd4_args_stcnt(int64_t batch, int64_t N, int64_t M, const void* d, const void* e, const void* x, const void* count) {
+  ND4_CHECK_ARG(batch >= 0 && N >= 0 && M >= 0, "nd4hip_dstcnt_batched: negative extent");
+  ND4_CHECK_ARG(N <= 2048, "nd4hip_dstcnt_batched: N <= 2048");
+  if (batch == 0 || N == 0 || M == 0) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(d && (e || N < 2) && x && count, "nd4hip_dstcnt_batched: NULL pointer");
+  return ND4_ARGS_GO;
+}
+inline int nd4_args_subset(const char* op, int64_t batch, int64_t N, int64_t i0, int64_t i1, Nd4Ptrs ptrs) {
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_%s: negative extent", op);
+  ND4_CHECK_ARG(0 <= i0 && i0 <= i1 && i1 <= N, "nd4hip_%s: subset must satisfy 0 <= i0 <= i1 <= N", op);
+  ND4_CHECK_ARG(N <= 2048, "nd4hip_%s: N <= 2048", op);
+  if (batch == 0 || N == 0 || i0 == i1) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(nd4_none_null(ptrs), "nd4hip_%s: NULL pointer", op);
+  return ND4_ARGS_GO;
+}
+inline int nd4_args_stevx(int64_t batch, int64_t N, int64_t i0, int64_t i1, const void* d, const void* e, const void* lambda) {
+  return nd4_args_subset("dstevx_batched", batch, N, i0, i1, {d, e || N < 2 ? d : nullptr, lambda});
+}
+inline int nd4_args_syevx(int64_t batch, int64_t N, int64_t i0, int64_t i1, const void* S, const void* lambda) {
+  return nd4_args_subset("dsyevx_batched", batch, N, i0, i1, {S, lambda});
+}
 inline int nd4_args_sygvd(int algo, int64_t batch, int64_t N, const void* A, const void* B, int64_t strideB, const void* lambda) {
   ND4_CHECK_ARG(algo == 0 || algo == 1, "nd4hip_dsygvd_batched: algo must be 0 (dc) or 1 (jacobi)");
   ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsygvd_batched: negative extent");

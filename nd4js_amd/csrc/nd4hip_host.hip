@@ -928,6 +928,51 @@ extern "C" int nd4hip_dsyevj_batched(nd4hip_handle* h, int64_t batch, int64_t N,
   return run_host(h, batch, ops, fn);
 }
 
+// selected eigenpairs by bisection and inverse iteration (syevx.hip); Z, V = NULL: the values alone; e is not moved for N = 1
+extern "C" int nd4hip_dstcnt_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t M, const double* d, const double* e, const double* x,
+                                          int32_t* count) {
+  ND4_ARGS(nd4_args_stcnt(batch, N, M, d, e, x, count));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dstcnt_batched: NULL handle");
+  // the operands in the order d, x, count, [e]
+  std::vector<Operand> ops{in_op(d, N, N), in_op(x, M, M), out_op(count, M, 4)};
+  const int ie = N >= 2 ? (int)ops.size() : -1;
+  if (N >= 2) ops.push_back(in_op(e, N - 1, N - 1));
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return nd4hip_dstcnt_batched_dev(hd, nb, N, M, P(p, 0), ie >= 0 ? P(p, ie) : nullptr, P(p, 1), static_cast<int32_t*>(p[2]));
+  };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_dstevx_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* d, const double* e,
+                                          double* lambda, double* Z) {
+  ND4_ARGS(nd4_args_stevx(batch, N, i0, i1, d, e, lambda));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dstevx_batched: NULL handle");
+  const int64_t k = i1 - i0;
+  // the operands in the order d, lambda, [e], [Z]
+  std::vector<Operand> ops{in_op(d, N, N), out_op(lambda, k)};
+  const int ie = N >= 2 ? (int)ops.size() : -1;
+  if (N >= 2) ops.push_back(in_op(e, N - 1, N - 1));
+  const int iz = Z ? (int)ops.size() : -1;
+  if (Z) ops.push_back(out_op(Z, k * N));
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return nd4hip_dstevx_batched_dev(hd, nb, N, i0, i1, P(p, 0), ie >= 0 ? P(p, ie) : nullptr, P(p, 1), iz >= 0 ? P(p, iz) : nullptr);
+  };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_dsyevx_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* S, double* lambda,
+                                          double* V) {
+  ND4_ARGS(nd4_args_syevx(batch, N, i0, i1, S, lambda));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dsyevx_batched: NULL handle");
+  const int64_t k = i1 - i0;
+  // the operands that are wanted, in the order S, lambda, [V]
+  std::vector<Operand> ops{in_op(S, N * N, N * N), out_op(lambda, k)};
+  const int iv = V ? (int)ops.size() : -1;
+  if (V) ops.push_back(out_op(V, N * k));
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return nd4hip_dsyevx_batched_dev(hd, nb, N, i0, i1, P(p, 0), P(p, 1), iv >= 0 ? P(p, iv) : nullptr);
+  };
+  return run_host(h, batch, ops, fn);
+}
+
 // eigen_sym_gen / eigenvals_sym_gen (sygv.hip); X = NULL: the values alone; sweeps = NULL: not wanted; strideB = 0: one B, uploaded
 // once per device
 extern "C" int nd4hip_dsygvd_batched(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B, int64_t strideB,

@@ -35,6 +35,7 @@ struct nd4hip_handle {
   hipEvent_t ev_p0 = nullptr, ev_p1 = nullptr; double prof_flops = 0.0, prof_bytes = 0.0; char prof_op[32] = "";
   double dc_stage_ms[ND4HIP_DC_STAGES] = {0};   // per-stage times of the last divide & conquer SVD run with the profile enabled
   double syev_stage_ms[ND4HIP_SYEV_STAGES] = {0};   // the same for the last symmetric eigenproblem (syev.hip)
+  double syevx_stage_ms[ND4HIP_SYEVX_STAGES] = {0}; // and for the last one by bisection and inverse iteration (syevx.hip)
 };
 
 // Makes h->device the calling thread's current HIP device for the duration of an entry point and restores the previous
@@ -178,6 +179,12 @@ int nd4_gesdd(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const doubl
 int nd4_syevd(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V);
 // the same by two-sided Jacobi in one launch (syevj.hip): 1 <= N <= 128; sweeps [batch] may be NULL; synchronises
 int nd4_syevj(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V, int32_t* sweeps);
+// selected eigenpairs by bisection and inverse iteration (syevx.hip): arguments already checked, batch in 1 .. 32768, 1 <= N <= 2048,
+// 0 <= i0 < i1 <= N, k = i1 - i0. count [batch, M]; lambda [batch, k]; Z [batch, k, N] rows = vectors, V [batch, N, k] columns =
+// vectors, either may be NULL. nd4_stevx and nd4_syevx synchronise, nd4_stcnt enqueues only
+int nd4_stcnt(nd4hip_handle* h, int64_t batch, int64_t N, int64_t M, const double* d, const double* e, const double* x, int32_t* count);
+int nd4_stevx(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* d, const double* e, double* lambda, double* Z);
+int nd4_syevx(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* S, double* lambda, double* V);
 // generalised symmetric-definite eigenproblem (sygv.hip): arguments already checked, batch >= 1, 1 <= N; sB / sL 0 = one for all;
 // member0: index of the first member in the caller's batch (error text); nd4_sygvd synchronises
 int nd4_sygvd(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B, int64_t sB, double* lambda,

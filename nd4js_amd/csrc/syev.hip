@@ -23,27 +23,14 @@
 //      the unit vectors in that order for the rows of V2); V = U V2^T on the fp64 MFMA GEMM.
 // The subtraction in 5 cancels: the error of lambda is absolute, a few eps g <= a few eps sqrt(3) ||S||_F, for every eigenvalue,
 // small ones included. That is the bound of any backward stable symmetric solver, not more.
-#include "nd4hip_internal.h"
-#include <cfloat>
+#include "syev_internal.h"
 #include <climits>
-#include <cmath>
 
 namespace {
 
-typedef unsigned long long u64;
-
 constexpr int SYEV_TILE = 64;
 constexpr int SYEV_MAXN = 2048;            // the divide & conquer solver's limit; d and e of one member are staged in 32 KB of LDS
-constexpr u64 SYEV_MAX_BITS = 0x7FEFFFFFFFFFFFFFull;   // the bits of DBL_MAX: those of Inf and of every |NaN| lie above
 constexpr int SYEV_DIAG = INT_MIN;         // kexp of a member whose tridiagonal form is diagonal (e = 0): lambda = d, sorted
-
-// e1 of a member from the bits of max|s_ij| (0 for a zero or non-finite member: those are left alone)
-__device__ __forceinline__ int syev_exp(u64 bits) {
-  const double m = __longlong_as_double((long long)bits);
-  int e = 0;
-  if (m > 0.0 && m <= DBL_MAX) (void)frexp(m, &e);
-  return e;
-}
 
 // mx[b] = bits of max |S[b, i, j]| over j <= i (the bit pattern of |x| orders like |x|; NaN sorts above Inf). grid (rows, batch)
 __global__ __launch_bounds__(256) void syev_absmax_lower(const double* __restrict__ S, int N, u64* __restrict__ mx) {
@@ -200,6 +187,15 @@ struct SyevStamps {
 
 }  // namespace
 
+// step 1, shared with syevx.hip (syev_internal.h)
+int nd4_syev_symm(nd4hip_handle* h, int64_t batch, int N, const double* S, double* W, u64* mx) {
+  const unsigned tiles = (unsigned)((N + SYEV_TILE - 1) / SYEV_TILE);
+  hipLaunchKernelGGL(syev_absmax_lower, dim3((unsigned)(N < 256 ? N : 256), (unsigned)batch), dim3(256), 0, h->stream, S, N, mx);
+  hipLaunchKernelGGL(syev_symm, dim3(tiles, tiles, (unsigned)batch), dim3(256), 0, h->stream, S, W, N, mx);
+  ND4_HIP(hipGetLastError());
+  return 0;
+}
+
 // S [batch, N, N] -> lambda [batch, N] descending, V [batch, N, N] (columns = eigenvectors) or V = NULL for the values alone.
 // batch <= 32768 (the grids' z axis), 1 <= N <= 2048. Synchronises: the solver reads its flag word back, then this call its own.
 int nd4_syevd(nd4hip_handle* h, int64_t batch, int64_t N64, const double* S, double* lambda, double* V) {
@@ -225,10 +221,7 @@ int nd4_syevd(nd4hip_handle* h, int64_t batch, int64_t N64, const double* S, dou
   ND4_HIP(hipMemsetAsync(flag, 0, sizeof(int), h->stream));
   SyevStamps st(h);
   st.mark();
-  const unsigned tiles = (unsigned)((N + SYEV_TILE - 1) / SYEV_TILE);
-  hipLaunchKernelGGL(syev_absmax_lower, dim3((unsigned)(N < 256 ? N : 256), (unsigned)batch), dim3(256), 0, h->stream, S, N, mx);
-  hipLaunchKernelGGL(syev_symm, dim3(tiles, tiles, (unsigned)batch), dim3(256), 0, h->stream, S, W, N, mx);
-  ND4_HIP(hipGetLastError());
+  ND4_TRY(nd4_syev_symm(h, batch, N, S, W, mx));
   st.mark();
   ND4_TRY(nd4_gehrd(h, batch, N, W, U, W));                   // in place: H overwrites W
   st.mark();

@@ -1,0 +1,457 @@
+// Selected eigenpairs of symmetric tridiagonal and dense symmetric matrices: eigen_sym(S, subset=(i0, i1)), tridiag_eigen(d, e),
+// tridiag_count(d, e, x). Bisection on Sturm counts for the values, inverse iteration for the vectors (LAPACK's
+// dstebz + dstein, restated for one lane per eigenvalue and one lane per eigenvector). Every recurrence is serial in N and
+// independent of every other, so k of them run side by side; no workgroup waits for another, there is no spin loop and no atomic
+// apart from raising the call's flag word, and every loop has a bound computed from N, k or a constant.
+//   1. stx_prepare, one wave per member: the finite check (the identity's d, e for a bad member and the flag raised, as
+//      syev_shift_chol does), the exact scale 2^-m with m the frexp exponent of max(|d|, |e|), so that the scaled entries lie in
+//      (-1, 1); g = max_i((|d_i| + |e_i-1|) + |e_i|) >= rho(T) of the scaled member; e^2; the mark of a diagonal member (e = 0).
+//      pivmin is 2^-1022 for every member: the scaled e^2 are below 1.
+//   2. stx_count: #{lambda > x} = N - #{i: q_i < 0}, q_0 = d_0 - x, q_i = (d_i - x) - e^2_i-1 / q_i-1, |q| < pivmin replaced by
+//      -pivmin; one lane per (member, x), d and e^2 of the member in LDS (every lane reads the same word at each step).
+//   3. stx_bisect: lambda_j, j the index in the descending spectrum, is the least x with #{lambda > x} <= j: bisection from
+//      [-g', g'], g' = g (1 + 2^-20), until hi - lo <= 2 eps max(|lo|, |hi|) + eps g or the midpoint meets an end, at most 128
+//      halvings; lambda = 2^m midpoint. stx_diag gives a diagonal member its d by descending rank (ties by index) and the unit
+//      vectors, exactly as syev_values does.
+//   4. stx_clusters, one lane per member: a cluster starts where the gap to the previous selected value exceeds 1e-3 g; inside a
+//      cluster the shifts are kept 10 eps g apart (dstein's perturbation).
+//   5. stx_factor_solve, one lane per vector: LU of T - shift with partial pivoting (dlagtf's scheme, a pivot below eps g in
+//      magnitude replaced by +-eps g), the forward substitution fused into the elimination, then the back substitution. The
+//      factors and the right-hand side live in a workspace laid out [row][vector]. Start vector u(seed, j N + i) of the project's
+//      counter-based generator, j the index in the full spectrum; before each solve the iterate is scaled to N g eps / max|z|.
+//   6. stx_orth, grid (k, batch): the workgroup of a cluster head walks its cluster: vector j is orthogonalised against the
+//      cluster's earlier vectors by Gram-Schmidt applied twice, normalised and, in the last round, given the sign that makes its
+//      first component of largest magnitude positive. Reductions have a fixed order: results are the same bits run to run.
+//   Steps 5 and 6 run three times. 7 (dsyevx): steps 1-2 of syev.hip, then V = U Z^T on the fp64 MFMA GEMM.
+// Arithmetic of 1-4 is + - * / and comparisons, each rounded once (the file is compiled without contraction): the device returns
+// the bits of the numpy model in tests/eigsym_subset_common.py.
+#include "syev_internal.h"
+#include <climits>
+
+namespace {
+
+constexpr int STX_MAXN = 2048;             // d and e^2 of one member are staged in 2 x 16 KB of LDS
+constexpr int STX_MAXIT = 128;
+constexpr double STX_EPS = 0x1p-52;
+constexpr double STX_PIVMIN = 0x1p-1022;
+constexpr unsigned STX_SEED = 20480u;      // of the start vectors
+constexpr int STX_ORTH_THREADS = 512;
+constexpr int STX_STAGES = ND4HIP_SYEVX_STAGES;
+
+__device__ __forceinline__ unsigned stx_fmix32(unsigned x) {
+  x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
+  return x;
+}
+// u(seed, idx) of nd4js_amd/rng.py, s = fmix32(seed)
+__device__ __forceinline__ double stx_uniform(unsigned s, unsigned idx) {
+  const unsigned hi = stx_fmix32(idx ^ s);
+  const unsigned lo = stx_fmix32(hi + 0x9E3779B9u + idx);
+  const double m = (double)(hi >> 5) * 67108864.0 + (double)(lo >> 6);
+  return m * 0x1p-52 - 1.0;
+}
+
+// d (elements dinc apart, members dstride apart) and e (likewise; NULL for N = 1) -> ds, es, e2 [batch, N] (es, e2 [N-1] = 0),
+// g [batch], lexp [batch] = m + e1 (e1 from mx, 0 without), diag [batch]. mx (may be NULL): syev_absmax_lower's word of the member.
+__global__ __launch_bounds__(64) void stx_prepare(const double* __restrict__ d, long dinc, long dstride, const double* __restrict__ e, long einc,
+                                                  long estride, int N, const u64* __restrict__ mx, double* __restrict__ ds,
+                                                  double* __restrict__ es, double* __restrict__ e2, double* __restrict__ g,
+                                                  int* __restrict__ lexp, int* __restrict__ diag, int* __restrict__ flag) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const double* dm = d + (size_t)b * dstride;
+  const double* em = N > 1 ? e + (size_t)b * estride : nullptr;
+  double* dsb = ds + (size_t)b * N; double* esb = es + (size_t)b * N; double* e2b = e2 + (size_t)b * N;
+  u64 m = 0;
+  for (int i = lane; i < N; i += 64) {
+    u64 w = (u64)__double_as_longlong(fabs(dm[(size_t)i * dinc]));
+    m = w > m ? w : m;
+    if (i + 1 < N) { w = (u64)__double_as_longlong(fabs(em[(size_t)i * einc])); m = w > m ? w : m; }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) { const u64 o = __shfl_xor(m, off); m = o > m ? o : m; }
+  if (m > SYEV_MAX_BITS || (mx && mx[b] > SYEV_MAX_BITS)) {   // NaN or Inf: the identity stands in
+    for (int i = lane; i < N; i += 64) { dsb[i] = 1.0; esb[i] = 0.0; e2b[i] = 0.0; }
+    if (lane == 0) { g[b] = 1.0; lexp[b] = 0; diag[b] = 1; atomicMax(flag, 1); }
+    return;
+  }
+  int mm = 0;
+  const double mv = __longlong_as_double((long long)m);
+  if (mv > 0.0) (void)frexp(mv, &mm);
+  double gg = 0.0; int offdiag = 0;
+  for (int i = lane; i < N; i += 64) {
+    const double di = ldexp(dm[(size_t)i * dinc], -mm);
+    const double ei = i + 1 < N ? ldexp(em[(size_t)i * einc], -mm) : 0.0;
+    const double ep = i > 0 ? ldexp(em[(size_t)(i - 1) * einc], -mm) : 0.0;
+    dsb[i] = di; esb[i] = ei; e2b[i] = ei * ei;
+    offdiag |= ei != 0.0;
+    gg = fmax(gg, (fabs(di) + fabs(ep)) + fabs(ei));
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) { gg = fmax(gg, __shfl_xor(gg, off)); offdiag |= __shfl_xor(offdiag, off); }
+  if (lane == 0) { g[b] = gg; lexp[b] = mm + (mx ? syev_exp(mx[b]) : 0); diag[b] = !offdiag; }
+}
+
+// #{i: q_i < 0} of the member staged at sd, s2
+__device__ __forceinline__ int stx_negatives(const double* sd, const double* s2, int N, double x) {
+  double q = sd[0] - x;
+  if (fabs(q) < STX_PIVMIN) q = -STX_PIVMIN;
+  int c = q < 0.0;
+  for (int i = 1; i < N; ++i) {
+    q = (sd[i] - x) - s2[i - 1] / q;
+    if (fabs(q) < STX_PIVMIN) q = -STX_PIVMIN;
+    c += q < 0.0;
+  }
+  return c;
+}
+
+// count [batch, M] = #{lambda > x} of the member; grid (ceil(M / 256), batch)
+__global__ __launch_bounds__(256) void stx_count(const double* __restrict__ ds, const double* __restrict__ e2, const int* __restrict__ lexp, int N,
+                                                 long M, const double* __restrict__ x, int* __restrict__ count) {
+  __shared__ double sd[STX_MAXN], s2[STX_MAXN];
+  const int b = blockIdx.y;
+  for (int i = threadIdx.x; i < N; i += 256) { sd[i] = ds[(size_t)b * N + i]; s2[i] = e2[(size_t)b * N + i]; }
+  __syncthreads();
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= M) return;
+  const double xs = ldexp(x[(size_t)b * M + t], -lexp[b]);
+  count[(size_t)b * M + t] = N - stx_negatives(sd, s2, N, xs);
+}
+
+// lams [batch, k] (scaled) and lam [batch, k] = 2^lexp lams for the indices i0 .. i0 + k - 1 of the descending spectrum;
+// grid (ceil(k / 256), batch). A diagonal member is left to stx_diag.
+__global__ __launch_bounds__(256) void stx_bisect(const double* __restrict__ ds, const double* __restrict__ e2, const double* __restrict__ g,
+                                                  const int* __restrict__ lexp, const int* __restrict__ diag, int N, int i0, int k,
+                                                  double* __restrict__ lams, double* __restrict__ lam) {
+  __shared__ double sd[STX_MAXN], s2[STX_MAXN];
+  const int b = blockIdx.y;
+  if (diag[b]) return;                                        // the whole workgroup: nobody waits at the barrier below
+  for (int i = threadIdx.x; i < N; i += 256) { sd[i] = ds[(size_t)b * N + i]; s2[i] = e2[(size_t)b * N + i]; }
+  __syncthreads();
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= k) return;
+  const int j = i0 + t;
+  const double gg = g[b], floor_ = STX_EPS * gg;
+  double hi = gg * (1.0 + 0x1p-20), lo = -hi;
+  for (int it = 0; it < STX_MAXIT; ++it) {
+    const double mid = 0.5 * (lo + hi);
+    if (hi - lo <= (2.0 * STX_EPS) * fmax(fabs(lo), fabs(hi)) + floor_ || mid == lo || mid == hi) break;
+    if (N - stx_negatives(sd, s2, N, mid) > j) lo = mid; else hi = mid;
+  }
+  const double v = 0.5 * (lo + hi);
+  lams[(size_t)b * k + t] = v;
+  lam[(size_t)b * k + t] = ldexp(v, lexp[b]);
+}
+
+// a diagonal member: thread (b, r) writes d_r at its descending rank (ties by index) if that rank is selected, and, where the
+// vectors are wanted (Z != NULL), the unit vector e_r as that row of Z [batch, k, N]
+__global__ __launch_bounds__(256) void stx_diag(const double* __restrict__ ds, const int* __restrict__ lexp, const int* __restrict__ diag, int N,
+                                                long total, int i0, int k, double* __restrict__ lams, double* __restrict__ lam,
+                                                double* __restrict__ Z) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const long b = i / N;
+  if (!diag[b]) return;
+  const int r = (int)(i - b * N);
+  const double* db = ds + (size_t)b * N;
+  const double dr = db[r];
+  int rank = 0;
+  for (int m = 0; m < N; ++m) { const double dm = db[m]; rank += dm > dr || (dm == dr && m < r); }
+  if (rank < i0 || rank >= i0 + k) return;
+  const size_t o = (size_t)b * k + (rank - i0);               // rank - i0 < k
+  lams[o] = dr;
+  lam[o] = ldexp(dr, lexp[b]);
+  if (Z) {
+    double* row = Z + o * N;
+    for (int m = 0; m < N; ++m) row[m] = m == r ? 1.0 : 0.0;
+  }
+}
+
+// head [batch, k]: the index (in the subset) of the first vector of the cluster each vector belongs to; shift [batch, k]: the
+// value, moved where needed so that the shifts of one cluster are at least 10 eps g apart. One lane per member.
+__global__ __launch_bounds__(64) void stx_clusters(const double* __restrict__ lams, const double* __restrict__ g, const int* __restrict__ diag,
+                                                   int batch, int k, int* __restrict__ head, double* __restrict__ shift) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= batch || diag[b]) return;
+  const double* l = lams + (size_t)b * k;
+  int* hd = head + (size_t)b * k;
+  double* sh = shift + (size_t)b * k;
+  const double ctol = 1e-3 * g[b], pert = (10.0 * STX_EPS) * g[b];
+  int cur = 0; double prev = l[0];
+  hd[0] = 0; sh[0] = prev;
+  for (int j = 1; j < k; ++j) {
+    double s = l[j];
+    if (l[j - 1] - s > ctol) cur = j;
+    else if (prev - s < pert) s = prev - pert;
+    hd[j] = cur; sh[j] = s;
+    prev = s;
+  }
+}
+
+__device__ __forceinline__ double stx_guard(double p, double tiny) { return fabs(p) < tiny ? copysign(tiny, p) : p; }
+
+// One lane per (member, vector): (T - shift) x = scale z, z the start vector (round 0) or row j of Z; x overwrites that row.
+// u0, u1, u2, y [batch, N, k]: the rows of U and the eliminated right-hand side.
+__global__ __launch_bounds__(64) void stx_factor_solve(const double* __restrict__ ds, const double* __restrict__ es, const double* __restrict__ g,
+                                                       const int* __restrict__ diag, const double* __restrict__ shift, int N, int i0, int k,
+                                                       long total, int round, double* __restrict__ u0, double* __restrict__ u1,
+                                                       double* __restrict__ u2, double* __restrict__ y, double* __restrict__ Z) {
+  const long t = (long)blockIdx.x * 64 + threadIdx.x;
+  if (t >= total) return;
+  const long b = t / k;
+  if (diag[b]) return;
+  const int jj = (int)(t - b * k);
+  const double* D = ds + (size_t)b * N;
+  const double* E = es + (size_t)b * N;
+  double* z = Z + (size_t)t * N;                               // row jj of member b: t = b k + jj < batch k
+  const size_t w = (size_t)b * N * k + jj;                     // row i of the workspace: w + i k < batch N k
+  const double gg = g[b], tiny = STX_EPS * gg, sigma = shift[t];
+  const unsigned s = stx_fmix32(STX_SEED), base = (unsigned)(i0 + jj) * (unsigned)N;
+  double zmax = 0.0;
+  for (int i = 0; i < N; ++i) zmax = fmax(zmax, fabs(round == 0 ? stx_uniform(s, base + i) : z[i]));
+  const double scale = zmax > 0.0 && zmax <= DBL_MAX ? (((double)N * gg) * STX_EPS) / zmax : 1.0;
+#define STX_SRC(i) ((round == 0 ? stx_uniform(s, base + (i)) : z[i]) * scale)
+  double p = D[0] - sigma, sup = N > 1 ? E[0] : 0.0, yi = STX_SRC(0);
+  for (int i = 0; i + 1 < N; ++i) {
+    const double l = E[i], dd = D[i + 1] - sigma, ee = i + 2 < N ? E[i + 1] : 0.0, zn = STX_SRC(i + 1);
+    const size_t o = w + (size_t)i * k;
+    if (fabs(p) >= fabs(l)) {
+      const double piv = stx_guard(p, tiny), mult = l / piv;
+      u0[o] = piv; u1[o] = sup; u2[o] = 0.0; y[o] = yi;
+      p = dd - mult * sup; sup = ee; yi = zn - mult * yi;
+    } else {                                                   // rows i and i + 1 change places
+      const double piv = stx_guard(l, tiny), mult = p / piv;
+      u0[o] = piv; u1[o] = dd; u2[o] = ee; y[o] = zn;
+      p = sup - mult * dd; sup = -(mult * ee); yi = yi - mult * zn;
+    }
+  }
+#undef STX_SRC
+  double x1 = yi / stx_guard(p, tiny), x2 = 0.0;
+  z[N - 1] = x1;
+  for (int i = N - 2; i >= 0; --i) {
+    const size_t o = w + (size_t)i * k;
+    const double x = ((y[o] - u1[o] * x1) - u2[o] * x2) / u0[o];
+    z[i] = x; x2 = x1; x1 = x;
+  }
+}
+
+// sum over the workgroup in a fixed order: lanes by the xor butterfly, then the waves' sums in wave order
+__device__ __forceinline__ double stx_block_sum(double v, double* part) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  __syncthreads();                                             // part may still be read from the previous call
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+  for (int wv = 0; wv < STX_ORTH_THREADS / 64; ++wv) s += part[wv];
+  return s;
+}
+
+// grid (k, batch), STX_ORTH_THREADS threads: see step 6 in the head of this file. Z [batch, k, N], rows = vectors, in place.
+__global__ __launch_bounds__(STX_ORTH_THREADS) void stx_orth(double* __restrict__ Z, const int* __restrict__ head, const int* __restrict__ diag,
+                                                             int N, int k, int last) {
+  __shared__ double dots[STX_MAXN];
+  __shared__ double part[STX_ORTH_THREADS / 64];
+  __shared__ double pmax[STX_ORTH_THREADS / 64];
+  __shared__ int pidx[STX_ORTH_THREADS / 64];
+  const int jj = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int* hd = head + (size_t)b * k;
+  if (diag[b] || hd[jj] != jj) return;                        // the whole workgroup
+  int c = 1;
+  while (jj + c < k && hd[jj + c] == jj) ++c;                 // at most k - jj steps
+  double* Zc = Z + ((size_t)b * k + jj) * N;                  // the cluster's rows: jj + c <= k
+  for (int v = 0; v < c; ++v) {
+    double* zv = Zc + (size_t)v * N;
+    for (int pass = 0; pass < 2 && v > 0; ++pass) {
+      for (int t = wave; t < v; t += STX_ORTH_THREADS / 64) { // all dots of the pass, one wave each
+        const double* zt = Zc + (size_t)t * N;
+        double s = 0.0;
+        for (int i = lane; i < N; i += 64) s += zt[i] * zv[i];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+        if (lane == 0) dots[t] = s;                           // t < v < c <= k <= STX_MAXN
+      }
+      __syncthreads();
+      for (int i = tid; i < N; i += STX_ORTH_THREADS) {
+        double a = zv[i];
+        for (int t = 0; t < v; ++t) a -= dots[t] * Zc[(size_t)t * N + i];
+        zv[i] = a;
+      }
+      __syncthreads();
+    }
+    double ss = 0.0, am = -1.0; int ai = INT_MAX;
+    for (int i = tid; i < N; i += STX_ORTH_THREADS) {
+      const double a = zv[i];
+      ss += a * a;
+      if (fabs(a) > am) { am = fabs(a); ai = i; }             // ascending i: the first of equal magnitudes stays
+    }
+    const double nrm = sqrt(stx_block_sum(ss, part));
+    double sign = 1.0;
+    if (last) {
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) {
+        const double om = __shfl_xor(am, off); const int oi = __shfl_xor(ai, off);
+        if (om > am || (om == am && oi < ai)) { am = om; ai = oi; }
+      }
+      if (lane == 0) { pmax[wave] = am; pidx[wave] = ai; }
+      __syncthreads();
+      for (int wv = 0; wv < STX_ORTH_THREADS / 64; ++wv)
+        if (pmax[wv] > am || (pmax[wv] == am && pidx[wv] < ai)) { am = pmax[wv]; ai = pidx[wv]; }
+      if (ai < N && zv[ai] < 0.0) sign = -1.0;
+      __syncthreads();                                        // everybody has read zv[ai] before it is rewritten
+    }
+    if (nrm > 0.0 && nrm <= DBL_MAX)
+      for (int i = tid; i < N; i += STX_ORTH_THREADS) zv[i] = sign * (zv[i] / nrm);
+    __syncthreads();                                          // the next vector of the cluster reads this one
+  }
+}
+
+template <class T> int stx_alloc(nd4hip_handle* h, size_t count, T** out) {
+  void* p = nullptr;
+  ND4_TRY(nd4_ws_alloc(h, sizeof(T) * (count ? count : 1), &p));
+  *out = static_cast<T*>(p);
+  return 0;
+}
+
+// HIP-event time per stage while the profile is enabled
+struct StxStamps {
+  nd4hip_handle* h; bool on; int n = 0;
+  hipEvent_t ev[STX_STAGES + 1] = {};
+  explicit StxStamps(nd4hip_handle* hh) : h(hh), on(hh->prof_on) {}
+  void mark() {
+    if (!on || n > STX_STAGES) return;
+    if (hipEventCreate(&ev[n]) != hipSuccess) { on = false; return; }
+    (void)hipEventRecord(ev[n++], h->stream);
+  }
+  void collect() {                                            // after the call's synchronisation
+    for (int i = 0; i < STX_STAGES; ++i) {
+      float ms = 0.f;
+      h->syevx_stage_ms[i] = on && i + 1 < n && hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess ? ms : 0.0;
+    }
+  }
+  ~StxStamps() { for (int i = 0; i < n; ++i) (void)hipEventDestroy(ev[i]); }
+};
+
+struct StxPrepared { double *ds, *es, *e2, *g; int *lexp, *diag, *flag; };
+
+// step 1 into the caller's workspace scope
+int stx_prepare_run(nd4hip_handle* h, int64_t batch, int N, const double* d, long dinc, long dstride, const double* e, long einc, long estride,
+                    const u64* mx, StxPrepared* w) {
+  const size_t bn = (size_t)batch * N;
+  ND4_TRY(stx_alloc(h, bn, &w->ds)); ND4_TRY(stx_alloc(h, bn, &w->es)); ND4_TRY(stx_alloc(h, bn, &w->e2));
+  ND4_TRY(stx_alloc(h, (size_t)batch, &w->g)); ND4_TRY(stx_alloc(h, (size_t)batch, &w->lexp)); ND4_TRY(stx_alloc(h, (size_t)batch, &w->diag));
+  ND4_TRY(stx_alloc(h, 1, &w->flag));
+  ND4_HIP(hipMemsetAsync(w->flag, 0, sizeof(int), h->stream));
+  hipLaunchKernelGGL(stx_prepare, dim3((unsigned)batch), dim3(64), 0, h->stream, d, dinc, dstride, e, einc, estride, N, mx, w->ds, w->es, w->e2,
+                     w->g, w->lexp, w->diag, w->flag);
+  ND4_HIP(hipGetLastError());
+  return 0;
+}
+
+// steps 1-6 for the tridiagonal members given by (d, dinc, dstride), (e, einc, estride): lambda [batch, k], Z [batch, k, N] or NULL.
+// Enqueues only; *flag is the call's flag word for the caller to read back. st: marks after the values and after the vectors.
+int stx_run(nd4hip_handle* h, int64_t batch, int N, int i0, int k, const double* d, long dinc, long dstride, const double* e, long einc,
+            long estride, const u64* mx, double* lambda, double* Z, StxStamps* st, int** flag) {
+  StxPrepared w;
+  ND4_TRY(stx_prepare_run(h, batch, N, d, dinc, dstride, e, einc, estride, mx, &w));
+  *flag = w.flag;
+  const size_t bk = (size_t)batch * k;
+  double* lams = nullptr;
+  ND4_TRY(stx_alloc(h, bk, &lams));
+  const long total = (long)batch * N;
+  hipLaunchKernelGGL(stx_diag, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, w.ds, w.lexp, w.diag, N, total, i0, k, lams, lambda, Z);
+  hipLaunchKernelGGL(stx_bisect, dim3((unsigned)((k + 255) / 256), (unsigned)batch), dim3(256), 0, h->stream, w.ds, w.e2, w.g, w.lexp, w.diag, N, i0,
+                     k, lams, lambda);
+  ND4_HIP(hipGetLastError());
+  st->mark();
+  if (Z) {
+    int* head = nullptr; double *shift, *u0, *u1, *u2, *y;
+    ND4_TRY(stx_alloc(h, bk, &head)); ND4_TRY(stx_alloc(h, bk, &shift));
+    ND4_TRY(stx_alloc(h, bk * N, &u0)); ND4_TRY(stx_alloc(h, bk * N, &u1)); ND4_TRY(stx_alloc(h, bk * N, &u2)); ND4_TRY(stx_alloc(h, bk * N, &y));
+    hipLaunchKernelGGL(stx_clusters, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, h->stream, lams, w.g, w.diag, (int)batch, k, head, shift);
+    for (int round = 0; round < 3; ++round) {
+      hipLaunchKernelGGL(stx_factor_solve, dim3((unsigned)((bk + 63) / 64)), dim3(64), 0, h->stream, w.ds, w.es, w.g, w.diag, shift, N, i0, k,
+                         (long)bk, round, u0, u1, u2, y, Z);
+      hipLaunchKernelGGL(stx_orth, dim3((unsigned)k, (unsigned)batch), dim3(STX_ORTH_THREADS), 0, h->stream, Z, head, w.diag, N, k, round == 2);
+    }
+    ND4_HIP(hipGetLastError());
+  }
+  st->mark();
+  return 0;
+}
+
+int stx_read_flag(nd4hip_handle* h, const int* flag, int* value) {
+  void* hp = nullptr;
+  ND4_TRY(nd4_pinned(h, sizeof(int), &hp));
+  ND4_HIP(hipMemcpyAsync(hp, flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  ND4_HIP(hipStreamSynchronize(h->stream));
+  *value = *static_cast<int*>(hp);
+  return 0;
+}
+
+}  // namespace
+
+// count [batch, M] = #{lambda > x [batch, M]} of tridiag(d [batch, N], e [batch, N-1]); batch <= 32768, 1 <= N <= 2048. Enqueues only.
+int nd4_stcnt(nd4hip_handle* h, int64_t batch, int64_t N64, int64_t M, const double* d, const double* e, const double* x, int32_t* count) {
+  ND4_CHECK_ARG(N64 <= STX_MAXN && batch <= 32768 && M <= (int64_t)INT32_MAX, "nd4hip_dstcnt_batched: extent out of range");
+  const int N = (int)N64;
+  Nd4WsScope scope(h);
+  StxPrepared w;
+  ND4_TRY(stx_prepare_run(h, batch, N, d, 1, N, e, 1, N - 1, nullptr, &w));
+  hipLaunchKernelGGL(stx_count, dim3((unsigned)((M + 255) / 256), (unsigned)batch), dim3(256), 0, h->stream, w.ds, w.e2, w.lexp, N, (long)M, x, count);
+  ND4_HIP(hipGetLastError());
+  return 0;
+}
+
+// lambda [batch, k] = the eigenvalues i0 .. i1 - 1 of the descending spectrum of tridiag(d, e), Z [batch, k, N] (rows = vectors) or
+// NULL; batch <= 32768, 1 <= N <= 2048, 0 <= i0 < i1 <= N. Synchronises.
+int nd4_stevx(nd4hip_handle* h, int64_t batch, int64_t N64, int64_t i0, int64_t i1, const double* d, const double* e, double* lambda, double* Z) {
+  ND4_CHECK_ARG(N64 <= STX_MAXN && batch <= 32768, "nd4hip_dstevx_batched: extent out of range");
+  const int N = (int)N64;
+  Nd4WsScope scope(h);
+  StxStamps st(h);
+  st.mark(); st.mark(); st.mark();                            // no symmetrisation, no reduction
+  int* flag = nullptr; int bad = 0;
+  ND4_TRY(stx_run(h, batch, N, (int)i0, (int)(i1 - i0), d, 1, N, e, 1, N - 1, nullptr, lambda, Z, &st, &flag));
+  st.mark();
+  ND4_TRY(stx_read_flag(h, flag, &bad));
+  st.collect();
+  h->syevx_stage_ms[0] = h->syevx_stage_ms[1] = 0.0;          // (the time between two event records, not a stage)
+  if (bad) {
+    nd4_set_error("tridiag_eigen(d,e): d or e contains NaN or Infinity.");
+    return ND4HIP_ERR_NOCONV;
+  }
+  return 0;
+}
+
+// the same for the lower triangle of S [batch, N, N]: V [batch, N, k] (columns = eigenvectors) or NULL. Synchronises.
+int nd4_syevx(nd4hip_handle* h, int64_t batch, int64_t N64, int64_t i0, int64_t i1, const double* S, double* lambda, double* V) {
+  ND4_CHECK_ARG(N64 <= STX_MAXN && batch <= 32768, "nd4hip_dsyevx_batched: extent out of range");
+  const int N = (int)N64, k = (int)(i1 - i0);
+  Nd4WsScope scope(h);
+  StxStamps st(h);
+  int* flag = nullptr; int bad = 0;
+  st.mark();
+  if (N == 1) {                                               // T = S; Z [batch, 1, 1] is V
+    st.mark(); st.mark();
+    ND4_TRY(stx_run(h, batch, 1, (int)i0, k, S, 1, 1, nullptr, 1, 0, nullptr, lambda, V, &st, &flag));
+  } else {
+    const size_t nn = (size_t)N * N;
+    u64* mx = nullptr; double *W, *U, *Z = nullptr;
+    ND4_TRY(stx_alloc(h, (size_t)batch, &mx)); ND4_TRY(stx_alloc(h, (size_t)batch * nn, &W)); ND4_TRY(stx_alloc(h, (size_t)batch * nn, &U));
+    if (V) ND4_TRY(stx_alloc(h, (size_t)batch * k * N, &Z));
+    ND4_HIP(hipMemsetAsync(mx, 0, sizeof(u64) * (size_t)batch, h->stream));
+    ND4_TRY(nd4_syev_symm(h, batch, N, S, W, mx));
+    st.mark();
+    ND4_TRY(nd4_gehrd(h, batch, N, W, U, W));                 // in place: H overwrites W; d = diag(H), e = subdiag(H)
+    st.mark();
+    ND4_TRY(stx_run(h, batch, N, (int)i0, k, W, N + 1, (long)nn, W + N, N + 1, (long)nn, mx, lambda, Z, &st, &flag));
+    if (V) ND4_TRY(nd4_gemm(h, false, true, N, k, N, 1.0, U, N, (int64_t)nn, Z, N, (int64_t)k * N, 0.0, V, k, (int64_t)N * k, batch));
+  }
+  st.mark();
+  ND4_TRY(stx_read_flag(h, flag, &bad));
+  st.collect();
+  if (bad) {
+    nd4_set_error("eigen_sym(S): S contains NaN or Infinity in its lower triangle.");
+    return ND4HIP_ERR_NOCONV;
+  }
+  return 0;
+}

@@ -751,9 +751,13 @@ def eigenvals(A):
     return L
 
 
-def _syevd(S, what, vectors, algo=None, info=None):
-    from .la import _eigsym_algo
+def _syevd(S, what, vectors, algo=None, info=None, subset=None):
+    from .la import _eigsym_algo, _subset
     jacobi = _eigsym_algo(algo, what)
+    if subset is not None:
+        what = what.replace("(S)", "(S, subset)")
+        if jacobi:
+            _subset(subset, 0, what, True)
     if isinstance(S, torch.Tensor) and S.dtype != torch.float64:
         raise TypeError("%s: S.dtype must be float." % what)
     _chk(S, "S")
@@ -763,6 +767,14 @@ def _syevd(S, what, vectors, algo=None, info=None):
     if S.shape[-2] != N:
         raise ValueError("%s: S must be quadratic." % what)
     lead = tuple(S.shape[:-2])
+    if subset is not None:                                                  # bisection and inverse iteration (csrc/syevx.hip)
+        i0, i1 = _subset(subset, N, what)
+        L = torch.empty(lead + (i1 - i0,), dtype=torch.float64, device=S.device)
+        V = torch.empty(lead + (N, i1 - i0), dtype=torch.float64, device=S.device) if vectors else None
+        if L.numel():
+            h = _h(S)
+            _lib.check(h.lib.nd4hip_dsyevx_batched_dev(h.ptr, _batch(lead), N, i0, i1, _p(S), _p(L), _p(V) if vectors else None))
+        return (L, V) if vectors else L
     L = torch.empty(lead + (N,), dtype=torch.float64, device=S.device)
     V = torch.empty(lead + (N, N), dtype=torch.float64, device=S.device) if vectors else None
     h = _h(S)
@@ -776,16 +788,59 @@ def _syevd(S, what, vectors, algo=None, info=None):
     return (L, V) if vectors else L
 
 
-def eigen_sym(S, algo=None, info=None):
+def eigen_sym(S, algo=None, info=None, subset=None):
     """device-resident la.eigen_sym: (eigenvalues [..., N] descending, eigenvectors [..., N, N] as columns), float64; only the
     lower triangle of S is read and S is not written. algo='jacobi' (N <= 128): the one-launch Jacobi route; `info` then
-    receives 'sweeps', an int32 tensor [...] on the device."""
-    return _syevd(S, "eigen_sym(S)", True, algo, info)
+    receives 'sweeps', an int32 tensor [...] on the device. subset=(i0, i1): L[i0:i1] and the matching columns alone, [..., k] and
+    [..., N, k], by bisection and inverse iteration."""
+    return _syevd(S, "eigen_sym(S)", True, algo, info, subset)
 
 
-def eigenvals_sym(S, algo=None, info=None):
+def eigenvals_sym(S, algo=None, info=None, subset=None):
     """device-resident la.eigenvals_sym: the eigenvalues of eigen_sym alone, the same bits"""
-    return _syevd(S, "eigenvals_sym(S)", False, algo, info)
+    return _syevd(S, "eigenvals_sym(S)", False, algo, info, subset)
+
+
+def _stevx(d, e, subset, what, vectors):
+    from .la import _subset, _tridiag_args
+    _chk(d, "d"), _chk(e, "e")
+    N = _tridiag_args(d, e, what, lambda a: a.dim(), lambda a: a.shape)
+    i0, i1 = _subset((0, N) if subset is None else subset, N, what)
+    lead = tuple(d.shape[:-1])
+    L = torch.empty(lead + (i1 - i0,), dtype=torch.float64, device=d.device)
+    Z = torch.empty(lead + (i1 - i0, N), dtype=torch.float64, device=d.device) if vectors else None
+    if L.numel():
+        h = _h(d)
+        _lib.check(h.lib.nd4hip_dstevx_batched_dev(h.ptr, _batch(lead), N, i0, i1, _p(d), _p(e), _p(L), _p(Z) if vectors else None))
+    return (L, Z.transpose(-1, -2).contiguous()) if vectors else L
+
+
+def tridiag_eigen(d, e, subset=None):
+    """device-resident la.tridiag_eigen: (L [..., k] descending, Z [..., N, k] with the eigenvectors as columns), the same bits"""
+    return _stevx(d, e, subset, "tridiag_eigen(d,e)", True)
+
+
+def tridiag_eigenvals(d, e, subset=None):
+    """device-resident la.tridiag_eigenvals: the eigenvalues of tridiag_eigen alone, the same bits"""
+    return _stevx(d, e, subset, "tridiag_eigenvals(d,e)", False)
+
+
+def tridiag_count(d, e, x):
+    """device-resident la.tridiag_count: int32 [..., M], how many eigenvalues of tridiag(d, e) are greater than each x [..., M].
+    The NaN check of x reads one flag back; the count itself is only enqueued."""
+    from .la import _tridiag_args
+    what = "tridiag_count(d,e,x)"
+    _chk(d, "d"), _chk(e, "e"), _chk(x, "x")
+    N = _tridiag_args(d, e, what, lambda a: a.dim(), lambda a: a.shape)
+    if x.dim() < 1 or tuple(x.shape[:-1]) != tuple(d.shape[:-1]):
+        raise ValueError("%s: x must have the leading dimensions of d." % what)
+    if bool(torch.isnan(x).any()):
+        raise ValueError("%s: x contains NaN." % what)
+    count = torch.empty(tuple(x.shape), dtype=torch.int32, device=x.device)
+    if count.numel():
+        h = _h(d)
+        _lib.check(h.lib.nd4hip_dstcnt_batched_dev(h.ptr, _batch(d.shape[:-1]), N, int(x.shape[-1]), _p(d), _p(e), _p(x), _p(count)))
+    return count
 
 
 def _sygv_chk(A, B, what):

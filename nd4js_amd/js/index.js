@@ -1450,12 +1450,20 @@ function makeLa(NDA, fallback, SolveError, Complex) {
    * only in its lower triangle -> [eigenvalues [..., N] descending, eigenvectors [..., N, N] as columns], resp. the eigenvalues alone.
    * Host arrays or DeviceNDArrays in, the same kind out. Not enumerable, like concat: the reference's nd.la has no such names.
    * opts.algo: undefined / 'dc' (the default route) or 'jacobi' (csrc/syevj.hip, N <= 128: two-sided Jacobi in one launch, small
-   * eigenvalues of a positive definite S to their own relative accuracy). ---- */
+   * eigenvalues of a positive definite S to their own relative accuracy).
+   * opts.subset: [i0, i1], 0 <= i0 < i1 <= N (not with 'jacobi'; an empty subset has no NDArray, whose axes are at least 1 long): the eigenvalues i0 .. i1 - 1 of the descending spectrum alone,
+   * [..., k], and their eigenvectors, [..., N, k], k = i1 - i0, by bisection and inverse iteration (csrc/syevx.hip). ---- */
   const eigSym = (name, vectors) => {
     const f = function (S, opts) {
       const algo = opts == null ? undefined : opts.algo;
       if (algo !== undefined && algo !== null && algo !== 'dc' && algo !== 'jacobi') throw new Error(`${name}(S, {algo}): algo must be 'dc' or 'jacobi'.`);
       const jac = algo === 'jacobi';
+      const subset = opts == null ? undefined : opts.subset;
+      if (subset != null) {
+        if (jac) throw new Error(`${name}(S, {subset}): subset is not available with algo 'jacobi'.`);
+        if (!(Array.isArray(subset) || ArrayBuffer.isView(subset)) || subset.length !== 2)
+          throw new Error(`${name}(S, {subset}): subset must be [i0, i1] with 0 <= i0 <= i1 <= N.`);
+      }
       S = asarray(S);
       if (isComplexDev(S) || String(dtypeOf(S)).startsWith('complex')) throw new TypeError(`${name}(S): S.dtype must be float.`);
       if (S.ndim < 2) throw new Error(`${name}(S): S.ndim must be at least 2.`);
@@ -1463,6 +1471,22 @@ function makeLa(NDA, fallback, SolveError, Complex) {
       if (S.shape[nd_ - 2] != N) throw new Error(`${name}(S): S must be quadratic.`);
       if (!gpuOk(S)) throw new TypeError(`${name}(S): dtype ${dtypeOf(S)} is not accelerated.`);
       const batch = prod(S.shape, 0, nd_ - 2), dev = isDev(S), temps = [];
+      if (subset != null) {                        // bisection and inverse iteration, csrc/syevx.hip
+        const [i0, i1] = subset, k = i1 - i0;
+        if (!(Number.isInteger(i0) && Number.isInteger(i1) && 0 <= i0 && i0 <= i1 && i1 <= N))
+          throw new Error(`${name}(S, {subset}): subset must be [i0, i1] with 0 <= i0 <= i1 <= N, got [${i0}, ${i1}] for N = ${N}.`);
+        if (k === 0) throw new Error(`${name}(S, {subset}): the subset [${i0}, ${i1}] is empty, and an NDArray has no axis of length 0.`);
+        const lead = Array.from(S.shape.subarray(0, nd_ - 2));
+        const Ls = alloc(dev, batch * k), Vs = vectors ? alloc(dev, batch * N * k) : null;
+        try {
+          if (vectors) native().dsyevx_batched(batch, N, i0, i1, view(opF64(S, dev, temps), 0), view(Ls, 0), view(Vs, 0));
+          else native().dsyevxals_batched(batch, N, i0, i1, view(opF64(S, dev, temps), 0), view(Ls, 0));
+        }
+        catch (e) { if (dev) { Ls.free(); if (Vs) Vs.free(); } throw e; }
+        finally { release(temps); }
+        const Lsw = wrap(dev, lead.concat([k]), Ls);
+        return vectors ? [Lsw, wrap(dev, lead.concat([N, k]), Vs)] : Lsw;
+      }
       const L = alloc(dev, batch * N), V = vectors ? alloc(dev, batch * N * N) : null;
       try {
         if (vectors) native()[jac ? 'dsyevj_batched' : 'dsyevd_batched'](batch, N, view(opF64(S, dev, temps), 0), view(L, 0), view(V, 0));

@@ -9,6 +9,8 @@ JS wrapper nd4js_amd/js/index.js over the N-API shim; both call the same libnd4h
   svd_decomp(A)        src/la/svd.js:25             -> nd4hip_dgesvdj_batched; algo='dc' (opt-in): nd4hip_dgesdd_batched
   bidiag_svd(d, e)     src/la/svd_dc.js:169-824     -> nd4hip_dbdsdc_batched
   eigen_sym(S), eigenvals_sym(S)   planned at src/la/eigen.js:28-30   -> nd4hip_dsyevd_batched; algo='jacobi' (opt-in): nd4hip_dsyevj_batched
+                                   subset=(i0, i1) (opt-in): a slice of the descending spectrum -> nd4hip_dsyevx_batched_host
+  tridiag_eigen(d, e), tridiag_eigenvals(d, e), tridiag_count(d, e, x)   not in the reference   -> nd4hip_dstevx_batched_host, nd4hip_dstcnt_batched_host
   eigen_sym_gen(A, B), eigenvals_sym_gen(A, B)   A x = lambda B x, not in the reference   -> nd4hip_dsygvd_batched
 
 Inputs are numpy arrays / nested lists (NDArray analogue: dense, row-major, leading axes = batch).
@@ -1129,8 +1131,27 @@ def _eigsym_algo(algo, what):
     raise ValueError("%s: algo must be None, 'dc' or 'jacobi'." % what.replace("(S)", "(S, algo)"))
 
 
-def _syevd(S, what, vectors, device, algo=None, info=None):
+def _subset(subset, N, what, jacobi=False):
+    """(i0, i1) of subset=(i0, i1), the half-open slice lambda[i0:i1] of the descending spectrum, 0 <= i0 <= i1 <= N"""
+    if jacobi:
+        raise ValueError("%s: subset is not available with algo='jacobi'." % what)
+    try:
+        i0, i1 = subset
+        i0, i1 = int(i0), int(i1)
+        ok = (i0, i1) == tuple(subset)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or not 0 <= i0 <= i1 <= N:
+        raise ValueError("%s: subset must be (i0, i1) with 0 <= i0 <= i1 <= N, got %r for N = %d." % (what, subset, N))
+    return i0, i1
+
+
+def _syevd(S, what, vectors, device, algo=None, info=None, subset=None):
     jacobi = _eigsym_algo(algo, what)
+    if subset is not None:
+        what = what.replace("(S)", "(S, subset)")
+        if jacobi:
+            _subset(subset, 0, what, True)
     S = np.asarray(S)
     if np.iscomplexobj(S):
         raise TypeError("%s: S.dtype must be float." % what)
@@ -1140,10 +1161,18 @@ def _syevd(S, what, vectors, device, algo=None, info=None):
         raise ValueError("%s: S must be quadratic." % what)
     S = _asarray(S, what)
     N = S.shape[-1]
+    batch = int(np.prod(S.shape[:-2], dtype=np.int64))
+    if subset is not None:                                                  # bisection and inverse iteration (csrc/syevx.hip)
+        i0, i1 = _subset(subset, N, what)
+        L = np.empty(S.shape[:-2] + (i1 - i0,))
+        V = np.empty(S.shape[:-1] + (i1 - i0,)) if vectors else None
+        if L.size:
+            h = _lib.handle(device)
+            _lib.check(h.lib.nd4hip_dsyevx_batched_host(h.ptr, batch, N, i0, i1, _ptr(S), _ptr(L), _ptr(V) if vectors else None))
+        return (L, V) if vectors else L
     L = np.empty(S.shape[:-1])
     V = np.empty(S.shape) if vectors else None
     h = _lib.handle(device)
-    batch = int(np.prod(S.shape[:-2], dtype=np.int64))
     if jacobi:
         sweeps = np.zeros(S.shape[:-2], dtype=np.int32)
         _lib.check(h.lib.nd4hip_dsyevj_batched(h.ptr, batch, N, _ptr(S), _ptr(L), _ptr(V) if vectors else None, sweeps.ctypes.data))
@@ -1154,20 +1183,79 @@ def _syevd(S, what, vectors, device, algo=None, info=None):
     return (L, V) if vectors else L
 
 
-def eigen_sym(S, device=None, algo=None, info=None):
+def eigen_sym(S, device=None, algo=None, info=None, subset=None):
     """the function the reference plans at eigen.js:28-30: (eigenvalues float64 [..., N] descending, eigenvectors float64
     [..., N, N] as columns) of the symmetric S, S V = V diag(L) and V^T V = I. Only the lower triangle of S is read. NaN or
     Infinity there raises Nd4HipError with code -3. N <= 2048.
     algo None / 'dc': tridiagonalisation + divide & conquer (the default route). algo 'jacobi' (opt-in, N <= 128): every member by
     cyclic two-sided Jacobi inside one launch; for positive definite S every eigenvalue, however small, is accurate to
-    N eps kappa_2(D^-1 S D^-1) relative to itself, D = diag(sqrt s_ii). `info` (a dict) then receives 'sweeps', int32 [...]."""
-    return _syevd(S, "eigen_sym(S)", True, device, algo, info)
+    N eps kappa_2(D^-1 S D^-1) relative to itself, D = diag(sqrt s_ii). `info` (a dict) then receives 'sweeps', int32 [...].
+    subset=(i0, i1) (opt-in, not with 'jacobi'): only L[i0:i1] of the descending spectrum and the matching columns of V, k = i1 - i0
+    of them: (L [..., k], V [..., N, k]), by bisection and inverse iteration on the tridiagonal form (tridiag_eigen below)."""
+    return _syevd(S, "eigen_sym(S)", True, device, algo, info, subset)
 
 
-def eigenvals_sym(S, device=None, algo=None, info=None):
+def eigenvals_sym(S, device=None, algo=None, info=None, subset=None):
     """the eigenvalues of eigen_sym alone (the same bits); no eigenvector product is computed or stored. With algo='jacobi' no
-    eigenvector is accumulated at all."""
-    return _syevd(S, "eigenvals_sym(S)", False, device, algo, info)
+    eigenvector is accumulated at all; with subset no inverse iteration is made."""
+    return _syevd(S, "eigenvals_sym(S)", False, device, algo, info, subset)
+
+
+def _tridiag_args(d, e, what, ndim, shape):
+    """the argument checks of tridiag_eigen / tridiag_eigenvals / tridiag_count, shared with dev.py; returns N"""
+    if ndim(d) < 1 or ndim(e) < 1 or tuple(shape(d)[:-1]) != tuple(shape(e)[:-1]):
+        raise ValueError("%s: d and e must have the same leading dimensions." % what)
+    N = int(shape(d)[-1])
+    if N < 1 or int(shape(e)[-1]) != N - 1:
+        raise ValueError("%s: e must have len(d) - 1 entries." % what)
+    if N > 2048:
+        raise ValueError("%s: N <= 2048." % what)
+    return N
+
+
+def _stevx(d, e, subset, what, vectors, device):
+    d, e = _asarray(d, what), _asarray(e, what)
+    N = _tridiag_args(d, e, what, lambda a: a.ndim, lambda a: a.shape)
+    i0, i1 = _subset((0, N) if subset is None else subset, N, what)
+    lead = d.shape[:-1]
+    L = np.empty(lead + (i1 - i0,))
+    Z = np.empty(lead + (i1 - i0, N)) if vectors else None
+    if L.size:
+        h = _lib.handle(device)
+        _lib.check(h.lib.nd4hip_dstevx_batched_host(h.ptr, int(np.prod(lead, dtype=np.int64)), N, i0, i1, _ptr(d), _ptr(e), _ptr(L),
+                                                    _ptr(Z) if vectors else None))
+    return (L, np.ascontiguousarray(np.swapaxes(Z, -1, -2))) if vectors else L
+
+
+def tridiag_eigen(d, e, subset=None, device=None):
+    """selected eigenpairs of the symmetric tridiagonal T with diagonal d [..., N] and off-diagonal e [..., N-1], N <= 2048:
+    (L [..., k] descending, Z [..., N, k] with the eigenvectors as columns) for subset=(i0, i1), the slice L[i0:i1] of the descending
+    spectrum (None: all of it). Bisection on Sturm counts, inverse iteration, Gram-Schmidt inside clusters (csrc/syevx.hip). NaN or
+    Infinity in d or e raises Nd4HipError with code -3."""
+    return _stevx(d, e, subset, "tridiag_eigen(d,e)", True, device)
+
+
+def tridiag_eigenvals(d, e, subset=None, device=None):
+    """the eigenvalues of tridiag_eigen alone (the same bits); no inverse iteration is made"""
+    return _stevx(d, e, subset, "tridiag_eigenvals(d,e)", False, device)
+
+
+def tridiag_count(d, e, x, device=None):
+    """int32 [..., M]: how many eigenvalues of tridiag(d [..., N], e [..., N-1]) are greater than each x [..., M] (the Sturm count alone).
+    count(lo) and count(hi) turn the value interval (lo, hi] into subset=(count(hi), count(lo))."""
+    what = "tridiag_count(d,e,x)"
+    d, e, x = _asarray(d, what), _asarray(e, what), _asarray(x, what)
+    N = _tridiag_args(d, e, what, lambda a: a.ndim, lambda a: a.shape)
+    if x.ndim < 1 or x.shape[:-1] != d.shape[:-1]:
+        raise ValueError("%s: x must have the leading dimensions of d." % what)
+    if np.isnan(x).any():
+        raise ValueError("%s: x contains NaN." % what)
+    count = np.empty(x.shape, dtype=np.int32)
+    if count.size:
+        h = _lib.handle(device)
+        _lib.check(h.lib.nd4hip_dstcnt_batched_host(h.ptr, int(np.prod(d.shape[:-1], dtype=np.int64)), N, x.shape[-1], _ptr(d), _ptr(e), _ptr(x),
+                                                    count.ctypes.data))
+    return count
 
 
 def _sygv_args(A, B, what, is_float64, ndim, shape):
