@@ -634,6 +634,35 @@ int nd4hip_dsyevx_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64
 #define ND4HIP_SYEVX_STAGES 5
 int nd4hip_dsyevx_last_stages(nd4hip_handle* h, double* ms, int capacity);
 
+/* ---- tridiag_factor / tridiag_apply_q / tridiag_decomp and eigen_sym(S, reduction='tridiag') (csrc/sytrd.hip) ----
+ * As with the selected eigenpairs above, the host-pointer forms of these four end in _host, not in the bare name.
+ * S [batch,N,N] symmetric, read only in its lower triangle and never written; 1 <= N <= 2048; N = 0 and an empty batch have nothing
+ * to do and write nothing.
+ *   dsytrd: S = Q tridiag(d, e) Q^T, Q = H_0 H_1 ... H_{N-3}, H_k = I - tau_k v_k v_k^T with v_k zero in rows 0..k, 1 in row k+1 and its
+ *           tail in F[k+2:, k] (LAPACK's dsytrd, lower, on row-major members). F [batch,N,N] carries d on its diagonal, e on its first
+ *           subdiagonal and zeros above the diagonal; tau [batch,N-1] with tau[N-2] = 0; d [batch,N]; e [batch,N-1] (tau and e may be
+ *           NULL for N = 1). e_k = -sign(alpha) |x| for the column x = [alpha; tail] (sign(0) = +1); a column whose tail is zero gets
+ *           tau_k = 0, e_k = alpha. Each member is scaled by the exact power of two that puts max|s_ij| in [0.5, 1): 2^m S gives the
+ *           same tails, tau and Q bit for bit and 2^m d, 2^m e. NaN or Inf in a lower triangle: ND4HIP_ERR_NOCONV,
+ *           'tridiag_decomp(S): S contains NaN or Infinity in its lower triangle.'; the outputs are then unspecified.
+ *   dormtr: Z [batch,N,K] <- Q Z (transpose = 1: Q^T Z) in place; Q is never formed. Enqueues only (the _dev form).
+ *   dsyevd_tr, dsyevx_tr: dsyevd and dsyevx (their argument lists, contracts, bounds and error text) with dsytrd in place of the
+ *           symmetrised copy and the Hessenberg reduction and dormtr in place of the product with U; V = NULL runs neither Q nor dormtr.
+ * No sum depends on the run, the batch or a member's position, up to the GEMM's choice of a split inner dimension for N > 512 in
+ * dormtr. dsytrd and the two eigen routes synchronise (one flag word). Profile ops "dsytrd_batched" (4/3 N^3), "dormtr_batched"
+ * (2 N^2 K), "dsyevd_tr_batched", "dsyevx_tr_batched"; the stage times of the last two are read with nd4hip_dsyevd_last_stages and
+ * nd4hip_dsyevx_last_stages (the symmetrise stage is 0). */
+int nd4hip_dsytrd_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* F, double* tau, double* d, double* e);
+int nd4hip_dsytrd_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* F, double* tau, double* d, double* e);
+int nd4hip_dormtr_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, int transpose, const double* F, const double* tau,
+                               double* Z);
+int nd4hip_dormtr_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, int transpose, const double* F, const double* tau,
+                               double* Z);
+int nd4hip_dsyevd_tr_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V);
+int nd4hip_dsyevd_tr_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V);
+int nd4hip_dsyevx_tr_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* S, double* lambda, double* V);
+int nd4hip_dsyevx_tr_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* S, double* lambda, double* V);
+
 /* ---- eigen_sym_gen / eigenvals_sym_gen: A x = lambda B x, A symmetric, B symmetric positive definite (csrc/sygv.hip) ----
  * A [batch,N,N]; B [batch,N,N] (strideB = N*N) or ONE B [N,N] for every member (strideB = 0; it is factorised once per call of the
  * _dev form, once per staged chunk of the host form, never once per member). Only the lower triangles of A and B are read and

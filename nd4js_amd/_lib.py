@@ -161,6 +161,14 @@ SIGNATURES = {
     "nd4hip_dsyevx_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
     "nd4hip_dsyevx_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
     "nd4hip_dsyevx_last_stages": (c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), c_int]),
+    "nd4hip_dsytrd_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "nd4hip_dormtr_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_int, c_dp, c_dp, c_dp]),
+    "nd4hip_dsyevd_tr_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_dsyevx_tr_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_dsytrd_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "nd4hip_dormtr_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_int, c_dp, c_dp, c_dp]),
+    "nd4hip_dsyevd_tr_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_dsyevx_tr_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
     "nd4hip_dsygvd_batched_dev": (c_int, [ctypes.c_void_p, c_int, c_i64, c_i64, c_dp, c_dp, c_i64, c_dp, c_dp, ctypes.c_void_p]),
     "nd4hip_dsygvd_batched": (c_int, [ctypes.c_void_p, c_int, c_i64, c_i64, c_dp, c_dp, c_i64, c_dp, c_dp, ctypes.c_void_p]),
     "nd4hip_dsygst_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_i64, c_dp]),

@@ -76,6 +76,8 @@ static int (*p_dgeev[2])(nd4hip_handle*, int64_t, int64_t, const double*, double
 static int (*p_dsyevd[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*, double*);
 static int (*p_dsyevj[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*, double*, int32_t*);
 static int (*p_dsyevx[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, const double*, double*, double*);
+static int (*p_dsyevd_tr[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*, double*);
+static int (*p_dsyevx_tr[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, const double*, double*, double*);
 static int (*p_dsygvd[2])(nd4hip_handle*, int, int64_t, int64_t, const double*, const double*, int64_t, double*, double*, int32_t*);
 static int (*p_dqp3rank[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, int32_t*);
 static int (*p_dqp3ls[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t,
@@ -178,6 +180,8 @@ static int load_library(void) {
   SYM2(p_dsyevd, "nd4hip_dsyevd_batched");
   SYM2(p_dsyevj, "nd4hip_dsyevj_batched");
   SYM(p_dsyevx[0], "nd4hip_dsyevx_batched_host"); SYM(p_dsyevx[1], "nd4hip_dsyevx_batched_dev");   /* this pair's host form ends in _host */
+  SYM(p_dsyevd_tr[0], "nd4hip_dsyevd_tr_batched_host"); SYM(p_dsyevd_tr[1], "nd4hip_dsyevd_tr_batched_dev");   /* and so do these two */
+  SYM(p_dsyevx_tr[0], "nd4hip_dsyevx_tr_batched_host"); SYM(p_dsyevx_tr[1], "nd4hip_dsyevx_tr_batched_dev");
   SYM2(p_dsygvd, "nd4hip_dsygvd_batched");
   SYM2(p_dqp3rank, "nd4hip_dqp3rank_batched");
   SYM2(p_dsrrqr, "nd4hip_dsrrqr_batched");
@@ -791,6 +795,52 @@ static napi_value js_dsyevxals(napi_env env, napi_callback_info info) {
   FAIL_IF(p_dsyevx[S.dev](g_handle, batch, N, i0, i1, (const double*)S.p, (double*)L.p, NULL));
   return NULL;
 }
+/* dsyevd_tr_batched / dsyevdals_tr_batched / dsyevx_tr_batched / dsyevxals_tr_batched: the four calls above with {reduction:
+ * 'tridiag'} (csrc/sytrd.hip), the same argument lists */
+static napi_value js_dsyevd_tr(napi_env env, napi_callback_info info) {
+  ARGS(5, "dsyevd_tr_batched");
+  int64_t batch, N; opnd S, L, V;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || F64(2, S) || F64(3, L) || F64(4, V)) return NULL;
+  NEED(batch >= 0 && N >= 0 && (size_t)(batch * N * N) <= S.len && (size_t)(batch * N) <= L.len && (size_t)(batch * N * N) <= V.len,
+       "dsyevd_tr_batched: buffer too small");
+  SAME_SIDE(S.dev == L.dev && L.dev == V.dev, "dsyevd_tr_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dsyevd_tr[S.dev](g_handle, batch, N, (const double*)S.p, (double*)L.p, (double*)V.p));
+  return NULL;
+}
+static napi_value js_dsyevdals_tr(napi_env env, napi_callback_info info) {
+  ARGS(4, "dsyevdals_tr_batched");
+  int64_t batch, N; opnd S, L;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || F64(2, S) || F64(3, L)) return NULL;
+  NEED(batch >= 0 && N >= 0 && (size_t)(batch * N * N) <= S.len && (size_t)(batch * N) <= L.len, "dsyevdals_tr_batched: buffer too small");
+  SAME_SIDE(S.dev == L.dev, "dsyevdals_tr_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dsyevd_tr[S.dev](g_handle, batch, N, (const double*)S.p, (double*)L.p, NULL));
+  return NULL;
+}
+static napi_value js_dsyevx_tr(napi_env env, napi_callback_info info) {
+  ARGS(7, "dsyevx_tr_batched");
+  int64_t batch, N, i0, i1; opnd S, L, V;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || get_i64(env, a[2], &i0) || get_i64(env, a[3], &i1) || F64(4, S) || F64(5, L) ||
+      F64(6, V)) return NULL;
+  NEED(batch >= 0 && N >= 0 && 0 <= i0 && i0 <= i1 && i1 <= N && (size_t)(batch * N * N) <= S.len && (size_t)(batch * (i1 - i0)) <= L.len &&
+       (size_t)(batch * N * (i1 - i0)) <= V.len, "dsyevx_tr_batched: bad subset or buffer too small");
+  SAME_SIDE(S.dev == L.dev && L.dev == V.dev, "dsyevx_tr_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dsyevx_tr[S.dev](g_handle, batch, N, i0, i1, (const double*)S.p, (double*)L.p, (double*)V.p));
+  return NULL;
+}
+static napi_value js_dsyevxals_tr(napi_env env, napi_callback_info info) {
+  ARGS(6, "dsyevxals_tr_batched");
+  int64_t batch, N, i0, i1; opnd S, L;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || get_i64(env, a[2], &i0) || get_i64(env, a[3], &i1) || F64(4, S) || F64(5, L)) return NULL;
+  NEED(batch >= 0 && N >= 0 && 0 <= i0 && i0 <= i1 && i1 <= N && (size_t)(batch * N * N) <= S.len && (size_t)(batch * (i1 - i0)) <= L.len,
+       "dsyevxals_tr_batched: bad subset or buffer too small");
+  SAME_SIDE(S.dev == L.dev, "dsyevxals_tr_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dsyevx_tr[S.dev](g_handle, batch, N, i0, i1, (const double*)S.p, (double*)L.p, NULL));
+  return NULL;
+}
 /* dsygvd_batched(algo, batch, N, A, B, strideB, L, X) / dsygvals_batched(algo, batch, N, A, B, strideB, L)   (eigen_sym_gen /
  * eigenvals_sym_gen: A x = lambda B x; algo 0 dc, 1 jacobi; strideB N*N or 0 = one B; the sweep counts are not asked for) */
 static napi_value js_dsygvd(napi_env env, napi_callback_info info) {
@@ -1241,6 +1291,10 @@ static napi_value init(napi_env env, napi_value exports) {
     {"dsyevjals_batched", NULL, js_dsyevjals, NULL, NULL, NULL, napi_default, NULL},
     {"dsyevx_batched", NULL, js_dsyevx, NULL, NULL, NULL, napi_default, NULL},
     {"dsyevxals_batched", NULL, js_dsyevxals, NULL, NULL, NULL, napi_default, NULL},
+    {"dsyevd_tr_batched", NULL, js_dsyevd_tr, NULL, NULL, NULL, napi_default, NULL},
+    {"dsyevdals_tr_batched", NULL, js_dsyevdals_tr, NULL, NULL, NULL, napi_default, NULL},
+    {"dsyevx_tr_batched", NULL, js_dsyevx_tr, NULL, NULL, NULL, napi_default, NULL},
+    {"dsyevxals_tr_batched", NULL, js_dsyevxals_tr, NULL, NULL, NULL, napi_default, NULL},
     {"dsygvd_batched", NULL, js_dsygvd, NULL, NULL, NULL, napi_default, NULL},
     {"dsygvals_batched", NULL, js_dsygvals, NULL, NULL, NULL, napi_default, NULL},
     {"dqp3rank_batched", NULL, js_dqp3rank, NULL, NULL, NULL, napi_default, NULL},

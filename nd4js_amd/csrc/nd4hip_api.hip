@@ -748,6 +748,50 @@ extern "C" int nd4hip_dsyevx_last_stages(nd4hip_handle* h, double* ms, int capac
   return ND4HIP_SYEVX_STAGES;
 }
 
+// ---- symmetric tridiagonal reduction, its Q and the eigen routes on them (sytrd.hip). The argument checks come
+// first: they need no handle. Flops: 4/3 N^3 for the reduction, 2 N^2 K for Q Z; the eigen routes add the solver's 2 N^3 (dsyevd)
+extern "C" int nd4hip_dsytrd_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* F, double* tau, double* d, double* e) {
+  ND4_ARGS(nd4_args_sytrd(batch, N, S, F, tau, d, e));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dsytrd_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  const double n2 = (double)N * N;
+  Nd4Prof prof(h, "dsytrd_batched", batch * (4.0 / 3.0 * n2 * N), 8.0 * batch * (double)(N * N / 2 + N * N + 3 * N));
+  const int64_t ne = N > 1 ? N - 1 : 0;
+  ND4_FOR_CHUNKS(batch)
+    ND4_TRY(nd4_sytrd_run(h, nb, N, S + b0 * N * N, F + b0 * N * N, tau ? tau + b0 * ne : nullptr, d + b0 * N, e ? e + b0 * ne : nullptr));
+  return 0;
+}
+extern "C" int nd4hip_dormtr_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, int transpose, const double* F,
+                                         const double* tau, double* Z) {
+  ND4_ARGS(nd4_args_ormtr(batch, N, K, transpose, F, tau, Z));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dormtr_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "dormtr_batched", batch * (2.0 * N * (double)N * K), 8.0 * batch * (double)(N * N / 2 + 2 * N * K));
+  const int64_t ne = N > 1 ? N - 1 : 0;
+  ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_ormtr(h, nb, N, K, transpose != 0, F + b0 * N * N, tau ? tau + b0 * ne : nullptr, Z + b0 * N * K));
+  return 0;
+}
+extern "C" int nd4hip_dsyevd_tr_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V) {
+  ND4_ARGS(nd4_args_syevd_tr(batch, N, S, lambda));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dsyevd_tr_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  const double n3 = (double)N * N * N;
+  Nd4Prof prof(h, "dsyevd_tr_batched", batch * ((4.0 / 3.0 + 2.0 + (V ? 2.0 : 0.0)) * n3), 8.0 * batch * (double)(N * N / 2 + N + (V ? N * N : 0)));
+  ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_syevd_tr(h, nb, N, S + b0 * N * N, lambda + b0 * N, V ? V + b0 * N * N : nullptr));
+  return 0;
+}
+extern "C" int nd4hip_dsyevx_tr_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* S, double* lambda,
+                                            double* V) {
+  ND4_ARGS(nd4_args_syevx_tr(batch, N, i0, i1, S, lambda));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dsyevx_tr_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  const int64_t k = i1 - i0;
+  const double n2 = (double)N * N;
+  Nd4Prof prof(h, "dsyevx_tr_batched", batch * (4.0 / 3.0 * n2 * N + (V ? 2.0 * n2 * k : 0.0)), 8.0 * batch * (double)(N * N / 2 + k + (V ? N * k : 0)));
+  ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_syevx_tr(h, nb, N, i0, i1, S + b0 * N * N, lambda + b0 * k, V ? V + b0 * N * k : nullptr));
+  return 0;
+}
+
 // ---- eigen_sym_gen / eigenvals_sym_gen (sygv.hip). Flops: the solver's count above, (1/3 + 2) N^3 for L = chol(B) and the two
 // triangular solves of C = L^-1 A L^-T, N^3 for X = L^-T Y
 int nd4_sygvd_run(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B, int64_t strideB, double* lambda,

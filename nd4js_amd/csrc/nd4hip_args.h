@@ -251,6 +251,32 @@ inline int nd4_args_stevx(int64_t batch, int64_t N, int64_t i0, int64_t i1, cons
 inline int nd4_args_syevx(int64_t batch, int64_t N, int64_t i0, int64_t i1, const void* S, const void* lambda) {
   return nd4_args_subset("dsyevx_batched", batch, N, i0, i1, {S, lambda});
 }
+// ---- symmetric tridiagonal reduction, its Q, and the eigen routes on it (sytrd.hip): tau and e have no entry for N = 1; V is optional
+inline int nd4_args_sytrd(int64_t batch, int64_t N, const void* S, const void* F, const void* tau, const void* d, const void* e) {
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsytrd_batched: negative extent");
+  ND4_CHECK_ARG(N <= 2048, "nd4hip_dsytrd_batched: N <= 2048");
+  if (batch == 0 || N == 0) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(S && F && d && ((tau && e) || N < 2), "nd4hip_dsytrd_batched: NULL pointer");
+  return ND4_ARGS_GO;
+}
+inline int nd4_args_ormtr(int64_t batch, int64_t N, int64_t K, int transpose, const void* F, const void* tau, const void* Z) {
+  ND4_CHECK_ARG(batch >= 0 && N >= 0 && K >= 0, "nd4hip_dormtr_batched: negative extent");
+  ND4_CHECK_ARG(N <= 2048, "nd4hip_dormtr_batched: N <= 2048");
+  ND4_CHECK_ARG(transpose == 0 || transpose == 1, "nd4hip_dormtr_batched: transpose must be 0 or 1");
+  if (batch == 0 || N == 0 || K == 0) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(F && (tau || N < 2) && Z, "nd4hip_dormtr_batched: NULL pointer");
+  return ND4_ARGS_GO;
+}
+inline int nd4_args_syevd_tr(int64_t batch, int64_t N, const void* S, const void* lambda) {
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsyevd_tr_batched: negative extent");
+  ND4_CHECK_ARG(N <= 2048, "nd4hip_dsyevd_tr_batched: N <= 2048");
+  if (batch == 0 || N == 0) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(S && lambda, "nd4hip_dsyevd_tr_batched: NULL pointer");
+  return ND4_ARGS_GO;
+}
+inline int nd4_args_syevx_tr(int64_t batch, int64_t N, int64_t i0, int64_t i1, const void* S, const void* lambda) {
+  return nd4_args_subset("dsyevx_tr_batched", batch, N, i0, i1, {S, lambda});
+}
 inline int nd4_args_sygvd(int algo, int64_t batch, int64_t N, const void* A, const void* B, int64_t strideB, const void* lambda) {
   ND4_CHECK_ARG(algo == 0 || algo == 1, "nd4hip_dsygvd_batched: algo must be 0 (dc) or 1 (jacobi)");
   ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsygvd_batched: negative extent");

@@ -973,6 +973,58 @@ extern "C" int nd4hip_dsyevx_batched_host(nd4hip_handle* h, int64_t batch, int64
   return run_host(h, batch, ops, fn);
 }
 
+// symmetric tridiagonal reduction, its Q and the eigen routes on them (sytrd.hip); tau and e are not moved for N = 1; V = NULL: the
+// values alone
+extern "C" int nd4hip_dsytrd_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* F, double* tau, double* d, double* e) {
+  ND4_ARGS(nd4_args_sytrd(batch, N, S, F, tau, d, e));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dsytrd_batched: NULL handle");
+  // the operands in the order S, F, d, [tau, e]
+  std::vector<Operand> ops{in_op(S, N * N, N * N), out_op(F, N * N), out_op(d, N)};
+  if (N >= 2) { ops.push_back(out_op(tau, N - 1)); ops.push_back(out_op(e, N - 1)); }
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return nd4hip_dsytrd_batched_dev(hd, nb, N, P(p, 0), P(p, 1), N >= 2 ? P(p, 3) : nullptr, P(p, 2), N >= 2 ? P(p, 4) : nullptr);
+  };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_dormtr_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, int transpose, const double* F,
+                                          const double* tau, double* Z) {
+  ND4_ARGS(nd4_args_ormtr(batch, N, K, transpose, F, tau, Z));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dormtr_batched: NULL handle");
+  // the operands in the order F, Z, [tau]
+  std::vector<Operand> ops{in_op(F, N * N, N * N), inout_op(Z, N * K)};
+  if (N >= 2) ops.push_back(in_op(tau, N - 1, N - 1));
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return nd4hip_dormtr_batched_dev(hd, nb, N, K, transpose, P(p, 0), N >= 2 ? P(p, 2) : nullptr, P(p, 1));
+  };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_dsyevd_tr_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V) {
+  ND4_ARGS(nd4_args_syevd_tr(batch, N, S, lambda));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dsyevd_tr_batched: NULL handle");
+  // the operands that are wanted, in the order S, lambda, [V]
+  std::vector<Operand> ops{in_op(S, N * N, N * N), out_op(lambda, N)};
+  const int iv = V ? (int)ops.size() : -1;
+  if (V) ops.push_back(out_op(V, N * N));
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return nd4hip_dsyevd_tr_batched_dev(hd, nb, N, P(p, 0), P(p, 1), iv >= 0 ? P(p, iv) : nullptr);
+  };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_dsyevx_tr_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* S, double* lambda,
+                                             double* V) {
+  ND4_ARGS(nd4_args_syevx_tr(batch, N, i0, i1, S, lambda));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dsyevx_tr_batched: NULL handle");
+  const int64_t k = i1 - i0;
+  // the operands that are wanted, in the order S, lambda, [V]
+  std::vector<Operand> ops{in_op(S, N * N, N * N), out_op(lambda, k)};
+  const int iv = V ? (int)ops.size() : -1;
+  if (V) ops.push_back(out_op(V, N * k));
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return nd4hip_dsyevx_tr_batched_dev(hd, nb, N, i0, i1, P(p, 0), P(p, 1), iv >= 0 ? P(p, iv) : nullptr);
+  };
+  return run_host(h, batch, ops, fn);
+}
+
 // eigen_sym_gen / eigenvals_sym_gen (sygv.hip); X = NULL: the values alone; sweeps = NULL: not wanted; strideB = 0: one B, uploaded
 // once per device
 extern "C" int nd4hip_dsygvd_batched(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B, int64_t strideB,

@@ -185,6 +185,18 @@ int nd4_syevj(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, doubl
 int nd4_stcnt(nd4hip_handle* h, int64_t batch, int64_t N, int64_t M, const double* d, const double* e, const double* x, int32_t* count);
 int nd4_stevx(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* d, const double* e, double* lambda, double* Z);
 int nd4_syevx(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* S, double* lambda, double* V);
+// symmetric tridiagonal reduction and its Q (sytrd.hip): arguments already checked, batch in 1 .. 32768, 1 <= N <= 2048, K >= 1.
+// nd4_sytrd_run synchronises (one flag word), nd4_ormtr (Z [batch, N, K] in place) enqueues only. The four functions after them are
+// the host-side arithmetic of the tiers: 0 = one workgroup per member in LDS, 1 = one launch per column.
+int nd4_sytrd_run(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* F, double* tau, double* d, double* e);
+int nd4_ormtr(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, bool transpose, const double* F, const double* tau, double* Z);
+int nd4_sytrd_tier(int64_t N);
+size_t nd4_sytrd_lds(int64_t N);
+int64_t nd4_sytrd_blocks(int64_t N);
+size_t nd4_sytrd_ws_doubles(int64_t N);
+// eigen_sym(S, reduction='tridiag'): nd4_syevd / nd4_syevx with that reduction in place of nd4_gehrd, the vectors by nd4_ormtr
+int nd4_syevd_tr(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V);
+int nd4_syevx_tr(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* S, double* lambda, double* V);
 // generalised symmetric-definite eigenproblem (sygv.hip): arguments already checked, batch >= 1, 1 <= N; sB / sL 0 = one for all;
 // member0: index of the first member in the caller's batch (error text); nd4_sygvd synchronises
 int nd4_sygvd(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B, int64_t sB, double* lambda,

@@ -248,3 +248,78 @@ int nd4_syevd(nd4hip_handle* h, int64_t batch, int64_t N64, const double* S, dou
   }
   return 0;
 }
+
+namespace {
+// reduction='tridiag' only, one wave per member, before step 3: an off-diagonal entry of T = tridiag(d, e) on the diagonals of F
+// with |e_i| <= eps g, g = max_i(|d_i| + |e_i-1| + |e_i|) the Gershgorin bound, becomes zero. The perturbation is at most eps g per
+// entry, inside the error of the route (a few eps g). Why: nd4_sytrd works from the top, so a rank-deficient S leaves its rounding
+// noise (d, e ~ 1e-16 g) in the trailing rows of T, and on such a tail the divide & conquer solver's own assertion (svd_dc.js:206, a
+// child's values out of order) fails for about one input in seven; with the noise cut off, T splits there and none does
+// (DESIGN.md 4.21). NaN or Inf: every comparison is false and nothing is written; the entrance word mx has flagged the member.
+__global__ __launch_bounds__(64) void syev_tr_deflate(double* __restrict__ F, int N) {
+  double* f = F + (size_t)blockIdx.x * N * N;
+  const int lane = threadIdx.x;
+  double g = 0.0;
+  for (int i = lane; i < N; i += 64) {
+    const double em = i > 0 ? fabs(f[(size_t)i * N + i - 1]) : 0.0, ep = i + 1 < N ? fabs(f[(size_t)(i + 1) * N + i]) : 0.0;
+    g = fmax(g, (fabs(f[(size_t)i * N + i]) + em) + ep);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) g = fmax(g, __shfl_xor(g, off));
+  for (int i = lane; i + 1 < N; i += 64)                      // (every read of e above is done: the shuffles are a wave barrier)
+    if (fabs(f[(size_t)(i + 1) * N + i]) <= DBL_EPSILON * g) f[(size_t)(i + 1) * N + i] = 0.0;
+}
+}  // namespace
+
+// The same with reduction='tridiag' (DESIGN.md 4.21): nd4_sytrd (sytrd.hip) runs straight on the lower triangle of S, so there is no
+// symmetrised copy and no U; its scaled d and e stand on the diagonals of F, where steps 3-5 above read them (after
+// syev_tr_deflate, above). The vectors are V = Q V2^T by nd4_ormtr on the transposed rows of V2; for the values alone neither
+// runs. The symmetrise stage reads 0.
+int nd4_syevd_tr(nd4hip_handle* h, int64_t batch, int64_t N64, const double* S, double* lambda, double* V) {
+  ND4_CHECK_ARG(N64 <= SYEV_MAXN, "nd4hip_dsyevd_tr_batched: the divide & conquer solver takes N <= %d", SYEV_MAXN);
+  ND4_CHECK_ARG(batch <= 32768, "nd4hip_dsyevd_tr_batched: batch %lld exceeds 32768 per call", (long long)batch);
+  if (N64 == 1) return nd4_syevd(h, batch, N64, S, lambda, V);
+  const int N = (int)N64;
+  Nd4WsScope scope(h);
+  const size_t nn = (size_t)N * N;
+  u64* mx = nullptr; int *kexp = nullptr, *flag = nullptr;
+  double *F, *tau, *U2, *V2, *p, *q, *sv, *cs;
+  ND4_TRY(syev_alloc(h, (size_t)batch, &mx)); ND4_TRY(syev_alloc(h, (size_t)batch, &kexp)); ND4_TRY(syev_alloc(h, 1, &flag));
+  ND4_TRY(syev_alloc(h, (size_t)batch, &cs)); ND4_TRY(syev_alloc(h, (size_t)batch * N, &tau));
+  ND4_TRY(syev_alloc(h, (size_t)batch * N, &p)); ND4_TRY(syev_alloc(h, (size_t)batch * N, &q)); ND4_TRY(syev_alloc(h, (size_t)batch * N, &sv));
+  ND4_TRY(syev_alloc(h, (size_t)batch * nn, &F));
+  ND4_TRY(syev_alloc(h, (size_t)batch * nn, &U2)); ND4_TRY(syev_alloc(h, (size_t)batch * nn, &V2));
+  ND4_HIP(hipMemsetAsync(mx, 0, sizeof(u64) * (size_t)batch, h->stream));
+  ND4_HIP(hipMemsetAsync(flag, 0, sizeof(int), h->stream));
+  SyevStamps st(h);
+  st.mark(); st.mark();                                       // no symmetrisation
+  ND4_TRY(nd4_sytrd(h, batch, N, S, F, tau, nullptr, nullptr, mx, false, flag));
+  hipLaunchKernelGGL(syev_tr_deflate, dim3((unsigned)batch), dim3(64), 0, h->stream, F, N);
+  st.mark();
+  hipLaunchKernelGGL(syev_shift_chol, dim3((unsigned)batch), dim3(64), 0, h->stream, F, N, mx, p, q, cs, kexp, flag);
+  ND4_HIP(hipGetLastError());
+  st.mark();
+  ND4_TRY(nd4_bdsdc_rows(h, batch, N, N, p, q, U2, sv, V2));  // synchronises
+  st.mark();
+  const long total = (long)batch * N;
+  hipLaunchKernelGGL(syev_values, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, sv, F, N, total, cs, kexp, mx, lambda,
+                     V ? V2 : nullptr);
+  ND4_HIP(hipGetLastError());
+  if (V) {
+    ND4_TRY(nd4_transpose(h, N, N, V2, N, V, N, batch, (int64_t)nn, (int64_t)nn));
+    ND4_TRY(nd4_ormtr(h, batch, N, N, false, F, tau, V));
+  }
+  st.mark();
+  void* hp = nullptr;
+  ND4_TRY(nd4_pinned(h, sizeof(int), &hp));
+  int* host = static_cast<int*>(hp);
+  ND4_HIP(hipMemcpyAsync(host, flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  ND4_HIP(hipStreamSynchronize(h->stream));
+  st.collect();
+  h->syev_stage_ms[0] = 0.0;                                  // (the time between two event records, not a stage)
+  if (host[0] != 0) {
+    nd4_set_error("eigen_sym(S): S contains NaN or Infinity in its lower triangle.");
+    return ND4HIP_ERR_NOCONV;
+  }
+  return 0;
+}

@@ -455,3 +455,39 @@ int nd4_syevx(nd4hip_handle* h, int64_t batch, int64_t N64, int64_t i0, int64_t 
   }
   return 0;
 }
+
+// The same with reduction='tridiag' (DESIGN.md 4.21): nd4_sytrd (sytrd.hip) in place of the symmetrised copy and nd4_gehrd; the
+// scaled d and e stand on the diagonals of F, where stx_prepare reads them. V = Q Z^T by nd4_ormtr on the k transposed rows of Z:
+// 2 N^2 k flops, no U. The symmetrise stage reads 0.
+int nd4_syevx_tr(nd4hip_handle* h, int64_t batch, int64_t N64, int64_t i0, int64_t i1, const double* S, double* lambda, double* V) {
+  ND4_CHECK_ARG(N64 <= STX_MAXN && batch <= 32768, "nd4hip_dsyevx_tr_batched: extent out of range");
+  if (N64 == 1) return nd4_syevx(h, batch, N64, i0, i1, S, lambda, V);
+  const int N = (int)N64, k = (int)(i1 - i0);
+  Nd4WsScope scope(h);
+  StxStamps st(h);
+  int *flag = nullptr, *flag0 = nullptr; int bad = 0;         // flag0: stx_prepare raises its own word from mx as well
+  const size_t nn = (size_t)N * N;
+  u64* mx = nullptr; double *F, *tau, *Z = nullptr;
+  ND4_TRY(stx_alloc(h, (size_t)batch, &mx)); ND4_TRY(stx_alloc(h, 1, &flag0));
+  ND4_TRY(stx_alloc(h, (size_t)batch * nn, &F)); ND4_TRY(stx_alloc(h, (size_t)batch * N, &tau));
+  if (V) ND4_TRY(stx_alloc(h, (size_t)batch * k * N, &Z));
+  ND4_HIP(hipMemsetAsync(mx, 0, sizeof(u64) * (size_t)batch, h->stream));
+  ND4_HIP(hipMemsetAsync(flag0, 0, sizeof(int), h->stream));
+  st.mark(); st.mark();                                       // no symmetrisation
+  ND4_TRY(nd4_sytrd(h, batch, N, S, F, tau, nullptr, nullptr, mx, false, flag0));
+  st.mark();
+  ND4_TRY(stx_run(h, batch, N, (int)i0, k, F, N + 1, (long)nn, F + N, N + 1, (long)nn, mx, lambda, Z, &st, &flag));
+  if (V) {
+    ND4_TRY(nd4_transpose(h, k, N, Z, N, V, k, batch, (int64_t)k * N, (int64_t)N * k));
+    ND4_TRY(nd4_ormtr(h, batch, N, k, false, F, tau, V));
+  }
+  st.mark();
+  ND4_TRY(stx_read_flag(h, flag, &bad));
+  st.collect();
+  h->syevx_stage_ms[0] = 0.0;                                 // (the time between two event records, not a stage)
+  if (bad) {
+    nd4_set_error("eigen_sym(S): S contains NaN or Infinity in its lower triangle.");
+    return ND4HIP_ERR_NOCONV;
+  }
+  return 0;
+}

@@ -751,9 +751,10 @@ def eigenvals(A):
     return L
 
 
-def _syevd(S, what, vectors, algo=None, info=None, subset=None):
-    from .la import _eigsym_algo, _subset
+def _syevd(S, what, vectors, algo=None, info=None, subset=None, reduction=None):
+    from .la import _eigsym_algo, _reduction, _subset
     jacobi = _eigsym_algo(algo, what)
+    tr = _reduction(reduction, what, jacobi)
     if subset is not None:
         what = what.replace("(S)", "(S, subset)")
         if jacobi:
@@ -773,12 +774,15 @@ def _syevd(S, what, vectors, algo=None, info=None, subset=None):
         V = torch.empty(lead + (N, i1 - i0), dtype=torch.float64, device=S.device) if vectors else None
         if L.numel():
             h = _h(S)
-            _lib.check(h.lib.nd4hip_dsyevx_batched_dev(h.ptr, _batch(lead), N, i0, i1, _p(S), _p(L), _p(V) if vectors else None))
+            fn = h.lib.nd4hip_dsyevx_tr_batched_dev if tr else h.lib.nd4hip_dsyevx_batched_dev
+            _lib.check(fn(h.ptr, _batch(lead), N, i0, i1, _p(S), _p(L), _p(V) if vectors else None))
         return (L, V) if vectors else L
     L = torch.empty(lead + (N,), dtype=torch.float64, device=S.device)
     V = torch.empty(lead + (N, N), dtype=torch.float64, device=S.device) if vectors else None
     h = _h(S)
-    if jacobi:
+    if tr:                                                                  # the symmetric reduction (csrc/sytrd.hip)
+        _lib.check(h.lib.nd4hip_dsyevd_tr_batched_dev(h.ptr, _batch(lead), N, _p(S), _p(L), _p(V) if vectors else None))
+    elif jacobi:
         sweeps = torch.zeros(lead, dtype=torch.int32, device=S.device)
         _lib.check(h.lib.nd4hip_dsyevj_batched_dev(h.ptr, _batch(lead), N, _p(S), _p(L), _p(V) if vectors else None, _p(sweeps)))
         if info is not None:
@@ -788,17 +792,58 @@ def _syevd(S, what, vectors, algo=None, info=None, subset=None):
     return (L, V) if vectors else L
 
 
-def eigen_sym(S, algo=None, info=None, subset=None):
+def eigen_sym(S, algo=None, info=None, subset=None, reduction=None):
     """device-resident la.eigen_sym: (eigenvalues [..., N] descending, eigenvectors [..., N, N] as columns), float64; only the
     lower triangle of S is read and S is not written. algo='jacobi' (N <= 128): the one-launch Jacobi route; `info` then
     receives 'sweeps', an int32 tensor [...] on the device. subset=(i0, i1): L[i0:i1] and the matching columns alone, [..., k] and
-    [..., N, k], by bisection and inverse iteration."""
-    return _syevd(S, "eigen_sym(S)", True, algo, info, subset)
+    [..., N, k], by bisection and inverse iteration. reduction='tridiag': the reduction of tridiag_factor and the vectors by
+    tridiag_apply_q in place of the Hessenberg reduction and its U."""
+    return _syevd(S, "eigen_sym(S)", True, algo, info, subset, reduction)
 
 
-def eigenvals_sym(S, algo=None, info=None, subset=None):
+def eigenvals_sym(S, algo=None, info=None, subset=None, reduction=None):
     """device-resident la.eigenvals_sym: the eigenvalues of eigen_sym alone, the same bits"""
-    return _syevd(S, "eigenvals_sym(S)", False, algo, info, subset)
+    return _syevd(S, "eigenvals_sym(S)", False, algo, info, subset, reduction)
+
+
+def tridiag_factor(S):
+    """device-resident la.tridiag_factor: (F [..., N, N], tau [..., N-1], d [..., N], e [..., N-1]), the same bits"""
+    from .la import _tridiag_s
+    what = "tridiag_factor(S)"
+    if isinstance(S, torch.Tensor) and S.dtype != torch.float64:
+        raise TypeError("%s: S.dtype must be float." % what)
+    _chk(S, "S")
+    N = _tridiag_s(S.dim(), tuple(S.shape), what)
+    lead, ne = tuple(S.shape[:-2]), max(N - 1, 0)
+    F, tau, d, e = (torch.empty(lead + tail, dtype=torch.float64, device=S.device) for tail in ((N, N), (ne,), (N,), (ne,)))
+    if F.numel():
+        h = _h(S)
+        _lib.check(h.lib.nd4hip_dsytrd_batched_dev(h.ptr, _batch(lead), N, _p(S), _p(F), _p(tau), _p(d), _p(e)))
+    return F, tau, d, e
+
+
+def tridiag_apply_q(F, tau, Z, transpose=False):
+    """device-resident la.tridiag_apply_q: Q Z (transpose: Q^T Z) as a new tensor, the same bits; only enqueued"""
+    from .la import _tridiag_fz
+    what = "tridiag_apply_q(F,tau,Z)"
+    for a in (F, tau, Z):
+        if isinstance(a, torch.Tensor) and a.dtype != torch.float64:
+            raise TypeError("%s: F, tau and Z must be float." % what)
+    _chk(F, "F"), _chk(tau, "tau")
+    N, K = _tridiag_fz(tuple(F.shape), tuple(tau.shape), tuple(Z.shape), what)
+    out = _chk(Z.clone(memory_format=torch.contiguous_format), "Z")       # the product is made in place
+    if out.numel():
+        h = _h(F)
+        _lib.check(h.lib.nd4hip_dormtr_batched_dev(h.ptr, _batch(F.shape[:-2]), N, K, 1 if transpose else 0, _p(F), _p(tau), _p(out)))
+    return out
+
+
+def tridiag_decomp(S):
+    """device-resident la.tridiag_decomp: (Q [..., N, N], d, e), Q = tridiag_apply_q(F, tau, I)"""
+    F, tau, d, e = tridiag_factor(S)
+    N = F.shape[-1]
+    eye = torch.eye(N, dtype=torch.float64, device=F.device).expand(F.shape)
+    return tridiag_apply_q(F, tau, eye), d, e
 
 
 def _stevx(d, e, subset, what, vectors):

@@ -1452,12 +1452,19 @@ function makeLa(NDA, fallback, SolveError, Complex) {
    * opts.algo: undefined / 'dc' (the default route) or 'jacobi' (csrc/syevj.hip, N <= 128: two-sided Jacobi in one launch, small
    * eigenvalues of a positive definite S to their own relative accuracy).
    * opts.subset: [i0, i1], 0 <= i0 < i1 <= N (not with 'jacobi'; an empty subset has no NDArray, whose axes are at least 1 long): the eigenvalues i0 .. i1 - 1 of the descending spectrum alone,
-   * [..., k], and their eigenvectors, [..., N, k], k = i1 - i0, by bisection and inverse iteration (csrc/syevx.hip). ---- */
+   * [..., k], and their eigenvectors, [..., N, k], k = i1 - i0, by bisection and inverse iteration (csrc/syevx.hip).
+   * opts.reduction: undefined / 'hessenberg' (the default) or 'tridiag' (not with 'jacobi'): the symmetric tridiagonal reduction of
+   * csrc/sytrd.hip under either route, the eigenvectors by its reflectors. ---- */
   const eigSym = (name, vectors) => {
     const f = function (S, opts) {
       const algo = opts == null ? undefined : opts.algo;
       if (algo !== undefined && algo !== null && algo !== 'dc' && algo !== 'jacobi') throw new Error(`${name}(S, {algo}): algo must be 'dc' or 'jacobi'.`);
       const jac = algo === 'jacobi';
+      const reduction = opts == null ? undefined : opts.reduction;
+      if (reduction !== undefined && reduction !== null && reduction !== 'hessenberg' && reduction !== 'tridiag')
+        throw new Error(`${name}(S, {reduction}): reduction must be 'hessenberg' or 'tridiag'.`);
+      const tr = reduction === 'tridiag';
+      if (tr && jac) throw new Error(`${name}(S, {reduction}): reduction is not available with algo 'jacobi'.`);
       const subset = opts == null ? undefined : opts.subset;
       if (subset != null) {
         if (jac) throw new Error(`${name}(S, {subset}): subset is not available with algo 'jacobi'.`);
@@ -1479,8 +1486,8 @@ function makeLa(NDA, fallback, SolveError, Complex) {
         const lead = Array.from(S.shape.subarray(0, nd_ - 2));
         const Ls = alloc(dev, batch * k), Vs = vectors ? alloc(dev, batch * N * k) : null;
         try {
-          if (vectors) native().dsyevx_batched(batch, N, i0, i1, view(opF64(S, dev, temps), 0), view(Ls, 0), view(Vs, 0));
-          else native().dsyevxals_batched(batch, N, i0, i1, view(opF64(S, dev, temps), 0), view(Ls, 0));
+          if (vectors) native()[tr ? 'dsyevx_tr_batched' : 'dsyevx_batched'](batch, N, i0, i1, view(opF64(S, dev, temps), 0), view(Ls, 0), view(Vs, 0));
+          else native()[tr ? 'dsyevxals_tr_batched' : 'dsyevxals_batched'](batch, N, i0, i1, view(opF64(S, dev, temps), 0), view(Ls, 0));
         }
         catch (e) { if (dev) { Ls.free(); if (Vs) Vs.free(); } throw e; }
         finally { release(temps); }
@@ -1489,8 +1496,8 @@ function makeLa(NDA, fallback, SolveError, Complex) {
       }
       const L = alloc(dev, batch * N), V = vectors ? alloc(dev, batch * N * N) : null;
       try {
-        if (vectors) native()[jac ? 'dsyevj_batched' : 'dsyevd_batched'](batch, N, view(opF64(S, dev, temps), 0), view(L, 0), view(V, 0));
-        else native()[jac ? 'dsyevjals_batched' : 'dsyevals_batched'](batch, N, view(opF64(S, dev, temps), 0), view(L, 0));
+        if (vectors) native()[tr ? 'dsyevd_tr_batched' : jac ? 'dsyevj_batched' : 'dsyevd_batched'](batch, N, view(opF64(S, dev, temps), 0), view(L, 0), view(V, 0));
+        else native()[tr ? 'dsyevdals_tr_batched' : jac ? 'dsyevjals_batched' : 'dsyevals_batched'](batch, N, view(opF64(S, dev, temps), 0), view(L, 0));
       }
       catch (e) { if (dev) { L.free(); if (V) V.free(); } throw e; }
       finally { release(temps); }

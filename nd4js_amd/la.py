@@ -10,6 +10,8 @@ JS wrapper nd4js_amd/js/index.js over the N-API shim; both call the same libnd4h
   bidiag_svd(d, e)     src/la/svd_dc.js:169-824     -> nd4hip_dbdsdc_batched
   eigen_sym(S), eigenvals_sym(S)   planned at src/la/eigen.js:28-30   -> nd4hip_dsyevd_batched; algo='jacobi' (opt-in): nd4hip_dsyevj_batched
                                    subset=(i0, i1) (opt-in): a slice of the descending spectrum -> nd4hip_dsyevx_batched_host
+                                   reduction='tridiag' (opt-in): the symmetric reduction of csrc/sytrd.hip -> nd4hip_dsyevd_tr_batched_host, nd4hip_dsyevx_tr_batched_host
+  tridiag_factor(S), tridiag_apply_q(F, tau, Z), tridiag_decomp(S)   not in the reference   -> nd4hip_dsytrd_batched_host, nd4hip_dormtr_batched_host
   tridiag_eigen(d, e), tridiag_eigenvals(d, e), tridiag_count(d, e, x)   not in the reference   -> nd4hip_dstevx_batched_host, nd4hip_dstcnt_batched_host
   eigen_sym_gen(A, B), eigenvals_sym_gen(A, B)   A x = lambda B x, not in the reference   -> nd4hip_dsygvd_batched
 
@@ -1146,8 +1148,21 @@ def _subset(subset, N, what, jacobi=False):
     return i0, i1
 
 
-def _syevd(S, what, vectors, device, algo=None, info=None, subset=None):
+def _reduction(reduction, what, jacobi):
+    """True for reduction='tridiag' (csrc/sytrd.hip, opt-in); None / 'hessenberg' is the default reduction (csrc/hess.hip)"""
+    what = what.replace("(S)", "(S, reduction)")
+    if reduction is None or reduction == "hessenberg":
+        return False
+    if reduction != "tridiag":
+        raise ValueError("%s: reduction must be None, 'hessenberg' or 'tridiag'." % what)
+    if jacobi:
+        raise ValueError("%s: reduction is not available with algo='jacobi'." % what)
+    return True
+
+
+def _syevd(S, what, vectors, device, algo=None, info=None, subset=None, reduction=None):
     jacobi = _eigsym_algo(algo, what)
+    tr = _reduction(reduction, what, jacobi)
     if subset is not None:
         what = what.replace("(S)", "(S, subset)")
         if jacobi:
@@ -1168,12 +1183,15 @@ def _syevd(S, what, vectors, device, algo=None, info=None, subset=None):
         V = np.empty(S.shape[:-1] + (i1 - i0,)) if vectors else None
         if L.size:
             h = _lib.handle(device)
-            _lib.check(h.lib.nd4hip_dsyevx_batched_host(h.ptr, batch, N, i0, i1, _ptr(S), _ptr(L), _ptr(V) if vectors else None))
+            fn = h.lib.nd4hip_dsyevx_tr_batched_host if tr else h.lib.nd4hip_dsyevx_batched_host
+            _lib.check(fn(h.ptr, batch, N, i0, i1, _ptr(S), _ptr(L), _ptr(V) if vectors else None))
         return (L, V) if vectors else L
     L = np.empty(S.shape[:-1])
     V = np.empty(S.shape) if vectors else None
     h = _lib.handle(device)
-    if jacobi:
+    if tr:                                                                  # the symmetric reduction (csrc/sytrd.hip)
+        _lib.check(h.lib.nd4hip_dsyevd_tr_batched_host(h.ptr, batch, N, _ptr(S), _ptr(L), _ptr(V) if vectors else None))
+    elif jacobi:
         sweeps = np.zeros(S.shape[:-2], dtype=np.int32)
         _lib.check(h.lib.nd4hip_dsyevj_batched(h.ptr, batch, N, _ptr(S), _ptr(L), _ptr(V) if vectors else None, sweeps.ctypes.data))
         if info is not None:
@@ -1183,7 +1201,7 @@ def _syevd(S, what, vectors, device, algo=None, info=None, subset=None):
     return (L, V) if vectors else L
 
 
-def eigen_sym(S, device=None, algo=None, info=None, subset=None):
+def eigen_sym(S, device=None, algo=None, info=None, subset=None, reduction=None):
     """the function the reference plans at eigen.js:28-30: (eigenvalues float64 [..., N] descending, eigenvectors float64
     [..., N, N] as columns) of the symmetric S, S V = V diag(L) and V^T V = I. Only the lower triangle of S is read. NaN or
     Infinity there raises Nd4HipError with code -3. N <= 2048.
@@ -1191,14 +1209,87 @@ def eigen_sym(S, device=None, algo=None, info=None, subset=None):
     cyclic two-sided Jacobi inside one launch; for positive definite S every eigenvalue, however small, is accurate to
     N eps kappa_2(D^-1 S D^-1) relative to itself, D = diag(sqrt s_ii). `info` (a dict) then receives 'sweeps', int32 [...].
     subset=(i0, i1) (opt-in, not with 'jacobi'): only L[i0:i1] of the descending spectrum and the matching columns of V, k = i1 - i0
-    of them: (L [..., k], V [..., N, k]), by bisection and inverse iteration on the tridiagonal form (tridiag_eigen below)."""
-    return _syevd(S, "eigen_sym(S)", True, device, algo, info, subset)
+    of them: (L [..., k], V [..., N, k]), by bisection and inverse iteration on the tridiagonal form (tridiag_eigen below).
+    reduction='tridiag' (opt-in, not with 'jacobi'; None / 'hessenberg': the default): the tridiagonal form by tridiag_factor below,
+    straight from the lower triangle, and the eigenvectors by tridiag_apply_q, 2 N^2 k flops for k of them."""
+    return _syevd(S, "eigen_sym(S)", True, device, algo, info, subset, reduction)
 
 
-def eigenvals_sym(S, device=None, algo=None, info=None, subset=None):
+def eigenvals_sym(S, device=None, algo=None, info=None, subset=None, reduction=None):
     """the eigenvalues of eigen_sym alone (the same bits); no eigenvector product is computed or stored. With algo='jacobi' no
-    eigenvector is accumulated at all; with subset no inverse iteration is made."""
-    return _syevd(S, "eigenvals_sym(S)", False, device, algo, info, subset)
+    eigenvector is accumulated at all; with subset no inverse iteration is made; with reduction='tridiag' no Q is applied."""
+    return _syevd(S, "eigenvals_sym(S)", False, device, algo, info, subset, reduction)
+
+
+def _tridiag_s(S_ndim, S_shape, what):
+    """the shape checks of tridiag_factor / tridiag_decomp, shared with dev.py; returns N"""
+    if S_ndim < 2:
+        raise ValueError("%s: S.ndim must be at least 2." % what)
+    if S_shape[-2] != S_shape[-1]:
+        raise ValueError("%s: S must be quadratic." % what)
+    if S_shape[-1] > 2048:
+        raise ValueError("%s: N <= 2048." % what)
+    return int(S_shape[-1])
+
+
+def _tridiag_fz(F_shape, tau_shape, Z_shape, what):
+    """the shape checks of tridiag_apply_q, shared with dev.py; returns (N, K)"""
+    if len(F_shape) < 2 or F_shape[-2] != F_shape[-1]:
+        raise ValueError("%s: F must be quadratic." % what)
+    N = int(F_shape[-1])
+    if N > 2048:
+        raise ValueError("%s: N <= 2048." % what)
+    lead = tuple(F_shape[:-2])
+    if len(tau_shape) < 1 or tuple(tau_shape) != lead + (max(N - 1, 0),):
+        raise ValueError("%s: tau must be [..., N - 1] with the leading dimensions of F." % what)
+    if len(Z_shape) < 2 or tuple(Z_shape[:-1]) != lead + (N,):
+        raise ValueError("%s: Z must be [..., N, K] with the leading dimensions of F." % what)
+    return N, int(Z_shape[-1])
+
+
+def tridiag_factor(S, device=None):
+    """(F [..., N, N], tau [..., max(N-1, 0)], d [..., N], e [..., max(N-1, 0)]) with S = Q tridiag(d, e) Q^T for the symmetric float64 S,
+    read only in its lower triangle: Q = H_0 H_1 ... H_{N-3}, H_k = I - tau_k v_k v_k^T, v_k zero in rows 0..k, 1 in row k+1, its tail in
+    F[k+2:, k] (LAPACK's dsytrd, lower). F carries d on its diagonal, e on its first subdiagonal and zeros above. e_k = -sign(alpha) |x|
+    for the column x = [alpha; tail] (sign(0) = +1); a column whose tail is zero gets tau_k = 0 and e_k = alpha. NaN or Infinity in the
+    lower triangle raises Nd4HipError with code -3. N <= 2048 (csrc/sytrd.hip)."""
+    what = "tridiag_factor(S)"
+    S = np.asarray(S)
+    if np.iscomplexobj(S):
+        raise TypeError("%s: S.dtype must be float." % what)
+    N = _tridiag_s(S.ndim, S.shape, what)
+    S = _asarray(S, what)
+    lead, ne = S.shape[:-2], max(N - 1, 0)
+    F, tau, d, e = np.empty(S.shape), np.empty(lead + (ne,)), np.empty(lead + (N,)), np.empty(lead + (ne,))
+    if F.size:
+        h = _lib.handle(device)
+        _lib.check(h.lib.nd4hip_dsytrd_batched_host(h.ptr, int(np.prod(lead, dtype=np.int64)), N, _ptr(S), _ptr(F), _ptr(tau), _ptr(d), _ptr(e)))
+    return F, tau, d, e
+
+
+def tridiag_apply_q(F, tau, Z, transpose=False, device=None):
+    """Q Z (transpose: Q^T Z) for the Q of tridiag_factor's (F, tau) and Z [..., N, K] with the leading dimensions of F. Q is never
+    formed: N <= 128 reflector by reflector in LDS, above in compact WY blocks on the GEMM."""
+    what = "tridiag_apply_q(F,tau,Z)"
+    F, tau, Z = np.asarray(F), np.asarray(tau), np.asarray(Z)
+    if np.iscomplexobj(F) or np.iscomplexobj(tau) or np.iscomplexobj(Z):
+        raise TypeError("%s: F, tau and Z must be float." % what)
+    N, K = _tridiag_fz(F.shape, tau.shape, Z.shape, what)
+    F, tau = _asarray(F, what), _asarray(tau, what)
+    out = np.array(Z, dtype=np.float64, order="C")                          # a copy: the product is made in place
+    if out.size:
+        h = _lib.handle(device)
+        _lib.check(h.lib.nd4hip_dormtr_batched_host(h.ptr, int(np.prod(F.shape[:-2], dtype=np.int64)), N, K, 1 if transpose else 0, _ptr(F),
+                                                    _ptr(tau), _ptr(out)))
+    return out
+
+
+def tridiag_decomp(S, device=None):
+    """(Q [..., N, N], d [..., N], e [..., N-1]) with S = Q tridiag(d, e) Q^T: tridiag_factor, and Q = tridiag_apply_q(F, tau, I), the
+    same bits."""
+    F, tau, d, e = tridiag_factor(S, device)
+    N = F.shape[-1]
+    return tridiag_apply_q(F, tau, np.broadcast_to(np.eye(N), F.shape), False, device), d, e
 
 
 def _tridiag_args(d, e, what, ndim, shape):
