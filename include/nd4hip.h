@@ -663,6 +663,52 @@ int nd4hip_dsyevd_tr_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, co
 int nd4hip_dsyevx_tr_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* S, double* lambda, double* V);
 int nd4hip_dsyevx_tr_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* S, double* lambda, double* V);
 
+/* ---- eigenpairs in a value interval: eigen_sym(S, interval=(lo, hi)), tridiag_eigen(d, e, interval) (csrc/syevx.hip) ----
+ * dstevxv, dsyevxv and dsyevxv_tr are dstevx, dsyevx and dsyevx_tr with the subset of each member chosen by value: bounds [batch,2]
+ * holds (lo, hi) per member and selects the eigenvalues lo < lambda <= hi, which is exactly the subset (i0_b, i1_b) =
+ * (count(hi), count(lo)) with dstcnt's count on the member's scaled tridiagonal form. lo <= hi; +-Infinity is a bound like any other
+ * (count(+inf) = 0, count(-inf) = N); NaN, or lo > hi, is ND4HIP_ERR_ARG (the _host forms look at bounds before anything moves; the
+ * _dev forms see lo > hi as i1_b < i0_b after the count, and a NaN bound there selects nothing).
+ * Results are ragged: range [batch,2] (int32) receives (i0_b, i1_b), *kmax (a host word in BOTH forms) the largest k_b = i1_b - i0_b.
+ * lambda [batch,kcap], Z [batch,kcap,N] (dstevxv; rows = vectors) and V [batch,N,kcap] (columns = vectors) have room for kcap values
+ * per member: member b's k_b results stand first, bit for bit those of the subset form with (i0_b, i1_b); its entries k_b .. kmax-1
+ * are NaN in lambda and zero in Z / V; nothing from kmax on is written. kcap < kmax: ND4HIP_ERR_ARG, reported after the count and
+ * before anything else is launched (kcap = N always fits). Z / V = NULL: the values alone. Device work, and the device-to-host copy
+ * of the _host forms, grow with kmax, not with kcap; kmax = 0 launches nothing after the count. The ranges are read back once (the
+ * host needs kmax to size the grids) and the calls synchronise. N = 0 and an empty batch have nothing to do and write nothing, kmax
+ * included. Errors as the subset forms'. Profile ops "dstevxv_batched", "dsyevxv_batched", "dsyevxv_tr_batched"; stage times through
+ * nd4hip_dsyevx_last_stages, the count inside the bisection stage. */
+int nd4hip_dstevxv_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, int64_t kcap, const double* bounds, const double* d, const double* e,
+                                double* lambda, double* Z, int32_t* range, int64_t* kmax);
+int nd4hip_dstevxv_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t kcap, const double* bounds, const double* d, const double* e,
+                                double* lambda, double* Z, int32_t* range, int64_t* kmax);
+int nd4hip_dsyevxv_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, int64_t kcap, const double* bounds, const double* S, double* lambda,
+                                double* V, int32_t* range, int64_t* kmax);
+int nd4hip_dsyevxv_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t kcap, const double* bounds, const double* S, double* lambda,
+                                double* V, int32_t* range, int64_t* kmax);
+int nd4hip_dsyevxv_tr_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, int64_t kcap, const double* bounds, const double* S, double* lambda,
+                                   double* V, int32_t* range, int64_t* kmax);
+int nd4hip_dsyevxv_tr_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t kcap, const double* bounds, const double* S, double* lambda,
+                                   double* V, int32_t* range, int64_t* kmax);
+
+/* ---- eigen_sym_gen / eigenvals_sym_gen with subset, interval or reduction (csrc/sygv.hip) ----
+ * dsygvd below (divide & conquer side, algo 0) with step 3, the eigenproblem of C = L^-1 A L^-T, chosen by two selectors:
+ *   reduction 0: the Hessenberg reduction (dsygvd's), 1: dsytrd;
+ *   select 0: every eigenpair, lambda [batch,N], X [batch,N,N] (with reduction 1: dsyevd_tr);
+ *          1: the subset (i0, i1) of the descending spectrum, lambda [batch,k], X [batch,N,k], k = i1 - i0 (dsyevx / dsyevx_tr);
+ *          2: the eigenvalues lo < lambda <= hi of every member, bounds [batch,2] = (lo, hi): lambda [batch,kcap], X [batch,N,kcap],
+ *             range [batch,2] (int32) and *kmax (a host word in both forms), ragged exactly as dsyevxv's (dsyevxv / dsyevxv_tr).
+ * i0, i1 are looked at for select 1 only; kcap, bounds, range and kmax for select 2 only (pass 0 / NULL otherwise). Steps 1 and 2, the
+ * errors (B not positive definite with its member: ND4HIP_ERR_SINGULAR; C not finite: ND4HIP_ERR_NOCONV) and the passes over a large
+ * batch are dsygvd's. Step 4, X = L^-T Y, runs on the k (or kmax) columns that step 3 computed; for N <= 64 every column has the bits
+ * it has in dsygvd's X. X = NULL: the values alone. The host-pointer form ends in _host, as those of the selected eigenpairs do. Profile op "dsygvx_batched". */
+int nd4hip_dsygvx_batched_dev (nd4hip_handle* h, int reduction, int select, int64_t batch, int64_t N, int64_t i0, int64_t i1, int64_t kcap,
+                               const double* bounds, const double* A, const double* B, int64_t strideB, double* lambda, double* X,
+                               int32_t* range, int64_t* kmax);
+int nd4hip_dsygvx_batched_host(nd4hip_handle* h, int reduction, int select, int64_t batch, int64_t N, int64_t i0, int64_t i1, int64_t kcap,
+                              const double* bounds, const double* A, const double* B, int64_t strideB, double* lambda, double* X,
+                              int32_t* range, int64_t* kmax);
+
 /* ---- eigen_sym_gen / eigenvals_sym_gen: A x = lambda B x, A symmetric, B symmetric positive definite (csrc/sygv.hip) ----
  * A [batch,N,N]; B [batch,N,N] (strideB = N*N) or ONE B [N,N] for every member (strideB = 0; it is factorised once per call of the
  * _dev form, once per staged chunk of the host form, never once per member). Only the lower triangles of A and B are read and

@@ -169,8 +169,20 @@ SIGNATURES = {
     "nd4hip_dormtr_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_int, c_dp, c_dp, c_dp]),
     "nd4hip_dsyevd_tr_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),
     "nd4hip_dsyevx_tr_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    # (handle, batch, N, kcap, bounds, d, e | S, lambda, Z | V, range int32, kmax int64 on the host)
+    "nd4hip_dstevxv_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, c_dp, ctypes.c_void_p, ctypes.POINTER(c_i64)]),
+    "nd4hip_dstevxv_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, c_dp, ctypes.c_void_p, ctypes.POINTER(c_i64)]),
+    "nd4hip_dsyevxv_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, ctypes.c_void_p, ctypes.POINTER(c_i64)]),
+    "nd4hip_dsyevxv_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, ctypes.c_void_p, ctypes.POINTER(c_i64)]),
+    "nd4hip_dsyevxv_tr_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, ctypes.c_void_p, ctypes.POINTER(c_i64)]),
+    "nd4hip_dsyevxv_tr_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, ctypes.c_void_p, ctypes.POINTER(c_i64)]),
     "nd4hip_dsygvd_batched_dev": (c_int, [ctypes.c_void_p, c_int, c_i64, c_i64, c_dp, c_dp, c_i64, c_dp, c_dp, ctypes.c_void_p]),
     "nd4hip_dsygvd_batched": (c_int, [ctypes.c_void_p, c_int, c_i64, c_i64, c_dp, c_dp, c_i64, c_dp, c_dp, ctypes.c_void_p]),
+    # (handle, reduction, select, batch, N, i0, i1, kcap, bounds, A, B, strideB, lambda, X, range int32, kmax int64 on the host)
+    "nd4hip_dsygvx_batched_dev": (c_int, [ctypes.c_void_p, c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_i64, c_dp, c_dp,
+                                          ctypes.c_void_p, ctypes.POINTER(c_i64)]),
+    "nd4hip_dsygvx_batched_host": (c_int, [ctypes.c_void_p, c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_i64, c_dp, c_dp,
+                                      ctypes.c_void_p, ctypes.POINTER(c_i64)]),
     "nd4hip_dsygst_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_i64, c_dp]),
     "nd4hip_dsygst_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_i64, c_dp]),
     "nd4hip_dgeqr2_panel_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),

@@ -79,6 +79,12 @@ static int (*p_dsyevx[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, co
 static int (*p_dsyevd_tr[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*, double*);
 static int (*p_dsyevx_tr[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, const double*, double*, double*);
 static int (*p_dsygvd[2])(nd4hip_handle*, int, int64_t, int64_t, const double*, const double*, int64_t, double*, double*, int32_t*);
+static int (*p_dstcnt[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, const double*, const double*, int32_t*);
+static int (*p_dstevx[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, const double*, const double*, double*, double*);
+static int (*p_dstevxv[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, const double*, const double*, double*, double*, int32_t*, int64_t*);
+static int (*p_dsyevxv[2][2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, const double*, double*, double*, int32_t*, int64_t*);   /* [tridiag][dev] */
+static int (*p_dsygvx[2])(nd4hip_handle*, int, int, int64_t, int64_t, int64_t, int64_t, int64_t, const double*, const double*, const double*, int64_t,
+                          double*, double*, int32_t*, int64_t*);
 static int (*p_dqp3rank[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, int32_t*);
 static int (*p_dqp3ls[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t,
                           const int32_t*, int64_t, const double*, int64_t, double*, int32_t*);
@@ -183,6 +189,12 @@ static int load_library(void) {
   SYM(p_dsyevd_tr[0], "nd4hip_dsyevd_tr_batched_host"); SYM(p_dsyevd_tr[1], "nd4hip_dsyevd_tr_batched_dev");   /* and so do these two */
   SYM(p_dsyevx_tr[0], "nd4hip_dsyevx_tr_batched_host"); SYM(p_dsyevx_tr[1], "nd4hip_dsyevx_tr_batched_dev");
   SYM2(p_dsygvd, "nd4hip_dsygvd_batched");
+  SYM(p_dstcnt[0], "nd4hip_dstcnt_batched_host"); SYM(p_dstcnt[1], "nd4hip_dstcnt_batched_dev");
+  SYM(p_dstevx[0], "nd4hip_dstevx_batched_host"); SYM(p_dstevx[1], "nd4hip_dstevx_batched_dev");
+  SYM(p_dstevxv[0], "nd4hip_dstevxv_batched_host"); SYM(p_dstevxv[1], "nd4hip_dstevxv_batched_dev");
+  SYM(p_dsyevxv[0][0], "nd4hip_dsyevxv_batched_host"); SYM(p_dsyevxv[0][1], "nd4hip_dsyevxv_batched_dev");
+  SYM(p_dsyevxv[1][0], "nd4hip_dsyevxv_tr_batched_host"); SYM(p_dsyevxv[1][1], "nd4hip_dsyevxv_tr_batched_dev");
+  SYM(p_dsygvx[0], "nd4hip_dsygvx_batched_host"); SYM(p_dsygvx[1], "nd4hip_dsygvx_batched_dev");
   SYM2(p_dqp3rank, "nd4hip_dqp3rank_batched");
   SYM2(p_dsrrqr, "nd4hip_dsrrqr_batched");
   SYM2(p_durv, "nd4hip_durv_batched");
@@ -867,6 +879,91 @@ static napi_value js_dsygvals(napi_env env, napi_callback_info info) {
   FAIL_IF(p_dsygvd[A.dev](g_handle, (int)algo, batch, N, (const double*)A.p, (const double*)B.p, sB, (double*)L.p, NULL, NULL));
   return NULL;
 }
+/* ---- the tridiagonal solver and the interval forms (csrc/syevx.hip). An operand that the call does not
+ * need is passed as null: e for N = 1, Z / V / X for the values alone, bounds and range where no interval is selected. The interval
+ * forms return kmax as a number. ---- */
+static int is_nullish(napi_env env, napi_value v) {
+  napi_valuetype t;
+  return napi_typeof(env, v, &t) == napi_ok && (t == napi_null || t == napi_undefined);
+}
+/* an optional operand: absent -> p = NULL, and it takes the side of the others */
+static int opt_op(napi_env env, napi_value v, napi_typedarray_type want, int side, opnd* out) {
+  if (is_nullish(env, v)) { out->p = NULL; out->len = 0; out->dev = side; return 0; }
+  return get_op(env, v, want, out);
+}
+static napi_value kmax_value(napi_env env, int64_t kmax) { napi_value r; napi_create_double(env, (double)kmax, &r); return r; }
+/* dstcnt_batched(batch, N, M, d, e, x, count) */
+static napi_value js_dstcnt(napi_env env, napi_callback_info info) {
+  ARGS(7, "dstcnt_batched");
+  int64_t batch, N, M; opnd d, e, x, c;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || get_i64(env, a[2], &M) || F64(3, d) || opt_op(env, a[4], napi_float64_array, d.dev, &e) ||
+      F64(5, x) || I32(6, c)) return NULL;
+  NEED(batch >= 0 && N >= 1 && M >= 0 && (size_t)(batch * N) <= d.len && (N < 2 || (size_t)(batch * (N - 1)) <= e.len) && (size_t)(batch * M) <= x.len &&
+       (size_t)(batch * M) <= c.len, "dstcnt_batched: buffer too small");
+  SAME_SIDE(d.dev == e.dev && e.dev == x.dev && x.dev == c.dev, "dstcnt_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dstcnt[d.dev](g_handle, batch, N, M, (const double*)d.p, (const double*)e.p, (const double*)x.p, (int32_t*)c.p));
+  return NULL;
+}
+/* dstevx_batched(batch, N, i0, i1, d, e, L, Z): L [batch, k], Z [batch, k, N] (rows = vectors) or null */
+static napi_value js_dstevx(napi_env env, napi_callback_info info) {
+  ARGS(8, "dstevx_batched");
+  int64_t batch, N, i0, i1; opnd d, e, L, Z;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || get_i64(env, a[2], &i0) || get_i64(env, a[3], &i1) || F64(4, d) ||
+      opt_op(env, a[5], napi_float64_array, d.dev, &e) || F64(6, L) || opt_op(env, a[7], napi_float64_array, d.dev, &Z)) return NULL;
+  NEED(batch >= 0 && N >= 1 && 0 <= i0 && i0 <= i1 && i1 <= N && (size_t)(batch * N) <= d.len && (N < 2 || (size_t)(batch * (N - 1)) <= e.len) &&
+       (size_t)(batch * (i1 - i0)) <= L.len && (!Z.p || (size_t)(batch * (i1 - i0) * N) <= Z.len), "dstevx_batched: bad subset or buffer too small");
+  SAME_SIDE(d.dev == e.dev && e.dev == L.dev && L.dev == Z.dev, "dstevx_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dstevx[d.dev](g_handle, batch, N, i0, i1, (const double*)d.p, (const double*)e.p, (double*)L.p, (double*)Z.p));
+  return NULL;
+}
+/* dstevxv_batched(batch, N, kcap, bounds, d, e, L, Z, range) -> kmax: L [batch, kcap], Z [batch, kcap, N] or null, range int32 [batch, 2] */
+static napi_value js_dstevxv(napi_env env, napi_callback_info info) {
+  ARGS(9, "dstevxv_batched");
+  int64_t batch, N, kcap, kmax = 0; opnd bd, d, e, L, Z, rg;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || get_i64(env, a[2], &kcap) || F64(3, bd) || F64(4, d) ||
+      opt_op(env, a[5], napi_float64_array, d.dev, &e) || F64(6, L) || opt_op(env, a[7], napi_float64_array, d.dev, &Z) || I32(8, rg)) return NULL;
+  NEED(batch >= 0 && N >= 1 && kcap >= 0 && (size_t)(batch * 2) <= bd.len && (size_t)(batch * N) <= d.len && (N < 2 || (size_t)(batch * (N - 1)) <= e.len) &&
+       (size_t)(batch * kcap) <= L.len && (!Z.p || (size_t)(batch * kcap * N) <= Z.len) && (size_t)(batch * 2) <= rg.len, "dstevxv_batched: buffer too small");
+  SAME_SIDE(bd.dev == d.dev && d.dev == e.dev && e.dev == L.dev && L.dev == Z.dev && Z.dev == rg.dev, "dstevxv_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dstevxv[d.dev](g_handle, batch, N, kcap, (const double*)bd.p, (const double*)d.p, (const double*)e.p, (double*)L.p, (double*)Z.p,
+                           (int32_t*)rg.p, &kmax));
+  return kmax_value(env, kmax);
+}
+/* dsyevxv_batched(tridiag, batch, N, kcap, bounds, S, L, V, range) -> kmax: L [batch, kcap], V [batch, N, kcap] or null */
+static napi_value js_dsyevxv(napi_env env, napi_callback_info info) {
+  ARGS(9, "dsyevxv_batched");
+  int64_t tr, batch, N, kcap, kmax = 0; opnd bd, S, L, V, rg;
+  if (get_i64(env, a[0], &tr) || get_i64(env, a[1], &batch) || get_i64(env, a[2], &N) || get_i64(env, a[3], &kcap) || F64(4, bd) || F64(5, S) ||
+      F64(6, L) || opt_op(env, a[7], napi_float64_array, S.dev, &V) || I32(8, rg)) return NULL;
+  NEED((tr == 0 || tr == 1) && batch >= 0 && N >= 0 && kcap >= 0 && (size_t)(batch * 2) <= bd.len && (size_t)(batch * N * N) <= S.len &&
+       (size_t)(batch * kcap) <= L.len && (!V.p || (size_t)(batch * N * kcap) <= V.len) && (size_t)(batch * 2) <= rg.len, "dsyevxv_batched: buffer too small");
+  SAME_SIDE(bd.dev == S.dev && S.dev == L.dev && L.dev == V.dev && V.dev == rg.dev, "dsyevxv_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dsyevxv[tr][S.dev](g_handle, batch, N, kcap, (const double*)bd.p, (const double*)S.p, (double*)L.p, (double*)V.p, (int32_t*)rg.p, &kmax));
+  return kmax_value(env, kmax);
+}
+/* dsygvx_batched(reduction, select, batch, N, i0, i1, kcap, bounds, A, B, strideB, L, X, range) -> kmax (0 unless select = 2): L and X are
+ * K = N (select 0), i1 - i0 (1) or kcap (2) wide; bounds and range are null unless select = 2; X null: the values alone */
+static napi_value js_dsygvx(napi_env env, napi_callback_info info) {
+  ARGS(14, "dsygvx_batched");
+  int64_t red, sel, batch, N, i0, i1, kcap, sB, kmax = 0; opnd bd, A, B, L, X, rg;
+  if (get_i64(env, a[0], &red) || get_i64(env, a[1], &sel) || get_i64(env, a[2], &batch) || get_i64(env, a[3], &N) || get_i64(env, a[4], &i0) ||
+      get_i64(env, a[5], &i1) || get_i64(env, a[6], &kcap) || F64(8, A) || opt_op(env, a[7], napi_float64_array, A.dev, &bd) || F64(9, B) ||
+      get_i64(env, a[10], &sB) || F64(11, L) || opt_op(env, a[12], napi_float64_array, A.dev, &X) || opt_op(env, a[13], napi_int32_array, A.dev, &rg)) return NULL;
+  NEED(sel >= 0 && sel <= 2 && batch >= 0 && N >= 0 && (sel != 1 || (0 <= i0 && i0 <= i1 && i1 <= N)) && (sel != 2 || kcap >= 0), "dsygvx_batched: bad selector");
+  const int64_t K = sel == 0 ? N : sel == 1 ? i1 - i0 : kcap;
+  NEED((sB == 0 || sB == N * N) && (size_t)(batch * N * N) <= A.len && (size_t)((sB ? batch : 1) * N * N) <= B.len && (size_t)(batch * K) <= L.len &&
+       (!X.p || (size_t)(batch * N * K) <= X.len) && (sel != 2 || (bd.p && rg.p && (size_t)(batch * 2) <= bd.len && (size_t)(batch * 2) <= rg.len)),
+       "dsygvx_batched: buffer too small");
+  SAME_SIDE(A.dev == B.dev && B.dev == L.dev && L.dev == X.dev && X.dev == bd.dev && bd.dev == rg.dev, "dsygvx_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dsygvx[A.dev](g_handle, (int)red, (int)sel, batch, N, i0, i1, kcap, (const double*)bd.p, (const double*)A.p, (const double*)B.p, sB,
+                          (double*)L.p, (double*)X.p, (int32_t*)rg.p, sel == 2 ? &kmax : NULL));
+  return kmax_value(env, kmax);
+}
 /* dnrmfro(n, A) -> number   (norm(A) 'fro', norm.js:22-85); a device operand's result comes back as a host number too */
 static napi_value js_dnrmfro(napi_env env, napi_callback_info info) {
   ARGS(2, "dnrmfro");
@@ -1297,6 +1394,11 @@ static napi_value init(napi_env env, napi_value exports) {
     {"dsyevxals_tr_batched", NULL, js_dsyevxals_tr, NULL, NULL, NULL, napi_default, NULL},
     {"dsygvd_batched", NULL, js_dsygvd, NULL, NULL, NULL, napi_default, NULL},
     {"dsygvals_batched", NULL, js_dsygvals, NULL, NULL, NULL, napi_default, NULL},
+    {"dstcnt_batched", NULL, js_dstcnt, NULL, NULL, NULL, napi_default, NULL},
+    {"dstevx_batched", NULL, js_dstevx, NULL, NULL, NULL, napi_default, NULL},
+    {"dstevxv_batched", NULL, js_dstevxv, NULL, NULL, NULL, napi_default, NULL},
+    {"dsyevxv_batched", NULL, js_dsyevxv, NULL, NULL, NULL, napi_default, NULL},
+    {"dsygvx_batched", NULL, js_dsygvx, NULL, NULL, NULL, napi_default, NULL},
     {"dqp3rank_batched", NULL, js_dqp3rank, NULL, NULL, NULL, napi_default, NULL},
     {"dsrrqr_batched", NULL, js_dsrrqr, NULL, NULL, NULL, napi_default, NULL},
     {"durv_batched", NULL, js_durv, NULL, NULL, NULL, napi_default, NULL},

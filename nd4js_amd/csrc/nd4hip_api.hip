@@ -792,6 +792,63 @@ extern "C" int nd4hip_dsyevx_tr_batched_dev(nd4hip_handle* h, int64_t batch, int
   return 0;
 }
 
+// ---- the eigenpairs in a value interval (syevx.hip). The argument checks come first: they need no handle. How many
+// values an interval holds is not known when the profile opens: it counts the reduction and the two Sturm counts per member.
+namespace {
+// `run(b0, nb, &kmax_of_the_chunk)` for every chunk of the batch; *kmax is the largest; where the chunks found different kmax the
+// padding of every member is extended to it
+template <class Run>
+int interval_chunks(nd4hip_handle* h, int64_t batch, int64_t N, int64_t kcap, const int32_t* range, double* lambda, double* vectors, bool by_rows,
+                    int64_t* kmax, Run run) {
+  int64_t km = 0; bool uneven = false;
+  *kmax = 0;
+  ND4_FOR_CHUNKS(batch) {
+    int64_t kc = 0;
+    ND4_TRY(run(b0, nb, &kc));
+    uneven = uneven || (b0 > 0 && kc != km);
+    km = kc > km ? kc : km;
+  }
+  *kmax = km;
+  if (uneven) {
+    ND4_TRY(nd4_stxv_pad(h, batch, N, kcap, km, range, lambda, vectors, by_rows));
+    ND4_HIP(hipStreamSynchronize(h->stream));
+  }
+  return 0;
+}
+int syevxv_dev(nd4hip_handle* h, bool tridiag, int64_t batch, int64_t N, int64_t kcap, const double* bounds, const double* S, double* lambda,
+               double* V, int32_t* range, int64_t* kmax) {
+  ND4_ARGS(nd4_args_syevxv(tridiag, batch, N, kcap, bounds, S, lambda, range, kmax));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_%s: NULL handle", tridiag ? "dsyevxv_tr_batched" : "dsyevxv_batched");
+  Nd4DeviceGuard guard(h);
+  const double n2 = (double)N * N;
+  Nd4Prof prof(h, tridiag ? "dsyevxv_tr_batched" : "dsyevxv_batched", batch * ((tridiag ? 4.0 : 10.0) / 3.0 * n2 * N + 6.0 * N),
+               8.0 * batch * (double)(N * N / 2 + 2) + 8.0 * batch);
+  return interval_chunks(h, batch, N, kcap, range, lambda, V, false, kmax, [&](int64_t b0, int64_t nb, int64_t* kc) {
+    return nd4_syevxv(h, tridiag, nb, N, kcap, bounds + 2 * b0, S + b0 * N * N, lambda + b0 * kcap, V ? V + b0 * N * kcap : nullptr, range + 2 * b0, kc);
+  });
+}
+}  // namespace
+extern "C" int nd4hip_dstevxv_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, int64_t kcap, const double* bounds, const double* d,
+                                          const double* e, double* lambda, double* Z, int32_t* range, int64_t* kmax) {
+  ND4_ARGS(nd4_args_stevxv(batch, N, kcap, bounds, d, e, lambda, range, kmax));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dstevxv_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "dstevxv_batched", 6.0 * batch * (double)N, 8.0 * batch * (double)(2 * N + 2) + 8.0 * batch);
+  const int64_t ne = N > 1 ? N - 1 : 0;
+  return interval_chunks(h, batch, N, kcap, range, lambda, Z, true, kmax, [&](int64_t b0, int64_t nb, int64_t* kc) {
+    return nd4_stevxv(h, nb, N, kcap, bounds + 2 * b0, d + b0 * N, e ? e + b0 * ne : nullptr, lambda + b0 * kcap, Z ? Z + b0 * kcap * N : nullptr,
+                      range + 2 * b0, kc);
+  });
+}
+extern "C" int nd4hip_dsyevxv_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, int64_t kcap, const double* bounds, const double* S,
+                                          double* lambda, double* V, int32_t* range, int64_t* kmax) {
+  return syevxv_dev(h, false, batch, N, kcap, bounds, S, lambda, V, range, kmax);
+}
+extern "C" int nd4hip_dsyevxv_tr_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, int64_t kcap, const double* bounds, const double* S,
+                                             double* lambda, double* V, int32_t* range, int64_t* kmax) {
+  return syevxv_dev(h, true, batch, N, kcap, bounds, S, lambda, V, range, kmax);
+}
+
 // ---- eigen_sym_gen / eigenvals_sym_gen (sygv.hip). Flops: the solver's count above, (1/3 + 2) N^3 for L = chol(B) and the two
 // triangular solves of C = L^-1 A L^-T, N^3 for X = L^-T Y
 int nd4_sygvd_run(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B, int64_t strideB, double* lambda,
@@ -809,6 +866,27 @@ int nd4_sygvd_run(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const do
 extern "C" int nd4hip_dsygvd_batched_dev(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B,
                                          int64_t strideB, double* lambda, double* X, int32_t* sweeps) {
   return nd4_sygvd_run(h, algo, batch, N, A, B, strideB, lambda, X, sweeps, 0);
+}
+// the same with the selectors of step 3 (nd4_sygvx). Flops as above for what is known when the profile opens: the reduction of C
+// by either route, the solver's 2 N^3 (+ 2 N^3 with X) for select 0, 2 N^2 k for the vectors of a subset
+int nd4_sygvx_run(nd4hip_handle* h, int reduction, int select, int64_t batch, int64_t N, int64_t i0, int64_t i1, int64_t kcap,
+                  const double* bounds, const double* A, const double* B, int64_t strideB, double* lambda, double* X, int32_t* range,
+                  int64_t* kmax, int64_t member0) {
+  ND4_ARGS(nd4_args_sygvx(reduction, select, batch, N, i0, i1, kcap, bounds, A, B, strideB, lambda, range, kmax));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dsygvx_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  const double n3 = (double)N * N * N, k = select == 1 ? (double)(i1 - i0) : 0.0;
+  const double solver = (reduction ? 4.0 : 10.0) / 3.0 + (select == 0 ? 2.0 + (X ? 2.0 : 0.0) : X ? 3.0 * k / N : 0.0);
+  Nd4Prof prof(h, "dsygvx_batched", batch * ((solver + 1.0 / 3.0 + 2.0) * n3),
+               8.0 * ((double)(batch + (strideB ? batch : 1)) * (double)(N * N / 2) + batch * (double)N));
+  const Nd4SygvSel sel{reduction, select, select == 1 ? i0 : 0, select == 1 ? i1 : 0, select == 2 ? kcap : 0, select == 2 ? bounds : nullptr,
+                       select == 2 ? range : nullptr, select == 2 ? kmax : nullptr};
+  return nd4_sygvx(h, 0, sel, batch, N, A, B, strideB, lambda, X, nullptr, member0);
+}
+extern "C" int nd4hip_dsygvx_batched_dev(nd4hip_handle* h, int reduction, int select, int64_t batch, int64_t N, int64_t i0, int64_t i1,
+                                         int64_t kcap, const double* bounds, const double* A, const double* B, int64_t strideB,
+                                         double* lambda, double* X, int32_t* range, int64_t* kmax) {
+  return nd4_sygvx_run(h, reduction, select, batch, N, i0, i1, kcap, bounds, A, B, strideB, lambda, X, range, kmax, 0);
 }
 extern "C" int nd4hip_dsygst_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, const double* L, int64_t strideL,
                                          double* C) {

@@ -251,6 +251,57 @@ inline int nd4_args_stevx(int64_t batch, int64_t N, int64_t i0, int64_t i1, cons
 inline int nd4_args_syevx(int64_t batch, int64_t N, int64_t i0, int64_t i1, const void* S, const void* lambda) {
   return nd4_args_subset("dsyevx_batched", batch, N, i0, i1, {S, lambda});
 }
+// ---- eigenpairs in a value interval (syevx.hip): bounds [batch, 2] = (lo, hi), lambda [batch, kcap], range
+// [batch, 2] and the host word kmax are needed; the vectors are optional. `op`: dstevxv_batched (`e`: its off-diagonal, not read for
+// N = 1), dsyevxv_batched or dsyevxv_tr_batched (e = NULL). An empty call writes neither range nor kmax.
+inline int nd4_args_interval(const char* op, int64_t batch, int64_t N, int64_t kcap, const void* bounds, const void* in, const void* e,
+                             bool needs_e, const void* lambda, const void* range, const void* kmax) {
+  ND4_CHECK_ARG(batch >= 0 && N >= 0 && kcap >= 0, "nd4hip_%s: negative extent", op);
+  ND4_CHECK_ARG(N <= 2048, "nd4hip_%s: N <= 2048", op);
+  if (batch == 0 || N == 0) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(bounds && in && (e || !needs_e || N < 2) && range && kmax && (lambda || kcap == 0), "nd4hip_%s: NULL pointer", op);
+  return ND4_ARGS_GO;
+}
+inline int nd4_args_stevxv(int64_t batch, int64_t N, int64_t kcap, const void* bounds, const void* d, const void* e, const void* lambda,
+                           const void* range, const void* kmax) {
+  return nd4_args_interval("dstevxv_batched", batch, N, kcap, bounds, d, e, true, lambda, range, kmax);
+}
+inline int nd4_args_syevxv(bool tridiag, int64_t batch, int64_t N, int64_t kcap, const void* bounds, const void* S, const void* lambda,
+                           const void* range, const void* kmax) {
+  return nd4_args_interval(tridiag ? "dsyevxv_tr_batched" : "dsyevxv_batched", batch, N, kcap, bounds, S, nullptr, false, lambda, range, kmax);
+}
+// the bounds where they are host memory (the _host forms): NaN and lo > hi are refused; +-Infinity is a bound like any other
+inline int nd4_args_bounds(const char* op, int64_t batch, const double* bounds) {
+  for (int64_t b = 0; b < batch; ++b) {
+    const double lo = bounds[2 * b], hi = bounds[2 * b + 1];
+    ND4_CHECK_ARG(lo == lo && hi == hi, "nd4hip_%s: interval contains NaN", op);
+    ND4_CHECK_ARG(lo <= hi, "nd4hip_%s: interval must satisfy lo <= hi", op);
+  }
+  return ND4_ARGS_GO;
+}
+// the ranges read back after the count, range [batch, 2] = (i0_b, i1_b) on the host: *kmax = max_b(i1_b - i0_b). lo > hi in device
+// memory shows here as i1_b < i0_b
+inline int nd4_interval_kmax(const char* op, int64_t batch, int64_t N, const int32_t* range, int64_t* kmax) {
+  int64_t km = 0;
+  for (int64_t b = 0; b < batch; ++b) {
+    const int64_t i0 = range[2 * b], i1 = range[2 * b + 1];
+    ND4_CHECK_ARG(0 <= i0 && i0 <= i1 && i1 <= N, "nd4hip_%s: interval must satisfy lo <= hi", op);
+    km = i1 - i0 > km ? i1 - i0 : km;
+  }
+  *kmax = km;
+  return ND4_ARGS_GO;
+}
+inline int nd4_args_kcap(const char* op, int64_t kcap, int64_t kmax) {
+  ND4_CHECK_ARG(kcap >= kmax, "nd4hip_%s: kcap = %lld is less than the %lld eigenvalues a member has in its interval", op, (long long)kcap,
+                (long long)kmax);
+  return ND4_ARGS_GO;
+}
+// the grids of a call with k values per member (syevx.hip): workgroups of stx_bisect per member, of stx_factor_solve, and of
+// stx_ragged over `rows` rows
+inline int64_t nd4_stx_bisect_blocks(int64_t k) { return (k + 255) / 256; }
+inline int64_t nd4_stx_solve_blocks(int64_t batch, int64_t k) { return (batch * k + 63) / 64; }
+inline int64_t nd4_stx_ragged_blocks(int64_t batch, int64_t rows, int64_t k) { return (batch * rows * k + 255) / 256; }
+
 // ---- symmetric tridiagonal reduction, its Q, and the eigen routes on it (sytrd.hip): tau and e have no entry for N = 1; V is optional
 inline int nd4_args_sytrd(int64_t batch, int64_t N, const void* S, const void* F, const void* tau, const void* d, const void* e) {
   ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsytrd_batched: negative extent");
@@ -285,6 +336,21 @@ inline int nd4_args_sygvd(int algo, int64_t batch, int64_t N, const void* A, con
   ND4_CHECK_ARG(strideB == 0 || strideB == N * N, "nd4hip_dsygvd_batched: strideB must be N*N or 0");
   if (batch == 0 || N == 0) return ND4_ARGS_EMPTY;
   ND4_CHECK_ARG(A && B && lambda, "nd4hip_dsygvd_batched: NULL pointer");
+  return ND4_ARGS_GO;
+}
+// eigen_sym_gen with a selector (divide & conquer side only): reduction 0 / 1, select 0 (all), 1 (subset (i0, i1)) or 2 (interval:
+// bounds, kcap, range and kmax as the interval forms above); what a select does not use is not looked at
+inline int nd4_args_sygvx(int reduction, int select, int64_t batch, int64_t N, int64_t i0, int64_t i1, int64_t kcap, const void* bounds,
+                          const void* A, const void* B, int64_t strideB, const void* lambda, const void* range, const void* kmax) {
+  ND4_CHECK_ARG(reduction == 0 || reduction == 1, "nd4hip_dsygvx_batched: reduction must be 0 (hessenberg) or 1 (tridiag)");
+  ND4_CHECK_ARG(select >= 0 && select <= 2, "nd4hip_dsygvx_batched: select must be 0 (all), 1 (subset) or 2 (interval)");
+  ND4_CHECK_ARG(batch >= 0 && N >= 0 && (select != 2 || kcap >= 0), "nd4hip_dsygvx_batched: negative extent");
+  ND4_CHECK_ARG(select != 1 || (0 <= i0 && i0 <= i1 && i1 <= N), "nd4hip_dsygvx_batched: subset must satisfy 0 <= i0 <= i1 <= N");
+  ND4_CHECK_ARG(N <= 2048, "nd4hip_dsygvx_batched: N <= 2048");
+  ND4_CHECK_ARG(strideB == 0 || strideB == N * N, "nd4hip_dsygvx_batched: strideB must be N*N or 0");
+  if (batch == 0 || N == 0 || (select == 1 && i0 == i1)) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(A && B && (lambda || (select == 2 && kcap == 0)) && (select != 2 || (bounds && range && kmax)),
+                "nd4hip_dsygvx_batched: NULL pointer");
   return ND4_ARGS_GO;
 }
 inline int nd4_args_sygst(int64_t batch, int64_t N, const void* A, const void* L, int64_t strideL, const void* C) {

@@ -1025,6 +1025,102 @@ extern "C" int nd4hip_dsyevx_tr_batched_host(nd4hip_handle* h, int64_t batch, in
   return run_host(h, batch, ops, fn);
 }
 
+// The eigenpairs in a value interval (syevx.hip). bounds, the inputs and range travel through the driver. lambda and
+// the vectors do not: a chunk computes them into kcap-wide staging of its own and brings down the kmax columns it found, no more,
+// straight to their place in the caller's arrays. The padding up to the kmax of the whole call is then written on the host, from
+// range. bounds are host memory here, so NaN and lo > hi are refused before anything is moved.
+namespace {
+struct IntervalCall {
+  int64_t N, kcap;
+  double *lambda, *vectors;          // the caller's; vectors may be NULL
+  bool by_rows;                      // vectors [batch, kcap, N] (dstevxv), else [batch, N, kcap]
+  std::atomic<int64_t> kmax{0};      // the largest of the chunks, which may run on several threads
+};
+// kc columns of nb members: from kcap-wide device staging to the same columns of the kcap-wide host array `host` (the chunk's part)
+int interval_download(nd4hip_handle* hd, int64_t nb, int64_t rows, int64_t kcap, int64_t kc, bool by_rows, const void* dev, double* host) {
+  if (kc == 0) return 0;
+  if (kc == kcap) { ND4_HIP(hipMemcpyAsync(host, dev, (size_t)(nb * rows * kcap) * D, hipMemcpyDeviceToHost, hd->stream)); return 0; }
+  const size_t unit = (size_t)(by_rows ? rows : 1) * D, height = (size_t)(by_rows ? nb : nb * rows);
+  ND4_HIP(hipMemcpy2DAsync(host, (size_t)kcap * unit, dev, (size_t)kcap * unit, (size_t)kc * unit, height, hipMemcpyDeviceToHost, hd->stream));
+  return 0;
+}
+// one chunk: `dev_call(lambda_dev, vectors_dev, &kc)` runs the _dev form on the staging, then the kc columns come down
+template <class DevCall> int interval_chunk(nd4hip_handle* hd, int64_t nb, IntervalCall* c, DevCall dev_call) {
+  const int64_t first = g_chunk_first;
+  DevBuf dl, dv;
+  ND4_TRY(dl.alloc(hd, (size_t)(nb * c->kcap) * D));
+  if (c->vectors) ND4_TRY(dv.alloc(hd, (size_t)(nb * c->N * c->kcap) * D));
+  int64_t kc = 0;
+  ND4_TRY(dev_call(static_cast<double*>(dl.p), c->vectors ? static_cast<double*>(dv.p) : nullptr, &kc));
+  ND4_TRY(interval_download(hd, nb, 1, c->kcap, kc, false, dl.p, c->lambda + first * c->kcap));
+  if (c->vectors) ND4_TRY(interval_download(hd, nb, c->N, c->kcap, kc, c->by_rows, dv.p, c->vectors + first * c->N * c->kcap));
+  ND4_HIP(hipStreamSynchronize(hd->stream));                 // before the staging goes back to the cache
+  int64_t seen = c->kmax.load();
+  while (kc > seen && !c->kmax.compare_exchange_weak(seen, kc)) {}
+  return 0;
+}
+// NaN / zeros in the columns k_b .. kmax - 1 of every member, on the host
+void interval_pad(const IntervalCall& c, int64_t batch, const int32_t* range, int64_t kmax) {
+  for (int64_t b = 0; b < batch; ++b) {
+    const int64_t kb = range[2 * b + 1] - range[2 * b];
+    for (int64_t j = kb; j < kmax; ++j) {
+      c.lambda[b * c.kcap + j] = std::nan("");
+      if (!c.vectors) continue;
+      if (c.by_rows) std::fill_n(c.vectors + (b * c.kcap + j) * c.N, c.N, 0.0);
+      else for (int64_t i = 0; i < c.N; ++i) c.vectors[(b * c.N + i) * c.kcap + j] = 0.0;
+    }
+  }
+}
+int syevxv_host(nd4hip_handle* h, bool tridiag, int64_t batch, int64_t N, int64_t kcap, const double* bounds, const double* S, double* lambda,
+                double* V, int32_t* range, int64_t* kmax) {
+  const char* op = tridiag ? "dsyevxv_tr_batched" : "dsyevxv_batched";
+  ND4_ARGS(nd4_args_syevxv(tridiag, batch, N, kcap, bounds, S, lambda, range, kmax));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_%s: NULL handle", op);
+  ND4_TRY(nd4_args_bounds(op, batch, bounds));
+  IntervalCall call{N, kcap, lambda, V, false};
+  // the operands in the order bounds, S, range
+  std::vector<Operand> ops{in_op(bounds, 2, 2), in_op(S, N * N, N * N), out_op(range, 2, 4)};
+  ChunkFn fn = [=, &call](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return interval_chunk(hd, nb, &call, [=](double* ld, double* vd, int64_t* kc) {
+      return (tridiag ? nd4hip_dsyevxv_tr_batched_dev : nd4hip_dsyevxv_batched_dev)(hd, nb, N, kcap, P(p, 0), P(p, 1), ld, vd,
+                                                                                  static_cast<int32_t*>(p[2]), kc);
+    });
+  };
+  ND4_TRY(run_host(h, batch, ops, fn));
+  *kmax = call.kmax.load();
+  interval_pad(call, batch, range, *kmax);
+  return 0;
+}
+}  // namespace
+extern "C" int nd4hip_dstevxv_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t kcap, const double* bounds, const double* d,
+                                           const double* e, double* lambda, double* Z, int32_t* range, int64_t* kmax) {
+  ND4_ARGS(nd4_args_stevxv(batch, N, kcap, bounds, d, e, lambda, range, kmax));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dstevxv_batched: NULL handle");
+  ND4_TRY(nd4_args_bounds("dstevxv_batched", batch, bounds));
+  IntervalCall call{N, kcap, lambda, Z, true};
+  // the operands in the order bounds, d, range, [e]
+  std::vector<Operand> ops{in_op(bounds, 2, 2), in_op(d, N, N), out_op(range, 2, 4)};
+  const int ie = N >= 2 ? (int)ops.size() : -1;
+  if (N >= 2) ops.push_back(in_op(e, N - 1, N - 1));
+  ChunkFn fn = [=, &call](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return interval_chunk(hd, nb, &call, [=](double* ld, double* zd, int64_t* kc) {
+      return nd4hip_dstevxv_batched_dev(hd, nb, N, kcap, P(p, 0), P(p, 1), ie >= 0 ? P(p, ie) : nullptr, ld, zd, static_cast<int32_t*>(p[2]), kc);
+    });
+  };
+  ND4_TRY(run_host(h, batch, ops, fn));
+  *kmax = call.kmax.load();
+  interval_pad(call, batch, range, *kmax);
+  return 0;
+}
+extern "C" int nd4hip_dsyevxv_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t kcap, const double* bounds, const double* S,
+                                           double* lambda, double* V, int32_t* range, int64_t* kmax) {
+  return syevxv_host(h, false, batch, N, kcap, bounds, S, lambda, V, range, kmax);
+}
+extern "C" int nd4hip_dsyevxv_tr_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t kcap, const double* bounds, const double* S,
+                                              double* lambda, double* V, int32_t* range, int64_t* kmax) {
+  return syevxv_host(h, true, batch, N, kcap, bounds, S, lambda, V, range, kmax);
+}
+
 // eigen_sym_gen / eigenvals_sym_gen (sygv.hip); X = NULL: the values alone; sweeps = NULL: not wanted; strideB = 0: one B, uploaded
 // once per device
 extern "C" int nd4hip_dsygvd_batched(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B, int64_t strideB,
@@ -1041,6 +1137,41 @@ extern "C" int nd4hip_dsygvd_batched(nd4hip_handle* h, int algo, int64_t batch, 
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) {
     return nd4_sygvd_run(hd, algo, nb, N, P(d, 0), P(d, 1), strideB, P(d, 2), ix >= 0 ? P(d, ix) : nullptr,
                          is >= 0 ? static_cast<int32_t*>(d[is]) : nullptr, g_chunk_first);
+  };
+  return run_host(h, batch, ops, fn);
+}
+
+// the same with the selectors of step 3. select 0 and 1 are plain operands; select 2 is an interval call (see IntervalCall above):
+// lambda and X stay out of the driver and come down kmax columns wide
+extern "C" int nd4hip_dsygvx_batched_host(nd4hip_handle* h, int reduction, int select, int64_t batch, int64_t N, int64_t i0, int64_t i1,
+                                     int64_t kcap, const double* bounds, const double* A, const double* B, int64_t strideB, double* lambda,
+                                     double* X, int32_t* range, int64_t* kmax) {
+  ND4_ARGS(nd4_args_sygvx(reduction, select, batch, N, i0, i1, kcap, bounds, A, B, strideB, lambda, range, kmax));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dsygvx_batched: NULL handle");
+  if (select == 2) {
+    ND4_TRY(nd4_args_bounds("dsygvx_batched", batch, bounds));
+    IntervalCall call{N, kcap, lambda, X, false};
+    // the operands in the order bounds, A, B, range
+    std::vector<Operand> ops{in_op(bounds, 2, 2), in_op(A, N * N, N * N), in_op(B, N * N, strideB), out_op(range, 2, 4)};
+    ChunkFn fn = [=, &call](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+      const int64_t first = g_chunk_first;
+      return interval_chunk(hd, nb, &call, [=](double* ld, double* xd, int64_t* kc) {
+        return nd4_sygvx_run(hd, reduction, 2, nb, N, 0, 0, kcap, P(p, 0), P(p, 1), P(p, 2), strideB, ld, xd, static_cast<int32_t*>(p[3]), kc, first);
+      });
+    };
+    ND4_TRY(run_host(h, batch, ops, fn));
+    *kmax = call.kmax.load();
+    interval_pad(call, batch, range, *kmax);
+    return 0;
+  }
+  const int64_t K = select == 1 ? i1 - i0 : N;
+  // the operands that are wanted, in the order A, B, lambda, [X]
+  std::vector<Operand> ops{in_op(A, N * N, N * N), in_op(B, N * N, strideB), out_op(lambda, K)};
+  const int ix = X ? (int)ops.size() : -1;
+  if (X) ops.push_back(out_op(X, N * K));
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return nd4_sygvx_run(hd, reduction, select, nb, N, i0, i1, 0, nullptr, P(p, 0), P(p, 1), strideB, P(p, 2), ix >= 0 ? P(p, ix) : nullptr, nullptr,
+                         nullptr, g_chunk_first);
   };
   return run_host(h, batch, ops, fn);
 }

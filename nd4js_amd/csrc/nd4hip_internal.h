@@ -185,6 +185,15 @@ int nd4_syevj(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, doubl
 int nd4_stcnt(nd4hip_handle* h, int64_t batch, int64_t N, int64_t M, const double* d, const double* e, const double* x, int32_t* count);
 int nd4_stevx(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* d, const double* e, double* lambda, double* Z);
 int nd4_syevx(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* S, double* lambda, double* V);
+// the eigenpairs in a value interval (syevx.hip): bounds [batch, 2] = (lo, hi) and range [batch, 2] on the device,
+// *kmax on the host; lambda [batch, kcap], Z [batch, kcap, N] rows = vectors, V [batch, N, kcap] columns = vectors, either may be
+// NULL. Both synchronise. nd4_stxv_pad: NaN / zeros in the columns k_b .. kmax - 1 of every member (any batch); enqueues only
+int nd4_stevxv(nd4hip_handle* h, int64_t batch, int64_t N, int64_t kcap, const double* bounds, const double* d, const double* e, double* lambda,
+               double* Z, int32_t* range, int64_t* kmax);
+int nd4_syevxv(nd4hip_handle* h, bool tridiag, int64_t batch, int64_t N, int64_t kcap, const double* bounds, const double* S, double* lambda,
+               double* V, int32_t* range, int64_t* kmax);
+int nd4_stxv_pad(nd4hip_handle* h, int64_t batch, int64_t N, int64_t kcap, int64_t kmax, const int32_t* range, double* lambda, double* vectors,
+                 bool by_rows);
 // symmetric tridiagonal reduction and its Q (sytrd.hip): arguments already checked, batch in 1 .. 32768, 1 <= N <= 2048, K >= 1.
 // nd4_sytrd_run synchronises (one flag word), nd4_ormtr (Z [batch, N, K] in place) enqueues only. The four functions after them are
 // the host-side arithmetic of the tiers: 0 = one workgroup per member in LDS, 1 = one launch per column.
@@ -202,6 +211,16 @@ int nd4_syevx_tr(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t
 int nd4_sygvd(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B, int64_t sB, double* lambda,
               double* X, int32_t* sweeps, int64_t member0);
 int nd4_sygst(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, const double* L, int64_t sL, double* C);
+// eigen_sym_gen with subset, interval or reduction: what step 3 computes of C = L^-1 A L^-T. reduction 1: nd4_sytrd in
+// place of the Hessenberg reduction. select 0: every eigenpair (lambda [batch, N], X [batch, N, N]); 1: the subset (i0, i1) (K = i1 - i0
+// wide); 2: the interval bounds [batch, 2] of every member, kcap wide and ragged, with range [batch, 2] and *kmax as nd4_syevxv's.
+// Fields that a select does not use are 0 / NULL.
+struct Nd4SygvSel { int reduction, select; int64_t i0, i1, kcap; const double* bounds; int32_t* range; int64_t* kmax; };
+int nd4_sygvx(nd4hip_handle* h, int algo, const Nd4SygvSel& sel, int64_t batch, int64_t N, const double* A, const double* B, int64_t sB,
+              double* lambda, double* X, int32_t* sweeps, int64_t member0);
+int nd4_sygvx_run(nd4hip_handle* h, int reduction, int select, int64_t batch, int64_t N, int64_t i0, int64_t i1, int64_t kcap,
+                  const double* bounds, const double* A, const double* B, int64_t strideB, double* lambda, double* X, int32_t* range,
+                  int64_t* kmax, int64_t member0);
 // the _dev entry point of eigen_sym_gen with member0 (for the host-pointer form, as nd4_sytrf_bk_run)
 int nd4_sygvd_run(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B, int64_t strideB, double* lambda,
                   double* X, int32_t* sweeps, int64_t member0);

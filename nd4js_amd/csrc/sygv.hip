@@ -13,7 +13,8 @@
 //                      is replaced in place by column c of C = L^-1 W^T, so the tile ends up holding C^T and no third tile is needed.
 //                      L and the lower triangle of C (exact zeros above it) go to the workspace; a radicand that is not a finite
 //                      number > 0 raises bit 1 of the member's flag, a non-finite entry of C's lower triangle bit 2.
-//   sygv_back_small    X = L^-T Y in place on X, L and Y in LDS, lane c owning column c (backward substitution).
+//   sygv_back_small    X = L^-T Y in place on X, L and Y in LDS, lane c owning column c (backward substitution); Y may have fewer
+//                      than N columns (k of them, in rows ldx apart): the selected eigenvectors of nd4_sygvx.
 // A broadcast B (strideB = 0) is factorised once per call by a pass of its own (sygv_chol_small, the same device function); the
 // members then read L from the workspace.
 // The order of every operation is that of the numpy model in tests/sygv_common.py, and the file is built without FMA contraction:
@@ -24,7 +25,7 @@
 // so the device returns the model's bits. 2 * 64 * 65 doubles are 66 560 bytes: dynamic LDS, sized by N (1 152 bytes at N = 8).
 //
 // Large tier, 64 < N <= 2048: nd4_potrf, a mirror of A's lower triangle, nd4_trsm, nd4_transpose, nd4_trsm, and nd4_trsm_t for
-// step 4; new are only sygv_diag_check (diag(L) finite and > 0 per member: it sees the exact zero in the LAST pivot, which makes no
+// step 4 (on k columns where nd4_sygvx selected k eigenvectors); new are only sygv_diag_check (diag(L) finite and > 0 per member: it sees the exact zero in the LAST pivot, which makes no
 // NaN and which nd4_potrf's flag does not see) and sygv_finish_c (zeros above C's diagonal, bit 2 for a non-finite entry below).
 // Two 2048^2 triangular solves with 2048 right-hand sides cost about 1 ms against 27 ms for the solver: no symmetry-aware reduction.
 #include "nd4hip_internal.h"
@@ -169,26 +170,27 @@ __global__ __launch_bounds__(64) void sygv_reduce_small(const double* __restrict
   }
 }
 
-// X <- L^-T X per member; L stride sL (0 = one for all)
-__global__ __launch_bounds__(64) void sygv_back_small(const double* __restrict__ L, long sL, double* __restrict__ X, int N) {
+// X <- L^-T X per member, on the first k <= N columns of X [N, ldx]; L stride sL (0 = one for all). Lane c < k owns column c: the
+// order of a column's operations does not depend on k
+__global__ __launch_bounds__(64) void sygv_back_small(const double* __restrict__ L, long sL, double* __restrict__ X, int N, int k, long ldx) {
   extern __shared__ __align__(16) double sygv_smem[];
   const int ld = sygv_ld(N), t = threadIdx.x;
   const long mat = blockIdx.x;
   double* Ls = sygv_smem;
   double* Xs = sygv_smem + N * ld;
-  X += mat * N * N;
+  X += mat * N * ldx;
   sygv_load_lower(L + mat * sL, Ls, N, ld, false);
-  for (int e = t; e < N * N; e += 64) { const int i = e / N, j = e - i * N; Xs[i * ld + j] = X[e]; }
+  for (int e = t; e < N * k; e += 64) { const int i = e / k, j = e - i * k; Xs[i * ld + j] = X[i * ldx + j]; }
   __syncthreads();
-  if (t < N) {
+  if (t < k) {
     for (int i = N - 1; i >= 0; --i) {
       double v = Xs[i * ld + t];
-      for (int k = i + 1; k < N; ++k) v = v - Ls[k * ld + i] * Xs[k * ld + t];
+      for (int r = i + 1; r < N; ++r) v = v - Ls[r * ld + i] * Xs[r * ld + t];
       Xs[i * ld + t] = v / Ls[i * ld + i];
     }
   }
   __syncthreads();
-  for (int e = t; e < N * N; e += 64) { const int i = e / N, j = e - i * N; X[e] = Xs[i * ld + j]; }
+  for (int e = t; e < N * k; e += 64) { const int i = e / k, j = e - i * k; X[i * ldx + j] = Xs[i * ld + j]; }
 }
 
 // ---- large tier: the three elementwise kernels beside the existing launchers. grid (tiles of 256 entries, members) ----
@@ -295,7 +297,19 @@ int sygv_verdict(nd4hip_handle* h, const int* flags, int64_t nb, int64_t member0
 // first member in the caller's batch, for the error text. Synchronises.
 int nd4_sygvd(nd4hip_handle* h, int algo, int64_t batch, int64_t N64, const double* A, const double* B, int64_t sB, double* lambda,
               double* X, int32_t* sweeps, int64_t member0) {
+  const Nd4SygvSel all{0, 0, 0, 0, 0, nullptr, nullptr, nullptr};
+  return nd4_sygvx(h, algo, all, batch, N64, A, B, sB, lambda, X, sweeps, member0);
+}
+
+// The same with step 3 chosen by sel (nd4hip_internal.h): the reduction of C, and all of its eigenpairs, the subset (i0, i1) or the
+// interval bounds [batch, 2]. lambda [batch, K] and X [batch, N, K] with K = N, i1 - i0 or kcap; the interval's results are ragged as
+// nd4_syevxv's, with range and *kmax. Steps 1-2, their verdicts and the passes over the batch do not depend on sel; step 4 runs on
+// the columns that step 3 computed: K of them, or the kmax of the pass. sel.select = 0 and sel.reduction = 0 is nd4_sygvd.
+int nd4_sygvx(nd4hip_handle* h, int algo, const Nd4SygvSel& sel, int64_t batch, int64_t N64, const double* A, const double* B, int64_t sB,
+              double* lambda, double* X, int32_t* sweeps, int64_t member0) {
   const int N = (int)N64;
+  const int64_t K = sel.select == 0 ? N64 : sel.select == 1 ? sel.i1 - sel.i0 : sel.kcap;
+  int64_t kmax = 0; bool uneven = false;
   const int64_t nn = N64 * N64;
   const bool small = N <= SYGV_SMALL_N, shared = sB == 0;
   const int64_t chunk = sygv_chunk(batch, N64);
@@ -322,7 +336,8 @@ int nd4_sygvd(nd4hip_handle* h, int algo, int64_t batch, int64_t N64, const doub
   for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
     const int64_t nb = batch - b0 < chunk ? batch - b0 : chunk;
     const double* Ab = A + b0 * nn;
-    double* Xb = X ? X + b0 * nn : nullptr;
+    double* lam = lambda + b0 * K;
+    double* Xb = X ? X + b0 * N64 * K : nullptr;
     ND4_HIP(hipMemsetAsync(flags, 0, sizeof(int) * (size_t)(nb + 1), h->stream));
     if (small) {
       ND4_TRY(sygv_reduce_small_launch(h, nb, N, Ab, shared ? Lw : B + b0 * sB, sB, shared, (shared || !X) ? nullptr : Lw, Cw, flags));
@@ -331,14 +346,38 @@ int nd4_sygvd(nd4hip_handle* h, int algo, int64_t batch, int64_t N64, const doub
       ND4_TRY(sygv_reduce_large(h, nb, N, Ab, Lw, shared ? 0 : nn, Ww, Cw, flags));
     }
     ND4_TRY(sygv_verdict(h, flags, nb, member0 + b0));
-    if (algo == 1) ND4_TRY(nd4_syevj(h, nb, N, Cw, lambda + b0 * N, Xb, sweeps ? sweeps + b0 : nullptr));
-    else           ND4_TRY(nd4_syevd(h, nb, N, Cw, lambda + b0 * N, Xb));
-    if (!Xb) continue;
+    int64_t k = K;                              // the columns of X that step 3 computes
+    if (sel.select == 2) {
+      ND4_TRY(nd4_syevxv(h, sel.reduction != 0, nb, N, sel.kcap, sel.bounds + 2 * b0, Cw, lam, Xb, sel.range + 2 * b0, &k));
+      uneven = uneven || (b0 > 0 && k != kmax);
+      kmax = k > kmax ? k : kmax;
+    } else if (sel.select == 1) {
+      ND4_TRY((sel.reduction ? nd4_syevx_tr : nd4_syevx)(h, nb, N, sel.i0, sel.i1, Cw, lam, Xb));
+    } else if (sel.reduction) ND4_TRY(nd4_syevd_tr(h, nb, N, Cw, lam, Xb));
+    else if (algo == 1)       ND4_TRY(nd4_syevj(h, nb, N, Cw, lam, Xb, sweeps ? sweeps + b0 : nullptr));
+    else                      ND4_TRY(nd4_syevd(h, nb, N, Cw, lam, Xb));
+    if (!Xb || k == 0) continue;
     if (small) {
       ND4_TRY(sygv_small_attr(reinterpret_cast<const void*>(&sygv_back_small), lds));
-      hipLaunchKernelGGL(sygv_back_small, dim3((unsigned)nb), dim3(64), lds, h->stream, Lw, (long)(shared ? 0 : nn), Xb, N);
+      hipLaunchKernelGGL(sygv_back_small, dim3((unsigned)nb), dim3(64), lds, h->stream, Lw, (long)(shared ? 0 : nn), Xb, N, (int)k, (long)K);
       ND4_HIP(hipGetLastError());
-    } else ND4_TRY(nd4_trsm_t(h, nb, N, N, Lw, N, shared ? 0 : nn, Xb, nn));
+    } else if (k == K) {
+      ND4_TRY(nd4_trsm_t(h, nb, N, K, Lw, N, shared ? 0 : nn, Xb, N64 * K));
+    } else {                                    // the kmax columns of an interval, out of kcap: solved in a dense copy
+      Nd4WsScope pass(h);
+      ND4_TRY(nd4_ws_alloc(h, sizeof(double) * (size_t)(nb * N64 * k), &p));
+      double* Xc = static_cast<double*>(p);
+      ND4_TRY(nd4_copy_matrix(h, N, k, Xb, K, Xc, k, nb, N64 * K, N64 * k));
+      ND4_TRY(nd4_trsm_t(h, nb, N, k, Lw, N, shared ? 0 : nn, Xc, N64 * k));
+      ND4_TRY(nd4_copy_matrix(h, N, k, Xc, k, Xb, K, nb, N64 * k, N64 * K));
+    }
+  }
+  if (sel.select == 2) {
+    *sel.kmax = kmax;
+    if (uneven) {                               // the passes found different kmax: the padding of every member reaches the largest
+      ND4_TRY(nd4_stxv_pad(h, batch, N64, sel.kcap, kmax, sel.range, lambda, X, false));
+      ND4_HIP(hipStreamSynchronize(h->stream));
+    }
   }
   return 0;
 }

@@ -751,11 +751,52 @@ def eigenvals(A):
     return L
 
 
-def _syevd(S, what, vectors, algo=None, info=None, subset=None, reduction=None):
-    from .la import _eigsym_algo, _reduction, _subset
+def _interval(interval, lead, what, device):
+    """la._interval on the device: bounds float64 [..., 2] = (lo, hi); lo and hi are numbers, arrays or tensors that broadcast to the
+    leading dimensions. The NaN and lo <= hi checks read one flag back before the call: an interval call through dev synchronises
+    twice, here and at the read-back of the ranges inside the library (the C _dev form alone would see lo > hi only after the count,
+    and a NaN bound not at all: it selects nothing)."""
+    try:
+        lo, hi = interval
+        lo, hi = (torch.as_tensor(x, dtype=torch.float64, device=device) for x in (lo, hi))
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError("%s: interval must be (lo, hi), got %r." % (what, interval)) from None
+    try:
+        bounds = torch.stack((lo.broadcast_to(lead), hi.broadcast_to(lead)), dim=-1).contiguous()
+    except RuntimeError:
+        raise ValueError("%s: interval must broadcast to the leading dimensions %r." % (what, tuple(lead))) from None
+    bad = torch.stack((torch.isnan(bounds).any(), (bounds[..., 0] > bounds[..., 1]).any())).tolist() if bounds.numel() else (False, False)
+    if bad[0]:
+        raise ValueError("%s: interval contains NaN." % what)
+    if bad[1]:
+        raise ValueError("%s: interval must satisfy lo <= hi." % what)
+    return bounds
+
+
+def _interval_call(name, N, bounds, operands, vshape, info):
+    """la._interval_call on the device: (L [..., N], vectors of shape vshape or None, kmax) of the entry point `name` with kcap = N;
+    info['range'] = int32 [..., 2] on the device"""
+    lead, dv = tuple(bounds.shape[:-1]), bounds.device
+    L = torch.empty(lead + (N,), dtype=torch.float64, device=dv)
+    Zs = torch.empty(vshape, dtype=torch.float64, device=dv) if vshape is not None else None
+    ranges = torch.zeros(lead + (2,), dtype=torch.int32, device=dv)
+    kmax = ctypes.c_int64(0)
+    if L.numel():
+        h = _h(bounds)
+        _lib.check(getattr(h.lib, name)(h.ptr, _batch(lead), N, N, _p(bounds), *[_p(a) for a in operands], _p(L),
+                                        _p(Zs) if Zs is not None else None, _p(ranges), ctypes.byref(kmax)))
+    if info is not None:
+        info["range"] = ranges
+    return L, Zs, kmax.value
+
+
+def _syevd(S, what, vectors, algo=None, info=None, subset=None, reduction=None, interval=None):
+    from .la import _eigsym_algo, _interval_what, _reduction, _subset
     jacobi = _eigsym_algo(algo, what)
     tr = _reduction(reduction, what, jacobi)
-    if subset is not None:
+    if interval is not None:
+        what = _interval_what(what, jacobi, subset)
+    elif subset is not None:
         what = what.replace("(S)", "(S, subset)")
         if jacobi:
             _subset(subset, 0, what, True)
@@ -768,6 +809,12 @@ def _syevd(S, what, vectors, algo=None, info=None, subset=None, reduction=None):
     if S.shape[-2] != N:
         raise ValueError("%s: S must be quadratic." % what)
     lead = tuple(S.shape[:-2])
+    if interval is not None:                                                # the same, the subset of each member chosen by value
+        bounds = _interval(interval, lead, what, S.device)
+        L, V, k = _interval_call("nd4hip_dsyevxv_tr_batched_dev" if tr else "nd4hip_dsyevxv_batched_dev", N, bounds, (S,),
+                                 tuple(S.shape) if vectors else None, info)
+        L = L[..., :k].contiguous()
+        return (L, V[..., :k].contiguous()) if vectors else L
     if subset is not None:                                                  # bisection and inverse iteration (csrc/syevx.hip)
         i0, i1 = _subset(subset, N, what)
         L = torch.empty(lead + (i1 - i0,), dtype=torch.float64, device=S.device)
@@ -792,18 +839,21 @@ def _syevd(S, what, vectors, algo=None, info=None, subset=None, reduction=None):
     return (L, V) if vectors else L
 
 
-def eigen_sym(S, algo=None, info=None, subset=None, reduction=None):
+def eigen_sym(S, algo=None, info=None, subset=None, reduction=None, interval=None):
     """device-resident la.eigen_sym: (eigenvalues [..., N] descending, eigenvectors [..., N, N] as columns), float64; only the
     lower triangle of S is read and S is not written. algo='jacobi' (N <= 128): the one-launch Jacobi route; `info` then
     receives 'sweeps', an int32 tensor [...] on the device. subset=(i0, i1): L[i0:i1] and the matching columns alone, [..., k] and
     [..., N, k], by bisection and inverse iteration. reduction='tridiag': the reduction of tridiag_factor and the vectors by
-    tridiag_apply_q in place of the Hessenberg reduction and its U."""
-    return _syevd(S, "eigen_sym(S)", True, algo, info, subset, reduction)
+    tridiag_apply_q in place of the Hessenberg reduction and its U. interval=(lo, hi): the eigenvalues lo < lambda <= hi of every
+    member, ragged: (L [..., kmax], V [..., N, kmax]), NaN and zero columns after a member's own k_b pairs; `info` receives 'range', an
+    int32 tensor [..., 2] on the device. The ranges are read back once inside the call, after one flag for the NaN and lo <= hi checks
+    of the bounds (two synchronisations in all)."""
+    return _syevd(S, "eigen_sym(S)", True, algo, info, subset, reduction, interval)
 
 
-def eigenvals_sym(S, algo=None, info=None, subset=None, reduction=None):
+def eigenvals_sym(S, algo=None, info=None, subset=None, reduction=None, interval=None):
     """device-resident la.eigenvals_sym: the eigenvalues of eigen_sym alone, the same bits"""
-    return _syevd(S, "eigenvals_sym(S)", False, algo, info, subset, reduction)
+    return _syevd(S, "eigenvals_sym(S)", False, algo, info, subset, reduction, interval)
 
 
 def tridiag_factor(S):
@@ -846,10 +896,18 @@ def tridiag_decomp(S):
     return tridiag_apply_q(F, tau, eye), d, e
 
 
-def _stevx(d, e, subset, what, vectors):
-    from .la import _subset, _tridiag_args
+def _stevx(d, e, subset, what, vectors, interval=None, info=None):
+    from .la import _interval_what, _subset, _tridiag_args
+    if interval is not None:
+        what = _interval_what(what, False, subset)
     _chk(d, "d"), _chk(e, "e")
     N = _tridiag_args(d, e, what, lambda a: a.dim(), lambda a: a.shape)
+    if interval is not None:                                                # the subset of each member chosen by value
+        lead = tuple(d.shape[:-1])
+        bounds = _interval(interval, lead, what, d.device)
+        L, Z, k = _interval_call("nd4hip_dstevxv_batched_dev", N, bounds, (d, e), lead + (N, N) if vectors else None, info)
+        L = L[..., :k].contiguous()
+        return (L, Z[..., :k, :].transpose(-1, -2).contiguous()) if vectors else L
     i0, i1 = _subset((0, N) if subset is None else subset, N, what)
     lead = tuple(d.shape[:-1])
     L = torch.empty(lead + (i1 - i0,), dtype=torch.float64, device=d.device)
@@ -860,14 +918,15 @@ def _stevx(d, e, subset, what, vectors):
     return (L, Z.transpose(-1, -2).contiguous()) if vectors else L
 
 
-def tridiag_eigen(d, e, subset=None):
-    """device-resident la.tridiag_eigen: (L [..., k] descending, Z [..., N, k] with the eigenvectors as columns), the same bits"""
-    return _stevx(d, e, subset, "tridiag_eigen(d,e)", True)
+def tridiag_eigen(d, e, subset=None, interval=None, info=None):
+    """device-resident la.tridiag_eigen: (L [..., k] descending, Z [..., N, k] with the eigenvectors as columns), the same bits;
+    interval=(lo, hi) and `info` as in eigen_sym"""
+    return _stevx(d, e, subset, "tridiag_eigen(d,e)", True, interval, info)
 
 
-def tridiag_eigenvals(d, e, subset=None):
+def tridiag_eigenvals(d, e, subset=None, interval=None, info=None):
     """device-resident la.tridiag_eigenvals: the eigenvalues of tridiag_eigen alone, the same bits"""
-    return _stevx(d, e, subset, "tridiag_eigenvals(d,e)", False)
+    return _stevx(d, e, subset, "tridiag_eigenvals(d,e)", False, interval, info)
 
 
 def tridiag_count(d, e, x):
@@ -902,10 +961,41 @@ def _sygv_chk(A, B, what):
     return one
 
 
-def _sygvd(A, B, what, vectors, algo, info):
-    from .la import _eigsym_algo
+def _sygvx(A, B, what, vectors, one_b, tr, subset, interval, info):
+    """la._sygvx on the device: nd4hip_dsygvx_batched_dev"""
+    from .la import _subset
+    N, lead = A.shape[-1], tuple(A.shape[:-2])
+    select, i0, i1, bounds, ranges, kmax = 0, 0, 0, None, None, ctypes.c_int64(0)
+    if interval is not None:
+        select, bounds = 2, _interval(interval, lead, what, A.device)
+        ranges = torch.zeros(lead + (2,), dtype=torch.int32, device=A.device)
+    elif subset is not None:
+        select = 1
+        i0, i1 = _subset(subset, N, what)
+    K = i1 - i0 if select == 1 else N
+    L = torch.empty(lead + (K,), dtype=torch.float64, device=A.device)
+    X = torch.empty(lead + (N, K), dtype=torch.float64, device=A.device) if vectors else None
+    if L.numel():
+        h = _h(A)
+        _lib.check(h.lib.nd4hip_dsygvx_batched_dev(h.ptr, 1 if tr else 0, select, _batch(lead), N, i0, i1, N if select == 2 else 0,
+                                                   _p(bounds) if select == 2 else None, _p(A), _p(B), 0 if one_b else N * N, _p(L),
+                                                   _p(X) if vectors else None, _p(ranges) if select == 2 else None,
+                                                   ctypes.byref(kmax) if select == 2 else None))
+    if select == 2:
+        if info is not None:
+            info["range"] = ranges
+        L = L[..., :kmax.value].contiguous()
+        X = X[..., :kmax.value].contiguous() if vectors else None
+    return (L, X) if vectors else L
+
+
+def _sygvd(A, B, what, vectors, algo, info, subset=None, interval=None, reduction=None):
+    from .la import _eigsym_algo, _sygv_select
     jacobi = _eigsym_algo(algo, what)
+    what, tr = _sygv_select(what, jacobi, subset, interval, reduction)
     one_b = _sygv_chk(A, B, what)
+    if tr or subset is not None or interval is not None:
+        return _sygvx(A, B, what, vectors, one_b, tr, subset, interval, info)
     N = A.shape[-1]
     lead = tuple(A.shape[:-2])
     L = torch.empty(lead + (N,), dtype=torch.float64, device=A.device)
@@ -919,16 +1009,17 @@ def _sygvd(A, B, what, vectors, algo, info):
     return (L, X) if vectors else L
 
 
-def eigen_sym_gen(A, B, algo=None, info=None):
+def eigen_sym_gen(A, B, algo=None, info=None, subset=None, interval=None, reduction=None):
     """device-resident la.eigen_sym_gen: A x = lambda B x with A symmetric and B symmetric positive definite, (eigenvalues [..., N]
     descending, eigenvectors [..., N, N] as columns, X^T B X = I), float64. B has A's shape or is exactly [N, N] (one B for every
-    member, factorised once). Only the lower triangles are read; A and B are not written. The same bits as through la."""
-    return _sygvd(A, B, "eigen_sym_gen(A,B)", True, algo, info)
+    member, factorised once). Only the lower triangles are read; A and B are not written. The same bits as through la. subset,
+    interval and reduction as in la.eigen_sym_gen; info['range'] is an int32 tensor on the device."""
+    return _sygvd(A, B, "eigen_sym_gen(A,B)", True, algo, info, subset, interval, reduction)
 
 
-def eigenvals_sym_gen(A, B, algo=None, info=None):
+def eigenvals_sym_gen(A, B, algo=None, info=None, subset=None, interval=None, reduction=None):
     """device-resident la.eigenvals_sym_gen: the eigenvalues of eigen_sym_gen alone, the same bits"""
-    return _sygvd(A, B, "eigenvals_sym_gen(A,B)", False, algo, info)
+    return _sygvd(A, B, "eigenvals_sym_gen(A,B)", False, algo, info, subset, interval, reduction)
 
 
 def _sygst(A, L):

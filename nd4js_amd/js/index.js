@@ -1455,6 +1455,64 @@ function makeLa(NDA, fallback, SolveError, Complex) {
    * [..., k], and their eigenvectors, [..., N, k], k = i1 - i0, by bisection and inverse iteration (csrc/syevx.hip).
    * opts.reduction: undefined / 'hessenberg' (the default) or 'tridiag' (not with 'jacobi'): the symmetric tridiagonal reduction of
    * csrc/sytrd.hip under either route, the eigenvectors by its reflectors. ---- */
+  /* ---- opts.interval = [lo, hi] (csrc/syevx.hip, DESIGN.md 4.22): the eigenvalues lo < lambda <= hi of every member. lo and hi are
+   * numbers, or arrays / NDArrays with one entry per member in the order of the leading dimensions; lo <= hi, NaN is refused,
+   * +-Infinity is a bound like any other. Results are ragged: [..., kmax] and [..., N, kmax], a member's own k_b pairs first, then
+   * NaN / zero columns. The ranges (i0_b, i1_b) come back as the non-enumerable property `range` of the result (of the [L, V]
+   * array, or of L where the values alone are asked for): int32 [..., 2], of the kind of the operands. An interval that holds no
+   * eigenvalue of any member throws, as the empty subset does: an NDArray has no axis of length 0. ---- */
+  const intervalBounds = (what, interval, batch) => {
+    const bad = () => new Error(`${what}: interval must be [lo, hi] with lo <= hi, numbers or one entry per member.`);
+    if (!(Array.isArray(interval) || ArrayBuffer.isView(interval)) || interval.length !== 2) throw bad();
+    const side = x => {
+      if (typeof x === 'number') return new Float64Array(batch).fill(x);
+      const v = x != null && x.data != null ? x.data : x;
+      if (!(Array.isArray(v) || ArrayBuffer.isView(v)) || (v.length !== batch && v.length !== 1) || Array.from(v).some(t => typeof t !== 'number')) throw bad();
+      return v.length === batch ? Float64Array.from(v) : new Float64Array(batch).fill(v[0]);
+    };
+    const lo = side(interval[0]), hi = side(interval[1]), out = new Float64Array(2 * batch);
+    for (let b = 0; b < batch; b++) {
+      if (Number.isNaN(lo[b]) || Number.isNaN(hi[b])) throw new Error(`${what}: interval contains NaN.`);
+      if (lo[b] > hi[b]) throw new Error(`${what}: interval must satisfy lo <= hi.`);
+      out[2 * b] = lo[b]; out[2 * b + 1] = hi[b];
+    }
+    return out;
+  };
+  // the first k of kcap selected entries into a dense buffer [batch, R, k]; src element (b, r, j) at b sb + r sr + j sj
+  const takeSelected = (dev, src, batch, R, k, sb, sr, sj) => {
+    const out = alloc(dev, batch * R * k);
+    if (dev) gatherBox(out, 0, [R * k, k, 1], src, 0, [sb, sr, sj], [batch, R, k], false);
+    else for (let b = 0; b < batch; b++) for (let r = 0; r < R; r++) for (let j = 0; j < k; j++) out[(b * R + r) * k + j] = src[b * sb + r * sr + j * sj];
+    return out;
+  };
+  const noneSelected = what => new Error(`${what}: the interval holds no eigenvalue of any member, and an NDArray has no axis of length 0.`);
+  const withRange = (result, dev, lead, rg) => {
+    const range = dev ? new DeviceNDArray(Int32Array.from(lead.concat([2])), rg) : new NDA(Int32Array.from(lead.concat([2])), rg);
+    Object.defineProperty(result, 'range', {value: range, writable: true, enumerable: false, configurable: true});
+    return result;
+  };
+  // one interval call with kcap = N and its ragged results cut to kmax: run(bounds, L, V, range) -> kmax; layout of the vectors:
+  // 'cols' [batch, N, kcap] or 'rows' [batch, kcap, N]; both come back as [..., N, kmax]
+  const intervalCall = (what, dev, lead, batch, N, interval, vectors, layout, run) => {
+    const bounds = intervalBounds(what, interval, batch), temps = [];
+    const L = alloc(dev, batch * N), V = vectors ? alloc(dev, batch * N * N) : null, rg = alloc(dev, batch * 2, Int32Array);
+    const drop = () => { if (dev) { L.free(); if (V) V.free(); } };
+    let k, Lk, Vk = null;
+    try {
+      let bd = bounds;
+      if (dev) { bd = DevBuf.from(bounds); temps.push(bd); }
+      k = run(view(bd, 0), view(L, 0), vectors ? view(V, 0) : null, view(rg, 0));
+      if (k === 0) throw noneSelected(what);
+      Lk = takeSelected(dev, L, batch, 1, k, N, 0, 1);
+      if (vectors) Vk = layout === 'cols' ? takeSelected(dev, V, batch, N, k, N * N, N, 1) : takeSelected(dev, V, batch, N, k, N * N, 1, N);
+    }
+    catch (e) { if (dev) rg.free(); drop(); throw e; }
+    finally { release(temps); }
+    drop();
+    const Lw = wrap(dev, lead.concat([k]), Lk);
+    return withRange(vectors ? [Lw, wrap(dev, lead.concat([N, k]), Vk)] : Lw, dev, lead, rg);
+  };
+
   const eigSym = (name, vectors) => {
     const f = function (S, opts) {
       const algo = opts == null ? undefined : opts.algo;
@@ -1471,6 +1529,11 @@ function makeLa(NDA, fallback, SolveError, Complex) {
         if (!(Array.isArray(subset) || ArrayBuffer.isView(subset)) || subset.length !== 2)
           throw new Error(`${name}(S, {subset}): subset must be [i0, i1] with 0 <= i0 <= i1 <= N.`);
       }
+      const interval = opts == null ? undefined : opts.interval;
+      if (interval != null) {
+        if (jac) throw new Error(`${name}(S, {interval}): interval is not available with algo 'jacobi'.`);
+        if (subset != null) throw new Error(`${name}(S, {interval}): interval and subset exclude each other.`);
+      }
       S = asarray(S);
       if (isComplexDev(S) || String(dtypeOf(S)).startsWith('complex')) throw new TypeError(`${name}(S): S.dtype must be float.`);
       if (S.ndim < 2) throw new Error(`${name}(S): S.ndim must be at least 2.`);
@@ -1478,6 +1541,13 @@ function makeLa(NDA, fallback, SolveError, Complex) {
       if (S.shape[nd_ - 2] != N) throw new Error(`${name}(S): S must be quadratic.`);
       if (!gpuOk(S)) throw new TypeError(`${name}(S): dtype ${dtypeOf(S)} is not accelerated.`);
       const batch = prod(S.shape, 0, nd_ - 2), dev = isDev(S), temps = [];
+      if (interval != null) {                      // the same, the subset of each member chosen by value
+        try {
+          const Sd = opF64(S, dev, temps);
+          return intervalCall(`${name}(S, {interval})`, dev, Array.from(S.shape.subarray(0, nd_ - 2)), batch, N, interval, vectors, 'cols',
+                              (bd, L, V, rg) => native().dsyevxv_batched(tr ? 1 : 0, batch, N, N, bd, view(Sd, 0), L, V, rg));
+        } finally { release(temps); }
+      }
       if (subset != null) {                        // bisection and inverse iteration, csrc/syevx.hip
         const [i0, i1] = subset, k = i1 - i0;
         if (!(Number.isInteger(i0) && Number.isInteger(i1) && 0 <= i0 && i0 <= i1 && i1 <= N))
@@ -1517,6 +1587,17 @@ function makeLa(NDA, fallback, SolveError, Complex) {
     const f = function (A, B, opts) {
       const algo = opts == null ? undefined : opts.algo;
       if (algo !== undefined && algo !== null && algo !== 'dc' && algo !== 'jacobi') throw new Error(`${name}(A,B, {algo}): algo must be 'dc' or 'jacobi'.`);
+      // opts.subset, opts.interval and opts.reduction as for eigen_sym, applied to C = L^-1 A L^-T (not with 'jacobi'); the
+      // back-transformation runs on the selected columns; an interval's ranges are the property `range` of the result
+      const reduction = opts == null ? undefined : opts.reduction, subset = opts == null ? undefined : opts.subset, interval = opts == null ? undefined : opts.interval;
+      if (reduction !== undefined && reduction !== null && reduction !== 'hessenberg' && reduction !== 'tridiag')
+        throw new Error(`${name}(A,B, {reduction}): reduction must be 'hessenberg' or 'tridiag'.`);
+      const tr = reduction === 'tridiag';
+      for (const [kw, on] of [['reduction', tr], ['subset', subset != null], ['interval', interval != null]])
+        if (on && algo === 'jacobi') throw new Error(`${name}(A,B, {${kw}}): ${kw} is not available with algo 'jacobi'.`);
+      if (interval != null && subset != null) throw new Error(`${name}(A,B, {interval}): interval and subset exclude each other.`);
+      if (subset != null && (!(Array.isArray(subset) || ArrayBuffer.isView(subset)) || subset.length !== 2))
+        throw new Error(`${name}(A,B, {subset}): subset must be [i0, i1] with 0 <= i0 <= i1 <= N.`);
       A = asarray(A); B = asarray(B);
       for (const [nm, M] of [['A', A], ['B', B]]) {
         if (isComplexDev(M) || String(dtypeOf(M)).startsWith('complex')) throw new TypeError(`${name}(A,B): ${nm}.dtype must be float.`);
@@ -1529,6 +1610,32 @@ function makeLa(NDA, fallback, SolveError, Complex) {
       if (!same && !one) throw new Error(`${name}(A,B): B.shape must be A.shape or A.shape.slice(-2), got [${Array.from(B.shape)}] and [${Array.from(A.shape)}].`);
       if (isDev(A) !== isDev(B)) throw new TypeError(`${name}(A,B): A and B must be both host arrays or both DeviceNDArrays.`);
       const batch = prod(A.shape, 0, nd_ - 2), dev = isDev(A), temps = [], jac = algo === 'jacobi' ? 1 : 0;
+      const lead = Array.from(A.shape.subarray(0, nd_ - 2)), sB = same ? N * N : 0;
+      if (interval != null) {
+        try {
+          const a = view(opF64(A, dev, temps), 0), b = view(opF64(B, dev, temps), 0);
+          return intervalCall(`${name}(A,B, {interval})`, dev, lead, batch, N, interval, vectors, 'cols',
+                              (bd, L, X, rg) => native().dsygvx_batched(tr ? 1 : 0, 2, batch, N, 0, 0, N, bd, a, b, sB, L, X, rg));
+        } finally { release(temps); }
+      }
+      if (subset != null || tr) {
+        let i0 = 0, i1 = N;
+        if (subset != null) {
+          [i0, i1] = subset;
+          if (!(Number.isInteger(i0) && Number.isInteger(i1) && 0 <= i0 && i0 <= i1 && i1 <= N))
+            throw new Error(`${name}(A,B, {subset}): subset must be [i0, i1] with 0 <= i0 <= i1 <= N, got [${i0}, ${i1}] for N = ${N}.`);
+          if (i1 === i0) throw new Error(`${name}(A,B, {subset}): the subset [${i0}, ${i1}] is empty, and an NDArray has no axis of length 0.`);
+        }
+        const k = i1 - i0, Ls = alloc(dev, batch * k), Xs = vectors ? alloc(dev, batch * N * k) : null;
+        try {
+          native().dsygvx_batched(tr ? 1 : 0, subset != null ? 1 : 0, batch, N, i0, i1, 0, null, view(opF64(A, dev, temps), 0), view(opF64(B, dev, temps), 0), sB,
+                                  view(Ls, 0), vectors ? view(Xs, 0) : null, null);
+        }
+        catch (e) { if (dev) { Ls.free(); if (Xs) Xs.free(); } throw e; }
+        finally { release(temps); }
+        const Lsw = wrap(dev, lead.concat([k]), Ls);
+        return vectors ? [Lsw, wrap(dev, lead.concat([N, k]), Xs)] : Lsw;
+      }
       const L = alloc(dev, batch * N), X = vectors ? alloc(dev, batch * N * N) : null;
       try {
         const a = view(opF64(A, dev, temps), 0), b = view(opF64(B, dev, temps), 0);
@@ -1544,6 +1651,73 @@ function makeLa(NDA, fallback, SolveError, Complex) {
     Object.defineProperty(la, name, {value: f, writable: true, enumerable: false, configurable: true});
   };
   eigSymGen('eigen_sym_gen', true); eigSymGen('eigenvals_sym_gen', false);
+
+  /* ---- tridiag_eigen(d, e, opts) / tridiag_eigenvals(d, e, opts) / tridiag_count(d, e, x), csrc/syevx.hip: the symmetric tridiagonal T
+   * with diagonal d [..., N] and off-diagonal e [..., N-1] (N = 1: e is null, an NDArray has no axis of length 0), N <= 2048.
+   * opts.subset = [i0, i1] (default: all) or opts.interval = [lo, hi] as for eigen_sym -> [L [..., k] descending, Z [..., N, k] with the
+   * eigenvectors as columns], resp. L alone; tridiag_count -> int32 [..., M], how many eigenvalues are greater than each x [..., M].
+   * Host arrays or DeviceNDArrays in (all of one kind), the same kind out. Not enumerable, like eigen_sym. ---- */
+  const tridiagArgs = (what, d, e, extra) => {
+    d = asarray(d); e = e == null ? null : asarray(e);
+    const all = [d].concat(e ? [e] : []).concat(extra ? [extra] : []);
+    for (const M of all) {
+      if (isComplexDev(M) || String(dtypeOf(M)).startsWith('complex')) throw new TypeError(`${what}: the operands must be float.`);
+      if (!gpuOk(M)) throw new TypeError(`${what}: dtype ${dtypeOf(M)} is not accelerated.`);
+    }
+    if (all.some(M => isDev(M) !== isDev(d))) throw new TypeError(`${what}: the operands must be all host arrays or all DeviceNDArrays.`);
+    const nd_ = d.ndim, N = d.shape[nd_ - 1], lead = Array.from(d.shape.subarray(0, nd_ - 1));
+    if (N > 2048) throw new Error(`${what}: N <= 2048.`);
+    if (N === 1 ? e != null : (e == null || e.ndim !== nd_ || e.shape[nd_ - 1] !== N - 1 || lead.some((s, i) => s != e.shape[i])))
+      throw new Error(`${what}: e must have the leading dimensions of d and len(d) - 1 entries (null for N = 1).`);
+    return {d, e, N, lead, batch: lead.reduce((p, q) => p * q, 1), dev: isDev(d)};
+  };
+  const tridiagEigen = (name, vectors) => {
+    const f = function (d, e, opts) {
+      const what = `${name}(d,e)`, subset = opts == null ? undefined : opts.subset, interval = opts == null ? undefined : opts.interval;
+      if (interval != null && subset != null) throw new Error(`${what}: interval and subset exclude each other.`);
+      if (subset != null && (!(Array.isArray(subset) || ArrayBuffer.isView(subset)) || subset.length !== 2))
+        throw new Error(`${what}: subset must be [i0, i1] with 0 <= i0 <= i1 <= N.`);
+      const t = tridiagArgs(what, d, e), {N, lead, batch, dev} = t, temps = [];
+      try {
+        const dd = view(opF64(t.d, dev, temps), 0), ee = t.e ? view(opF64(t.e, dev, temps), 0) : null;
+        if (interval != null)
+          return intervalCall(`${what}`, dev, lead, batch, N, interval, vectors, 'rows', (bd, L, Z, rg) => native().dstevxv_batched(batch, N, N, bd, dd, ee, L, Z, rg));
+        const [i0, i1] = subset != null ? subset : [0, N], k = i1 - i0;
+        if (!(Number.isInteger(i0) && Number.isInteger(i1) && 0 <= i0 && i0 <= i1 && i1 <= N))
+          throw new Error(`${what}: subset must be [i0, i1] with 0 <= i0 <= i1 <= N, got [${i0}, ${i1}] for N = ${N}.`);
+        if (k === 0) throw new Error(`${what}: the subset [${i0}, ${i1}] is empty, and an NDArray has no axis of length 0.`);
+        const L = alloc(dev, batch * k), Z = vectors ? alloc(dev, batch * k * N) : null;
+        let Zt = null;
+        try {
+          native().dstevx_batched(batch, N, i0, i1, dd, ee, view(L, 0), vectors ? view(Z, 0) : null);
+          if (vectors) Zt = takeSelected(dev, Z, batch, N, k, k * N, 1, N);      // rows = vectors -> columns
+        }
+        catch (err) { if (dev) L.free(); throw err; }
+        finally { if (dev && Z) Z.free(); }
+        const Lw = wrap(dev, lead.concat([k]), L);
+        return vectors ? [Lw, wrap(dev, lead.concat([N, k]), Zt)] : Lw;
+      } finally { release(temps); }
+    };
+    Object.defineProperty(f, 'name', {value: name});
+    Object.defineProperty(la, name, {value: f, writable: true, enumerable: false, configurable: true});
+  };
+  tridiagEigen('tridiag_eigen', true); tridiagEigen('tridiag_eigenvals', false);
+  const tridiag_count = function (d, e, x) {
+    const what = 'tridiag_count(d,e,x)';
+    x = asarray(x);
+    const t = tridiagArgs(what, d, e, x), {N, lead, batch, dev} = t, temps = [];
+    if (x.ndim !== lead.length + 1 || lead.some((s, i) => s != x.shape[i])) throw new Error(`${what}: x must have the leading dimensions of d.`);
+    const M = x.shape[x.ndim - 1];
+    if (!dev && Array.from(f64(x)).some(Number.isNaN)) throw new Error(`${what}: x contains NaN.`);
+    const count = alloc(dev, batch * M, Int32Array);
+    try {
+      native().dstcnt_batched(batch, N, M, view(opF64(t.d, dev, temps), 0), t.e ? view(opF64(t.e, dev, temps), 0) : null, view(opF64(x, dev, temps), 0), view(count, 0));
+    }
+    catch (err) { if (dev) count.free(); throw err; }
+    finally { release(temps); }
+    return wrap(dev, lead.concat([M]), count);
+  };
+  Object.defineProperty(la, 'tridiag_count', {value: tridiag_count, writable: true, enumerable: false, configurable: true});
 
   // complex128 device arrays are accepted by matmul2 / matmul only: every other function refuses them before it looks at the
   // buffer (which holds 2n doubles, not n float64 entries)

@@ -13,7 +13,10 @@ JS wrapper nd4js_amd/js/index.js over the N-API shim; both call the same libnd4h
                                    reduction='tridiag' (opt-in): the symmetric reduction of csrc/sytrd.hip -> nd4hip_dsyevd_tr_batched_host, nd4hip_dsyevx_tr_batched_host
   tridiag_factor(S), tridiag_apply_q(F, tau, Z), tridiag_decomp(S)   not in the reference   -> nd4hip_dsytrd_batched_host, nd4hip_dormtr_batched_host
   tridiag_eigen(d, e), tridiag_eigenvals(d, e), tridiag_count(d, e, x)   not in the reference   -> nd4hip_dstevx_batched_host, nd4hip_dstcnt_batched_host
+                                   interval=(lo, hi) (opt-in, here and in eigen_sym): the eigenvalues in (lo, hi] -> nd4hip_dstevxv_batched_host,
+                                   nd4hip_dsyevxv_batched_host, nd4hip_dsyevxv_tr_batched_host
   eigen_sym_gen(A, B), eigenvals_sym_gen(A, B)   A x = lambda B x, not in the reference   -> nd4hip_dsygvd_batched
+                                   subset, interval, reduction (opt-in, as eigen_sym's) -> nd4hip_dsygvx_batched_host
 
 Inputs are numpy arrays / nested lists (NDArray analogue: dense, row-major, leading axes = batch).
 Only float64 (and int32 promoted to float64 for QR/LU/SVD, as qr.js:31-37, lu.js:27, svd_dc.js:904
@@ -1148,6 +1151,52 @@ def _subset(subset, N, what, jacobi=False):
     return i0, i1
 
 
+def _interval_what(what, jacobi, subset):
+    """the text that names a call with interval=(lo, hi), after the two refusals that need no operand"""
+    what = what.replace("(S)", "(S, interval)").replace("(d,e)", "(d,e, interval)")
+    if jacobi:
+        raise ValueError("%s: interval is not available with algo='jacobi'." % what)
+    if subset is not None:
+        raise ValueError("%s: interval and subset exclude each other." % what)
+    return what
+
+
+def _interval(interval, lead, what):
+    """bounds float64 [..., 2] = (lo, hi) of interval=(lo, hi), which selects the eigenvalues lo < lambda <= hi: lo and hi are scalars
+    or arrays that broadcast to the leading dimensions `lead`; lo <= hi; NaN is refused, +-inf is a bound like any other"""
+    try:
+        lo, hi = interval
+        lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("%s: interval must be (lo, hi), got %r." % (what, interval)) from None
+    if np.isnan(lo).any() or np.isnan(hi).any():
+        raise ValueError("%s: interval contains NaN." % what)
+    try:
+        lo, hi = np.broadcast_to(lo, lead), np.broadcast_to(hi, lead)
+    except ValueError:
+        raise ValueError("%s: interval must broadcast to the leading dimensions %r." % (what, tuple(lead))) from None
+    if (lo > hi).any():
+        raise ValueError("%s: interval must satisfy lo <= hi." % what)
+    return np.ascontiguousarray(np.stack((lo, hi), axis=-1))
+
+
+def _interval_call(name, device, N, bounds, operands, vshape, info):
+    """the interval entry point `name` with kcap = N: (L [..., N], vectors of shape vshape or None (vshape None), kmax): the first
+    kmax entries along the selected axis are the results; info['range'] = int32 [..., 2]"""
+    lead = bounds.shape[:-1]
+    L = np.empty(lead + (N,))
+    Zs = np.empty(vshape) if vshape is not None else None
+    ranges = np.zeros(lead + (2,), dtype=np.int32)
+    kmax = ctypes.c_int64(0)
+    if L.size:
+        h = _lib.handle(device)
+        _lib.check(getattr(h.lib, name)(h.ptr, int(np.prod(lead, dtype=np.int64)), N, N, _ptr(bounds), *[_ptr(a) for a in operands], _ptr(L),
+                                        _ptr(Zs) if Zs is not None else None, _ptr(ranges), ctypes.byref(kmax)))
+    if info is not None:
+        info["range"] = ranges
+    return L, Zs, kmax.value
+
+
 def _reduction(reduction, what, jacobi):
     """True for reduction='tridiag' (csrc/sytrd.hip, opt-in); None / 'hessenberg' is the default reduction (csrc/hess.hip)"""
     what = what.replace("(S)", "(S, reduction)")
@@ -1160,10 +1209,12 @@ def _reduction(reduction, what, jacobi):
     return True
 
 
-def _syevd(S, what, vectors, device, algo=None, info=None, subset=None, reduction=None):
+def _syevd(S, what, vectors, device, algo=None, info=None, subset=None, reduction=None, interval=None):
     jacobi = _eigsym_algo(algo, what)
     tr = _reduction(reduction, what, jacobi)
-    if subset is not None:
+    if interval is not None:
+        what = _interval_what(what, jacobi, subset)
+    elif subset is not None:
         what = what.replace("(S)", "(S, subset)")
         if jacobi:
             _subset(subset, 0, what, True)
@@ -1177,6 +1228,12 @@ def _syevd(S, what, vectors, device, algo=None, info=None, subset=None, reductio
     S = _asarray(S, what)
     N = S.shape[-1]
     batch = int(np.prod(S.shape[:-2], dtype=np.int64))
+    if interval is not None:                                                # the same, the subset of each member chosen by value
+        bounds = _interval(interval, S.shape[:-2], what)
+        L, V, k = _interval_call("nd4hip_dsyevxv_tr_batched_host" if tr else "nd4hip_dsyevxv_batched_host", device, N, bounds, (S,),
+                                 S.shape if vectors else None, info)
+        L = np.ascontiguousarray(L[..., :k])
+        return (L, np.ascontiguousarray(V[..., :k])) if vectors else L
     if subset is not None:                                                  # bisection and inverse iteration (csrc/syevx.hip)
         i0, i1 = _subset(subset, N, what)
         L = np.empty(S.shape[:-2] + (i1 - i0,))
@@ -1201,7 +1258,7 @@ def _syevd(S, what, vectors, device, algo=None, info=None, subset=None, reductio
     return (L, V) if vectors else L
 
 
-def eigen_sym(S, device=None, algo=None, info=None, subset=None, reduction=None):
+def eigen_sym(S, device=None, algo=None, info=None, subset=None, reduction=None, interval=None):
     """the function the reference plans at eigen.js:28-30: (eigenvalues float64 [..., N] descending, eigenvectors float64
     [..., N, N] as columns) of the symmetric S, S V = V diag(L) and V^T V = I. Only the lower triangle of S is read. NaN or
     Infinity there raises Nd4HipError with code -3. N <= 2048.
@@ -1211,14 +1268,19 @@ def eigen_sym(S, device=None, algo=None, info=None, subset=None, reduction=None)
     subset=(i0, i1) (opt-in, not with 'jacobi'): only L[i0:i1] of the descending spectrum and the matching columns of V, k = i1 - i0
     of them: (L [..., k], V [..., N, k]), by bisection and inverse iteration on the tridiagonal form (tridiag_eigen below).
     reduction='tridiag' (opt-in, not with 'jacobi'; None / 'hessenberg': the default): the tridiagonal form by tridiag_factor below,
-    straight from the lower triangle, and the eigenvectors by tridiag_apply_q, 2 N^2 k flops for k of them."""
-    return _syevd(S, "eigen_sym(S)", True, device, algo, info, subset, reduction)
+    straight from the lower triangle, and the eigenvectors by tridiag_apply_q, 2 N^2 k flops for k of them.
+    interval=(lo, hi) (opt-in, not with subset or 'jacobi'; combines with reduction): the eigenvalues lo < lambda <= hi of every member,
+    lo and hi scalars or arrays that broadcast to the leading dimensions of S, lo <= hi, +-inf allowed, NaN refused. Member b gets
+    subset=(i0_b, i1_b) = (count(hi), count(lo)) with tridiag_count's count on its tridiagonal form, and the bits of that subset call.
+    The results are ragged: (L [..., kmax], V [..., N, kmax]) with kmax the largest k_b = i1_b - i0_b; a member's k_b pairs stand
+    first, then NaN in L and zero columns in V. `info` receives 'range', int32 [..., 2], the (i0_b, i1_b)."""
+    return _syevd(S, "eigen_sym(S)", True, device, algo, info, subset, reduction, interval)
 
 
-def eigenvals_sym(S, device=None, algo=None, info=None, subset=None, reduction=None):
+def eigenvals_sym(S, device=None, algo=None, info=None, subset=None, reduction=None, interval=None):
     """the eigenvalues of eigen_sym alone (the same bits); no eigenvector product is computed or stored. With algo='jacobi' no
-    eigenvector is accumulated at all; with subset no inverse iteration is made; with reduction='tridiag' no Q is applied."""
-    return _syevd(S, "eigenvals_sym(S)", False, device, algo, info, subset, reduction)
+    eigenvector is accumulated at all; with subset or interval no inverse iteration is made; with reduction='tridiag' no Q is applied."""
+    return _syevd(S, "eigenvals_sym(S)", False, device, algo, info, subset, reduction, interval)
 
 
 def _tridiag_s(S_ndim, S_shape, what):
@@ -1304,9 +1366,16 @@ def _tridiag_args(d, e, what, ndim, shape):
     return N
 
 
-def _stevx(d, e, subset, what, vectors, device):
+def _stevx(d, e, subset, what, vectors, device, interval=None, info=None):
+    if interval is not None:
+        what = _interval_what(what, False, subset)
     d, e = _asarray(d, what), _asarray(e, what)
     N = _tridiag_args(d, e, what, lambda a: a.ndim, lambda a: a.shape)
+    if interval is not None:                                                # the subset of each member chosen by value
+        bounds = _interval(interval, d.shape[:-1], what)
+        L, Z, k = _interval_call("nd4hip_dstevxv_batched_host", device, N, bounds, (d, e), d.shape[:-1] + (N, N) if vectors else None, info)
+        L = np.ascontiguousarray(L[..., :k])
+        return (L, np.ascontiguousarray(np.swapaxes(Z[..., :k, :], -1, -2))) if vectors else L
     i0, i1 = _subset((0, N) if subset is None else subset, N, what)
     lead = d.shape[:-1]
     L = np.empty(lead + (i1 - i0,))
@@ -1318,17 +1387,20 @@ def _stevx(d, e, subset, what, vectors, device):
     return (L, np.ascontiguousarray(np.swapaxes(Z, -1, -2))) if vectors else L
 
 
-def tridiag_eigen(d, e, subset=None, device=None):
+def tridiag_eigen(d, e, subset=None, device=None, interval=None, info=None):
     """selected eigenpairs of the symmetric tridiagonal T with diagonal d [..., N] and off-diagonal e [..., N-1], N <= 2048:
     (L [..., k] descending, Z [..., N, k] with the eigenvectors as columns) for subset=(i0, i1), the slice L[i0:i1] of the descending
     spectrum (None: all of it). Bisection on Sturm counts, inverse iteration, Gram-Schmidt inside clusters (csrc/syevx.hip). NaN or
-    Infinity in d or e raises Nd4HipError with code -3."""
-    return _stevx(d, e, subset, "tridiag_eigen(d,e)", True, device)
+    Infinity in d or e raises Nd4HipError with code -3.
+    interval=(lo, hi) in place of subset: the eigenvalues lo < lambda <= hi of every member, as in eigen_sym: (L [..., kmax],
+    Z [..., N, kmax]), member b's k_b pairs first (the bits of subset=(count(hi), count(lo)) with tridiag_count), then NaN and zero
+    columns; `info` (a dict) receives 'range', int32 [..., 2]."""
+    return _stevx(d, e, subset, "tridiag_eigen(d,e)", True, device, interval, info)
 
 
-def tridiag_eigenvals(d, e, subset=None, device=None):
+def tridiag_eigenvals(d, e, subset=None, device=None, interval=None, info=None):
     """the eigenvalues of tridiag_eigen alone (the same bits); no inverse iteration is made"""
-    return _stevx(d, e, subset, "tridiag_eigenvals(d,e)", False, device)
+    return _stevx(d, e, subset, "tridiag_eigenvals(d,e)", False, device, interval, info)
 
 
 def tridiag_count(d, e, x, device=None):
@@ -1365,11 +1437,51 @@ def _sygv_args(A, B, what, is_float64, ndim, shape):
     return sb != sa
 
 
-def _sygvd(A, B, what, vectors, device, algo, info):
+def _sygv_select(what, jacobi, subset, interval, reduction):
+    """(what, tridiag) of an eigen_sym_gen call after the refusals that need no operand, as eigen_sym's"""
+    tr = _reduction(reduction, what, jacobi)
+    if interval is not None:
+        what = _interval_what(what, jacobi, subset)
+    elif subset is not None and jacobi:
+        _subset(subset, 0, what, True)
+    return what, tr
+
+
+def _sygvx(A, B, what, vectors, device, one_b, tr, subset, interval, info):
+    """eigen_sym_gen with subset, interval or reduction='tridiag': nd4hip_dsygvx_batched_host (select 0: all, 1: subset, 2: interval)"""
+    N, lead = A.shape[-1], A.shape[:-2]
+    batch = int(np.prod(lead, dtype=np.int64))
+    select, i0, i1, bounds, ranges, kmax = 0, 0, 0, None, None, ctypes.c_int64(0)
+    if interval is not None:
+        select, bounds, ranges = 2, _interval(interval, lead, what), np.zeros(lead + (2,), dtype=np.int32)
+    elif subset is not None:
+        select = 1
+        i0, i1 = _subset(subset, N, what)
+    K = i1 - i0 if select == 1 else N
+    L = np.empty(lead + (K,))
+    X = np.empty(lead + (N, K)) if vectors else None
+    if L.size:
+        h = _lib.handle(device)
+        _lib.check(h.lib.nd4hip_dsygvx_batched_host(h.ptr, 1 if tr else 0, select, batch, N, i0, i1, N if select == 2 else 0,
+                                               _ptr(bounds) if select == 2 else None, _ptr(A), _ptr(B), 0 if one_b else N * N, _ptr(L),
+                                               _ptr(X) if vectors else None, _ptr(ranges) if select == 2 else None,
+                                               ctypes.byref(kmax) if select == 2 else None))
+    if select == 2:
+        if info is not None:
+            info["range"] = ranges
+        L = np.ascontiguousarray(L[..., :kmax.value])
+        X = np.ascontiguousarray(X[..., :kmax.value]) if vectors else None
+    return (L, X) if vectors else L
+
+
+def _sygvd(A, B, what, vectors, device, algo, info, subset=None, interval=None, reduction=None):
     jacobi = _eigsym_algo(algo, what)
+    what, tr = _sygv_select(what, jacobi, subset, interval, reduction)
     A, B = np.asarray(A), np.asarray(B)
     one_b = _sygv_args(A, B, what, lambda M: not np.iscomplexobj(M), lambda M: M.ndim, lambda M: M.shape)
     A, B = _asarray(A, what), _asarray(B, what)
+    if tr or subset is not None or interval is not None:
+        return _sygvx(A, B, what, vectors, device, one_b, tr, subset, interval, info)
     N = A.shape[-1]
     L = np.empty(A.shape[:-1])
     X = np.empty(A.shape) if vectors else None
@@ -1383,19 +1495,22 @@ def _sygvd(A, B, what, vectors, device, algo, info):
     return (L, X) if vectors else L
 
 
-def eigen_sym_gen(A, B, device=None, algo=None, info=None):
+def eigen_sym_gen(A, B, device=None, algo=None, info=None, subset=None, interval=None, reduction=None):
     """the generalised symmetric-definite eigenproblem A x = lambda B x: (eigenvalues float64 [..., N] descending, eigenvectors
     float64 [..., N, N] as columns) with A X = B X diag(L) and X^T B X = I. A [..., N, N] symmetric; B of the same shape, or exactly
     [N, N]: one B for every member, factorised once. Only the lower triangles of A and B are read; neither is written.
     Route: L = chol(B), C = L^-1 A L^-T, eigen_sym(C, algo) unchanged, X = L^-T Y (csrc/sygv.hip; N <= 64 in two fused kernels).
     algo and info as for eigen_sym (N <= 2048; 'jacobi': N <= 128, info['sweeps']). B not positive definite raises Nd4HipError with
-    code -5 and the lowest such member; NaN or Infinity in A's lower triangle, or overflow of C, code -3."""
-    return _sygvd(A, B, "eigen_sym_gen(A,B)", True, device, algo, info)
+    code -5 and the lowest such member; NaN or Infinity in A's lower triangle, or overflow of C, code -3.
+    subset=(i0, i1), interval=(lo, hi) and reduction='tridiag' (opt-in, not with 'jacobi') are eigen_sym's keywords applied to C:
+    (L [..., k], X [..., N, k]) for a subset, ragged (L [..., kmax], X [..., N, kmax]) with info['range'] for an interval; the
+    back-transformation then runs on the selected columns alone. The errors above keep their codes and members."""
+    return _sygvd(A, B, "eigen_sym_gen(A,B)", True, device, algo, info, subset, interval, reduction)
 
 
-def eigenvals_sym_gen(A, B, device=None, algo=None, info=None):
+def eigenvals_sym_gen(A, B, device=None, algo=None, info=None, subset=None, interval=None, reduction=None):
     """the eigenvalues of eigen_sym_gen alone (the same bits); no back-transformation is computed"""
-    return _sygvd(A, B, "eigenvals_sym_gen(A,B)", False, device, algo, info)
+    return _sygvd(A, B, "eigenvals_sym_gen(A,B)", False, device, algo, info, subset, interval, reduction)
 
 
 def _sygst(A, L, device=None):
