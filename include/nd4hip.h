@@ -559,6 +559,40 @@ int nd4hip_dbdsdc_levels(int64_t n, int32_t* nodes, int64_t capacity);
 #define ND4HIP_DC_STAGES 8
 int nd4hip_dgesdd_last_stages(nd4hip_handle* h, double* ms, int capacity);
 
+/* ---- selected singular triplets: svd_decomp(A, subset), svd_vals(A), bidiag_svd(d, e, subset), bidiag_svdvals (csrc/bdsvdx.hip,
+ * DESIGN.md 4.23). As with the selected eigenpairs below, the host-pointer forms end in _host, not in the bare name.
+ * B is the upper bidiagonal K x J matrix of dbdsdc (d [batch,K], e [batch,J-1], J = K or K + 1), 1 <= K <= 2048. The subset
+ * (i0, i1), 0 <= i0 <= i1 <= K, selects sv[i0:i1] of the DESCENDING singular values, k = i1 - i0. K = 0, an empty batch and an empty
+ * subset have nothing to do and write nothing.
+ *   dbdsvdx: sv [batch,k] by bisection on the Sturm count of the Golub-Kahan matrix of B, the symmetric tridiagonal of order K + J
+ *            with a zero diagonal and the off-diagonals d0, e0, d1, e1, ...: the arithmetic of dstevx below with d = 0 (the same
+ *            scale, interval, stopping rule and 128-step cap), then max(value, +0). U2 [batch,K,k] (columns = left vectors) and
+ *            V2 [batch,k,J] (rows = right vectors), both or neither (NULL, NULL: the values alone, the same bits): three rounds of
+ *            dstevx's inverse iteration and Gram-Schmidt on the eigenvector (v0, u0, v1, u1, ...), then u and v are normalised
+ *            each on its own. A member goes to the full solver instead (dbdsdc on that member alone, columns i0 .. i1 - 1 of its
+ *            U2 and rows i0 .. i1 - 1 of its V2, bit for bit; sv stays the bisection's) when B = 0, when two or more of its
+ *            selected scaled values lie below 1e-3 g / 2 (g the Gershgorin bound of the scaled member), or when
+ *            min(|u|^2, |v|^2) < 1/8 for one of its vectors. fallback [batch] (int32, may be NULL) receives those flags.
+ *            NaN or Inf in d or e: ND4HIP_ERR_NOCONV, 'bidiag_svd(d,e): d or e contains NaN or Infinity.'; dbdsdc's errors pass through.
+ *   dgesvdx: A [batch,M,N] -> U [batch,M,k], sv [batch,k], V [batch,k,N] (U = V = NULL: the values alone, the same bits, no product):
+ *            the scaling and dgebrd of dgesdd (M > N through the transpose), dbdsvdx, U = U_b U2 and V = V2 V_b on the k selected
+ *            columns and rows. min(M, N) <= 2048. NaN or Inf in A: ND4HIP_ERR_NOCONV, 'svd_decomp(A): A contains NaN or Infinity.'
+ * Bounds: 1e-12 norm-wise (values, both residuals, orthogonality of U and V). A member's results do not depend on the batch or on
+ * the run. All forms synchronise (the flags are read back once per chunk). Profile ops "dbdsvdx_batched", "dgesvdx_batched". */
+int nd4hip_dbdsvdx_batched_dev (nd4hip_handle* h, int64_t batch, int64_t K, int64_t J, int64_t i0, int64_t i1, const double* d, const double* e,
+                                double* U2, double* sv, double* V2, int32_t* fallback);
+int nd4hip_dbdsvdx_batched_host(nd4hip_handle* h, int64_t batch, int64_t K, int64_t J, int64_t i0, int64_t i1, const double* d, const double* e,
+                                double* U2, double* sv, double* V2, int32_t* fallback);
+int nd4hip_dgesvdx_batched_dev (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t i0, int64_t i1, const double* A, double* U,
+                                double* sv, double* V, int32_t* fallback);
+int nd4hip_dgesvdx_batched_host(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t i0, int64_t i1, const double* A, double* U,
+                                double* sv, double* V, int32_t* fallback);
+/* HIP-event time per stage of the LAST dgesvdx / dbdsvdx call (one chunk) made on this handle while nd4hip_profile_enable was on,
+ * in ms: bidiagonalisation with the scaling and the transposes (0 for dbdsvdx), bisection, inverse iteration and split, the full
+ * solver on the flagged members (the read-back included), the two products (0 for dbdsvdx). */
+#define ND4HIP_SVDX_STAGES 5
+int nd4hip_dgesvdx_last_stages(nd4hip_handle* h, double* ms, int capacity);
+
 /* ---- eigen_sym / eigenvals_sym: the symmetric eigenproblem (planned by the reference, src/la/eigen.js:28-30; csrc/syev.hip) ----
  * S [batch,N,N] symmetric, read ONLY in its lower triangle (j <= i; the upper triangle may hold anything, NaN included) and never
  * written -> lambda [batch,N] descending and V [batch,N,N] with the eigenvectors as columns: S V = V diag(lambda), V^T V = I.

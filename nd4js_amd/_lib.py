@@ -149,6 +149,11 @@ SIGNATURES = {
     "nd4hip_dgesdd_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp]),
     "nd4hip_dbdsdc_levels": (c_int, [c_i64, ctypes.POINTER(ctypes.c_int32), c_i64]),
     "nd4hip_dgesdd_last_stages": (c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), c_int]),
+    "nd4hip_dbdsvdx_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, c_dp, ctypes.c_void_p]),
+    "nd4hip_dbdsvdx_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, c_dp, ctypes.c_void_p]),
+    "nd4hip_dgesvdx_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, ctypes.c_void_p]),
+    "nd4hip_dgesvdx_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, ctypes.c_void_p]),
+    "nd4hip_dgesvdx_last_stages": (c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), c_int]),
     "nd4hip_dsyevd_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),
     "nd4hip_dsyevd_batched": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),
     "nd4hip_dsyevd_last_stages": (c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), c_int]),
@@ -315,6 +320,17 @@ class Handle:
         if n < 0:
             check(n)
         return dict(zip(self.EIGSYM_SUBSET_STAGES, ms))
+
+    SVD_SUBSET_STAGES = ("bidiag", "bisect", "invit", "fallback", "gemm")
+
+    def svd_subset_last_stages(self):
+        """ms per stage of the last svd_decomp(A, subset) / svd_vals / bidiag_svd(d, e, subset) made with the profile enabled
+        (nd4hip_dgesvdx_last_stages)"""
+        ms = (ctypes.c_double * len(self.SVD_SUBSET_STAGES))()
+        n = self.lib.nd4hip_dgesvdx_last_stages(self._h, ms, len(self.SVD_SUBSET_STAGES))
+        if n < 0:
+            check(n)
+        return dict(zip(self.SVD_SUBSET_STAGES, ms))
 
     def close(self):
         if self._h:

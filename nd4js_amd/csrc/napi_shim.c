@@ -81,6 +81,8 @@ static int (*p_dsyevx_tr[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t,
 static int (*p_dsygvd[2])(nd4hip_handle*, int, int64_t, int64_t, const double*, const double*, int64_t, double*, double*, int32_t*);
 static int (*p_dstcnt[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, const double*, const double*, int32_t*);
 static int (*p_dstevx[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, const double*, const double*, double*, double*);
+static int (*p_dbdsvdx[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, int64_t, const double*, const double*, double*, double*, double*, int32_t*);
+static int (*p_dgesvdx[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, int64_t, const double*, double*, double*, double*, int32_t*);
 static int (*p_dstevxv[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, const double*, const double*, double*, double*, int32_t*, int64_t*);
 static int (*p_dsyevxv[2][2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, const double*, double*, double*, int32_t*, int64_t*);   /* [tridiag][dev] */
 static int (*p_dsygvx[2])(nd4hip_handle*, int, int, int64_t, int64_t, int64_t, int64_t, int64_t, const double*, const double*, const double*, int64_t,
@@ -191,6 +193,8 @@ static int load_library(void) {
   SYM2(p_dsygvd, "nd4hip_dsygvd_batched");
   SYM(p_dstcnt[0], "nd4hip_dstcnt_batched_host"); SYM(p_dstcnt[1], "nd4hip_dstcnt_batched_dev");
   SYM(p_dstevx[0], "nd4hip_dstevx_batched_host"); SYM(p_dstevx[1], "nd4hip_dstevx_batched_dev");
+  SYM(p_dbdsvdx[0], "nd4hip_dbdsvdx_batched_host"); SYM(p_dbdsvdx[1], "nd4hip_dbdsvdx_batched_dev");
+  SYM(p_dgesvdx[0], "nd4hip_dgesvdx_batched_host"); SYM(p_dgesvdx[1], "nd4hip_dgesvdx_batched_dev");
   SYM(p_dstevxv[0], "nd4hip_dstevxv_batched_host"); SYM(p_dstevxv[1], "nd4hip_dstevxv_batched_dev");
   SYM(p_dsyevxv[0][0], "nd4hip_dsyevxv_batched_host"); SYM(p_dsyevxv[0][1], "nd4hip_dsyevxv_batched_dev");
   SYM(p_dsyevxv[1][0], "nd4hip_dsyevxv_tr_batched_host"); SYM(p_dsyevxv[1][1], "nd4hip_dsyevxv_tr_batched_dev");
@@ -918,6 +922,39 @@ static napi_value js_dstevx(napi_env env, napi_callback_info info) {
   FAIL_IF(p_dstevx[d.dev](g_handle, batch, N, i0, i1, (const double*)d.p, (const double*)e.p, (double*)L.p, (double*)Z.p));
   return NULL;
 }
+/* dbdsvdx_batched(batch, K, J, i0, i1, d, e, U2, sv, V2, fallback): U2 [batch, K, k] and V2 [batch, k, J] or both null; fallback int32 [batch] or null */
+static napi_value js_dbdsvdx(napi_env env, napi_callback_info info) {
+  ARGS(11, "dbdsvdx_batched");
+  int64_t batch, K, J, i0, i1; opnd d, e, U, S, V, fb;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &K) || get_i64(env, a[2], &J) || get_i64(env, a[3], &i0) || get_i64(env, a[4], &i1) ||
+      F64(5, d) || opt_op(env, a[6], napi_float64_array, d.dev, &e) || opt_op(env, a[7], napi_float64_array, d.dev, &U) || F64(8, S) ||
+      opt_op(env, a[9], napi_float64_array, d.dev, &V) || opt_op(env, a[10], napi_int32_array, d.dev, &fb)) return NULL;
+  NEED(batch >= 0 && K >= 1 && (J == K || J == K + 1) && 0 <= i0 && i0 <= i1 && i1 <= K && (size_t)(batch * K) <= d.len &&
+       (J < 2 || (size_t)(batch * (J - 1)) <= e.len) && (size_t)(batch * (i1 - i0)) <= S.len && !U.p == !V.p &&
+       (!U.p || ((size_t)(batch * K * (i1 - i0)) <= U.len && (size_t)(batch * (i1 - i0) * J) <= V.len)) && (!fb.p || (size_t)batch <= fb.len),
+       "dbdsvdx_batched: bad subset or buffer too small");
+  SAME_SIDE(d.dev == e.dev && e.dev == U.dev && U.dev == S.dev && S.dev == V.dev && V.dev == fb.dev, "dbdsvdx_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dbdsvdx[d.dev](g_handle, batch, K, J, i0, i1, (const double*)d.p, (const double*)e.p, (double*)U.p, (double*)S.p, (double*)V.p,
+                           (int32_t*)fb.p));
+  return NULL;
+}
+/* dgesvdx_batched(batch, M, N, i0, i1, A, U, sv, V, fallback): U [batch, M, k] and V [batch, k, N] or both null; fallback int32 [batch] or null */
+static napi_value js_dgesvdx(napi_env env, napi_callback_info info) {
+  ARGS(10, "dgesvdx_batched");
+  int64_t batch, M, N, i0, i1; opnd A, U, S, V, fb;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &M) || get_i64(env, a[2], &N) || get_i64(env, a[3], &i0) || get_i64(env, a[4], &i1) ||
+      F64(5, A) || opt_op(env, a[6], napi_float64_array, A.dev, &U) || F64(7, S) || opt_op(env, a[8], napi_float64_array, A.dev, &V) ||
+      opt_op(env, a[9], napi_int32_array, A.dev, &fb)) return NULL;
+  NEED(batch >= 0 && M >= 1 && N >= 1 && 0 <= i0 && i0 <= i1 && i1 <= (M < N ? M : N) && (size_t)(batch * M * N) <= A.len &&
+       (size_t)(batch * (i1 - i0)) <= S.len && !U.p == !V.p &&
+       (!U.p || ((size_t)(batch * M * (i1 - i0)) <= U.len && (size_t)(batch * (i1 - i0) * N) <= V.len)) && (!fb.p || (size_t)batch <= fb.len),
+       "dgesvdx_batched: bad subset or buffer too small");
+  SAME_SIDE(A.dev == U.dev && U.dev == S.dev && S.dev == V.dev && V.dev == fb.dev, "dgesvdx_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_dgesvdx[A.dev](g_handle, batch, M, N, i0, i1, (const double*)A.p, (double*)U.p, (double*)S.p, (double*)V.p, (int32_t*)fb.p));
+  return NULL;
+}
 /* dstevxv_batched(batch, N, kcap, bounds, d, e, L, Z, range) -> kmax: L [batch, kcap], Z [batch, kcap, N] or null, range int32 [batch, 2] */
 static napi_value js_dstevxv(napi_env env, napi_callback_info info) {
   ARGS(9, "dstevxv_batched");
@@ -1397,6 +1434,8 @@ static napi_value init(napi_env env, napi_value exports) {
     {"dstcnt_batched", NULL, js_dstcnt, NULL, NULL, NULL, napi_default, NULL},
     {"dstevx_batched", NULL, js_dstevx, NULL, NULL, NULL, napi_default, NULL},
     {"dstevxv_batched", NULL, js_dstevxv, NULL, NULL, NULL, napi_default, NULL},
+    {"dbdsvdx_batched", NULL, js_dbdsvdx, NULL, NULL, NULL, napi_default, NULL},
+    {"dgesvdx_batched", NULL, js_dgesvdx, NULL, NULL, NULL, napi_default, NULL},
     {"dsyevxv_batched", NULL, js_dsyevxv, NULL, NULL, NULL, napi_default, NULL},
     {"dsygvx_batched", NULL, js_dsygvx, NULL, NULL, NULL, napi_default, NULL},
     {"dqp3rank_batched", NULL, js_dqp3rank, NULL, NULL, NULL, napi_default, NULL},

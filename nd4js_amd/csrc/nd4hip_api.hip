@@ -682,6 +682,41 @@ extern "C" int nd4hip_dgesdd_last_stages(nd4hip_handle* h, double* ms, int capac
   return ND4HIP_DC_STAGES;
 }
 
+// ---- selected singular triplets (bdsvdx.hip). The argument checks come first: they need no handle. Algorithmic flops:
+// a Sturm count of the Golub-Kahan matrix is 3 (K + J), a bisection about 55 of them per value, an inverse iteration 13 (K + J) per
+// vector and round; dgesvdx: 8/3 m^2 (3 n - m) for the bidiagonalisation with U_b and V_b, 2 m k (m + n) for the two products
+extern "C" int nd4hip_dbdsvdx_batched_dev(nd4hip_handle* h, int64_t batch, int64_t K, int64_t J, int64_t i0, int64_t i1, const double* d,
+                                          const double* e, double* U2, double* sv, double* V2, int32_t* fallback) {
+  ND4_ARGS(nd4_args_bdsvdx(batch, K, J, i0, i1, d, e, U2, sv, V2));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dbdsvdx_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  const int64_t k = i1 - i0, n = K + J;
+  Nd4Prof prof(h, "dbdsvdx_batched", batch * (double)k * n * (165.0 + (U2 ? 39.0 : 0.0)), 8.0 * batch * (double)(n - 1 + k + (U2 ? k * n : 0)));
+  ND4_FOR_CHUNKS(batch)
+    ND4_TRY(nd4_bdsvdx(h, nb, K, J, i0, i1, d + b0 * K, e ? e + b0 * (J - 1) : nullptr, U2 ? U2 + b0 * K * k : nullptr, sv + b0 * k,
+                       V2 ? V2 + b0 * k * J : nullptr, fallback ? fallback + b0 : nullptr));
+  return 0;
+}
+extern "C" int nd4hip_dgesvdx_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t i0, int64_t i1, const double* A, double* U,
+                                          double* sv, double* V, int32_t* fallback) {
+  ND4_ARGS(nd4_args_gesvdx(batch, M, N, i0, i1, A, U, sv, V));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dgesvdx_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  const int64_t k = i1 - i0;
+  const double m = (double)(M < N ? M : N), n = (double)(M < N ? N : M);
+  Nd4Prof prof(h, "dgesvdx_batched", batch * (8.0 / 3.0 * m * m * (3.0 * n - m) + (U ? 2.0 * m * k * (m + n) : 0.0)),
+               8.0 * batch * (double)(M * N + k + (U ? (M + N) * k : 0)));
+  ND4_FOR_CHUNKS(batch)
+    ND4_TRY(nd4_gesvdx(h, nb, M, N, i0, i1, A + b0 * M * N, U ? U + b0 * M * k : nullptr, sv + b0 * k, V ? V + b0 * k * N : nullptr,
+                       fallback ? fallback + b0 : nullptr));
+  return 0;
+}
+extern "C" int nd4hip_dgesvdx_last_stages(nd4hip_handle* h, double* ms, int capacity) {
+  ND4_CHECK_ARG(h != nullptr && (ms != nullptr || capacity <= 0), "nd4hip_dgesvdx_last_stages: NULL argument");
+  for (int i = 0; i < capacity && i < ND4HIP_SVDX_STAGES; ++i) ms[i] = h->svdx_stage_ms[i];
+  return ND4HIP_SVDX_STAGES;
+}
+
 // ---- eigen_sym / eigenvals_sym (syev.hip). Algorithmic flops per matrix: 10/3 N^3 for the reduction with U (4/3 N^3 for T, 2 N^3
 // for U), 2 N^3 for the eigenvector half of the solver's merges, 2 N^3 for V = U V2^T; without V the last term drops out
 extern "C" int nd4hip_dsyevd_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V) {

@@ -219,6 +219,34 @@ inline int nd4_args_bdsdc(int64_t batch, int64_t K, int64_t J, const void* d, co
   return ND4_ARGS_GO;
 }
 
+// ---- selected singular triplets (bdsvdx.hip): the vectors go together and are optional, as is `fallback`; e is not read for J = 1
+inline int nd4_args_bdsvdx(int64_t batch, int64_t K, int64_t J, int64_t i0, int64_t i1, const void* d, const void* e, const void* U2,
+                           const void* sv, const void* V2) {
+  ND4_CHECK_ARG(batch >= 0 && K >= 0, "nd4hip_dbdsvdx_batched: negative extent");
+  ND4_CHECK_ARG(J == K || J == K + 1, "nd4hip_dbdsvdx_batched: B must be K x K or K x (K+1)");
+  ND4_CHECK_ARG(0 <= i0 && i0 <= i1 && i1 <= K, "nd4hip_dbdsvdx_batched: subset must satisfy 0 <= i0 <= i1 <= K");
+  ND4_CHECK_ARG(K <= 2048, "nd4hip_dbdsvdx_batched: K <= 2048");
+  if (batch == 0 || K == 0 || i0 == i1) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(d && (e || J < 2) && sv, "nd4hip_dbdsvdx_batched: NULL pointer");
+  ND4_CHECK_ARG(!U2 == !V2, "nd4hip_dbdsvdx_batched: U2 and V2 go together");
+  return ND4_ARGS_GO;
+}
+inline int nd4_args_gesvdx(int64_t batch, int64_t M, int64_t N, int64_t i0, int64_t i1, const void* A, const void* U, const void* sv,
+                           const void* V) {
+  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_dgesvdx_batched: negative extent");
+  ND4_CHECK_ARG(0 <= i0 && i0 <= i1 && i1 <= (M < N ? M : N), "nd4hip_dgesvdx_batched: subset must satisfy 0 <= i0 <= i1 <= min(M, N)");
+  ND4_CHECK_ARG((M < N ? M : N) <= 2048, "nd4hip_dgesvdx_batched: min(M, N) <= 2048");
+  if (batch == 0 || M == 0 || N == 0 || i0 == i1) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(A && sv, "nd4hip_dgesvdx_batched: NULL pointer");
+  ND4_CHECK_ARG(!U == !V, "nd4hip_dgesvdx_batched: U and V go together");
+  return ND4_ARGS_GO;
+}
+// the workspace and grid arithmetic of a dbdsvdx call (bdsvdx.hip; tools/bdsvdx_host_check.hip walks every K and J): the order of
+// the Golub-Kahan matrix, its off-diagonals (what stx_bisect's LDS array must hold: at most 4096), the doubles of the vector stage
+inline int64_t nd4_bdx_order(int64_t K, int64_t J) { return K + J; }
+inline int64_t nd4_bdx_offdiagonals(int64_t K, int64_t J) { return K + J - 1; }
+inline size_t nd4_bdx_lds_bytes(int64_t K, int64_t J) { return sizeof(double) * (size_t)nd4_bdx_offdiagonals(K, J); }
+inline size_t nd4_bdx_vector_doubles(int64_t batch, int64_t K, int64_t J, int64_t k) { return (size_t)batch * (size_t)k * (size_t)nd4_bdx_order(K, J) * 5; }
 // ---- symmetric eigenproblems: the divide & conquer solver takes N <= 2048, the Jacobi route (`jacobi`) N <= 128; V, X and the
 // sweep counts are optional
 inline int nd4_args_syev(const char* op, bool jacobi, int64_t batch, int64_t N, const void* S, const void* lambda) {

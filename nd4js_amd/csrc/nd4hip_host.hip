@@ -898,6 +898,44 @@ extern "C" int nd4hip_dbdsdc_batched(nd4hip_handle* h, int64_t batch, int64_t K,
   return run_host(h, batch, ops, fn);
 }
 
+// selected singular triplets (bdsvdx.hip); U2 = V2 = NULL (U = V = NULL): the values alone; fallback = NULL: not wanted; e is not moved for J = 1
+extern "C" int nd4hip_dbdsvdx_batched_host(nd4hip_handle* h, int64_t batch, int64_t K, int64_t J, int64_t i0, int64_t i1, const double* d,
+                                           const double* e, double* U2, double* sv, double* V2, int32_t* fallback) {
+  ND4_ARGS(nd4_args_bdsvdx(batch, K, J, i0, i1, d, e, U2, sv, V2));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dbdsvdx_batched: NULL handle");
+  const int64_t k = i1 - i0;
+  // the operands in the order d, sv, [e], [U2, V2], [fallback]
+  std::vector<Operand> ops{in_op(d, K, K), out_op(sv, k)};
+  const int ie = J >= 2 ? (int)ops.size() : -1;
+  if (J >= 2) ops.push_back(in_op(e, J - 1, J - 1));
+  const int iu = U2 ? (int)ops.size() : -1;
+  if (U2) { ops.push_back(out_op(U2, K * k)); ops.push_back(out_op(V2, k * J)); }
+  const int ifb = fallback ? (int)ops.size() : -1;
+  if (fallback) ops.push_back(out_op(fallback, 1, 4));
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return nd4hip_dbdsvdx_batched_dev(hd, nb, K, J, i0, i1, P(p, 0), ie >= 0 ? P(p, ie) : nullptr, iu >= 0 ? P(p, iu) : nullptr, P(p, 1),
+                                      iu >= 0 ? P(p, iu + 1) : nullptr, ifb >= 0 ? static_cast<int32_t*>(p[ifb]) : nullptr);
+  };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_dgesvdx_batched_host(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t i0, int64_t i1, const double* A, double* U,
+                                           double* sv, double* V, int32_t* fallback) {
+  ND4_ARGS(nd4_args_gesvdx(batch, M, N, i0, i1, A, U, sv, V));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dgesvdx_batched: NULL handle");
+  const int64_t k = i1 - i0;
+  // the operands in the order A, sv, [U, V], [fallback]
+  std::vector<Operand> ops{in_op(A, M * N, M * N), out_op(sv, k)};
+  const int iu = U ? (int)ops.size() : -1;
+  if (U) { ops.push_back(out_op(U, M * k)); ops.push_back(out_op(V, k * N)); }
+  const int ifb = fallback ? (int)ops.size() : -1;
+  if (fallback) ops.push_back(out_op(fallback, 1, 4));
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return nd4hip_dgesvdx_batched_dev(hd, nb, M, N, i0, i1, P(p, 0), iu >= 0 ? P(p, iu) : nullptr, P(p, 1), iu >= 0 ? P(p, iu + 1) : nullptr,
+                                      ifb >= 0 ? static_cast<int32_t*>(p[ifb]) : nullptr);
+  };
+  return run_host(h, batch, ops, fn);
+}
+
 // eigen_sym / eigenvals_sym (syev.hip); V = NULL: the values alone
 extern "C" int nd4hip_dsyevd_batched(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dsyevd_batched: NULL handle");

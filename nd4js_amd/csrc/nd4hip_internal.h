@@ -36,6 +36,7 @@ struct nd4hip_handle {
   double dc_stage_ms[ND4HIP_DC_STAGES] = {0};   // per-stage times of the last divide & conquer SVD run with the profile enabled
   double syev_stage_ms[ND4HIP_SYEV_STAGES] = {0};   // the same for the last symmetric eigenproblem (syev.hip)
   double syevx_stage_ms[ND4HIP_SYEVX_STAGES] = {0}; // and for the last one by bisection and inverse iteration (syevx.hip)
+  double svdx_stage_ms[ND4HIP_SVDX_STAGES] = {0};   // and for the last selected-triplet SVD (bdsvdx.hip)
 };
 
 // Makes h->device the calling thread's current HIP device for the duration of an entry point and restores the previous
@@ -175,6 +176,13 @@ int nd4_svd_scale_undo(nd4hip_handle* h, int64_t batch, int64_t L, double* sv, c
 int nd4_bdsdc_plan(int64_t n, int32_t* out, int64_t capacity);
 int nd4_bdsdc_rows(nd4hip_handle* h, int64_t batch, int64_t K, int64_t J, const double* d, const double* e, double* U2, double* sv, double* V2);
 int nd4_gesdd(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* U, double* sv, double* V);
+// selected singular triplets (bdsvdx.hip): arguments already checked, batch in 1 .. 32768, 1 <= K <= 2048, 0 <= i0 < i1 <= K (min(M, N)),
+// k = i1 - i0. U2 [batch, K, k] and V2 [batch, k, J] (U [batch, M, k] and V [batch, k, N]) both or neither; fallback [batch] may be NULL.
+// Both synchronise.
+int nd4_bdsvdx(nd4hip_handle* h, int64_t batch, int64_t K, int64_t J, int64_t i0, int64_t i1, const double* d, const double* e, double* U2,
+               double* sv, double* V2, int32_t* fallback);
+int nd4_gesvdx(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t i0, int64_t i1, const double* A, double* U, double* sv, double* V,
+               int32_t* fallback);
 // symmetric eigenproblem (syev.hip): lower triangle of S -> lambda descending, V columns (V may be NULL); synchronises
 int nd4_syevd(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V);
 // the same by two-sided Jacobi in one launch (syevj.hip): 1 <= N <= 128; sweeps [batch] may be NULL; synchronises

@@ -23,6 +23,8 @@
 //      cluster's earlier vectors by Gram-Schmidt applied twice, normalised and, in the last round, given the sign that makes its
 //      first component of largest magnitude positive. Reductions have a fixed order: results are the same bits run to run.
 //   Steps 5 and 6 run three times. 7 (dsyevx): steps 1-2 of syev.hip, then V = U Z^T on the fp64 MFMA GEMM.
+//   The bisection loop (stx_bisect_value) and steps 4-6 as one launcher (nd4_stx_vectors) are declared in syev_internal.h: bdsvdx.hip
+//   runs them on the Golub-Kahan form of a bidiagonal matrix.
 // Arithmetic of 1-4 is + - * / and comparisons, each rounded once (the file is compiled without contraction): the device returns
 // the bits of the numpy model in tests/eigsym_subset_common.py.
 //   The interval forms select the eigenvalues in (lo, hi] of each member: after step 1 one stx_count launch with the
@@ -38,9 +40,6 @@
 namespace {
 
 constexpr int STX_MAXN = 2048;             // d and e^2 of one member are staged in 2 x 16 KB of LDS
-constexpr int STX_MAXIT = 128;
-constexpr double STX_EPS = 0x1p-52;
-constexpr double STX_PIVMIN = 0x1p-1022;
 constexpr unsigned STX_SEED = 20480u;      // of the start vectors
 constexpr int STX_ORTH_THREADS = 512;
 constexpr int STX_STAGES = ND4HIP_SYEVX_STAGES;
@@ -147,14 +146,7 @@ __global__ __launch_bounds__(256) void stx_bisect(const double* __restrict__ ds,
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (t >= kb) return;
   const int j = first + t;
-  const double gg = g[b], floor_ = STX_EPS * gg;
-  double hi = gg * (1.0 + 0x1p-20), lo = -hi;
-  for (int it = 0; it < STX_MAXIT; ++it) {
-    const double mid = 0.5 * (lo + hi);
-    if (hi - lo <= (2.0 * STX_EPS) * fmax(fabs(lo), fabs(hi)) + floor_ || mid == lo || mid == hi) break;
-    if (N - stx_negatives(sd, s2, N, mid) > j) lo = mid; else hi = mid;
-  }
-  const double v = 0.5 * (lo + hi);
+  const double v = stx_bisect_value(g[b], j, N, [&](double x) { return stx_negatives(sd, s2, N, x); });
   lams[(size_t)b * k + t] = v;
   lam[(size_t)b * k + t] = ldexp(v, lexp[b]);
 }
@@ -333,30 +325,9 @@ __global__ __launch_bounds__(STX_ORTH_THREADS) void stx_orth(double* __restrict_
   }
 }
 
-template <class T> int stx_alloc(nd4hip_handle* h, size_t count, T** out) {
-  void* p = nullptr;
-  ND4_TRY(nd4_ws_alloc(h, sizeof(T) * (count ? count : 1), &p));
-  *out = static_cast<T*>(p);
-  return 0;
-}
-
 // HIP-event time per stage while the profile is enabled
-struct StxStamps {
-  nd4hip_handle* h; bool on; int n = 0;
-  hipEvent_t ev[STX_STAGES + 1] = {};
-  explicit StxStamps(nd4hip_handle* hh) : h(hh), on(hh->prof_on) {}
-  void mark() {
-    if (!on || n > STX_STAGES) return;
-    if (hipEventCreate(&ev[n]) != hipSuccess) { on = false; return; }
-    (void)hipEventRecord(ev[n++], h->stream);
-  }
-  void collect() {                                            // after the call's synchronisation
-    for (int i = 0; i < STX_STAGES; ++i) {
-      float ms = 0.f;
-      h->syevx_stage_ms[i] = on && i + 1 < n && hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess ? ms : 0.0;
-    }
-  }
-  ~StxStamps() { for (int i = 0; i < n; ++i) (void)hipEventDestroy(ev[i]); }
+struct StxStamps : Nd4StageStamps<STX_STAGES> {
+  explicit StxStamps(nd4hip_handle* hh) : Nd4StageStamps<STX_STAGES>(hh, hh->syevx_stage_ms) {}
 };
 
 struct StxPrepared { double *ds, *es, *e2, *g; int *lexp, *diag, *flag; };
@@ -402,18 +373,7 @@ int stx_solve(nd4hip_handle* h, int64_t batch, int N, int i0, int k, const int* 
                      k, rng, lams, lambda);
   ND4_HIP(hipGetLastError());
   st->mark();
-  if (Z) {
-    int* head = nullptr; double *shift, *u0, *u1, *u2, *y;
-    ND4_TRY(stx_alloc(h, bk, &head)); ND4_TRY(stx_alloc(h, bk, &shift));
-    ND4_TRY(stx_alloc(h, bk * N, &u0)); ND4_TRY(stx_alloc(h, bk * N, &u1)); ND4_TRY(stx_alloc(h, bk * N, &u2)); ND4_TRY(stx_alloc(h, bk * N, &y));
-    hipLaunchKernelGGL(stx_clusters, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, h->stream, lams, w.g, w.diag, (int)batch, k, rng, head, shift);
-    for (int round = 0; round < 3; ++round) {
-      hipLaunchKernelGGL(stx_factor_solve, dim3((unsigned)nd4_stx_solve_blocks(batch, k)), dim3(64), 0, h->stream, w.ds, w.es, w.g, w.diag, shift, N, i0, k, rng,
-                         (long)bk, round, u0, u1, u2, y, Z);
-      hipLaunchKernelGGL(stx_orth, dim3((unsigned)k, (unsigned)batch), dim3(STX_ORTH_THREADS), 0, h->stream, Z, head, w.diag, N, k, rng, round == 2);
-    }
-    ND4_HIP(hipGetLastError());
-  }
+  if (Z) ND4_TRY(nd4_stx_vectors(h, batch, N, i0, k, rng, w.ds, w.es, w.g, w.diag, lams, Z));
   st->mark();
   return 0;
 }
@@ -462,15 +422,39 @@ int stx_ragged_run(nd4hip_handle* h, int64_t batch, int64_t rows, int k, int64_t
 constexpr double STX_NAN = __builtin_nan("");
 
 int stx_read_flag(nd4hip_handle* h, const int* flag, int* value) {
-  void* hp = nullptr;
-  ND4_TRY(nd4_pinned(h, sizeof(int), &hp));
-  ND4_HIP(hipMemcpyAsync(hp, flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  ND4_HIP(hipStreamSynchronize(h->stream));
-  *value = *static_cast<int*>(hp);
+  const int* host = nullptr;
+  ND4_TRY(nd4_stx_read_flags(h, flag, 1, &host));
+  *value = host[0];
   return 0;
 }
 
 }  // namespace
+
+int nd4_stx_read_flags(nd4hip_handle* h, const int* flags, size_t count, const int** host) {
+  void* hp = nullptr;
+  ND4_TRY(nd4_pinned(h, sizeof(int) * count, &hp));
+  ND4_HIP(hipMemcpyAsync(hp, flags, sizeof(int) * count, hipMemcpyDeviceToHost, h->stream));
+  ND4_HIP(hipStreamSynchronize(h->stream));
+  *host = static_cast<const int*>(hp);
+  return 0;
+}
+
+// steps 4-6 (declared in syev_internal.h: bdsvdx.hip runs them on the Golub-Kahan form of a bidiagonal matrix)
+int nd4_stx_vectors(nd4hip_handle* h, int64_t batch, int N, int i0, int k, const int* rng, const double* ds, const double* es, const double* g,
+                    const int* diag, const double* lams, double* Z) {
+  const size_t bk = (size_t)batch * k;
+  int* head = nullptr; double *shift, *u0, *u1, *u2, *y;
+  ND4_TRY(stx_alloc(h, bk, &head)); ND4_TRY(stx_alloc(h, bk, &shift));
+  ND4_TRY(stx_alloc(h, bk * N, &u0)); ND4_TRY(stx_alloc(h, bk * N, &u1)); ND4_TRY(stx_alloc(h, bk * N, &u2)); ND4_TRY(stx_alloc(h, bk * N, &y));
+  hipLaunchKernelGGL(stx_clusters, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, h->stream, lams, g, diag, (int)batch, k, rng, head, shift);
+  for (int round = 0; round < 3; ++round) {
+    hipLaunchKernelGGL(stx_factor_solve, dim3((unsigned)nd4_stx_solve_blocks(batch, k)), dim3(64), 0, h->stream, ds, es, g, diag, shift, N, i0, k, rng,
+                       (long)bk, round, u0, u1, u2, y, Z);
+    hipLaunchKernelGGL(stx_orth, dim3((unsigned)k, (unsigned)batch), dim3(STX_ORTH_THREADS), 0, h->stream, Z, head, diag, N, k, rng, round == 2);
+  }
+  ND4_HIP(hipGetLastError());
+  return 0;
+}
 
 // count [batch, M] = #{lambda > x [batch, M]} of tridiag(d [batch, N], e [batch, N-1]); batch <= 32768, 1 <= N <= 2048. Enqueues only.
 int nd4_stcnt(nd4hip_handle* h, int64_t batch, int64_t N64, int64_t M, const double* d, const double* e, const double* x, int32_t* count) {

@@ -138,10 +138,40 @@ def qr_decomp(A):
     return Q, R
 
 
-def svd_decomp(A, info=None, algo=None):
-    """algo None / 'jacobi': block one-sided Jacobi (the default route); 'dc': bidiagonalisation + divide & conquer (opt-in)"""
+def _gesvdx(A, what, subset, vectors, info):
+    from .la import _svd_subset
+    _chk(A, "A")
+    if A.dim() < 2:
+        raise ValueError("%s: A.ndim must be at least 2." % what)
+    M, N = A.shape[-2:]
+    L = min(M, N)
+    if L > 2048:
+        raise ValueError("%s: min(M, N) <= 2048." % what)
+    lead = tuple(A.shape[:-2])
+    i0, i1 = (0, L) if subset is None else _svd_subset(subset, L, what, False)
+    k = i1 - i0
+    sv = torch.empty(lead + (k,), dtype=torch.float64, device=A.device)
+    U = torch.empty(lead + (M, k), dtype=torch.float64, device=A.device) if vectors else None
+    V = torch.empty(lead + (k, N), dtype=torch.float64, device=A.device) if vectors else None
+    fb = torch.zeros(lead, dtype=torch.int32, device=A.device) if info is not None else None
+    if sv.numel():
+        h = _h(A)
+        _lib.check(h.lib.nd4hip_dgesvdx_batched_dev(h.ptr, _batch(lead), M, N, i0, i1, _p(A), _p(U) if vectors else None, _p(sv),
+                                                    _p(V) if vectors else None, _p(fb) if fb is not None else None))
+    if info is not None:
+        info["fallback"] = fb
+    return (U, sv, V) if vectors else sv
+
+
+def svd_decomp(A, info=None, algo=None, *, subset=None):
+    """algo None / 'jacobi': block one-sided Jacobi (the default route); 'dc': bidiagonalisation + divide & conquer (opt-in);
+    subset=(i0, i1) (opt-in, not with 'jacobi'): the triplets sv[i0:i1] alone (csrc/bdsvdx.hip)"""
     if algo not in (None, "jacobi", "dc"):
         raise ValueError("svd_decomp(A, algo): algo must be None, 'jacobi' or 'dc'.")
+    if subset is not None:
+        if algo == "jacobi":
+            raise ValueError("svd_decomp(A, subset): subset is not available with algo='jacobi'.")
+        return _gesvdx(A, "svd_decomp(A, subset)", subset, True, info)
     _chk(A, "A")
     if A.dim() < 2:
         raise ValueError("svd_decomp(A): A.ndim must be at least 2.")
@@ -164,8 +194,36 @@ def svd_decomp(A, info=None, algo=None):
     return U, sv, V
 
 
-def bidiag_svd(d, e):
-    """device-resident la.bidiag_svd: d [..., K], e [..., J-1] (J = K or K + 1) -> U2 [..., K, K], sv [..., K], V2 [..., J, J]"""
+def svd_vals(A, info=None, subset=None):
+    """device-resident la.svd_vals: sv [..., k] alone, the bits of svd_decomp(A, subset)'s"""
+    return _gesvdx(A, "svd_vals(A)", subset, False, info)
+
+
+def _bdsvdx(d, e, what, subset, vectors, info):
+    from .la import _bidiag_operands, _subset
+    d, e, K, J = _bidiag_operands(d, e, what, lambda t, w: _chk(t, w[:w.index("(")] + " operand"))
+    if K > 2048:
+        raise ValueError("%s: K <= 2048." % what)
+    i0, i1 = (0, K) if subset is None else _subset(subset, K, what)
+    lead, k = tuple(d.shape[:-1]), i1 - i0
+    sv = torch.empty(lead + (k,), dtype=torch.float64, device=d.device)
+    U2 = torch.empty(lead + (K, k), dtype=torch.float64, device=d.device) if vectors else None
+    V2 = torch.empty(lead + (k, J), dtype=torch.float64, device=d.device) if vectors else None
+    fb = torch.zeros(lead, dtype=torch.int32, device=d.device) if info is not None else None
+    if sv.numel():
+        h = _h(d)
+        _lib.check(h.lib.nd4hip_dbdsvdx_batched_dev(h.ptr, _batch(lead), K, J, i0, i1, _p(d), _p(e), _p(U2) if vectors else None, _p(sv),
+                                                    _p(V2) if vectors else None, _p(fb) if fb is not None else None))
+    if info is not None:
+        info["fallback"] = fb
+    return (U2, sv, V2) if vectors else sv
+
+
+def bidiag_svd(d, e, subset=None, info=None):
+    """device-resident la.bidiag_svd: d [..., K], e [..., J-1] (J = K or K + 1) -> U2 [..., K, K], sv [..., K], V2 [..., J, J];
+    subset=(i0, i1) (opt-in): U2 [..., K, k], sv [..., k], V2 [..., k, J] (csrc/bdsvdx.hip), info['fallback'] int32 [...]"""
+    if subset is not None:
+        return _bdsvdx(d, e, "bidiag_svd(d,e, subset)", subset, True, info)
     _chk(d, "d"), _chk(e, "e")
     if d.dim() < 1 or e.dim() < 1 or tuple(d.shape[:-1]) != tuple(e.shape[:-1]):
         raise ValueError("bidiag_svd(d,e): d and e must have the same leading dimensions.")
@@ -179,6 +237,11 @@ def bidiag_svd(d, e):
     h = _h(d)
     _lib.check(h.lib.nd4hip_dbdsdc_batched_dev(h.ptr, _batch(lead), K, J, _p(d), _p(e), _p(U2), _p(sv), _p(V2)))
     return U2, sv, V2
+
+
+def bidiag_svdvals(d, e, subset=None, info=None):
+    """device-resident la.bidiag_svdvals: sv [..., k] by bisection alone, the bits of bidiag_svd(d, e, subset)'s"""
+    return _bdsvdx(d, e, "bidiag_svdvals(d,e)", subset, False, info)
 
 
 def lu_solve(LU, P, Y):

@@ -684,6 +684,10 @@ function makeLa(NDA, fallback, SolveError, Complex) {
   la.svd_decomp = function svd_decomp(A, opts) {
     const algo = opts == null ? undefined : opts.algo;
     if (algo !== undefined && algo !== null && algo !== 'jacobi' && algo !== 'dc') throw new Error("svd_decomp(A, {algo}): algo must be 'jacobi' or 'dc'.");
+    if (opts != null && opts.subset != null) {     // the selected triplets alone, csrc/bdsvdx.hip (not with 'jacobi')
+      if (algo === 'jacobi') throw new Error("svd_decomp(A, {subset}): subset is not available with algo 'jacobi'.");
+      return svdSubset('svd_decomp(A, {subset})', A, opts.subset, true);
+    }
     A = asarray(A);
     if (String(dtypeOf(A)).startsWith('complex')) throw new Error('svd_dc(A): A.dtype must be float.');
     if (A.ndim < 2) throw new Error('svd_decomp(A): A.ndim must be at least 2.');
@@ -698,6 +702,74 @@ function makeLa(NDA, fallback, SolveError, Complex) {
     return [wrap(dev, Us, U), wrap(dev, Vs.subarray(0, nd_ - 1), sv), wrap(dev, Vs, V)];
   };
   la.svd_dc = la.svd_decomp;
+
+  /* ---- selected singular triplets, csrc/bdsvdx.hip (not in the reference): svd_decomp(A, {subset: [i0, i1]}) -> [U [..., M, k],
+   * sv [..., k], V [..., k, N]] for sv[i0:i1] of the descending singular values; svd_vals(A, {subset}) -> sv alone (default: all),
+   * the same bits; bidiag_svd(d, e, {subset}) -> [U2 [..., K, k], sv [..., k], V2 [..., k, J]] and bidiag_svdvals(d, e, {subset}) for
+   * the upper bidiagonal K x J matrix (J = K or K + 1; e null for K = J = 1), default subset: all. min(M, N), K <= 2048. An empty
+   * subset throws: an NDArray has no axis of length 0. Host arrays or DeviceNDArrays in, the same kind out. ---- */
+  const subsetOf = (what, subset, L, bound) => {
+    if (subset == null) return [0, L];
+    const ok = (Array.isArray(subset) || ArrayBuffer.isView(subset)) && subset.length === 2;
+    const [i0, i1] = ok ? subset : [NaN, NaN];
+    if (!(ok && Number.isInteger(i0) && Number.isInteger(i1) && 0 <= i0 && i0 <= i1 && i1 <= L))
+      throw new Error(`${what}: subset must be [i0, i1] with 0 <= i0 <= i1 <= ${bound}, got ${JSON.stringify(ok ? Array.from(subset) : subset)} for ${bound} = ${L}.`);
+    if (i0 === i1) throw new Error(`${what}: the subset [${i0}, ${i1}] is empty, and an NDArray has no axis of length 0.`);
+    return [i0, i1];
+  };
+  const svdSubset = (what, A, subset, vectors) => {
+    A = asarray(A);
+    if (isComplexDev(A) || String(dtypeOf(A)).startsWith('complex')) throw new TypeError(`${what}: A.dtype must be float.`);
+    if (A.ndim < 2) throw new Error(`${what}: A.ndim must be at least 2.`);
+    if (!gpuOk(A)) throw new TypeError(`${what}: dtype ${dtypeOf(A)} is not accelerated.`);
+    const nd_ = A.ndim, M = A.shape[nd_ - 2], N = A.shape[nd_ - 1], L = Math.min(M, N), batch = prod(A.shape, 0, nd_ - 2);
+    if (L > 2048) throw new Error(`${what}: min(M, N) <= 2048.`);
+    const [i0, i1] = subsetOf(what, subset, L, 'min(M, N)'), k = i1 - i0, lead = Array.from(A.shape.subarray(0, nd_ - 2));
+    const dev = isDev(A), temps = [], out = [];
+    try {
+      const sv = alloc(dev, batch * k); out.push(sv);
+      const U = vectors ? alloc(dev, batch * M * k) : null; if (U) out.push(U);
+      const V = vectors ? alloc(dev, batch * k * N) : null; if (V) out.push(V);
+      native().dgesvdx_batched(batch, M, N, i0, i1, view(opF64(A, dev, temps), 0), U ? view(U, 0) : null, view(sv, 0), V ? view(V, 0) : null, null);
+      const svw = wrap(dev, lead.concat([k]), sv);
+      return vectors ? [wrap(dev, lead.concat([M, k]), U), svw, wrap(dev, lead.concat([k, N]), V)] : svw;
+    }
+    catch (err) { if (dev) for (const b of out) b.free(); throw err; }
+    finally { release(temps); }
+  };
+  const svd_vals = function (A, opts) { return svdSubset('svd_vals(A)', A, opts == null ? undefined : opts.subset, false); };
+  Object.defineProperty(la, 'svd_vals', {value: svd_vals, writable: true, enumerable: false, configurable: true});
+  const bidiagSubset = (name, vectors) => {
+    const f = function (d, e, opts) {
+      const what = `${name}(d,e)`;
+      d = asarray(d); e = e == null ? null : asarray(e);
+      for (const X of e ? [d, e] : [d]) {
+        if (isComplexDev(X) || String(dtypeOf(X)).startsWith('complex')) throw new TypeError(`${what}: the operands must be float.`);
+        if (!gpuOk(X)) throw new TypeError(`${what}: dtype ${dtypeOf(X)} is not accelerated.`);
+      }
+      if (e && isDev(e) !== isDev(d)) throw new TypeError(`${what}: the operands must be all host arrays or all DeviceNDArrays.`);
+      const nd_ = d.ndim, K = d.shape[nd_ - 1], lead = Array.from(d.shape.subarray(0, nd_ - 1)), J = e ? e.shape[e.ndim - 1] + 1 : 1;
+      if ((J !== K && J !== K + 1) || (e && (e.ndim !== nd_ || lead.some((s, i) => s != e.shape[i]))))
+        throw new Error(`${what}: e must have the leading dimensions of d and len(d) - 1 or len(d) entries (null for a 1 x 1 matrix).`);
+      if (K > 2048) throw new Error(`${what}: K <= 2048.`);
+      const [i0, i1] = subsetOf(what, opts == null ? undefined : opts.subset, K, 'K'), k = i1 - i0, batch = lead.reduce((p, q) => p * q, 1);
+      const dev = isDev(d), temps = [], out = [];
+      try {
+        const sv = alloc(dev, batch * k); out.push(sv);
+        const U2 = vectors ? alloc(dev, batch * K * k) : null; if (U2) out.push(U2);
+        const V2 = vectors ? alloc(dev, batch * k * J) : null; if (V2) out.push(V2);
+        native().dbdsvdx_batched(batch, K, J, i0, i1, view(opF64(d, dev, temps), 0), e ? view(opF64(e, dev, temps), 0) : null, U2 ? view(U2, 0) : null,
+                                 view(sv, 0), V2 ? view(V2, 0) : null, null);
+        const svw = wrap(dev, lead.concat([k]), sv);
+        return vectors ? [wrap(dev, lead.concat([K, k]), U2), svw, wrap(dev, lead.concat([k, J]), V2)] : svw;
+      }
+      catch (err) { if (dev) for (const b of out) b.free(); throw err; }
+      finally { release(temps); }
+    };
+    Object.defineProperty(f, 'name', {value: name});
+    Object.defineProperty(la, name, {value: f, writable: true, enumerable: false, configurable: true});
+  };
+  bidiagSubset('bidiag_svd', true); bidiagSubset('bidiag_svdvals', false);
 
   /* ---- SURVEY §8f N1: solve-side consumers (csrc/trsm.hip) ---- */
   const triSolve = (upper, name, T, Y) => {

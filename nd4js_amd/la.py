@@ -8,6 +8,8 @@ JS wrapper nd4js_amd/js/index.js over the N-API shim; both call the same libnd4h
   lu_decomp(A)         src/la/lu.js:24-81           -> nd4hip_dgetrf_batched
   svd_decomp(A)        src/la/svd.js:25             -> nd4hip_dgesvdj_batched; algo='dc' (opt-in): nd4hip_dgesdd_batched
   bidiag_svd(d, e)     src/la/svd_dc.js:169-824     -> nd4hip_dbdsdc_batched
+  svd_decomp(A, subset), svd_vals(A), bidiag_svd(d, e, subset), bidiag_svdvals(d, e)   not in the reference (opt-in): selected
+                                   singular triplets -> nd4hip_dgesvdx_batched_host, nd4hip_dbdsvdx_batched_host
   eigen_sym(S), eigenvals_sym(S)   planned at src/la/eigen.js:28-30   -> nd4hip_dsyevd_batched; algo='jacobi' (opt-in): nd4hip_dsyevj_batched
                                    subset=(i0, i1) (opt-in): a slice of the descending spectrum -> nd4hip_dsyevx_batched_host
                                    reduction='tridiag' (opt-in): the symmetric reduction of csrc/sytrd.hip -> nd4hip_dsyevd_tr_batched_host, nd4hip_dsyevx_tr_batched_host
@@ -248,8 +250,52 @@ def _svd_algo(algo):
     raise ValueError("svd_decomp(A, algo): algo must be None, 'jacobi' or 'dc'.")
 
 
-def svd_decomp(A, device=None, info=None, algo=None):
+def _svd_subset(subset, L, what, jacobi):
+    """(i0, i1) of subset=(i0, i1), the half-open slice sv[i0:i1] of the descending singular values, 0 <= i0 <= i1 <= L"""
+    if jacobi:
+        raise ValueError("%s: subset is not available with algo='jacobi'." % what)
+    try:
+        return _subset(subset, L, what)
+    except ValueError:
+        raise ValueError("%s: subset must be (i0, i1) with 0 <= i0 <= i1 <= min(M, N), got %r for min(M, N) = %d." % (what, subset, L)) from None
+
+
+def _gesvdx(A, what, subset, vectors, device, info):
+    """the selected-triplet route (csrc/bdsvdx.hip): bidiagonalisation, bisection and inverse iteration on the Golub-Kahan form"""
+    A = np.asarray(A)
+    if np.iscomplexobj(A):
+        raise TypeError("%s: A.dtype must be float." % what)
+    A = _asarray(A, what)
+    if A.ndim < 2:
+        raise ValueError("%s: A.ndim must be at least 2." % what)
+    M, N = A.shape[-2:]
+    L = min(M, N)
+    if L > 2048:
+        raise ValueError("%s: min(M, N) <= 2048." % what)
+    lead = A.shape[:-2]
+    i0, i1 = (0, L) if subset is None else _svd_subset(subset, L, what, False)
+    k = i1 - i0
+    sv = np.empty(lead + (k,))
+    U = np.empty(lead + (M, k)) if vectors else None
+    V = np.empty(lead + (k, N)) if vectors else None
+    fb = np.zeros(lead, dtype=np.int32)
+    if sv.size:
+        h = _lib.handle(device)
+        _lib.check(h.lib.nd4hip_dgesvdx_batched_host(h.ptr, int(np.prod(lead, dtype=np.int64)), M, N, i0, i1, _ptr(A), _ptr(U) if vectors else None,
+                                                     _ptr(sv), _ptr(V) if vectors else None, _ptr(fb) if info is not None else None))
+    if info is not None:
+        info["fallback"] = fb
+    return (U, sv, V) if vectors else sv
+
+
+def svd_decomp(A, device=None, info=None, algo=None, subset=None):
+    """subset=(i0, i1) (opt-in): the triplets sv[i0:i1] of the descending singular values alone, U [..., M, k], sv [..., k],
+    V [..., k, N], by bidiagonalisation, bisection and inverse iteration (csrc/bdsvdx.hip); algo None or 'dc'."""
     dc = _svd_algo(algo)
+    if subset is not None:
+        if algo == "jacobi":
+            _svd_subset(subset, 0, "svd_decomp(A, subset)", True)
+        return _gesvdx(A, "svd_decomp(A, subset)", subset, True, device, info)
     A = np.asarray(A)
     if np.iscomplexobj(A):
         raise TypeError("svd_dc(A): A.dtype must be float.")
@@ -278,22 +324,64 @@ def svd_decomp(A, device=None, info=None, algo=None):
 svd_dc = svd_decomp
 
 
-def bidiag_svd(d, e, device=None):
-    """SVD of the upper bidiagonal K x J matrix with diagonal d [..., K] and super-diagonal e [..., J-1], J = K or K + 1 (the
-    shapes bidiag_decomp produces), by the reference's divide & conquer (svd_dc.js:169-824):
-    (U2 [..., K, K], sv [..., K] >= 0 descending, V2 [..., J, J] with rows = right vectors), B = U2 diag(sv) V2[:K]."""
-    d = _asarray(d, "bidiag_svd(d,e)")
-    e = _asarray(e, "bidiag_svd(d,e)")
-    if d.ndim < 1 or e.ndim < 1 or d.shape[:-1] != e.shape[:-1]:
-        raise ValueError("bidiag_svd(d,e): d and e must have the same leading dimensions.")
+def svd_vals(A, device=None, info=None, subset=None):
+    """The singular values of A [..., M, N] alone, descending (subset=(i0, i1): sv[i0:i1]): no vectors are formed and no product
+    runs. The bits of the sv of svd_decomp(A, subset). min(M, N) <= 2048."""
+    return _gesvdx(A, "svd_vals(A)", subset, False, device, info)
+
+
+def _bidiag_operands(d, e, what, asarray):
+    d, e = asarray(d, what), asarray(e, what)
+    if d.ndim < 1 or e.ndim < 1 or tuple(d.shape[:-1]) != tuple(e.shape[:-1]):
+        raise ValueError("%s: d and e must have the same leading dimensions." % what)
     K, J = d.shape[-1], e.shape[-1] + 1
     if K < 1 or J not in (K, K + 1):
-        raise ValueError("bidiag_svd(d,e): e must have len(d) - 1 or len(d) entries.")
+        raise ValueError("%s: e must have len(d) - 1 or len(d) entries." % what)
+    return d, e, K, J
+
+
+def _bdsvdx(d, e, what, subset, vectors, device, info):
+    """the selected-triplet solver on a bidiagonal matrix (csrc/bdsvdx.hip)"""
+    d, e, K, J = _bidiag_operands(d, e, what, _asarray)
+    if K > 2048:
+        raise ValueError("%s: K <= 2048." % what)
+    i0, i1 = (0, K) if subset is None else _subset(subset, K, what)
+    lead, k = d.shape[:-1], i1 - i0
+    sv = np.empty(lead + (k,))
+    U2 = np.empty(lead + (K, k)) if vectors else None
+    V2 = np.empty(lead + (k, J)) if vectors else None
+    fb = np.zeros(lead, dtype=np.int32)
+    if sv.size:
+        h = _lib.handle(device)
+        _lib.check(h.lib.nd4hip_dbdsvdx_batched_host(h.ptr, int(np.prod(lead, dtype=np.int64)), K, J, i0, i1, _ptr(d), _ptr(e),
+                                                     _ptr(U2) if vectors else None, _ptr(sv), _ptr(V2) if vectors else None,
+                                                     _ptr(fb) if info is not None else None))
+    if info is not None:
+        info["fallback"] = fb
+    return (U2, sv, V2) if vectors else sv
+
+
+def bidiag_svd(d, e, device=None, subset=None, info=None):
+    """SVD of the upper bidiagonal K x J matrix with diagonal d [..., K] and super-diagonal e [..., J-1], J = K or K + 1 (the
+    shapes bidiag_decomp produces), by the reference's divide & conquer (svd_dc.js:169-824):
+    (U2 [..., K, K], sv [..., K] >= 0 descending, V2 [..., J, J] with rows = right vectors), B = U2 diag(sv) V2[:K].
+    subset=(i0, i1) (opt-in): the triplets sv[i0:i1] alone, (U2 [..., K, k], sv [..., k], V2 [..., k, J]), by bisection and inverse
+    iteration on the Golub-Kahan form (csrc/bdsvdx.hip); info['fallback'] (int32 [...]) marks the members that went through the
+    divide & conquer solver instead (their sv is still the bisection's). K <= 2048 there."""
+    if subset is not None:
+        return _bdsvdx(d, e, "bidiag_svd(d,e, subset)", subset, True, device, info)
+    d, e, K, J = _bidiag_operands(d, e, "bidiag_svd(d,e)", _asarray)
     lead = d.shape[:-1]
     U2, sv, V2 = np.empty(lead + (K, K)), np.empty(lead + (K,)), np.empty(lead + (J, J))
     h = _lib.handle(device)
     _lib.check(h.lib.nd4hip_dbdsdc_batched(h.ptr, int(np.prod(lead, dtype=np.int64)), K, J, _ptr(d), _ptr(e), _ptr(U2), _ptr(sv), _ptr(V2)))
     return U2, sv, V2
+
+
+def bidiag_svdvals(d, e, device=None, subset=None, info=None):
+    """The singular values sv[i0:i1] (subset=None: all) of the bidiagonal matrix of bidiag_svd, descending, by bisection alone: the
+    bits of the sv of bidiag_svd(d, e, subset). K <= 2048."""
+    return _bdsvdx(d, e, "bidiag_svdvals(d,e)", subset, False, device, info)
 
 
 # ---------------------------------------------------------------------------------------------------
