@@ -697,6 +697,40 @@ int nd4hip_dsyevd_tr_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, co
 int nd4hip_dsyevx_tr_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* S, double* lambda, double* V);
 int nd4hip_dsyevx_tr_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* S, double* lambda, double* V);
 
+/* ---- herm_tridiag_factor / herm_tridiag_apply_q / herm_tridiag_decomp, eigen_herm and eigenvals_herm (csrc/hetrd.hip) ----
+ * The Hermitian counterparts of the four above; the host-pointer forms end in _host. H, F, tau, Z and V are complex128 as interleaved
+ * (re, im) doubles; d, e and lambda are real. H [batch,N,N] Hermitian, read only where i >= j, the imaginary part of its diagonal
+ * ignored, never written; 1 <= N <= 2048; N = 0 and an empty batch have nothing to do and write nothing.
+ *   zhetrd: H = Q tridiag(d, e) Q^H with d and e REAL, Q = H_0 H_1 ... H_{N-2}, H_k = I - tau_k v_k v_k^H with v_k zero in rows 0..k, 1
+ *           in row k+1 and its tail in F[k+2:, k] (LAPACK's zhetrd, lower, on row-major members): N - 1 reflectors, the last with an
+ *           empty tail. F [batch,N,N] carries d on its diagonal and e on its first subdiagonal, both with zero imaginary part, and zeros
+ *           above the diagonal; tau [batch,N-1] complex; d [batch,N]; e [batch,N-1] (tau and e may be NULL for N = 1). For the column
+ *           x = [alpha; tail]: tail = 0 and Im alpha = 0 give tau_k = 0, e_k = Re alpha; else e_k = beta = -sign(Re alpha) |x|
+ *           (sign(0) = +1), tau_k = ((beta - Re alpha) / beta, -Im alpha / beta), tail / (alpha - beta). Each member is scaled by the
+ *           exact power of two that puts max(|Re h_ij|, |Im h_ij|) in [0.5, 1): 2^m H gives the same tails, tau and Q bit for bit and
+ *           2^m d, 2^m e. NaN or Inf in what is read: ND4HIP_ERR_NOCONV, 'herm_tridiag_decomp(H): H contains NaN or Infinity in its
+ *           lower triangle.'; the outputs are then unspecified, the handle stays usable.
+ *   zunmtr: Z [batch,N,K] complex <- Q Z (adjoint = 1: Q^H Z) in place; Q is never formed. Enqueues only (the _dev form).
+ *   zheevd: lambda [batch,N] real, descending; V [batch,N,N] complex, the eigenvectors as columns, H V = V diag(lambda), V^H V = I, or
+ *           V = NULL for the values alone (neither Q nor zunmtr runs): zhetrd, then dsyevd_tr's real solver on (d, e), then zunmtr. The
+ *           phase of a vector is what the route produces: deterministic, not normalised. N = 1: lambda = Re h_00, V = 1 (NaN or Inf in h_00 is refused there too).
+ *   zheevx: the same for the subset i0 <= i < i1 of the descending spectrum (dstevx on (d, e)): lambda [batch,k], V [batch,N,k].
+ *           NaN or Inf: 'eigen_herm(H): H contains NaN or Infinity in its lower triangle.'.
+ * No sum depends on the run, the batch or a member's position. zhetrd and the two eigen routes synchronise. Profile ops
+ * "zhetrd_batched" (16/3 N^3 real flops), "zunmtr_batched" (8 N^2 K), "zheevd_batched", "zheevx_batched"; the stage times of the last
+ * two are read with nd4hip_dsyevd_last_stages and nd4hip_dsyevx_last_stages (the symmetrise stage is 0; zheevx reports the reduction
+ * and the solver's stages, not its zunmtr). */
+int nd4hip_zhetrd_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, const double* H, double* F, double* tau, double* d, double* e);
+int nd4hip_zhetrd_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, const double* H, double* F, double* tau, double* d, double* e);
+int nd4hip_zunmtr_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, int adjoint, const double* F, const double* tau,
+                               double* Z);
+int nd4hip_zunmtr_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, int adjoint, const double* F, const double* tau,
+                               double* Z);
+int nd4hip_zheevd_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, const double* H, double* lambda, double* V);
+int nd4hip_zheevd_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, const double* H, double* lambda, double* V);
+int nd4hip_zheevx_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* H, double* lambda, double* V);
+int nd4hip_zheevx_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* H, double* lambda, double* V);
+
 /* ---- eigenpairs in a value interval: eigen_sym(S, interval=(lo, hi)), tridiag_eigen(d, e, interval) (csrc/syevx.hip) ----
  * dstevxv, dsyevxv and dsyevxv_tr are dstevx, dsyevx and dsyevx_tr with the subset of each member chosen by value: bounds [batch,2]
  * holds (lo, hi) per member and selects the eigenvalues lo < lambda <= hi, which is exactly the subset (i0_b, i1_b) =

@@ -174,6 +174,15 @@ SIGNATURES = {
     "nd4hip_dormtr_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_int, c_dp, c_dp, c_dp]),
     "nd4hip_dsyevd_tr_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),
     "nd4hip_dsyevx_tr_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    # the Hermitian four (csrc/hetrd.hip): H, F, tau, Z, V complex128 as interleaved doubles
+    "nd4hip_zhetrd_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "nd4hip_zunmtr_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_int, c_dp, c_dp, c_dp]),
+    "nd4hip_zheevd_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_zheevx_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_zhetrd_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "nd4hip_zunmtr_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_int, c_dp, c_dp, c_dp]),
+    "nd4hip_zheevd_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_zheevx_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
     # (handle, batch, N, kcap, bounds, d, e | S, lambda, Z | V, range int32, kmax int64 on the host)
     "nd4hip_dstevxv_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, c_dp, ctypes.c_void_p, ctypes.POINTER(c_i64)]),
     "nd4hip_dstevxv_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, c_dp, ctypes.c_void_p, ctypes.POINTER(c_i64)]),

@@ -78,6 +78,8 @@ static int (*p_dsyevj[2])(nd4hip_handle*, int64_t, int64_t, const double*, doubl
 static int (*p_dsyevx[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, const double*, double*, double*);
 static int (*p_dsyevd_tr[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*, double*);
 static int (*p_dsyevx_tr[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, const double*, double*, double*);
+static int (*p_zheevd[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*, double*);
+static int (*p_zheevx[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, const double*, double*, double*);
 static int (*p_dsygvd[2])(nd4hip_handle*, int, int64_t, int64_t, const double*, const double*, int64_t, double*, double*, int32_t*);
 static int (*p_dstcnt[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, const double*, const double*, int32_t*);
 static int (*p_dstevx[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, const double*, const double*, double*, double*);
@@ -190,6 +192,8 @@ static int load_library(void) {
   SYM(p_dsyevx[0], "nd4hip_dsyevx_batched_host"); SYM(p_dsyevx[1], "nd4hip_dsyevx_batched_dev");   /* this pair's host form ends in _host */
   SYM(p_dsyevd_tr[0], "nd4hip_dsyevd_tr_batched_host"); SYM(p_dsyevd_tr[1], "nd4hip_dsyevd_tr_batched_dev");   /* and so do these two */
   SYM(p_dsyevx_tr[0], "nd4hip_dsyevx_tr_batched_host"); SYM(p_dsyevx_tr[1], "nd4hip_dsyevx_tr_batched_dev");
+  SYM(p_zheevd[0], "nd4hip_zheevd_batched_host"); SYM(p_zheevd[1], "nd4hip_zheevd_batched_dev");
+  SYM(p_zheevx[0], "nd4hip_zheevx_batched_host"); SYM(p_zheevx[1], "nd4hip_zheevx_batched_dev");
   SYM2(p_dsygvd, "nd4hip_dsygvd_batched");
   SYM(p_dstcnt[0], "nd4hip_dstcnt_batched_host"); SYM(p_dstcnt[1], "nd4hip_dstcnt_batched_dev");
   SYM(p_dstevx[0], "nd4hip_dstevx_batched_host"); SYM(p_dstevx[1], "nd4hip_dstevx_batched_dev");
@@ -857,6 +861,53 @@ static napi_value js_dsyevxals_tr(napi_env env, napi_callback_info info) {
   FAIL_IF(p_dsyevx_tr[S.dev](g_handle, batch, N, i0, i1, (const double*)S.p, (double*)L.p, NULL));
   return NULL;
 }
+/* zheevd_batched(batch, N, H, L, V) / zheevdals_batched(batch, N, H, L) / zheevx_batched(batch, N, i0, i1, H, L, V) /
+ * zheevxals_batched(batch, N, i0, i1, H, L)   (eigen_herm / eigenvals_herm, csrc/hetrd.hip: H and V are complex128 as interleaved
+ * doubles in Float64Arrays of twice the element count, L is real) */
+static napi_value js_zheevd(napi_env env, napi_callback_info info) {
+  ARGS(5, "zheevd_batched");
+  int64_t batch, N; opnd H, L, V;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || F64(2, H) || F64(3, L) || F64(4, V)) return NULL;
+  NEED(batch >= 0 && N >= 0 && (size_t)(2 * batch * N * N) <= H.len && (size_t)(batch * N) <= L.len && (size_t)(2 * batch * N * N) <= V.len,
+       "zheevd_batched: buffer too small");
+  SAME_SIDE(H.dev == L.dev && L.dev == V.dev, "zheevd_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_zheevd[H.dev](g_handle, batch, N, (const double*)H.p, (double*)L.p, (double*)V.p));
+  return NULL;
+}
+static napi_value js_zheevdals(napi_env env, napi_callback_info info) {
+  ARGS(4, "zheevdals_batched");
+  int64_t batch, N; opnd H, L;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || F64(2, H) || F64(3, L)) return NULL;
+  NEED(batch >= 0 && N >= 0 && (size_t)(2 * batch * N * N) <= H.len && (size_t)(batch * N) <= L.len, "zheevdals_batched: buffer too small");
+  SAME_SIDE(H.dev == L.dev, "zheevdals_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_zheevd[H.dev](g_handle, batch, N, (const double*)H.p, (double*)L.p, NULL));
+  return NULL;
+}
+static napi_value js_zheevx(napi_env env, napi_callback_info info) {
+  ARGS(7, "zheevx_batched");
+  int64_t batch, N, i0, i1; opnd H, L, V;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || get_i64(env, a[2], &i0) || get_i64(env, a[3], &i1) || F64(4, H) || F64(5, L) ||
+      F64(6, V)) return NULL;
+  NEED(batch >= 0 && N >= 0 && 0 <= i0 && i0 <= i1 && i1 <= N && (size_t)(2 * batch * N * N) <= H.len && (size_t)(batch * (i1 - i0)) <= L.len &&
+       (size_t)(2 * batch * N * (i1 - i0)) <= V.len, "zheevx_batched: bad subset or buffer too small");
+  SAME_SIDE(H.dev == L.dev && L.dev == V.dev, "zheevx_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_zheevx[H.dev](g_handle, batch, N, i0, i1, (const double*)H.p, (double*)L.p, (double*)V.p));
+  return NULL;
+}
+static napi_value js_zheevxals(napi_env env, napi_callback_info info) {
+  ARGS(6, "zheevxals_batched");
+  int64_t batch, N, i0, i1; opnd H, L;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || get_i64(env, a[2], &i0) || get_i64(env, a[3], &i1) || F64(4, H) || F64(5, L)) return NULL;
+  NEED(batch >= 0 && N >= 0 && 0 <= i0 && i0 <= i1 && i1 <= N && (size_t)(2 * batch * N * N) <= H.len && (size_t)(batch * (i1 - i0)) <= L.len,
+       "zheevxals_batched: bad subset or buffer too small");
+  SAME_SIDE(H.dev == L.dev, "zheevxals_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_zheevx[H.dev](g_handle, batch, N, i0, i1, (const double*)H.p, (double*)L.p, NULL));
+  return NULL;
+}
 /* dsygvd_batched(algo, batch, N, A, B, strideB, L, X) / dsygvals_batched(algo, batch, N, A, B, strideB, L)   (eigen_sym_gen /
  * eigenvals_sym_gen: A x = lambda B x; algo 0 dc, 1 jacobi; strideB N*N or 0 = one B; the sweep counts are not asked for) */
 static napi_value js_dsygvd(napi_env env, napi_callback_info info) {
@@ -1429,6 +1480,10 @@ static napi_value init(napi_env env, napi_value exports) {
     {"dsyevdals_tr_batched", NULL, js_dsyevdals_tr, NULL, NULL, NULL, napi_default, NULL},
     {"dsyevx_tr_batched", NULL, js_dsyevx_tr, NULL, NULL, NULL, napi_default, NULL},
     {"dsyevxals_tr_batched", NULL, js_dsyevxals_tr, NULL, NULL, NULL, napi_default, NULL},
+    {"zheevd_batched", NULL, js_zheevd, NULL, NULL, NULL, napi_default, NULL},
+    {"zheevdals_batched", NULL, js_zheevdals, NULL, NULL, NULL, napi_default, NULL},
+    {"zheevx_batched", NULL, js_zheevx, NULL, NULL, NULL, napi_default, NULL},
+    {"zheevxals_batched", NULL, js_zheevxals, NULL, NULL, NULL, napi_default, NULL},
     {"dsygvd_batched", NULL, js_dsygvd, NULL, NULL, NULL, napi_default, NULL},
     {"dsygvals_batched", NULL, js_dsygvals, NULL, NULL, NULL, napi_default, NULL},
     {"dstcnt_batched", NULL, js_dstcnt, NULL, NULL, NULL, napi_default, NULL},

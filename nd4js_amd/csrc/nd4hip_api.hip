@@ -827,6 +827,52 @@ extern "C" int nd4hip_dsyevx_tr_batched_dev(nd4hip_handle* h, int64_t batch, int
   return 0;
 }
 
+// ---- Hermitian tridiagonal reduction, its Q and the eigen routes on them (hetrd.hip): complex128 operands as
+// interleaved doubles. The argument checks come first: they need no handle. Flops are real ones: four times the real routes' counts
+// where the operands are complex (16/3 N^3 for the reduction, 8 N^2 K for Q Z); the real solver's 2 N^3 stay
+extern "C" int nd4hip_zhetrd_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* H, double* F, double* tau, double* d, double* e) {
+  ND4_ARGS(nd4_args_hetrd(batch, N, H, F, tau, d, e));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zhetrd_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  const double n2 = (double)N * N;
+  Nd4Prof prof(h, "zhetrd_batched", batch * (16.0 / 3.0 * n2 * N), 16.0 * batch * (double)(N * N / 2 + N * N + 2 * N));
+  const int64_t ne = N > 1 ? N - 1 : 0;
+  ND4_FOR_CHUNKS(batch)
+    ND4_TRY(nd4_hetrd_run(h, nb, N, H + 2 * b0 * N * N, F + 2 * b0 * N * N, tau ? tau + 2 * b0 * ne : nullptr, d + b0 * N, e ? e + b0 * ne : nullptr));
+  return 0;
+}
+extern "C" int nd4hip_zunmtr_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, int adjoint, const double* F, const double* tau,
+                                         double* Z) {
+  ND4_ARGS(nd4_args_unmtr(batch, N, K, adjoint, F, tau, Z));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zunmtr_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "zunmtr_batched", batch * (8.0 * N * (double)N * K), 16.0 * batch * (double)(N * N / 2 + 2 * N * K));
+  const int64_t ne = N > 1 ? N - 1 : 0;
+  ND4_FOR_CHUNKS(batch)
+    ND4_TRY(nd4_zunmtr(h, nb, N, K, adjoint != 0, F + 2 * b0 * N * N, tau ? tau + 2 * b0 * ne : nullptr, Z + 2 * b0 * N * K));
+  return 0;
+}
+extern "C" int nd4hip_zheevd_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* H, double* lambda, double* V) {
+  ND4_ARGS(nd4_args_heevd(batch, N, H, lambda));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zheevd_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  const double n3 = (double)N * N * N;
+  Nd4Prof prof(h, "zheevd_batched", batch * ((16.0 / 3.0 + 2.0 + (V ? 8.0 : 0.0)) * n3), 8.0 * batch * (double)(N * N + N + (V ? 2 * N * N : 0)));
+  ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_zheevd(h, nb, N, H + 2 * b0 * N * N, lambda + b0 * N, V ? V + 2 * b0 * N * N : nullptr));
+  return 0;
+}
+extern "C" int nd4hip_zheevx_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* H, double* lambda,
+                                         double* V) {
+  ND4_ARGS(nd4_args_heevx(batch, N, i0, i1, H, lambda));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zheevx_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  const int64_t k = i1 - i0;
+  const double n2 = (double)N * N;
+  Nd4Prof prof(h, "zheevx_batched", batch * (16.0 / 3.0 * n2 * N + (V ? 8.0 * n2 * k : 0.0)), 8.0 * batch * (double)(N * N + k + (V ? 2 * N * k : 0)));
+  ND4_FOR_CHUNKS(batch) ND4_TRY(nd4_zheevx(h, nb, N, i0, i1, H + 2 * b0 * N * N, lambda + b0 * k, V ? V + 2 * b0 * N * k : nullptr));
+  return 0;
+}
+
 // ---- the eigenpairs in a value interval (syevx.hip). The argument checks come first: they need no handle. How many
 // values an interval holds is not known when the profile opens: it counts the reduction and the two Sturm counts per member.
 namespace {

@@ -356,6 +356,32 @@ inline int nd4_args_syevd_tr(int64_t batch, int64_t N, const void* S, const void
 inline int nd4_args_syevx_tr(int64_t batch, int64_t N, int64_t i0, int64_t i1, const void* S, const void* lambda) {
   return nd4_args_subset("dsyevx_tr_batched", batch, N, i0, i1, {S, lambda});
 }
+// ---- Hermitian tridiagonal reduction, its Q, and the eigen routes on it (hetrd.hip): the checks of the four above in the same order
+inline int nd4_args_hetrd(int64_t batch, int64_t N, const void* H, const void* F, const void* tau, const void* d, const void* e) {
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_zhetrd_batched: negative extent");
+  ND4_CHECK_ARG(N <= 2048, "nd4hip_zhetrd_batched: N <= 2048");
+  if (batch == 0 || N == 0) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(H && F && d && ((tau && e) || N < 2), "nd4hip_zhetrd_batched: NULL pointer");
+  return ND4_ARGS_GO;
+}
+inline int nd4_args_unmtr(int64_t batch, int64_t N, int64_t K, int adjoint, const void* F, const void* tau, const void* Z) {
+  ND4_CHECK_ARG(batch >= 0 && N >= 0 && K >= 0, "nd4hip_zunmtr_batched: negative extent");
+  ND4_CHECK_ARG(N <= 2048, "nd4hip_zunmtr_batched: N <= 2048");
+  ND4_CHECK_ARG(adjoint == 0 || adjoint == 1, "nd4hip_zunmtr_batched: adjoint must be 0 or 1");
+  if (batch == 0 || N == 0 || K == 0) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(F && (tau || N < 2) && Z, "nd4hip_zunmtr_batched: NULL pointer");
+  return ND4_ARGS_GO;
+}
+inline int nd4_args_heevd(int64_t batch, int64_t N, const void* H, const void* lambda) {
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_zheevd_batched: negative extent");
+  ND4_CHECK_ARG(N <= 2048, "nd4hip_zheevd_batched: N <= 2048");
+  if (batch == 0 || N == 0) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(H && lambda, "nd4hip_zheevd_batched: NULL pointer");
+  return ND4_ARGS_GO;
+}
+inline int nd4_args_heevx(int64_t batch, int64_t N, int64_t i0, int64_t i1, const void* H, const void* lambda) {
+  return nd4_args_subset("zheevx_batched", batch, N, i0, i1, {H, lambda});
+}
 inline int nd4_args_sygvd(int algo, int64_t batch, int64_t N, const void* A, const void* B, int64_t strideB, const void* lambda) {
   ND4_CHECK_ARG(algo == 0 || algo == 1, "nd4hip_dsygvd_batched: algo must be 0 (dc) or 1 (jacobi)");
   ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsygvd_batched: negative extent");

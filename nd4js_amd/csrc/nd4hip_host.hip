@@ -1063,6 +1063,58 @@ extern "C" int nd4hip_dsyevx_tr_batched_host(nd4hip_handle* h, int64_t batch, in
   return run_host(h, batch, ops, fn);
 }
 
+// Hermitian tridiagonal reduction, its Q and the eigen routes on them (hetrd.hip): complex operands move as elements of 2 D bytes; tau
+// and e are not moved for N = 1; V = NULL: the values alone
+extern "C" int nd4hip_zhetrd_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, const double* H, double* F, double* tau, double* d, double* e) {
+  ND4_ARGS(nd4_args_hetrd(batch, N, H, F, tau, d, e));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zhetrd_batched: NULL handle");
+  // the operands in the order H, F, d, [tau, e]
+  std::vector<Operand> ops{in_op(H, N * N, N * N, 2 * D), out_op(F, N * N, 2 * D), out_op(d, N)};
+  if (N >= 2) { ops.push_back(out_op(tau, N - 1, 2 * D)); ops.push_back(out_op(e, N - 1)); }
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return nd4hip_zhetrd_batched_dev(hd, nb, N, P(p, 0), P(p, 1), N >= 2 ? P(p, 3) : nullptr, P(p, 2), N >= 2 ? P(p, 4) : nullptr);
+  };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_zunmtr_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, int adjoint, const double* F, const double* tau,
+                                          double* Z) {
+  ND4_ARGS(nd4_args_unmtr(batch, N, K, adjoint, F, tau, Z));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zunmtr_batched: NULL handle");
+  // the operands in the order F, Z, [tau]
+  std::vector<Operand> ops{in_op(F, N * N, N * N, 2 * D), inout_op(Z, N * K, 2 * D)};
+  if (N >= 2) ops.push_back(in_op(tau, N - 1, N - 1, 2 * D));
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return nd4hip_zunmtr_batched_dev(hd, nb, N, K, adjoint, P(p, 0), N >= 2 ? P(p, 2) : nullptr, P(p, 1));
+  };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_zheevd_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, const double* H, double* lambda, double* V) {
+  ND4_ARGS(nd4_args_heevd(batch, N, H, lambda));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zheevd_batched: NULL handle");
+  // the operands that are wanted, in the order H, lambda, [V]
+  std::vector<Operand> ops{in_op(H, N * N, N * N, 2 * D), out_op(lambda, N)};
+  const int iv = V ? (int)ops.size() : -1;
+  if (V) ops.push_back(out_op(V, N * N, 2 * D));
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return nd4hip_zheevd_batched_dev(hd, nb, N, P(p, 0), P(p, 1), iv >= 0 ? P(p, iv) : nullptr);
+  };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_zheevx_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* H, double* lambda,
+                                          double* V) {
+  ND4_ARGS(nd4_args_heevx(batch, N, i0, i1, H, lambda));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zheevx_batched: NULL handle");
+  const int64_t k = i1 - i0;
+  // the operands that are wanted, in the order H, lambda, [V]
+  std::vector<Operand> ops{in_op(H, N * N, N * N, 2 * D), out_op(lambda, k)};
+  const int iv = V ? (int)ops.size() : -1;
+  if (V) ops.push_back(out_op(V, N * k, 2 * D));
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return nd4hip_zheevx_batched_dev(hd, nb, N, i0, i1, P(p, 0), P(p, 1), iv >= 0 ? P(p, iv) : nullptr);
+  };
+  return run_host(h, batch, ops, fn);
+}
+
 // The eigenpairs in a value interval (syevx.hip). bounds, the inputs and range travel through the driver. lambda and
 // the vectors do not: a chunk computes them into kcap-wide staging of its own and brings down the kmax columns it found, no more,
 // straight to their place in the caller's arrays. The padding up to the kmax of the whole call is then written on the host, from

@@ -214,6 +214,30 @@ size_t nd4_sytrd_ws_doubles(int64_t N);
 // eigen_sym(S, reduction='tridiag'): nd4_syevd / nd4_syevx with that reduction in place of nd4_gehrd, the vectors by nd4_ormtr
 int nd4_syevd_tr(nd4hip_handle* h, int64_t batch, int64_t N, const double* S, double* lambda, double* V);
 int nd4_syevx_tr(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* S, double* lambda, double* V);
+// Hermitian tridiagonal reduction, its Q and the eigen routes on them (hetrd.hip): complex128 operands (H, F, tau, Z,
+// V) as interleaved doubles, d, e and lambda real. Arguments already checked, batch in 1 .. 32768, 1 <= N <= 2048, K >= 1. nd4_hetrd is
+// nd4_sytrd's counterpart (mx ZERO on entry, *flag zero on entry; enqueues only), nd4_hetrd_run synchronises (one flag word), nd4_zunmtr
+// (Z [batch, N, K] in place) enqueues only. The five functions after them are the host-side arithmetic of the tiers: 0 = one
+// workgroup per member in LDS, 1 = one launch per column; bytes of dynamic LDS, row blocks, bytes of workspace per member.
+int nd4_hetrd(nd4hip_handle* h, int64_t batch, int64_t N, const double* H, double* F, double* tau, double* d, double* e, unsigned long long* mx,
+              bool unscale, int* flag);
+int nd4_hetrd_run(nd4hip_handle* h, int64_t batch, int64_t N, const double* H, double* F, double* tau, double* d, double* e);
+int nd4_zunmtr(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, bool adjoint, const double* F, const double* tau, double* Z);
+int nd4_hetrd_tier(int64_t N);
+size_t nd4_hetrd_lds(int64_t N);
+size_t nd4_zunmtr_lds(int64_t N);
+int64_t nd4_hetrd_blocks(int64_t N);
+size_t nd4_hetrd_ws_bytes(int64_t N);
+// the small kernels the routes share: d, e of F onto the diagonals of the real Tr [batch, N, N]; V [batch, N, k] complex = the transposed
+// rows of the real R [batch, k, N] (both enqueue only); the eigen routes at N = 1 (lambda = Re h_00, V = 1 or NULL; synchronises: NaN or
+// Inf is refused with eigen_herm's text)
+int nd4_hetrd_diagonals(nd4hip_handle* h, int64_t batch, int N, const double* F, double* Tr);
+int nd4_hetrd_rows_to_columns(nd4hip_handle* h, int64_t batch, int N, int k, const double* R, double* V);
+int nd4_hetrd_order_one(nd4hip_handle* h, int64_t batch, const double* H, double* lambda, double* V);
+// eigen_herm: every eigenpair by divide & conquer (syev.hip), the subset (i0, i1) by bisection and inverse iteration (hetrd.hip);
+// V = NULL: the values alone. Both synchronise
+int nd4_zheevd(nd4hip_handle* h, int64_t batch, int64_t N, const double* H, double* lambda, double* V);
+int nd4_zheevx(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* H, double* lambda, double* V);
 // generalised symmetric-definite eigenproblem (sygv.hip): arguments already checked, batch >= 1, 1 <= N; sB / sL 0 = one for all;
 // member0: index of the first member in the caller's batch (error text); nd4_sygvd synchronises
 int nd4_sygvd(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B, int64_t sB, double* lambda,

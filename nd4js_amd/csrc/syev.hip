@@ -323,3 +323,58 @@ int nd4_syevd_tr(nd4hip_handle* h, int64_t batch, int64_t N64, const double* S, 
   }
   return 0;
 }
+
+// eigen_herm / eigenvals_herm: the route of nd4_syevd_tr for a Hermitian H [batch, N, N] (complex128 as interleaved
+// doubles). nd4_hetrd (hetrd.hip) leaves the real scaled d and e on the diagonals of the complex F; hetrd_diagonals copies them to
+// the diagonals of a real N x N array, the layout steps 3-5 above read, so those kernels run unchanged. The vectors are
+// V = Q V2^T: the rows of V2 transposed into the complex V, then nd4_zunmtr; for the values alone neither runs. lambda [batch, N]
+// real descending, V [batch, N, N] complex (columns) or NULL. The symmetrise stage reads 0. Synchronises.
+int nd4_zheevd(nd4hip_handle* h, int64_t batch, int64_t N64, const double* H, double* lambda, double* V) {
+  ND4_CHECK_ARG(N64 >= 1 && N64 <= SYEV_MAXN, "nd4hip_zheevd_batched: the divide & conquer solver takes N <= %d", SYEV_MAXN);
+  ND4_CHECK_ARG(batch <= 32768, "nd4hip_zheevd_batched: batch %lld exceeds 32768 per call", (long long)batch);
+  if (N64 == 1) return nd4_hetrd_order_one(h, batch, H, lambda, V);
+  const int N = (int)N64;
+  Nd4WsScope scope(h);
+  const size_t nn = (size_t)N * N;
+  u64* mx = nullptr; int *kexp = nullptr, *flag = nullptr;
+  double *F, *Tr, *tau, *U2, *V2, *p, *q, *sv, *cs;
+  ND4_TRY(syev_alloc(h, (size_t)batch, &mx)); ND4_TRY(syev_alloc(h, (size_t)batch, &kexp)); ND4_TRY(syev_alloc(h, 1, &flag));
+  ND4_TRY(syev_alloc(h, (size_t)batch, &cs)); ND4_TRY(syev_alloc(h, 2 * (size_t)batch * N, &tau));
+  ND4_TRY(syev_alloc(h, (size_t)batch * N, &p)); ND4_TRY(syev_alloc(h, (size_t)batch * N, &q)); ND4_TRY(syev_alloc(h, (size_t)batch * N, &sv));
+  ND4_TRY(syev_alloc(h, 2 * (size_t)batch * nn, &F)); ND4_TRY(syev_alloc(h, (size_t)batch * nn, &Tr));
+  ND4_TRY(syev_alloc(h, (size_t)batch * nn, &U2)); ND4_TRY(syev_alloc(h, (size_t)batch * nn, &V2));
+  ND4_HIP(hipMemsetAsync(mx, 0, sizeof(u64) * (size_t)batch, h->stream));
+  ND4_HIP(hipMemsetAsync(flag, 0, sizeof(int), h->stream));
+  SyevStamps st(h);
+  st.mark(); st.mark();                                       // no symmetrisation
+  ND4_TRY(nd4_hetrd(h, batch, N, H, F, tau, nullptr, nullptr, mx, false, flag));
+  ND4_TRY(nd4_hetrd_diagonals(h, batch, N, F, Tr));
+  hipLaunchKernelGGL(syev_tr_deflate, dim3((unsigned)batch), dim3(64), 0, h->stream, Tr, N);
+  st.mark();
+  hipLaunchKernelGGL(syev_shift_chol, dim3((unsigned)batch), dim3(64), 0, h->stream, Tr, N, mx, p, q, cs, kexp, flag);
+  ND4_HIP(hipGetLastError());
+  st.mark();
+  ND4_TRY(nd4_bdsdc_rows(h, batch, N, N, p, q, U2, sv, V2));  // synchronises
+  st.mark();
+  const long total = (long)batch * N;
+  hipLaunchKernelGGL(syev_values, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, sv, Tr, N, total, cs, kexp, mx, lambda,
+                     V ? V2 : nullptr);
+  ND4_HIP(hipGetLastError());
+  if (V) {
+    ND4_TRY(nd4_hetrd_rows_to_columns(h, batch, N, N, V2, V));
+    ND4_TRY(nd4_zunmtr(h, batch, N, N, false, F, tau, V));
+  }
+  st.mark();
+  void* hp = nullptr;
+  ND4_TRY(nd4_pinned(h, sizeof(int), &hp));
+  int* host = static_cast<int*>(hp);
+  ND4_HIP(hipMemcpyAsync(host, flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  ND4_HIP(hipStreamSynchronize(h->stream));
+  st.collect();
+  h->syev_stage_ms[0] = 0.0;                                  // (the time between two event records, not a stage)
+  if (host[0] != 0) {
+    nd4_set_error("eigen_herm(H): H contains NaN or Infinity in its lower triangle.");
+    return ND4HIP_ERR_NOCONV;
+  }
+  return 0;
+}

@@ -959,6 +959,96 @@ def tridiag_decomp(S):
     return tridiag_apply_q(F, tau, eye), d, e
 
 
+def _chk_herm(t, name, what):
+    """a contiguous complex128 CUDA tensor without a lazy conjugate or negative bit (the kernels read the stored numbers); a
+    float64 tensor is sent to eigen_sym"""
+    if isinstance(t, torch.Tensor) and not t.is_complex():
+        raise TypeError("%s: %s.dtype must be complex128; a real symmetric matrix goes to eigen_sym / tridiag_factor." % (what, name))
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.complex128 and t.is_contiguous()):
+        raise TypeError("%s: %s must be a contiguous complex128 CUDA tensor" % (what, name))
+    return t.resolve_conj().resolve_neg()
+
+
+def herm_tridiag_factor(H):
+    """device-resident la.herm_tridiag_factor: (F complex128 [..., N, N], tau complex128 [..., N-1], d float64 [..., N], e float64
+    [..., N-1]), the same bits"""
+    from .la import _herm_shape
+    what = "herm_tridiag_factor(H)"
+    H = _chk_herm(H, "H", what)
+    N = _herm_shape(H.dim(), tuple(H.shape), what)
+    lead, ne = tuple(H.shape[:-2]), max(N - 1, 0)
+    F, tau = (torch.empty(lead + tail, dtype=torch.complex128, device=H.device) for tail in ((N, N), (ne,)))
+    d, e = (torch.empty(lead + tail, dtype=torch.float64, device=H.device) for tail in ((N,), (ne,)))
+    if F.numel():
+        h = _h(H)
+        _lib.check(h.lib.nd4hip_zhetrd_batched_dev(h.ptr, _batch(lead), N, _p(H), _p(F), _p(tau), _p(d), _p(e)))
+    return F, tau, d, e
+
+
+def herm_tridiag_apply_q(F, tau, Z, adjoint=False):
+    """device-resident la.herm_tridiag_apply_q: Q Z (adjoint: Q^H Z) as a new complex128 tensor, the same bits; a float64 Z is promoted;
+    only enqueued"""
+    from .la import _tridiag_fz
+    what = "herm_tridiag_apply_q(F,tau,Z)"
+    for a in (F, tau):
+        if not (isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == torch.complex128 and a.is_contiguous()):
+            raise TypeError("%s: F and tau must be contiguous complex128 CUDA tensors." % what)
+    if not (isinstance(Z, torch.Tensor) and Z.is_cuda and Z.dtype in (torch.float64, torch.complex128)):
+        raise TypeError("%s: Z must be a complex128 or float64 CUDA tensor." % what)
+    F, tau = F.resolve_conj().resolve_neg(), tau.resolve_conj().resolve_neg()
+    N, K = _tridiag_fz(tuple(F.shape), tuple(tau.shape), tuple(Z.shape), what)
+    out = Z.to(torch.complex128).resolve_conj().resolve_neg().clone(memory_format=torch.contiguous_format)   # the product is made in place
+    if out.numel():
+        h = _h(F)
+        _lib.check(h.lib.nd4hip_zunmtr_batched_dev(h.ptr, _batch(F.shape[:-2]), N, K, 1 if adjoint else 0, _p(F), _p(tau), _p(out)))
+    return out
+
+
+def herm_tridiag_decomp(H):
+    """device-resident la.herm_tridiag_decomp: (Q complex128 [..., N, N], d, e), Q = herm_tridiag_apply_q(F, tau, I)"""
+    F, tau, d, e = herm_tridiag_factor(H)
+    N = F.shape[-1]
+    eye = torch.eye(N, dtype=torch.float64, device=F.device).expand(F.shape)
+    return herm_tridiag_apply_q(F, tau, eye), d, e
+
+
+def _heev(H, what, vectors, subset):
+    from .la import _subset
+    if subset is not None:
+        what = what.replace("(H)", "(H, subset)")
+    H = _chk_herm(H, "H", what)
+    if H.dim() < 2:
+        raise ValueError("%s: H.ndim must be at least 2." % what)
+    N = H.shape[-1]
+    if H.shape[-2] != N:
+        raise ValueError("%s: H must be quadratic." % what)
+    lead = tuple(H.shape[:-2])
+    if subset is not None:                                                  # bisection and inverse iteration on (d, e)
+        i0, i1 = _subset(subset, N, what)
+        L = torch.empty(lead + (i1 - i0,), dtype=torch.float64, device=H.device)
+        V = torch.empty(lead + (N, i1 - i0), dtype=torch.complex128, device=H.device) if vectors else None
+        if L.numel():
+            h = _h(H)
+            _lib.check(h.lib.nd4hip_zheevx_batched_dev(h.ptr, _batch(lead), N, i0, i1, _p(H), _p(L), _p(V) if vectors else None))
+        return (L, V) if vectors else L
+    L = torch.empty(lead + (N,), dtype=torch.float64, device=H.device)
+    V = torch.empty(lead + (N, N), dtype=torch.complex128, device=H.device) if vectors else None
+    h = _h(H)
+    _lib.check(h.lib.nd4hip_zheevd_batched_dev(h.ptr, _batch(lead), N, _p(H), _p(L), _p(V) if vectors else None))
+    return (L, V) if vectors else L
+
+
+def eigen_herm(H, subset=None):
+    """device-resident la.eigen_herm: (eigenvalues float64 [..., N] descending, eigenvectors complex128 [..., N, N] as columns) of the
+    Hermitian complex128 H, read only where i >= j and not written; subset=(i0, i1) as eigen_sym's. The same bits."""
+    return _heev(H, "eigen_herm(H)", True, subset)
+
+
+def eigenvals_herm(H, subset=None):
+    """device-resident la.eigenvals_herm: the eigenvalues of eigen_herm alone, the same bits"""
+    return _heev(H, "eigenvals_herm(H)", False, subset)
+
+
 def _stevx(d, e, subset, what, vectors, interval=None, info=None):
     from .la import _interval_what, _subset, _tridiag_args
     if interval is not None:

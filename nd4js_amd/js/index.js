@@ -1651,6 +1651,52 @@ function makeLa(NDA, fallback, SolveError, Complex) {
   };
   eigSym('eigen_sym', true); eigSym('eigenvals_sym', false);
 
+  /* ---- eigen_herm / eigenvals_herm, csrc/hetrd.hip (DESIGN.md 4.24): H [..., N, N] complex128 Hermitian, read only where i >= j, the
+   * imaginary part of its diagonal ignored, not written -> [eigenvalues float64 [..., N] descending, eigenvectors complex128
+   * [..., N, N] as columns], resp. the eigenvalues alone (the same bits). Host arrays of the host module (install(nd): complex128
+   * lives in its Complex128Array) or complex DeviceNDArrays in, the same kind out. opts.subset: [i0, i1] as for eigen_sym. A real
+   * matrix is sent to eigen_sym. Not enumerable, like eigen_sym. ---- */
+  const eigHerm = (name, vectors) => {
+    const f = function (H, opts) {
+      const subset = opts == null ? undefined : opts.subset;
+      if (subset != null && (!(Array.isArray(subset) || ArrayBuffer.isView(subset)) || subset.length !== 2))
+        throw new Error(`${name}(H, {subset}): subset must be [i0, i1] with 0 <= i0 <= i1 <= N.`);
+      H = asarray(H);
+      if (dtypeOf(H) !== 'complex128') throw new TypeError(`${name}(H): H.dtype must be complex128; a real symmetric matrix goes to eigen_sym.`);
+      if (H.ndim < 2) throw new Error(`${name}(H): H.ndim must be at least 2.`);
+      const nd_ = H.ndim, N = H.shape[nd_ - 1];
+      if (H.shape[nd_ - 2] != N) throw new Error(`${name}(H): H must be quadratic.`);
+      let i0 = 0, i1 = N;
+      if (subset != null) {
+        [i0, i1] = subset;
+        if (!(Number.isInteger(i0) && Number.isInteger(i1) && 0 <= i0 && i0 <= i1 && i1 <= N))
+          throw new Error(`${name}(H, {subset}): subset must be [i0, i1] with 0 <= i0 <= i1 <= N, got [${i0}, ${i1}] for N = ${N}.`);
+        if (i1 === i0) throw new Error(`${name}(H, {subset}): the subset [${i0}, ${i1}] is empty, and an NDArray has no axis of length 0.`);
+      }
+      const Cx = needComplex(name);
+      const k = i1 - i0, batch = prod(H.shape, 0, nd_ - 2), dev = isDev(H), temps = [], lead = Array.from(H.shape.subarray(0, nd_ - 2));
+      const L = alloc(dev, batch * k), V = vectors ? alloc(dev, 2 * batch * N * k) : null;
+      try {
+        const Hd = view(opZ(H, dev, temps), 0);
+        if (subset != null) {
+          if (vectors) native().zheevx_batched(batch, N, i0, i1, Hd, view(L, 0), view(V, 0));
+          else native().zheevxals_batched(batch, N, i0, i1, Hd, view(L, 0));
+        }
+        else if (vectors) native().zheevd_batched(batch, N, Hd, view(L, 0), view(V, 0));
+        else native().zheevdals_batched(batch, N, Hd, view(L, 0));
+      }
+      catch (e) { if (dev) { L.free(); if (V) V.free(); } throw e; }
+      finally { release(temps); }
+      const Lw = wrap(dev, lead.concat([k]), L);
+      if (!vectors) return Lw;
+      const vs = Int32Array.from(lead.concat([N, k]));
+      return [Lw, dev ? new DeviceNDArray(vs, V, Cx) : new NDA(vs, complexOver(Cx, V))];
+    };
+    Object.defineProperty(f, 'name', {value: name});
+    Object.defineProperty(la, name, {value: f, writable: true, enumerable: false, configurable: true});
+  };
+  eigHerm('eigen_herm', true); eigHerm('eigenvals_herm', false);
+
   /* ---- eigen_sym_gen / eigenvals_sym_gen, csrc/sygv.hip: A x = lambda B x, A symmetric, B symmetric positive definite, both read
    * only in their lower triangles. A [..., N, N]; B of the same shape or exactly [N, N] (one B for every member, factorised once)
    * -> [eigenvalues [..., N] descending, eigenvectors [..., N, N] as columns with X^T B X = I], resp. the eigenvalues alone (the
@@ -1892,7 +1938,7 @@ function install(nd, opts) {
     return f;
   };
   for (const k of Object.keys(original)) Object.defineProperty(patched, k, {value: route(k), writable: true, enumerable: true, configurable: true});
-  for (const k of ['to_device', 'to_host', 'synchronize', 'DeviceNDArray', 'profile_enable', 'profile_last', 'schur_qrfrancis', 'concat', 'stack', 'zip_elems', 'eigen_sym', 'eigenvals_sym', 'eigen_sym_gen', 'eigenvals_sym_gen'])   // §8f N3 / §8b extensions, not in the reference (schur_qrfrancis: its private step)
+  for (const k of ['to_device', 'to_host', 'synchronize', 'DeviceNDArray', 'profile_enable', 'profile_last', 'schur_qrfrancis', 'concat', 'stack', 'zip_elems', 'eigen_sym', 'eigenvals_sym', 'eigen_sym_gen', 'eigenvals_sym_gen', 'eigen_herm', 'eigenvals_herm'])   // §8f N3 / §8b extensions, not in the reference (schur_qrfrancis: its private step)
     Object.defineProperty(patched, k, {value: acc[k], writable: true, enumerable: false, configurable: true});
   if (!target) { try { nd.la = patched; } catch (e) { /* exported getter: caller uses the returned object */ } }
   patched.__nd4hip_original__ = original;

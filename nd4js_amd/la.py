@@ -14,6 +14,9 @@ JS wrapper nd4js_amd/js/index.js over the N-API shim; both call the same libnd4h
                                    subset=(i0, i1) (opt-in): a slice of the descending spectrum -> nd4hip_dsyevx_batched_host
                                    reduction='tridiag' (opt-in): the symmetric reduction of csrc/sytrd.hip -> nd4hip_dsyevd_tr_batched_host, nd4hip_dsyevx_tr_batched_host
   tridiag_factor(S), tridiag_apply_q(F, tau, Z), tridiag_decomp(S)   not in the reference   -> nd4hip_dsytrd_batched_host, nd4hip_dormtr_batched_host
+  herm_tridiag_factor(H), herm_tridiag_apply_q(F, tau, Z), herm_tridiag_decomp(H)   complex128 Hermitian H, not in the reference
+                                   -> nd4hip_zhetrd_batched_host, nd4hip_zunmtr_batched_host (csrc/hetrd.hip)
+  eigen_herm(H, subset), eigenvals_herm(H, subset)   not in the reference   -> nd4hip_zheevd_batched_host, nd4hip_zheevx_batched_host
   tridiag_eigen(d, e), tridiag_eigenvals(d, e), tridiag_count(d, e, x)   not in the reference   -> nd4hip_dstevx_batched_host, nd4hip_dstcnt_batched_host
                                    interval=(lo, hi) (opt-in, here and in eigen_sym): the eigenvalues in (lo, hi] -> nd4hip_dstevxv_batched_host,
                                    nd4hip_dsyevxv_batched_host, nd4hip_dsyevxv_tr_batched_host
@@ -1440,6 +1443,112 @@ def tridiag_decomp(S, device=None):
     F, tau, d, e = tridiag_factor(S, device)
     N = F.shape[-1]
     return tridiag_apply_q(F, tau, np.broadcast_to(np.eye(N), F.shape), False, device), d, e
+
+
+def _herm_h(H, what):
+    """the dtype rule of the Hermitian functions on host arrays: complex128 as it is; a real matrix is sent to eigen_sym"""
+    H = np.asarray(H)
+    if H.dtype.kind != "c":
+        raise TypeError("%s: H.dtype must be complex128; a real symmetric matrix goes to eigen_sym / tridiag_factor." % what)
+    if H.dtype != np.complex128:
+        raise TypeError("%s: only complex128 runs on the GPU path, got %s" % (what, H.dtype))
+    return np.ascontiguousarray(H)
+
+
+def _herm_shape(H_ndim, H_shape, what):
+    """the shape checks of herm_tridiag_factor / herm_tridiag_decomp, shared with dev.py; returns N"""
+    if H_ndim < 2:
+        raise ValueError("%s: H.ndim must be at least 2." % what)
+    if H_shape[-2] != H_shape[-1]:
+        raise ValueError("%s: H must be quadratic." % what)
+    if H_shape[-1] > 2048:
+        raise ValueError("%s: N <= 2048." % what)
+    return int(H_shape[-1])
+
+
+def herm_tridiag_factor(H, device=None):
+    """(F complex128 [..., N, N], tau complex128 [..., max(N-1, 0)], d float64 [..., N], e float64 [..., max(N-1, 0)]) with
+    H = Q tridiag(d, e) Q^H for the Hermitian complex128 H, read only where i >= j (the imaginary part of its diagonal is ignored): d and
+    e are real, Q = H_0 H_1 ... H_{N-2}, H_k = I - tau_k v_k v_k^H, v_k zero in rows 0..k, 1 in row k+1, its tail in F[k+2:, k] (LAPACK's
+    zhetrd, lower): N - 1 reflectors, the last with an empty tail, there to make e_{N-2} real. F carries d on its diagonal, e on its first
+    subdiagonal and zeros above. NaN or Infinity in what is read raises Nd4HipError with code -3. N <= 2048 (csrc/hetrd.hip)."""
+    what = "herm_tridiag_factor(H)"
+    H = _herm_h(H, what)
+    N = _herm_shape(H.ndim, H.shape, what)
+    lead, ne = H.shape[:-2], max(N - 1, 0)
+    F, tau = np.empty(H.shape, dtype=np.complex128), np.empty(lead + (ne,), dtype=np.complex128)
+    d, e = np.empty(lead + (N,)), np.empty(lead + (ne,))
+    if F.size:
+        h = _lib.handle(device)
+        _lib.check(h.lib.nd4hip_zhetrd_batched_host(h.ptr, int(np.prod(lead, dtype=np.int64)), N, _ptr(H), _ptr(F), _ptr(tau), _ptr(d), _ptr(e)))
+    return F, tau, d, e
+
+
+def herm_tridiag_apply_q(F, tau, Z, adjoint=False, device=None):
+    """Q Z (adjoint: Q^H Z), complex128, for the Q of herm_tridiag_factor's (F, tau) and Z [..., N, K] with the leading dimensions of F; a
+    float64 Z is promoted. Q is never formed: N <= 96 reflector by reflector in LDS, above in compact WY blocks on the complex GEMM."""
+    what = "herm_tridiag_apply_q(F,tau,Z)"
+    F, tau, Z = np.asarray(F), np.asarray(tau), np.asarray(Z)
+    if F.dtype != np.complex128 or tau.dtype != np.complex128:
+        raise TypeError("%s: F and tau must be complex128." % what)
+    if Z.dtype != np.complex128 and Z.dtype != np.float64:
+        raise TypeError("%s: Z must be complex128 or float64." % what)
+    N, K = _tridiag_fz(F.shape, tau.shape, Z.shape, what)
+    F, tau = np.ascontiguousarray(F), np.ascontiguousarray(tau)
+    out = np.array(Z, dtype=np.complex128, order="C")                       # a copy: the product is made in place
+    if out.size:
+        h = _lib.handle(device)
+        _lib.check(h.lib.nd4hip_zunmtr_batched_host(h.ptr, int(np.prod(F.shape[:-2], dtype=np.int64)), N, K, 1 if adjoint else 0, _ptr(F),
+                                                    _ptr(tau), _ptr(out)))
+    return out
+
+
+def herm_tridiag_decomp(H, device=None):
+    """(Q complex128 [..., N, N], d [..., N], e [..., N-1]) with H = Q tridiag(d, e) Q^H: herm_tridiag_factor, and
+    Q = herm_tridiag_apply_q(F, tau, I), the same bits."""
+    F, tau, d, e = herm_tridiag_factor(H, device)
+    N = F.shape[-1]
+    return herm_tridiag_apply_q(F, tau, np.broadcast_to(np.eye(N), F.shape), False, device), d, e
+
+
+def _heev(H, what, vectors, device, subset):
+    if subset is not None:
+        what = what.replace("(H)", "(H, subset)")
+    H = _herm_h(H, what)
+    if H.ndim < 2:
+        raise ValueError("%s: H.ndim must be at least 2." % what)
+    if H.shape[-2] != H.shape[-1]:
+        raise ValueError("%s: H must be quadratic." % what)
+    N = H.shape[-1]
+    batch = int(np.prod(H.shape[:-2], dtype=np.int64))
+    if subset is not None:                                                  # bisection and inverse iteration on (d, e)
+        i0, i1 = _subset(subset, N, what)
+        L = np.empty(H.shape[:-2] + (i1 - i0,))
+        V = np.empty(H.shape[:-1] + (i1 - i0,), dtype=np.complex128) if vectors else None
+        if L.size:
+            h = _lib.handle(device)
+            _lib.check(h.lib.nd4hip_zheevx_batched_host(h.ptr, batch, N, i0, i1, _ptr(H), _ptr(L), _ptr(V) if vectors else None))
+        return (L, V) if vectors else L
+    L = np.empty(H.shape[:-1])
+    V = np.empty(H.shape, dtype=np.complex128) if vectors else None
+    h = _lib.handle(device)
+    _lib.check(h.lib.nd4hip_zheevd_batched_host(h.ptr, batch, N, _ptr(H), _ptr(L), _ptr(V) if vectors else None))
+    return (L, V) if vectors else L
+
+
+def eigen_herm(H, device=None, subset=None):
+    """(eigenvalues float64 [..., N] descending, eigenvectors complex128 [..., N, N] as columns) of the Hermitian complex128 H:
+    H V = V diag(L) and V^H V = I. H is read only where i >= j and the imaginary part of its diagonal is ignored. The route is
+    herm_tridiag_factor, eigen_sym(reduction='tridiag')'s real divide & conquer solver on (d, e), and herm_tridiag_apply_q on the vectors.
+    The phase of a vector is what the route produces: deterministic, not normalised. subset=(i0, i1) as eigen_sym's: L[i0:i1] and the
+    matching columns alone, by bisection and inverse iteration on (d, e). NaN or Infinity in what is read raises Nd4HipError with code
+    -3. N <= 2048. A float64 S raises TypeError: it goes to eigen_sym."""
+    return _heev(H, "eigen_herm(H)", True, device, subset)
+
+
+def eigenvals_herm(H, device=None, subset=None):
+    """the eigenvalues of eigen_herm alone (the same bits); no Q is applied and no eigenvector is computed"""
+    return _heev(H, "eigenvals_herm(H)", False, device, subset)
 
 
 def _tridiag_args(d, e, what, ndim, shape):
