@@ -731,6 +731,46 @@ int nd4hip_zheevd_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, const
 int nd4hip_zheevx_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* H, double* lambda, double* V);
 int nd4hip_zheevx_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* H, double* lambda, double* V);
 
+/* ---- herm_cholesky_decomp / herm_cholesky_solve / ztril_solve / herm_gen_reduce / eigen_herm_gen / eigenvals_herm_gen (csrc/hegv.hip,
+ * DESIGN.md 4.25) ---- The Hermitian counterparts of dpotrf, dpotrs, dtrsm (lower), dsygst, dsygvd and dsygvx; the host-pointer forms
+ * end in _host. H, L, A, B, C and X are complex128 as interleaved (re, im) doubles, lambda is real. H, A and B are read only where
+ * i >= j, the imaginary part of their diagonals is ignored, and they are never written. 1 <= N <= 2048; an empty batch, N = 0 and
+ * K = 0 have nothing to do and write nothing. strideL and strideB are in complex elements: N*N, or 0 for one L or B for all members.
+ *   zpotrf: L [batch,N,N] with H = L L^H: exact zeros above the diagonal, a real diagonal > 0 with imaginary part +0. Column j:
+ *           l_jj = sqrt(Re h_jj - sum_k |l_jk|^2), l_ij = (h_ij - sum_k l_ik conj(l_jk)) / l_jj. A radicand that is not a finite number
+ *           > 0 (the exact zero in the last pivot included): ND4HIP_ERR_SINGULAR, 'herm_cholesky_decomp(H): H is not positive
+ *           definite. (matrix <b>)' with the lowest such member.
+ *   zpotrs: X [batch,N,K] with L L^H X = Y; X may be Y.       ztrsm: L X = X (adjoint = 1: L^H X = X) in place; L is complex
+ *           lower triangular, read only where i >= j, its diagonal may be complex. Both only enqueue (the _dev forms).
+ *   zhegst: C [batch,N,N] = L^-1 A L^-H (LAPACK's zhegst, itype 1, lower): the lower triangle, zeros above, a real diagonal. Enqueues.
+ *   zhegvd: lambda [batch,N] descending and X [batch,N,N] (columns) with A X = B X diag(lambda), X^H B X = I, or X = NULL for the
+ *           values alone: zpotrf(B), zhegst, zheevd on C, X = L^-H Y. zhegvx: the same for the subset i0 <= i < i1 (zheevx):
+ *           lambda [batch,k], X [batch,N,k]. N = 1: lambda = Re a / Re b, X = 1 / sqrt(Re b). B not positive definite:
+ *           ND4HIP_ERR_SINGULAR, 'eigen_herm_gen(A,B): B is not positive definite. (matrix <b>)'; a non-finite C: ND4HIP_ERR_NOCONV,
+ *           'eigen_herm_gen(A,B): L^-1 A L^-H is not finite (NaN or Infinity in the lower triangle of A, or overflow).'. Outputs are
+ *           unspecified after an error; the handle stays usable.
+ * No sum depends on the run, the batch or a member's position. zpotrf, zhegvd and zhegvx synchronise. Profile ops "zpotrf_batched"
+ * (4/3 N^3 real flops), "zpotrs_batched", "ztrsm_batched", "zhegst_batched" (8 N^3), "zhegvd_batched" and "zhegvx_batched" (zheevd's or
+ * zheevx's count, + 4/3 N^3 + 8 N^3, + 4 N^2 k with vectors). */
+int nd4hip_zpotrf_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, const double* H, double* L);
+int nd4hip_zpotrf_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, const double* H, double* L);
+int nd4hip_zpotrs_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, const double* L, int64_t strideL, const double* Y,
+                               double* X);
+int nd4hip_zpotrs_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, const double* L, int64_t strideL, const double* Y,
+                               double* X);
+int nd4hip_ztrsm_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, int adjoint, const double* L, int64_t strideL, double* X);
+int nd4hip_ztrsm_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, int adjoint, const double* L, int64_t strideL, double* X);
+int nd4hip_zhegst_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, const double* A, const double* L, int64_t strideL, double* C);
+int nd4hip_zhegst_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, const double* L, int64_t strideL, double* C);
+int nd4hip_zhegvd_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, const double* A, const double* B, int64_t strideB, double* lambda,
+                               double* X);
+int nd4hip_zhegvd_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, const double* B, int64_t strideB, double* lambda,
+                               double* X);
+int nd4hip_zhegvx_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* A, const double* B,
+                               int64_t strideB, double* lambda, double* X);
+int nd4hip_zhegvx_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* A, const double* B,
+                               int64_t strideB, double* lambda, double* X);
+
 /* ---- eigenpairs in a value interval: eigen_sym(S, interval=(lo, hi)), tridiag_eigen(d, e, interval) (csrc/syevx.hip) ----
  * dstevxv, dsyevxv and dsyevxv_tr are dstevx, dsyevx and dsyevx_tr with the subset of each member chosen by value: bounds [batch,2]
  * holds (lo, hi) per member and selects the eigenvalues lo < lambda <= hi, which is exactly the subset (i0_b, i1_b) =

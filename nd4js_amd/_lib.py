@@ -183,6 +183,19 @@ SIGNATURES = {
     "nd4hip_zunmtr_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_int, c_dp, c_dp, c_dp]),
     "nd4hip_zheevd_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),
     "nd4hip_zheevx_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    # Hermitian Cholesky, complex triangular solves, eigen_herm_gen (csrc/hegv.hip): complex128 as interleaved doubles, strides in complex elements
+    "nd4hip_zpotrf_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp]),
+    "nd4hip_zpotrs_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_i64, c_dp, c_dp]),
+    "nd4hip_ztrsm_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_int, c_dp, c_i64, c_dp]),
+    "nd4hip_zhegst_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_i64, c_dp]),
+    "nd4hip_zhegvd_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_i64, c_dp, c_dp]),
+    "nd4hip_zhegvx_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp, c_i64, c_dp, c_dp]),
+    "nd4hip_zpotrf_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp]),
+    "nd4hip_zpotrs_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_i64, c_dp, c_dp]),
+    "nd4hip_ztrsm_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_int, c_dp, c_i64, c_dp]),
+    "nd4hip_zhegst_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_i64, c_dp]),
+    "nd4hip_zhegvd_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_i64, c_dp, c_dp]),
+    "nd4hip_zhegvx_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp, c_i64, c_dp, c_dp]),
     # (handle, batch, N, kcap, bounds, d, e | S, lambda, Z | V, range int32, kmax int64 on the host)
     "nd4hip_dstevxv_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, c_dp, ctypes.c_void_p, ctypes.POINTER(c_i64)]),
     "nd4hip_dstevxv_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, c_dp, ctypes.c_void_p, ctypes.POINTER(c_i64)]),

@@ -16,7 +16,7 @@ OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libnd4hip.so")
 ADDON = os.path.join(HERE, "js", "nd4hip_napi.node")
 ARCH = "gfx950"
-HIP_SOURCES = ["nd4hip_core.hip", "nd4hip_api.hip", "nd4hip_host.hip", "gemm.hip", "zgemm.hip", "lu.hip", "qr.hip", "qr_house.hip", "qr_rowsplit.hip", "qr_batched_panel.hip", "qr_wy.hip", "qr_signs.hip", "svd.hip", "svd_block.hip", "svd_dc.hip", "syev.hip", "syevj.hip", "syevx.hip", "bdsvdx.hip", "sytrd.hip", "hetrd.hip", "sygv.hip", "trsm.hip", "chol.hip", "hess.hip", "bidiag.hip", "rrqr.hip", "srrqr.hip", "det.hip", "eigvec.hip", "schur.hip", "pldlp.hip", "struct.hip", "gather.hip", "elem.hip"]
+HIP_SOURCES = ["nd4hip_core.hip", "nd4hip_api.hip", "nd4hip_host.hip", "gemm.hip", "zgemm.hip", "lu.hip", "qr.hip", "qr_house.hip", "qr_rowsplit.hip", "qr_batched_panel.hip", "qr_wy.hip", "qr_signs.hip", "svd.hip", "svd_block.hip", "svd_dc.hip", "syev.hip", "syevj.hip", "syevx.hip", "bdsvdx.hip", "sytrd.hip", "hetrd.hip", "sygv.hip", "hegv.hip", "trsm.hip", "chol.hip", "hess.hip", "bidiag.hip", "rrqr.hip", "srrqr.hip", "det.hip", "eigvec.hip", "schur.hip", "pldlp.hip", "struct.hip", "gather.hip", "elem.hip"]
 # -pragma-unroll-threshold: the register-resident panel kernels fully unroll 16 columns x R rows x 16 FMAs;
 # below the default threshold LLVM silently keeps a rolled loop and the row arrays fall into scratch memory.
 HIPCC_FLAGS = ["-O3", "--offload-arch=" + ARCH, "-fPIC", "-std=c++17", "-ffp-contract=on",
@@ -25,6 +25,7 @@ HIPCC_FLAGS = ["-O3", "--offload-arch=" + ARCH, "-fPIC", "-std=c++17", "-ffp-con
 # syevj.hip promises the bits of its numpy model (tests/eigsym_jacobi_common.py) in the same way, sygv.hip those of tests/sygv_common.py,
 # syevx.hip those of tests/eigsym_subset_common.py, bdsvdx.hip those of tests/svd_subset_common.py
 FILE_FLAGS = {"pldlp.hip": ["-ffp-contract=off"], "syevj.hip": ["-ffp-contract=off"], "sygv.hip": ["-ffp-contract=off"],
+              "hegv.hip": ["-ffp-contract=off"],   # the bits of tests/hegv_common.py
               "syevx.hip": ["-ffp-contract=off"], "bdsvdx.hip": ["-ffp-contract=off"]}
 
 

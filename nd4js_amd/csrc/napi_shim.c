@@ -80,6 +80,10 @@ static int (*p_dsyevd_tr[2])(nd4hip_handle*, int64_t, int64_t, const double*, do
 static int (*p_dsyevx_tr[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, const double*, double*, double*);
 static int (*p_zheevd[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*, double*);
 static int (*p_zheevx[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, const double*, double*, double*);
+static int (*p_zpotrf[2])(nd4hip_handle*, int64_t, int64_t, const double*, double*);
+static int (*p_zpotrs[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, int64_t, const double*, double*);
+static int (*p_zhegvd[2])(nd4hip_handle*, int64_t, int64_t, const double*, const double*, int64_t, double*, double*);
+static int (*p_zhegvx[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, const double*, const double*, int64_t, double*, double*);
 static int (*p_dsygvd[2])(nd4hip_handle*, int, int64_t, int64_t, const double*, const double*, int64_t, double*, double*, int32_t*);
 static int (*p_dstcnt[2])(nd4hip_handle*, int64_t, int64_t, int64_t, const double*, const double*, const double*, int32_t*);
 static int (*p_dstevx[2])(nd4hip_handle*, int64_t, int64_t, int64_t, int64_t, const double*, const double*, double*, double*);
@@ -194,6 +198,10 @@ static int load_library(void) {
   SYM(p_dsyevx_tr[0], "nd4hip_dsyevx_tr_batched_host"); SYM(p_dsyevx_tr[1], "nd4hip_dsyevx_tr_batched_dev");
   SYM(p_zheevd[0], "nd4hip_zheevd_batched_host"); SYM(p_zheevd[1], "nd4hip_zheevd_batched_dev");
   SYM(p_zheevx[0], "nd4hip_zheevx_batched_host"); SYM(p_zheevx[1], "nd4hip_zheevx_batched_dev");
+  SYM(p_zpotrf[0], "nd4hip_zpotrf_batched_host"); SYM(p_zpotrf[1], "nd4hip_zpotrf_batched_dev");
+  SYM(p_zpotrs[0], "nd4hip_zpotrs_batched_host"); SYM(p_zpotrs[1], "nd4hip_zpotrs_batched_dev");
+  SYM(p_zhegvd[0], "nd4hip_zhegvd_batched_host"); SYM(p_zhegvd[1], "nd4hip_zhegvd_batched_dev");
+  SYM(p_zhegvx[0], "nd4hip_zhegvx_batched_host"); SYM(p_zhegvx[1], "nd4hip_zhegvx_batched_dev");
   SYM2(p_dsygvd, "nd4hip_dsygvd_batched");
   SYM(p_dstcnt[0], "nd4hip_dstcnt_batched_host"); SYM(p_dstcnt[1], "nd4hip_dstcnt_batched_dev");
   SYM(p_dstevx[0], "nd4hip_dstevx_batched_host"); SYM(p_dstevx[1], "nd4hip_dstevx_batched_dev");
@@ -908,6 +916,78 @@ static napi_value js_zheevxals(napi_env env, napi_callback_info info) {
   FAIL_IF(p_zheevx[H.dev](g_handle, batch, N, i0, i1, (const double*)H.p, (double*)L.p, NULL));
   return NULL;
 }
+/* zpotrf_batched(batch, N, H, L) / zpotrs_batched(batch, N, K, L, strideL, Y, X) / zhegvd_batched(batch, N, A, B, strideB, Lam, X) /
+ * zhegvals_batched(batch, N, A, B, strideB, Lam) / zhegvx_batched(batch, N, i0, i1, A, B, strideB, Lam, X) / zhegvxals_batched(batch,
+ * N, i0, i1, A, B, strideB, Lam)   (herm_cholesky_decomp / herm_cholesky_solve / eigen_herm_gen / eigenvals_herm_gen, csrc/hegv.hip:
+ * H, L, Y, X, A and B are complex128 as interleaved doubles in Float64Arrays of twice the element count, Lam is real; strides
+ * count complex elements, N*N or 0 = one L or B) */
+static napi_value js_zpotrf(napi_env env, napi_callback_info info) {
+  ARGS(4, "zpotrf_batched");
+  int64_t batch, N; opnd H, L;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || F64(2, H) || F64(3, L)) return NULL;
+  NEED(batch >= 0 && N >= 0 && (size_t)(2 * batch * N * N) <= H.len && (size_t)(2 * batch * N * N) <= L.len, "zpotrf_batched: buffer too small");
+  SAME_SIDE(H.dev == L.dev, "zpotrf_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_zpotrf[H.dev](g_handle, batch, N, (const double*)H.p, (double*)L.p));
+  return NULL;
+}
+static napi_value js_zpotrs(napi_env env, napi_callback_info info) {
+  ARGS(7, "zpotrs_batched");
+  int64_t batch, N, K, sL; opnd L, Y, X;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || get_i64(env, a[2], &K) || F64(3, L) || get_i64(env, a[4], &sL) || F64(5, Y) ||
+      F64(6, X)) return NULL;
+  NEED(batch >= 0 && N >= 0 && K >= 0 && (sL == 0 || sL == N * N) && (size_t)(2 * (sL ? batch : 1) * N * N) <= L.len &&
+       (size_t)(2 * batch * N * K) <= Y.len && (size_t)(2 * batch * N * K) <= X.len, "zpotrs_batched: buffer too small");
+  SAME_SIDE(L.dev == Y.dev && Y.dev == X.dev, "zpotrs_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_zpotrs[L.dev](g_handle, batch, N, K, (const double*)L.p, sL, (const double*)Y.p, (double*)X.p));
+  return NULL;
+}
+#define ZHEGV_FITS(k) (batch >= 0 && N >= 0 && (sB == 0 || sB == N * N) && (size_t)(2 * batch * N * N) <= A.len && \
+                       (size_t)(2 * (sB ? batch : 1) * N * N) <= B.len && (size_t)(batch * (k)) <= L.len)
+static napi_value js_zhegvd(napi_env env, napi_callback_info info) {
+  ARGS(7, "zhegvd_batched");
+  int64_t batch, N, sB; opnd A, B, L, X;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || F64(2, A) || F64(3, B) || get_i64(env, a[4], &sB) || F64(5, L) || F64(6, X)) return NULL;
+  NEED(ZHEGV_FITS(N) && (size_t)(2 * batch * N * N) <= X.len, "zhegvd_batched: buffer too small");
+  SAME_SIDE(A.dev == B.dev && B.dev == L.dev && L.dev == X.dev, "zhegvd_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_zhegvd[A.dev](g_handle, batch, N, (const double*)A.p, (const double*)B.p, sB, (double*)L.p, (double*)X.p));
+  return NULL;
+}
+static napi_value js_zhegvals(napi_env env, napi_callback_info info) {
+  ARGS(6, "zhegvals_batched");
+  int64_t batch, N, sB; opnd A, B, L;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || F64(2, A) || F64(3, B) || get_i64(env, a[4], &sB) || F64(5, L)) return NULL;
+  NEED(ZHEGV_FITS(N), "zhegvals_batched: buffer too small");
+  SAME_SIDE(A.dev == B.dev && B.dev == L.dev, "zhegvals_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_zhegvd[A.dev](g_handle, batch, N, (const double*)A.p, (const double*)B.p, sB, (double*)L.p, NULL));
+  return NULL;
+}
+static napi_value js_zhegvx(napi_env env, napi_callback_info info) {
+  ARGS(9, "zhegvx_batched");
+  int64_t batch, N, i0, i1, sB; opnd A, B, L, X;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || get_i64(env, a[2], &i0) || get_i64(env, a[3], &i1) || F64(4, A) || F64(5, B) ||
+      get_i64(env, a[6], &sB) || F64(7, L) || F64(8, X)) return NULL;
+  NEED(0 <= i0 && i0 <= i1 && i1 <= N && ZHEGV_FITS(i1 - i0) && (size_t)(2 * batch * N * (i1 - i0)) <= X.len,
+       "zhegvx_batched: bad subset or buffer too small");
+  SAME_SIDE(A.dev == B.dev && B.dev == L.dev && L.dev == X.dev, "zhegvx_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_zhegvx[A.dev](g_handle, batch, N, i0, i1, (const double*)A.p, (const double*)B.p, sB, (double*)L.p, (double*)X.p));
+  return NULL;
+}
+static napi_value js_zhegvxals(napi_env env, napi_callback_info info) {
+  ARGS(8, "zhegvxals_batched");
+  int64_t batch, N, i0, i1, sB; opnd A, B, L;
+  if (get_i64(env, a[0], &batch) || get_i64(env, a[1], &N) || get_i64(env, a[2], &i0) || get_i64(env, a[3], &i1) || F64(4, A) || F64(5, B) ||
+      get_i64(env, a[6], &sB) || F64(7, L)) return NULL;
+  NEED(0 <= i0 && i0 <= i1 && i1 <= N && ZHEGV_FITS(i1 - i0), "zhegvxals_batched: bad subset or buffer too small");
+  SAME_SIDE(A.dev == B.dev && B.dev == L.dev, "zhegvxals_batched");
+  if (ensure_handle(env)) return NULL;
+  FAIL_IF(p_zhegvx[A.dev](g_handle, batch, N, i0, i1, (const double*)A.p, (const double*)B.p, sB, (double*)L.p, NULL));
+  return NULL;
+}
 /* dsygvd_batched(algo, batch, N, A, B, strideB, L, X) / dsygvals_batched(algo, batch, N, A, B, strideB, L)   (eigen_sym_gen /
  * eigenvals_sym_gen: A x = lambda B x; algo 0 dc, 1 jacobi; strideB N*N or 0 = one B; the sweep counts are not asked for) */
 static napi_value js_dsygvd(napi_env env, napi_callback_info info) {
@@ -1484,6 +1564,12 @@ static napi_value init(napi_env env, napi_value exports) {
     {"zheevdals_batched", NULL, js_zheevdals, NULL, NULL, NULL, napi_default, NULL},
     {"zheevx_batched", NULL, js_zheevx, NULL, NULL, NULL, napi_default, NULL},
     {"zheevxals_batched", NULL, js_zheevxals, NULL, NULL, NULL, napi_default, NULL},
+    {"zpotrf_batched", NULL, js_zpotrf, NULL, NULL, NULL, napi_default, NULL},
+    {"zpotrs_batched", NULL, js_zpotrs, NULL, NULL, NULL, napi_default, NULL},
+    {"zhegvd_batched", NULL, js_zhegvd, NULL, NULL, NULL, napi_default, NULL},
+    {"zhegvals_batched", NULL, js_zhegvals, NULL, NULL, NULL, napi_default, NULL},
+    {"zhegvx_batched", NULL, js_zhegvx, NULL, NULL, NULL, napi_default, NULL},
+    {"zhegvxals_batched", NULL, js_zhegvxals, NULL, NULL, NULL, napi_default, NULL},
     {"dsygvd_batched", NULL, js_dsygvd, NULL, NULL, NULL, napi_default, NULL},
     {"dsygvals_batched", NULL, js_dsygvals, NULL, NULL, NULL, napi_default, NULL},
     {"dstcnt_batched", NULL, js_dstcnt, NULL, NULL, NULL, napi_default, NULL},

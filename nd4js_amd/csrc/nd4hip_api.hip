@@ -979,6 +979,74 @@ extern "C" int nd4hip_dsygst_batched_dev(nd4hip_handle* h, int64_t batch, int64_
   return nd4_sygst(h, batch, N, A, L, strideL, C);
 }
 
+// ---- herm_cholesky_decomp / herm_cholesky_solve / ztril_solve / herm_gen_reduce / eigen_herm_gen (hegv.hip). The argument
+// checks come first: they need no handle. Real flops: 4/3 N^3 for L = chol(B), 8 N^3 for the two-sided reduction, 4 N^2 k for the
+// back-transformation of k columns, on top of eigen_herm's count for the same N
+int nd4_zpotrf_run(nd4hip_handle* h, int64_t batch, int64_t N, const double* H, double* L, int64_t member0) {
+  ND4_ARGS(nd4_args_zpotrf(batch, N, H, L));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zpotrf_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "zpotrf_batched", batch * (4.0 / 3.0 * (double)N * N * N), 16.0 * batch * 1.5 * (double)(N * N));
+  return nd4_zpotrf(h, batch, N, H, L, member0);
+}
+extern "C" int nd4hip_zpotrf_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* H, double* L) {
+  return nd4_zpotrf_run(h, batch, N, H, L, 0);
+}
+extern "C" int nd4hip_zpotrs_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, const double* L, int64_t strideL,
+                                         const double* Y, double* X) {
+  ND4_ARGS(nd4_args_zpotrs(batch, N, K, L, strideL, Y, X));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zpotrs_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "zpotrs_batched", batch * (8.0 * N * (double)N * K), 16.0 * batch * (double)(N * N / 2 + 2 * N * K));
+  if (Y != X) ND4_HIP(hipMemcpyAsync(X, Y, 16 * (size_t)batch * N * K, hipMemcpyDeviceToDevice, h->stream));   // the solve is made in place
+  return nd4_ztrsm(h, 2, batch, N, K, L, strideL, X);
+}
+extern "C" int nd4hip_ztrsm_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, int adjoint, const double* L, int64_t strideL,
+                                        double* X) {
+  ND4_ARGS(nd4_args_ztrsm(batch, N, K, adjoint, L, strideL, X));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_ztrsm_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "ztrsm_batched", batch * (4.0 * N * (double)N * K), 16.0 * batch * (double)(N * N / 2 + 2 * N * K));
+  return nd4_ztrsm(h, adjoint ? 1 : 0, batch, N, K, L, strideL, X);
+}
+extern "C" int nd4hip_zhegst_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, const double* L, int64_t strideL,
+                                         double* C) {
+  ND4_ARGS(nd4_args_zhegst(batch, N, A, L, strideL, C));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zhegst_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "zhegst_batched", batch * 8.0 * (double)N * N * N, 16.0 * batch * 2.0 * (double)(N * N));
+  return nd4_zhegst(h, batch, N, A, L, strideL, C);
+}
+int nd4_zhegvd_run(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, const double* B, int64_t strideB, double* lambda, double* X,
+                   int64_t member0) {
+  ND4_ARGS(nd4_args_zhegvd(batch, N, A, B, strideB, lambda));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zhegvd_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  const double n3 = (double)N * N * N;
+  Nd4Prof prof(h, "zhegvd_batched", batch * ((16.0 / 3.0 + 2.0 + (X ? 8.0 : 0.0) + 4.0 / 3.0 + 8.0 + (X ? 4.0 : 0.0)) * n3),
+               8.0 * batch * (double)(4 * N * N + N + (X ? 2 * N * N : 0)));
+  return nd4_zhegvx(h, true, 0, N, batch, N, A, B, strideB, lambda, X, member0);
+}
+extern "C" int nd4hip_zhegvd_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, const double* B, int64_t strideB,
+                                         double* lambda, double* X) {
+  return nd4_zhegvd_run(h, batch, N, A, B, strideB, lambda, X, 0);
+}
+int nd4_zhegvx_run(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* A, const double* B, int64_t strideB,
+                   double* lambda, double* X, int64_t member0) {
+  ND4_ARGS(nd4_args_zhegvx(batch, N, i0, i1, A, B, strideB, lambda));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zhegvx_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  const int64_t k = i1 - i0;
+  const double n2 = (double)N * N;
+  Nd4Prof prof(h, "zhegvx_batched", batch * ((16.0 / 3.0 + 4.0 / 3.0 + 8.0) * n2 * N + (X ? (8.0 + 4.0) * n2 * k : 0.0)),
+               8.0 * batch * (double)(4 * N * N + k + (X ? 2 * N * k : 0)));
+  return nd4_zhegvx(h, false, i0, i1, batch, N, A, B, strideB, lambda, X, member0);
+}
+extern "C" int nd4hip_zhegvx_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* A, const double* B,
+                                         int64_t strideB, double* lambda, double* X) {
+  return nd4_zhegvx_run(h, batch, N, i0, i1, A, B, strideB, lambda, X, 0);
+}
+
 extern "C" int nd4hip_dsyevd_last_stages(nd4hip_handle* h, double* ms, int capacity) {
   ND4_CHECK_ARG(h != nullptr && (ms != nullptr || capacity <= 0), "nd4hip_dsyevd_last_stages: NULL argument");
   for (int i = 0; i < capacity && i < ND4HIP_SYEV_STAGES; ++i) ms[i] = h->syev_stage_ms[i];

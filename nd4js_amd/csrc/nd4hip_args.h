@@ -382,6 +382,56 @@ inline int nd4_args_heevd(int64_t batch, int64_t N, const void* H, const void* l
 inline int nd4_args_heevx(int64_t batch, int64_t N, int64_t i0, int64_t i1, const void* H, const void* lambda) {
   return nd4_args_subset("zheevx_batched", batch, N, i0, i1, {H, lambda});
 }
+// ---- Hermitian Cholesky, complex triangular solves and the generalised Hermitian-definite eigenproblem (hegv.hip): strides in complex
+// elements, N*N or 0 (one L or B for every member)
+inline int nd4_args_zpotrf(int64_t batch, int64_t N, const void* H, const void* L) {
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_zpotrf_batched: negative extent");
+  ND4_CHECK_ARG(N <= 2048, "nd4hip_zpotrf_batched: N <= 2048");
+  if (batch == 0 || N == 0) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(H && L, "nd4hip_zpotrf_batched: NULL pointer");
+  return ND4_ARGS_GO;
+}
+// zpotrs and ztrsm: X [batch, N, K] in place
+inline int nd4_args_ztrs(const char* op, int64_t batch, int64_t N, int64_t K, int adjoint, const void* L, int64_t strideL, const void* X) {
+  ND4_CHECK_ARG(batch >= 0 && N >= 0 && K >= 0, "nd4hip_%s: negative extent", op);
+  ND4_CHECK_ARG(N <= 2048, "nd4hip_%s: N <= 2048", op);
+  ND4_CHECK_ARG(adjoint == 0 || adjoint == 1, "nd4hip_%s: adjoint must be 0 or 1", op);
+  ND4_CHECK_ARG(strideL == 0 || strideL == N * N, "nd4hip_%s: strideL must be N*N or 0", op);
+  if (batch == 0 || N == 0 || K == 0) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(L && X, "nd4hip_%s: NULL pointer", op);
+  return ND4_ARGS_GO;
+}
+inline int nd4_args_zpotrs(int64_t batch, int64_t N, int64_t K, const void* L, int64_t strideL, const void* Y, const void* X) {
+  return nd4_args_ztrs("zpotrs_batched", batch, N, K, 0, L, strideL, Y ? X : nullptr);
+}
+inline int nd4_args_ztrsm(int64_t batch, int64_t N, int64_t K, int adjoint, const void* L, int64_t strideL, const void* X) {
+  return nd4_args_ztrs("ztrsm_batched", batch, N, K, adjoint, L, strideL, X);
+}
+inline int nd4_args_zhegst(int64_t batch, int64_t N, const void* A, const void* L, int64_t strideL, const void* C) {
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_zhegst_batched: negative extent");
+  ND4_CHECK_ARG(N <= 2048, "nd4hip_zhegst_batched: N <= 2048");
+  ND4_CHECK_ARG(strideL == 0 || strideL == N * N, "nd4hip_zhegst_batched: strideL must be N*N or 0");
+  if (batch == 0 || N == 0) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(A && L && C, "nd4hip_zhegst_batched: NULL pointer");
+  return ND4_ARGS_GO;
+}
+inline int nd4_args_zhegvd(int64_t batch, int64_t N, const void* A, const void* B, int64_t strideB, const void* lambda) {
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_zhegvd_batched: negative extent");
+  ND4_CHECK_ARG(N <= 2048, "nd4hip_zhegvd_batched: N <= 2048");
+  ND4_CHECK_ARG(strideB == 0 || strideB == N * N, "nd4hip_zhegvd_batched: strideB must be N*N or 0");
+  if (batch == 0 || N == 0) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(A && B && lambda, "nd4hip_zhegvd_batched: NULL pointer");
+  return ND4_ARGS_GO;
+}
+inline int nd4_args_zhegvx(int64_t batch, int64_t N, int64_t i0, int64_t i1, const void* A, const void* B, int64_t strideB, const void* lambda) {
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_zhegvx_batched: negative extent");
+  ND4_CHECK_ARG(0 <= i0 && i0 <= i1 && i1 <= N, "nd4hip_zhegvx_batched: subset must satisfy 0 <= i0 <= i1 <= N");
+  ND4_CHECK_ARG(N <= 2048, "nd4hip_zhegvx_batched: N <= 2048");
+  ND4_CHECK_ARG(strideB == 0 || strideB == N * N, "nd4hip_zhegvx_batched: strideB must be N*N or 0");
+  if (batch == 0 || N == 0 || i0 == i1) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(A && B && lambda, "nd4hip_zhegvx_batched: NULL pointer");
+  return ND4_ARGS_GO;
+}
 inline int nd4_args_sygvd(int algo, int64_t batch, int64_t N, const void* A, const void* B, int64_t strideB, const void* lambda) {
   ND4_CHECK_ARG(algo == 0 || algo == 1, "nd4hip_dsygvd_batched: algo must be 0 (dc) or 1 (jacobi)");
   ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsygvd_batched: negative extent");

@@ -1273,3 +1273,68 @@ extern "C" int nd4hip_dsygst_batched(nd4hip_handle* h, int64_t batch, int64_t N,
   ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* d) { return nd4hip_dsygst_batched_dev(hd, nb, N, P(d, 0), P(d, 1), strideL, P(d, 2)); };
   return run_host(h, batch, ops, fn);
 }
+
+// Hermitian Cholesky, the complex triangular solves and eigen_herm_gen (hegv.hip): complex operands move as elements of 2 D bytes;
+// strideL / strideB = 0: one L or B, uploaded once per device; X = NULL: the values alone
+extern "C" int nd4hip_zpotrf_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, const double* H, double* L) {
+  ND4_ARGS(nd4_args_zpotrf(batch, N, H, L));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zpotrf_batched: NULL handle");
+  std::vector<Operand> ops{in_op(H, N * N, N * N, 2 * D), out_op(L, N * N, 2 * D)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) { return nd4_zpotrf_run(hd, nb, N, P(p, 0), P(p, 1), g_chunk_first); };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_zpotrs_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, const double* L, int64_t strideL,
+                                          const double* Y, double* X) {
+  ND4_ARGS(nd4_args_zpotrs(batch, N, K, L, strideL, Y, X));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zpotrs_batched: NULL handle");
+  std::vector<Operand> ops{in_op(L, N * N, strideL, 2 * D), in_op(Y, N * K, N * K, 2 * D), out_op(X, N * K, 2 * D)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return nd4hip_zpotrs_batched_dev(hd, nb, N, K, P(p, 0), strideL, P(p, 1), P(p, 2));
+  };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_ztrsm_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, int adjoint, const double* L, int64_t strideL,
+                                         double* X) {
+  ND4_ARGS(nd4_args_ztrsm(batch, N, K, adjoint, L, strideL, X));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_ztrsm_batched: NULL handle");
+  std::vector<Operand> ops{in_op(L, N * N, strideL, 2 * D), inout_op(X, N * K, 2 * D)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return nd4hip_ztrsm_batched_dev(hd, nb, N, K, adjoint, P(p, 0), strideL, P(p, 1));
+  };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_zhegst_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, const double* L, int64_t strideL,
+                                          double* C) {
+  ND4_ARGS(nd4_args_zhegst(batch, N, A, L, strideL, C));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zhegst_batched: NULL handle");
+  std::vector<Operand> ops{in_op(A, N * N, N * N, 2 * D), in_op(L, N * N, strideL, 2 * D), out_op(C, N * N, 2 * D)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) { return nd4hip_zhegst_batched_dev(hd, nb, N, P(p, 0), P(p, 1), strideL, P(p, 2)); };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_zhegvd_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, const double* B, int64_t strideB,
+                                          double* lambda, double* X) {
+  ND4_ARGS(nd4_args_zhegvd(batch, N, A, B, strideB, lambda));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zhegvd_batched: NULL handle");
+  // the operands that are wanted, in the order A, B, lambda, [X]
+  std::vector<Operand> ops{in_op(A, N * N, N * N, 2 * D), in_op(B, N * N, strideB, 2 * D), out_op(lambda, N)};
+  const int ix = X ? (int)ops.size() : -1;
+  if (X) ops.push_back(out_op(X, N * N, 2 * D));
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return nd4_zhegvd_run(hd, nb, N, P(p, 0), P(p, 1), strideB, P(p, 2), ix >= 0 ? P(p, ix) : nullptr, g_chunk_first);
+  };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_zhegvx_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* A, const double* B,
+                                          int64_t strideB, double* lambda, double* X) {
+  ND4_ARGS(nd4_args_zhegvx(batch, N, i0, i1, A, B, strideB, lambda));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zhegvx_batched: NULL handle");
+  const int64_t k = i1 - i0;
+  // the operands that are wanted, in the order A, B, lambda, [X]
+  std::vector<Operand> ops{in_op(A, N * N, N * N, 2 * D), in_op(B, N * N, strideB, 2 * D), out_op(lambda, k)};
+  const int ix = X ? (int)ops.size() : -1;
+  if (X) ops.push_back(out_op(X, N * k, 2 * D));
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return nd4_zhegvx_run(hd, nb, N, i0, i1, P(p, 0), P(p, 1), strideB, P(p, 2), ix >= 0 ? P(p, ix) : nullptr, g_chunk_first);
+  };
+  return run_host(h, batch, ops, fn);
+}

@@ -238,6 +238,26 @@ int nd4_hetrd_order_one(nd4hip_handle* h, int64_t batch, const double* H, double
 // V = NULL: the values alone. Both synchronise
 int nd4_zheevd(nd4hip_handle* h, int64_t batch, int64_t N, const double* H, double* lambda, double* V);
 int nd4_zheevx(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* H, double* lambda, double* V);
+// Hermitian Cholesky, complex lower triangular solves and the generalised Hermitian-definite eigenproblem (hegv.hip):
+// complex128 operands as interleaved doubles, strides in complex elements (0 = one for all). Arguments already checked, batch >= 1,
+// 1 <= N <= 2048, K >= 1; member0: index of the first member in the caller's batch (error text). nd4_zpotrf and nd4_zhegvx synchronise,
+// nd4_ztrsm (mode 0 L X = Y, 1 L^H X = Y, 2 L L^H X = Y, X in place) and nd4_zhegst enqueue only. all: every eigenpair, else the subset
+// i0 <= i < i1; X = NULL: the values alone. The three functions after them are the host-side arithmetic: tier (0: a member in LDS,
+// 1: blocks of 64), the largest dynamic LDS request in bytes, members per pass.
+int nd4_zpotrf(nd4hip_handle* h, int64_t batch, int64_t N, const double* H, double* L, int64_t member0);
+int nd4_ztrsm(nd4hip_handle* h, int mode, int64_t batch, int64_t N, int64_t K, const double* L, int64_t sL, double* X);
+int nd4_zhegst(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, const double* L, int64_t sL, double* C);
+int nd4_zhegvx(nd4hip_handle* h, bool all, int64_t i0, int64_t i1, int64_t batch, int64_t N, const double* A, const double* B, int64_t sB,
+               double* lambda, double* X, int64_t member0);
+int nd4_hegv_tier(int64_t N);
+size_t nd4_hegv_lds(int64_t N);
+int64_t nd4_hegv_chunk(int64_t batch, int64_t N);
+// the entry points with member0, shared by the _dev and _host forms (nd4hip_api.hip)
+int nd4_zpotrf_run(nd4hip_handle* h, int64_t batch, int64_t N, const double* H, double* L, int64_t member0);
+int nd4_zhegvd_run(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, const double* B, int64_t strideB, double* lambda, double* X,
+                   int64_t member0);
+int nd4_zhegvx_run(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* A, const double* B, int64_t strideB,
+                   double* lambda, double* X, int64_t member0);
 // generalised symmetric-definite eigenproblem (sygv.hip): arguments already checked, batch >= 1, 1 <= N; sB / sL 0 = one for all;
 // member0: index of the first member in the caller's batch (error text); nd4_sygvd synchronises
 int nd4_sygvd(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B, int64_t sB, double* lambda,

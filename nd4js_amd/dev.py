@@ -1049,6 +1049,107 @@ def eigenvals_herm(H, subset=None):
     return _heev(H, "eigenvals_herm(H)", False, subset)
 
 
+def _chk_c128(t, name, what, real_goes_to):
+    """a contiguous complex128 CUDA tensor with its stored numbers (no lazy conjugate or negative bit); la's dtype errors"""
+    from .la import _hegv_dtype
+    if isinstance(t, torch.Tensor):
+        _hegv_dtype(name, what, t.is_complex(), t.dtype == torch.complex128, t.dtype, real_goes_to)
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous()):
+        raise TypeError("%s: %s must be a contiguous complex128 CUDA tensor" % (what, name))
+    return t.resolve_conj().resolve_neg()
+
+
+def herm_cholesky_decomp(H):
+    """device-resident la.herm_cholesky_decomp: L complex128 [..., N, N] with H = L L^H, the same bits"""
+    from .la import _hegv_square
+    what = "herm_cholesky_decomp(H)"
+    H = _chk_c128(H, "H", what, "cholesky_decomp")
+    N = _hegv_square(tuple(H.shape), "H", what)
+    L = torch.empty_like(H)
+    if L.numel():
+        h = _h(H)
+        _lib.check(h.lib.nd4hip_zpotrf_batched_dev(h.ptr, _batch(H.shape[:-2]), N, _p(H), _p(L)))
+    return L
+
+
+def _ztrs(L, Y, what, entry, *flag, twice=False):
+    from .la import _hegv_ly
+    L = _chk_c128(L, "L", what, "cholesky_solve / tril_solve")
+    if not (isinstance(Y, torch.Tensor) and Y.is_cuda and Y.dtype in (torch.float64, torch.complex128)):
+        raise TypeError("%s: Y must be a complex128 or float64 CUDA tensor." % what)
+    N, K, one_l = _hegv_ly(tuple(L.shape), tuple(Y.shape), what)
+    if L.device != Y.device:
+        raise ValueError("%s: both operands must be on the same device." % what)
+    X = Y.to(torch.complex128).resolve_conj().resolve_neg().clone(memory_format=torch.contiguous_format)   # the solve is made in place
+    if X.numel():
+        h = _h(L)
+        _lib.check(getattr(h.lib, entry)(h.ptr, _batch(Y.shape[:-2]), N, K, *flag, _p(L), 0 if one_l else N * N, *([_p(X)] * (2 if twice else 1))))
+    return X
+
+
+def herm_cholesky_solve(L, Y):
+    """device-resident la.herm_cholesky_solve: X with L L^H X = Y, the same bits; only enqueued"""
+    return _ztrs(L, Y, "herm_cholesky_solve(L,Y)", "nd4hip_zpotrs_batched_dev", twice=True)   # (Y, X) = (X, X): in place
+
+
+def ztril_solve(L, Y, adjoint=False):
+    """device-resident la.ztril_solve: X with L X = Y (adjoint: L^H X = Y), the same bits; only enqueued"""
+    return _ztrs(L, Y, "ztril_solve(L,Y)", "nd4hip_ztrsm_batched_dev", 1 if adjoint else 0)
+
+
+def _hegv_ab(A, B, nb, what):
+    from .la import _hegv_pair, _hegv_square
+    A, B = _chk_c128(A, "A", what, "eigen_sym_gen"), _chk_c128(B, nb, what, "eigen_sym_gen")
+    N = _hegv_square(tuple(A.shape), "A", what)
+    _hegv_square(tuple(B.shape), nb, what)
+    one = _hegv_pair(A.shape, B.shape, nb, what)
+    if B.device != A.device:
+        raise ValueError("%s: both operands must be on the same device." % what)
+    return A, B, N, one
+
+
+def herm_gen_reduce(A, L):
+    """device-resident la.herm_gen_reduce: C = L^-1 A L^-H, lower triangle, zeros above, a real diagonal; the same bits; only enqueued"""
+    A, L, N, one_l = _hegv_ab(A, L, "L", "herm_gen_reduce(A,L)")
+    C = torch.empty_like(A)
+    if C.numel():
+        h = _h(A)
+        _lib.check(h.lib.nd4hip_zhegst_batched_dev(h.ptr, _batch(A.shape[:-2]), N, _p(A), _p(L), 0 if one_l else N * N, _p(C)))
+    return C
+
+
+def _hegv(A, B, what, vectors, subset):
+    from .la import _subset
+    if subset is not None:
+        what = what.replace("(A,B)", "(A,B, subset)")
+    A, B, N, one_b = _hegv_ab(A, B, "B", what)
+    lead = tuple(A.shape[:-2])
+    i0, i1 = _subset(subset, N, what) if subset is not None else (0, N)
+    lam = torch.empty(lead + (i1 - i0,), dtype=torch.float64, device=A.device)
+    X = torch.empty(lead + (N, i1 - i0), dtype=torch.complex128, device=A.device) if vectors else None
+    if lam.numel():
+        h = _h(A)
+        if subset is not None:
+            _lib.check(h.lib.nd4hip_zhegvx_batched_dev(h.ptr, _batch(lead), N, i0, i1, _p(A), _p(B), 0 if one_b else N * N, _p(lam),
+                                                       _p(X) if vectors else None))
+        else:
+            _lib.check(h.lib.nd4hip_zhegvd_batched_dev(h.ptr, _batch(lead), N, _p(A), _p(B), 0 if one_b else N * N, _p(lam),
+                                                       _p(X) if vectors else None))
+    return (lam, X) if vectors else lam
+
+
+def eigen_herm_gen(A, B, subset=None):
+    """device-resident la.eigen_herm_gen: A x = lambda B x with A Hermitian and B Hermitian positive definite, complex128: (eigenvalues
+    float64 [..., N] descending, eigenvectors complex128 [..., N, N] as columns, X^H B X = I). B has A's shape or is exactly [N, N] (one B
+    for every member, factorised once). Only i >= j is read; A and B are not written. The same bits as through la."""
+    return _hegv(A, B, "eigen_herm_gen(A,B)", True, subset)
+
+
+def eigenvals_herm_gen(A, B, subset=None):
+    """device-resident la.eigenvals_herm_gen: the eigenvalues of eigen_herm_gen alone, the same bits"""
+    return _hegv(A, B, "eigenvals_herm_gen(A,B)", False, subset)
+
+
 def _stevx(d, e, subset, what, vectors, interval=None, info=None):
     from .la import _interval_what, _subset, _tridiag_args
     if interval is not None:

@@ -1697,6 +1697,98 @@ function makeLa(NDA, fallback, SolveError, Complex) {
   };
   eigHerm('eigen_herm', true); eigHerm('eigenvals_herm', false);
 
+  /* ---- herm_cholesky_decomp / herm_cholesky_solve / eigen_herm_gen / eigenvals_herm_gen, csrc/hegv.hip (DESIGN.md 4.25): complex128
+   * operands of the host module (install(nd)) or complex DeviceNDArrays in, the same kind out. Hermitian operands are read only where
+   * i >= j, the imaginary part of their diagonals is ignored, nothing is written. A real matrix is sent to the real function. Not
+   * enumerable, like eigen_herm. ---- */
+  const zSquare = (what, nm, M, goesTo) => {
+    if (dtypeOf(M) !== 'complex128') throw new TypeError(`${what}: ${nm}.dtype must be complex128; a real symmetric matrix goes to ${goesTo}.`);
+    if (M.ndim < 2) throw new Error(`${what}: ${nm}.ndim must be at least 2.`);
+    if (M.shape[M.ndim - 2] != M.shape[M.ndim - 1]) throw new Error(`${what}: ${nm} must be quadratic.`);
+    return M.shape[M.ndim - 1];
+  };
+  const zOut = (Cx, dev, shape, x) => dev ? new DeviceNDArray(Int32Array.from(shape), x, Cx) : new NDA(Int32Array.from(shape), complexOver(Cx, x));
+  const hidden = (name, f) => {
+    Object.defineProperty(f, 'name', {value: name});
+    Object.defineProperty(la, name, {value: f, writable: true, enumerable: false, configurable: true});
+  };
+  // L [..., N, N] with H = L L^H: zeros above the diagonal, a real positive diagonal
+  hidden('herm_cholesky_decomp', function (H) {
+    const what = 'herm_cholesky_decomp(H)';
+    H = asarray(H);
+    const N = zSquare(what, 'H', H, 'cholesky_decomp'), Cx = needComplex('herm_cholesky_decomp');
+    const batch = prod(H.shape, 0, H.ndim - 2), dev = isDev(H), temps = [], L = alloc(dev, 2 * batch * N * N);
+    try { native().zpotrf_batched(batch, N, view(opZ(H, dev, temps), 0), view(L, 0)); }
+    catch (e) { if (dev) L.free(); throw e; }
+    finally { release(temps); }
+    return zOut(Cx, dev, H.shape, L);
+  });
+  // X with L L^H X = Y; Y [..., N, K] complex128 or float64 (promoted); L has Y's leading dimensions or is exactly [N, N]
+  hidden('herm_cholesky_solve', function (L, Y) {
+    const what = 'herm_cholesky_solve(L,Y)';
+    L = asarray(L); Y = asarray(Y);
+    const N = zSquare(what, 'L', L, 'cholesky_solve'), Cx = needComplex('herm_cholesky_solve');
+    const dy = dtypeOf(Y);
+    if (dy !== 'complex128' && dy !== 'float64') throw new TypeError(`${what}: Y must be complex128 or float64.`);
+    if (Y.ndim < 2) throw new Error(`${what}: Y.ndim must be at least 2.`);
+    if (Y.shape[Y.ndim - 2] != N) throw new Error(`${what}: L and Y don't match.`);
+    const K = Y.shape[Y.ndim - 1], leadY = Array.from(Y.shape.subarray(0, Y.ndim - 2)), leadL = Array.from(L.shape.subarray(0, L.ndim - 2));
+    const same = leadL.length === leadY.length && leadL.every((s, i) => s == leadY[i]);
+    if (!same && L.ndim !== 2) throw new Error(`${what}: L must have the leading dimensions of Y or be [N, N], got [${Array.from(L.shape)}] and [${Array.from(Y.shape)}].`);
+    if (isDev(L) !== isDev(Y)) throw new TypeError(`${what}: L and Y must be both host arrays or both DeviceNDArrays.`);
+    const batch = prod(Y.shape, 0, Y.ndim - 2), dev = isDev(L), temps = [], X = alloc(dev, 2 * batch * N * K);
+    try {
+      let y;
+      if (dy === 'complex128') y = opZ(Y, dev, temps);
+      else {                                     // a real Y: interleaved with zero imaginary parts on the host, then on the call's side
+        const r = isDev(Y) ? la.to_host(Y).data : f64(Y), z = new Float64Array(2 * r.length);
+        for (let i = 0; i < r.length; i++) z[2 * i] = r[i];
+        if (dev) { y = DevBuf.from(z); temps.push(y); } else y = z;
+      }
+      native().zpotrs_batched(batch, N, K, view(opZ(L, dev, temps), 0), same ? N * N : 0, view(y, 0), view(X, 0));
+    }
+    catch (e) { if (dev) X.free(); throw e; }
+    finally { release(temps); }
+    return zOut(Cx, dev, Y.shape, X);
+  });
+  const eigHermGen = (name, vectors) => hidden(name, function (A, B, opts) {
+    const what = `${name}(A,B)`;
+    const subset = opts == null ? undefined : opts.subset;
+    if (subset != null && (!(Array.isArray(subset) || ArrayBuffer.isView(subset)) || subset.length !== 2))
+      throw new Error(`${name}(A,B, {subset}): subset must be [i0, i1] with 0 <= i0 <= i1 <= N.`);
+    A = asarray(A); B = asarray(B);
+    const N = zSquare(what, 'A', A, 'eigen_sym_gen');
+    zSquare(what, 'B', B, 'eigen_sym_gen');
+    const nd_ = A.ndim;
+    const same = B.ndim === nd_ && A.shape.every((s, i) => s == B.shape[i]), one = !same && B.ndim === 2 && B.shape[0] == N && B.shape[1] == N;
+    if (!same && !one) throw new Error(`${what}: B.shape must be A.shape or A.shape.slice(-2), got [${Array.from(B.shape)}] and [${Array.from(A.shape)}].`);
+    if (isDev(A) !== isDev(B)) throw new TypeError(`${what}: A and B must be both host arrays or both DeviceNDArrays.`);
+    let i0 = 0, i1 = N;
+    if (subset != null) {
+      [i0, i1] = subset;
+      if (!(Number.isInteger(i0) && Number.isInteger(i1) && 0 <= i0 && i0 <= i1 && i1 <= N))
+        throw new Error(`${name}(A,B, {subset}): subset must be [i0, i1] with 0 <= i0 <= i1 <= N, got [${i0}, ${i1}] for N = ${N}.`);
+      if (i1 === i0) throw new Error(`${name}(A,B, {subset}): the subset [${i0}, ${i1}] is empty, and an NDArray has no axis of length 0.`);
+    }
+    const Cx = needComplex(name);
+    const k = i1 - i0, batch = prod(A.shape, 0, nd_ - 2), dev = isDev(A), temps = [], lead = Array.from(A.shape.subarray(0, nd_ - 2)), sB = same ? N * N : 0;
+    const L = alloc(dev, batch * k), X = vectors ? alloc(dev, 2 * batch * N * k) : null;
+    try {
+      const a = view(opZ(A, dev, temps), 0), b = view(opZ(B, dev, temps), 0);
+      if (subset != null) {
+        if (vectors) native().zhegvx_batched(batch, N, i0, i1, a, b, sB, view(L, 0), view(X, 0));
+        else native().zhegvxals_batched(batch, N, i0, i1, a, b, sB, view(L, 0));
+      }
+      else if (vectors) native().zhegvd_batched(batch, N, a, b, sB, view(L, 0), view(X, 0));
+      else native().zhegvals_batched(batch, N, a, b, sB, view(L, 0));
+    }
+    catch (e) { if (dev) { L.free(); if (X) X.free(); } throw e; }
+    finally { release(temps); }
+    const Lw = wrap(dev, lead.concat([k]), L);
+    return vectors ? [Lw, zOut(Cx, dev, lead.concat([N, k]), X)] : Lw;
+  });
+  eigHermGen('eigen_herm_gen', true); eigHermGen('eigenvals_herm_gen', false);
+
   /* ---- eigen_sym_gen / eigenvals_sym_gen, csrc/sygv.hip: A x = lambda B x, A symmetric, B symmetric positive definite, both read
    * only in their lower triangles. A [..., N, N]; B of the same shape or exactly [N, N] (one B for every member, factorised once)
    * -> [eigenvalues [..., N] descending, eigenvectors [..., N, N] as columns with X^T B X = I], resp. the eigenvalues alone (the
@@ -1938,7 +2030,7 @@ function install(nd, opts) {
     return f;
   };
   for (const k of Object.keys(original)) Object.defineProperty(patched, k, {value: route(k), writable: true, enumerable: true, configurable: true});
-  for (const k of ['to_device', 'to_host', 'synchronize', 'DeviceNDArray', 'profile_enable', 'profile_last', 'schur_qrfrancis', 'concat', 'stack', 'zip_elems', 'eigen_sym', 'eigenvals_sym', 'eigen_sym_gen', 'eigenvals_sym_gen', 'eigen_herm', 'eigenvals_herm'])   // §8f N3 / §8b extensions, not in the reference (schur_qrfrancis: its private step)
+  for (const k of ['to_device', 'to_host', 'synchronize', 'DeviceNDArray', 'profile_enable', 'profile_last', 'schur_qrfrancis', 'concat', 'stack', 'zip_elems', 'eigen_sym', 'eigenvals_sym', 'eigen_sym_gen', 'eigenvals_sym_gen', 'eigen_herm', 'eigenvals_herm', 'herm_cholesky_decomp', 'herm_cholesky_solve', 'eigen_herm_gen', 'eigenvals_herm_gen'])   // §8f N3 / §8b extensions, not in the reference (schur_qrfrancis: its private step)
     Object.defineProperty(patched, k, {value: acc[k], writable: true, enumerable: false, configurable: true});
   if (!target) { try { nd.la = patched; } catch (e) { /* exported getter: caller uses the returned object */ } }
   patched.__nd4hip_original__ = original;

@@ -17,6 +17,10 @@ JS wrapper nd4js_amd/js/index.js over the N-API shim; both call the same libnd4h
   herm_tridiag_factor(H), herm_tridiag_apply_q(F, tau, Z), herm_tridiag_decomp(H)   complex128 Hermitian H, not in the reference
                                    -> nd4hip_zhetrd_batched_host, nd4hip_zunmtr_batched_host (csrc/hetrd.hip)
   eigen_herm(H, subset), eigenvals_herm(H, subset)   not in the reference   -> nd4hip_zheevd_batched_host, nd4hip_zheevx_batched_host
+  herm_cholesky_decomp(H), herm_cholesky_solve(L, Y), ztril_solve(L, Y, adjoint), herm_gen_reduce(A, L)   complex128, not in the reference
+                                   -> nd4hip_zpotrf_batched_host, nd4hip_zpotrs_batched_host, nd4hip_ztrsm_batched_host, nd4hip_zhegst_batched_host
+  eigen_herm_gen(A, B, subset), eigenvals_herm_gen(A, B, subset)   not in the reference   -> nd4hip_zhegvd_batched_host, nd4hip_zhegvx_batched_host
+                                   (csrc/hegv.hip)
   tridiag_eigen(d, e), tridiag_eigenvals(d, e), tridiag_count(d, e, x)   not in the reference   -> nd4hip_dstevx_batched_host, nd4hip_dstcnt_batched_host
                                    interval=(lo, hi) (opt-in, here and in eigen_sym): the eigenvalues in (lo, hi] -> nd4hip_dstevxv_batched_host,
                                    nd4hip_dsyevxv_batched_host, nd4hip_dsyevxv_tr_batched_host
@@ -1549,6 +1553,151 @@ def eigen_herm(H, device=None, subset=None):
 def eigenvals_herm(H, device=None, subset=None):
     """the eigenvalues of eigen_herm alone (the same bits); no Q is applied and no eigenvector is computed"""
     return _heev(H, "eigenvals_herm(H)", False, device, subset)
+
+
+def _hegv_dtype(name, what, is_complex, is_c128, dtype, real_goes_to):
+    """the dtype rule of the Hermitian Cholesky and generalised functions, shared with dev.py: complex128 as it is; a real matrix is sent
+    to the real function"""
+    if not is_complex:
+        raise TypeError("%s: %s.dtype must be complex128; a real symmetric matrix goes to %s." % (what, name, real_goes_to))
+    if not is_c128:
+        raise TypeError("%s: only complex128 runs on the GPU path, got %s" % (what, dtype))
+
+
+def _hegv_square(shape, name, what):
+    """N of a stack of square matrices, N <= 2048"""
+    if len(shape) < 2:
+        raise ValueError("%s: %s.ndim must be at least 2." % (what, name))
+    if shape[-2] != shape[-1]:
+        raise ValueError("%s: %s must be quadratic." % (what, name))
+    if shape[-1] > 2048:
+        raise ValueError("%s: N <= 2048." % what)
+    return int(shape[-1])
+
+
+def _hegv_pair(sa, sb, nb, what):
+    """whether one B (or L) [N, N] serves every member of A [..., N, N]"""
+    sa, sb = tuple(sa), tuple(sb)
+    if sb != sa and sb != sa[-2:]:
+        raise ValueError("%s: %s.shape must be A.shape or A.shape[-2:], got %s and %s." % (what, nb, list(sb), list(sa)))
+    return sb != sa
+
+
+def _hegv_ly(sl, sy, what):
+    """(N, K, one L for all) of L [..., N, N] or [N, N] and Y [..., N, K]"""
+    sl, sy = tuple(sl), tuple(sy)
+    N = _hegv_square(sl, "L", what)
+    if len(sy) < 2:
+        raise ValueError("%s: Y.ndim must be at least 2." % what)
+    if sy[-2] != N:
+        raise ValueError("%s: L and Y don't match." % what)
+    if sl[:-2] != sy[:-2] and len(sl) != 2:
+        raise ValueError("%s: L must have the leading dimensions of Y or be [N, N], got %s and %s." % (what, list(sl), list(sy)))
+    return N, int(sy[-1]), sl[:-2] != sy[:-2]
+
+
+def _hegv_m(M, name, what, real_goes_to):
+    M = np.asarray(M)
+    _hegv_dtype(name, what, M.dtype.kind == "c", M.dtype == np.complex128, M.dtype, real_goes_to)
+    return np.ascontiguousarray(M)
+
+
+def herm_cholesky_decomp(H, device=None):
+    """L complex128 [..., N, N] with H = L L^H for the Hermitian positive definite complex128 H (LAPACK's zpotrf, lower): exact zeros above
+    the diagonal, a real diagonal > 0 with imaginary part +0. H is read only where i >= j, the imaginary part of its diagonal is ignored,
+    and it is not written. A radicand that is not a finite number > 0 raises Nd4HipError with code -5 and the lowest such member.
+    N <= 2048 (csrc/hegv.hip). A float64 H raises TypeError: it goes to cholesky_decomp."""
+    what = "herm_cholesky_decomp(H)"
+    H = _hegv_m(H, "H", what, "cholesky_decomp")
+    N = _hegv_square(H.shape, "H", what)
+    L = np.empty(H.shape, dtype=np.complex128)
+    if L.size:
+        h = _lib.handle(device)
+        _lib.check(h.lib.nd4hip_zpotrf_batched_host(h.ptr, int(np.prod(H.shape[:-2], dtype=np.int64)), N, _ptr(H), _ptr(L)))
+    return L
+
+
+def _ztrs(L, Y, what, device, entry, *flag, twice=False):
+    L, Y = np.asarray(L), np.asarray(Y)
+    _hegv_dtype("L", what, L.dtype.kind == "c", L.dtype == np.complex128, L.dtype, "cholesky_solve / tril_solve")
+    if Y.dtype != np.complex128 and Y.dtype != np.float64:
+        raise TypeError("%s: Y must be complex128 or float64." % what)
+    N, K, one_l = _hegv_ly(L.shape, Y.shape, what)
+    L = np.ascontiguousarray(L)
+    X = np.array(Y, dtype=np.complex128, order="C")                         # a copy: the solve is made in place
+    if X.size:
+        h = _lib.handle(device)
+        _lib.check(getattr(h.lib, entry)(h.ptr, int(np.prod(Y.shape[:-2], dtype=np.int64)), N, K, *flag, _ptr(L), 0 if one_l else N * N,
+                                         *([_ptr(X)] * (2 if twice else 1))))
+    return X
+
+
+def herm_cholesky_solve(L, Y, device=None):
+    """X complex128 with L L^H X = Y for the L of herm_cholesky_decomp and Y [..., N, K], complex128 or float64 (promoted). L has Y's
+    leading dimensions or is exactly [N, N]: one factor for every member."""
+    return _ztrs(L, Y, "herm_cholesky_solve(L,Y)", device, "nd4hip_zpotrs_batched_host", twice=True)   # (Y, X) = (X, X): in place
+
+
+def ztril_solve(L, Y, adjoint=False, device=None):
+    """X complex128 with L X = Y (adjoint: L^H X = Y) for a complex128 lower triangular L, read only where i >= j; its diagonal may be
+    complex. Shapes as herm_cholesky_solve's."""
+    return _ztrs(L, Y, "ztril_solve(L,Y)", device, "nd4hip_ztrsm_batched_host", 1 if adjoint else 0)
+
+
+def herm_gen_reduce(A, L, device=None):
+    """C = L^-1 A L^-H (LAPACK's zhegst, itype 1, lower) for the Hermitian complex128 A [..., N, N], read only where i >= j, and the L of
+    herm_cholesky_decomp, A's shape or [N, N]: the lower triangle of C, zeros above it and an exactly real diagonal, what eigen_herm reads."""
+    what = "herm_gen_reduce(A,L)"
+    A, L = _hegv_m(A, "A", what, "eigen_sym_gen"), _hegv_m(L, "L", what, "eigen_sym_gen")
+    N = _hegv_square(A.shape, "A", what)
+    _hegv_square(L.shape, "L", what)
+    one_l = _hegv_pair(A.shape, L.shape, "L", what)
+    C = np.empty(A.shape, dtype=np.complex128)
+    if C.size:
+        h = _lib.handle(device)
+        _lib.check(h.lib.nd4hip_zhegst_batched_host(h.ptr, int(np.prod(A.shape[:-2], dtype=np.int64)), N, _ptr(A), _ptr(L),
+                                                    0 if one_l else N * N, _ptr(C)))
+    return C
+
+
+def _hegv(A, B, what, vectors, device, subset):
+    if subset is not None:
+        what = what.replace("(A,B)", "(A,B, subset)")
+    A, B = _hegv_m(A, "A", what, "eigen_sym_gen"), _hegv_m(B, "B", what, "eigen_sym_gen")
+    N = _hegv_square(A.shape, "A", what)
+    _hegv_square(B.shape, "B", what)
+    one_b = _hegv_pair(A.shape, B.shape, "B", what)
+    lead = A.shape[:-2]
+    batch = int(np.prod(lead, dtype=np.int64))
+    i0, i1 = _subset(subset, N, what) if subset is not None else (0, N)
+    lam = np.empty(lead + (i1 - i0,))
+    X = np.empty(lead + (N, i1 - i0), dtype=np.complex128) if vectors else None
+    if lam.size:
+        h = _lib.handle(device)
+        if subset is not None:
+            _lib.check(h.lib.nd4hip_zhegvx_batched_host(h.ptr, batch, N, i0, i1, _ptr(A), _ptr(B), 0 if one_b else N * N, _ptr(lam),
+                                                        _ptr(X) if vectors else None))
+        else:
+            _lib.check(h.lib.nd4hip_zhegvd_batched_host(h.ptr, batch, N, _ptr(A), _ptr(B), 0 if one_b else N * N, _ptr(lam),
+                                                        _ptr(X) if vectors else None))
+    return (lam, X) if vectors else lam
+
+
+def eigen_herm_gen(A, B, device=None, subset=None):
+    """the generalised Hermitian-definite eigenproblem A x = lambda B x: (eigenvalues float64 [..., N] descending, eigenvectors complex128
+    [..., N, N] as columns) with A X = B X diag(lam) and X^H B X = I. A [..., N, N] Hermitian complex128; B Hermitian positive definite of
+    the same shape, or exactly [N, N]: one B for every member, factorised once. Both are read only where i >= j, the imaginary parts of
+    their diagonals are ignored, neither is written. Route: L = herm_cholesky_decomp(B), C = herm_gen_reduce(A, L), eigen_herm(C)
+    unchanged, X = L^-H Y (csrc/hegv.hip). The phase of a column is what the route produces: deterministic, not normalised.
+    subset=(i0, i1) as eigen_herm's; the back-transformation then runs on the selected columns alone. B not positive definite raises
+    Nd4HipError with code -5 and the lowest such member; NaN or Infinity in A's lower triangle, or overflow of C, code -3. N <= 2048.
+    A float64 A or B raises TypeError: the pair goes to eigen_sym_gen."""
+    return _hegv(A, B, "eigen_herm_gen(A,B)", True, device, subset)
+
+
+def eigenvals_herm_gen(A, B, device=None, subset=None):
+    """the eigenvalues of eigen_herm_gen alone (the same bits); no back-transformation is computed"""
+    return _hegv(A, B, "eigenvals_herm_gen(A,B)", False, device, subset)
 
 
 def _tridiag_args(d, e, what, ndim, shape):
