@@ -771,6 +771,31 @@ int nd4hip_zhegvx_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, int64
 int nd4hip_zhegvx_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* A, const double* B,
                                int64_t strideB, double* lambda, double* X);
 
+/* ---- general complex LU and its solves: zlu_decomp / zlu_solve / zsolve (csrc/zgetrf.hip) ----
+ * LAPACK's zgetrf / zgetrs with lu_decomp's conventions. A, LU, Y and X are complex128 as interleaved (re, im) doubles on 16-byte
+ * boundaries, P and info are int32; strides are in complex elements (strideP in ints), 0 for one operand for all members. 1 <= N <= 2048:
+ * a larger N is ND4HIP_ERR_ARG before anything is written; an empty batch, N = 0 and K = 0 have nothing to do and write nothing.
+ *   zgetrf: LU [batch,N,N] and P [batch,N] with (L U)[i,:] = A[P[i],:], L unit lower below the diagonal of LU, U on and above it; A is
+ *           not written. The pivot of column j is the first row i >= j with the largest |Re a_ij| + |Im a_ij| (a later row wins only by
+ *           strict >; a NaN never wins unless it is the start row); l_ij = a_ij / a_jj is a true complex division in Smith's form. A
+ *           pivot whose |Re| + |Im| is zero or not finite is no error: the column is left unscaled, the factorisation goes on, and
+ *           info [batch] (may be NULL; device memory in the _dev form) receives 1 + the first such column per member, 0 for none.
+ *   zgetrs: X [batch,N,K] with A X = Y from LU and P: the rows of Y gathered through P, the unit lower sweep, the upper sweep. An entry
+ *           of P outside 0 .. N-1 makes that row NaN. Both only enqueue (the _dev forms).
+ *   zgesv:  zgetrf and zgetrs back to back with LU and P in workspace. A flagged member: ND4HIP_ERR_SINGULAR, 'zsolve(A,Y): A is
+ *           singular. (matrix <b>)' with the lowest such member; the handle stays usable. Synchronises (one flag word per pass).
+ * Up to N = 64 the results are those of the numpy model in tests/zlu_common.py bit for bit; above, the trailing updates run on the
+ * fp64 matrix cores. No sum depends on the run, the batch or a member's position. Profile ops "zgetrf_batched" (8/3 N^3 real flops),
+ * "zgetrs_batched" (8 N^2 K) and "zgesv_batched". */
+int nd4hip_zgetrf_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* LU, int32_t* P, int32_t* info);
+int nd4hip_zgetrf_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* LU, int32_t* P, int32_t* info);
+int nd4hip_zgetrs_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, const double* LU, int64_t strideLU, const int32_t* P,
+                               int64_t strideP, const double* Y, int64_t strideY, double* X);
+int nd4hip_zgetrs_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, const double* LU, int64_t strideLU, const int32_t* P,
+                               int64_t strideP, const double* Y, int64_t strideY, double* X);
+int nd4hip_zgesv_batched_dev  (nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, const double* A, const double* Y, double* X);
+int nd4hip_zgesv_batched_host (nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, const double* A, const double* Y, double* X);
+
 /* ---- eigenpairs in a value interval: eigen_sym(S, interval=(lo, hi)), tridiag_eigen(d, e, interval) (csrc/syevx.hip) ----
  * dstevxv, dsyevxv and dsyevxv_tr are dstevx, dsyevx and dsyevx_tr with the subset of each member chosen by value: bounds [batch,2]
  * holds (lo, hi) per member and selects the eigenvalues lo < lambda <= hi, which is exactly the subset (i0_b, i1_b) =

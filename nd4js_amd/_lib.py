@@ -190,6 +190,13 @@ SIGNATURES = {
     "nd4hip_zhegst_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_i64, c_dp]),
     "nd4hip_zhegvd_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_i64, c_dp, c_dp]),
     "nd4hip_zhegvx_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_dp, c_dp, c_i64, c_dp, c_dp]),
+    # general complex LU and its solves (csrc/zgetrf.hip): P and info int32
+    "nd4hip_zgetrf_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, ctypes.c_void_p, ctypes.c_void_p]),
+    "nd4hip_zgetrf_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, ctypes.c_void_p, ctypes.c_void_p]),
+    "nd4hip_zgetrs_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_i64, ctypes.c_void_p, c_i64, c_dp, c_i64, c_dp]),
+    "nd4hip_zgetrs_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_i64, ctypes.c_void_p, c_i64, c_dp, c_i64, c_dp]),
+    "nd4hip_zgesv_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_zgesv_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
     "nd4hip_zpotrf_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp]),
     "nd4hip_zpotrs_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_i64, c_dp, c_dp]),
     "nd4hip_ztrsm_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_int, c_dp, c_i64, c_dp]),

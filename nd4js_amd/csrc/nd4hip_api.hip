@@ -1047,6 +1047,34 @@ extern "C" int nd4hip_zhegvx_batched_dev(nd4hip_handle* h, int64_t batch, int64_
   return nd4_zhegvx_run(h, batch, N, i0, i1, A, B, strideB, lambda, X, 0);
 }
 
+// ---- zlu_decomp / zlu_solve / zsolve (zgetrf.hip). Real flops: 8/3 N^3 for the factorisation, 8 N^2 K for the solve
+extern "C" int nd4hip_zgetrf_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* LU, int32_t* P, int32_t* info) {
+  ND4_ARGS(nd4_args_zgetrf(batch, N, A, LU, P));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zgetrf_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "zgetrf_batched", batch * (8.0 / 3.0 * (double)N * N * N), 16.0 * batch * 2.0 * (double)(N * N));
+  return nd4_zgetrf(h, batch, N, A, LU, P, info);
+}
+extern "C" int nd4hip_zgetrs_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, const double* LU, int64_t strideLU,
+                                         const int32_t* P, int64_t strideP, const double* Y, int64_t strideY, double* X) {
+  ND4_ARGS(nd4_args_zgetrs(batch, N, K, LU, strideLU, P, strideP, Y, strideY, X));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zgetrs_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "zgetrs_batched", batch * (8.0 * N * (double)N * K), 16.0 * batch * (double)(N * N + 2 * N * K));
+  return nd4_zgetrs(h, batch, N, K, LU, strideLU, P, strideP, Y, strideY, X);
+}
+int nd4_zgesv_run(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, const double* A, const double* Y, double* X, int64_t member0,
+                  int64_t* first_bad) {
+  ND4_ARGS(nd4_args_zgesv(batch, N, K, A, Y, X));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zgesv_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "zgesv_batched", batch * (8.0 / 3.0 * (double)N * N * N + 8.0 * N * (double)N * K), 16.0 * batch * (double)(N * N + 2 * N * K));
+  return nd4_zgesv(h, batch, N, K, A, Y, X, member0, first_bad);
+}
+extern "C" int nd4hip_zgesv_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, const double* A, const double* Y, double* X) {
+  return nd4_zgesv_run(h, batch, N, K, A, Y, X, 0, nullptr);
+}
+
 extern "C" int nd4hip_dsyevd_last_stages(nd4hip_handle* h, double* ms, int capacity) {
   ND4_CHECK_ARG(h != nullptr && (ms != nullptr || capacity <= 0), "nd4hip_dsyevd_last_stages: NULL argument");
   for (int i = 0; i < capacity && i < ND4HIP_SYEV_STAGES; ++i) ms[i] = h->syev_stage_ms[i];

@@ -432,6 +432,34 @@ inline int nd4_args_zhegvx(int64_t batch, int64_t N, int64_t i0, int64_t i1, con
   ND4_CHECK_ARG(A && B && lambda, "nd4hip_zhegvx_batched: NULL pointer");
   return ND4_ARGS_GO;
 }
+// ---- general complex LU and its solves (zgetrf.hip): N <= 2048 and K (65535 tiles of 64 columns in a grid dimension) before
+// anything is launched or written; info may be NULL
+constexpr int64_t ND4_ZLU_MAX_K = 65535 * 64;
+inline int nd4_args_zgetrf(int64_t batch, int64_t N, const void* A, const void* LU, const void* P) {
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_zgetrf_batched: negative extent");
+  ND4_CHECK_ARG(N <= 2048, "nd4hip_zgetrf_batched: N <= 2048");
+  if (batch == 0 || N == 0) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(A && LU && P, "nd4hip_zgetrf_batched: NULL pointer");
+  return ND4_ARGS_GO;
+}
+inline int nd4_args_zgetrs(int64_t batch, int64_t N, int64_t K, const void* LU, int64_t strideLU, const void* P, int64_t strideP, const void* Y,
+                           int64_t strideY, const void* X) {
+  ND4_CHECK_ARG(batch >= 0 && N >= 0 && K >= 0, "nd4hip_zgetrs_batched: negative extent");
+  ND4_CHECK_ARG(N <= 2048, "nd4hip_zgetrs_batched: N <= 2048");
+  ND4_CHECK_ARG(K <= ND4_ZLU_MAX_K, "nd4hip_zgetrs_batched: K exceeds 4 194 240 right-hand sides");
+  ND4_CHECK_ARG(nd4_strides_fit({{LU, strideLU, N * N}, {P, strideP, N}, {Y, strideY, N * K}}), ND4_STRIDE_TEXT, "zgetrs_batched");
+  if (batch == 0 || N == 0 || K == 0) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(LU && P && Y && X, "nd4hip_zgetrs_batched: NULL pointer");
+  return ND4_ARGS_GO;
+}
+inline int nd4_args_zgesv(int64_t batch, int64_t N, int64_t K, const void* A, const void* Y, const void* X) {
+  ND4_CHECK_ARG(batch >= 0 && N >= 0 && K >= 0, "nd4hip_zgesv_batched: negative extent");
+  ND4_CHECK_ARG(N <= 2048, "nd4hip_zgesv_batched: N <= 2048");
+  ND4_CHECK_ARG(K <= ND4_ZLU_MAX_K, "nd4hip_zgesv_batched: K exceeds 4 194 240 right-hand sides");
+  if (batch == 0 || N == 0 || K == 0) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(A && Y && X, "nd4hip_zgesv_batched: NULL pointer");
+  return ND4_ARGS_GO;
+}
 inline int nd4_args_sygvd(int algo, int64_t batch, int64_t N, const void* A, const void* B, int64_t strideB, const void* lambda) {
   ND4_CHECK_ARG(algo == 0 || algo == 1, "nd4hip_dsygvd_batched: algo must be 0 (dc) or 1 (jacobi)");
   ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsygvd_batched: negative extent");

@@ -1338,3 +1338,46 @@ extern "C" int nd4hip_zhegvx_batched_host(nd4hip_handle* h, int64_t batch, int64
   };
   return run_host(h, batch, ops, fn);
 }
+
+// zlu_decomp / zlu_solve / zsolve (zgetrf.hip): info = NULL: no flags wanted. A singular member does not stop zsolve's other chunks:
+// every chunk runs and comes back, the lowest singular member is reported at the end
+extern "C" int nd4hip_zgetrf_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* LU, int32_t* Pv, int32_t* info) {
+  ND4_ARGS(nd4_args_zgetrf(batch, N, A, LU, Pv));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zgetrf_batched: NULL handle");
+  std::vector<Operand> ops{in_op(A, N * N, N * N, 2 * D), out_op(LU, N * N, 2 * D), out_op(Pv, N, 4)};
+  if (info) ops.push_back(out_op(info, 1, 4));
+  const bool want = info != nullptr;
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return nd4hip_zgetrf_batched_dev(hd, nb, N, P(p, 0), P(p, 1), static_cast<int32_t*>(p[2]), want ? static_cast<int32_t*>(p[3]) : nullptr);
+  };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_zgetrs_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, const double* LU, int64_t strideLU,
+                                          const int32_t* Pv, int64_t strideP, const double* Y, int64_t strideY, double* X) {
+  ND4_ARGS(nd4_args_zgetrs(batch, N, K, LU, strideLU, Pv, strideP, Y, strideY, X));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zgetrs_batched: NULL handle");
+  std::vector<Operand> ops{in_op(LU, N * N, strideLU, 2 * D), in_op(Pv, N, strideP, 4), in_op(Y, N * K, strideY, 2 * D), out_op(X, N * K, 2 * D)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return nd4hip_zgetrs_batched_dev(hd, nb, N, K, P(p, 0), strideLU, static_cast<const int32_t*>(p[1]), strideP, P(p, 2), strideY, P(p, 3));
+  };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_zgesv_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, const double* A, const double* Y, double* X) {
+  ND4_ARGS(nd4_args_zgesv(batch, N, K, A, Y, X));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zgesv_batched: NULL handle");
+  std::vector<Operand> ops{in_op(A, N * N, N * N, 2 * D), in_op(Y, N * K, N * K, 2 * D), out_op(X, N * K, 2 * D)};
+  std::atomic<int64_t> worst(INT64_MAX);
+  ChunkFn fn = [=, &worst](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    int64_t bad = INT64_MAX;
+    const int rc = nd4_zgesv_run(hd, nb, N, K, P(p, 0), P(p, 1), P(p, 2), g_chunk_first, &bad);
+    if (rc != ND4HIP_ERR_SINGULAR) return rc;
+    for (int64_t seen = worst.load(); bad < seen && !worst.compare_exchange_weak(seen, bad);) {}
+    return 0;
+  };
+  ND4_TRY(run_host(h, batch, ops, fn));
+  if (worst.load() != INT64_MAX) {
+    nd4_set_error("zsolve(A,Y): A is singular. (matrix %lld)", (long long)worst.load());
+    return ND4HIP_ERR_SINGULAR;
+  }
+  return 0;
+}

@@ -258,6 +258,23 @@ int nd4_zhegvd_run(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, 
                    int64_t member0);
 int nd4_zhegvx_run(nd4hip_handle* h, int64_t batch, int64_t N, int64_t i0, int64_t i1, const double* A, const double* B, int64_t strideB,
                    double* lambda, double* X, int64_t member0);
+// general complex LU and its solves (zgetrf.hip): complex128 operands as interleaved doubles, 16-byte aligned, strides
+// in complex elements (P: in ints; 0 = one for all). Arguments already checked, batch >= 1, 1 <= N <= 2048, K >= 1. nd4_zgetrf (info:
+// device int32 [batch] or NULL, 1 + the first column with an unusable pivot, 0 if none) and nd4_zgetrs enqueue only; nd4_zgesv reads
+// one flag word per pass back and answers ND4HIP_ERR_SINGULAR with the lowest flagged member (also in *first_bad, may be NULL). The three
+// functions after them are the host-side arithmetic: tier (0: a member per wave in registers, 1: a member in LDS, 2: blocked), the largest dynamic
+// LDS request in bytes, members per pass (with_lu: LU in workspace, as in nd4_zgesv).
+int nd4_zgetrf(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* LU, int32_t* P, int32_t* info);
+int nd4_zgetrs(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, const double* LU, int64_t sLU, const int32_t* P, int64_t sP,
+               const double* Y, int64_t sY, double* X);
+int nd4_zgesv(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, const double* A, const double* Y, double* X, int64_t member0,
+              int64_t* first_bad);
+int nd4_zgetrf_tier(int64_t N);
+size_t nd4_zgetrf_lds(int64_t N);
+int64_t nd4_zgetrf_chunk(int64_t batch, int64_t N, bool with_lu);
+// zsolve's entry point with member0, shared by the _dev and _host forms (nd4hip_api.hip)
+int nd4_zgesv_run(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, const double* A, const double* Y, double* X, int64_t member0,
+                  int64_t* first_bad);
 // generalised symmetric-definite eigenproblem (sygv.hip): arguments already checked, batch >= 1, 1 <= N; sB / sL 0 = one for all;
 // member0: index of the first member in the caller's batch (error text); nd4_sygvd synchronises
 int nd4_sygvd(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B, int64_t sB, double* lambda,

@@ -1150,6 +1150,90 @@ def eigenvals_herm_gen(A, B, subset=None):
     return _hegv(A, B, "eigenvals_herm_gen(A,B)", False, subset)
 
 
+def _zlu_c128(t, name, what, real_goes_to):
+    """_chk_c128 with the complex LU functions' dtype errors"""
+    from .la import _zlu_dtype
+    if isinstance(t, torch.Tensor):
+        _zlu_dtype(name, what, t.is_complex(), t.dtype == torch.complex128, t.dtype, real_goes_to)
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous()):
+        raise TypeError("%s: %s must be a contiguous complex128 CUDA tensor" % (what, name))
+    return t.resolve_conj().resolve_neg()
+
+
+def _zlu_rhs(Y, what):
+    if not (isinstance(Y, torch.Tensor) and Y.is_cuda and Y.dtype in (torch.float64, torch.complex128)):
+        raise TypeError("%s: Y must be a complex128 or float64 CUDA tensor." % what)
+    return Y.to(torch.complex128).resolve_conj().resolve_neg().contiguous()
+
+
+def zlu_decomp(A, info=None):
+    """device-resident la.zlu_decomp: (LU complex128 [..., N, N], P int32 [..., N]) of the general complex128 A, the same bits; A is not
+    written. info["singular"] receives an int32 tensor [...] on A's device. Only enqueued."""
+    from .la import _hegv_square
+    what = "zlu_decomp(A)"
+    A = _zlu_c128(A, "A", what, "lu_decomp")
+    N = _hegv_square(tuple(A.shape), "A", what)
+    LU = torch.empty_like(A)
+    P = torch.empty(tuple(A.shape[:-1]), dtype=torch.int32, device=A.device)
+    flags = torch.zeros(tuple(A.shape[:-2]), dtype=torch.int32, device=A.device) if info is not None else None
+    if LU.numel():
+        h = _h(A)
+        _lib.check(h.lib.nd4hip_zgetrf_batched_dev(h.ptr, _batch(A.shape[:-2]), N, _p(A), _p(LU), ctypes.c_void_p(P.data_ptr()),
+                                                   ctypes.c_void_p(flags.data_ptr()) if flags is not None else None))
+    if info is not None:
+        info["singular"] = flags
+    return LU, P
+
+
+def zlu_solve(LU, P, Y=None):
+    """device-resident la.zlu_solve: X with A X = Y, the same bits; LU and P have Y's leading dimensions or are exactly [N, N] and [N]
+    (one factorisation for every member). Only enqueued."""
+    from .la import _zlu_solve_shapes
+    if Y is None:
+        Y = P
+        LU, P = LU
+    what = "zlu_solve(LU,P,Y)"
+    LU = _zlu_c128(LU, "LU", what, "lu_solve")
+    Y = _zlu_rhs(Y, what)
+    if not (isinstance(P, torch.Tensor) and P.is_cuda and P.dtype == torch.int32 and P.is_contiguous()):
+        raise TypeError("%s: P must be a contiguous int32 CUDA tensor" % what)
+    N, K, lead = _zlu_solve_shapes(tuple(LU.shape), tuple(P.shape), tuple(Y.shape))
+    one = LU.dim() == 2 and P.dim() == 1
+    if lead != tuple(Y.shape[:-2]) or not (one or (tuple(LU.shape[:-2]) == lead and tuple(P.shape[:-1]) == lead)):
+        raise ValueError("LU and y are not broadcast-compatible.")   # general broadcasting: host wrapper (la.py)
+    if LU.device != Y.device or P.device != Y.device:
+        raise ValueError("%s: the operands must be on the same device." % what)
+    X = torch.empty(lead + (N, K), dtype=torch.complex128, device=Y.device)
+    if X.numel():
+        h = _h(Y)
+        _lib.check(h.lib.nd4hip_zgetrs_batched_dev(h.ptr, _batch(lead), N, K, _p(LU), 0 if one else N * N, ctypes.c_void_p(P.data_ptr()),
+                                                   0 if one else N, _p(Y), N * K, _p(X)))
+    return X
+
+
+def zsolve(A, Y):
+    """device-resident la.zsolve: X with A X = Y for A [..., N, N] and Y [..., N, K] with equal leading dimensions, the same bits; A and Y
+    are not written. Raises as la.zsolve for a singular member."""
+    from .la import _hegv_square
+    what = "zsolve(A,Y)"
+    A = _zlu_c128(A, "A", what, "solve")
+    Y = _zlu_rhs(Y, what)
+    N = _hegv_square(tuple(A.shape), "A", what)
+    if Y.dim() < 2:
+        raise ValueError("%s: Y.ndim must be at least 2." % what)
+    if Y.shape[-2] != N:
+        raise ValueError("%s: A and Y don't match." % what)
+    if tuple(A.shape[:-2]) != tuple(Y.shape[:-2]):
+        raise ValueError("%s: A and Y are not broadcast-compatible." % what)   # general broadcasting: host wrapper (la.py)
+    if A.device != Y.device:
+        raise ValueError("%s: both operands must be on the same device." % what)
+    X = torch.empty_like(Y)
+    if X.numel():
+        h = _h(A)
+        _lib.check(h.lib.nd4hip_zgesv_batched_dev(h.ptr, _batch(A.shape[:-2]), N, int(Y.shape[-1]), _p(A), _p(Y), _p(X)))
+    return X
+
+
 def _stevx(d, e, subset, what, vectors, interval=None, info=None):
     from .la import _interval_what, _subset, _tridiag_args
     if interval is not None:

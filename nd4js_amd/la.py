@@ -21,6 +21,8 @@ JS wrapper nd4js_amd/js/index.js over the N-API shim; both call the same libnd4h
                                    -> nd4hip_zpotrf_batched_host, nd4hip_zpotrs_batched_host, nd4hip_ztrsm_batched_host, nd4hip_zhegst_batched_host
   eigen_herm_gen(A, B, subset), eigenvals_herm_gen(A, B, subset)   not in the reference   -> nd4hip_zhegvd_batched_host, nd4hip_zhegvx_batched_host
                                    (csrc/hegv.hip)
+  zlu_decomp(A, info), zlu_solve(LU, P, Y), zsolve(A, Y)   general complex128 A, not in the reference
+                                   -> nd4hip_zgetrf_batched_host, nd4hip_zgetrs_batched_host, nd4hip_zgesv_batched_host (csrc/zgetrf.hip)
   tridiag_eigen(d, e), tridiag_eigenvals(d, e), tridiag_count(d, e, x)   not in the reference   -> nd4hip_dstevx_batched_host, nd4hip_dstcnt_batched_host
                                    interval=(lo, hi) (opt-in, here and in eigen_sym): the eigenvalues in (lo, hi] -> nd4hip_dstevxv_batched_host,
                                    nd4hip_dsyevxv_batched_host, nd4hip_dsyevxv_tr_batched_host
@@ -1698,6 +1700,119 @@ def eigen_herm_gen(A, B, device=None, subset=None):
 def eigenvals_herm_gen(A, B, device=None, subset=None):
     """the eigenvalues of eigen_herm_gen alone (the same bits); no back-transformation is computed"""
     return _hegv(A, B, "eigenvals_herm_gen(A,B)", False, device, subset)
+
+
+def _zlu_dtype(name, what, is_complex, is_c128, dtype, real_goes_to):
+    """the dtype rule of the complex LU functions, shared with dev.py: complex128 as it is; a real matrix is sent to the real function"""
+    if not is_complex:
+        raise TypeError("%s: %s.dtype must be complex128; a real matrix goes to %s." % (what, name, real_goes_to))
+    if not is_c128:
+        raise TypeError("%s: only complex128 runs on the GPU path, got %s" % (what, dtype))
+
+
+def _zlu_solve_shapes(slu, sp, sy):
+    """lu_solve's shape checks and texts (lu.js:84-177) on the shapes of LU, P and Y: (N, K, broadcast leading shape)"""
+    if len(slu) < 2:
+        raise ValueError("LU must be at least 2D.")
+    if len(sp) < 1:
+        raise ValueError("P must be at least 1D.")
+    if len(sy) < 2:
+        raise ValueError("y must be at least 2D.")
+    N = int(slu[-2])
+    if slu[-1] != N:
+        raise ValueError("Last two dimensions of LU must be quadratic.")
+    if N != sy[-2]:
+        raise ValueError("LU and y don't match.")
+    if sp[-1] != N:
+        raise ValueError("LU and P don't match.")
+    if N > 2048:
+        raise ValueError("zlu_solve(LU,P,Y): N <= 2048.")
+    try:
+        lead = np.broadcast_shapes(tuple(slu[:-2]), tuple(sy[:-2]))
+    except ValueError:
+        raise ValueError("LU and y are not broadcast-compatible.")
+    try:
+        lead = np.broadcast_shapes(lead, tuple(sp[:-1]))
+    except ValueError:
+        raise ValueError("P is not broadcast-compatible.")
+    return N, int(sy[-1]), tuple(lead)
+
+
+def zlu_decomp(A, info=None, device=None):
+    """(LU complex128 [..., N, N], P int32 [..., N]) of the general complex128 A with lu_decomp's conventions (lu.js:42-62):
+    (L U)[i, :] = A[P[i], :], L unit lower below the diagonal of LU, U on and above it (LAPACK's zgetrf). The pivot of column j is the first
+    row i >= j with the largest |Re a_ij| + |Im a_ij|; l_ij = a_ij / a_jj is a true complex division. A singular matrix does not raise, as
+    in lu_decomp: a pivot whose |Re| + |Im| is zero or not finite leaves its column unscaled, and info["singular"] (info: a dict) receives
+    int32 [...]: 1 + the first such column of every member, 0 for none. N <= 2048 (csrc/zgetrf.hip). A float64 A raises TypeError: it
+    goes to lu_decomp."""
+    what = "zlu_decomp(A)"
+    A = np.asarray(A)
+    _zlu_dtype("A", what, A.dtype.kind == "c", A.dtype == np.complex128, A.dtype, "lu_decomp")
+    A = np.ascontiguousarray(A)
+    N = _hegv_square(A.shape, "A", what)
+    LU = np.empty(A.shape, dtype=np.complex128)
+    P = np.empty(A.shape[:-1], dtype=np.int32)
+    flags = np.zeros(A.shape[:-2], dtype=np.int32)
+    if LU.size:
+        h = _lib.handle(device)
+        _lib.check(h.lib.nd4hip_zgetrf_batched_host(h.ptr, int(np.prod(A.shape[:-2], dtype=np.int64)), N, _ptr(A), _ptr(LU), _ptr(P),
+                                                    _ptr(flags) if info is not None else None))
+    if info is not None:
+        info["singular"] = flags
+    return LU, P
+
+
+def zlu_solve(LU, P, Y=None, device=None):
+    """X complex128 with A X = Y for the (LU, P) of zlu_decomp and Y [..., N, K], complex128 or float64 (promoted); accepts
+    zlu_solve((LU, P), Y). LU, P and Y broadcast as in lu_solve, with its error texts."""
+    if Y is None:
+        Y = P
+        LU, P = LU
+    what = "zlu_solve(LU,P,Y)"
+    LU, Y = np.asarray(LU), np.asarray(Y)
+    _zlu_dtype("LU", what, LU.dtype.kind == "c", LU.dtype == np.complex128, LU.dtype, "lu_solve")
+    if Y.dtype != np.complex128 and Y.dtype != np.float64:
+        raise TypeError("%s: Y must be complex128 or float64." % what)
+    LU = np.ascontiguousarray(LU)
+    P = np.ascontiguousarray(np.asarray(P), dtype=np.int32)
+    Y = np.ascontiguousarray(Y, dtype=np.complex128)
+    N, K, lead = _zlu_solve_shapes(LU.shape, P.shape, Y.shape)
+    X = np.empty(lead + (N, K), dtype=np.complex128)
+    if X.size:
+        h = _lib.handle(device)
+        for cnt, (oLU, oP, oY), (sLU, sP, sY), b0 in _bcast_groups_n(lead, [LU.shape[:-2], P.shape[:-1], Y.shape[:-2]], [N * N, N, N * K]):
+            _lib.check(h.lib.nd4hip_zgetrs_batched_host(h.ptr, cnt, N, K, _off(LU, oLU, 16), sLU, _off(P, oP, 4), sP, _off(Y, oY, 16), sY,
+                                                        _off(X, b0 * N * K, 16)))
+    return X
+
+
+def zsolve(A, Y, device=None):
+    """X complex128 with A X = Y for the general complex128 A [..., N, N] and Y [..., N, K], complex128 or float64 (promoted): zlu_decomp
+    and zlu_solve in one call, LU and P in device workspace; the leading dimensions broadcast. A member with an unusable pivot raises
+    Nd4HipError with code -5, 'zsolve(A,Y): A is singular. (matrix <b>)', b the lowest such member. A float64 A raises TypeError: it goes
+    to solve."""
+    what = "zsolve(A,Y)"
+    A, Y = np.asarray(A), np.asarray(Y)
+    _zlu_dtype("A", what, A.dtype.kind == "c", A.dtype == np.complex128, A.dtype, "solve")
+    if Y.dtype != np.complex128 and Y.dtype != np.float64:
+        raise TypeError("%s: Y must be complex128 or float64." % what)
+    N = _hegv_square(A.shape, "A", what)
+    if Y.ndim < 2:
+        raise ValueError("%s: Y.ndim must be at least 2." % what)
+    if Y.shape[-2] != N:
+        raise ValueError("%s: A and Y don't match." % what)
+    try:
+        lead = tuple(np.broadcast_shapes(A.shape[:-2], Y.shape[:-2]))
+    except ValueError:
+        raise ValueError("%s: A and Y are not broadcast-compatible." % what)
+    K = int(Y.shape[-1])
+    A = np.ascontiguousarray(np.broadcast_to(A, lead + (N, N)))
+    Y = np.ascontiguousarray(np.broadcast_to(Y, lead + (N, K)), dtype=np.complex128)
+    X = np.empty(lead + (N, K), dtype=np.complex128)
+    if X.size:
+        h = _lib.handle(device)
+        _lib.check(h.lib.nd4hip_zgesv_batched_host(h.ptr, int(np.prod(lead, dtype=np.int64)), N, K, _ptr(A), _ptr(Y), _ptr(X)))
+    return X
 
 
 def _tridiag_args(d, e, what, ndim, shape):
