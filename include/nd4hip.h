@@ -796,6 +796,34 @@ int nd4hip_zgetrs_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64
 int nd4hip_zgesv_batched_dev  (nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, const double* A, const double* Y, double* X);
 int nd4hip_zgesv_batched_host (nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, const double* A, const double* Y, double* X);
 
+/* ---- complex QR: zqr_factor / zqr_apply_q / zqr_decomp / zqr_lstsq (csrc/zgeqrf.hip) ----
+ * LAPACK's zgeqrf / zunmqr / zungqr / zgels on row-major members, complex128 as interleaved (re, im) doubles on 16-byte boundaries,
+ * strides in complex elements. 0 <= N <= M <= 2048 and K <= 4 194 240, refused before anything is written; an extent of 0 is an empty call.
+ *   zgeqrf: F [batch,M,N] and tau [batch,N] with A = H_0 ... H_{N-1} [R; 0], H_k = I - tau_k v_k v_k^H, v_k = (0, .., 1, F[k+1:, k]), R on
+ *           and above the diagonal of F with an exactly real diagonal; A is not written. Only enqueues.
+ *   zunmqr: Z [batch,M,K] <- Q Z (adjoint = 1: Q^H Z) in place; strideF = M*N and strideTau = N, or both 0: one (F, tau) for every
+ *           member. Only enqueues.
+ *   zungqr: the thin Q [batch,M,N] = Q [I; 0] and R [batch,N,N] (zeros below the diagonal) of A in one call. Only enqueues.
+ *   zgels:  X [batch,N,K] = R^-1 (Q^H Y)[:N] for Y [batch,M,K]. tau = NULL: A is the matrix (strideA = M*N); else A is F of zgeqrf with
+ *           its tau (strideA = M*N, or 0: one factorisation for all, tau then [N]). A diagonal entry of R that is zero or not finite:
+ *           info (int32 [batch]) receives 1 + the first such column of every member, 0 for none; with info = NULL the call answers
+ *           ND4HIP_ERR_SINGULAR, 'zqr_lstsq(A,Y): A is rank-deficient. (matrix <b>)', b the lowest such member.
+ * Members that fit one workgroup's LDS (up to 96 x 96, M <= 152) have the bits of the numpy model in tests/zqr_common.py; above, the
+ * block updates run on the fp64 matrix cores. No sum depends on the run, the batch or a member's position. Profile ops
+ * "zgeqrf_batched", "zunmqr_batched", "zungqr_batched", "zgels_batched". */
+int nd4hip_zgeqrf_batched_dev (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* F, double* tau);
+int nd4hip_zgeqrf_batched_host(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* F, double* tau);
+int nd4hip_zunmqr_batched_dev (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t K, int adjoint, const double* F, int64_t strideF,
+                               const double* tau, int64_t strideTau, double* Z);
+int nd4hip_zunmqr_batched_host(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t K, int adjoint, const double* F, int64_t strideF,
+                               const double* tau, int64_t strideTau, double* Z);
+int nd4hip_zungqr_batched_dev (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* Q, double* R);
+int nd4hip_zungqr_batched_host(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* Q, double* R);
+int nd4hip_zgels_batched_dev  (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t K, const double* A, int64_t strideA,
+                               const double* tau, const double* Y, double* X, int32_t* info);
+int nd4hip_zgels_batched_host (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t K, const double* A, int64_t strideA,
+                               const double* tau, const double* Y, double* X, int32_t* info);
+
 /* ---- eigenpairs in a value interval: eigen_sym(S, interval=(lo, hi)), tridiag_eigen(d, e, interval) (csrc/syevx.hip) ----
  * dstevxv, dsyevxv and dsyevxv_tr are dstevx, dsyevx and dsyevx_tr with the subset of each member chosen by value: bounds [batch,2]
  * holds (lo, hi) per member and selects the eigenvalues lo < lambda <= hi, which is exactly the subset (i0_b, i1_b) =

@@ -197,6 +197,15 @@ SIGNATURES = {
     "nd4hip_zgetrs_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_i64, ctypes.c_void_p, c_i64, c_dp, c_i64, c_dp]),
     "nd4hip_zgesv_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
     "nd4hip_zgesv_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    # complex QR, its Q, the thin factors and least squares (csrc/zgeqrf.hip): info int32
+    "nd4hip_zgeqrf_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_zgeqrf_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_zunmqr_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_dp, c_i64, c_dp, c_i64, c_dp]),
+    "nd4hip_zunmqr_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_dp, c_i64, c_dp, c_i64, c_dp]),
+    "nd4hip_zungqr_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_zungqr_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_zgels_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_dp, c_i64, c_dp, c_dp, c_dp, ctypes.c_void_p]),
+    "nd4hip_zgels_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_dp, c_i64, c_dp, c_dp, c_dp, ctypes.c_void_p]),
     "nd4hip_zpotrf_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp]),
     "nd4hip_zpotrs_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_i64, c_dp, c_dp]),
     "nd4hip_ztrsm_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_int, c_dp, c_i64, c_dp]),

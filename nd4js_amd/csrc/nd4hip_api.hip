@@ -1075,6 +1075,44 @@ extern "C" int nd4hip_zgesv_batched_dev(nd4hip_handle* h, int64_t batch, int64_t
   return nd4_zgesv_run(h, batch, N, K, A, Y, X, 0, nullptr);
 }
 
+// ---- zqr_factor / zqr_apply_q / zqr_decomp / zqr_lstsq (zgeqrf.hip). Real flops: 8 N^2 (M - N / 3) for the factorisation and for
+// the thin Q, 8 N K (2 M - N) for Q Z, 4 N^2 K for the upper sweep
+extern "C" int nd4hip_zgeqrf_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* F, double* tau) {
+  ND4_ARGS(nd4_args_zgeqrf(batch, M, N, A, F, tau));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zgeqrf_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "zgeqrf_batched", batch * (8.0 * N * N * (M - N / 3.0)), 16.0 * batch * (double)(2 * M * N + N));
+  return nd4_zgeqrf(h, batch, M, N, A, F, tau);
+}
+extern "C" int nd4hip_zunmqr_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t K, int adjoint, const double* F,
+                                         int64_t strideF, const double* tau, int64_t strideTau, double* Z) {
+  ND4_ARGS(nd4_args_zunmqr(batch, M, N, K, adjoint, F, strideF, tau, strideTau, Z));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zunmqr_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "zunmqr_batched", batch * (8.0 * N * K * (2.0 * M - N)), 16.0 * batch * (double)(M * N + 2 * M * K));
+  return nd4_zunmqr(h, batch, M, N, K, adjoint != 0, F, strideF, tau, strideTau, Z);
+}
+extern "C" int nd4hip_zungqr_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* Q, double* R) {
+  ND4_ARGS(nd4_args_zungqr(batch, M, N, A, Q, R));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zungqr_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "zungqr_batched", batch * (16.0 * N * N * (M - N / 3.0)), 16.0 * batch * (double)(2 * M * N + N * N));
+  return nd4_zungqr(h, batch, M, N, A, Q, R);
+}
+int nd4_zgels_run(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t K, const double* A, int64_t strideA, const double* tau,
+                  const double* Y, double* X, int32_t* info, int64_t member0, int64_t* first_bad) {
+  ND4_ARGS(nd4_args_zgels(batch, M, N, K, A, strideA, tau, Y, X));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zgels_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "zgels_batched", batch * ((tau ? 0.0 : 8.0 * N * N * (M - N / 3.0)) + 8.0 * N * K * (2.0 * M - N) + 4.0 * N * N * K),
+               16.0 * batch * (double)(M * N + M * K + N * K));
+  return nd4_zgels(h, batch, M, N, K, A, strideA, tau, Y, X, info, member0, first_bad);
+}
+extern "C" int nd4hip_zgels_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t K, const double* A, int64_t strideA,
+                                        const double* tau, const double* Y, double* X, int32_t* info) {
+  return nd4_zgels_run(h, batch, M, N, K, A, strideA, tau, Y, X, info, 0, nullptr);
+}
+
 extern "C" int nd4hip_dsyevd_last_stages(nd4hip_handle* h, double* ms, int capacity) {
   ND4_CHECK_ARG(h != nullptr && (ms != nullptr || capacity <= 0), "nd4hip_dsyevd_last_stages: NULL argument");
   for (int i = 0; i < capacity && i < ND4HIP_SYEV_STAGES; ++i) ms[i] = h->syev_stage_ms[i];

@@ -460,6 +460,34 @@ inline int nd4_args_zgesv(int64_t batch, int64_t N, int64_t K, const void* A, co
   ND4_CHECK_ARG(A && Y && X, "nd4hip_zgesv_batched: NULL pointer");
   return ND4_ARGS_GO;
 }
+// ---- complex QR (zgeqrf.hip): N <= M <= 2048 and K before anything is launched or written. zgels: tau = NULL: A is the matrix and
+// strideA must be M*N; else A is F with its tau, strideA M*N or 0 (one factorisation for all); info may be NULL
+inline int nd4_args_zqr(const char* op, int64_t batch, int64_t M, int64_t N, int64_t K, Nd4Ptrs ptrs) {
+  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0 && K >= 0, "nd4hip_%s: negative extent", op);
+  ND4_CHECK_ARG(N <= M && M <= 2048, "nd4hip_%s: the shape must satisfy N <= M <= 2048", op);
+  ND4_CHECK_ARG(K <= ND4_ZLU_MAX_K, "nd4hip_%s: K exceeds 4 194 240 columns", op);
+  if (batch == 0 || N == 0 || K == 0) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(nd4_none_null(ptrs), "nd4hip_%s: NULL pointer", op);
+  return ND4_ARGS_GO;
+}
+inline int nd4_args_zgeqrf(int64_t batch, int64_t M, int64_t N, const void* A, const void* F, const void* tau) {
+  return nd4_args_zqr("zgeqrf_batched", batch, M, N, 1, {A, F, tau});
+}
+inline int nd4_args_zunmqr(int64_t batch, int64_t M, int64_t N, int64_t K, int adjoint, const void* F, int64_t strideF, const void* tau,
+                           int64_t strideTau, const void* Z) {
+  ND4_CHECK_ARG(adjoint == 0 || adjoint == 1, "nd4hip_zunmqr_batched: adjoint must be 0 or 1");
+  ND4_CHECK_ARG(M < 0 || N < 0 || ((strideF == 0 && strideTau == 0) || (strideF == M * N && strideTau == N)),
+                "nd4hip_zunmqr_batched: the strides of F and tau must be M*N and N, or both 0");
+  return nd4_args_zqr("zunmqr_batched", batch, M, N, K, {F, tau, Z});
+}
+inline int nd4_args_zungqr(int64_t batch, int64_t M, int64_t N, const void* A, const void* Q, const void* R) {
+  return nd4_args_zqr("zungqr_batched", batch, M, N, 1, {A, Q, R});
+}
+inline int nd4_args_zgels(int64_t batch, int64_t M, int64_t N, int64_t K, const void* A, int64_t strideA, const void* tau, const void* Y,
+                          const void* X) {
+  ND4_CHECK_ARG(M < 0 || N < 0 || strideA == M * N || (tau && strideA == 0), "nd4hip_zgels_batched: strideA must be M*N, or 0 with a factorisation");
+  return nd4_args_zqr("zgels_batched", batch, M, N, K, {A, Y, X});
+}
 inline int nd4_args_sygvd(int algo, int64_t batch, int64_t N, const void* A, const void* B, int64_t strideB, const void* lambda) {
   ND4_CHECK_ARG(algo == 0 || algo == 1, "nd4hip_dsygvd_batched: algo must be 0 (dc) or 1 (jacobi)");
   ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsygvd_batched: negative extent");

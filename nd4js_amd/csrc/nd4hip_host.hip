@@ -1381,3 +1381,56 @@ extern "C" int nd4hip_zgesv_batched_host(nd4hip_handle* h, int64_t batch, int64_
   }
   return 0;
 }
+
+// zqr_factor / zqr_apply_q / zqr_decomp / zqr_lstsq (zgeqrf.hip). zgels: tau = NULL: A is the matrix; info = NULL: a rank-deficient member is
+// an error, which does not stop the other chunks: every chunk runs and comes back, the lowest such member is reported at the end
+extern "C" int nd4hip_zgeqrf_batched_host(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* F, double* tau) {
+  ND4_ARGS(nd4_args_zgeqrf(batch, M, N, A, F, tau));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zgeqrf_batched: NULL handle");
+  std::vector<Operand> ops{in_op(A, M * N, M * N, 2 * D), out_op(F, M * N, 2 * D), out_op(tau, N, 2 * D)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) { return nd4hip_zgeqrf_batched_dev(hd, nb, M, N, P(p, 0), P(p, 1), P(p, 2)); };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_zunmqr_batched_host(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t K, int adjoint, const double* F,
+                                          int64_t strideF, const double* tau, int64_t strideTau, double* Z) {
+  ND4_ARGS(nd4_args_zunmqr(batch, M, N, K, adjoint, F, strideF, tau, strideTau, Z));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zunmqr_batched: NULL handle");
+  std::vector<Operand> ops{in_op(F, M * N, strideF, 2 * D), in_op(tau, N, strideTau, 2 * D), inout_op(Z, M * K, 2 * D)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return nd4hip_zunmqr_batched_dev(hd, nb, M, N, K, adjoint, P(p, 0), strideF, P(p, 1), strideTau, P(p, 2));
+  };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_zungqr_batched_host(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* Q, double* R) {
+  ND4_ARGS(nd4_args_zungqr(batch, M, N, A, Q, R));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zungqr_batched: NULL handle");
+  std::vector<Operand> ops{in_op(A, M * N, M * N, 2 * D), out_op(Q, M * N, 2 * D), out_op(R, N * N, 2 * D)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) { return nd4hip_zungqr_batched_dev(hd, nb, M, N, P(p, 0), P(p, 1), P(p, 2)); };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_zgels_batched_host(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t K, const double* A, int64_t strideA,
+                                         const double* tau, const double* Y, double* X, int32_t* info) {
+  ND4_ARGS(nd4_args_zgels(batch, M, N, K, A, strideA, tau, Y, X));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zgels_batched: NULL handle");
+  // the operands that are wanted, in the order A, Y, X, [tau], [info]
+  std::vector<Operand> ops{in_op(A, M * N, strideA, 2 * D), in_op(Y, M * K, M * K, 2 * D), out_op(X, N * K, 2 * D)};
+  const int it = tau ? (int)ops.size() : -1;
+  if (tau) ops.push_back(in_op(tau, N, strideA ? N : 0, 2 * D));
+  const int ii = info ? (int)ops.size() : -1;
+  if (info) ops.push_back(out_op(info, 1, 4));
+  std::atomic<int64_t> worst(INT64_MAX);
+  ChunkFn fn = [=, &worst](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    int64_t bad = INT64_MAX;
+    const int rc = nd4_zgels_run(hd, nb, M, N, K, P(p, 0), strideA, it >= 0 ? P(p, it) : nullptr, P(p, 1), P(p, 2),
+                                 ii >= 0 ? static_cast<int32_t*>(p[ii]) : nullptr, g_chunk_first, &bad);
+    if (rc != ND4HIP_ERR_SINGULAR) return rc;
+    for (int64_t seen = worst.load(); bad < seen && !worst.compare_exchange_weak(seen, bad);) {}
+    return 0;
+  };
+  ND4_TRY(run_host(h, batch, ops, fn));
+  if (worst.load() != INT64_MAX) {
+    nd4_set_error("zqr_lstsq(A,Y): A is rank-deficient. (matrix %lld)", (long long)worst.load());
+    return ND4HIP_ERR_SINGULAR;
+  }
+  return 0;
+}

@@ -272,9 +272,39 @@ int nd4_zgesv(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, const doubl
 int nd4_zgetrf_tier(int64_t N);
 size_t nd4_zgetrf_lds(int64_t N);
 int64_t nd4_zgetrf_chunk(int64_t batch, int64_t N, bool with_lu);
+// the pieces the complex QR takes from zgetrf.hip (zgeqrf.hip): C [M][N] (row pitch ldc) -= A [M][K] (lda) B [K][N] (ldb) on the fp64
+// matrix cores for nb members (pointers to interleaved doubles, pitches and member strides in complex elements, stride 0: one operand
+// for all; the three do not overlap, every base 16-byte aligned), and the upper sweep of nd4_zgetrs: U X = X in place on X [nb, N, K],
+// U the upper triangle of LU (row pitch N, members sLU apart). Both enqueue only
+struct ZluUpd {
+  const double* A; long lda, sA;
+  const double* B; long ldb, sB;
+  double* C; long ldc, sC;
+  int M, N, K;
+};
+int zlu_update_launch(nd4hip_handle* h, int64_t nb, const ZluUpd& u);
+int nd4_zgetrs_upper(nd4hip_handle* h, int64_t nb, int N, int K, const double* LU, int64_t sLU, double* X);
 // zsolve's entry point with member0, shared by the _dev and _host forms (nd4hip_api.hip)
 int nd4_zgesv_run(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, const double* A, const double* Y, double* X, int64_t member0,
                   int64_t* first_bad);
+// complex QR, the application of its Q, the thin factors and least squares (zgeqrf.hip): complex128 operands as
+// interleaved doubles, 16-byte aligned, strides in complex elements (0 = one for all). Arguments already checked, batch >= 1,
+// 1 <= N <= M <= 2048, K >= 1. All enqueue only, except nd4_zgels with info = NULL, which reads one flag word per pass back and answers
+// ND4HIP_ERR_SINGULAR with the lowest flagged member (also in *first_bad, may be NULL). nd4_zgels: tau = NULL: A is the matrix, else the F
+// of nd4_zgeqrf. The three functions after them are the host-side arithmetic: tier (0: a member in LDS, 1: blocked), the largest dynamic
+// LDS request in bytes, members per pass (products n columns wide, extra complex elements of workspace per member).
+int nd4_zgeqrf(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* F, double* tau);
+int nd4_zunmqr(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t K, bool adjoint, const double* F, int64_t sF, const double* tau,
+               int64_t sTau, double* Z);
+int nd4_zungqr(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* Q, double* R);
+int nd4_zgels(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t K, const double* A, int64_t sA, const double* tau, const double* Y,
+              double* X, int32_t* info, int64_t member0, int64_t* first_bad);
+int nd4_zgeqrf_tier(int64_t M, int64_t N);
+size_t nd4_zgeqrf_lds(int64_t M, int64_t N);
+int64_t nd4_zgeqrf_chunk(int64_t batch, int64_t M, int64_t N, int64_t n, int64_t extra);
+// zqr_lstsq's entry point with member0, shared by the _dev and _host forms (nd4hip_api.hip)
+int nd4_zgels_run(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t K, const double* A, int64_t strideA, const double* tau,
+                  const double* Y, double* X, int32_t* info, int64_t member0, int64_t* first_bad);
 // generalised symmetric-definite eigenproblem (sygv.hip): arguments already checked, batch >= 1, 1 <= N; sB / sL 0 = one for all;
 // member0: index of the first member in the caller's batch (error text); nd4_sygvd synchronises
 int nd4_sygvd(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B, int64_t sB, double* lambda,

@@ -447,12 +447,7 @@ __global__ __launch_bounds__(ZLU_T) void zlu_u12(cd* __restrict__ LU, int N, int
 
 // C [M][N] (row pitch ldc) -= A [M][K] (lda) B [K][N] (ldb) on the fp64 MFMA; the three do not overlap in what is read and written,
 // every base is 16-byte aligned. grid (column tiles of 64, row tiles of 128, members); strides 0: one operand for all
-struct ZluUpd {
-  const double* A; long lda, sA;
-  const double* B; long ldb, sB;
-  double* C; long ldc, sC;
-  int M, N, K;
-};
+// (struct ZluUpd: nd4hip_internal.h)
 __global__ __launch_bounds__(256, 2) void zlu_update(ZluUpd g) {
   __shared__ __attribute__((aligned(16))) double lds[2 * ZBUF];   // [buf][A | B]
   const int m0 = blockIdx.y * ZBM, n0 = blockIdx.x * ZBN;
@@ -600,13 +595,6 @@ template <class T> int zlu_alloc(nd4hip_handle* h, size_t n, T** out) {
   return 0;
 }
 
-int zlu_update_launch(nd4hip_handle* h, int64_t nb, const ZluUpd& u) {
-  const dim3 grid((unsigned)((u.N + ZBN - 1) / ZBN), (unsigned)((u.M + ZBM - 1) / ZBM), (unsigned)nb);
-  hipLaunchKernelGGL(zlu_update, grid, dim3(256), 0, h->stream, u);
-  ND4_HIP(hipGetLastError());
-  return 0;
-}
-
 // LU, P [nb members] from A; flags [1 + nb] zero on entry; ipiv [nb][N] scratch of the blocked tier
 int zlu_factor(nd4hip_handle* h, int64_t nb, int N, const cd* A, cd* LU, int* P, int* flags, int* ipiv) {
   if (N <= ZLU_REG_N) {
@@ -672,9 +660,30 @@ int zlu_solve(nd4hip_handle* h, int64_t nb, int N, int64_t K64, const cd* LU, in
     const ZluUpd u{lu + 2 * ((int64_t)j1 * N + j0), N, sLU, x + 2 * (int64_t)j0 * K, K, nk, x + 2 * (int64_t)j1 * K, K, nk, rest, K, kb};
     ND4_TRY(zlu_update_launch(h, nb, u));
   }
-  for (int s = nblocks - 1; s >= 0; --s) {                     // U X = that
+  return nd4_zgetrs_upper(h, nb, N, K, lu, sLU, x);            // U X = that
+}
+
+inline bool zlu_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+}  // namespace
+
+int zlu_update_launch(nd4hip_handle* h, int64_t nb, const ZluUpd& u) {
+  const dim3 grid((unsigned)((u.N + ZBN - 1) / ZBN), (unsigned)((u.M + ZBM - 1) / ZBM), (unsigned)nb);
+  hipLaunchKernelGGL(zlu_update, grid, dim3(256), 0, h->stream, u);
+  ND4_HIP(hipGetLastError());
+  return 0;
+}
+
+// the upper sweep of the blocked solve, U X = X in place: X [nb, N, K] dense, U the upper triangle of LU (row pitch N, members sLU
+// apart, 0: one for all), blocks of 64 from the last: zgetrs_diag, then zlu_update on the rows above. K <= 4 194 240. Enqueues only
+int nd4_zgetrs_upper(nd4hip_handle* h, int64_t nb, int N, int K, const double* lu, int64_t sLU, double* x) {
+  const unsigned tiles = (unsigned)((K + ZLU_NB - 1) / ZLU_NB);
+  const int64_t nk = (int64_t)N * K;
+  const int nblocks = (N + ZLU_NB - 1) / ZLU_NB;
+  ND4_TRY(zlu_attr(reinterpret_cast<const void*>(&zgetrs_diag), ZLU_BLOCK_LDS));
+  for (int s = nblocks - 1; s >= 0; --s) {
     const int j0 = s * ZLU_NB, kb = N - j0 < ZLU_NB ? N - j0 : ZLU_NB;
-    hipLaunchKernelGGL(zgetrs_diag, dim3((unsigned)nb, tiles), dim3(ZLU_T), ZLU_BLOCK_LDS, h->stream, LU, (long)sLU, X, N, K, j0, kb, 1);
+    hipLaunchKernelGGL(zgetrs_diag, dim3((unsigned)nb, tiles), dim3(ZLU_T), ZLU_BLOCK_LDS, h->stream, ccd(lu), (long)sLU, mcd(x), N, K, j0, kb, 1);
     ND4_HIP(hipGetLastError());
     if (j0 == 0) break;
     const ZluUpd u{lu + 2 * (int64_t)j0, N, sLU, x + 2 * (int64_t)j0 * K, K, nk, x, K, nk, j0, K, kb};
@@ -682,10 +691,6 @@ int zlu_solve(nd4hip_handle* h, int64_t nb, int N, int64_t K64, const cd* LU, in
   }
   return 0;
 }
-
-inline bool zlu_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-}  // namespace
 
 // ---- the host-side arithmetic of the tiers (tools/zlu_host_check.hip) ----
 int nd4_zgetrf_tier(int64_t N) { return N <= ZLU_REG_N ? 0 : N <= ZLU_SMALL_N ? 1 : 2; }

@@ -1234,6 +1234,85 @@ def zsolve(A, Y):
     return X
 
 
+def zqr_factor(A):
+    """device-resident la.zqr_factor: (F complex128 [..., M, N], tau complex128 [..., N]) of the complex128 A, the same bits; A is not
+    written. Only enqueued."""
+    from .la import _zqr_shape
+    what = "zqr_factor(A)"
+    A = _zlu_c128(A, "A", what, "qr_decomp")
+    M, N = _zqr_shape(tuple(A.shape), "A", what)
+    F = torch.empty_like(A)
+    tau = torch.empty(tuple(A.shape[:-2]) + (N,), dtype=torch.complex128, device=A.device)
+    if F.numel():
+        h = _h(A)
+        _lib.check(h.lib.nd4hip_zgeqrf_batched_dev(h.ptr, _batch(A.shape[:-2]), M, N, _p(A), _p(F), _p(tau)))
+    return F, tau
+
+
+def zqr_apply_q(F, tau, Z, adjoint=False):
+    """device-resident la.zqr_apply_q: Q Z (adjoint: Q^H Z), the same bits; F and tau have Z's leading dimensions or are exactly one
+    member. Z is not written. Only enqueued."""
+    from .la import _zqr_factored
+    what = "zqr_apply_q(F,tau,Z)"
+    F, tau = _zlu_c128(F, "F", what, "qr_decomp"), _zlu_c128(tau, "tau", what, "qr_decomp")
+    Z = _zlu_rhs(Z, what).clone()
+    M, N, K, lead, one = _zqr_factored(tuple(F.shape), tuple(tau.shape), tuple(Z.shape), what)
+    if F.device != Z.device or tau.device != Z.device:
+        raise ValueError("%s: the operands must be on the same device." % what)
+    if Z.numel() and N:
+        h = _h(Z)
+        _lib.check(h.lib.nd4hip_zunmqr_batched_dev(h.ptr, _batch(lead), M, N, K, 1 if adjoint else 0, _p(F), 0 if one else M * N, _p(tau),
+                                                   0 if one else N, _p(Z)))
+    return Z
+
+
+def zqr_decomp(A):
+    """device-resident la.zqr_decomp: the thin (Q [..., M, N], R [..., N, N]) of the complex128 A, the same bits; A is not written. Only
+    enqueued."""
+    from .la import _zqr_shape
+    what = "zqr_decomp(A)"
+    A = _zlu_c128(A, "A", what, "qr_decomp")
+    M, N = _zqr_shape(tuple(A.shape), "A", what)
+    Q = torch.empty_like(A)
+    R = torch.empty(tuple(A.shape[:-2]) + (N, N), dtype=torch.complex128, device=A.device)
+    if Q.numel():
+        h = _h(A)
+        _lib.check(h.lib.nd4hip_zungqr_batched_dev(h.ptr, _batch(A.shape[:-2]), M, N, _p(A), _p(Q), _p(R)))
+    return Q, R
+
+
+def zqr_lstsq(A, Y, info=None):
+    """device-resident la.zqr_lstsq: X [..., N, K] that minimises |A X - Y|_F, or zqr_lstsq((F, tau), Y), the same bits; the operands are
+    not written. Raises as la.zqr_lstsq for a rank-deficient member unless info (a dict) is given: info["singular"] then receives an
+    int32 tensor [...] on A's device and the call only enqueues."""
+    from .la import _zqr_factored, _zqr_shape
+    what = "zqr_lstsq(A,Y)"
+    tau = None
+    if isinstance(A, tuple):
+        A, tau = A
+        tau = _zlu_c128(tau, "tau", what, "qr_lstsq")
+    A = _zlu_c128(A, "A", what, "qr_lstsq")
+    Y = _zlu_rhs(Y, what)
+    if tau is not None:
+        M, N, K, lead, one = _zqr_factored(tuple(A.shape), tuple(tau.shape), tuple(Y.shape), what)
+    else:
+        M, N = _zqr_shape(tuple(A.shape), "A", what)
+        if Y.dim() < 2 or Y.shape[-2] != M or tuple(Y.shape[:-2]) != tuple(A.shape[:-2]):
+            raise ValueError("%s: A and Y don't match." % what)
+        K, lead, one = int(Y.shape[-1]), tuple(A.shape[:-2]), False
+    if A.device != Y.device or (tau is not None and tau.device != Y.device):
+        raise ValueError("%s: the operands must be on the same device." % what)
+    X = torch.empty(lead + (N, K), dtype=torch.complex128, device=Y.device)
+    flags = torch.zeros(lead, dtype=torch.int32, device=Y.device) if info is not None else None
+    if X.numel():
+        h = _h(Y)
+        _lib.check(h.lib.nd4hip_zgels_batched_dev(h.ptr, _batch(lead), M, N, K, _p(A), 0 if one else M * N, _p(tau) if tau is not None else None,
+                                                  _p(Y), _p(X), ctypes.c_void_p(flags.data_ptr()) if flags is not None else None))
+    if info is not None:
+        info["singular"] = flags
+    return X
+
+
 def _stevx(d, e, subset, what, vectors, interval=None, info=None):
     from .la import _interval_what, _subset, _tridiag_args
     if interval is not None:

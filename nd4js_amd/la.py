@@ -21,6 +21,9 @@ JS wrapper nd4js_amd/js/index.js over the N-API shim; both call the same libnd4h
                                    -> nd4hip_zpotrf_batched_host, nd4hip_zpotrs_batched_host, nd4hip_ztrsm_batched_host, nd4hip_zhegst_batched_host
   eigen_herm_gen(A, B, subset), eigenvals_herm_gen(A, B, subset)   not in the reference   -> nd4hip_zhegvd_batched_host, nd4hip_zhegvx_batched_host
                                    (csrc/hegv.hip)
+  zqr_factor(A), zqr_apply_q(F, tau, Z, adjoint), zqr_decomp(A), zqr_lstsq(A, Y, info)   complex128 A [..., M, N], N <= M, not in the reference
+                                   -> nd4hip_zgeqrf_batched_host, nd4hip_zunmqr_batched_host, nd4hip_zungqr_batched_host,
+                                      nd4hip_zgels_batched_host (csrc/zgeqrf.hip)
   zlu_decomp(A, info), zlu_solve(LU, P, Y), zsolve(A, Y)   general complex128 A, not in the reference
                                    -> nd4hip_zgetrf_batched_host, nd4hip_zgetrs_batched_host, nd4hip_zgesv_batched_host (csrc/zgetrf.hip)
   tridiag_eigen(d, e), tridiag_eigenvals(d, e), tridiag_count(d, e, x)   not in the reference   -> nd4hip_dstevx_batched_host, nd4hip_dstcnt_batched_host
@@ -1812,6 +1815,129 @@ def zsolve(A, Y, device=None):
     if X.size:
         h = _lib.handle(device)
         _lib.check(h.lib.nd4hip_zgesv_batched_host(h.ptr, int(np.prod(lead, dtype=np.int64)), N, K, _ptr(A), _ptr(Y), _ptr(X)))
+    return X
+
+
+def _zqr_shape(shape, name, what):
+    """(M, N) of a tall complex member stack for the complex QR functions, shared with dev.py"""
+    if len(shape) < 2:
+        raise ValueError("%s: %s.ndim must be at least 2." % (what, name))
+    M, N = int(shape[-2]), int(shape[-1])
+    if M < N:
+        raise ValueError("%s: %s must have at least as many rows as columns (M >= N)." % (what, name))
+    if M > 2048:
+        raise ValueError("%s: M <= 2048." % what)
+    return M, N
+
+
+def _zqr_factored(sf, st, sz, what):
+    """the shapes of (F, tau) against Z or Y [..., M, K]: (M, N, K, leading shape, one factorisation for all)"""
+    M, N = _zqr_shape(sf, "F", what)
+    if len(st) < 1 or int(st[-1]) != N or tuple(st[:-1]) != tuple(sf[:-2]):
+        raise ValueError("%s: F and tau don't match." % what)
+    if len(sz) < 2 or int(sz[-2]) != M:
+        raise ValueError("%s: F and the right-hand side don't match." % what)
+    lead, one = tuple(sz[:-2]), len(sf) == 2
+    if not one and tuple(sf[:-2]) != lead:
+        raise ValueError("%s: F must have the right-hand side's leading dimensions or be one member." % what)
+    return M, N, int(sz[-1]), lead, one
+
+
+def _zqr_tau(tau, what):
+    tau = np.asarray(tau)
+    if tau.dtype != np.complex128:
+        raise TypeError("%s: tau.dtype must be complex128, as zqr_factor returns it." % what)
+    return np.ascontiguousarray(tau)
+
+
+def _zqr_rhs(Y, what):
+    Y = np.asarray(Y)
+    if Y.dtype != np.complex128 and Y.dtype != np.float64:
+        raise TypeError("%s: the right-hand side must be complex128 or float64." % what)
+    return np.ascontiguousarray(Y, dtype=np.complex128)
+
+
+def zqr_factor(A, device=None):
+    """(F complex128 [..., M, N], tau complex128 [..., N]) of the complex128 A, N <= M <= 2048 (LAPACK's zgeqrf on row-major members):
+    A = H_0 ... H_{N-1} [R; 0], H_k = I - tau_k v_k v_k^H, v_k zero above row k, 1 in row k, its tail in F[k+1:, k]; R on and above the
+    diagonal of F, its diagonal exactly real. A -> 2^m A leaves tails and tau bit-identical and scales R exactly (csrc/zgeqrf.hip). A
+    float64 A raises TypeError: it goes to qr_decomp."""
+    what = "zqr_factor(A)"
+    A = np.asarray(A)
+    _zlu_dtype("A", what, A.dtype.kind == "c", A.dtype == np.complex128, A.dtype, "qr_decomp")
+    A = np.ascontiguousarray(A)
+    M, N = _zqr_shape(A.shape, "A", what)
+    F = np.empty(A.shape, dtype=np.complex128)
+    tau = np.empty(A.shape[:-2] + (N,), dtype=np.complex128)
+    if F.size:
+        h = _lib.handle(device)
+        _lib.check(h.lib.nd4hip_zgeqrf_batched_host(h.ptr, int(np.prod(A.shape[:-2], dtype=np.int64)), M, N, _ptr(A), _ptr(F), _ptr(tau)))
+    return F, tau
+
+
+def zqr_apply_q(F, tau, Z, adjoint=False, device=None):
+    """Q Z (adjoint: Q^H Z) complex128 [..., M, K] for the (F, tau) of zqr_factor and Z complex128 or float64 (promoted). F and tau have
+    Z's leading dimensions or are exactly one member [M, N], [N]. Z is not written."""
+    what = "zqr_apply_q(F,tau,Z)"
+    F = np.asarray(F)
+    _zlu_dtype("F", what, F.dtype.kind == "c", F.dtype == np.complex128, F.dtype, "qr_decomp")
+    F, tau = np.ascontiguousarray(F), _zqr_tau(tau, what)
+    Z = np.array(_zqr_rhs(Z, what))
+    M, N, K, lead, one = _zqr_factored(F.shape, tau.shape, Z.shape, what)
+    if Z.size and N:
+        h = _lib.handle(device)
+        _lib.check(h.lib.nd4hip_zunmqr_batched_host(h.ptr, int(np.prod(lead, dtype=np.int64)), M, N, K, 1 if adjoint else 0, _ptr(F),
+                                                    0 if one else M * N, _ptr(tau), 0 if one else N, _ptr(Z)))
+    return Z
+
+
+def zqr_decomp(A, device=None):
+    """the thin factors (Q complex128 [..., M, N], R complex128 [..., N, N]) of the complex128 A, N <= M <= 2048, in one library call:
+    Q = H_0 ... H_{N-1} [I; 0] with the bits of zqr_apply_q(F, tau, I[:, :N]), R upper triangular with an exactly real diagonal (of either
+    sign) and exact zeros below it. A float64 A raises TypeError: it goes to qr_decomp."""
+    what = "zqr_decomp(A)"
+    A = np.asarray(A)
+    _zlu_dtype("A", what, A.dtype.kind == "c", A.dtype == np.complex128, A.dtype, "qr_decomp")
+    A = np.ascontiguousarray(A)
+    M, N = _zqr_shape(A.shape, "A", what)
+    Q = np.empty(A.shape, dtype=np.complex128)
+    R = np.empty(A.shape[:-2] + (N, N), dtype=np.complex128)
+    if Q.size:
+        h = _lib.handle(device)
+        _lib.check(h.lib.nd4hip_zungqr_batched_host(h.ptr, int(np.prod(A.shape[:-2], dtype=np.int64)), M, N, _ptr(A), _ptr(Q), _ptr(R)))
+    return Q, R
+
+
+def zqr_lstsq(A, Y, info=None, device=None):
+    """X complex128 [..., N, K] that minimises |A X - Y|_F for the complex128 A [..., M, N], N <= M <= 2048, and Y [..., M, K], complex128
+    or float64 (promoted), with A's leading dimensions: X = R^-1 (Q^H Y)[:N]. zqr_lstsq((F, tau), Y) takes a factorisation of zqr_factor,
+    with Y's leading dimensions or exactly one member. A diagonal entry of R that is zero or not finite raises Nd4HipError with code -5,
+    'zqr_lstsq(A,Y): A is rank-deficient. (matrix <b>)', b the lowest such member; with info (a dict) nothing is raised and
+    info["singular"] receives int32 [...]: 1 + the first such column, 0 for none. A float64 A raises TypeError: it goes to qr_lstsq."""
+    what = "zqr_lstsq(A,Y)"
+    tau = None
+    if isinstance(A, tuple):
+        A, tau = A
+        tau = _zqr_tau(tau, what)
+    A = np.asarray(A)
+    _zlu_dtype("A", what, A.dtype.kind == "c", A.dtype == np.complex128, A.dtype, "qr_lstsq")
+    A, Y = np.ascontiguousarray(A), _zqr_rhs(Y, what)
+    if tau is not None:
+        M, N, K, lead, one = _zqr_factored(A.shape, tau.shape, Y.shape, what)
+    else:
+        M, N = _zqr_shape(A.shape, "A", what)
+        if Y.ndim < 2 or Y.shape[-2] != M or tuple(Y.shape[:-2]) != tuple(A.shape[:-2]):
+            raise ValueError("%s: A and Y don't match." % what)
+        K, lead, one = int(Y.shape[-1]), tuple(A.shape[:-2]), False
+    X = np.empty(lead + (N, K), dtype=np.complex128)
+    flags = np.zeros(lead, dtype=np.int32)
+    if X.size:
+        h = _lib.handle(device)
+        _lib.check(h.lib.nd4hip_zgels_batched_host(h.ptr, int(np.prod(lead, dtype=np.int64)), M, N, K, _ptr(A), 0 if one else M * N,
+                                                   _ptr(tau) if tau is not None else None, _ptr(Y), _ptr(X),
+                                                   _ptr(flags) if info is not None else None))
+    if info is not None:
+        info["singular"] = flags
     return X
 
 
