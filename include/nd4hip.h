@@ -824,6 +824,34 @@ int nd4hip_zgels_batched_dev  (nd4hip_handle* h, int64_t batch, int64_t M, int64
 int nd4hip_zgels_batched_host (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t K, const double* A, int64_t strideA,
                                const double* tau, const double* Y, double* X, int32_t* info);
 
+/* ---- complex bidiagonalisation and SVD: zbidiag_factor / zbidiag_apply_p / zsvd_decomp / zsvd_vals (csrc/zgebrd.hip) ----
+ * LAPACK's zgebrd (upper form) / zunmbr ('P') / zgesdd on row-major members, complex128 as interleaved (re, im) doubles on 16-byte
+ * boundaries, d, e and sv real, strides in complex elements. Shapes beyond 2048, and N > M for the first two, are refused before
+ * anything is written; an extent of 0 is an empty call.
+ *   zgebrd:   A = Q B P^H, B real upper bidiagonal with d [batch,N] and e [batch,N-1] (also on F's diagonal and superdiagonal).
+ *             Q = H_0 ... H_{N-1}, H_k = I - tauq_k v_k v_k^H, v_k = (0, .., 1 at k, F[k+1:, k]): zgeqrf's layout, so zunmqr(F, tauq) applies
+ *             Q. P = G_0 ... G_{N-2}, G_k = I - taup_k u_k u_k^H, u_k = (0, .., 1 at k+1, F[k, k+2:]); taup [batch,N] ends in 0. A is not
+ *             written; A -> 2^m A leaves tails, tauq and taup bit-identical and scales d and e exactly. NaN or Inf in A:
+ *             ND4HIP_ERR_NOCONV, 'zbidiag_factor(A): A contains NaN or Infinity.' Synchronises (one flag word).
+ *   zunmbr_p: Z [batch,N,K] <- P Z (adjoint = 1: P^H Z) in place; strideF = M*N and strideTau = N, or both 0: one (F, taup) for every
+ *             member. Only enqueues.
+ *   zgesdd:   the singular triplets i0 <= i < i1 of the descending spectrum of A [batch,M,N], any 1 <= M, N <= 2048, k = i1 - i0:
+ *             sv [batch,k] >= 0 and, with vectors = 1, U [batch,M,k] and V [batch,k,N] with A = U diag(sv) V (V is LAPACK's V^H); with
+ *             vectors = 0, U = V = NULL. NaN or Inf: ND4HIP_ERR_NOCONV, 'zsvd_decomp(A): A contains NaN or Infinity.' Synchronises.
+ * No sum depends on the run, the batch or a member's position. Profile ops "zgebrd_batched", "zunmbr_p_batched", "zgesdd_batched". */
+int nd4hip_zgebrd_batched_dev  (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* F, double* tauq, double* taup,
+                                double* d, double* e);
+int nd4hip_zgebrd_batched_host (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* F, double* tauq, double* taup,
+                                double* d, double* e);
+int nd4hip_zunmbr_p_batched_dev (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t K, int adjoint, const double* F, int64_t strideF,
+                                 const double* taup, int64_t strideTau, double* Z);
+int nd4hip_zunmbr_p_batched_host(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t K, int adjoint, const double* F, int64_t strideF,
+                                 const double* taup, int64_t strideTau, double* Z);
+int nd4hip_zgesdd_batched_dev  (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t i0, int64_t i1, int vectors, const double* A,
+                                double* U, double* sv, double* V);
+int nd4hip_zgesdd_batched_host (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t i0, int64_t i1, int vectors, const double* A,
+                                double* U, double* sv, double* V);
+
 /* ---- eigenpairs in a value interval: eigen_sym(S, interval=(lo, hi)), tridiag_eigen(d, e, interval) (csrc/syevx.hip) ----
  * dstevxv, dsyevxv and dsyevxv_tr are dstevx, dsyevx and dsyevx_tr with the subset of each member chosen by value: bounds [batch,2]
  * holds (lo, hi) per member and selects the eigenvalues lo < lambda <= hi, which is exactly the subset (i0_b, i1_b) =

@@ -206,6 +206,13 @@ SIGNATURES = {
     "nd4hip_zungqr_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
     "nd4hip_zgels_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_dp, c_i64, c_dp, c_dp, c_dp, ctypes.c_void_p]),
     "nd4hip_zgels_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_dp, c_i64, c_dp, c_dp, c_dp, ctypes.c_void_p]),
+    # complex bidiagonalisation, its P and the complex SVD (csrc/zgebrd.hip)
+    "nd4hip_zgebrd_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "nd4hip_zgebrd_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "nd4hip_zunmbr_p_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_dp, c_i64, c_dp, c_i64, c_dp]),
+    "nd4hip_zunmbr_p_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_dp, c_i64, c_dp, c_i64, c_dp]),
+    "nd4hip_zgesdd_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_dp, c_dp, c_dp, c_dp]),
+    "nd4hip_zgesdd_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_dp, c_dp, c_dp, c_dp]),
     "nd4hip_zpotrf_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp]),
     "nd4hip_zpotrs_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_i64, c_dp, c_dp]),
     "nd4hip_ztrsm_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_int, c_dp, c_i64, c_dp]),

@@ -1113,6 +1113,35 @@ extern "C" int nd4hip_zgels_batched_dev(nd4hip_handle* h, int64_t batch, int64_t
   return nd4_zgels_run(h, batch, M, N, K, A, strideA, tau, Y, X, info, 0, nullptr);
 }
 
+// ---- zbidiag_factor / zbidiag_apply_p / zsvd_decomp / zsvd_vals (zgebrd.hip). Real flops: 16 N^2 (M - N / 3) for the reduction,
+// 8 N K (2 N - N) for P Z; the SVD adds the real solver and the two back-transformations
+extern "C" int nd4hip_zgebrd_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* F, double* tauq, double* taup,
+                                         double* d, double* e) {
+  ND4_ARGS(nd4_args_zgebrd(batch, M, N, A, F, tauq, taup, d, e));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zgebrd_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "zgebrd_batched", batch * (16.0 * N * N * (M - N / 3.0)), 16.0 * batch * (double)(2 * M * N + 3 * N));
+  return nd4_zgebrd(h, batch, M, N, A, F, tauq, taup, d, e, "zbidiag_factor(A)");
+}
+extern "C" int nd4hip_zunmbr_p_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t K, int adjoint, const double* F,
+                                           int64_t strideF, const double* taup, int64_t strideTau, double* Z) {
+  ND4_ARGS(nd4_args_zunmbr_p(batch, M, N, K, adjoint, F, strideF, taup, strideTau, Z));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zunmbr_p_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "zunmbr_p_batched", batch * (8.0 * N * N * K), 16.0 * batch * (double)(N * N + 2 * N * K));
+  return nd4_zunmbr_p(h, batch, M, N, K, adjoint != 0, F, strideF, taup, strideTau, Z);
+}
+extern "C" int nd4hip_zgesdd_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t i0, int64_t i1, int vectors, const double* A,
+                                         double* U, double* sv, double* V) {
+  ND4_ARGS(nd4_args_zgesdd(batch, M, N, i0, i1, vectors, A, U, sv, V));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zgesdd_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  const double m = M > N ? M : N, n = M > N ? N : M, k = (double)(i1 - i0);
+  Nd4Prof prof(h, "zgesdd_batched", batch * (16.0 * n * n * (m - n / 3.0) + (vectors ? 4.0 * n * n * k + 8.0 * n * k * (2.0 * m - n) + 8.0 * n * n * k : 0.0)),
+               16.0 * batch * (m * n + (vectors ? (m + n) * k : 0.0)));
+  return nd4_zgesdd(h, batch, M, N, i0, i1, A, U, sv, V);
+}
+
 extern "C" int nd4hip_dsyevd_last_stages(nd4hip_handle* h, double* ms, int capacity) {
   ND4_CHECK_ARG(h != nullptr && (ms != nullptr || capacity <= 0), "nd4hip_dsyevd_last_stages: NULL argument");
   for (int i = 0; i < capacity && i < ND4HIP_SYEV_STAGES; ++i) ms[i] = h->syev_stage_ms[i];

@@ -488,6 +488,38 @@ inline int nd4_args_zgels(int64_t batch, int64_t M, int64_t N, int64_t K, const 
   ND4_CHECK_ARG(M < 0 || N < 0 || strideA == M * N || (tau && strideA == 0), "nd4hip_zgels_batched: strideA must be M*N, or 0 with a factorisation");
   return nd4_args_zqr("zgels_batched", batch, M, N, K, {A, Y, X});
 }
+// ---- complex bidiagonalisation and SVD (zgebrd.hip): the shape before anything is launched or written. zgebrd and zunmbr_p take
+// N <= M <= 2048; zgesdd any M, N <= 2048, the subset 0 <= i0 <= i1 <= min(M, N) and U, V only with vectors = 1
+inline int nd4_args_zgebrd(int64_t batch, int64_t M, int64_t N, const void* A, const void* F, const void* tauq, const void* taup, const void* d,
+                           const void* e) {
+  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_zgebrd_batched: negative extent");
+  ND4_CHECK_ARG(N <= M && M <= 2048, "nd4hip_zgebrd_batched: the shape must satisfy N <= M <= 2048");
+  if (batch == 0 || N == 0) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(A && F && tauq && taup && d && (e || N < 2), "nd4hip_zgebrd_batched: NULL pointer");
+  return ND4_ARGS_GO;
+}
+inline int nd4_args_zunmbr_p(int64_t batch, int64_t M, int64_t N, int64_t K, int adjoint, const void* F, int64_t strideF, const void* taup,
+                             int64_t strideTau, const void* Z) {
+  ND4_CHECK_ARG(adjoint == 0 || adjoint == 1, "nd4hip_zunmbr_p_batched: adjoint must be 0 or 1");
+  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0 && K >= 0, "nd4hip_zunmbr_p_batched: negative extent");
+  ND4_CHECK_ARG((strideF == 0 && strideTau == 0) || (strideF == M * N && strideTau == N),
+                "nd4hip_zunmbr_p_batched: the strides of F and taup must be M*N and N, or both 0");
+  ND4_CHECK_ARG(N <= M && M <= 2048, "nd4hip_zunmbr_p_batched: the shape must satisfy N <= M <= 2048");
+  ND4_CHECK_ARG(K <= ND4_ZLU_MAX_K, "nd4hip_zunmbr_p_batched: K exceeds 4 194 240 columns");
+  if (batch == 0 || N == 0 || K == 0) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(F && taup && Z, "nd4hip_zunmbr_p_batched: NULL pointer");
+  return ND4_ARGS_GO;
+}
+inline int nd4_args_zgesdd(int64_t batch, int64_t M, int64_t N, int64_t i0, int64_t i1, int vectors, const void* A, const void* U, const void* sv,
+                           const void* V) {
+  ND4_CHECK_ARG(vectors == 0 || vectors == 1, "nd4hip_zgesdd_batched: vectors must be 0 or 1");
+  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_zgesdd_batched: negative extent");
+  ND4_CHECK_ARG(M <= 2048 && N <= 2048, "nd4hip_zgesdd_batched: M <= 2048 and N <= 2048");
+  ND4_CHECK_ARG(0 <= i0 && i0 <= i1 && i1 <= (M < N ? M : N), "nd4hip_zgesdd_batched: subset must satisfy 0 <= i0 <= i1 <= min(M, N)");
+  if (batch == 0 || i0 == i1) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(A && sv && (vectors ? U && V : !U && !V), "nd4hip_zgesdd_batched: NULL pointer, or vectors without the flag");
+  return ND4_ARGS_GO;
+}
 inline int nd4_args_sygvd(int algo, int64_t batch, int64_t N, const void* A, const void* B, int64_t strideB, const void* lambda) {
   ND4_CHECK_ARG(algo == 0 || algo == 1, "nd4hip_dsygvd_batched: algo must be 0 (dc) or 1 (jacobi)");
   ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsygvd_batched: negative extent");

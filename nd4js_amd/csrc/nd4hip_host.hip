@@ -1434,3 +1434,39 @@ extern "C" int nd4hip_zgels_batched_host(nd4hip_handle* h, int64_t batch, int64_
   }
   return 0;
 }
+
+// zbidiag_factor / zbidiag_apply_p / zsvd_decomp / zsvd_vals (zgebrd.hip). e is empty for N = 1; U and V travel only with vectors = 1
+extern "C" int nd4hip_zgebrd_batched_host(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* F, double* tauq, double* taup,
+                                          double* d, double* e) {
+  ND4_ARGS(nd4_args_zgebrd(batch, M, N, A, F, tauq, taup, d, e));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zgebrd_batched: NULL handle");
+  std::vector<Operand> ops{in_op(A, M * N, M * N, 2 * D), out_op(F, M * N, 2 * D), out_op(tauq, N, 2 * D), out_op(taup, N, 2 * D), out_op(d, N)};
+  const int ie = N > 1 ? (int)ops.size() : -1;
+  if (N > 1) ops.push_back(out_op(e, N - 1));
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return nd4hip_zgebrd_batched_dev(hd, nb, M, N, P(p, 0), P(p, 1), P(p, 2), P(p, 3), P(p, 4), ie >= 0 ? P(p, ie) : nullptr);
+  };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_zunmbr_p_batched_host(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t K, int adjoint, const double* F,
+                                            int64_t strideF, const double* taup, int64_t strideTau, double* Z) {
+  ND4_ARGS(nd4_args_zunmbr_p(batch, M, N, K, adjoint, F, strideF, taup, strideTau, Z));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zunmbr_p_batched: NULL handle");
+  std::vector<Operand> ops{in_op(F, M * N, strideF, 2 * D), in_op(taup, N, strideTau, 2 * D), inout_op(Z, N * K, 2 * D)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return nd4hip_zunmbr_p_batched_dev(hd, nb, M, N, K, adjoint, P(p, 0), strideF, P(p, 1), strideTau, P(p, 2));
+  };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_zgesdd_batched_host(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t i0, int64_t i1, int vectors, const double* A,
+                                          double* U, double* sv, double* V) {
+  ND4_ARGS(nd4_args_zgesdd(batch, M, N, i0, i1, vectors, A, U, sv, V));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zgesdd_batched: NULL handle");
+  const int64_t k = i1 - i0;
+  std::vector<Operand> ops{in_op(A, M * N, M * N, 2 * D), out_op(sv, k)};
+  if (vectors) { ops.push_back(out_op(U, M * k, 2 * D)); ops.push_back(out_op(V, k * N, 2 * D)); }
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return nd4hip_zgesdd_batched_dev(hd, nb, M, N, i0, i1, vectors, P(p, 0), vectors ? P(p, 2) : nullptr, P(p, 1), vectors ? P(p, 3) : nullptr);
+  };
+  return run_host(h, batch, ops, fn);
+}

@@ -305,6 +305,22 @@ int64_t nd4_zgeqrf_chunk(int64_t batch, int64_t M, int64_t N, int64_t n, int64_t
 // zqr_lstsq's entry point with member0, shared by the _dev and _host forms (nd4hip_api.hip)
 int nd4_zgels_run(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t K, const double* A, int64_t strideA, const double* tau,
                   const double* Y, double* X, int32_t* info, int64_t member0, int64_t* first_bad);
+// complex bidiagonalisation, the application of its P and the complex SVD (zgebrd.hip): complex128 operands as
+// interleaved doubles, 16-byte aligned, d, e and sv real, strides in complex elements (0 = one for all). Arguments already checked,
+// batch >= 1, K >= 1; 1 <= N <= M <= 2048 for the first two, 1 <= M, N <= 2048 for nd4_zgesdd (0 <= i0 < i1 <= min(M, N); U = V = NULL:
+// the values alone). nd4_zgebrd and nd4_zgesdd synchronise (one flag word per pass: NaN or Inf is ND4HIP_ERR_NOCONV, '<what>: A contains
+// NaN or Infinity.'), nd4_zunmbr_p enqueues only. The four functions after them are the host-side arithmetic: tier (0: a member in LDS,
+// 1: two launches per column), the largest dynamic LDS request of the reduction in bytes, members per pass (extra complex elements
+// of workspace per member), and whether a tall m x n member is factorised by QR first.
+int nd4_zgebrd(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* F, double* tauq, double* taup, double* d, double* e,
+               const char* what);
+int nd4_zunmbr_p(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t K, bool adjoint, const double* F, int64_t sF, const double* taup,
+                 int64_t sT, double* Z);
+int nd4_zgesdd(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t i0, int64_t i1, const double* A, double* U, double* sv, double* V);
+int nd4_zgebrd_tier(int64_t M, int64_t N);
+size_t nd4_zgebrd_lds(int64_t M, int64_t N);
+int64_t nd4_zgebrd_chunk(int64_t batch, int64_t M, int64_t N, int64_t extra);
+bool nd4_zgesdd_qr_first(int64_t m, int64_t n);
 // generalised symmetric-definite eigenproblem (sygv.hip): arguments already checked, batch >= 1, 1 <= N; sB / sL 0 = one for all;
 // member0: index of the first member in the caller's batch (error text); nd4_sygvd synchronises
 int nd4_sygvd(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B, int64_t sB, double* lambda,

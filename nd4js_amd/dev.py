@@ -1313,6 +1313,70 @@ def zqr_lstsq(A, Y, info=None):
     return X
 
 
+def zbidiag_factor(A):
+    """device-resident la.zbidiag_factor: (F, tauq, taup, d, e) of the complex128 A, the same bits; A is not written. Synchronises (one
+    flag word)."""
+    from .la import _zqr_shape
+    what = "zbidiag_factor(A)"
+    A = _zlu_c128(A, "A", what, "bidiag_decomp")
+    M, N = _zqr_shape(tuple(A.shape), "A", what)
+    lead = tuple(A.shape[:-2])
+    F = torch.empty_like(A)
+    tauq = torch.empty(lead + (N,), dtype=torch.complex128, device=A.device)
+    taup = torch.empty(lead + (N,), dtype=torch.complex128, device=A.device)
+    d = torch.empty(lead + (N,), dtype=torch.float64, device=A.device)
+    e = torch.empty(lead + (max(N - 1, 0),), dtype=torch.float64, device=A.device)
+    if F.numel():
+        h = _h(A)
+        _lib.check(h.lib.nd4hip_zgebrd_batched_dev(h.ptr, _batch(lead), M, N, _p(A), _p(F), _p(tauq), _p(taup), _p(d), _p(e) if N > 1 else None))
+    return F, tauq, taup, d, e
+
+
+def zbidiag_apply_p(F, taup, Z, adjoint=False):
+    """device-resident la.zbidiag_apply_p: P Z (adjoint: P^H Z), the same bits; F and taup have Z's leading dimensions or are exactly one
+    member. Z is not written. Only enqueued."""
+    from .la import _zsvd_factored
+    what = "zbidiag_apply_p(F,taup,Z)"
+    F, taup = _zlu_c128(F, "F", what, "bidiag_decomp"), _zlu_c128(taup, "taup", what, "bidiag_decomp")
+    Z = _zlu_rhs(Z, what).clone()
+    M, N, K, lead, one = _zsvd_factored(tuple(F.shape), tuple(taup.shape), tuple(Z.shape), what)
+    if F.device != Z.device or taup.device != Z.device:
+        raise ValueError("%s: the operands must be on the same device." % what)
+    if Z.numel():
+        h = _h(Z)
+        _lib.check(h.lib.nd4hip_zunmbr_p_batched_dev(h.ptr, _batch(lead), M, N, K, 1 if adjoint else 0, _p(F), 0 if one else M * N, _p(taup),
+                                                     0 if one else N, _p(Z)))
+    return Z
+
+
+def _zsvd(A, subset, vectors):
+    from .la import _subset, _zsvd_shape
+    what = "zsvd_decomp(A)" if vectors else "zsvd_vals(A)"
+    A = _zlu_c128(A, "A", what, "svd_decomp")
+    M, N = _zsvd_shape(tuple(A.shape), what)
+    i0, i1 = _subset(subset, min(M, N), what) if subset is not None else (0, min(M, N))
+    k, lead = i1 - i0, tuple(A.shape[:-2])
+    sv = torch.empty(lead + (k,), dtype=torch.float64, device=A.device)
+    U = torch.empty(lead + (M, k), dtype=torch.complex128, device=A.device) if vectors else None
+    V = torch.empty(lead + (k, N), dtype=torch.complex128, device=A.device) if vectors else None
+    if A.numel() and k:
+        h = _h(A)
+        _lib.check(h.lib.nd4hip_zgesdd_batched_dev(h.ptr, _batch(lead), M, N, i0, i1, 1 if vectors else 0, _p(A), _p(U) if vectors else None,
+                                                   _p(sv), _p(V) if vectors else None))
+    return (U, sv, V) if vectors else sv
+
+
+def zsvd_decomp(A, subset=None):
+    """device-resident la.zsvd_decomp: (U [..., M, k], sv [..., k], V [..., k, N]) of the complex128 A, the same bits; A is not written.
+    Synchronises."""
+    return _zsvd(A, subset, True)
+
+
+def zsvd_vals(A, subset=None):
+    """device-resident la.zsvd_vals: sv [..., k] of the complex128 A, the same bits. Synchronises."""
+    return _zsvd(A, subset, False)
+
+
 def _stevx(d, e, subset, what, vectors, interval=None, info=None):
     from .la import _interval_what, _subset, _tridiag_args
     if interval is not None:

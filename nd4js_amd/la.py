@@ -24,6 +24,8 @@ JS wrapper nd4js_amd/js/index.js over the N-API shim; both call the same libnd4h
   zqr_factor(A), zqr_apply_q(F, tau, Z, adjoint), zqr_decomp(A), zqr_lstsq(A, Y, info)   complex128 A [..., M, N], N <= M, not in the reference
                                    -> nd4hip_zgeqrf_batched_host, nd4hip_zunmqr_batched_host, nd4hip_zungqr_batched_host,
                                       nd4hip_zgels_batched_host (csrc/zgeqrf.hip)
+  zbidiag_factor(A), zbidiag_apply_p(F, taup, Z, adjoint), zsvd_decomp(A, subset), zsvd_vals(A, subset)   complex128 A, not in the reference
+                                   -> nd4hip_zgebrd_batched_host, nd4hip_zunmbr_p_batched_host, nd4hip_zgesdd_batched_host (csrc/zgebrd.hip)
   zlu_decomp(A, info), zlu_solve(LU, P, Y), zsolve(A, Y)   general complex128 A, not in the reference
                                    -> nd4hip_zgetrf_batched_host, nd4hip_zgetrs_batched_host, nd4hip_zgesv_batched_host (csrc/zgetrf.hip)
   tridiag_eigen(d, e), tridiag_eigenvals(d, e), tridiag_count(d, e, x)   not in the reference   -> nd4hip_dstevx_batched_host, nd4hip_dstcnt_batched_host
@@ -1939,6 +1941,100 @@ def zqr_lstsq(A, Y, info=None, device=None):
     if info is not None:
         info["singular"] = flags
     return X
+
+
+def _zsvd_shape(shape, what):
+    """(M, N) of a complex member stack for zsvd_decomp / zsvd_vals, shared with dev.py"""
+    if len(shape) < 2:
+        raise ValueError("%s: A.ndim must be at least 2." % what)
+    M, N = int(shape[-2]), int(shape[-1])
+    if M > 2048 or N > 2048:
+        raise ValueError("%s: M <= 2048 and N <= 2048." % what)
+    return M, N
+
+
+def _zsvd_factored(sf, st, sz, what):
+    """the shapes of (F, taup) against Z [..., N, K]: (M, N, K, leading shape, one factorisation for all)"""
+    M, N = _zqr_shape(sf, "F", what)
+    if len(st) < 1 or int(st[-1]) != N or tuple(st[:-1]) != tuple(sf[:-2]):
+        raise ValueError("%s: F and taup don't match." % what)
+    if len(sz) < 2 or int(sz[-2]) != N:
+        raise ValueError("%s: F and Z don't match." % what)
+    lead, one = tuple(sz[:-2]), len(sf) == 2
+    if not one and tuple(sf[:-2]) != lead:
+        raise ValueError("%s: F must have Z's leading dimensions or be one member." % what)
+    return M, N, int(sz[-1]), lead, one
+
+
+def zbidiag_factor(A, device=None):
+    """(F complex128 [..., M, N], tauq, taup complex128 [..., N], d float64 [..., N], e float64 [..., N-1]) of the complex128 A,
+    N <= M <= 2048 (LAPACK's zgebrd, upper form, on row-major members): A = Q B P^H with B real upper bidiagonal. Q = H_0 ... H_{N-1},
+    H_k = I - tauq_k v_k v_k^H, v_k = (0, .., 1 at k, F[k+1:, k]): zqr_apply_q(F, tauq, Z) applies Q. P = G_0 ... G_{N-2},
+    G_k = I - taup_k u_k u_k^H, u_k = (0, .., 1 at k+1, F[k, k+2:]): zbidiag_apply_p(F, taup, Z); taup ends in 0. A -> 2^m A leaves tails,
+    tauq and taup bit-identical and scales d and e exactly (csrc/zgebrd.hip). NaN or Inf in A raises Nd4HipError. A float64 A raises
+    TypeError: it goes to bidiag_decomp."""
+    what = "zbidiag_factor(A)"
+    A = np.asarray(A)
+    _zlu_dtype("A", what, A.dtype.kind == "c", A.dtype == np.complex128, A.dtype, "bidiag_decomp")
+    A = np.ascontiguousarray(A)
+    M, N = _zqr_shape(A.shape, "A", what)
+    lead = A.shape[:-2]
+    F = np.empty(A.shape, dtype=np.complex128)
+    tauq, taup = np.empty(lead + (N,), dtype=np.complex128), np.empty(lead + (N,), dtype=np.complex128)
+    d, e = np.empty(lead + (N,), dtype=np.float64), np.empty(lead + (max(N - 1, 0),), dtype=np.float64)
+    if F.size:
+        h = _lib.handle(device)
+        _lib.check(h.lib.nd4hip_zgebrd_batched_host(h.ptr, int(np.prod(lead, dtype=np.int64)), M, N, _ptr(A), _ptr(F), _ptr(tauq), _ptr(taup),
+                                                    _ptr(d), _ptr(e) if N > 1 else None))
+    return F, tauq, taup, d, e
+
+
+def zbidiag_apply_p(F, taup, Z, adjoint=False, device=None):
+    """P Z (adjoint: P^H Z) complex128 [..., N, K] for the (F, taup) of zbidiag_factor and Z complex128 or float64 (promoted). F and taup
+    have Z's leading dimensions or are exactly one member [M, N], [N]. Z is not written."""
+    what = "zbidiag_apply_p(F,taup,Z)"
+    F = np.asarray(F)
+    _zlu_dtype("F", what, F.dtype.kind == "c", F.dtype == np.complex128, F.dtype, "bidiag_decomp")
+    F, taup = np.ascontiguousarray(F), _zqr_tau(taup, what)
+    Z = np.array(_zqr_rhs(Z, what))
+    M, N, K, lead, one = _zsvd_factored(F.shape, taup.shape, Z.shape, what)
+    if Z.size:
+        h = _lib.handle(device)
+        _lib.check(h.lib.nd4hip_zunmbr_p_batched_host(h.ptr, int(np.prod(lead, dtype=np.int64)), M, N, K, 1 if adjoint else 0, _ptr(F),
+                                                      0 if one else M * N, _ptr(taup), 0 if one else N, _ptr(Z)))
+    return Z
+
+
+def _zsvd(A, subset, vectors, device):
+    what = "zsvd_decomp(A)" if vectors else "zsvd_vals(A)"
+    A = np.asarray(A)
+    _zlu_dtype("A", what, A.dtype.kind == "c", A.dtype == np.complex128, A.dtype, "svd_decomp")
+    A = np.ascontiguousarray(A)
+    M, N = _zsvd_shape(A.shape, what)
+    i0, i1 = _subset(subset, min(M, N), what) if subset is not None else (0, min(M, N))
+    k, lead = i1 - i0, A.shape[:-2]
+    sv = np.empty(lead + (k,), dtype=np.float64)
+    U = np.empty(lead + (M, k), dtype=np.complex128) if vectors else None
+    V = np.empty(lead + (k, N), dtype=np.complex128) if vectors else None
+    if A.size and k:
+        h = _lib.handle(device)
+        _lib.check(h.lib.nd4hip_zgesdd_batched_host(h.ptr, int(np.prod(lead, dtype=np.int64)), M, N, i0, i1, 1 if vectors else 0, _ptr(A),
+                                                    _ptr(U) if vectors else None, _ptr(sv), _ptr(V) if vectors else None))
+    return (U, sv, V) if vectors else sv
+
+
+def zsvd_decomp(A, subset=None, device=None):
+    """(U complex128 [..., M, k], sv float64 [..., k], V complex128 [..., k, N]) of the complex128 A, 1 <= M, N <= 2048, with
+    A = U diag(sv) V (svd_decomp's convention: V is LAPACK's V^H), sv descending and >= 0. subset=(i0, i1) selects the triplets
+    i0 <= i < i1 of the descending spectrum, k = i1 - i0; else k = min(M, N). A reduces to a real bidiagonal matrix (zbidiag_factor, after
+    a QR factorisation when 3 M >= 5 N), which the real solvers of svd_decomp(algo='dc') and of its subset route take (csrc/zgebrd.hip).
+    NaN or Inf in A raises Nd4HipError. A float64 A raises TypeError: it goes to svd_decomp."""
+    return _zsvd(A, subset, True, device)
+
+
+def zsvd_vals(A, subset=None, device=None):
+    """sv float64 [..., k] of zsvd_decomp(A, subset) without the vectors, by bisection on the bidiagonal matrix."""
+    return _zsvd(A, subset, False, device)
 
 
 def _tridiag_args(d, e, what, ndim, shape):
