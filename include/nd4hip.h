@@ -852,6 +852,36 @@ int nd4hip_zgesdd_batched_dev  (nd4hip_handle* h, int64_t batch, int64_t M, int6
 int nd4hip_zgesdd_batched_host (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, int64_t i0, int64_t i1, int vectors, const double* A,
                                 double* U, double* sv, double* V);
 
+/* ---- general complex eigenproblem: zhess_factor / zhess_apply_q / zschur_qr / zschur_decomp / zschur_eigen / zeigen / zeigenvals
+ * (csrc/zgehrd.hip, csrc/zhseqr.hip) ----
+ * LAPACK's zgehrd / zunmhr / zlahqr / zgees / ztrevc / zgeev (without balancing) on row-major members, complex128 as interleaved
+ * (re, im) doubles on 16-byte boundaries. N <= 2048 for the first two, N <= 1024 for the rest; larger shapes are refused before
+ * anything is written; an extent of 0 is an empty call.
+ *   zgehrd: A = Q H Q^H, H upper Hessenberg with an exactly real subdiagonal, on and above the subdiagonal of F. Q = H_0 ... H_{N-2},
+ *           H_k = I - tau_k v_k v_k^H, v_k = (0, .., 1 at k+1, F[k+2:, k]); tau [batch,N-1] (the last reflector has an empty tail and
+ *           makes h_{N-1,N-2} real). A -> 2^m A leaves tails and tau bit-identical and scales H exactly.
+ *   zunmhr: Z [batch,N,K] <- Q Z (adjoint = 1: Q^H Z) in place. Only enqueues.
+ *   zhseqr: (Q, T) with Q T Q^H = Q0 H Q0^H from an upper Hessenberg H (what lies below its subdiagonal is not read), T upper
+ *           triangular with exact zeros below the diagonal; want_t = 0: Q0 = Q = NULL and only the diagonal of T is meaningful.
+ *   zgees:  A = Q T Q^H.   ztrevc: lam [batch,N] = diag(T) and the eigenvectors V [batch,N,N] of Q T Q^H as columns of unit 2-norm.
+ *   zgeev:  lam and V of A, nothing sorted; V = NULL: the values alone (Q is never formed).
+ * NaN or Inf in the input: ND4HIP_ERR_NOCONV, '<function>(..): <operand> contains NaN or Infinity. (matrix b)', b the lowest such
+ * member; a member that has not converged after 30 max(10, N) sweeps: ND4HIP_ERR_NOCONV, '<function>(..): no convergence (matrix b)'.
+ * All but zunmhr synchronise (one read-back of the flag words per pass). No sum depends on the run, the batch or a member's position.
+ * Profile ops "zgehrd_batched", "zunmhr_batched", "zhseqr_batched", "zgees_batched", "ztrevc_batched", "zgeev_batched". */
+int nd4hip_zgehrd_batched_dev  (nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* F, double* tau);
+int nd4hip_zgehrd_batched_host (nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* F, double* tau);
+int nd4hip_zunmhr_batched_dev  (nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, int adjoint, const double* F, const double* tau, double* Z);
+int nd4hip_zunmhr_batched_host (nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, int adjoint, const double* F, const double* tau, double* Z);
+int nd4hip_zhseqr_batched_dev  (nd4hip_handle* h, int64_t batch, int64_t N, int want_t, const double* Q0, const double* H, double* Q, double* T);
+int nd4hip_zhseqr_batched_host (nd4hip_handle* h, int64_t batch, int64_t N, int want_t, const double* Q0, const double* H, double* Q, double* T);
+int nd4hip_zgees_batched_dev   (nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* Q, double* T);
+int nd4hip_zgees_batched_host  (nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* Q, double* T);
+int nd4hip_ztrevc_batched_dev  (nd4hip_handle* h, int64_t batch, int64_t N, const double* Q, const double* T, double* lam, double* V);
+int nd4hip_ztrevc_batched_host (nd4hip_handle* h, int64_t batch, int64_t N, const double* Q, const double* T, double* lam, double* V);
+int nd4hip_zgeev_batched_dev   (nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* lam, double* V);
+int nd4hip_zgeev_batched_host  (nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* lam, double* V);
+
 /* ---- eigenpairs in a value interval: eigen_sym(S, interval=(lo, hi)), tridiag_eigen(d, e, interval) (csrc/syevx.hip) ----
  * dstevxv, dsyevxv and dsyevxv_tr are dstevx, dsyevx and dsyevx_tr with the subset of each member chosen by value: bounds [batch,2]
  * holds (lo, hi) per member and selects the eigenvalues lo < lambda <= hi, which is exactly the subset (i0_b, i1_b) =

@@ -213,6 +213,19 @@ SIGNATURES = {
     "nd4hip_zunmbr_p_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_dp, c_i64, c_dp, c_i64, c_dp]),
     "nd4hip_zgesdd_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_dp, c_dp, c_dp, c_dp]),
     "nd4hip_zgesdd_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_dp, c_dp, c_dp, c_dp]),
+    # complex Hessenberg reduction, Schur form and eigenpairs (csrc/zgehrd.hip, csrc/zhseqr.hip)
+    "nd4hip_zgehrd_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_zunmhr_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_int, c_dp, c_dp, c_dp]),
+    "nd4hip_zhseqr_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_int, c_dp, c_dp, c_dp, c_dp]),
+    "nd4hip_zgees_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_ztrevc_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp]),
+    "nd4hip_zgeev_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_zgehrd_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_zunmhr_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_int, c_dp, c_dp, c_dp]),
+    "nd4hip_zhseqr_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_int, c_dp, c_dp, c_dp, c_dp]),
+    "nd4hip_zgees_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    "nd4hip_ztrevc_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp]),
+    "nd4hip_zgeev_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp]),
     "nd4hip_zpotrf_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp]),
     "nd4hip_zpotrs_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_i64, c_dp, c_dp]),
     "nd4hip_ztrsm_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_int, c_dp, c_i64, c_dp]),

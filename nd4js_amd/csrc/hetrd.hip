@@ -544,6 +544,9 @@ int nd4_zunmtr(nd4hip_handle* h, int64_t batch, int64_t N64, int64_t K64, bool a
   return 0;
 }
 
+// complex elements of workspace per member that nd4_zunmtr allocates for Z [N, K] (its callers size their passes by it)
+int64_t nd4_zunmtr_ws_elems(int64_t N, int64_t K) { return nd4_hetrd_tier(N) == 0 ? 0 : 2 * N * HET_WY + 2 * (int64_t)HET_WY * HET_WY + 2 * HET_WY * K; }
+
 // herm_tridiag_factor on device pointers: arguments already checked, batch in 1 .. 32768, 1 <= N <= 2048. Synchronises (the flag word).
 int nd4_hetrd_run(nd4hip_handle* h, int64_t batch, int64_t N, const double* H, double* F, double* tau, double* d, double* e) {
   Nd4WsScope scope(h);

@@ -1142,6 +1142,53 @@ extern "C" int nd4hip_zgesdd_batched_dev(nd4hip_handle* h, int64_t batch, int64_
   return nd4_zgesdd(h, batch, M, N, i0, i1, A, U, sv, V);
 }
 
+// ---- zhess_factor / zhess_apply_q / zschur_qr / zschur_decomp / zschur_eigen / zeigen / zeigenvals (zgehrd.hip, zhseqr.hip).
+// Real flops: 40 N^3 / 3 for the reduction, 16 N^2 K for Q Z, about 100 N^3 for the iteration with Q, 8 N^3 / 3 + 8 N^3 for the vectors
+extern "C" int nd4hip_zgehrd_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* F, double* tau) {
+  ND4_ARGS(nd4_args_zgehrd(batch, N, A, F, tau));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zgehrd_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "zgehrd_batched", batch * (40.0 / 3.0 * N * N * N), 16.0 * batch * (double)(2 * N * N + N));
+  return nd4_zgehrd_run(h, batch, N, A, F, tau, "zhess_factor(A): A", 0, nullptr);
+}
+extern "C" int nd4hip_zunmhr_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, int adjoint, const double* F, const double* tau,
+                                         double* Z) {
+  ND4_ARGS(nd4_args_zunmhr(batch, N, K, adjoint, F, tau, Z));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zunmhr_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "zunmhr_batched", batch * (16.0 * N * N * K), 16.0 * batch * (double)(N * N + 2 * N * K));
+  return nd4_zunmhr(h, batch, N, K, adjoint != 0, F, tau, Z);
+}
+extern "C" int nd4hip_zhseqr_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, int want_t, const double* Q0, const double* H, double* Q,
+                                         double* T) {
+  ND4_ARGS(nd4_args_zhseqr(batch, N, want_t, Q0, H, Q, T));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zhseqr_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "zhseqr_batched", batch * ((want_t ? 100.0 : 30.0) * N * N * N), 16.0 * batch * (double)((want_t ? 4 : 2) * N * N));
+  return nd4_zhseqr_run(h, batch, N, Q0, H, Q, T, want_t != 0, "zschur_qr(Q0,H): H", 0, nullptr);
+}
+extern "C" int nd4hip_zgees_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* Q, double* T) {
+  ND4_ARGS(nd4_args_zgees(batch, N, A, Q, T));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zgees_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "zgees_batched", batch * (130.0 * N * N * N), 16.0 * batch * (double)(3 * N * N));
+  return nd4_zgees_run(h, batch, N, A, Q, T, "zschur_decomp(A): A", 0, nullptr);
+}
+extern "C" int nd4hip_ztrevc_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* Q, const double* T, double* lam, double* V) {
+  ND4_ARGS(nd4_args_ztrevc(batch, N, Q, T, lam, V));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_ztrevc_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "ztrevc_batched", batch * (32.0 / 3.0 * N * N * N), 16.0 * batch * (double)(3 * N * N + N));
+  return nd4_ztrevc_run(h, batch, N, Q, T, lam, V, "zschur_eigen(Q,T): Q or T", 0, nullptr);
+}
+extern "C" int nd4hip_zgeev_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* lam, double* V) {
+  ND4_ARGS(nd4_args_zgeev(batch, N, A, lam, V));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zgeev_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "zgeev_batched", batch * ((V ? 141.0 : 43.0) * N * N * N), 16.0 * batch * (double)((V ? 2 : 1) * N * N + N));
+  return nd4_zgeev_run(h, batch, N, A, lam, V, V ? "zeigen(A): A" : "zeigenvals(A): A", 0, nullptr);
+}
+
 extern "C" int nd4hip_dsyevd_last_stages(nd4hip_handle* h, double* ms, int capacity) {
   ND4_CHECK_ARG(h != nullptr && (ms != nullptr || capacity <= 0), "nd4hip_dsyevd_last_stages: NULL argument");
   for (int i = 0; i < capacity && i < ND4HIP_SYEV_STAGES; ++i) ms[i] = h->syev_stage_ms[i];

@@ -520,6 +520,54 @@ inline int nd4_args_zgesdd(int64_t batch, int64_t M, int64_t N, int64_t i0, int6
   ND4_CHECK_ARG(A && sv && (vectors ? U && V : !U && !V), "nd4hip_zgesdd_batched: NULL pointer, or vectors without the flag");
   return ND4_ARGS_GO;
 }
+// ---- complex Hessenberg reduction, Schur form and eigenpairs (zgehrd.hip, zhseqr.hip): the shape before anything is launched or written.
+// zgehrd and zunmhr take N <= 2048, the rest N <= 1024; zhseqr's Q0 and Q only with want_t = 1, zgeev's V may be NULL
+inline int nd4_args_zgehrd(int64_t batch, int64_t N, const void* A, const void* F, const void* tau) {
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_zgehrd_batched: negative extent");
+  ND4_CHECK_ARG(N <= 2048, "nd4hip_zgehrd_batched: N <= 2048");
+  if (batch == 0 || N == 0) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(A && F && (tau || N < 2), "nd4hip_zgehrd_batched: NULL pointer");
+  return ND4_ARGS_GO;
+}
+inline int nd4_args_zunmhr(int64_t batch, int64_t N, int64_t K, int adjoint, const void* F, const void* tau, const void* Z) {
+  ND4_CHECK_ARG(adjoint == 0 || adjoint == 1, "nd4hip_zunmhr_batched: adjoint must be 0 or 1");
+  ND4_CHECK_ARG(batch >= 0 && N >= 0 && K >= 0, "nd4hip_zunmhr_batched: negative extent");
+  ND4_CHECK_ARG(N <= 2048, "nd4hip_zunmhr_batched: N <= 2048");
+  ND4_CHECK_ARG(K <= ND4_ZLU_MAX_K, "nd4hip_zunmhr_batched: K exceeds 4 194 240 columns");
+  if (batch == 0 || N == 0 || K == 0) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(F && (tau || N < 2) && Z, "nd4hip_zunmhr_batched: NULL pointer");
+  return ND4_ARGS_GO;
+}
+inline int nd4_args_zhseqr(int64_t batch, int64_t N, int want_t, const void* Q0, const void* H, const void* Q, const void* T) {
+  ND4_CHECK_ARG(want_t == 0 || want_t == 1, "nd4hip_zhseqr_batched: want_t must be 0 or 1");
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_zhseqr_batched: negative extent");
+  ND4_CHECK_ARG(N <= 1024, "nd4hip_zhseqr_batched: N <= 1024");
+  if (batch == 0 || N == 0) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(H && T && (want_t ? Q0 && Q : !Q0 && !Q), "nd4hip_zhseqr_batched: NULL pointer, or Q without want_t");
+  return ND4_ARGS_GO;
+}
+inline int nd4_args_zgees(int64_t batch, int64_t N, const void* A, const void* Q, const void* T) {
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_zgees_batched: negative extent");
+  ND4_CHECK_ARG(N <= 1024, "nd4hip_zgees_batched: N <= 1024");
+  if (batch == 0 || N == 0) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(A && Q && T, "nd4hip_zgees_batched: NULL pointer");
+  return ND4_ARGS_GO;
+}
+inline int nd4_args_ztrevc(int64_t batch, int64_t N, const void* Q, const void* T, const void* lam, const void* V) {
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_ztrevc_batched: negative extent");
+  ND4_CHECK_ARG(N <= 1024, "nd4hip_ztrevc_batched: N <= 1024");
+  if (batch == 0 || N == 0) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(Q && T && lam && V, "nd4hip_ztrevc_batched: NULL pointer");
+  return ND4_ARGS_GO;
+}
+inline int nd4_args_zgeev(int64_t batch, int64_t N, const void* A, const void* lam, const void* V) {
+  (void)V;
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_zgeev_batched: negative extent");
+  ND4_CHECK_ARG(N <= 1024, "nd4hip_zgeev_batched: N <= 1024");
+  if (batch == 0 || N == 0) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(A && lam, "nd4hip_zgeev_batched: NULL pointer");
+  return ND4_ARGS_GO;
+}
 inline int nd4_args_sygvd(int algo, int64_t batch, int64_t N, const void* A, const void* B, int64_t strideB, const void* lambda) {
   ND4_CHECK_ARG(algo == 0 || algo == 1, "nd4hip_dsygvd_batched: algo must be 0 (dc) or 1 (jacobi)");
   ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_dsygvd_batched: negative extent");

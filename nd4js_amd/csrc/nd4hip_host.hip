@@ -1470,3 +1470,73 @@ extern "C" int nd4hip_zgesdd_batched_host(nd4hip_handle* h, int64_t batch, int64
   };
   return run_host(h, batch, ops, fn);
 }
+
+// zhess_factor / zhess_apply_q / zschur_qr / zschur_decomp / zschur_eigen / zeigen / zeigenvals (zgehrd.hip, zhseqr.hip). tau is empty for N = 1;
+// Q0 and Q travel only with want_t = 1, V only when it is given. A flagged member is counted in the caller's batch
+extern "C" int nd4hip_zgehrd_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* F, double* tau) {
+  ND4_ARGS(nd4_args_zgehrd(batch, N, A, F, tau));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zgehrd_batched: NULL handle");
+  std::vector<Operand> ops{in_op(A, N * N, N * N, 2 * D), out_op(F, N * N, 2 * D)};
+  if (N > 1) ops.push_back(out_op(tau, N - 1, 2 * D));
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    Nd4DeviceGuard guard(hd);
+    return nd4_zgehrd_run(hd, nb, N, P(p, 0), P(p, 1), N > 1 ? P(p, 2) : nullptr, "zhess_factor(A): A", g_chunk_first, nullptr);
+  };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_zunmhr_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, int adjoint, const double* F, const double* tau,
+                                          double* Z) {
+  ND4_ARGS(nd4_args_zunmhr(batch, N, K, adjoint, F, tau, Z));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zunmhr_batched: NULL handle");
+  std::vector<Operand> ops{in_op(F, N * N, N * N, 2 * D), inout_op(Z, N * K, 2 * D)};
+  if (N > 1) ops.push_back(in_op(tau, N - 1, N - 1, 2 * D));
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    return nd4hip_zunmhr_batched_dev(hd, nb, N, K, adjoint, P(p, 0), N > 1 ? P(p, 2) : nullptr, P(p, 1));
+  };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_zhseqr_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int want_t, const double* Q0, const double* H, double* Q,
+                                          double* T) {
+  ND4_ARGS(nd4_args_zhseqr(batch, N, want_t, Q0, H, Q, T));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zhseqr_batched: NULL handle");
+  std::vector<Operand> ops{in_op(H, N * N, N * N, 2 * D), out_op(T, N * N, 2 * D)};
+  if (want_t) { ops.push_back(in_op(Q0, N * N, N * N, 2 * D)); ops.push_back(out_op(Q, N * N, 2 * D)); }
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    Nd4DeviceGuard guard(hd);
+    return nd4_zhseqr_run(hd, nb, N, want_t ? P(p, 2) : nullptr, P(p, 0), want_t ? P(p, 3) : nullptr, P(p, 1), want_t != 0, "zschur_qr(Q0,H): H",
+                          g_chunk_first, nullptr);
+  };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_zgees_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* Q, double* T) {
+  ND4_ARGS(nd4_args_zgees(batch, N, A, Q, T));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zgees_batched: NULL handle");
+  std::vector<Operand> ops{in_op(A, N * N, N * N, 2 * D), out_op(Q, N * N, 2 * D), out_op(T, N * N, 2 * D)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    Nd4DeviceGuard guard(hd);
+    return nd4_zgees_run(hd, nb, N, P(p, 0), P(p, 1), P(p, 2), "zschur_decomp(A): A", g_chunk_first, nullptr);
+  };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_ztrevc_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, const double* Q, const double* T, double* lam, double* V) {
+  ND4_ARGS(nd4_args_ztrevc(batch, N, Q, T, lam, V));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_ztrevc_batched: NULL handle");
+  std::vector<Operand> ops{in_op(Q, N * N, N * N, 2 * D), in_op(T, N * N, N * N, 2 * D), out_op(lam, N, 2 * D), out_op(V, N * N, 2 * D)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    Nd4DeviceGuard guard(hd);
+    return nd4_ztrevc_run(hd, nb, N, P(p, 0), P(p, 1), P(p, 2), P(p, 3), "zschur_eigen(Q,T): Q or T", g_chunk_first, nullptr);
+  };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_zgeev_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* lam, double* V) {
+  ND4_ARGS(nd4_args_zgeev(batch, N, A, lam, V));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_zgeev_batched: NULL handle");
+  std::vector<Operand> ops{in_op(A, N * N, N * N, 2 * D), out_op(lam, N, 2 * D)};
+  if (V) ops.push_back(out_op(V, N * N, 2 * D));
+  const bool vec = V != nullptr;
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    Nd4DeviceGuard guard(hd);
+    return nd4_zgeev_run(hd, nb, N, P(p, 0), P(p, 1), vec ? P(p, 2) : nullptr, vec ? "zeigen(A): A" : "zeigenvals(A): A", g_chunk_first, nullptr);
+  };
+  return run_host(h, batch, ops, fn);
+}

@@ -321,6 +321,36 @@ int nd4_zgebrd_tier(int64_t M, int64_t N);
 size_t nd4_zgebrd_lds(int64_t M, int64_t N);
 int64_t nd4_zgebrd_chunk(int64_t batch, int64_t M, int64_t N, int64_t extra);
 bool nd4_zgesdd_qr_first(int64_t m, int64_t n);
+// complex Hessenberg reduction, Schur form and eigenpairs (zgehrd.hip, zhseqr.hip): complex128 operands as interleaved
+// doubles, 16-byte aligned; tau [batch, N-1] (hetrd.hip's layout: nd4_zunmtr applies Q). Arguments already checked, batch >= 1, K >= 1;
+// 1 <= N <= 2048 for the reduction and its Q, 1 <= N <= 1024 for the rest. The _run drivers synchronise once per pass (the flag words)
+// and answer ND4HIP_ERR_NOCONV with '<what> contains NaN or Infinity. (matrix b)' or '<fn>: no convergence (matrix b)', what =
+// "<fn>(..): <operand>", b the lowest flagged member counted from member0 (also in *first_bad, may be NULL); nd4_zunmhr enqueues only.
+// nd4_zhseqr_run: want_t = false leaves Q0 and Q alone (both may be NULL) and only T's diagonal is meaningful; nd4_zgeev_run: V = NULL:
+// the values alone. The functions after them are the host-side arithmetic: tier of the reduction (0: a member in LDS, 1: one launch per
+// column), its largest dynamic LDS request in bytes, complex elements of its workspace per member, members per pass (extra complex
+// elements of workspace per member); tier of the iteration (0: H in LDS, 1: H in global memory), rows of its staging tile, its LDS bytes.
+int nd4_zgehrd_run(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* F, double* tau, const char* what, int64_t member0,
+                   int64_t* first_bad);
+int nd4_zunmhr(nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, bool adjoint, const double* F, const double* tau, double* Z);
+int nd4_zhseqr_run(nd4hip_handle* h, int64_t batch, int64_t N, const double* Q0, const double* H, double* Q, double* T, bool want_t,
+                   const char* what, int64_t member0, int64_t* first_bad);
+int nd4_zgees_run(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* Q, double* T, const char* what, int64_t member0,
+                  int64_t* first_bad);
+int nd4_ztrevc_run(nd4hip_handle* h, int64_t batch, int64_t N, const double* Q, const double* T, double* lam, double* V, const char* what,
+                   int64_t member0, int64_t* first_bad);
+int nd4_zgeev_run(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* lam, double* V, const char* what, int64_t member0,
+                  int64_t* first_bad);
+int nd4_zgehrd_tier(int64_t N);
+size_t nd4_zgehrd_lds(int64_t N);
+int64_t nd4_zgehrd_ws_elems(int64_t N);
+int64_t nd4_zgehrd_chunk(int64_t batch, int64_t N, int64_t extra);
+int64_t nd4_zeig_chunk(int64_t batch, int64_t per);
+int64_t nd4_zunmtr_ws_elems(int64_t N, int64_t K);   // hetrd.hip
+int nd4_ztrevc_tier(int64_t N);                      // 0: one kernel (N <= 64), 1: blocks of 64
+int nd4_zhseqr_tier(int64_t N);
+int nd4_zhseqr_tile_rows(int64_t N);
+size_t nd4_zhseqr_lds(int64_t N);
 // generalised symmetric-definite eigenproblem (sygv.hip): arguments already checked, batch >= 1, 1 <= N; sB / sL 0 = one for all;
 // member0: index of the first member in the caller's batch (error text); nd4_sygvd synchronises
 int nd4_sygvd(nd4hip_handle* h, int algo, int64_t batch, int64_t N, const double* A, const double* B, int64_t sB, double* lambda,

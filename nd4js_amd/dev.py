@@ -1377,6 +1377,110 @@ def zsvd_vals(A, subset=None):
     return _zsvd(A, subset, False)
 
 
+def _zeig_in(A, name, what, real_goes_to, nmax):
+    from .la import _zeig_square
+    A = _zlu_c128(A, name, what, real_goes_to)
+    return A, _zeig_square(tuple(A.shape), name, what, nmax)
+
+
+def zhess_factor(A):
+    """device-resident la.zhess_factor: (F, tau) of the complex128 A, the same bits; A is not written. Synchronises (one flag word)."""
+    from .la import _zeig_check
+    A, N = _zeig_in(A, "A", "zhess_factor(A)", "hessenberg_decomp", 2048)
+    F = torch.empty_like(A)
+    tau = torch.empty(tuple(A.shape[:-2]) + (max(N - 1, 0),), dtype=torch.complex128, device=A.device)
+    if F.numel():
+        h = _h(A)
+        _zeig_check(h.lib.nd4hip_zgehrd_batched_dev(h.ptr, _batch(tuple(A.shape[:-2])), N, _p(A), _p(F), _p(tau) if N > 1 else None))
+    return F, tau
+
+
+def zhess_apply_q(F, tau, Z, adjoint=False):
+    """device-resident la.zhess_apply_q: Q Z (adjoint: Q^H Z), the same bits. Z is not written. Only enqueued."""
+    from .la import _zhess_factored
+    what = "zhess_apply_q(F,tau,Z)"
+    F, tau = _zlu_c128(F, "F", what, "hessenberg_decomp"), _zlu_c128(tau, "tau", what, "hessenberg_decomp")
+    Z = _zlu_rhs(Z, what).clone()
+    N, K, lead = _zhess_factored(tuple(F.shape), tuple(tau.shape), tuple(Z.shape), what)
+    if F.device != Z.device or tau.device != Z.device:
+        raise ValueError("%s: the operands must be on the same device." % what)
+    if Z.numel():
+        h = _h(Z)
+        _lib.check(h.lib.nd4hip_zunmhr_batched_dev(h.ptr, _batch(lead), N, K, 1 if adjoint else 0, _p(F), _p(tau) if N > 1 else None, _p(Z)))
+    return Z
+
+
+def zhess_decomp(A):
+    """device-resident la.zhess_decomp: (Q, H), the same bits."""
+    F, tau = zhess_factor(A)
+    N = F.shape[-1]
+    Q = zhess_apply_q(F, tau, torch.eye(N, dtype=torch.complex128, device=F.device).expand(F.shape).contiguous())
+    return Q, torch.triu(F, -1)
+
+
+def zschur_qr(Q0, H):
+    """device-resident la.zschur_qr: (Q, T), the same bits; Q0 and H are not written. Synchronises."""
+    from .la import _zeig_check
+    what = "zschur_qr(Q0,H)"
+    H, N = _zeig_in(H, "H", what, "schur_decomp", 1024)
+    Q0, _ = _zeig_in(Q0, "Q0", what, "schur_decomp", 1024)
+    if Q0.shape != H.shape or Q0.device != H.device:
+        raise ValueError("%s: Q0 and H don't match." % what)
+    Q, T = torch.empty_like(H), torch.empty_like(H)
+    if H.numel():
+        h = _h(H)
+        _zeig_check(h.lib.nd4hip_zhseqr_batched_dev(h.ptr, _batch(tuple(H.shape[:-2])), N, 1, _p(Q0), _p(H), _p(Q), _p(T)))
+    return Q, T
+
+
+def zschur_decomp(A):
+    """device-resident la.zschur_decomp: (Q, T), the same bits; A is not written. Synchronises."""
+    from .la import _zeig_check
+    A, N = _zeig_in(A, "A", "zschur_decomp(A)", "schur_decomp", 1024)
+    Q, T = torch.empty_like(A), torch.empty_like(A)
+    if A.numel():
+        h = _h(A)
+        _zeig_check(h.lib.nd4hip_zgees_batched_dev(h.ptr, _batch(tuple(A.shape[:-2])), N, _p(A), _p(Q), _p(T)))
+    return Q, T
+
+
+def zschur_eigen(Q, T):
+    """device-resident la.zschur_eigen: (lam, V), the same bits. Synchronises."""
+    from .la import _zeig_check
+    what = "zschur_eigen(Q,T)"
+    T, N = _zeig_in(T, "T", what, "schur_eigen", 1024)
+    Q, _ = _zeig_in(Q, "Q", what, "schur_eigen", 1024)
+    if Q.shape != T.shape or Q.device != T.device:
+        raise ValueError("%s: Q and T don't match." % what)
+    lam = torch.empty(tuple(T.shape[:-1]), dtype=torch.complex128, device=T.device)
+    V = torch.empty_like(T)
+    if T.numel():
+        h = _h(T)
+        _zeig_check(h.lib.nd4hip_ztrevc_batched_dev(h.ptr, _batch(tuple(T.shape[:-2])), N, _p(Q), _p(T), _p(lam), _p(V)))
+    return lam, V
+
+
+def _zgeev(A, vectors):
+    from .la import _zeig_check
+    A, N = _zeig_in(A, "A", "zeigen(A)" if vectors else "zeigenvals(A)", "eigen", 1024)
+    lam = torch.empty(tuple(A.shape[:-1]), dtype=torch.complex128, device=A.device)
+    V = torch.empty_like(A) if vectors else None
+    if A.numel():
+        h = _h(A)
+        _zeig_check(h.lib.nd4hip_zgeev_batched_dev(h.ptr, _batch(tuple(A.shape[:-2])), N, _p(A), _p(lam), _p(V) if vectors else None))
+    return (lam, V) if vectors else lam
+
+
+def zeigen(A):
+    """device-resident la.zeigen: (lam, V), the same bits; A is not written. Synchronises."""
+    return _zgeev(A, True)
+
+
+def zeigenvals(A):
+    """device-resident la.zeigenvals: lam, the same bits. Synchronises."""
+    return _zgeev(A, False)
+
+
 def _stevx(d, e, subset, what, vectors, interval=None, info=None):
     from .la import _interval_what, _subset, _tridiag_args
     if interval is not None:

@@ -26,6 +26,10 @@ JS wrapper nd4js_amd/js/index.js over the N-API shim; both call the same libnd4h
                                       nd4hip_zgels_batched_host (csrc/zgeqrf.hip)
   zbidiag_factor(A), zbidiag_apply_p(F, taup, Z, adjoint), zsvd_decomp(A, subset), zsvd_vals(A, subset)   complex128 A, not in the reference
                                    -> nd4hip_zgebrd_batched_host, nd4hip_zunmbr_p_batched_host, nd4hip_zgesdd_batched_host (csrc/zgebrd.hip)
+  zhess_factor(A), zhess_apply_q(F, tau, Z, adjoint), zhess_decomp(A), zschur_qr(Q0, H), zschur_decomp(A), zschur_eigen(Q, T), zeigen(A),
+  zeigenvals(A)                    general complex128 A, not in the reference
+                                   -> nd4hip_zgehrd_batched_host, nd4hip_zunmhr_batched_host, nd4hip_zhseqr_batched_host, nd4hip_zgees_batched_host,
+                                      nd4hip_ztrevc_batched_host, nd4hip_zgeev_batched_host (csrc/zgehrd.hip, csrc/zhseqr.hip)
   zlu_decomp(A, info), zlu_solve(LU, P, Y), zsolve(A, Y)   general complex128 A, not in the reference
                                    -> nd4hip_zgetrf_batched_host, nd4hip_zgetrs_batched_host, nd4hip_zgesv_batched_host (csrc/zgetrf.hip)
   tridiag_eigen(d, e), tridiag_eigenvals(d, e), tridiag_count(d, e, x)   not in the reference   -> nd4hip_dstevx_batched_host, nd4hip_dstcnt_batched_host
@@ -2035,6 +2039,156 @@ def zsvd_decomp(A, subset=None, device=None):
 def zsvd_vals(A, subset=None, device=None):
     """sv float64 [..., k] of zsvd_decomp(A, subset) without the vectors, by bisection on the bidiagonal matrix."""
     return _zsvd(A, subset, False, device)
+
+
+def _zeig_square(shape, name, what, nmax):
+    """N of a stack of square complex members, N <= nmax, shared with dev.py"""
+    if len(shape) < 2:
+        raise ValueError("%s: %s.ndim must be at least 2." % (what, name))
+    if shape[-2] != shape[-1]:
+        raise ValueError("%s: %s must be quadratic." % (what, name))
+    if shape[-1] > nmax:
+        raise ValueError("%s: N <= %d." % (what, nmax))
+    return int(shape[-1])
+
+
+def _zeig_check(rc):
+    """_lib.check with the family's ValueError for NaN or Infinity in a member and for a member that did not converge (code -3)"""
+    try:
+        _lib.check(rc)
+    except _lib.Nd4HipError as e:
+        if e.code == -3:
+            raise ValueError(str(e).split(": ", 1)[1])
+        raise
+
+
+def _zeig_in(A, name, what, real_goes_to, nmax):
+    A = np.asarray(A)
+    _zlu_dtype(name, what, A.dtype.kind == "c", A.dtype == np.complex128, A.dtype, real_goes_to)
+    A = np.ascontiguousarray(A)
+    return A, _zeig_square(A.shape, name, what, nmax)
+
+
+def _nb(lead):
+    return int(np.prod(lead, dtype=np.int64))
+
+
+def zhess_factor(A, device=None):
+    """(F complex128 [..., N, N], tau complex128 [..., N-1]) of the complex128 A, N <= 2048 (LAPACK's zgehrd on row-major members):
+    A = Q H Q^H, H upper Hessenberg with an exactly real subdiagonal, on and above the subdiagonal of F. Q = H_0 ... H_{N-2},
+    H_k = I - tau_k v_k v_k^H, v_k = (0, .., 1 at k+1, F[k+2:, k]); the last reflector has an empty tail and only makes h_{N-1,N-2} real.
+    A -> 2^m A leaves tails and tau bit-identical and scales H exactly (csrc/zgehrd.hip). NaN or Inf in a member raises ValueError with
+    the lowest such member. A float64 A raises TypeError: it goes to hessenberg_decomp."""
+    what = "zhess_factor(A)"
+    A, N = _zeig_in(A, "A", what, "hessenberg_decomp", 2048)
+    F = np.empty(A.shape, dtype=np.complex128)
+    tau = np.empty(A.shape[:-2] + (max(N - 1, 0),), dtype=np.complex128)
+    if F.size:
+        h = _lib.handle(device)
+        _zeig_check(h.lib.nd4hip_zgehrd_batched_host(h.ptr, _nb(A.shape[:-2]), N, _ptr(A), _ptr(F), _ptr(tau) if N > 1 else None))
+    return F, tau
+
+
+def _zhess_factored(sf, st, sz, what):
+    """the shapes of (F, tau) against Z [..., N, K]: (N, K, leading shape)"""
+    N = _zeig_square(sf, "F", what, 2048)
+    if len(st) < 1 or int(st[-1]) != max(N - 1, 0) or tuple(st[:-1]) != tuple(sf[:-2]):
+        raise ValueError("%s: F and tau don't match." % what)
+    if len(sz) < 2 or int(sz[-2]) != N or tuple(sz[:-2]) != tuple(sf[:-2]):
+        raise ValueError("%s: F and Z don't match." % what)
+    return N, int(sz[-1]), tuple(sz[:-2])
+
+
+def zhess_apply_q(F, tau, Z, adjoint=False, device=None):
+    """Q Z (adjoint: Q^H Z) complex128 [..., N, K] for the (F, tau) of zhess_factor and Z complex128 or float64 (promoted) with the same
+    leading dimensions. Z is not written."""
+    what = "zhess_apply_q(F,tau,Z)"
+    F = np.asarray(F)
+    _zlu_dtype("F", what, F.dtype.kind == "c", F.dtype == np.complex128, F.dtype, "hessenberg_decomp")
+    F, tau = np.ascontiguousarray(F), _zqr_tau(tau, what)
+    Z = np.array(_zqr_rhs(Z, what))
+    N, K, lead = _zhess_factored(F.shape, tau.shape, Z.shape, what)
+    if Z.size:
+        h = _lib.handle(device)
+        _lib.check(h.lib.nd4hip_zunmhr_batched_host(h.ptr, _nb(lead), N, K, 1 if adjoint else 0, _ptr(F), _ptr(tau) if N > 1 else None, _ptr(Z)))
+    return Z
+
+
+def zhess_decomp(A, device=None):
+    """(Q, H) complex128 [..., N, N] with A = Q H Q^H, Q unitary, H upper Hessenberg with exact zeros below its exactly real
+    subdiagonal: zhess_factor, then zhess_apply_q on the identity."""
+    F, tau = zhess_factor(A, device)
+    N = F.shape[-1]
+    Q = zhess_apply_q(F, tau, np.broadcast_to(np.eye(N, dtype=np.complex128), F.shape), device=device)
+    return Q, np.triu(F, -1)
+
+
+def zschur_qr(Q0, H, device=None):
+    """(Q, T) complex128 [..., N, N], N <= 1024, with Q T Q^H = Q0 H Q0^H from an upper Hessenberg H (what lies below its subdiagonal
+    is not read): the single-shift QR iteration alone (LAPACK's zlahqr; csrc/zhseqr.hip). T is upper triangular with exact zeros below
+    its diagonal. A member that has not converged after 30 max(10, N) sweeps, or holds NaN or Inf, raises ValueError."""
+    what = "zschur_qr(Q0,H)"
+    H, N = _zeig_in(H, "H", what, "schur_decomp", 1024)
+    Q0, _ = _zeig_in(Q0, "Q0", what, "schur_decomp", 1024)
+    if Q0.shape != H.shape:
+        raise ValueError("%s: Q0 and H don't match." % what)
+    Q, T = np.empty_like(H), np.empty_like(H)
+    if H.size:
+        h = _lib.handle(device)
+        _zeig_check(h.lib.nd4hip_zhseqr_batched_host(h.ptr, _nb(H.shape[:-2]), N, 1, _ptr(Q0), _ptr(H), _ptr(Q), _ptr(T)))
+    return Q, T
+
+
+def zschur_decomp(A, device=None):
+    """(Q, T) complex128 [..., N, N] of the general complex128 A, N <= 1024: A = Q T Q^H, Q unitary, T upper triangular with exact zeros
+    below its diagonal (LAPACK's zgees without sorting: zhess_factor, its Q, zschur_qr). A -> 2^m A leaves Q bit-identical and scales T
+    exactly. Raises as zschur_qr. A float64 A raises TypeError: it goes to schur_decomp."""
+    what = "zschur_decomp(A)"
+    A, N = _zeig_in(A, "A", what, "schur_decomp", 1024)
+    Q, T = np.empty_like(A), np.empty_like(A)
+    if A.size:
+        h = _lib.handle(device)
+        _zeig_check(h.lib.nd4hip_zgees_batched_host(h.ptr, _nb(A.shape[:-2]), N, _ptr(A), _ptr(Q), _ptr(T)))
+    return Q, T
+
+
+def zschur_eigen(Q, T, device=None):
+    """(lam complex128 [..., N], V complex128 [..., N, N]) from a complex Schur form: lam = diag(T) in T's order, the columns of V the
+    eigenvectors of Q T Q^H, each of unit 2-norm (LAPACK's ztrevc with its pivot floor max(eps |t_kk|, smallnum), then V = Q X)."""
+    what = "zschur_eigen(Q,T)"
+    T, N = _zeig_in(T, "T", what, "schur_eigen", 1024)
+    Q, _ = _zeig_in(Q, "Q", what, "schur_eigen", 1024)
+    if Q.shape != T.shape:
+        raise ValueError("%s: Q and T don't match." % what)
+    lam, V = np.empty(T.shape[:-1], dtype=np.complex128), np.empty_like(T)
+    if T.size:
+        h = _lib.handle(device)
+        _zeig_check(h.lib.nd4hip_ztrevc_batched_host(h.ptr, _nb(T.shape[:-2]), N, _ptr(Q), _ptr(T), _ptr(lam), _ptr(V)))
+    return lam, V
+
+
+def _zgeev(A, vectors, device):
+    what = "zeigen(A)" if vectors else "zeigenvals(A)"
+    A, N = _zeig_in(A, "A", what, "eigen", 1024)
+    lam = np.empty(A.shape[:-1], dtype=np.complex128)
+    V = np.empty_like(A) if vectors else None
+    if A.size:
+        h = _lib.handle(device)
+        _zeig_check(h.lib.nd4hip_zgeev_batched_host(h.ptr, _nb(A.shape[:-2]), N, _ptr(A), _ptr(lam), _ptr(V) if vectors else None))
+    return (lam, V) if vectors else lam
+
+
+def zeigen(A, device=None):
+    """(lam complex128 [..., N], V complex128 [..., N, N]) of the general complex128 A, N <= 1024: A V = V diag(lam), every column of V
+    of unit 2-norm (eigen's convention), lam in the order of the Schur form's diagonal: nothing is sorted (LAPACK's zgeev). There is NO
+    diagonal balancing (zgebal): the exact scaling by a power of two, which makes zeigen(2^m A) = (2^m lam, V) bit for bit, is the
+    only preconditioning. Raises as zschur_qr. A float64 A raises TypeError: it goes to eigen."""
+    return _zgeev(A, True, device)
+
+
+def zeigenvals(A, device=None):
+    """lam of zeigen(A), the same bits, without Q and the vectors."""
+    return _zgeev(A, False, device)
 
 
 def _tridiag_args(d, e, what, ndim, shape):
