@@ -796,6 +796,32 @@ int nd4hip_zgetrs_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, int64
 int nd4hip_zgesv_batched_dev  (nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, const double* A, const double* Y, double* X);
 int nd4hip_zgesv_batched_host (nd4hip_handle* h, int64_t batch, int64_t N, int64_t K, const double* A, const double* Y, double* X);
 
+/* ---- matrix inverses: inv / tril_inv, triu_inv / cholesky_inv (csrc/getri.hip) ----
+ * float64, row-major members, dense batches. 1 <= N <= 2048: a larger N is ND4HIP_ERR_ARG before anything is written; an empty batch and
+ * N = 0 have nothing to do and write nothing. No operand is written.
+ *   dgetri: X [batch,N,N] with A X = I, LAPACK's getri on dgetrf's factorisation (X = U^-1 (L^-1 P), never Gauss-Jordan): the pivot of
+ *           column j is the first row i >= j with the largest |a_ij| (a NaN never wins unless it is the start row), every division is a
+ *           true division. A member with a zero or non-finite pivot: with info (int32 [batch]; device memory in the _dev form) nothing
+ *           fails, info receives 1 + the first such column per member (0 for none), that member's X is all NaN, every other member has
+ *           the bits it has alone, and the _dev form only enqueues. info = NULL: ND4HIP_ERR_SINGULAR, 'inv(A): A is singular. (matrix
+ *           <b>)' with the lowest such member; the handle stays usable; synchronises (one flag word per pass).
+ *   dtrtri: X = the inverse of the upper (upper != 0) or lower triangle of T by substitution with true divisions. The other triangle of T
+ *           is never read, the other triangle of X is +0. A zero on the diagonal is no error: inside the triangle X is inf / NaN where the
+ *           substitution on the whole identity is (that row, and every row after it in the order of the substitution).
+ *   dpotri: X = L^-T L^-1 from the lower triangle of dpotrf's L; both triangles of X are written with identical bits.
+ * dtrtri and dpotri only enqueue (the _dev forms). No sum depends on the run. dtrtri and dpotri at every N, and dgetri up to N = 128, give
+ * a member the bits it has alone, whatever the batch and its position in it. Above N = 128 dgetri starts from dgetrf's factorisation,
+ * which takes one strategy for up to 12 members in a pass and another for more (factors equal within rounding, not bit for bit); a pass
+ * holds min(batch, 32768, 2^27 / (2 N^2 + 65 N)) members. Within one strategy a member has the bits it has alone. From N = 128 on these
+ * entries are slower than dgetrs / dtrsm / dpotrs on an identity; they win on stacks of small members. Profile ops
+ * "dgetri_batched" (2 N^3 flops), "dtrtri_batched" (N^3 / 3) and "dpotri_batched" (2/3 N^3). */
+int nd4hip_dgetri_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* X, int32_t* info);
+int nd4hip_dgetri_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* X, int32_t* info);
+int nd4hip_dtrtri_batched_dev (nd4hip_handle* h, int upper, int64_t batch, int64_t N, const double* T, double* X);
+int nd4hip_dtrtri_batched_host(nd4hip_handle* h, int upper, int64_t batch, int64_t N, const double* T, double* X);
+int nd4hip_dpotri_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, const double* L, double* X);
+int nd4hip_dpotri_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, const double* L, double* X);
+
 /* ---- complex QR: zqr_factor / zqr_apply_q / zqr_decomp / zqr_lstsq (csrc/zgeqrf.hip) ----
  * LAPACK's zgeqrf / zunmqr / zungqr / zgels on row-major members, complex128 as interleaved (re, im) doubles on 16-byte boundaries,
  * strides in complex elements. 0 <= N <= M <= 2048 and K <= 4 194 240, refused before anything is written; an extent of 0 is an empty call.

@@ -197,6 +197,13 @@ SIGNATURES = {
     "nd4hip_zgetrs_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_i64, ctypes.c_void_p, c_i64, c_dp, c_i64, c_dp]),
     "nd4hip_zgesv_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
     "nd4hip_zgesv_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
+    # inv, tril_inv / triu_inv (upper, batch, N), cholesky_inv (csrc/getri.hip): info int32 or NULL
+    "nd4hip_dgetri_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, ctypes.c_void_p]),
+    "nd4hip_dgetri_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, ctypes.c_void_p]),
+    "nd4hip_dtrtri_batched_dev": (c_int, [ctypes.c_void_p, c_int, c_i64, c_i64, c_dp, c_dp]),
+    "nd4hip_dtrtri_batched_host": (c_int, [ctypes.c_void_p, c_int, c_i64, c_i64, c_dp, c_dp]),
+    "nd4hip_dpotri_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp]),
+    "nd4hip_dpotri_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp]),
     # complex QR, its Q, the thin factors and least squares (csrc/zgeqrf.hip): info int32
     "nd4hip_zgeqrf_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
     "nd4hip_zgeqrf_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),

@@ -472,10 +472,12 @@ int launch(nd4hip_handle* h, const GemmArgs& g, bool vec, int64_t batch) {
 
 }  // namespace
 
-int nd4_gemm(nd4hip_handle* h, bool transA, bool transB, int64_t M, int64_t N, int64_t K,
-             double alpha, const double* A, int64_t lda, int64_t sA,
-             const double* B, int64_t ldb, int64_t sB,
-             double beta, double* C, int64_t ldc, int64_t sC, int64_t batch) {
+// split_k: whether a long K may be split over blockIdx.z when the launch has few tiles. That choice counts the tiles of the whole
+// batch, so with it the summation order of a member depends on how many members share the launch
+static int gemm_run(nd4hip_handle* h, bool transA, bool transB, int64_t M, int64_t N, int64_t K,
+                    double alpha, const double* A, int64_t lda, int64_t sA,
+                    const double* B, int64_t ldb, int64_t sB,
+                    double beta, double* C, int64_t ldc, int64_t sC, int64_t batch, bool split_k) {
   if (M <= 0 || N <= 0 || batch <= 0) return 0;
   ND4_CHECK_ARG(K >= 0 && M < (1 << 30) && N < (1 << 30) && K < (1 << 30), "nd4_gemm: extent out of range");
   ND4_CHECK_ARG(batch <= 65535, "nd4_gemm: batch %lld exceeds 65535 per launch", (long long)batch);
@@ -491,7 +493,7 @@ int nd4_gemm(nd4hip_handle* h, bool transA, bool transB, int64_t M, int64_t N, i
   Nd4WsScope scope(h);
   const int64_t tiles = (int64_t)g.tiles_m * g.tiles_n * batch;
   int nsplit = 1;
-  if (tiles <= 160 && K >= 512) {                       // (<= 160: a launch of 128-160 tiles leaves a third of the 256 CUs idle)
+  if (split_k && tiles <= 160 && K >= 512) {                       // (<= 160: a launch of 128-160 tiles leaves a third of the 256 CUs idle)
     int64_t want = 384 / tiles;
     if (want > K / 256) want = K / 256;
     if (want > 32) want = 32;
@@ -517,6 +519,20 @@ int nd4_gemm(nd4hip_handle* h, bool transA, bool transB, int64_t M, int64_t N, i
     ND4_HIP(hipGetLastError());
   }
   return 0;
+}
+
+int nd4_gemm(nd4hip_handle* h, bool transA, bool transB, int64_t M, int64_t N, int64_t K,
+             double alpha, const double* A, int64_t lda, int64_t sA,
+             const double* B, int64_t ldb, int64_t sB,
+             double beta, double* C, int64_t ldc, int64_t sC, int64_t batch) {
+  return gemm_run(h, transA, transB, M, N, K, alpha, A, lda, sA, B, ldb, sB, beta, C, ldc, sC, batch, true);
+}
+// the same product with every member's sums in one order whatever the batch: K is never split
+int nd4_gemm_member_order(nd4hip_handle* h, bool transA, bool transB, int64_t M, int64_t N, int64_t K,
+                          double alpha, const double* A, int64_t lda, int64_t sA,
+                          const double* B, int64_t ldb, int64_t sB,
+                          double beta, double* C, int64_t ldc, int64_t sC, int64_t batch) {
+  return gemm_run(h, transA, transB, M, N, K, alpha, A, lda, sA, B, ldb, sB, beta, C, ldc, sC, batch, false);
 }
 
 // C[lower tiles] = alpha * A A^T + beta * C for A [N, K] (row-major, lda): every 128x128 tile that touches the diagonal

@@ -1075,6 +1075,33 @@ extern "C" int nd4hip_zgesv_batched_dev(nd4hip_handle* h, int64_t batch, int64_t
   return nd4_zgesv_run(h, batch, N, K, A, Y, X, 0, nullptr);
 }
 
+// ---- inv / tril_inv, triu_inv / cholesky_inv (getri.hip). Flops: 2 N^3 for inv, N^3 / 3 for a triangle, 2/3 N^3 for
+// cholesky_inv
+int nd4_getri_run(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* X, int32_t* info, int64_t member0, int64_t* first_bad) {
+  ND4_ARGS(nd4_args_inv("dgetri_batched", batch, N, A, X));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dgetri_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "dgetri_batched", batch * (2.0 * (double)N * N * N), 8.0 * batch * 2.0 * (double)(N * N));
+  return nd4_getri(h, batch, N, A, X, info, member0, first_bad);
+}
+extern "C" int nd4hip_dgetri_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* X, int32_t* info) {
+  return nd4_getri_run(h, batch, N, A, X, info, 0, nullptr);
+}
+extern "C" int nd4hip_dtrtri_batched_dev(nd4hip_handle* h, int upper, int64_t batch, int64_t N, const double* T, double* X) {
+  ND4_ARGS(nd4_args_inv("dtrtri_batched", batch, N, T, X));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dtrtri_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "dtrtri_batched", batch * ((double)N * N * N / 3.0), 8.0 * batch * 1.5 * (double)(N * N));
+  return nd4_trtri(h, upper != 0, batch, N, T, X);
+}
+extern "C" int nd4hip_dpotri_batched_dev(nd4hip_handle* h, int64_t batch, int64_t N, const double* L, double* X) {
+  ND4_ARGS(nd4_args_inv("dpotri_batched", batch, N, L, X));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dpotri_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "dpotri_batched", batch * (2.0 / 3.0 * (double)N * N * N), 8.0 * batch * 1.5 * (double)(N * N));
+  return nd4_potri(h, batch, N, L, X);
+}
+
 // ---- zqr_factor / zqr_apply_q / zqr_decomp / zqr_lstsq (zgeqrf.hip). Real flops: 8 N^2 (M - N / 3) for the factorisation and for
 // the thin Q, 8 N K (2 M - N) for Q Z, 4 N^2 K for the upper sweep
 extern "C" int nd4hip_zgeqrf_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* F, double* tau) {

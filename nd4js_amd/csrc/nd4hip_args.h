@@ -460,6 +460,14 @@ inline int nd4_args_zgesv(int64_t batch, int64_t N, int64_t K, const void* A, co
   ND4_CHECK_ARG(A && Y && X, "nd4hip_zgesv_batched: NULL pointer");
   return ND4_ARGS_GO;
 }
+// ---- matrix inverses (getri.hip; dgetri, dtrtri, dpotri): N <= 2048 before anything is launched or written; dgetri's info may be NULL
+inline int nd4_args_inv(const char* op, int64_t batch, int64_t N, const void* A, const void* X) {
+  ND4_CHECK_ARG(batch >= 0 && N >= 0, "nd4hip_%s: negative extent", op);
+  ND4_CHECK_ARG(N <= 2048, "nd4hip_%s: N <= 2048", op);
+  if (batch == 0 || N == 0) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(A && X, "nd4hip_%s: NULL pointer", op);
+  return ND4_ARGS_GO;
+}
 // ---- complex QR (zgeqrf.hip): N <= M <= 2048 and K before anything is launched or written. zgels: tau = NULL: A is the matrix and
 // strideA must be M*N; else A is F with its tau, strideA M*N or 0 (one factorisation for all); info may be NULL
 inline int nd4_args_zqr(const char* op, int64_t batch, int64_t M, int64_t N, int64_t K, Nd4Ptrs ptrs) {

@@ -1382,6 +1382,44 @@ extern "C" int nd4hip_zgesv_batched_host(nd4hip_handle* h, int64_t batch, int64_
   return 0;
 }
 
+// inv / tril_inv, triu_inv / cholesky_inv (getri.hip). dgetri: info = NULL: a singular member is an error, which does not stop the other
+// chunks: every chunk runs and comes back, the lowest singular member is reported at the end
+extern "C" int nd4hip_dgetri_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* X, int32_t* info) {
+  ND4_ARGS(nd4_args_inv("dgetri_batched", batch, N, A, X));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dgetri_batched: NULL handle");
+  std::vector<Operand> ops{in_op(A, N * N, N * N), out_op(X, N * N)};
+  if (info) ops.push_back(out_op(info, 1, 4));
+  const bool want = info != nullptr;
+  std::atomic<int64_t> worst(INT64_MAX);
+  ChunkFn fn = [=, &worst](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    int64_t bad = INT64_MAX;
+    const int rc = nd4_getri_run(hd, nb, N, P(p, 0), P(p, 1), want ? static_cast<int32_t*>(p[2]) : nullptr, g_chunk_first, &bad);
+    if (rc != ND4HIP_ERR_SINGULAR) return rc;
+    for (int64_t seen = worst.load(); bad < seen && !worst.compare_exchange_weak(seen, bad);) {}
+    return 0;
+  };
+  ND4_TRY(run_host(h, batch, ops, fn));
+  if (worst.load() != INT64_MAX) {
+    nd4_set_error("inv(A): A is singular. (matrix %lld)", (long long)worst.load());
+    return ND4HIP_ERR_SINGULAR;
+  }
+  return 0;
+}
+extern "C" int nd4hip_dtrtri_batched_host(nd4hip_handle* h, int upper, int64_t batch, int64_t N, const double* T, double* X) {
+  ND4_ARGS(nd4_args_inv("dtrtri_batched", batch, N, T, X));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dtrtri_batched: NULL handle");
+  std::vector<Operand> ops{in_op(T, N * N, N * N), out_op(X, N * N)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) { return nd4hip_dtrtri_batched_dev(hd, upper, nb, N, P(p, 0), P(p, 1)); };
+  return run_host(h, batch, ops, fn);
+}
+extern "C" int nd4hip_dpotri_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, const double* L, double* X) {
+  ND4_ARGS(nd4_args_inv("dpotri_batched", batch, N, L, X));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dpotri_batched: NULL handle");
+  std::vector<Operand> ops{in_op(L, N * N, N * N), out_op(X, N * N)};
+  ChunkFn fn = [=](nd4hip_handle* hd, int, int64_t nb, void* const* p) { return nd4hip_dpotri_batched_dev(hd, nb, N, P(p, 0), P(p, 1)); };
+  return run_host(h, batch, ops, fn);
+}
+
 // zqr_factor / zqr_apply_q / zqr_decomp / zqr_lstsq (zgeqrf.hip). zgels: tau = NULL: A is the matrix; info = NULL: a rank-deficient member is
 // an error, which does not stop the other chunks: every chunk runs and comes back, the lowest such member is reported at the end
 extern "C" int nd4hip_zgeqrf_batched_host(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* F, double* tau) {

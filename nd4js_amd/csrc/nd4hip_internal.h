@@ -92,6 +92,11 @@ int nd4_gemm(nd4hip_handle* h, bool transA, bool transB, int64_t M, int64_t N, i
              double alpha, const double* A, int64_t lda, int64_t sA,
              const double* B, int64_t ldb, int64_t sB,
              double beta, double* C, int64_t ldc, int64_t sC, int64_t batch);
+// nd4_gemm without the split of K that depends on the number of tiles in the launch: a member's sums do not depend on the batch
+int nd4_gemm_member_order(nd4hip_handle* h, bool transA, bool transB, int64_t M, int64_t N, int64_t K,
+                          double alpha, const double* A, int64_t lda, int64_t sA,
+                          const double* B, int64_t ldb, int64_t sB,
+                          double beta, double* C, int64_t ldc, int64_t sC, int64_t batch);
 // complex: C[b] = A[b] * B[b] on interleaved (re, im) doubles, A complex I x K, B complex (b_complex) or real K x J,
 // C dense complex [batch, I, J]; strides in elements of each operand, batch <= 65535 (zgemm.hip)
 int nd4_zgemm(nd4hip_handle* h, bool b_complex, int64_t batch, int64_t I, int64_t K, int64_t J,
@@ -165,6 +170,19 @@ int64_t nd4_hseqr_chunk(int64_t N);
 // output of out_elems doubles
 const char* nd4_permute_name(int cols, int inverse);
 bool nd4_struct_overlap(const void* in, int64_t in_elems, const void* out, int64_t out_elems);
+// the kernels of one dpermute call without its flag read-back: *flag (device, zero on entry) is raised by an index of P outside its
+// range, whose element is skipped, never addressed. Enqueues only
+int nd4_permute_enqueue(nd4hip_handle* h, int cols, int inverse, int64_t batch, int64_t M, int64_t N, const double* A, int64_t strideA,
+                        const int32_t* P, int64_t strideP, double* B, int* flag);
+// matrix inverses (getri.hip): arguments already checked, batch >= 1, 1 <= N <= 2048. nd4_getri: info (device int32
+// [batch]) receives 1 + the first column with an unusable pivot per member, 0 if none, and the call only enqueues; info = NULL: one flag
+// word per pass is read back and a flagged member is ND4HIP_ERR_SINGULAR with the lowest such member counted from member0 (also in
+// *first_bad, may be NULL). nd4_trtri and nd4_potri enqueue only
+int nd4_getri(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* X, int32_t* info, int64_t member0, int64_t* first_bad);
+int nd4_trtri(nd4hip_handle* h, bool upper, int64_t batch, int64_t N, const double* T, double* X);
+int nd4_potri(nd4hip_handle* h, int64_t batch, int64_t N, const double* L, double* X);
+// inv's entry point with member0, shared by the _dev and _host forms (nd4hip_api.hip)
+int nd4_getri_run(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* X, int32_t* info, int64_t member0, int64_t* first_bad);
 int nd4_gesvdj(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A,
                double* U, double* sv, double* V, int* sweeps_out, double* offnorm_out);
 // the exact power-of-two scaling of the SVD entries (svd.hip): max|a| per member, dst = 2^-e src, sv *= 2^e

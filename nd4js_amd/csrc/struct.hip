@@ -287,6 +287,10 @@ const char* nd4_permute_name(int cols, int inverse) {
 bool nd4_struct_overlap(const void* in, int64_t in_elems, const void* out, int64_t out_elems) {
   return overlaps(in, (size_t)in_elems * 8, out, (size_t)out_elems * 8);
 }
+int nd4_permute_enqueue(nd4hip_handle* h, int cols, int inverse, int64_t batch, int64_t M, int64_t N, const double* A, int64_t strideA,
+                        const int32_t* P, int64_t strideP, double* B, int* flag) {
+  return launch_permute(h, cols, inverse, batch, M, N, A, strideA, P, strideP, B, flag);
+}
 
 extern "C" int nd4hip_dtranspose_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* B) {
   ND4_CHECK_ARG(h != nullptr, "nd4hip_dtranspose_batched: NULL handle");

@@ -1234,6 +1234,47 @@ def zsolve(A, Y):
     return X
 
 
+def _inv_dev(A, name, what, call):
+    """X of A's shape from call(handle, members, N, A, X), with la's checks and texts"""
+    from .la import _hegv_square, _inv_dtype
+    if isinstance(A, torch.Tensor):
+        _inv_dtype(name, what, A.is_complex(), A.dtype == torch.float64, A.dtype)
+    if not (isinstance(A, torch.Tensor) and A.is_cuda and A.is_contiguous()):
+        raise TypeError("%s: %s must be a contiguous float64 CUDA tensor" % (what, name))
+    N = _hegv_square(tuple(A.shape), name, what)
+    X = torch.empty_like(A)
+    if X.numel():
+        h = _h(A)
+        _lib.check(call(h, _batch(A.shape[:-2]), N, _p(A), _p(X)))
+    return X
+
+
+def inv(A, info=None):
+    """device-resident la.inv: X with A X = I, the same bits; A is not written. With info (a dict) the call is only enqueued and
+    info["singular"] receives an int32 tensor [...] on A's device; without it a singular member raises as la.inv (one flag word is read back)."""
+    flags = torch.zeros(tuple(A.shape[:-2]), dtype=torch.int32, device=A.device) if info is not None and isinstance(A, torch.Tensor) else None
+    X = _inv_dev(A, "A", "inv(A)", lambda h, b, N, a, x: h.lib.nd4hip_dgetri_batched_dev(
+        h.ptr, b, N, a, x, ctypes.c_void_p(flags.data_ptr()) if flags is not None else None))
+    if info is not None:
+        info["singular"] = flags
+    return X
+
+
+def tril_inv(L):
+    """device-resident la.tril_inv: the inverse of the lower triangle of L, the same bits; L is not written. Only enqueued."""
+    return _inv_dev(L, "L", "tril_inv(L)", lambda h, b, N, a, x: h.lib.nd4hip_dtrtri_batched_dev(h.ptr, 0, b, N, a, x))
+
+
+def triu_inv(U):
+    """device-resident la.triu_inv: the inverse of the upper triangle of U, the same bits; U is not written. Only enqueued."""
+    return _inv_dev(U, "U", "triu_inv(U)", lambda h, b, N, a, x: h.lib.nd4hip_dtrtri_batched_dev(h.ptr, 1, b, N, a, x))
+
+
+def cholesky_inv(L):
+    """device-resident la.cholesky_inv: L^-T L^-1 from the lower triangle of L, the same bits; L is not written. Only enqueued."""
+    return _inv_dev(L, "L", "cholesky_inv(L)", lambda h, b, N, a, x: h.lib.nd4hip_dpotri_batched_dev(h.ptr, b, N, a, x))
+
+
 def zqr_factor(A):
     """device-resident la.zqr_factor: (F complex128 [..., M, N], tau complex128 [..., N]) of the complex128 A, the same bits; A is not
     written. Only enqueued."""

@@ -32,6 +32,8 @@ JS wrapper nd4js_amd/js/index.js over the N-API shim; both call the same libnd4h
                                       nd4hip_ztrevc_batched_host, nd4hip_zgeev_batched_host (csrc/zgehrd.hip, csrc/zhseqr.hip)
   zlu_decomp(A, info), zlu_solve(LU, P, Y), zsolve(A, Y)   general complex128 A, not in the reference
                                    -> nd4hip_zgetrf_batched_host, nd4hip_zgetrs_batched_host, nd4hip_zgesv_batched_host (csrc/zgetrf.hip)
+  inv(A, info), tril_inv(L), triu_inv(U), cholesky_inv(L)   float64, not in the reference
+                                   -> nd4hip_dgetri_batched_host, nd4hip_dtrtri_batched_host, nd4hip_dpotri_batched_host (csrc/getri.hip)
   tridiag_eigen(d, e), tridiag_eigenvals(d, e), tridiag_count(d, e, x)   not in the reference   -> nd4hip_dstevx_batched_host, nd4hip_dstcnt_batched_host
                                    interval=(lo, hi) (opt-in, here and in eigen_sym): the eigenvalues in (lo, hi] -> nd4hip_dstevxv_batched_host,
                                    nd4hip_dsyevxv_batched_host, nd4hip_dsyevxv_tr_batched_host
@@ -1822,6 +1824,62 @@ def zsolve(A, Y, device=None):
         h = _lib.handle(device)
         _lib.check(h.lib.nd4hip_zgesv_batched_host(h.ptr, int(np.prod(lead, dtype=np.int64)), N, K, _ptr(A), _ptr(Y), _ptr(X)))
     return X
+
+
+def _inv_dtype(name, what, is_complex, is_f64, dtype):
+    """the dtype rule of the inverses, shared with dev.py: float64 only; a complex matrix is refused by name"""
+    if is_complex:
+        raise TypeError("%s: %s.dtype must be float64; complex inverses are not implemented." % (what, name))
+    if not is_f64:
+        raise TypeError("%s: only float64 runs on the GPU path, got %s" % (what, dtype))
+
+
+def _inv_host(A, name, what, device, call):
+    """X float64 of A's shape from call(handle, members, N, A, X); the checks come first, and nothing is launched for an empty stack"""
+    A = np.asarray(A)
+    _inv_dtype(name, what, A.dtype.kind == "c", A.dtype == np.float64, A.dtype)
+    A = np.ascontiguousarray(A)
+    N = _hegv_square(A.shape, name, what)
+    X = np.empty(A.shape, dtype=np.float64)
+    if X.size:
+        h = _lib.handle(device)
+        _lib.check(call(h, int(np.prod(A.shape[:-2], dtype=np.int64)), N, _ptr(A), _ptr(X)))
+    return X
+
+
+def inv(A, info=None, device=None):
+    """X float64 [..., N, N] with A X = I: LAPACK's getri on lu_decomp's factorisation, X = U^-1 (L^-1 P), N <= 2048 (csrc/getri.hip). A
+    member with a zero or non-finite pivot raises Nd4HipError with code -5, 'inv(A): A is singular. (matrix <b>)', b the lowest such
+    member. With info (a dict) nothing raises: info["singular"] receives int32 [...]: 1 + the first such column of every member, 0 for
+    none; such a member's X is all NaN, every other member has the bits it has alone (above N = 128: within lu_decomp's strategy, which
+    changes between 12 and 13 members in a pass). A complex A raises TypeError. Faster than lu_solve(*lu_decomp(A), I) for stacks of
+    members up to N = 64 (1.5 - 8 x); from N = 128 on it takes 1.3 - 2.7 x the time of that composition."""
+    flags = np.zeros(np.shape(A)[:-2], dtype=np.int32)
+    X = _inv_host(A, "A", "inv(A)", device,
+                  lambda h, b, N, a, x: h.lib.nd4hip_dgetri_batched_host(h.ptr, b, N, a, x, _ptr(flags) if info is not None else None))
+    if info is not None:
+        info["singular"] = flags
+    return X
+
+
+def tril_inv(L, device=None):
+    """the inverse of the lower triangle of L [..., N, N] by substitution with true divisions, N <= 2048 (csrc/getri.hip). The upper
+    triangle of L is never read, the upper triangle of the result is +0. A zero on the diagonal does not raise: the result holds the
+    inf / NaN that tril_solve(L, I) produces. Faster than tril_solve(L, I) only for stacks of tiny members; it takes 1.1 - 3 x its time
+    for stacks of 32^2 - 128^2 and 7 - 12 x for one 512^2 - 2048^2 matrix."""
+    return _inv_host(L, "L", "tril_inv(L)", device, lambda h, b, N, a, x: h.lib.nd4hip_dtrtri_batched_host(h.ptr, 0, b, N, a, x))
+
+
+def triu_inv(U, device=None):
+    """the inverse of the upper triangle of U [..., N, N]: tril_inv's mirror image"""
+    return _inv_host(U, "U", "triu_inv(U)", device, lambda h, b, N, a, x: h.lib.nd4hip_dtrtri_batched_host(h.ptr, 1, b, N, a, x))
+
+
+def cholesky_inv(L, device=None):
+    """S^-1 = L^-T L^-1 [..., N, N] from cholesky_decomp's L, of which only the lower triangle is read, N <= 2048 (csrc/getri.hip). Both
+    triangles of the result are written with identical bits. Faster than cholesky_solve(L, I) only for stacks of tiny members; about
+    equal for stacks of 32^2 - 64^2 and 64 x 512^2, 2.6 x its time at 256 x 128^2 and 4 - 7 x for one 512^2 - 2048^2 matrix."""
+    return _inv_host(L, "L", "cholesky_inv(L)", device, lambda h, b, N, a, x: h.lib.nd4hip_dpotri_batched_host(h.ptr, b, N, a, x))
 
 
 def _zqr_shape(shape, name, what):
