@@ -822,6 +822,32 @@ int nd4hip_dtrtri_batched_host(nd4hip_handle* h, int upper, int64_t batch, int64
 int nd4hip_dpotri_batched_dev (nd4hip_handle* h, int64_t batch, int64_t N, const double* L, double* X);
 int nd4hip_dpotri_batched_host(nd4hip_handle* h, int64_t batch, int64_t N, const double* L, double* X);
 
+/* ---- Sylvester and Lyapunov equations: schur_sylvester / sylvester_solve, lyapunov_solve (csrc/trsyl.hip) ----
+ * float64, row-major members, dense batches. 1 <= M, N <= 2048: a larger order is ND4HIP_ERR_ARG before anything is written; an empty
+ * batch and M = 0 or N = 0 have nothing to do and write nothing. No operand is written; X overlaps no operand.
+ *   dtrsyl: Y [batch,M,N] in X with TA Y + Y TB = C (trans_b = 0) or TA Y + Y TB^T = C (trans_b != 0): LAPACK's trsyl WITHOUT its scale
+ *           output, nothing guards against overflow. TA [batch,M,M] and TB [batch,N,N] are upper quasi-triangular as dgees returns them:
+ *           a nonzero T[i+1][i] joins rows i and i + 1 into a 2 x 2 block; entries below the first subdiagonal are never read. Two
+ *           nonzero subdiagonal entries in a row are no valid structure: the result is then undefined (nothing is read or written out
+ *           of bounds). Every pair of diagonal blocks is a Kronecker system of order 1, 2 or 4, solved by Gaussian elimination with
+ *           complete pivoting.
+ *   dgesyl: X [batch,M,N] with A X + X B = C by Bartels-Stewart: dgees of A [batch,M,M] and of B [batch,N,N], F = QA^T C QB, dtrsyl,
+ *           X = QA Y QB^T, the intermediates in the handle's workspace. B = NULL (M == N): the Lyapunov equation A X + X A^T = C from one
+ *           dgees of A and dtrsyl with trans_b; X is not symmetrised. dgees's errors (ND4HIP_ERR_NOCONV) are passed on.
+ * A member is singular when a pivot of one of its Kronecker systems is zero or not finite (A and -B share an eigenvalue). With info
+ * (int32 [batch]; device memory in the _dev form) nothing fails, info receives a nonzero word for such a member (0 otherwise), that
+ * member's X is all NaN, every other member has the bits it has alone, and dtrsyl's _dev form only enqueues. info = NULL:
+ * ND4HIP_ERR_SINGULAR, '<function>: the equation is singular. (matrix <b>)' with the lowest such member; the handle stays usable;
+ * synchronises (one flag word per pass of up to 32768 members). dgesyl synchronises in either case (dgees reads its flags back).
+ * No sum depends on the run, on the batch or on a member's position in it: dtrsyl gives a member the bits it has alone at every M, N.
+ * dgesyl does within one strategy of dgehrd, which reduces ONE matrix of order 128 .. 2048 by another kernel than a batch of them
+ * (equal within rounding, not bit for bit); a pass holds min(batch, 32768, 2^27 / (2 M^2 + 2 N^2 + 2 M N)) members. Profile ops
+ * "dtrsyl_batched" (M N (M + N) flops) and "dgesyl_batched". */
+int nd4hip_dtrsyl_batched_dev (nd4hip_handle* h, int trans_b, int64_t batch, int64_t M, int64_t N, const double* TA, const double* TB, const double* C, double* X, int32_t* info);
+int nd4hip_dtrsyl_batched_host(nd4hip_handle* h, int trans_b, int64_t batch, int64_t M, int64_t N, const double* TA, const double* TB, const double* C, double* X, int32_t* info);
+int nd4hip_dgesyl_batched_dev (nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, const double* B, const double* C, double* X, int32_t* info);
+int nd4hip_dgesyl_batched_host(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, const double* B, const double* C, double* X, int32_t* info);
+
 /* ---- complex QR: zqr_factor / zqr_apply_q / zqr_decomp / zqr_lstsq (csrc/zgeqrf.hip) ----
  * LAPACK's zgeqrf / zunmqr / zungqr / zgels on row-major members, complex128 as interleaved (re, im) doubles on 16-byte boundaries,
  * strides in complex elements. 0 <= N <= M <= 2048 and K <= 4 194 240, refused before anything is written; an extent of 0 is an empty call.

@@ -204,6 +204,12 @@ SIGNATURES = {
     "nd4hip_dtrtri_batched_host": (c_int, [ctypes.c_void_p, c_int, c_i64, c_i64, c_dp, c_dp]),
     "nd4hip_dpotri_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp]),
     "nd4hip_dpotri_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp]),
+    # schur_sylvester (trans_b, batch, M, N, TA, TB, C, X, info), sylvester_solve / lyapunov_solve (batch, M, N, A, B or NULL, C, X, info)
+    # (csrc/trsyl.hip): info int32 or NULL
+    "nd4hip_dtrsyl_batched_dev": (c_int, [ctypes.c_void_p, c_int, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, ctypes.c_void_p]),
+    "nd4hip_dtrsyl_batched_host": (c_int, [ctypes.c_void_p, c_int, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, ctypes.c_void_p]),
+    "nd4hip_dgesyl_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, ctypes.c_void_p]),
+    "nd4hip_dgesyl_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, ctypes.c_void_p]),
     # complex QR, its Q, the thin factors and least squares (csrc/zgeqrf.hip): info int32
     "nd4hip_zgeqrf_batched_dev": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),
     "nd4hip_zgeqrf_batched_host": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp]),

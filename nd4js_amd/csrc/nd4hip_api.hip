@@ -1102,6 +1102,35 @@ extern "C" int nd4hip_dpotri_batched_dev(nd4hip_handle* h, int64_t batch, int64_
   return nd4_potri(h, batch, N, L, X);
 }
 
+// ---- schur_sylvester / sylvester_solve, lyapunov_solve (trsyl.hip). Flops: M N (M + N) for the triangular stage; the
+// driver adds the Schur decompositions (29.7 n^3 each) and four products
+int nd4_trsyl_run(nd4hip_handle* h, int trans_b, int64_t batch, int64_t M, int64_t N, const double* TA, const double* TB, const double* C,
+                  double* X, int32_t* info, int64_t member0, int64_t* first_bad) {
+  ND4_ARGS(nd4_args_syl("dtrsyl_batched", batch, M, N, TA, TB, false, C, X));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dtrsyl_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  Nd4Prof prof(h, "dtrsyl_batched", batch * ((double)M * N * (M + N)), 8.0 * batch * (double)(M * M + N * N + 2 * M * N));
+  return nd4_trsyl(h, trans_b != 0, batch, M, N, TA, TB, C, X, info, member0, first_bad);
+}
+int nd4_gesyl_run(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, const double* B, const double* C, double* X,
+                  int32_t* info, int64_t member0, int64_t* first_bad) {
+  ND4_ARGS(nd4_args_syl("dgesyl_batched", batch, M, N, A, B, true, C, X));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dgesyl_batched: NULL handle");
+  Nd4DeviceGuard guard(h);
+  const double m = (double)M, n = (double)N, schur = 25.0 + 14.0 / 3.0;
+  Nd4Prof prof(h, "dgesyl_batched", batch * (schur * (m * m * m + (B ? n * n * n : 0.0)) + 5.0 * m * n * (m + n)),
+               8.0 * batch * (double)(M * M + (B ? N * N : 0) + 2 * M * N));
+  return nd4_gesyl(h, batch, M, N, A, B, C, X, info, member0, first_bad);
+}
+extern "C" int nd4hip_dtrsyl_batched_dev(nd4hip_handle* h, int trans_b, int64_t batch, int64_t M, int64_t N, const double* TA, const double* TB,
+                                         const double* C, double* X, int32_t* info) {
+  return nd4_trsyl_run(h, trans_b, batch, M, N, TA, TB, C, X, info, 0, nullptr);
+}
+extern "C" int nd4hip_dgesyl_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, const double* B, const double* C,
+                                         double* X, int32_t* info) {
+  return nd4_gesyl_run(h, batch, M, N, A, B, C, X, info, 0, nullptr);
+}
+
 // ---- zqr_factor / zqr_apply_q / zqr_decomp / zqr_lstsq (zgeqrf.hip). Real flops: 8 N^2 (M - N / 3) for the factorisation and for
 // the thin Q, 8 N K (2 M - N) for Q Z, 4 N^2 K for the upper sweep
 extern "C" int nd4hip_zgeqrf_batched_dev(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* F, double* tau) {

@@ -468,6 +468,17 @@ inline int nd4_args_inv(const char* op, int64_t batch, int64_t N, const void* A,
   ND4_CHECK_ARG(A && X, "nd4hip_%s: NULL pointer", op);
   return ND4_ARGS_GO;
 }
+// ---- Sylvester equations (trsyl.hip; dtrsyl, dgesyl): M, N <= 2048 before anything is launched or written; info may be NULL. dgesyl's B
+// may be NULL (b_optional): the Lyapunov form, which needs M == N
+inline int nd4_args_syl(const char* op, int64_t batch, int64_t M, int64_t N, const void* A, const void* B, bool b_optional, const void* C,
+                        const void* X) {
+  ND4_CHECK_ARG(batch >= 0 && M >= 0 && N >= 0, "nd4hip_%s: negative extent", op);
+  ND4_CHECK_ARG(M <= 2048 && N <= 2048, "nd4hip_%s: M, N <= 2048", op);
+  ND4_CHECK_ARG(B || !b_optional || M == N, "nd4hip_%s: B = NULL needs M == N", op);
+  if (batch == 0 || M == 0 || N == 0) return ND4_ARGS_EMPTY;
+  ND4_CHECK_ARG(A && (B || b_optional) && C && X, "nd4hip_%s: NULL pointer", op);
+  return ND4_ARGS_GO;
+}
 // ---- complex QR (zgeqrf.hip): N <= M <= 2048 and K before anything is launched or written. zgels: tau = NULL: A is the matrix and
 // strideA must be M*N; else A is F with its tau, strideA M*N or 0 (one factorisation for all); info may be NULL
 inline int nd4_args_zqr(const char* op, int64_t batch, int64_t M, int64_t N, int64_t K, Nd4Ptrs ptrs) {

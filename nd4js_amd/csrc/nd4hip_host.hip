@@ -1420,6 +1420,53 @@ extern "C" int nd4hip_dpotri_batched_host(nd4hip_handle* h, int64_t batch, int64
   return run_host(h, batch, ops, fn);
 }
 
+// schur_sylvester / sylvester_solve, lyapunov_solve (trsyl.hip). info = NULL: a singular member is an error, which does not stop the other
+// chunks: every chunk runs and comes back, the lowest singular member is reported at the end. B = NULL (dgesyl only): the Lyapunov form
+namespace {
+using SylRun = std::function<int(nd4hip_handle*, int64_t nb, const double* A, const double* B, const double* C, double* X, int32_t* info,
+                                 int64_t* bad)>;
+int syl_host(nd4hip_handle* h, const char* what, int64_t batch, int64_t M, int64_t N, const double* A, const double* B, const double* C,
+             double* X, int32_t* info, const SylRun& run) {
+  std::vector<Operand> ops{in_op(A, M * M, M * M), in_op(C, M * N, M * N), out_op(X, M * N)};
+  const int ib = B ? (int)ops.size() : -1;
+  if (B) ops.push_back(in_op(B, N * N, N * N));
+  const int ii = info ? (int)ops.size() : -1;
+  if (info) ops.push_back(out_op(info, 1, 4));
+  std::atomic<int64_t> worst(INT64_MAX);
+  ChunkFn fn = [=, &worst, &run](nd4hip_handle* hd, int, int64_t nb, void* const* p) {
+    int64_t bad = INT64_MAX;
+    const int rc = run(hd, nb, P(p, 0), ib >= 0 ? P(p, ib) : nullptr, P(p, 1), P(p, 2), ii >= 0 ? static_cast<int32_t*>(p[ii]) : nullptr, &bad);
+    if (rc != ND4HIP_ERR_SINGULAR) return rc;
+    for (int64_t seen = worst.load(); bad < seen && !worst.compare_exchange_weak(seen, bad);) {}
+    return 0;
+  };
+  ND4_TRY(run_host(h, batch, ops, fn));
+  if (worst.load() != INT64_MAX) {
+    nd4_set_error("%s: the equation is singular. (matrix %lld)", what, (long long)worst.load());
+    return ND4HIP_ERR_SINGULAR;
+  }
+  return 0;
+}
+}  // namespace
+extern "C" int nd4hip_dtrsyl_batched_host(nd4hip_handle* h, int trans_b, int64_t batch, int64_t M, int64_t N, const double* TA, const double* TB,
+                                          const double* C, double* X, int32_t* info) {
+  ND4_ARGS(nd4_args_syl("dtrsyl_batched", batch, M, N, TA, TB, false, C, X));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dtrsyl_batched: NULL handle");
+  return syl_host(h, "schur_sylvester(TA,TB,C)", batch, M, N, TA, TB, C, X, info,
+                  [=](nd4hip_handle* hd, int64_t nb, const double* a, const double* b, const double* c, double* x, int32_t* f, int64_t* bad) {
+                    return nd4_trsyl_run(hd, trans_b, nb, M, N, a, b, c, x, f, g_chunk_first, bad);
+                  });
+}
+extern "C" int nd4hip_dgesyl_batched_host(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, const double* B, const double* C,
+                                          double* X, int32_t* info) {
+  ND4_ARGS(nd4_args_syl("dgesyl_batched", batch, M, N, A, B, true, C, X));
+  ND4_CHECK_ARG(h != nullptr, "nd4hip_dgesyl_batched: NULL handle");
+  return syl_host(h, B ? "sylvester_solve(A,B,C)" : "lyapunov_solve(A,Q)", batch, M, N, A, B, C, X, info,
+                  [=](nd4hip_handle* hd, int64_t nb, const double* a, const double* b, const double* c, double* x, int32_t* f, int64_t* bad) {
+                    return nd4_gesyl_run(hd, nb, M, N, a, b, c, x, f, g_chunk_first, bad);
+                  });
+}
+
 // zqr_factor / zqr_apply_q / zqr_decomp / zqr_lstsq (zgeqrf.hip). zgels: tau = NULL: A is the matrix; info = NULL: a rank-deficient member is
 // an error, which does not stop the other chunks: every chunk runs and comes back, the lowest such member is reported at the end
 extern "C" int nd4hip_zgeqrf_batched_host(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, double* F, double* tau) {

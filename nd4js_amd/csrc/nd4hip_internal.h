@@ -183,6 +183,19 @@ int nd4_trtri(nd4hip_handle* h, bool upper, int64_t batch, int64_t N, const doub
 int nd4_potri(nd4hip_handle* h, int64_t batch, int64_t N, const double* L, double* X);
 // inv's entry point with member0, shared by the _dev and _host forms (nd4hip_api.hip)
 int nd4_getri_run(nd4hip_handle* h, int64_t batch, int64_t N, const double* A, double* X, int32_t* info, int64_t member0, int64_t* first_bad);
+// Sylvester equations (trsyl.hip): arguments already checked, batch >= 1, 1 <= M, N <= 2048. nd4_trsyl: TA Y + Y op(TB)
+// = C; nd4_gesyl: A X + X B = C, B = NULL (M == N): A X + X A^T = C. info (device int32 [batch]) receives a nonzero word per singular
+// member and nd4_trsyl only enqueues; info = NULL: one flag word per pass is read back and a flagged member is ND4HIP_ERR_SINGULAR with
+// the lowest such member counted from member0 (also in *first_bad, may be NULL). The _run forms are the entry points with member0,
+// shared by the _dev and _host forms (nd4hip_api.hip)
+int nd4_trsyl(nd4hip_handle* h, bool trans_b, int64_t batch, int64_t M, int64_t N, const double* TA, const double* TB, const double* C, double* X,
+              int32_t* info, int64_t member0, int64_t* first_bad);
+int nd4_gesyl(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, const double* B, const double* C, double* X,
+              int32_t* info, int64_t member0, int64_t* first_bad);
+int nd4_trsyl_run(nd4hip_handle* h, int trans_b, int64_t batch, int64_t M, int64_t N, const double* TA, const double* TB, const double* C,
+                  double* X, int32_t* info, int64_t member0, int64_t* first_bad);
+int nd4_gesyl_run(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A, const double* B, const double* C, double* X,
+                  int32_t* info, int64_t member0, int64_t* first_bad);
 int nd4_gesvdj(nd4hip_handle* h, int64_t batch, int64_t M, int64_t N, const double* A,
                double* U, double* sv, double* V, int* sweeps_out, double* offnorm_out);
 // the exact power-of-two scaling of the SVD entries (svd.hip): max|a| per member, dst = 2^-e src, sv *= 2^e

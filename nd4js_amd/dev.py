@@ -1275,6 +1275,47 @@ def cholesky_inv(L):
     return _inv_dev(L, "L", "cholesky_inv(L)", lambda h, b, N, a, x: h.lib.nd4hip_dpotri_batched_dev(h.ptr, b, N, a, x))
 
 
+def _syl_dev(mats, names, what, info, call):
+    """X [..., M, N] from call(handle, members, M, N, A, B, C, X, info), with la's checks and texts; the leading dimensions broadcast"""
+    from .la import _inv_dtype, _syl_shapes
+    for m, name in zip(mats, names):
+        if isinstance(m, torch.Tensor):
+            _inv_dtype(name, what, m.is_complex(), m.dtype == torch.float64, m.dtype)
+        if not (isinstance(m, torch.Tensor) and m.is_cuda and m.device == mats[0].device):
+            raise TypeError("%s: %s must be a float64 CUDA tensor on one device" % (what, name))
+    lead, M, N = _syl_shapes(tuple(mats[0].shape), tuple(mats[1].shape), tuple(mats[2].shape), names, what)
+    A, B, C = (m.expand(lead + tuple(m.shape[-2:])).contiguous() for m in mats)
+    X = torch.empty(lead + (M, N), dtype=torch.float64, device=C.device)
+    flags = torch.zeros(lead, dtype=torch.int32, device=C.device) if info is not None else None
+    if X.numel():
+        h = _h(C)
+        _lib.check(call(h, _batch(lead), M, N, _p(A), _p(B), _p(C), _p(X), _p(flags) if flags is not None else None))
+    if info is not None:
+        info["singular"] = flags
+    return X
+
+
+def schur_sylvester(TA, TB, C, trans_b=False, info=None):
+    """device-resident la.schur_sylvester: Y with TA Y + Y TB = C (trans_b: TA Y + Y TB^T = C), the same bits; no operand is written, no
+    scaling against overflow. The block structure is not checked here (that would be a round trip): two nonzero subdiagonal entries in
+    a row give an undefined result. With info (a dict) the call is only enqueued and info["singular"] receives an int32 tensor [...];
+    without it a singular member raises as in la (one flag word is read back)."""
+    return _syl_dev((TA, TB, C), ("TA", "TB", "C"), "schur_sylvester(TA,TB,C)", info,
+                    lambda h, b, M, N, ta, tb, c, x, f: h.lib.nd4hip_dtrsyl_batched_dev(h.ptr, int(bool(trans_b)), b, M, N, ta, tb, c, x, f))
+
+
+def sylvester_solve(A, B, C, info=None):
+    """device-resident la.sylvester_solve: X with A X + X B = C, the same bits; no operand is written. Synchronises (schur_decomp's flags)."""
+    return _syl_dev((A, B, C), ("A", "B", "C"), "sylvester_solve(A,B,C)", info,
+                    lambda h, b, M, N, a, bb, c, x, f: h.lib.nd4hip_dgesyl_batched_dev(h.ptr, b, M, N, a, bb, c, x, f))
+
+
+def lyapunov_solve(A, Q, info=None):
+    """device-resident la.lyapunov_solve: X with A X + X A^T = Q, the same bits; not symmetrised. Synchronises (schur_decomp's flags)."""
+    return _syl_dev((A, A, Q), ("A", "A", "Q"), "lyapunov_solve(A,Q)", info,
+                    lambda h, b, M, N, a, bb, c, x, f: h.lib.nd4hip_dgesyl_batched_dev(h.ptr, b, M, N, a, None, c, x, f))
+
+
 def zqr_factor(A):
     """device-resident la.zqr_factor: (F complex128 [..., M, N], tau complex128 [..., N]) of the complex128 A, the same bits; A is not
     written. Only enqueued."""

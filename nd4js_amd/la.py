@@ -34,6 +34,8 @@ JS wrapper nd4js_amd/js/index.js over the N-API shim; both call the same libnd4h
                                    -> nd4hip_zgetrf_batched_host, nd4hip_zgetrs_batched_host, nd4hip_zgesv_batched_host (csrc/zgetrf.hip)
   inv(A, info), tril_inv(L), triu_inv(U), cholesky_inv(L)   float64, not in the reference
                                    -> nd4hip_dgetri_batched_host, nd4hip_dtrtri_batched_host, nd4hip_dpotri_batched_host (csrc/getri.hip)
+  schur_sylvester(TA, TB, C, trans_b, info), sylvester_solve(A, B, C, info), lyapunov_solve(A, Q, info)   float64, not in the reference
+                                   -> nd4hip_dtrsyl_batched_host, nd4hip_dgesyl_batched_host (csrc/trsyl.hip)
   tridiag_eigen(d, e), tridiag_eigenvals(d, e), tridiag_count(d, e, x)   not in the reference   -> nd4hip_dstevx_batched_host, nd4hip_dstcnt_batched_host
                                    interval=(lo, hi) (opt-in, here and in eigen_sym): the eigenvalues in (lo, hi] -> nd4hip_dstevxv_batched_host,
                                    nd4hip_dsyevxv_batched_host, nd4hip_dsyevxv_tr_batched_host
@@ -1880,6 +1882,71 @@ def cholesky_inv(L, device=None):
     triangles of the result are written with identical bits. Faster than cholesky_solve(L, I) only for stacks of tiny members; about
     equal for stacks of 32^2 - 64^2 and 64 x 512^2, 2.6 x its time at 256 x 128^2 and 4 - 7 x for one 512^2 - 2048^2 matrix."""
     return _inv_host(L, "L", "cholesky_inv(L)", device, lambda h, b, N, a, x: h.lib.nd4hip_dpotri_batched_host(h.ptr, b, N, a, x))
+
+
+def _syl_shapes(sa, sb, sc, names, what):
+    """(lead, M, N) of A [..., M, M], B [..., N, N], C [..., M, N] with broadcast leading dimensions, 1 <= M, N <= 2048; shared with dev.py"""
+    M, N = _hegv_square(tuple(sa), names[0], what), _hegv_square(tuple(sb), names[1], what)
+    if M < 1 or N < 1:
+        raise ValueError("%s: M, N >= 1." % what)
+    if len(sc) < 2 or tuple(sc[-2:]) != (M, N):
+        raise ValueError("%s: %s must be [..., %d, %d]." % (what, names[2], M, N))
+    try:
+        lead = np.broadcast_shapes(tuple(sa[:-2]), tuple(sb[:-2]), tuple(sc[:-2]))
+    except ValueError:
+        raise ValueError("Shapes are not broadcast-compatible.") from None
+    return tuple(int(x) for x in lead), M, N
+
+
+def _syl_host(mats, names, what, info, device, call, quasi=False):
+    """X float64 [..., M, N] from call(handle, members, M, N, A, B, C, X, info); the checks come first, and nothing is launched for an
+    empty stack"""
+    mats = [np.asarray(m) for m in mats]
+    for m, name in zip(mats, names):
+        _inv_dtype(name, what, m.dtype.kind == "c", m.dtype == np.float64, m.dtype)
+    lead, M, N = _syl_shapes(mats[0].shape, mats[1].shape, mats[2].shape, names, what)
+    if quasi:
+        for m, name in zip(mats[:2], names):
+            sub = np.diagonal(m, -1, -2, -1) != 0
+            if np.any(sub[..., 1:] & sub[..., :-1]):
+                raise ValueError("%s: %s is not quasi-triangular (two nonzero subdiagonal entries in a row)." % (what, name))
+    A, B, C = (np.ascontiguousarray(np.broadcast_to(m, lead + m.shape[-2:])) for m in mats)
+    X = np.empty(lead + (M, N), dtype=np.float64)
+    flags = np.zeros(lead, dtype=np.int32)
+    if X.size:
+        h = _lib.handle(device)
+        _lib.check(call(h, int(np.prod(lead, dtype=np.int64)), M, N, _ptr(A), _ptr(B), _ptr(C), _ptr(X), _ptr(flags) if info is not None else None))
+    if info is not None:
+        info["singular"] = flags
+    return X
+
+
+def schur_sylvester(TA, TB, C, trans_b=False, info=None, device=None):
+    """Y float64 [..., M, N] with TA Y + Y TB = C, or TA Y + Y TB^T = C with trans_b: the triangular stage of Bartels-Stewart (LAPACK's
+    trsyl; csrc/trsyl.hip), M, N <= 2048, leading dimensions broadcast. TA [..., M, M] and TB [..., N, N] are upper quasi-triangular as
+    schur_decomp returns them: a nonzero T[i+1, i] marks a 2x2 block, nothing below the first subdiagonal is read; two nonzero
+    subdiagonal entries in a row raise ValueError. There is NO scaling against overflow (LAPACK's scale output is always 1 here). A
+    member whose TA and -TB share an eigenvalue (a zero or non-finite pivot under complete pivoting) raises Nd4HipError with code -5,
+    'schur_sylvester(TA,TB,C): the equation is singular. (matrix <b>)', b the lowest such member. With info (a dict) nothing raises:
+    info["singular"] receives int32 [...], nonzero for such a member, whose Y is all NaN; every other member has the bits it has alone."""
+    return _syl_host((TA, TB, C), ("TA", "TB", "C"), "schur_sylvester(TA,TB,C)", info, device,
+                     lambda h, b, M, N, ta, tb, c, x, f: h.lib.nd4hip_dtrsyl_batched_host(h.ptr, int(bool(trans_b)), b, M, N, ta, tb, c, x, f),
+                     quasi=True)
+
+
+def sylvester_solve(A, B, C, info=None, device=None):
+    """X float64 [..., M, N] with A X + X B = C by Bartels-Stewart on the device without a round trip: schur_decomp of A [..., M, M] and
+    of B [..., N, N], F = QA^T C QB, schur_sylvester, X = QA Y QB^T; M, N <= 2048, leading dimensions broadcast. Singular equations
+    (A and -B share an eigenvalue) and info as in schur_sylvester, the text names sylvester_solve(A,B,C). No scaling against overflow."""
+    return _syl_host((A, B, C), ("A", "B", "C"), "sylvester_solve(A,B,C)", info, device,
+                     lambda h, b, M, N, a, bb, c, x, f: h.lib.nd4hip_dgesyl_batched_host(h.ptr, b, M, N, a, bb, c, x, f))
+
+
+def lyapunov_solve(A, Q, info=None, device=None):
+    """X float64 [..., N, N] with A X + X A^T = Q from one schur_decomp of A and the transposed form of schur_sylvester. For a symmetric
+    Q, X is symmetric within rounding; it is not symmetrised. Singular equations and info as in sylvester_solve."""
+    return _syl_host((A, A, Q), ("A", "A", "Q"), "lyapunov_solve(A,Q)", info, device,
+                     lambda h, b, M, N, a, bb, c, x, f: h.lib.nd4hip_dgesyl_batched_host(h.ptr, b, M, N, a, None, c, x, f))
 
 
 def _zqr_shape(shape, name, what):
